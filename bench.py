@@ -15,9 +15,18 @@ itself — each with the bytes its busiest rank receives and the fraction of the
 `replicas` carries the weak-scaling mode (every rank encodes its own independent stripe, no collective).  A single-process run that sees several GPUs additionally times the
 C-ABI form (fastecc_create_sharded: peer copies instead of RCCL) in a child process.
 
-At N = 1 the line additionally carries `other_paths`: short, checked timings of the rows around the headline path (few-loss repair
-and a 2 % loss pattern, a code with 4 parity blocks, a mixed-radix order) and BASELINE configs[4] (the 64-bit field, 32 + 32 GiB),
-measured in a child process — so that the driver's record holds them too; none of it enters `value` (--no-other-paths skips it).
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.  With --full the line also carries what is
+measured or checked besides `value`: a second, instrumented pass with HIP events around every kernel (`roofline`,
+`ms_per_step_instrumented`), the golden-hash gate (`parity_check`), the CPU baseline (`cpu_baseline`), at N = 1 the one-stripe modes
+(`one_stripe`) and the C-ABI form on several visible GPUs, and `other_paths`: short, checked timings of the rows around the headline
+path (few-loss repair and a 2 % loss pattern, a code with 4 parity blocks, a mixed-radix order) and BASELINE configs[4] (the 64-bit
+field, 32 + 32 GiB), measured in a child process; none of it enters `value` (--no-other-paths skips other_paths).  At N > 1 `value`
+is the one-stripe all-to-all mode, so the one-stripe modes run in a plain run too.
+
+--dump-outputs DIR writes the parity of the last timed step as DIR/parity.npy (float64, exact for the field's words): the whole
+parity when it fits in 32 MB, else a fixed, seeded sample of its words, whose indices go to DIR/parity_index.npy.  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.  At N > 1 the file holds rank 0's parity from
+the replica pass (its own stripe, the timed region every rank runs first), not the one-stripe all-to-all mode that gives `value` there.
 
 Throughput convention = the reference's (RS.cpp:38): bytes = data + parity = 2*k*block_bytes per encode,
 reported in GB/s (1e9).  Prints ONE JSON line on rank 0.
@@ -137,6 +146,9 @@ def parse():
     ap.add_argument("--cabi-sharded-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--other-paths-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--slabs", type=int, default=0, help="column slabs on internal streams (0 = library default)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what is not the headline figure (instrumented pass, roofline, "
+                                                         "parity gate, CPU baseline, one-stripe modes at N = 1, other_paths); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the parity of the last timed step to DIR/*.npy (float64); at N > 1 rank 0's replica-pass parity")
     ap.add_argument("--option", action="append", default=[], help="library tuning option name=value (fastecc_set_option)")
     return ap.parse_args()
 
@@ -275,6 +287,40 @@ def oracle_columns(data, got, k, S, rows_out, which, cols=(0, -1)):
     want = which(orc, x)
     have = got.view(rows_out, S)[:, idx].cpu().numpy().view(np.uint32)
     return "ok" if want.shape == have.shape and np.array_equal(want, have) else "FAILED"
+
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: float64 bytes written at most (parity.npy); a larger parity is sampled
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(dirname, parity, block_bytes, p61):
+    """--dump-outputs: what the timed path hands its caller, the parity of the last step, as float64 (exact: the 32-bit field's words are < 2^32;
+    a 64-bit field word is split into its low and high 32-bit halves along a last axis of 2).  Whole when it fits in DUMP_BYTES, shaped [blocks,
+    words]; else the words at a fixed, seeded set of indices into the flat parity (parity_index.npy), in index order."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    halves = 2 if p61 else 1
+    flat = parity.view(-1)
+    n = flat.numel()
+    if n * halves * 8 <= DUMP_BYTES:
+        idx, words = None, flat
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_BYTES // (8 * halves)))
+        words = flat[torch.from_numpy(idx).to(flat.device)]
+    host = words.cpu().numpy()
+    if p61:
+        u = host.view(np.uint64)
+        out = np.stack([u & np.uint64(0xFFFFFFFF), u >> np.uint64(32)], axis=-1).astype(np.float64)
+    else:
+        out = host.view(np.uint32).astype(np.float64)
+    if idx is None:
+        out = out.reshape((-1, block_bytes // parity.element_size()) + out.shape[1:])
+    np.save(os.path.join(dirname, "parity.npy"), out)
+    rec = {"dir": dirname, "parity": list(out.shape), "sampled": idx is not None}
+    if idx is not None:
+        np.save(os.path.join(dirname, "parity_index.npy"), idx.astype(np.float64))
+        rec["sample"] = "%d of %d words, seed 0x%x" % (idx.size, n, DUMP_SEED)
+    return rec
 
 
 def other_paths(fastecc_amd, enc, data, parity, log2k, block_bytes, device, stream):
@@ -907,19 +953,22 @@ def main():
     for _ in range(args.warmup):
         step()
     elapsed = max_over_ranks(time_steps(step, args.steps, barrier))
-    # ---- a second, instrumented pass of K steps: HIP events around every kernel, on the stream the kernels run on ----
-    enc.profile(True)
-    enc.profile_reset()
-    elapsed_prof = max_over_ranks(time_steps(step, args.steps, barrier))
-    kernels = enc.profile_read()
-    enc.profile(False)
+    dumped = dump_outputs(args.dump_outputs, parity, args.block_bytes, p61) if args.dump_outputs and rank == 0 else None
+    # ---- --full: a second, instrumented pass of K steps: HIP events around every kernel, on the stream the kernels run on ----
+    kernels, elapsed_prof = {}, None
+    if args.full:
+        enc.profile(True)
+        enc.profile_reset()
+        elapsed_prof = max_over_ranks(time_steps(step, args.steps, barrier))
+        kernels = enc.profile_read()
+        enc.profile(False)
 
     # ---- everything the line needs from the replica measurement, before anything that could stall ----
     roof = check = None
     if rank == 0:
         bytes_per_encode = float(k + m_blocks) * args.block_bytes * args.batch  # data + parity, RS.cpp:38
         ms_per_step = elapsed / args.steps * 1e3
-        ms_per_step_prof = elapsed_prof / args.steps * 1e3
+        ms_per_step_prof = None if elapsed_prof is None else elapsed_prof / args.steps * 1e3
         value = world * bytes_per_encode / (ms_per_step * 1e-3) / 1e9
         # dominant kernel by total time; a launch reads its part of the stripe once and writes it once (the
         # library reports those algorithmic bytes per launch: the whole stripe, or one column slab of it)
@@ -983,7 +1032,7 @@ def main():
                              "issue_floor_frac": None if not pmc else pmc["encode"]["valu_floor_frac"]},
                     "per_kernel_avg_ms": {kn: round(v[0] / v[1], 4) for kn, v in sorted(kernels.items())},
                     "launches_per_step": {kn: v[1] // args.steps for kn, v in sorted(kernels.items())}}
-        if not args.no_parity_check and args.batch == 1 and m_blocks == k:
+        if args.full and not args.no_parity_check and args.batch == 1 and m_blocks == k:
             try:
                 check = parity_check_p61(data, parity, k, args.block_bytes) if p61 else parity_check(enc, args.log2k, args.block_bytes, device)
             except Exception as e:  # noqa: BLE001
@@ -1059,7 +1108,7 @@ def main():
             "value": round(v, 2), "value_kind": kind,
             "complete": kind != "replicas_fallback" and (one or {}).get("complete", True) is not False,
             "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms, 4), "ms_per_step_instrumented": round(ms_per_step_prof, 4),
+            "ms_per_step": round(ms, 4), "ms_per_step_instrumented": None if ms_per_step_prof is None else round(ms_per_step_prof, 4),
             "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
             "dtype": "u64" if p61 else "u32", "data": "synthetic",
             "config": {"workload": workload, "stripes_per_step": args.batch, "plan": enc.plan(), "parallelism": par},
@@ -1082,6 +1131,9 @@ def main():
             "one_stripe": one,
             "devices": devices, "distributed": dist_info,
         }
+        line["full"] = args.full
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if _ACTIVE_TEST_HOOKS:
             line["test_hooks_active"] = {v: os.environ[v] for v in _ACTIVE_TEST_HOOKS}
         if other_paths_result:
@@ -1139,7 +1191,8 @@ def main():
     one = None
     unit = 8 if p61 else 4  # bytes per tensor word
     words = args.block_bytes // unit
-    shardable = (not args.no_sharded and args.batch == 1 and m_blocks == k and words % world == 0 and (not p61 or world > 1)
+    # (at N = 1 these modes are not the headline: --full)
+    shardable = ((args.full or world > 1) and not args.no_sharded and args.batch == 1 and m_blocks == k and words % world == 0 and (not p61 or world > 1)
                  and (args.block_bytes // world) % (16 if p61 else 4) == 0 and k % world == 0)
     if shardable:
         try:
@@ -1154,7 +1207,7 @@ def main():
 
     cabi = cpu = None
     if rank == 0:
-        if (world == 1 and torch.cuda.device_count() > 1 and not args.no_sharded and not p61 and args.batch == 1 and m_blocks == k
+        if (args.full and world == 1 and torch.cuda.device_count() > 1 and not args.no_sharded and not p61 and args.batch == 1 and m_blocks == k
                 and not os.environ.get("FASTECC_BENCH_NO_CABI_SHARDED")):
             # the single-process form of configs[3] on every visible GPU, in a child (its own HIP contexts; a failure
             # or a hang costs this entry, not the line)
@@ -1182,12 +1235,12 @@ def main():
                 cabi["incomplete"] = "child timed out after these measurements"
             except Exception as e:  # noqa: BLE001
                 cabi = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 cpu = (cpu_baseline_p61 if p61 else cpu_baseline)(args.cpu_log2k or args.log2k, args.block_bytes)
             except Exception as e:  # the baseline is a report, never a reason to lose the GPU number
                 cpu = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_other_paths and not p61 and args.batch == 1 and m_blocks == k and not args.plan and not args.option:
+    if args.full and rank == 0 and world == 1 and not args.no_other_paths and not p61 and args.batch == 1 and m_blocks == k and not args.plan and not args.option:
         # in a child process: a fault in one of these paths must not cost the line its headline number
         import subprocess
         cmd = [sys.executable, os.path.abspath(__file__), "--other-paths-child", "--log2k", str(args.log2k), "--block-bytes", str(args.block_bytes)]

@@ -30,7 +30,7 @@ def _bench(world, fault=None, mode_timeout=120, log2k=12, extra=()):
         env["FASTECC_BENCH_TEST_STALL"] = fault
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--log2k", str(log2k), "--mode-timeout", str(mode_timeout), "--sharded-timeout", "400", *extra]
+           "--log2k", str(log2k), "--mode-timeout", str(mode_timeout), "--sharded-timeout", "400", "--full", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, "bench.py must print exactly one JSON line (rc %d)\n%s\n%s" % (r.returncode, r.stdout[-2000:], r.stderr[-2000:])

@@ -27,7 +27,7 @@ def _run(extra):
     env = dict(os.environ, FASTECC_BENCH_TEST_ONE_RANK_GROUP="1", FASTECC_SHARDING_FORCE_COLLECTIVES="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     env.pop("FASTECC_BENCH_BACKEND", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-other-paths",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-other-paths",
                         "--startup-timeout", "120"] + extra, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and lines, (r.stdout[-1500:], r.stderr[-3000:])

@@ -160,6 +160,18 @@ def test_large_orders_linearity_and_sampled_columns(torch_cuda, fe, oracle):
         torch.cuda.empty_cache()
 
 
+def flag_code(oracle, x, m, order):
+    """The parity of FASTECC_CODE_MIXED_RADIX: the first m parity blocks of the order's code; with q = 1 (a power-of-two order) the flag's
+    code IS fastecc_create's (include/fastecc.h): every 2^fold-th parity block of the zero-extended (2N,N) code, fold = min(log2 N - ceil(log2 m), 4)."""
+    k, S = x.shape
+    if order & (order - 1):
+        return oracle.encode_mixed_code(x, k + m, order)
+    fold = min(order.bit_length() - 1 - (m - 1).bit_length(), 4)
+    padded = np.zeros((order, S), dtype=np.uint32)
+    padded[:k] = x
+    return oracle.encode_fast(padded)[:: 1 << fold][:m]
+
+
 def erase_and_check(torch, fe, enc, x, par, lost_data, lost_parity, repair):
     """Overwrite the lost blocks with garbage, decode (or repair) on the device, compare with the originals."""
     k, S = x.shape
@@ -224,9 +236,7 @@ def test_decoder_of_zero_extended_mixed_codes(torch_cuda, fe, k, m):
     as lost), so exactly m losses among the k + m blocks are repaired."""
     torch = torch_cuda
     S = 24
-    order = fe.mixed_radix_order(k)
-    if not order & (order - 1):
-        pytest.skip("a power of two: the ordinary code, tests/test_gpu_decode.py")
+    order = fe.mixed_radix_order(k)  # (k = 1000: order 1024, q = 1 — the flag's code on a power-of-two order is the ordinary one)
     rng = np.random.default_rng(k * 7 + m)
     x = rand_stripe(k + m, k, S)
     with fe.Encoder(k + m, k, 4 * S, flags=fe.CODE_MIXED_RADIX) as enc:
@@ -376,14 +386,12 @@ def test_few_parity_blocks_of_mixed_radix_codes(torch_cuda, fe, oracle, k):
     pipeline (encode_direct_max = 0) and the oracle."""
     torch = torch_cuda
     S = 12
-    order = fe.mixed_radix_order(k)
-    if not order & (order - 1):
-        pytest.skip("a power of two: tests/test_gpu_general.py")
+    order = fe.mixed_radix_order(k)  # (k = 1000: order 1024, q = 1 — the ordinary code)
     x = rand_stripe(k, k, S)
     for m in (1, 3, 8):
         if m > order:
             continue
-        want = oracle.encode_mixed_code(x, k + m, order)
+        want = flag_code(oracle, x, m, order)
         with fe.Encoder(k + m, k, 4 * S, flags=fe.CODE_MIXED_RADIX) as enc:
             for direct_max in (8, 0):
                 enc.set_option("encode_direct_max", direct_max)

@@ -73,8 +73,6 @@ def test_golden_vectors(torch_cuda, fe):
 @pytest.mark.parametrize("elems", [1, 3, 64, 100])
 def test_encode_matches_oracle(torch_cuda, fe, orc61, logn, elems):
     N = 1 << logn
-    if N * elems > (1 << 17):
-        pytest.skip("oracle time")
     x = rand_stripe(np.random.default_rng(1000 * logn + elems), N, elems)
     want = orc61.encode(x)
     with encoder(fe, N, elems) as enc:

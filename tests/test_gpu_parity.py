@@ -138,8 +138,6 @@ def test_encode_golden_vectors(torch_cuda, fe, golden_vectors):
 def test_encode_matches_oracle(torch_cuda, fe, oracle, log2n, S):
     torch = torch_cuda
     N = 1 << log2n
-    if N * S > (1 << 22):
-        pytest.skip("kept for the golden-hash test")
     x = rand_stripe(np.random.default_rng(1000 * log2n + S), N, S)
     d = to_dev(torch, x)
     with fe.Encoder(2 * N, N, 4 * S) as enc:
@@ -454,33 +452,27 @@ def test_blocks_too_large_for_tile_offsets_fall_back(torch_cuda, fe, oracle):
 
 
 # ------------------------------------------------------------------------------------------------
-# directly against the unmodified reference (prebuilt oracle/_ref travels to the GPU box)
+# directly against the unmodified reference (its results recorded in tests/golden/golden_reference.json)
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("log2n,S,avx2", [(7, 1024, False), (12, 513, True), (15, 1024, True), (16, 256, False)])
-def test_encode_equals_unmodified_reference(torch_cuda, fe, log2n, S, avx2):
+def test_encode_equals_unmodified_reference(torch_cuda, fe, reference, log2n, S, avx2):
     """HIP encode vs FastECC's own code (RS.cpp:41-63 call sequence on MFA_NTT, scalar and AVX2 builds)."""
-    from oracle import Reference
-    if not Reference.available(avx2):
-        pytest.skip("oracle/_ref not prebuilt")
     torch = torch_cuda
-    ref = Reference(avx2)
+    ref = reference.variant(avx2)
     N = 1 << log2n
     x = rand_stripe(np.random.default_rng(log2n + S), N, S)
     d = to_dev(torch, x)
     with fe.Encoder(2 * N, N, 4 * S) as enc:
         enc.encode(d)
         torch.cuda.synchronize()
-    assert np.array_equal(to_host(d), ref.encode(x))
+    assert ref.agrees(to_host(d).reshape(N, S), ref.encode(x))
 
 
 @pytest.mark.parametrize("log2n,S", [(8, 1024), (13, 64)])
-def test_ntt_equals_unmodified_reference(torch_cuda, fe, log2n, S):
+def test_ntt_equals_unmodified_reference(torch_cuda, fe, reference, log2n, S):
     """fastecc_ntt vs MFA_NTT and Rec_NTT of the reference, read back in logical block order."""
-    from oracle import Reference
-    if not Reference.available():
-        pytest.skip("oracle/_ref not prebuilt")
     torch = torch_cuda
-    ref = Reference()
+    ref = reference
     N = 1 << log2n
     x = rand_stripe(np.random.default_rng(log2n), N, S)
     with fe.Encoder(2 * N, N, 4 * S) as enc:
@@ -488,21 +480,16 @@ def test_ntt_equals_unmodified_reference(torch_cuda, fe, log2n, S):
             d = to_dev(torch, x)
             enc.ntt(d, inverse)
             torch.cuda.synchronize()
-            got = to_host(d)
-            assert np.array_equal(got, ref.ntt(x, inverse, Reference.MFA))
-            assert np.array_equal(got, ref.ntt(x, inverse, Reference.REC))
+            got = to_host(d).reshape(N, S)
+            assert ref.agrees(got, ref.ntt(x, inverse, ref.MFA))
+            assert ref.agrees(got, ref.ntt(x, inverse, ref.REC))
 
 
 @pytest.mark.parametrize("order", [2, 4])
-def test_ntt_of_order_2_and_4_equals_the_reference_codelets(torch_cuda, fe, order):
+def test_ntt_of_order_2_and_4_equals_the_reference_codelets(torch_cuda, fe, reference, order):
     """fastecc_ntt at N = 2, 4 against NTT2 / NTT4 (ntt.cpp:16-22, 50-62) themselves, column by column, natural
     order in and out (NTT4's closing swap included), both directions."""
-    from oracle import Reference
-    if not Reference.available():
-        pytest.skip("oracle/_ref not prebuilt")
-    ref = Reference()
-    if not hasattr(ref.lib, "ref_small_ntt") or ref.lib.ref_small_ntt(np.zeros(4, np.uint32), 4, 0) != 0:
-        pytest.skip("oracle/_ref predates the order-2 / order-4 entries of ref_small_ntt")
+    ref = reference
     torch = torch_cuda
     for S in (1, 33, 1024):
         x = rand_stripe(np.random.default_rng(100 * order + S), order, S)
@@ -512,8 +499,8 @@ def test_ntt_of_order_2_and_4_equals_the_reference_codelets(torch_cuda, fe, orde
                 d = to_dev(torch, x)
                 enc.ntt(d, inverse)
                 torch.cuda.synchronize()
-                want = np.stack([ref.small_ntt(x[:, c], inverse) for c in range(S)], axis=1)
-                assert np.array_equal(to_host(d), want), (order, S, inverse)
+                want = ref.small_ntt_columns(x, inverse)
+                assert ref.agrees(to_host(d).reshape(order, S), want), (order, S, inverse)
 
 
 def test_check_range_counts_non_field_words(torch_cuda, fe):

@@ -7,7 +7,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 timeout 120 fastecc_amd/lib/microbench radix > "$OUT/microbench_radix.jsonl" 2>&1; cat "$OUT/microbench_radix.jsonl"
-timeout 600 python bench.py --field p61 --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_p61.json" 2> "$OUT/bench_p61.err"; echo "p61 rc=$?"; python - "$OUT/bench_p61.json" <<'PY'
+timeout 600 python bench.py --field p61 --steps 5 --warmup 2 --full --no-cpu-baseline > "$OUT/bench_p61.json" 2> "$OUT/bench_p61.err"; echo "p61 rc=$?"; python - "$OUT/bench_p61.json" <<'PY'
 import json, sys
 try:
     r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -10,7 +10,7 @@ timeout 900 python -m pytest tests/test_gpu_bench_multirank.py tests/test_distri
 timeout 900 bash tools/prof_pmc.sh 0 "$OUT/pmc_default" > "$OUT/pmc_default.txt" 2>&1; tail -70 "$OUT/pmc_default.txt"
 # kernel durations of the same command, un-instrumented by counters (for the effective clock: GRBM cycles of the PMC pass / its own duration is not available)
 timeout 600 bash tools/prof_stats.sh "$OUT/stats" > "$OUT/stats.txt" 2>&1; grep -E "fastecc" "$OUT/stats.txt" | head -4 | cut -c1-220
-timeout 900 python bench.py > "$OUT/bench_n1_default.json" 2> "$OUT/bench_n1_default.err"; echo "bench rc=$?"; cut -c1-600 "$OUT/bench_n1_default.json"
+timeout 900 python bench.py --full > "$OUT/bench_n1_default.json" 2> "$OUT/bench_n1_default.err"; echo "bench rc=$?"; cut -c1-600 "$OUT/bench_n1_default.json"
 # direct MFMA kernel: counters per output count (separate processes, so the launches are not averaged together)
 for e in 64 128; do
   for grp in "sq1 SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_ACTIVE_INST_VALU" \
@@ -40,5 +40,5 @@ PY
 timeout 300 python tools/bench_direct.py 19 16,64,128 > "$OUT/direct_bench.jsonl" 2> "$OUT/direct.err"; tail -3 "$OUT/direct_bench.jsonl" | cut -c1-300
 # configs[3] geometry: 8 ranks on this one GPU through gloo at the headline size (control flow + hash gate; times are host-staging times)
 FASTECC_BENCH_BACKEND=gloo OMP_NUM_THREADS=2 timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29688 \
-    bench.py --gpus 8 --steps 2 --warmup 1 --mode-timeout 400 --sharded-timeout 1000 > "$OUT/bench_8rank_gloo_one_gpu_control_flow.json" 2> "$OUT/bench_8rank.err"
+    bench.py --gpus 8 --steps 2 --warmup 1 --full --mode-timeout 400 --sharded-timeout 1000 > "$OUT/bench_8rank_gloo_one_gpu_control_flow.json" 2> "$OUT/bench_8rank.err"
 echo "bench 8 ranks rc=$?"; cut -c1-400 "$OUT/bench_8rank_gloo_one_gpu_control_flow.json"; tail -3 "$OUT/bench_8rank.err"

@@ -13,7 +13,7 @@ cp "$OUT/counters/stamped/"* profiles/r06/ 2>/dev/null
 timeout 2400 python -m pytest tests -m gpu -x -q > "$OUT/pytest_gpu.log" 2>&1; echo "pytest rc=$?" | tee -a "$OUT/pytest_gpu.log"; tail -3 "$OUT/pytest_gpu.log"
 timeout 300 python -c 'import __graft_entry__ as g; g.smoke()' > "$OUT/smoke.log" 2>&1; echo "smoke rc=$?"; tail -1 "$OUT/smoke.log"
 ( tail -3 "$OUT/pytest_gpu.log"; tail -1 "$OUT/smoke.log" ) > "$OUT/profiles/pytest_gpu_summary.txt"
-timeout 900 python bench.py > "$OUT/bench_n1_default.json" 2> "$OUT/bench_n1_default.err"; echo "bench rc=$?"; cut -c1-400 "$OUT/bench_n1_default.json"
+timeout 900 python bench.py --full > "$OUT/bench_n1_default.json" 2> "$OUT/bench_n1_default.err"; echo "bench rc=$?"; cut -c1-400 "$OUT/bench_n1_default.json"
 cp "$OUT/bench_n1_default.json" "$OUT/box.txt" "$OUT/profiles/"
 # 3. the decoder's set-up, traced (cold process; after an encode as in bench.py)
 bash tools/sessions/gpu_r06_prepare_trace.sh > "$OUT/prepare_cold.txt" 2>&1
