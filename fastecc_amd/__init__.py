@@ -23,7 +23,7 @@ CODE_MIXED_RADIX = 1  # fastecc_create_ex flag: transform order q * 2^m, q in {1
 CODE_MIXED_RADIX_PFA = 4  # ... and the composite q = 21, 35, 39, 45, 63, 65, 91, 105, 117 (prime-factor map)
 CODE_TOP_RADIX2 = 2  # fastecc_create_ex flag (A/B experiment): the top level of a power-of-two transform through the fused odd-radix kernel
 
-OK, E_INVAL, E_NOMEM, E_DEVICE, E_UNSUPPORTED = 0, -1, -2, -3, -4
+OK, E_INVAL, E_NOMEM, E_DEVICE, E_UNSUPPORTED, E_UNCORRECTABLE = 0, -1, -2, -3, -4, -5
 
 _LIB = None
 
@@ -96,6 +96,12 @@ def lib():
     L.fastecc_decode_prepare.argtypes, L.fastecc_decode_prepare.restype = [vp, u8p, u8p], i32
     L.fastecc_decode.argtypes, L.fastecc_decode.restype = [vp, vp, vp, i32, vp], i32
     L.fastecc_repair.argtypes, L.fastecc_repair.restype = [vp, vp, vp, i32, vp], i32
+    L.fastecc_verify.argtypes, L.fastecc_verify.restype = [vp, vp, vp, i32, vp, u64, ctypes.POINTER(i32)], i32
+    for name in ("locate_errors", "correct"):
+        f = getattr(L, "fastecc_" + name)
+        f.argtypes, f.restype = [vp, vp, vp, i32, vp, u64, ctypes.POINTER(u64), u64, ctypes.POINTER(u64)], i32
+    L.fastecc_gf_berlekamp_massey.argtypes = [ctypes.POINTER(u32), u32, ctypes.POINTER(u32), u32]
+    L.fastecc_gf_berlekamp_massey.restype = i32
     L.fastecc_pack_blocks.argtypes, L.fastecc_pack_blocks.restype = [vp, vp, vp, i32, vp], i32
     L.fastecc_unpack_blocks.argtypes, L.fastecc_unpack_blocks.restype = [vp, vp, vp, i32, vp, ctypes.POINTER(u64)], i32
     pair = ctypes.POINTER(u64)
@@ -254,6 +260,28 @@ class Encoder:
         _check(lib().fastecc_repair(self._h, _addr(data), _addr(parity), mem, stream or None), "fastecc_repair")
         return data, parity
 
+    def verify(self, data, parity, seed=0, stream=0, mem=MEM_DEVICE):
+        """True iff every word is < p and the k data + n - k parity blocks form a codeword (fingerprints drawn from `seed`)."""
+        ok = ctypes.c_int()
+        _check(lib().fastecc_verify(self._h, _addr(data), _addr(parity), mem, stream or None, seed, ctypes.byref(ok)), "fastecc_verify")
+        return bool(ok.value)
+
+    def _located(self, fn, what, data, parity, seed, stream, mem):
+        cap = self.n - self.k
+        out = (ctypes.c_uint64 * max(cap, 1))()
+        count = ctypes.c_uint64()
+        _check(fn(self._h, _addr(data), _addr(parity), mem, stream or None, seed, out, cap, ctypes.byref(count)), what)
+        return [int(out[i]) for i in range(min(int(count.value), cap))]
+
+    def locate_errors(self, data, parity, seed=0, stream=0, mem=MEM_DEVICE):
+        """Codeword indices (data i -> i, parity j -> k + j) of the corrupted blocks, increasing; [] if consistent.  Reads only.
+        Raises FastEccError with code E_UNCORRECTABLE when they cannot be located."""
+        return self._located(lib().fastecc_locate_errors, "fastecc_locate_errors", data, parity, seed, stream, mem)
+
+    def correct(self, data, parity, seed=0, stream=0, mem=MEM_DEVICE):
+        """locate_errors, then rebuild those blocks in place (replaces the prepared erasure pattern); returns the located blocks."""
+        return self._located(lib().fastecc_correct, "fastecc_correct", data, parity, seed, stream, mem)
+
     def pack_blocks(self, raw, packed, stream=0, mem=MEM_DEVICE):
         """GF.md:72-104: k blocks of block_bytes - 4 arbitrary bytes -> k encodable blocks of block_bytes."""
         _check(lib().fastecc_pack_blocks(self._h, _addr(raw), _addr(packed), mem, stream or None), "fastecc_pack_blocks")
@@ -363,6 +391,16 @@ def gf_mul(x, y): return lib().fastecc_gf_mul(x, y)
 def gf_pow(x, e): return lib().fastecc_gf_pow(x, e)
 def gf_root(order): return lib().fastecc_gf_root(order)
 def gf_inv(x): return lib().fastecc_gf_inv(x)
+
+
+def gf_berlekamp_massey(syndromes, cap=None):
+    """Host-only: the shortest LFSR of `syndromes` over GF(p) as [Lambda_0 = 1, ..., Lambda_L]."""
+    n = len(syndromes)
+    s = (ctypes.c_uint32 * max(n, 1))(*[int(x) % P for x in syndromes])
+    cap = n + 1 if cap is None else cap
+    lam = (ctypes.c_uint32 * max(cap, 1))()
+    L = _check(lib().fastecc_gf_berlekamp_massey(s, n, lam, cap), "fastecc_gf_berlekamp_massey")
+    return [int(lam[i]) for i in range(L + 1)]
 
 
 # GF((2^61-1)^2) scalars, (re, im) tuples

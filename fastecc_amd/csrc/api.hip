@@ -48,6 +48,7 @@ const char* fastecc_strerror(int code)
         case FASTECC_E_NOMEM: return "out of memory";
         case FASTECC_E_DEVICE: return "HIP device or runtime error";
         case FASTECC_E_UNSUPPORTED: return "unsupported field or size";
+        case FASTECC_E_UNCORRECTABLE: return "corrupted blocks could not be located (too many errors)";
         default: return "unknown error";
     }
 }
@@ -161,6 +162,8 @@ void fastecc_destroy(fastecc_ctx* c)
     c->sharded = nullptr;
     destroy_decode_state(c->decoder);
     c->decoder = nullptr;
+    destroy_scrub_state(c->scrub);
+    c->scrub = nullptr;
     DeviceGuard dg(c->device);
     direct_encode_destroy(c->direct_enc);
     c->direct_enc = nullptr;

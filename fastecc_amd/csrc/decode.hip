@@ -1065,6 +1065,9 @@ static int decode_prepare_impl(fastecc_ctx* c, const uint8_t* data_present, cons
     d->sub = false;
     ++d->pattern_serial;  // (the lists of rebuilt rows for FASTECC_MEM_HOST calls are made when such a call comes: decode_impl)
     if (erased_data == 0) {  // no data block to recover
+        // standard_state_kernel's writes of the lost-parity flags are still pending on the null stream: a repair on a non-blocking
+        // stream is not ordered after them (the full path below ends with the same synchronise)
+        if (device_scan) DEC_TRY(hipStreamSynchronize(nullptr));
         d->ready = true;
         return FASTECC_OK;
     }

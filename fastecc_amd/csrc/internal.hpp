@@ -13,6 +13,8 @@ namespace fastecc {
 
 struct DecodeState;                        // decode.hip: tables of one erasure pattern + the size-2k transform context
 void destroy_decode_state(DecodeState*);   // decode.hip, called by fastecc_destroy
+struct ScrubState;                         // scrub.hip: error detection and location (fastecc_verify, _locate_errors, _correct)
+void destroy_scrub_state(ScrubState*);     // scrub.hip, called by fastecc_destroy
 
 // ---- sharded.hip: one stripe in column slabs on several devices (fastecc_create_sharded) ----
 struct Sharded;

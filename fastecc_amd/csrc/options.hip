@@ -98,6 +98,11 @@ int fastecc_set_option(fastecc_ctx* c, const char* name, int value)
         c->decode_direct_max = value;
         return FASTECC_OK;
     }
+    if (!strcmp(name, "locate_max")) {  // fastecc_locate_errors / _correct: most unknown corrupted blocks searched for (host Berlekamp-Massey work)
+        if (value < 0 || value > 4096) return FASTECC_E_INVAL;
+        c->locate_max = value;
+        return FASTECC_OK;
+    }
     if (!strcmp(name, "decode_split")) {  // (2k,k) codes, from the next fastecc_decode_prepare: see context.hpp
         if (value < 0 || value > 2) return FASTECC_E_INVAL;  // 2: the split transform in its block-group form only (A/B against the small form)
         c->decode_split = value;

@@ -1,0 +1,689 @@
+// scrub.hip — error detection and location: fastecc_verify, fastecc_locate_errors, fastecc_correct (include/fastecc.h).
+//
+// The erasure decoder (decode.hip) acts on losses the caller names.  Here the corrupted blocks are found first.  Every code of the
+// library is f (degree < N) on a subset of the NC-th roots of unity, NC = N << e, position u <-> w^u: data block i at i << e, parity at
+// the positions decode.hip's parity_position gives, zero-extended data blocks are known zeros, positions that hold no block are
+// fixed erasures.  With l the locator of the erased positions, p = f * l has degree < N + |erased| (the decoder's identity), so the
+// coefficients of the inverse transform of c[u] l(w^u) (0 at erased positions) above that vanish for a codeword.  For a received word
+// c + e they are S_m = sum_u e_u l(w^u) w^(-um) / NC: power sums in the locators X_u = w^(-u) — the syndromes of classic RS decoding,
+// n - k - b of them with b further erasures.
+//
+// Blocks are long (kilobytes), so the decoding runs on a FINGERPRINT of the codeword: per block j and column c, F_c[j] = sum_w
+// rho_c[w] r_j[w] mod p with small random weights (rho < 2^20, splitmix64 of the seed), R = 3 columns.  F is linear, so the
+// fingerprints of a codeword are a codeword of the same code (of the polynomial sum_w rho_c[w] f_w) and the fingerprints of a corrupted
+// block differ from the clean ones except with probability <= 2^-20 per column.  The pass that reads the codeword once is the only
+// part that scales with the stripe; the rest works on NC x 4 words:
+//   fingerprint_kernel  : one wave per block, dwordx4 loads, v_mad_u64_u32 into 64-bit sums (a product is < 2^52), a per-block
+//                         "word >= p" flag (those blocks are certainly corrupt: known erasures), F written in position order;
+//   syndromes           : F times l(w^u) (the fixed erasures' values, cached per context, times the further erasures' factors),
+//                         the library's stand-alone inverse transform of NC points (transform_bitrev), and a pass that checks
+//                         every coefficient above the degree bound for zero and gathers the first 2 locate_max of each column;
+//   Berlekamp-Massey    : on the host, per column; the longest LFSR is the locator Lambda(x) = prod (1 - X_u x);
+//   root search         : Lambda(w^u) by Horner at every position on the device;
+//   confirmation        : the syndromes once more with the located positions erased must all vanish, in every column.
+// fastecc_correct then hands the located blocks to fastecc_decode_prepare + fastecc_repair.
+#include <algorithm>
+#include <vector>
+
+#include "drivers.hpp"
+
+namespace fastecc {
+
+namespace {
+
+constexpr int R = 3;   // fingerprint columns (the transform stripe has 4 words per position; the 4th stays zero)
+constexpr int RW = 4;  // words per position of the fingerprint stripe
+
+uint64_t splitmix64(uint64_t& s)
+{
+    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// x mod p for any 64-bit x (2^32 = 2^20 - 1 mod p); three folds leave < 2^33 < 3p
+__device__ __forceinline__ uint64_t fold64(uint64_t x)
+{
+    x = (x >> 32) * 0xFFFFFull + (x & 0xFFFFFFFFull);
+    x = (x >> 32) * 0xFFFFFull + (x & 0xFFFFFFFFull);
+    x = (x >> 32) * 0xFFFFFull + (x & 0xFFFFFFFFull);
+    return x;
+}
+__device__ __forceinline__ uint32_t reduce64(uint64_t x)
+{
+    x = fold64(x);
+    if (x >= gf::P) x -= gf::P;
+    if (x >= gf::P) x -= gf::P;
+    return (uint32_t)x;
+}
+
+__device__ __forceinline__ void mad3(uint64_t& a0, uint64_t& a1, uint64_t& a2, uint32_t v, uint32_t wx, uint32_t wy)
+{
+    // packed weights of one word: wx = rho0 | (rho2 & 0xFFF) << 20, wy = rho1 | (rho2 >> 12) << 20
+    const uint32_t r0 = wx & 0xFFFFFu, r1 = wy & 0xFFFFFu, r2 = (wx >> 20) | ((wy >> 20) << 12);
+    a0 += (uint64_t)v * r0;
+    a1 += (uint64_t)v * r1;
+    a2 += (uint64_t)v * r2;
+}
+
+// One wave per block (blocks wave, wave + waves, ...).  VEC: S % 4 == 0 and 16-byte aligned stripes — lane l reads words 4l + 256 i
+// as dwordx4, four loads in flight per batch; else one word per lane and step.  Sums: products < 2^52, folded every 4096 of them.
+// F[pos[j] * 4 + c] receives the block's fingerprint c; a block with a word >= p is appended to bad[1 ..] (bad[0] counts them).
+template <bool VEC>
+__global__ __launch_bounds__(256) void fingerprint_kernel(const uint32_t* __restrict__ data, const uint32_t* __restrict__ parity, uint32_t k_blocks,
+                                                          uint32_t n_blocks, uint32_t S, const uint2* __restrict__ wt, const uint32_t* __restrict__ pos,
+                                                          uint32_t* __restrict__ F, uint32_t* __restrict__ bad, uint32_t bad_cap)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint32_t waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t j = wave; j < n_blocks; j += waves) {
+        const uint32_t* blk = j < k_blocks ? data + (size_t)j * S : parity + (size_t)(j - k_blocks) * S;
+        uint64_t a0 = 0, a1 = 0, a2 = 0;
+        uint32_t big = 0;
+        if (VEC) {
+            const uint4* wt4 = reinterpret_cast<const uint4*>(wt);
+            uint32_t batches = 0;
+            for (uint32_t base = lane * 4u; base < S; base += 1024u) {
+                uint4 v[4], wa[4], wb[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const uint32_t w = base + 256u * u;
+                    if (w < S) {
+                        v[u] = *reinterpret_cast<const uint4*>(blk + w);
+                        wa[u] = wt4[w >> 1];
+                        wb[u] = wt4[(w >> 1) + 1];
+                    } else {
+                        v[u] = wa[u] = wb[u] = make_uint4(0, 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    big |= (uint32_t)(v[u].x >= gf::P) | (uint32_t)(v[u].y >= gf::P) | (uint32_t)(v[u].z >= gf::P) | (uint32_t)(v[u].w >= gf::P);
+                    mad3(a0, a1, a2, v[u].x, wa[u].x, wa[u].y);
+                    mad3(a0, a1, a2, v[u].y, wa[u].z, wa[u].w);
+                    mad3(a0, a1, a2, v[u].z, wb[u].x, wb[u].y);
+                    mad3(a0, a1, a2, v[u].w, wb[u].z, wb[u].w);
+                }
+                if ((++batches & 255u) == 0) {  // 16 products per batch: 4096 since the last fold
+                    a0 = fold64(a0);
+                    a1 = fold64(a1);
+                    a2 = fold64(a2);
+                }
+            }
+        } else {
+            uint32_t steps = 0;
+            for (uint32_t w = lane; w < S; w += 64u) {
+                const uint32_t v = blk[w];
+                const uint2 q = wt[w];
+                big |= (uint32_t)(v >= gf::P);
+                mad3(a0, a1, a2, v, q.x, q.y);
+                if ((++steps & 4095u) == 0) {
+                    a0 = fold64(a0);
+                    a1 = fold64(a1);
+                    a2 = fold64(a2);
+                }
+            }
+        }
+        // lane sums < p, wave sums < 2^38
+        a0 = reduce64(a0);
+        a1 = reduce64(a1);
+        a2 = reduce64(a2);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            a0 += __shfl_xor(a0, o, 64);
+            a1 += __shfl_xor(a1, o, 64);
+            a2 += __shfl_xor(a2, o, 64);
+        }
+        const bool any_big = __any(big != 0);
+        if (lane == 0) {
+            uint32_t* f = F + (size_t)pos[j] * RW;
+            f[0] = reduce64(a0);
+            f[1] = reduce64(a1);
+            f[2] = reduce64(a2);
+            if (any_big) {
+                const uint32_t slot = atomicAdd(bad, 1u);
+                if (slot < bad_cap) bad[1 + slot] = j;
+            }
+        }
+    }
+}
+
+// out[u] = base[u] (or 1) * prod_i (w^u - roots[i]); WITH_F: G[u][c] = F[u][c] * that instead (all plain representatives)
+template <bool WITH_F>
+__global__ __launch_bounds__(256) void locator_kernel(const uint32_t* __restrict__ base, const uint32_t* __restrict__ roots, uint32_t nroots,
+                                                      const uint32_t* __restrict__ wpow, uint32_t NC, const uint32_t* __restrict__ F, uint32_t* __restrict__ out)
+{
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= NC) return;
+    const uint32_t x = wpow[u];
+    uint32_t v = base ? base[u] : 1u;
+    for (uint32_t i = 0; i < nroots; i++) v = gf::mul(v, gf::sub(x, roots[i]));
+    if (!WITH_F) {
+        out[u] = v;
+        return;
+    }
+    const uint4 f = reinterpret_cast<const uint4*>(F)[u];
+    reinterpret_cast<uint4*>(out)[u] = make_uint4(gf::mul(f.x, v), gf::mul(f.y, v), gf::mul(f.z, v), 0u);
+}
+
+// G holds the inverse transform in bit-reversed order (G[bitrev(m)] = NC * coefficient m).  Every coefficient m >= m_lo must vanish:
+// flag[0] |= 1 otherwise; the first `gather` of them per column go to syn[c * gather + (m - m_lo)].
+__global__ __launch_bounds__(256) void syndrome_kernel(const uint32_t* __restrict__ G, int lgc, uint32_t NC, uint32_t m_lo, uint32_t gather,
+                                                       uint32_t* __restrict__ syn, uint32_t* __restrict__ flag)
+{
+    const uint32_t m = m_lo + blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= NC) return;
+    const uint32_t slot = __brev(m) >> (32 - lgc);
+    const uint4 g = reinterpret_cast<const uint4*>(G)[slot];
+    if ((g.x | g.y | g.z) != 0) atomicOr(flag, 1u);
+    const uint32_t i = m - m_lo;
+    if (i < gather) {
+        syn[i] = g.x;
+        syn[gather + i] = g.y;
+        syn[2 * gather + i] = g.z;
+    }
+}
+
+// Lambda(w^u) == 0 -> u appended to found[1 ..] (found[0] counts)
+__global__ __launch_bounds__(256) void root_search_kernel(const uint32_t* __restrict__ lambda, uint32_t L, const uint32_t* __restrict__ wpow, uint32_t NC,
+                                                          uint32_t* __restrict__ found, uint32_t cap)
+{
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= NC) return;
+    const uint32_t x = wpow[u];
+    uint32_t acc = lambda[L];
+    for (int i = (int)L - 1; i >= 0; i--) acc = gf::add(gf::mul(acc, x), lambda[i]);
+    if (acc == 0) {
+        const uint32_t slot = atomicAdd(found, 1u);
+        if (slot < cap) found[1 + slot] = u;
+    }
+}
+
+__global__ __launch_bounds__(256) void powers_kernel(uint32_t* __restrict__ wpow, uint32_t w, uint32_t count)
+{
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= count) return;
+    uint32_t r = 1, b = w;
+    for (uint32_t e = u; e; e >>= 1) {
+        if (e & 1u) r = gf::mul(r, b);
+        b = gf::mul(b, b);
+    }
+    wpow[u] = r;
+}
+
+}  // namespace
+
+struct ScrubState {
+    uint64_t N = 0, NC = 0, n = 0, k = 0;  // transform length of the code, positions, blocks (user k + user m), data blocks
+    int lgc = 0;
+    uint64_t fixed = 0;                     // positions that hold no block (fixed erasures)
+    std::vector<uint32_t> pos;              // block -> position
+    std::vector<uint32_t> block_at;         // position -> block, ~0u if none (fixed erasure or known-zero data block)
+    fastecc_ctx* ntt = nullptr;             // stand-alone transform of NC points, 4 words per position
+    uint32_t* d_pos = nullptr;              // n words
+    uint32_t* d_wpow = nullptr;             // NC words: w^u
+    uint32_t* d_lfix = nullptr;             // NC words: the fixed erasures' locator at w^u (null: none)
+    uint32_t* d_F = nullptr;                // NC x 4 words: fingerprints by position (zero where no block is read)
+    uint32_t* d_G = nullptr;                // NC x 4 words: weighted fingerprints, transformed in place
+    uint32_t* d_small = nullptr;            // counters and lists: [bad: 1 + n], [flag: 1], [found: 1 + cap_found], syndromes, lambda, roots
+    uint64_t small_words = 0;
+    uint2* d_weights = nullptr;             // S packed weights of the current seed
+    uint64_t weights_seed = 0;
+    bool weights_valid = false;
+};
+
+void destroy_scrub_state(ScrubState* s)
+{
+    if (!s) return;
+    if (s->ntt) fastecc_destroy(s->ntt);
+    for (void* p : {(void*)s->d_pos, (void*)s->d_wpow, (void*)s->d_lfix, (void*)s->d_F, (void*)s->d_G, (void*)s->d_small, (void*)s->d_weights})
+        if (p) (void)hipFree(p);
+    delete s;
+}
+
+namespace {
+
+#define SCRUB_TRY(expr)                                   \
+    do {                                                  \
+        hipError_t e_ = (expr);                           \
+        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
+    } while (0)
+
+int scrub_args(fastecc_ctx* c, const void* data, const void* parity, int mem_kind)
+{
+    if (!c || !data || !parity || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
+    if (mem_kind != FASTECC_MEM_HOST && mem_kind != FASTECC_MEM_DEVICE && mem_kind != FASTECC_MEM_HOST_PINNED) return FASTECC_E_INVAL;
+    if (c->sharded || c->p61 || c->field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
+    if (c->q > 1) return FASTECC_E_UNSUPPORTED;  // mixed radix: the syndromes would need the decoder's mixed transforms in natural order
+    if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;
+    if (mem_kind != FASTECC_MEM_DEVICE) return FASTECC_E_UNSUPPORTED;
+    return FASTECC_OK;
+}
+
+// The context's geometry, position map, w^u table and fixed-erasure locator (once per context; synchronous).
+int scrub_state(fastecc_ctx* c, ScrubState** out)
+{
+    if (c->scrub) {
+        *out = c->scrub;
+        return FASTECC_OK;
+    }
+    ScrubState* s = new (std::nothrow) ScrubState();
+    if (!s) return FASTECC_E_NOMEM;
+    c->scrub = s;  // (partially built state is freed with the context; a failed build is retried from scratch)
+    auto fail = [&](int rc) {
+        destroy_scrub_state(s);
+        c->scrub = nullptr;
+        return rc;
+    };
+    int e = 1;
+    while ((1 << e) < c->cosets + 1) e++;
+    s->N = c->N;
+    s->NC = c->N << e;
+    s->lgc = c->n + e;
+    s->k = c->K;
+    s->n = c->K + c->Mu;
+    if (s->NC > (1ull << 20) || s->NC < 4) return fail(FASTECC_E_UNSUPPORTED);
+    auto parity_position = [&](uint64_t q) -> uint64_t {  // decode.hip, fastecc_decode_prepare
+        if (c->cosets > 1) {
+            const uint64_t t = q / c->N, j = q % c->N;
+            int jj = 1;
+            while ((1ull << jj) - 1 <= t) jj++;
+            const uint64_t odd = 2 * (t + 1 - (1ull << (jj - 1))) + 1;
+            return (odd << (e - jj)) + (j << e);
+        }
+        return ((q << c->fold) << 1) + 1;
+    };
+    s->pos.resize(s->n);
+    s->block_at.assign(s->NC, ~0u);
+    std::vector<uint8_t> held(s->NC, 0);
+    for (uint64_t i = 0; i < s->N; i++) held[i << e] = 1;  // data positions, the zero-extended ones included (known zeros)
+    for (uint64_t i = 0; i < s->k; i++) s->pos[i] = (uint32_t)(i << e);
+    for (uint64_t q = 0; q < c->Mu; q++) s->pos[s->k + q] = (uint32_t)parity_position(q);
+    for (uint64_t j = 0; j < s->n; j++) {
+        held[s->pos[j]] = 1;
+        s->block_at[s->pos[j]] = (uint32_t)j;
+    }
+    std::vector<uint32_t> fixed_roots;
+    const uint32_t w = gf::h_root((uint32_t)s->NC);
+    for (uint64_t u = 0; u < s->NC; u++)
+        if (!held[u]) fixed_roots.push_back(gf::h_pow(w, u));
+    s->fixed = fixed_roots.size();
+    if (s->N + s->fixed + (s->n - s->k) != s->NC) return fail(FASTECC_E_DEVICE);  // (the layout is inconsistent: cannot happen)
+
+    const int rc = create_ntt_ctx(&s->ntt, s->lgc, 4 * RW, c->device);
+    if (rc != FASTECC_OK) return fail(rc);
+    const uint64_t NC = s->NC;
+    hipError_t he = hipSuccess;
+    auto grid = [](uint64_t items) { return dim3((unsigned)((items + 255) / 256)); };
+    if ((he = hipMalloc((void**)&s->d_pos, s->n * 4)) != hipSuccess || (he = hipMalloc((void**)&s->d_wpow, NC * 4)) != hipSuccess ||
+        (he = hipMalloc((void**)&s->d_F, NC * RW * 4)) != hipSuccess || (he = hipMalloc((void**)&s->d_G, NC * RW * 4)) != hipSuccess)
+        return fail(hip_fail(he, "hipMalloc"));
+    if ((he = hipMemcpy(s->d_pos, s->pos.data(), s->n * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(hip_fail(he, "hipMemcpy"));
+    // positions no block is read from (fixed erasures, known-zero data blocks) keep fingerprint 0 for good
+    if ((he = hipMemset(s->d_F, 0, NC * RW * 4)) != hipSuccess) return fail(hip_fail(he, "hipMemset"));
+    hipLaunchKernelGGL(powers_kernel, grid(NC), dim3(256), 0, nullptr, s->d_wpow, w, (uint32_t)NC);
+    if ((he = hipGetLastError()) != hipSuccess) return fail(hip_fail(he, "powers_kernel"));
+    if (!fixed_roots.empty()) {
+        uint32_t* d_roots = nullptr;
+        if ((he = hipMalloc((void**)&s->d_lfix, NC * 4)) != hipSuccess || (he = hipMalloc((void**)&d_roots, fixed_roots.size() * 4)) != hipSuccess)
+            return fail(hip_fail(he, "hipMalloc"));
+        he = hipMemcpy(d_roots, fixed_roots.data(), fixed_roots.size() * 4, hipMemcpyHostToDevice);
+        if (he == hipSuccess) {
+            hipLaunchKernelGGL(locator_kernel<false>, grid(NC), dim3(256), 0, nullptr, nullptr, d_roots, (uint32_t)fixed_roots.size(), s->d_wpow,
+                               (uint32_t)NC, nullptr, s->d_lfix);
+            he = hipGetLastError();
+        }
+        if (he == hipSuccess) he = hipDeviceSynchronize();
+        (void)hipFree(d_roots);
+        if (he != hipSuccess) return fail(hip_fail(he, "locator_kernel"));
+    }
+    if ((he = hipDeviceSynchronize()) != hipSuccess) return fail(hip_fail(he, "hipDeviceSynchronize"));
+    *out = s;
+    return FASTECC_OK;
+}
+
+// The small buffer's layout for this call: bad list, flag, found list, gathered syndromes, lambda, extra roots
+struct Small {
+    uint32_t *bad, *flag, *found, *syn, *lambda, *roots;
+    uint64_t bad_cap, found_cap, gather, roots_cap;
+};
+
+int small_buffers(ScrubState* s, uint32_t locate_max, Small* sm)
+{
+    const uint64_t m = s->n - s->k;
+    sm->bad_cap = m + 1;
+    sm->found_cap = (uint64_t)locate_max + 1;
+    sm->gather = std::min<uint64_t>(2ull * locate_max, m);
+    sm->roots_cap = m + 1;
+    const uint64_t words = (1 + sm->bad_cap) + 1 + (1 + sm->found_cap) + R * std::max<uint64_t>(sm->gather, 1) + (locate_max + 1) + sm->roots_cap;
+    if (words > s->small_words) {
+        if (s->d_small) (void)hipFree(s->d_small);
+        s->d_small = nullptr;
+        s->small_words = 0;
+        SCRUB_TRY(hipMalloc((void**)&s->d_small, words * 4));
+        s->small_words = words;
+    }
+    uint32_t* p = s->d_small;
+    sm->bad = p;
+    p += 1 + sm->bad_cap;
+    sm->flag = p;
+    p += 1;
+    sm->found = p;
+    p += 1 + sm->found_cap;
+    sm->syn = p;
+    p += R * std::max<uint64_t>(sm->gather, 1);
+    sm->lambda = p;
+    p += locate_max + 1;
+    sm->roots = p;
+    return FASTECC_OK;
+}
+
+int upload_weights(fastecc_ctx* c, ScrubState* s, uint64_t seed, hipStream_t st)
+{
+    if (s->weights_valid && s->weights_seed == seed) return FASTECC_OK;
+    std::vector<uint32_t> h(2 * c->S);
+    uint64_t state = seed;
+    for (uint64_t w = 0; w < c->S; w++) {
+        const uint64_t x = splitmix64(state);
+        const uint32_t r0 = (uint32_t)(x & 0xFFFFF), r1 = (uint32_t)((x >> 20) & 0xFFFFF), r2 = (uint32_t)((x >> 40) & 0xFFFFF);
+        h[2 * w] = r0 | ((r2 & 0xFFFu) << 20);
+        h[2 * w + 1] = r1 | ((r2 >> 12) << 20);
+    }
+    s->weights_valid = false;
+    if (!s->d_weights) SCRUB_TRY(hipMalloc((void**)&s->d_weights, 2 * c->S * 4 + 16));
+    SCRUB_TRY(hipStreamSynchronize(st));  // (the previous call's kernels are done: calls end with a synchronise; this one has enqueued nothing yet)
+    SCRUB_TRY(hipMemcpy(s->d_weights, h.data(), 2 * c->S * 4, hipMemcpyHostToDevice));
+    s->weights_seed = seed;
+    s->weights_valid = true;
+    return FASTECC_OK;
+}
+
+// The fingerprint pass; the blocks holding a word >= p come back sorted in `bad` (b > bad_cap - 1: *overflow).
+int fingerprints(fastecc_ctx* c, ScrubState* s, const Small& sm, const uint32_t* data, const uint32_t* parity, uint64_t seed, hipStream_t st,
+                 std::vector<uint32_t>& bad)
+{
+    int rc = upload_weights(c, s, seed, st);
+    if (rc != FASTECC_OK) return rc;
+    SCRUB_TRY(hipMemsetAsync(sm.bad, 0, 4, st));
+    const bool vec = (c->S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
+    // every workgroup resident at once (6 waves per SIMD at 75 VGPRs): a grid-stride loop over the blocks without a tail wave of late groups
+    const uint64_t groups = std::min<uint64_t>((s->n + 3) / 4, (uint64_t)c->cus * 6);
+    {
+        ProfScope ps(c, st, "fingerprint", s->n * c->S * 4);
+        if (vec)
+            hipLaunchKernelGGL(fingerprint_kernel<true>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)c->S,
+                               s->d_weights, s->d_pos, s->d_F, sm.bad, (uint32_t)sm.bad_cap);
+        else
+            hipLaunchKernelGGL(fingerprint_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)c->S,
+                               s->d_weights, s->d_pos, s->d_F, sm.bad, (uint32_t)sm.bad_cap);
+        SCRUB_TRY(hipGetLastError());
+    }
+    uint32_t nb = 0;
+    SCRUB_TRY(hipMemcpyAsync(&nb, sm.bad, 4, hipMemcpyDeviceToHost, st));
+    SCRUB_TRY(hipStreamSynchronize(st));
+    bad.assign(std::min<uint64_t>(nb, sm.bad_cap), 0);
+    if (!bad.empty()) SCRUB_TRY(hipMemcpy(bad.data(), sm.bad + 1, bad.size() * 4, hipMemcpyDeviceToHost));
+    if (nb > bad.size()) bad.push_back(~0u);  // more than n - k: marks the overflow
+    std::sort(bad.begin(), bad.end());
+    return FASTECC_OK;
+}
+
+// Syndromes of the fingerprints with the positions `erased` (besides the fixed ones) erased: *nonzero = some coefficient above the
+// degree bound is not zero in some column; the first `gather` of each column land in syn (host) if gather > 0.
+int syndromes(fastecc_ctx* c, ScrubState* s, const Small& sm, const std::vector<uint32_t>& erased, uint64_t gather, hipStream_t st, bool* nonzero,
+              std::vector<uint32_t>* syn)
+{
+    const uint64_t NC = s->NC;
+    const uint64_t m_lo = s->N + s->fixed + erased.size();
+    *nonzero = false;
+    if (m_lo >= NC) return FASTECC_OK;  // nothing left to check: every set of n - k erasures explains any word
+    if (erased.size() > sm.roots_cap) return FASTECC_E_INVAL;
+    std::vector<uint32_t> pts(erased.size());
+    const uint32_t w = gf::h_root((uint32_t)NC);
+    for (size_t i = 0; i < erased.size(); i++) pts[i] = gf::h_pow(w, erased[i]);
+    if (!pts.empty()) SCRUB_TRY(hipMemcpyAsync(sm.roots, pts.data(), pts.size() * 4, hipMemcpyHostToDevice, st));
+    auto grid = [](uint64_t items) { return dim3((unsigned)((items + 255) / 256)); };
+    {
+        ProfScope ps(c, st, "scrub_weigh");
+        hipLaunchKernelGGL(locator_kernel<true>, grid(NC), dim3(256), 0, st, s->d_lfix, sm.roots, (uint32_t)pts.size(), s->d_wpow, (uint32_t)NC, s->d_F, s->d_G);
+        SCRUB_TRY(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, st, "scrub_transform");
+        const int rc = transform_bitrev(s->ntt, s->d_G, s->d_G, false, true, RW, st);
+        if (rc != FASTECC_OK) return rc;
+    }
+    gather = std::min<uint64_t>(gather, NC - m_lo);
+    SCRUB_TRY(hipMemsetAsync(sm.flag, 0, 4, st));
+    {
+        ProfScope ps(c, st, "scrub_syndromes");
+        hipLaunchKernelGGL(syndrome_kernel, grid(NC - m_lo), dim3(256), 0, st, s->d_G, s->lgc, (uint32_t)NC, (uint32_t)m_lo, (uint32_t)gather, sm.syn, sm.flag);
+        SCRUB_TRY(hipGetLastError());
+    }
+    uint32_t flag = 0;
+    SCRUB_TRY(hipMemcpyAsync(&flag, sm.flag, 4, hipMemcpyDeviceToHost, st));
+    if (syn) {
+        syn->assign(R * gather, 0);
+        if (gather) SCRUB_TRY(hipMemcpyAsync(syn->data(), sm.syn, R * gather * 4, hipMemcpyDeviceToHost, st));
+    }
+    SCRUB_TRY(hipStreamSynchronize(st));
+    *nonzero = flag != 0;
+    return FASTECC_OK;
+}
+
+// Berlekamp-Massey over GF(p): lambda = connection polynomial (lambda[0] = 1), returns its length L
+int berlekamp_massey(const uint32_t* s, uint32_t count, std::vector<uint32_t>& C)
+{
+    C.assign(count + 1, 0);
+    std::vector<uint32_t> B(count + 1, 0), T;
+    C[0] = B[0] = 1;
+    uint32_t L = 0, m = 1, b = 1;
+    for (uint32_t n = 0; n < count; n++) {
+        uint64_t d = s[n] % gf::P;
+        for (uint32_t i = 1; i <= L; i++) d = (d + (uint64_t)C[i] * (s[n - i] % gf::P)) % gf::P;
+        if (d == 0) {
+            m++;
+            continue;
+        }
+        const uint32_t coef = gf::h_mul((uint32_t)d, gf::h_inv(b));
+        const bool grow = 2 * L <= n;
+        if (grow) T = C;
+        for (uint32_t i = 0; i + m <= count; i++) {
+            if (!B[i]) continue;
+            C[i + m] = (uint32_t)((C[i + m] + (uint64_t)(gf::P - gf::h_mul(coef, B[i]))) % gf::P);
+        }
+        if (grow) {
+            L = n + 1 - L;
+            B = T;
+            b = (uint32_t)d;
+            m = 1;
+        } else {
+            m++;
+        }
+    }
+    C.resize(L + 1);
+    return (int)L;
+}
+
+// fastecc_locate_errors on a locked context: the sorted codeword indices of the corrupted blocks, or FASTECC_E_UNCORRECTABLE
+int locate(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t seed, hipStream_t st, std::vector<uint32_t>& result, bool verify_only)
+{
+    ScrubState* s = nullptr;
+    int rc = scrub_state(c, &s);
+    if (rc != FASTECC_OK) return rc;
+    const uint32_t tmax = (uint32_t)c->locate_max;
+    Small sm;
+    rc = small_buffers(s, tmax, &sm);
+    if (rc != FASTECC_OK) return rc;
+    std::vector<uint32_t> bad;
+    rc = fingerprints(c, s, sm, data, parity, seed, st, bad);
+    if (rc != FASTECC_OK) return rc;
+    const uint64_t m = s->n - s->k;
+    result.clear();
+    if (verify_only) {  // fastecc_verify: any out-of-range word or any non-zero syndrome is an inconsistency
+        if (!bad.empty()) {
+            result.push_back(bad[0]);
+            return FASTECC_OK;
+        }
+        bool nonzero = false;
+        rc = syndromes(c, s, sm, {}, 0, st, &nonzero, nullptr);
+        if (rc != FASTECC_OK) return rc;
+        if (nonzero) result.push_back(~0u);
+        return FASTECC_OK;
+    }
+    if (bad.size() > m) return FASTECC_E_UNCORRECTABLE;  // more known erasures than parity blocks
+    std::vector<uint32_t> erased(bad.size());
+    for (size_t i = 0; i < bad.size(); i++) erased[i] = s->pos[bad[i]];
+    const uint64_t avail = m - bad.size();  // syndromes left after the known erasures
+    bool nonzero = false;
+    std::vector<uint32_t> syn;
+    const uint64_t gather = std::min<uint64_t>(2ull * tmax, avail);
+    rc = syndromes(c, s, sm, erased, gather, st, &nonzero, &syn);
+    if (rc != FASTECC_OK) return rc;
+    if (nonzero) {
+        // the locator: the longest of the columns' LFSRs (a column may miss an error with probability <= 2^-20; the check below covers all)
+        std::vector<uint32_t> lambda, cand;
+        int L = 0;
+        for (int col = 0; col < R; col++) {
+            const int Lc = berlekamp_massey(syn.data() + col * gather, (uint32_t)gather, cand);
+            if (Lc > L) {
+                L = Lc;
+                lambda = cand;
+            }
+        }
+        if (L == 0 || (uint32_t)L > tmax || 2ull * (uint64_t)L > gather) return FASTECC_E_UNCORRECTABLE;
+        SCRUB_TRY(hipMemcpyAsync(sm.lambda, lambda.data(), (L + 1) * 4, hipMemcpyHostToDevice, st));
+        SCRUB_TRY(hipMemsetAsync(sm.found, 0, 4, st));
+        {
+            ProfScope ps(c, st, "scrub_root_search");
+            hipLaunchKernelGGL(root_search_kernel, dim3((unsigned)((s->NC + 255) / 256)), dim3(256), 0, st, sm.lambda, (uint32_t)L, s->d_wpow, (uint32_t)s->NC, sm.found,
+                               (uint32_t)sm.found_cap);
+            SCRUB_TRY(hipGetLastError());
+        }
+        uint32_t nf = 0;
+        SCRUB_TRY(hipMemcpyAsync(&nf, sm.found, 4, hipMemcpyDeviceToHost, st));
+        SCRUB_TRY(hipStreamSynchronize(st));
+        if (nf != (uint32_t)L) return FASTECC_E_UNCORRECTABLE;  // a locator splits into distinct roots at the code's positions, or it is no locator
+        std::vector<uint32_t> roots(nf);
+        SCRUB_TRY(hipMemcpy(roots.data(), sm.found + 1, nf * 4, hipMemcpyDeviceToHost));
+        for (uint32_t u : roots) {
+            const uint32_t j = s->block_at[u];
+            if (j == ~0u || std::binary_search(bad.begin(), bad.end(), j)) return FASTECC_E_UNCORRECTABLE;  // no block there, or one already erased
+            erased.push_back(u);
+            result.push_back(j);
+        }
+        // confirmation: with the located blocks erased too, every syndrome of every column vanishes
+        rc = syndromes(c, s, sm, erased, 0, st, &nonzero, nullptr);
+        if (rc != FASTECC_OK) return rc;
+        if (nonzero) return FASTECC_E_UNCORRECTABLE;
+    }
+    result.insert(result.end(), bad.begin(), bad.end());
+    std::sort(result.begin(), result.end());
+    return FASTECC_OK;
+}
+
+int report(const std::vector<uint32_t>& found, uint64_t* blocks, uint64_t cap, uint64_t* count)
+{
+    for (uint64_t i = 0; i < found.size() && i < cap; i++) blocks[i] = found[i];
+    *count = found.size();
+    return FASTECC_OK;
+}
+
+template <class F> int guarded(F body)
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return FASTECC_E_NOMEM;
+    } catch (...) {
+        return FASTECC_E_DEVICE;
+    }
+}
+
+}  // namespace
+
+}  // namespace fastecc
+
+using namespace fastecc;
+
+extern "C" {
+
+int fastecc_gf_berlekamp_massey(const uint32_t* s, uint32_t count, uint32_t* lambda, uint32_t cap)
+{
+    if ((!s && count) || !lambda) return FASTECC_E_INVAL;
+    return guarded([&]() -> int {
+        std::vector<uint32_t> C;
+        const int L = berlekamp_massey(s, count, C);
+        if ((uint64_t)cap < (uint64_t)L + 1) return FASTECC_E_INVAL;
+        std::copy(C.begin(), C.end(), lambda);
+        return L;
+    });
+}
+
+int fastecc_verify(fastecc_ctx* c, const void* data, const void* parity, int mem_kind, void* stream, uint64_t seed, int* consistent)
+{
+    if (!consistent) return FASTECC_E_INVAL;
+    int rc = scrub_args(c, data, parity, mem_kind);
+    if (rc != FASTECC_OK) return rc;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallLock lk(c->mu);
+    return guarded([&]() -> int {
+        std::vector<uint32_t> found;
+        const int r = locate(c, (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, true);
+        if (r == FASTECC_OK) *consistent = found.empty() ? 1 : 0;
+        return r;
+    });
+}
+
+int fastecc_locate_errors(fastecc_ctx* c, const void* data, const void* parity, int mem_kind, void* stream, uint64_t seed, uint64_t* blocks, uint64_t cap,
+                          uint64_t* count)
+{
+    if (!count || (!blocks && cap)) return FASTECC_E_INVAL;
+    int rc = scrub_args(c, data, parity, mem_kind);
+    if (rc != FASTECC_OK) return rc;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallLock lk(c->mu);
+    return guarded([&]() -> int {
+        std::vector<uint32_t> found;
+        const int r = locate(c, (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, false);
+        return r == FASTECC_OK ? report(found, blocks, cap, count) : r;
+    });
+}
+
+int fastecc_correct(fastecc_ctx* c, void* data, void* parity, int mem_kind, void* stream, uint64_t seed, uint64_t* blocks, uint64_t cap, uint64_t* count)
+{
+    if (!count || (!blocks && cap)) return FASTECC_E_INVAL;
+    int rc = scrub_args(c, data, parity, mem_kind);
+    if (rc != FASTECC_OK) return rc;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    return guarded([&]() -> int {
+        std::vector<uint32_t> found;
+        {
+            CallLock lk(c->mu);
+            const int r = locate(c, (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, false);
+            if (r != FASTECC_OK) return r;
+        }
+        if (found.empty()) return report(found, blocks, cap, count);
+        // the erasure decoder rebuilds the located blocks (prepare and repair take the context's lock themselves)
+        std::vector<uint8_t> dp(c->K, 1), pp(c->Mu, 1);
+        for (uint32_t j : found) (j < c->K ? dp[j] : pp[j - c->K]) = 0;
+        int r = fastecc_decode_prepare(c, dp.data(), pp.data());
+        if (r != FASTECC_OK) return r;
+        r = fastecc_repair(c, data, parity, FASTECC_MEM_DEVICE, stream);
+        if (r != FASTECC_OK) return r;
+        uint64_t seed2 = seed ^ 0x5C7B5C7B5C7B5C7Bull;
+        seed2 = splitmix64(seed2);
+        int ok = 0;
+        r = fastecc_verify(c, data, parity, FASTECC_MEM_DEVICE, stream, seed2, &ok);
+        if (r != FASTECC_OK) return r;
+        if (!ok) return FASTECC_E_UNCORRECTABLE;
+        return report(found, blocks, cap, count);
+    });
+}
+
+}  // extern "C"

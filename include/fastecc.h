@@ -34,15 +34,16 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 200 /* 0.2.0 */
+#define FASTECC_VERSION 300 /* 0.3.0: error detection and location (fastecc_verify / _locate_errors / _correct) */
 
 enum {
     FASTECC_OK = 0,
     FASTECC_E_INVAL = -1,       /* bad argument (n != 2k, k not a power of two, block_bytes % 4, null pointer, ...) */
     FASTECC_E_NOMEM = -2,       /* host or device allocation failed */
     FASTECC_E_DEVICE = -3,      /* no HIP device / HIP runtime error */
-    FASTECC_E_UNSUPPORTED = -4  /* field or size outside what GF(0xFFF00001) admits (k > 2^19), or an entry point the
+    FASTECC_E_UNSUPPORTED = -4, /* field or size outside what GF(0xFFF00001) admits (k > 2^19), or an entry point the
                                    context kind does not offer */
+    FASTECC_E_UNCORRECTABLE = -5 /* fastecc_locate_errors / fastecc_correct: the corrupted blocks could not be located */
 };
 
 enum {
@@ -317,6 +318,44 @@ int fastecc_decode(fastecc_ctx *ctx, void *data, const void *parity, int mem_kin
 int fastecc_repair(fastecc_ctx *ctx, void *data, void *parity, int mem_kind, void *stream);
 
 /*
+ * Error detection and location ("scrub"): find blocks that are present but wrong — bit rot, torn or misdirected writes — which
+ * the erasure decoder above cannot, because it only acts on losses the caller names.  The reference implements erasure decoding
+ * only (README.md:138); its write-up gives the budget used here: E errors plus W erasures need 2E + W check blocks.
+ * GF(0xFFF00001), DEVICE memory, every code fastecc_create accepts: (2k,k), n = k + N/2^d, n = 4k / 8k and zero-extended (n,k).
+ * Mixed-radix contexts (fastecc_create_ex), GF((2^61-1)^2), sharded contexts, a set "row_pitch_words" and FASTECC_MEM_HOST /
+ * HOST_PINNED return FASTECC_E_UNSUPPORTED; null or misaligned (not 4-byte) pointers FASTECC_E_INVAL before any device work.
+ * data = k blocks, parity = n - k blocks, each contiguous, as for fastecc_decode.  Enqueued on `stream`; every call waits for it.
+ *   fastecc_verify        : *consistent = 1 iff every word is < p and the blocks form a codeword, else 0.
+ *   fastecc_locate_errors : the corrupted blocks as codeword indices (data i -> i, parity j -> k + j), increasing; *count = 0 if
+ *                           the codeword is consistent.  At most `cap` are written to `blocks` (may be NULL when cap = 0), *count is
+ *                           the full number.  Reads only.
+ *   fastecc_correct       : locate, rebuild the located blocks in place with the erasure decoder (fastecc_decode_prepare +
+ *                           fastecc_repair: this REPLACES the context's prepared erasure pattern), then verify again with a seed
+ *                           derived from `seed`.  Same outputs as fastecc_locate_errors.
+ * Guarantee: let b be the number of blocks holding a word >= p (certainly corrupt: they count as known erasures) and t the number
+ * of other corrupted blocks.  Location succeeds and is exact whenever 2t + b <= n - k and t <= "locate_max" (fastecc_set_option,
+ * 0..4096, default 256 = the direct decode path's limit, so that fastecc_correct repairs in one pass; it bounds the host's
+ * Berlekamp-Massey work).  Beyond that the calls return FASTECC_E_UNCORRECTABLE or a located set that explains every syndrome of
+ * every fingerprint column — never one that does not.  fastecc_correct writes nothing to data or parity unless the located set
+ * does; otherwise it returns FASTECC_E_UNCORRECTABLE with both buffers untouched.  (If t + locate_max < n - k + 1 no other
+ * codeword is within locate_max blocks of the input, so t = locate_max + 1 errors always give FASTECC_E_UNCORRECTABLE there.)
+ * Method: one read of the codeword computes R = 3 fingerprints per block, F_c[j] = sum_w rho_c[w] r_j[w]
+ * mod p, with weights rho_c[w] < 2^20 drawn from `seed` (splitmix64), plus a per-block "word >= p" flag.  F is linear, so the
+ * fingerprints of a codeword form a codeword of the same code; they are decoded like one: syndromes by one transform of size
+ * NC = N << e, Berlekamp-Massey on the host, root search on the device.
+ * Seed and detection bound: a corrupted block whose words are all < p differs from the clean one by a non-zero vector mod p;
+ * for each column at most one of the 2^20 values of rho_c at a differing word cancels it, so a column misses it with probability
+ * <= 2^-20 over the weights, and all three independent columns with probability <= 2^-60 per block.  Words >= p are caught by
+ * the flag always.  The same seed gives the same answer.  fastecc_correct checks its result with a second seed: a block missed
+ * by all columns of the first (<= 2^-60) is reported as FASTECC_E_UNCORRECTABLE there, after the located blocks were written.
+ */
+int fastecc_verify(fastecc_ctx *ctx, const void *data, const void *parity, int mem_kind, void *stream, uint64_t seed, int *consistent);
+int fastecc_locate_errors(fastecc_ctx *ctx, const void *data, const void *parity, int mem_kind, void *stream, uint64_t seed,
+                          uint64_t *blocks, uint64_t cap, uint64_t *count);
+int fastecc_correct(fastecc_ctx *ctx, void *data, void *parity, int mem_kind, void *stream, uint64_t seed, uint64_t *blocks,
+                    uint64_t cap, uint64_t *count);
+
+/*
  * Data packing (GF.md:72-104 "Efficient data packing", README.md:160-163): RS.cpp only encodes words < p, so
  * arbitrary bytes are first recoded with one extra word per block — 4096-byte sectors become the 4100-byte
  * blocks the encoder then works on.  The reference describes this in prose and has NO code for it; the exact
@@ -343,6 +382,10 @@ uint32_t fastecc_gf_mul(uint32_t x, uint32_t y);
 uint32_t fastecc_gf_pow(uint32_t x, uint32_t e);
 uint32_t fastecc_gf_root(uint32_t order); /* 19^((p-1)/order); order must divide 2^20 */
 uint32_t fastecc_gf_inv(uint32_t x);
+/* Berlekamp-Massey over GF(0xFFF00001): the shortest LFSR that generates the `count` syndromes s (reduced mod p) — for power
+ * sums s_i = sum Y X^i the error locator Lambda(x) = prod (1 - X x).  Writes Lambda_0 = 1 .. Lambda_L to lambda and returns L;
+ * FASTECC_E_INVAL for a null pointer or cap < L + 1.  Host only (used by fastecc_locate_errors). */
+int fastecc_gf_berlekamp_massey(const uint32_t *s, uint32_t count, uint32_t *lambda, uint32_t cap);
 /* The same for FASTECC_FIELD_GF_P61_SQUARED: z[0] = re, z[1] = im (inputs are reduced mod p); out may alias.
  * fastecc_gf61_root returns FASTECC_E_INVAL unless order is a power of two <= 2^62. */
 int fastecc_gf61_mul(const uint64_t x[2], const uint64_t y[2], uint64_t out[2]);
@@ -391,6 +434,7 @@ const char *fastecc_plan_string(fastecc_ctx *ctx);
  *   "decode_direct_max" = 0..256 (default 256; 0..32 for GF((2^61-1)^2)): lost blocks up to which the decoder's direct path is used (next
  *                  decode_prepare); rows the matrix-core kernel cannot take stop at 96 (not for mixed-radix orders above 2^20, whose transform
  *                  path is much dearer: there the option alone decides);
+ *   "locate_max" = 0..4096 (default 256): the most unknown corrupted blocks fastecc_locate_errors / fastecc_correct look for;
  *   "decode_split" = 0 / 1 / 2 (default 1; codes over GF(0xFFF00001) with n <= 2k and k >= 2^17 (power-of-two orders), next decode_prepare): the
  *                  decoder's 2k-point transform as two transforms of k points — the data half, and of the parity half only the blocks needed: the
  *                  survivors at multiples of 2^h of that half (largest h <= 5 that leaves as many as there are lost data blocks), whose transform is
