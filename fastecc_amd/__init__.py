@@ -100,6 +100,11 @@ def lib():
     for name in ("locate_errors", "correct"):
         f = getattr(L, "fastecc_" + name)
         f.argtypes, f.restype = [vp, vp, vp, i32, vp, u64, ctypes.POINTER(u64), u64, ctypes.POINTER(u64)], i32
+    u64p = ctypes.POINTER(u64)
+    L.fastecc_update.argtypes, L.fastecc_update.restype = [vp, vp, vp, u64p, u64, vp, i32, vp], i32
+    L.fastecc_update_parity.argtypes, L.fastecc_update_parity.restype = [vp, vp, u64p, u64, vp, vp, i32, vp], i32
+    L.fastecc_code_coefficient.argtypes = [u64, u64, ctypes.c_uint, u64, u64, ctypes.POINTER(u32)]
+    L.fastecc_code_coefficient.restype = i32
     L.fastecc_gf_berlekamp_massey.argtypes = [ctypes.POINTER(u32), u32, ctypes.POINTER(u32), u32]
     L.fastecc_gf_berlekamp_massey.restype = i32
     L.fastecc_pack_blocks.argtypes, L.fastecc_pack_blocks.restype = [vp, vp, vp, i32, vp], i32
@@ -282,6 +287,25 @@ class Encoder:
         """locate_errors, then rebuild those blocks in place (replaces the prepared erasure pattern); returns the located blocks."""
         return self._located(lib().fastecc_correct, "fastecc_correct", data, parity, seed, stream, mem)
 
+    @staticmethod
+    def _block_list(blocks):
+        idx = [int(b) for b in blocks]
+        return len(idx), (ctypes.c_uint64 * max(len(idx), 1))(*idx)
+
+    def update(self, data, parity, blocks, new, stream=0, mem=MEM_DEVICE):
+        """Small write: data blocks `blocks` become the len(blocks) contiguous blocks of `new`; the parity is brought up to date
+        from the change alone (the rest of the stripe is not read).  data and parity then equal encode of the new stripe."""
+        count, arr = self._block_list(blocks)
+        _check(lib().fastecc_update(self._h, _addr(data), _addr(parity), arr, count, _addr(new), mem, stream or None), "fastecc_update")
+        return data, parity
+
+    def update_parity(self, parity, blocks, new, old=None, stream=0, mem=MEM_DEVICE):
+        """parity += the effect of data blocks `blocks` changing from `old` to `new` (contiguous blocks each; old=None: from zero)."""
+        count, arr = self._block_list(blocks)
+        _check(lib().fastecc_update_parity(self._h, _addr(parity), arr, count, _addr(old), _addr(new), mem, stream or None),
+               "fastecc_update_parity")
+        return parity
+
     def pack_blocks(self, raw, packed, stream=0, mem=MEM_DEVICE):
         """GF.md:72-104: k blocks of block_bytes - 4 arbitrary bytes -> k encodable blocks of block_bytes."""
         _check(lib().fastecc_pack_blocks(self._h, _addr(raw), _addr(packed), mem, stream or None), "fastecc_pack_blocks")
@@ -385,6 +409,13 @@ def plan_twiddles(k, block_bytes, plan=0, which=0):
     sl = (ctypes.c_int32 * max(n, 1))()
     _check(lib().fastecc_plan_twiddles(k, block_bytes, plan, which, out, sl), "fastecc_plan_twiddles")
     return list(out), list(sl)[:n]
+
+
+def code_coefficient(n, k, data_block, parity_block, flags=0):
+    """Host-only: the weight of data block `data_block` in parity block `parity_block` of the (n,k) code (fastecc_create_ex flags)."""
+    out = ctypes.c_uint32()
+    _check(lib().fastecc_code_coefficient(n, k, flags, data_block, parity_block, ctypes.byref(out)), "fastecc_code_coefficient")
+    return int(out.value)
 
 
 def gf_mul(x, y): return lib().fastecc_gf_mul(x, y)

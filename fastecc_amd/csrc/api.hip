@@ -164,6 +164,8 @@ void fastecc_destroy(fastecc_ctx* c)
     c->decoder = nullptr;
     destroy_scrub_state(c->scrub);
     c->scrub = nullptr;
+    destroy_update_state(c->update);
+    c->update = nullptr;
     DeviceGuard dg(c->device);
     direct_encode_destroy(c->direct_enc);
     c->direct_enc = nullptr;

@@ -64,6 +64,43 @@ int setup_mixed(fastecc_ctx* c, int q, uint64_t k_user, uint64_t m_user, const u
     return upload_twiddles(c);
 }
 
+// fastecc_create's rule for (n,k) over the power-of-two order 2^lg >= k (RS.md:23-27 "find N1 >= N ... extend input vector with zeroes"):
+// parity blocks k (the reference's configuration), 3k or 7k (further cosets), or any m <= N1: then the smallest power-of-two count >= m
+// (at least N1/16) is computed and the first m blocks are the parity.  Also what fastecc_code_coefficient (update.hip) describes.
+int pow2_code_shape(uint64_t n, uint64_t k, int* lg_out, int* fold_out, int* cosets_out)
+{
+    int lg = 1;
+    while ((1ull << lg) < k && lg < 63) lg++;
+    const uint64_t N1 = 1ull << lg, m = n - k;
+    int fold = 0, cosets = 1;
+    if (N1 == k && (n == 4 * k || n == 8 * k)) {
+        cosets = (int)(n / k) - 1;
+    } else {
+        if (m > N1) return FASTECC_E_UNSUPPORTED;
+        int lgm = 0;
+        while ((1ull << lgm) < m) lgm++;
+        fold = std::min(lg - lgm, 4);
+    }
+    *lg_out = lg;
+    *fold_out = fold;
+    *cosets_out = cosets;
+    return FASTECC_OK;
+}
+
+// fastecc_create_ex's transform order for the mixed-radix flags: the smallest q * 2^m >= k (q from the flags' set, 1 <= m <= 19); 0 if none
+uint64_t mixed_radix_order(uint64_t k, unsigned flags, int* q_out, int* m_out)
+{
+    uint64_t best = 0;
+    for (int q : {1, 3, 5, 7, 9, 13, 15, 21, 35, 39, 45, 63, 65, 91, 105, 117}) {
+        if (q > 15 && !(flags & FASTECC_CODE_MIXED_RADIX_PFA)) break;
+        for (int m = 1; m <= 19; m++) {
+            const uint64_t N1 = (uint64_t)q << m;
+            if (N1 >= k && (best == 0 || N1 < best)) best = N1, *q_out = q, *m_out = m;
+        }
+    }
+    return best;
+}
+
 }  // namespace fastecc
 
 extern "C" {
@@ -75,22 +112,12 @@ int fastecc_create(fastecc_ctx** out, uint64_t n, uint64_t k, uint64_t block_byt
     const bool f61 = field == FASTECC_FIELD_GF_P61_SQUARED;
     if (field != FASTECC_FIELD_GF_FFF00001 && !f61) return FASTECC_E_UNSUPPORTED;
     if (k < 1 || n <= k || block_bytes == 0 || (block_bytes % (f61 ? 16 : 4)) != 0) return FASTECC_E_INVAL;
-    // transform size: the next power of two (RS.md:23-27 "find N1 >= N ... extend input vector with zeroes")
-    int lg = 1;
-    while ((1ull << lg) < k && lg < 63) lg++;
-    const uint64_t N1 = 1ull << lg, m = n - k;
-    const bool pow2 = N1 == k;
-    // parity blocks: k (the reference's configuration), 3k or 7k (further cosets), or any m <= N1: then the smallest
-    // power-of-two count >= m (at least N1/16) is computed and the first m blocks are the parity
-    int fold = 0, cosets = 1;
-    if (pow2 && (n == 4 * k || n == 8 * k)) {
-        cosets = (int)(n / k) - 1;
-    } else {
-        if (m > N1) return FASTECC_E_UNSUPPORTED;
-        int lgm = 0;
-        while ((1ull << lgm) < m) lgm++;
-        fold = std::min(lg - lgm, 4);
+    int lg = 0, fold = 0, cosets = 1;
+    {
+        const int rc = pow2_code_shape(n, k, &lg, &fold, &cosets);  // transform order 2^lg, parity layout (the rules above)
+        if (rc != FASTECC_OK) return rc;
     }
+    const uint64_t N1 = 1ull << lg, m = n - k;
     // The 64-bit field always runs the (2 N1, N1) transform; other (n,k) of the rules above (zero extension, fewer parity blocks) work on
     // padded copies of the stripes, and parity block j is block j * 2^fold of the full parity — the same code definition as for
     // GF(0xFFF00001), without the kernels' bounds handling (RS.md:23-33 spells out exactly this: extend with zeroes, output some values).
@@ -140,15 +167,8 @@ int fastecc_create_ex(fastecc_ctx** out, uint64_t n, uint64_t k, uint64_t block_
     // transform order: the smallest q * 2^m >= k with q in {1, 3, 5, 7, 9, 13, 15} — with FASTECC_CODE_MIXED_RADIX_PFA also the products
     // of coprime factors 21 ... 117 —, m >= 1 (NTT.md:43-46: "the next divider of 0xFFF00000 is only a few percents larger than N itself");
     // w_(2 q 2^m) must exist: 2^(m+1) | 2^20
-    uint64_t best = 0;
     int bq = 1, bm = 0;
-    for (int q : {1, 3, 5, 7, 9, 13, 15, 21, 35, 39, 45, 63, 65, 91, 105, 117}) {
-        if (q > 15 && !(flags & FASTECC_CODE_MIXED_RADIX_PFA)) break;
-        for (int m = 1; m <= 19; m++) {
-            const uint64_t N1 = (uint64_t)q << m;
-            if (N1 >= k && (best == 0 || N1 < best)) best = N1, bq = q, bm = m;
-        }
-    }
+    const uint64_t best = mixed_radix_order(k, flags, &bq, &bm);
     if (best == 0 || n - k > best) return FASTECC_E_UNSUPPORTED;
     if (bq == 1) return fastecc_create(out, n, k, block_bytes, field, device);
     if (block_bytes / 4 > 0xFFFFFFFFull / 2) return FASTECC_E_UNSUPPORTED;

@@ -779,8 +779,7 @@ static int decode_prepare_impl(fastecc_ctx* c, const uint8_t* data_present, cons
     // i << e (blocks k..N-1 of a zero-extended code are known zero blocks), parity at the positions fastecc_create
     // documents — odd multiples of 2^fold for the codes inside (2N,N), the cosets' offsets for n = 4k / 8k.  Positions
     // that hold no block of the code count as erased, which is exactly what limits the losses to n - k.
-    int e = 1;
-    while ((1 << e) < ci.cosets + 1) e++;
+    const int e = code_coset_shift(ci.cosets);
     const uint64_t NC = N << e;
     const int lgc = ci.log2k + e;
     // the matrix-core kernel recomputes 256 blocks in a third of the transform path's time, the VALU kernel breaks even near 128
@@ -797,16 +796,7 @@ static int decode_prepare_impl(fastecc_ctx* c, const uint8_t* data_present, cons
         // matrix-core kernel cannot take is a speed trade-off against a transform path that is much dearer here, so it does not apply)
         if (T > (1ull << 20) && ci.direct_max > 0) direct_limit = std::max(direct_limit, std::min(ci.direct_max, direct_cap()));
     }
-    auto parity_position = [&](uint64_t q) -> uint64_t {
-        if (ci.cosets > 1) {
-            const uint64_t t = q / N, j = q % N;  // coset t = generator w_(N << jj)^c, see fastecc_create
-            int jj = 1;
-            while ((1ull << jj) - 1 <= t) jj++;
-            const uint64_t odd = 2 * (t + 1 - (1ull << (jj - 1))) + 1;
-            return (odd << (e - jj)) + (j << e);
-        }
-        return ((q << ci.fold) << 1) + 1;
-    };
+    auto parity_position = [&](uint64_t q) -> uint64_t { return code_parity_position(N, e, ci.fold, ci.cosets, q); };
     // ---- few losses (decided before any per-position table is built): interpolation on the surviving data points + a few parity points ----
     if (direct_limit > 0 && ci.user_k < 0xFFFFFFF0ull) {
         PhaseTimer ptd;

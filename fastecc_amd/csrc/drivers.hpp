@@ -117,5 +117,8 @@ int create_impl(fastecc_ctx** out, uint64_t n, uint64_t k, int lg, uint64_t bloc
                 const uint32_t* custom_factor);
 extern const uint32_t* const NTT_ONLY;  // custom_factor value: see create_ntt_ctx
 int setup_mixed(fastecc_ctx* c, int q, uint64_t k_user, uint64_t m_user, const uint32_t* custom_factor = nullptr);
+// the code geometry fastecc_create / fastecc_create_ex choose (also read by fastecc_code_coefficient, update.hip)
+int pow2_code_shape(uint64_t n, uint64_t k, int* lg, int* fold, int* cosets);
+uint64_t mixed_radix_order(uint64_t k, unsigned flags, int* q, int* m);
 
 }  // namespace fastecc

@@ -15,6 +15,29 @@ struct DecodeState;                        // decode.hip: tables of one erasure 
 void destroy_decode_state(DecodeState*);   // decode.hip, called by fastecc_destroy
 struct ScrubState;                         // scrub.hip: error detection and location (fastecc_verify, _locate_errors, _correct)
 void destroy_scrub_state(ScrubState*);     // scrub.hip, called by fastecc_destroy
+struct UpdateState;                        // update.hip: the parity update's weight table and delta rows (fastecc_update, _update_parity)
+void destroy_update_state(UpdateState*);   // update.hip, called by fastecc_destroy
+
+// Every GF(0xFFF00001) code is f (degree < N, the transform order: a power of two, or q * 2^m for the mixed-radix codes) on a subset of
+// the NC-th roots of unity, NC = N << e, position u <-> w_NC^u: data block i at i << e, parity block q at code_parity_position — odd
+// multiples of 2^fold for the codes inside (2N,N), the cosets' offsets for n = 4k / 8k (fastecc_create).  decode.hip, scrub.hip, update.hip.
+inline int code_coset_shift(int cosets)
+{
+    int e = 1;
+    while ((1 << e) < cosets + 1) e++;
+    return e;
+}
+inline uint64_t code_parity_position(uint64_t N, int e, int fold, int cosets, uint64_t q)
+{
+    if (cosets > 1) {
+        const uint64_t t = q / N, j = q % N;  // coset t = generator w_(N << jj)^c, see fastecc_create
+        int jj = 1;
+        while ((1ull << jj) - 1 <= t) jj++;
+        const uint64_t odd = 2 * (t + 1 - (1ull << (jj - 1))) + 1;
+        return (odd << (e - jj)) + (j << e);
+    }
+    return ((q << fold) << 1) + 1;
+}
 
 // ---- sharded.hip: one stripe in column slabs on several devices (fastecc_create_sharded) ----
 struct Sharded;

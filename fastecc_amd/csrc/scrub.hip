@@ -2,7 +2,7 @@
 //
 // The erasure decoder (decode.hip) acts on losses the caller names.  Here the corrupted blocks are found first.  Every code of the
 // library is f (degree < N) on a subset of the NC-th roots of unity, NC = N << e, position u <-> w^u: data block i at i << e, parity at
-// the positions decode.hip's parity_position gives, zero-extended data blocks are known zeros, positions that hold no block are
+// the positions code_parity_position (internal.hpp) gives, zero-extended data blocks are known zeros, positions that hold no block are
 // fixed erasures.  With l the locator of the erased positions, p = f * l has degree < N + |erased| (the decoder's identity), so the
 // coefficients of the inverse transform of c[u] l(w^u) (0 at erased positions) above that vanish for a codeword.  For a received word
 // c + e they are S_m = sum_u e_u l(w^u) w^(-um) / NC: power sums in the locators X_u = w^(-u) — the syndromes of classic RS decoding,
@@ -285,16 +285,7 @@ int scrub_state(fastecc_ctx* c, ScrubState** out)
     s->k = c->K;
     s->n = c->K + c->Mu;
     if (s->NC > (1ull << 20) || s->NC < 4) return fail(FASTECC_E_UNSUPPORTED);
-    auto parity_position = [&](uint64_t q) -> uint64_t {  // decode.hip, fastecc_decode_prepare
-        if (c->cosets > 1) {
-            const uint64_t t = q / c->N, j = q % c->N;
-            int jj = 1;
-            while ((1ull << jj) - 1 <= t) jj++;
-            const uint64_t odd = 2 * (t + 1 - (1ull << (jj - 1))) + 1;
-            return (odd << (e - jj)) + (j << e);
-        }
-        return ((q << c->fold) << 1) + 1;
-    };
+    auto parity_position = [&](uint64_t q) -> uint64_t { return code_parity_position(c->N, e, c->fold, c->cosets, q); };
     s->pos.resize(s->n);
     s->block_at.assign(s->NC, ~0u);
     std::vector<uint8_t> held(s->NC, 0);

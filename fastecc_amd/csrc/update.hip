@@ -1,0 +1,540 @@
+// update.hip — small writes: fastecc_update, fastecc_update_parity, fastecc_code_coefficient (include/fastecc.h).
+//
+// The code is linear, so after data blocks i_u change by D_u = new_u - old_u the parity changes by
+//     parity[q][w] += sum_u L_{i_u}(y_q) * D_u[w]   (mod p),
+// L_i the Lagrange basis on the data points.  Every code of the library sits on the NC-th roots of unity (internal.hpp:
+// code_parity_position): data block i at position i << e, parity block q at pos(q).  With x_i = w^(i << e), y = w^pos and
+// L_i(y) = (y^N - 1) x_i / (N (y - x_i)) (direct.hip) the weight depends on the difference of positions only:
+//     L_i(y_q) = G[(pos(q) - (i << e)) mod NC],   G[u] = (w^(uN) - 1) / (N (w^u - 1))   (u not a multiple of 2^e),
+// so ONE table of NC words serves every data block, every parity block and every call.  For e = 1 only odd u occur and the table holds
+// G[2v + 1] at v (NC / 2 words).
+//
+// A call runs in passes of up to ROWS changed blocks:
+//   update_table_kernel : G in Montgomery form, one thread per entry, once per context (on the stream of the first call);
+//   update_delta_kernel : D_u into the context's delta rows; fastecc_update also stores new_u into the stripe, after reading old_u;
+//   update_parity_kernel: a wave owns a column slice of 64 V words and a run of parity blocks.  It loads the pass's T <= ROWS delta
+//                         rows of its slice into VGPRs once, then streams its parity blocks: T wave-uniform weights from G (scalar
+//                         loads behind one wait), T x V mac96 into 96-bit sums (lazy96.hpp), + the old parity word, one reduction, a
+//                         non-temporal store.  The next block's parity load is in flight during the current block's arithmetic.
+#include <algorithm>
+#include <atomic>
+#include <vector>
+
+#include "drivers.hpp"
+#include "lazy96.hpp"
+#include "ntt_device.hpp"
+
+namespace fastecc {
+
+namespace {
+
+constexpr int ROWS = 16;  // changed blocks per pass: delta rows held in VGPRs (32 spills SGPRs: the 32 row positions and their weights)
+
+struct CodeGeom {
+    uint64_t N = 0;  // transform order (q * 2^m for the mixed-radix codes)
+    int e = 1, fold = 0, cosets = 1;
+    uint64_t K = 0, Mu = 0;  // data and parity blocks of the caller's stripes
+};
+
+uint32_t geom_weight(const CodeGeom& g, uint64_t i, uint64_t q)
+{
+    const uint64_t NC = g.N << g.e;
+    const uint64_t u = (code_parity_position(g.N, g.e, g.fold, g.cosets, q) + NC - (i << g.e)) % NC;
+    const uint32_t w = gf::h_root((uint32_t)NC), wu = gf::h_pow(w, u);
+    const uint32_t num = (uint32_t)(((uint64_t)gf::h_pow(wu, g.N) + gf::P - 1u) % gf::P);
+    const uint32_t den = gf::h_mul((uint32_t)(g.N % gf::P), (uint32_t)(((uint64_t)wu + gf::P - 1u) % gf::P));
+    return gf::h_mul(num, gf::h_inv(den));
+}
+
+// The geometry fastecc_create / fastecc_create_ex give (n, k, flags) over GF(0xFFF00001), without a device.
+int geom_of_code(uint64_t n, uint64_t k, unsigned flags, CodeGeom* g)
+{
+    if (flags & ~(unsigned)(FASTECC_CODE_MIXED_RADIX | FASTECC_CODE_TOP_RADIX2 | FASTECC_CODE_MIXED_RADIX_PFA)) return FASTECC_E_INVAL;
+    if (k < 1 || n <= k) return FASTECC_E_INVAL;
+    g->K = k;
+    g->Mu = n - k;
+    if (flags & FASTECC_CODE_TOP_RADIX2) {  // the (2k,k) code through another kernel
+        int lg = 0;
+        while ((1ull << lg) < k) lg++;
+        if (flags != FASTECC_CODE_TOP_RADIX2 || n != 2 * k || (1ull << lg) != k || lg < 12 || lg > 19) return FASTECC_E_UNSUPPORTED;
+        g->N = k;
+        return FASTECC_OK;
+    }
+    if (flags & (FASTECC_CODE_MIXED_RADIX | FASTECC_CODE_MIXED_RADIX_PFA)) {  // create.hip: the same choice as fastecc_create_ex
+        int bq = 1, bm = 0;
+        const uint64_t best = mixed_radix_order(k, flags, &bq, &bm);
+        if (best == 0 || n - k > best) return FASTECC_E_UNSUPPORTED;
+        if (bq > 1) {
+            g->N = best;
+            return FASTECC_OK;
+        }
+    }
+    int lg = 0;
+    const int rc = pow2_code_shape(n, k, &lg, &g->fold, &g->cosets);  // create.hip: the same rule as fastecc_create
+    if (rc != FASTECC_OK) return rc;
+    const uint64_t N1 = 1ull << lg;
+    if (lg > 19 || (g->cosets > 1 && n > (1ull << 20))) return FASTECC_E_UNSUPPORTED;
+    g->N = N1;
+    g->e = code_coset_shift(g->cosets);
+    return FASTECC_OK;
+}
+
+CodeGeom geom_of_ctx(const fastecc_ctx* c)
+{
+    CodeGeom g;
+    g.N = (uint64_t)c->q * c->N;
+    g.cosets = c->cosets;
+    g.fold = c->fold;
+    g.e = code_coset_shift(c->cosets);
+    g.K = c->K;
+    g.Mu = c->Mu;
+    return g;
+}
+
+__device__ __forceinline__ uint32_t dev_pow(uint32_t x, uint64_t e)
+{
+    uint32_t r = 1;
+    for (; e; e >>= 1) {
+        if (e & 1u) r = gf::mul(r, x);
+        x = gf::mul(x, x);
+    }
+    return r;
+}
+
+// G[v], u = (v << tshift) | tshift; Montgomery form; 0 where u is a multiple of 2^e (no weight has that index)
+__global__ __launch_bounds__(256) void update_table_kernel(uint32_t* __restrict__ G, uint32_t words, uint32_t w, uint32_t N_mod_p, uint64_t N, uint32_t tshift,
+                                                           uint32_t emask)
+{
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= words) return;
+    const uint32_t u = (v << tshift) | tshift;
+    uint32_t r = 0;
+    if (u & emask) {
+        const uint32_t wu = dev_pow(w, u);
+        const uint32_t num = gf::sub(dev_pow(wu, N), 1u);
+        const uint32_t den = gf::mul(N_mod_p, gf::sub(wu, 1u));
+        r = gf::mul(gf::mul(num, dev_pow(den, gf::P - 2u)), gf::MONT_ONE);
+    }
+    G[v] = r;
+}
+
+struct DeltaArgs {
+    uint32_t* data;              // fastecc_update: the stripe (old blocks read, new ones stored); else null
+    const uint32_t* old_blocks;  // fastecc_update_parity: the pass's old blocks, contiguous (null: zero)
+    const uint32_t* new_blocks;  // the pass's new blocks, contiguous
+    uint32_t* delta;             // [rows][S]
+    uint64_t S;
+    uint32_t rows;               // rows of the pass; rows [rows, gridDim.y) of delta are zeroed (the parity kernel reads T rows)
+    uint32_t idx[ROWS];          // data block of each row
+};
+
+// thread (word w, row r): delta[r][w] = new - old; the stripe gets new after old was read
+__global__ __launch_bounds__(256) void update_delta_kernel(const DeltaArgs a)
+{
+    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t r = blockIdx.y;
+    if (w >= a.S) return;
+    if (r >= a.rows) {
+        a.delta[(uint64_t)r * a.S + w] = 0;
+        return;
+    }
+    const uint32_t nv = a.new_blocks[(uint64_t)r * a.S + w];
+    uint32_t ov = 0;
+    if (a.data) {
+        uint32_t* p = a.data + (uint64_t)a.idx[r] * a.S + w;
+        ov = *p;
+        *p = nv;
+    } else if (a.old_blocks) {
+        ov = a.old_blocks[(uint64_t)r * a.S + w];
+    }
+    a.delta[(uint64_t)r * a.S + w] = gf::sub(nv, ov);
+}
+
+struct ParityArgs {
+    uint32_t* parity;        // Mu blocks of S words
+    const uint32_t* delta;   // [rows][S]
+    const uint32_t* G;       // weight table (Montgomery form)
+    uint64_t S;
+    uint32_t M;              // parity blocks
+    uint32_t slices;         // column slices of 64 V words
+    uint32_t run;            // parity blocks per wave
+    uint32_t waves;
+    uint32_t rows;           // live delta rows of the pass (<= T)
+    uint32_t NC, tshift;     // positions; weight index = ((pos - d) mod NC) >> tshift
+    uint32_t qs, qmask, ps;  // pos(q) = off[q >> qs] + ((q & qmask) << ps)
+    uint32_t off[8];
+    uint32_t d[ROWS];        // position of each row's data block (i << e)
+};
+
+// Parity blocks through buffer descriptors: the descriptor (base = the block, range = its S words) is scalar and the lane offset is one
+// VGPR fixed for the whole loop, so no address register is rewritten between a block's load and the next one.  A lane past the end of
+// the row gets an offset outside the range: its loads return 0 and its stores are dropped by the hardware.  aux 2: non-temporal.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t block_desc(const uint32_t* p, uint32_t bytes)
+{
+    const uint64_t v = reinterpret_cast<uint64_t>(p);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0, bytes, 0x00020000);
+}
+template <int V> __device__ __forceinline__ void load_nt(uint32_t (&dst)[V], __amdgpu_buffer_rsrc_t d, uint32_t voff)
+{
+    if constexpr (V == 1) {
+        dst[0] = __builtin_amdgcn_raw_buffer_load_b32(d, voff, 0, 2);
+    } else if constexpr (V == 2) {
+        typedef unsigned v2 __attribute__((ext_vector_type(2)));
+        const v2 t = __builtin_amdgcn_raw_buffer_load_b64(d, voff, 0, 2);
+        dst[0] = t[0], dst[1] = t[1];
+    } else {
+        typedef unsigned v4 __attribute__((ext_vector_type(4)));
+        const v4 t = __builtin_amdgcn_raw_buffer_load_b128(d, voff, 0, 2);
+        dst[0] = t[0], dst[1] = t[1], dst[2] = t[2], dst[3] = t[3];
+    }
+}
+template <int V> __device__ __forceinline__ void store_nt(const uint32_t (&src)[V], __amdgpu_buffer_rsrc_t d, uint32_t voff)
+{
+    if constexpr (V == 1) {
+        __builtin_amdgcn_raw_buffer_store_b32(src[0], d, voff, 0, 2);
+    } else if constexpr (V == 2) {
+        typedef unsigned v2 __attribute__((ext_vector_type(2)));
+        __builtin_amdgcn_raw_buffer_store_b64(v2{src[0], src[1]}, d, voff, 0, 2);
+    } else {
+        typedef unsigned v4 __attribute__((ext_vector_type(4)));
+        __builtin_amdgcn_raw_buffer_store_b128(v4{src[0], src[1], src[2], src[3]}, d, voff, 0, 2);
+    }
+}
+
+// The loop has no branch on the row count or the lane: every one of the T delta rows is loaded (rows past the pass's count are zero in
+// d_delta and point at a valid weight), dead lanes read column 0 and only skip the store, and the parity block of the next step is
+// requested at a clamped index.  So the T weights of a block go out as T scalar loads behind one wait, and the next block's parity load
+// stays in flight under the current block's arithmetic (two register sets, the loop unrolled by two: no copy between them).
+template <int T, int V>
+__global__ __launch_bounds__(256) void update_parity_kernel(const ParityArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (wave >= a.waves) return;
+    const uint32_t slice = wave % a.slices;
+    const uint32_t q0 = (wave / a.slices) * a.run, q1 = min(q0 + a.run, a.M);
+    const uint64_t col = ((uint64_t)slice * 64u + lane) * V;
+    const bool live = col < a.S;  // (V > 1 only when S % V == 0: a live lane's V words all exist)
+    const uint64_t lcol = live ? col : 0;
+    const uint32_t bytes = (uint32_t)(a.S * 4u);
+    const uint32_t voff = live ? (uint32_t)col * 4u : bytes;  // (S * 4 < 2^32: update_pass)
+    uint32_t x[T][V];
+#pragma unroll
+    for (int i = 0; i < T; ++i) load_vec<V>(x[i], a.delta + (uint64_t)i * a.S + lcol);
+    const_u32_ptr G = as_constant(a.G);
+    auto desc = [&](uint32_t q) { return block_desc(a.parity + (uint64_t)q * a.S, bytes); };
+    auto step = [&](uint32_t q, const uint32_t (&old)[V]) {
+        const uint32_t pos = a.off[q >> a.qs] + ((q & a.qmask) << a.ps);
+        uint32_t w[T];
+#pragma unroll
+        for (int i = 0; i < T; ++i) {
+            int32_t u = (int32_t)(pos - a.d[i]);
+            if (u < 0) u += (int32_t)a.NC;
+            w[i] = G[(uint32_t)u >> a.tshift];
+        }
+        uint64_t lo[V];
+        uint32_t hi[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) lo[v] = 0, hi[v] = 0;
+#pragma unroll
+        for (int i = 0; i < T; ++i)
+#pragma unroll
+            for (int v = 0; v < V; ++v) mac96(lo[v], hi[v], x[i][v], w[i]);
+        uint32_t r[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) r[v] = gf::add(reduce96(lo[v], hi[v]), old[v]);
+        store_nt<V>(r, desc(q), voff);
+    };
+    if (q0 >= q1) return;
+    const uint32_t last = q1 - 1;
+    uint32_t pa[V], pb[V];
+    load_nt<V>(pa, desc(q0), voff);
+    for (uint32_t q = q0; q < q1; q += 2) {
+        load_nt<V>(pb, desc(min(q + 1, last)), voff);
+        step(q, pa);
+        if (q + 1 > last) break;
+        load_nt<V>(pa, desc(min(q + 2, last)), voff);
+        step(q + 1, pb);
+    }
+}
+
+#define UPD_TRY(expr)                                     \
+    do {                                                  \
+        hipError_t e_ = (expr);                           \
+        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
+    } while (0)
+
+}  // namespace
+
+struct UpdateState {
+    CodeGeom g;
+    uint64_t NC = 0;
+    uint32_t tshift = 0;
+    uint32_t* d_G = nullptr;  // weight table, (NC >> tshift) words
+    bool table_ready = false, table_pending = false;
+    hipEvent_t table_event = nullptr;  // end of the table kernel (on table_stream)
+    hipStream_t table_stream = nullptr;
+    uint32_t* d_delta = nullptr;  // ROWS x S words (an internal buffer: ordered between streams by buf_event)
+};
+
+void destroy_update_state(UpdateState* s)
+{
+    if (!s) return;
+    if (s->d_G) (void)hipFree(s->d_G);
+    if (s->d_delta) (void)hipFree(s->d_delta);
+    if (s->table_event) (void)hipEventDestroy(s->table_event);
+    delete s;
+}
+
+namespace {
+
+// The weight table for stream st: built by a kernel on st at the first call (no host synchronisation); a use on another stream waits
+// for that kernel on the device until it is seen complete.
+int update_table(fastecc_ctx* c, UpdateState* s, hipStream_t st)
+{
+    if (s->table_ready) {
+        if (s->table_pending && st != s->table_stream) {
+            if (hipEventQuery(s->table_event) == hipSuccess) s->table_pending = false;
+            else UPD_TRY(hipStreamWaitEvent(st, s->table_event, 0));
+            (void)hipGetLastError();  // hipErrorNotReady of the query is not an error
+        }
+        return FASTECC_OK;
+    }
+    const uint64_t words = s->NC >> s->tshift;
+    if (!s->d_G) UPD_TRY(hipMalloc((void**)&s->d_G, words * 4));
+    if (!s->table_event) UPD_TRY(hipEventCreateWithFlags(&s->table_event, hipEventDisableTiming));
+    {
+        ProfScope ps(c, st, "update_table", words * 4);
+        hipLaunchKernelGGL(update_table_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, s->d_G, (uint32_t)words, gf::h_root((uint32_t)s->NC),
+                           (uint32_t)(s->g.N % gf::P), (uint64_t)s->g.N, s->tshift, (uint32_t)((1u << s->g.e) - 1u));
+        UPD_TRY(hipGetLastError());
+    }
+    UPD_TRY(hipEventRecord(s->table_event, st));
+    s->table_stream = st;
+    s->table_ready = s->table_pending = true;
+    return FASTECC_OK;
+}
+
+int update_state(fastecc_ctx* c, UpdateState** out)
+{
+    if (!c->update) {
+        UpdateState* s = new (std::nothrow) UpdateState();
+        if (!s) return FASTECC_E_NOMEM;
+        s->g = geom_of_ctx(c);
+        s->NC = s->g.N << s->g.e;
+        s->tshift = s->g.e == 1 ? 1u : 0u;
+        if (s->NC > 0xFFFFFFFFull / 2) {
+            delete s;
+            return FASTECC_E_UNSUPPORTED;
+        }
+        c->update = s;
+    }
+    *out = c->update;
+    return FASTECC_OK;
+}
+
+template <int V> const void* parity_kernel_v(int T)
+{
+    switch (T) {
+        case 1: return (const void*)update_parity_kernel<1, V>;
+        case 2: return (const void*)update_parity_kernel<2, V>;
+        case 4: return (const void*)update_parity_kernel<4, V>;
+        case 8: return (const void*)update_parity_kernel<8, V>;
+        default: return (const void*)update_parity_kernel<ROWS, V>;
+    }
+}
+
+// waves of update_parity_kernel<T, V> one SIMD holds: 512 VGPRs in granules of 8, at most 8 (queried once per shape)
+int resident_waves_per_simd(int T, int V)
+{
+    static std::atomic<int> cache[3][5];  // zero-initialised (static storage)
+    const int vi = V == 4 ? 0 : V == 2 ? 1 : 2;
+    int ti = 0;
+    while ((1 << ti) < T) ti++;
+    std::atomic<int>& slot = cache[vi][ti];
+    if (!slot.load()) {
+        hipFuncAttributes attr{};
+        const void* fn = V == 4 ? parity_kernel_v<4>(T) : V == 2 ? parity_kernel_v<2>(T) : parity_kernel_v<1>(T);
+        int waves = 4;  // (if the query fails: a safe middle)
+        if (hipFuncGetAttributes(&attr, fn) == hipSuccess && attr.numRegs > 0) waves = std::max(1, std::min(8, 512 / ((attr.numRegs + 7) / 8 * 8)));
+        (void)hipGetLastError();
+        slot.store(waves);
+    }
+    return slot.load();
+}
+
+template <int V> void launch_parity_v(int T, const ParityArgs& a, dim3 grid, hipStream_t st)
+{
+    switch (T) {
+        case 1: hipLaunchKernelGGL((update_parity_kernel<1, V>), grid, dim3(256), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((update_parity_kernel<2, V>), grid, dim3(256), 0, st, a); break;
+        case 4: hipLaunchKernelGGL((update_parity_kernel<4, V>), grid, dim3(256), 0, st, a); break;
+        case 8: hipLaunchKernelGGL((update_parity_kernel<8, V>), grid, dim3(256), 0, st, a); break;
+        default: hipLaunchKernelGGL((update_parity_kernel<ROWS, V>), grid, dim3(256), 0, st, a); break;
+    }
+}
+
+// One pass: rows [r0, r0 + rows) of the call
+int update_pass(fastecc_ctx* c, UpdateState* s, uint32_t* data, uint32_t* parity, const uint64_t* blocks, uint32_t rows, const uint32_t* old_blocks,
+                const uint32_t* new_blocks, hipStream_t st)
+{
+    const uint64_t S = c->S;
+    DeltaArgs da{};
+    da.data = data;
+    da.old_blocks = old_blocks;
+    da.new_blocks = new_blocks;
+    da.delta = s->d_delta;
+    da.S = S;
+    da.rows = rows;
+    int T = 1;
+    while (T < (int)rows) T <<= 1;
+    ParityArgs pa{};
+    for (int r = 0; r < T; r++) {  // rows past the count: zero delta rows, any valid weight
+        const uint64_t b = blocks[(uint32_t)r < rows ? r : 0];
+        if ((uint32_t)r < rows) da.idx[r] = (uint32_t)b;
+        pa.d[r] = (uint32_t)(b << s->g.e);
+    }
+    {
+        ProfScope ps(c, st, "update_delta", (uint64_t)rows * S * 4 * (data || old_blocks ? 3 : 2) + (data ? rows * S * 4 : 0));
+        hipLaunchKernelGGL(update_delta_kernel, dim3((unsigned)((S + 255) / 256), (unsigned)T), dim3(256), 0, st, da);
+        UPD_TRY(hipGetLastError());
+    }
+    const CodeGeom& g = s->g;
+    pa.parity = parity;
+    pa.delta = s->d_delta;
+    pa.G = s->d_G;
+    pa.S = S;
+    pa.M = (uint32_t)g.Mu;
+    pa.rows = rows;
+    pa.NC = (uint32_t)s->NC;
+    pa.tshift = s->tshift;
+    if (g.cosets > 1) {  // N a power of two: coset t = q >> log2 N
+        int lgN = 0;
+        while ((1ull << lgN) < g.N) lgN++;
+        pa.qs = (uint32_t)lgN;
+        pa.qmask = (uint32_t)(g.N - 1);
+        pa.ps = (uint32_t)g.e;
+        for (int t = 0; t < g.cosets && t < 8; t++) pa.off[t] = (uint32_t)code_parity_position(g.N, g.e, g.fold, g.cosets, (uint64_t)t * g.N);
+    } else {
+        pa.qs = 31;  // q < 2^31: always entry 0
+        pa.qmask = 0xFFFFFFFFu;
+        pa.ps = (uint32_t)g.fold + 1u;
+        pa.off[0] = 1;
+    }
+    if (S * 4 + 64 * 16 > 0xFFFFFFFFull) return FASTECC_E_UNSUPPORTED;  // (blocks of 4 GiB: the kernel addresses a block through one buffer descriptor)
+    int V = 4;
+    while (V > 1 && ((S % V) != 0 || ((uintptr_t)parity & (4u * V - 1u)) != 0)) V >>= 1;
+    pa.slices = (uint32_t)((S + 64u * V - 1) / (64u * V));
+    // every wave resident at once (the kernel's waves per SIMD from its register count), each with an equal run of parity blocks
+    const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(T, V);
+    const uint64_t runs = std::max<uint64_t>(1, std::min<uint64_t>(g.Mu, target / pa.slices));
+    pa.run = (uint32_t)((g.Mu + runs - 1) / runs);
+    const uint64_t waves = (uint64_t)pa.slices * ((g.Mu + pa.run - 1) / pa.run);
+    if (waves > 0xFFFFFFFFull / 64) return FASTECC_E_UNSUPPORTED;
+    pa.waves = (uint32_t)waves;
+    const dim3 grid((unsigned)((waves + 3) / 4));
+    {
+        ProfScope ps(c, st, "update_parity", g.Mu * S * 8);
+        if (V == 4) launch_parity_v<4>(T, pa, grid, st);
+        else if (V == 2) launch_parity_v<2>(T, pa, grid, st);
+        else launch_parity_v<1>(T, pa, grid, st);
+        UPD_TRY(hipGetLastError());
+    }
+    return FASTECC_OK;
+}
+
+int update_args(fastecc_ctx* c, const void* data, const void* parity, const uint64_t* blocks, uint64_t count, const void* old_blocks, const void* new_blocks,
+                int mem_kind, bool with_data)
+{
+    if (!c) return FASTECC_E_INVAL;
+    if (count > 0 && (!parity || !blocks || !new_blocks || (with_data && !data))) return FASTECC_E_INVAL;
+    if ((((uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks) & 3u) != 0) return FASTECC_E_INVAL;
+    if (mem_kind != FASTECC_MEM_HOST && mem_kind != FASTECC_MEM_DEVICE && mem_kind != FASTECC_MEM_HOST_PINNED) return FASTECC_E_INVAL;
+    if (c->sharded || c->p61 || c->field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
+    if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;
+    if (mem_kind != FASTECC_MEM_DEVICE) return FASTECC_E_UNSUPPORTED;
+    if (count == 0) return FASTECC_OK;
+    std::vector<uint64_t> sorted(blocks, blocks + count);
+    std::sort(sorted.begin(), sorted.end());
+    if (sorted.back() >= c->K) return FASTECC_E_INVAL;
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return FASTECC_E_INVAL;  // a duplicate index
+    return FASTECC_OK;
+}
+
+int update_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const uint64_t* blocks, uint64_t count, const uint32_t* old_blocks, const uint32_t* new_blocks,
+               hipStream_t st)
+{
+    UpdateState* s = nullptr;
+    int rc = update_state(c, &s);
+    if (rc != FASTECC_OK) return rc;
+    if (!s->d_delta) UPD_TRY(hipMalloc((void**)&s->d_delta, (size_t)ROWS * c->S * 4));
+    rc = update_table(c, s, st);
+    if (rc != FASTECC_OK) return rc;
+    return with_internal_buffers(c, st, [&]() -> int {
+        for (uint64_t r0 = 0; r0 < count; r0 += ROWS) {
+            const uint32_t rows = (uint32_t)std::min<uint64_t>(ROWS, count - r0);
+            const size_t off = (size_t)r0 * c->S;
+            const int r = update_pass(c, s, data, parity, blocks + r0, rows, old_blocks ? old_blocks + off : nullptr, new_blocks + off, st);
+            if (r != FASTECC_OK) return r;
+        }
+        return FASTECC_OK;
+    });
+}
+
+template <class F> int guarded(F body)
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return FASTECC_E_NOMEM;
+    } catch (...) {
+        return FASTECC_E_DEVICE;
+    }
+}
+
+}  // namespace
+
+}  // namespace fastecc
+
+using namespace fastecc;
+
+extern "C" {
+
+int fastecc_update(fastecc_ctx* c, void* data, void* parity, const uint64_t* blocks, uint64_t count, const void* new_blocks, int mem_kind, void* stream)
+{
+    return guarded([&]() -> int {
+        int rc = update_args(c, data, parity, blocks, count, nullptr, new_blocks, mem_kind, true);
+        if (rc != FASTECC_OK || count == 0) return rc;
+        DeviceGuard dg(c->device);
+        if (!dg.ok) return FASTECC_E_DEVICE;
+        CallLock lk(c->mu);
+        return update_run(c, (uint32_t*)data, (uint32_t*)parity, blocks, count, nullptr, (const uint32_t*)new_blocks, (hipStream_t)stream);
+    });
+}
+
+int fastecc_update_parity(fastecc_ctx* c, void* parity, const uint64_t* blocks, uint64_t count, const void* old_blocks, const void* new_blocks, int mem_kind,
+                          void* stream)
+{
+    return guarded([&]() -> int {
+        int rc = update_args(c, nullptr, parity, blocks, count, old_blocks, new_blocks, mem_kind, false);
+        if (rc != FASTECC_OK || count == 0) return rc;
+        DeviceGuard dg(c->device);
+        if (!dg.ok) return FASTECC_E_DEVICE;
+        CallLock lk(c->mu);
+        return update_run(c, nullptr, (uint32_t*)parity, blocks, count, (const uint32_t*)old_blocks, (const uint32_t*)new_blocks, (hipStream_t)stream);
+    });
+}
+
+int fastecc_code_coefficient(uint64_t n, uint64_t k, unsigned flags, uint64_t data_block, uint64_t parity_block, uint32_t* out)
+{
+    if (!out) return FASTECC_E_INVAL;
+    CodeGeom g;
+    const int rc = geom_of_code(n, k, flags, &g);
+    if (rc != FASTECC_OK) return rc;
+    if (data_block >= g.K || parity_block >= g.Mu) return FASTECC_E_INVAL;
+    *out = geom_weight(g, data_block, parity_block);
+    return FASTECC_OK;
+}
+
+}  // extern "C"

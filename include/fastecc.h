@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 300 /* 0.3.0: error detection and location (fastecc_verify / _locate_errors / _correct) */
+#define FASTECC_VERSION 310 /* 0.3.1: incremental parity update for small writes (fastecc_update / _update_parity) */
 
 enum {
     FASTECC_OK = 0,
@@ -354,6 +354,32 @@ int fastecc_locate_errors(fastecc_ctx *ctx, const void *data, const void *parity
                           uint64_t *blocks, uint64_t cap, uint64_t *count);
 int fastecc_correct(fastecc_ctx *ctx, void *data, void *parity, int mem_kind, void *stream, uint64_t seed, uint64_t *blocks,
                     uint64_t cap, uint64_t *count);
+
+/*
+ * Small writes: bring the parity up to date after `count` data blocks changed, without reading the rest of the stripe.  The code is
+ * linear, so the new parity is the old one plus the weighted changes; the weight of data block i in parity block q is the generator-
+ * matrix entry fastecc_code_coefficient gives.  One read-modify-write pass over the parity per 16 changed blocks; the rest of the
+ * data is never touched.
+ *   fastecc_update        : data is the whole k-block stripe.  Reads the old content of data[blocks[u]], adds its change to parity
+ *                           and writes new_blocks[u] (count blocks, contiguous) into the stripe.  Afterwards data and parity are
+ *                           exactly what fastecc_encode of the new stripe gives.
+ *   fastecc_update_parity : the data blocks live elsewhere: old_blocks and new_blocks are count contiguous blocks each; old_blocks ==
+ *                           NULL means zero blocks (incremental encoding: zero the parity, then add blocks as they arrive).
+ * Every GF(0xFFF00001) code of fastecc_create / fastecc_create_ex, FASTECC_MEM_DEVICE only.  blocks: a host array of distinct indices
+ * < k in any order (it may be reused as soon as the call returns); count = 0 is a no-op and there is no upper limit.  Enqueued on
+ * `stream` without synchronising, the first call included (its weight table is built by a kernel on `stream`).  Inputs must be < p;
+ * new_blocks / old_blocks must not overlap data or parity.  FASTECC_E_INVAL (before any device work): null pointers with count > 0,
+ * an index >= k, a duplicate index, pointers that are not 4-byte aligned.  FASTECC_E_UNSUPPORTED: GF((2^61-1)^2), sharded contexts,
+ * a set "row_pitch_words", host memory.  At (2^20, 2^19) x 4 KB an update is cheaper than a fresh fastecc_encode up to 40 changed blocks and dearer at 64.
+ */
+int fastecc_update(fastecc_ctx *ctx, void *data, void *parity, const uint64_t *blocks, uint64_t count, const void *new_blocks,
+                   int mem_kind, void *stream);
+int fastecc_update_parity(fastecc_ctx *ctx, void *parity, const uint64_t *blocks, uint64_t count, const void *old_blocks,
+                          const void *new_blocks, int mem_kind, void *stream);
+/* Host only, no device: the code's generator-matrix entry L_i(y_q) for data block i and parity block q of the (n,k) code that
+ * fastecc_create_ex(n, k, ..., flags) builds over GF(0xFFF00001), plain form in [0,p): parity block q = sum_i L_i(y_q) data block i.
+ * FASTECC_E_INVAL for a null out, an index out of range or unknown flags; FASTECC_E_UNSUPPORTED for a code fastecc_create_ex refuses. */
+int fastecc_code_coefficient(uint64_t n, uint64_t k, unsigned flags, uint64_t data_block, uint64_t parity_block, uint32_t *out);
 
 /*
  * Data packing (GF.md:72-104 "Efficient data packing", README.md:160-163): RS.cpp only encodes words < p, so
