@@ -96,6 +96,8 @@ def lib():
     L.fastecc_decode_prepare.argtypes, L.fastecc_decode_prepare.restype = [vp, u8p, u8p], i32
     L.fastecc_decode.argtypes, L.fastecc_decode.restype = [vp, vp, vp, i32, vp], i32
     L.fastecc_repair.argtypes, L.fastecc_repair.restype = [vp, vp, vp, i32, vp], i32
+    L.fastecc_decode_batch.argtypes, L.fastecc_decode_batch.restype = [vp, vp, vp, u64, vp], i32
+    L.fastecc_repair_batch.argtypes, L.fastecc_repair_batch.restype = [vp, vp, vp, u64, vp], i32
     L.fastecc_verify.argtypes, L.fastecc_verify.restype = [vp, vp, vp, i32, vp, u64, ctypes.POINTER(i32)], i32
     for name in ("locate_errors", "correct"):
         f = getattr(L, "fastecc_" + name)
@@ -263,6 +265,26 @@ class Encoder:
     def repair(self, data, parity, stream=0, mem=MEM_DEVICE):
         """decode, then rebuild the erased parity blocks as well (both buffers are written where blocks were lost)."""
         _check(lib().fastecc_repair(self._h, _addr(data), _addr(parity), mem, stream or None), "fastecc_repair")
+        return data, parity
+
+    @staticmethod
+    def _batch_count(count):
+        if isinstance(count, bool) or not isinstance(count, int):
+            raise TypeError("count must be an int")
+        if count < 1 or count >= 1 << 64:
+            raise ValueError("count must be in [1, 2^64)")
+        return count
+
+    def decode_batch(self, data, parity, count, stream=0):
+        """`count` stripes back to back in device memory, all with the prepared erasure pattern: decode of each (parity is read only)."""
+        count = self._batch_count(count)
+        _check(lib().fastecc_decode_batch(self._h, _addr(data), _addr(parity), count, stream or None), "fastecc_decode_batch")
+        return data
+
+    def repair_batch(self, data, parity, count, stream=0):
+        """repair of `count` stripes back to back in device memory, all with the prepared erasure pattern."""
+        count = self._batch_count(count)
+        _check(lib().fastecc_repair_batch(self._h, _addr(data), _addr(parity), count, stream or None), "fastecc_repair_batch")
         return data, parity
 
     def verify(self, data, parity, seed=0, stream=0, mem=MEM_DEVICE):

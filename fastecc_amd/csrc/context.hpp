@@ -163,6 +163,7 @@ struct fastecc_ctx {
     int decode_split = 1;         // (2k,k) codes: 1 = the decoder's transform as two half-size ones (decode.hip, "even / odd split"), 0 = one of size 2k
     int decode_direct_max = 256;  // up to this many lost blocks are recomputed directly (direct.hip), 0 = always the transform; 96 without the MFMA kernel
     int direct_kernel = 0;        // 0 choose, 1 VALU, 2 MFMA
+    int decode_batch_kernel = 0;  // fastecc_decode_batch / _repair_batch: 0 choose, 1 one launch per pass whenever it can, 2 stripe by stripe
     int slab_mode = 0;       // how `slabs` > 1 are scheduled (fastecc_set_option "slab_mode")
     int slabs = 1;           // > 1: encode in this many column slabs on internal streams, staggered by one pass,
                              // so the VALU-bound MID of one slab runs beside the HBM-bound outer passes of others

@@ -1403,6 +1403,8 @@ int fastecc_repair(fastecc_ctx* c, void* data, void* parity, int mem_kind, void*
     }
 }
 
+static int decode_locked(fastecc_ctx* c, CallScope& call, void* data, const void* parity, int mem_kind, void* stream, void* parity_out);
+
 // parity_out != null (== parity): also rebuild the lost parity blocks from the repaired data
 static int decode_impl(fastecc_ctx* c, void* data, const void* parity, int mem_kind, void* stream, void* parity_out)
 {
@@ -1411,6 +1413,12 @@ static int decode_impl(fastecc_ctx* c, void* data, const void* parity, int mem_k
     if (mem_kind == FASTECC_MEM_HOST_PINNED) mem_kind = FASTECC_MEM_HOST;  // the same staging; the copies are simply faster from pinned memory
     if (mem_kind != FASTECC_MEM_HOST && mem_kind != FASTECC_MEM_DEVICE) return FASTECC_E_INVAL;
     CallScope call(c);
+    return decode_locked(c, call, data, parity, mem_kind, stream, parity_out);
+}
+
+// one stripe, the context's call lock held (fastecc_decode_batch runs the transform path through this, stripe by stripe)
+static int decode_locked(fastecc_ctx* c, CallScope& call, void* data, const void* parity, int mem_kind, void* stream, void* parity_out)
+{
     if (info_of(c).field == FASTECC_FIELD_GF_P61_SQUARED) {
         if ((((uintptr_t)data | (uintptr_t)parity) & 15u)) return FASTECC_E_INVAL;
         p61::Decoder* d61 = decoder61_of(c);
@@ -1777,6 +1785,103 @@ static int decode_impl(fastecc_ctx* c, void* data, const void* parity, int mem_k
         }
         DEC_TRY(hipStreamSynchronize(st));
     }
+    return FASTECC_OK;
+}
+
+static int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream, bool repair);
+
+int fastecc_decode_batch(fastecc_ctx* c, void* data, const void* parity, uint64_t count, void* stream)
+{
+    try {
+        return decode_batch_impl(c, data, const_cast<void*>(parity), count, stream, false);
+    } catch (const std::bad_alloc&) {
+        return FASTECC_E_NOMEM;
+    } catch (...) {
+        return FASTECC_E_DEVICE;
+    }
+}
+
+int fastecc_repair_batch(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream)
+{
+    try {
+        return decode_batch_impl(c, data, parity, count, stream, true);
+    } catch (const std::bad_alloc&) {
+        return FASTECC_E_NOMEM;
+    } catch (...) {
+        return FASTECC_E_DEVICE;
+    }
+}
+
+// `count` stripes back to back in device memory, all with the prepared pattern.  The direct path runs each of its passes over the whole batch in
+// one launch (direct_run_batch) when the pass has fewer than 4096 rows (from 4096 data rows on, the single-stripe path takes the matrix cores) and
+// the batch gives at least one wave per SIMD; otherwise (option "decode_batch_kernel" decides when set) direct_run stripe by stripe.  Patterns of
+// the transform path: the single-stripe decode, stripe by stripe.
+static int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream, bool repair)
+{
+    if (!c || !data || !parity || count == 0 || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
+    if (sharded_of(c)) return FASTECC_E_UNSUPPORTED;
+    CallScope call(c);
+    const CtxInfo ci = info_of(c);
+    if (ci.field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
+    if (ci.pitch != ci.words) return FASTECC_E_UNSUPPORTED;  // stripes of a batch are contiguous
+    const uint64_t block = ci.words * 4, data_bytes = ci.user_k * block, parity_bytes = ci.user_m * block;
+    if (count > UINT64_MAX / data_bytes || count > UINT64_MAX / parity_bytes) return FASTECC_E_INVAL;
+    if ((uint64_t)(uintptr_t)data > UINT64_MAX - count * data_bytes || (uint64_t)(uintptr_t)parity > UINT64_MAX - count * parity_bytes) return FASTECC_E_INVAL;
+    DecodeState* d = decoder_of(c);
+    if (!d || !d->ready) return FASTECC_E_INVAL;  // fastecc_decode_prepare first
+    const bool rebuild = repair && d->erased_parity != 0;
+    if (d->erased_data == 0 && !rebuild) return FASTECC_OK;
+    DeviceScope ds(ci.device);
+    if (!ds.ok) return FASTECC_E_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    if (!d->sub) {
+        // more losses than the direct path takes: correct, not faster than the caller's own loop
+        for (uint64_t b = 0; b < count; b++) {
+            char* pb = (char*)parity + b * parity_bytes;
+            const int rc = decode_locked(c, call, (char*)data + b * data_bytes, pb, FASTECC_MEM_DEVICE, stream, repair ? pb : nullptr);
+            if (rc != FASTECC_OK) return rc;
+        }
+        return FASTECC_OK;
+    }
+    struct Marker {  // the passes' tables and partial sums are internal buffers: order their uses between streams
+        CallScope& s;
+        hipStream_t st;
+        ~Marker() { (void)s.end(st); }
+    };
+    {
+        const int rc0 = call.begin(st);
+        if (rc0 != FASTECC_OK) return rc0;
+    }
+    Marker marker{call, st};
+    const uint64_t S = ci.words, data_words = ci.user_k * S, parity_words = ci.user_m * S;
+    uint32_t* ddata = (uint32_t*)data;
+    uint32_t* dparity = (uint32_t*)parity;
+    auto pass = [&](DirectPass* p, const uint32_t* par_in, uint32_t* data_to, uint32_t* par_to) -> int {
+        const uint64_t rows = (uint64_t)direct_pass_rows(p);
+        const int mode = ci.decode_batch_kernel;
+        const bool batched = mode == 1 || (mode == 0 && d->direct_kernel != 2 && rows < 4096 && direct_batch_waves(p, ddata, dparity, S, count) >= 1024);
+        if (batched) {
+            const uint64_t outputs = (data_to ? (uint64_t)d->sub_lost_data : 0) + (par_to ? (uint64_t)d->sub_lost_parity : 0);
+            void* scope = profile_scope_begin(c, st, "direct_pass_batch", count * (rows + outputs) * block);
+            const int rc = direct_run_batch(p, ddata, par_in, data_to, par_to, S, count, data_words, parity_words, st);
+            profile_scope_end(scope);
+            return rc;
+        }
+        void* scope = profile_scope_begin(c, st, "direct_pass", count * (ci.user_k + (uint64_t)d->sub_lost_data) * block);
+        int rc = FASTECC_OK;
+        for (uint64_t b = 0; b < count && rc == FASTECC_OK; b++)
+            rc = direct_run(p, ddata + b * data_words, par_in ? par_in + b * parity_words : nullptr, data_to ? data_to + b * data_words : nullptr,
+                            par_to ? par_to + b * parity_words : nullptr, (uint32_t)S, d->direct_kernel, st);
+        profile_scope_end(scope);
+        return rc;
+    };
+    // the pass sequence of decode_impl
+    if (d->sub_both && (rebuild || d->sub_only_both)) return pass(d->direct_both, dparity, ddata, rebuild ? dparity : nullptr);
+    if (d->sub_lost_data > 0) {
+        const int rc = pass(d->direct_data, dparity, ddata, nullptr);
+        if (rc != FASTECC_OK) return rc;
+    }
+    if (rebuild) return pass(d->direct_parity, nullptr, nullptr, dparity);
     return FASTECC_OK;
 }
 

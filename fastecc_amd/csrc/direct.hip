@@ -826,6 +826,145 @@ int direct_run(DirectPass* p, const uint32_t* data, const uint32_t* parity, uint
 }
 
 // ------------------------------------------------------------------------------------------------
+// MANY STRIPES, ONE PATTERN (fastecc_decode_batch / _repair_batch).  A block's weight depends on its row and output only, so one pass's
+// tables serve every stripe of a batch.  The batch is count x S word columns, flattened: lane g holds the V words g*V .. g*V+V-1, i.e.
+// stripe b = gV / S, column c = gV % S — full waves at any block size, even below 64 words.  Each lane sums ALL rows of its stripe for
+// EB outputs, reduces once and stores canonical words straight to the output rows: one launch, no partial sums, no reduce kernels.
+// Exact for any rows <= 2^32: every term x * w is < 2^64 and hi counts the carries out of lo.
+// In place: data is read and written (lost data rows are read with weight 0 while this or another sweep writes them: x * 0 = 0), hence
+// no __restrict__ on the stripes.
+// ------------------------------------------------------------------------------------------------
+struct BatchArgs {
+    const uint32_t* data;     // stripe b's data rows at data + b * data_stride
+    const uint32_t* parity;   // ... its parity rows at parity + b * parity_stride (rows data_rows.. read parity row extra[u - data_rows])
+    const uint32_t* extra;
+    const uint32_t* coef;     // the pass's table (coef_index layout), Montgomery form
+    const uint32_t* pos;      // outputs: data row pos >> 1 (even) or parity row pos >> 1 (odd)
+    uint32_t* data_out;       // null: data outputs are skipped (the same strides as data / parity)
+    uint32_t* parity_out;     // null: parity outputs are skipped
+    uint64_t data_stride, parity_stride;
+    uint64_t groups;          // count * S / V
+    uint64_t group_base;      // the launch's first group (batches of more than 2^30 groups take several launches)
+    uint32_t S, rows, data_rows, pad, outputs;
+};
+
+template <int EB, int V>
+__global__ __launch_bounds__(256) void direct_batch_kernel(const BatchArgs a)
+{
+    constexpr int U = EB >= 16 ? 2 : EB >= 8 ? 4 : 8;  // rows in flight; U * EB <= 32 weights live in SGPRs (at 64, with the stripe addressing, SGPRs spilled into the row loop)
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t sweep = blockIdx.y;
+    const uint32_t cstride = a.pad <= 16u ? a.pad : 16u;
+    const_u32_ptr coef = as_constant(a.coef) + (size_t)sweep * a.rows * 16u;
+    {
+        const uint64_t g = a.group_base + ((uint64_t)blockIdx.x * 4u + wave) * 64u + lane;
+        const bool live = g < a.groups;
+        const uint64_t word = live ? g * V : 0, b = word / a.S, c = word - b * a.S;
+        const uint32_t* dbase = a.data + b * a.data_stride + c;
+        const uint64_t poff = b * a.parity_stride + c;  // (a lane's parity rows: a.parity + poff + row * S)
+        uint64_t lo[EB][V];
+        uint32_t hi[EB][V];
+#pragma unroll
+        for (int j = 0; j < EB; ++j)
+#pragma unroll
+            for (int v = 0; v < V; ++v) lo[j][v] = 0, hi[j][v] = 0;
+        for (uint32_t ub = 0; ub < a.rows; ub += U) {
+            uint32_t w[U][EB], x[U][V];
+#pragma unroll
+            for (int i = 0; i < U; ++i) {
+                const uint32_t u = ub + i;
+                const bool in = u < a.rows;  // wave-uniform
+#pragma unroll
+                for (int j = 0; j < EB; ++j) w[i][j] = 0;
+                if (in) {
+                    const_u32_ptr cf = coef + (size_t)u * cstride;
+#pragma unroll
+                    for (int j = 0; j < EB; ++j) w[i][j] = cf[j];
+                }
+#pragma unroll
+                for (int v = 0; v < V; ++v) x[i][v] = 0;
+                if (in && live) {
+                    const uint32_t* row = u < a.data_rows ? dbase + (size_t)u * a.S : a.parity + poff + (size_t)as_constant(a.extra)[u - a.data_rows] * a.S;
+                    load_vec<V>(x[i], row);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < U; ++i)
+#pragma unroll
+                for (int j = 0; j < EB; ++j)
+#pragma unroll
+                    for (int v = 0; v < V; ++v) mac96(lo[j][v], hi[j][v], x[i][v], w[i][j]);
+        }
+#pragma unroll
+        for (int j = 0; j < EB; ++j) {
+            const uint32_t t = sweep * EB + j;
+            if (t >= a.outputs) break;  // wave-uniform
+            const uint32_t p = as_constant(a.pos)[t];
+            uint32_t* out = (p & 1u) ? a.parity_out : a.data_out;
+            if (!out || !live) continue;  // (no stripe given for that kind of output: fastecc_decode_batch on a pass that also holds the lost parity blocks)
+            const uint64_t stride = (p & 1u) ? a.parity_stride : a.data_stride;
+            uint32_t r[V];
+#pragma unroll
+            for (int v = 0; v < V; ++v) r[v] = reduce96(lo[j][v], hi[j][v]);
+            store_vec<V>(out + b * stride + (size_t)(p >> 1) * a.S + c, r);
+        }
+    }
+}
+
+int direct_pass_rows(const DirectPass* p) { return p && p->built ? (int)p->rows : 0; }
+
+static int batch_vec(const DirectPass* p, const void* data, const void* parity, uint64_t S)
+{
+    const int eb = std::min(p->pad, 16), vmax = eb <= 4 ? 4 : eb == 8 ? 2 : 1;
+    const uintptr_t align = (uintptr_t)data | (uintptr_t)parity;
+    int v = vmax;
+    while (v > 1 && ((S % v) != 0 || (align & (4u * v - 1u)) != 0)) v >>= 1;
+    return v;
+}
+
+uint64_t direct_batch_waves(const DirectPass* p, const void* data, const void* parity, uint64_t S, uint64_t count)
+{
+    if (!p || !p->built) return 0;
+    const uint64_t v = (uint64_t)batch_vec(p, data, parity, S), sweeps = p->pad > 16 ? (uint64_t)p->pad / 16u : 1u;
+    return (count * S / v + 63u) / 64u * sweeps;
+}
+
+int direct_run_batch(DirectPass* p, const uint32_t* data, const uint32_t* parity, uint32_t* data_out, uint32_t* parity_out, uint64_t S, uint64_t count,
+                     uint64_t data_stride, uint64_t parity_stride, hipStream_t st)
+{
+    if (!p || !p->built || S == 0 || S > 0xFFFFFFFFull || count == 0) return FASTECC_E_INVAL;
+    const int pad = p->pad, sweeps = pad > 16 ? pad / 16 : 1, eb = std::min(pad, 16);
+    // every pointer a lane touches: the stripes it reads and the ones it writes (data_out / parity_out are data / parity or null)
+    const int v = batch_vec(p, (const void*)((uintptr_t)data | (uintptr_t)data_out), (const void*)((uintptr_t)parity | (uintptr_t)parity_out), S);
+    BatchArgs a{data, parity, p->lists, p->coef, p->lists + DIRECT_CAP, data_out, parity_out, data_stride, parity_stride, count * S / (uint64_t)v, 0,
+                (uint32_t)S, p->rows, p->data_rows, (uint32_t)pad, (uint32_t)p->outputs};
+    // a dispatch holds fewer than 2^32 work-items per dimension: at most 2^22 workgroups (2^30 groups) per launch
+    constexpr uint64_t LAUNCH_GROUPS = 1ull << 30;
+    for (a.group_base = 0; a.group_base < a.groups; a.group_base += LAUNCH_GROUPS) {
+    const dim3 grid((unsigned)((std::min(a.groups - a.group_base, LAUNCH_GROUPS) + 255u) / 256u), (unsigned)sweeps);
+#define FASTECC_BATCH(EB, V) hipLaunchKernelGGL((direct_batch_kernel<EB, V>), grid, dim3(256), 0, st, a)
+    switch (eb * 8 + v) {
+        case 1 * 8 + 4: FASTECC_BATCH(1, 4); break;
+        case 1 * 8 + 2: FASTECC_BATCH(1, 2); break;
+        case 1 * 8 + 1: FASTECC_BATCH(1, 1); break;
+        case 2 * 8 + 4: FASTECC_BATCH(2, 4); break;
+        case 2 * 8 + 2: FASTECC_BATCH(2, 2); break;
+        case 2 * 8 + 1: FASTECC_BATCH(2, 1); break;
+        case 4 * 8 + 4: FASTECC_BATCH(4, 4); break;
+        case 4 * 8 + 2: FASTECC_BATCH(4, 2); break;
+        case 4 * 8 + 1: FASTECC_BATCH(4, 1); break;
+        case 8 * 8 + 2: FASTECC_BATCH(8, 2); break;
+        case 8 * 8 + 1: FASTECC_BATCH(8, 1); break;
+        default: FASTECC_BATCH(16, 1); break;
+    }
+    }
+#undef FASTECC_BATCH
+    DIR_TRY(hipGetLastError());
+    return FASTECC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // ENCODING when a code has few parity blocks: with the data points x_i = w_N^i the parity block j = f(y_j) = sum_i data_i * L_i(y_j),
 // y_j = w_2N^(odd): y_j^N = -1, so coef[i][j] = -2 x_i / (N (y_j - x_i)) — one read of the data instead of the three trips of the
 // transform pipeline.  Exactly the polynomial evaluation the transform computes (RS.cpp:40-63), hence the same parity bits.

@@ -66,6 +66,12 @@ int direct_build_interp(DirectPass* p, uint32_t wd, uint64_t N, uint32_t K, cons
                         const std::vector<uint32_t>* more_points = nullptr, const std::vector<uint32_t>* more_pos = nullptr);
 // kernel: 0 = choose, 1 = VALU (96-bit lazy accumulation), 2 = MFMA (i8 digits) when the stripes allow it
 int direct_run(DirectPass* p, const uint32_t* data, const uint32_t* parity, uint32_t* data_out, uint32_t* parity_out, uint32_t S, int kernel, hipStream_t st);
+// The same pass over `count` stripes in ONE launch (VALU, no partial sums): stripe b's rows at data + b * data_stride and parity + b * parity_stride
+// (words), its outputs at the same places of data_out / parity_out (each either the input stripe or null: that kind of output is skipped)
+int direct_run_batch(DirectPass* p, const uint32_t* data, const uint32_t* parity, uint32_t* data_out, uint32_t* parity_out, uint64_t S, uint64_t count,
+                     uint64_t data_stride, uint64_t parity_stride, hipStream_t st);
+uint64_t direct_batch_waves(const DirectPass* p, const void* data, const void* parity, uint64_t S, uint64_t count);  // waves of that launch, all sweeps
+int direct_pass_rows(const DirectPass* p);  // rows a pass reads (lost data rows included, at weight 0)
 bool direct_mfma_applies(const void* data, const void* parity, uint64_t words);
 // encoding straight from the Lagrange basis for codes with few parity blocks (n - k <= direct_encode_max())
 struct DirectEncode;
@@ -85,6 +91,7 @@ struct CtxInfo {
     int direct_kernel;         // 0 choose, 1 VALU, 2 MFMA (option "direct_kernel")
     int p61_stride;            // GF((2^61-1)^2) codes other than (2N,N): parity block j = block j * p61_stride of the (2N,N) parity
     int decode_split;          // option "decode_split"
+    int decode_batch_kernel;   // option "decode_batch_kernel": 0 choose, 1 the batched kernel, 2 stripe by stripe
 };
 CtxInfo info_of(const fastecc_ctx* c);
 DecodeState*& decoder_of(fastecc_ctx* c);

@@ -113,6 +113,11 @@ int fastecc_set_option(fastecc_ctx* c, const char* name, int value)
         c->direct_kernel = value;
         return FASTECC_OK;
     }
+    if (!strcmp(name, "decode_batch_kernel")) {  // fastecc_decode_batch / _repair_batch, at call time: 0 = choose, 1 = batched kernel, 2 = stripe by stripe
+        if (value < 0 || value > 2) return FASTECC_E_INVAL;
+        c->decode_batch_kernel = value;
+        return FASTECC_OK;
+    }
     if (!strcmp(name, "fuse_radix")) {  // mixed-radix contexts: 1 = odd-radix level fused into the outer tiles (default), 0 = its own passes
         if (value < 0 || value > 1) return FASTECC_E_INVAL;
         if (c->fuse_radix == value) return FASTECC_OK;

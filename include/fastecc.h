@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 310 /* 0.3.1: incremental parity update for small writes (fastecc_update / _update_parity) */
+#define FASTECC_VERSION 320 /* 0.3.2: batched decode and repair of many stripes with one erasure pattern (fastecc_decode_batch / _repair_batch) */
 
 enum {
     FASTECC_OK = 0,
@@ -316,6 +316,23 @@ int fastecc_decode(fastecc_ctx *ctx, void *data, const void *parity, int mem_kin
 /* fastecc_decode, then the erased PARITY blocks as well: the repaired data is encoded once more and the lost parity blocks
  * (only those) are written into `parity` — the whole codeword is whole again ("repair").  Same arguments otherwise. */
 int fastecc_repair(fastecc_ctx *ctx, void *data, void *parity, int mem_kind, void *stream);
+/*
+ * Many stripes, one erasure pattern (rebuilding a failed device: every stripe lost the same blocks).  Same result as `count` calls of
+ * fastecc_decode / fastecc_repair with FASTECC_MEM_DEVICE, using the pattern of the last fastecc_decode_prepare for every stripe.
+ * Stripes lie back to back in DEVICE memory: stripe b's k data blocks at data + b*k*block_bytes, its n - k parity blocks at
+ * parity + b*(n-k)*block_bytes (for (2k,k) codes the layout of fastecc_encode_batch).  Only erased blocks are written;
+ * fastecc_decode_batch leaves erased parity blocks alone.  Enqueued on `stream`, no synchronisation.  Every GF(0xFFF00001) code
+ * fastecc_decode takes on device memory: (2k,k), n = k + N/2^d, n = 4k / 8k, zero-extended (n,k), mixed radix.
+ *   - Patterns of the direct path (at most "decode_direct_max" losses) run each pass over ALL stripes in one launch when the pass reads fewer than
+ *     4096 blocks and the batch fills the GPU (count * block_bytes / 4 words make at least 1024 waves of 64 lanes); otherwise direct pass by direct
+ *     pass, stripe by stripe.  Option "decode_batch_kernel" (0 = choose, 1 = the batched kernel always, 2 = stripe by stripe), at call time.
+ *   - Patterns of the transform path (more losses) are decoded stripe by stripe: correct, but no faster than the caller's own loop.
+ * FASTECC_E_INVAL: null or misaligned (not 4-byte) pointers, count == 0, byte sizes beyond 64 bits, no prepared pattern.
+ * FASTECC_E_UNSUPPORTED: GF((2^61-1)^2), sharded contexts, a set "row_pitch_words".  A refused call does no device work and writes
+ * nothing.  A pattern with nothing to do (no lost data for decode, no lost block for repair) returns FASTECC_OK at once.
+ */
+int fastecc_decode_batch(fastecc_ctx *ctx, void *data, const void *parity, uint64_t count, void *stream);
+int fastecc_repair_batch(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, void *stream);
 
 /*
  * Error detection and location ("scrub"): find blocks that are present but wrong — bit rot, torn or misdirected writes — which
@@ -470,6 +487,8 @@ const char *fastecc_plan_string(fastecc_ctx *ctx);
  *                  k = 2^19 x 4 KB and 2 % lost, 72 ms = 1.14 x the encode at 64 KB blocks; patterns it does not take run the folded 2k-point transform;
  *   "direct_kernel" = 0 / 1 / 2 (default 0 = choose): the kernel of those direct paths — 1 = VALU (96-bit lazy accumulation, any rows),
  *                  2 = MFMA (i8 digits; falls back to 1 where it cannot run).  Same bits either way;
+ *   "decode_batch_kernel" = 0 / 1 / 2 (default 0 = choose; at call time): how fastecc_decode_batch / _repair_batch run a direct-path pass — 1 = one
+ *                  launch over all stripes whenever the pass allows it, 2 = stripe by stripe (direct_kernel then picks the kernel).  Same bits either way;
  *   "fuse_radix" = 0 / 1 (default 1; mixed-radix contexts): the odd-radix level fused into the outer tile passes, or as its own passes;
  *   "slabs" = H (1..32): encode H column slabs of the stripe on internal streams, each one pass
  * behind the previous, so that different kinds of passes overlap on the GPU, or with "slab_mode" = 1 one
