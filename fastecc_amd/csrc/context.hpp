@@ -186,12 +186,6 @@ struct fastecc_ctx {
 namespace fastecc {
 
 extern thread_local char g_detail[256];  // fastecc_last_error_detail
-int hip_fail(hipError_t e, const char* what);
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t e_ = (expr);                         \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-    } while (0)
 
 int ilog2_exact(uint64_t v);
 uint32_t bitrev_host(uint32_t v, int bits);
@@ -211,20 +205,5 @@ enum { TW_ENC_DIF = 0, TW_ENC_DIT = 1, TW_NTT_FWD = 2, TW_NTT_INV = 3, TW_FOLD_D
 const uint32_t* twiddle_table(fastecc_ctx* c, int which, hipStream_t st);
 
 using CallLock = std::lock_guard<std::mutex>;
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 
 }  // namespace fastecc

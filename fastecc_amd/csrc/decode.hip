@@ -38,6 +38,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <vector>
 
@@ -142,38 +143,23 @@ struct DecodeState {
 void destroy_decode_state(DecodeState* d)
 {
     if (!d) return;
-    if (d->transform) fastecc_destroy(d->transform);
-    if (d->transform_full) fastecc_destroy(d->transform_full);
-    if (d->split) fastecc_destroy(d->split);
-    for (fastecc_ctx* sc : d->split_small)
-        if (sc) fastecc_destroy(sc);
-    if (d->split_small_buf) (void)hipFree(d->split_small_buf);
-    for (uint32_t* b : {d->split_order, d->split_rows_data, d->split_rows_parity, d->split_rows_out, d->split_pos_parity, d->split_impulse, d->split_r1, d->split_r2, d->split_r0, d->split_q2, d->split_pos_data_odd,
-                        d->split_rows_out_parity})
-        if (b) (void)hipFree(b);
-    if (d->gout_par) (void)hipFree(d->gout_par);
-    if (d->dev_present) (void)hipFree(d->dev_present);
-    if (d->dev_counts) (void)hipFree(d->dev_counts);
-    if (d->recovered_full) (void)hipFree(d->recovered_full);
-    if (d->pattern_ntt) fastecc_destroy(d->pattern_ntt);
-    if (d->pattern_buf) (void)hipFree(d->pattern_buf);
+    for (fastecc_ctx* x : {d->transform, d->transform_full, d->split, d->pattern_ntt, d->tree_top})
+        if (x) fastecc_destroy(x);
+    for (fastecc_ctx* x : d->split_small)
+        if (x) fastecc_destroy(x);
+    for (fastecc_ctx* x : d->tree_ctx)
+        if (x) fastecc_destroy(x);
     if (d->fin_first_pass && d->fin_first_pass != d->fin) (void)hipFree(d->fin_first_pass);
-    if (d->fin) (void)hipFree(d->fin);
-    if (d->srcmap) (void)hipFree(d->srcmap);
-    if (d->gout) (void)hipFree(d->gout);
-    if (d->recovered) (void)hipFree(d->recovered);
-    if (d->parity_dev) (void)hipFree(d->parity_dev);
-    if (d->lost_rows_dev) (void)hipFree(d->lost_rows_dev);
-    if (d->pack_dev) (void)hipFree(d->pack_dev);
+    for (void* b : std::initializer_list<void*>{d->split_small_buf, d->split_order, d->split_rows_data, d->split_rows_parity, d->split_rows_out, d->split_pos_parity,
+                                                d->split_impulse, d->split_r1, d->split_r2, d->split_r0, d->split_q2, d->split_pos_data_odd, d->split_rows_out_parity,
+                                                d->gout_par, d->dev_present, d->dev_counts, d->recovered_full, d->pattern_buf, d->fin, d->srcmap, d->gout, d->recovered,
+                                                d->parity_dev, d->lost_rows_dev, d->pack_dev, d->parity_lost, d->parity_again, d->tree_x, d->tree_f, d->tree_y, d->tree_p,
+                                                d->wpow, d->roots, d->dev_state, d->dev_erased, d->tile_order})
+        if (b) (void)hipFree(b);
     if (d->pack_host) (void)hipHostFree(d->pack_host);
-    for (fastecc_ctx* t : d->tree_ctx)
-        if (t) fastecc_destroy(t);
-    if (d->tree_top) fastecc_destroy(d->tree_top);
     direct_pass_free(d->direct_data);
     direct_pass_free(d->direct_parity);
     direct_pass_free(d->direct_both);
-    for (uint32_t* b : {d->parity_lost, d->parity_again, d->tree_x, d->tree_f, d->tree_y, d->tree_p, d->wpow, d->roots, d->dev_state, d->dev_erased, d->tile_order})
-        if (b) (void)hipFree(b);
     delete d;
 }
 
@@ -674,12 +660,6 @@ __global__ __launch_bounds__(256) void restore_parity_kernel(const uint32_t* __r
     store_vec<V>(parity + (size_t)q * S + col, x);
 }
 
-int hip_code(const char* what, hipError_t e)
-{
-    set_error_detail(what, e);
-    return e == hipErrorOutOfMemory ? FASTECC_E_NOMEM : FASTECC_E_DEVICE;
-}
-
 // FASTECC_TRACE_PREPARE=1: wall-clock of the phases of fastecc_decode_prepare on stderr (where does a first call spend its time)
 struct PhaseTimer {
     bool on = getenv("FASTECC_TRACE_PREPARE") != nullptr;
@@ -693,430 +673,521 @@ struct PhaseTimer {
     }
 };
 
-#define DEC_TRY(expr)                                      \
-    do {                                                   \
-        hipError_t e_ = (expr);                            \
-        if (e_ != hipSuccess) return hip_code(#expr, e_);  \
-    } while (0)
+dim3 grid_of(uint64_t items) { return dim3((unsigned)((items + 255) / 256)); }  // one thread per item, 256 per workgroup
 
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-}  // namespace
-
-}  // namespace fastecc
-
-using namespace fastecc;
-
-extern "C" {
-
-static int decode_prepare_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t* parity_present);
-
-// No exception crosses the ABI: the set-up and the host staging use std::vector; an allocation failure there is FASTECC_E_NOMEM (the call
-// locks of the context are scoped objects, so they are released on the way out).
-int fastecc_decode_prepare(fastecc_ctx* c, const uint8_t* data_present, const uint8_t* parity_present)
+// The row kernels above over `rows` rows of S words: one wave per (row, column chunk of 64 V words), V = 4 when S is a multiple of 4 and every
+// pointer in `ptrs` is 16-byte aligned, else 1.  `args` are the kernel's arguments but the last two (chunks per row, waves in all).
+template <class... K, class... A>
+void launch_rows(void (*k4)(K...), void (*k1)(K...), uint64_t rows, uint32_t S, std::initializer_list<const void*> ptrs, hipStream_t st, A... args)
 {
-    try {
-        return decode_prepare_impl(c, data_present, parity_present);
-    } catch (const std::bad_alloc&) {
-        return FASTECC_E_NOMEM;
-    } catch (...) {
-        return FASTECC_E_DEVICE;
-    }
+    uintptr_t bits = 0;
+    for (const void* p : ptrs) bits |= (uintptr_t)p;
+    const bool v4 = (S % 4) == 0 && (bits & 15u) == 0;
+    const uint32_t col_chunks = (S + (v4 ? 256 : 64) - 1) / (v4 ? 256 : 64);
+    const uint64_t items = rows * col_chunks;
+    hipLaunchKernelGGL(v4 ? k4 : k1, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, args..., col_chunks, items);
 }
 
-static int decode_prepare_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t* parity_present)
+// the context's decoder state, made at its first use (nullptr: no memory)
+DecodeState* state_of(fastecc_ctx* c)
 {
-    if (!c || !data_present || !parity_present) return FASTECC_E_INVAL;
-    if (sharded_of(c)) return sharded_decode_prepare(c, data_present, parity_present);
-    const CtxInfo ci = info_of(c);
-    if (ci.field == FASTECC_FIELD_GF_P61_SQUARED) {
-        // the 64-bit field has its own decoder (gf61_decode.hip); its contexts are (2k,k), (4k,k) or (8k,k) with k a power of two (and their zero-extended relatives)
-        int e61 = 1;
-        while ((1 << e61) < ci.cosets + 1) e61++;  // n = 4k / 8k: the same decoder on the (k << e)-th roots of unity (gf61_decode.hip)
-        DeviceScope ds61(ci.device);
-        if (!ds61.ok) return FASTECC_E_DEVICE;
-        CallScope call61(c);
-        {
-            const int rc0 = call61.wait_idle();  // a decode still using the previous pattern
-            if (rc0 != FASTECC_OK) return rc0;
-        }
-        char detail[160] = "";
-        // codes other than (2N,N): the decoder sees the (2N,N) codeword — data blocks beyond the caller's k are surviving zero blocks,
-        // parity positions the code does not use are lost (which is what limits the losses to n - k)
-        std::vector<uint8_t> dfull, pfull;
-        if (ci.zero_extended) {
-            dfull.assign(ci.k, 1);
-            pfull.assign(ci.k, 0);
-            for (uint64_t i = 0; i < ci.user_k; i++) dfull[i] = data_present[i] ? 1 : 0;
-            for (uint64_t q = 0; q < ci.user_m; q++) pfull[q * (uint64_t)ci.p61_stride] = parity_present[q] ? 1 : 0;
-            data_present = dfull.data();
-            parity_present = pfull.data();
-        }
-        const int rc = p61::decode_prepare(&decoder61_of(c), ci.log2k, ci.words / 4, data_present, parity_present, ci.direct_max, detail, sizeof detail, ci.decode_split, e61);
-        if (rc != FASTECC_OK && detail[0]) set_error_detail(detail, hipErrorUnknown);
-        return rc;
-    }
-    if (ci.field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
-    if (ci.pitch != ci.words) return FASTECC_E_UNSUPPORTED;
-    // mixed-radix codes (fastecc_create_ex): the same scheme on the (2 q 2^m)-th roots of unity; the decoder's transform is a
-    // mixed-radix context one size up, the locator's values come from the way down of another one (mixed_dif)
-    const bool mixed = ci.q > 1;
-    const uint64_t N = mixed ? (uint64_t)ci.q * ci.k : ci.k;
+    DecodeState*& slot = decoder_of(c);
+    if (!slot) slot = new (std::nothrow) DecodeState();
+    return slot;
+}
 
-    // Every code is f on a subset of the NC-th roots of unity, NC = N << e (position u <-> w_NC^u): data block i at
-    // i << e (blocks k..N-1 of a zero-extended code are known zero blocks), parity at the positions fastecc_create
-    // documents — odd multiples of 2^fold for the codes inside (2N,N), the cosets' offsets for n = 4k / 8k.  Positions
-    // that hold no block of the code count as erased, which is exactly what limits the losses to n - k.
-    const int e = code_coset_shift(ci.cosets);
-    const uint64_t NC = N << e;
-    const int lgc = ci.log2k + e;
-    // the matrix-core kernel recomputes 256 blocks in a third of the transform path's time, the VALU kernel breaks even near 128
-    // (profiles/r03/direct_bench.jsonl); stripes the MFMA kernel cannot take (odd or short rows) stop at 96 unless a kernel was asked for — at 80
-    // where the split transform (4.3 ms instead of 7.2 at k = 2^19 x 4 KB) is the alternative
-    int direct_limit = std::min(ci.direct_max, direct_cap());
-    const bool split_applies = ci.decode_split && ci.q <= 1 && ci.cosets == 1 && ci.log2k >= 17;
-    if (ci.direct_kernel == 0 && !direct_mfma_applies(nullptr, nullptr, ci.words)) direct_limit = std::min(direct_limit, split_applies ? 80 : 96);
+// The decoder's work stripes and tables are internal buffers: a call orders its uses of them between streams (CallScope::begin, then this).
+struct EndScope {
+    CallScope& s;
+    hipStream_t st;
+    ~EndScope() { (void)s.end(st); }
+};
+
+// ---- fastecc_decode_prepare ----
+// The 64-bit field has its own decoder (gf61_decode.hip); its contexts are (2k,k), (4k,k) or (8k,k) with k a power of two (and their zero-extended
+// relatives), n = 4k / 8k the same decoder on the (k << e)-th roots of unity
+int prepare_p61(fastecc_ctx* c, const CtxInfo& ci, const uint8_t* data_present, const uint8_t* parity_present)
+{
+    DeviceGuard dg(ci.device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallScope call(c);
+    const int rc0 = call.wait_idle();  // a decode still using the previous pattern
+    if (rc0 != FASTECC_OK) return rc0;
+    char detail[160] = "";
+    // codes other than (2N,N): the decoder sees the (2N,N) codeword — data blocks beyond the caller's k are surviving zero blocks,
+    // parity positions the code does not use are lost (which is what limits the losses to n - k)
+    std::vector<uint8_t> dfull, pfull;
+    if (ci.zero_extended) {
+        dfull.assign(ci.k, 1);
+        pfull.assign(ci.k, 0);
+        for (uint64_t i = 0; i < ci.user_k; i++) dfull[i] = data_present[i] ? 1 : 0;
+        for (uint64_t q = 0; q < ci.user_m; q++) pfull[q * (uint64_t)ci.p61_stride] = parity_present[q] ? 1 : 0;
+        data_present = dfull.data();
+        parity_present = pfull.data();
+    }
+    const int rc = p61::decode_prepare(&decoder61_of(c), ci.log2k, ci.words / 4, data_present, parity_present, ci.direct_max, detail, sizeof detail,
+                                       ci.decode_split, code_coset_shift(ci.cosets));
+    if (rc != FASTECC_OK && detail[0]) set_error_detail(detail, hipErrorUnknown);
+    return rc;
+}
+
+// lost(i) for each flag i < count that is zero, until lost returns false.  (Eight flags per step: a word without a zero byte holds no lost
+// block — byte by byte the two scans took 0.2-0.4 ms of a 0.3-0.5 ms call at k = 2^19.)
+template <class F> void each_lost(const uint8_t* flags, uint64_t count, F&& lost)
+{
+    uint64_t i = 0;
+    for (; i + 8 <= count; i += 8) {
+        uint64_t v;
+        memcpy(&v, flags + i, 8);
+        if (((v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull) == 0) continue;
+        for (uint64_t j = i; j < i + 8; j++)
+            if (!flags[j] && !lost(j)) return;
+    }
+    for (; i < count; i++)
+        if (!flags[i] && !lost(i)) return;
+}
+
+// The parity half's low levels when few block groups are in use (run_split_decode): what the DIF levels with strides 512 ... 16 make of a
+// 1024-block tile in which block q0 alone is 1 — simulated here exactly as the tile does them, (a, b) -> (a + b, (a - b) w_2s^i) with the inverse
+// roots; entry [t][g][c] = block g + 16 c for q0 = g + 16 t (Montgomery form).  w: of order 2N.
+std::vector<uint32_t> split_impulse_table(uint32_t w, uint64_t N)
+{
+    const uint32_t w1024_inv = gf::h_pow(gf::h_inv(gf::h_mul(w, w)), N / 1024);
+    const uint32_t tables = (uint32_t)split_impulse_max();
+    std::vector<uint32_t> table((size_t)tables * 16 * 64), v(1024), tw(512);
+    for (uint32_t q0 = 0; q0 < 16u * tables; q0++) {
+        std::fill(v.begin(), v.end(), 0u);
+        v[q0] = 1;
+        for (uint32_t sdist = 512; sdist >= 16; sdist >>= 1) {
+            const uint32_t root = gf::h_pow(w1024_inv, 512 / sdist);  // order 2 * sdist
+            tw[0] = 1;
+            for (uint32_t i = 1; i < sdist; i++) tw[i] = gf::h_mul(tw[i - 1], root);
+            for (uint32_t base = 0; base < 1024; base += 2 * sdist)
+                for (uint32_t i = 0; i < sdist; i++) {
+                    const uint32_t lo = v[base + i], hi = v[base + i + sdist];
+                    if ((lo | hi) == 0) continue;
+                    v[base + i] = (uint32_t)(((uint64_t)lo + hi) % gf::P);
+                    v[base + i + sdist] = gf::h_mul((uint32_t)(((uint64_t)lo + gf::P - hi) % gf::P), tw[i]);
+                }
+        }
+        const uint32_t t = q0 / 16, g0 = q0 % 16;
+        for (uint32_t cc = 0; cc < 64; cc++) table[(t * 16 + g0) * 64 + cc] = gf::h_to_mont(v[g0 + 16 * cc]);
+    }
+    return table;
+}
+
+// What the pattern scan of the transform path found
+struct PatternScan {
+    bool device_scan = false;      // the (2k,k) layout's scan ran on the device: the state and the lost-parity flags are written there
+    std::vector<uint8_t> state;    // host scan: ST_* per position
+    std::vector<uint32_t> srcmap;  // host scan, layouts other than (2k,k): the block at each position (the table-driven gather's map)
+    uint64_t erased_data = 0, erased_parity = 0;  // lost blocks
+    uint64_t erased_count = 0;                    // roots of the locator: lost or unused positions and those that hold no block of the code
+    uint32_t split_groups = 0;  // non-zero: the pattern goes through the split transform — parity block groups in use (1 for the small form)
+    uint32_t split_shift = 0;   // the small form's shift (0: the group form)
+};
+
+// One fastecc_decode_prepare of a GF(0xFFF00001) code.  Every code is f on a subset of the NC-th roots of unity, NC = N << e (position u <->
+// w_NC^u): data block i at i << e (blocks k..N-1 of a zero-extended code are known zero blocks), parity at the positions fastecc_create documents —
+// odd multiples of 2^fold for the codes inside (2N,N), the cosets' offsets for n = 4k / 8k.  Positions that hold no block of the code count as
+// erased, which is exactly what limits the losses to n - k.  Mixed-radix codes (fastecc_create_ex): the same scheme on the (2 q 2^m)-th roots of
+// unity; the decoder's transform is a mixed-radix context one size up, the locator's values come from the way down of another one (mixed_dif).
+struct Prepare {
+    fastecc_ctx* c;
+    CtxInfo ci;
+    const uint8_t* data_present;
+    const uint8_t* parity_present;
+    bool mixed;     // mixed radix
+    uint64_t N;     // the transform order
+    int e;          // data block i at position i << e
+    uint64_t NC;    // positions
+    int lgc;        // log2k + e
+    bool standard;  // the reference's (2k,k) layout
+    bool narrow;    // NC is a power of two: the w^u table holds every root the chunks of chunk_transform_kernel need
+    DecodeState* d = nullptr;
+    PatternScan s;
+    // The locator's product tree.  T = padded root count: the smallest power of two that holds the most losses the code tolerates, NC - N (the
+    // top of the tree is a cyclic product of length T, so w_T must exist: T <= 2^20.  Orders above 2^20 — mixed radix — tolerate more losses than
+    // that; there T = 2^20 and patterns with more erasures than T are refused.)  The levels below 2^TREE_LOW roots per polynomial are one kernel
+    // (tree_low_levels_kernel) when the tree is tall enough to have them.
+    uint64_t T = 1;
+    int lgT = 0, leaf_log = 0;
+    // parity block j at position 2j + 1 (the (2k,k) layout and its zero-extended relatives with fold 0): a pattern that loses data AND parity
+    // gets the factors of its lost parity blocks too — fastecc_repair then needs no second encode
+    bool parity_factors = false;
+    PhaseTimer pt;
+
+    Prepare(fastecc_ctx* ctx, const uint8_t* dp, const uint8_t* pp)
+        : c(ctx), ci(info_of(ctx)), data_present(dp), parity_present(pp), mixed(ci.q > 1), N(mixed ? (uint64_t)ci.q * ci.k : ci.k),
+          e(code_coset_shift(ci.cosets)), NC(N << e), lgc(ci.log2k + e), standard(!mixed && ci.cosets == 1 && ci.fold == 0 && !ci.zero_extended),
+          narrow(!mixed && (1ull << lgc) == NC)
     {
+    }
+    uint64_t parity_position(uint64_t q) const { return code_parity_position(N, e, ci.fold, ci.cosets, q); }
+    void new_pattern(uint64_t erased_data, uint64_t erased_total)  // (the previous pattern is dropped)
+    {
+        d->ready = false;
+        d->erased_data = erased_data;
+        d->erased_total = erased_total;
+        d->positions = NC;
+        d->standard = standard;
+        d->mixed = mixed;
+    }
+
+    // ---- few losses: interpolation on the surviving data points + a few parity points (direct.hip) ----
+    // The most lost blocks for the direct path.  The matrix-core kernel recomputes 256 blocks in a third of the transform path's time, the VALU
+    // kernel breaks even near 128 (profiles/r03/direct_bench.jsonl); stripes the MFMA kernel cannot take (odd or short rows) stop at 96 unless a
+    // kernel was asked for — at 80 where the split transform (4.3 ms instead of 7.2 at k = 2^19 x 4 KB) is the alternative.
+    int direct_limit() const
+    {
+        int limit = std::min(ci.direct_max, direct_cap());
+        const bool split_applies = ci.decode_split && ci.q <= 1 && ci.cosets == 1 && ci.log2k >= 17;
+        if (ci.direct_kernel == 0 && !direct_mfma_applies(nullptr, nullptr, ci.words)) limit = std::min(limit, split_applies ? 80 : 96);
         // orders above 2^20 (mixed radix): the locator tree is padded to 2^20 roots whatever the pattern
-        uint64_t T = 1;
-        while (T < NC - N) T <<= 1;
+        uint64_t T20 = 1;
+        while (T20 < NC - N) T20 <<= 1;
         // their tree costs a 2^20-point product: the direct path first, up to the caller's "decode_direct_max" (the 80 / 96 cap of rows the
         // matrix-core kernel cannot take is a speed trade-off against a transform path that is much dearer here, so it does not apply)
-        if (T > (1ull << 20) && ci.direct_max > 0) direct_limit = std::max(direct_limit, std::min(ci.direct_max, direct_cap()));
+        if (T20 > (1ull << 20) && ci.direct_max > 0) limit = std::max(limit, std::min(ci.direct_max, direct_cap()));
+        return limit;
     }
-    auto parity_position = [&](uint64_t q) -> uint64_t { return code_parity_position(N, e, ci.fold, ci.cosets, q); };
-    // ---- few losses (decided before any per-position table is built): interpolation on the surviving data points + a few parity points ----
-    if (direct_limit > 0 && ci.user_k < 0xFFFFFFF0ull) {
+
+    // Every lost data block is a fixed linear combination of the surviving data blocks and as many surviving parity blocks, the lost parity blocks
+    // one of the data; decided before any per-position table is built.  *done = false: too many losses, or no memory for the weight tables —
+    // the transform path needs none of them.
+    int direct(bool* done)
+    {
+        *done = false;
+        const int limit = direct_limit();
+        if (limit <= 0 || ci.user_k >= 0xFFFFFFF0ull) return FASTECC_OK;
         PhaseTimer ptd;
-        std::vector<uint32_t> R, Pl, A;
+        std::vector<uint32_t> R, Pl, A;  // lost data blocks, lost parity blocks, the surviving parity blocks that serve as nodes
         bool over = false;
-        // (eight flags per step: a word without a zero byte holds no lost block — byte by byte the two scans took 0.2-0.4 ms of a 0.3-0.5 ms call at k = 2^19)
-        auto each_lost = [](const uint8_t* flags, uint64_t count, auto&& lost) {  // lost(i) returns false to stop
-            uint64_t i = 0;
-            for (; i + 8 <= count; i += 8) {
-                uint64_t v;
-                memcpy(&v, flags + i, 8);
-                if (((v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull) == 0) continue;
-                for (uint64_t j = i; j < i + 8; j++)
-                    if (!flags[j] && !lost(j)) return;
-            }
-            for (; i < count; i++)
-                if (!flags[i] && !lost(i)) return;
-        };
-        each_lost(data_present, ci.user_k, [&](uint64_t i) { R.push_back((uint32_t)i); return !(over = (int)R.size() > direct_limit); });
-        if (!over) each_lost(parity_present, ci.user_m, [&](uint64_t q) { Pl.push_back((uint32_t)q); return !(over = (int)(R.size() + Pl.size()) > direct_limit); });
+        each_lost(data_present, ci.user_k, [&](uint64_t i) { R.push_back((uint32_t)i); return !(over = (int)R.size() > limit); });
+        if (!over) each_lost(parity_present, ci.user_m, [&](uint64_t q) { Pl.push_back((uint32_t)q); return !(over = (int)(R.size() + Pl.size()) > limit); });
         for (uint64_t q = 0; q < ci.user_m && !over && A.size() < R.size(); q++)
             if (parity_present[q]) A.push_back((uint32_t)q);
-        if (!over && R.size() + Pl.size() >= 1 && A.size() == R.size()) {
-            const int ed = (int)R.size(), ep = (int)Pl.size();
-            ptd.mark("few losses: pattern scan");
-            DeviceScope ds(ci.device);
-            if (!ds.ok) return FASTECC_E_DEVICE;
-            CallScope call(c);
-            DecodeState*& slot = decoder_of(c);
-            if (!slot) {
-                slot = new (std::nothrow) DecodeState();
-                if (!slot) return FASTECC_E_NOMEM;
-            }
-            DecodeState* d = slot;
-            d->ready = false;
-            d->sub = false;
-            d->erased_data = ed;
-            d->erased_parity = ep;
-            d->erased_total = ed + ep;
-            d->positions = NC;
-            d->standard = !mixed && ci.cosets == 1 && ci.fold == 0 && !ci.zero_extended;
-            d->mixed = mixed;
-            d->direct_kernel = ci.direct_kernel;
-            const uint32_t K = (uint32_t)ci.user_k;
-            const uint32_t w = gf::h_root((uint32_t)NC), wd = gf::h_pow(w, 1ull << e);  // data row i sits at wd^i
-            auto fsub = [](uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a + gf::P - b) % gf::P); };
-            {
-                const int rc = call.wait_idle();  // a decode still using the previous pattern
-                if (rc != FASTECC_OK) return rc;
-            }
-            ptd.mark("few losses: lock, idle");
-            int rc = FASTECC_OK;
-            // (up to 32 outputs a pass costs the read of the survivors whatever it computes, profiles/r03/direct_bench.jsonl: one table then serves decode and repair)
-            d->sub_only_both = ed > 0 && ep > 0 && ed + ep <= 32;
-            if (ed > 0 && !d->sub_only_both) {
-                std::vector<uint32_t> xr(ed), ya(ed);
-                for (int r = 0; r < ed; r++) xr[r] = gf::h_pow(w, (uint64_t)R[r] << e);
-                for (int a = 0; a < ed; a++) ya[a] = gf::h_pow(w, parity_position(A[a]));
-                if (!d->direct_data && !(d->direct_data = direct_pass_new())) return FASTECC_E_NOMEM;
-                rc = direct_build_interp(d->direct_data, wd, N, K, R, xr, A, ya, nullptr);
-            }
-            ptd.mark("few losses: data table");
-            d->sub_both = false;
-            if (rc == FASTECC_OK && ep > 0) {
-                std::vector<uint32_t> yt(ep), ct(ep), pos(ep);
-                const uint32_t inv_N = gf::h_inv((uint32_t)(N % gf::P));
-                for (int t = 0; t < ep; t++) {
-                    yt[t] = gf::h_pow(w, parity_position(Pl[t]));
-                    ct[t] = gf::h_mul(fsub(gf::h_pow(yt[t], N), 1u), inv_N);  // (y_t^N - 1) / N
-                    pos[t] = 2u * Pl[t] + 1u;
-                }
-                if (d->sub_only_both) {
-                    // data lost as well, few outputs: fastecc_repair reads the survivors ONCE — the lost parity blocks are further outputs on the data
-                    // pass's nodes (the surviving data and as many parity blocks), not a second pass over the repaired data.  (Above 32 outputs the
-                    // matrix cores bound the pass, not the read: 128 + 128 lost take 2.40 ms in one pass, 2.48 in two, and the set-up of the second
-                    // 256-output table costs 0.9 ms.)
-                    std::vector<uint32_t> xr(ed), ya(ed);
-                    for (int r = 0; r < ed; r++) xr[r] = gf::h_pow(w, (uint64_t)R[r] << e);
-                    for (int a = 0; a < ed; a++) ya[a] = gf::h_pow(w, parity_position(A[a]));
-                    if (!d->direct_both && !(d->direct_both = direct_pass_new())) return FASTECC_E_NOMEM;
-                    rc = direct_build_interp(d->direct_both, wd, N, K, R, xr, A, ya, nullptr, &yt, &pos);
-                    d->sub_both = rc == FASTECC_OK;
-                } else {
-                    if (!d->direct_parity && !(d->direct_parity = direct_pass_new())) return FASTECC_E_NOMEM;
-                    rc = direct_build_lagrange(d->direct_parity, wd, K, yt, ct, pos, nullptr);
-                }
-            }
-            ptd.mark("few losses: parity table");
-            if (rc == FASTECC_OK) {
-                d->sub = true;
-                d->sub_lost_data = ed;
-                d->sub_lost_parity = ep;
-                d->host_lost_data = R;  // (FASTECC_MEM_HOST calls: the rows that travel back)
-                d->host_lost_parity = Pl;
-                d->host_parity_used = A;
-                d->host_lists_of = ++d->pattern_serial;
-                d->ready = true;
-                return FASTECC_OK;
-            }
-            if (rc != FASTECC_E_NOMEM) return rc;
-            // no memory for the weight tables: the transform path below needs none of them
+        if (over || R.size() + Pl.size() < 1 || A.size() != R.size()) return FASTECC_OK;
+        const int ed = (int)R.size(), ep = (int)Pl.size();
+        ptd.mark("few losses: pattern scan");
+        DeviceGuard dg(ci.device);
+        if (!dg.ok) return FASTECC_E_DEVICE;
+        CallScope call(c);
+        if (!(d = state_of(c))) return FASTECC_E_NOMEM;
+        new_pattern(ed, ed + ep);
+        d->sub = false;
+        d->erased_parity = ep;
+        d->direct_kernel = ci.direct_kernel;
+        int rc = call.wait_idle();  // a decode still using the previous pattern
+        if (rc != FASTECC_OK) return rc;
+        ptd.mark("few losses: lock, idle");
+        const uint32_t K = (uint32_t)ci.user_k;
+        const uint32_t w = gf::h_root((uint32_t)NC), wd = gf::h_pow(w, 1ull << e);  // data row i sits at wd^i
+        std::vector<uint32_t> xr(ed), ya(ed);  // the points of the lost data blocks and of their parity nodes
+        for (int r = 0; r < ed; r++) xr[r] = gf::h_pow(w, (uint64_t)R[r] << e);
+        for (int a = 0; a < ed; a++) ya[a] = gf::h_pow(w, parity_position(A[a]));
+        // (up to 32 outputs a pass costs the read of the survivors whatever it computes, profiles/r03/direct_bench.jsonl: one table then serves decode and repair)
+        d->sub_only_both = ed > 0 && ep > 0 && ed + ep <= 32;
+        if (ed > 0 && !d->sub_only_both) {
+            if (!d->direct_data && !(d->direct_data = direct_pass_new())) return FASTECC_E_NOMEM;
+            rc = direct_build_interp(d->direct_data, wd, N, K, R, xr, A, ya, nullptr);
         }
+        ptd.mark("few losses: data table");
+        d->sub_both = false;
+        if (rc == FASTECC_OK && ep > 0) {
+            std::vector<uint32_t> yt(ep), ct(ep), pos(ep);
+            const uint32_t inv_N = gf::h_inv((uint32_t)(N % gf::P));
+            for (int t = 0; t < ep; t++) {
+                yt[t] = gf::h_pow(w, parity_position(Pl[t]));
+                ct[t] = gf::h_mul((uint32_t)(((uint64_t)gf::h_pow(yt[t], N) + gf::P - 1u) % gf::P), inv_N);  // (y_t^N - 1) / N
+                pos[t] = 2u * Pl[t] + 1u;
+            }
+            if (d->sub_only_both) {
+                // data lost as well, few outputs: fastecc_repair reads the survivors ONCE — the lost parity blocks are further outputs on the data
+                // pass's nodes (the surviving data and as many parity blocks), not a second pass over the repaired data.  (Above 32 outputs the
+                // matrix cores bound the pass, not the read: 128 + 128 lost take 2.40 ms in one pass, 2.48 in two, and the set-up of the second
+                // 256-output table costs 0.9 ms.)
+                if (!d->direct_both && !(d->direct_both = direct_pass_new())) return FASTECC_E_NOMEM;
+                rc = direct_build_interp(d->direct_both, wd, N, K, R, xr, A, ya, nullptr, &yt, &pos);
+                d->sub_both = rc == FASTECC_OK;
+            } else {
+                if (!d->direct_parity && !(d->direct_parity = direct_pass_new())) return FASTECC_E_NOMEM;
+                rc = direct_build_lagrange(d->direct_parity, wd, K, yt, ct, pos, nullptr);
+            }
+        }
+        ptd.mark("few losses: parity table");
+        if (rc == FASTECC_E_NOMEM) return FASTECC_OK;  // no memory for the weight tables: the transform path
+        if (rc != FASTECC_OK) return rc;
+        d->sub = true;
+        d->sub_lost_data = ed;
+        d->sub_lost_parity = ep;
+        d->host_lost_data = R;  // (FASTECC_MEM_HOST calls: the rows that travel back)
+        d->host_lost_parity = Pl;
+        d->host_parity_used = A;
+        d->host_lists_of = ++d->pattern_serial;
+        d->ready = true;
+        *done = true;
+        return FASTECC_OK;
     }
-    PhaseTimer pt;
-    enum : uint8_t { LOST = ST_LOST, HELD = ST_HELD, ZERO = ST_ZERO };
-    const bool standard_layout = !mixed && ci.cosets == 1 && ci.fold == 0 && !ci.zero_extended;
-    uint64_t erased_data = 0;
-    uint32_t split_groups = 0, split_shift = 0;
-    // ---- the reference's (2k,k) layout: the pattern is scanned on the DEVICE (the host loops below took 1.2-1.4 ms of a 2.6 ms call at k = 2^19:
+
+    // ---- the transform path ----
+    int transform_path()
+    {
+        pt = PhaseTimer();
+        DeviceGuard dg(ci.device);
+        if (!dg.ok) return FASTECC_E_DEVICE;
+        CallScope call(c);  // (held from here on: the device scan already writes the context's pattern state)
+        if (!(d = state_of(c))) return FASTECC_E_NOMEM;
+        int rc;
+        if (standard && N <= 0x7FFFFFFFull && (rc = scan_device(call)) != FASTECC_OK) return rc;
+        if (!s.device_scan) scan_host();
+        if (s.erased_count > NC - N) return FASTECC_E_INVAL;  // fewer than k blocks survive: not decodable
+        pt.mark(s.device_scan ? "pattern scan (device)" : "pattern scan (host)");
+        if ((rc = set_pattern(call)) != FASTECC_OK) return rc;
+        if (s.erased_data == 0) {  // no data block to recover
+            // standard_state_kernel's writes of the lost-parity flags are still pending on the null stream: a repair on a non-blocking
+            // stream is not ordered after them (the full path below ends with the same synchronise)
+            if (s.device_scan) HIP_TRY(hipStreamSynchronize(nullptr));
+            d->ready = true;
+            return FASTECC_OK;
+        }
+        while (T < NC - N && T < (1ull << 20)) T <<= 1;
+        while ((1ull << lgT) < T) lgT++;
+        if (s.erased_count > T) return FASTECC_E_UNSUPPORTED;
+        leaf_log = lgT >= TREE_LOW + 2 ? TREE_LOW : std::min(LEAF_LOG, lgT);
+        parity_factors = d->erased_parity != 0 && (d->standard || (s.split_groups != 0 && ci.fold == 0));
+        if ((rc = build_shape()) != FASTECC_OK) return rc;
+        if ((rc = call.wait_idle()) != FASTECC_OK) return rc;  // a decode still using the previous pattern
+        pt.mark("tables, tile order");
+        uint32_t* coeffs = nullptr;
+        if ((rc = locator_tree(&coeffs)) != FASTECC_OK || (rc = locator_tables(coeffs)) != FASTECC_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        pt.mark("this pattern (device)");
+        d->ready = true;
+        return FASTECC_OK;
+    }
+
+    // The reference's (2k,k) layout: the pattern is scanned on the DEVICE (the host loops of scan_host took 1.2-1.4 ms of a 2.6 ms call at k = 2^19:
     // four passes over a million byte-sized coin flips).  Two 512 KB uploads, one counting kernel, 32 bytes back; the per-position state and the
-    // lost-parity flags are then written by a kernel.  Patterns the "small form" of the split transform does not take (too few surviving
-    // parity blocks at multiples of 2^h) keep the host path. ----
-    bool device_scan = false;
-    uint64_t device_erased_count = 0, device_erased_parity = 0;
-    DeviceScope ds(ci.device);
-    if (!ds.ok) return FASTECC_E_DEVICE;
-    CallScope call(c);  // (held from here on: the scan below already writes the context's pattern state)
-    DecodeState*& slot = decoder_of(c);
-    if (!slot) {
-        slot = new (std::nothrow) DecodeState();
-        if (!slot) return FASTECC_E_NOMEM;
-    }
-    if (standard_layout && N <= 0x7FFFFFFFull) {
-        DecodeState* d0 = slot;
-        if (!d0->dev_present) DEC_TRY(hipMalloc((void**)&d0->dev_present, 2 * N));
-        if (!d0->dev_counts) DEC_TRY(hipMalloc((void**)&d0->dev_counts, 8 * 4));
-        if (!d0->dev_state) DEC_TRY(hipMalloc((void**)&d0->dev_state, NC));
-        if (!d0->parity_lost) DEC_TRY(hipMalloc((void**)&d0->parity_lost, ci.user_m * 4));
-        {
-            const int rc = call.wait_idle();  // a decode or repair still reading the previous pattern's state
-            if (rc != FASTECC_OK) return rc;
-        }
-        d0->ready = false;
-        hipStream_t st0 = nullptr;
-        DEC_TRY(hipMemcpyAsync(d0->dev_present, data_present, N, hipMemcpyHostToDevice, st0));
-        DEC_TRY(hipMemcpyAsync(d0->dev_present + N, parity_present, N, hipMemcpyHostToDevice, st0));
-        DEC_TRY(hipMemsetAsync(d0->dev_counts, 0, 8 * 4, st0));
-        hipLaunchKernelGGL(presence_counts_kernel, dim3(128), dim3(256), 0, st0, d0->dev_present, d0->dev_present + N, (uint32_t)N, d0->dev_counts);
-        DEC_TRY(hipGetLastError());
+    // lost-parity flags are then written by a kernel.  Patterns the "small form" of the split transform does not take (too few surviving parity
+    // blocks at multiples of 2^h) leave s as it is: the host scan.
+    int scan_device(CallScope& call)
+    {
+        if (!d->dev_present) HIP_TRY(hipMalloc((void**)&d->dev_present, 2 * N));
+        if (!d->dev_counts) HIP_TRY(hipMalloc((void**)&d->dev_counts, 8 * 4));
+        if (!d->dev_state) HIP_TRY(hipMalloc((void**)&d->dev_state, NC));
+        if (!d->parity_lost) HIP_TRY(hipMalloc((void**)&d->parity_lost, ci.user_m * 4));
+        const int rc = call.wait_idle();  // a decode or repair still reading the previous pattern's state
+        if (rc != FASTECC_OK) return rc;
+        d->ready = false;
+        HIP_TRY(hipMemcpyAsync(d->dev_present, data_present, N, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(d->dev_present + N, parity_present, N, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemsetAsync(d->dev_counts, 0, 8 * 4, nullptr));
+        hipLaunchKernelGGL(presence_counts_kernel, dim3(128), dim3(256), 0, nullptr, d->dev_present, d->dev_present + N, (uint32_t)N, d->dev_counts);
+        HIP_TRY(hipGetLastError());
         uint32_t counts[8] = {};
-        DEC_TRY(hipMemcpy(counts, d0->dev_counts, sizeof counts, hipMemcpyDeviceToHost));
-        erased_data = counts[0];
-        device_erased_parity = counts[1];
-        const bool want_split0 = ci.decode_split && ci.log2k >= 17 && erased_data != 0;
-        if (want_split0 && ci.decode_split != 2)
-            for (int h = 5; h >= 1 && split_shift == 0; h--)
-                if (counts[1 + h] >= erased_data) split_shift = (uint32_t)h;
-        if (!want_split0 || split_shift != 0) {
-            device_scan = true;
-            const uint64_t unused = split_shift ? (N - device_erased_parity) - counts[1 + split_shift] : 0;
-            device_erased_count = erased_data + device_erased_parity + unused;
-            split_groups = split_shift ? 1u : 0u;  // (non-zero: "this pattern goes through the split transform" for the code below)
-            hipLaunchKernelGGL(standard_state_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st0, d0->dev_present, d0->dev_present + N, (uint32_t)N,
-                               split_shift ? (1u << split_shift) - 1u : 0u, (uint8_t*)d0->dev_state, d0->parity_lost);
-            DEC_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(counts, d->dev_counts, sizeof counts, hipMemcpyDeviceToHost));
+        const uint64_t erased_data = counts[0], erased_parity = counts[1];
+        uint32_t shift = 0;
+        const bool want_split = ci.decode_split && ci.log2k >= 17 && erased_data != 0;
+        if (want_split && ci.decode_split != 2)
+            for (int h = 5; h >= 1 && shift == 0; h--)
+                if (counts[1 + h] >= erased_data) shift = (uint32_t)h;
+        if (want_split && shift == 0) return FASTECC_OK;  // the host path counts again
+        s.device_scan = true;
+        s.erased_data = erased_data;
+        s.erased_parity = erased_parity;
+        s.erased_count = erased_data + erased_parity + (shift ? (N - erased_parity) - counts[1 + shift] : 0);
+        s.split_shift = shift;
+        s.split_groups = shift ? 1u : 0u;
+        hipLaunchKernelGGL(standard_state_kernel, grid_of(N), dim3(256), 0, nullptr, d->dev_present, d->dev_present + N, (uint32_t)N,
+                           shift ? (1u << shift) - 1u : 0u, (uint8_t*)d->dev_state, d->parity_lost);
+        HIP_TRY(hipGetLastError());
+        return FASTECC_OK;
+    }
+
+    // The pattern scanned on the host.  (Branch-free loops: on a random pattern every "if (present)" is a coin flip — 2^20 mispredictions were
+    // most of this call's time at 50 % loss.)
+    void scan_host()
+    {
+        std::vector<uint8_t>& state = s.state;
+        state.assign(NC, ST_LOST);
+        if (standard) {  // (the (2k,k) layout reads its two stripes by position: no block map)
+            for (uint64_t i = 0; i < N; i++) {
+                const uint32_t held_d = data_present[i] != 0, held_p = parity_present[i] != 0;
+                state[2 * i] = held_d ? ST_HELD : ST_LOST;
+                state[2 * i + 1] = held_p ? ST_HELD : ST_LOST;
+                s.erased_data += 1u - held_d;
+                s.erased_parity += 1u - held_p;
+            }
         } else {
-            erased_data = 0;  // the host path counts again
-            split_shift = 0;
+            std::vector<uint32_t>& srcmap = s.srcmap;
+            srcmap.assign(NC, 0);
+            for (uint64_t i = 0; i < ci.user_k; i++) {
+                const uint64_t u = i << e;
+                const uint32_t held = data_present[i] != 0;
+                state[u] = held ? ST_HELD : ST_LOST;
+                srcmap[u] = (uint32_t)i & (0u - held);
+                s.erased_data += 1u - held;
+            }
+            for (uint64_t i = ci.user_k; i < N; i++) state[i << e] = ST_ZERO;
+            for (uint64_t q = 0; q < ci.user_m; q++) {
+                const uint64_t u = parity_position(q);
+                const uint32_t held = parity_present[q] != 0;
+                state[u] = held ? ST_HELD : ST_LOST;
+                srcmap[u] = ((uint32_t)q | 0x80000000u) & (0u - held);
+                s.erased_parity += 1u - held;
+            }
         }
+        if (ci.decode_split && !mixed && ci.cosets == 1 && ci.log2k >= 17 && s.erased_data != 0) choose_split();
+        if (s.split_groups != 0 && !s.srcmap.empty())
+            for (uint64_t u = 1; u < NC; u += 2) s.srcmap[u] &= 0u - (uint32_t)(state[u] != ST_UNUSED);
+        // the erased positions themselves are listed on the device (erased_list_kernel): the host needs their number only
+        for (uint64_t u = 0; u < NC; u++) s.erased_count += (unsigned)(state[u] == ST_LOST) + (unsigned)(state[u] == ST_UNUSED);
     }
-    // (branch-free loops: on a random pattern every "if (present)" is a coin flip — 2^20 mispredictions were most of this call's time at 50 % loss)
-    std::vector<uint8_t> state(device_scan ? 0 : NC, LOST);
-    // the block map serves the table-driven gather only: the (2k,k) layout reads its two stripes by position
-    std::vector<uint32_t> srcmap(standard_layout ? 0 : NC, 0);
-    if (device_scan) {
-        // nothing to do on the host
-    } else if (standard_layout) {
-        for (uint64_t i = 0; i < N; i++) {
-            const uint32_t held_d = data_present[i] != 0, held_p = parity_present[i] != 0;
-            state[2 * i] = held_d ? HELD : LOST;
-            state[2 * i + 1] = held_p ? HELD : LOST;
-            erased_data += 1u - held_d;
-        }
-    } else {
-        for (uint64_t i = 0; i < ci.user_k; i++) {
-            const uint64_t u = i << e;
-            const uint32_t held = data_present[i] != 0;
-            state[u] = held ? HELD : LOST;
-            srcmap[u] = (uint32_t)i & (0u - held);
-            erased_data += 1u - held;
-        }
-        for (uint64_t i = ci.user_k; i < N; i++) state[i << e] = ZERO;
-        for (uint64_t q = 0; q < ci.user_m; q++) {
-            const uint64_t u = parity_position(q);
-            const uint32_t held = parity_present[q] != 0;
-            state[u] = held ? HELD : LOST;
-            srcmap[u] = ((uint32_t)q | 0x80000000u) & (0u - held);
-        }
-    }
-    // (2k,k) layout, split transform: recovering e lost data blocks takes e parity blocks, not all of them — the surviving parity blocks of
-    // the first few block groups of the parity stripe (group g = blocks g + (t << 10): what one tile of the first pass reads).  The others
-    // are left unread: roots of the locator like the lost ones.
-    // (also the zero-extended codes inside (2N,N): data block i at position 2i, parity block j at 2j + 1, fewer blocks than N in either stripe;
-    // and the codes with fewer parity blocks: parity block j at position 2 (j << fold) + 1, i.e. block j << fold of the parity half)
-    const bool split_layout = !mixed && ci.cosets == 1;
-    const bool want_split = !device_scan && ci.decode_split && split_layout && ci.log2k >= 17 && erased_data != 0;
-    if (want_split) {
-        // first choice: the surviving parity blocks at multiples of 2^h of the parity half, the largest h <= 5 that still leaves as many as there are
-        // lost data blocks (2 % of the codeword lost: h = 5) — r~ is then the transform of k >> h rows (see DecodeState::split_shift)
+
+    // (2k,k) layout, split transform: recovering e lost data blocks takes e parity blocks, not all of them — the surviving parity blocks of the
+    // first few block groups of the parity stripe (group g = blocks g + (t << 10): what one tile of the first pass reads).  The others are left
+    // unread: roots of the locator like the lost ones.  (Also the zero-extended codes inside (2N,N): data block i at position 2i, parity block j at
+    // 2j + 1, fewer blocks than N in either stripe; and the codes with fewer parity blocks: parity block j at position 2 (j << fold) + 1, i.e.
+    // block j << fold of the parity half.)
+    void choose_split()
+    {
+        std::vector<uint8_t>& state = s.state;
+        // first choice: the surviving parity blocks at multiples of 2^h of the parity half, the largest h <= 5 that still leaves as many as there
+        // are lost data blocks (2 % of the codeword lost: h = 5) — r~ is then the transform of k >> h rows (see DecodeState::split_shift)
         uint64_t at_multiple[6] = {};
         for (uint64_t q = 0; q < ci.user_m; q++) {
             if (!parity_present[q]) continue;
             const uint64_t hpos = q << ci.fold;
             for (int h = 1; h <= 5 && (hpos & ((1ull << h) - 1ull)) == 0; h++) at_multiple[h]++;
         }
-        for (int h = 5; h >= 1 && split_shift == 0; h--)
-            if (at_multiple[h] >= erased_data && ci.decode_split != 2) split_shift = (uint32_t)h;
-        if (split_shift != 0) {
-            const uint64_t mask = (1ull << split_shift) - 1ull;
+        for (int h = 5; h >= 1 && s.split_shift == 0; h--)
+            if (at_multiple[h] >= s.erased_data && ci.decode_split != 2) s.split_shift = (uint32_t)h;
+        if (s.split_shift != 0) {
+            const uint64_t mask = (1ull << s.split_shift) - 1ull;
             for (uint64_t q = 0; q < N; q++)
-                if ((q & mask) != 0 && state[2 * q + 1] == HELD) state[2 * q + 1] = (uint8_t)ST_UNUSED;
-            split_groups = 1;  // (non-zero: "this pattern goes through the split transform" for the code below)
-        } else {
+                if ((q & mask) != 0 && state[2 * q + 1] == ST_HELD) state[2 * q + 1] = (uint8_t)ST_UNUSED;
+            s.split_groups = 1;
+            return;
+        }
         constexpr uint32_t GROUPS = 1024;
         uint32_t held_in[GROUPS] = {};
         for (uint64_t q = 0; q < ci.user_m; q++) held_in[(q << ci.fold) & (GROUPS - 1u)] += parity_present[q] != 0;
         uint64_t have = 0;
-        while (split_groups < GROUPS && have < erased_data) have += held_in[split_groups++];
-        if (have >= erased_data) {
-            for (uint64_t q0 = 0; q0 < N; q0 += GROUPS)  // (the blocks of the groups in use keep their state)
-                for (uint64_t q = q0 + split_groups; q < q0 + GROUPS; q++) state[2 * q + 1] = state[2 * q + 1] == HELD ? (uint8_t)ST_UNUSED : state[2 * q + 1];
-        } else {
-            split_groups = 0;  // not decodable: refused below
+        while (s.split_groups < GROUPS && have < s.erased_data) have += held_in[s.split_groups++];
+        if (have < s.erased_data) {
+            s.split_groups = 0;  // not decodable: refused by the caller
+            return;
         }
-        }
+        for (uint64_t q0 = 0; q0 < N; q0 += GROUPS)  // (the blocks of the groups in use keep their state)
+            for (uint64_t q = q0 + s.split_groups; q < q0 + GROUPS; q++) state[2 * q + 1] = state[2 * q + 1] == ST_HELD ? (uint8_t)ST_UNUSED : state[2 * q + 1];
     }
-    if (split_groups != 0 && !srcmap.empty())
-        for (uint64_t u = 1; u < NC; u += 2) srcmap[u] &= 0u - (uint32_t)(state[u] != ST_UNUSED);
-    // the erased positions themselves are listed on the device (erased_list_kernel): the host needs their number only
-    uint64_t erased_count = device_erased_count;
-    if (!device_scan)
-        for (uint64_t u = 0; u < NC; u++) erased_count += (unsigned)(state[u] == LOST) + (unsigned)(state[u] == ST_UNUSED);
-    if (erased_count > NC - N) return FASTECC_E_INVAL;  // fewer than k blocks survive: not decodable
-    pt.mark(device_scan ? "pattern scan (device)" : "pattern scan (host)");
 
-    DecodeState* d = slot;
-    d->ready = false;
-    d->erased_data = erased_data;
-    d->erased_total = erased_count;
-    d->positions = NC;
-    d->standard = !mixed && ci.cosets == 1 && ci.fold == 0 && !ci.zero_extended;
-    d->mixed = mixed;
-    pt.mark("lock, state");
-    if (device_scan) {
-        d->erased_parity = device_erased_parity;  // (the flags were written by standard_state_kernel)
-    } else {
-        std::vector<uint32_t> plost(ci.user_m);
-        d->erased_parity = 0;
-        for (uint64_t q = 0; q < ci.user_m; q++) d->erased_parity += (plost[q] = parity_present[q] ? 0u : 1u);
-        if (!d->parity_lost) DEC_TRY(hipMalloc((void**)&d->parity_lost, ci.user_m * 4));
-        const int rc = call.wait_idle();  // a repair still reading the previous pattern
-        if (rc != FASTECC_OK) return rc;
-        DEC_TRY(hipMemcpy(d->parity_lost, plost.data(), ci.user_m * 4, hipMemcpyHostToDevice));
-    }
-    pt.mark("lost-parity flags");
-    d->sub = false;
-    ++d->pattern_serial;  // (the lists of rebuilt rows for FASTECC_MEM_HOST calls are made when such a call comes: decode_impl)
-    if (erased_data == 0) {  // no data block to recover
-        // standard_state_kernel's writes of the lost-parity flags are still pending on the null stream: a repair on a non-blocking
-        // stream is not ordered after them (the full path below ends with the same synchronise)
-        if (device_scan) DEC_TRY(hipStreamSynchronize(nullptr));
-        d->ready = true;
+    // the pattern's counts into the decoder's state (the previous pattern is dropped) and the lost-parity flags of a host scan to the device
+    int set_pattern(CallScope& call)
+    {
+        new_pattern(s.erased_data, s.erased_count);
+        pt.mark("lock, state");
+        d->erased_parity = s.erased_parity;
+        if (!s.device_scan) {
+            std::vector<uint32_t> plost(ci.user_m);
+            for (uint64_t q = 0; q < ci.user_m; q++) plost[q] = parity_present[q] ? 0u : 1u;
+            if (!d->parity_lost) HIP_TRY(hipMalloc((void**)&d->parity_lost, ci.user_m * 4));
+            const int rc = call.wait_idle();  // a repair still reading the previous pattern
+            if (rc != FASTECC_OK) return rc;
+            HIP_TRY(hipMemcpy(d->parity_lost, plost.data(), ci.user_m * 4, hipMemcpyHostToDevice));
+        }
+        pt.mark("lost-parity flags");
+        d->sub = false;
+        ++d->pattern_serial;  // (the lists of rebuilt rows for FASTECC_MEM_HOST calls are made when such a call comes: StripeDecode::stage_host)
         return FASTECC_OK;
     }
 
-    // ---- device state of the decoder (built once) ----
-    // T = padded root count: the smallest power of two that holds the most losses the code tolerates, NC - N
-    // (the top of the product tree is a cyclic product of length T, so w_T must exist: T <= 2^20.  Orders above 2^20 — mixed radix —
-    // tolerate more losses than that; there T = 2^20 and patterns with more erasures than T are refused.)
-    uint64_t T = 1;
-    while (T < NC - N && T < (1ull << 20)) T <<= 1;
-    int lgT = 0;
-    while ((1ull << lgT) < T) lgT++;
-    if (erased_count > T) return FASTECC_E_UNSUPPORTED;
-    // the levels below 2^TREE_LOW roots per polynomial are one kernel (tree_low_levels_kernel) when the tree is tall enough to have them
-    const int leaf_log = lgT >= TREE_LOW + 2 ? TREE_LOW : std::min(LEAF_LOG, lgT), leaf = 1 << leaf_log;
-    const uint32_t w = gf::h_root((uint32_t)NC);
-    hipStream_t st = nullptr;  // the set-up is synchronous: it runs on the default stream and ends with a synchronise
-    const bool narrow = !mixed && (1ull << lgc) == NC;  // (the w^u table then holds every root the chunks need)
-    if (!d->pattern_ntt) {
-        int rc;
-        if (mixed) {
-            const std::vector<uint32_t> ones(NC, 1u);
-            rc = create_mixed_transform_ctx(&d->pattern_ntt, ci.q, lgc, 8, ones.data(), ci.device);
-        } else {
-            // only its stand-alone transform is used; long ones as the upper row bits of a four-step transform (chunk_transform_kernel)
-            d->pattern_narrow = narrow && lgc + 1 - CHUNK_LOG >= 1;
-            rc = d->pattern_narrow ? create_ntt_ctx(&d->pattern_ntt, lgc + 1 - CHUNK_LOG, 4 * CHUNK, ci.device) : create_ntt_ctx(&d->pattern_ntt, lgc, 8, ci.device);
-        }
+    // Everything that outlives a pattern, built once per context or shape: contexts, tree buffers, tables, the split transform and its buffers,
+    // the one-transform repair's context, the tile order.  May clear s.split_groups (split_buffers).
+    int build_shape()
+    {
+        int rc = build_transforms();
         if (rc != FASTECC_OK) return rc;
-    }
-    pt.mark("pattern_ntt context");
-    if (!d->pattern_buf) DEC_TRY(hipMalloc((void**)&d->pattern_buf, 2 * NC * 4));
-    if (!d->transform) {
-        // x p'(x): coefficient m times m, and the 1/NC of the inverse transform.  fold e: only the data positions (multiples of 2^e) are
-        // evaluated (mixed radix: all positions, the even ones are used)
-        const uint32_t inv_nc = gf::h_inv((uint32_t)NC);
-        int rc;
-        if (mixed) {
-            std::vector<uint32_t> factor(NC);
-            const uint32_t inv_nc_m = gf::h_to_mont(inv_nc);
-            for (uint64_t m = 0; m < NC; m++) factor[m] = gf::h_mont_mul((uint32_t)m, inv_nc_m);
-            rc = create_mixed_transform_ctx(&d->transform, ci.q, lgc, ci.words * 4, factor.data(), ci.device);
-        } else {
-            rc = create_ramp_transform_ctx(&d->transform, lgc, ci.words * 4, e, inv_nc, ci.device);
+        if ((d->tree_T != T || d->tree_low != leaf_log) && (rc = build_tree()) != FASTECC_OK) return rc;
+        pt.mark("tree contexts + buffers");
+        if ((rc = build_tables()) != FASTECC_OK) return rc;
+        d->split_ready = false;
+        d->split_repair_ready = false;
+        if (s.split_groups != 0 && !d->split_unavailable && !d->split && (rc = build_split()) != FASTECC_OK) return rc;
+        if (s.split_groups != 0 && d->split && (rc = split_buffers()) != FASTECC_OK) return rc;
+        if (d->standard && d->erased_parity != 0 && !(s.split_groups != 0 && d->split) && !d->transform_full) {
+            // repair in one transform (see DecodeState::transform_full): the form for patterns or plans the split transform does not take
+            rc = create_ramp_transform_ctx(&d->transform_full, lgc, ci.words * 4, 0, gf::h_inv((uint32_t)NC), ci.device);
+            if (rc != FASTECC_OK && rc != FASTECC_E_NOMEM) return rc;
+            d->full_ok = d->transform_full && same_tile_order(d->transform, d->transform_full);
+            if (getenv("FASTECC_TRACE_PREPARE"))
+                fprintf(stderr, "[fastecc prepare] one-transform repair: context %s, same first-pass order %d (%s | %s)\n", d->transform_full ? "built" : "none",
+                        (int)d->full_ok, fastecc_plan_string(d->transform), d->transform_full ? fastecc_plan_string(d->transform_full) : "");
         }
-        if (rc != FASTECC_OK) return rc;
+        if (d->standard && !d->tile_order_valid) {
+            if (same_tile_order(d->transform, d->transform)) {  // (a tile first pass: the order exists)
+                HIP_TRY(hipMalloc((void**)&d->tile_order, NC * 4));
+                if (!gather_tile_order_device(d->transform, d->tile_order, nullptr)) return FASTECC_E_DEVICE;
+                HIP_TRY(hipMalloc((void**)&d->fin_first_pass, NC * 4));
+            } else {
+                d->fin_first_pass = d->fin;
+            }
+            d->tile_order_valid = true;
+        }
+        if (!d->standard) d->fin_first_pass = d->fin;
+        return FASTECC_OK;
     }
-    pt.mark("transform context");
-    if (d->tree_T != T || d->tree_low != leaf_log) {
-        // level k >= leaf_log multiplies pairs of degree-2^k polynomials: transforms of length 2^(k+1) on T / 2^k columns
-        for (fastecc_ctx* t : d->tree_ctx)
-            if (t) fastecc_destroy(t);
+
+    // the pattern's transform (two columns: l and l') and the decoder's own
+    int build_transforms()
+    {
+        if (!d->pattern_ntt) {
+            int rc;
+            if (mixed) {
+                const std::vector<uint32_t> ones(NC, 1u);
+                rc = create_mixed_transform_ctx(&d->pattern_ntt, ci.q, lgc, 8, ones.data(), ci.device);
+            } else {
+                // only its stand-alone transform is used; long ones as the upper row bits of a four-step transform (chunk_transform_kernel)
+                d->pattern_narrow = narrow && lgc + 1 - CHUNK_LOG >= 1;
+                rc = d->pattern_narrow ? create_ntt_ctx(&d->pattern_ntt, lgc + 1 - CHUNK_LOG, 4 * CHUNK, ci.device) : create_ntt_ctx(&d->pattern_ntt, lgc, 8, ci.device);
+            }
+            if (rc != FASTECC_OK) return rc;
+        }
+        pt.mark("pattern_ntt context");
+        if (!d->pattern_buf) HIP_TRY(hipMalloc((void**)&d->pattern_buf, 2 * NC * 4));
+        if (!d->transform) {
+            // x p'(x): coefficient m times m, and the 1/NC of the inverse transform.  fold e: only the data positions (multiples of 2^e) are
+            // evaluated (mixed radix: all positions, the even ones are used)
+            const uint32_t inv_nc = gf::h_inv((uint32_t)NC);
+            int rc;
+            if (mixed) {
+                std::vector<uint32_t> factor(NC);
+                const uint32_t inv_nc_m = gf::h_to_mont(inv_nc);
+                for (uint64_t m = 0; m < NC; m++) factor[m] = gf::h_mont_mul((uint32_t)m, inv_nc_m);
+                rc = create_mixed_transform_ctx(&d->transform, ci.q, lgc, ci.words * 4, factor.data(), ci.device);
+            } else {
+                rc = create_ramp_transform_ctx(&d->transform, lgc, ci.words * 4, e, inv_nc, ci.device);
+            }
+            if (rc != FASTECC_OK) return rc;
+        }
+        pt.mark("transform context");
+        return FASTECC_OK;
+    }
+
+    // the tree's contexts and buffers: level k >= leaf_log multiplies pairs of degree-2^k polynomials — transforms of length 2^(k+1) on T / 2^k columns
+    int build_tree()
+    {
+        for (fastecc_ctx* x : d->tree_ctx)
+            if (x) fastecc_destroy(x);
         if (d->tree_top) fastecc_destroy(d->tree_top);
         d->tree_top = nullptr;
         d->tree_ctx.assign(lgT, nullptr);
         const bool narrow_tree = narrow && lgT + 1 - CHUNK_LOG >= 1 && lgT > leaf_log;
-        for (int k = leaf_log; k < lgT; k++) {
-            if (narrow_tree && (T >> k) <= NARROW_COLUMNS) continue;  // tree_top + chunk_transform_kernel
-            const int rc = create_ntt_ctx(&d->tree_ctx[k], k + 1, 4 * (T >> k), ci.device);
+        for (int lv = leaf_log; lv < lgT; lv++) {
+            if (narrow_tree && (T >> lv) <= NARROW_COLUMNS) continue;  // tree_top + chunk_transform_kernel
+            const int rc = create_ntt_ctx(&d->tree_ctx[lv], lv + 1, 4 * (T >> lv), ci.device);
             if (rc != FASTECC_OK) return rc;
         }
         if (narrow_tree) {
@@ -1127,286 +1198,588 @@ static int decode_prepare_impl(fastecc_ctx* c, const uint8_t* data_present, cons
             if (*b) (void)hipFree(*b);
             *b = nullptr;
         }
-        DEC_TRY(hipMalloc((void**)&d->tree_x, 2 * T * 4));
-        DEC_TRY(hipMalloc((void**)&d->tree_f, 2 * T * 4));
-        DEC_TRY(hipMalloc((void**)&d->tree_y, 2 * T * 4));
-        DEC_TRY(hipMalloc((void**)&d->tree_p, 2 * T * 4));
-        DEC_TRY(hipMalloc((void**)&d->roots, T * 4));
-        DEC_TRY(hipMalloc((void**)&d->dev_erased, (T + 1) * 4));  // + the counter of erased_list_kernel
+        for (uint32_t** b : {&d->tree_x, &d->tree_f, &d->tree_y, &d->tree_p}) HIP_TRY(hipMalloc((void**)b, 2 * T * 4));
+        HIP_TRY(hipMalloc((void**)&d->roots, T * 4));
+        HIP_TRY(hipMalloc((void**)&d->dev_erased, (T + 1) * 4));  // + the counter of erased_list_kernel
         d->tree_T = T;
         d->tree_low = leaf_log;
+        return FASTECC_OK;
     }
-    pt.mark("tree contexts + buffers");
-    if (!d->wpow) {
-        // the table becomes visible to later calls only once the kernel that fills it has been launched without error
-        // (an unfilled table behind a non-null pointer would give silently wrong weights on the next prepare)
-        uint32_t* fresh = nullptr;
-        DEC_TRY(hipMalloc((void**)&fresh, NC * 4));
-        hipLaunchKernelGGL(wpow_kernel, dim3((unsigned)((NC + 255) / 256)), dim3(256), 0, st, fresh, w, (uint32_t)NC);
-        const hipError_t e_fill = hipGetLastError();
-        if (e_fill != hipSuccess) {
-            (void)hipFree(fresh);
-            return hip_code("wpow_kernel", e_fill);
+
+    // the tables by position and block, and the stripe of the recovered blocks
+    int build_tables()
+    {
+        if (!d->wpow) {
+            // the table becomes visible to later calls only once the kernel that fills it has been launched without error
+            // (an unfilled table behind a non-null pointer would give silently wrong weights on the next prepare)
+            uint32_t* fresh = nullptr;
+            HIP_TRY(hipMalloc((void**)&fresh, NC * 4));
+            hipLaunchKernelGGL(wpow_kernel, grid_of(NC), dim3(256), 0, nullptr, fresh, gf::h_root((uint32_t)NC), (uint32_t)NC);
+            const hipError_t e_fill = hipGetLastError();
+            if (e_fill != hipSuccess) {
+                (void)hipFree(fresh);
+                return hip_fail(e_fill, "wpow_kernel");
+            }
+            d->wpow = fresh;
         }
-        d->wpow = fresh;
+        if (!d->dev_state) HIP_TRY(hipMalloc((void**)&d->dev_state, NC));
+        if (!d->fin) HIP_TRY(hipMalloc((void**)&d->fin, NC * 4));
+        if (!d->srcmap) HIP_TRY(hipMalloc((void**)&d->srcmap, NC * 4));
+        if (!d->gout) HIP_TRY(hipMalloc((void**)&d->gout, N * 4));
+        if (parity_factors && !d->gout_par) HIP_TRY(hipMalloc((void**)&d->gout_par, N * 4));
+        // mixed radix: the work stripe of all NC positions, transformed in place; else the N recovered data positions
+        if (!d->recovered) HIP_TRY(hipMalloc((void**)&d->recovered, (mixed ? NC : N) * ci.words * 4));
+        return FASTECC_OK;
     }
-    if (!d->dev_state) DEC_TRY(hipMalloc((void**)&d->dev_state, NC));
-    if (!d->fin) DEC_TRY(hipMalloc((void**)&d->fin, NC * 4));
-    if (!d->srcmap) DEC_TRY(hipMalloc((void**)&d->srcmap, NC * 4));
-    if (!d->gout) DEC_TRY(hipMalloc((void**)&d->gout, N * 4));
-    // parity block j at position 2j + 1 (the (2k,k) layout and its zero-extended relatives with fold 0): a pattern that loses data AND parity
-    // gets the factors of its lost parity blocks too — fastecc_repair then needs no second encode
-    const bool parity_factors = d->erased_parity != 0 && (d->standard || (split_groups != 0 && ci.fold == 0));
-    if (parity_factors && !d->gout_par) DEC_TRY(hipMalloc((void**)&d->gout_par, N * 4));
-    // mixed radix: the work stripe of all NC positions, transformed in place; else the N recovered data positions
-    if (!d->recovered) DEC_TRY(hipMalloc((void**)&d->recovered, (mixed ? NC : N) * ci.words * 4));
-    d->split_ready = false;
-    d->split_repair_ready = false;
-    if (split_groups != 0 && !d->split_unavailable && !d->split) {
-        // ---- the split transform's context and tables (once).  Anything missing — a plan without the tile shapes, no memory for the two extra
-        // stripes — leaves the 2k-point transform in charge; the pattern's unused parity blocks are unused there as well. ----
-        const int rc_split = [&]() -> int {
+
+    // The split transform's context and tables (once).  Anything missing — a plan without the tile shapes, no memory for the two extra stripes —
+    // leaves the 2k-point transform in charge for good (split_unavailable); the pattern's unused parity blocks are unused there as well.
+    int build_split()
+    {
+        const int rc = [&]() -> int {
             // per-block factor (2m + k) / 2k = m / k + 1 / 2
-            int rc = create_ramp_transform_ctx(&d->split, ci.log2k, ci.words * 4, 0, gf::h_inv((uint32_t)N), ci.device, gf::h_inv(2u));
+            const int rc = create_ramp_transform_ctx(&d->split, ci.log2k, ci.words * 4, 0, gf::h_inv((uint32_t)N), ci.device, gf::h_inv(2u));
             if (rc != FASTECC_OK) return rc;
             if (!split_decode_supported(d->split) || split_decode_groups(d->split) != 1024u) return FASTECC_E_UNSUPPORTED;
             for (uint32_t** b : {&d->split_order, &d->split_rows_data, &d->split_rows_parity, &d->split_rows_out, &d->split_pos_parity, &d->split_pos_data_odd,
                                  &d->split_rows_out_parity})
-                DEC_TRY(hipMalloc((void**)b, N * 4));
-            if (!gather_tile_order_device(d->split, d->split_order, st)) return FASTECC_E_UNSUPPORTED;
-            {
-                // the parity half's low levels when few block groups are in use (run_split_decode): what the DIF levels with strides 512 ... 16
-                // make of a 1024-block tile in which block q0 alone is 1 — simulated here exactly as the tile does them, (a, b) -> (a + b,
-                // (a - b) w_2s^i) with the inverse roots; entry [t][g][c] = block g + 16 c for q0 = g + 16 t
-                const uint32_t w1024_inv = gf::h_pow(gf::h_inv(gf::h_mul(w, w)), N / 1024);
-                const uint32_t tables = (uint32_t)split_impulse_max();
-                std::vector<uint32_t> table((size_t)tables * 16 * 64), v(1024), tw(512);
-                for (uint32_t q0 = 0; q0 < 16u * tables; q0++) {
-                    std::fill(v.begin(), v.end(), 0u);
-                    v[q0] = 1;
-                    for (uint32_t sdist = 512; sdist >= 16; sdist >>= 1) {
-                        const uint32_t root = gf::h_pow(w1024_inv, 512 / sdist);  // order 2 * sdist
-                        tw[0] = 1;
-                        for (uint32_t i = 1; i < sdist; i++) tw[i] = gf::h_mul(tw[i - 1], root);
-                        for (uint32_t base = 0; base < 1024; base += 2 * sdist)
-                            for (uint32_t i = 0; i < sdist; i++) {
-                                const uint32_t lo = v[base + i], hi = v[base + i + sdist];
-                                if ((lo | hi) == 0) continue;
-                                v[base + i] = (uint32_t)(((uint64_t)lo + hi) % gf::P);
-                                v[base + i + sdist] = gf::h_mul((uint32_t)(((uint64_t)lo + gf::P - hi) % gf::P), tw[i]);
-                            }
-                    }
-                    const uint32_t t = q0 / 16, g0 = q0 % 16;
-                    for (uint32_t cc = 0; cc < 64; cc++) table[(t * 16 + g0) * 64 + cc] = gf::h_to_mont(v[g0 + 16 * cc]);
-                }
-                DEC_TRY(hipMalloc((void**)&d->split_impulse, table.size() * 4));
-                DEC_TRY(hipMemcpy(d->split_impulse, table.data(), table.size() * 4, hipMemcpyHostToDevice));
-            }
+                HIP_TRY(hipMalloc((void**)b, N * 4));
+            if (!gather_tile_order_device(d->split, d->split_order, nullptr)) return FASTECC_E_UNSUPPORTED;
+            const std::vector<uint32_t> table = split_impulse_table(gf::h_root((uint32_t)NC), N);
+            HIP_TRY(hipMalloc((void**)&d->split_impulse, table.size() * 4));
+            HIP_TRY(hipMemcpy(d->split_impulse, table.data(), table.size() * 4, hipMemcpyHostToDevice));
             const uint32_t neg_half = (uint32_t)(gf::P - gf::h_inv(2u));
-            hipLaunchKernelGGL(split_pos_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, d->wpow, d->split_pos_parity, (uint32_t)N, ci.log2k, neg_half, false);
-            hipLaunchKernelGGL(split_pos_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, d->wpow, d->split_pos_data_odd, (uint32_t)N, ci.log2k, neg_half, true);
-            DEC_TRY(hipGetLastError());
+            hipLaunchKernelGGL(split_pos_kernel, grid_of(N), dim3(256), 0, nullptr, d->wpow, d->split_pos_parity, (uint32_t)N, ci.log2k, neg_half, false);
+            hipLaunchKernelGGL(split_pos_kernel, grid_of(N), dim3(256), 0, nullptr, d->wpow, d->split_pos_data_odd, (uint32_t)N, ci.log2k, neg_half, true);
+            HIP_TRY(hipGetLastError());
             return FASTECC_OK;
         }();
-        if (rc_split == FASTECC_OK) d->split_dirty = 0;
-        if (rc_split != FASTECC_OK) {
-            // nothing half-built stays behind: a later call either builds all of it or none
-            (void)hipGetLastError();
-            if (d->split) fastecc_destroy(d->split);
-            d->split = nullptr;
-            for (uint32_t** b : {&d->split_order, &d->split_rows_data, &d->split_rows_parity, &d->split_rows_out, &d->split_pos_parity, &d->split_impulse, &d->split_r1,
-                                 &d->split_r2, &d->split_pos_data_odd, &d->split_rows_out_parity}) {
-                if (*b) (void)hipFree(*b);
-                *b = nullptr;
-            }
-            if (rc_split != FASTECC_E_NOMEM && rc_split != FASTECC_E_UNSUPPORTED) return rc_split;
-            d->split_unavailable = true;
+        if (rc == FASTECC_OK) {
+            d->split_dirty = 0;
+            return FASTECC_OK;
         }
+        // nothing half-built stays behind: a later call either builds all of it or none
+        (void)hipGetLastError();
+        if (d->split) fastecc_destroy(d->split);
+        d->split = nullptr;
+        for (uint32_t** b : {&d->split_order, &d->split_rows_data, &d->split_rows_parity, &d->split_rows_out, &d->split_pos_parity, &d->split_impulse,
+                             &d->split_r1, &d->split_r2, &d->split_pos_data_odd, &d->split_rows_out_parity}) {
+            if (*b) (void)hipFree(*b);
+            *b = nullptr;
+        }
+        if (rc != FASTECC_E_NOMEM && rc != FASTECC_E_UNSUPPORTED) return rc;
+        d->split_unavailable = true;
+        return FASTECC_OK;
     }
-    if (split_groups != 0 && d->split) {
-        // the parity half's work buffers, by form.  No memory for them: the 2k-point transform serves this pattern (as for a missing tile shape).
-        hipError_t e = hipSuccess;
-        if (split_shift != 0) {
-            const uint64_t rows = N >> split_shift;
-            if (!d->split_small[split_shift]) {
-                const int rc = create_ntt_ctx(&d->split_small[split_shift], ci.log2k - (int)split_shift, ci.words * 4, ci.device);
+
+    // The split transform's work buffers for the parity half, by form.  No memory for them: the 2k-point transform serves this pattern (as for a
+    // missing tile shape) and s.split_groups / split_shift are cleared — the pattern's unused parity blocks stay unused, the 2k-point transform
+    // reads the same factors.
+    int split_buffers()
+    {
+        hipError_t err = hipSuccess;
+        if (s.split_shift != 0) {
+            const uint64_t rows = N >> s.split_shift;
+            if (!d->split_small[s.split_shift]) {
+                const int rc = create_ntt_ctx(&d->split_small[s.split_shift], ci.log2k - (int)s.split_shift, ci.words * 4, ci.device);
                 if (rc != FASTECC_OK && rc != FASTECC_E_NOMEM && rc != FASTECC_E_UNSUPPORTED) return rc;
-                if (rc != FASTECC_OK) e = hipErrorOutOfMemory;
+                if (rc != FASTECC_OK) err = hipErrorOutOfMemory;
             }
-            if (e == hipSuccess && d->split_small_blocks < rows) {
+            if (err == hipSuccess && d->split_small_blocks < rows) {
                 if (d->split_small_buf) (void)hipFree(d->split_small_buf);
                 d->split_small_buf = nullptr;
                 d->split_small_blocks = 0;
-                e = hipMalloc((void**)&d->split_small_buf, rows * ci.words * 4);
-                if (e == hipSuccess) d->split_small_blocks = rows;
+                err = hipMalloc((void**)&d->split_small_buf, rows * ci.words * 4);
+                if (err == hipSuccess) d->split_small_blocks = rows;
             }
         } else if (!d->split_r1 || !d->split_r2) {
-            if (!d->split_r1) e = hipMalloc((void**)&d->split_r1, N * ci.words * 4);
-            if (e == hipSuccess && !d->split_r2) e = hipMalloc((void**)&d->split_r2, N * ci.words * 4);
-            if (e == hipSuccess) e = hipMemsetAsync(d->split_r1, 0, N * ci.words * 4, st);
+            if (!d->split_r1) err = hipMalloc((void**)&d->split_r1, N * ci.words * 4);
+            if (err == hipSuccess && !d->split_r2) err = hipMalloc((void**)&d->split_r2, N * ci.words * 4);
+            if (err == hipSuccess) err = hipMemsetAsync(d->split_r1, 0, N * ci.words * 4, nullptr);
             d->split_dirty = 0;
-            if (e != hipSuccess) {
+            if (err != hipSuccess) {
                 for (uint32_t** b : {&d->split_r1, &d->split_r2}) {
                     if (*b) (void)hipFree(*b);
                     *b = nullptr;
                 }
             }
         }
-        if (e != hipSuccess) {
+        if (err != hipSuccess) {
             (void)hipGetLastError();
-            split_groups = 0;  // (the pattern's unused parity blocks stay unused: the 2k-point transform reads the same factors)
-            split_shift = 0;
+            s.split_groups = 0;
+            s.split_shift = 0;
         }
-    }
-    if (d->standard && d->erased_parity != 0 && !(split_groups != 0 && d->split)) {
-        // repair in one transform (see DecodeState::transform_full): the form for patterns or plans the split transform does not take
-        if (!d->transform_full) {
-            const int rc = create_ramp_transform_ctx(&d->transform_full, lgc, ci.words * 4, 0, gf::h_inv((uint32_t)NC), ci.device);
-            if (rc != FASTECC_OK && rc != FASTECC_E_NOMEM) return rc;
-            d->full_ok = d->transform_full && same_tile_order(d->transform, d->transform_full);
-            if (getenv("FASTECC_TRACE_PREPARE"))
-                fprintf(stderr, "[fastecc prepare] one-transform repair: context %s, same first-pass order %d (%s | %s)\n", d->transform_full ? "built" : "none",
-                        (int)d->full_ok, fastecc_plan_string(d->transform), d->transform_full ? fastecc_plan_string(d->transform_full) : "");
-        }
-    }
-    if (d->standard && !d->tile_order_valid) {
-        if (same_tile_order(d->transform, d->transform)) {  // (a tile first pass: the order exists)
-            DEC_TRY(hipMalloc((void**)&d->tile_order, NC * 4));
-            if (!gather_tile_order_device(d->transform, d->tile_order, st)) return FASTECC_E_DEVICE;
-            DEC_TRY(hipMalloc((void**)&d->fin_first_pass, NC * 4));
-        } else {
-            d->fin_first_pass = d->fin;
-        }
-        d->tile_order_valid = true;
-    }
-    if (!d->standard) d->fin_first_pass = d->fin;
-    {
-        const int rc = call.wait_idle();  // a decode still using the previous pattern
-        if (rc != FASTECC_OK) return rc;
+        return FASTECC_OK;
     }
 
-    pt.mark("tables, tile order");
-    // ---- this pattern ----
-    if (!device_scan) DEC_TRY(hipMemcpyAsync(d->dev_state, state.data(), NC, hipMemcpyHostToDevice, st));
-    auto grid = [](uint64_t items) { return dim3((unsigned)((items + 255) / 256)); };
-    if (!srcmap.empty()) DEC_TRY(hipMemcpyAsync(d->srcmap, srcmap.data(), NC * 4, hipMemcpyHostToDevice, st));
-    else hipLaunchKernelGGL(standard_srcmap_kernel, grid(NC), dim3(256), 0, st, (const uint8_t*)d->dev_state, (uint32_t)NC, d->srcmap);
-    // the list of erased positions (any order: the locator is their product); its counter sits behind the list
-    DEC_TRY(hipMemsetAsync(d->dev_erased + T, 0, 4, st));
-    hipLaunchKernelGGL(erased_list_kernel, grid((NC + 15) / 16), dim3(256), 0, st, (const uint8_t*)d->dev_state, (uint32_t)NC, d->dev_erased, d->dev_erased + T);
-    hipLaunchKernelGGL(roots_kernel, grid(T), dim3(256), 0, st, d->roots, d->dev_erased, d->wpow, (uint32_t)erased_count, (uint32_t)T);
-    // leaves: T / leaf polynomials of degree `leaf`, side by side ([coefficient][polynomial]); the upper half of the
-    // 2*leaf rows the first product needs is zero
-    DEC_TRY(hipMemsetAsync(d->tree_x, 0, 2 * T * 4, st));
-    if (leaf_log == TREE_LOW) hipLaunchKernelGGL(tree_low_levels_kernel<TREE_LOW>, dim3((unsigned)(T >> leaf_log)), dim3(1 << TREE_LOW), 0, st, d->roots, d->tree_x, (uint32_t)(T >> leaf_log));
-    else hipLaunchKernelGGL(leaf_products_kernel, grid(T >> leaf_log), dim3(256), 0, st, d->roots, d->tree_x, (uint32_t)leaf, (uint32_t)(T >> leaf_log));
-    DEC_TRY(hipGetLastError());
+    // ---- this pattern on the device ----
     // 2^log_rows rows of 2^logE words (2^log_rows divides NC): DIF with the forward roots (natural -> bit-reversed rows) or DIT with the inverse
     // roots (bit-reversed -> natural); `top` has 2^(log_rows + logE) / CHUNK rows of CHUNK words
-    auto narrow_transform = [&](fastecc_ctx* top, int log_rows, int logE, const uint32_t* in, uint32_t* out, bool dit) -> int {
+    int narrow_transform(fastecc_ctx* top, int log_rows, int logE, const uint32_t* in, uint32_t* out, bool dit)
+    {
         const int logN1 = log_rows + logE - CHUNK_LOG;
         const uint32_t step_n = (uint32_t)(NC >> log_rows), step_n2 = (uint32_t)(NC >> (CHUNK_LOG - logE));
         if (!dit) {
-            const int rc = transform_bitrev(top, in, out, false, false, CHUNK, st);
+            const int rc = transform_bitrev(top, in, out, false, false, CHUNK, nullptr);
             if (rc != FASTECC_OK) return rc;
-            hipLaunchKernelGGL(chunk_transform_kernel<false>, dim3(1u << logN1), dim3(256), 0, st, out, d->wpow, logE, logN1, step_n, step_n2, (uint32_t)(NC - 1));
+            hipLaunchKernelGGL(chunk_transform_kernel<false>, dim3(1u << logN1), dim3(256), 0, nullptr, out, d->wpow, logE, logN1, step_n, step_n2, (uint32_t)(NC - 1));
             return hipGetLastError() == hipSuccess ? FASTECC_OK : FASTECC_E_DEVICE;
         }
         if (in != out) return FASTECC_E_INVAL;
-        hipLaunchKernelGGL(chunk_transform_kernel<true>, dim3(1u << logN1), dim3(256), 0, st, out, d->wpow, logE, logN1, step_n, step_n2, (uint32_t)(NC - 1));
+        hipLaunchKernelGGL(chunk_transform_kernel<true>, dim3(1u << logN1), dim3(256), 0, nullptr, out, d->wpow, logE, logN1, step_n, step_n2, (uint32_t)(NC - 1));
         if (hipGetLastError() != hipSuccess) return FASTECC_E_DEVICE;
-        return transform_bitrev(top, out, out, true, true, CHUNK, st);
-    };
-    uint32_t* x = d->tree_x;
-    uint32_t* spare = d->tree_y;  // x / spare swap roles level by level; tree_f always holds the transforms
-    for (int k = leaf_log; k < lgT; k++) {
-        const uint64_t deg = 1ull << k, m = T >> k;  // m polynomials of degree deg in x: [2 deg][m], rows deg.. are zero
-        fastecc_ctx* t = d->tree_ctx[k];  // (none: few columns, narrow_transform)
-        int rc = t ? transform_bitrev(t, x, d->tree_f, false, false, (uint32_t)m, st)                   // all of them at once
-                   : narrow_transform(d->tree_top, k + 1, lgT - k, x, d->tree_f, false);
-        if (rc != FASTECC_OK) return rc;
-        const uint32_t scale = gf::h_to_mont(gf::h_inv((uint32_t)(2 * deg)));
-        hipLaunchKernelGGL(pointwise_pairs_kernel, grid(2 * deg * (m / 2)), dim3(256), 0, st, d->tree_f, d->tree_p, (uint32_t)m, 2 * deg * (m / 2), scale);
-        DEC_TRY(hipGetLastError());
-        rc = t ? transform_bitrev(t, d->tree_p, d->tree_p, true, true, (uint32_t)(m / 2), st)          // the products, back in natural order
-               : narrow_transform(d->tree_top, k + 1, lgT - k, d->tree_p, d->tree_p, true);              // (the unused columns ride along)
-        if (rc != FASTECC_OK) return rc;
-        const bool top = k + 1 == lgT;
-        const uint64_t rows = top ? 2 * deg : 4 * deg;
-        hipLaunchKernelGGL(combine_kernel, grid(rows * (m / 2)), dim3(256), 0, st, d->tree_p, x, spare, (uint32_t)deg, (uint32_t)m, rows * (m / 2), top);
-        DEC_TRY(hipGetLastError());
-        std::swap(x, spare);
+        return transform_bitrev(top, out, out, true, true, CHUNK, nullptr);
     }
-    // x now holds the T lower coefficients of L = x^pad * l (monic of degree T), pad = T - |E|
-    hipLaunchKernelGGL(locator_columns_kernel, grid(NC), dim3(256), 0, st, x, d->pattern_buf, (uint32_t)T, (uint32_t)NC);
-    DEC_TRY(hipGetLastError());
+
+    // The locator's product tree: the erased positions' roots, the leaves (T / leaf polynomials of degree `leaf` side by side, [coefficient]
+    // [polynomial]; the upper half of the 2 leaf rows the first product needs is zero), then level by level up.  *coeffs: the buffer that ends
+    // with the T lower coefficients of L = x^pad * l (monic of degree T), pad = T - |E|.
+    int locator_tree(uint32_t** coeffs)
     {
+        hipStream_t st = nullptr;
+        if (!s.device_scan) HIP_TRY(hipMemcpyAsync(d->dev_state, s.state.data(), NC, hipMemcpyHostToDevice, st));
+        if (!s.srcmap.empty()) HIP_TRY(hipMemcpyAsync(d->srcmap, s.srcmap.data(), NC * 4, hipMemcpyHostToDevice, st));
+        else hipLaunchKernelGGL(standard_srcmap_kernel, grid_of(NC), dim3(256), 0, st, (const uint8_t*)d->dev_state, (uint32_t)NC, d->srcmap);
+        // the list of erased positions (any order: the locator is their product); its counter sits behind the list
+        HIP_TRY(hipMemsetAsync(d->dev_erased + T, 0, 4, st));
+        hipLaunchKernelGGL(erased_list_kernel, grid_of((NC + 15) / 16), dim3(256), 0, st, (const uint8_t*)d->dev_state, (uint32_t)NC, d->dev_erased, d->dev_erased + T);
+        hipLaunchKernelGGL(roots_kernel, grid_of(T), dim3(256), 0, st, d->roots, d->dev_erased, d->wpow, (uint32_t)s.erased_count, (uint32_t)T);
+        HIP_TRY(hipMemsetAsync(d->tree_x, 0, 2 * T * 4, st));
+        const uint32_t leaves = (uint32_t)(T >> leaf_log);
+        if (leaf_log == TREE_LOW) hipLaunchKernelGGL(tree_low_levels_kernel<TREE_LOW>, dim3(leaves), dim3(1 << TREE_LOW), 0, st, d->roots, d->tree_x, leaves);
+        else hipLaunchKernelGGL(leaf_products_kernel, grid_of(leaves), dim3(256), 0, st, d->roots, d->tree_x, (uint32_t)(1 << leaf_log), leaves);
+        HIP_TRY(hipGetLastError());
+        uint32_t* x = d->tree_x;
+        uint32_t* spare = d->tree_y;  // x / spare swap roles level by level; tree_f always holds the transforms
+        for (int lv = leaf_log; lv < lgT; lv++) {
+            const uint64_t deg = 1ull << lv, m = T >> lv;  // m polynomials of degree deg in x: [2 deg][m], rows deg.. are zero
+            fastecc_ctx* t = d->tree_ctx[lv];            // (none: few columns, narrow_transform)
+            int rc = t ? transform_bitrev(t, x, d->tree_f, false, false, (uint32_t)m, st)  // all of them at once
+                       : narrow_transform(d->tree_top, lv + 1, lgT - lv, x, d->tree_f, false);
+            if (rc != FASTECC_OK) return rc;
+            const uint32_t scale = gf::h_to_mont(gf::h_inv((uint32_t)(2 * deg)));
+            hipLaunchKernelGGL(pointwise_pairs_kernel, grid_of(2 * deg * (m / 2)), dim3(256), 0, st, d->tree_f, d->tree_p, (uint32_t)m, 2 * deg * (m / 2), scale);
+            HIP_TRY(hipGetLastError());
+            rc = t ? transform_bitrev(t, d->tree_p, d->tree_p, true, true, (uint32_t)(m / 2), st)      // the products, back in natural order
+                   : narrow_transform(d->tree_top, lv + 1, lgT - lv, d->tree_p, d->tree_p, true);  // (the unused columns ride along)
+            if (rc != FASTECC_OK) return rc;
+            const bool top = lv + 1 == lgT;
+            const uint64_t rows = top ? 2 * deg : 4 * deg;
+            hipLaunchKernelGGL(combine_kernel, grid_of(rows * (m / 2)), dim3(256), 0, st, d->tree_p, x, spare, (uint32_t)deg, (uint32_t)m, rows * (m / 2), top);
+            HIP_TRY(hipGetLastError());
+            std::swap(x, spare);
+        }
+        *coeffs = x;
+        return FASTECC_OK;
+    }
+
+    // From the locator's coefficients to the decoder's tables: its values and its derivative's by one transform of a two-column stripe, fin and
+    // gout (gout_par) by finish_tables_kernel, fin in the first pass's order, and the split transform's rows
+    int locator_tables(const uint32_t* coeffs)
+    {
+        hipStream_t st = nullptr;
+        hipLaunchKernelGGL(locator_columns_kernel, grid_of(NC), dim3(256), 0, st, coeffs, d->pattern_buf, (uint32_t)T, (uint32_t)NC);
+        HIP_TRY(hipGetLastError());
         // (power of two: the values stay in bit-reversed order, finish_tables_kernel reads them there — the reordering pass of fastecc_ntt was 87 us)
         const int rc = mixed               ? mixed_dif(d->pattern_ntt, d->pattern_buf, d->pattern_buf, st)
                        : d->pattern_narrow ? narrow_transform(d->pattern_ntt, lgc, 1, d->pattern_buf, d->pattern_buf, false)
                                            : transform_bitrev(d->pattern_ntt, d->pattern_buf, d->pattern_buf, false, false, 2, st);
         if (rc != FASTECC_OK) return rc;
-    }
-    hipLaunchKernelGGL(finish_tables_kernel, grid(NC), dim3(256), 0, st, d->pattern_buf, d->dev_state, d->wpow, d->fin, d->gout, (uint32_t)NC,
-                       (uint32_t)(T - erased_count), e, (uint32_t)ci.user_k, (uint32_t)(mixed ? ci.q : 1), lgc,
-                       parity_factors ? d->gout_par : nullptr, !mixed);
-    DEC_TRY(hipGetLastError());
-    if (d->fin_first_pass != d->fin) {
-        hipLaunchKernelGGL(permute_kernel, grid(NC), dim3(256), 0, st, d->fin, d->tile_order, d->fin_first_pass, (uint32_t)NC);
-        DEC_TRY(hipGetLastError());
-    }
-    if (split_groups != 0 && d->split) {
+        hipLaunchKernelGGL(finish_tables_kernel, grid_of(NC), dim3(256), 0, st, d->pattern_buf, d->dev_state, d->wpow, d->fin, d->gout, (uint32_t)NC,
+                           (uint32_t)(T - s.erased_count), e, (uint32_t)ci.user_k, (uint32_t)(mixed ? ci.q : 1), lgc, parity_factors ? d->gout_par : nullptr,
+                           !mixed);
+        HIP_TRY(hipGetLastError());
+        if (d->fin_first_pass != d->fin) {
+            hipLaunchKernelGGL(permute_kernel, grid_of(NC), dim3(256), 0, st, d->fin, d->tile_order, d->fin_first_pass, (uint32_t)NC);
+            HIP_TRY(hipGetLastError());
+        }
+        if (s.split_groups == 0 || !d->split) return FASTECC_OK;
         // (fastecc_repair in the (2k,k) layout: the lost parity blocks' factors too — gout_par is filled above for such patterns)
         const bool with_parity = parity_factors && d->gout_par != nullptr;
-        hipLaunchKernelGGL(split_rows_kernel, grid(N), dim3(256), 0, st, d->fin, d->gout, d->split_order, d->split_rows_data, d->split_rows_parity, d->split_rows_out,
-                           (uint32_t)N, with_parity ? d->gout_par : nullptr, with_parity ? d->split_rows_out_parity : nullptr);
+        hipLaunchKernelGGL(split_rows_kernel, grid_of(N), dim3(256), 0, st, d->fin, d->gout, d->split_order, d->split_rows_data, d->split_rows_parity,
+                           d->split_rows_out, (uint32_t)N, with_parity ? d->gout_par : nullptr, with_parity ? d->split_rows_out_parity : nullptr);
         d->split_repair_ready = with_parity;
-        DEC_TRY(hipGetLastError());
-        d->split_shift = split_shift;
-        if (split_shift == 0 && d->split_dirty > split_groups) {
+        HIP_TRY(hipGetLastError());
+        d->split_shift = s.split_shift;
+        if (s.split_shift == 0 && d->split_dirty > s.split_groups) {
             // rows of groups this pattern does not write any more: group g = blocks g + (t << 10)
             const size_t row = ci.words * 4;
-            DEC_TRY(hipMemset2DAsync(d->split_r1 + (size_t)split_groups * ci.words, 1024 * row, 0, (d->split_dirty - split_groups) * row,
+            HIP_TRY(hipMemset2DAsync(d->split_r1 + (size_t)s.split_groups * ci.words, 1024 * row, 0, (d->split_dirty - s.split_groups) * row,
                                      split_decode_group_rows(d->split), st));
-            d->split_dirty = split_groups;
+            d->split_dirty = s.split_groups;
         }
-        d->split_groups = split_shift == 0 ? split_groups : 0;
+        d->split_groups = s.split_shift == 0 ? s.split_groups : 0;
         d->split_ready = true;
+        return FASTECC_OK;
     }
-    DEC_TRY(hipStreamSynchronize(st));
-    pt.mark("this pattern (device)");
-    d->ready = true;
-    return FASTECC_OK;
-}
+};
 
-static int decode_impl(fastecc_ctx* c, void* data, const void* parity, int mem_kind, void* stream, void* parity_out);
-
-int fastecc_decode(fastecc_ctx* c, void* data, const void* parity, int mem_kind, void* stream)
+int decode_prepare_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t* parity_present)
 {
-    try {
-        return decode_impl(c, data, parity, mem_kind, stream, nullptr);
-    } catch (const std::bad_alloc&) {
-        return FASTECC_E_NOMEM;
-    } catch (...) {
-        return FASTECC_E_DEVICE;
-    }
+    if (!c || !data_present || !parity_present) return FASTECC_E_INVAL;
+    if (sharded_of(c)) return sharded_decode_prepare(c, data_present, parity_present);
+    const CtxInfo ci = info_of(c);
+    if (ci.field == FASTECC_FIELD_GF_P61_SQUARED) return prepare_p61(c, ci, data_present, parity_present);
+    if (ci.field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
+    if (ci.pitch != ci.words) return FASTECC_E_UNSUPPORTED;
+    Prepare p(c, data_present, parity_present);
+    bool done = false;
+    const int rc = p.direct(&done);
+    return rc != FASTECC_OK || done ? rc : p.transform_path();
 }
 
-int fastecc_repair(fastecc_ctx* c, void* data, void* parity, int mem_kind, void* stream)
+// ---- fastecc_decode / fastecc_repair ----
+// The 64-bit field's decode (gf61_decode.hip), the context's call lock held.  Codes other than (2N,N): the padded (2N,N) codeword is decoded in
+// the context's two work stripes and the caller's blocks are copied back.
+int decode_p61(fastecc_ctx* c, CallScope& call, void* data, const void* parity, int mem_kind, hipStream_t st, void* parity_out)
 {
-    try {
-        return decode_impl(c, data, parity, mem_kind, stream, parity);
-    } catch (const std::bad_alloc&) {
-        return FASTECC_E_NOMEM;
-    } catch (...) {
-        return FASTECC_E_DEVICE;
+    if ((((uintptr_t)data | (uintptr_t)parity) & 15u)) return FASTECC_E_INVAL;
+    p61::Decoder* d61 = decoder61_of(c);
+    if (!p61::decoder_ready(d61)) return FASTECC_E_INVAL;
+    const CtxInfo ci = info_of(c);
+    DeviceGuard dg(ci.device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    int rc = call.begin(st);  // the decoder's work stripe and tables are internal buffers
+    if (rc != FASTECC_OK) return rc;
+    void* prof = nullptr;
+    const p61::LaunchHooks* hooks = p61_profile_hooks(c, &prof);
+    p61::Path* encoder = parity_out ? p61_path_of(c) : nullptr;
+    if (!ci.zero_extended) {
+        rc = mem_kind == FASTECC_MEM_DEVICE ? p61::decode(d61, (uint64_t*)data, (uint64_t*)const_cast<void*>(parity), encoder, st, hooks)
+                                            : p61::decode_host(d61, data, const_cast<void*>(parity), encoder, st, hooks);
+    } else if (mem_kind != FASTECC_MEM_DEVICE) {
+        (void)call.end(st);
+        return FASTECC_E_UNSUPPORTED;
+    } else {
+        const size_t row = ci.words * 4, prow = row * (size_t)ci.p61_stride;
+        uint64_t *wd = nullptr, *wp = nullptr;
+        rc = p61_work_stripes(c, &wd, &wp);
+        auto step = [&](hipError_t e, const char* what) {
+            if (rc == FASTECC_OK && e != hipSuccess) rc = hip_fail(e, what);
+        };
+        if (rc == FASTECC_OK) {
+            step(hipMemcpyAsync(wd, data, ci.user_k * row, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync(data)");
+            step(hipMemsetAsync((char*)wd + ci.user_k * row, 0, (ci.k - ci.user_k) * row, st), "hipMemsetAsync");
+            step(hipMemcpy2DAsync(wp, prow, parity, row, row, ci.user_m, hipMemcpyDeviceToDevice, st), "hipMemcpy2DAsync(parity)");
+        }
+        if (rc == FASTECC_OK) rc = p61::decode(d61, wd, wp, encoder, st, hooks);
+        if (rc == FASTECC_OK) {
+            step(hipMemcpyAsync(data, wd, ci.user_k * row, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync(data back)");
+            if (parity_out) step(hipMemcpy2DAsync(parity_out, row, wp, prow, row, ci.user_m, hipMemcpyDeviceToDevice, st), "hipMemcpy2DAsync(parity back)");
+        }
     }
+    p61_profile_done(prof);
+    const int rc_end = call.end(st);
+    return rc != FASTECC_OK ? rc : rc_end;
 }
 
-static int decode_locked(fastecc_ctx* c, CallScope& call, void* data, const void* parity, int mem_kind, void* stream, void* parity_out);
+// The direct path's passes over a stripe or a batch: pass(p, parity_in, data_out, parity_out) runs one of them.  Data and parity lost with a table
+// for both: one pass over the survivors writes both (fastecc_decode: the data only); else the lost data, then (rebuild) the lost parity from it.
+template <class Pass> int direct_passes(const DecodeState* d, bool rebuild, uint32_t* data, const uint32_t* parity, uint32_t* parity_out, Pass&& pass)
+{
+    if (d->sub_both && (rebuild || d->sub_only_both)) return pass(d->direct_both, parity, data, rebuild ? parity_out : nullptr);
+    if (d->sub_lost_data > 0) {
+        const int rc = pass(d->direct_data, parity, data, nullptr);
+        if (rc != FASTECC_OK) return rc;
+    }
+    return rebuild ? pass(d->direct_parity, nullptr, nullptr, parity_out) : FASTECC_OK;
+}
 
-// parity_out != null (== parity): also rebuild the lost parity blocks from the repaired data
-static int decode_impl(fastecc_ctx* c, void* data, const void* parity, int mem_kind, void* stream, void* parity_out)
+// a grow-only buffer of `need` words, device or pinned host memory (false: no memory, the old buffer is gone as well)
+bool grow(uint32_t** p, uint64_t* have, uint64_t need, bool host)
+{
+    if (*have >= need) return true;
+    if (*p) (void)(host ? hipHostFree(*p) : hipFree(*p));
+    *p = nullptr;
+    *have = 0;
+    if ((host ? hipHostMalloc((void**)p, need * 4, hipHostMallocDefault) : hipMalloc((void**)p, need * 4)) != hipSuccess) return false;
+    *have = need;
+    return true;
+}
+
+// One stripe's decode of a GF(0xFFF00001) code, the call lock held and the internal buffers ordered on `st`
+struct StripeDecode {
+    fastecc_ctx* c;
+    DecodeState* d;
+    CtxInfo ci;
+    hipStream_t st;
+    bool rebuild;            // fastecc_repair of a pattern that lost parity blocks
+    uint32_t* data;          // the data stripe on the device (FASTECC_MEM_HOST: the staging copy)
+    const uint32_t* parity;  // the parity stripe ...
+    uint32_t* parity_out;    // where the rebuilt parity blocks go
+    uint64_t N;              // the transform order
+    size_t block;            // bytes per block
+    uint32_t S;              // words per block
+
+    // FASTECC_MEM_HOST: the codeword staged in the decoder's stripe (parity, then data) — of the parity stripe only what the decoder will read where
+    // that is known to be a few blocks or block groups.  *rows_only: only the rebuilt blocks will travel back (few enough of them, their rows known).
+    int stage_host(const void* host_data, const void* host_parity, bool* rows_only)
+    {
+        const size_t data_bytes = ci.user_k * block, parity_bytes = ci.user_m * block;
+        if (!d->parity_dev) HIP_TRY(hipMalloc((void**)&d->parity_dev, parity_bytes + data_bytes));
+        if (d->host_lists_of != d->pattern_serial) {
+            // the rows that travel back: known from the set-up (few losses), else read off the decoder's tables once per pattern
+            d->host_lost_data.clear();
+            d->host_lost_parity.clear();
+            if (d->erased_data + d->erased_parity <= (ci.user_k + ci.user_m) / 8 && d->parity_lost && (d->erased_data == 0 || d->gout)) {
+                std::vector<uint32_t> flags(std::max(ci.user_k, ci.user_m));
+                if (d->erased_data != 0) {
+                    HIP_TRY(hipMemcpy(flags.data(), d->gout, ci.user_k * 4, hipMemcpyDeviceToHost));
+                    for (uint64_t i = 0; i < ci.user_k; i++)
+                        if (flags[i] != 0) d->host_lost_data.push_back((uint32_t)i);
+                }
+                HIP_TRY(hipMemcpy(flags.data(), d->parity_lost, ci.user_m * 4, hipMemcpyDeviceToHost));
+                for (uint64_t q = 0; q < ci.user_m; q++)
+                    if (flags[q] != 0) d->host_lost_parity.push_back((uint32_t)q);
+                if (d->host_lost_data.size() != d->erased_data) d->host_lost_data.clear(), d->host_lost_parity.clear();  // (tables of another shape: whole stripes back)
+            }
+            d->host_lists_of = d->pattern_serial;
+        }
+        const uint64_t back = (d->erased_data != 0 ? d->host_lost_data.size() : 0) + (rebuild ? d->host_lost_parity.size() : 0);
+        *rows_only = back != 0 && (d->erased_data == 0 || d->host_lost_data.size() == d->erased_data) &&
+                     (!rebuild || d->host_lost_parity.size() == d->erased_parity) && back <= (ci.user_k + ci.user_m) / 8;
+        const bool partial = !rebuild || *rows_only;  // (a repair that copies the whole parity stripe back must have staged all of it)
+        const bool split = !d->sub && d->split_ready && d->standard && d->erased_data != 0 && partial;
+        if (split && d->split_shift != 0) {
+            // split transform, small form: the parity blocks at multiples of 2^shift are all it reads — one strided copy of every 2^shift-th block
+            const size_t pitch = block << d->split_shift;
+            HIP_TRY(hipMemcpy2DAsync(d->parity_dev, pitch, host_parity, pitch, block, (ci.user_m + (1ull << d->split_shift) - 1) >> d->split_shift, hipMemcpyHostToDevice, st));
+        } else if (split && d->split_groups < 512) {
+            // group form: groups g < split_groups = blocks g + 1024 t, one strided copy
+            HIP_TRY(hipMemcpy2DAsync(d->parity_dev, 1024 * block, host_parity, 1024 * block, (size_t)d->split_groups * block, ci.user_m / 1024, hipMemcpyHostToDevice, st));
+        } else if (d->sub && partial) {
+            // few losses: the direct path reads as many parity blocks as data blocks are lost (at most 256 copies of a block)
+            for (uint32_t q : d->host_parity_used)
+                HIP_TRY(hipMemcpyAsync(d->parity_dev + (size_t)q * S, (const char*)host_parity + (size_t)q * block, block, hipMemcpyHostToDevice, st));
+        } else {
+            HIP_TRY(hipMemcpyAsync(d->parity_dev, host_parity, parity_bytes, hipMemcpyHostToDevice, st));
+        }
+        HIP_TRY(hipMemcpyAsync(d->parity_dev + ci.user_m * S, host_data, data_bytes, hipMemcpyHostToDevice, st));
+        parity = parity_out = d->parity_dev;
+        data = d->parity_dev + ci.user_m * S;
+        return FASTECC_OK;
+    }
+
+    // any layout, few losses (profile: one "direct_pass" per read of the stripe)
+    int direct()
+    {
+        return direct_passes(d, rebuild, data, parity, parity_out, [&](DirectPass* p, const uint32_t* par_in, uint32_t* data_to, uint32_t* par_to) {
+            void* scope = profile_scope_begin(c, st, "direct_pass", (ci.user_k + (uint64_t)d->sub_lost_data) * block);
+            const int rc = direct_run(p, data, par_in, data_to, par_to, S, d->direct_kernel, st);
+            profile_scope_end(scope);
+            return rc;
+        });
+    }
+
+    // The transform path: fastecc_repair in one transform where the pattern's tables allow it, else the lost data and then the lost parity from
+    // one more encode
+    int transform()
+    {
+        if (rebuild && d->erased_data != 0) {
+            bool done = false;
+            int rc = d->split_ready && d->split_repair_ready ? repair_split(&done) : FASTECC_OK;
+            if (rc == FASTECC_OK && !done && d->standard && d->transform_full && d->full_ok && d->gout_par) rc = repair_full(&done);
+            if (rc != FASTECC_OK || done) return rc;
+        }
+        if (d->erased_data != 0) {
+            const int rc = decode_data();
+            if (rc != FASTECC_OK) return rc;
+        }
+        return rebuild ? reencode_parity() : FASTECC_OK;
+    }
+
+    // split transform, small form: the rows of the parity half in use (multiples of 2^shift), times l, and their stand-alone DIF in place; then
+    // the split transform over the data stripe and that addend, whose last pass writes the rebuilt blocks into the data stripe (odd: fastecc_repair's
+    // second chain too).  (The gather reads parity block (h >> fold) for position h itself: no staging stripe for codes with fewer parity blocks.)
+    int split_small(const SplitRepair* odd)
+    {
+        launch_rows(split_small_gather_kernel<4>, split_small_gather_kernel<1>, N >> d->split_shift, S, {parity, d->split_small_buf}, st, parity, d->split_small_buf,
+                    d->fin, S, (int)d->split_shift, ci.fold, (uint32_t)ci.user_m);
+        HIP_TRY(hipGetLastError());
+        const int rc = transform_bitrev(d->split_small[d->split_shift], d->split_small_buf, d->split_small_buf, false, true, S, st);
+        if (rc != FASTECC_OK) return rc;
+        return run_split_decode(d->split, data, nullptr, d->split_rows_data, nullptr, 0, d->split_pos_parity, d->recovered, nullptr, nullptr, d->split_rows_out,
+                                data, nullptr, (uint32_t)ci.user_k, (uint32_t)ci.user_m, st, odd, d->split_small_buf, d->split_shift);
+    }
+
+    // fastecc_repair through the split transform: the data chain as in fastecc_decode, and a second MID + DIT over the same two halves for x p'(x)
+    // at the odd positions — the lost parity blocks, written straight into the parity stripe.  No room for the extra k-block stripe, or a plan the
+    // form does not take: *done stays false.
+    int repair_split(bool* done)
+    {
+        if (!d->split_q2 && hipMalloc((void**)&d->split_q2, N * block) != hipSuccess) {
+            (void)hipGetLastError();
+            d->split_q2 = nullptr;
+            return FASTECC_OK;
+        }
+        const SplitRepair odd{d->split_q2, d->split_pos_data_odd, d->split_rows_out_parity, parity_out};
+        d->split_dirty = std::max(d->split_dirty, d->split_groups);  // (before the launches: a failure half way must not hide written groups)
+        void* scope = profile_scope_begin(c, st, "repair_split_transform", (5 * N + (uint64_t)d->split_groups * split_decode_group_rows(d->split)) * block);
+        const int rc = d->split_shift != 0 ? split_small(&odd)
+                                           : run_split_decode(d->split, data, parity, d->split_rows_data, d->split_rows_parity, d->split_groups, d->split_pos_parity,
+                                                              d->recovered, d->split_r1, d->split_r2, d->split_rows_out, data, d->split_impulse,
+                                                              (uint32_t)ci.user_k, (uint32_t)ci.user_m, st, &odd);
+        profile_scope_end(scope);
+        if (rc == FASTECC_E_UNSUPPORTED) return FASTECC_OK;
+        *done = rc == FASTECC_OK;
+        return rc;
+    }
+
+    // fastecc_repair, (2k,k) layout: x p'(x) at all 2k positions — the even rows give the lost data, the odd rows the lost parity.  No room for
+    // the 2k-block stripe, or a plan whose first pass cannot read the codeword: *done stays false.
+    int repair_full(bool* done)
+    {
+        if (!d->recovered_full && hipMalloc((void**)&d->recovered_full, d->positions * (size_t)S * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            return FASTECC_OK;
+        }
+        const int rc = run_gathered(d->transform_full, data, parity, d->fin_first_pass, d->recovered_full, st);
+        if (rc != FASTECC_OK) return rc == FASTECC_E_UNSUPPORTED ? FASTECC_OK : rc;
+        launch_rows(decode_scatter_kernel<4>, decode_scatter_kernel<1>, N, S, {data, parity_out, d->recovered_full}, st, d->recovered_full, data, d->gout, S, 2u * S, S);
+        launch_rows(decode_scatter_kernel<4>, decode_scatter_kernel<1>, N, S, {data, parity_out, d->recovered_full}, st, d->recovered_full + S, parity_out, d->gout_par,
+                    S, 2u * S, S);
+        HIP_TRY(hipGetLastError());
+        *done = true;
+        return FASTECC_OK;
+    }
+
+    // The lost data through the split transform (two half-size transforms instead of one of size 2k, see "even / odd split"), whose last pass
+    // writes the rebuilt blocks straight into the data stripe.  FASTECC_E_UNSUPPORTED: not on this plan, or no room for the staging stripe.
+    int decode_split()
+    {
+        if (d->split_shift != 0) {
+            void* scope = profile_scope_begin(c, st, "decode_split_transform", (3 * N + 3 * (N >> d->split_shift)) * block);
+            const int rc = split_small(nullptr);
+            profile_scope_end(scope);
+            return rc;
+        }
+        if (ci.fold > 0 && !d->split_r0 && hipMalloc((void**)&d->split_r0, N * block) != hipSuccess) {
+            (void)hipGetLastError();
+            d->split_r0 = nullptr;
+            return FASTECC_E_UNSUPPORTED;
+        }
+        void* scope = profile_scope_begin(c, st, "decode_split_transform", (3 * N + (uint64_t)d->split_groups * split_decode_group_rows(d->split)) * block);
+        const uint32_t* parity_half = parity;
+        uint32_t parity_half_blocks = (uint32_t)ci.user_m;
+        if (ci.fold > 0) {
+            // fewer parity blocks than data blocks: block j belongs at j << fold of the parity half — the blocks in use are copied there
+            launch_rows(split_stage_kernel<4>, split_stage_kernel<1>, ci.user_m, S, {parity, d->split_r0}, st, parity, d->split_r0, d->fin, S, ci.fold);
+            parity_half = d->split_r0;
+            parity_half_blocks = (uint32_t)N;
+        }
+        d->split_dirty = std::max(d->split_dirty, d->split_groups);  // (before the launches, as in repair_split)
+        const int rc = run_split_decode(d->split, data, parity_half, d->split_rows_data, d->split_rows_parity, d->split_groups, d->split_pos_parity, d->recovered,
+                                        d->split_r1, d->split_r2, d->split_rows_out, data, d->split_impulse, (uint32_t)ci.user_k, parity_half_blocks, st);
+        profile_scope_end(scope);
+        return rc;
+    }
+
+    // The lost data blocks: the split transform, else the 2k-point one.  The (2k,k) layout lets the transform's first pass read the two halves of
+    // the codeword itself (no gather pass).  The other codes do not hold every position in memory: they take the table-driven gather, which never
+    // touches a position whose factor is zero, instead of a tile that reads first and multiplies by zero afterwards.
+    int decode_data()
+    {
+        int rc = d->split_ready ? decode_split() : FASTECC_E_UNSUPPORTED;
+        if (rc == FASTECC_OK) return FASTECC_OK;
+        if (rc == FASTECC_E_UNSUPPORTED && d->standard) {
+            void* scope = profile_scope_begin(c, st, "decode_transform_2k", 3 * N * block);
+            rc = run_gathered(d->transform, data, parity, d->fin_first_pass, d->recovered, st);
+            profile_scope_end(scope);
+        }
+        const bool fused = rc == FASTECC_OK;
+        if (!fused && rc != FASTECC_E_UNSUPPORTED) return rc;
+        uint32_t* work = d->recovered;
+        if (!d->mixed && !fused && (rc = scratch_of(d->transform, &work)) != FASTECC_OK) return rc;  // (only the unfused form gathers into it)
+        if (!fused) {
+            launch_rows(decode_gather_kernel<4>, decode_gather_kernel<1>, d->positions, S, {data, parity, work, d->recovered}, st, data, parity, work, d->fin,
+                        d->srcmap, S, S, S);
+            HIP_TRY(hipGetLastError());
+            rc = fastecc_encode(d->transform, work, d->mixed ? work : d->recovered, FASTECC_MEM_DEVICE, st);
+            if (rc != FASTECC_OK) return rc;
+        }
+        // (mixed radix: data position i is row 2i of the transformed work stripe)
+        launch_rows(decode_scatter_kernel<4>, decode_scatter_kernel<1>, N, S, {data, parity, work, d->recovered}, st, d->recovered, data, d->gout, S,
+                    d->mixed ? 2u * S : S, S);
+        HIP_TRY(hipGetLastError());
+        return FASTECC_OK;
+    }
+
+    // The lost parity blocks are whatever the encoder makes of the (now complete) data: one more encode into a stripe of the decoder's, from which
+    // only the lost blocks are copied — the surviving ones are left as they are
+    int reencode_parity()
+    {
+        if (!d->parity_again) HIP_TRY(hipMalloc((void**)&d->parity_again, ci.user_m * block));
+        const int rc = encode_unlocked(c, data, d->parity_again, st);
+        if (rc != FASTECC_OK) return rc;
+        launch_rows(restore_parity_kernel<4>, restore_parity_kernel<1>, ci.user_m, S, {parity_out, d->parity_again}, st, d->parity_again, parity_out, d->parity_lost, S);
+        HIP_TRY(hipGetLastError());
+        return FASTECC_OK;
+    }
+
+    // FASTECC_MEM_HOST: the rebuilt blocks back to the caller's stripes.  rows_only: packed side by side on the device, one copy into a pinned
+    // landing buffer, and a memcpy per block on the host — the repair has already run, so if one of the buffers of this shortcut cannot be had the
+    // whole stripes go back instead.
+    int copy_back(void* host_data, void* host_parity, bool rows_only)
+    {
+        const uint64_t nd = d->erased_data != 0 ? d->host_lost_data.size() : 0, np = rebuild ? d->host_lost_parity.size() : 0;
+        if (rows_only && grow(&d->lost_rows_dev, &d->lost_rows_cap, nd + np, false) && grow(&d->pack_dev, &d->pack_words, (nd + np) * S, false) &&
+            grow(&d->pack_host, &d->pack_host_words, (nd + np) * S, true)) {
+            if (nd) HIP_TRY(hipMemcpyAsync(d->lost_rows_dev, d->host_lost_data.data(), nd * 4, hipMemcpyHostToDevice, st));
+            if (np) HIP_TRY(hipMemcpyAsync(d->lost_rows_dev + nd, d->host_lost_parity.data(), np * 4, hipMemcpyHostToDevice, st));
+            if (nd)
+                launch_rows(pack_rows_kernel<4>, pack_rows_kernel<1>, nd, S, {data, d->parity_dev, d->pack_dev}, st, (const uint32_t*)data, d->lost_rows_dev,
+                            d->pack_dev, S);
+            if (np)
+                launch_rows(pack_rows_kernel<4>, pack_rows_kernel<1>, np, S, {data, d->parity_dev, d->pack_dev}, st, (const uint32_t*)d->parity_dev,
+                            d->lost_rows_dev + nd, d->pack_dev + nd * S, S);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(d->pack_host, d->pack_dev, (nd + np) * (size_t)S * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            for (uint64_t r = 0; r < nd; r++) memcpy((char*)host_data + (size_t)d->host_lost_data[r] * block, d->pack_host + r * S, block);
+            for (uint64_t r = 0; r < np; r++) memcpy((char*)host_parity + (size_t)d->host_lost_parity[r] * block, d->pack_host + (nd + r) * S, block);
+            return FASTECC_OK;
+        }
+        if (rows_only) (void)hipGetLastError();  // out of memory for the shortcut only
+        if (d->erased_data != 0) {
+            const int rc = download_pageable(c, host_data, data, ci.user_k * block, st);
+            if (rc != FASTECC_OK) return rc;
+        }
+        if (rebuild) {
+            const int rc = download_pageable(c, host_parity, d->parity_dev, ci.user_m * block, st);
+            if (rc != FASTECC_OK) return rc;
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+        return FASTECC_OK;
+    }
+};
+
+// one stripe, the context's call lock held (fastecc_decode_batch runs the transform path through this, stripe by stripe).  parity_out != null
+// (== parity): also rebuild the lost parity blocks
+int decode_locked(fastecc_ctx* c, CallScope& call, void* data, const void* parity, int mem_kind, void* stream, void* parity_out)
+{
+    if (info_of(c).field == FASTECC_FIELD_GF_P61_SQUARED) return decode_p61(c, call, data, parity, mem_kind, (hipStream_t)stream, parity_out);
+    DecodeState* d = decoder_of(c);
+    if (!d || !d->ready) return FASTECC_E_INVAL;  // fastecc_decode_prepare first
+    const bool rebuild = parity_out != nullptr && d->erased_parity != 0;
+    if (d->erased_data == 0 && !rebuild) return FASTECC_OK;
+    const CtxInfo ci = info_of(c);
+    if (ci.pitch != ci.words) return FASTECC_E_UNSUPPORTED;  // the gather / scatter passes address contiguous stripes
+    DeviceGuard dg(ci.device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = call.begin(st);
+    if (rc != FASTECC_OK) return rc;
+    EndScope end{call, st};
+    StripeDecode j{c, d, ci, st, rebuild, (uint32_t*)data, (const uint32_t*)parity, (uint32_t*)parity_out, d->mixed ? (uint64_t)ci.q * ci.k : ci.k, ci.words * 4,
+                   (uint32_t)ci.words};
+    const bool host = mem_kind == FASTECC_MEM_HOST;
+    bool rows_only = false;
+    if (host && (rc = j.stage_host(data, parity, &rows_only)) != FASTECC_OK) return rc;
+    if ((rc = d->sub ? j.direct() : j.transform()) != FASTECC_OK) return rc;
+    return host ? j.copy_back(data, parity_out, rows_only) : FASTECC_OK;
+}
+
+int decode_impl(fastecc_ctx* c, void* data, const void* parity, int mem_kind, void* stream, void* parity_out)
 {
     if (!c || !data || !parity || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
     if (sharded_of(c)) return sharded_decode_stripe(c, data, const_cast<void*>(parity), mem_kind, parity_out != nullptr, (hipStream_t)stream);
@@ -1416,407 +1789,11 @@ static int decode_impl(fastecc_ctx* c, void* data, const void* parity, int mem_k
     return decode_locked(c, call, data, parity, mem_kind, stream, parity_out);
 }
 
-// one stripe, the context's call lock held (fastecc_decode_batch runs the transform path through this, stripe by stripe)
-static int decode_locked(fastecc_ctx* c, CallScope& call, void* data, const void* parity, int mem_kind, void* stream, void* parity_out)
-{
-    if (info_of(c).field == FASTECC_FIELD_GF_P61_SQUARED) {
-        if ((((uintptr_t)data | (uintptr_t)parity) & 15u)) return FASTECC_E_INVAL;
-        p61::Decoder* d61 = decoder61_of(c);
-        if (!p61::decoder_ready(d61)) return FASTECC_E_INVAL;
-        DeviceScope ds61(info_of(c).device);
-        if (!ds61.ok) return FASTECC_E_DEVICE;
-        int rc61 = call.begin((hipStream_t)stream);  // the decoder's work stripe and tables are internal buffers
-        if (rc61 != FASTECC_OK) return rc61;
-        const CtxInfo ci61 = info_of(c);
-        void* prof61 = nullptr;
-        const p61::LaunchHooks* hooks61 = p61_profile_hooks(c, &prof61);
-        if (ci61.zero_extended) {
-            // codes other than (2N,N): decode the padded (2N,N) codeword in the context's two work stripes and copy the caller's blocks back
-            if (mem_kind != FASTECC_MEM_DEVICE) {
-                (void)call.end((hipStream_t)stream);
-                return FASTECC_E_UNSUPPORTED;
-            }
-            hipStream_t st61 = (hipStream_t)stream;
-            const size_t row = ci61.words * 4, prow = row * (size_t)ci61.p61_stride;
-            uint64_t *wd = nullptr, *wp = nullptr;
-            rc61 = p61_work_stripes(c, &wd, &wp);
-            auto step = [&](hipError_t e, const char* what) {
-                if (rc61 == FASTECC_OK && e != hipSuccess) rc61 = hip_code(what, e);
-            };
-            if (rc61 == FASTECC_OK) {
-                step(hipMemcpyAsync(wd, data, ci61.user_k * row, hipMemcpyDeviceToDevice, st61), "hipMemcpyAsync(data)");
-                step(hipMemsetAsync((char*)wd + ci61.user_k * row, 0, (ci61.k - ci61.user_k) * row, st61), "hipMemsetAsync");
-                step(hipMemcpy2DAsync(wp, prow, parity, row, row, ci61.user_m, hipMemcpyDeviceToDevice, st61), "hipMemcpy2DAsync(parity)");
-            }
-            if (rc61 == FASTECC_OK) rc61 = p61::decode(d61, wd, wp, parity_out ? p61_path_of(c) : nullptr, st61, hooks61);
-            if (rc61 == FASTECC_OK) {
-                step(hipMemcpyAsync(data, wd, ci61.user_k * row, hipMemcpyDeviceToDevice, st61), "hipMemcpyAsync(data back)");
-                if (parity_out) step(hipMemcpy2DAsync(parity_out, row, wp, prow, row, ci61.user_m, hipMemcpyDeviceToDevice, st61), "hipMemcpy2DAsync(parity back)");
-            }
-            p61_profile_done(prof61);
-            const int rc_end61 = call.end((hipStream_t)stream);
-            return rc61 != FASTECC_OK ? rc61 : rc_end61;
-        }
-        rc61 = mem_kind == FASTECC_MEM_DEVICE
-                   ? p61::decode(d61, (uint64_t*)data, (uint64_t*)const_cast<void*>(parity), parity_out ? p61_path_of(c) : nullptr, (hipStream_t)stream, hooks61)
-                   : p61::decode_host(d61, data, const_cast<void*>(parity), parity_out ? p61_path_of(c) : nullptr, (hipStream_t)stream, hooks61);
-        p61_profile_done(prof61);
-        const int rc_end = call.end((hipStream_t)stream);
-        return rc61 != FASTECC_OK ? rc61 : rc_end;
-    }
-    DecodeState* d = decoder_of(c);
-    if (!d || !d->ready) return FASTECC_E_INVAL;  // fastecc_decode_prepare first
-    const bool rebuild = parity_out != nullptr && d->erased_parity != 0;
-    if (d->erased_data == 0 && !rebuild) return FASTECC_OK;
-    const CtxInfo ci = info_of(c);
-    if (ci.pitch != ci.words) return FASTECC_E_UNSUPPORTED;  // the gather / scatter passes address contiguous stripes
-    DeviceScope ds(ci.device);
-    if (!ds.ok) return FASTECC_E_DEVICE;
-    hipStream_t st = (hipStream_t)stream;
-    struct Marker {  // the decoder's work stripes are internal buffers: order their uses between streams
-        CallScope& s;
-        hipStream_t st;
-        ~Marker() { (void)s.end(st); }
-    };
-    {
-        const int rc0 = call.begin(st);
-        if (rc0 != FASTECC_OK) return rc0;
-    }
-    Marker marker{call, st};
-    const uint64_t N = d->mixed ? (uint64_t)ci.q * ci.k : ci.k;
-    const size_t block = ci.words * 4, data_bytes = ci.user_k * block, parity_bytes = ci.user_m * block;
-
-    uint32_t* ddata = (uint32_t*)data;
-    const uint32_t* dparity = (const uint32_t*)parity;
-    bool host_rows_only = false;  // FASTECC_MEM_HOST: only the rebuilt blocks are copied back (few enough of them, their rows known)
-    if (mem_kind == FASTECC_MEM_HOST) {
-        // stage the codeword — of the parity stripe only what the decoder will read where that is known to be a few block groups (the split
-        // transform of the (2k,k) layout: groups g < split_groups = blocks g + 1024 t, one strided copy)
-        if (!d->parity_dev) DEC_TRY(hipMalloc((void**)&d->parity_dev, parity_bytes + data_bytes));
-        // the rows that will travel back: known from the set-up (few losses), else read off the decoder's tables once per pattern
-        if (d->host_lists_of != d->pattern_serial) {
-            d->host_lost_data.clear();
-            d->host_lost_parity.clear();
-            if (d->erased_data + d->erased_parity <= (ci.user_k + ci.user_m) / 8 && d->parity_lost && (d->erased_data == 0 || d->gout)) {
-                std::vector<uint32_t> flags(std::max(ci.user_k, ci.user_m));
-                if (d->erased_data != 0) {
-                    DEC_TRY(hipMemcpy(flags.data(), d->gout, ci.user_k * 4, hipMemcpyDeviceToHost));
-                    for (uint64_t i = 0; i < ci.user_k; i++)
-                        if (flags[i] != 0) d->host_lost_data.push_back((uint32_t)i);
-                }
-                DEC_TRY(hipMemcpy(flags.data(), d->parity_lost, ci.user_m * 4, hipMemcpyDeviceToHost));
-                for (uint64_t q = 0; q < ci.user_m; q++)
-                    if (flags[q] != 0) d->host_lost_parity.push_back((uint32_t)q);
-                if (d->host_lost_data.size() != d->erased_data) d->host_lost_data.clear(), d->host_lost_parity.clear();  // (tables of another shape: whole stripes back)
-            }
-            d->host_lists_of = d->pattern_serial;
-        }
-        const uint64_t back = (d->erased_data != 0 ? d->host_lost_data.size() : 0) + (rebuild ? d->host_lost_parity.size() : 0);
-        host_rows_only = back != 0 && (d->erased_data == 0 || d->host_lost_data.size() == d->erased_data) &&
-                         (!rebuild || d->host_lost_parity.size() == d->erased_parity) && back <= (ci.user_k + ci.user_m) / 8;
-        // (a repair that copies the whole parity stripe back must have staged all of it)
-        if (!d->sub && d->split_ready && d->split_shift != 0 && d->standard && d->erased_data != 0 && (!rebuild || host_rows_only)) {
-            // small form: the parity blocks at multiples of 2^shift are all the decoder reads — one strided copy of every 2^shift-th block
-            const size_t pitch = block << d->split_shift;
-            DEC_TRY(hipMemcpy2DAsync(d->parity_dev, pitch, parity, pitch, block, (ci.user_m + (1ull << d->split_shift) - 1) >> d->split_shift, hipMemcpyHostToDevice, st));
-        } else if (!d->sub && d->split_ready && d->split_shift == 0 && d->standard && d->erased_data != 0 && d->split_groups < 512 && (!rebuild || host_rows_only)) {
-            DEC_TRY(hipMemcpy2DAsync(d->parity_dev, 1024 * block, parity, 1024 * block, (size_t)d->split_groups * block, ci.user_m / 1024, hipMemcpyHostToDevice, st));
-        } else if (d->sub && (!rebuild || host_rows_only)) {
-            // few losses: the direct path reads as many parity blocks as data blocks are lost (at most 256 copies of a block)
-            for (uint32_t q : d->host_parity_used)
-                DEC_TRY(hipMemcpyAsync(d->parity_dev + (size_t)q * ci.words, (const char*)parity + (size_t)q * block, block, hipMemcpyHostToDevice, st));
-        } else {
-            DEC_TRY(hipMemcpyAsync(d->parity_dev, parity, parity_bytes, hipMemcpyHostToDevice, st));
-        }
-        DEC_TRY(hipMemcpyAsync(d->parity_dev + ci.user_m * ci.words, data, data_bytes, hipMemcpyHostToDevice, st));
-        dparity = d->parity_dev;
-        ddata = d->parity_dev + ci.user_m * ci.words;
-    }
-
-    if (d->sub) {
-        // any layout, few losses: the lost data from the surviving data + a few parity blocks, then (repair) the lost parity from the data
-        const uint32_t S = (uint32_t)ci.words;
-        uint32_t* dpar_out = mem_kind == FASTECC_MEM_HOST ? d->parity_dev : (uint32_t*)parity_out;
-        // (profile: one "direct_pass" per read of the stripe)
-        auto pass = [&](DirectPass* p, const uint32_t* par_in, uint32_t* data_to, uint32_t* par_to) -> int {
-            void* scope = profile_scope_begin(c, st, "direct_pass", (ci.user_k + (uint64_t)d->sub_lost_data) * block);
-            const int rc = direct_run(p, ddata, par_in, data_to, par_to, S, d->direct_kernel, st);
-            profile_scope_end(scope);
-            return rc;
-        };
-        if (d->sub_both && (rebuild || d->sub_only_both)) {
-            // data and parity lost: one pass over the survivors writes both (fastecc_decode: the data only)
-            const int rc = pass(d->direct_both, dparity, ddata, rebuild ? dpar_out : nullptr);
-            if (rc != FASTECC_OK) return rc;
-        } else {
-            if (d->sub_lost_data > 0) {
-                const int rc = pass(d->direct_data, dparity, ddata, nullptr);
-                if (rc != FASTECC_OK) return rc;
-            }
-            if (rebuild) {
-                const int rc = pass(d->direct_parity, nullptr, nullptr, dpar_out);
-                if (rc != FASTECC_OK) return rc;
-            }
-        }
-    } else {
-    bool repaired_in_one_pass = false;
-    // split transform, small form: the rows of the parity half in use (multiples of 2^shift), times l, and their stand-alone DIF — in place
-    auto small_parity_half = [&]() -> int {
-        const uint32_t S0 = (uint32_t)ci.words, rows = (uint32_t)(N >> d->split_shift);
-        const bool w4 = (S0 % 4) == 0 && ((((uintptr_t)dparity | (uintptr_t)d->split_small_buf) & 15u) == 0);
-        const uint32_t chunks = (S0 + (w4 ? 256 : 64) - 1) / (w4 ? 256 : 64);
-        const uint64_t items = (uint64_t)rows * chunks;
-        const dim3 grid((unsigned)((items + 3) / 4));
-        if (w4) hipLaunchKernelGGL(split_small_gather_kernel<4>, grid, dim3(256), 0, st, dparity, d->split_small_buf, d->fin, S0, (int)d->split_shift, ci.fold, (uint32_t)ci.user_m, chunks, items);
-        else    hipLaunchKernelGGL(split_small_gather_kernel<1>, grid, dim3(256), 0, st, dparity, d->split_small_buf, d->fin, S0, (int)d->split_shift, ci.fold, (uint32_t)ci.user_m, chunks, items);
-        DEC_TRY(hipGetLastError());
-        return transform_bitrev(d->split_small[d->split_shift], d->split_small_buf, d->split_small_buf, false, true, S0, st);
-    };
-    if (rebuild && d->erased_data != 0 && d->split_ready && d->split_repair_ready) {
-        // fastecc_repair through the split transform: the data chain as in fastecc_decode, and a second MID + DIT over the same two halves for
-        // x p'(x) at the odd positions — the lost parity blocks, written straight into the parity stripe.  (No room for the extra k-block
-        // stripe: the forms below.)
-        hipError_t e_alloc = hipSuccess;
-        if (!d->split_q2) e_alloc = hipMalloc((void**)&d->split_q2, N * block);
-        if (e_alloc != hipSuccess) {
-            (void)hipGetLastError();
-            d->split_q2 = nullptr;
-        } else {
-            uint32_t* dpar_out = mem_kind == FASTECC_MEM_HOST ? d->parity_dev : (uint32_t*)parity_out;
-            const SplitRepair odd{d->split_q2, d->split_pos_data_odd, d->split_rows_out_parity, dpar_out};
-            d->split_dirty = std::max(d->split_dirty, d->split_groups);  // (before the launches: a failure half way must not hide written groups)
-            void* scope = profile_scope_begin(c, st, "repair_split_transform", (5 * N + (uint64_t)d->split_groups * split_decode_group_rows(d->split)) * block);
-            int rc;
-            if (d->split_shift != 0) {
-                rc = small_parity_half();
-                if (rc == FASTECC_OK)
-                    rc = run_split_decode(d->split, ddata, nullptr, d->split_rows_data, nullptr, 0, d->split_pos_parity, d->recovered, nullptr, nullptr, d->split_rows_out, ddata,
-                                          nullptr, (uint32_t)ci.user_k, (uint32_t)ci.user_m, st, &odd, d->split_small_buf, d->split_shift);
-            } else {
-                rc = run_split_decode(d->split, ddata, dparity, d->split_rows_data, d->split_rows_parity, d->split_groups, d->split_pos_parity, d->recovered,
-                                      d->split_r1, d->split_r2, d->split_rows_out, ddata, d->split_impulse, (uint32_t)ci.user_k, (uint32_t)ci.user_m, st, &odd);
-            }
-            profile_scope_end(scope);
-            if (rc != FASTECC_OK && rc != FASTECC_E_UNSUPPORTED) return rc;
-            if (rc == FASTECC_OK) repaired_in_one_pass = true;
-        }
-    }
-    if (!repaired_in_one_pass && rebuild && d->erased_data != 0 && d->standard && d->transform_full && d->full_ok && d->gout_par) {
-        // fastecc_repair, (2k,k) layout: x p'(x) at all 2k positions — the even rows give the lost data, the odd rows the lost parity
-        const uint32_t S = (uint32_t)ci.words;
-        hipError_t e_alloc = hipSuccess;
-        if (!d->recovered_full) e_alloc = hipMalloc((void**)&d->recovered_full, d->positions * (size_t)S * 4);
-        if (e_alloc != hipSuccess) (void)hipGetLastError();  // no room for the 2k-block stripe: the two-step form below
-        const int rc = e_alloc == hipSuccess ? run_gathered(d->transform_full, ddata, dparity, d->fin_first_pass, d->recovered_full, st) : FASTECC_E_UNSUPPORTED;
-        if (rc != FASTECC_OK && rc != FASTECC_E_UNSUPPORTED) return rc;
-        if (rc == FASTECC_OK) {
-            uint32_t* dpar_out = mem_kind == FASTECC_MEM_HOST ? d->parity_dev : (uint32_t*)parity_out;
-            const bool v4 = (S % 4) == 0 && ((((uintptr_t)ddata | (uintptr_t)dpar_out | (uintptr_t)d->recovered_full) & 15u) == 0);
-            const uint32_t col_chunks = (S + (v4 ? 256 : 64) - 1) / (v4 ? 256 : 64);
-            const uint64_t items = N * col_chunks;
-            const dim3 grid((unsigned)((items + 3) / 4));
-            if (v4) {
-                hipLaunchKernelGGL(decode_scatter_kernel<4>, grid, dim3(256), 0, st, d->recovered_full, ddata, d->gout, S, 2u * S, S, col_chunks, items);
-                hipLaunchKernelGGL(decode_scatter_kernel<4>, grid, dim3(256), 0, st, d->recovered_full + S, dpar_out, d->gout_par, S, 2u * S, S, col_chunks, items);
-            } else {
-                hipLaunchKernelGGL(decode_scatter_kernel<1>, grid, dim3(256), 0, st, d->recovered_full, ddata, d->gout, S, 2u * S, S, col_chunks, items);
-                hipLaunchKernelGGL(decode_scatter_kernel<1>, grid, dim3(256), 0, st, d->recovered_full + S, dpar_out, d->gout_par, S, 2u * S, S, col_chunks, items);
-            }
-            DEC_TRY(hipGetLastError());
-            repaired_in_one_pass = true;
-        }
-    }
-    if (d->erased_data != 0 && !repaired_in_one_pass) {
-    // The (2k,k) layout lets the transform's first pass read the two halves of the codeword itself (no gather pass).
-    // The other codes do not hold every position in memory: they take the table-driven gather, which never touches a
-    // position whose factor is zero, instead of a tile that reads first and multiplies by zero afterwards.
-    int rc = FASTECC_E_UNSUPPORTED;
-    bool scattered = false;
-    if (d->split_ready) {
-        // two half-size transforms instead of one of size 2k (see "even / odd split")
-        const uint32_t* parity_half = dparity;
-        uint32_t parity_half_blocks = (uint32_t)ci.user_m;
-        bool staged_ok = true;
-        if (d->split_shift != 0) {
-            // (the gather of the small form reads parity block (h >> fold) for position h itself: no staging stripe for codes with fewer parity blocks)
-            void* scope = profile_scope_begin(c, st, "decode_split_transform", (3 * N + 3 * (N >> d->split_shift)) * block);
-            rc = small_parity_half();
-            if (rc == FASTECC_OK)
-                rc = run_split_decode(d->split, ddata, nullptr, d->split_rows_data, nullptr, 0, d->split_pos_parity, d->recovered, nullptr, nullptr, d->split_rows_out, ddata,
-                                      nullptr, (uint32_t)ci.user_k, (uint32_t)ci.user_m, st, nullptr, d->split_small_buf, d->split_shift);
-            profile_scope_end(scope);
-            scattered = rc == FASTECC_OK;
-            staged_ok = false;  // (done, or unsupported: nothing more to try in this branch)
-        } else
-        if (ci.fold > 0 && !d->split_r0 && hipMalloc((void**)&d->split_r0, N * block) != hipSuccess) {
-            (void)hipGetLastError();  // no room for the staging stripe: the 2k-point transform below
-            d->split_r0 = nullptr;
-            staged_ok = false;
-        }
-        void* scope = staged_ok ? profile_scope_begin(c, st, "decode_split_transform", (3 * N + (uint64_t)d->split_groups * split_decode_group_rows(d->split)) * block)
-                                : nullptr;
-        if (ci.fold > 0 && staged_ok) {
-            // fewer parity blocks than data blocks: block j belongs at j << fold of the parity half — the blocks in use are copied there
-            const uint32_t S0 = (uint32_t)ci.words;
-            const bool w4 = (S0 % 4) == 0 && ((((uintptr_t)dparity | (uintptr_t)d->split_r0) & 15u) == 0);
-            const uint32_t chunks = (S0 + (w4 ? 256 : 64) - 1) / (w4 ? 256 : 64);
-            const uint64_t items = ci.user_m * chunks;
-            const dim3 grid((unsigned)((items + 3) / 4));
-            if (w4) hipLaunchKernelGGL(split_stage_kernel<4>, grid, dim3(256), 0, st, dparity, d->split_r0, d->fin, S0, ci.fold, chunks, items);
-            else    hipLaunchKernelGGL(split_stage_kernel<1>, grid, dim3(256), 0, st, dparity, d->split_r0, d->fin, S0, ci.fold, chunks, items);
-            parity_half = d->split_r0;
-            parity_half_blocks = (uint32_t)N;
-        }
-        if (staged_ok) d->split_dirty = std::max(d->split_dirty, d->split_groups);  // (before the launches, as above)
-        if (staged_ok) rc = run_split_decode(d->split, ddata, parity_half, d->split_rows_data, d->split_rows_parity, d->split_groups, d->split_pos_parity, d->recovered, d->split_r1,
-                              d->split_r2, d->split_rows_out, ddata, d->split_impulse, (uint32_t)ci.user_k, parity_half_blocks, st);  // ... whose last pass writes the rebuilt blocks straight into the data stripe
-        profile_scope_end(scope);
-        scattered = rc == FASTECC_OK;
-    }
-    if (rc == FASTECC_E_UNSUPPORTED && d->standard) {
-        void* scope = profile_scope_begin(c, st, "decode_transform_2k", 3 * N * block);
-        rc = run_gathered(d->transform, ddata, dparity, d->fin_first_pass, d->recovered, st);
-        profile_scope_end(scope);
-    }
-    const bool fused = rc == FASTECC_OK;
-    if (!fused && rc != FASTECC_E_UNSUPPORTED) return rc;
-    uint32_t* work = d->recovered;
-    if (!d->mixed && !fused) {  // (the transform context's scratch stripe: only the unfused form gathers into it)
-        rc = scratch_of(d->transform, &work);
-        if (rc != FASTECC_OK) return rc;
-    }
-    const uint32_t S = (uint32_t)ci.words;
-    const uint32_t ld_rec = d->mixed ? 2u * S : S;  // mixed radix: data position i is row 2i of the transformed work stripe
-    const bool v4 = (S % 4) == 0 && ((((uintptr_t)ddata | (uintptr_t)dparity | (uintptr_t)work | (uintptr_t)d->recovered) & 15u) == 0);
-    const uint32_t col_chunks = (S + (v4 ? 256 : 64) - 1) / (v4 ? 256 : 64);
-    if (!fused) {
-        const uint64_t items = d->positions * col_chunks;
-        const dim3 grid((unsigned)((items + 3) / 4));
-        if (v4) hipLaunchKernelGGL(decode_gather_kernel<4>, grid, dim3(256), 0, st, ddata, dparity, work, d->fin, d->srcmap, S, S, S, col_chunks, items);
-        else    hipLaunchKernelGGL(decode_gather_kernel<1>, grid, dim3(256), 0, st, ddata, dparity, work, d->fin, d->srcmap, S, S, S, col_chunks, items);
-        DEC_TRY(hipGetLastError());
-        rc = fastecc_encode(d->transform, work, d->mixed ? work : d->recovered, FASTECC_MEM_DEVICE, st);
-        if (rc != FASTECC_OK) return rc;
-    }
-    if (!scattered) {
-        const uint64_t items = N * col_chunks;
-        const dim3 grid((unsigned)((items + 3) / 4));
-        if (v4) hipLaunchKernelGGL(decode_scatter_kernel<4>, grid, dim3(256), 0, st, d->recovered, ddata, d->gout, S, ld_rec, S, col_chunks, items);
-        else    hipLaunchKernelGGL(decode_scatter_kernel<1>, grid, dim3(256), 0, st, d->recovered, ddata, d->gout, S, ld_rec, S, col_chunks, items);
-        DEC_TRY(hipGetLastError());
-    }
-    }
-    if (rebuild && !repaired_in_one_pass) {
-        // the lost parity blocks are whatever the encoder makes of the (now complete) data: one more encode into a stripe
-        // of the decoder's, from which only the lost blocks are copied — the surviving ones are left as they are
-        if (!d->parity_again) DEC_TRY(hipMalloc((void**)&d->parity_again, parity_bytes));
-        const int rc = encode_unlocked(c, ddata, d->parity_again, st);
-        if (rc != FASTECC_OK) return rc;
-        const uint32_t S = (uint32_t)ci.words;
-        uint32_t* dpar_out = mem_kind == FASTECC_MEM_HOST ? d->parity_dev : (uint32_t*)parity_out;
-        const bool v4 = (S % 4) == 0 && ((((uintptr_t)dpar_out | (uintptr_t)d->parity_again) & 15u) == 0);
-        const uint32_t col_chunks = (S + (v4 ? 256 : 64) - 1) / (v4 ? 256 : 64);
-        const uint64_t items = ci.user_m * col_chunks;
-        const dim3 grid((unsigned)((items + 3) / 4));
-        if (v4) hipLaunchKernelGGL(restore_parity_kernel<4>, grid, dim3(256), 0, st, d->parity_again, dpar_out, d->parity_lost, S, col_chunks, items);
-        else    hipLaunchKernelGGL(restore_parity_kernel<1>, grid, dim3(256), 0, st, d->parity_again, dpar_out, d->parity_lost, S, col_chunks, items);
-        DEC_TRY(hipGetLastError());
-    }
-    }  // transform path
-    bool rows_copied = false;
-    if (mem_kind == FASTECC_MEM_HOST && host_rows_only) {
-        // the rebuilt blocks packed side by side on the device, one copy into a pinned landing buffer, and a memcpy per block on the host.
-        // The repair has already run: if one of the buffers of this shortcut cannot be had, the whole-stripe copy below still delivers it.
-        const uint32_t S = (uint32_t)ci.words;
-        const uint64_t nd = d->erased_data != 0 ? d->host_lost_data.size() : 0, np = rebuild ? d->host_lost_parity.size() : 0;
-        bool have = true;
-        if (d->lost_rows_cap < nd + np) {
-            if (d->lost_rows_dev) (void)hipFree(d->lost_rows_dev);
-            d->lost_rows_dev = nullptr;
-            d->lost_rows_cap = 0;
-            if (hipMalloc((void**)&d->lost_rows_dev, (nd + np) * 4) == hipSuccess) d->lost_rows_cap = nd + np;
-            else have = false;
-        }
-        if (have && d->pack_words < (nd + np) * S) {
-            if (d->pack_dev) (void)hipFree(d->pack_dev);
-            d->pack_dev = nullptr;
-            d->pack_words = 0;
-            if (hipMalloc((void**)&d->pack_dev, (nd + np) * S * 4) == hipSuccess) d->pack_words = (nd + np) * S;
-            else have = false;
-        }
-        if (have && d->pack_host_words < (nd + np) * S) {
-            if (d->pack_host) (void)hipHostFree(d->pack_host);
-            d->pack_host = nullptr;
-            d->pack_host_words = 0;
-            if (hipHostMalloc((void**)&d->pack_host, (nd + np) * S * 4, hipHostMallocDefault) == hipSuccess) d->pack_host_words = (nd + np) * S;
-            else have = false;
-        }
-        if (!have) {
-            (void)hipGetLastError();  // out of memory for the shortcut only
-        } else {
-            if (nd) DEC_TRY(hipMemcpyAsync(d->lost_rows_dev, d->host_lost_data.data(), nd * 4, hipMemcpyHostToDevice, st));
-            if (np) DEC_TRY(hipMemcpyAsync(d->lost_rows_dev + nd, d->host_lost_parity.data(), np * 4, hipMemcpyHostToDevice, st));
-            const bool v4 = (S % 4) == 0 && ((((uintptr_t)ddata | (uintptr_t)d->parity_dev | (uintptr_t)d->pack_dev) & 15u) == 0);
-            const uint32_t col_chunks = (S + (v4 ? 256 : 64) - 1) / (v4 ? 256 : 64);
-            auto pack = [&](const uint32_t* stripe, const uint32_t* rows, uint32_t* out, uint64_t count) {
-                const uint64_t items = count * col_chunks;
-                const dim3 grid((unsigned)((items + 3) / 4));
-                if (v4) hipLaunchKernelGGL(pack_rows_kernel<4>, grid, dim3(256), 0, st, stripe, rows, out, S, col_chunks, items);
-                else    hipLaunchKernelGGL(pack_rows_kernel<1>, grid, dim3(256), 0, st, stripe, rows, out, S, col_chunks, items);
-            };
-            if (nd) pack(ddata, d->lost_rows_dev, d->pack_dev, nd);
-            if (np) pack(d->parity_dev, d->lost_rows_dev + nd, d->pack_dev + nd * S, np);
-            DEC_TRY(hipGetLastError());
-            DEC_TRY(hipMemcpyAsync(d->pack_host, d->pack_dev, (nd + np) * (size_t)S * 4, hipMemcpyDeviceToHost, st));
-            DEC_TRY(hipStreamSynchronize(st));
-            for (uint64_t r = 0; r < nd; r++) memcpy((char*)data + (size_t)d->host_lost_data[r] * block, d->pack_host + r * S, block);
-            for (uint64_t r = 0; r < np; r++) memcpy((char*)parity_out + (size_t)d->host_lost_parity[r] * block, d->pack_host + (nd + r) * S, block);
-            rows_copied = true;
-        }
-    }
-    if (mem_kind == FASTECC_MEM_HOST && !rows_copied) {
-        if (d->erased_data != 0) {
-            const int rc = download_pageable(c, data, ddata, data_bytes, st);
-            if (rc != FASTECC_OK) return rc;
-        }
-        if (rebuild) {
-            const int rc = download_pageable(c, parity_out, d->parity_dev, parity_bytes, st);
-            if (rc != FASTECC_OK) return rc;
-        }
-        DEC_TRY(hipStreamSynchronize(st));
-    }
-    return FASTECC_OK;
-}
-
-static int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream, bool repair);
-
-int fastecc_decode_batch(fastecc_ctx* c, void* data, const void* parity, uint64_t count, void* stream)
-{
-    try {
-        return decode_batch_impl(c, data, const_cast<void*>(parity), count, stream, false);
-    } catch (const std::bad_alloc&) {
-        return FASTECC_E_NOMEM;
-    } catch (...) {
-        return FASTECC_E_DEVICE;
-    }
-}
-
-int fastecc_repair_batch(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream)
-{
-    try {
-        return decode_batch_impl(c, data, parity, count, stream, true);
-    } catch (const std::bad_alloc&) {
-        return FASTECC_E_NOMEM;
-    } catch (...) {
-        return FASTECC_E_DEVICE;
-    }
-}
-
 // `count` stripes back to back in device memory, all with the prepared pattern.  The direct path runs each of its passes over the whole batch in
 // one launch (direct_run_batch) when the pass has fewer than 4096 rows (from 4096 data rows on, the single-stripe path takes the matrix cores) and
 // the batch gives at least one wave per SIMD; otherwise (option "decode_batch_kernel" decides when set) direct_run stripe by stripe.  Patterns of
 // the transform path: the single-stripe decode, stripe by stripe.
-static int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream, bool repair)
+int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream, bool repair)
 {
     if (!c || !data || !parity || count == 0 || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
     if (sharded_of(c)) return FASTECC_E_UNSUPPORTED;
@@ -1831,8 +1808,8 @@ static int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t 
     if (!d || !d->ready) return FASTECC_E_INVAL;  // fastecc_decode_prepare first
     const bool rebuild = repair && d->erased_parity != 0;
     if (d->erased_data == 0 && !rebuild) return FASTECC_OK;
-    DeviceScope ds(ci.device);
-    if (!ds.ok) return FASTECC_E_DEVICE;
+    DeviceGuard dg(ci.device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
     hipStream_t st = (hipStream_t)stream;
     if (!d->sub) {
         // more losses than the direct path takes: correct, not faster than the caller's own loop
@@ -1843,46 +1820,64 @@ static int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t 
         }
         return FASTECC_OK;
     }
-    struct Marker {  // the passes' tables and partial sums are internal buffers: order their uses between streams
-        CallScope& s;
-        hipStream_t st;
-        ~Marker() { (void)s.end(st); }
-    };
-    {
-        const int rc0 = call.begin(st);
-        if (rc0 != FASTECC_OK) return rc0;
-    }
-    Marker marker{call, st};
+    const int rc = call.begin(st);
+    if (rc != FASTECC_OK) return rc;
+    EndScope end{call, st};
     const uint64_t S = ci.words, data_words = ci.user_k * S, parity_words = ci.user_m * S;
     uint32_t* ddata = (uint32_t*)data;
     uint32_t* dparity = (uint32_t*)parity;
-    auto pass = [&](DirectPass* p, const uint32_t* par_in, uint32_t* data_to, uint32_t* par_to) -> int {
+    return direct_passes(d, rebuild, ddata, dparity, dparity, [&](DirectPass* p, const uint32_t* par_in, uint32_t* data_to, uint32_t* par_to) -> int {
         const uint64_t rows = (uint64_t)direct_pass_rows(p);
         const int mode = ci.decode_batch_kernel;
         const bool batched = mode == 1 || (mode == 0 && d->direct_kernel != 2 && rows < 4096 && direct_batch_waves(p, ddata, dparity, S, count) >= 1024);
         if (batched) {
             const uint64_t outputs = (data_to ? (uint64_t)d->sub_lost_data : 0) + (par_to ? (uint64_t)d->sub_lost_parity : 0);
             void* scope = profile_scope_begin(c, st, "direct_pass_batch", count * (rows + outputs) * block);
-            const int rc = direct_run_batch(p, ddata, par_in, data_to, par_to, S, count, data_words, parity_words, st);
+            const int r = direct_run_batch(p, ddata, par_in, data_to, par_to, S, count, data_words, parity_words, st);
             profile_scope_end(scope);
-            return rc;
+            return r;
         }
         void* scope = profile_scope_begin(c, st, "direct_pass", count * (ci.user_k + (uint64_t)d->sub_lost_data) * block);
-        int rc = FASTECC_OK;
-        for (uint64_t b = 0; b < count && rc == FASTECC_OK; b++)
-            rc = direct_run(p, ddata + b * data_words, par_in ? par_in + b * parity_words : nullptr, data_to ? data_to + b * data_words : nullptr,
-                            par_to ? par_to + b * parity_words : nullptr, (uint32_t)S, d->direct_kernel, st);
+        int r = FASTECC_OK;
+        for (uint64_t b = 0; b < count && r == FASTECC_OK; b++)
+            r = direct_run(p, ddata + b * data_words, par_in ? par_in + b * parity_words : nullptr, data_to ? data_to + b * data_words : nullptr,
+                           par_to ? par_to + b * parity_words : nullptr, (uint32_t)S, d->direct_kernel, st);
         profile_scope_end(scope);
-        return rc;
-    };
-    // the pass sequence of decode_impl
-    if (d->sub_both && (rebuild || d->sub_only_both)) return pass(d->direct_both, dparity, ddata, rebuild ? dparity : nullptr);
-    if (d->sub_lost_data > 0) {
-        const int rc = pass(d->direct_data, dparity, ddata, nullptr);
-        if (rc != FASTECC_OK) return rc;
-    }
-    if (rebuild) return pass(d->direct_parity, nullptr, nullptr, dparity);
-    return FASTECC_OK;
+        return r;
+    });
+}
+
+}  // namespace
+
+}  // namespace fastecc
+
+using namespace fastecc;
+
+extern "C" {
+
+int fastecc_decode_prepare(fastecc_ctx* c, const uint8_t* data_present, const uint8_t* parity_present)
+{
+    return guarded([&]() -> int { return decode_prepare_impl(c, data_present, parity_present); });
+}
+
+int fastecc_decode(fastecc_ctx* c, void* data, const void* parity, int mem_kind, void* stream)
+{
+    return guarded([&]() -> int { return decode_impl(c, data, parity, mem_kind, stream, nullptr); });
+}
+
+int fastecc_repair(fastecc_ctx* c, void* data, void* parity, int mem_kind, void* stream)
+{
+    return guarded([&]() -> int { return decode_impl(c, data, parity, mem_kind, stream, parity); });
+}
+
+int fastecc_decode_batch(fastecc_ctx* c, void* data, const void* parity, uint64_t count, void* stream)
+{
+    return guarded([&]() -> int { return decode_batch_impl(c, data, const_cast<void*>(parity), count, stream, false); });
+}
+
+int fastecc_repair_batch(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream)
+{
+    return guarded([&]() -> int { return decode_batch_impl(c, data, parity, count, stream, true); });
 }
 
 }  // extern "C"

@@ -544,17 +544,6 @@ __global__ __launch_bounds__(256) void interp_node_kernel(uint32_t* __restrict__
     coef[coef_index(K + (uint32_t)a, (uint32_t)t, K + (uint32_t)ed, (uint32_t)pad)] = v;
 }
 
-int hip_code(const char* what, hipError_t e)
-{
-    set_error_detail(what, e);
-    return e == hipErrorOutOfMemory ? FASTECC_E_NOMEM : FASTECC_E_DEVICE;
-}
-#define DIR_TRY(expr)                                      \
-    do {                                                   \
-        hipError_t e_ = (expr);                            \
-        if (e_ != hipSuccess) return hip_code(#expr, e_);  \
-    } while (0)
-
 // grow-only device buffer
 template <class T> int ensure(T*& p, uint64_t& have, uint64_t need)
 {
@@ -562,7 +551,7 @@ template <class T> int ensure(T*& p, uint64_t& have, uint64_t need)
     if (p) (void)hipFree(p);
     p = nullptr;
     have = 0;
-    DIR_TRY(hipMalloc((void**)&p, need * sizeof(T)));
+    HIP_TRY(hipMalloc((void**)&p, need * sizeof(T)));
     have = need;
     return FASTECC_OK;
 }
@@ -628,12 +617,12 @@ int direct_build_lagrange(DirectPass* p, uint32_t wd, uint32_t K, const std::vec
     if (c.size() != y.size() || out_pos.size() != y.size() || K < 1) return FASTECC_E_INVAL;
     const int rc = pass_common(p, K, K, outputs);
     if (rc != FASTECC_OK) return rc;
-    DIR_TRY(hipMemcpyAsync(p->params, y.data(), outputs * 4, hipMemcpyHostToDevice, st));
-    DIR_TRY(hipMemcpyAsync(p->params + DIRECT_CAP, c.data(), outputs * 4, hipMemcpyHostToDevice, st));
-    DIR_TRY(hipMemcpyAsync(p->lists + DIRECT_CAP, out_pos.data(), outputs * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p->params, y.data(), outputs * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p->params + DIRECT_CAP, c.data(), outputs * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p->lists + DIRECT_CAP, out_pos.data(), outputs * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(lagrange_coef_kernel, dim3((K + 255) / 256), dim3(256), 0, st, p->coef, p->params, wd, K, outputs, p->pad);
-    DIR_TRY(hipGetLastError());
-    DIR_TRY(hipStreamSynchronize(st));  // the host vectors may go out of scope
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));  // the host vectors may go out of scope
     p->built = true;
     return FASTECC_OK;
 }
@@ -660,17 +649,17 @@ int direct_build_interp(DirectPass* p, uint32_t wd, uint64_t N, uint32_t K, cons
         targets[ed + t] = y;
         cfar[t] = gf::h_mul(gf::h_mul(gf::h_mul(fsub(gf::h_pow(y, N), 1u), A), inv_n), gf::h_inv(R));  // (y^N - 1) A(y) / (N R(y))
     }
-    DIR_TRY(hipMemcpyAsync(p->params, targets.data(), (ed + ep) * 4, hipMemcpyHostToDevice, st));
-    DIR_TRY(hipMemcpyAsync(p->params + DIRECT_CAP, node_points.data(), ed * 4, hipMemcpyHostToDevice, st));
-    if (ep) DIR_TRY(hipMemcpyAsync(p->params + 2 * DIRECT_CAP + ed, cfar.data(), ep * 4, hipMemcpyHostToDevice, st));
-    DIR_TRY(hipMemcpyAsync(p->lists, node_rows.data(), ed * 4, hipMemcpyHostToDevice, st));
-    DIR_TRY(hipMemcpyAsync(p->lists + DIRECT_CAP, pos.data(), (ed + ep) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p->params, targets.data(), (ed + ep) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p->params + DIRECT_CAP, node_points.data(), ed * 4, hipMemcpyHostToDevice, st));
+    if (ep) HIP_TRY(hipMemcpyAsync(p->params + 2 * DIRECT_CAP + ed, cfar.data(), ep * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p->lists, node_rows.data(), ed * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p->lists + DIRECT_CAP, pos.data(), (ed + ep) * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(interp_params_kernel, dim3((ed + 255) / 256), dim3(256), 0, st, p->params, ed);
     hipLaunchKernelGGL(interp_coef_kernel, dim3((K + 255) / 256), dim3(256), 0, st, p->coef, p->params, wd, K, K + (uint32_t)ed, ed, ep, p->pad);
     hipLaunchKernelGGL(interp_node_kernel, dim3((unsigned)(((uint64_t)ed * p->pad + 255) / 256)), dim3(256), 0, st, p->coef, p->params, K, (uint32_t)(N % gf::P), ed, ep,
                        p->pad);
-    DIR_TRY(hipGetLastError());
-    DIR_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
     p->built = true;
     return FASTECC_OK;
 }
@@ -704,7 +693,7 @@ static int launch_accumulate(DirectPass* p, const uint32_t* data, const uint32_t
         default: FASTECC_ACC(16, 1); break;
     }
 #undef FASTECC_ACC
-    DIR_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return FASTECC_OK;
 }
 
@@ -750,7 +739,7 @@ int direct_run(DirectPass* p, const uint32_t* data, const uint32_t* parity, uint
             const int rc = ensure(p->frag, p->frag_count, count);
             if (rc != FASTECC_OK) return rc;
             hipLaunchKernelGGL(mfma_weights_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, p->coef, p->frag, bulk, rows, (uint32_t)p->pad, mt_total, count);
-            DIR_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             p->frag_valid = true;
             p->mfma_pad = pad;
         }
@@ -802,7 +791,7 @@ int direct_run(DirectPass* p, const uint32_t* data, const uint32_t* parity, uint
                 break;
 #endif
         }
-        DIR_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         if (tail_chunks) {  // the last data rows and the parity rows used as nodes
             rc = launch_accumulate(p, data, parity, S, bulk, mchunks, (uint32_t)pad, TAIL_ROWS, st);
             if (rc != FASTECC_OK) return rc;
@@ -821,7 +810,7 @@ int direct_run(DirectPass* p, const uint32_t* data, const uint32_t* parity, uint
     hipLaunchKernelGGL(direct_reduce1_kernel, dim3((S + 255) / 256, (unsigned)p->outputs, DIRECT_SEGS), dim3(256), 0, st, p->partial, stage, S, chunks, pad, p->outputs);
     hipLaunchKernelGGL(direct_reduce2_kernel, dim3((S + 255) / 256, (unsigned)p->outputs), dim3(256), 0, st, stage, p->lists + DIRECT_CAP, data_out, parity_out, S, pad,
                        p->outputs);
-    DIR_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return FASTECC_OK;
 }
 
@@ -960,7 +949,7 @@ int direct_run_batch(DirectPass* p, const uint32_t* data, const uint32_t* parity
     }
     }
 #undef FASTECC_BATCH
-    DIR_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return FASTECC_OK;
 }
 

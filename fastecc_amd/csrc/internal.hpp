@@ -4,12 +4,51 @@
 #include <stdint.h>
 
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/fastecc.h"
 
 namespace fastecc {
+
+// ---- the helpers of every entry point ----
+// The failed HIP call `what` becomes this thread's fastecc_last_error_detail and the error is cleared: FASTECC_E_NOMEM for an out-of-memory error,
+// else FASTECC_E_DEVICE (api.hip)
+int hip_fail(hipError_t e, const char* what);
+#define HIP_TRY(expr)                                     \
+    do {                                                  \
+        hipError_t e_ = (expr);                           \
+        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
+    } while (0)
+
+// the current device is `dev` for the scope, the previous one again after it
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = false;
+    explicit DeviceGuard(int dev)
+    {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        ok = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard()
+    {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// No exception crosses the ABI: an entry point's body runs through this, and an allocation failure of the host code (std::vector) is
+// FASTECC_E_NOMEM (the call locks of the context are scoped objects, so they are released on the way out)
+template <class F> int guarded(F body)
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return FASTECC_E_NOMEM;
+    } catch (...) {
+        return FASTECC_E_DEVICE;
+    }
+}
 
 struct DecodeState;                        // decode.hip: tables of one erasure pattern + the size-2k transform context
 void destroy_decode_state(DecodeState*);   // decode.hip, called by fastecc_destroy

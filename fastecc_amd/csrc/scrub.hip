@@ -245,12 +245,6 @@ void destroy_scrub_state(ScrubState* s)
 
 namespace {
 
-#define SCRUB_TRY(expr)                                   \
-    do {                                                  \
-        hipError_t e_ = (expr);                           \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-    } while (0)
-
 int scrub_args(fastecc_ctx* c, const void* data, const void* parity, int mem_kind)
 {
     if (!c || !data || !parity || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
@@ -353,7 +347,7 @@ int small_buffers(ScrubState* s, uint32_t locate_max, Small* sm)
         if (s->d_small) (void)hipFree(s->d_small);
         s->d_small = nullptr;
         s->small_words = 0;
-        SCRUB_TRY(hipMalloc((void**)&s->d_small, words * 4));
+        HIP_TRY(hipMalloc((void**)&s->d_small, words * 4));
         s->small_words = words;
     }
     uint32_t* p = s->d_small;
@@ -383,9 +377,9 @@ int upload_weights(fastecc_ctx* c, ScrubState* s, uint64_t seed, hipStream_t st)
         h[2 * w + 1] = r1 | ((r2 >> 12) << 20);
     }
     s->weights_valid = false;
-    if (!s->d_weights) SCRUB_TRY(hipMalloc((void**)&s->d_weights, 2 * c->S * 4 + 16));
-    SCRUB_TRY(hipStreamSynchronize(st));  // (the previous call's kernels are done: calls end with a synchronise; this one has enqueued nothing yet)
-    SCRUB_TRY(hipMemcpy(s->d_weights, h.data(), 2 * c->S * 4, hipMemcpyHostToDevice));
+    if (!s->d_weights) HIP_TRY(hipMalloc((void**)&s->d_weights, 2 * c->S * 4 + 16));
+    HIP_TRY(hipStreamSynchronize(st));  // (the previous call's kernels are done: calls end with a synchronise; this one has enqueued nothing yet)
+    HIP_TRY(hipMemcpy(s->d_weights, h.data(), 2 * c->S * 4, hipMemcpyHostToDevice));
     s->weights_seed = seed;
     s->weights_valid = true;
     return FASTECC_OK;
@@ -397,7 +391,7 @@ int fingerprints(fastecc_ctx* c, ScrubState* s, const Small& sm, const uint32_t*
 {
     int rc = upload_weights(c, s, seed, st);
     if (rc != FASTECC_OK) return rc;
-    SCRUB_TRY(hipMemsetAsync(sm.bad, 0, 4, st));
+    HIP_TRY(hipMemsetAsync(sm.bad, 0, 4, st));
     const bool vec = (c->S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
     // every workgroup resident at once (6 waves per SIMD at 75 VGPRs): a grid-stride loop over the blocks without a tail wave of late groups
     const uint64_t groups = std::min<uint64_t>((s->n + 3) / 4, (uint64_t)c->cus * 6);
@@ -409,13 +403,13 @@ int fingerprints(fastecc_ctx* c, ScrubState* s, const Small& sm, const uint32_t*
         else
             hipLaunchKernelGGL(fingerprint_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)c->S,
                                s->d_weights, s->d_pos, s->d_F, sm.bad, (uint32_t)sm.bad_cap);
-        SCRUB_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     uint32_t nb = 0;
-    SCRUB_TRY(hipMemcpyAsync(&nb, sm.bad, 4, hipMemcpyDeviceToHost, st));
-    SCRUB_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&nb, sm.bad, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     bad.assign(std::min<uint64_t>(nb, sm.bad_cap), 0);
-    if (!bad.empty()) SCRUB_TRY(hipMemcpy(bad.data(), sm.bad + 1, bad.size() * 4, hipMemcpyDeviceToHost));
+    if (!bad.empty()) HIP_TRY(hipMemcpy(bad.data(), sm.bad + 1, bad.size() * 4, hipMemcpyDeviceToHost));
     if (nb > bad.size()) bad.push_back(~0u);  // more than n - k: marks the overflow
     std::sort(bad.begin(), bad.end());
     return FASTECC_OK;
@@ -434,12 +428,12 @@ int syndromes(fastecc_ctx* c, ScrubState* s, const Small& sm, const std::vector<
     std::vector<uint32_t> pts(erased.size());
     const uint32_t w = gf::h_root((uint32_t)NC);
     for (size_t i = 0; i < erased.size(); i++) pts[i] = gf::h_pow(w, erased[i]);
-    if (!pts.empty()) SCRUB_TRY(hipMemcpyAsync(sm.roots, pts.data(), pts.size() * 4, hipMemcpyHostToDevice, st));
+    if (!pts.empty()) HIP_TRY(hipMemcpyAsync(sm.roots, pts.data(), pts.size() * 4, hipMemcpyHostToDevice, st));
     auto grid = [](uint64_t items) { return dim3((unsigned)((items + 255) / 256)); };
     {
         ProfScope ps(c, st, "scrub_weigh");
         hipLaunchKernelGGL(locator_kernel<true>, grid(NC), dim3(256), 0, st, s->d_lfix, sm.roots, (uint32_t)pts.size(), s->d_wpow, (uint32_t)NC, s->d_F, s->d_G);
-        SCRUB_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     {
         ProfScope ps(c, st, "scrub_transform");
@@ -447,19 +441,19 @@ int syndromes(fastecc_ctx* c, ScrubState* s, const Small& sm, const std::vector<
         if (rc != FASTECC_OK) return rc;
     }
     gather = std::min<uint64_t>(gather, NC - m_lo);
-    SCRUB_TRY(hipMemsetAsync(sm.flag, 0, 4, st));
+    HIP_TRY(hipMemsetAsync(sm.flag, 0, 4, st));
     {
         ProfScope ps(c, st, "scrub_syndromes");
         hipLaunchKernelGGL(syndrome_kernel, grid(NC - m_lo), dim3(256), 0, st, s->d_G, s->lgc, (uint32_t)NC, (uint32_t)m_lo, (uint32_t)gather, sm.syn, sm.flag);
-        SCRUB_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     uint32_t flag = 0;
-    SCRUB_TRY(hipMemcpyAsync(&flag, sm.flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&flag, sm.flag, 4, hipMemcpyDeviceToHost, st));
     if (syn) {
         syn->assign(R * gather, 0);
-        if (gather) SCRUB_TRY(hipMemcpyAsync(syn->data(), sm.syn, R * gather * 4, hipMemcpyDeviceToHost, st));
+        if (gather) HIP_TRY(hipMemcpyAsync(syn->data(), sm.syn, R * gather * 4, hipMemcpyDeviceToHost, st));
     }
-    SCRUB_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     *nonzero = flag != 0;
     return FASTECC_OK;
 }
@@ -545,20 +539,20 @@ int locate(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_
             }
         }
         if (L == 0 || (uint32_t)L > tmax || 2ull * (uint64_t)L > gather) return FASTECC_E_UNCORRECTABLE;
-        SCRUB_TRY(hipMemcpyAsync(sm.lambda, lambda.data(), (L + 1) * 4, hipMemcpyHostToDevice, st));
-        SCRUB_TRY(hipMemsetAsync(sm.found, 0, 4, st));
+        HIP_TRY(hipMemcpyAsync(sm.lambda, lambda.data(), (L + 1) * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(sm.found, 0, 4, st));
         {
             ProfScope ps(c, st, "scrub_root_search");
             hipLaunchKernelGGL(root_search_kernel, dim3((unsigned)((s->NC + 255) / 256)), dim3(256), 0, st, sm.lambda, (uint32_t)L, s->d_wpow, (uint32_t)s->NC, sm.found,
                                (uint32_t)sm.found_cap);
-            SCRUB_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
         uint32_t nf = 0;
-        SCRUB_TRY(hipMemcpyAsync(&nf, sm.found, 4, hipMemcpyDeviceToHost, st));
-        SCRUB_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(&nf, sm.found, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         if (nf != (uint32_t)L) return FASTECC_E_UNCORRECTABLE;  // a locator splits into distinct roots at the code's positions, or it is no locator
         std::vector<uint32_t> roots(nf);
-        SCRUB_TRY(hipMemcpy(roots.data(), sm.found + 1, nf * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(roots.data(), sm.found + 1, nf * 4, hipMemcpyDeviceToHost));
         for (uint32_t u : roots) {
             const uint32_t j = s->block_at[u];
             if (j == ~0u || std::binary_search(bad.begin(), bad.end(), j)) return FASTECC_E_UNCORRECTABLE;  // no block there, or one already erased
@@ -580,17 +574,6 @@ int report(const std::vector<uint32_t>& found, uint64_t* blocks, uint64_t cap, u
     for (uint64_t i = 0; i < found.size() && i < cap; i++) blocks[i] = found[i];
     *count = found.size();
     return FASTECC_OK;
-}
-
-template <class F> int guarded(F body)
-{
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        return FASTECC_E_NOMEM;
-    } catch (...) {
-        return FASTECC_E_DEVICE;
-    }
 }
 
 }  // namespace

@@ -259,12 +259,6 @@ __global__ __launch_bounds__(256) void update_parity_kernel(const ParityArgs a)
     }
 }
 
-#define UPD_TRY(expr)                                     \
-    do {                                                  \
-        hipError_t e_ = (expr);                           \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-    } while (0)
-
 }  // namespace
 
 struct UpdateState {
@@ -296,21 +290,21 @@ int update_table(fastecc_ctx* c, UpdateState* s, hipStream_t st)
     if (s->table_ready) {
         if (s->table_pending && st != s->table_stream) {
             if (hipEventQuery(s->table_event) == hipSuccess) s->table_pending = false;
-            else UPD_TRY(hipStreamWaitEvent(st, s->table_event, 0));
+            else HIP_TRY(hipStreamWaitEvent(st, s->table_event, 0));
             (void)hipGetLastError();  // hipErrorNotReady of the query is not an error
         }
         return FASTECC_OK;
     }
     const uint64_t words = s->NC >> s->tshift;
-    if (!s->d_G) UPD_TRY(hipMalloc((void**)&s->d_G, words * 4));
-    if (!s->table_event) UPD_TRY(hipEventCreateWithFlags(&s->table_event, hipEventDisableTiming));
+    if (!s->d_G) HIP_TRY(hipMalloc((void**)&s->d_G, words * 4));
+    if (!s->table_event) HIP_TRY(hipEventCreateWithFlags(&s->table_event, hipEventDisableTiming));
     {
         ProfScope ps(c, st, "update_table", words * 4);
         hipLaunchKernelGGL(update_table_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, s->d_G, (uint32_t)words, gf::h_root((uint32_t)s->NC),
                            (uint32_t)(s->g.N % gf::P), (uint64_t)s->g.N, s->tshift, (uint32_t)((1u << s->g.e) - 1u));
-        UPD_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    UPD_TRY(hipEventRecord(s->table_event, st));
+    HIP_TRY(hipEventRecord(s->table_event, st));
     s->table_stream = st;
     s->table_ready = s->table_pending = true;
     return FASTECC_OK;
@@ -398,7 +392,7 @@ int update_pass(fastecc_ctx* c, UpdateState* s, uint32_t* data, uint32_t* parity
     {
         ProfScope ps(c, st, "update_delta", (uint64_t)rows * S * 4 * (data || old_blocks ? 3 : 2) + (data ? rows * S * 4 : 0));
         hipLaunchKernelGGL(update_delta_kernel, dim3((unsigned)((S + 255) / 256), (unsigned)T), dim3(256), 0, st, da);
-        UPD_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     const CodeGeom& g = s->g;
     pa.parity = parity;
@@ -439,7 +433,7 @@ int update_pass(fastecc_ctx* c, UpdateState* s, uint32_t* data, uint32_t* parity
         if (V == 4) launch_parity_v<4>(T, pa, grid, st);
         else if (V == 2) launch_parity_v<2>(T, pa, grid, st);
         else launch_parity_v<1>(T, pa, grid, st);
-        UPD_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     return FASTECC_OK;
 }
@@ -468,7 +462,7 @@ int update_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const uint64_t*
     UpdateState* s = nullptr;
     int rc = update_state(c, &s);
     if (rc != FASTECC_OK) return rc;
-    if (!s->d_delta) UPD_TRY(hipMalloc((void**)&s->d_delta, (size_t)ROWS * c->S * 4));
+    if (!s->d_delta) HIP_TRY(hipMalloc((void**)&s->d_delta, (size_t)ROWS * c->S * 4));
     rc = update_table(c, s, st);
     if (rc != FASTECC_OK) return rc;
     return with_internal_buffers(c, st, [&]() -> int {
@@ -480,17 +474,6 @@ int update_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const uint64_t*
         }
         return FASTECC_OK;
     });
-}
-
-template <class F> int guarded(F body)
-{
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        return FASTECC_E_NOMEM;
-    } catch (...) {
-        return FASTECC_E_DEVICE;
-    }
 }
 
 }  // namespace
