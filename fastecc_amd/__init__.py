@@ -103,6 +103,9 @@ def lib():
         f = getattr(L, "fastecc_" + name)
         f.argtypes, f.restype = [vp, vp, vp, i32, vp, u64, ctypes.POINTER(u64), u64, ctypes.POINTER(u64)], i32
     u64p = ctypes.POINTER(u64)
+    for name in ("verify_batch", "correct_batch"):
+        f = getattr(L, "fastecc_" + name)
+        f.argtypes, f.restype = [vp, vp, vp, u64, vp, u64, u8p, u64p], i32
     L.fastecc_update.argtypes, L.fastecc_update.restype = [vp, vp, vp, u64p, u64, vp, i32, vp], i32
     L.fastecc_update_parity.argtypes, L.fastecc_update_parity.restype = [vp, vp, u64p, u64, vp, vp, i32, vp], i32
     L.fastecc_code_coefficient.argtypes = [u64, u64, ctypes.c_uint, u64, u64, ctypes.POINTER(u32)]
@@ -292,6 +295,33 @@ class Encoder:
         ok = ctypes.c_int()
         _check(lib().fastecc_verify(self._h, _addr(data), _addr(parity), mem, stream or None, seed, ctypes.byref(ok)), "fastecc_verify")
         return bool(ok.value)
+
+    def _scrub_batch(self, fn, data, parity, count, seed, stream):
+        import numpy as np
+        count = self._batch_count(count)
+        out = np.zeros(count, np.uint8)
+        bad = ctypes.c_uint64()
+        code = fn(self._h, _addr(data), _addr(parity), count, stream or None, seed, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(bad))
+        return code, out
+
+    def verify_batch(self, data, parity, count, seed=0, stream=0):
+        """`count` stripes back to back in device memory (the layout of decode_batch): a numpy bool array, True where verify with the
+        same seed finds the stripe consistent.  Reads only."""
+        code, out = self._scrub_batch(lib().fastecc_verify_batch, data, parity, count, seed, stream)
+        _check(code, "fastecc_verify_batch")
+        return out.astype(bool)
+
+    def correct_batch(self, data, parity, count, seed=0, stream=0):
+        """verify_batch, then correct on each inconsistent stripe (replaces the prepared erasure pattern).  Returns the numpy uint8
+        status array: 0 = consistent and untouched, 1 = corrected, 2 = uncorrectable.  If any stripe is uncorrectable, raises
+        FastEccError with code E_UNCORRECTABLE after the others were corrected; the full status array is its `status` attribute."""
+        code, out = self._scrub_batch(lib().fastecc_correct_batch, data, parity, count, seed, stream)
+        if code == E_UNCORRECTABLE:
+            err = FastEccError(code, "fastecc_correct_batch")
+            err.status = out
+            raise err
+        _check(code, "fastecc_correct_batch")
+        return out
 
     def _located(self, fn, what, data, parity, seed, stream, mem):
         cap = self.n - self.k

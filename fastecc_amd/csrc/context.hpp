@@ -87,6 +87,7 @@ struct fastecc_ctx {
     ScrubState* scrub = nullptr;        // fastecc_verify / _locate_errors / _correct: position map, fixed-erasure locator, fingerprint buffers (scrub.hip)
     UpdateState* update = nullptr;      // fastecc_update / _update_parity: weight table and delta rows (update.hip)
     int locate_max = 256;               // option "locate_max": most unknown corrupted blocks fastecc_locate_errors looks for
+    int scrub_batch_chunk = 0;          // option "scrub_batch_chunk": most stripes per chunk of fastecc_verify_batch (0 = the state's capacity)
     int p61_stride = 1;  // 64-bit field, codes other than (2N,N): parity block j of the code is block j * p61_stride of the (2N,N) parity (N = 2^n)
     p61::Path* p61 = nullptr;  // FASTECC_FIELD_GF_P61_SQUARED: tables and plan of gf61_kernels.hip (everything uint32 below is unused)
     uint64_t N = 0;   // k

@@ -103,6 +103,11 @@ int fastecc_set_option(fastecc_ctx* c, const char* name, int value)
         c->locate_max = value;
         return FASTECC_OK;
     }
+    if (!strcmp(name, "scrub_batch_chunk")) {  // fastecc_verify_batch / _correct_batch, at call time: 0 = auto, else at most this many stripes per chunk
+        if (value < 0) return FASTECC_E_INVAL;
+        c->scrub_batch_chunk = value;
+        return FASTECC_OK;
+    }
     if (!strcmp(name, "decode_split")) {  // (2k,k) codes, from the next fastecc_decode_prepare: see context.hpp
         if (value < 0 || value > 2) return FASTECC_E_INVAL;  // 2: the split transform in its block-group form only (A/B against the small form)
         c->decode_split = value;

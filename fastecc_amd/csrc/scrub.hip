@@ -1,4 +1,5 @@
-// scrub.hip — error detection and location: fastecc_verify, fastecc_locate_errors, fastecc_correct (include/fastecc.h).
+// scrub.hip — error detection and location: fastecc_verify, fastecc_locate_errors, fastecc_correct and the batched fastecc_verify_batch,
+// fastecc_correct_batch (include/fastecc.h).
 //
 // The erasure decoder (decode.hip) acts on losses the caller names.  Here the corrupted blocks are found first.  Every code of the
 // library is f (degree < N) on a subset of the NC-th roots of unity, NC = N << e, position u <-> w^u: data block i at i << e, parity at
@@ -22,6 +23,8 @@
 //   root search         : Lambda(w^u) by Horner at every position on the device;
 //   confirmation        : the syndromes once more with the located positions erased must all vanish, in every column.
 // fastecc_correct then hands the located blocks to fastecc_decode_prepare + fastecc_repair.
+// fastecc_verify_batch / _correct_batch run the verify over many stripes at once: the stripe index becomes extra word columns of
+// the fingerprint stripe, so one transform serves a whole chunk of stripes (fingerprint_batch_kernel, syndrome_batch_kernel, verify_batch_locked).
 #include <algorithm>
 #include <vector>
 
@@ -67,9 +70,77 @@ __device__ __forceinline__ void mad3(uint64_t& a0, uint64_t& a1, uint64_t& a2, u
     a2 += (uint64_t)v * r2;
 }
 
-// One wave per block (blocks wave, wave + waves, ...).  VEC: S % 4 == 0 and 16-byte aligned stripes — lane l reads words 4l + 256 i
-// as dwordx4, four loads in flight per batch; else one word per lane and step.  Sums: products < 2^52, folded every 4096 of them.
-// F[pos[j] * 4 + c] receives the block's fingerprint c; a block with a word >= p is appended to bad[1 ..] (bad[0] counts them).
+// One wave's fingerprint of one block of S words.  VEC: S % 4 == 0 and a 16-byte aligned block — lane l reads words 4l + 256 i as
+// dwordx4, four loads in flight per batch; else one word per lane and step.  Sums: products < 2^52, folded every 4096 of them.
+// Every lane gets the three fingerprints (mod p) and whether some word of the block is >= p.
+template <bool VEC>
+__device__ __forceinline__ void block_fingerprint(const uint32_t* __restrict__ blk, uint32_t S, const uint2* __restrict__ wt, uint32_t lane, uint32_t f[R],
+                                                  bool& any_big)
+{
+    uint64_t a0 = 0, a1 = 0, a2 = 0;
+    uint32_t big = 0;
+    if (VEC) {
+        const uint4* wt4 = reinterpret_cast<const uint4*>(wt);
+        uint32_t batches = 0;
+        for (uint32_t base = lane * 4u; base < S; base += 1024u) {
+            uint4 v[4], wa[4], wb[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const uint32_t w = base + 256u * u;
+                if (w < S) {
+                    v[u] = *reinterpret_cast<const uint4*>(blk + w);
+                    wa[u] = wt4[w >> 1];
+                    wb[u] = wt4[(w >> 1) + 1];
+                } else {
+                    v[u] = wa[u] = wb[u] = make_uint4(0, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                big |= (uint32_t)(v[u].x >= gf::P) | (uint32_t)(v[u].y >= gf::P) | (uint32_t)(v[u].z >= gf::P) | (uint32_t)(v[u].w >= gf::P);
+                mad3(a0, a1, a2, v[u].x, wa[u].x, wa[u].y);
+                mad3(a0, a1, a2, v[u].y, wa[u].z, wa[u].w);
+                mad3(a0, a1, a2, v[u].z, wb[u].x, wb[u].y);
+                mad3(a0, a1, a2, v[u].w, wb[u].z, wb[u].w);
+            }
+            if ((++batches & 255u) == 0) {  // 16 products per batch: 4096 since the last fold
+                a0 = fold64(a0);
+                a1 = fold64(a1);
+                a2 = fold64(a2);
+            }
+        }
+    } else {
+        uint32_t steps = 0;
+        for (uint32_t w = lane; w < S; w += 64u) {
+            const uint32_t v = blk[w];
+            const uint2 q = wt[w];
+            big |= (uint32_t)(v >= gf::P);
+            mad3(a0, a1, a2, v, q.x, q.y);
+            if ((++steps & 4095u) == 0) {
+                a0 = fold64(a0);
+                a1 = fold64(a1);
+                a2 = fold64(a2);
+            }
+        }
+    }
+    // lane sums < p, wave sums < 2^38
+    a0 = reduce64(a0);
+    a1 = reduce64(a1);
+    a2 = reduce64(a2);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a0 += __shfl_xor(a0, o, 64);
+        a1 += __shfl_xor(a1, o, 64);
+        a2 += __shfl_xor(a2, o, 64);
+    }
+    any_big = __any(big != 0);
+    f[0] = reduce64(a0);
+    f[1] = reduce64(a1);
+    f[2] = reduce64(a2);
+}
+
+// One wave per block (blocks wave, wave + waves, ...).  F[pos[j] * 4 + c] receives the block's fingerprint c; a block with a word >= p
+// is appended to bad[1 ..] (bad[0] counts them).
 template <bool VEC>
 __global__ __launch_bounds__(256) void fingerprint_kernel(const uint32_t* __restrict__ data, const uint32_t* __restrict__ parity, uint32_t k_blocks,
                                                           uint32_t n_blocks, uint32_t S, const uint2* __restrict__ wt, const uint32_t* __restrict__ pos,
@@ -80,72 +151,53 @@ __global__ __launch_bounds__(256) void fingerprint_kernel(const uint32_t* __rest
     const uint32_t waves = (gridDim.x * blockDim.x) >> 6;
     for (uint32_t j = wave; j < n_blocks; j += waves) {
         const uint32_t* blk = j < k_blocks ? data + (size_t)j * S : parity + (size_t)(j - k_blocks) * S;
-        uint64_t a0 = 0, a1 = 0, a2 = 0;
-        uint32_t big = 0;
-        if (VEC) {
-            const uint4* wt4 = reinterpret_cast<const uint4*>(wt);
-            uint32_t batches = 0;
-            for (uint32_t base = lane * 4u; base < S; base += 1024u) {
-                uint4 v[4], wa[4], wb[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const uint32_t w = base + 256u * u;
-                    if (w < S) {
-                        v[u] = *reinterpret_cast<const uint4*>(blk + w);
-                        wa[u] = wt4[w >> 1];
-                        wb[u] = wt4[(w >> 1) + 1];
-                    } else {
-                        v[u] = wa[u] = wb[u] = make_uint4(0, 0, 0, 0);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    big |= (uint32_t)(v[u].x >= gf::P) | (uint32_t)(v[u].y >= gf::P) | (uint32_t)(v[u].z >= gf::P) | (uint32_t)(v[u].w >= gf::P);
-                    mad3(a0, a1, a2, v[u].x, wa[u].x, wa[u].y);
-                    mad3(a0, a1, a2, v[u].y, wa[u].z, wa[u].w);
-                    mad3(a0, a1, a2, v[u].z, wb[u].x, wb[u].y);
-                    mad3(a0, a1, a2, v[u].w, wb[u].z, wb[u].w);
-                }
-                if ((++batches & 255u) == 0) {  // 16 products per batch: 4096 since the last fold
-                    a0 = fold64(a0);
-                    a1 = fold64(a1);
-                    a2 = fold64(a2);
-                }
-            }
-        } else {
-            uint32_t steps = 0;
-            for (uint32_t w = lane; w < S; w += 64u) {
-                const uint32_t v = blk[w];
-                const uint2 q = wt[w];
-                big |= (uint32_t)(v >= gf::P);
-                mad3(a0, a1, a2, v, q.x, q.y);
-                if ((++steps & 4095u) == 0) {
-                    a0 = fold64(a0);
-                    a1 = fold64(a1);
-                    a2 = fold64(a2);
-                }
-            }
-        }
-        // lane sums < p, wave sums < 2^38
-        a0 = reduce64(a0);
-        a1 = reduce64(a1);
-        a2 = reduce64(a2);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            a0 += __shfl_xor(a0, o, 64);
-            a1 += __shfl_xor(a1, o, 64);
-            a2 += __shfl_xor(a2, o, 64);
-        }
-        const bool any_big = __any(big != 0);
+        uint32_t fp[R];
+        bool any_big;
+        block_fingerprint<VEC>(blk, S, wt, lane, fp, any_big);
         if (lane == 0) {
             uint32_t* f = F + (size_t)pos[j] * RW;
-            f[0] = reduce64(a0);
-            f[1] = reduce64(a1);
-            f[2] = reduce64(a2);
+            f[0] = fp[0];
+            f[1] = fp[1];
+            f[2] = fp[2];
             if (any_big) {
                 const uint32_t slot = atomicAdd(bad, 1u);
                 if (slot < bad_cap) bad[1 + slot] = j;
             }
+        }
+    }
+}
+
+// fastecc_verify_batch: the same per block over the B stripes [b0, b0 + B) of a batch, global block g = b * n + j (stripe b - b0 of the chunk, block j;
+// both wave-uniform).  Fingerprint c of that block, times the fixed erasures' locator at its position (lfix, null: 1), lands in
+// F[pos[j] * row + (b - b0) * 4 + c] — the chunk's stripes are word columns of one fingerprint stripe of NC rows.  A block with a word >= p
+// sets flag[b] (a plain store of 1: idempotent, no atomics).  At most 80 VGPRs: six waves per SIMD, the grid the host launches all resident.
+template <bool VEC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void fingerprint_batch_kernel(const uint32_t* __restrict__ data, const uint32_t* __restrict__ parity, uint32_t k_blocks,
+                                                                uint32_t n_blocks, uint32_t S, uint64_t b0, uint64_t B, const uint2* __restrict__ wt,
+                                                                const uint32_t* __restrict__ pos, const uint32_t* __restrict__ lfix, uint32_t* __restrict__ F,
+                                                                uint64_t row, uint8_t* __restrict__ flag)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint64_t waves = (gridDim.x * blockDim.x) >> 6;
+    const uint64_t total = B * n_blocks;
+    const uint64_t m_blocks = n_blocks - k_blocks;
+    for (uint64_t g = wave; g < total; g += waves) {
+        const uint64_t bl = g / n_blocks;
+        const uint32_t j = (uint32_t)(g - bl * n_blocks);
+        const uint64_t b = b0 + bl;
+        const uint32_t* blk = j < k_blocks ? data + (b * k_blocks + j) * S : parity + (b * m_blocks + (j - k_blocks)) * S;
+        uint32_t fp[R];
+        bool any_big;
+        block_fingerprint<VEC>(blk, S, wt, lane, fp, any_big);
+        if (lane == 0) {
+            const uint32_t u = pos[j];
+            const uint32_t l = lfix ? lfix[u] : 1u;
+            uint32_t* f = F + (uint64_t)u * row + bl * RW;
+            f[0] = gf::mul(fp[0], l);
+            f[1] = gf::mul(fp[1], l);
+            f[2] = gf::mul(fp[2], l);
+            if (any_big) flag[b] = 1;
         }
     }
 }
@@ -184,6 +236,19 @@ __global__ __launch_bounds__(256) void syndrome_kernel(const uint32_t* __restric
         syn[gather + i] = g.y;
         syn[2 * gather + i] = g.z;
     }
+}
+
+// fastecc_verify_batch: G as above with the chunk's B stripes as word columns (row words per position); item i <-> stripe b = i % B of the chunk,
+// coefficient m = m_lo + i / B.  Any non-zero coefficient m >= m_lo in one of stripe b's three columns sets flag[b0 + b].
+__global__ __launch_bounds__(256) void syndrome_batch_kernel(const uint32_t* __restrict__ G, int lgc, uint32_t NC, uint32_t m_lo, uint64_t row, uint32_t B,
+                                                             uint64_t b0, uint8_t* __restrict__ flag)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (NC - m_lo) * B) return;
+    const uint32_t b = i % B, m = m_lo + i / B;
+    const uint32_t slot = __brev(m) >> (32 - lgc);
+    const uint4 g = *reinterpret_cast<const uint4*>(G + (uint64_t)slot * row + (uint64_t)b * RW);
+    if ((g.x | g.y | g.z) != 0) flag[b0 + b] = 1;
 }
 
 // Lambda(w^u) == 0 -> u appended to found[1 ..] (found[0] counts)
@@ -232,13 +297,22 @@ struct ScrubState {
     uint2* d_weights = nullptr;             // S packed weights of the current seed
     uint64_t weights_seed = 0;
     bool weights_valid = false;
+    // fastecc_verify_batch (built at its first call): a chunk of up to batch_cap stripes as word columns of one fingerprint stripe
+    fastecc_ctx* ntt_batch = nullptr;       // stand-alone transform of NC points over rows of 4 x batch_cap words
+    uint64_t batch_cap = 0;
+    uint32_t* d_FB = nullptr;               // NC x 4 batch_cap words: weighted fingerprints by position (zero where no block is read)
+    uint32_t* d_GB = nullptr;               // their transform
+    uint8_t* d_flag = nullptr;              // one byte per stripe of the call: 1 = inconsistent
+    uint64_t flag_cap = 0;
 };
 
 void destroy_scrub_state(ScrubState* s)
 {
     if (!s) return;
     if (s->ntt) fastecc_destroy(s->ntt);
-    for (void* p : {(void*)s->d_pos, (void*)s->d_wpow, (void*)s->d_lfix, (void*)s->d_F, (void*)s->d_G, (void*)s->d_small, (void*)s->d_weights})
+    if (s->ntt_batch) fastecc_destroy(s->ntt_batch);
+    for (void* p : {(void*)s->d_pos, (void*)s->d_wpow, (void*)s->d_lfix, (void*)s->d_F, (void*)s->d_G, (void*)s->d_small, (void*)s->d_weights, (void*)s->d_FB,
+                    (void*)s->d_GB, (void*)s->d_flag})
         if (p) (void)hipFree(p);
     delete s;
 }
@@ -393,7 +467,7 @@ int fingerprints(fastecc_ctx* c, ScrubState* s, const Small& sm, const uint32_t*
     if (rc != FASTECC_OK) return rc;
     HIP_TRY(hipMemsetAsync(sm.bad, 0, 4, st));
     const bool vec = (c->S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
-    // every workgroup resident at once (6 waves per SIMD at 75 VGPRs): a grid-stride loop over the blocks without a tail wave of late groups
+    // every workgroup resident at once (6 waves per SIMD at 77 VGPRs): a grid-stride loop over the blocks without a tail wave of late groups
     const uint64_t groups = std::min<uint64_t>((s->n + 3) / 4, (uint64_t)c->cus * 6);
     {
         ProfScope ps(c, st, "fingerprint", s->n * c->S * 4);
@@ -569,6 +643,102 @@ int locate(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_
     return FASTECC_OK;
 }
 
+// MANY STRIPES (fastecc_verify_batch / _correct_batch).  Stripes back to back as for fastecc_decode_batch; the same refusals as one stripe, and
+// count == 0 or a batch whose byte extent overflows 64 bits is FASTECC_E_INVAL.
+int batch_args(fastecc_ctx* c, const void* data, const void* parity, uint64_t count)
+{
+    if (count == 0) return FASTECC_E_INVAL;
+    const int rc = scrub_args(c, data, parity, FASTECC_MEM_DEVICE);
+    if (rc != FASTECC_OK) return rc;
+    const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
+    if (count > UINT64_MAX / data_bytes || count > UINT64_MAX / parity_bytes) return FASTECC_E_INVAL;
+    if ((uint64_t)(uintptr_t)data > UINT64_MAX - count * data_bytes || (uint64_t)(uintptr_t)parity > UINT64_MAX - count * parity_bytes) return FASTECC_E_INVAL;
+    return FASTECC_OK;
+}
+
+// The chunk buffers (once per context): the largest power-of-two chunk whose fingerprint stripe holds at most 32 MiB with rows of at most 1 MiB.
+// The chunk does not depend on the call's count, so one transform context serves every call.  F is zeroed here once: the positions that hold
+// no block are the same for every stripe, and the transform reads F and writes G, so they stay zero.
+int batch_state(fastecc_ctx* c, ScrubState* s)
+{
+    if (s->ntt_batch) return FASTECC_OK;
+    uint64_t cap = 1;
+    while (cap < (1ull << 16) && s->NC * 16 * (2 * cap) <= (32ull << 20)) cap *= 2;
+    const uint64_t bytes = s->NC * RW * cap * 4;
+    fastecc_ctx* t = nullptr;
+    uint32_t *F = nullptr, *G = nullptr;
+    int rc = create_ntt_ctx(&t, s->lgc, RW * 4 * cap, c->device);
+    if (rc != FASTECC_OK) return rc;
+    hipError_t he = hipMalloc((void**)&F, bytes);
+    if (he == hipSuccess) he = hipMalloc((void**)&G, bytes);
+    if (he == hipSuccess) he = hipMemset(F, 0, bytes);
+    if (he == hipSuccess) he = hipDeviceSynchronize();  // (the call's stream may not order after the null stream)
+    if (he != hipSuccess) {
+        fastecc_destroy(t);
+        if (F) (void)hipFree(F);
+        if (G) (void)hipFree(G);
+        return hip_fail(he, "scrub batch buffers");
+    }
+    s->ntt_batch = t;
+    s->batch_cap = cap;
+    s->d_FB = F;
+    s->d_GB = G;
+    return FASTECC_OK;
+}
+
+// fastecc_verify_batch on a locked context: flag[b] = 1 iff fastecc_verify with this seed would find stripe b inconsistent.  Per chunk of B
+// stripes: the fingerprints (weighed by the fixed erasures' locator as they are stored), one transform of NC points over 4B word columns,
+// the syndrome check of every stripe; then one copy of the flags and one synchronisation for the whole call.
+int verify_batch_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, uint64_t seed, hipStream_t st, std::vector<uint8_t>& flag)
+{
+    ScrubState* s = nullptr;
+    int rc = scrub_state(c, &s);
+    if (rc != FASTECC_OK) return rc;
+    if ((rc = batch_state(c, s)) != FASTECC_OK) return rc;
+    if (s->flag_cap < count) {
+        if (s->d_flag) (void)hipFree(s->d_flag);
+        s->d_flag = nullptr;
+        s->flag_cap = 0;
+        HIP_TRY(hipMalloc((void**)&s->d_flag, count));
+        s->flag_cap = count;
+    }
+    if ((rc = upload_weights(c, s, seed, st)) != FASTECC_OK) return rc;
+    HIP_TRY(hipMemsetAsync(s->d_flag, 0, count, st));
+    const uint64_t chunk = c->scrub_batch_chunk > 0 ? std::min<uint64_t>(s->batch_cap, (uint64_t)c->scrub_batch_chunk) : s->batch_cap;
+    const uint64_t row = RW * s->batch_cap, NC = s->NC, m_lo = s->N + s->fixed, S = c->S;
+    const bool vec = (S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
+    for (uint64_t b0 = 0; b0 < count; b0 += chunk) {
+        const uint64_t B = std::min(chunk, count - b0);
+        // every workgroup resident at once, as for one stripe
+        const uint64_t groups = std::min<uint64_t>((B * s->n + 3) / 4, (uint64_t)c->cus * 6);
+        {
+            ProfScope ps(c, st, "fingerprint_batch", B * s->n * S * 4);
+            if (vec)
+                hipLaunchKernelGGL(fingerprint_batch_kernel<true>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)S,
+                                   b0, B, s->d_weights, s->d_pos, s->d_lfix, s->d_FB, row, s->d_flag);
+            else
+                hipLaunchKernelGGL(fingerprint_batch_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)S,
+                                   b0, B, s->d_weights, s->d_pos, s->d_lfix, s->d_FB, row, s->d_flag);
+            HIP_TRY(hipGetLastError());
+        }
+        {
+            ProfScope ps(c, st, "scrub_transform_batch");
+            if ((rc = transform_bitrev(s->ntt_batch, s->d_FB, s->d_GB, false, true, (uint32_t)(RW * B), st)) != FASTECC_OK) return rc;
+        }
+        if (m_lo < NC) {  // (always: n > k)
+            ProfScope ps(c, st, "scrub_syndromes_batch");
+            const uint64_t items = (NC - m_lo) * B;  // <= NC * batch_cap <= 2^21
+            hipLaunchKernelGGL(syndrome_batch_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, s->d_GB, s->lgc, (uint32_t)NC, (uint32_t)m_lo, row,
+                               (uint32_t)B, b0, s->d_flag);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    flag.assign(count, 0);
+    HIP_TRY(hipMemcpyAsync(flag.data(), s->d_flag, count, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return FASTECC_OK;
+}
+
 int report(const std::vector<uint32_t>& found, uint64_t* blocks, uint64_t cap, uint64_t* count)
 {
     for (uint64_t i = 0; i < found.size() && i < cap; i++) blocks[i] = found[i];
@@ -657,6 +827,68 @@ int fastecc_correct(fastecc_ctx* c, void* data, void* parity, int mem_kind, void
         if (r != FASTECC_OK) return r;
         if (!ok) return FASTECC_E_UNCORRECTABLE;
         return report(found, blocks, cap, count);
+    });
+}
+
+int fastecc_verify_batch(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, void* stream, uint64_t seed, uint8_t* consistent,
+                         uint64_t* inconsistent)
+{
+    if (!consistent || !inconsistent) return FASTECC_E_INVAL;
+    const int rc = batch_args(c, data, parity, count);
+    if (rc != FASTECC_OK) return rc;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallLock lk(c->mu);
+    return guarded([&]() -> int {
+        std::vector<uint8_t> flag;
+        const int r = verify_batch_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, seed, (hipStream_t)stream, flag);
+        if (r != FASTECC_OK) return r;
+        uint64_t bad = 0;
+        for (uint64_t b = 0; b < count; b++) {
+            consistent[b] = flag[b] ? 0 : 1;
+            bad += flag[b] ? 1 : 0;
+        }
+        *inconsistent = bad;
+        return FASTECC_OK;
+    });
+}
+
+int fastecc_correct_batch(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream, uint64_t seed, uint8_t* status, uint64_t* inconsistent)
+{
+    if (!status || !inconsistent) return FASTECC_E_INVAL;
+    const int rc = batch_args(c, data, parity, count);
+    if (rc != FASTECC_OK) return rc;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    return guarded([&]() -> int {
+        std::vector<uint8_t> flag;
+        {
+            CallLock lk(c->mu);
+            const int r = verify_batch_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, seed, (hipStream_t)stream, flag);
+            if (r != FASTECC_OK) return r;
+        }
+        // failures are rare: fastecc_correct on each inconsistent stripe through its own pointers (it takes the lock itself)
+        const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
+        std::vector<uint8_t> st(count, 0);
+        uint64_t bad = 0;
+        bool uncorrectable = false;
+        for (uint64_t b = 0; b < count; b++) {
+            if (!flag[b]) continue;
+            bad++;
+            uint64_t found = 0;
+            const int r = fastecc_correct(c, (char*)data + b * data_bytes, (char*)parity + b * parity_bytes, FASTECC_MEM_DEVICE, stream, seed, nullptr, 0, &found);
+            if (r == FASTECC_E_UNCORRECTABLE) {
+                st[b] = 2;
+                uncorrectable = true;
+            } else if (r != FASTECC_OK) {
+                return r;
+            } else {
+                st[b] = found ? 1 : 0;
+            }
+        }
+        std::copy(st.begin(), st.end(), status);
+        *inconsistent = bad;
+        return uncorrectable ? FASTECC_E_UNCORRECTABLE : FASTECC_OK;
     });
 }
 

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 320 /* 0.3.2: batched decode and repair of many stripes with one erasure pattern (fastecc_decode_batch / _repair_batch) */
+#define FASTECC_VERSION 330 /* 0.3.3: batched scrub of many stripes (fastecc_verify_batch / _correct_batch) */
 
 enum {
     FASTECC_OK = 0,
@@ -371,6 +371,32 @@ int fastecc_locate_errors(fastecc_ctx *ctx, const void *data, const void *parity
                           uint64_t *blocks, uint64_t cap, uint64_t *count);
 int fastecc_correct(fastecc_ctx *ctx, void *data, void *parity, int mem_kind, void *stream, uint64_t seed, uint64_t *blocks,
                     uint64_t cap, uint64_t *count);
+/*
+ * Scrubbing a pool: many stripes, laid out back to back as for fastecc_decode_batch — stripe b's k data blocks at data + b*k*block_bytes,
+ * its n - k parity blocks at parity + b*(n-k)*block_bytes.  Same codes, memory kind (DEVICE) and refusals as fastecc_verify, and
+ * FASTECC_E_INVAL before any device work for null pointers (consistent / status / inconsistent included), count == 0, data or parity
+ * not 4-byte aligned, byte sizes beyond 64 bits.  A refused call writes nothing.  Synchronous: ordered after prior work on `stream`.
+ *   fastecc_verify_batch  : consistent[b] (host, count bytes) = 1 exactly when fastecc_verify with the same seed reports stripe b
+ *                           consistent, else 0; *inconsistent = the number of zeros.  Reads only.
+ *   fastecc_correct_batch : fastecc_verify_batch, then fastecc_correct with the same seed on each inconsistent stripe through its own
+ *                           pointers — this REPLACES the context's prepared erasure pattern.  status[b] (host, count bytes): 0 = consistent
+ *                           and untouched, 1 = corrected, 2 = uncorrectable (fastecc_correct's guarantee and refusal, per stripe);
+ *                           *inconsistent = the number of non-zero entries.  Returns FASTECC_E_UNCORRECTABLE if any stripe has status 2,
+ *                           with status filled for every stripe either way.
+ * Why the answer is the per-stripe one, bit for bit: the fingerprint of a block depends on its words and the seed only, and the syndrome
+ * transform acts on each word column of the fingerprint stripe on its own.  The batch puts stripe b's three fingerprint columns at word
+ * columns 4b .. 4b+2 of one stripe of NC rows and runs the single-stripe transform once over all of them: every column sees exactly the
+ * numbers fastecc_verify computes for that stripe, and exact arithmetic over GF(p) gives the same coefficients.
+ * Chunks: a context takes up to 2^21 / NC stripes (at most 2^16, a power of two; NC = the code's transform length N << e) per chunk, so
+ * the fingerprint stripe is at most 32 MiB; option "scrub_batch_chunk" (0 = that, else at most this many, at call time) lowers it.  Per
+ * chunk: one fingerprint pass that reads the chunk's codewords once (the fixed erasures' locator is applied as it stores), one transform
+ * of NC points over 4B words per row, one syndrome check; then one copy of count flags and one synchronisation for the whole call.  The
+ * read of the codewords is the cost that scales; the rest is a few launches per chunk.
+ */
+int fastecc_verify_batch(fastecc_ctx *ctx, const void *data, const void *parity, uint64_t count, void *stream, uint64_t seed,
+                         uint8_t *consistent, uint64_t *inconsistent);
+int fastecc_correct_batch(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, void *stream, uint64_t seed, uint8_t *status,
+                          uint64_t *inconsistent);
 
 /*
  * Small writes: bring the parity up to date after `count` data blocks changed, without reading the rest of the stripe.  The code is
@@ -489,6 +515,8 @@ const char *fastecc_plan_string(fastecc_ctx *ctx);
  *                  2 = MFMA (i8 digits; falls back to 1 where it cannot run).  Same bits either way;
  *   "decode_batch_kernel" = 0 / 1 / 2 (default 0 = choose; at call time): how fastecc_decode_batch / _repair_batch run a direct-path pass — 1 = one
  *                  launch over all stripes whenever the pass allows it, 2 = stripe by stripe (direct_kernel then picks the kernel).  Same bits either way;
+ *   "scrub_batch_chunk" = 0 .. INT_MAX (default 0 = the context's chunk capacity; at call time): the most stripes per chunk of
+ *                  fastecc_verify_batch / _correct_batch.  Same answers either way;
  *   "fuse_radix" = 0 / 1 (default 1; mixed-radix contexts): the odd-radix level fused into the outer tile passes, or as its own passes;
  *   "slabs" = H (1..32): encode H column slabs of the stripe on internal streams, each one pass
  * behind the previous, so that different kinds of passes overlap on the GPU, or with "slab_mode" = 1 one
