@@ -660,19 +660,6 @@ __global__ __launch_bounds__(256) void restore_parity_kernel(const uint32_t* __r
     store_vec<V>(parity + (size_t)q * S + col, x);
 }
 
-// FASTECC_TRACE_PREPARE=1: wall-clock of the phases of fastecc_decode_prepare on stderr (where does a first call spend its time)
-struct PhaseTimer {
-    bool on = getenv("FASTECC_TRACE_PREPARE") != nullptr;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    void mark(const char* what)
-    {
-        if (!on) return;
-        const auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "[fastecc prepare] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    }
-};
-
 dim3 grid_of(uint64_t items) { return dim3((unsigned)((items + 255) / 256)); }  // one thread per item, 256 per workgroup
 
 // The row kernels above over `rows` rows of S words: one wave per (row, column chunk of 64 V words), V = 4 when S is a multiple of 4 and every

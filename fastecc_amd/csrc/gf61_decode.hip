@@ -21,12 +21,12 @@
 #include <algorithm>
 #include <cstdio>
 #include <new>
-#include <chrono>
 #include <vector>
 
 #include "../../include/fastecc.h"
 #include "gf61.hpp"
 #include "gf61_path.hpp"
+#include "internal.hpp"
 
 namespace fastecc {
 namespace p61 {
@@ -46,11 +46,11 @@ __device__ __forceinline__ Elem ld(const uint64_t* p)
     const u64x2 t = *reinterpret_cast<const u64x2*>(p);
     return Elem{t.x, t.y};
 }
-__device__ __forceinline__ void st(uint64_t* p, Elem e)
+__device__ __forceinline__ void st(uint64_t* p, Elem v)
 {
     u64x2 t;
-    t.x = e.re;
-    t.y = e.im;
+    t.x = v.re;
+    t.y = v.im;
     *reinterpret_cast<u64x2*>(p) = t;
 }
 // canonical x canonical -> canonical (both operands per lane: the twiddle limbs live in VGPRs here)
@@ -62,11 +62,11 @@ __device__ __forceinline__ uint64_t addc(uint64_t x, uint64_t y)
 }
 __device__ __forceinline__ uint64_t subc(uint64_t x, uint64_t y) { return x >= y ? x - y : x + P - y; }
 __device__ __forceinline__ Elem addc(Elem x, Elem y) { return Elem{addc(x.re, y.re), addc(x.im, y.im)}; }
-__device__ __forceinline__ Elem powc(Elem x, uint64_t e, const gf61::Opaque& k)
+__device__ __forceinline__ Elem powc(Elem x, uint64_t n, const gf61::Opaque& k)
 {
     Elem r{1, 0};
-    for (; e; e >>= 1) {
-        if (e & 1u) r = mulc(r, x, k);
+    for (; n; n >>= 1) {
+        if (n & 1u) r = mulc(r, x, k);
         x = mulc(x, x, k);
     }
     return r;
@@ -343,7 +343,15 @@ __global__ __launch_bounds__(256) void k_finish_lost(const uint64_t* __restrict_
     if (gout_all) st(gout_all + 2ull * u, g);  // every lost position, parity too: fastecc_repair in one transform
 }
 
-// One wave per (row, 64-element column chunk); the row's factor is wave-uniform.
+// The row kernels: one wave per (row, 64-element column chunk), four waves per workgroup (host: RowGrid); the row's factor is wave-uniform.
+// This wave's item (in range below `items`), its row, and this lane's column (it may lie beyond a ragged last chunk)
+struct RowItem {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t item = (uint64_t)blockIdx.x * 4u + wave;
+    __device__ __forceinline__ uint32_t row(uint32_t col_chunks) const { return (uint32_t)(item / col_chunks); }
+    __device__ __forceinline__ uint32_t col(uint32_t col_chunks) const { return (uint32_t)(item % col_chunks) * 64u + lane; }
+};
 using const_u64_ptr = const uint64_t __attribute__((address_space(4)))*;
 __device__ __forceinline__ const_u64_ptr as_constant(const uint64_t* p) { return (const_u64_ptr)(reinterpret_cast<uintptr_t>(p)); }
 
@@ -351,13 +359,9 @@ __device__ __forceinline__ const_u64_ptr as_constant(const uint64_t* p) { return
 __global__ __launch_bounds__(256) void k_gather(const uint64_t* __restrict__ data, const uint64_t* __restrict__ parity, uint64_t* __restrict__ work,
                                                 const uint64_t* __restrict__ fin, uint32_t elems, uint32_t col_chunks, uint64_t items)
 {
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t item = (uint64_t)blockIdx.x * 4u + wave;
-    if (item >= items) return;
-    const uint32_t cc = (uint32_t)(item % col_chunks);
-    const uint32_t u = (uint32_t)(item / col_chunks);
-    const uint32_t col = cc * 64u + lane;
+    const RowItem it;
+    if (it.item >= items) return;
+    const uint32_t u = it.row(col_chunks), col = it.col(col_chunks);
     if (col >= elems) return;
     const gf61::Opaque k = gf61::make_opaque();
     const uint64_t fre = as_constant(fin)[2ull * u], fim = as_constant(fin)[2ull * u + 1];
@@ -374,13 +378,9 @@ __global__ __launch_bounds__(256) void k_gather(const uint64_t* __restrict__ dat
 __global__ __launch_bounds__(256) void k_split_small_gather(const uint64_t* __restrict__ parity, uint64_t* __restrict__ small, const uint64_t* __restrict__ fin,
                                                             uint32_t elems, int h, uint32_t col_chunks, uint64_t items)
 {
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t item = (uint64_t)blockIdx.x * 4u + wave;
-    if (item >= items) return;
-    const uint32_t cc = (uint32_t)(item % col_chunks);
-    const uint32_t m = (uint32_t)(item / col_chunks);
-    const uint32_t col = cc * 64u + lane;
+    const RowItem it;
+    if (it.item >= items) return;
+    const uint32_t m = it.row(col_chunks), col = it.col(col_chunks);
     if (col >= elems) return;
     const gf61::Opaque k = gf61::make_opaque();
     const uint64_t j = (uint64_t)m << h;
@@ -395,13 +395,9 @@ __global__ __launch_bounds__(256) void k_gather_map(const uint64_t* __restrict__
                                                     const uint64_t* __restrict__ fin, const uint32_t* __restrict__ srcmap, uint32_t elems, uint32_t col_chunks,
                                                     uint64_t items)
 {
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t item = (uint64_t)blockIdx.x * 4u + wave;
-    if (item >= items) return;
-    const uint32_t cc = (uint32_t)(item % col_chunks);
-    const uint32_t u = (uint32_t)(item / col_chunks);
-    const uint32_t col = cc * 64u + lane;
+    const RowItem it;
+    if (it.item >= items) return;
+    const uint32_t u = it.row(col_chunks), col = it.col(col_chunks);
     if (col >= elems) return;
     const gf61::Opaque k = gf61::make_opaque();
     const uint64_t fre = as_constant(fin)[2ull * u], fim = as_constant(fin)[2ull * u + 1];
@@ -417,14 +413,11 @@ __global__ __launch_bounds__(256) void k_gather_map(const uint64_t* __restrict__
 __global__ __launch_bounds__(256) void k_restore_map(const uint64_t* __restrict__ again, uint64_t* __restrict__ parity, const uint8_t* __restrict__ lost,
                                                      uint32_t elems, uint32_t col_chunks, uint64_t items)
 {
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t item = (uint64_t)blockIdx.x * 4u + wave;
-    if (item >= items) return;
-    const uint32_t cc = (uint32_t)(item % col_chunks);
-    const uint32_t q = (uint32_t)(item / col_chunks);
+    const RowItem it;
+    if (it.item >= items) return;
+    const uint32_t q = it.row(col_chunks);
     if (!lost[q]) return;
-    const uint32_t col = cc * 64u + lane;
+    const uint32_t col = it.col(col_chunks);
     if (col >= elems) return;
     st(parity + ((uint64_t)q * elems + col) * 2, ld(again + ((uint64_t)q * elems + col) * 2));
 }
@@ -443,15 +436,12 @@ __global__ __launch_bounds__(256) void k_gout_par(const uint64_t* __restrict__ g
 __global__ __launch_bounds__(256) void k_scatter(const uint64_t* __restrict__ work, uint64_t* __restrict__ data, const uint64_t* __restrict__ gout,
                                                  uint32_t elems, uint32_t col_chunks, uint64_t items, uint32_t stride)
 {
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t item = (uint64_t)blockIdx.x * 4u + wave;
-    if (item >= items) return;
-    const uint32_t cc = (uint32_t)(item % col_chunks);
-    const uint32_t i = (uint32_t)(item / col_chunks);
+    const RowItem it;
+    if (it.item >= items) return;
+    const uint32_t i = it.row(col_chunks);
     const uint64_t gre = as_constant(gout)[2ull * i], gim = as_constant(gout)[2ull * i + 1];
     if ((gre | gim) == 0) return;  // wave-uniform
-    const uint32_t col = cc * 64u + lane;
+    const uint32_t col = it.col(col_chunks);
     if (col >= elems) return;
     const gf61::Opaque k = gf61::make_opaque();
     const Elem v = gf61::mul(ld(work + ((uint64_t)stride * i * elems + col) * 2), gf61::make_twiddle(gre, gim), k);  // stride 2: row 2i of the 2k outputs
@@ -462,14 +452,11 @@ __global__ __launch_bounds__(256) void k_scatter(const uint64_t* __restrict__ wo
 __global__ __launch_bounds__(256) void k_restore(const uint64_t* __restrict__ again, uint64_t* __restrict__ parity, const uint8_t* __restrict__ state,
                                                  uint32_t elems, uint32_t col_chunks, uint64_t items)
 {
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t item = (uint64_t)blockIdx.x * 4u + wave;
-    if (item >= items) return;
-    const uint32_t cc = (uint32_t)(item % col_chunks);
-    const uint32_t j = (uint32_t)(item / col_chunks);
+    const RowItem it;
+    if (it.item >= items) return;
+    const uint32_t j = it.row(col_chunks);
     if (state[2u * j + 1u] == ST_HELD) return;
-    const uint32_t col = cc * 64u + lane;
+    const uint32_t col = it.col(col_chunks);
     if (col >= elems) return;
     st(parity + ((uint64_t)j * elems + col) * 2, ld(again + ((uint64_t)j * elems + col) * 2));
 }
@@ -515,7 +502,7 @@ __device__ __forceinline__ uint64_t gather3(const Acc3& s)
 // (x - x_r) over the lost data rows, R_r = R / (x - x_r), and y^k = -1 at every parity point:
 //     data row i, lost data row r:     C_r x_i R_r(x_i) / A(x_i),                   C_r = -A(x_r) / (x_r R_r(x_r))
 //     data row i, lost parity block t: c_t x_i R(x_i) / (A(x_i) (y_t - x_i)),       c_t = -2 A(y_t) / (k R(y_t))
-//     parity node a: on the host (decode_prepare), packed by k_direct_pack
+//     parity node a: on the host (direct_weights), packed by k_direct_pack
 // params (elements): [0, MAX) the targets x_r then y_t, [MAX, 2 MAX) y_a, [2 MAX, 3 MAX) C_r then c_t
 __device__ __forceinline__ Elem subc(Elem x, Elem y) { return Elem{subc(x.re, y.re), subc(x.im, y.im)}; }
 __device__ __forceinline__ void store_weight(uint32_t* __restrict__ o, Elem v)
@@ -524,8 +511,8 @@ __device__ __forceinline__ void store_weight(uint32_t* __restrict__ o, Elem v)
         for (int i = 0; i < COEF_WORDS; ++i) o[i] = 0;
         return;
     }
-    const uint64_t e = gf61::P - v.im;
-    const uint64_t parts[6] = {v.re, times_2_32(v.re), v.im, times_2_32(v.im), e, times_2_32(e)};
+    const uint64_t nim = gf61::P - v.im;
+    const uint64_t parts[6] = {v.re, times_2_32(v.re), v.im, times_2_32(v.im), nim, times_2_32(nim)};
     for (int i = 0; i < 6; ++i) {
         const Limbs l = limbs_of(parts[i]);
         o[3 * i] = l.l0;
@@ -583,14 +570,10 @@ __global__ __launch_bounds__(256) void k_direct_accumulate(const uint64_t* __res
     constexpr int U = EB >= 8 ? 2 : 4;      // rows per trip of the loop; the next trip's rows are requested before this trip's arithmetic
     constexpr int G = EB >= 4 ? 4 : EB;     // outputs and
     constexpr int RB = EB >= 4 ? 1 : 4 / EB;  // rows whose limbs come in one scalar fetch (72 SGPRs); rows are adjacent in the table when pad == EB (EB < 8)
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t item = (uint64_t)blockIdx.x * 4u + wave;
-    if (item >= items) return;
-    const uint32_t j0 = blockIdx.y * EB;
-    const uint32_t cc = (uint32_t)(item % col_chunks);
-    const uint32_t chunk = (uint32_t)(item / col_chunks);
-    const uint32_t col = min(cc * 64u + lane, elems - 1u);  // lanes past a ragged end repeat the last column (same loads, same stores)
+    const RowItem it;
+    if (it.item >= items) return;
+    const uint32_t j0 = blockIdx.y * EB, chunk = it.row(col_chunks);
+    const uint32_t col = min(it.col(col_chunks), elems - 1u);  // lanes past a ragged end repeat the last column (same loads, same stores)
     Acc3 re[EB], im[EB];
 #pragma unroll
     for (int j = 0; j < EB; ++j) re[j] = im[j] = Acc3{0, 0, 0};
@@ -653,12 +636,12 @@ __global__ __launch_bounds__(256) void k_direct_accumulate(const uint64_t* __res
 }
 
 __global__ __launch_bounds__(256) void k_direct_reduce1(const uint64_t* __restrict__ partial, uint64_t* __restrict__ stage, uint32_t elems, uint32_t chunks,
-                                                        int pad, int e)
+                                                        int pad, int outputs)
 {
     const uint32_t col = blockIdx.x * blockDim.x + threadIdx.x;
     const int j = blockIdx.y;
     const uint32_t seg = blockIdx.z;
-    if (col >= elems || j >= e) return;
+    if (col >= elems || j >= outputs) return;
     const gf61::Opaque k = gf61::make_opaque();
     const uint32_t per = (chunks + DIRECT_SEGS - 1) / DIRECT_SEGS;
     const uint32_t c0 = seg * per, c1 = min(c0 + per, chunks);
@@ -668,11 +651,11 @@ __global__ __launch_bounds__(256) void k_direct_reduce1(const uint64_t* __restri
     st(stage + 2ull * (((uint64_t)seg * pad + j) * elems + col), v);
 }
 __global__ __launch_bounds__(256) void k_direct_reduce2(const uint64_t* __restrict__ stage, const uint32_t* __restrict__ epos, uint64_t* __restrict__ data,
-                                                        uint64_t* __restrict__ parity, uint32_t elems, int pad, int e, bool with_parity)
+                                                        uint64_t* __restrict__ parity, uint32_t elems, int pad, int outputs, bool with_parity)
 {
     const uint32_t col = blockIdx.x * blockDim.x + threadIdx.x;
     const int j = blockIdx.y;
-    if (col >= elems || j >= e) return;
+    if (col >= elems || j >= outputs) return;
     const uint32_t pos = epos[j];
     if ((pos & 1u) && !with_parity) return;
     const gf61::Opaque k = gf61::make_opaque();
@@ -681,31 +664,28 @@ __global__ __launch_bounds__(256) void k_direct_reduce2(const uint64_t* __restri
     st(((pos & 1u) ? parity : data) + ((uint64_t)(pos >> 1) * elems + col) * 2, gf61::canon(v));
 }
 
-// FASTECC_TRACE_PREPARE=1: wall-clock of the phases of the first decode_prepare on stderr (as decode.hip does for the 32-bit field)
-struct PhaseTimer {
-    bool on = getenv("FASTECC_TRACE_PREPARE") != nullptr;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    void mark(const char* what)
-    {
-        if (!on) return;
-        const auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "[fastecc prepare p61] %-24s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    }
+// ---- host helpers ----
+dim3 grid_of(uint64_t items) { return dim3((unsigned)((items + 255) / 256)); }  // one thread per item, 256 per workgroup
+
+// The grid of a row kernel (row_item): one wave per (row, chunk of 64 element columns), four waves per workgroup
+struct RowGrid {
+    uint32_t col_chunks;
+    uint64_t items;
+    RowGrid(uint64_t rows, uint32_t elems) : col_chunks((elems + 63) / 64), items(rows * col_chunks) {}
+    dim3 grid(unsigned y = 1) const { return dim3((unsigned)((items + 3) / 4), y); }
 };
 
-int fail(char* detail, size_t cap, hipError_t e, const char* what)
+// A buffer that only grows: *ptr holds *have units of `unit` bytes and is replaced when `need` is more (no memory: it holds nothing)
+template <class T> hipError_t grow(T** ptr, uint64_t* have, uint64_t need, uint64_t unit)
 {
-    if (detail && cap) snprintf(detail, cap, "%s: %s", what, hipGetErrorString(e));
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? FASTECC_E_NOMEM : FASTECC_E_DEVICE;
+    if (*have >= need) return hipSuccess;
+    if (*ptr) (void)hipFree(*ptr);
+    *ptr = nullptr;
+    *have = 0;
+    const hipError_t err = hipMalloc((void**)ptr, need * unit);
+    if (err == hipSuccess) *have = need;
+    return err;
 }
-
-#define D61_TRY(expr)                                              \
-    do {                                                           \
-        hipError_t e_ = (expr);                                    \
-        if (e_ != hipSuccess) return fail(detail, cap, e_, #expr); \
-    } while (0)
 
 }  // namespace
 
@@ -760,7 +740,7 @@ struct Decoder {
     uint64_t erased_data = 0, erased_parity = 0;
     bool built = false;  // contexts, buffers and the w^u table exist
     // few losses: the direct path
-    int direct = 0, direct_pad = 0;
+    int direct = 0, direct_pad = 0;      // its outputs (0: the transform path) and their number rounded up to a power of two
     uint64_t direct_nc = 0;              // positions of the code the direct path works in (2k; NC unless e > 1)
     int direct_ed = 0;                   // ... of its outputs the first direct_ed are the lost data blocks
     uint64_t direct_rows = 0;            // ... and its rows: the k data blocks, then direct_ed parity blocks
@@ -779,279 +759,367 @@ bool decoder_ready(const Decoder* d) { return d && d->ready; }
 void destroy_decoder(Decoder* d)
 {
     if (!d) return;
-    destroy(d->transform);
-    destroy(d->half);
-    destroy(d->pattern);
-    destroy(d->narrow_tree);
-    destroy(d->narrow_tree_inv);
-    for (Path* t : d->tree_inv) destroy(t);
-    destroy(d->narrow_pattern);
-    destroy(d->splitp);
-    for (Path* t : d->small) destroy(t);
-    for (void* b : {(void*)d->small_buf, (void*)d->split_af, (void*)d->split_work, (void*)d->state_real, (void*)d->srcmap, (void*)d->parity_lost, (void*)d->cos_work,
-                    (void*)d->split_q2, (void*)d->split_pos_odd, (void*)d->gout_par})
-        if (b) (void)hipFree(b);
-    for (Path* t : d->tree) destroy(t);
-    for (void* b : {(void*)d->tree_x, (void*)d->tree_y, (void*)d->tree_f, (void*)d->wpow, (void*)d->roots, (void*)d->lv, (void*)d->fin,
-                    (void*)d->gout, (void*)d->gout_all, (void*)d->erased, (void*)d->state, (void*)d->work, (void*)d->rec, (void*)d->again, (void*)d->stage, (void*)d->direct_coef,
-                    (void*)d->direct_inv, (void*)d->direct_pos, (void*)d->direct_partial, (void*)d->direct_wpow})
+    for (Path* p : {d->transform, d->half, d->pattern, d->narrow_tree, d->narrow_tree_inv, d->narrow_pattern, d->splitp}) destroy(p);
+    for (const std::vector<Path*>* level : {&d->tree, &d->tree_inv})
+        for (Path* p : *level) destroy(p);
+    for (Path* p : d->small) destroy(p);
+    for (void* b : {(void*)d->tree_x, (void*)d->tree_y, (void*)d->tree_f, (void*)d->wpow, (void*)d->roots, (void*)d->lv, (void*)d->fin, (void*)d->gout,
+                    (void*)d->gout_all, (void*)d->erased, (void*)d->state, (void*)d->work, (void*)d->rec, (void*)d->again, (void*)d->stage, (void*)d->srcmap,
+                    (void*)d->parity_lost, (void*)d->cos_work, (void*)d->small_buf, (void*)d->split_af, (void*)d->split_work, (void*)d->state_real,
+                    (void*)d->split_q2, (void*)d->split_pos_odd, (void*)d->gout_par, (void*)d->direct_coef, (void*)d->direct_inv, (void*)d->direct_pos,
+                    (void*)d->direct_partial, (void*)d->direct_wpow})
         if (b) (void)hipFree(b);
     delete d;
 }
 
-int decode_prepare(Decoder** slot, int log2k, uint64_t elems, const uint8_t* data_present, const uint8_t* parity_present, int direct_max, char* detail,
-                   size_t cap, int split, int e)
-{
-    if (e < 1 || e > 3 || (*slot && (*slot)->built && (*slot)->e != e)) return FASTECC_E_INVAL;
-    PhaseTimer pt_call;
-    const uint64_t N = 1ull << log2k, NC = N << e, M = NC - N;
-    if (NC > 0x7FFFFFFFull) return FASTECC_E_UNSUPPORTED;
-    std::vector<uint8_t> state(NC);
-    std::vector<uint32_t> srcmap(e > 1 ? NC : 0);
-    std::vector<uint8_t> plost(e > 1 ? M : 0);
-    uint64_t erased_data = 0, erased_parity = 0;
-    if (e == 1) {  // data block i at 2i, parity block j at 2j + 1: one interleaving pass
-        for (uint64_t i = 0; i < N; i++) {
-            const uint8_t a = data_present[i] != 0, b = parity_present[i] != 0;
-            state[2 * i] = a ? ST_HELD : ST_LOST;
-            state[2 * i + 1] = b ? ST_HELD : ST_LOST;
-            erased_data += !a;
-            erased_parity += !b;
-        }
-    } else {
-        for (uint64_t i = 0; i < N; i++) {
-            state[i << e] = data_present[i] ? ST_HELD : ST_LOST;
-            erased_data += !data_present[i];
-            srcmap[i << e] = (uint32_t)i;
-        }
-        for (uint64_t q = 0; q < M; q++) {
-            // parity block q = block j of coset t: generator w_(2^jt k)^c, jt = floor(log2(t + 1)) + 1, c the (t + 2 - 2^(jt-1))-th odd number (include/fastecc.h)
-            const uint64_t t = q >> log2k, j = q & (N - 1);
-            int jt = 1;
-            while ((1ull << jt) - 1 <= t) jt++;
-            const uint64_t c = 2 * (t + 1 - (1ull << (jt - 1))) + 1;
-            const uint64_t u = (c << (e - jt)) + (j << e);
-            state[u] = parity_present[q] ? ST_HELD : ST_LOST;
-            erased_parity += !parity_present[q];
-            srcmap[u] = (uint32_t)q | 0x80000000u;
-            plost[q] = !parity_present[q];
-        }
-    }
-    const int direct_max_user = direct_max;
-    if (e > 1) {
-        split = 0;       // the even / odd split and the direct path are the (2k,k) code's (the latter: of the (2k,k) code inside, see below)
-        direct_max = 0;
-    }
-    // ---- even / odd split: recovering e data blocks takes e parity blocks, so the others may count as erased too; take them at multiples of 2^h of
-    // the parity half (largest h <= 5 that leaves enough survivors) and the parity half's transform shrinks to k >> h rows ----
-    int split_shift = 0;
-    uint64_t unused_held = 0;  // parity blocks the caller holds that the split leaves aside: they count as lost in the locator
-    const bool few = erased_data + erased_parity != 0 && (int)(erased_data + erased_parity) <= std::min(direct_max, DECODE_DIRECT_MAX);
-    if (split && log2k >= 11 && erased_data != 0 && !few && !(*slot && (*slot)->split_unavailable)) {
-        // (a pattern that has lost parity blocks too may be REPAIRED: the split then runs a second MID + DIT chain for the odd positions — or, without
-        //  the memory for its extra stripe, re-encodes — see decode())
-        for (int h = 5; h >= 1 && split_shift == 0; h--) {  // (light patterns stop at h = 5: k / 32 flags read)
-            uint64_t held = 0;
-            for (uint64_t j = 0; j < N; j += 1ull << h) held += parity_present[j] != 0;
-            if (held >= erased_data) {
-                split_shift = h;
-                unused_held = (N - erased_parity) - held;  // marked on the device (k_mark_unused): the host's `state` stays the caller's
-            }
-        }
-    }
-    // the positions themselves are listed on the device (k_erased_list); the host needs their number, and the list itself only for the few-loss path
-    const uint64_t n_erased = erased_data + erased_parity + unused_held;
-    if (n_erased > NC - N) return FASTECC_E_INVAL;  // fewer than k blocks survive
-    std::vector<uint32_t> erased;
-    if (n_erased != 0 && (int64_t)n_erased <= std::min(direct_max, DECODE_DIRECT_MAX))
-        for (uint64_t u = 0; u < NC; u++)
-            if (state[u] == ST_LOST) erased.push_back((uint32_t)u);
-    // n = 4k / 8k, few losses: the data and the FIRST coset are a (2k,k) code of their own (generator w_2k, parity blocks 0 .. k-1), and that code's
-    // direct path rebuilds the data from its 2k - few survivors — a read of 2k blocks instead of a transform over n; lost parity blocks of the other
-    // cosets are re-encoded (fastecc_repair)
+namespace {
+
+// ---- decode_prepare ----
+// FASTECC_TRACE_PREPARE=1: wall-clock of the phases of the first decode_prepare on stderr (as decode.hip does for the 32-bit field)
+PhaseTimer phase_timer() { return PhaseTimer("[fastecc prepare p61]", 24); }
+
+// What the pattern scan found
+struct PatternScan {
+    std::vector<uint8_t> state;        // ST_* per position
+    std::vector<uint32_t> srcmap;      // e > 1: position -> block (bit 31: parity stripe)
+    std::vector<uint8_t> parity_lost;  // e > 1: the lost parity blocks by number
+    uint64_t erased_data = 0, erased_parity = 0;  // lost blocks
+    int split_shift = 0;               // non-zero: the pattern goes through the even / odd split with the parity blocks at multiples of 2^split_shift
+    uint64_t unused_held = 0;          // parity blocks the caller holds that the split leaves aside: they count as lost in the locator
+    std::vector<uint32_t> erased;      // few losses: the lost positions
+    // n = 4k / 8k, few losses: the data and the FIRST coset as a (2k,k) code of their own
     std::vector<uint8_t> state_sub;
     std::vector<uint32_t> erased_sub;
-    if (e > 1 && erased_data != 0 && (int64_t)erased_data <= std::min(direct_max_user, DECODE_DIRECT_MAX)) {
-        uint64_t lost0 = 0;
-        for (uint64_t j = 0; j < N; j++) lost0 += !parity_present[j];
-        if ((int64_t)(erased_data + lost0) <= std::min(direct_max_user, DECODE_DIRECT_MAX) && erased_data + lost0 <= N) {  // (k of the inner code's 2k blocks survive)
-            state_sub.resize(2 * N);
-            for (uint64_t i = 0; i < N; i++) {
-                state_sub[2 * i] = data_present[i] ? ST_HELD : ST_LOST;
-                state_sub[2 * i + 1] = parity_present[i] ? ST_HELD : ST_LOST;
-            }
-            for (uint64_t u = 0; u < 2 * N; u++)
-                if (state_sub[u] == ST_LOST) erased_sub.push_back((uint32_t)u);
-        }
-    }
-    pt_call.mark("pattern scan (host)");
+    uint64_t n_erased() const { return erased_data + erased_parity + unused_held; }  // roots of the locator
+};
 
-    if (!*slot) {
-        *slot = new (std::nothrow) Decoder();
-        if (!*slot) return FASTECC_E_NOMEM;
-    }
-    Decoder* d = *slot;
-    d->ready = false;
-    d->log2k = log2k;
-    d->N = N;
-    d->NC = NC;
-    d->elems = elems;
-    d->erased_data = erased_data;
-    d->erased_parity = erased_parity;
-    if (erased_parity == 0) {
-        // fastecc_repair's re-encode stripes (n - k and, for n = 4k / 8k, k more blocks: up to 32 + 8 GiB at 2^17 x 64 KB) are only held while the
-        // pattern has lost parity blocks; the caller has waited for the last call that used them
-        for (uint64_t** b : {&d->again, &d->cos_work}) {
-            if (*b) (void)hipFree(*b);
-            *b = nullptr;
-        }
-    }
-    d->split_ready = false;
-    d->split_repair_ready = false;
-    d->split_shift = 0;
-    d->e = e;
-    d->M = M;
-    const uint64_t T = e == 1 ? N : NC;  // a power of two >= n - k, the most losses the code tolerates (3k -> 4k, 7k -> 8k: the roots beyond are padding)
-    int lgT = e == 1 ? log2k : log2k + e;
-    const int leaf_log = lgT >= TREE_LOW + 2 ? TREE_LOW : std::min(LEAF_LOG, lgT), leaf = 1 << leaf_log;
-    const bool narrow_tree = lgT + 1 - CHUNK_LOG >= 1, narrow_pattern = log2k + e + 1 - CHUNK_LOG >= 1;  // at least two chunks
-    const bool narrow_tree_inv = lgT - CHUNK_LOG >= 1;  // (the products are half as many columns)
+// The code the direct path works in: the (2k,k) code, or for n = 4k / 8k the (2k,k) code of the data and the first coset (generator w_2k, parity
+// blocks 0 .. k-1)
+struct DirectCode {
+    uint64_t NC;                         // its positions: data block i at 2i, parity block j at 2j + 1
+    const std::vector<uint8_t>& state;   // ST_* per position
+    const std::vector<uint32_t>& erased; // its lost positions
+    bool inner;                          // the code inside n = 4k / 8k: the w^u table is its own (w_2k, not w_n)
+};
 
-    // e > 1: the caller's lost parity blocks by number and the cosets that have one (what fastecc_repair re-encodes)
-    auto upload_parity_flags = [&]() -> int {
-        if (!d->parity_lost) D61_TRY(hipMalloc((void**)&d->parity_lost, M));
-        D61_TRY(hipMemcpyAsync(d->parity_lost, plost.data(), M, hipMemcpyHostToDevice, nullptr));
-        d->lost_coset_mask = 0;
-        for (uint64_t q = 0; q < M; q++)
-            if (plost[q]) d->lost_coset_mask |= 1u << (q / N);
-        return FASTECC_OK;
-    };
-    d->direct = 0;
-    const bool direct_sub = !erased_sub.empty();
-    const std::vector<uint32_t>& erased_all = erased;
-    const std::vector<uint8_t>& state_all = state;
-    const uint64_t NC_all = NC;
-    if (direct_sub || (!erased.empty() && (int)erased.size() <= std::min(direct_max, DECODE_DIRECT_MAX))) {
-        // few losses: a coefficient table, no locator tree and no transform contexts.  Out of memory for its tables is not an
-        // error: the transform path below needs none of them.
-        const int rc_direct = [&]() -> int {
-            const std::vector<uint32_t>& erased = direct_sub ? erased_sub : erased_all;
-            const std::vector<uint8_t>& state = direct_sub ? state_sub : state_all;
-            const uint64_t NC = direct_sub ? 2 * N : NC_all;  // (the code the path works in)
-            if (direct_sub) {
-                const int rc = upload_parity_flags();
-                if (rc != FASTECC_OK) return rc;
+// The weights of the direct path that the host computes, and the lists its kernels read
+struct DirectWeights {
+    int ed = 0, ep = 0, pad = 1;   // lost data blocks, lost parity blocks, their sum rounded up to a power of two
+    std::vector<uint64_t> params;  // k_direct_coef's: [0, MAX) the targets x_r then y_t, [MAX, 2 MAX) y_a, [2 MAX, 3 MAX) C_r then c_t
+    std::vector<uint32_t> lists;   // [0, MAX) output positions (row << 1 | parity), [MAX, 2 MAX) the parity nodes' rows
+    std::vector<Elem> nodew;       // [ed][pad]: the parity nodes' weights
+};
+// nodes: the data rows and the first |lost data| surviving parity blocks; targets: the lost data rows, then the lost parity blocks.  False: fewer
+// surviving parity blocks than lost data rows.
+bool direct_weights(const DirectCode& code, DirectWeights& out)
+{
+    const int lost = (int)code.erased.size();
+    const uint64_t Nd = code.NC / 2;
+    const Elem w = gf61::h_root(code.NC);
+    std::vector<uint32_t> Rr, Pl, An;
+    for (uint32_t u : code.erased) ((u & 1u) ? Pl : Rr).push_back(u >> 1);
+    for (uint64_t q = 0; q < Nd && An.size() < Rr.size(); q++)
+        if (code.state[2 * q + 1] == ST_HELD) An.push_back((uint32_t)q);
+    if (An.size() != Rr.size()) return false;
+    const int ed = out.ed = (int)Rr.size(), ep = out.ep = (int)Pl.size();
+    while (out.pad < lost) out.pad <<= 1;
+    const int pad = out.pad;
+    auto sub = [](Elem a, Elem b) { return Elem{gf61::h_subp(a.re, b.re), gf61::h_subp(a.im, b.im)}; };
+    auto neg = [](Elem a) { return Elem{gf61::h_subp(0, a.re), gf61::h_subp(0, a.im)}; };
+    auto mul = [](Elem a, Elem b) { return gf61::h_mul(a, b); };
+    const Elem one{1, 0}, two{2, 0}, kk{Nd % P, 0};
+    std::vector<Elem> z(lost), ya(ed), cst(lost), &nodew = out.nodew;
+    nodew.assign((size_t)ed * pad, Elem{0, 0});
+    for (int r = 0; r < ed; r++) z[r] = gf61::h_pow(w, 2ull * Rr[r]), ya[r] = gf61::h_pow(w, 2ull * An[r] + 1);
+    for (int t = 0; t < ep; t++) z[ed + t] = gf61::h_pow(w, 2ull * Pl[t] + 1);
+    auto A_at = [&](Elem x, int skip) { Elem v = one; for (int a = 0; a < ed; a++) if (a != skip) v = mul(v, sub(x, ya[a])); return v; };
+    auto R_at = [&](Elem x, int skip) { Elem v = one; for (int r = 0; r < ed; r++) if (r != skip) v = mul(v, sub(x, z[r])); return v; };
+    for (int r = 0; r < ed; r++) cst[r] = neg(mul(A_at(z[r], -1), gf61::h_inv(mul(z[r], R_at(z[r], r)))));  // C_r = -A(x_r) / (x_r R_r(x_r))
+    for (int t = ed; t < lost; t++) cst[t] = neg(mul(mul(two, A_at(z[t], -1)), gf61::h_inv(mul(kk, R_at(z[t], -1)))));  // c_t = -2 A(y_t) / (k R(y_t))
+    for (int a = 0; a < ed; a++) {
+        // parity node a (y_a^k - 1 = -2): target r: k A_a(x_r) R(y_a) / (-2 x_r R_r(x_r) A_a(y_a)); target t: A_a(y_t) R(y_a) / (R(y_t) A_a(y_a))
+        const Elem Rya = R_at(ya[a], -1), Aaya = A_at(ya[a], a);
+        for (int r = 0; r < ed; r++)
+            nodew[(size_t)a * pad + r] = mul(mul(mul(kk, A_at(z[r], a)), Rya), gf61::h_inv(neg(mul(mul(mul(two, z[r]), R_at(z[r], r)), Aaya))));
+        for (int t = ed; t < lost; t++) nodew[(size_t)a * pad + t] = mul(mul(A_at(z[t], a), Rya), gf61::h_inv(mul(R_at(z[t], -1), Aaya)));
+    }
+    std::vector<uint64_t>& params = out.params;
+    std::vector<uint32_t>& lists = out.lists;
+    params.assign(6 * DIRECT_MAX, 0);
+    lists.assign(2 * DIRECT_MAX, 0xFFFFFFFFu);
+    for (int j = 0; j < lost; j++) {
+        params[2 * j] = z[j].re, params[2 * j + 1] = z[j].im;
+        params[4 * DIRECT_MAX + 2 * j] = cst[j].re, params[4 * DIRECT_MAX + 2 * j + 1] = cst[j].im;
+        lists[j] = j < ed ? 2u * Rr[j] : 2u * Pl[j - ed] + 1u;
+    }
+    for (int a = 0; a < ed; a++) params[2 * DIRECT_MAX + 2 * a] = ya[a].re, params[2 * DIRECT_MAX + 2 * a + 1] = ya[a].im, lists[DIRECT_MAX + a] = An[a];
+    return true;
+}
+
+// One decode_prepare.  The stages and their names are those of decode.hip's Prepare where the stage is the same.
+struct Prepare {
+    Decoder** slot;
+    int log2k;
+    uint64_t elems;
+    const uint8_t *data_present, *parity_present;
+    int direct_max_user;  // the caller's "decode_direct_max": the limit of the inner code's direct path (e > 1)
+    char* detail;         // p61::create*'s message (the failed HIP calls of this file: hip_fail)
+    size_t cap;
+    int split_user;       // the caller's "decode_split"
+    int e;                // data block i at position i << e
+    // the even / odd split and the direct path are the (2k,k) code's (the latter for e > 1: of the (2k,k) code inside, see scan)
+    int split = e > 1 ? 0 : split_user, direct_max = e > 1 ? 0 : direct_max_user;
+    uint64_t N = 1ull << log2k, NC = N << e, M = NC - N;  // data blocks, positions, parity blocks
+    // The locator's product tree: T roots, a power of two >= n - k, the most losses the code tolerates (3k -> 4k, 7k -> 8k: the roots beyond are padding)
+    uint64_t T = e == 1 ? N : NC;
+    int lgT = e == 1 ? log2k : log2k + e, leaf_log = lgT >= TREE_LOW + 2 ? TREE_LOW : std::min(LEAF_LOG, lgT);
+    // few columns, at least two chunks: narrow() (the products are half as many columns)
+    bool narrow_tree = lgT + 1 - CHUNK_LOG >= 1, narrow_pattern = log2k + e + 1 - CHUNK_LOG >= 1, narrow_tree_inv = lgT - CHUNK_LOG >= 1;
+    Decoder* d = nullptr;
+    PatternScan s;
+    hipStream_t s0 = nullptr;
+    PhaseTimer pt = phase_timer();
+
+    // a failure that a fall-back absorbs leaves no message behind
+    void forget_error()
+    {
+        (void)hipGetLastError();
+        if (detail && cap) detail[0] = 0;
+    }
+
+    int run()
+    {
+        if (NC > 0x7FFFFFFFull) return FASTECC_E_UNSUPPORTED;
+        scan();
+        if (s.n_erased() > NC - N) return FASTECC_E_INVAL;  // fewer than k blocks survive
+        pt.mark("pattern scan (host)");
+        int rc = new_pattern();
+        if (rc != FASTECC_OK) return rc;
+        // few losses: a coefficient table, no locator tree and no transform contexts.  Out of memory for its tables is not an error: the transform
+        // path below needs none of them.
+        const bool inner = !s.erased_sub.empty();
+        if (inner || !s.erased.empty()) {
+            rc = inner ? direct(DirectCode{2 * N, s.state_sub, s.erased_sub, true}) : direct(DirectCode{NC, s.state, s.erased, false});
+            if (rc == FASTECC_OK) {
+                d->ready = true;
+                return FASTECC_OK;
             }
-            const int e = (int)erased.size();
-            int pad = 1;
-            while (pad < e) pad <<= 1;
-            const gf61::Elem w = gf61::h_root(NC);
-            // nodes: the data rows and the first |lost data| surviving parity blocks; targets: the lost data rows, then the lost parity blocks
-            using gf61::Elem;
-            const uint64_t Nd = NC / 2;
-            std::vector<uint32_t> Rr, Pl, An;
-            for (uint32_t u : erased) ((u & 1u) ? Pl : Rr).push_back(u >> 1);
-            for (uint64_t q = 0; q < Nd && An.size() < Rr.size(); q++)
-                if (state[2 * q + 1] == ST_HELD) An.push_back((uint32_t)q);
-            if (An.size() != Rr.size()) return FASTECC_E_INVAL;
-            const int ed = (int)Rr.size(), ep = (int)Pl.size();
-            auto sub = [](Elem a, Elem b) { return Elem{gf61::h_subp(a.re, b.re), gf61::h_subp(a.im, b.im)}; };
-            auto neg = [](Elem a) { return Elem{gf61::h_subp(0, a.re), gf61::h_subp(0, a.im)}; };
-            auto mul = [](Elem a, Elem b) { return gf61::h_mul(a, b); };
-            const Elem one{1, 0}, two{2, 0}, kk{Nd % P, 0};
-            std::vector<Elem> z(e), ya(ed), cst(e), nodew((size_t)ed * pad, Elem{0, 0});
-            for (int r = 0; r < ed; r++) z[r] = gf61::h_pow(w, 2ull * Rr[r]), ya[r] = gf61::h_pow(w, 2ull * An[r] + 1);
-            for (int t = 0; t < ep; t++) z[ed + t] = gf61::h_pow(w, 2ull * Pl[t] + 1);
-            auto A_at = [&](Elem x, int skip) { Elem v = one; for (int a = 0; a < ed; a++) if (a != skip) v = mul(v, sub(x, ya[a])); return v; };
-            auto R_at = [&](Elem x, int skip) { Elem v = one; for (int r = 0; r < ed; r++) if (r != skip) v = mul(v, sub(x, z[r])); return v; };
-            for (int r = 0; r < ed; r++) cst[r] = neg(mul(A_at(z[r], -1), gf61::h_inv(mul(z[r], R_at(z[r], r)))));  // C_r = -A(x_r) / (x_r R_r(x_r))
-            for (int t = ed; t < e; t++) cst[t] = neg(mul(mul(two, A_at(z[t], -1)), gf61::h_inv(mul(kk, R_at(z[t], -1)))));  // c_t = -2 A(y_t) / (k R(y_t))
-            for (int a = 0; a < ed; a++) {
-                // parity node a (y_a^k - 1 = -2): target r: k A_a(x_r) R(y_a) / (-2 x_r R_r(x_r) A_a(y_a)); target t: A_a(y_t) R(y_a) / (R(y_t) A_a(y_a))
-                const Elem Rya = R_at(ya[a], -1), Aaya = A_at(ya[a], a);
-                for (int r = 0; r < ed; r++)
-                    nodew[(size_t)a * pad + r] = mul(mul(mul(kk, A_at(z[r], a)), Rya), gf61::h_inv(neg(mul(mul(mul(two, z[r]), R_at(z[r], r)), Aaya))));
-                for (int t = ed; t < e; t++) nodew[(size_t)a * pad + t] = mul(mul(A_at(z[t], a), Rya), gf61::h_inv(mul(R_at(z[t], -1), Aaya)));
+            if (rc != FASTECC_E_NOMEM) return rc;
+            forget_error();
+            d->direct = 0;
+        }
+        // built once; a failure half way leaves no decoder behind (the next call starts from scratch)
+        if (!d->built && (rc = build_once()) != FASTECC_OK) {
+            destroy_decoder(d);
+            *slot = nullptr;
+            return rc;
+        }
+        if ((rc = set_pattern()) != FASTECC_OK) return rc;
+        if (s.split_shift != 0) {
+            // Anything missing — no plan of the needed shape, no memory — leaves the folded 2k-point transform in charge: it decodes the same
+            // pattern (the unused parity blocks are unused there as well).
+            rc = build_split();
+            if (rc == FASTECC_OK) {
+                d->split_shift = s.split_shift;
+                d->split_ready = true;
+            } else {
+                if (rc != FASTECC_E_NOMEM && rc != FASTECC_E_UNSUPPORTED) return rc;
+                forget_error();
+                destroy(d->splitp);
+                d->splitp = nullptr;
+                d->split_unavailable = true;  // (the pattern stays as it is: the folded transform decodes it)
             }
-            std::vector<uint64_t> params(6 * DIRECT_MAX, 0);
-            std::vector<uint32_t> lists(2 * DIRECT_MAX, 0xFFFFFFFFu);  // [0, MAX) output positions (row << 1 | parity), [MAX, 2 MAX) the parity nodes' rows
-            for (int j = 0; j < e; j++) {
-                params[2 * j] = z[j].re, params[2 * j + 1] = z[j].im;
-                params[4 * DIRECT_MAX + 2 * j] = cst[j].re, params[4 * DIRECT_MAX + 2 * j + 1] = cst[j].im;
-                lists[j] = j < ed ? 2u * Rr[j] : 2u * Pl[j - ed] + 1u;
-            }
-            for (int a = 0; a < ed; a++) params[2 * DIRECT_MAX + 2 * a] = ya[a].re, params[2 * DIRECT_MAX + 2 * a + 1] = ya[a].im, lists[DIRECT_MAX + a] = An[a];
-            hipStream_t s0 = nullptr;
-            uint64_t* wp = direct_sub ? d->direct_wpow : d->built ? d->wpow : d->direct_wpow;  // (the inner code's table is its own: w_2k, not w_n)
-            if (!wp) {
-                // the table becomes visible to later calls only once it has been filled
-                uint64_t* fresh = nullptr;
-                D61_TRY(hipMalloc((void**)&fresh, NC * 16));
-                hipLaunchKernelGGL(k_wpow, dim3((unsigned)((NC + 255) / 256)), dim3(256), 0, s0, fresh, w.re, w.im, (uint32_t)NC);
-                hipError_t e1 = hipGetLastError();
-                if (e1 == hipSuccess) e1 = hipStreamSynchronize(s0);
-                if (e1 != hipSuccess) {
-                    (void)hipFree(fresh);
-                    D61_TRY(e1);
-                }
-                d->direct_wpow = wp = fresh;
-            }
-            // [k + ed][pad] weights: sized for this pattern's pad (0.5 GiB instead of 16 GiB at k = 2^24 for one lost block), grown on demand
-            const uint64_t rows = Nd + (uint64_t)ed;
-            const uint64_t coef_elems = (rows + 4) * (uint64_t)pad;  // (k_direct_accumulate fetches the rows of a trip together)
-            if (d->direct_coef_elems < coef_elems) {
-                if (d->direct_coef) (void)hipFree(d->direct_coef);
-                d->direct_coef = nullptr;
-                d->direct_coef_elems = 0;
-                D61_TRY(hipMalloc((void**)&d->direct_coef, coef_elems * COEF_WORDS * 4));
-                d->direct_coef_elems = coef_elems;
-            }
-            if (!d->direct_inv) D61_TRY(hipMalloc((void**)&d->direct_inv, (6 * DIRECT_MAX + 2 * DIRECT_MAX * DIRECT_MAX) * 8));  // the parameters, the nodes' weights
-            if (!d->direct_pos) D61_TRY(hipMalloc((void**)&d->direct_pos, 2 * DIRECT_MAX * 4));
-            const uint64_t chunks = (rows + DIRECT_ROWS - 1) / DIRECT_ROWS;
-            const uint64_t need = (chunks + DIRECT_SEGS) * pad * elems;
-            if (d->direct_partial_elems < need) {
-                if (d->direct_partial) (void)hipFree(d->direct_partial);
-                d->direct_partial = nullptr;
-                d->direct_partial_elems = 0;
-                D61_TRY(hipMalloc((void**)&d->direct_partial, need * 16));
-                d->direct_partial_elems = need;
-            }
-            D61_TRY(hipMemcpyAsync(d->direct_pos, lists.data(), 2 * DIRECT_MAX * 4, hipMemcpyHostToDevice, s0));
-            D61_TRY(hipMemcpyAsync(d->direct_inv, params.data(), 6 * DIRECT_MAX * 8, hipMemcpyHostToDevice, s0));
-            D61_TRY(hipMemsetAsync(d->direct_coef + rows * pad * COEF_WORDS, 0, 4ull * pad * COEF_WORDS * 4, s0));  // (the four spare rows)
-            hipLaunchKernelGGL(k_direct_coef, dim3((unsigned)((Nd + 255) / 256)), dim3(256), 0, s0, d->direct_coef, wp, d->direct_inv, (uint32_t)Nd, ed, ep, pad);
-            if (ed > 0) {
-                D61_TRY(hipMemcpyAsync(d->direct_inv + 6 * DIRECT_MAX, nodew.data(), (size_t)ed * pad * 16, hipMemcpyHostToDevice, s0));
-                hipLaunchKernelGGL(k_direct_pack, dim3((unsigned)((ed * pad + 255) / 256)), dim3(256), 0, s0, d->direct_coef + Nd * pad * COEF_WORDS, d->direct_inv + 6 * DIRECT_MAX,
-                                   (uint32_t)(ed * pad));
-            }
-            D61_TRY(hipGetLastError());
-            D61_TRY(hipStreamSynchronize(s0));
-            d->direct_ed = ed;
-            d->direct_rows = rows;
-            d->direct = e;
-            d->direct_pad = pad;
-            d->direct_nc = NC;
-            return FASTECC_OK;
-        }();
-        if (rc_direct == FASTECC_OK) {
+        }
+        if (s.erased_data == 0 && s.erased_parity == 0) {
+            HIP_TRY(hipStreamSynchronize(s0));
             d->ready = true;
             return FASTECC_OK;
         }
-        if (rc_direct != FASTECC_E_NOMEM) return rc_direct;
-        (void)hipGetLastError();
-        d->direct = 0;
+        pt.mark("set-up, uploads");
+        uint64_t* coeffs = nullptr;
+        if ((rc = locator_tree(&coeffs)) != FASTECC_OK || (rc = locator_tables(coeffs)) != FASTECC_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(s0));
+        pt.mark("this pattern (device)");
+        d->ready = true;
+        return FASTECC_OK;
     }
-    // ---- built once; a failure half way leaves no decoder behind (the next call starts from scratch) ----
-    auto build_once = [&]() -> int {
-        PhaseTimer pt;
+
+    // ---- the pattern on the host: no HIP call ----
+    void scan()
+    {
+        s.state.assign(NC, ST_LOST);
+        s.srcmap.assign(e > 1 ? NC : 0, 0);
+        s.parity_lost.assign(e > 1 ? M : 0, 0);
+        if (e == 1) {  // data block i at 2i, parity block j at 2j + 1: one interleaving pass
+            for (uint64_t i = 0; i < N; i++) {
+                const uint8_t a = data_present[i] != 0, b = parity_present[i] != 0;
+                s.state[2 * i] = a ? ST_HELD : ST_LOST;
+                s.state[2 * i + 1] = b ? ST_HELD : ST_LOST;
+                s.erased_data += !a;
+                s.erased_parity += !b;
+            }
+        } else {
+            for (uint64_t i = 0; i < N; i++) {
+                s.state[i << e] = data_present[i] ? ST_HELD : ST_LOST;
+                s.erased_data += !data_present[i];
+                s.srcmap[i << e] = (uint32_t)i;
+            }
+            for (uint64_t q = 0; q < M; q++) {
+                // parity block q = block j of coset t: generator w_(2^jt k)^c, jt = floor(log2(t + 1)) + 1, c the (t + 2 - 2^(jt-1))-th odd number (include/fastecc.h)
+                const uint64_t t = q >> log2k, j = q & (N - 1);
+                int jt = 1;
+                while ((1ull << jt) - 1 <= t) jt++;
+                const uint64_t c = 2 * (t + 1 - (1ull << (jt - 1))) + 1;
+                const uint64_t u = (c << (e - jt)) + (j << e);
+                s.state[u] = parity_present[q] ? ST_HELD : ST_LOST;
+                s.erased_parity += !parity_present[q];
+                s.srcmap[u] = (uint32_t)q | 0x80000000u;
+                s.parity_lost[q] = !parity_present[q];
+            }
+        }
+        const uint64_t lost = s.erased_data + s.erased_parity;
+        // even / odd split: recovering the lost data blocks takes as many parity blocks, so the others may count as erased too; take them at multiples
+        // of 2^h of the parity half (largest h <= 5 that leaves enough survivors) and the parity half's transform shrinks to k >> h rows
+        const bool few = lost != 0 && (int)lost <= std::min(direct_max, DECODE_DIRECT_MAX);
+        if (split && log2k >= 11 && s.erased_data != 0 && !few && !(*slot && (*slot)->split_unavailable)) {
+            // (a pattern that has lost parity blocks too may be REPAIRED: the split then runs a second MID + DIT chain for the odd positions — or, without
+            //  the memory for its extra stripe, re-encodes — see StripeDecode)
+            for (int h = 5; h >= 1 && s.split_shift == 0; h--) {  // (light patterns stop at h = 5: k / 32 flags read)
+                uint64_t held = 0;
+                for (uint64_t j = 0; j < N; j += 1ull << h) held += parity_present[j] != 0;
+                if (held >= s.erased_data) {
+                    s.split_shift = h;
+                    s.unused_held = (N - s.erased_parity) - held;  // marked on the device (k_mark_unused): the host's `state` stays the caller's
+                }
+            }
+        }
+        // the positions themselves are listed on the device (k_erased_list); the host needs their number, and the list itself only for the few-loss path
+        if (s.n_erased() != 0 && (int64_t)s.n_erased() <= std::min(direct_max, DECODE_DIRECT_MAX))
+            for (uint64_t u = 0; u < NC; u++)
+                if (s.state[u] == ST_LOST) s.erased.push_back((uint32_t)u);
+        // n = 4k / 8k, few losses: the data and the FIRST coset are a (2k,k) code of their own, and that code's direct path rebuilds the data from
+        // its 2k - few survivors — a read of 2k blocks instead of a transform over n; lost parity blocks of the other cosets are re-encoded
+        // (fastecc_repair)
+        const int64_t limit = std::min(direct_max_user, DECODE_DIRECT_MAX);
+        if (e > 1 && s.erased_data != 0 && (int64_t)s.erased_data <= limit) {
+            uint64_t lost0 = 0;
+            for (uint64_t j = 0; j < N; j++) lost0 += !parity_present[j];
+            if ((int64_t)(s.erased_data + lost0) <= limit && s.erased_data + lost0 <= N) {  // (k of the inner code's 2k blocks survive)
+                s.state_sub.resize(2 * N);
+                for (uint64_t i = 0; i < N; i++) {
+                    s.state_sub[2 * i] = data_present[i] ? ST_HELD : ST_LOST;
+                    s.state_sub[2 * i + 1] = parity_present[i] ? ST_HELD : ST_LOST;
+                }
+                for (uint64_t u = 0; u < 2 * N; u++)
+                    if (s.state_sub[u] == ST_LOST) s.erased_sub.push_back((uint32_t)u);
+            }
+        }
+    }
+
+    // the slot's decoder, the previous pattern dropped
+    int new_pattern()
+    {
+        if (!*slot) {
+            *slot = new (std::nothrow) Decoder();
+            if (!*slot) return FASTECC_E_NOMEM;
+        }
+        d = *slot;
+        d->ready = false;
+        d->log2k = log2k;
+        d->N = N;
+        d->NC = NC;
+        d->elems = elems;
+        d->erased_data = s.erased_data;
+        d->erased_parity = s.erased_parity;
+        if (s.erased_parity == 0) {
+            // fastecc_repair's re-encode stripes (n - k and, for n = 4k / 8k, k more blocks: up to 32 + 8 GiB at 2^17 x 64 KB) are only held while the
+            // pattern has lost parity blocks; the caller has waited for the last call that used them
+            for (uint64_t** b : {&d->again, &d->cos_work}) {
+                if (*b) (void)hipFree(*b);
+                *b = nullptr;
+            }
+        }
+        d->split_ready = false;
+        d->split_repair_ready = false;
+        d->split_shift = 0;
+        d->e = e;
+        d->M = M;
+        d->direct = 0;
+        return FASTECC_OK;
+    }
+
+    // e > 1: the caller's lost parity blocks by number and the cosets that have one (what fastecc_repair re-encodes)
+    int upload_parity_flags()
+    {
+        if (!d->parity_lost) HIP_TRY(hipMalloc((void**)&d->parity_lost, M));
+        HIP_TRY(hipMemcpyAsync(d->parity_lost, s.parity_lost.data(), M, hipMemcpyHostToDevice, nullptr));
+        d->lost_coset_mask = 0;
+        for (uint64_t q = 0; q < M; q++)
+            if (s.parity_lost[q]) d->lost_coset_mask |= 1u << (q / N);
+        return FASTECC_OK;
+    }
+
+    // ---- few losses: every lost block of `code` is a fixed linear combination of its k data rows and as many surviving parity blocks ----
+    int direct(const DirectCode& code)
+    {
+        if (code.inner) {
+            const int rc = upload_parity_flags();
+            if (rc != FASTECC_OK) return rc;
+        }
+        DirectWeights w;
+        if (!direct_weights(code, w)) return FASTECC_E_INVAL;
+        const uint64_t Nd = code.NC / 2;
+        uint64_t* wp = code.inner ? d->direct_wpow : d->built ? d->wpow : d->direct_wpow;
+        if (!wp) {
+            // the table becomes visible to later calls only once it has been filled
+            const Elem root = gf61::h_root(code.NC);
+            uint64_t* fresh = nullptr;
+            HIP_TRY(hipMalloc((void**)&fresh, code.NC * 16));
+            hipLaunchKernelGGL(k_wpow, grid_of(code.NC), dim3(256), 0, s0, fresh, root.re, root.im, (uint32_t)code.NC);
+            hipError_t filled = hipGetLastError();
+            if (filled == hipSuccess) filled = hipStreamSynchronize(s0);
+            if (filled != hipSuccess) {
+                (void)hipFree(fresh);
+                return hip_fail(filled, "k_wpow");
+            }
+            d->direct_wpow = wp = fresh;
+        }
+        // [k + ed][pad] weights: sized for this pattern's pad (0.5 GiB instead of 16 GiB at k = 2^24 for one lost block), grown on demand
+        const uint64_t rows = Nd + (uint64_t)w.ed;
+        const uint64_t chunks = (rows + DIRECT_ROWS - 1) / DIRECT_ROWS;
+        HIP_TRY(grow(&d->direct_coef, &d->direct_coef_elems, (rows + 4) * (uint64_t)w.pad, COEF_WORDS * 4));  // (k_direct_accumulate fetches the rows of a trip together)
+        if (!d->direct_inv) HIP_TRY(hipMalloc((void**)&d->direct_inv, (6 * DIRECT_MAX + 2 * DIRECT_MAX * DIRECT_MAX) * 8));  // the parameters, the nodes' weights
+        if (!d->direct_pos) HIP_TRY(hipMalloc((void**)&d->direct_pos, 2 * DIRECT_MAX * 4));
+        HIP_TRY(grow(&d->direct_partial, &d->direct_partial_elems, (chunks + DIRECT_SEGS) * w.pad * elems, 16));
+        HIP_TRY(hipMemcpyAsync(d->direct_pos, w.lists.data(), 2 * DIRECT_MAX * 4, hipMemcpyHostToDevice, s0));
+        HIP_TRY(hipMemcpyAsync(d->direct_inv, w.params.data(), 6 * DIRECT_MAX * 8, hipMemcpyHostToDevice, s0));
+        HIP_TRY(hipMemsetAsync(d->direct_coef + rows * w.pad * COEF_WORDS, 0, 4ull * w.pad * COEF_WORDS * 4, s0));  // (the four spare rows)
+        hipLaunchKernelGGL(k_direct_coef, grid_of(Nd), dim3(256), 0, s0, d->direct_coef, wp, d->direct_inv, (uint32_t)Nd, w.ed, w.ep, w.pad);
+        if (w.ed > 0) {
+            HIP_TRY(hipMemcpyAsync(d->direct_inv + 6 * DIRECT_MAX, w.nodew.data(), (size_t)w.ed * w.pad * 16, hipMemcpyHostToDevice, s0));
+            hipLaunchKernelGGL(k_direct_pack, grid_of(w.ed * w.pad), dim3(256), 0, s0, d->direct_coef + Nd * w.pad * COEF_WORDS, d->direct_inv + 6 * DIRECT_MAX,
+                               (uint32_t)(w.ed * w.pad));
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s0));
+        d->direct_ed = w.ed;
+        d->direct_rows = rows;
+        d->direct = w.ed + w.ep;
+        d->direct_pad = w.pad;
+        d->direct_nc = code.NC;
+        return FASTECC_OK;
+    }
+
+    // ---- the transform path: the paths, the buffers and the w^u table ----
+    int build_once()
+    {
+        PhaseTimer ptb = phase_timer();
         // only the even (data) positions of this transform are wanted: a 7-level MID here pairs with the 6-level MID of a size-k path,
         // whose DIT passes finish the folded transform (encode_fold); where no such pair of plans exists all 2k outputs are computed
         // (n = 4k: every FOURTH position — the size-4k transform's 7-level MID pairs with the 5-level MID of a size-k path; n = 8k: every fourth
         //  position as well, with a size-2k path: 2k outputs instead of 8k, the data at the even ones)
         int rc = create_transform_mid(&d->transform, log2k + e, elems, FACTOR_INDEX, 7, detail, cap);
-        pt.mark("transform path");
+        ptb.mark("transform path");
         if (rc == FASTECC_OK && log2k >= 6) rc = create_transform_mid(&d->half, e == 3 ? log2k + 1 : log2k, elems, FACTOR_ENCODE, e == 1 ? 6 : 5, detail, cap);
         if (rc == FASTECC_OK && e >= 2 && !(fold_caps(d->transform, d->half) & FOLD_PAIRS)) {
             // the two plans do not pair up at this size: the transform keeps its own choice of MID and computes all n outputs
@@ -1061,10 +1129,10 @@ int decode_prepare(Decoder** slot, int log2k, uint64_t elems, const uint8_t* dat
             d->half = nullptr;
             rc = create_transform_mid(&d->transform, log2k + e, elems, FACTOR_INDEX, 0, detail, cap);
         }
-        pt.mark("half path");
+        ptb.mark("half path");
         // (of these paths only the stand-alone transform is used; few columns: the upper row bits by a path of CHUNK columns, the rest by k_chunk_dif)
         if (rc == FASTECC_OK) rc = narrow_pattern ? create(&d->narrow_pattern, log2k + e + 1 - CHUNK_LOG, CHUNK, detail, cap) : create(&d->pattern, log2k + e, 2, detail, cap);
-        pt.mark("pattern path");
+        ptb.mark("pattern path");
         if (rc != FASTECC_OK) return rc;
         d->tree.assign(lgT, nullptr);
         d->tree_inv.assign(lgT, nullptr);
@@ -1079,104 +1147,72 @@ int decode_prepare(Decoder** slot, int log2k, uint64_t elems, const uint8_t* dat
             if (rc == FASTECC_OK && narrow_tree_inv) rc = create(&d->narrow_tree_inv, lgT - CHUNK_LOG, CHUNK, detail, cap);
             if (rc != FASTECC_OK) return rc;
         }
-        pt.mark("tree paths");
+        ptb.mark("tree paths");
         d->T = T;
-        D61_TRY(hipMalloc((void**)&d->tree_x, 2 * T * 16));
-        D61_TRY(hipMalloc((void**)&d->tree_y, 2 * T * 16));
-        D61_TRY(hipMalloc((void**)&d->tree_f, 2 * T * 16));
-        D61_TRY(hipMalloc((void**)&d->wpow, NC * 16));
-        D61_TRY(hipMalloc((void**)&d->roots, T * 16));
-        D61_TRY(hipMalloc((void**)&d->lv, NC * 32));
-        D61_TRY(hipMalloc((void**)&d->fin, NC * 16));
-        D61_TRY(hipMalloc((void**)&d->gout, N * 16));
-        D61_TRY(hipMalloc((void**)&d->erased, (T + 1) * 4));  // the list and its counter
-        D61_TRY(hipMalloc((void**)&d->state, NC));
-        if (e > 1) {
-            D61_TRY(hipMalloc((void**)&d->srcmap, NC * 4));
-        }
-        const gf61::Elem w = gf61::h_root(NC);
-        hipLaunchKernelGGL(k_wpow, dim3((unsigned)((NC + 255) / 256)), dim3(256), 0, nullptr, d->wpow, w.re, w.im, (uint32_t)NC);
-        D61_TRY(hipGetLastError());
+        HIP_TRY(hipMalloc((void**)&d->tree_x, 2 * T * 16));
+        HIP_TRY(hipMalloc((void**)&d->tree_y, 2 * T * 16));
+        HIP_TRY(hipMalloc((void**)&d->tree_f, 2 * T * 16));
+        HIP_TRY(hipMalloc((void**)&d->wpow, NC * 16));
+        HIP_TRY(hipMalloc((void**)&d->roots, T * 16));
+        HIP_TRY(hipMalloc((void**)&d->lv, NC * 32));
+        HIP_TRY(hipMalloc((void**)&d->fin, NC * 16));
+        HIP_TRY(hipMalloc((void**)&d->gout, N * 16));
+        HIP_TRY(hipMalloc((void**)&d->erased, (T + 1) * 4));  // the list and its counter
+        HIP_TRY(hipMalloc((void**)&d->state, NC));
+        if (e > 1) HIP_TRY(hipMalloc((void**)&d->srcmap, NC * 4));
+        const Elem w = gf61::h_root(NC);
+        hipLaunchKernelGGL(k_wpow, grid_of(NC), dim3(256), 0, nullptr, d->wpow, w.re, w.im, (uint32_t)NC);
+        HIP_TRY(hipGetLastError());
         d->built = true;
-        pt.mark("buffers, w^u");
-        return FASTECC_OK;
-    };
-    if (!d->built) {
-        const int rc = build_once();
-        if (rc != FASTECC_OK) {
-            destroy_decoder(d);
-            *slot = nullptr;
-            return rc;
-        }
-    }
-    hipStream_t s0 = nullptr;
-    // (the caller has waited for the last decode that used the previous pattern)
-    D61_TRY(hipMemcpyAsync(d->state, state.data(), NC, hipMemcpyHostToDevice, s0));
-    if (!d->state_real) D61_TRY(hipMalloc((void**)&d->state_real, NC));
-    D61_TRY(hipMemcpyAsync(d->state_real, d->state, NC, hipMemcpyDeviceToDevice, s0));
-    if (split_shift != 0) {
-        hipLaunchKernelGGL(k_mark_unused, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s0, d->state, (uint32_t)N, (1u << split_shift) - 1u);
-        D61_TRY(hipGetLastError());
-    }
-    if (e > 1) {
-        D61_TRY(hipMemcpyAsync(d->srcmap, srcmap.data(), NC * 4, hipMemcpyHostToDevice, s0));  // (fixed per code; cheap next to the locator)
-        const int rc = upload_parity_flags();
-        if (rc != FASTECC_OK) return rc;
-    }
-    if (split_shift != 0) {
-        // the split transform's paths and tables (once; the small transform per shift).  Anything missing — no plan of the needed shape, no memory
-        // — leaves the folded 2k-point transform in charge: it decodes the same pattern (the unused parity blocks are unused there as well).
-        const int rc_split = [&]() -> int {
-            if (!d->splitp) {
-                int rc = FASTECC_E_UNSUPPORTED;
-                for (int mid : {5, 6, 0}) {  // MID with the addend is leanest at 5 or 6 levels (78 VGPRs; the 7-level one spills)
-                    if (d->splitp) destroy(d->splitp);
-                    d->splitp = nullptr;
-                    rc = create_transform_mid(&d->splitp, log2k, elems, FACTOR_SPLIT, mid, detail, cap);
-                    if (rc != FASTECC_OK) return rc;
-                    if (split_decode_supported(d->splitp)) break;
-                }
-                if (!split_decode_supported(d->splitp)) return FASTECC_E_UNSUPPORTED;
-            }
-            if (!d->split_af) {
-                D61_TRY(hipMalloc((void**)&d->split_af, N * 16));
-                const int rc = split_addend_factors(d->split_af, log2k, s0);
-                if (rc != FASTECC_OK) return rc;
-            }
-            if (!d->split_work) D61_TRY(hipMalloc((void**)&d->split_work, N * elems * 16));
-            if (d->small_rows < (N >> split_shift)) {
-                if (d->small_buf) (void)hipFree(d->small_buf);
-                d->small_buf = nullptr;
-                d->small_rows = 0;
-                D61_TRY(hipMalloc((void**)&d->small_buf, (N >> split_shift) * elems * 16));
-                d->small_rows = N >> split_shift;
-            }
-            if (!d->small[split_shift]) {
-                const int rc = create(&d->small[split_shift], log2k - split_shift, elems, detail, cap);  // only its stand-alone transform's DIF passes are used
-                if (rc != FASTECC_OK) return rc;
-            }
-            return FASTECC_OK;
-        }();
-        if (rc_split != FASTECC_OK) {
-            (void)hipGetLastError();
-            if (rc_split != FASTECC_E_NOMEM && rc_split != FASTECC_E_UNSUPPORTED) return rc_split;
-            destroy(d->splitp);
-            d->splitp = nullptr;
-            d->split_unavailable = true;  // (the pattern stays as it is: the folded transform decodes it)
-        } else {
-            d->split_shift = split_shift;
-            d->split_ready = true;
-        }
-    }
-    if (erased_data == 0 && erased_parity == 0) {
-        D61_TRY(hipStreamSynchronize(s0));
-        d->ready = true;
+        ptb.mark("buffers, w^u");
         return FASTECC_OK;
     }
-    pt_call.mark("set-up, uploads");
-    auto grid = [](uint64_t items) { return dim3((unsigned)((items + 255) / 256)); };
+
+    // this pattern's state on the device (the caller has waited for the last decode that used the previous pattern)
+    int set_pattern()
+    {
+        HIP_TRY(hipMemcpyAsync(d->state, s.state.data(), NC, hipMemcpyHostToDevice, s0));
+        if (!d->state_real) HIP_TRY(hipMalloc((void**)&d->state_real, NC));
+        HIP_TRY(hipMemcpyAsync(d->state_real, d->state, NC, hipMemcpyDeviceToDevice, s0));
+        if (s.split_shift != 0) {
+            hipLaunchKernelGGL(k_mark_unused, grid_of(N), dim3(256), 0, s0, d->state, (uint32_t)N, (1u << s.split_shift) - 1u);
+            HIP_TRY(hipGetLastError());
+        }
+        if (e > 1) {
+            HIP_TRY(hipMemcpyAsync(d->srcmap, s.srcmap.data(), NC * 4, hipMemcpyHostToDevice, s0));  // (fixed per code; cheap next to the locator)
+            return upload_parity_flags();
+        }
+        return FASTECC_OK;
+    }
+
+    // the split transform's paths and tables (once; the small transform per shift)
+    int build_split()
+    {
+        const int h = s.split_shift;
+        if (!d->splitp) {
+            for (int mid : {5, 6, 0}) {  // MID with the addend is leanest at 5 or 6 levels (78 VGPRs; the 7-level one spills)
+                if (d->splitp) destroy(d->splitp);
+                d->splitp = nullptr;
+                const int rc = create_transform_mid(&d->splitp, log2k, elems, FACTOR_SPLIT, mid, detail, cap);
+                if (rc != FASTECC_OK) return rc;
+                if (split_decode_supported(d->splitp)) break;
+            }
+            if (!split_decode_supported(d->splitp)) return FASTECC_E_UNSUPPORTED;
+        }
+        if (!d->split_af) {
+            HIP_TRY(hipMalloc((void**)&d->split_af, N * 16));
+            const int rc = split_addend_factors(d->split_af, log2k, s0);
+            if (rc != FASTECC_OK) return rc;
+        }
+        if (!d->split_work) HIP_TRY(hipMalloc((void**)&d->split_work, N * elems * 16));
+        HIP_TRY(grow(&d->small_buf, &d->small_rows, N >> h, elems * 16));
+        if (!d->small[h]) return create(&d->small[h], log2k - h, elems, detail, cap);  // only its stand-alone transform's DIF passes are used
+        return FASTECC_OK;
+    }
+
     // a transform of 2^log_rows rows of 2^logE columns (2^log_rows <= NC): the upper row bits by `top`, a path of CHUNK columns, the rest inside LDS
-    auto narrow = [&](Path* top, int log_rows, int logE, const uint64_t* in, uint64_t* out, bool inverse) -> int {
+    int narrow(Path* top, int log_rows, int logE, const uint64_t* in, uint64_t* out, bool inverse)
+    {
         const int rc = in == out ? dif_only(top, out, inverse, s0, nullptr) : dif_only_to(top, in, out, inverse, s0, nullptr);
         if (rc != FASTECC_OK) return rc;
         const int logN1 = log_rows + logE - CHUNK_LOG;
@@ -1184,126 +1220,136 @@ int decode_prepare(Decoder** slot, int log2k, uint64_t elems, const uint8_t* dat
         hipLaunchKernelGGL(inverse ? k_chunk_dif<true> : k_chunk_dif<false>, dim3(1u << logN1), dim3(256), 0, s0, out, d->wpow, logE, logN1, step_n, step_n2,
                            (uint32_t)(NC - 1));
         const hipError_t launched = hipGetLastError();
-        return launched == hipSuccess ? FASTECC_OK : fail(detail, cap, launched, "k_chunk_dif");
-    };
-    D61_TRY(hipMemsetAsync(d->erased + T, 0, 4, s0));
-    hipLaunchKernelGGL(k_erased_list, grid((NC + 15) / 16), dim3(256), 0, s0, d->state, (uint32_t)NC, d->erased, d->erased + T);
-    hipLaunchKernelGGL(k_roots, grid(T), dim3(256), 0, s0, d->roots, d->erased, d->wpow, (uint32_t)n_erased, (uint32_t)T);
-    D61_TRY(hipMemsetAsync(d->tree_x, 0, 2 * T * 16, s0));
-    if (leaf_log == TREE_LOW) hipLaunchKernelGGL(k_tree_low<TREE_LOW>, dim3((unsigned)(T >> leaf_log)), dim3(1 << TREE_LOW), 0, s0, d->roots, d->tree_x, (uint32_t)(T >> leaf_log));
-    else hipLaunchKernelGGL(k_leaves, dim3((unsigned)(((T >> leaf_log) + 63) / 64)), dim3(64), 0, s0, d->roots, d->tree_x, (uint32_t)leaf, (uint32_t)(T >> leaf_log));
-    D61_TRY(hipGetLastError());
-    // three 2T-element buffers change roles level by level: a = this level's polynomials [2 deg][m] (rows deg.. zero),
-    // b = their transforms and then the next level's polynomials, c = the pairwise products
-    uint64_t *a = d->tree_x, *b = d->tree_f, *c = d->tree_y;
-    for (int k = leaf_log; k < lgT; k++) {
-        const uint64_t deg = 1ull << k, m = T >> k;
-        const bool few = d->tree[k] == nullptr;  // few columns: narrow()
-        int rc = few ? narrow(d->narrow_tree, k + 1, lgT - k, a, b, false)
-                     : dif_only_to(d->tree[k], a, b, false, s0, nullptr);  // all m polynomials at once, a -> b (a survives for the combine step); no reordering pass
-        if (rc != FASTECC_OK) return rc;
-        const gf61::Elem scale = gf61::h_inv(gf61::Elem{(2 * deg) % P, 0});
-        hipLaunchKernelGGL(k_pairs, grid(deg * m), dim3(256), 0, s0, b, c, (uint32_t)m, deg * m, scale.re, scale.im, k + 1);
-        D61_TRY(hipGetLastError());
-        rc = d->tree_inv[k] == nullptr ? narrow(d->narrow_tree_inv, k + 1, lgT - k - 1, c, c, true) : dif_only(d->tree_inv[k], c, true, s0, nullptr);  // the m/2 products, left in bit-reversed row order
-        if (rc != FASTECC_OK) return rc;
-        const bool top = k + 1 == lgT;
-        const uint64_t rows = top ? 2 * deg : 4 * deg;
-        hipLaunchKernelGGL(k_combine, grid(rows * (m / 2)), dim3(256), 0, s0, c, a, b, (uint32_t)deg, (uint32_t)m, rows * (m / 2), top, k + 1);
-        D61_TRY(hipGetLastError());
-        std::swap(a, b);
+        return launched == hipSuccess ? FASTECC_OK : hip_fail(launched, "k_chunk_dif");
     }
-    uint64_t* x = a;  // the T lower coefficients of L = x^pad l
-    hipLaunchKernelGGL(k_locator_columns, grid(NC), dim3(256), 0, s0, x, d->lv, (uint32_t)T, (uint32_t)NC);
-    D61_TRY(hipGetLastError());
+
+    // the locator l = prod (x - w^u) over the lost positions by a product tree; *coeffs: the T lower coefficients of L = x^pad l
+    int locator_tree(uint64_t** coeffs)
     {
+        HIP_TRY(hipMemsetAsync(d->erased + T, 0, 4, s0));
+        hipLaunchKernelGGL(k_erased_list, grid_of((NC + 15) / 16), dim3(256), 0, s0, d->state, (uint32_t)NC, d->erased, d->erased + T);
+        hipLaunchKernelGGL(k_roots, grid_of(T), dim3(256), 0, s0, d->roots, d->erased, d->wpow, (uint32_t)s.n_erased(), (uint32_t)T);
+        HIP_TRY(hipMemsetAsync(d->tree_x, 0, 2 * T * 16, s0));
+        if (leaf_log == TREE_LOW) hipLaunchKernelGGL(k_tree_low<TREE_LOW>, dim3((unsigned)(T >> leaf_log)), dim3(1 << TREE_LOW), 0, s0, d->roots, d->tree_x, (uint32_t)(T >> leaf_log));
+        else hipLaunchKernelGGL(k_leaves, dim3((unsigned)(((T >> leaf_log) + 63) / 64)), dim3(64), 0, s0, d->roots, d->tree_x, 1u << leaf_log, (uint32_t)(T >> leaf_log));
+        HIP_TRY(hipGetLastError());
+        // three 2T-element buffers change roles level by level: a = this level's polynomials [2 deg][m] (rows deg.. zero),
+        // b = their transforms and then the next level's polynomials, c = the pairwise products
+        uint64_t *a = d->tree_x, *b = d->tree_f, *c = d->tree_y;
+        for (int k = leaf_log; k < lgT; k++) {
+            const uint64_t deg = 1ull << k, m = T >> k;
+            const bool few = d->tree[k] == nullptr;  // few columns: narrow()
+            int rc = few ? narrow(d->narrow_tree, k + 1, lgT - k, a, b, false)
+                         : dif_only_to(d->tree[k], a, b, false, s0, nullptr);  // all m polynomials at once, a -> b (a survives for the combine step); no reordering pass
+            if (rc != FASTECC_OK) return rc;
+            const Elem scale = gf61::h_inv(Elem{(2 * deg) % P, 0});
+            hipLaunchKernelGGL(k_pairs, grid_of(deg * m), dim3(256), 0, s0, b, c, (uint32_t)m, deg * m, scale.re, scale.im, k + 1);
+            HIP_TRY(hipGetLastError());
+            rc = d->tree_inv[k] == nullptr ? narrow(d->narrow_tree_inv, k + 1, lgT - k - 1, c, c, true) : dif_only(d->tree_inv[k], c, true, s0, nullptr);  // the m/2 products, left in bit-reversed row order
+            if (rc != FASTECC_OK) return rc;
+            const bool top = k + 1 == lgT;
+            const uint64_t rows = top ? 2 * deg : 4 * deg;
+            hipLaunchKernelGGL(k_combine, grid_of(rows * (m / 2)), dim3(256), 0, s0, c, a, b, (uint32_t)deg, (uint32_t)m, rows * (m / 2), top, k + 1);
+            HIP_TRY(hipGetLastError());
+            std::swap(a, b);
+        }
+        *coeffs = a;
+        return FASTECC_OK;
+    }
+
+    // the values of L and x L' on the points, and from them fin, gout and the repair's tables
+    int locator_tables(const uint64_t* coeffs)
+    {
+        const uint64_t n_erased = s.n_erased();
+        hipLaunchKernelGGL(k_locator_columns, grid_of(NC), dim3(256), 0, s0, coeffs, d->lv, (uint32_t)T, (uint32_t)NC);
+        HIP_TRY(hipGetLastError());
         const int rc = d->narrow_pattern ? narrow(d->narrow_pattern, log2k + e, 1, d->lv, d->lv, false)
                                          : dif_only(d->pattern, d->lv, false, s0, nullptr);  // (k_finish reads the values where the DIF passes leave them)
         if (rc != FASTECC_OK) return rc;
-    }
-    d->gout_all_valid = false;
-    if (erased_data != 0 && erased_parity != 0 && e == 1) {  // fastecc_repair can then rebuild everything in one transform (no memory for the table: decode + encode)
-        // (with the split the locator counts the unused parity blocks as lost: the table then only feeds gout_par below)
-        if (!d->gout_all && hipMalloc((void**)&d->gout_all, NC * 16) != hipSuccess) {
-            (void)hipGetLastError();
-            d->gout_all = nullptr;
-        }
-        d->gout_all_valid = d->gout_all != nullptr;
-    }
-    hipLaunchKernelGGL(k_finish, grid(NC), dim3(256), 0, s0, d->lv, d->state, d->wpow, d->fin, d->gout, (uint32_t)NC, (uint32_t)(T - n_erased),
-                       d->gout_all_valid ? d->gout_all : nullptr, e, log2k + e);
-    // the inversions: one per position the CALLER lost.  The split's list also holds the parity blocks it leaves aside (their factors are never
-    // read: k_gout_par takes those of state_real's lost blocks), so its pattern gets a list of its own, in a tree buffer (all three are free by now)
-    const uint32_t* lost_list = d->erased;
-    uint64_t lost_count = n_erased;
-    if (split_shift != 0) {
-        uint32_t* scratch = reinterpret_cast<uint32_t*>(d->tree_y);  // NC positions and the counter: 4 (NC + 1) <= 32 T bytes
-        D61_TRY(hipMemsetAsync(scratch + NC, 0, 4, s0));
-        hipLaunchKernelGGL(k_erased_list, grid((NC + 15) / 16), dim3(256), 0, s0, d->state_real, (uint32_t)NC, scratch, scratch + NC);
-        lost_list = scratch;
-        lost_count = erased_data + erased_parity;
-    }
-    hipLaunchKernelGGL(k_finish_lost, grid(lost_count), dim3(256), 0, s0, d->lv, lost_list, (uint32_t)lost_count, d->wpow, d->gout, (uint32_t)NC,
-                       (uint32_t)(T - n_erased), d->gout_all_valid ? d->gout_all : nullptr, e, log2k + e);
-    D61_TRY(hipGetLastError());
-    if (d->split_ready && d->gout_all_valid) {
-        // the second chain's tables: the factor of q~ by position (once) and the lost parity blocks' output factors (this pattern)
-        const hipError_t e1 = d->split_pos_odd ? hipSuccess : hipMalloc((void**)&d->split_pos_odd, N * 16);
-        const hipError_t e2 = e1 != hipSuccess ? e1 : d->gout_par ? hipSuccess : hipMalloc((void**)&d->gout_par, N * 16);
-        if (e2 == hipSuccess) {
-            if (!d->split_pos_odd_built) {
-                const int rc = split_addend_factors(d->split_pos_odd, log2k, s0, true);
-                if (rc != FASTECC_OK) return rc;
-                d->split_pos_odd_built = true;
+        d->gout_all_valid = false;
+        if (s.erased_data != 0 && s.erased_parity != 0 && e == 1) {  // fastecc_repair can then rebuild everything in one transform (no memory for the table: decode + encode)
+            // (with the split the locator counts the unused parity blocks as lost: the table then only feeds gout_par below)
+            if (!d->gout_all && hipMalloc((void**)&d->gout_all, NC * 16) != hipSuccess) {
+                (void)hipGetLastError();
+                d->gout_all = nullptr;
             }
-            hipLaunchKernelGGL(k_gout_par, grid(N), dim3(256), 0, s0, d->gout_all, d->state_real, d->gout_par, (uint32_t)N);
-            D61_TRY(hipGetLastError());
-            d->split_repair_ready = true;
-        } else {
-            (void)hipGetLastError();  // no memory for the tables: the split decodes, the lost parity is re-encoded
+            d->gout_all_valid = d->gout_all != nullptr;
         }
-    }
-    // (the one-transform repair is the unsplit pattern's.  Also when the split's paths or buffers could NOT be built: the locator's state then still
-    //  counts the unused parity blocks as lost, so gout_all is non-zero there and that repair would rewrite up to k (1 - 2^-h) parity blocks the
-    //  caller holds — decode + re-encode restores only what state_real says is lost)
-    if (d->split_ready || split_shift != 0) d->gout_all_valid = false;
-    D61_TRY(hipStreamSynchronize(s0));
-    pt_call.mark("this pattern (device)");
-    d->ready = true;
-    return FASTECC_OK;
-}
-
-int decode(Decoder* d, uint64_t* data, uint64_t* parity, Path* rebuild_with, hipStream_t s0, const LaunchHooks* hooks)
-{
-    if (!d || !d->ready) return FASTECC_E_INVAL;
-    char* detail = nullptr;
-    const size_t cap = 0;
-    const uint32_t elems = (uint32_t)d->elems, col_chunks = (elems + 63) / 64;
-    const bool rebuild = rebuild_with != nullptr && d->erased_parity != 0;
-    // n = 4k / 8k: the lost parity blocks from the encoder again, on the repaired data; only the cosets with a lost block, only the lost ones written
-    auto rebuild_cosets = [&](uint32_t coset_mask, bool first_coset_done) -> int {
-        if (cosets_of(rebuild_with) != (1 << d->e) - 1) return FASTECC_E_INVAL;
-        if (!d->again) D61_TRY(hipMalloc((void**)&d->again, d->M * d->elems * 16));
-        if (encode_cosets_needs_work(rebuild_with) && !d->cos_work) D61_TRY(hipMalloc((void**)&d->cos_work, d->N * d->elems * 16));
-        const int rc = encode_cosets(rebuild_with, data, d->again, d->cos_work, s0, hooks, coset_mask);
-        if (rc != FASTECC_OK) return rc;
-        // (after the inner code's direct path the first coset's blocks are in place and `again` holds nothing for them)
-        const uint64_t skip = first_coset_done ? d->N : 0, items = (d->M - skip) * col_chunks;
-        hipLaunchKernelGGL(k_restore_map, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s0, d->again + 2 * skip * elems, parity + 2 * skip * elems,
-                           d->parity_lost + skip, elems, col_chunks, items);
-        D61_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_finish, grid_of(NC), dim3(256), 0, s0, d->lv, d->state, d->wpow, d->fin, d->gout, (uint32_t)NC, (uint32_t)(T - n_erased),
+                           d->gout_all_valid ? d->gout_all : nullptr, e, log2k + e);
+        // the inversions: one per position the CALLER lost.  The split's list also holds the parity blocks it leaves aside (their factors are never
+        // read: k_gout_par takes those of state_real's lost blocks), so its pattern gets a list of its own, in a tree buffer (all three are free by now)
+        const uint32_t* lost_list = d->erased;
+        uint64_t lost_count = n_erased;
+        if (s.split_shift != 0) {
+            uint32_t* scratch = reinterpret_cast<uint32_t*>(d->tree_y);  // NC positions and the counter: 4 (NC + 1) <= 32 T bytes
+            HIP_TRY(hipMemsetAsync(scratch + NC, 0, 4, s0));
+            hipLaunchKernelGGL(k_erased_list, grid_of((NC + 15) / 16), dim3(256), 0, s0, d->state_real, (uint32_t)NC, scratch, scratch + NC);
+            lost_list = scratch;
+            lost_count = s.erased_data + s.erased_parity;
+        }
+        hipLaunchKernelGGL(k_finish_lost, grid_of(lost_count), dim3(256), 0, s0, d->lv, lost_list, (uint32_t)lost_count, d->wpow, d->gout, (uint32_t)NC,
+                           (uint32_t)(T - n_erased), d->gout_all_valid ? d->gout_all : nullptr, e, log2k + e);
+        HIP_TRY(hipGetLastError());
+        if (d->split_ready && d->gout_all_valid) {
+            // the second chain's tables: the factor of q~ by position (once) and the lost parity blocks' output factors (this pattern)
+            const hipError_t e1 = d->split_pos_odd ? hipSuccess : hipMalloc((void**)&d->split_pos_odd, N * 16);
+            const hipError_t e2 = e1 != hipSuccess ? e1 : d->gout_par ? hipSuccess : hipMalloc((void**)&d->gout_par, N * 16);
+            if (e2 == hipSuccess) {
+                if (!d->split_pos_odd_built) {
+                    const int rc2 = split_addend_factors(d->split_pos_odd, log2k, s0, true);
+                    if (rc2 != FASTECC_OK) return rc2;
+                    d->split_pos_odd_built = true;
+                }
+                hipLaunchKernelGGL(k_gout_par, grid_of(N), dim3(256), 0, s0, d->gout_all, d->state_real, d->gout_par, (uint32_t)N);
+                HIP_TRY(hipGetLastError());
+                d->split_repair_ready = true;
+            } else {
+                (void)hipGetLastError();  // no memory for the tables: the split decodes, the lost parity is re-encoded
+            }
+        }
+        // (the one-transform repair is the unsplit pattern's.  Also when the split's paths or buffers could NOT be built: the locator's state then still
+        //  counts the unused parity blocks as lost, so gout_all is non-zero there and that repair would rewrite up to k (1 - 2^-h) parity blocks the
+        //  caller holds — decode + re-encode restores only what state_real says is lost)
+        if (d->split_ready || s.split_shift != 0) d->gout_all_valid = false;
         return FASTECC_OK;
-    };
-    if (d->direct > 0) {
+    }
+};
+
+// ---- decode ----
+// One fastecc_decode (rebuild_with == null) or fastecc_repair of a stripe in device memory, enqueued on s0
+struct StripeDecode {
+    Decoder* d;
+    uint64_t *data, *parity;
+    Path* rebuild_with;
+    hipStream_t s0;
+    const LaunchHooks* hooks;
+    uint32_t elems = (uint32_t)d->elems;
+    bool rebuild = rebuild_with != nullptr && d->erased_parity != 0;  // the lost parity blocks are wanted too
+
+    int run()
+    {
+        if (d->direct > 0) return direct();
+        int rc;
+        bool data_done = d->erased_data == 0, all_done = false;
+        if (!data_done && rebuild && d->gout_all_valid && ((rc = repair_one_transform(&all_done)) != FASTECC_OK || all_done)) return rc;
+        if (!data_done && d->e == 1 && d->split_ready && ((rc = decode_split(&data_done, &all_done)) != FASTECC_OK || all_done)) return rc;
+        if (!data_done && (rc = transform_data()) != FASTECC_OK) return rc;
+        if (!rebuild) return FASTECC_OK;
+        return d->e > 1 ? rebuild_cosets(d->lost_coset_mask, false) : reencode_parity();
+    }
+
+    // few losses.  rows: the k data blocks and as many parity blocks as data blocks are lost; outputs: the lost data blocks first — fastecc_decode
+    // stops after them
+    int direct()
+    {
         if (d->erased_data == 0 && !rebuild) return FASTECC_OK;
-        // rows: the k data blocks and as many parity blocks as data blocks are lost; outputs: the lost data blocks first — fastecc_decode stops after them
         const uint32_t rows = (uint32_t)d->direct_rows, chunks = (rows + DIRECT_ROWS - 1) / DIRECT_ROWS;
         const int outputs = rebuild ? d->direct : d->direct_ed;
-        const uint64_t items = (uint64_t)chunks * col_chunks;
-        const dim3 grid((unsigned)((items + 3) / 4));
-#define FASTECC_DIRECT61(EB)                                                                                                                                  \
-    hipLaunchKernelGGL(k_direct_accumulate<EB>, dim3(grid.x, (unsigned)((std::min(outputs, d->direct_pad) + EB - 1) / EB)), dim3(256), 0, s0, data, parity,    \
-                       d->direct_coef, d->direct_partial, elems, rows, col_chunks, items, (uint32_t)d->direct_pad, (uint32_t)(d->direct_nc / 2),               \
+        const RowGrid g(chunks, elems);
+#define FASTECC_DIRECT61(EB)                                                                                                                            \
+    hipLaunchKernelGGL(k_direct_accumulate<EB>, g.grid((unsigned)((std::min(outputs, d->direct_pad) + EB - 1) / EB)), dim3(256), 0, s0, data, parity,    \
+                       d->direct_coef, d->direct_partial, elems, rows, g.col_chunks, g.items, (uint32_t)d->direct_pad, (uint32_t)(d->direct_nc / 2),     \
                        d->direct_pos + DIRECT_MAX)
         switch (d->direct_pad) {
             case 1: FASTECC_DIRECT61(1); break;
@@ -1312,165 +1358,163 @@ int decode(Decoder* d, uint64_t* data, uint64_t* parity, Path* rebuild_with, hip
             default: FASTECC_DIRECT61(8); break;  // 8, 16, 32: sweeps of 8 outputs
         }
 #undef FASTECC_DIRECT61
-        D61_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         uint64_t* stage = d->direct_partial + 2ull * (uint64_t)chunks * d->direct_pad * elems;
         hipLaunchKernelGGL(k_direct_reduce1, dim3((elems + 255) / 256, (unsigned)outputs, DIRECT_SEGS), dim3(256), 0, s0, d->direct_partial, stage, elems, chunks,
                            d->direct_pad, outputs);
         hipLaunchKernelGGL(k_direct_reduce2, dim3((elems + 255) / 256, (unsigned)outputs), dim3(256), 0, s0, stage, d->direct_pos, data, parity, elems,
                            d->direct_pad, outputs, rebuild);
-        D61_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         // (n = 4k / 8k: that was the (2k,k) code of the data and the first coset; the other cosets' lost blocks are re-encoded)
         if (d->e > 1 && rebuild && (d->lost_coset_mask & ~1u) != 0) return rebuild_cosets(d->lost_coset_mask & ~1u, true);
         return FASTECC_OK;
     }
-    if (d->erased_data != 0 && rebuild && d->gout_all_valid) {
-        // fastecc_repair in ONE transform: x p'(x) at all 2k positions, the gather in its first tile, the scatter — lost data AND lost parity
-        // blocks, each times its factor — in its last; no fold, no second encode
-        if (!d->work) D61_TRY(hipMalloc((void**)&d->work, d->NC * d->elems * 16));
+
+    // fastecc_repair in ONE transform: x p'(x) at all 2k positions, the gather in its first tile, the scatter — lost data AND lost parity
+    // blocks, each times its factor — in its last; no fold, no second encode.  *done = false: the plan has no such tiles.
+    int repair_one_transform(bool* done)
+    {
+        if (!d->work) HIP_TRY(hipMalloc((void**)&d->work, d->NC * d->elems * 16));
         const int rc = encode_ends(d->transform, data, parity, d->fin, d->work, d->gout_all, data, parity, s0, hooks);
-        if (rc == FASTECC_OK) return FASTECC_OK;
-        if (rc != FASTECC_E_UNSUPPORTED) return rc;
+        *done = rc == FASTECC_OK;
+        return rc == FASTECC_E_UNSUPPORTED ? FASTECC_OK : rc;
     }
-    bool data_done = false;
-    if (d->e > 1) {
-        // n = 4k / 8k: gather through the position map, x p'(x) on all k << e positions, the data positions (multiples of 2^e) scattered back
-        if (d->erased_data != 0) {
-            if (!d->work) D61_TRY(hipMalloc((void**)&d->work, d->NC * d->elems * 16));
-            // n = 4k: x p'(x) at the data positions only — the way down on all 4k positions, the folding MID tile, the way up on k positions
-            // (encode_fold), the gather through the position map in the first tile and the scatter in the last where the plans have such passes
-            const int caps = d->half ? fold_caps(d->transform, d->half) : 0;
-            // (n = 8k: the folded transform leaves 2k rows, the data at the even ones: k_scatter takes every second)
-            const bool folded = (caps & FOLD_PAIRS) != 0, fused_gather = folded && (caps & FOLD_GATHERS), fused_scatter = folded && (caps & FOLD_SCATTERS) && d->e == 2;
-            const int rec_shift = d->e - 2;
-            uint64_t items = d->NC * col_chunks;
-            if (!fused_gather) {
-                hipLaunchKernelGGL(k_gather_map, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s0, data, parity, d->work, d->fin, d->srcmap, elems, col_chunks, items);
-                D61_TRY(hipGetLastError());
-            }
-            if (folded) {
-                if (!d->rec) D61_TRY(hipMalloc((void**)&d->rec, (d->N << rec_shift) * d->elems * 16));
-                FoldEnds ends;
-                if (fused_gather) {
-                    ends.parity = parity;
-                    ends.fin = d->fin;
-                    ends.map = d->srcmap;
-                }
-                if (fused_scatter) {
-                    ends.gout = d->gout;
-                    ends.data_out = data;
-                }
-                const int rc = encode_fold(d->transform, d->half, fused_gather ? data : d->work, d->work, d->rec, s0, hooks, &ends);
-                if (rc != FASTECC_OK) return rc;
-            } else {
-                const int rc = encode(d->transform, d->work, d->work, s0, hooks);
-                if (rc != FASTECC_OK) return rc;
-            }
-            if (!fused_scatter) {
-                items = d->N * col_chunks;
-                hipLaunchKernelGGL(k_scatter, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s0, folded ? d->rec : d->work, data, d->gout, elems, col_chunks, items,
-                                   folded ? 1u << rec_shift : 1u << d->e);
-                D61_TRY(hipGetLastError());
-            }
-        }
-        if (rebuild) {
-            const int rc = rebuild_cosets(d->lost_coset_mask, false);
-            if (rc != FASTECC_OK) return rc;
-        }
-        return FASTECC_OK;
-    }
-    if (d->erased_data != 0 && d->split_ready) {
-        // even / odd split: r~ = DIF of the k >> h parity rows in use (times l), then the data chain — DIF of data * l, g = (2m+k)/2k q~ - 1/2 w^-m r~
-        // between the halves of MID, DIT, and only the rebuilt blocks stored, times 1 / (w^2i l'(w^2i)), straight into the data stripe
+
+    // even / odd split: r~ = DIF of the k >> h parity rows in use (times l), then the data chain — DIF of data * l, g = (2m+k)/2k q~ - 1/2 w^-m r~
+    // between the halves of MID, DIT, and only the rebuilt blocks stored, times 1 / (w^2i l'(w^2i)), straight into the data stripe.
+    // *data_done: the data blocks are whole again; *all_done: the lost parity blocks too (the second chain)
+    int decode_split(bool* data_done, bool* all_done)
+    {
         const int h = d->split_shift;
-        const uint64_t rows = d->N >> h, items = rows * col_chunks;
-        hipLaunchKernelGGL(k_split_small_gather, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s0, parity, d->small_buf, d->fin, elems, h, col_chunks, items);
-        D61_TRY(hipGetLastError());
+        const RowGrid g(d->N >> h, elems);
+        hipLaunchKernelGGL(k_split_small_gather, g.grid(), dim3(256), 0, s0, parity, d->small_buf, d->fin, elems, h, g.col_chunks, g.items);
+        HIP_TRY(hipGetLastError());
         int rc = dif_only(d->small[h], d->small_buf, true, s0, hooks);
         // (repair: the data chain also stores q~, and a second MID + DIT chain turns it and the same r~ into the lost parity blocks)
         bool second = rebuild && d->split_repair_ready;
         if (second && !d->split_q2 && hipMalloc((void**)&d->split_q2, d->N * d->elems * 16) != hipSuccess) {
             (void)hipGetLastError();
             d->split_q2 = nullptr;
-            second = false;  // no room for the extra stripe: the lost parity is re-encoded below
+            second = false;  // no room for the extra stripe: the lost parity is re-encoded
         }
         if (rc == FASTECC_OK)
             rc = split_decode(d->splitp, data, d->fin, 2, d->small_buf, h, d->split_af, d->split_work, d->gout, data, s0, hooks, second ? d->split_q2 : nullptr);
         if (rc != FASTECC_OK && rc != FASTECC_E_UNSUPPORTED) return rc;
-        data_done = rc == FASTECC_OK;
-        if (data_done && second) {
+        *data_done = rc == FASTECC_OK;
+        if (*data_done && second) {
             rc = split_repair_parity(d->splitp, d->split_q2, d->split_pos_odd, d->small_buf, h, d->split_work, d->gout_par, parity, s0, hooks);
             if (rc != FASTECC_OK && rc != FASTECC_E_UNSUPPORTED) return rc;
-            if (rc == FASTECC_OK) return FASTECC_OK;  // data and parity are whole again
+            *all_done = rc == FASTECC_OK;
         }
+        return FASTECC_OK;
     }
-    if (d->erased_data != 0 && !data_done) {
-        if (!d->work) D61_TRY(hipMalloc((void**)&d->work, d->NC * d->elems * 16));
-        // x p'(x) at the even (data) positions only where the plans pair up (encode_fold) — then the gather rides in the first DIF tile and the
-        // scatter in the last DIT tile where there are such passes — else on all 2k points
+
+    // The lost data blocks by the transform: gather work[u] = block at u times fin[u], x p'(x), scatter the data positions times gout.
+    // e = 1: x p'(x) at the even (data) positions only where the plans pair up (encode_fold: the way down on all 2k positions, the folding MID
+    // tile, the way up on k positions) — then the gather rides in the first DIF tile and the scatter in the last DIT tile where there are such
+    // passes — else on all 2k points.  n = 4k: the same at every fourth position, the gather through the position map; n = 8k: the folded
+    // transform leaves 2k rows, the data at the even ones (k_scatter takes every second: no fused scatter)
+    int transform_data()
+    {
+        if (!d->work) HIP_TRY(hipMalloc((void**)&d->work, d->NC * d->elems * 16));
+        const int rec_shift = d->e == 3 ? 1 : 0;  // the folded transform leaves k << rec_shift rows
         const int caps = d->half ? fold_caps(d->transform, d->half) : 0;
-        const bool fused_gather = (caps & FOLD_GATHERS) != 0, fused_scatter = (caps & FOLD_SCATTERS) != 0;
+        const bool folded = (caps & FOLD_PAIRS) != 0, fused_gather = folded && (caps & FOLD_GATHERS), fused_scatter = folded && (caps & FOLD_SCATTERS) && rec_shift == 0;
         if (!fused_gather) {
-            const uint64_t items = d->NC * col_chunks;
-            hipLaunchKernelGGL(k_gather, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s0, data, parity, d->work, d->fin, elems, col_chunks, items);
-            D61_TRY(hipGetLastError());
+            const RowGrid g(d->NC, elems);
+            if (d->e > 1) hipLaunchKernelGGL(k_gather_map, g.grid(), dim3(256), 0, s0, data, parity, d->work, d->fin, d->srcmap, elems, g.col_chunks, g.items);
+            else hipLaunchKernelGGL(k_gather, g.grid(), dim3(256), 0, s0, data, parity, d->work, d->fin, elems, g.col_chunks, g.items);
+            HIP_TRY(hipGetLastError());
         }
-        int rc = FASTECC_E_UNSUPPORTED;
-        if (caps & FOLD_PAIRS) {
-            if (!d->rec) D61_TRY(hipMalloc((void**)&d->rec, d->N * d->elems * 16));
+        if (folded) {
+            if (!d->rec) HIP_TRY(hipMalloc((void**)&d->rec, (d->N << rec_shift) * d->elems * 16));
             FoldEnds ends;
             if (fused_gather) {
                 ends.parity = parity;
                 ends.fin = d->fin;
+                ends.map = d->e > 1 ? d->srcmap : nullptr;
             }
             if (fused_scatter) {
                 ends.gout = d->gout;
                 ends.data_out = data;
             }
-            rc = encode_fold(d->transform, d->half, fused_gather ? data : d->work, d->work, d->rec, s0, hooks, &ends);
+            const int rc = encode_fold(d->transform, d->half, fused_gather ? data : d->work, d->work, d->rec, s0, hooks, &ends);
+            if (rc != FASTECC_OK) return rc;
+        } else {
+            const int rc = encode(d->transform, d->work, d->work, s0, hooks);
             if (rc != FASTECC_OK) return rc;
         }
-        const bool folded = rc == FASTECC_OK;
-        if (!folded) {
-            rc = encode(d->transform, d->work, d->work, s0, hooks);
-            if (rc != FASTECC_OK) return rc;
+        if (!fused_scatter) {
+            const RowGrid g(d->N, elems);
+            hipLaunchKernelGGL(k_scatter, g.grid(), dim3(256), 0, s0, folded ? d->rec : d->work, data, d->gout, elems, g.col_chunks, g.items,
+                               folded ? 1u << rec_shift : 1u << d->e);
+            HIP_TRY(hipGetLastError());
         }
-        if (!(folded && fused_scatter)) {
-            const uint64_t items = d->N * col_chunks;
-            hipLaunchKernelGGL(k_scatter, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s0, folded ? d->rec : d->work, data, d->gout, elems, col_chunks, items,
-                               folded ? 1u : 2u);
-            D61_TRY(hipGetLastError());
-        }
+        return FASTECC_OK;
     }
-    if (rebuild) {
-        if (!d->again) D61_TRY(hipMalloc((void**)&d->again, d->N * d->elems * 16));
+
+    // (2k,k): the lost parity blocks from the encoder again, on the repaired data
+    int reencode_parity()
+    {
+        if (!d->again) HIP_TRY(hipMalloc((void**)&d->again, d->N * d->elems * 16));
         const int rc = encode(rebuild_with, data, d->again, s0, hooks);
         if (rc != FASTECC_OK) return rc;
-        const uint64_t items = d->N * col_chunks;
-        hipLaunchKernelGGL(k_restore, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s0, d->again, parity, d->state_real ? d->state_real : d->state, elems, col_chunks, items);
-        D61_TRY(hipGetLastError());
+        const RowGrid g(d->N, elems);
+        hipLaunchKernelGGL(k_restore, g.grid(), dim3(256), 0, s0, d->again, parity, d->state_real ? d->state_real : d->state, elems, g.col_chunks, g.items);
+        HIP_TRY(hipGetLastError());
+        return FASTECC_OK;
     }
-    return FASTECC_OK;
+
+    // n = 4k / 8k: the same; only the cosets with a lost block, only the lost ones written
+    int rebuild_cosets(uint32_t coset_mask, bool first_coset_done)
+    {
+        if (cosets_of(rebuild_with) != (1 << d->e) - 1) return FASTECC_E_INVAL;
+        if (!d->again) HIP_TRY(hipMalloc((void**)&d->again, d->M * d->elems * 16));
+        if (encode_cosets_needs_work(rebuild_with) && !d->cos_work) HIP_TRY(hipMalloc((void**)&d->cos_work, d->N * d->elems * 16));
+        const int rc = encode_cosets(rebuild_with, data, d->again, d->cos_work, s0, hooks, coset_mask);
+        if (rc != FASTECC_OK) return rc;
+        // (after the inner code's direct path the first coset's blocks are in place and `again` holds nothing for them)
+        const uint64_t skip = first_coset_done ? d->N : 0;
+        const RowGrid g(d->M - skip, elems);
+        hipLaunchKernelGGL(k_restore_map, g.grid(), dim3(256), 0, s0, d->again + 2 * skip * elems, parity + 2 * skip * elems, d->parity_lost + skip, elems,
+                           g.col_chunks, g.items);
+        HIP_TRY(hipGetLastError());
+        return FASTECC_OK;
+    }
+};
+
+}  // namespace
+
+int decode_prepare(Decoder** slot, int log2k, uint64_t elems, const uint8_t* data_present, const uint8_t* parity_present, int direct_max, char* detail,
+                   size_t cap, int split, int e)
+{
+    if (e < 1 || e > 3 || (*slot && (*slot)->built && (*slot)->e != e)) return FASTECC_E_INVAL;
+    return Prepare{slot, log2k, elems, data_present, parity_present, direct_max, detail, cap, split, e}.run();
+}
+
+int decode(Decoder* d, uint64_t* data, uint64_t* parity, Path* rebuild_with, hipStream_t s0, const LaunchHooks* hooks)
+{
+    if (!d || !d->ready) return FASTECC_E_INVAL;
+    return StripeDecode{d, data, parity, rebuild_with, s0, hooks}.run();
 }
 
 // The same for stripes in (pageable) host memory: staged through HBM, synchronous.
 int decode_host(Decoder* d, void* data, void* parity, Path* rebuild_with, hipStream_t s0, const LaunchHooks* hooks)
 {
     if (!d || !d->ready) return FASTECC_E_INVAL;
-    char* detail = nullptr;
-    const size_t cap = 0;
     const bool rebuild = rebuild_with != nullptr && d->erased_parity != 0;
     if (d->erased_data == 0 && !rebuild) return FASTECC_OK;
     const size_t stripe = d->N * d->elems * 16, pstripe = (d->e > 1 ? d->M : d->N) * d->elems * 16;
-    if (!d->stage) D61_TRY(hipMalloc((void**)&d->stage, stripe + pstripe));
+    if (!d->stage) HIP_TRY(hipMalloc((void**)&d->stage, stripe + pstripe));
     uint64_t* ddata = d->stage;
     uint64_t* dpar = d->stage + stripe / 8;
-    D61_TRY(hipMemcpyAsync(ddata, data, stripe, hipMemcpyHostToDevice, s0));
-    D61_TRY(hipMemcpyAsync(dpar, parity, pstripe, hipMemcpyHostToDevice, s0));
+    HIP_TRY(hipMemcpyAsync(ddata, data, stripe, hipMemcpyHostToDevice, s0));
+    HIP_TRY(hipMemcpyAsync(dpar, parity, pstripe, hipMemcpyHostToDevice, s0));
     const int rc = decode(d, ddata, dpar, rebuild_with, s0, hooks);
     if (rc != FASTECC_OK) return rc;
-    if (d->erased_data != 0) D61_TRY(hipMemcpyAsync(data, ddata, stripe, hipMemcpyDeviceToHost, s0));
-    if (rebuild) D61_TRY(hipMemcpyAsync(parity, dpar, pstripe, hipMemcpyDeviceToHost, s0));
-    D61_TRY(hipStreamSynchronize(s0));
+    if (d->erased_data != 0) HIP_TRY(hipMemcpyAsync(data, ddata, stripe, hipMemcpyDeviceToHost, s0));
+    if (rebuild) HIP_TRY(hipMemcpyAsync(parity, dpar, pstripe, hipMemcpyDeviceToHost, s0));
+    HIP_TRY(hipStreamSynchronize(s0));
     return FASTECC_OK;
 }
 

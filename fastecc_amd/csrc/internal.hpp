@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
 #include <mutex>
 #include <new>
 #include <string>
@@ -21,6 +24,23 @@ int hip_fail(hipError_t e, const char* what);
         hipError_t e_ = (expr);                           \
         if (e_ != hipSuccess) return hip_fail(e_, #expr); \
     } while (0)
+
+// FASTECC_TRACE_PREPARE=1: wall-clock of the phases of a decode_prepare on stderr (where does a first call spend its time), one line per mark():
+// the prefix, the label padded to `width`, the time since the previous mark
+struct PhaseTimer {
+    const char* prefix;
+    int width;
+    bool on = getenv("FASTECC_TRACE_PREPARE") != nullptr;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    explicit PhaseTimer(const char* prefix_ = "[fastecc prepare]", int width_ = 28) : prefix(prefix_), width(width_) {}
+    void mark(const char* what)
+    {
+        if (!on) return;
+        const auto t1 = std::chrono::steady_clock::now();
+        fprintf(stderr, "%s %-*s %8.3f ms\n", prefix, width, what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+        t0 = t1;
+    }
+};
 
 // the current device is `dev` for the scope, the previous one again after it
 struct DeviceGuard {
