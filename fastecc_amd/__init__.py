@@ -119,6 +119,7 @@ def lib():
     L.fastecc_gf61_pow.argtypes, L.fastecc_gf61_pow.restype = [pair, u64, pair], i32
     L.fastecc_gf61_inv.argtypes, L.fastecc_gf61_inv.restype = [pair, pair], i32
     L.fastecc_gf61_root.argtypes, L.fastecc_gf61_root.restype = [u64, pair], i32
+    L.fastecc_gf61_binary.argtypes, L.fastecc_gf61_binary.restype = [vp, i32, vp, vp, vp, u64, vp], i32
     L.fastecc_profile_enable.argtypes, L.fastecc_profile_enable.restype = [vp, i32], i32
     L.fastecc_profile_reset.argtypes, L.fastecc_profile_reset.restype = [vp], i32
     L.fastecc_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double),
@@ -237,6 +238,24 @@ class Encoder:
         code = {"add": 0, "sub": 1, "mul": 2, "mul_mont": 3}[op] if isinstance(op, str) else op
         _check(lib().fastecc_gf_binary(self._h, code, _addr(x), _addr(y), _addr(out), count, stream or None),
                "fastecc_gf_binary")
+        return out
+
+    # op codes of fastecc_gf61_binary (include/fastecc.h: FASTECC_GF61_OP_*); the run ops take "run_dif" / "run_dif_inv" / "run_dit" + levels
+    GF61_OPS = {"add": 0, "sub": 1, "mul": 2, "mul_raw": 3, "mul_w8": 4, "mul_w8i": 5, "mul_w8_inv": 6, "mul_w8i_inv": 7, "fold": 8, "canon": 9,
+                "run_dif": 16, "run_dif_inv": 20, "run_dit": 24}
+
+    def gf61_binary(self, op, x, y, out, count, stream=0, levels=1):
+        """The 64-bit field's device arithmetic on `count` elements (re, im) of device memory, results NOT made canonical (tests only).
+        op: a name of GF61_OPS (run ops: `levels` = 1..4 radix-2 levels on runs of 2^levels elements) or a raw op code."""
+        if isinstance(op, str):
+            code = self.GF61_OPS[op]
+            if op.startswith("run_"):
+                if not 1 <= levels <= 4:
+                    raise ValueError("a run has 1..4 levels")
+                code += levels - 1
+        else:
+            code = op
+        _check(lib().fastecc_gf61_binary(self._h, code, _addr(x), _addr(y), _addr(out), count, stream or None), "fastecc_gf61_binary")
         return out
 
     def check_range(self, data, stream=0, mem=MEM_DEVICE):

@@ -394,6 +394,17 @@ int fastecc_gf_binary(fastecc_ctx* c, int op, const uint32_t* x, const uint32_t*
     return FASTECC_OK;
 }
 
+int fastecc_gf61_binary(fastecc_ctx* c, int op, const uint64_t* x, const uint64_t* y, uint64_t* out, uint64_t count, void* stream)
+{
+    if (!c || !x || !out) return FASTECC_E_INVAL;
+    if (!c->p61) return FASTECC_E_UNSUPPORTED;  // 64-bit words: GF((2^61-1)^2) only
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallLock lk(c->mu);
+    ProfScope ps(c, (hipStream_t)stream, "gf61_binary");
+    return p61::gf_probe(c->p61, op, x, y, out, count, (hipStream_t)stream);  // checks op, y and count
+}
+
 int fastecc_check_range(fastecc_ctx* c, const void* data, int mem_kind, void* stream, uint64_t* bad_words)
 {
     if (!c || !data || !bad_words || ((uintptr_t)data & (c->p61 ? 15u : 3u))) return FASTECC_E_INVAL;  // as fastecc_encode

@@ -161,7 +161,9 @@ GF61_D Twiddle make_twiddle(uint64_t c, uint64_t d)
     return w;
 }
 
-// x < 2^63 -> limbs with x = x1 2^31 + x0 (mod p), x0 < 2^31 + 4, x1 < 2^30: bits 61, 62 (weight 2^61 = 1) join the low limb
+// ANY 64-bit x -> limbs with x = x1 2^31 + x0 (mod p), x0 < 2^31 + 8, x1 < 2^30: bits 61, 62 and 63 (weights 2^61, 2^62, 2^63 = 1, 2, 4 mod p)
+// join the low limb as the number hi >> 29 = x >> 61 <= 7.  The loose differences of a butterfly (sub_raw4 above) reach 3.5 * 2^62 + 2^34, so bit 63
+// does occur; checked on the device for the whole range by the probe (fastecc_gf61_binary, tests/test_gpu_p61_edges.py).
 GF61_D void split_raw(uint64_t x, uint32_t& x0, uint32_t& x1)
 {
     const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
@@ -185,7 +187,8 @@ GF61_D uint64_t combine(uint64_t acc, uint64_t mid, const Opaque& k)
     return fold(t, k);
 }
 
-// (a + b i)(c + d i) = (a c + b e) + (a d + b c) i,  e = -d; limbs a0, b0 < 2^31 + 4 and a1, b1 <= 2^30 + 4
+// (a + b i)(c + d i) = (a c + b e) + (a d + b c) i,  e = -d; limbs a0, b0 < 2^31 + 8 with a1, b1 < 2^30 (split_raw), or a0, b0 < 2^31 with
+// a1, b1 <= 2^30 + 3 (split_lazy); either way acc < 1.5 2^63 + 2^35 and mid < 2^63 + 2^35, what combine takes
 GF61_D Elem mul_limbs(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, const Twiddle& w, const Opaque& k)
 {
     const uint64_t re_acc = mad64(b1, w.e1d, mad64(a1, w.c1d, mad64(b0, w.e0, mad64(a0, w.c0, 0))));
@@ -202,7 +205,7 @@ GF61_D Elem mul(Elem x, const Twiddle& w, const Opaque& k)
     split_lazy(x.im, b0, b1);
     return mul_limbs(a0, a1, b0, b1, w, k);
 }
-// x components < 2^63 (sub_raw results)
+// x components: any 64-bit value (sub_raw results, < 2^63, and the loose differences of dif_bfly / dit_bfly, up to 3.5 * 2^62 + 2^34)
 GF61_D Elem mul_raw(Elem x, const Twiddle& w, const Opaque& k)
 {
     uint32_t a0, a1, b0, b1;

@@ -676,6 +676,67 @@ __global__ __launch_bounds__(256) void p61_count_out_of_range_kernel(const uint6
     if ((threadIdx.x & 63u) == 0 && bad) atomicAdd(counter, bad);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The probe of fastecc_gf61_binary (tests only): the field primitives and the register runs on operands the caller chooses, lazy and
+// loose words included, and the results stored as the device function leaves them — no canon — so that a test sees the residue AND
+// the bound.  One thread per element (element ops) or per run of 2^L consecutive elements (run ops); the twiddle of mul / mul_raw is
+// per lane here (its limbs in VGPRs, as in mul_canon).
+__global__ __launch_bounds__(256) void p61_probe_elem_kernel(int op, const uint64_t* x, const uint64_t* y, uint64_t* out, uint64_t count)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const gf61::Opaque k = gf61::make_opaque();
+    const Elem a{x[2 * i], x[2 * i + 1]};
+    Elem b{0, 0};
+    if (op <= FASTECC_GF61_OP_MUL_RAW) b = Elem{y[2 * i], y[2 * i + 1]};
+    Elem r{0, 0};
+    switch (op) {
+    case FASTECC_GF61_OP_ADD:         r = gf61::add(a, b, k); break;
+    case FASTECC_GF61_OP_SUB:         r = gf61::sub(a, b, k); break;
+    case FASTECC_GF61_OP_MUL:         r = gf61::mul(a, gf61::make_twiddle(b.re, b.im), k); break;
+    case FASTECC_GF61_OP_MUL_RAW:     r = gf61::mul_raw(a, gf61::make_twiddle(b.re, b.im), k); break;
+    case FASTECC_GF61_OP_MUL_W8:      r = mul_w8<K_W8, false>(a, k); break;
+    case FASTECC_GF61_OP_MUL_W8I:     r = mul_w8<K_W8I, false>(a, k); break;
+    case FASTECC_GF61_OP_MUL_W8_INV:  r = mul_w8<K_W8, true>(a, k); break;
+    case FASTECC_GF61_OP_MUL_W8I_INV: r = mul_w8<K_W8I, true>(a, k); break;
+    case FASTECC_GF61_OP_FOLD:        r = gf61::fold(a, k); break;
+    default:                          r = gf61::canon(a); break;
+    }
+    out[2 * i] = r.re;
+    out[2 * i + 1] = r.im;
+}
+
+template <int L, bool DIT, bool INV>
+__global__ __launch_bounds__(256) void p61_probe_run_kernel(const uint64_t* x, uint64_t* out, uint64_t items, const SmallRoots sr)
+{
+    constexpr int R = 1 << L;
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= items) return;
+    const gf61::Opaque k = gf61::make_opaque();
+    Elem v[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) v[j] = Elem{x[2 * (i * R + j)], x[2 * (i * R + j) + 1]};
+    if constexpr (DIT) dit_levels<L, true, false>(v, nullptr, 0u, 0, k, sr);
+    else               dif_levels<L, true, INV>(v, nullptr, 0u, 0, k, sr);
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        out[2 * (i * R + j)] = v[j].re;
+        out[2 * (i * R + j) + 1] = v[j].im;
+    }
+}
+
+template <int L>
+hipError_t launch_probe_run(int kind, const uint64_t* x, uint64_t* out, uint64_t items, const SmallRoots& sr, hipStream_t st)
+{
+    const dim3 grid((unsigned)((items + 255) / 256));
+    switch (kind) {
+    case 0:  hipLaunchKernelGGL((p61_probe_run_kernel<L, false, false>), grid, dim3(256), 0, st, x, out, items, sr); break;
+    case 1:  hipLaunchKernelGGL((p61_probe_run_kernel<L, false, true>), grid, dim3(256), 0, st, x, out, items, sr); break;
+    default: hipLaunchKernelGGL((p61_probe_run_kernel<L, true, false>), grid, dim3(256), 0, st, x, out, items, sr); break;
+    }
+    return hipGetLastError();
+}
+
 template <int LOGR, int MODE, bool INV>
 hipError_t launch_canon(bool canon, const PassArgs& a, dim3 grid, hipStream_t st)
 {
@@ -1460,6 +1521,35 @@ int count_out_of_range(Path* p, const uint64_t* data, unsigned long long* counte
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, 0, e, "p61_count_out_of_range");
     return FASTECC_OK;
+}
+
+// fastecc_gf61_binary: see include/fastecc.h for the op table.  The run ops use the path's own w_16 constants, like every pass does.
+int gf_probe(Path* p, int op, const uint64_t* x, const uint64_t* y, uint64_t* out, uint64_t count, hipStream_t st)
+{
+    if (!p || !x || !out) return FASTECC_E_INVAL;
+    if (count == 0) return FASTECC_OK;
+    hipError_t e;
+    if (op >= FASTECC_GF61_OP_ADD && op <= FASTECC_GF61_OP_CANON) {
+        if (op <= FASTECC_GF61_OP_MUL_RAW && !y) return FASTECC_E_INVAL;
+        const uint64_t blocks = (count + 255) / 256;
+        if (blocks > 0x7FFFFFFFull) return FASTECC_E_UNSUPPORTED;
+        hipLaunchKernelGGL(p61_probe_elem_kernel, dim3((unsigned)blocks), dim3(256), 0, st, op, x, y, out, count);
+        e = hipGetLastError();
+    } else if (op >= FASTECC_GF61_OP_RUN_DIF && op < FASTECC_GF61_OP_RUN_DIT + 4) {
+        const int kind = (op - FASTECC_GF61_OP_RUN_DIF) / 4, L = (op - FASTECC_GF61_OP_RUN_DIF) % 4 + 1;
+        if (count & ((1ull << L) - 1)) return FASTECC_E_INVAL;
+        const uint64_t items = count >> L;
+        if ((items + 255) / 256 > 0x7FFFFFFFull) return FASTECC_E_UNSUPPORTED;
+        switch (L) {
+        case 1:  e = launch_probe_run<1>(kind, x, out, items, p->sr, st); break;
+        case 2:  e = launch_probe_run<2>(kind, x, out, items, p->sr, st); break;
+        case 3:  e = launch_probe_run<3>(kind, x, out, items, p->sr, st); break;
+        default: e = launch_probe_run<4>(kind, x, out, items, p->sr, st); break;
+        }
+    } else {
+        return FASTECC_E_INVAL;
+    }
+    return e == hipSuccess ? FASTECC_OK : fail(nullptr, 0, e, "p61_probe");
 }
 
 int set_plan(Path* p, int plan, char* detail, size_t cap)

@@ -79,6 +79,9 @@ int split_addend_factors(uint64_t* table, int n, hipStream_t st, bool forward = 
 // words >= p among the 2 * elems * k words of a stripe; `counter` is a device uint64 the caller zeroed
 int count_out_of_range(Path* p, const uint64_t* data, unsigned long long* counter, hipStream_t st);
 
+// fastecc_gf61_binary (tests of the device arithmetic): op FASTECC_GF61_OP_* on `count` elements of device memory, results not made canonical
+int gf_probe(Path* p, int op, const uint64_t* x, const uint64_t* y, uint64_t* out, uint64_t count, hipStream_t st);
+
 // plan id (fastecc_set_plan): 0 = default (LDS tiles + 4-level register passes), 1..4 = register passes only with that many
 // levels, 10 + L / 20 + L = tiles with a 64 / 128 KiB exchange buffer; rebuilds the tables.  The device must be idle.
 int set_plan(Path* p, int plan, char* detail, size_t detail_cap);

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 330 /* 0.3.3: batched scrub of many stripes (fastecc_verify_batch / _correct_batch) */
+#define FASTECC_VERSION 331 /* 0.3.3.1: fastecc_gf61_binary, a probe of the 64-bit field's device arithmetic for tests */
 
 enum {
     FASTECC_OK = 0,
@@ -58,7 +58,7 @@ enum {
      *     order 2^t is w_(2^62)^(2^(62-t)); so w_4 = i and w_8 = 2^30 (1 + i);
      *   - the encoder is the same composition as RS.cpp:40-63 over this field: parity block j is the value at
      *     w_2N^(2j+1) of the polynomial of degree < N whose value at w_N^i is data block i.
-     * Supported by create/destroy/encode/encode_blocks/ntt/check_range/decode_prepare/decode/repair/profile/plan_string and
+     * Supported by create/destroy/encode/encode_blocks/ntt/check_range/decode_prepare/decode/repair/profile/plan_string/gf61_binary and
      * fastecc_set_plan (0 = default: LDS tiles; 1..4 = register passes with that many radix-2 levels; 10+L / 20+L = tiles with a
      * 64 / 128 KiB exchange buffer); the 32-bit-word entry points
      * (scale_blocks, gf_binary, set_option other than "decode_direct_max" and "decode_split") return FASTECC_E_UNSUPPORTED.
@@ -272,6 +272,51 @@ int fastecc_scale_blocks(fastecc_ctx *ctx, void *data, uint32_t scale, uint32_t 
  */
 int fastecc_gf_binary(fastecc_ctx *ctx, int op, const uint32_t *x, const uint32_t *y, uint32_t *out, uint64_t count,
                       void *stream);
+
+/*
+ * The same for the device arithmetic of FASTECC_FIELD_GF_P61_SQUARED (gf61.hpp and the register runs of gf61_kernels.hip), over `count`
+ * elements (two uint64 words each: re, im) of DEVICE memory.  That arithmetic keeps words LAZY — congruent to the value and in
+ * [0, 2^61 + 2^33), not necessarily canonical — and, inside a run of levels, LOOSE (unfolded 64-bit sums and differences), so the
+ * operands here need NOT be canonical and the results are stored as the device function leaves them, with no final reduction: a test
+ * checks the residue mod p = 2^61 - 1 AND the output bound.  FASTECC_E_UNSUPPORTED on a GF(0xFFF00001) context; FASTECC_E_INVAL for a null
+ * pointer (y may be null where it is unused), an unknown op, or a run op whose count is no multiple of its run length.
+ * The op codes exist for tests: more may be added, and they are no part of the encode / decode contract.
+ *
+ *   op            result (each component)               input domain (each word)                         output bound
+ *   ADD           x + y                                 x + y < 2^64 (lazy + lazy: < 2^62 + 2^34)        < 2^61 + 8 (lazy inputs: < 2^61 + 2)
+ *   SUB           x - y                                 y <= 2p, x + 2p - y < 2^64 (lazy, lazy)          < 2^61 + 8 (lazy inputs: < 2^61 + 3)
+ *   MUL           x * y  in GF(p^2)                     x lazy; y canonical (re, im < p)                 < 2^61 + 8
+ *   MUL_RAW       x * y  in GF(p^2)                     x ANY 64-bit word (loose differences reach       < 2^61 + 8
+ *                                                       3.5 * 2^62 + 2^34); y canonical
+ *   MUL_W8        x * w_8,   w_8 = 2^30 (1 + i)         x lazy                                           < 2^61 + 2^32
+ *   MUL_W8I       x * w_8^3                             x lazy                                           < 2^61 + 2^32
+ *   MUL_W8_INV    x * w_8^-1                            x lazy                                           < 2^61 + 2^32
+ *   MUL_W8I_INV   x * w_8^-3                            x lazy                                           < 2^61 + 2^32
+ *   FOLD          x                                     any 64-bit word                                  < 2^61 + 8
+ *   CANON         x                                     x <= 2p (every lazy word)                        < p
+ *   RUN_DIF + l   2^(l+1)-point forward transform of each run of 2^(l+1) consecutive elements of x, as l + 1 radix-2 decimation-in-
+ *   RUN_DIF_INV+l frequency levels (result in bit-reversed order; _INV: with the inverse roots); RUN_DIT + l: the same number of
+ *   RUN_DIT + l   decimation-in-time levels with the forward roots (input in bit-reversed order, result in natural order).  l = 0..3.
+ *                 These are the register runs every pass is made of (levels that leave loose outputs every other level, w_4 / w_8 /
+ *                 w_16 specialised).  x lazy; y unused; count a multiple of 2^(l+1); output < 2^61 + 8.
+ */
+enum {
+    FASTECC_GF61_OP_ADD = 0,
+    FASTECC_GF61_OP_SUB = 1,
+    FASTECC_GF61_OP_MUL = 2,
+    FASTECC_GF61_OP_MUL_RAW = 3,
+    FASTECC_GF61_OP_MUL_W8 = 4,
+    FASTECC_GF61_OP_MUL_W8I = 5,
+    FASTECC_GF61_OP_MUL_W8_INV = 6,
+    FASTECC_GF61_OP_MUL_W8I_INV = 7,
+    FASTECC_GF61_OP_FOLD = 8,
+    FASTECC_GF61_OP_CANON = 9,
+    FASTECC_GF61_OP_RUN_DIF = 16,     /* + l, l = 0..3: l + 1 levels */
+    FASTECC_GF61_OP_RUN_DIF_INV = 20, /* + l */
+    FASTECC_GF61_OP_RUN_DIT = 24      /* + l */
+};
+int fastecc_gf61_binary(fastecc_ctx *ctx, int op, const uint64_t *x, const uint64_t *y, uint64_t *out, uint64_t count,
+                        void *stream);
 
 /*
  * Count the words of a stripe that are not field elements (>= p).  The reference documents "all words < p"
