@@ -108,6 +108,8 @@ def lib():
         f.argtypes, f.restype = [vp, vp, vp, u64, vp, u64, u8p, u64p], i32
     L.fastecc_update.argtypes, L.fastecc_update.restype = [vp, vp, vp, u64p, u64, vp, i32, vp], i32
     L.fastecc_update_parity.argtypes, L.fastecc_update_parity.restype = [vp, vp, u64p, u64, vp, vp, i32, vp], i32
+    L.fastecc_update_batch.argtypes, L.fastecc_update_batch.restype = [vp, vp, vp, u64, u64p, u64, vp, vp], i32
+    L.fastecc_update_parity_batch.argtypes, L.fastecc_update_parity_batch.restype = [vp, vp, u64, u64p, u64, vp, vp, vp], i32
     L.fastecc_code_coefficient.argtypes = [u64, u64, ctypes.c_uint, u64, u64, ctypes.POINTER(u32)]
     L.fastecc_code_coefficient.restype = i32
     L.fastecc_gf_berlekamp_massey.argtypes = [ctypes.POINTER(u32), u32, ctypes.POINTER(u32), u32]
@@ -375,6 +377,23 @@ class Encoder:
         count, arr = self._block_list(blocks)
         _check(lib().fastecc_update_parity(self._h, _addr(parity), arr, count, _addr(old), _addr(new), mem, stream or None),
                "fastecc_update_parity")
+        return parity
+
+    def update_batch(self, data, parity, count, writes, new, stream=0):
+        """Small writes into a pool of `count` stripes back to back in device memory (the layout of decode_batch): pool block
+        writes[u] = b * k + i (data block i of stripe b; distinct, any order) becomes row u of `new`, and every touched stripe's parity is
+        brought up to date — data and parity of those stripes then equal encode of the new stripe.  Other stripes are not touched."""
+        count = self._batch_count(count)
+        n, arr = self._block_list(writes)
+        _check(lib().fastecc_update_batch(self._h, _addr(data), _addr(parity), count, arr, n, _addr(new), stream or None), "fastecc_update_batch")
+        return data, parity
+
+    def update_parity_batch(self, parity, count, writes, new, old=None, stream=0):
+        """update_batch for the parity alone: pool blocks `writes` changed from row u of `old` (None: from zero) to row u of `new`."""
+        count = self._batch_count(count)
+        n, arr = self._block_list(writes)
+        _check(lib().fastecc_update_parity_batch(self._h, _addr(parity), count, arr, n, _addr(old), _addr(new), stream or None),
+               "fastecc_update_parity_batch")
         return parity
 
     def pack_blocks(self, raw, packed, stream=0, mem=MEM_DEVICE):

@@ -1,4 +1,5 @@
-// update.hip — small writes: fastecc_update, fastecc_update_parity, fastecc_code_coefficient (include/fastecc.h).
+// update.hip — small writes: fastecc_update, fastecc_update_parity, their pool forms fastecc_update_batch, fastecc_update_parity_batch, and
+// fastecc_code_coefficient (include/fastecc.h).
 //
 // The code is linear, so after data blocks i_u change by D_u = new_u - old_u the parity changes by
 //     parity[q][w] += sum_u L_{i_u}(y_q) * D_u[w]   (mod p),
@@ -16,6 +17,15 @@
 //                         rows of its slice into VGPRs once, then streams its parity blocks: T wave-uniform weights from G (scalar
 //                         loads behind one wait), T x V mac96 into 96-bit sums (lazy96.hpp), + the old parity word, one reduction, a
 //                         non-temporal store.  The next block's parity load is in flight during the current block's arithmetic.
+//
+// A pool of stripes stored back to back (fastecc_update_batch): G does not depend on the stripe, so nothing per stripe is
+// built.  The host sorts the writes by (stripe, block), cuts each stripe's writes into segments of at most ROWS, and uploads the sorted list and
+// the segment tables; the r-th segment of every stripe runs in round r (segments of one stripe read-modify-write the same parity blocks), one
+// launch per padded segment length T in {1, 2, 4, 8, 16}:
+//   update_batch_kernel  : a wave owns one segment, one column slice and one run of that stripe's parity blocks.  It forms D = new - old of its
+//                          <= T rows in VGPRs (no delta buffer) and streams its parity blocks exactly as update_parity_kernel does;
+//   update_scatter_kernel: after the last round, fastecc_update_batch only: new_blocks row u into its data block (several waves of the parity
+//                          kernel need the same old row, so the store waits for a later kernel on the same stream: no race, no flag).
 #include <algorithm>
 #include <atomic>
 #include <vector>
@@ -259,6 +269,138 @@ __global__ __launch_bounds__(256) void update_parity_kernel(const ParityArgs a)
     }
 }
 
+// ---- a pool of stripes (fastecc_update_batch / _update_parity_batch) ----
+constexpr int LIST_WORDS = 4;  // one write of the sorted list: position of its data block (i << e), its row of new_blocks, its stripe (low, high word)
+constexpr int SEG_HEAD = 2;    // one segment of a launch of class T: its first write in the sorted list, its number of writes (1 .. T), then the T
+                               // positions of its rows (rows past its length: that of row 0) — SEG_HEAD + T words
+
+struct BatchArgs {
+    uint32_t* parity;            // the pool's parity: stripe b's M blocks at parity + b * M * S
+    const uint32_t* data;        // fastecc_update_batch: the pool's data (old rows), stripe b's K blocks at data + b * K * S; else null
+    const uint32_t* old_blocks;  // fastecc_update_parity_batch: old rows by row of the caller's list (null: zero)
+    const uint32_t* new_blocks;  // new rows by row of the caller's list
+    const uint32_t* G;           // weight table (Montgomery form)
+    const uint32_t* list;        // the call's sorted writes, LIST_WORDS each
+    const uint32_t* segs;        // this launch's segments, SEG_HEAD + T words each
+    uint64_t S, K;
+    uint32_t M;                  // parity blocks per stripe
+    uint32_t slices;             // column slices of 64 V words
+    uint32_t run, runs;          // parity blocks per wave, runs per segment
+    uint32_t waves;              // segments of the launch x runs x slices
+    uint32_t e;                  // data block = position >> e
+    uint32_t NC, tshift;         // weight index = ((pos - d) mod NC) >> tshift
+    uint32_t qs, qmask, ps;      // pos(q) = off[q >> qs] + ((q & qmask) << ps)
+    uint32_t off[8];
+};
+
+// update_parity_kernel with the delta rows formed in registers and everything about the stripe read from the segment table and the write list
+// (wave-uniform: scalar loads).  Rows past the segment's length are zero and take the weight of row 0; they and dead lanes load from valid
+// addresses (row 0 of the segment, column 0), so the T row loads go out together without a branch.  All stripe offsets are 64-bit.
+template <int T, int V>
+__global__ __launch_bounds__(256) void update_batch_kernel(const BatchArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (wave >= a.waves) return;
+    const uint32_t slice = wave % a.slices, rest = wave / a.slices;
+    const uint32_t q0 = (rest % a.runs) * a.run, q1 = min(q0 + a.run, a.M);
+    const_u32_ptr seg = as_constant(a.segs) + (size_t)(rest / a.runs) * (SEG_HEAD + T);
+    const uint32_t len = seg[1];
+    const_u32_ptr list = as_constant(a.list) + (size_t)seg[0] * LIST_WORDS;
+    const uint64_t stripe = ((uint64_t)list[3] << 32) | list[2];
+    const uint64_t col = ((uint64_t)slice * 64u + lane) * V;
+    const bool live = col < a.S;  // (V > 1 only when S % V == 0: a live lane's V words all exist)
+    const uint64_t lcol = live ? col : 0;
+    const uint32_t bytes = (uint32_t)(a.S * 4u);
+    const uint32_t voff = live ? (uint32_t)col * 4u : bytes;  // (S * 4 < 2^32: update_batch_run)
+    // One form of the loop for the three sources of the old rows (no old rows: the new row once more, masked away), and masks instead of
+    // conditions: the row loads go out together, with no branch or wait between them.
+    const uint32_t omask = (a.data || a.old_blocks) ? 0xFFFFFFFFu : 0u;
+    const uint32_t* obase = a.data ? a.data : a.old_blocks ? a.old_blocks : a.new_blocks;
+    const uint64_t first_block = a.data ? stripe * a.K : 0;  // old row = block first_block + (data block | list row) of obase
+    const uint32_t dmask = a.data ? 0xFFFFFFFFu : 0u;
+    uint32_t x[T][V];
+    constexpr int H = T * V > 32 ? T / 2 : T;  // rows in flight together (both halves at once would hold 2 T V words beside x)
+#pragma unroll
+    for (int h = 0; h < T; h += H) {
+        uint32_t nv[H][V], ov[H][V];
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            const_u32_ptr wr = list + ((uint32_t)(h + i) < len ? h + i : 0) * LIST_WORDS;
+            const uint64_t nrow = (uint64_t)wr[1] * a.S;
+            const uint64_t orow = (first_block + (((wr[0] >> a.e) & dmask) | (wr[1] & ~dmask))) * a.S;
+            load_vec<V>(nv[i], a.new_blocks + nrow + lcol);
+            load_vec<V>(ov[i], obase + orow + lcol);
+        }
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            const uint32_t imask = (uint32_t)(h + i) < len ? 0xFFFFFFFFu : 0u;
+#pragma unroll
+            for (int v = 0; v < V; ++v) x[h + i][v] = gf::sub(nv[i][v], ov[i][v] & omask) & imask;
+        }
+    }
+    if (q0 >= q1) return;
+    const_u32_ptr G = as_constant(a.G);
+    const uint32_t* pbase = a.parity + stripe * a.M * a.S;
+    auto desc = [&](uint32_t q) { return block_desc(pbase + (uint64_t)q * a.S, bytes); };
+    auto step = [&](uint32_t q, const uint32_t (&old)[V]) {
+        const uint32_t pos = a.off[q >> a.qs] + ((q & a.qmask) << a.ps);
+        uint32_t w[T];
+#pragma unroll
+        for (int i = 0; i < T; ++i) {
+            int32_t u = (int32_t)(pos - seg[SEG_HEAD + i]);
+            if (u < 0) u += (int32_t)a.NC;
+            w[i] = G[(uint32_t)u >> a.tshift];
+        }
+        uint64_t lo[V];
+        uint32_t hi[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) lo[v] = 0, hi[v] = 0;
+#pragma unroll
+        for (int i = 0; i < T; ++i)
+#pragma unroll
+            for (int v = 0; v < V; ++v) mac96(lo[v], hi[v], x[i][v], w[i]);
+        uint32_t r[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) r[v] = gf::add(reduce96(lo[v], hi[v]), old[v]);
+        store_nt<V>(r, desc(q), voff);
+    };
+    const uint32_t last = q1 - 1;
+    uint32_t pa[V], pb[V];
+    load_nt<V>(pa, desc(q0), voff);
+    for (uint32_t q = q0; q < q1; q += 2) {
+        load_nt<V>(pb, desc(min(q + 1, last)), voff);
+        step(q, pa);
+        if (q + 1 > last) break;
+        load_nt<V>(pa, desc(min(q + 2, last)), voff);
+        step(q + 1, pb);
+    }
+}
+
+struct ScatterArgs {
+    uint32_t* data;
+    const uint32_t* new_blocks;
+    const uint32_t* list;  // the launch's first write
+    uint64_t S, K;
+    uint32_t slices, waves, e;
+};
+
+// wave (write, column slice): row u of new_blocks into data block (stripe, position >> e)
+template <int V>
+__global__ __launch_bounds__(256) void update_scatter_kernel(const ScatterArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (wave >= a.waves) return;
+    const_u32_ptr wr = as_constant(a.list) + (size_t)(wave / a.slices) * LIST_WORDS;
+    const uint64_t stripe = ((uint64_t)wr[3] << 32) | wr[2];
+    const uint64_t col = ((uint64_t)(wave % a.slices) * 64u + lane) * V;
+    if (col >= a.S) return;
+    uint32_t t[V];
+    load_vec<V>(t, a.new_blocks + (uint64_t)wr[1] * a.S + col);
+    store_vec<V>(a.data + (stripe * a.K + (wr[0] >> a.e)) * a.S + col, t);
+}
+
 }  // namespace
 
 struct UpdateState {
@@ -270,6 +412,13 @@ struct UpdateState {
     hipEvent_t table_event = nullptr;  // end of the table kernel (on table_stream)
     hipStream_t table_stream = nullptr;
     uint32_t* d_delta = nullptr;  // ROWS x S words (an internal buffer: ordered between streams by buf_event)
+    // fastecc_update_batch: one call's sorted write list and segment tables, written into the pinned h_list and copied to d_list on the call's
+    // stream.  d_list is an internal buffer like d_delta; h_list is free again once list_event (the end of that copy) has passed.
+    uint32_t* h_list = nullptr;
+    uint32_t* d_list = nullptr;
+    size_t list_cap = 0;  // words of each
+    hipEvent_t list_event = nullptr;
+    bool list_pending = false;
 };
 
 void destroy_update_state(UpdateState* s)
@@ -278,6 +427,9 @@ void destroy_update_state(UpdateState* s)
     if (s->d_G) (void)hipFree(s->d_G);
     if (s->d_delta) (void)hipFree(s->d_delta);
     if (s->table_event) (void)hipEventDestroy(s->table_event);
+    if (s->h_list) (void)hipHostFree(s->h_list);
+    if (s->d_list) (void)hipFree(s->d_list);
+    if (s->list_event) (void)hipEventDestroy(s->list_event);
     delete s;
 }
 
@@ -339,17 +491,29 @@ template <int V> const void* parity_kernel_v(int T)
     }
 }
 
-// waves of update_parity_kernel<T, V> one SIMD holds: 512 VGPRs in granules of 8, at most 8 (queried once per shape)
-int resident_waves_per_simd(int T, int V)
+template <int V> const void* batch_kernel_v(int T)
 {
-    static std::atomic<int> cache[3][5];  // zero-initialised (static storage)
+    switch (T) {
+        case 1: return (const void*)update_batch_kernel<1, V>;
+        case 2: return (const void*)update_batch_kernel<2, V>;
+        case 4: return (const void*)update_batch_kernel<4, V>;
+        case 8: return (const void*)update_batch_kernel<8, V>;
+        default: return (const void*)update_batch_kernel<ROWS, V>;
+    }
+}
+
+// waves of update_parity_kernel<T, V> (batch: update_batch_kernel<T, V>) one SIMD holds: 512 VGPRs in granules of 8, at most 8 (queried once per shape)
+int resident_waves_per_simd(int T, int V, bool batch = false)
+{
+    static std::atomic<int> cache[2][3][5];  // zero-initialised (static storage)
     const int vi = V == 4 ? 0 : V == 2 ? 1 : 2;
     int ti = 0;
     while ((1 << ti) < T) ti++;
-    std::atomic<int>& slot = cache[vi][ti];
+    std::atomic<int>& slot = cache[batch ? 1 : 0][vi][ti];
     if (!slot.load()) {
         hipFuncAttributes attr{};
-        const void* fn = V == 4 ? parity_kernel_v<4>(T) : V == 2 ? parity_kernel_v<2>(T) : parity_kernel_v<1>(T);
+        const void* fn = batch ? (V == 4 ? batch_kernel_v<4>(T) : V == 2 ? batch_kernel_v<2>(T) : batch_kernel_v<1>(T))
+                               : (V == 4 ? parity_kernel_v<4>(T) : V == 2 ? parity_kernel_v<2>(T) : parity_kernel_v<1>(T));
         int waves = 4;  // (if the query fails: a safe middle)
         if (hipFuncGetAttributes(&attr, fn) == hipSuccess && attr.numRegs > 0) waves = std::max(1, std::min(8, 512 / ((attr.numRegs + 7) / 8 * 8)));
         (void)hipGetLastError();
@@ -366,6 +530,27 @@ template <int V> void launch_parity_v(int T, const ParityArgs& a, dim3 grid, hip
         case 4: hipLaunchKernelGGL((update_parity_kernel<4, V>), grid, dim3(256), 0, st, a); break;
         case 8: hipLaunchKernelGGL((update_parity_kernel<8, V>), grid, dim3(256), 0, st, a); break;
         default: hipLaunchKernelGGL((update_parity_kernel<ROWS, V>), grid, dim3(256), 0, st, a); break;
+    }
+}
+
+// pos(q) of the code, in the form the two parity kernels evaluate it
+template <class Args> void set_positions(const UpdateState* s, Args& pa)
+{
+    const CodeGeom& g = s->g;
+    pa.NC = (uint32_t)s->NC;
+    pa.tshift = s->tshift;
+    if (g.cosets > 1) {  // N a power of two: coset t = q >> log2 N
+        int lgN = 0;
+        while ((1ull << lgN) < g.N) lgN++;
+        pa.qs = (uint32_t)lgN;
+        pa.qmask = (uint32_t)(g.N - 1);
+        pa.ps = (uint32_t)g.e;
+        for (int t = 0; t < g.cosets && t < 8; t++) pa.off[t] = (uint32_t)code_parity_position(g.N, g.e, g.fold, g.cosets, (uint64_t)t * g.N);
+    } else {
+        pa.qs = 31;  // q < 2^31: always entry 0
+        pa.qmask = 0xFFFFFFFFu;
+        pa.ps = (uint32_t)g.fold + 1u;
+        pa.off[0] = 1;
     }
 }
 
@@ -401,21 +586,7 @@ int update_pass(fastecc_ctx* c, UpdateState* s, uint32_t* data, uint32_t* parity
     pa.S = S;
     pa.M = (uint32_t)g.Mu;
     pa.rows = rows;
-    pa.NC = (uint32_t)s->NC;
-    pa.tshift = s->tshift;
-    if (g.cosets > 1) {  // N a power of two: coset t = q >> log2 N
-        int lgN = 0;
-        while ((1ull << lgN) < g.N) lgN++;
-        pa.qs = (uint32_t)lgN;
-        pa.qmask = (uint32_t)(g.N - 1);
-        pa.ps = (uint32_t)g.e;
-        for (int t = 0; t < g.cosets && t < 8; t++) pa.off[t] = (uint32_t)code_parity_position(g.N, g.e, g.fold, g.cosets, (uint64_t)t * g.N);
-    } else {
-        pa.qs = 31;  // q < 2^31: always entry 0
-        pa.qmask = 0xFFFFFFFFu;
-        pa.ps = (uint32_t)g.fold + 1u;
-        pa.off[0] = 1;
-    }
+    set_positions(s, pa);
     if (S * 4 + 64 * 16 > 0xFFFFFFFFull) return FASTECC_E_UNSUPPORTED;  // (blocks of 4 GiB: the kernel addresses a block through one buffer descriptor)
     int V = 4;
     while (V > 1 && ((S % V) != 0 || ((uintptr_t)parity & (4u * V - 1u)) != 0)) V >>= 1;
@@ -476,6 +647,217 @@ int update_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const uint64_t*
     });
 }
 
+
+// ---- a pool of stripes ----
+// What can be refused without the write list.  n_writes == 0 is decided by the caller (FASTECC_OK after these checks).
+int update_batch_args(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const uint64_t* writes, uint64_t n_writes, const void* old_blocks,
+                      const void* new_blocks, bool with_data)
+{
+    if (!c || count == 0) return FASTECC_E_INVAL;
+    if (n_writes > 0 && (!parity || !writes || !new_blocks || (with_data && !data))) return FASTECC_E_INVAL;
+    if ((((uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks) & 3u) != 0) return FASTECC_E_INVAL;
+    if (c->sharded || c->p61 || c->field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
+    if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;  // stripes of a pool are contiguous
+    const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
+    if (count > UINT64_MAX / data_bytes || count > UINT64_MAX / parity_bytes) return FASTECC_E_INVAL;
+    if ((with_data && (uint64_t)(uintptr_t)data > UINT64_MAX - count * data_bytes) || (uint64_t)(uintptr_t)parity > UINT64_MAX - count * parity_bytes)
+        return FASTECC_E_INVAL;
+    if (n_writes > UINT64_MAX / block) return FASTECC_E_INVAL;
+    if (n_writes > 0xFFFFFFFFull / (LIST_WORDS + SEG_HEAD + 1)) return FASTECC_E_UNSUPPORTED;  // (rows and list offsets are 32-bit: over 700 million writes in one call)
+    if (block + 64 * 16 > 0xFFFFFFFFull) return FASTECC_E_UNSUPPORTED;  // (blocks of 4 GiB: the kernel addresses a block through one buffer descriptor)
+    return FASTECC_OK;
+}
+
+struct SortedWrite {
+    uint64_t index;  // b * k + i
+    uint32_t row;    // its row of new_blocks / old_blocks
+};
+
+// The writes by (stripe, block), each with its row of the caller's blocks; FASTECC_E_INVAL for an index >= count * k or a duplicate
+int sort_writes(const fastecc_ctx* c, uint64_t count, const uint64_t* writes, uint64_t n_writes, std::vector<SortedWrite>& out)
+{
+    out.resize(n_writes);
+    for (uint64_t u = 0; u < n_writes; u++) out[u] = SortedWrite{writes[u], (uint32_t)u};
+    std::sort(out.begin(), out.end(), [](const SortedWrite& x, const SortedWrite& y) { return x.index < y.index; });
+    if (out.back().index >= count * c->K) return FASTECC_E_INVAL;  // (count * k fits: update_batch_args)
+    for (uint64_t u = 1; u < n_writes; u++)
+        if (out[u].index == out[u - 1].index) return FASTECC_E_INVAL;
+    return FASTECC_OK;
+}
+
+struct BatchLaunch {
+    int T;
+    uint32_t seg0, segs;  // its segment table: first word after the list, number of segments
+};
+
+// h_list / d_list for `words` words, h_list free to be written: a call whose predecessor's list is still on its way to the device waits for
+// that copy's event (not for the device); growing waits for the last use of the device buffer and allocates.
+int batch_list_buffers(fastecc_ctx* c, UpdateState* s, size_t words)
+{
+    if (!s->list_event) HIP_TRY(hipEventCreateWithFlags(&s->list_event, hipEventDisableTiming));
+    if (s->list_pending) {
+        HIP_TRY(hipEventSynchronize(s->list_event));
+        s->list_pending = false;
+    }
+    if (words <= s->list_cap) return FASTECC_OK;
+    const size_t cap = std::max<size_t>(std::max<size_t>(words, 2 * s->list_cap), 4096);
+    if (c->buf_used) HIP_TRY(hipEventSynchronize(c->buf_event));  // the kernels that read d_list
+    if (s->h_list) (void)hipHostFree(s->h_list);
+    if (s->d_list) (void)hipFree(s->d_list);
+    s->h_list = s->d_list = nullptr;
+    s->list_cap = 0;
+    HIP_TRY(hipHostMalloc((void**)&s->h_list, cap * 4, hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void**)&s->d_list, cap * 4));
+    s->list_cap = cap;
+    return FASTECC_OK;
+}
+
+template <int V> void launch_batch_v(int T, const BatchArgs& a, dim3 grid, hipStream_t st)
+{
+    switch (T) {
+        case 1: hipLaunchKernelGGL((update_batch_kernel<1, V>), grid, dim3(256), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((update_batch_kernel<2, V>), grid, dim3(256), 0, st, a); break;
+        case 4: hipLaunchKernelGGL((update_batch_kernel<4, V>), grid, dim3(256), 0, st, a); break;
+        case 8: hipLaunchKernelGGL((update_batch_kernel<8, V>), grid, dim3(256), 0, st, a); break;
+        default: hipLaunchKernelGGL((update_batch_kernel<ROWS, V>), grid, dim3(256), 0, st, a); break;
+    }
+}
+
+constexpr uint64_t LAUNCH_WAVES = 1ull << 24;  // a dispatch holds fewer than 2^32 work-items per dimension: at most 2^22 workgroups of 4 waves
+
+// sw: the call's writes, sorted and checked.  data == null: the parity form.
+int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std::vector<SortedWrite>& sw, const uint32_t* old_blocks, const uint32_t* new_blocks,
+                     hipStream_t st)
+{
+    UpdateState* s = nullptr;
+    int rc = update_state(c, &s);
+    if (rc != FASTECC_OK) return rc;
+    const uint64_t S = c->S, K = c->K, M = c->Mu, n = sw.size();
+    int V = 4;
+    const uintptr_t align = (uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks;  // every pointer a lane touches
+    while (V > 1 && ((S % V) != 0 || (align & (4u * V - 1u)) != 0)) V >>= 1;
+    const uint64_t slices = (S + 64u * V - 1) / (64u * V);
+    if (slices * M > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (one segment's waves fit a launch)
+    rc = batch_list_buffers(c, s, (size_t)n * (LIST_WORDS + SEG_HEAD + 1));  // (a segment of len writes takes SEG_HEAD + T <= 3 len words)
+    if (rc != FASTECC_OK) return rc;
+
+    // the list, and each stripe's writes cut into segments of at most ROWS: segment r of a stripe runs in round r, by padded length class
+    uint32_t* list = s->h_list;
+    std::vector<std::vector<uint32_t>> bucket;  // [round * 5 + class]: first write of each segment (its length: to the stripe's end, at most ROWS)
+    std::vector<uint32_t> stripe_end(n);        // per write: one past the last write of its stripe
+    for (uint64_t f = 0; f < n;) {
+        const uint64_t b = sw[f].index / K;
+        uint64_t g = f;
+        for (; g < n && sw[g].index < (b + 1) * K; g++) {
+            uint32_t* wr = list + g * LIST_WORDS;
+            wr[0] = (uint32_t)((sw[g].index - b * K) << s->g.e);
+            wr[1] = sw[g].row;
+            wr[2] = (uint32_t)b;
+            wr[3] = (uint32_t)(b >> 32);
+        }
+        for (uint64_t a0 = f, r = 0; a0 < g; a0 += ROWS, r++) {
+            int cls = 0;
+            while ((1u << cls) < std::min<uint64_t>(ROWS, g - a0)) cls++;
+            if (bucket.size() < (r + 1) * 5) bucket.resize((r + 1) * 5);
+            bucket[r * 5 + cls].push_back((uint32_t)a0);
+            stripe_end[a0] = (uint32_t)g;
+        }
+        f = g;
+    }
+    std::vector<BatchLaunch> launches;
+    uint32_t* segs = list + n * LIST_WORDS;
+    uint32_t seg_words = 0;
+    for (size_t i = 0; i < bucket.size(); i++) {
+        if (bucket[i].empty()) continue;
+        const int T = 1 << (int)(i % 5);
+        launches.push_back(BatchLaunch{T, seg_words, (uint32_t)bucket[i].size()});
+        for (uint32_t first : bucket[i]) {
+            const uint32_t len = std::min<uint32_t>(ROWS, stripe_end[first] - first);
+            uint32_t* seg = segs + seg_words;
+            seg[0] = first;
+            seg[1] = len;
+            for (int r = 0; r < T; r++) seg[SEG_HEAD + r] = list[(size_t)(first + ((uint32_t)r < len ? r : 0)) * LIST_WORDS];
+            seg_words += SEG_HEAD + T;
+        }
+    }
+
+    rc = update_table(c, s, st);
+    if (rc != FASTECC_OK) return rc;
+    return with_internal_buffers(c, st, [&]() -> int {
+        const size_t words = (size_t)n * LIST_WORDS + seg_words;
+        {
+            ProfScope ps(c, st, "update_batch_list", words * 4);
+            HIP_TRY(hipMemcpyAsync(s->d_list, s->h_list, words * 4, hipMemcpyHostToDevice, st));
+        }
+        HIP_TRY(hipEventRecord(s->list_event, st));
+        s->list_pending = true;
+        BatchArgs a{};
+        a.parity = parity;
+        a.data = data;
+        a.old_blocks = old_blocks;
+        a.new_blocks = new_blocks;
+        a.G = s->d_G;
+        a.list = s->d_list;
+        a.S = S;
+        a.K = K;
+        a.M = (uint32_t)M;
+        a.slices = (uint32_t)slices;
+        a.e = (uint32_t)s->g.e;
+        set_positions(s, a);
+        for (const BatchLaunch& l : launches) {
+            // at least every resident wave of the device, where the parity count allows it: runs of parity blocks per segment
+            const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(l.T, V, true);
+            const uint64_t per_run = (uint64_t)l.segs * slices;
+            const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>(M, (target + per_run - 1) / per_run));
+            a.run = (uint32_t)((M + want - 1) / want);
+            a.runs = (uint32_t)((M + a.run - 1) / a.run);
+            const uint64_t seg_waves = slices * a.runs, launch_segs = LAUNCH_WAVES / seg_waves;
+            ProfScope ps(c, st, "update_batch", (uint64_t)l.segs * M * S * 8);
+            for (uint64_t s0 = 0; s0 < l.segs; s0 += launch_segs) {
+                const uint64_t waves = std::min<uint64_t>(launch_segs, l.segs - s0) * seg_waves;
+                a.segs = s->d_list + n * LIST_WORDS + l.seg0 + (size_t)s0 * (SEG_HEAD + l.T);
+                a.waves = (uint32_t)waves;
+                const dim3 grid((unsigned)((waves + 3) / 4));
+                if (V == 4) launch_batch_v<4>(l.T, a, grid, st);
+                else if (V == 2) launch_batch_v<2>(l.T, a, grid, st);
+                else launch_batch_v<1>(l.T, a, grid, st);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        if (data) {
+            ScatterArgs sa{data, new_blocks, nullptr, S, K, (uint32_t)slices, 0, (uint32_t)s->g.e};
+            const uint64_t launch_writes = LAUNCH_WAVES / slices;
+            ProfScope ps(c, st, "update_scatter", n * S * 8);
+            for (uint64_t w0 = 0; w0 < n; w0 += launch_writes) {
+                const uint64_t waves = std::min<uint64_t>(launch_writes, n - w0) * slices;
+                sa.list = s->d_list + w0 * LIST_WORDS;
+                sa.waves = (uint32_t)waves;
+                const dim3 grid((unsigned)((waves + 3) / 4));
+                if (V == 4) hipLaunchKernelGGL(update_scatter_kernel<4>, grid, dim3(256), 0, st, sa);
+                else if (V == 2) hipLaunchKernelGGL(update_scatter_kernel<2>, grid, dim3(256), 0, st, sa);
+                else hipLaunchKernelGGL(update_scatter_kernel<1>, grid, dim3(256), 0, st, sa);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        return FASTECC_OK;
+    });
+}
+
+int update_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint64_t* writes, uint64_t n_writes, const void* old_blocks,
+                      const void* new_blocks, void* stream, bool with_data)
+{
+    int rc = update_batch_args(c, data, parity, count, writes, n_writes, old_blocks, new_blocks, with_data);
+    if (rc != FASTECC_OK || n_writes == 0) return rc;
+    std::vector<SortedWrite> sw;
+    rc = sort_writes(c, count, writes, n_writes, sw);
+    if (rc != FASTECC_OK) return rc;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallLock lk(c->mu);
+    return update_batch_run(c, with_data ? (uint32_t*)data : nullptr, (uint32_t*)parity, sw, (const uint32_t*)old_blocks, (const uint32_t*)new_blocks,
+                            (hipStream_t)stream);
+}
+
 }  // namespace
 
 }  // namespace fastecc
@@ -507,6 +889,17 @@ int fastecc_update_parity(fastecc_ctx* c, void* parity, const uint64_t* blocks, 
         CallLock lk(c->mu);
         return update_run(c, nullptr, (uint32_t*)parity, blocks, count, (const uint32_t*)old_blocks, (const uint32_t*)new_blocks, (hipStream_t)stream);
     });
+}
+
+int fastecc_update_batch(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint64_t* writes, uint64_t n_writes, const void* new_blocks, void* stream)
+{
+    return guarded([&]() -> int { return update_batch_impl(c, data, parity, count, writes, n_writes, nullptr, new_blocks, stream, true); });
+}
+
+int fastecc_update_parity_batch(fastecc_ctx* c, void* parity, uint64_t count, const uint64_t* writes, uint64_t n_writes, const void* old_blocks,
+                                const void* new_blocks, void* stream)
+{
+    return guarded([&]() -> int { return update_batch_impl(c, nullptr, parity, count, writes, n_writes, old_blocks, new_blocks, stream, false); });
 }
 
 int fastecc_code_coefficient(uint64_t n, uint64_t k, unsigned flags, uint64_t data_block, uint64_t parity_block, uint32_t* out)

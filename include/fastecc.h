@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 331 /* 0.3.3.1: fastecc_gf61_binary, a probe of the 64-bit field's device arithmetic for tests */
+#define FASTECC_VERSION 340 /* 0.3.4: fastecc_update_batch, fastecc_update_parity_batch (small writes into a pool of stripes) */
 
 enum {
     FASTECC_OK = 0,
@@ -464,6 +464,37 @@ int fastecc_update(fastecc_ctx *ctx, void *data, void *parity, const uint64_t *b
                    int mem_kind, void *stream);
 int fastecc_update_parity(fastecc_ctx *ctx, void *parity, const uint64_t *blocks, uint64_t count, const void *old_blocks,
                           const void *new_blocks, int mem_kind, void *stream);
+/*
+ * Small writes into a pool: many stripes stored back to back in DEVICE memory, the layout of fastecc_decode_batch — stripe b's k data
+ * blocks at data + b*k*block_bytes, its n - k parity blocks at parity + b*(n-k)*block_bytes, `count` stripes.  There is no mem_kind.
+ *   writes     : a host array of n_writes DISTINCT pool block indices in any order; writes[u] = b*k + i is data block i of stripe b.  It
+ *                may be reused as soon as the call returns.
+ *   new_blocks : n_writes contiguous blocks in device memory, row u for writes[u].  old_blocks (the parity form): the same shape, the
+ *                blocks' previous content; NULL means zero blocks (incremental encoding, as for fastecc_update_parity).
+ *   fastecc_update_batch        : every touched stripe's data and parity become, bit for bit, what fastecc_encode gives for the new
+ *                                 stripe — the result of fastecc_update on each touched stripe with its own writes.
+ *   fastecc_update_parity_batch : the same for the parity alone; the data blocks live elsewhere.
+ * A stripe that no write names is neither read nor written: it may hold anything, words >= p included.  Inputs of touched stripes must
+ * be < p; new_blocks / old_blocks must not overlap data or parity.  Every GF(0xFFF00001) code fastecc_update takes: (2k,k),
+ * n = k + N/2^d, n = 4k / 8k, zero-extended (n,k), mixed radix and PFA.  n_writes == 0 with otherwise valid arguments is a no-op.
+ * FASTECC_E_INVAL, before any device work: a null context, count == 0, a null parity, writes or new_blocks (or data, for
+ * fastecc_update_batch) with n_writes > 0, pointers that are not 4-byte aligned, an index >= count*k, a duplicate index, byte sizes
+ * beyond 64 bits.  FASTECC_E_UNSUPPORTED: GF((2^61-1)^2), sharded contexts, a set "row_pitch_words" (and more than (2^32 - 1) / 7 writes in
+ * one call).  A refused call writes nothing.
+ * Method: the weight table of fastecc_update serves every stripe, so nothing per stripe is built.  The host sorts
+ * the writes by (stripe, block) and cuts each stripe's writes into segments of at most 16; segment r of every stripe runs in round r, one
+ * launch per padded segment length (1, 2, 4, 8, 16) — the usual pool write, one block per stripe, is ONE launch for the parity plus one
+ * that stores the new blocks (fastecc_update_batch only).
+ * Streams: enqueued on `stream`; steady-state calls do not synchronise the device.  The sorted list travels through a pinned host
+ * buffer and a device buffer owned by the context, both grown on demand: the first call, and a call with a longer list than any before,
+ * allocate and may therefore synchronise.  A call made while the previous call's list is still on its way to the device waits on the host
+ * for that copy (an event), not for the device; the copy is itself enqueued on its call's stream, behind the work enqueued there before
+ * it, so the host runs at most one call ahead of the device.  Because of this host staging the calls cannot be captured into a hipGraph.
+ */
+int fastecc_update_batch(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, const uint64_t *writes, uint64_t n_writes,
+                         const void *new_blocks, void *stream);
+int fastecc_update_parity_batch(fastecc_ctx *ctx, void *parity, uint64_t count, const uint64_t *writes, uint64_t n_writes,
+                                const void *old_blocks, const void *new_blocks, void *stream);
 /* Host only, no device: the code's generator-matrix entry L_i(y_q) for data block i and parity block q of the (n,k) code that
  * fastecc_create_ex(n, k, ..., flags) builds over GF(0xFFF00001), plain form in [0,p): parity block q = sum_i L_i(y_q) data block i.
  * FASTECC_E_INVAL for a null out, an index out of range or unknown flags; FASTECC_E_UNSUPPORTED for a code fastecc_create_ex refuses. */
