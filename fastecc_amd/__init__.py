@@ -98,6 +98,7 @@ def lib():
     L.fastecc_repair.argtypes, L.fastecc_repair.restype = [vp, vp, vp, i32, vp], i32
     L.fastecc_decode_batch.argtypes, L.fastecc_decode_batch.restype = [vp, vp, vp, u64, vp], i32
     L.fastecc_repair_batch.argtypes, L.fastecc_repair_batch.restype = [vp, vp, vp, u64, vp], i32
+    L.fastecc_scrub_erasures.argtypes, L.fastecc_scrub_erasures.restype = [vp, u8p, u8p], i32
     L.fastecc_verify.argtypes, L.fastecc_verify.restype = [vp, vp, vp, i32, vp, u64, ctypes.POINTER(i32)], i32
     for name in ("locate_errors", "correct"):
         f = getattr(L, "fastecc_" + name)
@@ -270,16 +271,21 @@ class Encoder:
         """Erasure pattern: k data flags and n - k parity flags (truthy = the block survives)."""
         if len(data_present) != self.k or len(parity_present) != self.n - self.k:
             raise ValueError("need k data flags and n - k parity flags")
-        def flags(v, count):
-            # a contiguous uint8 numpy array goes through as it is (the C ABI takes plain byte arrays); anything else is converted
-            if hasattr(v, "ctypes") and getattr(v, "dtype", None) is not None and v.dtype.itemsize == 1 and v.flags["C_CONTIGUOUS"]:
-                return v, ctypes.cast(v.ctypes.data, ctypes.POINTER(ctypes.c_uint8))
-            arr = (ctypes.c_uint8 * count)(*[1 if x else 0 for x in v])
-            return arr, arr
-        keep_d, dp = flags(data_present, self.k)
-        keep_p, pp = flags(parity_present, self.n - self.k)
+        keep_d, dp = self._flags(data_present, self.k)
+        keep_p, pp = self._flags(parity_present, self.n - self.k)
         _check(lib().fastecc_decode_prepare(self._h, dp, pp), "fastecc_decode_prepare")
         del keep_d, keep_p
+
+    @staticmethod
+    def _flags(v, count):
+        """(object to keep alive, uint8 pointer) of `count` presence flags; None stays a null pointer."""
+        if v is None:
+            return None, None
+        # a contiguous uint8 numpy array goes through as it is (the C ABI takes plain byte arrays); anything else is converted
+        if hasattr(v, "ctypes") and getattr(v, "dtype", None) is not None and v.dtype.itemsize == 1 and v.flags["C_CONTIGUOUS"]:
+            return v, ctypes.cast(v.ctypes.data, ctypes.POINTER(ctypes.c_uint8))
+        arr = (ctypes.c_uint8 * count)(*[1 if x else 0 for x in v])
+        return arr, arr
 
     def decode(self, data, parity, stream=0, mem=MEM_DEVICE):
         """Recover the erased data blocks in place (README.md:102-119); parity is read only."""
@@ -311,8 +317,23 @@ class Encoder:
         _check(lib().fastecc_repair_batch(self._h, _addr(data), _addr(parity), count, stream or None), "fastecc_repair_batch")
         return data, parity
 
+    def scrub_erasures(self, data_present=None, parity_present=None):
+        """Name the blocks that are known to be absent (a device is down) for verify, locate_errors, correct and their batched forms:
+        k data flags and n - k parity flags, truthy = present, None = every block of that part is present; both None clears the
+        pattern.  Absent blocks are never read; correct rebuilds them together with the blocks it locates.  Independent of the
+        decode_prepare pattern."""
+        if data_present is not None and len(data_present) != self.k:
+            raise ValueError("need k data flags")
+        if parity_present is not None and len(parity_present) != self.n - self.k:
+            raise ValueError("need n - k parity flags")
+        keep_d, dp = self._flags(data_present, self.k)
+        keep_p, pp = self._flags(parity_present, self.n - self.k)
+        _check(lib().fastecc_scrub_erasures(self._h, dp, pp), "fastecc_scrub_erasures")
+        del keep_d, keep_p
+
     def verify(self, data, parity, seed=0, stream=0, mem=MEM_DEVICE):
-        """True iff every word is < p and the k data + n - k parity blocks form a codeword (fingerprints drawn from `seed`)."""
+        """True iff every word of every present block is < p and the present blocks of the k data + n - k parity blocks agree with a
+        codeword (fingerprints drawn from `seed`; every block is present unless scrub_erasures named some absent)."""
         ok = ctypes.c_int()
         _check(lib().fastecc_verify(self._h, _addr(data), _addr(parity), mem, stream or None, seed, ctypes.byref(ok)), "fastecc_verify")
         return bool(ok.value)

@@ -23,6 +23,8 @@
 //   root search         : Lambda(w^u) by Horner at every position on the device;
 //   confirmation        : the syndromes once more with the located positions erased must all vanish, in every column.
 // fastecc_correct then hands the located blocks to fastecc_decode_prepare + fastecc_repair.
+// fastecc_scrub_erasures names blocks that are absent: the fingerprint kernels skip them, their locator joins the
+// fixed erasures' in a table cached per pattern, w fewer syndromes are checked, and fastecc_correct rebuilds them with the located blocks.
 // fastecc_verify_batch / _correct_batch run the verify over many stripes at once: the stripe index becomes extra word columns of
 // the fingerprint stripe, so one transform serves a whole chunk of stripes (fingerprint_batch_kernel, syndrome_batch_kernel, verify_batch_locked).
 #include <algorithm>
@@ -139,8 +141,12 @@ __device__ __forceinline__ void block_fingerprint(const uint32_t* __restrict__ b
     f[2] = reduce64(a2);
 }
 
+// pos[j] of a block the caller named absent (fastecc_scrub_erasures) carries this mark: the block is not read
+constexpr uint32_t ABSENT = 0x80000000u;
+
 // One wave per block (blocks wave, wave + waves, ...).  F[pos[j] * 4 + c] receives the block's fingerprint c; a block with a word >= p
-// is appended to bad[1 ..] (bad[0] counts them).
+// is appended to bad[1 ..] (bad[0] counts them).  An absent block is skipped (j and pos[j] are wave-uniform: no lane diverges) and its
+// F keeps whatever an earlier call left: the weigh pass multiplies it by a locator that is zero there.
 template <bool VEC>
 __global__ __launch_bounds__(256) void fingerprint_kernel(const uint32_t* __restrict__ data, const uint32_t* __restrict__ parity, uint32_t k_blocks,
                                                           uint32_t n_blocks, uint32_t S, const uint2* __restrict__ wt, const uint32_t* __restrict__ pos,
@@ -150,12 +156,14 @@ __global__ __launch_bounds__(256) void fingerprint_kernel(const uint32_t* __rest
     const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     const uint32_t waves = (gridDim.x * blockDim.x) >> 6;
     for (uint32_t j = wave; j < n_blocks; j += waves) {
+        const uint32_t u = pos[j];
+        if (u & ABSENT) continue;
         const uint32_t* blk = j < k_blocks ? data + (size_t)j * S : parity + (size_t)(j - k_blocks) * S;
         uint32_t fp[R];
         bool any_big;
         block_fingerprint<VEC>(blk, S, wt, lane, fp, any_big);
         if (lane == 0) {
-            uint32_t* f = F + (size_t)pos[j] * RW;
+            uint32_t* f = F + (size_t)u * RW;
             f[0] = fp[0];
             f[1] = fp[1];
             f[2] = fp[2];
@@ -168,9 +176,11 @@ __global__ __launch_bounds__(256) void fingerprint_kernel(const uint32_t* __rest
 }
 
 // fastecc_verify_batch: the same per block over the B stripes [b0, b0 + B) of a batch, global block g = b * n + j (stripe b - b0 of the chunk, block j;
-// both wave-uniform).  Fingerprint c of that block, times the fixed erasures' locator at its position (lfix, null: 1), lands in
+// both wave-uniform).  Fingerprint c of that block, times the locator of the fixed and the named erasures at its position (lfix, null: 1), lands in
 // F[pos[j] * row + (b - b0) * 4 + c] — the chunk's stripes are word columns of one fingerprint stripe of NC rows.  A block with a word >= p
-// sets flag[b] (a plain store of 1: idempotent, no atomics).  At most 80 VGPRs: six waves per SIMD, the grid the host launches all resident.
+// sets flag[b] (a plain store of 1: idempotent, no atomics).  An absent block (pos[j] marked; wave-uniform) is not read and its entry is stored
+// as zero: nothing multiplies F by the locator afterwards, and the entry may hold another call's or another pattern's value.
+// At most 80 VGPRs: six waves per SIMD, the grid the host launches all resident.
 template <bool VEC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void fingerprint_batch_kernel(const uint32_t* __restrict__ data, const uint32_t* __restrict__ parity, uint32_t k_blocks,
                                                                 uint32_t n_blocks, uint32_t S, uint64_t b0, uint64_t B, const uint2* __restrict__ wt,
@@ -186,12 +196,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void f
         const uint64_t bl = g / n_blocks;
         const uint32_t j = (uint32_t)(g - bl * n_blocks);
         const uint64_t b = b0 + bl;
+        const uint32_t u = pos[j];
+        if (u & ABSENT) {
+            if (lane == 0) *reinterpret_cast<uint4*>(F + (uint64_t)(u & ~ABSENT) * row + bl * RW) = make_uint4(0, 0, 0, 0);
+            continue;
+        }
         const uint32_t* blk = j < k_blocks ? data + (b * k_blocks + j) * S : parity + (b * m_blocks + (j - k_blocks)) * S;
         uint32_t fp[R];
         bool any_big;
         block_fingerprint<VEC>(blk, S, wt, lane, fp, any_big);
         if (lane == 0) {
-            const uint32_t u = pos[j];
             const uint32_t l = lfix ? lfix[u] : 1u;
             uint32_t* f = F + (uint64_t)u * row + bl * RW;
             f[0] = gf::mul(fp[0], l);
@@ -304,6 +318,11 @@ struct ScrubState {
     uint32_t* d_GB = nullptr;               // their transform
     uint8_t* d_flag = nullptr;              // one byte per stripe of the call: 1 = inconsistent
     uint64_t flag_cap = 0;
+    // fastecc_scrub_erasures: the blocks the caller named absent (none: empty / null)
+    std::vector<uint32_t> absent;           // their codeword indices, increasing
+    std::vector<uint8_t> is_absent;         // n flags
+    uint32_t* d_pos_named = nullptr;        // n words: d_pos with ABSENT set at those blocks
+    uint32_t* d_lnamed = nullptr;           // NC words: d_lfix (or 1) times the locator of their positions at w^u
 };
 
 void destroy_scrub_state(ScrubState* s)
@@ -312,12 +331,26 @@ void destroy_scrub_state(ScrubState* s)
     if (s->ntt) fastecc_destroy(s->ntt);
     if (s->ntt_batch) fastecc_destroy(s->ntt_batch);
     for (void* p : {(void*)s->d_pos, (void*)s->d_wpow, (void*)s->d_lfix, (void*)s->d_F, (void*)s->d_G, (void*)s->d_small, (void*)s->d_weights, (void*)s->d_FB,
-                    (void*)s->d_GB, (void*)s->d_flag})
+                    (void*)s->d_GB, (void*)s->d_flag, (void*)s->d_pos_named, (void*)s->d_lnamed})
         if (p) (void)hipFree(p);
     delete s;
 }
 
 namespace {
+
+// What a scrub call erases up front besides the known-bad blocks: the position table its fingerprint pass reads, the locator of
+// those erasures at every position (null: 1) and the number of named ones (the fixed ones are counted by ScrubState::fixed).
+struct Erasures {
+    const uint32_t* d_pos;
+    const uint32_t* d_loc;
+    uint64_t w;
+};
+
+Erasures erasures(const ScrubState* s, bool named)
+{
+    if (named && !s->absent.empty()) return {s->d_pos_named, s->d_lnamed, s->absent.size()};
+    return {s->d_pos, s->d_lfix, 0};
+}
 
 int scrub_args(fastecc_ctx* c, const void* data, const void* parity, int mem_kind)
 {
@@ -459,24 +492,24 @@ int upload_weights(fastecc_ctx* c, ScrubState* s, uint64_t seed, hipStream_t st)
     return FASTECC_OK;
 }
 
-// The fingerprint pass; the blocks holding a word >= p come back sorted in `bad` (b > bad_cap - 1: *overflow).
-int fingerprints(fastecc_ctx* c, ScrubState* s, const Small& sm, const uint32_t* data, const uint32_t* parity, uint64_t seed, hipStream_t st,
-                 std::vector<uint32_t>& bad)
+// The fingerprint pass over the blocks `er` does not name absent; those holding a word >= p come back sorted in `bad` (b > bad_cap - 1: *overflow).
+int fingerprints(fastecc_ctx* c, ScrubState* s, const Small& sm, const Erasures& er, const uint32_t* data, const uint32_t* parity, uint64_t seed,
+                 hipStream_t st, std::vector<uint32_t>& bad)
 {
     int rc = upload_weights(c, s, seed, st);
     if (rc != FASTECC_OK) return rc;
     HIP_TRY(hipMemsetAsync(sm.bad, 0, 4, st));
     const bool vec = (c->S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
-    // every workgroup resident at once (6 waves per SIMD at 77 VGPRs): a grid-stride loop over the blocks without a tail wave of late groups
+    // every workgroup resident at once (6 waves per SIMD; its 72 VGPRs would fit a seventh): a grid-stride loop over the blocks without a tail wave of late groups
     const uint64_t groups = std::min<uint64_t>((s->n + 3) / 4, (uint64_t)c->cus * 6);
     {
-        ProfScope ps(c, st, "fingerprint", s->n * c->S * 4);
+        ProfScope ps(c, st, "fingerprint", (s->n - er.w) * c->S * 4);
         if (vec)
             hipLaunchKernelGGL(fingerprint_kernel<true>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)c->S,
-                               s->d_weights, s->d_pos, s->d_F, sm.bad, (uint32_t)sm.bad_cap);
+                               s->d_weights, er.d_pos, s->d_F, sm.bad, (uint32_t)sm.bad_cap);
         else
             hipLaunchKernelGGL(fingerprint_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)c->S,
-                               s->d_weights, s->d_pos, s->d_F, sm.bad, (uint32_t)sm.bad_cap);
+                               s->d_weights, er.d_pos, s->d_F, sm.bad, (uint32_t)sm.bad_cap);
         HIP_TRY(hipGetLastError());
     }
     uint32_t nb = 0;
@@ -489,13 +522,14 @@ int fingerprints(fastecc_ctx* c, ScrubState* s, const Small& sm, const uint32_t*
     return FASTECC_OK;
 }
 
-// Syndromes of the fingerprints with the positions `erased` (besides the fixed ones) erased: *nonzero = some coefficient above the
-// degree bound is not zero in some column; the first `gather` of each column land in syn (host) if gather > 0.
-int syndromes(fastecc_ctx* c, ScrubState* s, const Small& sm, const std::vector<uint32_t>& erased, uint64_t gather, hipStream_t st, bool* nonzero,
-              std::vector<uint32_t>* syn)
+// Syndromes of the fingerprints with the fixed positions, the named ones of `er` (both through er.d_loc, the cached locator the product
+// starts from) and then the positions `erased` erased: *nonzero = some coefficient above the degree bound is not zero in some column; the
+// first `gather` of each column land in syn (host) if gather > 0.
+int syndromes(fastecc_ctx* c, ScrubState* s, const Small& sm, const Erasures& er, const std::vector<uint32_t>& erased, uint64_t gather, hipStream_t st,
+              bool* nonzero, std::vector<uint32_t>* syn)
 {
     const uint64_t NC = s->NC;
-    const uint64_t m_lo = s->N + s->fixed + erased.size();
+    const uint64_t m_lo = s->N + s->fixed + er.w + erased.size();
     *nonzero = false;
     if (m_lo >= NC) return FASTECC_OK;  // nothing left to check: every set of n - k erasures explains any word
     if (erased.size() > sm.roots_cap) return FASTECC_E_INVAL;
@@ -506,7 +540,7 @@ int syndromes(fastecc_ctx* c, ScrubState* s, const Small& sm, const std::vector<
     auto grid = [](uint64_t items) { return dim3((unsigned)((items + 255) / 256)); };
     {
         ProfScope ps(c, st, "scrub_weigh");
-        hipLaunchKernelGGL(locator_kernel<true>, grid(NC), dim3(256), 0, st, s->d_lfix, sm.roots, (uint32_t)pts.size(), s->d_wpow, (uint32_t)NC, s->d_F, s->d_G);
+        hipLaunchKernelGGL(locator_kernel<true>, grid(NC), dim3(256), 0, st, er.d_loc, sm.roots, (uint32_t)pts.size(), s->d_wpow, (uint32_t)NC, s->d_F, s->d_G);
         HIP_TRY(hipGetLastError());
     }
     {
@@ -566,18 +600,22 @@ int berlekamp_massey(const uint32_t* s, uint32_t count, std::vector<uint32_t>& C
     return (int)L;
 }
 
-// fastecc_locate_errors on a locked context: the sorted codeword indices of the corrupted blocks, or FASTECC_E_UNCORRECTABLE
-int locate(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t seed, hipStream_t st, std::vector<uint32_t>& result, bool verify_only)
+// fastecc_locate_errors on a locked context: the sorted codeword indices of the corrupted blocks, or FASTECC_E_UNCORRECTABLE.  named: the
+// blocks fastecc_scrub_erasures named absent are erased and not read (they come back in *absent if asked for); else every block is read.
+int locate(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t seed, hipStream_t st, std::vector<uint32_t>& result, bool verify_only,
+           bool named = true, std::vector<uint32_t>* absent = nullptr)
 {
     ScrubState* s = nullptr;
     int rc = scrub_state(c, &s);
     if (rc != FASTECC_OK) return rc;
+    const Erasures er = erasures(s, named);
+    if (absent) absent->assign(s->absent.begin(), s->absent.begin() + er.w);
     const uint32_t tmax = (uint32_t)c->locate_max;
     Small sm;
     rc = small_buffers(s, tmax, &sm);
     if (rc != FASTECC_OK) return rc;
     std::vector<uint32_t> bad;
-    rc = fingerprints(c, s, sm, data, parity, seed, st, bad);
+    rc = fingerprints(c, s, sm, er, data, parity, seed, st, bad);
     if (rc != FASTECC_OK) return rc;
     const uint64_t m = s->n - s->k;
     result.clear();
@@ -587,19 +625,19 @@ int locate(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_
             return FASTECC_OK;
         }
         bool nonzero = false;
-        rc = syndromes(c, s, sm, {}, 0, st, &nonzero, nullptr);
+        rc = syndromes(c, s, sm, er, {}, 0, st, &nonzero, nullptr);
         if (rc != FASTECC_OK) return rc;
         if (nonzero) result.push_back(~0u);
         return FASTECC_OK;
     }
-    if (bad.size() > m) return FASTECC_E_UNCORRECTABLE;  // more known erasures than parity blocks
+    if (bad.size() + er.w > m) return FASTECC_E_UNCORRECTABLE;  // more known erasures than parity blocks
     std::vector<uint32_t> erased(bad.size());
     for (size_t i = 0; i < bad.size(); i++) erased[i] = s->pos[bad[i]];
-    const uint64_t avail = m - bad.size();  // syndromes left after the known erasures
+    const uint64_t avail = m - er.w - bad.size();  // syndromes left after the known erasures
     bool nonzero = false;
     std::vector<uint32_t> syn;
     const uint64_t gather = std::min<uint64_t>(2ull * tmax, avail);
-    rc = syndromes(c, s, sm, erased, gather, st, &nonzero, &syn);
+    rc = syndromes(c, s, sm, er, erased, gather, st, &nonzero, &syn);
     if (rc != FASTECC_OK) return rc;
     if (nonzero) {
         // the locator: the longest of the columns' LFSRs (a column may miss an error with probability <= 2^-20; the check below covers all)
@@ -629,12 +667,12 @@ int locate(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_
         HIP_TRY(hipMemcpy(roots.data(), sm.found + 1, nf * 4, hipMemcpyDeviceToHost));
         for (uint32_t u : roots) {
             const uint32_t j = s->block_at[u];
-            if (j == ~0u || std::binary_search(bad.begin(), bad.end(), j)) return FASTECC_E_UNCORRECTABLE;  // no block there, or one already erased
+            if (j == ~0u || std::binary_search(bad.begin(), bad.end(), j) || (er.w && s->is_absent[j])) return FASTECC_E_UNCORRECTABLE;  // no block there, or one already erased
             erased.push_back(u);
             result.push_back(j);
         }
         // confirmation: with the located blocks erased too, every syndrome of every column vanishes
-        rc = syndromes(c, s, sm, erased, 0, st, &nonzero, nullptr);
+        rc = syndromes(c, s, sm, er, erased, 0, st, &nonzero, nullptr);
         if (rc != FASTECC_OK) return rc;
         if (nonzero) return FASTECC_E_UNCORRECTABLE;
     }
@@ -687,8 +725,9 @@ int batch_state(fastecc_ctx* c, ScrubState* s)
 }
 
 // fastecc_verify_batch on a locked context: flag[b] = 1 iff fastecc_verify with this seed would find stripe b inconsistent.  Per chunk of B
-// stripes: the fingerprints (weighed by the fixed erasures' locator as they are stored), one transform of NC points over 4B word columns,
-// the syndrome check of every stripe; then one copy of the flags and one synchronisation for the whole call.
+// stripes: the fingerprints (weighed by the locator of the fixed and the named erasures as they are stored; absent blocks are not read and
+// store zero), one transform of NC points over 4B word columns, the syndrome check of every stripe from coefficient N + fixed + w on; then
+// one copy of the flags and one synchronisation for the whole call.
 int verify_batch_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, uint64_t seed, hipStream_t st, std::vector<uint8_t>& flag)
 {
     ScrubState* s = nullptr;
@@ -705,27 +744,29 @@ int verify_batch_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* pa
     if ((rc = upload_weights(c, s, seed, st)) != FASTECC_OK) return rc;
     HIP_TRY(hipMemsetAsync(s->d_flag, 0, count, st));
     const uint64_t chunk = c->scrub_batch_chunk > 0 ? std::min<uint64_t>(s->batch_cap, (uint64_t)c->scrub_batch_chunk) : s->batch_cap;
-    const uint64_t row = RW * s->batch_cap, NC = s->NC, m_lo = s->N + s->fixed, S = c->S;
+    const Erasures er = erasures(s, true);
+    const uint64_t row = RW * s->batch_cap, NC = s->NC, m_lo = s->N + s->fixed + er.w, S = c->S;
     const bool vec = (S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
     for (uint64_t b0 = 0; b0 < count; b0 += chunk) {
         const uint64_t B = std::min(chunk, count - b0);
         // every workgroup resident at once, as for one stripe
         const uint64_t groups = std::min<uint64_t>((B * s->n + 3) / 4, (uint64_t)c->cus * 6);
         {
-            ProfScope ps(c, st, "fingerprint_batch", B * s->n * S * 4);
+            ProfScope ps(c, st, "fingerprint_batch", B * (s->n - er.w) * S * 4);
             if (vec)
                 hipLaunchKernelGGL(fingerprint_batch_kernel<true>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)S,
-                                   b0, B, s->d_weights, s->d_pos, s->d_lfix, s->d_FB, row, s->d_flag);
+                                   b0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, s->d_flag);
             else
                 hipLaunchKernelGGL(fingerprint_batch_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)S,
-                                   b0, B, s->d_weights, s->d_pos, s->d_lfix, s->d_FB, row, s->d_flag);
+                                   b0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, s->d_flag);
             HIP_TRY(hipGetLastError());
         }
+        if (m_lo >= NC) continue;  // n - k blocks named absent: no coefficient is left to check, only the words >= p count
         {
             ProfScope ps(c, st, "scrub_transform_batch");
             if ((rc = transform_bitrev(s->ntt_batch, s->d_FB, s->d_GB, false, true, (uint32_t)(RW * B), st)) != FASTECC_OK) return rc;
         }
-        if (m_lo < NC) {  // (always: n > k)
+        {
             ProfScope ps(c, st, "scrub_syndromes_batch");
             const uint64_t items = (NC - m_lo) * B;  // <= NC * batch_cap <= 2^21
             hipLaunchKernelGGL(syndrome_batch_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, s->d_GB, s->lgc, (uint32_t)NC, (uint32_t)m_lo, row,
@@ -737,6 +778,70 @@ int verify_batch_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* pa
     HIP_TRY(hipMemcpyAsync(flag.data(), s->d_flag, count, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return FASTECC_OK;
+}
+
+// fastecc_scrub_erasures on a locked context: `absent` (codeword indices, increasing, at most n - k) replaces the named pattern.  The marked
+// position table and the locator table lfix * prod (x - w^pos) are built aside and swapped in, so a failure leaves the previous pattern in
+// force.  Synchronous; every scrub call ends with a synchronise, so nothing in flight reads the tables that are freed here.
+int set_erasures(fastecc_ctx* c, const std::vector<uint32_t>& absent)
+{
+    ScrubState* s = c->scrub;
+    uint32_t *d_pos = nullptr, *d_loc = nullptr, *d_roots = nullptr;
+    std::vector<uint8_t> is_absent;
+    if (!absent.empty()) {
+        const int rc = scrub_state(c, &s);
+        if (rc != FASTECC_OK) return rc;
+        std::vector<uint32_t> pos(s->pos), roots(absent.size());
+        is_absent.assign(s->n, 0);
+        const uint32_t w = gf::h_root((uint32_t)s->NC);
+        for (size_t i = 0; i < absent.size(); i++) {
+            roots[i] = gf::h_pow(w, s->pos[absent[i]]);
+            pos[absent[i]] |= ABSENT;
+            is_absent[absent[i]] = 1;
+        }
+        hipError_t he = hipMalloc((void**)&d_pos, s->n * 4);
+        if (he == hipSuccess) he = hipMalloc((void**)&d_loc, s->NC * 4);
+        if (he == hipSuccess) he = hipMalloc((void**)&d_roots, roots.size() * 4);
+        if (he == hipSuccess) he = hipMemcpy(d_pos, pos.data(), s->n * 4, hipMemcpyHostToDevice);
+        if (he == hipSuccess) he = hipMemcpy(d_roots, roots.data(), roots.size() * 4, hipMemcpyHostToDevice);
+        if (he == hipSuccess) {
+            hipLaunchKernelGGL(locator_kernel<false>, dim3((unsigned)((s->NC + 255) / 256)), dim3(256), 0, nullptr, s->d_lfix, d_roots, (uint32_t)roots.size(),
+                               s->d_wpow, (uint32_t)s->NC, nullptr, d_loc);
+            he = hipGetLastError();
+        }
+        if (he == hipSuccess) he = hipDeviceSynchronize();
+        if (d_roots) (void)hipFree(d_roots);
+        if (he != hipSuccess) {
+            if (d_pos) (void)hipFree(d_pos);
+            if (d_loc) (void)hipFree(d_loc);
+            return hip_fail(he, "scrub erasure tables");
+        }
+    }
+    if (!s) return FASTECC_OK;  // no scrub state yet and nothing to name
+    if (s->d_pos_named) (void)hipFree(s->d_pos_named);
+    if (s->d_lnamed) (void)hipFree(s->d_lnamed);
+    s->d_pos_named = d_pos;
+    s->d_lnamed = d_loc;
+    s->absent = absent;
+    s->is_absent.swap(is_absent);
+    return FASTECC_OK;
+}
+
+// fastecc_verify; named = false: over all blocks whatever fastecc_scrub_erasures named (the closing check of fastecc_correct)
+int verify_impl(fastecc_ctx* c, const void* data, const void* parity, int mem_kind, void* stream, uint64_t seed, int* consistent, bool named)
+{
+    if (!consistent) return FASTECC_E_INVAL;
+    int rc = scrub_args(c, data, parity, mem_kind);
+    if (rc != FASTECC_OK) return rc;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallLock lk(c->mu);
+    return guarded([&]() -> int {
+        std::vector<uint32_t> found;
+        const int r = locate(c, (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, true, named);
+        if (r == FASTECC_OK) *consistent = found.empty() ? 1 : 0;
+        return r;
+    });
 }
 
 int report(const std::vector<uint32_t>& found, uint64_t* blocks, uint64_t cap, uint64_t* count)
@@ -766,20 +871,27 @@ int fastecc_gf_berlekamp_massey(const uint32_t* s, uint32_t count, uint32_t* lam
     });
 }
 
+int fastecc_scrub_erasures(fastecc_ctx* c, const uint8_t* data_present, const uint8_t* parity_present)
+{
+    if (!c) return FASTECC_E_INVAL;
+    if (c->sharded || c->p61 || c->field != FASTECC_FIELD_GF_FFF00001 || c->q > 1) return FASTECC_E_UNSUPPORTED;  // fastecc_verify's refusals by kind
+    return guarded([&]() -> int {
+        std::vector<uint32_t> absent;
+        for (uint64_t i = 0; data_present && i < c->K; i++)
+            if (!data_present[i]) absent.push_back((uint32_t)i);
+        for (uint64_t q = 0; parity_present && q < c->Mu; q++)
+            if (!parity_present[q]) absent.push_back((uint32_t)(c->K + q));
+        if (absent.size() > c->Mu) return FASTECC_E_INVAL;
+        DeviceGuard dg(c->device);
+        if (!dg.ok) return FASTECC_E_DEVICE;
+        CallLock lk(c->mu);
+        return set_erasures(c, absent);
+    });
+}
+
 int fastecc_verify(fastecc_ctx* c, const void* data, const void* parity, int mem_kind, void* stream, uint64_t seed, int* consistent)
 {
-    if (!consistent) return FASTECC_E_INVAL;
-    int rc = scrub_args(c, data, parity, mem_kind);
-    if (rc != FASTECC_OK) return rc;
-    DeviceGuard dg(c->device);
-    if (!dg.ok) return FASTECC_E_DEVICE;
-    CallLock lk(c->mu);
-    return guarded([&]() -> int {
-        std::vector<uint32_t> found;
-        const int r = locate(c, (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, true);
-        if (r == FASTECC_OK) *consistent = found.empty() ? 1 : 0;
-        return r;
-    });
+    return verify_impl(c, data, parity, mem_kind, stream, seed, consistent, true);
 }
 
 int fastecc_locate_errors(fastecc_ctx* c, const void* data, const void* parity, int mem_kind, void* stream, uint64_t seed, uint64_t* blocks, uint64_t cap,
@@ -806,16 +918,18 @@ int fastecc_correct(fastecc_ctx* c, void* data, void* parity, int mem_kind, void
     DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
     return guarded([&]() -> int {
-        std::vector<uint32_t> found;
+        std::vector<uint32_t> found, absent;
         {
             CallLock lk(c->mu);
-            const int r = locate(c, (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, false);
+            const int r = locate(c, (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, false, true, &absent);
             if (r != FASTECC_OK) return r;
         }
-        if (found.empty()) return report(found, blocks, cap, count);
-        // the erasure decoder rebuilds the located blocks (prepare and repair take the context's lock themselves)
+        if (found.empty()) return report(found, blocks, cap, count);  // consistent: untouched, the absent blocks included
+        // the erasure decoder rebuilds the located blocks and, in the same repair, the ones named absent (prepare and repair take the
+        // context's lock themselves); the codeword is whole then, so the closing verify reads every block
         std::vector<uint8_t> dp(c->K, 1), pp(c->Mu, 1);
         for (uint32_t j : found) (j < c->K ? dp[j] : pp[j - c->K]) = 0;
+        for (uint32_t j : absent) (j < c->K ? dp[j] : pp[j - c->K]) = 0;
         int r = fastecc_decode_prepare(c, dp.data(), pp.data());
         if (r != FASTECC_OK) return r;
         r = fastecc_repair(c, data, parity, FASTECC_MEM_DEVICE, stream);
@@ -823,7 +937,7 @@ int fastecc_correct(fastecc_ctx* c, void* data, void* parity, int mem_kind, void
         uint64_t seed2 = seed ^ 0x5C7B5C7B5C7B5C7Bull;
         seed2 = splitmix64(seed2);
         int ok = 0;
-        r = fastecc_verify(c, data, parity, FASTECC_MEM_DEVICE, stream, seed2, &ok);
+        r = verify_impl(c, data, parity, FASTECC_MEM_DEVICE, stream, seed2, &ok, false);
         if (r != FASTECC_OK) return r;
         if (!ok) return FASTECC_E_UNCORRECTABLE;
         return report(found, blocks, cap, count);

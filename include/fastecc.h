@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 340 /* 0.3.4: fastecc_update_batch, fastecc_update_parity_batch (small writes into a pool of stripes) */
+#define FASTECC_VERSION 350 /* 0.3.5: fastecc_scrub_erasures (scrub of degraded stripes: verify, locate and correct with named erasures) */
 
 enum {
     FASTECC_OK = 0,
@@ -410,7 +410,31 @@ int fastecc_repair_batch(fastecc_ctx *ctx, void *data, void *parity, uint64_t co
  * <= 2^-20 over the weights, and all three independent columns with probability <= 2^-60 per block.  Words >= p are caught by
  * the flag always.  The same seed gives the same answer.  fastecc_correct checks its result with a second seed: a block missed
  * by all columns of the first (<= 2^-60) is reported as FASTECC_E_UNCORRECTABLE there, after the located blocks were written.
+ *
+ * Degraded stripes: fastecc_scrub_erasures names the blocks that are known to be ABSENT — a device is down —
+ * for the five scrub calls of this context (fastecc_verify, _locate_errors, _correct, _verify_batch, _correct_batch).  data_present = k
+ * flags, parity_present = n - k flags, non-zero = present, exactly as for fastecc_decode_prepare; either pointer may be NULL = every
+ * block of that part is present, both NULL (or no absent block) clears the pattern.  The pattern is context state, set under the
+ * context's lock and independent of the prepared decode pattern: fastecc_decode_prepare, _decode, _repair and fastecc_correct leave
+ * it alone, and it changes nothing they do.  Synchronous; may build the context's scrub state; the host arrays may be reused on
+ * return.  FASTECC_E_INVAL: null context, more than n - k absent blocks (the previous pattern stays in force).  FASTECC_E_UNSUPPORTED:
+ * the contexts fastecc_verify refuses by kind — GF((2^61-1)^2), sharded, mixed radix; a set "row_pitch_words" is refused by the
+ * scrub calls themselves, at call time, as before.  With no pattern set every scrub call behaves exactly as described above.  With
+ * W the set of absent blocks, w = |W|:
+ *   - absent blocks are never read: they may hold anything, words >= p included, and never count among the b blocks above;
+ *   - fastecc_verify / _verify_batch: consistent = 1 exactly when every word of every PRESENT block is < p and some codeword agrees
+ *     with all present blocks (w fewer syndromes are checked).  With w = n - k every word below p is explained by some codeword:
+ *     nothing can be checked and the answer is 1 unless a present block holds a word >= p.  The batch applies the one pattern to
+ *     every stripe (a device that is down) and its answer stays the single-stripe one under the same pattern and seed, bit for bit;
+ *   - fastecc_locate_errors returns the corrupted PRESENT blocks (absent ones are not listed); the guarantee becomes
+ *     2t + b + w <= n - k with t <= "locate_max", and beyond it the wording above holds unchanged;
+ *   - fastecc_correct / _correct_batch: a consistent stripe is left untouched, its absent blocks included (status 0).  When blocks
+ *     are located, the located AND the absent blocks are rebuilt in one repair (fastecc_decode_prepare with both sets lost, then
+ *     fastecc_repair); the codeword is whole afterwards, so the closing verify runs over all blocks with no erasures.  The returned
+ *     list still names the located blocks only; status 1.  Nothing is written on FASTECC_E_UNCORRECTABLE.  To get the absent blocks
+ *     of consistent stripes back, use fastecc_repair / fastecc_repair_batch with the same flags.
  */
+int fastecc_scrub_erasures(fastecc_ctx *ctx, const uint8_t *data_present, const uint8_t *parity_present);
 int fastecc_verify(fastecc_ctx *ctx, const void *data, const void *parity, int mem_kind, void *stream, uint64_t seed, int *consistent);
 int fastecc_locate_errors(fastecc_ctx *ctx, const void *data, const void *parity, int mem_kind, void *stream, uint64_t seed,
                           uint64_t *blocks, uint64_t cap, uint64_t *count);

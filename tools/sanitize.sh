@@ -4,7 +4,7 @@
 # test harness is run against it (FASTECC_HIP_LIB) with the sanitizer runtime preloaded into python.
 #   tools/sanitize.sh build            compile + link (no GPU needed)
 #   tools/sanitize.sh cpu  [outdir]    tests/test_host_logic.py + tests/test_abi.py + tests/test_scrub_host.py + tests/test_scrub_batch_host.py +
-#                                      tests/test_update_batch_host.py (no GPU needed)
+#                                      tests/test_update_batch_host.py + tests/test_scrub_erasures_abi.py (no GPU needed)
 #   tools/sanitize.sh gpu-all [outdir] the whole -m gpu suite
 #   tools/sanitize.sh gpu  [outdir]    one small GPU round trip per row of the scope table (encode, ntt, pack, decode / repair on both paths, mixed
 #                                      radix, 64-bit field, sharded incl. all-to-all and fault injection, host stripes)
@@ -47,7 +47,7 @@ run() { # name, pytest args...
 }
 case $MODE in
   build) build ;;
-  cpu) [ -f $LIB ] || build; run cpu tests/test_host_logic.py tests/test_abi.py tests/test_scrub_host.py tests/test_scrub_batch_host.py tests/test_update_batch_host.py -m "not gpu" ;;
+  cpu) [ -f $LIB ] || build; run cpu tests/test_host_logic.py tests/test_abi.py tests/test_scrub_host.py tests/test_scrub_batch_host.py tests/test_update_batch_host.py tests/test_scrub_erasures_abi.py -m "not gpu" ;;
   gpu) [ -f $LIB ] || build
        run gpu tests -m gpu -k "test_encode_matches_oracle or test_ntt_matches or test_scale_blocks or test_few_losses or test_repair_restores or test_split_transform_matches or test_host_stripes or test_mixed_radix_encode or test_other_n_k_over_the_64 or test_decode_transform_is_folded or test_block_distributed or test_a_failure_half_way or test_sharded_decode_and_repair or test_pack or test_first_call or test_codes_with_fewer_parity or test_few_parity_blocks" ;;
   # (the tests that load oracle/_ref are left out: the UNMODIFIED reference frees a new[] array through std::unique_ptr<T> — ntt.cpp:333, noted in
