@@ -107,6 +107,8 @@ def lib():
     for name in ("verify_batch", "correct_batch"):
         f = getattr(L, "fastecc_" + name)
         f.argtypes, f.restype = [vp, vp, vp, u64, vp, u64, u8p, u64p], i32
+    L.fastecc_locate_errors_batch.argtypes = [vp, vp, vp, u64, vp, u64, u8p, u64p, u64, ctypes.POINTER(u32), u64p]
+    L.fastecc_locate_errors_batch.restype = i32
     L.fastecc_update.argtypes, L.fastecc_update.restype = [vp, vp, vp, u64p, u64, vp, i32, vp], i32
     L.fastecc_update_parity.argtypes, L.fastecc_update_parity.restype = [vp, vp, u64p, u64, vp, vp, i32, vp], i32
     L.fastecc_update_batch.argtypes, L.fastecc_update_batch.restype = [vp, vp, vp, u64, u64p, u64, vp, vp], i32
@@ -354,9 +356,12 @@ class Encoder:
         return out.astype(bool)
 
     def correct_batch(self, data, parity, count, seed=0, stream=0):
-        """verify_batch, then correct on each inconsistent stripe (replaces the prepared erasure pattern).  Returns the numpy uint8
-        status array: 0 = consistent and untouched, 1 = corrected, 2 = uncorrectable.  If any stripe is uncorrectable, raises
-        FastEccError with code E_UNCORRECTABLE after the others were corrected; the full status array is its `status` attribute."""
+        """verify_batch, then what correct does to each inconsistent stripe (replaces the prepared erasure pattern; which pattern is
+        left behind is unspecified).  Option "correct_batch_mode": 2 = correct stripe by stripe, 1 = one batched location pass and one
+        repair per distinct set of lost blocks, 0 (default) = 1 from two qualifying stripes on; the same status and bytes in every mode.
+        Returns the numpy uint8 status array: 0 = consistent and untouched, 1 = corrected, 2 = uncorrectable.  If any stripe is
+        uncorrectable, raises FastEccError with code E_UNCORRECTABLE after the others were corrected; the full status array is its
+        `status` attribute."""
         code, out = self._scrub_batch(lib().fastecc_correct_batch, data, parity, count, seed, stream)
         if code == E_UNCORRECTABLE:
             err = FastEccError(code, "fastecc_correct_batch")
@@ -364,6 +369,29 @@ class Encoder:
             raise err
         _check(code, "fastecc_correct_batch")
         return out
+
+    def locate_errors_batch(self, data, parity, count, seed=0, stream=0):
+        """locate_errors for each of `count` stripes back to back in device memory: (status, lists) with the numpy uint8 status array
+        (0 = consistent, 1 = located, 2 = cannot be located) and one list of codeword indices per stripe (increasing; [] for status 0
+        and 2).  Reads only.  If any stripe cannot be located, raises FastEccError with code E_UNCORRECTABLE carrying both as its
+        `status` and `lists` attributes."""
+        import numpy as np
+        count = self._batch_count(count)
+        cap = self.n - self.k
+        status = np.zeros(count, np.uint8)
+        blocks = np.zeros(count * cap, np.uint64)
+        counts = np.zeros(count, np.uint32)
+        bad = ctypes.c_uint64()
+        code = lib().fastecc_locate_errors_batch(self._h, _addr(data), _addr(parity), count, stream or None, seed,
+                                                 status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), blocks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                                 cap, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(bad))
+        lists = [[int(x) for x in blocks[b * cap:b * cap + min(int(counts[b]), cap)]] for b in range(count)] if code in (OK, E_UNCORRECTABLE) else None
+        if code == E_UNCORRECTABLE:
+            err = FastEccError(code, "fastecc_locate_errors_batch")
+            err.status, err.lists = status, lists
+            raise err
+        _check(code, "fastecc_locate_errors_batch")
+        return status, lists
 
     def _located(self, fn, what, data, parity, seed, stream, mem):
         cap = self.n - self.k

@@ -1780,7 +1780,10 @@ int decode_impl(fastecc_ctx* c, void* data, const void* parity, int mem_kind, vo
 // one launch (direct_run_batch) when the pass has fewer than 4096 rows (from 4096 data rows on, the single-stripe path takes the matrix cores) and
 // the batch gives at least one wave per SIMD; otherwise (option "decode_batch_kernel" decides when set) direct_run stripe by stripe.  Patterns of
 // the transform path: the single-stripe decode, stripe by stripe.
-int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream, bool repair)
+// host_list / dev_list (the scrubber's repair_list; both or neither): the batch is the stripes list[0 .. count) of a pool whose extent the caller has
+// checked.  The same choice between one launch and stripe by stripe; the batched launch reads the device copy, the loops the host copy.
+int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream, bool repair, const uint64_t* host_list = nullptr,
+                      const uint64_t* dev_list = nullptr)
 {
     if (!c || !data || !parity || count == 0 || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
     if (sharded_of(c)) return FASTECC_E_UNSUPPORTED;
@@ -1790,7 +1793,9 @@ int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, 
     if (ci.pitch != ci.words) return FASTECC_E_UNSUPPORTED;  // stripes of a batch are contiguous
     const uint64_t block = ci.words * 4, data_bytes = ci.user_k * block, parity_bytes = ci.user_m * block;
     if (count > UINT64_MAX / data_bytes || count > UINT64_MAX / parity_bytes) return FASTECC_E_INVAL;
-    if ((uint64_t)(uintptr_t)data > UINT64_MAX - count * data_bytes || (uint64_t)(uintptr_t)parity > UINT64_MAX - count * parity_bytes) return FASTECC_E_INVAL;
+    if (!host_list && ((uint64_t)(uintptr_t)data > UINT64_MAX - count * data_bytes || (uint64_t)(uintptr_t)parity > UINT64_MAX - count * parity_bytes)) return FASTECC_E_INVAL;
+    if ((host_list != nullptr) != (dev_list != nullptr)) return FASTECC_E_INVAL;
+    auto stripe_of = [&](uint64_t b) { return host_list ? host_list[b] : b; };
     DecodeState* d = decoder_of(c);
     if (!d || !d->ready) return FASTECC_E_INVAL;  // fastecc_decode_prepare first
     const bool rebuild = repair && d->erased_parity != 0;
@@ -1801,8 +1806,8 @@ int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, 
     if (!d->sub) {
         // more losses than the direct path takes: correct, not faster than the caller's own loop
         for (uint64_t b = 0; b < count; b++) {
-            char* pb = (char*)parity + b * parity_bytes;
-            const int rc = decode_locked(c, call, (char*)data + b * data_bytes, pb, FASTECC_MEM_DEVICE, stream, repair ? pb : nullptr);
+            char* pb = (char*)parity + stripe_of(b) * parity_bytes;
+            const int rc = decode_locked(c, call, (char*)data + stripe_of(b) * data_bytes, pb, FASTECC_MEM_DEVICE, stream, repair ? pb : nullptr);
             if (rc != FASTECC_OK) return rc;
         }
         return FASTECC_OK;
@@ -1819,22 +1824,30 @@ int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, 
         const bool batched = mode == 1 || (mode == 0 && d->direct_kernel != 2 && rows < 4096 && direct_batch_waves(p, ddata, dparity, S, count) >= 1024);
         if (batched) {
             const uint64_t outputs = (data_to ? (uint64_t)d->sub_lost_data : 0) + (par_to ? (uint64_t)d->sub_lost_parity : 0);
-            void* scope = profile_scope_begin(c, st, "direct_pass_batch", count * (rows + outputs) * block);
-            const int r = direct_run_batch(p, ddata, par_in, data_to, par_to, S, count, data_words, parity_words, st);
+            void* scope = profile_scope_begin(c, st, dev_list ? "direct_pass_list" : "direct_pass_batch", count * (rows + outputs) * block);
+            const int r = direct_run_batch(p, ddata, par_in, data_to, par_to, S, count, data_words, parity_words, st, dev_list);
             profile_scope_end(scope);
             return r;
         }
         void* scope = profile_scope_begin(c, st, "direct_pass", count * (ci.user_k + (uint64_t)d->sub_lost_data) * block);
         int r = FASTECC_OK;
-        for (uint64_t b = 0; b < count && r == FASTECC_OK; b++)
-            r = direct_run(p, ddata + b * data_words, par_in ? par_in + b * parity_words : nullptr, data_to ? data_to + b * data_words : nullptr,
-                           par_to ? par_to + b * parity_words : nullptr, (uint32_t)S, d->direct_kernel, st);
+        for (uint64_t b = 0; b < count && r == FASTECC_OK; b++) {
+            const uint64_t sb = stripe_of(b);
+            r = direct_run(p, ddata + sb * data_words, par_in ? par_in + sb * parity_words : nullptr, data_to ? data_to + sb * data_words : nullptr,
+                           par_to ? par_to + sb * parity_words : nullptr, (uint32_t)S, d->direct_kernel, st);
+        }
         profile_scope_end(scope);
         return r;
     });
 }
 
 }  // namespace
+
+int repair_list(fastecc_ctx* c, void* data, void* parity, const uint64_t* host_list, const uint64_t* dev_list, uint64_t count, void* stream)
+{
+    if (!host_list || !dev_list) return FASTECC_E_INVAL;
+    return decode_batch_impl(c, data, parity, count, stream, true, host_list, dev_list);
+}
 
 }  // namespace fastecc
 

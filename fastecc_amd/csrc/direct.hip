@@ -835,9 +835,12 @@ struct BatchArgs {
     uint64_t groups;          // count * S / V
     uint64_t group_base;      // the launch's first group (batches of more than 2^30 groups take several launches)
     uint32_t S, rows, data_rows, pad, outputs;
+    const uint64_t* list;     // LIST form only: lane group g belongs to stripe list[gV / S] of the pool (count = the list's length)
 };
 
-template <int EB, int V>
+// LIST: the batch is the stripes list[0 .. count) of a pool instead of its stripes 0 .. count — the stripe a lane addresses is looked up per lane
+// (below 64 V words per block a wave spans several list entries); everything else is the same kernel.
+template <int EB, int V, bool LIST = false>
 __global__ __launch_bounds__(256) void direct_batch_kernel(const BatchArgs a)
 {
     constexpr int U = EB >= 16 ? 2 : EB >= 8 ? 4 : 8;  // rows in flight; U * EB <= 32 weights live in SGPRs (at 64, with the stripe addressing, SGPRs spilled into the row loop)
@@ -849,7 +852,8 @@ __global__ __launch_bounds__(256) void direct_batch_kernel(const BatchArgs a)
     {
         const uint64_t g = a.group_base + ((uint64_t)blockIdx.x * 4u + wave) * 64u + lane;
         const bool live = g < a.groups;
-        const uint64_t word = live ? g * V : 0, b = word / a.S, c = word - b * a.S;
+        const uint64_t word = live ? g * V : 0, entry = word / a.S, c = word - entry * a.S;
+        const uint64_t b = LIST ? (live ? a.list[entry] : 0) : entry;
         const uint32_t* dbase = a.data + b * a.data_stride + c;
         const uint64_t poff = b * a.parity_stride + c;  // (a lane's parity rows: a.parity + poff + row * S)
         uint64_t lo[EB][V];
@@ -920,19 +924,23 @@ uint64_t direct_batch_waves(const DirectPass* p, const void* data, const void* p
 }
 
 int direct_run_batch(DirectPass* p, const uint32_t* data, const uint32_t* parity, uint32_t* data_out, uint32_t* parity_out, uint64_t S, uint64_t count,
-                     uint64_t data_stride, uint64_t parity_stride, hipStream_t st)
+                     uint64_t data_stride, uint64_t parity_stride, hipStream_t st, const uint64_t* list)
 {
     if (!p || !p->built || S == 0 || S > 0xFFFFFFFFull || count == 0) return FASTECC_E_INVAL;
     const int pad = p->pad, sweeps = pad > 16 ? pad / 16 : 1, eb = std::min(pad, 16);
     // every pointer a lane touches: the stripes it reads and the ones it writes (data_out / parity_out are data / parity or null)
     const int v = batch_vec(p, (const void*)((uintptr_t)data | (uintptr_t)data_out), (const void*)((uintptr_t)parity | (uintptr_t)parity_out), S);
     BatchArgs a{data, parity, p->lists, p->coef, p->lists + DIRECT_CAP, data_out, parity_out, data_stride, parity_stride, count * S / (uint64_t)v, 0,
-                (uint32_t)S, p->rows, p->data_rows, (uint32_t)pad, (uint32_t)p->outputs};
+                (uint32_t)S, p->rows, p->data_rows, (uint32_t)pad, (uint32_t)p->outputs, list};
     // a dispatch holds fewer than 2^32 work-items per dimension: at most 2^22 workgroups (2^30 groups) per launch
     constexpr uint64_t LAUNCH_GROUPS = 1ull << 30;
     for (a.group_base = 0; a.group_base < a.groups; a.group_base += LAUNCH_GROUPS) {
     const dim3 grid((unsigned)((std::min(a.groups - a.group_base, LAUNCH_GROUPS) + 255u) / 256u), (unsigned)sweeps);
-#define FASTECC_BATCH(EB, V) hipLaunchKernelGGL((direct_batch_kernel<EB, V>), grid, dim3(256), 0, st, a)
+#define FASTECC_BATCH(EB, V)                                                                          \
+    do {                                                                                              \
+        if (list) hipLaunchKernelGGL((direct_batch_kernel<EB, V, true>), grid, dim3(256), 0, st, a);  \
+        else hipLaunchKernelGGL((direct_batch_kernel<EB, V>), grid, dim3(256), 0, st, a);             \
+    } while (0)
     switch (eb * 8 + v) {
         case 1 * 8 + 4: FASTECC_BATCH(1, 4); break;
         case 1 * 8 + 2: FASTECC_BATCH(1, 2); break;

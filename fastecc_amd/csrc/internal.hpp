@@ -126,12 +126,17 @@ int direct_build_interp(DirectPass* p, uint32_t wd, uint64_t N, uint32_t K, cons
 // kernel: 0 = choose, 1 = VALU (96-bit lazy accumulation), 2 = MFMA (i8 digits) when the stripes allow it
 int direct_run(DirectPass* p, const uint32_t* data, const uint32_t* parity, uint32_t* data_out, uint32_t* parity_out, uint32_t S, int kernel, hipStream_t st);
 // The same pass over `count` stripes in ONE launch (VALU, no partial sums): stripe b's rows at data + b * data_stride and parity + b * parity_stride
-// (words), its outputs at the same places of data_out / parity_out (each either the input stripe or null: that kind of output is skipped)
+// (words), its outputs at the same places of data_out / parity_out (each either the input stripe or null: that kind of output is skipped).
+// list != null (device, `count` entries): the stripes list[0 .. count) of the pool instead of its stripes 0 .. count
 int direct_run_batch(DirectPass* p, const uint32_t* data, const uint32_t* parity, uint32_t* data_out, uint32_t* parity_out, uint64_t S, uint64_t count,
-                     uint64_t data_stride, uint64_t parity_stride, hipStream_t st);
+                     uint64_t data_stride, uint64_t parity_stride, hipStream_t st, const uint64_t* list = nullptr);
 uint64_t direct_batch_waves(const DirectPass* p, const void* data, const void* parity, uint64_t S, uint64_t count);  // waves of that launch, all sweeps
 int direct_pass_rows(const DirectPass* p);  // rows a pass reads (lost data rows included, at weight 0)
 bool direct_mfma_applies(const void* data, const void* parity, uint64_t words);
+// decode.hip, for the scrubber (fastecc_correct_batch): fastecc_repair_batch's work on the `count` stripes list[0 .. count) of a pool of back-to-back
+// stripes, with the prepared pattern.  The list is given twice: on the host (the stripe-by-stripe forms) and on the device (the batched launch).
+// The caller has checked the pool's pointers and extent; takes the context's call lock itself.
+int repair_list(fastecc_ctx* c, void* data, void* parity, const uint64_t* host_list, const uint64_t* dev_list, uint64_t count, void* stream);
 // encoding straight from the Lagrange basis for codes with few parity blocks (n - k <= direct_encode_max())
 struct DirectEncode;
 int direct_encode_max();

@@ -123,6 +123,11 @@ int fastecc_set_option(fastecc_ctx* c, const char* name, int value)
         c->decode_batch_kernel = value;
         return FASTECC_OK;
     }
+    if (!strcmp(name, "correct_batch_mode")) {  // fastecc_correct_batch, at call time: 0 = choose, 1 = batched location + grouped repair, 2 = fastecc_correct stripe by stripe
+        if (value < 0 || value > 2) return FASTECC_E_INVAL;
+        c->correct_batch_mode = value;
+        return FASTECC_OK;
+    }
     if (!strcmp(name, "fuse_radix")) {  // mixed-radix contexts: 1 = odd-radix level fused into the outer tiles (default), 0 = its own passes
         if (value < 0 || value > 1) return FASTECC_E_INVAL;
         if (c->fuse_radix == value) return FASTECC_OK;

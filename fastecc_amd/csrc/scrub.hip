@@ -1,5 +1,5 @@
 // scrub.hip — error detection and location: fastecc_verify, fastecc_locate_errors, fastecc_correct and the batched fastecc_verify_batch,
-// fastecc_correct_batch (include/fastecc.h).
+// fastecc_correct_batch, fastecc_locate_errors_batch (include/fastecc.h).
 //
 // The erasure decoder (decode.hip) acts on losses the caller names.  Here the corrupted blocks are found first.  Every code of the
 // library is f (degree < N) on a subset of the NC-th roots of unity, NC = N << e, position u <-> w^u: data block i at i << e, parity at
@@ -27,7 +27,11 @@
 // fixed erasures' in a table cached per pattern, w fewer syndromes are checked, and fastecc_correct rebuilds them with the located blocks.
 // fastecc_verify_batch / _correct_batch run the verify over many stripes at once: the stripe index becomes extra word columns of
 // the fingerprint stripe, so one transform serves a whole chunk of stripes (fingerprint_batch_kernel, syndrome_batch_kernel, verify_batch_locked).
+// fastecc_locate_errors_batch and the grouped path of fastecc_correct_batch run the same passes over a LIST of stripes of the pool:
+// all syndromes of the flagged stripes gathered at once (syndrome_gather_kernel), Berlekamp-Massey per stripe on the host, one root search for all
+// locators (root_search_batch_kernel), then one fastecc_decode_prepare and one list-form repair (decode.hip repair_list) per distinct set of lost blocks.
 #include <algorithm>
+#include <map>
 #include <vector>
 
 #include "drivers.hpp"
@@ -181,11 +185,17 @@ __global__ __launch_bounds__(256) void fingerprint_kernel(const uint32_t* __rest
 // sets flag[b] (a plain store of 1: idempotent, no atomics).  An absent block (pos[j] marked; wave-uniform) is not read and its entry is stored
 // as zero: nothing multiplies F by the locator afterwards, and the entry may hold another call's or another pattern's value.
 // At most 80 VGPRs: six waves per SIMD, the grid the host launches all resident.
-template <bool VEC>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void fingerprint_batch_kernel(const uint32_t* __restrict__ data, const uint32_t* __restrict__ parity, uint32_t k_blocks,
+// LIST (batched location and the closing verify of fastecc_correct_batch): the chunk is B entries of a list of stripes of the
+// pool — list[bl] names the stripe whose blocks are read (wave-uniform like b), while the fingerprint columns, flag[] and big[] are addressed by the
+// position bl in the chunk (the host passes all three arrays from the chunk's first entry on; b0 is not used).  big[bl] = 1 records that a present
+// block of the entry held a word >= p (flag[bl] is set as well).  The list form needs two registers more than 80 in its vector form: five waves per
+// SIMD there (82 VGPRs, no scratch) instead of a spilled pointer; its grid is sized to match (list_chunk).
+template <bool VEC, bool LIST = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIST ? 5 : 6))) void fingerprint_batch_kernel(const uint32_t* __restrict__ data, const uint32_t* __restrict__ parity, uint32_t k_blocks,
                                                                 uint32_t n_blocks, uint32_t S, uint64_t b0, uint64_t B, const uint2* __restrict__ wt,
                                                                 const uint32_t* __restrict__ pos, const uint32_t* __restrict__ lfix, uint32_t* __restrict__ F,
-                                                                uint64_t row, uint8_t* __restrict__ flag)
+                                                                uint64_t row, uint8_t* __restrict__ flag, const uint64_t* __restrict__ list,
+                                                                uint8_t* __restrict__ big)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
@@ -195,7 +205,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void f
     for (uint64_t g = wave; g < total; g += waves) {
         const uint64_t bl = g / n_blocks;
         const uint32_t j = (uint32_t)(g - bl * n_blocks);
-        const uint64_t b = b0 + bl;
+        const uint32_t entry = __builtin_amdgcn_readfirstlane((uint32_t)bl);  // (LIST: a chunk has at most 2^16 entries)
+        const uint64_t b = LIST ? list[entry] : b0 + bl;
         const uint32_t u = pos[j];
         if (u & ABSENT) {
             if (lane == 0) *reinterpret_cast<uint4*>(F + (uint64_t)(u & ~ABSENT) * row + bl * RW) = make_uint4(0, 0, 0, 0);
@@ -211,7 +222,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void f
             f[0] = gf::mul(fp[0], l);
             f[1] = gf::mul(fp[1], l);
             f[2] = gf::mul(fp[2], l);
-            if (any_big) flag[b] = 1;
+            if (any_big) {
+                if (LIST) {
+                    flag[entry] = 1;
+                    big[entry] = 1;
+                } else {
+                    flag[b] = 1;
+                }
+            }
         }
     }
 }
@@ -263,6 +281,43 @@ __global__ __launch_bounds__(256) void syndrome_batch_kernel(const uint32_t* __r
     const uint32_t slot = __brev(m) >> (32 - lgc);
     const uint4 g = *reinterpret_cast<const uint4*>(G + (uint64_t)slot * row + (uint64_t)b * RW);
     if ((g.x | g.y | g.z) != 0) flag[b0 + b] = 1;
+}
+
+// Batched location: all avail = NC - m_lo coefficients from m_lo on of the chunk's B entries, by entry and column:
+// syn[(b * 3 + c) * avail + i] = NC * coefficient m_lo + i of column c of entry b (item = i * B + b, as above)
+__global__ __launch_bounds__(256) void syndrome_gather_kernel(const uint32_t* __restrict__ G, int lgc, uint32_t m_lo, uint32_t avail, uint64_t row, uint32_t B,
+                                                              uint32_t* __restrict__ syn)
+{
+    const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= avail * B) return;
+    const uint32_t b = item % B, i = item / B;
+    const uint32_t slot = __brev(m_lo + i) >> (32 - lgc);
+    const uint4 g = *reinterpret_cast<const uint4*>(G + (uint64_t)slot * row + (uint64_t)b * RW);
+    uint32_t* o = syn + (uint64_t)b * R * avail + i;
+    o[0] = g.x;
+    o[avail] = g.y;
+    o[2 * (uint64_t)avail] = g.z;
+}
+
+// Batched location: thread (e, u) evaluates the locator of entry e — lambda[e * stride + 0 .. L[e]] — at w^u; a root is appended to entry e's own list
+// found[e * (cap + 1) + 1 ..] (found[e * (cap + 1)] counts all of them, the list keeps the first cap)
+__global__ __launch_bounds__(256) void root_search_batch_kernel(const uint32_t* __restrict__ lambda, const uint32_t* __restrict__ Ls, uint32_t stride,
+                                                                const uint32_t* __restrict__ wpow, uint32_t NC, uint32_t entries, uint32_t* __restrict__ found,
+                                                                uint32_t cap)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= entries * NC) return;
+    const uint32_t e = t / NC, u = t - e * NC;
+    const uint32_t* l = lambda + (uint64_t)e * stride;
+    const uint32_t L = Ls[e];
+    const uint32_t x = wpow[u];
+    uint32_t acc = l[L];
+    for (int i = (int)L - 1; i >= 0; i--) acc = gf::add(gf::mul(acc, x), l[i]);
+    if (acc == 0) {
+        uint32_t* f = found + (uint64_t)e * (cap + 1);
+        const uint32_t slot = atomicAdd(f, 1u);
+        if (slot < cap) f[1 + slot] = u;
+    }
 }
 
 // Lambda(w^u) == 0 -> u appended to found[1 ..] (found[0] counts)
@@ -323,6 +378,12 @@ struct ScrubState {
     std::vector<uint8_t> is_absent;         // n flags
     uint32_t* d_pos_named = nullptr;        // n words: d_pos with ABSENT set at those blocks
     uint32_t* d_lnamed = nullptr;           // NC words: d_lfix (or 1) times the locator of their positions at w^u
+    // batched location and the list forms, all grow-only
+    uint64_t* d_list = nullptr;             // the stripes a list pass runs over
+    uint8_t* d_lflag = nullptr;             // per list entry: [0, list_cap) inconsistent, [list_cap, 2 list_cap) a present block held a word >= p
+    uint64_t list_cap = 0;
+    uint32_t* d_loc = nullptr;              // one chunk's syndromes, then its locators, their lengths and the found lists
+    uint64_t loc_words = 0;
 };
 
 void destroy_scrub_state(ScrubState* s)
@@ -331,7 +392,7 @@ void destroy_scrub_state(ScrubState* s)
     if (s->ntt) fastecc_destroy(s->ntt);
     if (s->ntt_batch) fastecc_destroy(s->ntt_batch);
     for (void* p : {(void*)s->d_pos, (void*)s->d_wpow, (void*)s->d_lfix, (void*)s->d_F, (void*)s->d_G, (void*)s->d_small, (void*)s->d_weights, (void*)s->d_FB,
-                    (void*)s->d_GB, (void*)s->d_flag, (void*)s->d_pos_named, (void*)s->d_lnamed})
+                    (void*)s->d_GB, (void*)s->d_flag, (void*)s->d_pos_named, (void*)s->d_lnamed, (void*)s->d_list, (void*)s->d_lflag, (void*)s->d_loc})
         if (p) (void)hipFree(p);
     delete s;
 }
@@ -755,10 +816,10 @@ int verify_batch_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* pa
             ProfScope ps(c, st, "fingerprint_batch", B * (s->n - er.w) * S * 4);
             if (vec)
                 hipLaunchKernelGGL(fingerprint_batch_kernel<true>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)S,
-                                   b0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, s->d_flag);
+                                   b0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, s->d_flag, nullptr, nullptr);
             else
                 hipLaunchKernelGGL(fingerprint_batch_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)S,
-                                   b0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, s->d_flag);
+                                   b0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, s->d_flag, nullptr, nullptr);
             HIP_TRY(hipGetLastError());
         }
         if (m_lo >= NC) continue;  // n - k blocks named absent: no coefficient is left to check, only the words >= p count
@@ -777,6 +838,217 @@ int verify_batch_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* pa
     flag.assign(count, 0);
     HIP_TRY(hipMemcpyAsync(flag.data(), s->d_flag, count, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return FASTECC_OK;
+}
+
+// ---- list forms: the same passes over the stripes list[0 .. L) of the pool ----
+
+// the device copy of a list and its cleared per-entry flags; enqueued on st (the host list must live until the next synchronise)
+int upload_list(ScrubState* s, const std::vector<uint64_t>& list, hipStream_t st)
+{
+    const uint64_t L = list.size();
+    if (s->list_cap < L) {
+        if (s->d_list) (void)hipFree(s->d_list);
+        if (s->d_lflag) (void)hipFree(s->d_lflag);
+        s->d_list = nullptr;
+        s->d_lflag = nullptr;
+        s->list_cap = 0;
+        HIP_TRY(hipMalloc((void**)&s->d_list, L * 8));
+        HIP_TRY(hipMalloc((void**)&s->d_lflag, 2 * L));
+        s->list_cap = L;
+    }
+    HIP_TRY(hipMemcpyAsync(s->d_list, list.data(), L * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(s->d_lflag, 0, 2 * s->list_cap, st));
+    return FASTECC_OK;
+}
+
+// One chunk of verify_batch_locked over the list entries [l0, l0 + B) of s->d_list: fingerprints, transform and either the flags of those entries
+// (syn == null) or all their `avail` = NC - m_lo syndromes gathered to syn.  Nothing is copied back and nothing waits.
+int list_chunk(fastecc_ctx* c, ScrubState* s, const Erasures& er, const uint32_t* data, const uint32_t* parity, uint64_t l0, uint64_t B, hipStream_t st,
+               uint32_t* syn)
+{
+    const uint64_t row = RW * s->batch_cap, NC = s->NC, m_lo = s->N + s->fixed + er.w, S = c->S;
+    const bool vec = (S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
+    const uint64_t groups = std::min<uint64_t>((B * s->n + 3) / 4, (uint64_t)c->cus * 5);  // every workgroup resident at once: five waves per SIMD
+    uint8_t *flag = s->d_lflag, *big = s->d_lflag + s->list_cap;
+    {
+        ProfScope ps(c, st, "fingerprint_batch_list", B * (s->n - er.w) * S * 4);
+        if (vec)
+            hipLaunchKernelGGL((fingerprint_batch_kernel<true, true>), dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n,
+                               (uint32_t)S, (uint64_t)0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, flag + l0, s->d_list + l0, big + l0);
+        else
+            hipLaunchKernelGGL((fingerprint_batch_kernel<false, true>), dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n,
+                               (uint32_t)S, (uint64_t)0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, flag + l0, s->d_list + l0, big + l0);
+        HIP_TRY(hipGetLastError());
+    }
+    if (m_lo >= NC) return FASTECC_OK;
+    {
+        ProfScope ps(c, st, "scrub_transform_batch");
+        const int rc = transform_bitrev(s->ntt_batch, s->d_FB, s->d_GB, false, true, (uint32_t)(RW * B), st);
+        if (rc != FASTECC_OK) return rc;
+    }
+    const uint64_t items = (NC - m_lo) * B;  // <= NC * batch_cap <= 2^21
+    if (syn) {
+        ProfScope ps(c, st, "scrub_syndromes_gather");
+        hipLaunchKernelGGL(syndrome_gather_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, s->d_GB, s->lgc, (uint32_t)m_lo, (uint32_t)(NC - m_lo), row,
+                           (uint32_t)B, syn);
+        HIP_TRY(hipGetLastError());
+    } else {
+        ProfScope ps(c, st, "scrub_syndromes_batch");
+        hipLaunchKernelGGL(syndrome_batch_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, s->d_GB, s->lgc, (uint32_t)NC, (uint32_t)m_lo, row,
+                           (uint32_t)B, l0, flag);
+        HIP_TRY(hipGetLastError());
+    }
+    return FASTECC_OK;
+}
+
+uint64_t chunk_of(const fastecc_ctx* c, const ScrubState* s)
+{
+    return c->scrub_batch_chunk > 0 ? std::min<uint64_t>(s->batch_cap, (uint64_t)c->scrub_batch_chunk) : s->batch_cap;
+}
+
+// verify_batch_locked over the stripes `list` of the pool: flag[i] = 1 iff fastecc_verify with this seed would find stripe list[i] inconsistent
+// (named: under the named erasures).  One copy of the flags and one synchronisation for the call.
+int verify_list_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, const std::vector<uint64_t>& list, uint64_t seed, hipStream_t st, bool named,
+                       std::vector<uint8_t>& flag)
+{
+    ScrubState* s = nullptr;
+    int rc = scrub_state(c, &s);
+    if (rc != FASTECC_OK) return rc;
+    if ((rc = batch_state(c, s)) != FASTECC_OK) return rc;
+    if ((rc = upload_weights(c, s, seed, st)) != FASTECC_OK) return rc;
+    if ((rc = upload_list(s, list, st)) != FASTECC_OK) return rc;
+    const Erasures er = erasures(s, named);
+    const uint64_t chunk = chunk_of(c, s), L = list.size();
+    for (uint64_t l0 = 0; l0 < L; l0 += chunk)
+        if ((rc = list_chunk(c, s, er, data, parity, l0, std::min(chunk, L - l0), st, nullptr)) != FASTECC_OK) return rc;
+    flag.assign(L, 0);
+    HIP_TRY(hipMemcpyAsync(flag.data(), s->d_lflag, L, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return FASTECC_OK;
+}
+
+// whether every s[i], L <= i < count, obeys the recurrence of lambda (lambda[0] = 1, length L)
+bool obeys_recurrence(const uint32_t* s, uint64_t count, const std::vector<uint32_t>& lambda)
+{
+    const uint64_t L = lambda.size() - 1;
+    for (uint64_t i = L; i < count; i++) {
+        uint64_t d = s[i] % gf::P;
+        for (uint64_t j = 1; j <= L; j++) d = (d + (uint64_t)lambda[j] * (s[i - j] % gf::P)) % gf::P;
+        if (d != 0) return false;
+    }
+    return true;
+}
+
+enum : uint8_t { LOC_FALLBACK = 0, LOC_FOUND = 1, LOC_UNCORRECTABLE = 2 };
+
+// Batched location on a locked context: for the stripes `list` of the pool — all of them inconsistent under `seed` and the
+// named erasures — state[i] = LOC_FOUND with blocks[i] the located blocks (increasing; what fastecc_locate_errors returns for that stripe),
+// LOC_UNCORRECTABLE where it would refuse, or LOC_FALLBACK for a stripe this path does not take: a present block holds a word >= p, or the code
+// has more than 512 syndromes.  Per chunk: one list pass that gathers every syndrome, Berlekamp-Massey and the recurrence check on the host,
+// one root search over all locators; two synchronisations.
+int locate_list(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, const std::vector<uint64_t>& list, uint64_t seed, hipStream_t st,
+                std::vector<uint8_t>& state, std::vector<std::vector<uint32_t>>& blocks)
+{
+    constexpr uint64_t GATHER_MAX = 512;
+    ScrubState* s = nullptr;
+    int rc = scrub_state(c, &s);
+    if (rc != FASTECC_OK) return rc;
+    const uint64_t L = list.size();
+    state.assign(L, LOC_FALLBACK);
+    blocks.assign(L, {});
+    const Erasures er = erasures(s, true);
+    const uint64_t m = s->n - s->k, avail = m > er.w ? m - er.w : 0, tmax = (uint64_t)c->locate_max;
+    if (L == 0 || avail == 0 || avail > GATHER_MAX) return FASTECC_OK;
+    if ((rc = batch_state(c, s)) != FASTECC_OK) return rc;
+    if ((rc = upload_weights(c, s, seed, st)) != FASTECC_OK) return rc;
+    if ((rc = upload_list(s, list, st)) != FASTECC_OK) return rc;
+    const uint64_t chunk = std::min(chunk_of(c, s), L), gather = std::min<uint64_t>(2 * tmax, avail);
+    const uint64_t lmax = std::min<uint64_t>(tmax, gather / 2), stride = lmax + 1, cap = lmax + 1;
+    // the chunk's buffer: syndromes | locators | their lengths | found lists
+    const uint64_t syn_words = chunk * R * avail, lam_words = chunk * stride, found_words = chunk * (cap + 1);
+    const uint64_t words = syn_words + lam_words + chunk + found_words;
+    if (s->loc_words < words) {
+        if (s->d_loc) (void)hipFree(s->d_loc);
+        s->d_loc = nullptr;
+        s->loc_words = 0;
+        HIP_TRY(hipMalloc((void**)&s->d_loc, words * 4));
+        s->loc_words = words;
+    }
+    uint32_t *d_syn = s->d_loc, *d_lam = d_syn + syn_words, *d_len = d_lam + lam_words, *d_found = d_len + chunk;
+    std::vector<uint32_t> syn(syn_words), lam, len, found, cand;
+    std::vector<uint8_t> big(chunk);
+    std::vector<uint64_t> who;                   // list entries with a locator, in table order
+    std::vector<std::vector<uint32_t>> lambdas;  // their locators
+    for (uint64_t l0 = 0; l0 < L; l0 += chunk) {
+        const uint64_t B = std::min(chunk, L - l0);
+        if ((rc = list_chunk(c, s, er, data, parity, l0, B, st, d_syn)) != FASTECC_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(syn.data(), d_syn, B * R * avail * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(big.data(), s->d_lflag + s->list_cap + l0, B, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        who.clear();
+        lambdas.clear();
+        for (uint64_t b = 0; b < B; b++) {
+            if (big[b]) continue;  // known erasures besides the named ones: the single-stripe code
+            const uint32_t* sy = syn.data() + b * R * avail;
+            bool nonzero = false;
+            for (uint64_t i = 0; i < R * avail && !nonzero; i++) nonzero = sy[i] != 0;
+            if (!nonzero) continue;  // (consistent after all: cannot happen for a stripe the same seed flagged)
+            // locate()'s decisions: the longest of the columns' LFSRs, the first column on ties
+            std::vector<uint32_t> lambda;
+            int len_best = 0;
+            for (int col = 0; col < R; col++) {
+                const int Lc = berlekamp_massey(sy + col * avail, (uint32_t)gather, cand);
+                if (Lc > len_best) {
+                    len_best = Lc;
+                    lambda = cand;
+                }
+            }
+            state[l0 + b] = LOC_UNCORRECTABLE;
+            if (len_best == 0 || (uint64_t)len_best > tmax || 2ull * (uint64_t)len_best > gather) continue;
+            // confirmation: every syndrome of every column obeys the locator's recurrence
+            bool ok = true;
+            for (int col = 0; col < R && ok; col++) ok = obeys_recurrence(sy + col * avail, avail, lambda);
+            if (!ok) continue;
+            who.push_back(l0 + b);
+            lambdas.push_back(std::move(lambda));
+        }
+        if (who.empty()) continue;
+        const uint64_t E = who.size();
+        lam.assign(E * stride, 0);
+        len.resize(E);
+        for (uint64_t e = 0; e < E; e++) {
+            std::copy(lambdas[e].begin(), lambdas[e].end(), lam.begin() + e * stride);
+            len[e] = (uint32_t)(lambdas[e].size() - 1);
+        }
+        HIP_TRY(hipMemcpyAsync(d_lam, lam.data(), E * stride * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_len, len.data(), E * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_found, 0, E * (cap + 1) * 4, st));
+        {
+            ProfScope ps(c, st, "scrub_root_search_batch");
+            hipLaunchKernelGGL(root_search_batch_kernel, dim3((unsigned)((E * s->NC + 255) / 256)), dim3(256), 0, st, d_lam, d_len, (uint32_t)stride, s->d_wpow,
+                               (uint32_t)s->NC, (uint32_t)E, d_found, (uint32_t)cap);
+            HIP_TRY(hipGetLastError());
+        }
+        found.resize(E * (cap + 1));
+        HIP_TRY(hipMemcpyAsync(found.data(), d_found, E * (cap + 1) * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint64_t e = 0; e < E; e++) {
+            const uint32_t* f = found.data() + e * (cap + 1);
+            if (f[0] != len[e]) continue;  // a locator splits into distinct roots at the code's positions, or it is no locator
+            std::vector<uint32_t> js;
+            bool ok = true;
+            for (uint32_t i = 0; i < f[0] && ok; i++) {
+                const uint32_t j = s->block_at[f[1 + i]];
+                ok = j != ~0u && !(er.w && s->is_absent[j]);  // a block is there, and not one already erased
+                js.push_back(j);
+            }
+            if (!ok) continue;
+            std::sort(js.begin(), js.end());
+            blocks[who[e]] = std::move(js);
+            state[who[e]] = LOC_FOUND;
+        }
+    }
     return FASTECC_OK;
 }
 
@@ -967,6 +1239,59 @@ int fastecc_verify_batch(fastecc_ctx* c, const void* data, const void* parity, u
     });
 }
 
+int fastecc_locate_errors_batch(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, void* stream, uint64_t seed, uint8_t* status,
+                                uint64_t* blocks, uint64_t cap, uint32_t* counts, uint64_t* inconsistent)
+{
+    if (!status || !inconsistent || (cap && (!blocks || !counts))) return FASTECC_E_INVAL;
+    const int rc = batch_args(c, data, parity, count);
+    if (rc != FASTECC_OK) return rc;
+    if (cap && count > UINT64_MAX / 8 / cap) return FASTECC_E_INVAL;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallLock lk(c->mu);
+    return guarded([&]() -> int {
+        hipStream_t st = (hipStream_t)stream;
+        std::vector<uint8_t> flag, state;
+        int r = verify_batch_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, seed, st, flag);
+        if (r != FASTECC_OK) return r;
+        std::vector<uint64_t> list;
+        for (uint64_t b = 0; b < count; b++)
+            if (flag[b]) list.push_back(b);
+        std::vector<std::vector<uint32_t>> found;
+        if ((r = locate_list(c, (const uint32_t*)data, (const uint32_t*)parity, list, seed, st, state, found)) != FASTECC_OK) return r;
+        const uint64_t data_words = c->K * c->S, parity_words = c->Mu * c->S;
+        for (size_t i = 0; i < list.size(); i++) {
+            if (state[i] != LOC_FALLBACK) continue;
+            // a word >= p in a present block, or more syndromes than the batched pass gathers: the single-stripe code through the stripe's own pointers
+            r = locate(c, (const uint32_t*)data + list[i] * data_words, (const uint32_t*)parity + list[i] * parity_words, seed, st, found[i], false);
+            if (r == FASTECC_E_UNCORRECTABLE) state[i] = LOC_UNCORRECTABLE;
+            else if (r != FASTECC_OK) return r;
+            else state[i] = LOC_FOUND;
+        }
+        // every output is written only now: a failed call leaves them alone
+        bool uncorrectable = false;
+        uint64_t bad = 0;
+        std::fill(status, status + count, (uint8_t)0);
+        if (counts) std::fill(counts, counts + count, 0u);
+        for (size_t i = 0; i < list.size(); i++) {
+            const uint64_t b = list[i];
+            if (state[i] == LOC_UNCORRECTABLE) {
+                status[b] = 2;
+                uncorrectable = true;
+                bad++;
+                continue;
+            }
+            if (found[i].empty()) continue;  // (consistent after all)
+            status[b] = 1;
+            bad++;
+            if (counts) counts[b] = (uint32_t)found[i].size();
+            for (uint64_t q = 0; q < found[i].size() && q < cap; q++) blocks[b * cap + q] = found[i][q];
+        }
+        *inconsistent = bad;
+        return uncorrectable ? FASTECC_E_UNCORRECTABLE : FASTECC_OK;
+    });
+}
+
 int fastecc_correct_batch(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream, uint64_t seed, uint8_t* status, uint64_t* inconsistent)
 {
     if (!status || !inconsistent) return FASTECC_E_INVAL;
@@ -975,33 +1300,117 @@ int fastecc_correct_batch(fastecc_ctx* c, void* data, void* parity, uint64_t cou
     DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
     return guarded([&]() -> int {
-        std::vector<uint8_t> flag;
+        hipStream_t hst = (hipStream_t)stream;
+        const int mode = c->correct_batch_mode;
+        std::vector<uint8_t> flag, state;
+        std::vector<uint64_t> list;
+        std::vector<std::vector<uint32_t>> found;
+        std::vector<uint32_t> absent;
+        bool grouped = false;
         {
             CallLock lk(c->mu);
-            const int r = verify_batch_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, seed, (hipStream_t)stream, flag);
+            int r = verify_batch_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, seed, hst, flag);
             if (r != FASTECC_OK) return r;
+            for (uint64_t b = 0; b < count; b++)
+                if (flag[b]) list.push_back(b);
+            // one stripe has nothing to share; mode 0 groups from two qualifying stripes on
+            if (mode != 2 && list.size() >= (mode == 1 ? 1u : 2u)) {
+                if ((r = locate_list(c, (const uint32_t*)data, (const uint32_t*)parity, list, seed, hst, state, found)) != FASTECC_OK) return r;
+                const uint64_t qualify = (uint64_t)(list.size() - std::count(state.begin(), state.end(), (uint8_t)LOC_FALLBACK));
+                grouped = qualify >= (mode == 1 ? 1u : 2u);
+                if (grouped) absent = c->scrub->absent;
+            }
         }
-        // failures are rare: fastecc_correct on each inconsistent stripe through its own pointers (it takes the lock itself)
         const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
         std::vector<uint8_t> st(count, 0);
-        uint64_t bad = 0;
         bool uncorrectable = false;
-        for (uint64_t b = 0; b < count; b++) {
-            if (!flag[b]) continue;
-            bad++;
-            uint64_t found = 0;
-            const int r = fastecc_correct(c, (char*)data + b * data_bytes, (char*)parity + b * parity_bytes, FASTECC_MEM_DEVICE, stream, seed, nullptr, 0, &found);
+        // fastecc_correct on one inconsistent stripe through its own pointers (it takes the lock itself)
+        auto correct_one = [&](uint64_t b) -> int {
+            uint64_t n_found = 0;
+            const int r = fastecc_correct(c, (char*)data + b * data_bytes, (char*)parity + b * parity_bytes, FASTECC_MEM_DEVICE, stream, seed, nullptr, 0, &n_found);
             if (r == FASTECC_E_UNCORRECTABLE) {
                 st[b] = 2;
                 uncorrectable = true;
             } else if (r != FASTECC_OK) {
                 return r;
             } else {
-                st[b] = found ? 1 : 0;
+                st[b] = n_found ? 1 : 0;
+            }
+            return FASTECC_OK;
+        };
+        if (!grouped) {
+            for (uint64_t b : list) {
+                const int r = correct_one(b);
+                if (r != FASTECC_OK) return r;
+            }
+        } else {
+            // the located stripes by their lost set — located blocks and blocks named absent — in the order the first stripe of each set appears
+            std::map<std::vector<uint32_t>, size_t> group_of;
+            std::vector<std::vector<uint32_t>> lost_sets;
+            std::vector<std::vector<uint64_t>> members;
+            uint64_t repaired = 0;
+            for (size_t i = 0; i < list.size(); i++) {
+                if (state[i] == LOC_UNCORRECTABLE) {
+                    st[list[i]] = 2;
+                    uncorrectable = true;
+                }
+                if (state[i] != LOC_FOUND || found[i].empty()) continue;
+                std::vector<uint32_t> lost(found[i]);
+                lost.insert(lost.end(), absent.begin(), absent.end());
+                std::sort(lost.begin(), lost.end());
+                auto it = group_of.find(lost);
+                if (it == group_of.end()) {
+                    it = group_of.emplace(lost, lost_sets.size()).first;
+                    lost_sets.push_back(lost);
+                    members.emplace_back();
+                }
+                members[it->second].push_back(list[i]);
+                repaired++;
+            }
+            if (repaired) {
+                std::vector<uint64_t> order;  // the groups' stripes back to back: group g at its offset
+                for (const auto& mb : members) order.insert(order.end(), mb.begin(), mb.end());
+                // the lists the repair launches read live on the device for this call only (the repair runs outside the scrub state's lock)
+                struct DeviceList {
+                    uint64_t* p = nullptr;
+                    ~DeviceList()
+                    {
+                        if (p) (void)hipFree(p);
+                    }
+                } dl;
+                HIP_TRY(hipMalloc((void**)&dl.p, order.size() * 8));
+                HIP_TRY(hipMemcpy(dl.p, order.data(), order.size() * 8, hipMemcpyHostToDevice));
+                uint64_t at = 0;
+                for (size_t g = 0; g < members.size(); g++) {
+                    std::vector<uint8_t> dp(c->K, 1), pp(c->Mu, 1);
+                    for (uint32_t j : lost_sets[g]) (j < c->K ? dp[j] : pp[j - c->K]) = 0;
+                    int r = fastecc_decode_prepare(c, dp.data(), pp.data());
+                    if (r != FASTECC_OK) return r;
+                    if ((r = repair_list(c, data, parity, order.data() + at, dl.p + at, members[g].size(), stream)) != FASTECC_OK) return r;
+                    at += members[g].size();
+                }
+                // the closing verify of fastecc_correct for all of them at once: its second seed, every block read (the stripes are whole now)
+                uint64_t seed2 = seed ^ 0x5C7B5C7B5C7B5C7Bull;
+                seed2 = splitmix64(seed2);
+                std::vector<uint8_t> still;
+                {
+                    CallLock lk(c->mu);
+                    const int r = verify_list_locked(c, (const uint32_t*)data, (const uint32_t*)parity, order, seed2, hst, false, still);
+                    if (r != FASTECC_OK) return r;
+                }
+                for (size_t i = 0; i < order.size(); i++) {
+                    st[order[i]] = still[i] ? 2 : 1;
+                    uncorrectable = uncorrectable || still[i];
+                }
+            }
+            for (size_t i = 0; i < list.size(); i++) {
+                if (state[i] != LOC_FALLBACK) continue;
+                const int r = correct_one(list[i]);
+                if (r != FASTECC_OK) return r;
             }
         }
         std::copy(st.begin(), st.end(), status);
-        *inconsistent = bad;
+        *inconsistent = list.size();
         return uncorrectable ? FASTECC_E_UNCORRECTABLE : FASTECC_OK;
     });
 }

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 350 /* 0.3.5: fastecc_scrub_erasures (scrub of degraded stripes: verify, locate and correct with named erasures) */
+#define FASTECC_VERSION 360 /* 0.3.6: fastecc_locate_errors_batch; fastecc_correct_batch locates in one pass and repairs by lost-block pattern */
 
 enum {
     FASTECC_OK = 0,
@@ -447,11 +447,35 @@ int fastecc_correct(fastecc_ctx *ctx, void *data, void *parity, int mem_kind, vo
  * not 4-byte aligned, byte sizes beyond 64 bits.  A refused call writes nothing.  Synchronous: ordered after prior work on `stream`.
  *   fastecc_verify_batch  : consistent[b] (host, count bytes) = 1 exactly when fastecc_verify with the same seed reports stripe b
  *                           consistent, else 0; *inconsistent = the number of zeros.  Reads only.
- *   fastecc_correct_batch : fastecc_verify_batch, then fastecc_correct with the same seed on each inconsistent stripe through its own
- *                           pointers — this REPLACES the context's prepared erasure pattern.  status[b] (host, count bytes): 0 = consistent
- *                           and untouched, 1 = corrected, 2 = uncorrectable (fastecc_correct's guarantee and refusal, per stripe);
- *                           *inconsistent = the number of non-zero entries.  Returns FASTECC_E_UNCORRECTABLE if any stripe has status 2,
- *                           with status filled for every stripe either way.
+ *   fastecc_correct_batch : fastecc_verify_batch, then what fastecc_correct with the same seed does to each inconsistent stripe — this
+ *                           REPLACES the context's prepared erasure pattern; which pattern is left behind is unspecified.  status[b]
+ *                           (host, count bytes): 0 = consistent and untouched, 1 = corrected, 2 = uncorrectable (fastecc_correct's
+ *                           guarantee and refusal, per stripe); *inconsistent = the number of non-zero entries.  Returns
+ *                           FASTECC_E_UNCORRECTABLE if any stripe has status 2, with status filled for every stripe either way.
+ *                           Option "correct_batch_mode" (at call time) chooses how: 2 = fastecc_correct on each inconsistent stripe through
+ *                           its own pointers, one after the other; 1 = the grouped path: one batched location pass over the inconsistent
+ *                           stripes (as fastecc_locate_errors_batch), the located stripes grouped by their lost set (located blocks and
+ *                           blocks named absent), one fastecc_decode_prepare and one repair over the group's stripes per distinct set
+ *                           (fastecc_repair_batch's choice of kernel, option "decode_batch_kernel" included), and one closing verify
+ *                           over all repaired stripes with fastecc_correct's second seed; 0 (default) = the grouped path when at least two
+ *                           inconsistent stripes qualify for it, else the loop.  Status bytes and the pool's bytes are the same in every
+ *                           mode.  Uncorrectable stripes and consistent stripes are never written.
+ *   fastecc_locate_errors_batch : fastecc_locate_errors for every stripe of the pool.  status[b] (host, count bytes): 0 = consistent,
+ *                           1 = located, 2 = cannot be located (where fastecc_locate_errors returns FASTECC_E_UNCORRECTABLE); counts[b]
+ *                           (host, count words) = the full number of located blocks, 0 for status 0 and 2; blocks[b*cap + i], i <
+ *                           min(counts[b], cap), = their codeword indices, increasing, as fastecc_locate_errors lists them (absent blocks
+ *                           are not listed) — entries beyond that are not written; *inconsistent = the number of non-zero statuses.
+ *                           Reads only.  Returns FASTECC_E_UNCORRECTABLE if any status is 2, with every output filled.  FASTECC_E_INVAL as
+ *                           for fastecc_verify_batch, and for a null status or inconsistent, or null blocks or counts with cap > 0.
+ *                           The answer of every stripe is the one fastecc_locate_errors gives with the same seed and named erasures.
+ * Batched location: the inconsistent stripes are read a second time by a list form of the verify pass that
+ * gathers all n - k - w syndromes of every fingerprint column; the host runs fastecc_locate_errors' Berlekamp-Massey decisions per stripe;
+ * one root search evaluates all locators; the confirmation checks that every syndrome of every column obeys the chosen locator's
+ * recurrence, which holds exactly when fastecc_locate_errors' own confirmation does.  Two synchronisations per chunk, none per stripe.
+ * Two kinds of stripes go through the single-stripe code with their own pointers instead, with the same answers: a stripe in which a
+ * present block holds a word >= p (those blocks are further known erasures of that stripe alone), and every stripe of a code with
+ * n - k - w > 512 (the batched pass gathers every syndrome, so their number is bounded: 512 is twice the default "locate_max").
+ * Profile scopes of these paths: "fingerprint_batch_list", "scrub_syndromes_gather", "scrub_root_search_batch", "direct_pass_list".
  * Why the answer is the per-stripe one, bit for bit: the fingerprint of a block depends on its words and the seed only, and the syndrome
  * transform acts on each word column of the fingerprint stripe on its own.  The batch puts stripe b's three fingerprint columns at word
  * columns 4b .. 4b+2 of one stripe of NC rows and runs the single-stripe transform once over all of them: every column sees exactly the
@@ -466,6 +490,8 @@ int fastecc_verify_batch(fastecc_ctx *ctx, const void *data, const void *parity,
                          uint8_t *consistent, uint64_t *inconsistent);
 int fastecc_correct_batch(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, void *stream, uint64_t seed, uint8_t *status,
                           uint64_t *inconsistent);
+int fastecc_locate_errors_batch(fastecc_ctx *ctx, const void *data, const void *parity, uint64_t count, void *stream, uint64_t seed,
+                                uint8_t *status, uint64_t *blocks, uint64_t cap, uint32_t *counts, uint64_t *inconsistent);
 
 /*
  * Small writes: bring the parity up to date after `count` data blocks changed, without reading the rest of the stripe.  The code is
@@ -616,7 +642,10 @@ const char *fastecc_plan_string(fastecc_ctx *ctx);
  *   "decode_batch_kernel" = 0 / 1 / 2 (default 0 = choose; at call time): how fastecc_decode_batch / _repair_batch run a direct-path pass — 1 = one
  *                  launch over all stripes whenever the pass allows it, 2 = stripe by stripe (direct_kernel then picks the kernel).  Same bits either way;
  *   "scrub_batch_chunk" = 0 .. INT_MAX (default 0 = the context's chunk capacity; at call time): the most stripes per chunk of
- *                  fastecc_verify_batch / _correct_batch.  Same answers either way;
+ *                  fastecc_verify_batch / _correct_batch / _locate_errors_batch.  Same answers either way;
+ *   "correct_batch_mode" = 0 / 1 / 2 (default 0 = choose; at call time): how fastecc_correct_batch corrects the inconsistent stripes — 1 = batched
+ *                  location and one repair per lost-block pattern for every stripe that qualifies, 2 = fastecc_correct stripe by stripe, 0 = 1 when
+ *                  at least two inconsistent stripes qualify, else 2.  Same status and same bytes either way;
  *   "fuse_radix" = 0 / 1 (default 1; mixed-radix contexts): the odd-radix level fused into the outer tile passes, or as its own passes;
  *   "slabs" = H (1..32): encode H column slabs of the stripe on internal streams, each one pass
  * behind the previous, so that different kinds of passes overlap on the GPU, or with "slab_mode" = 1 one
