@@ -23,6 +23,8 @@ CODE_MIXED_RADIX = 1  # fastecc_create_ex flag: transform order q * 2^m, q in {1
 CODE_MIXED_RADIX_PFA = 4  # ... and the composite q = 21, 35, 39, 45, 63, 65, 91, 105, 117 (prime-factor map)
 CODE_TOP_RADIX2 = 2  # fastecc_create_ex flag (A/B experiment): the top level of a power-of-two transform through the fused odd-radix kernel
 
+PATTERN_NONE = 0xFFFFFFFF  # pattern_of entry of decode_batch_set / repair_batch_set: the stripe is neither read nor written
+
 OK, E_INVAL, E_NOMEM, E_DEVICE, E_UNSUPPORTED, E_UNCORRECTABLE = 0, -1, -2, -3, -4, -5
 
 _LIB = None
@@ -98,6 +100,9 @@ def lib():
     L.fastecc_repair.argtypes, L.fastecc_repair.restype = [vp, vp, vp, i32, vp], i32
     L.fastecc_decode_batch.argtypes, L.fastecc_decode_batch.restype = [vp, vp, vp, u64, vp], i32
     L.fastecc_repair_batch.argtypes, L.fastecc_repair_batch.restype = [vp, vp, vp, u64, vp], i32
+    L.fastecc_decode_prepare_set.argtypes, L.fastecc_decode_prepare_set.restype = [vp, u8p, u8p, u64], i32
+    L.fastecc_decode_batch_set.argtypes, L.fastecc_decode_batch_set.restype = [vp, vp, vp, u64, ctypes.POINTER(u32), vp], i32
+    L.fastecc_repair_batch_set.argtypes, L.fastecc_repair_batch_set.restype = [vp, vp, vp, u64, ctypes.POINTER(u32), vp], i32
     L.fastecc_scrub_erasures.argtypes, L.fastecc_scrub_erasures.restype = [vp, u8p, u8p], i32
     L.fastecc_verify.argtypes, L.fastecc_verify.restype = [vp, vp, vp, i32, vp, u64, ctypes.POINTER(i32)], i32
     for name in ("locate_errors", "correct"):
@@ -317,6 +322,60 @@ class Encoder:
         """repair of `count` stripes back to back in device memory, all with the prepared erasure pattern."""
         count = self._batch_count(count)
         _check(lib().fastecc_repair_batch(self._h, _addr(data), _addr(parity), count, stream or None), "fastecc_repair_batch")
+        return data, parity
+
+    def decode_prepare_set(self, data_present, parity_present):
+        """A set of P erasure patterns for decode_batch_set / repair_batch_set: P rows of k data flags and P rows of n - k parity flags
+        (truthy = the block survives); every pattern loses at most 16 blocks and keeps at least k.  P = 0 (two empty arguments) clears the
+        set.  Independent of the decode_prepare pattern."""
+        import numpy as np
+        P = len(data_present)
+        if len(parity_present) != P:
+            raise ValueError("need as many rows of parity flags as of data flags")
+        m = self.n - self.k
+        if P and (any(len(r) != self.k for r in data_present) or any(len(r) != m for r in parity_present)):
+            raise ValueError("need P x k data flags and P x (n - k) parity flags")
+
+        def flat(v, width):
+            # a contiguous uint8 numpy array goes through as it is; anything else is converted
+            if isinstance(v, np.ndarray) and v.dtype.itemsize == 1 and v.flags["C_CONTIGUOUS"]:
+                return v
+            return np.ascontiguousarray(np.asarray(v, dtype=bool).reshape(P, width), dtype=np.uint8)
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        dp, pp = (flat(data_present, self.k), flat(parity_present, m)) if P else (None, None)
+        _check(lib().fastecc_decode_prepare_set(self._h, dp.ctypes.data_as(u8p) if P else None, pp.ctypes.data_as(u8p) if P else None, P),
+               "fastecc_decode_prepare_set")
+
+    @staticmethod
+    def _pattern_list(pattern_of, count):
+        """(object to keep alive, uint32 pointer) of the `count` pattern indices of a set call"""
+        import numpy as np
+        if len(pattern_of) != count:
+            raise ValueError("pattern_of needs one entry per stripe")
+        if isinstance(pattern_of, np.ndarray) and pattern_of.dtype == np.uint32 and pattern_of.flags["C_CONTIGUOUS"]:
+            arr = pattern_of
+        else:
+            idx = [int(q) for q in pattern_of]
+            if any(q < 0 or q > PATTERN_NONE for q in idx):
+                raise ValueError("a pattern index is a uint32")
+            arr = np.array(idx, dtype=np.uint32)
+        return arr, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+
+    def decode_batch_set(self, data, parity, count, pattern_of, stream=0):
+        """`count` stripes back to back in device memory, stripe b with pattern pattern_of[b] of the prepared set (PATTERN_NONE: the stripe
+        is not touched): decode of each (parity is read only)."""
+        count = self._batch_count(count)
+        keep, po = self._pattern_list(pattern_of, count)
+        _check(lib().fastecc_decode_batch_set(self._h, _addr(data), _addr(parity), count, po, stream or None), "fastecc_decode_batch_set")
+        del keep
+        return data
+
+    def repair_batch_set(self, data, parity, count, pattern_of, stream=0):
+        """repair of `count` stripes back to back in device memory, stripe b with pattern pattern_of[b] of the prepared set."""
+        count = self._batch_count(count)
+        keep, po = self._pattern_list(pattern_of, count)
+        _check(lib().fastecc_repair_batch_set(self._h, _addr(data), _addr(parity), count, po, stream or None), "fastecc_repair_batch_set")
+        del keep
         return data, parity
 
     def scrub_erasures(self, data_present=None, parity_present=None):

@@ -107,6 +107,7 @@ CtxInfo info_of(const fastecc_ctx* c)
     return CtxInfo{c->device, c->field, c->fold, c->cosets, c->n, c->N, c->S, c->ld, c->K != c->N || c->Mu != c->M, c->K, c->Mu, c->q, c->decode_direct_max, c->direct_kernel, c->p61_stride, c->decode_split, c->decode_batch_kernel};
 }
 DecodeState*& decoder_of(fastecc_ctx* c) { return c->decoder; }
+PatternSet*& pattern_set_of(fastecc_ctx* c) { return c->pattern_set; }
 Sharded*& sharded_of(fastecc_ctx* c) { return c->sharded; }
 p61::Decoder*& decoder61_of(fastecc_ctx* c) { return c->decoder61; }
 p61::Path* p61_path_of(fastecc_ctx* c) { return c->p61; }
@@ -162,6 +163,8 @@ void fastecc_destroy(fastecc_ctx* c)
     c->sharded = nullptr;
     destroy_decode_state(c->decoder);
     c->decoder = nullptr;
+    destroy_pattern_set(c->pattern_set);
+    c->pattern_set = nullptr;
     destroy_scrub_state(c->scrub);
     c->scrub = nullptr;
     destroy_update_state(c->update);

@@ -163,6 +163,48 @@ void destroy_decode_state(DecodeState* d)
     delete d;
 }
 
+// The direct path's tables of one erasure pattern (Prepare::direct_tables): which passes it takes and their weights
+struct PatternTables {
+    DirectPass* data = nullptr;    // the lost data blocks (only data lost, or more than 32 blocks lost in all)
+    DirectPass* parity = nullptr;  // the lost parity blocks from the complete data (only parity lost, or more than 32 in all)
+    DirectPass* both = nullptr;    // data AND parity lost, at most 32 in all: the single pass
+    bool both_built = false;       // `both` holds this pattern
+    bool only_both = false;        // ... and is its only pass
+    int ed = 0, ep = 0;            // lost data / parity blocks
+    bool host_nomem = false;       // direct_tables' FASTECC_E_NOMEM is the host's (no DirectPass object), not the device's (no room for a table)
+};
+
+// A pattern set (fastecc_decode_prepare_set): P patterns of at most 16 lost blocks, each exactly one direct pass, for pools in which the pattern
+// differs from stripe to stripe (fastecc_decode_batch_set / _repair_batch_set).  Independent of the DecodeState's single pattern.
+struct PatternSet {
+    enum : uint8_t { NOTHING = 0, DATA = 1, PARITY = 2, BOTH = 3 };  // which pass a pattern takes (NOTHING: no block lost)
+    std::vector<PatternTables> tables;  // per pattern
+    std::vector<uint8_t> kind;          // ... its pass
+    std::vector<uint8_t> cls;           // ... log2 of that pass's pad (1, 2, 4, 8, 16): the class a launch is templated on
+    std::vector<uint32_t> rows;         // ... the rows it reads
+    DirectSetPass* d_passes = nullptr;  // device: the descriptor table, entry q = pattern q's pass
+    // one call's entries, sorted by class: written into the pinned h_list and copied to d_list on the call's stream.  d_list is an internal buffer
+    // (ordered between streams by the context's buf_event); h_list is free again once list_event (the end of that copy) has passed.
+    DirectSetEntry* h_list = nullptr;
+    DirectSetEntry* d_list = nullptr;
+    size_t list_cap = 0;  // entries of each
+    hipEvent_t list_event = nullptr;
+    bool list_pending = false;
+    DirectPass* pass(uint64_t q) const { return kind[q] == DATA ? tables[q].data : kind[q] == PARITY ? tables[q].parity : tables[q].both; }
+};
+
+void destroy_pattern_set(PatternSet* s)
+{
+    if (!s) return;
+    for (PatternTables& t : s->tables)
+        for (DirectPass* p : {t.data, t.parity, t.both}) direct_pass_free(p);
+    if (s->d_passes) (void)hipFree(s->d_passes);
+    if (s->h_list) (void)hipHostFree(s->h_list);
+    if (s->d_list) (void)hipFree(s->d_list);
+    if (s->list_event) (void)hipEventDestroy(s->list_event);
+    delete s;
+}
+
 namespace {
 
 // ------------------------------------------------------------------------------------------------
@@ -839,6 +881,55 @@ struct Prepare {
         return limit;
     }
 
+    // The direct path's tables of one pattern: the lost data blocks R (each a fixed linear combination of the surviving data blocks and of the
+    // surviving parity blocks A, one per lost data block), the lost parity blocks Pl.  Data AND parity lost, at most 32 in all: one pass, `both`
+    // (the lost parity blocks as further outputs on the data pass's nodes); else `data` for the lost data and `parity` (from the complete data)
+    // for the lost parity.  Passes are allocated where t holds none yet.  Takes no lock and touches no context state: the single pattern's
+    // fastecc_decode_prepare (direct) and every pattern of a set (prepare_set_impl) come through here.
+    int direct_tables(const std::vector<uint32_t>& R, const std::vector<uint32_t>& Pl, const std::vector<uint32_t>& A, PatternTables& t, PhaseTimer& ptd)
+    {
+        const int ed = (int)R.size(), ep = (int)Pl.size();
+        int rc = FASTECC_OK;
+        t.ed = ed;
+        t.ep = ep;
+        const uint32_t K = (uint32_t)ci.user_k;
+        const uint32_t w = gf::h_root((uint32_t)NC), wd = gf::h_pow(w, 1ull << e);  // data row i sits at wd^i
+        std::vector<uint32_t> xr(ed), ya(ed);  // the points of the lost data blocks and of their parity nodes
+        for (int r = 0; r < ed; r++) xr[r] = gf::h_pow(w, (uint64_t)R[r] << e);
+        for (int a = 0; a < ed; a++) ya[a] = gf::h_pow(w, parity_position(A[a]));
+        // (up to 32 outputs a pass costs the read of the survivors whatever it computes, profiles/r03/direct_bench.jsonl: one table then serves decode and repair)
+        t.only_both = ed > 0 && ep > 0 && ed + ep <= 32;
+        if (ed > 0 && !t.only_both) {
+            if (!t.data && !(t.data = direct_pass_new())) return t.host_nomem = true, FASTECC_E_NOMEM;
+            rc = direct_build_interp(t.data, wd, N, K, R, xr, A, ya, nullptr);
+        }
+        ptd.mark("few losses: data table");
+        t.both_built = false;
+        if (rc == FASTECC_OK && ep > 0) {
+            std::vector<uint32_t> yt(ep), ct(ep), pos(ep);
+            const uint32_t inv_N = gf::h_inv((uint32_t)(N % gf::P));
+            for (int i = 0; i < ep; i++) {
+                yt[i] = gf::h_pow(w, parity_position(Pl[i]));
+                ct[i] = gf::h_mul((uint32_t)(((uint64_t)gf::h_pow(yt[i], N) + gf::P - 1u) % gf::P), inv_N);  // (y_t^N - 1) / N
+                pos[i] = 2u * Pl[i] + 1u;
+            }
+            if (t.only_both) {
+                // data lost as well, few outputs: fastecc_repair reads the survivors ONCE — the lost parity blocks are further outputs on the data
+                // pass's nodes (the surviving data and as many parity blocks), not a second pass over the repaired data.  (Above 32 outputs the
+                // matrix cores bound the pass, not the read: 128 + 128 lost take 2.40 ms in one pass, 2.48 in two, and the set-up of the second
+                // 256-output table costs 0.9 ms.)
+                if (!t.both && !(t.both = direct_pass_new())) return t.host_nomem = true, FASTECC_E_NOMEM;
+                rc = direct_build_interp(t.both, wd, N, K, R, xr, A, ya, nullptr, &yt, &pos);
+                t.both_built = rc == FASTECC_OK;
+            } else {
+                if (!t.parity && !(t.parity = direct_pass_new())) return t.host_nomem = true, FASTECC_E_NOMEM;
+                rc = direct_build_lagrange(t.parity, wd, K, yt, ct, pos, nullptr);
+            }
+        }
+        ptd.mark("few losses: parity table");
+        return rc;
+    }
+
     // Every lost data block is a fixed linear combination of the surviving data blocks and as many surviving parity blocks, the lost parity blocks
     // one of the data; decided before any per-position table is built.  *done = false: too many losses, or no memory for the weight tables —
     // the transform path needs none of them.
@@ -868,42 +959,14 @@ struct Prepare {
         int rc = call.wait_idle();  // a decode still using the previous pattern
         if (rc != FASTECC_OK) return rc;
         ptd.mark("few losses: lock, idle");
-        const uint32_t K = (uint32_t)ci.user_k;
-        const uint32_t w = gf::h_root((uint32_t)NC), wd = gf::h_pow(w, 1ull << e);  // data row i sits at wd^i
-        std::vector<uint32_t> xr(ed), ya(ed);  // the points of the lost data blocks and of their parity nodes
-        for (int r = 0; r < ed; r++) xr[r] = gf::h_pow(w, (uint64_t)R[r] << e);
-        for (int a = 0; a < ed; a++) ya[a] = gf::h_pow(w, parity_position(A[a]));
-        // (up to 32 outputs a pass costs the read of the survivors whatever it computes, profiles/r03/direct_bench.jsonl: one table then serves decode and repair)
-        d->sub_only_both = ed > 0 && ep > 0 && ed + ep <= 32;
-        if (ed > 0 && !d->sub_only_both) {
-            if (!d->direct_data && !(d->direct_data = direct_pass_new())) return FASTECC_E_NOMEM;
-            rc = direct_build_interp(d->direct_data, wd, N, K, R, xr, A, ya, nullptr);
-        }
-        ptd.mark("few losses: data table");
-        d->sub_both = false;
-        if (rc == FASTECC_OK && ep > 0) {
-            std::vector<uint32_t> yt(ep), ct(ep), pos(ep);
-            const uint32_t inv_N = gf::h_inv((uint32_t)(N % gf::P));
-            for (int t = 0; t < ep; t++) {
-                yt[t] = gf::h_pow(w, parity_position(Pl[t]));
-                ct[t] = gf::h_mul((uint32_t)(((uint64_t)gf::h_pow(yt[t], N) + gf::P - 1u) % gf::P), inv_N);  // (y_t^N - 1) / N
-                pos[t] = 2u * Pl[t] + 1u;
-            }
-            if (d->sub_only_both) {
-                // data lost as well, few outputs: fastecc_repair reads the survivors ONCE — the lost parity blocks are further outputs on the data
-                // pass's nodes (the surviving data and as many parity blocks), not a second pass over the repaired data.  (Above 32 outputs the
-                // matrix cores bound the pass, not the read: 128 + 128 lost take 2.40 ms in one pass, 2.48 in two, and the set-up of the second
-                // 256-output table costs 0.9 ms.)
-                if (!d->direct_both && !(d->direct_both = direct_pass_new())) return FASTECC_E_NOMEM;
-                rc = direct_build_interp(d->direct_both, wd, N, K, R, xr, A, ya, nullptr, &yt, &pos);
-                d->sub_both = rc == FASTECC_OK;
-            } else {
-                if (!d->direct_parity && !(d->direct_parity = direct_pass_new())) return FASTECC_E_NOMEM;
-                rc = direct_build_lagrange(d->direct_parity, wd, K, yt, ct, pos, nullptr);
-            }
-        }
-        ptd.mark("few losses: parity table");
-        if (rc == FASTECC_E_NOMEM) return FASTECC_OK;  // no memory for the weight tables: the transform path
+        PatternTables t{d->direct_data, d->direct_parity, d->direct_both};  // the state's passes are built over from pattern to pattern
+        rc = direct_tables(R, Pl, A, t, ptd);
+        d->direct_data = t.data;
+        d->direct_parity = t.parity;
+        d->direct_both = t.both;
+        d->sub_only_both = t.only_both;
+        d->sub_both = t.both_built;
+        if (rc == FASTECC_E_NOMEM && !t.host_nomem) return FASTECC_OK;  // no memory for the weight tables: the transform path
         if (rc != FASTECC_OK) return rc;
         d->sub = true;
         d->sub_lost_data = ed;
@@ -1841,6 +1904,200 @@ int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, 
     });
 }
 
+// ---- fastecc_decode_prepare_set / _decode_batch_set / _repair_batch_set: a pattern per stripe ----
+constexpr uint64_t SET_MAX_PATTERNS = 4096;
+constexpr size_t SET_MAX_LOST = 16;  // one direct pass of a single sweep: pad <= 16
+
+// The new set is built aside and swapped in at the end: a refused or failed call leaves the previous one in force.
+int prepare_set_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t* parity_present, uint64_t P)
+{
+    if (!c || P > SET_MAX_PATTERNS || (P > 0 && (!data_present || !parity_present))) return FASTECC_E_INVAL;
+    if (sharded_of(c)) return FASTECC_E_UNSUPPORTED;
+    const CtxInfo ci = info_of(c);
+    if (ci.field != FASTECC_FIELD_GF_FFF00001 || ci.pitch != ci.words || ci.user_k >= 0xFFFFFFF0ull) return FASTECC_E_UNSUPPORTED;
+    // every pattern's lists first, on the host: lost data blocks, lost parity blocks, the surviving parity blocks that serve as nodes
+    struct Lists {
+        std::vector<uint32_t> R, Pl, A;
+    };
+    std::vector<Lists> lists(P);
+    bool too_many = false;
+    for (uint64_t q = 0; q < P; q++) {
+        const uint8_t* dp = data_present + q * ci.user_k;
+        const uint8_t* pp = parity_present + q * ci.user_m;
+        Lists& l = lists[q];
+        uint64_t lost = 0;
+        each_lost(dp, ci.user_k, [&](uint64_t i) {
+            if (++lost <= SET_MAX_LOST) l.R.push_back((uint32_t)i);
+            return true;
+        });
+        each_lost(pp, ci.user_m, [&](uint64_t j) {
+            if (++lost <= SET_MAX_LOST) l.Pl.push_back((uint32_t)j);
+            return true;
+        });
+        if (lost > ci.user_m) return FASTECC_E_INVAL;  // fewer than k blocks survive: not decodable
+        too_many |= lost > SET_MAX_LOST;
+        for (uint64_t j = 0; j < ci.user_m && !too_many && l.A.size() < l.R.size(); j++)
+            if (pp[j]) l.A.push_back((uint32_t)j);
+    }
+    if (too_many) return FASTECC_E_UNSUPPORTED;
+    DeviceGuard dg(ci.device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallScope call(c);
+    PatternSet*& slot = pattern_set_of(c);
+    PatternSet* fresh = nullptr;
+    struct DropFresh {  // (whatever was built goes unless it became the context's set)
+        PatternSet*& f;
+        ~DropFresh() { destroy_pattern_set(f); }
+    } drop{fresh};
+    if (P > 0) {
+        if (!(fresh = new (std::nothrow) PatternSet())) return FASTECC_E_NOMEM;
+        fresh->tables.resize(P);
+        fresh->kind.assign(P, PatternSet::NOTHING);
+        fresh->cls.assign(P, 0);
+        fresh->rows.assign(P, 0);
+        std::vector<DirectSetPass> desc(P, DirectSetPass{});
+        Prepare geometry(c, nullptr, nullptr);
+        PhaseTimer pt("[fastecc prepare_set]"), quiet;  // one line per set, not two per pattern
+        quiet.on = false;
+        for (uint64_t q = 0; q < P; q++) {
+            const Lists& l = lists[q];
+            if (l.R.empty() && l.Pl.empty()) continue;  // nothing lost: its stripes are not touched
+            int rc = geometry.direct_tables(l.R, l.Pl, l.A, fresh->tables[q], quiet);
+            if (rc != FASTECC_OK) return rc;
+            fresh->kind[q] = !l.R.empty() && !l.Pl.empty() ? PatternSet::BOTH : !l.R.empty() ? PatternSet::DATA : PatternSet::PARITY;
+            if ((rc = direct_set_describe(fresh->pass(q), &desc[q])) != FASTECC_OK) return rc;
+            while ((1u << fresh->cls[q]) < desc[q].cstride) fresh->cls[q]++;
+            fresh->rows[q] = desc[q].rows;
+        }
+        HIP_TRY(hipMalloc((void**)&fresh->d_passes, P * sizeof(DirectSetPass)));
+        HIP_TRY(hipMemcpy(fresh->d_passes, desc.data(), P * sizeof(DirectSetPass), hipMemcpyHostToDevice));
+        pt.mark("tables of the set");
+    }
+    const int rc = call.wait_idle();  // device work that still uses the previous set (its tables, its list buffer)
+    if (rc != FASTECC_OK) return rc;
+    if (fresh && slot) {  // the list buffers outlive a set
+        std::swap(fresh->h_list, slot->h_list);
+        std::swap(fresh->d_list, slot->d_list);
+        std::swap(fresh->list_cap, slot->list_cap);
+        std::swap(fresh->list_event, slot->list_event);
+        fresh->list_pending = slot->list_pending = false;  // (the wait above outlasted the last copy out of h_list)
+    }
+    std::swap(slot, fresh);  // (DropFresh frees the previous set)
+    return FASTECC_OK;
+}
+
+// h_list / d_list for `entries` entries, h_list free to be written: a call whose predecessor's list is still on its way to the device waits for
+// that copy's event (not for the device); growing waits for the last use of the device buffer and allocates (update.hip: batch_list_buffers).
+int set_list_buffers(CallScope& call, PatternSet* s, size_t entries)
+{
+    if (!s->list_event) HIP_TRY(hipEventCreateWithFlags(&s->list_event, hipEventDisableTiming));
+    if (s->list_pending) {
+        HIP_TRY(hipEventSynchronize(s->list_event));
+        s->list_pending = false;
+    }
+    if (entries <= s->list_cap) return FASTECC_OK;
+    const size_t cap = std::max<size_t>(std::max<size_t>(entries, 2 * s->list_cap), 4096);
+    const int rc = call.wait_idle();  // the kernels that read d_list
+    if (rc != FASTECC_OK) return rc;
+    if (s->h_list) (void)hipHostFree(s->h_list);
+    if (s->d_list) (void)hipFree(s->d_list);
+    s->h_list = s->d_list = nullptr;
+    s->list_cap = 0;
+    HIP_TRY(hipHostMalloc((void**)&s->h_list, cap * sizeof(DirectSetEntry), hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void**)&s->d_list, cap * sizeof(DirectSetEntry)));
+    s->list_cap = cap;
+    return FASTECC_OK;
+}
+
+// `count` stripes back to back in device memory, stripe b with pattern pattern_of[b] of the prepared set (FASTECC_PATTERN_NONE: not touched).
+// The stripes that have work are sorted by the pad class of their pattern's pass; a class is ONE launch of direct_set_kernel when all its passes
+// read fewer than 4096 rows (from 4096 data rows on, the single-stripe path takes the matrix cores), else direct_run stripe by stripe with each
+// stripe's own table; option "decode_batch_kernel" decides when set.
+int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, void* stream, bool repair)
+{
+    if (!c || !data || !parity || !pattern_of || count == 0 || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
+    if (sharded_of(c)) return FASTECC_E_UNSUPPORTED;
+    CallScope call(c);
+    const CtxInfo ci = info_of(c);
+    if (ci.field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
+    if (ci.pitch != ci.words) return FASTECC_E_UNSUPPORTED;  // stripes of a pool are contiguous
+    const uint64_t block = ci.words * 4, data_bytes = ci.user_k * block, parity_bytes = ci.user_m * block;
+    if (count > UINT64_MAX / data_bytes || count > UINT64_MAX / parity_bytes) return FASTECC_E_INVAL;
+    if ((uint64_t)(uintptr_t)data > UINT64_MAX - count * data_bytes || (uint64_t)(uintptr_t)parity > UINT64_MAX - count * parity_bytes) return FASTECC_E_INVAL;
+    PatternSet* s = pattern_set_of(c);
+    if (!s) return FASTECC_E_INVAL;  // fastecc_decode_prepare_set first
+    const uint64_t P = s->tables.size();
+    constexpr int CLASSES = 5;
+    // the pass stripe b takes in this call: none for FASTECC_PATTERN_NONE, a pattern that lost nothing, and (decode) one that lost only parity
+    auto work_of = [&](uint32_t q) { return q != FASTECC_PATTERN_NONE && s->kind[q] != PatternSet::NOTHING && (repair || s->kind[q] != PatternSet::PARITY); };
+    uint64_t per_class[CLASSES] = {}, total = 0;
+    uint32_t rows_max[CLASSES] = {};
+    for (uint64_t b = 0; b < count; b++) {
+        const uint32_t q = pattern_of[b];
+        if (q != FASTECC_PATTERN_NONE && q >= P) return FASTECC_E_INVAL;
+        if (!work_of(q)) continue;
+        per_class[s->cls[q]]++;
+        rows_max[s->cls[q]] = std::max(rows_max[s->cls[q]], s->rows[q]);
+        total++;
+    }
+    if (total == 0) return FASTECC_OK;
+    DeviceGuard dg(ci.device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = set_list_buffers(call, s, total);
+    if (rc != FASTECC_OK) return rc;
+    uint64_t first[CLASSES], at[CLASSES], moved[CLASSES] = {};  // a class's entries: [first, first + per_class); blocks its passes read and write
+    for (int k = 0; k < CLASSES; k++) first[k] = at[k] = k ? first[k - 1] + per_class[k - 1] : 0;
+    for (uint64_t b = 0; b < count; b++) {
+        const uint32_t q = pattern_of[b];
+        if (q != FASTECC_PATTERN_NONE && q >= P) return FASTECC_E_INVAL;  // (the caller's array changed under the call)
+        if (!work_of(q)) continue;
+        const int k = s->cls[q];
+        if (at[k] >= first[k] + per_class[k]) return FASTECC_E_INVAL;
+        s->h_list[at[k]++] = DirectSetEntry{b, q, 0};
+        moved[k] += (uint64_t)s->rows[q] + (uint64_t)s->tables[q].ed + (repair ? (uint64_t)s->tables[q].ep : 0);
+    }
+    const uint64_t S = ci.words, data_words = ci.user_k * S, parity_words = ci.user_m * S;
+    uint32_t* ddata = (uint32_t*)data;
+    uint32_t* dparity = (uint32_t*)parity;
+    const int mode = ci.decode_batch_kernel;
+    bool kernel[CLASSES], any_kernel = false;
+    for (int k = 0; k < CLASSES; k++) {
+        kernel[k] = at[k] > first[k] && (mode == 1 || (mode == 0 && rows_max[k] < 4096)) && direct_set_waves_per_entry(1 << k, data, parity, S) <= (1ull << 24);
+        any_kernel |= kernel[k];
+    }
+    if ((rc = call.begin(st)) != FASTECC_OK) return rc;
+    EndScope end{call, st};
+    if (any_kernel) {
+        HIP_TRY(hipMemcpyAsync(s->d_list, s->h_list, total * sizeof(DirectSetEntry), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(s->list_event, st));
+        s->list_pending = true;
+    }
+    for (int k = 0; k < CLASSES; k++) {
+        const uint64_t n = at[k] - first[k];
+        if (n == 0) continue;
+        if (kernel[k]) {
+            void* scope = profile_scope_begin(c, st, "direct_pass_set", moved[k] * block);
+            rc = direct_run_set(1 << k, s->d_passes, s->d_list + first[k], n, ddata, dparity, ddata, repair ? dparity : nullptr, S, data_words, parity_words, st);
+            profile_scope_end(scope);
+            if (rc != FASTECC_OK) return rc;
+            continue;
+        }
+        void* scope = profile_scope_begin(c, st, "direct_pass", moved[k] * block);
+        for (uint64_t i = first[k]; i < at[k] && rc == FASTECC_OK; i++) {
+            const uint64_t b = s->h_list[i].stripe;
+            const uint32_t q = s->h_list[i].pass;
+            uint32_t* db = ddata + b * data_words;
+            uint32_t* pb = dparity + b * parity_words;
+            const bool reads_parity = s->kind[q] != PatternSet::PARITY, writes_data = reads_parity, writes_parity = repair && s->kind[q] != PatternSet::DATA;
+            rc = direct_run(s->pass(q), db, reads_parity ? pb : nullptr, writes_data ? db : nullptr, writes_parity ? pb : nullptr, (uint32_t)S, ci.direct_kernel, st);
+        }
+        profile_scope_end(scope);
+        if (rc != FASTECC_OK) return rc;
+    }
+    return FASTECC_OK;
+}
+
 }  // namespace
 
 int repair_list(fastecc_ctx* c, void* data, void* parity, const uint64_t* host_list, const uint64_t* dev_list, uint64_t count, void* stream)
@@ -1878,6 +2135,21 @@ int fastecc_decode_batch(fastecc_ctx* c, void* data, const void* parity, uint64_
 int fastecc_repair_batch(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream)
 {
     return guarded([&]() -> int { return decode_batch_impl(c, data, parity, count, stream, true); });
+}
+
+int fastecc_decode_prepare_set(fastecc_ctx* c, const uint8_t* data_present, const uint8_t* parity_present, uint64_t n_patterns)
+{
+    return guarded([&]() -> int { return prepare_set_impl(c, data_present, parity_present, n_patterns); });
+}
+
+int fastecc_decode_batch_set(fastecc_ctx* c, void* data, const void* parity, uint64_t count, const uint32_t* pattern_of, void* stream)
+{
+    return guarded([&]() -> int { return decode_batch_set_impl(c, data, const_cast<void*>(parity), count, pattern_of, stream, false); });
+}
+
+int fastecc_repair_batch_set(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, void* stream)
+{
+    return guarded([&]() -> int { return decode_batch_set_impl(c, data, parity, count, pattern_of, stream, true); });
 }
 
 }  // extern "C"

@@ -962,6 +962,165 @@ int direct_run_batch(DirectPass* p, const uint32_t* data, const uint32_t* parity
 }
 
 // ------------------------------------------------------------------------------------------------
+// MANY STRIPES, A PATTERN PER STRIPE (fastecc_decode_batch_set / _repair_batch_set: a pool with rotated placement that lost one device).
+// The launch gets a list of entries (stripe of the pool, pass of the pattern set) and the set's table of pass descriptors — what BatchArgs
+// takes from one DirectPass, per pattern.  Weights live in SGPRs, so a wave must not span two entries: an entry owns
+// ceil(S / (64 V)) WHOLE waves, and a wave finds its entry and column base from its index in the launch (made provably uniform by
+// readfirstlane), loads the entry and its descriptor with scalar loads and masks the lanes whose column is >= S.  The row loop, the 96-bit
+// accumulators, the single reduction and the canonical store are direct_batch_kernel's; the loop bound `rows` differs per pattern and is
+// wave-uniform.  EB is the pad class of every pass of the launch (the host sorts the entries by it), which is also the row stride of
+// their weight tables ([rows][pad], pad = EB <= 16: one sweep), so no lane multiplies by padding weights of a smaller pattern.
+// Blocks shorter than 64 V words leave lanes of their wave idle (S = 1: 63 of 64) — the price of uniform weights; set_vec picks the widest
+// V that still fills a wave, and fastecc_repair_batch (lanes flattened over stripes) remains the tool for one pattern and very short blocks.
+// In place like direct_batch_kernel; here a lane reads all rows of its own columns before it writes them and nobody else touches them.
+// ------------------------------------------------------------------------------------------------
+struct SetArgs {
+    const uint32_t* data;     // stripe b's data rows at data + b * data_stride
+    const uint32_t* parity;   // ... its parity rows at parity + b * parity_stride
+    uint32_t* data_out;       // null: data outputs are skipped
+    uint32_t* parity_out;     // null: parity outputs are skipped
+    uint64_t data_stride, parity_stride;
+    const DirectSetEntry* entries;  // the launch's first entry
+    const DirectSetPass* passes;    // the set's descriptor table
+    uint32_t waves;                 // entries of the launch * waves_per_entry (at most SET_LAUNCH_WAVES)
+    uint32_t waves_per_entry;
+    uint32_t S;
+};
+using const_set_entry_ptr = const DirectSetEntry __attribute__((address_space(4)))*;
+using const_set_pass_ptr = const DirectSetPass __attribute__((address_space(4)))*;
+
+template <int EB, int V>
+__global__ __launch_bounds__(256) void direct_set_kernel(const SetArgs a)
+{
+    constexpr int U = EB >= 16 ? 2 : EB >= 8 ? 4 : 8;  // rows in flight, as in direct_batch_kernel: U * EB <= 32 weights live in SGPRs
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (w >= a.waves) return;
+    const uint32_t e = w / a.waves_per_entry, cc = w - e * a.waves_per_entry;  // (wave-uniform, 32 bits: once per wave)
+    const const_set_entry_ptr ent = (const_set_entry_ptr)(reinterpret_cast<uintptr_t>(a.entries)) + e;
+    const uint64_t b = ent->stripe;
+    const const_set_pass_ptr d = (const_set_pass_ptr)(reinterpret_cast<uintptr_t>(a.passes)) + ent->pass;
+    const uint32_t rows = d->rows, data_rows = d->data_rows, outputs = d->outputs;
+    const_u32_ptr coef = as_constant(d->coef);
+    const_u32_ptr extra = as_constant(d->extra);
+    const_u32_ptr pos = as_constant(d->pos);
+    const uint32_t c = (cc * 64u + lane) * V;  // (32 bits: cc < waves_per_entry <= 2^24 and V <= 4, so c < 2^32; direct_run_set refuses more waves)
+    const bool live = c < a.S;  // (V divides S: a live lane's V words lie inside the block)
+    const uint32_t* dbase = a.data + b * a.data_stride + c;
+    const uint64_t poff = b * a.parity_stride + c;  // (a lane's parity rows: a.parity + poff + row * S)
+    uint64_t lo[EB][V];
+    uint32_t hi[EB][V];
+#pragma unroll
+    for (int j = 0; j < EB; ++j)
+#pragma unroll
+        for (int v = 0; v < V; ++v) lo[j][v] = 0, hi[j][v] = 0;
+    for (uint32_t ub = 0; ub < rows; ub += U) {
+        uint32_t wt[U][EB], x[U][V];
+#pragma unroll
+        for (int i = 0; i < U; ++i) {
+            const uint32_t u = ub + i;
+            const bool in = u < rows;  // wave-uniform
+#pragma unroll
+            for (int j = 0; j < EB; ++j) wt[i][j] = 0;
+            if (in) {
+                const_u32_ptr cf = coef + (size_t)u * EB;
+#pragma unroll
+                for (int j = 0; j < EB; ++j) wt[i][j] = cf[j];
+            }
+#pragma unroll
+            for (int v = 0; v < V; ++v) x[i][v] = 0;
+            if (in && live) {  // a lost row holds anything: its weights are zero
+                const uint32_t* row = u < data_rows ? dbase + (size_t)u * a.S : a.parity + poff + (size_t)extra[u - data_rows] * a.S;
+                load_vec<V>(x[i], row);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < U; ++i)
+#pragma unroll
+            for (int j = 0; j < EB; ++j)
+#pragma unroll
+                for (int v = 0; v < V; ++v) mac96(lo[j][v], hi[j][v], x[i][v], wt[i][j]);
+    }
+#pragma unroll
+    for (int j = 0; j < EB; ++j) {
+        if ((uint32_t)j < outputs) {  // wave-uniform
+            const uint32_t p = pos[j];
+            uint32_t* out = (p & 1u) ? a.parity_out : a.data_out;
+            if (out && live) {  // (out == null: no stripe given for that kind of output — fastecc_decode_batch_set on a pass that also holds the lost parity blocks)
+                const uint64_t stride = (p & 1u) ? a.parity_stride : a.data_stride;
+                uint32_t r[V];
+#pragma unroll
+                for (int v = 0; v < V; ++v) r[v] = reduce96(lo[j][v], hi[j][v]);
+                store_vec<V>(out + b * stride + (size_t)(p >> 1) * a.S + c, r);
+            }
+        }
+    }
+}
+
+constexpr uint64_t SET_LAUNCH_WAVES = 1ull << 24;  // 2^30 lane groups, as LAUNCH_GROUPS of direct_run_batch
+
+int direct_set_describe(const DirectPass* p, DirectSetPass* out)
+{
+    if (!p || !p->built || p->pad > 16) return FASTECC_E_INVAL;  // (one sweep: at most 16 outputs)
+    *out = DirectSetPass{p->coef, p->lists, p->lists + DIRECT_CAP, p->rows, p->data_rows, (uint32_t)p->outputs, (uint32_t)p->pad};
+    return FASTECC_OK;
+}
+
+// Words per lane: batch_vec's rule for the class, then halved while a block is shorter than a wave of such lanes (S = 64: V = 1 fills the
+// wave where V = 4 would leave 48 lanes idle)
+static int set_vec(int eb, const void* data, const void* parity, uint64_t S)
+{
+    const uintptr_t align = (uintptr_t)data | (uintptr_t)parity;
+    int v = eb <= 4 ? 4 : eb == 8 ? 2 : 1;
+    while (v > 1 && ((S % v) != 0 || (align & (4u * v - 1u)) != 0)) v >>= 1;
+    while (v > 1 && S < 64u * (uint64_t)v) v >>= 1;
+    return v;
+}
+
+uint64_t direct_set_waves_per_entry(int eb, const void* data, const void* parity, uint64_t S)
+{
+    const uint64_t v = (uint64_t)set_vec(eb, data, parity, S);
+    return (S + 64u * v - 1u) / (64u * v);
+}
+
+int direct_run_set(int eb, const DirectSetPass* passes, const DirectSetEntry* entries, uint64_t n_entries, const uint32_t* data, const uint32_t* parity,
+                   uint32_t* data_out, uint32_t* parity_out, uint64_t S, uint64_t data_stride, uint64_t parity_stride, hipStream_t st)
+{
+    if (!passes || !entries || n_entries == 0 || S == 0 || S > 0xFFFFFFFFull || eb < 1 || eb > 16 || (eb & (eb - 1))) return FASTECC_E_INVAL;
+    // every pointer a lane touches: the stripes it reads and the ones it writes (data_out / parity_out are data / parity or null)
+    const void* dptr = (const void*)((uintptr_t)data | (uintptr_t)data_out);
+    const void* pptr = (const void*)((uintptr_t)parity | (uintptr_t)parity_out);
+    const int v = set_vec(eb, dptr, pptr, S);
+    const uint64_t wpe = direct_set_waves_per_entry(eb, dptr, pptr, S);
+    if (wpe > SET_LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (a block of more than 2^30 lane groups: the caller goes stripe by stripe)
+    SetArgs a{data, parity, data_out, parity_out, data_stride, parity_stride, entries, passes, 0, (uint32_t)wpe, (uint32_t)S};
+    const uint64_t launch_entries = SET_LAUNCH_WAVES / wpe;
+    for (uint64_t e0 = 0; e0 < n_entries; e0 += launch_entries) {
+        a.entries = entries + e0;
+        a.waves = (uint32_t)(std::min(launch_entries, n_entries - e0) * wpe);
+        const dim3 grid((a.waves + 3u) / 4u);
+#define FASTECC_SET(EB, V) hipLaunchKernelGGL((direct_set_kernel<EB, V>), grid, dim3(256), 0, st, a)
+        switch (eb * 8 + v) {
+            case 1 * 8 + 4: FASTECC_SET(1, 4); break;
+            case 1 * 8 + 2: FASTECC_SET(1, 2); break;
+            case 1 * 8 + 1: FASTECC_SET(1, 1); break;
+            case 2 * 8 + 4: FASTECC_SET(2, 4); break;
+            case 2 * 8 + 2: FASTECC_SET(2, 2); break;
+            case 2 * 8 + 1: FASTECC_SET(2, 1); break;
+            case 4 * 8 + 4: FASTECC_SET(4, 4); break;
+            case 4 * 8 + 2: FASTECC_SET(4, 2); break;
+            case 4 * 8 + 1: FASTECC_SET(4, 1); break;
+            case 8 * 8 + 2: FASTECC_SET(8, 2); break;
+            case 8 * 8 + 1: FASTECC_SET(8, 1); break;
+            default: FASTECC_SET(16, 1); break;
+        }
+#undef FASTECC_SET
+        HIP_TRY(hipGetLastError());
+    }
+    return FASTECC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // ENCODING when a code has few parity blocks: with the data points x_i = w_N^i the parity block j = f(y_j) = sum_i data_i * L_i(y_j),
 // y_j = w_2N^(odd): y_j^N = -1, so coef[i][j] = -2 x_i / (N (y_j - x_i)) — one read of the data instead of the three trips of the
 // transform pipeline.  Exactly the polynomial evaluation the transform computes (RS.cpp:40-63), hence the same parity bits.

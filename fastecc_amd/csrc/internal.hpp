@@ -72,6 +72,8 @@ template <class F> int guarded(F body)
 
 struct DecodeState;                        // decode.hip: tables of one erasure pattern + the size-2k transform context
 void destroy_decode_state(DecodeState*);   // decode.hip, called by fastecc_destroy
+struct PatternSet;                         // decode.hip: the tables of a pattern set (fastecc_decode_prepare_set) and the set calls' list buffers
+void destroy_pattern_set(PatternSet*);     // decode.hip, called by fastecc_destroy
 struct ScrubState;                         // scrub.hip: error detection and location (fastecc_verify, _locate_errors, _correct)
 void destroy_scrub_state(ScrubState*);     // scrub.hip, called by fastecc_destroy
 struct UpdateState;                        // update.hip: the parity update's weight table and delta rows (fastecc_update, _update_parity)
@@ -132,6 +134,25 @@ int direct_run_batch(DirectPass* p, const uint32_t* data, const uint32_t* parity
                      uint64_t data_stride, uint64_t parity_stride, hipStream_t st, const uint64_t* list = nullptr);
 uint64_t direct_batch_waves(const DirectPass* p, const void* data, const void* parity, uint64_t S, uint64_t count);  // waves of that launch, all sweeps
 int direct_pass_rows(const DirectPass* p);  // rows a pass reads (lost data rows included, at weight 0)
+// Many stripes, a pattern per stripe, in ONE launch (direct_set_kernel): the stripes entries[0 .. n) of a pool, each with the pass passes[entry.pass].
+// Both arrays in DEVICE memory.  Every pass of a launch has at most 16 outputs and the same pad `eb` (1, 2, 4, 8, 16).
+struct DirectSetPass {  // what the kernel takes from one built DirectPass
+    const uint32_t* coef;   // [rows][cstride], Montgomery form
+    const uint32_t* extra;  // rows data_rows.. of the pass are parity rows extra[u - data_rows]
+    const uint32_t* pos;    // outputs: data row pos >> 1 (even) or parity row pos >> 1 (odd)
+    uint32_t rows, data_rows, outputs;
+    uint32_t cstride;       // == the pass's pad: the class a launch is templated on (the kernel strides by that constant)
+};
+struct DirectSetEntry {
+    uint64_t stripe;  // of the pool
+    uint32_t pass;    // index into the descriptor table
+    uint32_t reserved;
+};
+int direct_set_describe(const DirectPass* p, DirectSetPass* out);  // FASTECC_E_INVAL: not built, or more than 16 outputs
+// waves one entry takes (V chosen for the class, the pointers' alignment and S); more than 2^24: direct_run_set refuses (FASTECC_E_UNSUPPORTED)
+uint64_t direct_set_waves_per_entry(int eb, const void* data, const void* parity, uint64_t S);
+int direct_run_set(int eb, const DirectSetPass* passes, const DirectSetEntry* entries, uint64_t n_entries, const uint32_t* data, const uint32_t* parity,
+                   uint32_t* data_out, uint32_t* parity_out, uint64_t S, uint64_t data_stride, uint64_t parity_stride, hipStream_t st);
 bool direct_mfma_applies(const void* data, const void* parity, uint64_t words);
 // decode.hip, for the scrubber (fastecc_correct_batch): fastecc_repair_batch's work on the `count` stripes list[0 .. count) of a pool of back-to-back
 // stripes, with the prepared pattern.  The list is given twice: on the host (the stripe-by-stripe forms) and on the device (the batched launch).
@@ -159,6 +180,7 @@ struct CtxInfo {
 };
 CtxInfo info_of(const fastecc_ctx* c);
 DecodeState*& decoder_of(fastecc_ctx* c);
+PatternSet*& pattern_set_of(fastecc_ctx* c);
 Sharded*& sharded_of(fastecc_ctx* c);
 namespace p61 {
 struct Decoder;

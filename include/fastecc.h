@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 360 /* 0.3.6: fastecc_locate_errors_batch; fastecc_correct_batch locates in one pass and repairs by lost-block pattern */
+#define FASTECC_VERSION 370 /* 0.3.7: fastecc_decode_prepare_set, fastecc_decode_batch_set / _repair_batch_set: an erasure pattern per stripe (rotated placement) */
 
 enum {
     FASTECC_OK = 0,
@@ -378,6 +378,47 @@ int fastecc_repair(fastecc_ctx *ctx, void *data, void *parity, int mem_kind, voi
  */
 int fastecc_decode_batch(fastecc_ctx *ctx, void *data, const void *parity, uint64_t count, void *stream);
 int fastecc_repair_batch(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, void *stream);
+/*
+ * Many stripes, an erasure pattern PER STRIPE (rebuilding a failed device of a pool with rotated placement: stripe b keeps block i on device
+ * (i + b) mod n, so one lost device costs stripe b a different block, n patterns in all, and the stripes of one pattern lie n apart).
+ *   fastecc_decode_prepare_set : stores a SET of n_patterns erasure patterns in the context.  Pattern q's flags are data_present[q*k .. q*k+k)
+ *       and parity_present[q*(n-k) .. q*(n-k)+(n-k)), non-zero = the block survives, as for fastecc_decode_prepare.  The set is independent of
+ *       the single prepared pattern: fastecc_decode_prepare, _decode, _repair, _decode_batch, _repair_batch and fastecc_correct* neither read nor
+ *       change it, and the set calls neither read nor change the single pattern.  Synchronous: one table build and one synchronisation per
+ *       pattern, and a wait for device work that still uses the previous set.  The new set is built aside and swapped in on success: a refused
+ *       or failed call leaves the previous set in force.  n_patterns == 0 clears the set and frees its tables.
+ *       Limits: n_patterns <= 4096; every pattern loses at most 16 blocks in all (data + parity) and keeps at least k.  Such a pattern is
+ *       exactly ONE direct pass of at most 16 outputs: data and parity lost -> both in one pass, only data or only parity lost -> that pass.
+ *       A pattern that loses nothing is allowed (its stripes are not touched).  Option "decode_direct_max" does not apply to sets: it tunes the
+ *       single pattern's choice between two paths that give the same bits, and a set has the direct path only.
+ *       FASTECC_E_INVAL: null context, null flag arrays with n_patterns > 0, n_patterns > 4096, a pattern with fewer than k survivors.
+ *       FASTECC_E_UNSUPPORTED: a pattern with more than 16 losses, GF((2^61-1)^2), sharded contexts, a set "row_pitch_words".
+ *       FASTECC_E_NOMEM: the tables do not fit.
+ *   fastecc_repair_batch_set / fastecc_decode_batch_set : the pool layout of fastecc_repair_batch (stripe b's k data blocks at
+ *       data + b*k*block_bytes, its n - k parity blocks at parity + b*(n-k)*block_bytes, DEVICE memory).  pattern_of is a HOST array of `count`
+ *       entries and may be reused as soon as the call returns: pattern_of[b] < n_patterns treats stripe b with that pattern;
+ *       FASTECC_PATTERN_NONE: stripe b is neither read nor written (it may hold anything, words >= p included).  The result for every stripe,
+ *       bit for bit, is what fastecc_decode_prepare(that pattern) + fastecc_repair (resp. fastecc_decode) gives for the stripe alone.  Only erased
+ *       blocks are written; fastecc_decode_batch_set leaves erased parity blocks alone and skips stripes whose pattern lost only parity.  Every
+ *       GF(0xFFF00001) code fastecc_repair_batch takes.
+ *       The stripes that have work are sorted by the size class of their pattern's pass (1, 2, 4, 8 or 16 outputs, rounded up) and every
+ *       non-empty class is ONE launch, whatever the number of patterns in it: one lost device of a rotated pool is one launch.  A block owns
+ *       whole waves of 64 lanes (blocks shorter than 64 words leave lanes idle; for one pattern and very short blocks fastecc_repair_batch
+ *       remains the tool).  A class whose passes read 4096 blocks or more runs stripe by stripe instead (correct, the matrix cores from there
+ *       on, no faster than a loop).  Option "decode_batch_kernel" at call time: 0 = that choice, 1 = the kernel always, 2 = stripe by stripe
+ *       always; the same bits in every mode.
+ *       Enqueued on `stream`; steady-state calls do not synchronise the device.  The per-call list travels through a pinned host buffer and a
+ *       device buffer owned by the context, with the rules of fastecc_update_batch: they grow on demand (a growing call waits for the previous
+ *       one), an event guards reuse of the pinned buffer, and the calls cannot be captured into a hipGraph.
+ *       FASTECC_E_INVAL, before any device work: null context, data, parity or pattern_of, count == 0, pointers not 4-byte aligned, byte sizes
+ *       beyond 64 bits, no set prepared, an entry >= n_patterns that is not FASTECC_PATTERN_NONE.  FASTECC_E_UNSUPPORTED: GF((2^61-1)^2),
+ *       sharded contexts, a set "row_pitch_words".  A refused call does no device work and writes nothing.  A call in which no stripe has
+ *       anything to do returns FASTECC_OK at once.
+ */
+#define FASTECC_PATTERN_NONE 0xFFFFFFFFu
+int fastecc_decode_prepare_set(fastecc_ctx *ctx, const uint8_t *data_present, const uint8_t *parity_present, uint64_t n_patterns);
+int fastecc_decode_batch_set(fastecc_ctx *ctx, void *data, const void *parity, uint64_t count, const uint32_t *pattern_of, void *stream);
+int fastecc_repair_batch_set(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, const uint32_t *pattern_of, void *stream);
 
 /*
  * Error detection and location ("scrub"): find blocks that are present but wrong — bit rot, torn or misdirected writes — which
@@ -640,7 +681,9 @@ const char *fastecc_plan_string(fastecc_ctx *ctx);
  *   "direct_kernel" = 0 / 1 / 2 (default 0 = choose): the kernel of those direct paths — 1 = VALU (96-bit lazy accumulation, any rows),
  *                  2 = MFMA (i8 digits; falls back to 1 where it cannot run).  Same bits either way;
  *   "decode_batch_kernel" = 0 / 1 / 2 (default 0 = choose; at call time): how fastecc_decode_batch / _repair_batch run a direct-path pass — 1 = one
- *                  launch over all stripes whenever the pass allows it, 2 = stripe by stripe (direct_kernel then picks the kernel).  Same bits either way;
+ *                  launch over all stripes whenever the pass allows it, 2 = stripe by stripe (direct_kernel then picks the kernel).  Same bits either way.
+ *                  fastecc_decode_batch_set / _repair_batch_set read it too: 0 = one launch per class unless its passes read 4096 blocks or more,
+ *                  1 = one launch per class always, 2 = stripe by stripe;
  *   "scrub_batch_chunk" = 0 .. INT_MAX (default 0 = the context's chunk capacity; at call time): the most stripes per chunk of
  *                  fastecc_verify_batch / _correct_batch / _locate_errors_batch.  Same answers either way;
  *   "correct_batch_mode" = 0 / 1 / 2 (default 0 = choose; at call time): how fastecc_correct_batch corrects the inconsistent stripes — 1 = batched

@@ -32,9 +32,9 @@ for line in err.splitlines():
         cur = {"kernel": name}
         rows.append(cur)
         continue
-    m = re.search(r"remark: .*?\s+(SGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\d+)", line)
+    m = re.search(r"remark: .*?\s+((?:Total)?SGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\d+)", line)
     if m and cur is not None:
-        cur[m.group(1).split(" [")[0]] = int(m.group(2))
+        cur[m.group(1).split(" [")[0].replace("TotalSGPRs", "SGPRs")] = int(m.group(2))
 cols = ["VGPRs", "AGPRs", "SGPRs", "SGPRs Spill", "VGPRs Spill", "ScratchSize", "Occupancy", "LDS Size"]
 rows = [r for r in rows if args.filter in r["kernel"]]
 print("%-58s %s" % ("kernel", " ".join("%11s" % c for c in cols)))
