@@ -114,6 +114,7 @@ def lib():
         f.argtypes, f.restype = [vp, vp, vp, u64, vp, u64, u8p, u64p], i32
     L.fastecc_locate_errors_batch.argtypes = [vp, vp, vp, u64, vp, u64, u8p, u64p, u64, ctypes.POINTER(u32), u64p]
     L.fastecc_locate_errors_batch.restype = i32
+    L.fastecc_scrub_fingerprints.argtypes, L.fastecc_scrub_fingerprints.restype = [vp, vp, vp, u64, u64p, i32, vp, u64, ctypes.POINTER(u32), u8p], i32
     L.fastecc_update.argtypes, L.fastecc_update.restype = [vp, vp, vp, u64p, u64, vp, i32, vp], i32
     L.fastecc_update_parity.argtypes, L.fastecc_update_parity.restype = [vp, vp, u64p, u64, vp, vp, i32, vp], i32
     L.fastecc_update_batch.argtypes, L.fastecc_update_batch.restype = [vp, vp, vp, u64, u64p, u64, vp, vp], i32
@@ -451,6 +452,21 @@ class Encoder:
             raise err
         _check(code, "fastecc_locate_errors_batch")
         return status, lists
+
+    def scrub_fingerprints(self, data, parity, count=1, form=0, stripes=None, seed=0, stream=0):
+        """What the fingerprint pass of the scrub calls computes (tests only): (F, big) with F a numpy uint32 array [entries, n, 3], F[i, j, c]
+        = sum_w rho_c[w] * word w of block j of entry i mod p, and big a bool array, True where a block of the entry holds a word >= p.
+        form 0: the single-stripe pass (count 1); 1: the batch pass over `count` stripes; 2: the list pass over the stripes `stripes` of the pool."""
+        import numpy as np
+        arr = None
+        if stripes is not None:
+            count, arr = self._block_list(stripes)
+        out = np.zeros((count, self.n, 3), np.uint32)
+        big = np.zeros(count, np.uint8)
+        _check(lib().fastecc_scrub_fingerprints(self._h, _addr(data), _addr(parity), count, arr, form, stream or None, seed,
+                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), big.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))),
+               "fastecc_scrub_fingerprints")
+        return out, big.astype(bool)
 
     def _located(self, fn, what, data, parity, seed, stream, mem):
         cap = self.n - self.k

@@ -785,11 +785,31 @@ int batch_state(fastecc_ctx* c, ScrubState* s)
     return FASTECC_OK;
 }
 
+// fastecc_scrub_fingerprints (tests): a batched pass given one of these stops each chunk after its fingerprint launch and copies the chunk's
+// fingerprints out instead of transforming them.  out: host, 3 words per block and entry, the entry's blocks in codeword order.
+struct Probe {
+    uint32_t* out;
+};
+
+// the B entries of the chunk d_FB holds -> out[(i * n + j) * 3 + c], read by pos[j]; waits for the stream
+int probe_chunk(ScrubState* s, uint64_t B, hipStream_t st, uint32_t* out)
+{
+    std::vector<uint32_t> h(s->NC * B * RW);
+    HIP_TRY(hipMemcpy2DAsync(h.data(), B * RW * 4, s->d_FB, RW * s->batch_cap * 4, B * RW * 4, s->NC, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint64_t i = 0; i < B; i++)
+        for (uint64_t j = 0; j < s->n; j++)
+            for (int col = 0; col < R; col++) out[(i * s->n + j) * R + col] = h[((uint64_t)s->pos[j] * B + i) * RW + col];
+    return FASTECC_OK;
+}
+
 // fastecc_verify_batch on a locked context: flag[b] = 1 iff fastecc_verify with this seed would find stripe b inconsistent.  Per chunk of B
 // stripes: the fingerprints (weighed by the locator of the fixed and the named erasures as they are stored; absent blocks are not read and
 // store zero), one transform of NC points over 4B word columns, the syndrome check of every stripe from coefficient N + fixed + w on; then
 // one copy of the flags and one synchronisation for the whole call.
-int verify_batch_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, uint64_t seed, hipStream_t st, std::vector<uint8_t>& flag)
+// probe: the chunks end after their fingerprint pass (nothing else sets a flag then: flag[b] = 1 iff a block of stripe b holds a word >= p).
+int verify_batch_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, uint64_t seed, hipStream_t st, std::vector<uint8_t>& flag,
+                        const Probe* probe = nullptr)
 {
     ScrubState* s = nullptr;
     int rc = scrub_state(c, &s);
@@ -821,6 +841,10 @@ int verify_batch_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* pa
                 hipLaunchKernelGGL(fingerprint_batch_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)S,
                                    b0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, s->d_flag, nullptr, nullptr);
             HIP_TRY(hipGetLastError());
+        }
+        if (probe) {
+            if ((rc = probe_chunk(s, B, st, probe->out + b0 * s->n * R)) != FASTECC_OK) return rc;
+            continue;
         }
         if (m_lo >= NC) continue;  // n - k blocks named absent: no coefficient is left to check, only the words >= p count
         {
@@ -863,9 +887,10 @@ int upload_list(ScrubState* s, const std::vector<uint64_t>& list, hipStream_t st
 }
 
 // One chunk of verify_batch_locked over the list entries [l0, l0 + B) of s->d_list: fingerprints, transform and either the flags of those entries
-// (syn == null) or all their `avail` = NC - m_lo syndromes gathered to syn.  Nothing is copied back and nothing waits.
+// (syn == null) or all their `avail` = NC - m_lo syndromes gathered to syn.  Nothing is copied back and nothing waits — unless probe_out is
+// given (fastecc_scrub_fingerprints): then the chunk ends after the fingerprint pass with its fingerprints copied there (probe_chunk).
 int list_chunk(fastecc_ctx* c, ScrubState* s, const Erasures& er, const uint32_t* data, const uint32_t* parity, uint64_t l0, uint64_t B, hipStream_t st,
-               uint32_t* syn)
+               uint32_t* syn, uint32_t* probe_out = nullptr)
 {
     const uint64_t row = RW * s->batch_cap, NC = s->NC, m_lo = s->N + s->fixed + er.w, S = c->S;
     const bool vec = (S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
@@ -881,6 +906,7 @@ int list_chunk(fastecc_ctx* c, ScrubState* s, const Erasures& er, const uint32_t
                                (uint32_t)S, (uint64_t)0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, flag + l0, s->d_list + l0, big + l0);
         HIP_TRY(hipGetLastError());
     }
+    if (probe_out) return probe_chunk(s, B, st, probe_out);
     if (m_lo >= NC) return FASTECC_OK;
     {
         ProfScope ps(c, st, "scrub_transform_batch");
@@ -908,9 +934,10 @@ uint64_t chunk_of(const fastecc_ctx* c, const ScrubState* s)
 }
 
 // verify_batch_locked over the stripes `list` of the pool: flag[i] = 1 iff fastecc_verify with this seed would find stripe list[i] inconsistent
-// (named: under the named erasures).  One copy of the flags and one synchronisation for the call.
+// (named: under the named erasures).  One copy of the flags and one synchronisation for the call.  probe: as for verify_batch_locked, and
+// flag[i] = 1 iff a block of stripe list[i] holds a word >= p.
 int verify_list_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, const std::vector<uint64_t>& list, uint64_t seed, hipStream_t st, bool named,
-                       std::vector<uint8_t>& flag)
+                       std::vector<uint8_t>& flag, const Probe* probe = nullptr)
 {
     ScrubState* s = nullptr;
     int rc = scrub_state(c, &s);
@@ -921,9 +948,9 @@ int verify_list_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* par
     const Erasures er = erasures(s, named);
     const uint64_t chunk = chunk_of(c, s), L = list.size();
     for (uint64_t l0 = 0; l0 < L; l0 += chunk)
-        if ((rc = list_chunk(c, s, er, data, parity, l0, std::min(chunk, L - l0), st, nullptr)) != FASTECC_OK) return rc;
+        if ((rc = list_chunk(c, s, er, data, parity, l0, std::min(chunk, L - l0), st, nullptr, probe ? probe->out + l0 * s->n * R : nullptr)) != FASTECC_OK) return rc;
     flag.assign(L, 0);
-    HIP_TRY(hipMemcpyAsync(flag.data(), s->d_lflag, L, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(flag.data(), s->d_lflag + (probe ? s->list_cap : 0), L, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return FASTECC_OK;
 }
@@ -1140,6 +1167,47 @@ int fastecc_gf_berlekamp_massey(const uint32_t* s, uint32_t count, uint32_t* lam
         if ((uint64_t)cap < (uint64_t)L + 1) return FASTECC_E_INVAL;
         std::copy(C.begin(), C.end(), lambda);
         return L;
+    });
+}
+
+int fastecc_scrub_fingerprints(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const uint64_t* list, int form, void* stream, uint64_t seed,
+                               uint32_t* out, uint8_t* big)
+{
+    if (!out || !big || form < 0 || form > 2 || (form == 0 && count != 1) || (form == 2) != (list != nullptr)) return FASTECC_E_INVAL;
+    const int rc = batch_args(c, data, parity, count);
+    if (rc != FASTECC_OK) return rc;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallLock lk(c->mu);
+    return guarded([&]() -> int {
+        hipStream_t st = (hipStream_t)stream;
+        const uint32_t *d = (const uint32_t*)data, *p = (const uint32_t*)parity;
+        ScrubState* s = nullptr;
+        int r = scrub_state(c, &s);
+        if (r != FASTECC_OK) return r;
+        if (!s->absent.empty()) return FASTECC_E_UNSUPPORTED;
+        if (form == 0) {  // fingerprint_kernel stores F unweighed, by position
+            Small sm;
+            if ((r = small_buffers(s, (uint32_t)c->locate_max, &sm)) != FASTECC_OK) return r;
+            std::vector<uint32_t> bad;
+            if ((r = fingerprints(c, s, sm, erasures(s, false), d, p, seed, st, bad)) != FASTECC_OK) return r;
+            std::vector<uint32_t> F(s->NC * RW);
+            HIP_TRY(hipMemcpy(F.data(), s->d_F, F.size() * 4, hipMemcpyDeviceToHost));  // (fingerprints() has waited for the stream)
+            for (uint64_t j = 0; j < s->n; j++)
+                for (int col = 0; col < R; col++) out[j * R + col] = F[(uint64_t)s->pos[j] * RW + col];
+            big[0] = bad.empty() ? 0 : 1;
+            return FASTECC_OK;
+        }
+        if (s->d_lfix) return FASTECC_E_UNSUPPORTED;  // the batched passes store F times the fixed erasures' locator
+        const Probe probe{out};
+        std::vector<uint8_t> flag;
+        if (form == 1)
+            r = verify_batch_locked(c, d, p, count, seed, st, flag, &probe);
+        else
+            r = verify_list_locked(c, d, p, std::vector<uint64_t>(list, list + count), seed, st, false, flag, &probe);
+        if (r != FASTECC_OK) return r;
+        std::copy(flag.begin(), flag.end(), big);
+        return FASTECC_OK;
     });
 }
 

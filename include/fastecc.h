@@ -533,6 +533,25 @@ int fastecc_correct_batch(fastecc_ctx *ctx, void *data, void *parity, uint64_t c
                           uint64_t *inconsistent);
 int fastecc_locate_errors_batch(fastecc_ctx *ctx, const void *data, const void *parity, uint64_t count, void *stream, uint64_t seed,
                                 uint8_t *status, uint64_t *blocks, uint64_t cap, uint32_t *counts, uint64_t *inconsistent);
+/*
+ * The fingerprints themselves (tests only, like fastecc_gf_binary: this call is no part of the scrub contract and may change).  It runs the
+ * fingerprint pass of the scrub calls above — the same kernels through the same host paths and launch configurations — stops before the
+ * syndrome transform and returns what the pass computed, so that a test can compare it with an exact model:
+ *   weights : weight word w (w = 0 .. words per block - 1, the same for every block) comes from the w-th output x of splitmix64 started at
+ *             state `seed` (state += 0x9E3779B97F4A7C15; z = state; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) *
+ *             0x94D049BB133111EB; x = z ^ z >> 31): rho_0 = x & 0xFFFFF, rho_1 = (x >> 20) & 0xFFFFF, rho_2 = (x >> 40) & 0xFFFFF;
+ *   F_c     : sum over w of rho_c[w] * r[w] mod p, r[w] the block's 32-bit word as stored (words >= p are not reduced first), canonical.
+ * form 0 = the single-stripe pass of fastecc_verify / _locate_errors / _correct (count must be 1, list NULL); 1 = the batch pass of
+ * fastecc_verify_batch over the stripes 0 .. count-1 of a pool, in its chunks (option "scrub_batch_chunk" applies; list NULL); 2 = the list
+ * pass of fastecc_locate_errors_batch / _correct_batch over the stripes list[0 .. count) of the pool (list: a host array; a stripe may be
+ * named more than once).  out (host, count*n*3 words): out[(i*n + j)*3 + c] = F_c of block j of entry i, block j = data block j for j < k,
+ * else parity block j - k.  big (host, count bytes): big[i] = 1 iff some block of entry i holds a word >= p, else 0.  Synchronous.
+ * Refusals: those of fastecc_verify / fastecc_verify_batch; FASTECC_E_INVAL also for an unknown form, null out or big, form 0 with
+ * count != 1, a list without form 2 or form 2 without one; FASTECC_E_UNSUPPORTED while a fastecc_scrub_erasures pattern is set, and for
+ * forms 1 and 2 on a code with fixed erasures (zero-extended and n = k + N/2^d codes: those passes store F times the erasures' locator).
+ */
+int fastecc_scrub_fingerprints(fastecc_ctx *ctx, const void *data, const void *parity, uint64_t count, const uint64_t *list, int form,
+                               void *stream, uint64_t seed, uint32_t *out, uint8_t *big);
 
 /*
  * Small writes: bring the parity up to date after `count` data blocks changed, without reading the rest of the stripe.  The code is

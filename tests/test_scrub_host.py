@@ -18,7 +18,7 @@ def hip_lib():
 
 
 def test_scrub_symbols_exported(hip_lib):
-    for name in ("fastecc_verify", "fastecc_locate_errors", "fastecc_correct", "fastecc_gf_berlekamp_massey"):
+    for name in ("fastecc_verify", "fastecc_locate_errors", "fastecc_correct", "fastecc_gf_berlekamp_massey", "fastecc_scrub_fingerprints"):
         assert hasattr(hip_lib, name), name
     assert fe.E_UNCORRECTABLE == -5
     assert hip_lib.fastecc_version() >= 300
