@@ -23,7 +23,7 @@ CODE_MIXED_RADIX = 1  # fastecc_create_ex flag: transform order q * 2^m, q in {1
 CODE_MIXED_RADIX_PFA = 4  # ... and the composite q = 21, 35, 39, 45, 63, 65, 91, 105, 117 (prime-factor map)
 CODE_TOP_RADIX2 = 2  # fastecc_create_ex flag (A/B experiment): the top level of a power-of-two transform through the fused odd-radix kernel
 
-PATTERN_NONE = 0xFFFFFFFF  # pattern_of entry of decode_batch_set / repair_batch_set: the stripe is neither read nor written
+PATTERN_NONE = 0xFFFFFFFF  # pattern_of entry of the set calls (decode_batch_set, repair_batch_set, verify_batch_set, correct_batch_set): the stripe is neither read nor written
 
 OK, E_INVAL, E_NOMEM, E_DEVICE, E_UNSUPPORTED, E_UNCORRECTABLE = 0, -1, -2, -3, -4, -5
 
@@ -112,6 +112,10 @@ def lib():
     for name in ("verify_batch", "correct_batch"):
         f = getattr(L, "fastecc_" + name)
         f.argtypes, f.restype = [vp, vp, vp, u64, vp, u64, u8p, u64p], i32
+    L.fastecc_scrub_erasures_set.argtypes, L.fastecc_scrub_erasures_set.restype = [vp, u8p, u8p, u64], i32
+    for name in ("verify_batch_set", "correct_batch_set"):
+        f = getattr(L, "fastecc_" + name)
+        f.argtypes, f.restype = [vp, vp, vp, u64, ctypes.POINTER(u32), vp, u64, u8p, u64p], i32
     L.fastecc_locate_errors_batch.argtypes = [vp, vp, vp, u64, vp, u64, u8p, u64p, u64, ctypes.POINTER(u32), u64p]
     L.fastecc_locate_errors_batch.restype = i32
     L.fastecc_scrub_fingerprints.argtypes, L.fastecc_scrub_fingerprints.restype = [vp, vp, vp, u64, u64p, i32, vp, u64, ctypes.POINTER(u32), u8p], i32
@@ -329,6 +333,10 @@ class Encoder:
         """A set of P erasure patterns for decode_batch_set / repair_batch_set: P rows of k data flags and P rows of n - k parity flags
         (truthy = the block survives); every pattern loses at most 16 blocks and keeps at least k.  P = 0 (two empty arguments) clears the
         set.  Independent of the decode_prepare pattern."""
+        self._pattern_set(lib().fastecc_decode_prepare_set, "fastecc_decode_prepare_set", data_present, parity_present)
+
+    def _pattern_set(self, fn, what, data_present, parity_present):
+        """fn(handle, P x k data flags, P x (n - k) parity flags, P) with the shapes checked first"""
         import numpy as np
         P = len(data_present)
         if len(parity_present) != P:
@@ -344,8 +352,7 @@ class Encoder:
             return np.ascontiguousarray(np.asarray(v, dtype=bool).reshape(P, width), dtype=np.uint8)
         u8p = ctypes.POINTER(ctypes.c_uint8)
         dp, pp = (flat(data_present, self.k), flat(parity_present, m)) if P else (None, None)
-        _check(lib().fastecc_decode_prepare_set(self._h, dp.ctypes.data_as(u8p) if P else None, pp.ctypes.data_as(u8p) if P else None, P),
-               "fastecc_decode_prepare_set")
+        _check(fn(self._h, dp.ctypes.data_as(u8p) if P else None, pp.ctypes.data_as(u8p) if P else None, P), what)
 
     @staticmethod
     def _pattern_list(pattern_of, count):
@@ -428,6 +435,43 @@ class Encoder:
             err.status = out
             raise err
         _check(code, "fastecc_correct_batch")
+        return out
+
+    def scrub_erasures_set(self, data_present, parity_present):
+        """A set of P absent-block patterns for verify_batch_set / correct_batch_set (a degraded pool with rotated placement): P rows of k
+        data flags and P rows of n - k parity flags (truthy = present), the arrays decode_prepare_set takes; a pattern names 0 .. n - k
+        blocks absent.  P = 0 (two empty arguments) clears the set.  Independent of the scrub_erasures pattern and of both decode patterns."""
+        self._pattern_set(lib().fastecc_scrub_erasures_set, "fastecc_scrub_erasures_set", data_present, parity_present)
+
+    def _scrub_batch_set(self, fn, data, parity, count, pattern_of, seed, stream):
+        import numpy as np
+        count = self._batch_count(count)
+        keep, po = self._pattern_list(pattern_of, count)
+        out = np.zeros(count, np.uint8)
+        bad = ctypes.c_uint64()
+        code = fn(self._h, _addr(data), _addr(parity), count, po, stream or None, seed, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(bad))
+        del keep
+        return code, out
+
+    def verify_batch_set(self, data, parity, count, pattern_of, seed=0, stream=0):
+        """verify_batch with stripe b under pattern pattern_of[b] of the scrub_erasures_set set: a numpy bool array, True where
+        scrub_erasures(that pattern) + verify with the same seed finds the stripe consistent, and for PATTERN_NONE stripes, which are
+        not read.  Reads only."""
+        code, out = self._scrub_batch_set(lib().fastecc_verify_batch_set, data, parity, count, pattern_of, seed, stream)
+        _check(code, "fastecc_verify_batch_set")
+        return out.astype(bool)
+
+    def correct_batch_set(self, data, parity, count, pattern_of, seed=0, stream=0):
+        """verify_batch_set, then what scrub_erasures(its pattern) + correct does to each inconsistent stripe (replaces the prepared
+        erasure pattern, not the decode_prepare_set set).  Returns the numpy uint8 status array: 0 = consistent or skipped and untouched,
+        1 = corrected (the whole codeword is back), 2 = uncorrectable.  If any stripe is uncorrectable, raises FastEccError with code
+        E_UNCORRECTABLE after the others were corrected; the full status array is its `status` attribute."""
+        code, out = self._scrub_batch_set(lib().fastecc_correct_batch_set, data, parity, count, pattern_of, seed, stream)
+        if code == E_UNCORRECTABLE:
+            err = FastEccError(code, "fastecc_correct_batch_set")
+            err.status = out
+            raise err
+        _check(code, "fastecc_correct_batch_set")
         return out
 
     def locate_errors_batch(self, data, parity, count, seed=0, stream=0):

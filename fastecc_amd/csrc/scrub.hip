@@ -32,6 +32,7 @@
 // locators (root_search_batch_kernel), then one fastecc_decode_prepare and one list-form repair (decode.hip repair_list) per distinct set of lost blocks.
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <vector>
 
 #include "drivers.hpp"
@@ -234,6 +235,50 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIST ? 5 : 
     }
 }
 
+// fastecc_verify_batch_set: fingerprint_batch_kernel's pass with a pattern PER STRIPE.  q = pattern_of[b] is read once per wave and
+// made uniform by readfirstlane, so q, pos_set[q * n + j] and the absent test are scalar loads and one scalar branch, as above.  A stripe with
+// q = FASTECC_PATTERN_NONE reads nothing and stores a zero entry at every one of its n positions (through pattern 0's position table: a set has at least
+// one pattern, and the mark is masked off); an absent block stores its zero entry; a present one F * lset[q * NC + u], the fixed and the pattern's own
+// erasures' locator at its position.  Every (stripe, block) entry of the chunk is stored by every call: nothing an earlier call, set or pattern left in F
+// is read.  Six waves per SIMD (at most 80 VGPRs), the grid all resident, as for the batch kernel.
+template <bool VEC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void fingerprint_set_kernel(const uint32_t* __restrict__ data, const uint32_t* __restrict__ parity, uint32_t k_blocks,
+                                                              uint32_t n_blocks, uint32_t S, uint64_t b0, uint64_t B, const uint2* __restrict__ wt,
+                                                              const uint32_t* __restrict__ pattern_of, const uint32_t* __restrict__ pos_set,
+                                                              const uint32_t* __restrict__ lset, uint32_t NC, uint32_t* __restrict__ F, uint64_t row,
+                                                              uint8_t* __restrict__ flag)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint64_t waves = (gridDim.x * blockDim.x) >> 6;
+    const uint64_t total = B * n_blocks;
+    const uint64_t m_blocks = n_blocks - k_blocks;
+    for (uint64_t g = wave; g < total; g += waves) {
+        const uint64_t bl = g / n_blocks;
+        const uint32_t j = (uint32_t)(g - bl * n_blocks);
+        const uint64_t b = b0 + bl;
+        const uint32_t q = __builtin_amdgcn_readfirstlane(pattern_of[b]);
+        const bool none = q == FASTECC_PATTERN_NONE;
+        const uint32_t u = pos_set[(none ? 0u : q) * n_blocks + j];
+        if (none || (u & ABSENT)) {
+            if (lane == 0) *reinterpret_cast<uint4*>(F + (uint64_t)(u & ~ABSENT) * row + bl * RW) = make_uint4(0, 0, 0, 0);
+            continue;
+        }
+        const uint32_t* blk = j < k_blocks ? data + (b * k_blocks + j) * S : parity + (b * m_blocks + (j - k_blocks)) * S;
+        uint32_t fp[R];
+        bool any_big;
+        block_fingerprint<VEC>(blk, S, wt, lane, fp, any_big);
+        if (lane == 0) {
+            const uint32_t l = lset[q * NC + u];
+            uint32_t* f = F + (uint64_t)u * row + bl * RW;
+            f[0] = gf::mul(fp[0], l);
+            f[1] = gf::mul(fp[1], l);
+            f[2] = gf::mul(fp[2], l);
+            if (any_big) flag[b] = 1;
+        }
+    }
+}
+
 // out[u] = base[u] (or 1) * prod_i (w^u - roots[i]); WITH_F: G[u][c] = F[u][c] * that instead (all plain representatives)
 template <bool WITH_F>
 __global__ __launch_bounds__(256) void locator_kernel(const uint32_t* __restrict__ base, const uint32_t* __restrict__ roots, uint32_t nroots,
@@ -250,6 +295,19 @@ __global__ __launch_bounds__(256) void locator_kernel(const uint32_t* __restrict
     }
     const uint4 f = reinterpret_cast<const uint4*>(F)[u];
     reinterpret_cast<uint4*>(out)[u] = make_uint4(gf::mul(f.x, v), gf::mul(f.y, v), gf::mul(f.z, v), 0u);
+}
+
+// fastecc_scrub_erasures_set: locator_kernel<false> for every pattern of a set at once, one grid row per pattern q:
+// out[q * NC + u] = base[u] (or 1) * prod (w^u - roots[i]), i in [off[q], off[q + 1])
+__global__ __launch_bounds__(256) void locator_set_kernel(const uint32_t* __restrict__ base, const uint32_t* __restrict__ roots, const uint32_t* __restrict__ off,
+                                                          const uint32_t* __restrict__ wpow, uint32_t NC, uint32_t* __restrict__ out)
+{
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x, q = blockIdx.y;
+    if (u >= NC) return;
+    const uint32_t x = wpow[u];
+    uint32_t v = base ? base[u] : 1u;
+    for (uint32_t i = off[q], e = off[q + 1]; i < e; i++) v = gf::mul(v, gf::sub(x, roots[i]));
+    out[(uint64_t)q * NC + u] = v;
 }
 
 // G holds the inverse transform in bit-reversed order (G[bitrev(m)] = NC * coefficient m).  Every coefficient m >= m_lo must vanish:
@@ -278,6 +336,22 @@ __global__ __launch_bounds__(256) void syndrome_batch_kernel(const uint32_t* __r
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (NC - m_lo) * B) return;
     const uint32_t b = i % B, m = m_lo + i / B;
+    const uint32_t slot = __brev(m) >> (32 - lgc);
+    const uint4 g = *reinterpret_cast<const uint4*>(G + (uint64_t)slot * row + (uint64_t)b * RW);
+    if ((g.x | g.y | g.z) != 0) flag[b0 + b] = 1;
+}
+
+// fastecc_verify_batch_set: syndrome_batch_kernel's item mapping from m_lo = the smallest bound of the set on; stripe b0 + b checks the coefficients from its
+// own pattern's bound mlo_set[pattern_of[b0 + b]] = N + fixed + w on (the w below it are legitimately non-zero), a FASTECC_PATTERN_NONE stripe none
+__global__ __launch_bounds__(256) void syndrome_set_kernel(const uint32_t* __restrict__ G, int lgc, uint32_t NC, uint32_t m_lo, uint64_t row, uint32_t B,
+                                                           uint64_t b0, const uint32_t* __restrict__ pattern_of, const uint32_t* __restrict__ mlo_set,
+                                                           uint8_t* __restrict__ flag)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (NC - m_lo) * B) return;
+    const uint32_t b = i % B, m = m_lo + i / B;
+    const uint32_t q = pattern_of[b0 + b];
+    if (q == FASTECC_PATTERN_NONE || m < mlo_set[q]) return;
     const uint32_t slot = __brev(m) >> (32 - lgc);
     const uint4 g = *reinterpret_cast<const uint4*>(G + (uint64_t)slot * row + (uint64_t)b * RW);
     if ((g.x | g.y | g.z) != 0) flag[b0 + b] = 1;
@@ -349,6 +423,23 @@ __global__ __launch_bounds__(256) void powers_kernel(uint32_t* __restrict__ wpow
 
 }  // namespace
 
+// fastecc_scrub_erasures_set: P patterns of absent blocks, their tables side by side
+struct ScrubSet {
+    uint64_t P = 0;
+    std::vector<std::vector<uint32_t>> absent;    // per pattern: the absent blocks' codeword indices, increasing
+    std::vector<std::vector<uint8_t>> is_absent;  // per pattern: n flags
+    std::vector<uint32_t> mlo;                    // per pattern: N + fixed + w, the first coefficient that must vanish
+    uint32_t mlo_min = 0;
+    uint32_t* d_pos = nullptr;                    // P x n words: d_pos with ABSENT set at the pattern's absent blocks
+    uint32_t* d_l = nullptr;                      // P x NC words: d_lfix (or 1) times the locator of the pattern's absent positions at w^u
+    uint32_t* d_mlo = nullptr;                    // P words: mlo
+    ~ScrubSet()
+    {
+        for (void* p : {(void*)d_pos, (void*)d_l, (void*)d_mlo})
+            if (p) (void)hipFree(p);
+    }
+};
+
 struct ScrubState {
     uint64_t N = 0, NC = 0, n = 0, k = 0;  // transform length of the code, positions, blocks (user k + user m), data blocks
     int lgc = 0;
@@ -384,6 +475,10 @@ struct ScrubState {
     uint64_t list_cap = 0;
     uint32_t* d_loc = nullptr;              // one chunk's syndromes, then its locators, their lengths and the found lists
     uint64_t loc_words = 0;
+    // fastecc_scrub_erasures_set: the pattern set (null: none) and the device copy of a call's pattern_of (grow-only)
+    ScrubSet* set = nullptr;
+    uint32_t* d_pattern_of = nullptr;
+    uint64_t pattern_cap = 0;
 };
 
 void destroy_scrub_state(ScrubState* s)
@@ -392,25 +487,38 @@ void destroy_scrub_state(ScrubState* s)
     if (s->ntt) fastecc_destroy(s->ntt);
     if (s->ntt_batch) fastecc_destroy(s->ntt_batch);
     for (void* p : {(void*)s->d_pos, (void*)s->d_wpow, (void*)s->d_lfix, (void*)s->d_F, (void*)s->d_G, (void*)s->d_small, (void*)s->d_weights, (void*)s->d_FB,
-                    (void*)s->d_GB, (void*)s->d_flag, (void*)s->d_pos_named, (void*)s->d_lnamed, (void*)s->d_list, (void*)s->d_lflag, (void*)s->d_loc})
+                    (void*)s->d_GB, (void*)s->d_flag, (void*)s->d_pos_named, (void*)s->d_lnamed, (void*)s->d_list, (void*)s->d_lflag, (void*)s->d_loc, (void*)s->d_pattern_of})
         if (p) (void)hipFree(p);
+    delete s->set;
     delete s;
 }
 
 namespace {
 
 // What a scrub call erases up front besides the known-bad blocks: the position table its fingerprint pass reads, the locator of
-// those erasures at every position (null: 1) and the number of named ones (the fixed ones are counted by ScrubState::fixed).
+// those erasures at every position (null: 1), the number of named ones (the fixed ones are counted by ScrubState::fixed), their
+// codeword indices and the n flags (both null when w == 0).  A view of the single fastecc_scrub_erasures pattern (erasures) or of one
+// pattern of the set (set_view); it points into the scrub state and lives as long as the context's lock is held.
 struct Erasures {
     const uint32_t* d_pos;
     const uint32_t* d_loc;
     uint64_t w;
+    const std::vector<uint32_t>* absent;
+    const std::vector<uint8_t>* is_absent;
 };
 
 Erasures erasures(const ScrubState* s, bool named)
 {
-    if (named && !s->absent.empty()) return {s->d_pos_named, s->d_lnamed, s->absent.size()};
-    return {s->d_pos, s->d_lfix, 0};
+    if (named && !s->absent.empty()) return {s->d_pos_named, s->d_lnamed, s->absent.size(), &s->absent, &s->is_absent};
+    return {s->d_pos, s->d_lfix, 0, nullptr, nullptr};
+}
+
+// pattern q of the set: its rows of the set's tables (the locator row is lfix, or 1, for a pattern that names nothing)
+Erasures set_view(const ScrubState* s, uint32_t q)
+{
+    const ScrubSet* t = s->set;
+    const uint64_t w = t->absent[q].size();
+    return {t->d_pos + (uint64_t)q * s->n, t->d_l + (uint64_t)q * s->NC, w, w ? &t->absent[q] : nullptr, w ? &t->is_absent[q] : nullptr};
 }
 
 int scrub_args(fastecc_ctx* c, const void* data, const void* parity, int mem_kind)
@@ -661,16 +769,12 @@ int berlekamp_massey(const uint32_t* s, uint32_t count, std::vector<uint32_t>& C
     return (int)L;
 }
 
-// fastecc_locate_errors on a locked context: the sorted codeword indices of the corrupted blocks, or FASTECC_E_UNCORRECTABLE.  named: the
-// blocks fastecc_scrub_erasures named absent are erased and not read (they come back in *absent if asked for); else every block is read.
-int locate(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t seed, hipStream_t st, std::vector<uint32_t>& result, bool verify_only,
-           bool named = true, std::vector<uint32_t>* absent = nullptr)
+// fastecc_locate_errors on a locked context: the sorted codeword indices of the corrupted blocks, or FASTECC_E_UNCORRECTABLE.  The blocks
+// `er` names absent are erased and not read; with the view of no pattern every block is read.
+int locate(fastecc_ctx* c, ScrubState* s, const Erasures& er, const uint32_t* data, const uint32_t* parity, uint64_t seed, hipStream_t st,
+           std::vector<uint32_t>& result, bool verify_only)
 {
-    ScrubState* s = nullptr;
-    int rc = scrub_state(c, &s);
-    if (rc != FASTECC_OK) return rc;
-    const Erasures er = erasures(s, named);
-    if (absent) absent->assign(s->absent.begin(), s->absent.begin() + er.w);
+    int rc;
     const uint32_t tmax = (uint32_t)c->locate_max;
     Small sm;
     rc = small_buffers(s, tmax, &sm);
@@ -728,7 +832,7 @@ int locate(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_
         HIP_TRY(hipMemcpy(roots.data(), sm.found + 1, nf * 4, hipMemcpyDeviceToHost));
         for (uint32_t u : roots) {
             const uint32_t j = s->block_at[u];
-            if (j == ~0u || std::binary_search(bad.begin(), bad.end(), j) || (er.w && s->is_absent[j])) return FASTECC_E_UNCORRECTABLE;  // no block there, or one already erased
+            if (j == ~0u || std::binary_search(bad.begin(), bad.end(), j) || (er.w && (*er.is_absent)[j])) return FASTECC_E_UNCORRECTABLE;  // no block there, or one already erased
             erased.push_back(u);
             result.push_back(j);
         }
@@ -803,6 +907,32 @@ int probe_chunk(ScrubState* s, uint64_t B, hipStream_t st, uint32_t* out)
     return FASTECC_OK;
 }
 
+// What the batched verify passes share.  batch_begin: the chunk buffers, the seed's weights and `count` cleared flag bytes in d_flag (grow-only), enqueued on
+// st.  batch_end: the call's one copy of the flags and its one synchronisation.
+int batch_begin(fastecc_ctx* c, ScrubState* s, uint64_t count, uint64_t seed, hipStream_t st)
+{
+    int rc = batch_state(c, s);
+    if (rc != FASTECC_OK) return rc;
+    if (s->flag_cap < count) {
+        if (s->d_flag) (void)hipFree(s->d_flag);
+        s->d_flag = nullptr;
+        s->flag_cap = 0;
+        HIP_TRY(hipMalloc((void**)&s->d_flag, count));
+        s->flag_cap = count;
+    }
+    if ((rc = upload_weights(c, s, seed, st)) != FASTECC_OK) return rc;
+    HIP_TRY(hipMemsetAsync(s->d_flag, 0, count, st));
+    return FASTECC_OK;
+}
+
+int batch_end(ScrubState* s, uint64_t count, hipStream_t st, std::vector<uint8_t>& flag)
+{
+    flag.assign(count, 0);
+    HIP_TRY(hipMemcpyAsync(flag.data(), s->d_flag, count, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return FASTECC_OK;
+}
+
 // fastecc_verify_batch on a locked context: flag[b] = 1 iff fastecc_verify with this seed would find stripe b inconsistent.  Per chunk of B
 // stripes: the fingerprints (weighed by the locator of the fixed and the named erasures as they are stored; absent blocks are not read and
 // store zero), one transform of NC points over 4B word columns, the syndrome check of every stripe from coefficient N + fixed + w on; then
@@ -814,16 +944,7 @@ int verify_batch_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* pa
     ScrubState* s = nullptr;
     int rc = scrub_state(c, &s);
     if (rc != FASTECC_OK) return rc;
-    if ((rc = batch_state(c, s)) != FASTECC_OK) return rc;
-    if (s->flag_cap < count) {
-        if (s->d_flag) (void)hipFree(s->d_flag);
-        s->d_flag = nullptr;
-        s->flag_cap = 0;
-        HIP_TRY(hipMalloc((void**)&s->d_flag, count));
-        s->flag_cap = count;
-    }
-    if ((rc = upload_weights(c, s, seed, st)) != FASTECC_OK) return rc;
-    HIP_TRY(hipMemsetAsync(s->d_flag, 0, count, st));
+    if ((rc = batch_begin(c, s, count, seed, st)) != FASTECC_OK) return rc;
     const uint64_t chunk = c->scrub_batch_chunk > 0 ? std::min<uint64_t>(s->batch_cap, (uint64_t)c->scrub_batch_chunk) : s->batch_cap;
     const Erasures er = erasures(s, true);
     const uint64_t row = RW * s->batch_cap, NC = s->NC, m_lo = s->N + s->fixed + er.w, S = c->S;
@@ -859,10 +980,7 @@ int verify_batch_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* pa
             HIP_TRY(hipGetLastError());
         }
     }
-    flag.assign(count, 0);
-    HIP_TRY(hipMemcpyAsync(flag.data(), s->d_flag, count, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return FASTECC_OK;
+    return batch_end(s, count, st, flag);
 }
 
 // ---- list forms: the same passes over the stripes list[0 .. L) of the pool ----
@@ -1067,7 +1185,7 @@ int locate_list(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, co
             bool ok = true;
             for (uint32_t i = 0; i < f[0] && ok; i++) {
                 const uint32_t j = s->block_at[f[1 + i]];
-                ok = j != ~0u && !(er.w && s->is_absent[j]);  // a block is there, and not one already erased
+                ok = j != ~0u && !(er.w && (*er.is_absent)[j]);  // a block is there, and not one already erased
                 js.push_back(j);
             }
             if (!ok) continue;
@@ -1126,6 +1244,150 @@ int set_erasures(fastecc_ctx* c, const std::vector<uint32_t>& absent)
     return FASTECC_OK;
 }
 
+// ---- a pattern per stripe ----
+
+// fastecc_scrub_erasures_set on a locked context: `absent` (per pattern: codeword indices, increasing, at most n - k) replaces the set; none clears
+// it.  All tables are built aside — one 2-D locator launch and one synchronisation for the whole set — and swapped in, so a refusal or a failure
+// leaves the previous set in force.  Every scrub call ends with a synchronise, so nothing in flight reads the tables that are freed here.
+int set_erasures_set(fastecc_ctx* c, std::vector<std::vector<uint32_t>>& absent)
+{
+    ScrubState* s = c->scrub;
+    const uint64_t P = absent.size();
+    if (P == 0) {
+        if (s) {
+            delete s->set;
+            s->set = nullptr;
+        }
+        return FASTECC_OK;
+    }
+    const int rc = scrub_state(c, &s);
+    if (rc != FASTECC_OK) return rc;
+    const uint64_t n = s->n, NC = s->NC;
+    if (P * NC > (1ull << 24)) return FASTECC_E_UNSUPPORTED;  // the locator tables stay at most 64 MiB
+    std::unique_ptr<ScrubSet> t(new (std::nothrow) ScrubSet());
+    if (!t) return FASTECC_E_NOMEM;
+    t->P = P;
+    t->is_absent.resize(P);
+    t->mlo.resize(P);
+    std::vector<uint32_t> pos(P * n), roots, off(P + 1, 0);
+    const uint32_t w = gf::h_root((uint32_t)NC);
+    for (uint64_t q = 0; q < P; q++) {
+        std::copy(s->pos.begin(), s->pos.end(), pos.begin() + q * n);
+        t->is_absent[q].assign(n, 0);
+        for (uint32_t j : absent[q]) {
+            roots.push_back(gf::h_pow(w, s->pos[j]));
+            pos[q * n + j] |= ABSENT;
+            t->is_absent[q][j] = 1;
+        }
+        off[q + 1] = (uint32_t)roots.size();  // at most P (n - k) <= P NC <= 2^24
+        t->mlo[q] = (uint32_t)(s->N + s->fixed + absent[q].size());
+    }
+    t->mlo_min = *std::min_element(t->mlo.begin(), t->mlo.end());
+    t->absent.swap(absent);
+    uint32_t *d_roots = nullptr, *d_off = nullptr;
+    hipError_t he = hipMalloc((void**)&t->d_pos, P * n * 4);
+    if (he == hipSuccess) he = hipMalloc((void**)&t->d_l, P * NC * 4);
+    if (he == hipSuccess) he = hipMalloc((void**)&t->d_mlo, P * 4);
+    if (he == hipSuccess) he = hipMalloc((void**)&d_roots, std::max<size_t>(roots.size(), 1) * 4);
+    if (he == hipSuccess) he = hipMalloc((void**)&d_off, (P + 1) * 4);
+    if (he == hipSuccess) he = hipMemcpy(t->d_pos, pos.data(), P * n * 4, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(t->d_mlo, t->mlo.data(), P * 4, hipMemcpyHostToDevice);
+    if (he == hipSuccess && !roots.empty()) he = hipMemcpy(d_roots, roots.data(), roots.size() * 4, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(d_off, off.data(), (P + 1) * 4, hipMemcpyHostToDevice);
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(locator_set_kernel, dim3((unsigned)((NC + 255) / 256), (unsigned)P), dim3(256), 0, nullptr, s->d_lfix, d_roots, d_off, s->d_wpow, (uint32_t)NC,
+                           t->d_l);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) he = hipDeviceSynchronize();
+    if (d_roots) (void)hipFree(d_roots);
+    if (d_off) (void)hipFree(d_off);
+    if (he != hipSuccess) return hip_fail(he, "scrub erasure set tables");
+    delete s->set;
+    s->set = t.release();
+    return FASTECC_OK;
+}
+
+// fastecc_verify_batch_set's own argument check on a locked context: a set is prepared and every entry names one of its patterns or none
+int set_args(const fastecc_ctx* c, const uint32_t* pattern_of, uint64_t count)
+{
+    const ScrubState* s = c->scrub;
+    if (!s || !s->set) return FASTECC_E_INVAL;
+    for (uint64_t b = 0; b < count; b++)
+        if (pattern_of[b] >= s->set->P && pattern_of[b] != FASTECC_PATTERN_NONE) return FASTECC_E_INVAL;
+    return FASTECC_OK;
+}
+
+// fastecc_verify_batch_set on a locked context (set_args passed): verify_batch_locked with stripe b under pattern pattern_of[b] of the set.
+// flag[b] = 1 iff fastecc_scrub_erasures(that pattern) + fastecc_verify with this seed would find stripe b inconsistent; 0 for FASTECC_PATTERN_NONE.
+// Per chunk: the fingerprints (fingerprint_set_kernel), one transform, the syndrome check of every stripe from its own pattern's bound on.  A chunk
+// in which no block is read is skipped; one in which no stripe has a coefficient left skips transform and check.  pattern_of is copied synchronously
+// (every scrub call, a failed one included, leaves nothing in flight that reads the device copy), so the caller's array is free on every return.
+int verify_batch_set_chunks(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, const uint32_t* pattern_of, uint64_t seed, hipStream_t st,
+                            std::vector<uint8_t>& flag)
+{
+    ScrubState* s = c->scrub;
+    const ScrubSet* t = s->set;
+    int rc;
+    if (s->pattern_cap < count) {
+        if (s->d_pattern_of) (void)hipFree(s->d_pattern_of);
+        s->d_pattern_of = nullptr;
+        s->pattern_cap = 0;
+        HIP_TRY(hipMalloc((void**)&s->d_pattern_of, count * 4));
+        s->pattern_cap = count;
+    }
+    HIP_TRY(hipMemcpy(s->d_pattern_of, pattern_of, count * 4, hipMemcpyHostToDevice));
+    if ((rc = batch_begin(c, s, count, seed, st)) != FASTECC_OK) return rc;
+    const uint64_t chunk = chunk_of(c, s);
+    const uint64_t row = RW * s->batch_cap, NC = s->NC, S = c->S, m_lo = t->mlo_min;
+    const bool vec = (S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
+    for (uint64_t b0 = 0; b0 < count; b0 += chunk) {
+        const uint64_t B = std::min(chunk, count - b0);
+        uint64_t blocks_read = 0;
+        bool to_check = false;
+        for (uint64_t b = b0; b < b0 + B; b++) {
+            if (pattern_of[b] == FASTECC_PATTERN_NONE) continue;
+            blocks_read += s->n - t->absent[pattern_of[b]].size();
+            to_check = to_check || t->mlo[pattern_of[b]] < NC;
+        }
+        if (blocks_read == 0) continue;  // every stripe of the chunk is FASTECC_PATTERN_NONE (a stripe with a pattern reads at least k blocks)
+        // every workgroup resident at once, as for fastecc_verify_batch
+        const uint64_t groups = std::min<uint64_t>((B * s->n + 3) / 4, (uint64_t)c->cus * 6);
+        {
+            ProfScope ps(c, st, "fingerprint_set", blocks_read * S * 4);
+            if (vec)
+                hipLaunchKernelGGL(fingerprint_set_kernel<true>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)S, b0,
+                                   B, s->d_weights, s->d_pattern_of, t->d_pos, t->d_l, (uint32_t)NC, s->d_FB, row, s->d_flag);
+            else
+                hipLaunchKernelGGL(fingerprint_set_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)S, b0,
+                                   B, s->d_weights, s->d_pattern_of, t->d_pos, t->d_l, (uint32_t)NC, s->d_FB, row, s->d_flag);
+            HIP_TRY(hipGetLastError());
+        }
+        if (!to_check) continue;  // every stripe of the chunk has n - k blocks absent (or none named): only the words >= p count
+        {
+            ProfScope ps(c, st, "scrub_transform_batch");
+            if ((rc = transform_bitrev(s->ntt_batch, s->d_FB, s->d_GB, false, true, (uint32_t)(RW * B), st)) != FASTECC_OK) return rc;
+        }
+        {
+            ProfScope ps(c, st, "scrub_syndromes_set");
+            const uint64_t items = (NC - m_lo) * B;  // <= NC * batch_cap <= 2^21
+            hipLaunchKernelGGL(syndrome_set_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, s->d_GB, s->lgc, (uint32_t)NC, (uint32_t)m_lo, row,
+                               (uint32_t)B, b0, s->d_pattern_of, t->d_mlo, s->d_flag);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return batch_end(s, count, st, flag);
+}
+
+// a failed pass waits for what it enqueued: the next call may free or overwrite the buffers its kernels read
+int verify_batch_set_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, const uint32_t* pattern_of, uint64_t seed, hipStream_t st,
+                            std::vector<uint8_t>& flag)
+{
+    const int rc = verify_batch_set_chunks(c, data, parity, count, pattern_of, seed, st, flag);
+    if (rc != FASTECC_OK) (void)hipStreamSynchronize(st);
+    return rc;
+}
+
 // fastecc_verify; named = false: over all blocks whatever fastecc_scrub_erasures named (the closing check of fastecc_correct)
 int verify_impl(fastecc_ctx* c, const void* data, const void* parity, int mem_kind, void* stream, uint64_t seed, int* consistent, bool named)
 {
@@ -1137,10 +1399,47 @@ int verify_impl(fastecc_ctx* c, const void* data, const void* parity, int mem_ki
     CallLock lk(c->mu);
     return guarded([&]() -> int {
         std::vector<uint32_t> found;
-        const int r = locate(c, (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, true, named);
+        ScrubState* s = nullptr;
+        int r = scrub_state(c, &s);
+        if (r != FASTECC_OK) return r;
+        r = locate(c, s, erasures(s, named), (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, true);
         if (r == FASTECC_OK) *consistent = found.empty() ? 1 : 0;
         return r;
     });
+}
+
+// fastecc_correct on one stripe (DEVICE memory, arguments checked): locate under the single fastecc_scrub_erasures pattern, or under pattern q of
+// the set (from_set), then rebuild located and absent blocks and verify the whole codeword with the derived seed.  found: the located blocks.
+int correct_stripe(fastecc_ctx* c, void* data, void* parity, void* stream, uint64_t seed, bool from_set, uint32_t q, std::vector<uint32_t>& found)
+{
+    std::vector<uint32_t> absent;
+    {
+        CallLock lk(c->mu);
+        ScrubState* s = nullptr;
+        int r = scrub_state(c, &s);
+        if (r != FASTECC_OK) return r;
+        if (from_set && (!s->set || q >= s->set->P)) return FASTECC_E_INVAL;  // (the set was replaced while the call ran)
+        const Erasures er = from_set ? set_view(s, q) : erasures(s, true);
+        if (er.w) absent = *er.absent;
+        r = locate(c, s, er, (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, false);
+        if (r != FASTECC_OK) return r;
+    }
+    if (found.empty()) return FASTECC_OK;  // consistent: untouched, the absent blocks included
+    // the erasure decoder rebuilds the located blocks and, in the same repair, the ones named absent (prepare and repair take the
+    // context's lock themselves); the codeword is whole then, so the closing verify reads every block
+    std::vector<uint8_t> dp(c->K, 1), pp(c->Mu, 1);
+    for (uint32_t j : found) (j < c->K ? dp[j] : pp[j - c->K]) = 0;
+    for (uint32_t j : absent) (j < c->K ? dp[j] : pp[j - c->K]) = 0;
+    int r = fastecc_decode_prepare(c, dp.data(), pp.data());
+    if (r != FASTECC_OK) return r;
+    r = fastecc_repair(c, data, parity, FASTECC_MEM_DEVICE, stream);
+    if (r != FASTECC_OK) return r;
+    uint64_t seed2 = seed ^ 0x5C7B5C7B5C7B5C7Bull;
+    seed2 = splitmix64(seed2);
+    int ok = 0;
+    r = verify_impl(c, data, parity, FASTECC_MEM_DEVICE, stream, seed2, &ok, false);
+    if (r != FASTECC_OK) return r;
+    return ok ? FASTECC_OK : FASTECC_E_UNCORRECTABLE;
 }
 
 int report(const std::vector<uint32_t>& found, uint64_t* blocks, uint64_t cap, uint64_t* count)
@@ -1245,7 +1544,10 @@ int fastecc_locate_errors(fastecc_ctx* c, const void* data, const void* parity, 
     CallLock lk(c->mu);
     return guarded([&]() -> int {
         std::vector<uint32_t> found;
-        const int r = locate(c, (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, false);
+        ScrubState* s = nullptr;
+        int r = scrub_state(c, &s);
+        if (r != FASTECC_OK) return r;
+        r = locate(c, s, erasures(s, true), (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, false);
         return r == FASTECC_OK ? report(found, blocks, cap, count) : r;
     });
 }
@@ -1258,29 +1560,9 @@ int fastecc_correct(fastecc_ctx* c, void* data, void* parity, int mem_kind, void
     DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
     return guarded([&]() -> int {
-        std::vector<uint32_t> found, absent;
-        {
-            CallLock lk(c->mu);
-            const int r = locate(c, (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, false, true, &absent);
-            if (r != FASTECC_OK) return r;
-        }
-        if (found.empty()) return report(found, blocks, cap, count);  // consistent: untouched, the absent blocks included
-        // the erasure decoder rebuilds the located blocks and, in the same repair, the ones named absent (prepare and repair take the
-        // context's lock themselves); the codeword is whole then, so the closing verify reads every block
-        std::vector<uint8_t> dp(c->K, 1), pp(c->Mu, 1);
-        for (uint32_t j : found) (j < c->K ? dp[j] : pp[j - c->K]) = 0;
-        for (uint32_t j : absent) (j < c->K ? dp[j] : pp[j - c->K]) = 0;
-        int r = fastecc_decode_prepare(c, dp.data(), pp.data());
-        if (r != FASTECC_OK) return r;
-        r = fastecc_repair(c, data, parity, FASTECC_MEM_DEVICE, stream);
-        if (r != FASTECC_OK) return r;
-        uint64_t seed2 = seed ^ 0x5C7B5C7B5C7B5C7Bull;
-        seed2 = splitmix64(seed2);
-        int ok = 0;
-        r = verify_impl(c, data, parity, FASTECC_MEM_DEVICE, stream, seed2, &ok, false);
-        if (r != FASTECC_OK) return r;
-        if (!ok) return FASTECC_E_UNCORRECTABLE;
-        return report(found, blocks, cap, count);
+        std::vector<uint32_t> found;
+        const int r = correct_stripe(c, data, parity, stream, seed, false, 0, found);
+        return r == FASTECC_OK ? report(found, blocks, cap, count) : r;
     });
 }
 
@@ -1331,7 +1613,8 @@ int fastecc_locate_errors_batch(fastecc_ctx* c, const void* data, const void* pa
         for (size_t i = 0; i < list.size(); i++) {
             if (state[i] != LOC_FALLBACK) continue;
             // a word >= p in a present block, or more syndromes than the batched pass gathers: the single-stripe code through the stripe's own pointers
-            r = locate(c, (const uint32_t*)data + list[i] * data_words, (const uint32_t*)parity + list[i] * parity_words, seed, st, found[i], false);
+            r = locate(c, c->scrub, erasures(c->scrub, true), (const uint32_t*)data + list[i] * data_words, (const uint32_t*)parity + list[i] * parity_words, seed, st,
+                       found[i], false);
             if (r == FASTECC_E_UNCORRECTABLE) state[i] = LOC_UNCORRECTABLE;
             else if (r != FASTECC_OK) return r;
             else state[i] = LOC_FOUND;
@@ -1479,6 +1762,91 @@ int fastecc_correct_batch(fastecc_ctx* c, void* data, void* parity, uint64_t cou
         }
         std::copy(st.begin(), st.end(), status);
         *inconsistent = list.size();
+        return uncorrectable ? FASTECC_E_UNCORRECTABLE : FASTECC_OK;
+    });
+}
+
+int fastecc_scrub_erasures_set(fastecc_ctx* c, const uint8_t* data_present, const uint8_t* parity_present, uint64_t n_patterns)
+{
+    if (!c || (n_patterns && (!data_present || !parity_present)) || n_patterns > 4096) return FASTECC_E_INVAL;
+    if (c->sharded || c->p61 || c->field != FASTECC_FIELD_GF_FFF00001 || c->q > 1) return FASTECC_E_UNSUPPORTED;  // fastecc_scrub_erasures' refusals by kind
+    return guarded([&]() -> int {
+        std::vector<std::vector<uint32_t>> absent(n_patterns);
+        for (uint64_t q = 0; q < n_patterns; q++) {
+            for (uint64_t i = 0; i < c->K; i++)
+                if (!data_present[q * c->K + i]) absent[q].push_back((uint32_t)i);
+            for (uint64_t i = 0; i < c->Mu; i++)
+                if (!parity_present[q * c->Mu + i]) absent[q].push_back((uint32_t)(c->K + i));
+            if (absent[q].size() > c->Mu) return FASTECC_E_INVAL;
+        }
+        DeviceGuard dg(c->device);
+        if (!dg.ok) return FASTECC_E_DEVICE;
+        CallLock lk(c->mu);
+        return set_erasures_set(c, absent);
+    });
+}
+
+int fastecc_verify_batch_set(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const uint32_t* pattern_of, void* stream, uint64_t seed,
+                             uint8_t* consistent, uint64_t* inconsistent)
+{
+    if (!consistent || !inconsistent || !pattern_of) return FASTECC_E_INVAL;
+    int rc = batch_args(c, data, parity, count);
+    if (rc != FASTECC_OK) return rc;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallLock lk(c->mu);
+    if ((rc = set_args(c, pattern_of, count)) != FASTECC_OK) return rc;
+    return guarded([&]() -> int {
+        std::vector<uint8_t> flag;
+        const int r = verify_batch_set_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, pattern_of, seed, (hipStream_t)stream, flag);
+        if (r != FASTECC_OK) return r;
+        uint64_t bad = 0;
+        for (uint64_t b = 0; b < count; b++) {
+            consistent[b] = flag[b] ? 0 : 1;
+            bad += flag[b] ? 1 : 0;
+        }
+        *inconsistent = bad;
+        return FASTECC_OK;
+    });
+}
+
+int fastecc_correct_batch_set(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, void* stream, uint64_t seed, uint8_t* status,
+                              uint64_t* inconsistent)
+{
+    if (!status || !inconsistent || !pattern_of) return FASTECC_E_INVAL;
+    int rc = batch_args(c, data, parity, count);
+    if (rc != FASTECC_OK) return rc;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    return guarded([&]() -> int {
+        std::vector<uint8_t> flag;
+        {
+            CallLock lk(c->mu);
+            int r = set_args(c, pattern_of, count);
+            if (r != FASTECC_OK) return r;
+            if ((r = verify_batch_set_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, pattern_of, seed, (hipStream_t)stream, flag)) != FASTECC_OK) return r;
+        }
+        // fastecc_correct under the stripe's own pattern on each inconsistent stripe, one after the other (it takes the lock itself)
+        const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
+        std::vector<uint8_t> st(count, 0);
+        std::vector<uint32_t> found;
+        bool uncorrectable = false;
+        uint64_t bad = 0;
+        for (uint64_t b = 0; b < count; b++) {
+            if (!flag[b]) continue;
+            bad++;
+            const int r = correct_stripe(c, (char*)data + b * data_bytes, (char*)parity + b * parity_bytes, stream, seed, true, pattern_of[b], found);
+            if (r == FASTECC_E_UNCORRECTABLE) {
+                st[b] = 2;
+                uncorrectable = true;
+            } else if (r != FASTECC_OK) {
+                return r;
+            } else {
+                st[b] = found.empty() ? 0 : 1;
+            }
+        }
+        std::copy(st.begin(), st.end(), status);
+        *inconsistent = bad;
         return uncorrectable ? FASTECC_E_UNCORRECTABLE : FASTECC_OK;
     });
 }

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 370 /* 0.3.7: fastecc_decode_prepare_set, fastecc_decode_batch_set / _repair_batch_set: an erasure pattern per stripe (rotated placement) */
+#define FASTECC_VERSION 380 /* 0.3.8: fastecc_scrub_erasures_set, fastecc_verify_batch_set / _correct_batch_set: absent blocks per stripe (scrub of a degraded rotated pool) */
 
 enum {
     FASTECC_OK = 0,
@@ -533,6 +533,43 @@ int fastecc_correct_batch(fastecc_ctx *ctx, void *data, void *parity, uint64_t c
                           uint64_t *inconsistent);
 int fastecc_locate_errors_batch(fastecc_ctx *ctx, const void *data, const void *parity, uint64_t count, void *stream, uint64_t seed,
                                 uint8_t *status, uint64_t *blocks, uint64_t cap, uint32_t *counts, uint64_t *inconsistent);
+/*
+ * Scrubbing a DEGRADED pool with rotated placement: absent blocks PER STRIPE.  Stripe b of such a pool keeps block i on
+ * device (i + b) mod n, so one lost device costs every stripe a different block and no single fastecc_scrub_erasures pattern fits more than 1/n of
+ * the stripes.  Same codes, memory kind (DEVICE) and pool layout as fastecc_verify_batch.
+ *   fastecc_scrub_erasures_set : stores a SET of n_patterns absent-block patterns in the context's scrub state.  Pattern q's flags are
+ *       data_present[q*k .. q*k+k) and parity_present[q*(n-k) .. q*(n-k)+(n-k)), non-zero = present — the array layout of
+ *       fastecc_decode_prepare_set, so a caller passes the same two arrays to both.  A pattern names 0 .. n - k blocks absent (there is no 16-loss
+ *       limit: that belongs to the direct decode pass); one that names none asks for a full scrub of its stripes.  Limits: n_patterns <= 4096, and
+ *       n_patterns * NC <= 2^24 (NC = the code's transform length N << e: the per-pattern locator tables stay at most 64 MiB), beyond that
+ *       FASTECC_E_UNSUPPORTED.  FASTECC_E_INVAL: null context, null flag arrays with n_patterns > 0, n_patterns > 4096, a pattern with more than
+ *       n - k absent blocks.  FASTECC_E_UNSUPPORTED also for the contexts fastecc_scrub_erasures refuses: GF((2^61-1)^2), sharded, mixed radix.
+ *       n_patterns == 0 clears the set and frees its tables.  Synchronous: one table build and one synchronisation for the whole set; the new set
+ *       is built aside and swapped in under the context's lock, and a refused or failed call leaves the previous set in force.  The set is
+ *       independent of the single fastecc_scrub_erasures pattern in both directions — the five scrub calls above and fastecc_scrub_fingerprints
+ *       neither read nor change the set, the set calls neither read nor change the single pattern — and of both decode pattern states.
+ *   fastecc_verify_batch_set : pattern_of is a HOST array of `count` entries and may be reused on return.  pattern_of[b] < n_patterns:
+ *       consistent[b] is, bit for bit, what fastecc_scrub_erasures(that pattern) followed by fastecc_verify with the same seed answers for stripe
+ *       b alone; absent blocks are never read.  FASTECC_PATTERN_NONE: stripe b is not read at all (it may hold anything, words >= p included),
+ *       consistent[b] = 1 and it is not counted.  *inconsistent = the number of zeros in consistent.  Synchronous; reads only.
+ *       FASTECC_E_INVAL, before any device work and with nothing written: the refusals of fastecc_verify_batch, a null pattern_of, no set
+ *       prepared, an entry >= n_patterns that is not FASTECC_PATTERN_NONE.  FASTECC_E_UNSUPPORTED as for fastecc_verify_batch.  Option
+ *       "scrub_batch_chunk" applies.
+ *   fastecc_correct_batch_set : fastecc_verify_batch_set, then for each inconsistent stripe what fastecc_scrub_erasures(its pattern) +
+ *       fastecc_correct(same seed) does to that stripe alone: locate under that pattern's erasures (2t + b + w <= n - k, t <= "locate_max"),
+ *       rebuild located and absent blocks in one fastecc_decode_prepare + fastecc_repair, closing verify over all blocks with the derived seed.
+ *       status[b]: 0 = consistent or skipped, untouched, absent blocks included; 1 = corrected, the whole codeword is back; 2 = uncorrectable,
+ *       untouched.  *inconsistent = the number of stripes the verify pass flagged.  Returns FASTECC_E_UNCORRECTABLE if any status is 2, with
+ *       status filled either way.  REPLACES the context's single prepared decode pattern, as fastecc_correct does; the decode pattern SET is left
+ *       alone.  Inconsistent stripes are corrected one after the other ("correct_batch_mode" does not apply).  Workflow: this call makes the bad
+ *       stripes whole, then fastecc_repair_batch_set with the same flag arrays and pattern_of brings back the absent blocks of all the others.
+ * Profile scopes: "fingerprint_set" (its bytes: the blocks actually read), "scrub_transform_batch", "scrub_syndromes_set".
+ */
+int fastecc_scrub_erasures_set(fastecc_ctx *ctx, const uint8_t *data_present, const uint8_t *parity_present, uint64_t n_patterns);
+int fastecc_verify_batch_set(fastecc_ctx *ctx, const void *data, const void *parity, uint64_t count, const uint32_t *pattern_of,
+                             void *stream, uint64_t seed, uint8_t *consistent, uint64_t *inconsistent);
+int fastecc_correct_batch_set(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, const uint32_t *pattern_of,
+                              void *stream, uint64_t seed, uint8_t *status, uint64_t *inconsistent);
 /*
  * The fingerprints themselves (tests only, like fastecc_gf_binary: this call is no part of the scrub contract and may change).  It runs the
  * fingerprint pass of the scrub calls above — the same kernels through the same host paths and launch configurations — stops before the
