@@ -8,6 +8,8 @@ direct polynomial evaluation.  Bit-exact."""
 import numpy as np
 import pytest
 
+from pool_model import coset_generators, oracle_parity  # noqa: F401  (the coset form of the parity lives in tests/pool_model.py)
+
 pytestmark = pytest.mark.gpu
 
 P = 0xFFF00001
@@ -32,22 +34,6 @@ def to_dev(torch, a):
 
 def to_host(t, shape):
     return t.cpu().numpy().view(np.uint32).reshape(shape)
-
-
-def coset_generators(oracle, N, e):
-    """w_2N; w_4N, w_4N^3; w_8N, w_8N^3, w_8N^5, w_8N^7 — the nesting order of include/fastecc.h."""
-    gens = []
-    for j in range(1, e + 1):
-        w = oracle.gf_root(N << j)
-        gens += [oracle.gf_pow(w, c) for c in range(1, 1 << j, 2)]
-    return gens
-
-
-def oracle_parity(oracle, x, e):
-    N = x.shape[0]
-    coef = oracle.ntt_fast(x, inverse=True)
-    inv_n = oracle.gf_inv(N)
-    return np.concatenate([oracle.ntt_fast(oracle.scale_blocks(coef, inv_n, g)) for g in coset_generators(oracle, N, e)])
 
 
 @pytest.mark.parametrize("logn", [1, 2, 5, 6, 9, 10, 11, 13])

@@ -5,6 +5,8 @@ erasure pattern and repaired.  The fixed grids of the other test files pick thei
 import numpy as np
 import pytest
 
+from pool_model import expected_pow2  # the code forms live in one place: tests/pool_model.py
+
 pytestmark = pytest.mark.gpu
 
 P = 0xFFF00001
@@ -23,18 +25,6 @@ def torch_cuda():
 def fe(hip_lib):
     import fastecc_amd
     return fastecc_amd
-
-
-def expected_pow2(oracle, x, m):
-    """fastecc_create's code for any (k, m <= N): the (N + M, N) sub-code of the zero-extended stripe (RS.md:23-33)."""
-    k, S = x.shape
-    lg = max(1, int(np.ceil(np.log2(k))))
-    N = 1 << lg
-    lgm = int(np.ceil(np.log2(m))) if m > 1 else 0
-    fold = min(lg - lgm, 4)
-    padded = np.zeros((N, S), dtype=np.uint32)
-    padded[:k] = x
-    return oracle.encode_fast(padded)[:: 1 << fold][:m]
 
 
 def offset_view(torch, a, off):

@@ -1,0 +1,323 @@
+"""The pool model and its harness (tests/pool_model.py), checked without a GPU.
+
+  - the model is sound: its parity equals the generator matrix of fastecc_code_coefficient (host-only arithmetic of the library, the one
+    thing here that is not the oracle), and decoding its truth under every device-down pattern gives the truth back;
+  - every (config, seed) of tests/test_gpu_pool_sequences.py runs green on the exact numpy backend;
+  - seven injected defects are each reported at the step where they first change a byte or an answer;
+  - the committed seeds of every configuration cover what they must (operation kinds, variants, state probes, few illegal draws, the budget)."""
+import itertools
+
+import numpy as np
+import pytest
+
+import fastecc_amd as fe
+import pool_model as pm
+from pool_model import P
+
+FIXED = [c for c in pm.CONFIGS if c.placement == "fixed"]
+CASES = [(cfg.name, seed) for cfg in pm.CONFIGS for seed in pm.SEEDS]
+
+
+def group_of(cfg):
+    return cfg.name.rsplit("_", 1)[0]
+
+
+@pytest.fixture(scope="module")
+def generator_matrix():
+    cache = {}
+
+    def get(cfg):
+        key = (cfg.n, cfg.k, cfg.flags)
+        if key not in cache:
+            cache[key] = np.array([[fe.code_coefficient(cfg.n, cfg.k, i, q, cfg.flags) for i in range(cfg.k)] for q in range(cfg.n - cfg.k)],
+                                  dtype=np.uint64)
+        return cache[key]
+    return get
+
+
+def matrix_parity(G, x):
+    """parity block q = sum_i G[q, i] * data block i mod p, exactly (every product is below 2^64, the sum of reduced terms far below)"""
+    out = np.zeros((G.shape[0], x.shape[1]), dtype=np.uint64)
+    for i in range(G.shape[1]):
+        out += (G[:, i:i + 1] * x[i:i + 1].astype(np.uint64)) % np.uint64(P)
+    return (out % np.uint64(P)).astype(np.uint32)
+
+
+@pytest.mark.parametrize("cfg", FIXED, ids=[c.name for c in FIXED])
+def test_model_parity_is_the_generator_matrix(oracle, generator_matrix, cfg):
+    assert not cfg.order or fe.mixed_radix_order(cfg.k) == cfg.order
+    codec, G = pm.Codec(oracle, cfg.n, cfg.k, cfg.flags, cfg.order), generator_matrix(cfg)
+    rng = np.random.default_rng(cfg.n * 1000 + cfg.k)
+    x = rng.integers(0, P, size=(cfg.k, 5), dtype=np.uint64).astype(np.uint32)
+    x[0, :3] = [0, P - 1, 1]
+    assert np.array_equal(codec.parity(x), matrix_parity(G, x))
+    units = np.eye(cfg.k, dtype=np.uint32)  # word i of every block: the unit stripe e_i
+    assert np.array_equal(codec.parity(units), G.astype(np.uint32))
+
+
+def solve_lost_data(G, d, p, lost, k):
+    """the lost data blocks from the surviving ones: Gaussian elimination over GF(p) on the generator matrix (exact integers)"""
+    lost_d = [j for j in lost if j < k]
+    rows = [q for q in range(G.shape[0]) if q + k not in lost][:len(lost_d)]
+    out = d.copy()
+    for w in range(d.shape[1]):
+        A = [[int(G[q, i]) for i in lost_d] + [(int(p[q, w]) - sum(int(G[q, i]) * int(d[i, w]) for i in range(k) if i not in lost_d)) % P] for q in rows]
+        r = len(lost_d)
+        for c in range(r):
+            piv = next(i for i in range(c, r) if A[i][c])
+            A[c], A[piv] = A[piv], A[c]
+            inv = pow(A[c][c], P - 2, P)
+            A[c] = [v * inv % P for v in A[c]]
+            for i in range(r):
+                if i != c and A[i][c]:
+                    A[i] = [(v - A[i][c] * u) % P for v, u in zip(A[i], A[c])]
+        for c, j in enumerate(lost_d):
+            out[j, w] = A[c][r]
+    return out
+
+
+def oracle_decode(oracle, cfg, d, p, lost):
+    """Oracle.decode on the (2N,N) code this code is cut from: zero-extended data rows are known, folded parity block j sits at row
+    j << fold, the n = 4k code's first coset is the (2k,k) parity (its other cosets are not needed: at most two blocks are lost)."""
+    k, m, S = cfg.k, cfg.n - cfg.k, d.shape[1]
+    lg = max(1, int(np.ceil(np.log2(k))))
+    N = 1 << lg
+    coset = cfg.n == 4 * k
+    fold = 0 if coset else min(lg - (int(np.ceil(np.log2(m))) if m > 1 else 0), 4)
+    D, Q = np.zeros((N, S), np.uint32), np.zeros((N, S), np.uint32)
+    dp, pp = np.ones(N, np.uint8), np.zeros(N, np.uint8)
+    D[:k] = d
+    for j in range(min(m, N) if coset else m):
+        Q[j << fold], pp[j << fold] = p[j], 1
+    for j in lost:
+        if j < k:
+            dp[j], D[j] = 0, 0xABABABAB
+        elif (j - k) << fold < N and (not coset or j - k < N):
+            pp[(j - k) << fold] = 0
+    got = oracle.decode(D, Q, dp, pp)
+    assert got is not None
+    return got[:k]
+
+
+@pytest.mark.parametrize("cfg", FIXED, ids=[c.name for c in FIXED])
+def test_truth_decodes_under_every_device_down_pattern(oracle, generator_matrix, cfg):
+    codec = pm.Codec(oracle, cfg.n, cfg.k, cfg.flags, cfg.order)
+    rng = np.random.default_rng(cfg.n)
+    d = rng.integers(0, P, size=(cfg.k, 3), dtype=np.uint64).astype(np.uint32)
+    p = codec.parity(d)
+    pairs = [tuple(int(x) for x in rng.choice(cfg.n, size=2, replace=False)) for _ in range(24)] + [(0, cfg.k), (cfg.k - 1, cfg.n - 1), (0, 1)]
+    for lost in [(j,) for j in range(cfg.n)] + pairs:
+        if cfg.order:
+            got = solve_lost_data(generator_matrix(cfg), d, p, lost, cfg.k)
+        else:
+            got = oracle_decode(oracle, cfg, d, p, lost)
+        assert np.array_equal(got, d), lost
+
+
+_DRY = {}
+
+
+def dry_run(oracle, name, seed):
+    """the sequence of (name, seed) on the exact backend, once per session: its Coverage"""
+    if (name, seed) not in _DRY:
+        cfg = pm.config_named(name)
+        _DRY[name, seed] = pm.run_sequence(pm.ModelBackend(cfg, oracle), cfg, seed, oracle=oracle)
+    return _DRY[name, seed]
+
+
+@pytest.mark.parametrize("name,seed", CASES)
+def test_harness_passes_on_the_exact_backend(oracle, name, seed):
+    cfg = pm.config_named(name)
+    cov = dry_run(oracle, name, seed)
+    assert 4 * cov.skipped <= cov.drawn, (cov.skipped, cov.drawn)  # at most a quarter of the draws were illegal
+    assert 25 <= cfg.steps <= 40
+
+
+GROUPS = sorted({group_of(c) for c in pm.CONFIGS})
+
+
+@pytest.mark.parametrize("group", GROUPS)
+def test_coverage_of_the_committed_seeds(oracle, group):
+    """Run on the model backend: the sequences are the GPU test's (the generator never reads a backend), and Coverage.before raises if a
+    scrub operation meets a stripe outside the budget 2t + b + w <= n - k, t <= locate_max."""
+    cfgs = [c for c in pm.CONFIGS if group_of(c) == group]
+    total = pm.Coverage(None)
+    for cfg in cfgs:
+        for seed in pm.SEEDS:
+            total.merge(dry_run(oracle, cfg.name, seed))
+    mixed, k = bool(cfgs[0].flags), cfgs[0].k
+    kinds = [x for x in pm.KINDS if not (mixed and x == "corrupt")] + ["subrange"]
+    assert not {x: total.kinds[x] for x in kinds if total.kinds[x] < 5}
+    variants = ["set", "single", "correct_mode_0", "correct_mode_1", "correct_mode_2", "kernel_0", "kernel_1", "kernel_2", "write_parity",
+                "write_single", "write_batch", "subrange", "side_stream", "burst_two_streams"]
+    variants += ["segment_over_16"] if k > 16 else []   # more than 16 writes in one stripe need k > 16
+    variants += [] if mixed else ["multi_chunk"]        # a mixed-radix context refuses every scrub call
+    variants += ["over_16_lost"] if group == "256_128" else []
+    assert not [x for x in variants if not total.variants[x]]
+    probes = [f + "_after_" + v if f != "refused" else "refused_" + v for f, v in pm.PROBES]
+    if mixed:
+        probes = [x for x in probes if not x.startswith("scrub_") and not x.endswith(("_correct", "_locate"))]
+    assert not {x: total.probes[x] for x in probes if total.probes[x] < 2}
+
+
+def test_sequences_are_deterministic_and_replayable(oracle):
+    cfg = pm.config_named("20_16_s64_rotated")
+    logs = []
+    for steps in (None, None, 17):
+        log = []
+        pm.run_sequence(pm.ModelBackend(cfg, oracle), cfg, 3, steps=steps, oracle=oracle, on_step=lambda s, op: log.append(repr(op)))
+        logs.append(log)
+    assert logs[0] == logs[1] and len(logs[0]) == cfg.steps
+    assert logs[2] == logs[0][:17]
+
+
+def test_the_prepared_pattern_is_unspecified_after_correct(oracle):
+    """include/fastecc.h: fastecc_correct* REPLACES the prepared pattern; the model refuses to predict a use of it before a new decode_prepare."""
+    cfg = pm.config_named("20_16_s64_fixed")
+    model = pm.PoolModel(cfg, 1, oracle)
+    model.apply({"op": "prepare", "lost": [2]}, {})
+    model.apply({"op": "scrub_pattern", "absent": []}, {})
+    model.apply({"op": "correct", "set": False, "b0": 0, "b1": cfg.count, "seed": 1, "mode": 0}, {})
+    assert model.ctx.prepared == pm.UNSPECIFIED
+    probe = {"op": "probe_repair", "b": 0, "form": "repair", "dseed": 1}
+    with pytest.raises(pm.ModelError):
+        model.payload(probe)
+    with pytest.raises(pm.ModelError):
+        model.apply({"op": "repair", "set": False, "b0": 0, "b1": 2, "kernel": 0}, {})
+    model.apply({"op": "prepare", "lost": []}, {})
+    model.apply({"op": "repair", "set": False, "b0": 0, "b1": 2, "kernel": 0}, {})
+
+
+# ---- injected defects: each a ModelBackend that is wrong in one way; `fired` is the step at which the defect first changed a byte of the
+# pool or an answer as a caller sees them at the end of a step (None while it has not) ----
+class Defective(pm.ModelBackend):
+    """Runs an exact ModelBackend beside itself: `fired` is the first step after which its answers or its pool differ from the exact one's."""
+    fired = None
+
+    def __init__(self, cfg, oracle):
+        super().__init__(cfg, oracle)
+        self.exact, self.depth = pm.ModelBackend(cfg, oracle), 0
+
+    def start(self, d, p, quarantined):
+        super().start(d, p, quarantined)
+        self.exact.start(d, p, quarantined)
+
+    def run(self, op, pay):
+        self.depth += 1
+        got = super().run(op, pay)
+        self.depth -= 1
+        if self.depth == 0 and self.fired is None:
+            want = self.exact.run(op, pay)
+            same = all(pm._same(want[x], got.get(x)) for x in want) and np.array_equal(self.d, self.exact.d) and np.array_equal(self.p, self.exact.p)
+            if not same:
+                self.fired = self.step
+        return got
+
+
+class SkipsAParityBlock(Defective):
+    """update_batch skips one parity block of one touched stripe"""
+
+    def op_write(self, op, pay):
+        if op["form"] != "batch":
+            return super().op_write(op, pay)
+        b = op["writes"][0] // self.k
+        old = self.p[b, self.m - 1].copy()
+        super().op_write(op, pay)
+        self.p[b, self.m - 1] = old
+
+
+class TouchesAnotherStripe(Defective):
+    """update_batch touches a stripe that no write names"""
+
+    def op_write(self, op, pay):
+        super().op_write(op, pay)
+        touched = {w // self.k for w in op["writes"]}
+        others = [b for b in range(self.count) if b not in touched]
+        if op["form"] == "batch" and others:
+            self.p[others[len(others) // 2], 0, 0] ^= np.uint32(1)
+
+
+class ShiftedPatterns(Defective):
+    """repair_batch_set uses stripe b - 1's pattern for stripe b"""
+
+    def op_repair(self, op, pay):
+        if op["set"]:
+            po = op["pattern_of"]
+            shifted = [po[b] if po[b] == pm.PATTERN_NONE or b == 0 or po[b - 1] == pm.PATTERN_NONE else po[b - 1] for b in range(len(po))]
+            op = dict(op, pattern_of=shifted)
+        return super().op_repair(op, pay)
+
+
+class RewritesAbsentBlocks(Defective):
+    """correct_batch rewrites a consistent stripe's absent block"""
+
+    def op_correct(self, op, pay):
+        out = super().op_correct(op, pay)
+        if not op["set"] and out["code"] == pm.OK:
+            for i, b in enumerate(range(op["b0"], op["b1"])):
+                if out["status"][i] == 0:
+                    for j in self.scrub:
+                        self.blk(self.d, self.p, b, j)[:] = self.blk(self.td, self.tp, b, j)
+        return out
+
+
+class ReadsQuarantined(Defective):
+    """verify_batch_set reads a quarantined stripe: reports 0 for it"""
+
+    def op_verify(self, op, pay):
+        out = super().op_verify(op, pay)
+        if op["set"] and out["code"] == pm.OK:
+            for i, q in enumerate(op["pattern_of"]):
+                if q == pm.PATTERN_NONE:
+                    out["consistent"][i] = 0
+            out["inconsistent"] = out["consistent"].count(0)
+        return out
+
+
+class SetClobbersPrepared(Defective):
+    """decode_prepare_set clobbers the single prepared pattern"""
+
+    def op_prepare_set(self, op, pay):
+        super().op_prepare_set(op, pay)
+        self.prepared = self.prepared_set[0]
+
+
+class StaleChunking(Defective):
+    """a call after scrub_batch_chunk changed still walks the old chunks: the wrong stripes are answered"""
+    used = 0
+
+    def op_verify(self, op, pay):
+        out = super().op_verify(op, pay)
+        new = self.options.get("scrub_batch_chunk", 0)
+        if out["code"] == pm.OK and new != self.used:
+            right, cnt = list(out["consistent"]), op["b1"] - op["b0"]
+            old_c, new_c = self.used or 1 << 16, new or 1 << 16
+            src = [(i // new_c) * old_c + i % new_c for i in range(cnt)]
+            out["consistent"] = [right[s] if s < cnt else 1 for s in src]
+            out["inconsistent"] = out["consistent"].count(0)
+        self.used = new
+        return out
+
+
+DEFECTS = [SkipsAParityBlock, TouchesAnotherStripe, ShiftedPatterns, RewritesAbsentBlocks, ReadsQuarantined, SetClobbersPrepared, StaleChunking]
+DEFECT_CONFIGS = ("20_16_s64_fixed", "20_16_s64_rotated", "64_32_rotated", "32_8_fixed")
+
+
+@pytest.mark.parametrize("defect", DEFECTS, ids=[d.__name__ for d in DEFECTS])
+def test_injected_defect_is_reported_at_its_step(oracle, defect):
+    caught = 0
+    for name, seed in itertools.product(DEFECT_CONFIGS, pm.SEEDS):
+        cfg = pm.config_named(name)
+        backend = defect(cfg, oracle)
+        try:
+            pm.run_sequence(backend, cfg, seed, oracle=oracle)
+        except pm.SequenceFailure as e:
+            assert backend.fired == e.step, (name, seed, backend.fired, e.step)
+            text = str(e)
+            assert cfg.name in text and "seed %d" % seed in text and "step %d" % e.step in text
+            assert len(e.log) == e.step + 1 and all(line in text for line in e.log)  # the operation log up to that step
+            assert "steps=%d" % (e.step + 1) in text                                   # ... and how to replay it
+            caught += 1
+        else:
+            assert backend.fired is None, (name, seed, backend.fired)  # the defect changed something and no step noticed
+    assert caught >= 2, "no committed seed meets this defect: the generator is too weak"
