@@ -1,5 +1,5 @@
-// scrub.hip — error detection and location: fastecc_verify, fastecc_locate_errors, fastecc_correct and the batched fastecc_verify_batch,
-// fastecc_correct_batch, fastecc_locate_errors_batch (include/fastecc.h).
+// scrub.hip — error detection and location: fastecc_verify, fastecc_locate_errors, fastecc_correct, their batched, list and per-stripe-pattern forms
+// and degraded scrubbing (include/fastecc.h).  The kernels are in scrub_device.hpp.
 //
 // The erasure decoder (decode.hip) acts on losses the caller names.  Here the corrupted blocks are found first.  Every code of the
 // library is f (degree < N) on a subset of the NC-th roots of unity, NC = N << e, position u <-> w^u: data block i at i << e, parity at
@@ -13,36 +13,38 @@
 // rho_c[w] r_j[w] mod p with small random weights (rho < 2^20, splitmix64 of the seed), R = 3 columns.  F is linear, so the
 // fingerprints of a codeword are a codeword of the same code (of the polynomial sum_w rho_c[w] f_w) and the fingerprints of a corrupted
 // block differ from the clean ones except with probability <= 2^-20 per column.  The pass that reads the codeword once is the only
-// part that scales with the stripe; the rest works on NC x 4 words:
-//   fingerprint_kernel  : one wave per block, dwordx4 loads, v_mad_u64_u32 into 64-bit sums (a product is < 2^52), a per-block
-//                         "word >= p" flag (those blocks are certainly corrupt: known erasures), F written in position order;
-//   syndromes           : F times l(w^u) (the fixed erasures' values, cached per context, times the further erasures' factors),
-//                         the library's stand-alone inverse transform of NC points (transform_bitrev), and a pass that checks
-//                         every coefficient above the degree bound for zero and gathers the first 2 locate_max of each column;
-//   Berlekamp-Massey    : on the host, per column; the longest LFSR is the locator Lambda(x) = prod (1 - X_u x);
-//   root search         : Lambda(w^u) by Horner at every position on the device;
-//   confirmation        : the syndromes once more with the located positions erased must all vanish, in every column.
-// fastecc_correct then hands the located blocks to fastecc_decode_prepare + fastecc_repair.
-// fastecc_scrub_erasures names blocks that are absent: the fingerprint kernels skip them, their locator joins the
-// fixed erasures' in a table cached per pattern, w fewer syndromes are checked, and fastecc_correct rebuilds them with the located blocks.
-// fastecc_verify_batch / _correct_batch run the verify over many stripes at once: the stripe index becomes extra word columns of
-// the fingerprint stripe, so one transform serves a whole chunk of stripes (fingerprint_batch_kernel, syndrome_batch_kernel, verify_batch_locked).
-// fastecc_locate_errors_batch and the grouped path of fastecc_correct_batch run the same passes over a LIST of stripes of the pool:
-// all syndromes of the flagged stripes gathered at once (syndrome_gather_kernel), Berlekamp-Massey per stripe on the host, one root search for all
-// locators (root_search_batch_kernel), then one fastecc_decode_prepare and one list-form repair (decode.hip repair_list) per distinct set of lost blocks.
+// part that scales with the stripe; the rest works on NC x 4 words.
+//
+// The stages, in the order of this file:
+//   state        per context (scrub_state): geometry, position map, w^u, the fixed erasures' locator; the blocks named absent — one pattern
+//                (set_erasures) or a set with a pattern per stripe (set_erasures_set, section 19) — seen through Erasures: the
+//                fingerprint kernels skip them, their locator joins the fixed erasures', w fewer syndromes are checked.  Buffers only grow (grow).
+//   one stripe   locate: fingerprints (one wave per block, dwordx4 loads; a block with a word >= p is certainly corrupt: a known erasure), syndromes
+//                (F times the erasures' locator, the stand-alone inverse transform of NC points, every coefficient above the degree bound checked
+//                for zero and the first 2 locate_max of each column gathered), Berlekamp-Massey on the host per column and the longest LFSR as the
+//                locator Lambda(x) = prod (1 - X_u x) (longest_lfsr), Lambda(w^u) by Horner at every position on the device, the roots' blocks
+//                (accept_root), and the confirmation: the syndromes once more with the located positions erased must all vanish, in every column.
+//   chunk pass   many stripes (section 14): the stripe index becomes extra word columns of the fingerprint stripe, so one transform serves a whole
+//                chunk of stripes.  chunk_pass runs one chunk — fingerprints, transform, syndrome launch — in the form a ChunkForm names, for
+//                verify_batch_locked (the stripes of a batch), verify_list_locked and LocateList (a LIST of stripes of the pool, section 17) and
+//                verify_batch_set_locked (a pattern per stripe).  A pass that fails part-way waits for what it enqueued (settled).
+//   location     LocateList, per chunk of the flagged stripes: gather_chunk (all syndromes at once), solve_chunk (Berlekamp-Massey and the recurrence
+//                check per stripe on the host), search_chunk (one root search for all locators), accept_chunk.
+//   correction   correct_stripe: locate, fastecc_decode_prepare + fastecc_repair of the located and the absent blocks, the closing verify.
+//                CorrectBatch: flag_and_locate, group_by_lost_set, repair_groups (one prepare and one list-form repair, decode.hip repair_list, per
+//                distinct set of lost blocks), closing_verify, fallbacks (correct_stripe's work on what the grouped path does not take).
+//   entry points argument checks, then the stage inside on_device.
 #include <algorithm>
 #include <map>
 #include <memory>
 #include <vector>
 
 #include "drivers.hpp"
+#include "scrub_device.hpp"
 
 namespace fastecc {
 
 namespace {
-
-constexpr int R = 3;   // fingerprint columns (the transform stripe has 4 words per position; the 4th stays zero)
-constexpr int RW = 4;  // words per position of the fingerprint stripe
 
 uint64_t splitmix64(uint64_t& s)
 {
@@ -50,375 +52,6 @@ uint64_t splitmix64(uint64_t& s)
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
-}
-
-// x mod p for any 64-bit x (2^32 = 2^20 - 1 mod p); three folds leave < 2^33 < 3p
-__device__ __forceinline__ uint64_t fold64(uint64_t x)
-{
-    x = (x >> 32) * 0xFFFFFull + (x & 0xFFFFFFFFull);
-    x = (x >> 32) * 0xFFFFFull + (x & 0xFFFFFFFFull);
-    x = (x >> 32) * 0xFFFFFull + (x & 0xFFFFFFFFull);
-    return x;
-}
-__device__ __forceinline__ uint32_t reduce64(uint64_t x)
-{
-    x = fold64(x);
-    if (x >= gf::P) x -= gf::P;
-    if (x >= gf::P) x -= gf::P;
-    return (uint32_t)x;
-}
-
-__device__ __forceinline__ void mad3(uint64_t& a0, uint64_t& a1, uint64_t& a2, uint32_t v, uint32_t wx, uint32_t wy)
-{
-    // packed weights of one word: wx = rho0 | (rho2 & 0xFFF) << 20, wy = rho1 | (rho2 >> 12) << 20
-    const uint32_t r0 = wx & 0xFFFFFu, r1 = wy & 0xFFFFFu, r2 = (wx >> 20) | ((wy >> 20) << 12);
-    a0 += (uint64_t)v * r0;
-    a1 += (uint64_t)v * r1;
-    a2 += (uint64_t)v * r2;
-}
-
-// One wave's fingerprint of one block of S words.  VEC: S % 4 == 0 and a 16-byte aligned block — lane l reads words 4l + 256 i as
-// dwordx4, four loads in flight per batch; else one word per lane and step.  Sums: products < 2^52, folded every 4096 of them.
-// Every lane gets the three fingerprints (mod p) and whether some word of the block is >= p.
-template <bool VEC>
-__device__ __forceinline__ void block_fingerprint(const uint32_t* __restrict__ blk, uint32_t S, const uint2* __restrict__ wt, uint32_t lane, uint32_t f[R],
-                                                  bool& any_big)
-{
-    uint64_t a0 = 0, a1 = 0, a2 = 0;
-    uint32_t big = 0;
-    if (VEC) {
-        const uint4* wt4 = reinterpret_cast<const uint4*>(wt);
-        uint32_t batches = 0;
-        for (uint32_t base = lane * 4u; base < S; base += 1024u) {
-            uint4 v[4], wa[4], wb[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const uint32_t w = base + 256u * u;
-                if (w < S) {
-                    v[u] = *reinterpret_cast<const uint4*>(blk + w);
-                    wa[u] = wt4[w >> 1];
-                    wb[u] = wt4[(w >> 1) + 1];
-                } else {
-                    v[u] = wa[u] = wb[u] = make_uint4(0, 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                big |= (uint32_t)(v[u].x >= gf::P) | (uint32_t)(v[u].y >= gf::P) | (uint32_t)(v[u].z >= gf::P) | (uint32_t)(v[u].w >= gf::P);
-                mad3(a0, a1, a2, v[u].x, wa[u].x, wa[u].y);
-                mad3(a0, a1, a2, v[u].y, wa[u].z, wa[u].w);
-                mad3(a0, a1, a2, v[u].z, wb[u].x, wb[u].y);
-                mad3(a0, a1, a2, v[u].w, wb[u].z, wb[u].w);
-            }
-            if ((++batches & 255u) == 0) {  // 16 products per batch: 4096 since the last fold
-                a0 = fold64(a0);
-                a1 = fold64(a1);
-                a2 = fold64(a2);
-            }
-        }
-    } else {
-        uint32_t steps = 0;
-        for (uint32_t w = lane; w < S; w += 64u) {
-            const uint32_t v = blk[w];
-            const uint2 q = wt[w];
-            big |= (uint32_t)(v >= gf::P);
-            mad3(a0, a1, a2, v, q.x, q.y);
-            if ((++steps & 4095u) == 0) {
-                a0 = fold64(a0);
-                a1 = fold64(a1);
-                a2 = fold64(a2);
-            }
-        }
-    }
-    // lane sums < p, wave sums < 2^38
-    a0 = reduce64(a0);
-    a1 = reduce64(a1);
-    a2 = reduce64(a2);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a0 += __shfl_xor(a0, o, 64);
-        a1 += __shfl_xor(a1, o, 64);
-        a2 += __shfl_xor(a2, o, 64);
-    }
-    any_big = __any(big != 0);
-    f[0] = reduce64(a0);
-    f[1] = reduce64(a1);
-    f[2] = reduce64(a2);
-}
-
-// pos[j] of a block the caller named absent (fastecc_scrub_erasures) carries this mark: the block is not read
-constexpr uint32_t ABSENT = 0x80000000u;
-
-// One wave per block (blocks wave, wave + waves, ...).  F[pos[j] * 4 + c] receives the block's fingerprint c; a block with a word >= p
-// is appended to bad[1 ..] (bad[0] counts them).  An absent block is skipped (j and pos[j] are wave-uniform: no lane diverges) and its
-// F keeps whatever an earlier call left: the weigh pass multiplies it by a locator that is zero there.
-template <bool VEC>
-__global__ __launch_bounds__(256) void fingerprint_kernel(const uint32_t* __restrict__ data, const uint32_t* __restrict__ parity, uint32_t k_blocks,
-                                                          uint32_t n_blocks, uint32_t S, const uint2* __restrict__ wt, const uint32_t* __restrict__ pos,
-                                                          uint32_t* __restrict__ F, uint32_t* __restrict__ bad, uint32_t bad_cap)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    const uint32_t waves = (gridDim.x * blockDim.x) >> 6;
-    for (uint32_t j = wave; j < n_blocks; j += waves) {
-        const uint32_t u = pos[j];
-        if (u & ABSENT) continue;
-        const uint32_t* blk = j < k_blocks ? data + (size_t)j * S : parity + (size_t)(j - k_blocks) * S;
-        uint32_t fp[R];
-        bool any_big;
-        block_fingerprint<VEC>(blk, S, wt, lane, fp, any_big);
-        if (lane == 0) {
-            uint32_t* f = F + (size_t)u * RW;
-            f[0] = fp[0];
-            f[1] = fp[1];
-            f[2] = fp[2];
-            if (any_big) {
-                const uint32_t slot = atomicAdd(bad, 1u);
-                if (slot < bad_cap) bad[1 + slot] = j;
-            }
-        }
-    }
-}
-
-// fastecc_verify_batch: the same per block over the B stripes [b0, b0 + B) of a batch, global block g = b * n + j (stripe b - b0 of the chunk, block j;
-// both wave-uniform).  Fingerprint c of that block, times the locator of the fixed and the named erasures at its position (lfix, null: 1), lands in
-// F[pos[j] * row + (b - b0) * 4 + c] — the chunk's stripes are word columns of one fingerprint stripe of NC rows.  A block with a word >= p
-// sets flag[b] (a plain store of 1: idempotent, no atomics).  An absent block (pos[j] marked; wave-uniform) is not read and its entry is stored
-// as zero: nothing multiplies F by the locator afterwards, and the entry may hold another call's or another pattern's value.
-// At most 80 VGPRs: six waves per SIMD, the grid the host launches all resident.
-// LIST (batched location and the closing verify of fastecc_correct_batch): the chunk is B entries of a list of stripes of the
-// pool — list[bl] names the stripe whose blocks are read (wave-uniform like b), while the fingerprint columns, flag[] and big[] are addressed by the
-// position bl in the chunk (the host passes all three arrays from the chunk's first entry on; b0 is not used).  big[bl] = 1 records that a present
-// block of the entry held a word >= p (flag[bl] is set as well).  The list form needs two registers more than 80 in its vector form: five waves per
-// SIMD there (82 VGPRs, no scratch) instead of a spilled pointer; its grid is sized to match (list_chunk).
-template <bool VEC, bool LIST = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIST ? 5 : 6))) void fingerprint_batch_kernel(const uint32_t* __restrict__ data, const uint32_t* __restrict__ parity, uint32_t k_blocks,
-                                                                uint32_t n_blocks, uint32_t S, uint64_t b0, uint64_t B, const uint2* __restrict__ wt,
-                                                                const uint32_t* __restrict__ pos, const uint32_t* __restrict__ lfix, uint32_t* __restrict__ F,
-                                                                uint64_t row, uint8_t* __restrict__ flag, const uint64_t* __restrict__ list,
-                                                                uint8_t* __restrict__ big)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    const uint64_t waves = (gridDim.x * blockDim.x) >> 6;
-    const uint64_t total = B * n_blocks;
-    const uint64_t m_blocks = n_blocks - k_blocks;
-    for (uint64_t g = wave; g < total; g += waves) {
-        const uint64_t bl = g / n_blocks;
-        const uint32_t j = (uint32_t)(g - bl * n_blocks);
-        const uint32_t entry = __builtin_amdgcn_readfirstlane((uint32_t)bl);  // (LIST: a chunk has at most 2^16 entries)
-        const uint64_t b = LIST ? list[entry] : b0 + bl;
-        const uint32_t u = pos[j];
-        if (u & ABSENT) {
-            if (lane == 0) *reinterpret_cast<uint4*>(F + (uint64_t)(u & ~ABSENT) * row + bl * RW) = make_uint4(0, 0, 0, 0);
-            continue;
-        }
-        const uint32_t* blk = j < k_blocks ? data + (b * k_blocks + j) * S : parity + (b * m_blocks + (j - k_blocks)) * S;
-        uint32_t fp[R];
-        bool any_big;
-        block_fingerprint<VEC>(blk, S, wt, lane, fp, any_big);
-        if (lane == 0) {
-            const uint32_t l = lfix ? lfix[u] : 1u;
-            uint32_t* f = F + (uint64_t)u * row + bl * RW;
-            f[0] = gf::mul(fp[0], l);
-            f[1] = gf::mul(fp[1], l);
-            f[2] = gf::mul(fp[2], l);
-            if (any_big) {
-                if (LIST) {
-                    flag[entry] = 1;
-                    big[entry] = 1;
-                } else {
-                    flag[b] = 1;
-                }
-            }
-        }
-    }
-}
-
-// fastecc_verify_batch_set: fingerprint_batch_kernel's pass with a pattern PER STRIPE.  q = pattern_of[b] is read once per wave and
-// made uniform by readfirstlane, so q, pos_set[q * n + j] and the absent test are scalar loads and one scalar branch, as above.  A stripe with
-// q = FASTECC_PATTERN_NONE reads nothing and stores a zero entry at every one of its n positions (through pattern 0's position table: a set has at least
-// one pattern, and the mark is masked off); an absent block stores its zero entry; a present one F * lset[q * NC + u], the fixed and the pattern's own
-// erasures' locator at its position.  Every (stripe, block) entry of the chunk is stored by every call: nothing an earlier call, set or pattern left in F
-// is read.  Six waves per SIMD (at most 80 VGPRs), the grid all resident, as for the batch kernel.
-template <bool VEC>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void fingerprint_set_kernel(const uint32_t* __restrict__ data, const uint32_t* __restrict__ parity, uint32_t k_blocks,
-                                                              uint32_t n_blocks, uint32_t S, uint64_t b0, uint64_t B, const uint2* __restrict__ wt,
-                                                              const uint32_t* __restrict__ pattern_of, const uint32_t* __restrict__ pos_set,
-                                                              const uint32_t* __restrict__ lset, uint32_t NC, uint32_t* __restrict__ F, uint64_t row,
-                                                              uint8_t* __restrict__ flag)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    const uint64_t waves = (gridDim.x * blockDim.x) >> 6;
-    const uint64_t total = B * n_blocks;
-    const uint64_t m_blocks = n_blocks - k_blocks;
-    for (uint64_t g = wave; g < total; g += waves) {
-        const uint64_t bl = g / n_blocks;
-        const uint32_t j = (uint32_t)(g - bl * n_blocks);
-        const uint64_t b = b0 + bl;
-        const uint32_t q = __builtin_amdgcn_readfirstlane(pattern_of[b]);
-        const bool none = q == FASTECC_PATTERN_NONE;
-        const uint32_t u = pos_set[(none ? 0u : q) * n_blocks + j];
-        if (none || (u & ABSENT)) {
-            if (lane == 0) *reinterpret_cast<uint4*>(F + (uint64_t)(u & ~ABSENT) * row + bl * RW) = make_uint4(0, 0, 0, 0);
-            continue;
-        }
-        const uint32_t* blk = j < k_blocks ? data + (b * k_blocks + j) * S : parity + (b * m_blocks + (j - k_blocks)) * S;
-        uint32_t fp[R];
-        bool any_big;
-        block_fingerprint<VEC>(blk, S, wt, lane, fp, any_big);
-        if (lane == 0) {
-            const uint32_t l = lset[q * NC + u];
-            uint32_t* f = F + (uint64_t)u * row + bl * RW;
-            f[0] = gf::mul(fp[0], l);
-            f[1] = gf::mul(fp[1], l);
-            f[2] = gf::mul(fp[2], l);
-            if (any_big) flag[b] = 1;
-        }
-    }
-}
-
-// out[u] = base[u] (or 1) * prod_i (w^u - roots[i]); WITH_F: G[u][c] = F[u][c] * that instead (all plain representatives)
-template <bool WITH_F>
-__global__ __launch_bounds__(256) void locator_kernel(const uint32_t* __restrict__ base, const uint32_t* __restrict__ roots, uint32_t nroots,
-                                                      const uint32_t* __restrict__ wpow, uint32_t NC, const uint32_t* __restrict__ F, uint32_t* __restrict__ out)
-{
-    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= NC) return;
-    const uint32_t x = wpow[u];
-    uint32_t v = base ? base[u] : 1u;
-    for (uint32_t i = 0; i < nroots; i++) v = gf::mul(v, gf::sub(x, roots[i]));
-    if (!WITH_F) {
-        out[u] = v;
-        return;
-    }
-    const uint4 f = reinterpret_cast<const uint4*>(F)[u];
-    reinterpret_cast<uint4*>(out)[u] = make_uint4(gf::mul(f.x, v), gf::mul(f.y, v), gf::mul(f.z, v), 0u);
-}
-
-// fastecc_scrub_erasures_set: locator_kernel<false> for every pattern of a set at once, one grid row per pattern q:
-// out[q * NC + u] = base[u] (or 1) * prod (w^u - roots[i]), i in [off[q], off[q + 1])
-__global__ __launch_bounds__(256) void locator_set_kernel(const uint32_t* __restrict__ base, const uint32_t* __restrict__ roots, const uint32_t* __restrict__ off,
-                                                          const uint32_t* __restrict__ wpow, uint32_t NC, uint32_t* __restrict__ out)
-{
-    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x, q = blockIdx.y;
-    if (u >= NC) return;
-    const uint32_t x = wpow[u];
-    uint32_t v = base ? base[u] : 1u;
-    for (uint32_t i = off[q], e = off[q + 1]; i < e; i++) v = gf::mul(v, gf::sub(x, roots[i]));
-    out[(uint64_t)q * NC + u] = v;
-}
-
-// G holds the inverse transform in bit-reversed order (G[bitrev(m)] = NC * coefficient m).  Every coefficient m >= m_lo must vanish:
-// flag[0] |= 1 otherwise; the first `gather` of them per column go to syn[c * gather + (m - m_lo)].
-__global__ __launch_bounds__(256) void syndrome_kernel(const uint32_t* __restrict__ G, int lgc, uint32_t NC, uint32_t m_lo, uint32_t gather,
-                                                       uint32_t* __restrict__ syn, uint32_t* __restrict__ flag)
-{
-    const uint32_t m = m_lo + blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= NC) return;
-    const uint32_t slot = __brev(m) >> (32 - lgc);
-    const uint4 g = reinterpret_cast<const uint4*>(G)[slot];
-    if ((g.x | g.y | g.z) != 0) atomicOr(flag, 1u);
-    const uint32_t i = m - m_lo;
-    if (i < gather) {
-        syn[i] = g.x;
-        syn[gather + i] = g.y;
-        syn[2 * gather + i] = g.z;
-    }
-}
-
-// fastecc_verify_batch: G as above with the chunk's B stripes as word columns (row words per position); item i <-> stripe b = i % B of the chunk,
-// coefficient m = m_lo + i / B.  Any non-zero coefficient m >= m_lo in one of stripe b's three columns sets flag[b0 + b].
-__global__ __launch_bounds__(256) void syndrome_batch_kernel(const uint32_t* __restrict__ G, int lgc, uint32_t NC, uint32_t m_lo, uint64_t row, uint32_t B,
-                                                             uint64_t b0, uint8_t* __restrict__ flag)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (NC - m_lo) * B) return;
-    const uint32_t b = i % B, m = m_lo + i / B;
-    const uint32_t slot = __brev(m) >> (32 - lgc);
-    const uint4 g = *reinterpret_cast<const uint4*>(G + (uint64_t)slot * row + (uint64_t)b * RW);
-    if ((g.x | g.y | g.z) != 0) flag[b0 + b] = 1;
-}
-
-// fastecc_verify_batch_set: syndrome_batch_kernel's item mapping from m_lo = the smallest bound of the set on; stripe b0 + b checks the coefficients from its
-// own pattern's bound mlo_set[pattern_of[b0 + b]] = N + fixed + w on (the w below it are legitimately non-zero), a FASTECC_PATTERN_NONE stripe none
-__global__ __launch_bounds__(256) void syndrome_set_kernel(const uint32_t* __restrict__ G, int lgc, uint32_t NC, uint32_t m_lo, uint64_t row, uint32_t B,
-                                                           uint64_t b0, const uint32_t* __restrict__ pattern_of, const uint32_t* __restrict__ mlo_set,
-                                                           uint8_t* __restrict__ flag)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (NC - m_lo) * B) return;
-    const uint32_t b = i % B, m = m_lo + i / B;
-    const uint32_t q = pattern_of[b0 + b];
-    if (q == FASTECC_PATTERN_NONE || m < mlo_set[q]) return;
-    const uint32_t slot = __brev(m) >> (32 - lgc);
-    const uint4 g = *reinterpret_cast<const uint4*>(G + (uint64_t)slot * row + (uint64_t)b * RW);
-    if ((g.x | g.y | g.z) != 0) flag[b0 + b] = 1;
-}
-
-// Batched location: all avail = NC - m_lo coefficients from m_lo on of the chunk's B entries, by entry and column:
-// syn[(b * 3 + c) * avail + i] = NC * coefficient m_lo + i of column c of entry b (item = i * B + b, as above)
-__global__ __launch_bounds__(256) void syndrome_gather_kernel(const uint32_t* __restrict__ G, int lgc, uint32_t m_lo, uint32_t avail, uint64_t row, uint32_t B,
-                                                              uint32_t* __restrict__ syn)
-{
-    const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
-    if (item >= avail * B) return;
-    const uint32_t b = item % B, i = item / B;
-    const uint32_t slot = __brev(m_lo + i) >> (32 - lgc);
-    const uint4 g = *reinterpret_cast<const uint4*>(G + (uint64_t)slot * row + (uint64_t)b * RW);
-    uint32_t* o = syn + (uint64_t)b * R * avail + i;
-    o[0] = g.x;
-    o[avail] = g.y;
-    o[2 * (uint64_t)avail] = g.z;
-}
-
-// Batched location: thread (e, u) evaluates the locator of entry e — lambda[e * stride + 0 .. L[e]] — at w^u; a root is appended to entry e's own list
-// found[e * (cap + 1) + 1 ..] (found[e * (cap + 1)] counts all of them, the list keeps the first cap)
-__global__ __launch_bounds__(256) void root_search_batch_kernel(const uint32_t* __restrict__ lambda, const uint32_t* __restrict__ Ls, uint32_t stride,
-                                                                const uint32_t* __restrict__ wpow, uint32_t NC, uint32_t entries, uint32_t* __restrict__ found,
-                                                                uint32_t cap)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= entries * NC) return;
-    const uint32_t e = t / NC, u = t - e * NC;
-    const uint32_t* l = lambda + (uint64_t)e * stride;
-    const uint32_t L = Ls[e];
-    const uint32_t x = wpow[u];
-    uint32_t acc = l[L];
-    for (int i = (int)L - 1; i >= 0; i--) acc = gf::add(gf::mul(acc, x), l[i]);
-    if (acc == 0) {
-        uint32_t* f = found + (uint64_t)e * (cap + 1);
-        const uint32_t slot = atomicAdd(f, 1u);
-        if (slot < cap) f[1 + slot] = u;
-    }
-}
-
-// Lambda(w^u) == 0 -> u appended to found[1 ..] (found[0] counts)
-__global__ __launch_bounds__(256) void root_search_kernel(const uint32_t* __restrict__ lambda, uint32_t L, const uint32_t* __restrict__ wpow, uint32_t NC,
-                                                          uint32_t* __restrict__ found, uint32_t cap)
-{
-    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= NC) return;
-    const uint32_t x = wpow[u];
-    uint32_t acc = lambda[L];
-    for (int i = (int)L - 1; i >= 0; i--) acc = gf::add(gf::mul(acc, x), lambda[i]);
-    if (acc == 0) {
-        const uint32_t slot = atomicAdd(found, 1u);
-        if (slot < cap) found[1 + slot] = u;
-    }
-}
-
-__global__ __launch_bounds__(256) void powers_kernel(uint32_t* __restrict__ wpow, uint32_t w, uint32_t count)
-{
-    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= count) return;
-    uint32_t r = 1, b = w;
-    for (uint32_t e = u; e; e >>= 1) {
-        if (e & 1u) r = gf::mul(r, b);
-        b = gf::mul(b, b);
-    }
-    wpow[u] = r;
 }
 
 }  // namespace
@@ -471,8 +104,9 @@ struct ScrubState {
     uint32_t* d_lnamed = nullptr;           // NC words: d_lfix (or 1) times the locator of their positions at w^u
     // batched location and the list forms, all grow-only
     uint64_t* d_list = nullptr;             // the stripes a list pass runs over
-    uint8_t* d_lflag = nullptr;             // per list entry: [0, list_cap) inconsistent, [list_cap, 2 list_cap) a present block held a word >= p
     uint64_t list_cap = 0;
+    uint8_t* d_lflag = nullptr;             // per list entry: [0, lflag_cap) inconsistent, [lflag_cap, 2 lflag_cap) a present block held a word >= p
+    uint64_t lflag_cap = 0;                 // (grows with list_cap)
     uint32_t* d_loc = nullptr;              // one chunk's syndromes, then its locators, their lengths and the found lists
     uint64_t loc_words = 0;
     // fastecc_scrub_erasures_set: the pattern set (null: none) and the device copy of a call's pattern_of (grow-only)
@@ -519,6 +153,39 @@ Erasures set_view(const ScrubState* s, uint32_t q)
     const ScrubSet* t = s->set;
     const uint64_t w = t->absent[q].size();
     return {t->d_pos + (uint64_t)q * s->n, t->d_l + (uint64_t)q * s->NC, w, w ? &t->absent[q] : nullptr, w ? &t->is_absent[q] : nullptr};
+}
+
+// A grow-only device buffer: *p holds *cap elements of `elem` bytes and is replaced when `need` is more; a failed allocation leaves null and 0
+int grow(void** p, uint64_t* cap, uint64_t need, uint64_t elem)
+{
+    if (*cap >= need) return FASTECC_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    HIP_TRY(hipMalloc(p, need * elem));
+    *cap = need;
+    return FASTECC_OK;
+}
+
+// the fingerprint kernels' vector form: whole dwordx4 loads, 16-byte aligned stripes
+bool vec_form(const fastecc_ctx* c, const void* data, const void* parity)
+{
+    return (c->S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
+}
+
+// a fingerprint kernel in its vector (kv) or scalar (ks) form over `groups` workgroups of four waves
+template <class... K, class... A> void launch_fp(void (*kv)(K...), void (*ks)(K...), bool vec, uint64_t groups, hipStream_t st, A... args)
+{
+    hipLaunchKernelGGL(vec ? kv : ks, dim3((unsigned)groups), dim3(256), 0, st, args...);
+}
+
+// the frame of an entry point whose arguments are checked: the context's device current, exceptions turned into return codes (a body that touches the
+// scrub state takes the call lock first)
+template <class F> int on_device(fastecc_ctx* c, F body)
+{
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    return guarded(body);
 }
 
 int scrub_args(fastecc_ctx* c, const void* data, const void* parity, int mem_kind)
@@ -619,13 +286,8 @@ int small_buffers(ScrubState* s, uint32_t locate_max, Small* sm)
     sm->gather = std::min<uint64_t>(2ull * locate_max, m);
     sm->roots_cap = m + 1;
     const uint64_t words = (1 + sm->bad_cap) + 1 + (1 + sm->found_cap) + R * std::max<uint64_t>(sm->gather, 1) + (locate_max + 1) + sm->roots_cap;
-    if (words > s->small_words) {
-        if (s->d_small) (void)hipFree(s->d_small);
-        s->d_small = nullptr;
-        s->small_words = 0;
-        HIP_TRY(hipMalloc((void**)&s->d_small, words * 4));
-        s->small_words = words;
-    }
+    const int rc = grow((void**)&s->d_small, &s->small_words, words, 4);
+    if (rc != FASTECC_OK) return rc;
     uint32_t* p = s->d_small;
     sm->bad = p;
     p += 1 + sm->bad_cap;
@@ -668,17 +330,12 @@ int fingerprints(fastecc_ctx* c, ScrubState* s, const Small& sm, const Erasures&
     int rc = upload_weights(c, s, seed, st);
     if (rc != FASTECC_OK) return rc;
     HIP_TRY(hipMemsetAsync(sm.bad, 0, 4, st));
-    const bool vec = (c->S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
     // every workgroup resident at once (6 waves per SIMD; its 72 VGPRs would fit a seventh): a grid-stride loop over the blocks without a tail wave of late groups
     const uint64_t groups = std::min<uint64_t>((s->n + 3) / 4, (uint64_t)c->cus * 6);
     {
         ProfScope ps(c, st, "fingerprint", (s->n - er.w) * c->S * 4);
-        if (vec)
-            hipLaunchKernelGGL(fingerprint_kernel<true>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)c->S,
-                               s->d_weights, er.d_pos, s->d_F, sm.bad, (uint32_t)sm.bad_cap);
-        else
-            hipLaunchKernelGGL(fingerprint_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)c->S,
-                               s->d_weights, er.d_pos, s->d_F, sm.bad, (uint32_t)sm.bad_cap);
+        launch_fp(fingerprint_kernel<true>, fingerprint_kernel<false>, vec_form(c, data, parity), groups, st, data, parity, (uint32_t)s->k, (uint32_t)s->n,
+                  (uint32_t)c->S, s->d_weights, er.d_pos, s->d_F, sm.bad, (uint32_t)sm.bad_cap);
         HIP_TRY(hipGetLastError());
     }
     uint32_t nb = 0;
@@ -769,6 +426,33 @@ int berlekamp_massey(const uint32_t* s, uint32_t count, std::vector<uint32_t>& C
     return (int)L;
 }
 
+// The decisions of location, shared by one stripe (locate) and the list form (LocateList).  The locator of a stripe's syndromes — `gather` per column,
+// column c at syn + c * column_stride: the longest of the columns' LFSRs, the first column on ties (a column may miss an error with probability
+// <= 2^-20; the caller's confirmation covers all).  Returns its length L with lambda[0 .. L], or 0 where location refuses: no LFSR, more than tmax
+// errors, or fewer than 2L syndromes.  cand: scratch (a caller with many stripes keeps it).
+int longest_lfsr(const uint32_t* syn, uint64_t column_stride, uint64_t gather, uint64_t tmax, std::vector<uint32_t>& lambda, std::vector<uint32_t>& cand)
+{
+    int L = 0;
+    for (int col = 0; col < R; col++) {
+        const int Lc = berlekamp_massey(syn + col * column_stride, (uint32_t)gather, cand);
+        if (Lc > L) {
+            L = Lc;
+            lambda = cand;
+        }
+    }
+    return (L == 0 || (uint64_t)L > tmax || 2ull * (uint64_t)L > gather) ? 0 : L;
+}
+
+// The locator's root at position u names the block there: appended to `blocks`, or false where no block is there or the block is already erased —
+// named absent by `er`, or one of `bad` (sorted; null: none)
+bool accept_root(uint32_t u, const std::vector<uint32_t>& block_at, const Erasures& er, const std::vector<uint32_t>* bad, std::vector<uint32_t>& blocks)
+{
+    const uint32_t j = block_at[u];
+    if (j == ~0u || (bad && std::binary_search(bad->begin(), bad->end(), j)) || (er.w && (*er.is_absent)[j])) return false;
+    blocks.push_back(j);
+    return true;
+}
+
 // fastecc_locate_errors on a locked context: the sorted codeword indices of the corrupted blocks, or FASTECC_E_UNCORRECTABLE.  The blocks
 // `er` names absent are erased and not read; with the view of no pattern every block is read.
 int locate(fastecc_ctx* c, ScrubState* s, const Erasures& er, const uint32_t* data, const uint32_t* parity, uint64_t seed, hipStream_t st,
@@ -805,17 +489,9 @@ int locate(fastecc_ctx* c, ScrubState* s, const Erasures& er, const uint32_t* da
     rc = syndromes(c, s, sm, er, erased, gather, st, &nonzero, &syn);
     if (rc != FASTECC_OK) return rc;
     if (nonzero) {
-        // the locator: the longest of the columns' LFSRs (a column may miss an error with probability <= 2^-20; the check below covers all)
         std::vector<uint32_t> lambda, cand;
-        int L = 0;
-        for (int col = 0; col < R; col++) {
-            const int Lc = berlekamp_massey(syn.data() + col * gather, (uint32_t)gather, cand);
-            if (Lc > L) {
-                L = Lc;
-                lambda = cand;
-            }
-        }
-        if (L == 0 || (uint32_t)L > tmax || 2ull * (uint64_t)L > gather) return FASTECC_E_UNCORRECTABLE;
+        const int L = longest_lfsr(syn.data(), gather, gather, tmax, lambda, cand);
+        if (L == 0) return FASTECC_E_UNCORRECTABLE;
         HIP_TRY(hipMemcpyAsync(sm.lambda, lambda.data(), (L + 1) * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(sm.found, 0, 4, st));
         {
@@ -831,10 +507,8 @@ int locate(fastecc_ctx* c, ScrubState* s, const Erasures& er, const uint32_t* da
         std::vector<uint32_t> roots(nf);
         HIP_TRY(hipMemcpy(roots.data(), sm.found + 1, nf * 4, hipMemcpyDeviceToHost));
         for (uint32_t u : roots) {
-            const uint32_t j = s->block_at[u];
-            if (j == ~0u || std::binary_search(bad.begin(), bad.end(), j) || (er.w && (*er.is_absent)[j])) return FASTECC_E_UNCORRECTABLE;  // no block there, or one already erased
+            if (!accept_root(u, s->block_at, er, &bad, result)) return FASTECC_E_UNCORRECTABLE;
             erased.push_back(u);
-            result.push_back(j);
         }
         // confirmation: with the located blocks erased too, every syndrome of every column vanishes
         rc = syndromes(c, s, sm, er, erased, 0, st, &nonzero, nullptr);
@@ -913,13 +587,7 @@ int batch_begin(fastecc_ctx* c, ScrubState* s, uint64_t count, uint64_t seed, hi
 {
     int rc = batch_state(c, s);
     if (rc != FASTECC_OK) return rc;
-    if (s->flag_cap < count) {
-        if (s->d_flag) (void)hipFree(s->d_flag);
-        s->d_flag = nullptr;
-        s->flag_cap = 0;
-        HIP_TRY(hipMalloc((void**)&s->d_flag, count));
-        s->flag_cap = count;
-    }
+    if ((rc = grow((void**)&s->d_flag, &s->flag_cap, count, 1)) != FASTECC_OK) return rc;
     if ((rc = upload_weights(c, s, seed, st)) != FASTECC_OK) return rc;
     HIP_TRY(hipMemsetAsync(s->d_flag, 0, count, st));
     return FASTECC_OK;
@@ -933,122 +601,138 @@ int batch_end(ScrubState* s, uint64_t count, hipStream_t st, std::vector<uint8_t
     return FASTECC_OK;
 }
 
-// fastecc_verify_batch on a locked context: flag[b] = 1 iff fastecc_verify with this seed would find stripe b inconsistent.  Per chunk of B
-// stripes: the fingerprints (weighed by the locator of the fixed and the named erasures as they are stored; absent blocks are not read and
-// store zero), one transform of NC points over 4B word columns, the syndrome check of every stripe from coefficient N + fixed + w on; then
-// one copy of the flags and one synchronisation for the whole call.
-// probe: the chunks end after their fingerprint pass (nothing else sets a flag then: flag[b] = 1 iff a block of stripe b holds a word >= p).
-int verify_batch_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, uint64_t seed, hipStream_t st, std::vector<uint8_t>& flag,
-                        const Probe* probe = nullptr)
+uint64_t chunk_of(const fastecc_ctx* c, const ScrubState* s)
 {
-    ScrubState* s = nullptr;
-    int rc = scrub_state(c, &s);
-    if (rc != FASTECC_OK) return rc;
-    if ((rc = batch_begin(c, s, count, seed, st)) != FASTECC_OK) return rc;
-    const uint64_t chunk = c->scrub_batch_chunk > 0 ? std::min<uint64_t>(s->batch_cap, (uint64_t)c->scrub_batch_chunk) : s->batch_cap;
-    const Erasures er = erasures(s, true);
-    const uint64_t row = RW * s->batch_cap, NC = s->NC, m_lo = s->N + s->fixed + er.w, S = c->S;
-    const bool vec = (S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
-    for (uint64_t b0 = 0; b0 < count; b0 += chunk) {
-        const uint64_t B = std::min(chunk, count - b0);
-        // every workgroup resident at once, as for one stripe
-        const uint64_t groups = std::min<uint64_t>((B * s->n + 3) / 4, (uint64_t)c->cus * 6);
-        {
-            ProfScope ps(c, st, "fingerprint_batch", B * (s->n - er.w) * S * 4);
-            if (vec)
-                hipLaunchKernelGGL(fingerprint_batch_kernel<true>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)S,
-                                   b0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, s->d_flag, nullptr, nullptr);
-            else
-                hipLaunchKernelGGL(fingerprint_batch_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)S,
-                                   b0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, s->d_flag, nullptr, nullptr);
-            HIP_TRY(hipGetLastError());
-        }
-        if (probe) {
-            if ((rc = probe_chunk(s, B, st, probe->out + b0 * s->n * R)) != FASTECC_OK) return rc;
-            continue;
-        }
-        if (m_lo >= NC) continue;  // n - k blocks named absent: no coefficient is left to check, only the words >= p count
-        {
-            ProfScope ps(c, st, "scrub_transform_batch");
-            if ((rc = transform_bitrev(s->ntt_batch, s->d_FB, s->d_GB, false, true, (uint32_t)(RW * B), st)) != FASTECC_OK) return rc;
-        }
-        {
-            ProfScope ps(c, st, "scrub_syndromes_batch");
-            const uint64_t items = (NC - m_lo) * B;  // <= NC * batch_cap <= 2^21
-            hipLaunchKernelGGL(syndrome_batch_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, s->d_GB, s->lgc, (uint32_t)NC, (uint32_t)m_lo, row,
-                               (uint32_t)B, b0, s->d_flag);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    return batch_end(s, count, st, flag);
+    return c->scrub_batch_chunk > 0 ? std::min<uint64_t>(s->batch_cap, (uint64_t)c->scrub_batch_chunk) : s->batch_cap;
 }
 
-// ---- list forms (DESIGN.md section 17): the same passes over the stripes list[0 .. L) of the pool ----
-
-// the device copy of a list and its cleared per-entry flags; enqueued on st (the host list must live until the next synchronise)
-int upload_list(ScrubState* s, const std::vector<uint64_t>& list, hipStream_t st)
+// A batched pass that fails part-way waits for what it enqueued: the next call may free or overwrite the buffers its kernels read
+template <class F> int settled(hipStream_t st, F pass)
 {
-    const uint64_t L = list.size();
-    if (s->list_cap < L) {
-        if (s->d_list) (void)hipFree(s->d_list);
-        if (s->d_lflag) (void)hipFree(s->d_lflag);
-        s->d_list = nullptr;
-        s->d_lflag = nullptr;
-        s->list_cap = 0;
-        HIP_TRY(hipMalloc((void**)&s->d_list, L * 8));
-        HIP_TRY(hipMalloc((void**)&s->d_lflag, 2 * L));
-        s->list_cap = L;
-    }
-    HIP_TRY(hipMemcpyAsync(s->d_list, list.data(), L * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(s->d_lflag, 0, 2 * s->list_cap, st));
-    return FASTECC_OK;
+    const int rc = pass();
+    if (rc != FASTECC_OK) (void)hipStreamSynchronize(st);
+    return rc;
 }
 
-// One chunk of verify_batch_locked over the list entries [l0, l0 + B) of s->d_list: fingerprints, transform and either the flags of those entries
-// (syn == null) or all their `avail` = NC - m_lo syndromes gathered to syn.  Nothing is copied back and nothing waits — unless probe_out is
-// given (fastecc_scrub_fingerprints): then the chunk ends after the fingerprint pass with its fingerprints copied there (probe_chunk).
-int list_chunk(fastecc_ctx* c, ScrubState* s, const Erasures& er, const uint32_t* data, const uint32_t* parity, uint64_t l0, uint64_t B, hipStream_t st,
-               uint32_t* syn, uint32_t* probe_out = nullptr)
+// ---- the chunk pass: every batched verify and the batched location run their chunks through chunk_pass, in the form a ChunkForm names ----
+// Fp, the fingerprint launch: BATCH stripes [b0, b0 + B) of the call under `er`, flags in d_flag; LIST entries [b0, b0 + B) of d_list under `er`, flags
+// and big marks in d_lflag; SET stripes [b0, b0 + B) under d_pattern_of and the set's tables, flags in d_flag.  Syn, the syndrome launch: FLAGS a non-zero
+// coefficient from m_lo on sets the entry's flag; GATHER all of them are copied to syn_out; SET they are checked from the stripe's own bound on.
+enum class Fp { BATCH, LIST, SET };
+enum class Syn { FLAGS, GATHER, SET };
+constexpr const char* FP_SCOPE[] = {"fingerprint_batch", "fingerprint_batch_list", "fingerprint_set"};
+constexpr const char* SYN_SCOPE[] = {"scrub_syndromes_batch", "scrub_syndromes_gather", "scrub_syndromes_set"};
+
+struct ChunkForm {
+    Fp fp;
+    Syn syn;
+    uint64_t m_lo;         // the first coefficient the syndrome launch looks at
+    bool check;            // some coefficient is left to check (else the chunk ends after its fingerprints: only the words >= p count)
+    Erasures er;           // BATCH, LIST: the pattern
+    uint32_t* syn_out;     // GATHER: device, B x R x (NC - m_lo) words
+    uint64_t blocks_read;  // SET: the blocks the chunk reads (the others read B (n - er.w))
+};
+
+// One chunk of B entries from b0 on: the fingerprints (weighed by the erasures' locator as they are stored; absent blocks are not read and store
+// zero), one transform of NC points over 4B word columns, the syndrome launch.  Nothing is copied back and nothing waits — unless `probe` is
+// given (fastecc_scrub_fingerprints): then the chunk ends after its fingerprint launch with its fingerprints copied out (probe_chunk).
+int chunk_pass(fastecc_ctx* c, ScrubState* s, const ChunkForm& f, const uint32_t* data, const uint32_t* parity, uint64_t b0, uint64_t B, hipStream_t st,
+               const Probe* probe = nullptr)
 {
-    const uint64_t row = RW * s->batch_cap, NC = s->NC, m_lo = s->N + s->fixed + er.w, S = c->S;
-    const bool vec = (S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
-    const uint64_t groups = std::min<uint64_t>((B * s->n + 3) / 4, (uint64_t)c->cus * 5);  // every workgroup resident at once: five waves per SIMD
-    uint8_t *flag = s->d_lflag, *big = s->d_lflag + s->list_cap;
+    const ScrubSet* t = s->set;
+    const uint64_t row = RW * s->batch_cap;
+    const uint32_t k = (uint32_t)s->k, n = (uint32_t)s->n, S = (uint32_t)c->S, NC = (uint32_t)s->NC, m_lo = (uint32_t)f.m_lo;
+    const bool vec = vec_form(c, data, parity), list = f.fp == Fp::LIST;
+    // every workgroup resident at once, as for one stripe: six waves per SIMD, five for the list kernel
+    const uint64_t groups = std::min<uint64_t>((B * n + 3) / 4, (uint64_t)c->cus * (list ? 5 : 6));
+    uint8_t* flag = list ? s->d_lflag : s->d_flag;
     {
-        ProfScope ps(c, st, "fingerprint_batch_list", B * (s->n - er.w) * S * 4);
-        if (vec)
-            hipLaunchKernelGGL((fingerprint_batch_kernel<true, true>), dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n,
-                               (uint32_t)S, (uint64_t)0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, flag + l0, s->d_list + l0, big + l0);
-        else
-            hipLaunchKernelGGL((fingerprint_batch_kernel<false, true>), dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n,
-                               (uint32_t)S, (uint64_t)0, B, s->d_weights, er.d_pos, er.d_loc, s->d_FB, row, flag + l0, s->d_list + l0, big + l0);
+        ProfScope ps(c, st, FP_SCOPE[(int)f.fp], (f.fp == Fp::SET ? f.blocks_read : B * (n - f.er.w)) * S * 4);
+        switch (f.fp) {
+        case Fp::BATCH:
+            launch_fp(fingerprint_batch_kernel<true>, fingerprint_batch_kernel<false>, vec, groups, st, data, parity, k, n, S, b0, B, s->d_weights, f.er.d_pos,
+                      f.er.d_loc, s->d_FB, row, flag, nullptr, nullptr);
+            break;
+        case Fp::LIST:  // flags, list and big marks from the chunk's first entry on; b0 is not used
+            launch_fp(fingerprint_batch_kernel<true, true>, fingerprint_batch_kernel<false, true>, vec, groups, st, data, parity, k, n, S, (uint64_t)0, B,
+                      s->d_weights, f.er.d_pos, f.er.d_loc, s->d_FB, row, flag + b0, s->d_list + b0, flag + s->lflag_cap + b0);
+            break;
+        case Fp::SET:
+            launch_fp(fingerprint_set_kernel<true>, fingerprint_set_kernel<false>, vec, groups, st, data, parity, k, n, S, b0, B, s->d_weights, s->d_pattern_of,
+                      t->d_pos, t->d_l, NC, s->d_FB, row, flag);
+            break;
+        }
         HIP_TRY(hipGetLastError());
     }
-    if (probe_out) return probe_chunk(s, B, st, probe_out);
-    if (m_lo >= NC) return FASTECC_OK;
+    if (probe) return probe_chunk(s, B, st, probe->out + b0 * n * R);
+    if (!f.check) return FASTECC_OK;
     {
         ProfScope ps(c, st, "scrub_transform_batch");
         const int rc = transform_bitrev(s->ntt_batch, s->d_FB, s->d_GB, false, true, (uint32_t)(RW * B), st);
         if (rc != FASTECC_OK) return rc;
     }
-    const uint64_t items = (NC - m_lo) * B;  // <= NC * batch_cap <= 2^21
-    if (syn) {
-        ProfScope ps(c, st, "scrub_syndromes_gather");
-        hipLaunchKernelGGL(syndrome_gather_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, s->d_GB, s->lgc, (uint32_t)m_lo, (uint32_t)(NC - m_lo), row,
-                           (uint32_t)B, syn);
-        HIP_TRY(hipGetLastError());
-    } else {
-        ProfScope ps(c, st, "scrub_syndromes_batch");
-        hipLaunchKernelGGL(syndrome_batch_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, s->d_GB, s->lgc, (uint32_t)NC, (uint32_t)m_lo, row,
-                           (uint32_t)B, l0, flag);
+    {
+        ProfScope ps(c, st, SYN_SCOPE[(int)f.syn]);
+        const uint64_t items = (uint64_t)(NC - m_lo) * B;  // <= NC * batch_cap <= 2^21
+        const dim3 grid((unsigned)((items + 255) / 256));
+        switch (f.syn) {
+        case Syn::FLAGS:
+            hipLaunchKernelGGL(syndrome_batch_kernel, grid, dim3(256), 0, st, s->d_GB, s->lgc, NC, m_lo, row, (uint32_t)B, b0, flag);
+            break;
+        case Syn::GATHER:
+            hipLaunchKernelGGL(syndrome_gather_kernel, grid, dim3(256), 0, st, s->d_GB, s->lgc, m_lo, NC - m_lo, row, (uint32_t)B, f.syn_out);
+            break;
+        case Syn::SET:
+            hipLaunchKernelGGL(syndrome_set_kernel, grid, dim3(256), 0, st, s->d_GB, s->lgc, NC, m_lo, row, (uint32_t)B, b0, s->d_pattern_of, t->d_mlo, flag);
+            break;
+        }
         HIP_TRY(hipGetLastError());
     }
     return FASTECC_OK;
 }
 
-uint64_t chunk_of(const fastecc_ctx* c, const ScrubState* s)
+// the form of the single named pattern (`named`), or of no pattern: flags, or every syndrome gathered to syn_out
+ChunkForm pattern_form(const ScrubState* s, Fp fp, bool named, uint32_t* syn_out = nullptr)
 {
-    return c->scrub_batch_chunk > 0 ? std::min<uint64_t>(s->batch_cap, (uint64_t)c->scrub_batch_chunk) : s->batch_cap;
+    const Erasures er = erasures(s, named);
+    const uint64_t m_lo = s->N + s->fixed + er.w;  // m_lo >= NC: n - k blocks named absent, no coefficient is left to check
+    return {fp, syn_out ? Syn::GATHER : Syn::FLAGS, m_lo, m_lo < s->NC, er, syn_out, 0};
+}
+
+// fastecc_verify_batch on a locked context: flag[b] = 1 iff fastecc_verify with this seed would find stripe b inconsistent.  The chunks of
+// B stripes in the BATCH form, then one copy of the flags and one synchronisation for the whole call.
+// probe: the chunks end after their fingerprint pass (nothing else sets a flag then: flag[b] = 1 iff a block of stripe b holds a word >= p).
+int verify_batch_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, uint64_t seed, hipStream_t st, std::vector<uint8_t>& flag,
+                        const Probe* probe = nullptr)
+{
+    return settled(st, [&]() -> int {
+        ScrubState* s = nullptr;
+        int rc = scrub_state(c, &s);
+        if (rc != FASTECC_OK) return rc;
+        if ((rc = batch_begin(c, s, count, seed, st)) != FASTECC_OK) return rc;
+        const ChunkForm f = pattern_form(s, Fp::BATCH, true);
+        const uint64_t chunk = chunk_of(c, s);
+        for (uint64_t b0 = 0; b0 < count; b0 += chunk)
+            if ((rc = chunk_pass(c, s, f, data, parity, b0, std::min(chunk, count - b0), st, probe)) != FASTECC_OK) return rc;
+        return batch_end(s, count, st, flag);
+    });
+}
+
+// ---- list forms (DESIGN.md section 17): the same passes over the stripes list[0 .. L) of the pool ----
+
+// What a list pass needs before its first chunk: the chunk buffers, the seed's weights, the device copy of the list and its cleared per-entry flags;
+// enqueued on st (the host list must live until the next synchronise)
+int list_begin(fastecc_ctx* c, ScrubState* s, const std::vector<uint64_t>& list, uint64_t seed, hipStream_t st)
+{
+    const uint64_t L = list.size();
+    int rc = batch_state(c, s);
+    if (rc == FASTECC_OK) rc = upload_weights(c, s, seed, st);
+    if (rc == FASTECC_OK) rc = grow((void**)&s->d_list, &s->list_cap, L, 8);
+    if (rc == FASTECC_OK) rc = grow((void**)&s->d_lflag, &s->lflag_cap, L, 2);
+    if (rc != FASTECC_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_list, list.data(), L * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(s->d_lflag, 0, 2 * s->lflag_cap, st));
+    return FASTECC_OK;
 }
 
 // verify_batch_locked over the stripes `list` of the pool: flag[i] = 1 iff fastecc_verify with this seed would find stripe list[i] inconsistent
@@ -1057,20 +741,20 @@ uint64_t chunk_of(const fastecc_ctx* c, const ScrubState* s)
 int verify_list_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, const std::vector<uint64_t>& list, uint64_t seed, hipStream_t st, bool named,
                        std::vector<uint8_t>& flag, const Probe* probe = nullptr)
 {
-    ScrubState* s = nullptr;
-    int rc = scrub_state(c, &s);
-    if (rc != FASTECC_OK) return rc;
-    if ((rc = batch_state(c, s)) != FASTECC_OK) return rc;
-    if ((rc = upload_weights(c, s, seed, st)) != FASTECC_OK) return rc;
-    if ((rc = upload_list(s, list, st)) != FASTECC_OK) return rc;
-    const Erasures er = erasures(s, named);
-    const uint64_t chunk = chunk_of(c, s), L = list.size();
-    for (uint64_t l0 = 0; l0 < L; l0 += chunk)
-        if ((rc = list_chunk(c, s, er, data, parity, l0, std::min(chunk, L - l0), st, nullptr, probe ? probe->out + l0 * s->n * R : nullptr)) != FASTECC_OK) return rc;
-    flag.assign(L, 0);
-    HIP_TRY(hipMemcpyAsync(flag.data(), s->d_lflag + (probe ? s->list_cap : 0), L, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return FASTECC_OK;
+    return settled(st, [&]() -> int {
+        ScrubState* s = nullptr;
+        int rc = scrub_state(c, &s);
+        if (rc != FASTECC_OK) return rc;
+        if ((rc = list_begin(c, s, list, seed, st)) != FASTECC_OK) return rc;
+        const ChunkForm f = pattern_form(s, Fp::LIST, named);
+        const uint64_t chunk = chunk_of(c, s), L = list.size();
+        for (uint64_t l0 = 0; l0 < L; l0 += chunk)
+            if ((rc = chunk_pass(c, s, f, data, parity, l0, std::min(chunk, L - l0), st, probe)) != FASTECC_OK) return rc;
+        flag.assign(L, 0);
+        HIP_TRY(hipMemcpyAsync(flag.data(), s->d_lflag + (probe ? s->lflag_cap : 0), L, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return FASTECC_OK;
+    });
 }
 
 // whether every s[i], L <= i < count, obeys the recurrence of lambda (lambda[0] = 1, length L)
@@ -1090,67 +774,66 @@ enum : uint8_t { LOC_FALLBACK = 0, LOC_FOUND = 1, LOC_UNCORRECTABLE = 2 };
 // Batched location on a locked context: for the stripes `list` of the pool — all of them inconsistent under `seed` and the
 // named erasures — state[i] = LOC_FOUND with blocks[i] the located blocks (increasing; what fastecc_locate_errors returns for that stripe),
 // LOC_UNCORRECTABLE where it would refuse, or LOC_FALLBACK for a stripe this path does not take: a present block holds a word >= p, or the code
-// has more than 512 syndromes.  Per chunk: one list pass that gathers every syndrome, Berlekamp-Massey and the recurrence check on the host,
-// one root search over all locators; two synchronisations.
-int locate_list(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, const std::vector<uint64_t>& list, uint64_t seed, hipStream_t st,
-                std::vector<uint8_t>& state, std::vector<std::vector<uint32_t>>& blocks)
-{
-    constexpr uint64_t GATHER_MAX = 512;
-    ScrubState* s = nullptr;
-    int rc = scrub_state(c, &s);
-    if (rc != FASTECC_OK) return rc;
-    const uint64_t L = list.size();
-    state.assign(L, LOC_FALLBACK);
-    blocks.assign(L, {});
-    const Erasures er = erasures(s, true);
-    const uint64_t m = s->n - s->k, avail = m > er.w ? m - er.w : 0, tmax = (uint64_t)c->locate_max;
-    if (L == 0 || avail == 0 || avail > GATHER_MAX) return FASTECC_OK;
-    if ((rc = batch_state(c, s)) != FASTECC_OK) return rc;
-    if ((rc = upload_weights(c, s, seed, st)) != FASTECC_OK) return rc;
-    if ((rc = upload_list(s, list, st)) != FASTECC_OK) return rc;
-    const uint64_t chunk = std::min(chunk_of(c, s), L), gather = std::min<uint64_t>(2 * tmax, avail);
-    const uint64_t lmax = std::min<uint64_t>(tmax, gather / 2), stride = lmax + 1, cap = lmax + 1;
-    // the chunk's buffer: syndromes | locators | their lengths | found lists
-    const uint64_t syn_words = chunk * R * avail, lam_words = chunk * stride, found_words = chunk * (cap + 1);
-    const uint64_t words = syn_words + lam_words + chunk + found_words;
-    if (s->loc_words < words) {
-        if (s->d_loc) (void)hipFree(s->d_loc);
-        s->d_loc = nullptr;
-        s->loc_words = 0;
-        HIP_TRY(hipMalloc((void**)&s->d_loc, words * 4));
-        s->loc_words = words;
+// has more than 512 syndromes.  Per chunk: one list pass that gathers every syndrome (gather_chunk), Berlekamp-Massey and the recurrence check on
+// the host (solve_chunk), one root search over all locators (search_chunk), the roots' blocks (accept_chunk); two synchronisations.
+struct LocateList {
+    static constexpr uint64_t GATHER_MAX = 512;
+    fastecc_ctx* c;
+    ScrubState* s;
+    const uint32_t *data, *parity;
+    const std::vector<uint64_t>& list;
+    uint64_t seed;
+    hipStream_t st;
+    std::vector<uint8_t>& state;
+    std::vector<std::vector<uint32_t>>& blocks;
+    ChunkForm form{};                                                  // the list pass that gathers; form.syn_out: the chunk's syndromes
+    uint64_t avail = 0, tmax = 0, gather = 0, stride = 0, cap = 0;     // syndromes per column, locate_max, those Berlekamp-Massey reads, words per locator, roots kept
+    uint32_t *d_lam = nullptr, *d_len = nullptr, *d_found = nullptr;   // the chunk's locators, their lengths, the found lists
+    std::vector<uint32_t> syn, len, found, cand;                       // host copies; Berlekamp-Massey's scratch
+    std::vector<uint8_t> big;
+    std::vector<uint64_t> who;                                         // list entries with a locator, in table order
+    std::vector<std::vector<uint32_t>> lambdas;                        // their locators
+
+    // the chunk's buffer (d_loc, grow-only): syndromes | locators | their lengths | found lists
+    int layout(uint64_t chunk)
+    {
+        gather = std::min<uint64_t>(2 * tmax, avail);
+        stride = cap = std::min<uint64_t>(tmax, gather / 2) + 1;
+        const uint64_t syn_words = chunk * R * avail, lam_words = chunk * stride, found_words = chunk * (cap + 1);
+        const int rc = grow((void**)&s->d_loc, &s->loc_words, syn_words + lam_words + chunk + found_words, 4);
+        if (rc != FASTECC_OK) return rc;
+        form = pattern_form(s, Fp::LIST, true, s->d_loc);
+        d_lam = s->d_loc + syn_words;
+        d_len = d_lam + lam_words;
+        d_found = d_len + chunk;
+        syn.resize(syn_words);
+        big.resize(chunk);
+        return FASTECC_OK;
     }
-    uint32_t *d_syn = s->d_loc, *d_lam = d_syn + syn_words, *d_len = d_lam + lam_words, *d_found = d_len + chunk;
-    std::vector<uint32_t> syn(syn_words), lam, len, found, cand;
-    std::vector<uint8_t> big(chunk);
-    std::vector<uint64_t> who;                   // list entries with a locator, in table order
-    std::vector<std::vector<uint32_t>> lambdas;  // their locators
-    for (uint64_t l0 = 0; l0 < L; l0 += chunk) {
-        const uint64_t B = std::min(chunk, L - l0);
-        if ((rc = list_chunk(c, s, er, data, parity, l0, B, st, d_syn)) != FASTECC_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(syn.data(), d_syn, B * R * avail * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(big.data(), s->d_lflag + s->list_cap + l0, B, hipMemcpyDeviceToHost, st));
+
+    // the list pass over entries [l0, l0 + B), every syndrome and the big marks copied back; the chunk's first synchronisation
+    int gather_chunk(uint64_t l0, uint64_t B)
+    {
+        const int rc = chunk_pass(c, s, form, data, parity, l0, B, st);
+        if (rc != FASTECC_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(syn.data(), form.syn_out, B * R * avail * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(big.data(), s->d_lflag + s->lflag_cap + l0, B, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
+        return FASTECC_OK;
+    }
+
+    // host only: who and lambdas, the entries with a locator that every syndrome confirms; the others keep LOC_FALLBACK or become LOC_UNCORRECTABLE
+    void solve_chunk(uint64_t l0, uint64_t B)
+    {
         who.clear();
         lambdas.clear();
         for (uint64_t b = 0; b < B; b++) {
             if (big[b]) continue;  // known erasures besides the named ones: the single-stripe code
             const uint32_t* sy = syn.data() + b * R * avail;
-            bool nonzero = false;
-            for (uint64_t i = 0; i < R * avail && !nonzero; i++) nonzero = sy[i] != 0;
-            if (!nonzero) continue;  // (consistent after all: cannot happen for a stripe the same seed flagged)
-            // locate()'s decisions: the longest of the columns' LFSRs, the first column on ties
-            std::vector<uint32_t> lambda;
-            int len_best = 0;
-            for (int col = 0; col < R; col++) {
-                const int Lc = berlekamp_massey(sy + col * avail, (uint32_t)gather, cand);
-                if (Lc > len_best) {
-                    len_best = Lc;
-                    lambda = cand;
-                }
-            }
+            if (std::all_of(sy, sy + R * avail, [](uint32_t v) { return v == 0; })) continue;  // (consistent after all: cannot happen for a stripe the same seed flagged)
             state[l0 + b] = LOC_UNCORRECTABLE;
-            if (len_best == 0 || (uint64_t)len_best > tmax || 2ull * (uint64_t)len_best > gather) continue;
+            std::vector<uint32_t> lambda;
+            if (longest_lfsr(sy, avail, gather, tmax, lambda, cand) == 0) continue;
             // confirmation: every syndrome of every column obeys the locator's recurrence
             bool ok = true;
             for (int col = 0; col < R && ok; col++) ok = obeys_recurrence(sy + col * avail, avail, lambda);
@@ -1158,9 +841,13 @@ int locate_list(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, co
             who.push_back(l0 + b);
             lambdas.push_back(std::move(lambda));
         }
-        if (who.empty()) continue;
+    }
+
+    // the locators uploaded, one root search over all of them, the found lists copied back; the chunk's second synchronisation
+    int search_chunk()
+    {
         const uint64_t E = who.size();
-        lam.assign(E * stride, 0);
+        std::vector<uint32_t> lam(E * stride, 0);
         len.resize(E);
         for (uint64_t e = 0; e < E; e++) {
             std::copy(lambdas[e].begin(), lambdas[e].end(), lam.begin() + e * stride);
@@ -1178,23 +865,59 @@ int locate_list(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, co
         found.resize(E * (cap + 1));
         HIP_TRY(hipMemcpyAsync(found.data(), d_found, E * (cap + 1) * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        for (uint64_t e = 0; e < E; e++) {
+        return FASTECC_OK;
+    }
+
+    // an entry whose locator splits into as many distinct roots as its length, each at a block that is there and not erased, is LOC_FOUND
+    void accept_chunk()
+    {
+        for (uint64_t e = 0; e < who.size(); e++) {
             const uint32_t* f = found.data() + e * (cap + 1);
             if (f[0] != len[e]) continue;  // a locator splits into distinct roots at the code's positions, or it is no locator
             std::vector<uint32_t> js;
             bool ok = true;
-            for (uint32_t i = 0; i < f[0] && ok; i++) {
-                const uint32_t j = s->block_at[f[1 + i]];
-                ok = j != ~0u && !(er.w && (*er.is_absent)[j]);  // a block is there, and not one already erased
-                js.push_back(j);
-            }
+            for (uint32_t i = 0; i < f[0] && ok; i++) ok = accept_root(f[1 + i], s->block_at, form.er, nullptr, js);
             if (!ok) continue;
             std::sort(js.begin(), js.end());
             blocks[who[e]] = std::move(js);
             state[who[e]] = LOC_FOUND;
         }
     }
-    return FASTECC_OK;
+
+    int run()
+    {
+        const uint64_t L = list.size(), m = s->n - s->k, w = erasures(s, true).w;
+        state.assign(L, LOC_FALLBACK);
+        blocks.assign(L, {});
+        avail = m > w ? m - w : 0;
+        tmax = (uint64_t)c->locate_max;
+        if (L == 0 || avail == 0 || avail > GATHER_MAX) return FASTECC_OK;
+        int rc = list_begin(c, s, list, seed, st);
+        if (rc != FASTECC_OK) return rc;
+        const uint64_t chunk = std::min(chunk_of(c, s), L);
+        if ((rc = layout(chunk)) != FASTECC_OK) return rc;
+        for (uint64_t l0 = 0; l0 < L; l0 += chunk) {
+            const uint64_t B = std::min(chunk, L - l0);
+            if ((rc = gather_chunk(l0, B)) != FASTECC_OK) return rc;
+            solve_chunk(l0, B);
+            if (who.empty()) continue;
+            if ((rc = search_chunk()) != FASTECC_OK) return rc;
+            accept_chunk();
+        }
+        return FASTECC_OK;
+    }
+};
+
+int locate_list(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, const std::vector<uint64_t>& list, uint64_t seed, hipStream_t st,
+                std::vector<uint8_t>& state, std::vector<std::vector<uint32_t>>& blocks)
+{
+    return settled(st, [&]() -> int {
+        ScrubState* s = nullptr;
+        const int rc = scrub_state(c, &s);
+        if (rc != FASTECC_OK) return rc;
+        LocateList ll{c, s, data, parity, list, seed, st, state, blocks};
+        return ll.run();
+    });
 }
 
 // fastecc_scrub_erasures on a locked context: `absent` (codeword indices, increasing, at most n - k) replaces the named pattern.  The marked
@@ -1320,72 +1043,67 @@ int set_args(const fastecc_ctx* c, const uint32_t* pattern_of, uint64_t count)
 
 // fastecc_verify_batch_set on a locked context (set_args passed): verify_batch_locked with stripe b under pattern pattern_of[b] of the set.
 // flag[b] = 1 iff fastecc_scrub_erasures(that pattern) + fastecc_verify with this seed would find stripe b inconsistent; 0 for FASTECC_PATTERN_NONE.
-// Per chunk: the fingerprints (fingerprint_set_kernel), one transform, the syndrome check of every stripe from its own pattern's bound on.  A chunk
-// in which no block is read is skipped; one in which no stripe has a coefficient left skips transform and check.  pattern_of is copied synchronously
+// The chunks in the SET form, the syndrome check of every stripe from its own pattern's bound on.  A chunk in which no block is read is skipped; one
+// in which no stripe has a coefficient left (n - k blocks absent, or none named) skips transform and check.  pattern_of is copied synchronously
 // (every scrub call, a failed one included, leaves nothing in flight that reads the device copy), so the caller's array is free on every return.
-int verify_batch_set_chunks(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, const uint32_t* pattern_of, uint64_t seed, hipStream_t st,
-                            std::vector<uint8_t>& flag)
-{
-    ScrubState* s = c->scrub;
-    const ScrubSet* t = s->set;
-    int rc;
-    if (s->pattern_cap < count) {
-        if (s->d_pattern_of) (void)hipFree(s->d_pattern_of);
-        s->d_pattern_of = nullptr;
-        s->pattern_cap = 0;
-        HIP_TRY(hipMalloc((void**)&s->d_pattern_of, count * 4));
-        s->pattern_cap = count;
-    }
-    HIP_TRY(hipMemcpy(s->d_pattern_of, pattern_of, count * 4, hipMemcpyHostToDevice));
-    if ((rc = batch_begin(c, s, count, seed, st)) != FASTECC_OK) return rc;
-    const uint64_t chunk = chunk_of(c, s);
-    const uint64_t row = RW * s->batch_cap, NC = s->NC, S = c->S, m_lo = t->mlo_min;
-    const bool vec = (S % 4) == 0 && (((uintptr_t)data | (uintptr_t)parity) & 15u) == 0;
-    for (uint64_t b0 = 0; b0 < count; b0 += chunk) {
-        const uint64_t B = std::min(chunk, count - b0);
-        uint64_t blocks_read = 0;
-        bool to_check = false;
-        for (uint64_t b = b0; b < b0 + B; b++) {
-            if (pattern_of[b] == FASTECC_PATTERN_NONE) continue;
-            blocks_read += s->n - t->absent[pattern_of[b]].size();
-            to_check = to_check || t->mlo[pattern_of[b]] < NC;
-        }
-        if (blocks_read == 0) continue;  // every stripe of the chunk is FASTECC_PATTERN_NONE (a stripe with a pattern reads at least k blocks)
-        // every workgroup resident at once, as for fastecc_verify_batch
-        const uint64_t groups = std::min<uint64_t>((B * s->n + 3) / 4, (uint64_t)c->cus * 6);
-        {
-            ProfScope ps(c, st, "fingerprint_set", blocks_read * S * 4);
-            if (vec)
-                hipLaunchKernelGGL(fingerprint_set_kernel<true>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)S, b0,
-                                   B, s->d_weights, s->d_pattern_of, t->d_pos, t->d_l, (uint32_t)NC, s->d_FB, row, s->d_flag);
-            else
-                hipLaunchKernelGGL(fingerprint_set_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, data, parity, (uint32_t)s->k, (uint32_t)s->n, (uint32_t)S, b0,
-                                   B, s->d_weights, s->d_pattern_of, t->d_pos, t->d_l, (uint32_t)NC, s->d_FB, row, s->d_flag);
-            HIP_TRY(hipGetLastError());
-        }
-        if (!to_check) continue;  // every stripe of the chunk has n - k blocks absent (or none named): only the words >= p count
-        {
-            ProfScope ps(c, st, "scrub_transform_batch");
-            if ((rc = transform_bitrev(s->ntt_batch, s->d_FB, s->d_GB, false, true, (uint32_t)(RW * B), st)) != FASTECC_OK) return rc;
-        }
-        {
-            ProfScope ps(c, st, "scrub_syndromes_set");
-            const uint64_t items = (NC - m_lo) * B;  // <= NC * batch_cap <= 2^21
-            hipLaunchKernelGGL(syndrome_set_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, s->d_GB, s->lgc, (uint32_t)NC, (uint32_t)m_lo, row,
-                               (uint32_t)B, b0, s->d_pattern_of, t->d_mlo, s->d_flag);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    return batch_end(s, count, st, flag);
-}
-
-// a failed pass waits for what it enqueued: the next call may free or overwrite the buffers its kernels read
 int verify_batch_set_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, const uint32_t* pattern_of, uint64_t seed, hipStream_t st,
                             std::vector<uint8_t>& flag)
 {
-    const int rc = verify_batch_set_chunks(c, data, parity, count, pattern_of, seed, st, flag);
-    if (rc != FASTECC_OK) (void)hipStreamSynchronize(st);
-    return rc;
+    return settled(st, [&]() -> int {
+        ScrubState* s = c->scrub;
+        const ScrubSet* t = s->set;
+        int rc = grow((void**)&s->d_pattern_of, &s->pattern_cap, count, 4);
+        if (rc != FASTECC_OK) return rc;
+        HIP_TRY(hipMemcpy(s->d_pattern_of, pattern_of, count * 4, hipMemcpyHostToDevice));
+        if ((rc = batch_begin(c, s, count, seed, st)) != FASTECC_OK) return rc;
+        const uint64_t chunk = chunk_of(c, s);
+        ChunkForm f{Fp::SET, Syn::SET, t->mlo_min, false, {}, nullptr, 0};
+        for (uint64_t b0 = 0; b0 < count; b0 += chunk) {
+            const uint64_t B = std::min(chunk, count - b0);
+            f.blocks_read = 0;
+            f.check = false;
+            for (uint64_t b = b0; b < b0 + B; b++) {
+                if (pattern_of[b] == FASTECC_PATTERN_NONE) continue;
+                f.blocks_read += s->n - t->absent[pattern_of[b]].size();
+                f.check = f.check || t->mlo[pattern_of[b]] < s->NC;
+            }
+            if (f.blocks_read == 0) continue;  // every stripe of the chunk is FASTECC_PATTERN_NONE (a stripe with a pattern reads at least k blocks)
+            if ((rc = chunk_pass(c, s, f, data, parity, b0, B, st)) != FASTECC_OK) return rc;
+        }
+        return batch_end(s, count, st, flag);
+    });
+}
+
+// the seed of the closing verify of fastecc_correct and fastecc_correct_batch
+uint64_t closing_seed(uint64_t seed)
+{
+    uint64_t state = seed ^ 0x5C7B5C7B5C7B5C7Bull;
+    return splitmix64(state);
+}
+
+// fastecc_decode_prepare for exactly the blocks `lost` (codeword indices); it takes the context's lock itself
+int prepare_lost(fastecc_ctx* c, const std::vector<uint32_t>& lost)
+{
+    std::vector<uint8_t> dp(c->K, 1), pp(c->Mu, 1);
+    for (uint32_t j : lost) (j < c->K ? dp[j] : pp[j - c->K]) = 0;
+    return fastecc_decode_prepare(c, dp.data(), pp.data());
+}
+
+// a verify pass's flags as the entry points report them
+void report_flags(const std::vector<uint8_t>& flag, uint8_t* consistent, uint64_t* inconsistent)
+{
+    for (size_t b = 0; b < flag.size(); b++) consistent[b] = flag[b] ? 0 : 1;
+    *inconsistent = (uint64_t)(flag.size() - std::count(flag.begin(), flag.end(), (uint8_t)0));
+}
+
+// One stripe's return code rc of fastecc_correct (or of locate) in a batch's terms: FASTECC_E_UNCORRECTABLE is *status = 2 and *uncorrectable, success
+// is 1 where blocks were found (0: consistent after all); any other failure ends the call
+int record_status(int rc, bool found, uint8_t* status, bool* uncorrectable)
+{
+    if (rc != FASTECC_OK && rc != FASTECC_E_UNCORRECTABLE) return rc;
+    *status = rc != FASTECC_OK ? 2 : found ? 1 : 0;
+    *uncorrectable = *uncorrectable || rc != FASTECC_OK;
+    return FASTECC_OK;
 }
 
 // fastecc_verify; named = false: over all blocks whatever fastecc_scrub_erasures named (the closing check of fastecc_correct)
@@ -1394,10 +1112,8 @@ int verify_impl(fastecc_ctx* c, const void* data, const void* parity, int mem_ki
     if (!consistent) return FASTECC_E_INVAL;
     int rc = scrub_args(c, data, parity, mem_kind);
     if (rc != FASTECC_OK) return rc;
-    DeviceGuard dg(c->device);
-    if (!dg.ok) return FASTECC_E_DEVICE;
-    CallLock lk(c->mu);
-    return guarded([&]() -> int {
+    return on_device(c, [&]() -> int {
+        CallLock lk(c->mu);
         std::vector<uint32_t> found;
         ScrubState* s = nullptr;
         int r = scrub_state(c, &s);
@@ -1427,17 +1143,13 @@ int correct_stripe(fastecc_ctx* c, void* data, void* parity, void* stream, uint6
     if (found.empty()) return FASTECC_OK;  // consistent: untouched, the absent blocks included
     // the erasure decoder rebuilds the located blocks and, in the same repair, the ones named absent (prepare and repair take the
     // context's lock themselves); the codeword is whole then, so the closing verify reads every block
-    std::vector<uint8_t> dp(c->K, 1), pp(c->Mu, 1);
-    for (uint32_t j : found) (j < c->K ? dp[j] : pp[j - c->K]) = 0;
-    for (uint32_t j : absent) (j < c->K ? dp[j] : pp[j - c->K]) = 0;
-    int r = fastecc_decode_prepare(c, dp.data(), pp.data());
+    absent.insert(absent.end(), found.begin(), found.end());
+    int r = prepare_lost(c, absent);
     if (r != FASTECC_OK) return r;
     r = fastecc_repair(c, data, parity, FASTECC_MEM_DEVICE, stream);
     if (r != FASTECC_OK) return r;
-    uint64_t seed2 = seed ^ 0x5C7B5C7B5C7B5C7Bull;
-    seed2 = splitmix64(seed2);
     int ok = 0;
-    r = verify_impl(c, data, parity, FASTECC_MEM_DEVICE, stream, seed2, &ok, false);
+    r = verify_impl(c, data, parity, FASTECC_MEM_DEVICE, stream, closing_seed(seed), &ok, false);
     if (r != FASTECC_OK) return r;
     return ok ? FASTECC_OK : FASTECC_E_UNCORRECTABLE;
 }
@@ -1448,6 +1160,141 @@ int report(const std::vector<uint32_t>& found, uint64_t* blocks, uint64_t cap, u
     *count = found.size();
     return FASTECC_OK;
 }
+
+// a list the repair launches read, on the device for one call only (the repair runs outside the scrub state's lock)
+struct DeviceList {
+    uint64_t* p = nullptr;
+    ~DeviceList()
+    {
+        if (p) (void)hipFree(p);
+    }
+};
+
+// fastecc_correct_batch (arguments checked): the locked verify and location, then — grouped — one prepare and one list-form repair per distinct lost
+// set and one closing verify for all of them, and fastecc_correct stripe by stripe for whatever that leaves
+struct CorrectBatch {
+    fastecc_ctx* c;
+    void *data, *parity;
+    uint64_t count;
+    void* stream;
+    uint64_t seed;
+    std::vector<uint64_t> list;                    // the inconsistent stripes
+    std::vector<uint8_t> state;                    // grouped: LOC_* per list entry
+    std::vector<std::vector<uint32_t>> found;      // grouped: the located blocks per list entry
+    std::vector<uint32_t> absent;                  // grouped: the blocks named absent when the stripes were located
+    bool grouped = false;
+    std::vector<std::vector<uint32_t>> lost_sets;  // per group: located and absent blocks, sorted
+    std::vector<std::vector<uint64_t>> members;    // per group: its stripes
+    std::vector<uint64_t> order;                   // the groups' stripes back to back: group g at its offset
+    DeviceList dev_order;
+    std::vector<uint8_t> status;
+    bool uncorrectable = false;
+
+    // under the lock: the inconsistent stripes and, where the mode and their number allow grouping, their located blocks
+    int flag_and_locate()
+    {
+        const int mode = c->correct_batch_mode;
+        const uint32_t *d = (const uint32_t*)data, *p = (const uint32_t*)parity;
+        std::vector<uint8_t> flag;
+        CallLock lk(c->mu);
+        int r = verify_batch_locked(c, d, p, count, seed, (hipStream_t)stream, flag);
+        if (r != FASTECC_OK) return r;
+        for (uint64_t b = 0; b < count; b++)
+            if (flag[b]) list.push_back(b);
+        // one stripe has nothing to share; mode 0 groups from two qualifying stripes on
+        const size_t least = mode == 1 ? 1 : 2;
+        if (mode == 2 || list.size() < least) return FASTECC_OK;
+        if ((r = locate_list(c, d, p, list, seed, (hipStream_t)stream, state, found)) != FASTECC_OK) return r;
+        grouped = list.size() - (size_t)std::count(state.begin(), state.end(), (uint8_t)LOC_FALLBACK) >= least;
+        if (grouped) absent = c->scrub->absent;
+        return FASTECC_OK;
+    }
+
+    // the located stripes by their lost set — located blocks and blocks named absent — in the order the first stripe of each set appears
+    void group_by_lost_set()
+    {
+        std::map<std::vector<uint32_t>, size_t> group_of;
+        for (size_t i = 0; i < list.size(); i++) {
+            if (state[i] == LOC_UNCORRECTABLE) {
+                status[list[i]] = 2;
+                uncorrectable = true;
+            }
+            if (state[i] != LOC_FOUND || found[i].empty()) continue;
+            std::vector<uint32_t> lost(found[i]);
+            lost.insert(lost.end(), absent.begin(), absent.end());
+            std::sort(lost.begin(), lost.end());
+            auto it = group_of.find(lost);
+            if (it == group_of.end()) {
+                it = group_of.emplace(lost, lost_sets.size()).first;
+                lost_sets.push_back(lost);
+                members.emplace_back();
+            }
+            members[it->second].push_back(list[i]);
+        }
+        for (const auto& mb : members) order.insert(order.end(), mb.begin(), mb.end());
+    }
+
+    // one fastecc_decode_prepare and one list-form repair per group (both take the lock themselves)
+    int repair_groups()
+    {
+        HIP_TRY(hipMalloc((void**)&dev_order.p, order.size() * 8));
+        HIP_TRY(hipMemcpy(dev_order.p, order.data(), order.size() * 8, hipMemcpyHostToDevice));
+        uint64_t at = 0;
+        for (size_t g = 0; g < members.size(); g++) {
+            int r = prepare_lost(c, lost_sets[g]);
+            if (r != FASTECC_OK) return r;
+            if ((r = repair_list(c, data, parity, order.data() + at, dev_order.p + at, members[g].size(), stream)) != FASTECC_OK) return r;
+            at += members[g].size();
+        }
+        return FASTECC_OK;
+    }
+
+    // the closing verify of fastecc_correct for all repaired stripes at once: its second seed, every block read (the stripes are whole now)
+    int closing_verify()
+    {
+        std::vector<uint8_t> still;
+        {
+            CallLock lk(c->mu);
+            const int r = verify_list_locked(c, (const uint32_t*)data, (const uint32_t*)parity, order, closing_seed(seed), (hipStream_t)stream, false, still);
+            if (r != FASTECC_OK) return r;
+        }
+        for (size_t i = 0; i < order.size(); i++) {
+            status[order[i]] = still[i] ? 2 : 1;
+            uncorrectable = uncorrectable || still[i];
+        }
+        return FASTECC_OK;
+    }
+
+    // fastecc_correct through the stripe's own pointers (it takes the lock itself) on what the grouped path left: every inconsistent stripe, or
+    // the LOC_FALLBACK ones
+    int fallbacks()
+    {
+        const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
+        for (size_t i = 0; i < list.size(); i++) {
+            if (grouped && state[i] != LOC_FALLBACK) continue;
+            const uint64_t b = list[i];
+            uint64_t n_found = 0;
+            int r = fastecc_correct(c, (char*)data + b * data_bytes, (char*)parity + b * parity_bytes, FASTECC_MEM_DEVICE, stream, seed, nullptr, 0, &n_found);
+            if ((r = record_status(r, n_found != 0, &status[b], &uncorrectable)) != FASTECC_OK) return r;
+        }
+        return FASTECC_OK;
+    }
+
+    int run(uint8_t* status_out, uint64_t* inconsistent)
+    {
+        int r = flag_and_locate();
+        if (r != FASTECC_OK) return r;
+        status.assign(count, 0);
+        if (grouped) {
+            group_by_lost_set();
+            if (!order.empty() && ((r = repair_groups()) != FASTECC_OK || (r = closing_verify()) != FASTECC_OK)) return r;
+        }
+        if ((r = fallbacks()) != FASTECC_OK) return r;
+        std::copy(status.begin(), status.end(), status_out);
+        *inconsistent = list.size();
+        return uncorrectable ? FASTECC_E_UNCORRECTABLE : FASTECC_OK;
+    }
+};
 
 }  // namespace
 
@@ -1475,10 +1322,8 @@ int fastecc_scrub_fingerprints(fastecc_ctx* c, const void* data, const void* par
     if (!out || !big || form < 0 || form > 2 || (form == 0 && count != 1) || (form == 2) != (list != nullptr)) return FASTECC_E_INVAL;
     const int rc = batch_args(c, data, parity, count);
     if (rc != FASTECC_OK) return rc;
-    DeviceGuard dg(c->device);
-    if (!dg.ok) return FASTECC_E_DEVICE;
-    CallLock lk(c->mu);
-    return guarded([&]() -> int {
+    return on_device(c, [&]() -> int {
+        CallLock lk(c->mu);
         hipStream_t st = (hipStream_t)stream;
         const uint32_t *d = (const uint32_t*)data, *p = (const uint32_t*)parity;
         ScrubState* s = nullptr;
@@ -1539,10 +1384,8 @@ int fastecc_locate_errors(fastecc_ctx* c, const void* data, const void* parity, 
     if (!count || (!blocks && cap)) return FASTECC_E_INVAL;
     int rc = scrub_args(c, data, parity, mem_kind);
     if (rc != FASTECC_OK) return rc;
-    DeviceGuard dg(c->device);
-    if (!dg.ok) return FASTECC_E_DEVICE;
-    CallLock lk(c->mu);
-    return guarded([&]() -> int {
+    return on_device(c, [&]() -> int {
+        CallLock lk(c->mu);
         std::vector<uint32_t> found;
         ScrubState* s = nullptr;
         int r = scrub_state(c, &s);
@@ -1557,9 +1400,7 @@ int fastecc_correct(fastecc_ctx* c, void* data, void* parity, int mem_kind, void
     if (!count || (!blocks && cap)) return FASTECC_E_INVAL;
     int rc = scrub_args(c, data, parity, mem_kind);
     if (rc != FASTECC_OK) return rc;
-    DeviceGuard dg(c->device);
-    if (!dg.ok) return FASTECC_E_DEVICE;
-    return guarded([&]() -> int {
+    return on_device(c, [&]() -> int {
         std::vector<uint32_t> found;
         const int r = correct_stripe(c, data, parity, stream, seed, false, 0, found);
         return r == FASTECC_OK ? report(found, blocks, cap, count) : r;
@@ -1572,20 +1413,12 @@ int fastecc_verify_batch(fastecc_ctx* c, const void* data, const void* parity, u
     if (!consistent || !inconsistent) return FASTECC_E_INVAL;
     const int rc = batch_args(c, data, parity, count);
     if (rc != FASTECC_OK) return rc;
-    DeviceGuard dg(c->device);
-    if (!dg.ok) return FASTECC_E_DEVICE;
-    CallLock lk(c->mu);
-    return guarded([&]() -> int {
+    return on_device(c, [&]() -> int {
+        CallLock lk(c->mu);
         std::vector<uint8_t> flag;
         const int r = verify_batch_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, seed, (hipStream_t)stream, flag);
-        if (r != FASTECC_OK) return r;
-        uint64_t bad = 0;
-        for (uint64_t b = 0; b < count; b++) {
-            consistent[b] = flag[b] ? 0 : 1;
-            bad += flag[b] ? 1 : 0;
-        }
-        *inconsistent = bad;
-        return FASTECC_OK;
+        if (r == FASTECC_OK) report_flags(flag, consistent, inconsistent);
+        return r;
     });
 }
 
@@ -1596,12 +1429,11 @@ int fastecc_locate_errors_batch(fastecc_ctx* c, const void* data, const void* pa
     const int rc = batch_args(c, data, parity, count);
     if (rc != FASTECC_OK) return rc;
     if (cap && count > UINT64_MAX / 8 / cap) return FASTECC_E_INVAL;
-    DeviceGuard dg(c->device);
-    if (!dg.ok) return FASTECC_E_DEVICE;
-    CallLock lk(c->mu);
-    return guarded([&]() -> int {
+    return on_device(c, [&]() -> int {
+        CallLock lk(c->mu);
         hipStream_t st = (hipStream_t)stream;
         std::vector<uint8_t> flag, state;
+        bool uncorrectable = false;
         int r = verify_batch_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, seed, st, flag);
         if (r != FASTECC_OK) return r;
         std::vector<uint64_t> list;
@@ -1615,12 +1447,9 @@ int fastecc_locate_errors_batch(fastecc_ctx* c, const void* data, const void* pa
             // a word >= p in a present block, or more syndromes than the batched pass gathers: the single-stripe code through the stripe's own pointers
             r = locate(c, c->scrub, erasures(c->scrub, true), (const uint32_t*)data + list[i] * data_words, (const uint32_t*)parity + list[i] * parity_words, seed, st,
                        found[i], false);
-            if (r == FASTECC_E_UNCORRECTABLE) state[i] = LOC_UNCORRECTABLE;
-            else if (r != FASTECC_OK) return r;
-            else state[i] = LOC_FOUND;
+            if ((r = record_status(r, !found[i].empty(), &state[i], &uncorrectable)) != FASTECC_OK) return r;  // (the status codes 1 and 2 are LOC_FOUND and LOC_UNCORRECTABLE)
         }
         // every output is written only now: a failed call leaves them alone
-        bool uncorrectable = false;
         uint64_t bad = 0;
         std::fill(status, status + count, (uint8_t)0);
         if (counts) std::fill(counts, counts + count, 0u);
@@ -1648,121 +1477,9 @@ int fastecc_correct_batch(fastecc_ctx* c, void* data, void* parity, uint64_t cou
     if (!status || !inconsistent) return FASTECC_E_INVAL;
     const int rc = batch_args(c, data, parity, count);
     if (rc != FASTECC_OK) return rc;
-    DeviceGuard dg(c->device);
-    if (!dg.ok) return FASTECC_E_DEVICE;
-    return guarded([&]() -> int {
-        hipStream_t hst = (hipStream_t)stream;
-        const int mode = c->correct_batch_mode;
-        std::vector<uint8_t> flag, state;
-        std::vector<uint64_t> list;
-        std::vector<std::vector<uint32_t>> found;
-        std::vector<uint32_t> absent;
-        bool grouped = false;
-        {
-            CallLock lk(c->mu);
-            int r = verify_batch_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, seed, hst, flag);
-            if (r != FASTECC_OK) return r;
-            for (uint64_t b = 0; b < count; b++)
-                if (flag[b]) list.push_back(b);
-            // one stripe has nothing to share; mode 0 groups from two qualifying stripes on
-            if (mode != 2 && list.size() >= (mode == 1 ? 1u : 2u)) {
-                if ((r = locate_list(c, (const uint32_t*)data, (const uint32_t*)parity, list, seed, hst, state, found)) != FASTECC_OK) return r;
-                const uint64_t qualify = (uint64_t)(list.size() - std::count(state.begin(), state.end(), (uint8_t)LOC_FALLBACK));
-                grouped = qualify >= (mode == 1 ? 1u : 2u);
-                if (grouped) absent = c->scrub->absent;
-            }
-        }
-        const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
-        std::vector<uint8_t> st(count, 0);
-        bool uncorrectable = false;
-        // fastecc_correct on one inconsistent stripe through its own pointers (it takes the lock itself)
-        auto correct_one = [&](uint64_t b) -> int {
-            uint64_t n_found = 0;
-            const int r = fastecc_correct(c, (char*)data + b * data_bytes, (char*)parity + b * parity_bytes, FASTECC_MEM_DEVICE, stream, seed, nullptr, 0, &n_found);
-            if (r == FASTECC_E_UNCORRECTABLE) {
-                st[b] = 2;
-                uncorrectable = true;
-            } else if (r != FASTECC_OK) {
-                return r;
-            } else {
-                st[b] = n_found ? 1 : 0;
-            }
-            return FASTECC_OK;
-        };
-        if (!grouped) {
-            for (uint64_t b : list) {
-                const int r = correct_one(b);
-                if (r != FASTECC_OK) return r;
-            }
-        } else {
-            // the located stripes by their lost set — located blocks and blocks named absent — in the order the first stripe of each set appears
-            std::map<std::vector<uint32_t>, size_t> group_of;
-            std::vector<std::vector<uint32_t>> lost_sets;
-            std::vector<std::vector<uint64_t>> members;
-            uint64_t repaired = 0;
-            for (size_t i = 0; i < list.size(); i++) {
-                if (state[i] == LOC_UNCORRECTABLE) {
-                    st[list[i]] = 2;
-                    uncorrectable = true;
-                }
-                if (state[i] != LOC_FOUND || found[i].empty()) continue;
-                std::vector<uint32_t> lost(found[i]);
-                lost.insert(lost.end(), absent.begin(), absent.end());
-                std::sort(lost.begin(), lost.end());
-                auto it = group_of.find(lost);
-                if (it == group_of.end()) {
-                    it = group_of.emplace(lost, lost_sets.size()).first;
-                    lost_sets.push_back(lost);
-                    members.emplace_back();
-                }
-                members[it->second].push_back(list[i]);
-                repaired++;
-            }
-            if (repaired) {
-                std::vector<uint64_t> order;  // the groups' stripes back to back: group g at its offset
-                for (const auto& mb : members) order.insert(order.end(), mb.begin(), mb.end());
-                // the lists the repair launches read live on the device for this call only (the repair runs outside the scrub state's lock)
-                struct DeviceList {
-                    uint64_t* p = nullptr;
-                    ~DeviceList()
-                    {
-                        if (p) (void)hipFree(p);
-                    }
-                } dl;
-                HIP_TRY(hipMalloc((void**)&dl.p, order.size() * 8));
-                HIP_TRY(hipMemcpy(dl.p, order.data(), order.size() * 8, hipMemcpyHostToDevice));
-                uint64_t at = 0;
-                for (size_t g = 0; g < members.size(); g++) {
-                    std::vector<uint8_t> dp(c->K, 1), pp(c->Mu, 1);
-                    for (uint32_t j : lost_sets[g]) (j < c->K ? dp[j] : pp[j - c->K]) = 0;
-                    int r = fastecc_decode_prepare(c, dp.data(), pp.data());
-                    if (r != FASTECC_OK) return r;
-                    if ((r = repair_list(c, data, parity, order.data() + at, dl.p + at, members[g].size(), stream)) != FASTECC_OK) return r;
-                    at += members[g].size();
-                }
-                // the closing verify of fastecc_correct for all of them at once: its second seed, every block read (the stripes are whole now)
-                uint64_t seed2 = seed ^ 0x5C7B5C7B5C7B5C7Bull;
-                seed2 = splitmix64(seed2);
-                std::vector<uint8_t> still;
-                {
-                    CallLock lk(c->mu);
-                    const int r = verify_list_locked(c, (const uint32_t*)data, (const uint32_t*)parity, order, seed2, hst, false, still);
-                    if (r != FASTECC_OK) return r;
-                }
-                for (size_t i = 0; i < order.size(); i++) {
-                    st[order[i]] = still[i] ? 2 : 1;
-                    uncorrectable = uncorrectable || still[i];
-                }
-            }
-            for (size_t i = 0; i < list.size(); i++) {
-                if (state[i] != LOC_FALLBACK) continue;
-                const int r = correct_one(list[i]);
-                if (r != FASTECC_OK) return r;
-            }
-        }
-        std::copy(st.begin(), st.end(), status);
-        *inconsistent = list.size();
-        return uncorrectable ? FASTECC_E_UNCORRECTABLE : FASTECC_OK;
+    return on_device(c, [&]() -> int {
+        CorrectBatch cb{c, data, parity, count, stream, seed};
+        return cb.run(status, inconsistent);
     });
 }
 
@@ -1792,21 +1509,13 @@ int fastecc_verify_batch_set(fastecc_ctx* c, const void* data, const void* parit
     if (!consistent || !inconsistent || !pattern_of) return FASTECC_E_INVAL;
     int rc = batch_args(c, data, parity, count);
     if (rc != FASTECC_OK) return rc;
-    DeviceGuard dg(c->device);
-    if (!dg.ok) return FASTECC_E_DEVICE;
-    CallLock lk(c->mu);
-    if ((rc = set_args(c, pattern_of, count)) != FASTECC_OK) return rc;
-    return guarded([&]() -> int {
+    return on_device(c, [&]() -> int {
+        CallLock lk(c->mu);
+        if ((rc = set_args(c, pattern_of, count)) != FASTECC_OK) return rc;
         std::vector<uint8_t> flag;
         const int r = verify_batch_set_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, pattern_of, seed, (hipStream_t)stream, flag);
-        if (r != FASTECC_OK) return r;
-        uint64_t bad = 0;
-        for (uint64_t b = 0; b < count; b++) {
-            consistent[b] = flag[b] ? 0 : 1;
-            bad += flag[b] ? 1 : 0;
-        }
-        *inconsistent = bad;
-        return FASTECC_OK;
+        if (r == FASTECC_OK) report_flags(flag, consistent, inconsistent);
+        return r;
     });
 }
 
@@ -1816,9 +1525,7 @@ int fastecc_correct_batch_set(fastecc_ctx* c, void* data, void* parity, uint64_t
     if (!status || !inconsistent || !pattern_of) return FASTECC_E_INVAL;
     int rc = batch_args(c, data, parity, count);
     if (rc != FASTECC_OK) return rc;
-    DeviceGuard dg(c->device);
-    if (!dg.ok) return FASTECC_E_DEVICE;
-    return guarded([&]() -> int {
+    return on_device(c, [&]() -> int {
         std::vector<uint8_t> flag;
         {
             CallLock lk(c->mu);
@@ -1835,15 +1542,8 @@ int fastecc_correct_batch_set(fastecc_ctx* c, void* data, void* parity, uint64_t
         for (uint64_t b = 0; b < count; b++) {
             if (!flag[b]) continue;
             bad++;
-            const int r = correct_stripe(c, (char*)data + b * data_bytes, (char*)parity + b * parity_bytes, stream, seed, true, pattern_of[b], found);
-            if (r == FASTECC_E_UNCORRECTABLE) {
-                st[b] = 2;
-                uncorrectable = true;
-            } else if (r != FASTECC_OK) {
-                return r;
-            } else {
-                st[b] = found.empty() ? 0 : 1;
-            }
+            int r = correct_stripe(c, (char*)data + b * data_bytes, (char*)parity + b * parity_bytes, stream, seed, true, pattern_of[b], found);
+            if ((r = record_status(r, !found.empty(), &st[b], &uncorrectable)) != FASTECC_OK) return r;
         }
         std::copy(st.begin(), st.end(), status);
         *inconsistent = bad;
