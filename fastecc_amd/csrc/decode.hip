@@ -42,6 +42,7 @@
 #include <new>
 #include <vector>
 
+#include "devmem.hpp"
 #include "gf.hpp"
 #include "gf61_path.hpp"
 #include "internal.hpp"
@@ -49,130 +50,104 @@
 
 namespace fastecc {
 
+// The direct path's tables of one erasure pattern (Prepare::direct_tables): which passes it takes and their weights
+struct PatternTables {
+    DirectPassPtr data;    // the lost data blocks (only data lost, or more than 32 blocks lost in all)
+    DirectPassPtr parity;  // the lost parity blocks from the complete data (only parity lost, or more than 32 in all)
+    DirectPassPtr both;    // data AND parity lost, at most 32 in all: the single pass
+    bool both_built = false;       // `both` holds this pattern
+    bool only_both = false;        // ... and is its only pass
+    int ed = 0, ep = 0;    // lost data / parity blocks
+    bool host_nomem = false;       // direct_tables' FASTECC_E_NOMEM is the host's (no DirectPass object), not the device's (no room for a table)
+};
+
 struct DecodeState {
-    fastecc_ctx* transform = nullptr;  // size-2k transform context, fold 1
-    fastecc_ctx* pattern_ntt = nullptr;  // same length, 2 words per block: l and l' are evaluated on the device
-    uint32_t* pattern_buf = nullptr;     // its stripe
-    uint32_t* fin = nullptr;           // 2k factors by codeword position: l(w^u) (Montgomery) or 0 if erased
-    uint32_t* fin_first_pass = nullptr;  // the same in the order the transform's first pass reads them (may equal fin)
-    uint32_t* srcmap = nullptr;        // per codeword position: the block that sits there (row, bit 31 = parity stripe)
-    uint32_t* gout = nullptr;          // k factors by data block: 1 / (w^2i l'(w^2i)) (Montgomery) if erased, else 0
+    CtxPtr transform;                       // size-2k transform context, fold 1
+    CtxPtr pattern_ntt;                     // same length, 2 words per block: l and l' are evaluated on the device
+    DeviceBuf<uint32_t> pattern_buf;        // its stripe
+    DeviceBuf<uint32_t> fin;                // 2k factors by codeword position: l(w^u) (Montgomery) or 0 if erased
+    uint32_t* fin_first_pass = nullptr;     // the same in the order the transform's first pass reads them: a view of fin, or of fin_tiled
+    DeviceBuf<uint32_t> fin_tiled;          // ... where that order is not the order of the positions (permuted from fin for every pattern)
+    DeviceBuf<uint32_t> srcmap;             // per codeword position: the block that sits there (row, bit 31 = parity stripe)
+    DeviceBuf<uint32_t> gout;               // k factors by data block: 1 / (w^2i l'(w^2i)) (Montgomery) if erased, else 0
     // fastecc_repair of the (2k,k) layout in ONE transform: the same x p'(x) evaluated at ALL 2k positions (fold 0) gives the lost parity
     // blocks as well, f(w^u) = (x p')(w^u) / (w^u l'(w^u)) at odd u — instead of decoding the data and encoding it once more
-    fastecc_ctx* transform_full = nullptr;
-    uint32_t* gout_par = nullptr;       // k factors by parity block: 1 / (w^(2q+1) l'(w^(2q+1))) (Montgomery) if erased, else 0
-    uint32_t* recovered_full = nullptr; // 2k blocks: x p'(x) at every position (lazy: 4 GiB at the headline size)
-    bool full_ok = false;               // transform_full's first pass reads the factors in the same order as transform's
-    uint32_t* recovered = nullptr;     // k blocks: x p'(x) at the data positions
+    CtxPtr transform_full;
+    DeviceBuf<uint32_t> gout_par;           // k factors by parity block: 1 / (w^(2q+1) l'(w^(2q+1))) (Montgomery) if erased, else 0
+    DeviceBuf<uint32_t> recovered_full;     // 2k blocks: x p'(x) at every position (lazy: 4 GiB at the headline size)
+    bool full_ok = false;                   // transform_full's first pass reads the factors in the same order as transform's
+    DeviceBuf<uint32_t> recovered;          // k blocks: x p'(x) at the data positions
     // (2k,k) layout, the transform as two half-size ones ("even / odd split" below)
-    fastecc_ctx* split = nullptr;           // k blocks, per-block factor (2m + k) / 2k
-    uint32_t* split_order = nullptr;        // k words: the block each slot of its first pass holds (gather_tile_order)
-    uint32_t* split_rows_data = nullptr;    // k words, that order: l(w^2i) of the surviving data blocks (0: lost)
-    uint32_t* split_rows_parity = nullptr;  // k words, that order: l(w^(2i+1)) of the parity blocks in use (0: lost or unused)
-    uint32_t* split_rows_out = nullptr;     // k words, that order: gout of the block (0: not lost)
-    uint32_t* split_pos_parity = nullptr;   // k words by position: -w^(-m) / 2 at position bitrev(m)
-    uint32_t* split_impulse = nullptr;      // [IMPULSE_MAX][16][64]: what six DIF levels make of a lone block of a 1024-block tile (run_split_decode)
-    uint32_t* split_r1 = nullptr;           // k blocks: the parity half after its first pass (zero outside the groups in use)
-    uint32_t* split_r2 = nullptr;           // k blocks: ... after all DIF levels
-    uint32_t* split_q2 = nullptr;           // fastecc_repair: k blocks, the data chain's MID output while the top-level result serves the parity chain (lazy)
-    uint32_t* split_pos_data_odd = nullptr;   // k words by position: -w^m / 2 at position bitrev(m) (the parity chain's factor of the data half)
-    uint32_t* split_rows_out_parity = nullptr;  // k words, first-pass order: gout_par of the block (0: not lost)
+    CtxPtr split;                           // k blocks, per-block factor (2m + k) / 2k
+    DeviceBuf<uint32_t> split_order;        // k words: the block each slot of its first pass holds (gather_tile_order)
+    DeviceBuf<uint32_t> split_rows_data;    // k words, that order: l(w^2i) of the surviving data blocks (0: lost)
+    DeviceBuf<uint32_t> split_rows_parity;  // k words, that order: l(w^(2i+1)) of the parity blocks in use (0: lost or unused)
+    DeviceBuf<uint32_t> split_rows_out;     // k words, that order: gout of the block (0: not lost)
+    DeviceBuf<uint32_t> split_pos_parity;   // k words by position: -w^(-m) / 2 at position bitrev(m)
+    DeviceBuf<uint32_t> split_impulse;      // [IMPULSE_MAX][16][64]: what six DIF levels make of a lone block of a 1024-block tile (run_split_decode)
+    DeviceBuf<uint32_t> split_r1;           // k blocks: the parity half after its first pass (zero outside the groups in use)
+    DeviceBuf<uint32_t> split_r2;           // k blocks: ... after all DIF levels
+    DeviceBuf<uint32_t> split_q2;           // fastecc_repair: k blocks, the data chain's MID output while the top-level result serves the parity chain (lazy)
+    DeviceBuf<uint32_t> split_pos_data_odd; // k words by position: -w^m / 2 at position bitrev(m) (the parity chain's factor of the data half)
+    DeviceBuf<uint32_t> split_rows_out_parity;  // k words, first-pass order: gout_par of the block (0: not lost)
     bool split_repair_ready = false;        // this pattern's lost parity blocks can come from the split transform too
-    uint32_t* split_r0 = nullptr;           // codes with fewer parity blocks (fold > 0): parity block j copied to its place j << fold of a k-block stripe (lazy)
+    DeviceBuf<uint32_t> split_r0;           // codes with fewer parity blocks (fold > 0): parity block j copied to its place j << fold of a k-block stripe (lazy)
     uint32_t split_groups = 0;              // block groups of the parity stripe this pattern reads
     // "small" form of the parity half: the parity blocks in use are those at multiples of 2^split_shift of the parity half (1 <= shift <= 5), so r~
     // is the transform of (k >> shift) rows, each result block standing for 2^shift positions: no k-block stripes r1 / r2, no impulse pass
     uint32_t split_shift = 0;
-    fastecc_ctx* split_small[6] = {};       // stand-alone transform contexts of k >> shift blocks (lazy, by shift)
-    uint32_t* split_small_buf = nullptr;    // (k >> shift) blocks: those rows times l, then transformed in place
-    uint64_t split_small_blocks = 0;
+    CtxPtr split_small[6];                  // stand-alone transform contexts of k >> shift blocks (lazy, by shift)
+    DeviceBuf<uint32_t> split_small_buf;    // (k >> shift) blocks: those rows times l, then transformed in place
     uint32_t split_dirty = 0;               // groups of split_r1 that may hold non-zero rows
     bool split_ready = false;               // this pattern decodes through the split transform
     bool split_unavailable = false;         // it could not be built on this context (plan shape, memory): the 2k-point transform serves
-    uint32_t* parity_dev = nullptr;    // staging for FASTECC_MEM_HOST calls (lazy)
+    DeviceBuf<uint32_t> parity_dev;         // staging for FASTECC_MEM_HOST calls (lazy)
     // FASTECC_MEM_HOST: only the rebuilt blocks travel back — their row numbers (host, and a device copy), valid for pattern `host_lists_of`
     std::vector<uint32_t> host_lost_data, host_lost_parity;
-    std::vector<uint32_t> host_parity_used;  // few losses: the parity blocks the direct path reads (all it needs staged of a host parity stripe)
+    std::vector<uint32_t> host_parity_used; // few losses: the parity blocks the direct path reads (all it needs staged of a host parity stripe)
     uint64_t pattern_serial = 0, host_lists_of = ~0ull;
-    uint32_t* lost_rows_dev = nullptr;  // the two lists back to back
-    uint64_t lost_rows_cap = 0;
-    uint32_t* pack_dev = nullptr;       // the rebuilt blocks, packed
-    uint64_t pack_words = 0;
-    uint32_t* pack_host = nullptr;      // pinned landing buffer of that copy (kept between calls; the blocks go to their places from here)
-    uint64_t pack_host_words = 0;
+    DeviceBuf<uint32_t> lost_rows_dev;      // the two lists back to back
+    DeviceBuf<uint32_t> pack_dev;           // the rebuilt blocks, packed
+    PinnedBuf<uint32_t> pack_host;          // pinned landing buffer of that copy (kept between calls; the blocks go to their places from here)
     // fastecc_decode_prepare's device state (lazy): the product tree of the locator
-    uint64_t tree_T = 0;                   // padded number of roots: the smallest power of two >= the most losses a code tolerates
-    std::vector<fastecc_ctx*> tree_ctx;    // level k (polynomials of degree d = 2^k): transforms of length 2d, T/d columns
-    fastecc_ctx* tree_top = nullptr;       // few-column levels (chunk_transform_kernel): the upper row bits, 2T / CHUNK rows of CHUNK words
-    bool pattern_narrow = false;           // pattern_ntt is such a context too (2 NC / CHUNK rows)
-    uint32_t* tree_x = nullptr;            // 2T words: the level's polynomials, [coefficient][polynomial]
-    uint32_t* tree_f = nullptr;            // 2T words: their transforms
-    uint32_t* tree_y = nullptr;            // 2T words: the next level's polynomials (swaps roles with tree_x)
-    uint32_t* tree_p = nullptr;            // 2T words: pairwise products
-    uint32_t* wpow = nullptr;              // NC words: w^u (plain)
-    uint32_t* roots = nullptr;             // T words: the erased points, zero-padded
-    uint32_t* dev_state = nullptr;         // NC bytes (as words/4): LOST / HELD / ZERO per position
-    uint32_t* dev_erased = nullptr;        // T words: erased positions
-    uint8_t* dev_present = nullptr;        // (2k,k) layout: the caller's two presence arrays, k bytes each (the pattern is scanned on the device)
-    uint32_t* dev_counts = nullptr;        // ... and what presence_counts_kernel counts in them (8 words)
-    int tree_low = 0;                      // levels below this one are done by tree_low_levels_kernel (0: the per-thread leaves of degree 2^LEAF_LOG)
-    uint32_t* tile_order = nullptr;        // NC words: first-pass order of the factors (only for the (2k,k) layout)
+    uint64_t tree_T = 0;                    // padded number of roots: the smallest power of two >= the most losses a code tolerates
+    std::vector<CtxPtr> tree_ctx;           // level k (polynomials of degree d = 2^k): transforms of length 2d, T/d columns
+    CtxPtr tree_top;                        // few-column levels (chunk_transform_kernel): the upper row bits, 2T / CHUNK rows of CHUNK words
+    bool pattern_narrow = false;            // pattern_ntt is such a context too (2 NC / CHUNK rows)
+    DeviceBuf<uint32_t> tree_x;             // 2T words: the level's polynomials, [coefficient][polynomial]
+    DeviceBuf<uint32_t> tree_f;             // 2T words: their transforms
+    DeviceBuf<uint32_t> tree_y;             // 2T words: the next level's polynomials (swaps roles with tree_x)
+    DeviceBuf<uint32_t> tree_p;             // 2T words: pairwise products
+    DeviceBuf<uint32_t> wpow;               // NC words: w^u (plain)
+    DeviceBuf<uint32_t> roots;              // T words: the erased points, zero-padded
+    DeviceBuf<uint8_t> dev_state;           // NC bytes: LOST / HELD / ZERO per position
+    DeviceBuf<uint32_t> dev_erased;         // T words: erased positions
+    DeviceBuf<uint8_t> dev_present;         // (2k,k) layout: the caller's two presence arrays, k bytes each (the pattern is scanned on the device)
+    DeviceBuf<uint32_t> dev_counts;         // ... and what presence_counts_kernel counts in them (8 words)
+    int tree_low = 0;                       // levels below this one are done by tree_low_levels_kernel (0: the per-thread leaves of degree 2^LEAF_LOG)
+    DeviceBuf<uint32_t> tile_order;         // NC words: first-pass order of the factors (only for the (2k,k) layout)
     bool tile_order_valid = false;
     // fastecc_repair: which parity blocks are lost (one word each), and the stripe the re-encode writes to
-    uint32_t* parity_lost = nullptr;
-    uint32_t* parity_again = nullptr;
+    DeviceBuf<uint32_t> parity_lost;
+    DeviceBuf<uint32_t> parity_again;
     uint64_t erased_parity = 0;
     uint64_t erased_data = 0, erased_total = 0;
     // few losses (any layout: the reference's, zero extension, sub-/extra cosets, mixed radix): every lost data block is a fixed linear
     // combination of the surviving data blocks and as many surviving parity blocks (interpolation on N nodes); for repair the lost parity
     // blocks follow from the complete data (direct.hip)
-    DirectPass* direct_data = nullptr;
-    DirectPass* direct_parity = nullptr;
-    DirectPass* direct_both = nullptr;   // data AND parity lost: fastecc_repair's single pass (the lost parity blocks as further outputs on direct_data's nodes)
-    bool sub_both = false;               // ... is built for this pattern
-    bool sub_only_both = false;          // ... and is the only pass (few outputs: the pass is bound by the read of the survivors, fastecc_decode runs it too and drops the parity outputs)
+    PatternTables direct;                   // the passes of the current pattern: built over from pattern to pattern
+    bool sub_both = false;                  // direct.both (data AND parity lost: fastecc_repair's single pass) is built for this pattern
+    bool sub_only_both = false;             // ... and is the only pass (few outputs: the pass is bound by the read of the survivors, fastecc_decode runs it too and drops the parity outputs)
     int sub_lost_data = 0, sub_lost_parity = 0;
     bool sub = false;
-    int direct_kernel = 0;             // 0 choose, 1 VALU, 2 MFMA (option "direct_kernel")
-    uint64_t positions = 0;            // code length on the roots of unity: k << log2(n / k) rounded up to powers of two
-    bool mixed = false;                // mixed-radix code: `recovered` is the whole work stripe (all positions), transformed in place
-    bool standard = false;             // the reference's (2k,k) layout: position u = data u/2 or parity u/2, every block in memory
+    int direct_kernel = 0;                  // 0 choose, 1 VALU, 2 MFMA (option "direct_kernel")
+    uint64_t positions = 0;                 // code length on the roots of unity: k << log2(n / k) rounded up to powers of two
+    bool mixed = false;                     // mixed-radix code: `recovered` is the whole work stripe (all positions), transformed in place
+    bool standard = false;                  // the reference's (2k,k) layout: position u = data u/2 or parity u/2, every block in memory
     bool ready = false;
 };
 
-void destroy_decode_state(DecodeState* d)
-{
-    if (!d) return;
-    for (fastecc_ctx* x : {d->transform, d->transform_full, d->split, d->pattern_ntt, d->tree_top})
-        if (x) fastecc_destroy(x);
-    for (fastecc_ctx* x : d->split_small)
-        if (x) fastecc_destroy(x);
-    for (fastecc_ctx* x : d->tree_ctx)
-        if (x) fastecc_destroy(x);
-    if (d->fin_first_pass && d->fin_first_pass != d->fin) (void)hipFree(d->fin_first_pass);
-    for (void* b : std::initializer_list<void*>{d->split_small_buf, d->split_order, d->split_rows_data, d->split_rows_parity, d->split_rows_out, d->split_pos_parity,
-                                                d->split_impulse, d->split_r1, d->split_r2, d->split_r0, d->split_q2, d->split_pos_data_odd, d->split_rows_out_parity,
-                                                d->gout_par, d->dev_present, d->dev_counts, d->recovered_full, d->pattern_buf, d->fin, d->srcmap, d->gout, d->recovered,
-                                                d->parity_dev, d->lost_rows_dev, d->pack_dev, d->parity_lost, d->parity_again, d->tree_x, d->tree_f, d->tree_y, d->tree_p,
-                                                d->wpow, d->roots, d->dev_state, d->dev_erased, d->tile_order})
-        if (b) (void)hipFree(b);
-    if (d->pack_host) (void)hipHostFree(d->pack_host);
-    direct_pass_free(d->direct_data);
-    direct_pass_free(d->direct_parity);
-    direct_pass_free(d->direct_both);
-    delete d;
-}
-
-// The direct path's tables of one erasure pattern (Prepare::direct_tables): which passes it takes and their weights
-struct PatternTables {
-    DirectPass* data = nullptr;    // the lost data blocks (only data lost, or more than 32 blocks lost in all)
-    DirectPass* parity = nullptr;  // the lost parity blocks from the complete data (only parity lost, or more than 32 in all)
-    DirectPass* both = nullptr;    // data AND parity lost, at most 32 in all: the single pass
-    bool both_built = false;       // `both` holds this pattern
-    bool only_both = false;        // ... and is its only pass
-    int ed = 0, ep = 0;            // lost data / parity blocks
-    bool host_nomem = false;       // direct_tables' FASTECC_E_NOMEM is the host's (no DirectPass object), not the device's (no room for a table)
-};
+void destroy_decode_state(DecodeState* d) { delete d; }
 
 // A pattern set (fastecc_decode_prepare_set): P patterns of at most 16 lost blocks, each exactly one direct pass, for pools in which the pattern
 // differs from stripe to stripe (fastecc_decode_batch_set / _repair_batch_set).  Independent of the DecodeState's single pattern.
@@ -182,28 +157,13 @@ struct PatternSet {
     std::vector<uint8_t> kind;          // ... its pass
     std::vector<uint8_t> cls;           // ... log2 of that pass's pad (1, 2, 4, 8, 16): the class a launch is templated on
     std::vector<uint32_t> rows;         // ... the rows it reads
-    DirectSetPass* d_passes = nullptr;  // device: the descriptor table, entry q = pattern q's pass
-    // one call's entries, sorted by class: written into the pinned h_list and copied to d_list on the call's stream.  d_list is an internal buffer
-    // (ordered between streams by the context's buf_event); h_list is free again once list_event (the end of that copy) has passed.
-    DirectSetEntry* h_list = nullptr;
-    DirectSetEntry* d_list = nullptr;
-    size_t list_cap = 0;  // entries of each
-    hipEvent_t list_event = nullptr;
-    bool list_pending = false;
-    DirectPass* pass(uint64_t q) const { return kind[q] == DATA ? tables[q].data : kind[q] == PARITY ? tables[q].parity : tables[q].both; }
+    DeviceBuf<DirectSetPass> d_passes;  // device: the descriptor table, entry q = pattern q's pass
+    // one call's entries, sorted by class (list.dev is an internal buffer: ordered between streams by the context's buf_event).  Outlives the set.
+    StagedList<DirectSetEntry> list;
+    DirectPass* pass(uint64_t q) const { return kind[q] == DATA ? tables[q].data.get() : kind[q] == PARITY ? tables[q].parity.get() : tables[q].both.get(); }
 };
 
-void destroy_pattern_set(PatternSet* s)
-{
-    if (!s) return;
-    for (PatternTables& t : s->tables)
-        for (DirectPass* p : {t.data, t.parity, t.both}) direct_pass_free(p);
-    if (s->d_passes) (void)hipFree(s->d_passes);
-    if (s->h_list) (void)hipHostFree(s->h_list);
-    if (s->d_list) (void)hipFree(s->d_list);
-    if (s->list_event) (void)hipEventDestroy(s->list_event);
-    delete s;
-}
+void destroy_pattern_set(PatternSet* s) { delete s; }
 
 namespace {
 
@@ -707,7 +667,7 @@ dim3 grid_of(uint64_t items) { return dim3((unsigned)((items + 255) / 256)); }  
 // The row kernels above over `rows` rows of S words: one wave per (row, column chunk of 64 V words), V = 4 when S is a multiple of 4 and every
 // pointer in `ptrs` is 16-byte aligned, else 1.  `args` are the kernel's arguments but the last two (chunks per row, waves in all).
 template <class... K, class... A>
-void launch_rows(void (*k4)(K...), void (*k1)(K...), uint64_t rows, uint32_t S, std::initializer_list<const void*> ptrs, hipStream_t st, A... args)
+void launch_rows(void (*k4)(K...), void (*k1)(K...), uint64_t rows, uint32_t S, std::initializer_list<const void*> ptrs, hipStream_t st, const A&... args)
 {
     uintptr_t bits = 0;
     for (const void* p : ptrs) bits |= (uintptr_t)p;
@@ -890,6 +850,12 @@ struct Prepare {
     {
         const int ed = (int)R.size(), ep = (int)Pl.size();
         int rc = FASTECC_OK;
+        auto have = [&](DirectPassPtr& p) {  // a pass object where t holds none yet
+            if (!p) p.reset(direct_pass_new());
+            t.host_nomem = !p;
+            return !t.host_nomem;
+        };
+        t.host_nomem = false;
         t.ed = ed;
         t.ep = ep;
         const uint32_t K = (uint32_t)ci.user_k;
@@ -900,7 +866,7 @@ struct Prepare {
         // (up to 32 outputs a pass costs the read of the survivors whatever it computes, profiles/r03/direct_bench.jsonl: one table then serves decode and repair)
         t.only_both = ed > 0 && ep > 0 && ed + ep <= 32;
         if (ed > 0 && !t.only_both) {
-            if (!t.data && !(t.data = direct_pass_new())) return t.host_nomem = true, FASTECC_E_NOMEM;
+            if (!have(t.data)) return FASTECC_E_NOMEM;
             rc = direct_build_interp(t.data, wd, N, K, R, xr, A, ya, nullptr);
         }
         ptd.mark("few losses: data table");
@@ -918,11 +884,11 @@ struct Prepare {
                 // pass's nodes (the surviving data and as many parity blocks), not a second pass over the repaired data.  (Above 32 outputs the
                 // matrix cores bound the pass, not the read: 128 + 128 lost take 2.40 ms in one pass, 2.48 in two, and the set-up of the second
                 // 256-output table costs 0.9 ms.)
-                if (!t.both && !(t.both = direct_pass_new())) return t.host_nomem = true, FASTECC_E_NOMEM;
+                if (!have(t.both)) return FASTECC_E_NOMEM;
                 rc = direct_build_interp(t.both, wd, N, K, R, xr, A, ya, nullptr, &yt, &pos);
                 t.both_built = rc == FASTECC_OK;
             } else {
-                if (!t.parity && !(t.parity = direct_pass_new())) return t.host_nomem = true, FASTECC_E_NOMEM;
+                if (!have(t.parity)) return FASTECC_E_NOMEM;
                 rc = direct_build_lagrange(t.parity, wd, K, yt, ct, pos, nullptr);
             }
         }
@@ -959,11 +925,8 @@ struct Prepare {
         int rc = call.wait_idle();  // a decode still using the previous pattern
         if (rc != FASTECC_OK) return rc;
         ptd.mark("few losses: lock, idle");
-        PatternTables t{d->direct_data, d->direct_parity, d->direct_both};  // the state's passes are built over from pattern to pattern
-        rc = direct_tables(R, Pl, A, t, ptd);
-        d->direct_data = t.data;
-        d->direct_parity = t.parity;
-        d->direct_both = t.both;
+        const PatternTables& t = d->direct;
+        rc = direct_tables(R, Pl, A, d->direct, ptd);
         d->sub_only_both = t.only_both;
         d->sub_both = t.both_built;
         if (rc == FASTECC_E_NOMEM && !t.host_nomem) return FASTECC_OK;  // no memory for the weight tables: the transform path
@@ -1023,12 +986,11 @@ struct Prepare {
     // blocks at multiples of 2^h) leave s as it is: the host scan.
     int scan_device(CallScope& call)
     {
-        if (!d->dev_present) HIP_TRY(hipMalloc((void**)&d->dev_present, 2 * N));
-        if (!d->dev_counts) HIP_TRY(hipMalloc((void**)&d->dev_counts, 8 * 4));
-        if (!d->dev_state) HIP_TRY(hipMalloc((void**)&d->dev_state, NC));
-        if (!d->parity_lost) HIP_TRY(hipMalloc((void**)&d->parity_lost, ci.user_m * 4));
-        const int rc = call.wait_idle();  // a decode or repair still reading the previous pattern's state
-        if (rc != FASTECC_OK) return rc;
+        RC_TRY(d->dev_present.alloc(2 * N));
+        RC_TRY(d->dev_counts.alloc(8));
+        RC_TRY(d->dev_state.alloc(NC));
+        RC_TRY(d->parity_lost.alloc(ci.user_m));
+        RC_TRY(call.wait_idle());  // a decode or repair still reading the previous pattern's state
         d->ready = false;
         HIP_TRY(hipMemcpyAsync(d->dev_present, data_present, N, hipMemcpyHostToDevice, nullptr));
         HIP_TRY(hipMemcpyAsync(d->dev_present + N, parity_present, N, hipMemcpyHostToDevice, nullptr));
@@ -1051,7 +1013,7 @@ struct Prepare {
         s.split_shift = shift;
         s.split_groups = shift ? 1u : 0u;
         hipLaunchKernelGGL(standard_state_kernel, grid_of(N), dim3(256), 0, nullptr, d->dev_present, d->dev_present + N, (uint32_t)N,
-                           shift ? (1u << shift) - 1u : 0u, (uint8_t*)d->dev_state, d->parity_lost);
+                           shift ? (1u << shift) - 1u : 0u, d->dev_state, d->parity_lost);
         HIP_TRY(hipGetLastError());
         return FASTECC_OK;
     }
@@ -1143,9 +1105,8 @@ struct Prepare {
         if (!s.device_scan) {
             std::vector<uint32_t> plost(ci.user_m);
             for (uint64_t q = 0; q < ci.user_m; q++) plost[q] = parity_present[q] ? 0u : 1u;
-            if (!d->parity_lost) HIP_TRY(hipMalloc((void**)&d->parity_lost, ci.user_m * 4));
-            const int rc = call.wait_idle();  // a repair still reading the previous pattern
-            if (rc != FASTECC_OK) return rc;
+            RC_TRY(d->parity_lost.alloc(ci.user_m));
+            RC_TRY(call.wait_idle());  // a repair still reading the previous pattern
             HIP_TRY(hipMemcpy(d->parity_lost, plost.data(), ci.user_m * 4, hipMemcpyHostToDevice));
         }
         pt.mark("lost-parity flags");
@@ -1169,7 +1130,7 @@ struct Prepare {
         if (s.split_groups != 0 && d->split && (rc = split_buffers()) != FASTECC_OK) return rc;
         if (d->standard && d->erased_parity != 0 && !(s.split_groups != 0 && d->split) && !d->transform_full) {
             // repair in one transform (see DecodeState::transform_full): the form for patterns or plans the split transform does not take
-            rc = create_ramp_transform_ctx(&d->transform_full, lgc, ci.words * 4, 0, gf::h_inv((uint32_t)NC), ci.device);
+            rc = create_ramp_transform_ctx(d->transform_full.fill(), lgc, ci.words * 4, 0, gf::h_inv((uint32_t)NC), ci.device);
             if (rc != FASTECC_OK && rc != FASTECC_E_NOMEM) return rc;
             d->full_ok = d->transform_full && same_tile_order(d->transform, d->transform_full);
             if (getenv("FASTECC_TRACE_PREPARE"))
@@ -1178,9 +1139,10 @@ struct Prepare {
         }
         if (d->standard && !d->tile_order_valid) {
             if (same_tile_order(d->transform, d->transform)) {  // (a tile first pass: the order exists)
-                HIP_TRY(hipMalloc((void**)&d->tile_order, NC * 4));
+                RC_TRY(d->tile_order.alloc(NC));
                 if (!gather_tile_order_device(d->transform, d->tile_order, nullptr)) return FASTECC_E_DEVICE;
-                HIP_TRY(hipMalloc((void**)&d->fin_first_pass, NC * 4));
+                RC_TRY(d->fin_tiled.alloc(NC));
+                d->fin_first_pass = d->fin_tiled;
             } else {
                 d->fin_first_pass = d->fin;
             }
@@ -1197,16 +1159,16 @@ struct Prepare {
             int rc;
             if (mixed) {
                 const std::vector<uint32_t> ones(NC, 1u);
-                rc = create_mixed_transform_ctx(&d->pattern_ntt, ci.q, lgc, 8, ones.data(), ci.device);
+                rc = create_mixed_transform_ctx(d->pattern_ntt.fill(), ci.q, lgc, 8, ones.data(), ci.device);
             } else {
                 // only its stand-alone transform is used; long ones as the upper row bits of a four-step transform (chunk_transform_kernel)
                 d->pattern_narrow = narrow && lgc + 1 - CHUNK_LOG >= 1;
-                rc = d->pattern_narrow ? create_ntt_ctx(&d->pattern_ntt, lgc + 1 - CHUNK_LOG, 4 * CHUNK, ci.device) : create_ntt_ctx(&d->pattern_ntt, lgc, 8, ci.device);
+                rc = d->pattern_narrow ? create_ntt_ctx(d->pattern_ntt.fill(), lgc + 1 - CHUNK_LOG, 4 * CHUNK, ci.device) : create_ntt_ctx(d->pattern_ntt.fill(), lgc, 8, ci.device);
             }
             if (rc != FASTECC_OK) return rc;
         }
         pt.mark("pattern_ntt context");
-        if (!d->pattern_buf) HIP_TRY(hipMalloc((void**)&d->pattern_buf, 2 * NC * 4));
+        RC_TRY(d->pattern_buf.alloc(2 * NC));
         if (!d->transform) {
             // x p'(x): coefficient m times m, and the 1/NC of the inverse transform.  fold e: only the data positions (multiples of 2^e) are
             // evaluated (mixed radix: all positions, the even ones are used)
@@ -1216,9 +1178,9 @@ struct Prepare {
                 std::vector<uint32_t> factor(NC);
                 const uint32_t inv_nc_m = gf::h_to_mont(inv_nc);
                 for (uint64_t m = 0; m < NC; m++) factor[m] = gf::h_mont_mul((uint32_t)m, inv_nc_m);
-                rc = create_mixed_transform_ctx(&d->transform, ci.q, lgc, ci.words * 4, factor.data(), ci.device);
+                rc = create_mixed_transform_ctx(d->transform.fill(), ci.q, lgc, ci.words * 4, factor.data(), ci.device);
             } else {
-                rc = create_ramp_transform_ctx(&d->transform, lgc, ci.words * 4, e, inv_nc, ci.device);
+                rc = create_ramp_transform_ctx(d->transform.fill(), lgc, ci.words * 4, e, inv_nc, ci.device);
             }
             if (rc != FASTECC_OK) return rc;
         }
@@ -1229,28 +1191,23 @@ struct Prepare {
     // the tree's contexts and buffers: level k >= leaf_log multiplies pairs of degree-2^k polynomials — transforms of length 2^(k+1) on T / 2^k columns
     int build_tree()
     {
-        for (fastecc_ctx* x : d->tree_ctx)
-            if (x) fastecc_destroy(x);
-        if (d->tree_top) fastecc_destroy(d->tree_top);
-        d->tree_top = nullptr;
-        d->tree_ctx.assign(lgT, nullptr);
+        d->tree_ctx.clear();
+        d->tree_top.reset();
+        d->tree_ctx.resize(lgT);
         const bool narrow_tree = narrow && lgT + 1 - CHUNK_LOG >= 1 && lgT > leaf_log;
         for (int lv = leaf_log; lv < lgT; lv++) {
             if (narrow_tree && (T >> lv) <= NARROW_COLUMNS) continue;  // tree_top + chunk_transform_kernel
-            const int rc = create_ntt_ctx(&d->tree_ctx[lv], lv + 1, 4 * (T >> lv), ci.device);
+            const int rc = create_ntt_ctx(d->tree_ctx[lv].fill(), lv + 1, 4 * (T >> lv), ci.device);
             if (rc != FASTECC_OK) return rc;
         }
         if (narrow_tree) {
-            const int rc = create_ntt_ctx(&d->tree_top, lgT + 1 - CHUNK_LOG, 4 * CHUNK, ci.device);
+            const int rc = create_ntt_ctx(d->tree_top.fill(), lgT + 1 - CHUNK_LOG, 4 * CHUNK, ci.device);
             if (rc != FASTECC_OK) return rc;
         }
-        for (uint32_t** b : {&d->tree_x, &d->tree_f, &d->tree_y, &d->tree_p, &d->roots, &d->dev_erased}) {
-            if (*b) (void)hipFree(*b);
-            *b = nullptr;
-        }
-        for (uint32_t** b : {&d->tree_x, &d->tree_f, &d->tree_y, &d->tree_p}) HIP_TRY(hipMalloc((void**)b, 2 * T * 4));
-        HIP_TRY(hipMalloc((void**)&d->roots, T * 4));
-        HIP_TRY(hipMalloc((void**)&d->dev_erased, (T + 1) * 4));  // + the counter of erased_list_kernel
+        for (DeviceBuf<uint32_t>* b : {&d->tree_x, &d->tree_f, &d->tree_y, &d->tree_p, &d->roots, &d->dev_erased}) b->reset();
+        for (DeviceBuf<uint32_t>* b : {&d->tree_x, &d->tree_f, &d->tree_y, &d->tree_p}) RC_TRY(b->alloc(2 * T));
+        RC_TRY(d->roots.alloc(T));
+        RC_TRY(d->dev_erased.alloc(T + 1));  // + the counter of erased_list_kernel
         d->tree_T = T;
         d->tree_low = leaf_log;
         return FASTECC_OK;
@@ -1262,24 +1219,19 @@ struct Prepare {
         if (!d->wpow) {
             // the table becomes visible to later calls only once the kernel that fills it has been launched without error
             // (an unfilled table behind a non-null pointer would give silently wrong weights on the next prepare)
-            uint32_t* fresh = nullptr;
-            HIP_TRY(hipMalloc((void**)&fresh, NC * 4));
-            hipLaunchKernelGGL(wpow_kernel, grid_of(NC), dim3(256), 0, nullptr, fresh, gf::h_root((uint32_t)NC), (uint32_t)NC);
-            const hipError_t e_fill = hipGetLastError();
-            if (e_fill != hipSuccess) {
-                (void)hipFree(fresh);
-                return hip_fail(e_fill, "wpow_kernel");
-            }
-            d->wpow = fresh;
+            DeviceBuf<uint32_t> fresh;
+            RC_TRY(fresh.alloc(NC));
+            hipLaunchKernelGGL(wpow_kernel, grid_of(NC), dim3(256), 0, nullptr, fresh.get(), gf::h_root((uint32_t)NC), (uint32_t)NC);
+            HIP_TRY(hipGetLastError());
+            d->wpow = std::move(fresh);
         }
-        if (!d->dev_state) HIP_TRY(hipMalloc((void**)&d->dev_state, NC));
-        if (!d->fin) HIP_TRY(hipMalloc((void**)&d->fin, NC * 4));
-        if (!d->srcmap) HIP_TRY(hipMalloc((void**)&d->srcmap, NC * 4));
-        if (!d->gout) HIP_TRY(hipMalloc((void**)&d->gout, N * 4));
-        if (parity_factors && !d->gout_par) HIP_TRY(hipMalloc((void**)&d->gout_par, N * 4));
+        RC_TRY(d->dev_state.alloc(NC));
+        RC_TRY(d->fin.alloc(NC));
+        RC_TRY(d->srcmap.alloc(NC));
+        RC_TRY(d->gout.alloc(N));
+        if (parity_factors) RC_TRY(d->gout_par.alloc(N));
         // mixed radix: the work stripe of all NC positions, transformed in place; else the N recovered data positions
-        if (!d->recovered) HIP_TRY(hipMalloc((void**)&d->recovered, (mixed ? NC : N) * ci.words * 4));
-        return FASTECC_OK;
+        return d->recovered.alloc((mixed ? NC : N) * ci.words);
     }
 
     // The split transform's context and tables (once).  Anything missing — a plan without the tile shapes, no memory for the two extra stripes —
@@ -1288,15 +1240,15 @@ struct Prepare {
     {
         const int rc = [&]() -> int {
             // per-block factor (2m + k) / 2k = m / k + 1 / 2
-            const int rc = create_ramp_transform_ctx(&d->split, ci.log2k, ci.words * 4, 0, gf::h_inv((uint32_t)N), ci.device, gf::h_inv(2u));
+            const int rc = create_ramp_transform_ctx(d->split.fill(), ci.log2k, ci.words * 4, 0, gf::h_inv((uint32_t)N), ci.device, gf::h_inv(2u));
             if (rc != FASTECC_OK) return rc;
             if (!split_decode_supported(d->split) || split_decode_groups(d->split) != 1024u) return FASTECC_E_UNSUPPORTED;
-            for (uint32_t** b : {&d->split_order, &d->split_rows_data, &d->split_rows_parity, &d->split_rows_out, &d->split_pos_parity, &d->split_pos_data_odd,
-                                 &d->split_rows_out_parity})
-                HIP_TRY(hipMalloc((void**)b, N * 4));
+            for (DeviceBuf<uint32_t>* b : {&d->split_order, &d->split_rows_data, &d->split_rows_parity, &d->split_rows_out, &d->split_pos_parity,
+                                           &d->split_pos_data_odd, &d->split_rows_out_parity})
+                RC_TRY(b->alloc(N));
             if (!gather_tile_order_device(d->split, d->split_order, nullptr)) return FASTECC_E_UNSUPPORTED;
             const std::vector<uint32_t> table = split_impulse_table(gf::h_root((uint32_t)NC), N);
-            HIP_TRY(hipMalloc((void**)&d->split_impulse, table.size() * 4));
+            RC_TRY(d->split_impulse.alloc(table.size()));
             HIP_TRY(hipMemcpy(d->split_impulse, table.data(), table.size() * 4, hipMemcpyHostToDevice));
             const uint32_t neg_half = (uint32_t)(gf::P - gf::h_inv(2u));
             hipLaunchKernelGGL(split_pos_kernel, grid_of(N), dim3(256), 0, nullptr, d->wpow, d->split_pos_parity, (uint32_t)N, ci.log2k, neg_half, false);
@@ -1310,13 +1262,10 @@ struct Prepare {
         }
         // nothing half-built stays behind: a later call either builds all of it or none
         (void)hipGetLastError();
-        if (d->split) fastecc_destroy(d->split);
-        d->split = nullptr;
-        for (uint32_t** b : {&d->split_order, &d->split_rows_data, &d->split_rows_parity, &d->split_rows_out, &d->split_pos_parity, &d->split_impulse,
-                             &d->split_r1, &d->split_r2, &d->split_pos_data_odd, &d->split_rows_out_parity}) {
-            if (*b) (void)hipFree(*b);
-            *b = nullptr;
-        }
+        d->split.reset();
+        for (DeviceBuf<uint32_t>* b : {&d->split_order, &d->split_rows_data, &d->split_rows_parity, &d->split_rows_out, &d->split_pos_parity, &d->split_impulse,
+                                       &d->split_r1, &d->split_r2, &d->split_pos_data_odd, &d->split_rows_out_parity})
+            b->reset();
         if (rc != FASTECC_E_NOMEM && rc != FASTECC_E_UNSUPPORTED) return rc;
         d->split_unavailable = true;
         return FASTECC_OK;
@@ -1331,27 +1280,19 @@ struct Prepare {
         if (s.split_shift != 0) {
             const uint64_t rows = N >> s.split_shift;
             if (!d->split_small[s.split_shift]) {
-                const int rc = create_ntt_ctx(&d->split_small[s.split_shift], ci.log2k - (int)s.split_shift, ci.words * 4, ci.device);
+                const int rc = create_ntt_ctx(d->split_small[s.split_shift].fill(), ci.log2k - (int)s.split_shift, ci.words * 4, ci.device);
                 if (rc != FASTECC_OK && rc != FASTECC_E_NOMEM && rc != FASTECC_E_UNSUPPORTED) return rc;
                 if (rc != FASTECC_OK) err = hipErrorOutOfMemory;
             }
-            if (err == hipSuccess && d->split_small_blocks < rows) {
-                if (d->split_small_buf) (void)hipFree(d->split_small_buf);
-                d->split_small_buf = nullptr;
-                d->split_small_blocks = 0;
-                err = hipMalloc((void**)&d->split_small_buf, rows * ci.words * 4);
-                if (err == hipSuccess) d->split_small_blocks = rows;
-            }
+            if (err == hipSuccess) err = d->split_small_buf.try_grow(rows * ci.words);
         } else if (!d->split_r1 || !d->split_r2) {
-            if (!d->split_r1) err = hipMalloc((void**)&d->split_r1, N * ci.words * 4);
-            if (err == hipSuccess && !d->split_r2) err = hipMalloc((void**)&d->split_r2, N * ci.words * 4);
+            err = d->split_r1.try_alloc(N * ci.words);
+            if (err == hipSuccess) err = d->split_r2.try_alloc(N * ci.words);
             if (err == hipSuccess) err = hipMemsetAsync(d->split_r1, 0, N * ci.words * 4, nullptr);
             d->split_dirty = 0;
             if (err != hipSuccess) {
-                for (uint32_t** b : {&d->split_r1, &d->split_r2}) {
-                    if (*b) (void)hipFree(*b);
-                    *b = nullptr;
-                }
+                d->split_r1.reset();
+                d->split_r2.reset();
             }
         }
         if (err != hipSuccess) {
@@ -1389,10 +1330,10 @@ struct Prepare {
         hipStream_t st = nullptr;
         if (!s.device_scan) HIP_TRY(hipMemcpyAsync(d->dev_state, s.state.data(), NC, hipMemcpyHostToDevice, st));
         if (!s.srcmap.empty()) HIP_TRY(hipMemcpyAsync(d->srcmap, s.srcmap.data(), NC * 4, hipMemcpyHostToDevice, st));
-        else hipLaunchKernelGGL(standard_srcmap_kernel, grid_of(NC), dim3(256), 0, st, (const uint8_t*)d->dev_state, (uint32_t)NC, d->srcmap);
+        else hipLaunchKernelGGL(standard_srcmap_kernel, grid_of(NC), dim3(256), 0, st, d->dev_state, (uint32_t)NC, d->srcmap);
         // the list of erased positions (any order: the locator is their product); its counter sits behind the list
         HIP_TRY(hipMemsetAsync(d->dev_erased + T, 0, 4, st));
-        hipLaunchKernelGGL(erased_list_kernel, grid_of((NC + 15) / 16), dim3(256), 0, st, (const uint8_t*)d->dev_state, (uint32_t)NC, d->dev_erased, d->dev_erased + T);
+        hipLaunchKernelGGL(erased_list_kernel, grid_of((NC + 15) / 16), dim3(256), 0, st, d->dev_state, (uint32_t)NC, d->dev_erased, d->dev_erased + T);
         hipLaunchKernelGGL(roots_kernel, grid_of(T), dim3(256), 0, st, d->roots, d->dev_erased, d->wpow, (uint32_t)s.erased_count, (uint32_t)T);
         HIP_TRY(hipMemsetAsync(d->tree_x, 0, 2 * T * 4, st));
         const uint32_t leaves = (uint32_t)(T >> leaf_log);
@@ -1435,8 +1376,8 @@ struct Prepare {
                        : d->pattern_narrow ? narrow_transform(d->pattern_ntt, lgc, 1, d->pattern_buf, d->pattern_buf, false)
                                            : transform_bitrev(d->pattern_ntt, d->pattern_buf, d->pattern_buf, false, false, 2, st);
         if (rc != FASTECC_OK) return rc;
-        hipLaunchKernelGGL(finish_tables_kernel, grid_of(NC), dim3(256), 0, st, d->pattern_buf, d->dev_state, d->wpow, d->fin, d->gout, (uint32_t)NC,
-                           (uint32_t)(T - s.erased_count), e, (uint32_t)ci.user_k, (uint32_t)(mixed ? ci.q : 1), lgc, parity_factors ? d->gout_par : nullptr,
+        hipLaunchKernelGGL(finish_tables_kernel, grid_of(NC), dim3(256), 0, st, d->pattern_buf, (const uint32_t*)d->dev_state.get(), d->wpow, d->fin, d->gout, (uint32_t)NC,
+                           (uint32_t)(T - s.erased_count), e, (uint32_t)ci.user_k, (uint32_t)(mixed ? ci.q : 1), lgc, parity_factors ? d->gout_par.get() : nullptr,
                            !mixed);
         HIP_TRY(hipGetLastError());
         if (d->fin_first_pass != d->fin) {
@@ -1447,7 +1388,7 @@ struct Prepare {
         // (fastecc_repair in the (2k,k) layout: the lost parity blocks' factors too — gout_par is filled above for such patterns)
         const bool with_parity = parity_factors && d->gout_par != nullptr;
         hipLaunchKernelGGL(split_rows_kernel, grid_of(N), dim3(256), 0, st, d->fin, d->gout, d->split_order, d->split_rows_data, d->split_rows_parity,
-                           d->split_rows_out, (uint32_t)N, with_parity ? d->gout_par : nullptr, with_parity ? d->split_rows_out_parity : nullptr);
+                           d->split_rows_out, (uint32_t)N, with_parity ? d->gout_par.get() : nullptr, with_parity ? d->split_rows_out_parity.get() : nullptr);
         d->split_repair_ready = with_parity;
         HIP_TRY(hipGetLastError());
         d->split_shift = s.split_shift;
@@ -1527,24 +1468,12 @@ int decode_p61(fastecc_ctx* c, CallScope& call, void* data, const void* parity, 
 // for both: one pass over the survivors writes both (fastecc_decode: the data only); else the lost data, then (rebuild) the lost parity from it.
 template <class Pass> int direct_passes(const DecodeState* d, bool rebuild, uint32_t* data, const uint32_t* parity, uint32_t* parity_out, Pass&& pass)
 {
-    if (d->sub_both && (rebuild || d->sub_only_both)) return pass(d->direct_both, parity, data, rebuild ? parity_out : nullptr);
+    if (d->sub_both && (rebuild || d->sub_only_both)) return pass(d->direct.both, parity, data, rebuild ? parity_out : nullptr);
     if (d->sub_lost_data > 0) {
-        const int rc = pass(d->direct_data, parity, data, nullptr);
+        const int rc = pass(d->direct.data, parity, data, nullptr);
         if (rc != FASTECC_OK) return rc;
     }
-    return rebuild ? pass(d->direct_parity, nullptr, nullptr, parity_out) : FASTECC_OK;
-}
-
-// a grow-only buffer of `need` words, device or pinned host memory (false: no memory, the old buffer is gone as well)
-bool grow(uint32_t** p, uint64_t* have, uint64_t need, bool host)
-{
-    if (*have >= need) return true;
-    if (*p) (void)(host ? hipHostFree(*p) : hipFree(*p));
-    *p = nullptr;
-    *have = 0;
-    if ((host ? hipHostMalloc((void**)p, need * 4, hipHostMallocDefault) : hipMalloc((void**)p, need * 4)) != hipSuccess) return false;
-    *have = need;
-    return true;
+    return rebuild ? pass(d->direct.parity, nullptr, nullptr, parity_out) : FASTECC_OK;
 }
 
 // One stripe's decode of a GF(0xFFF00001) code, the call lock held and the internal buffers ordered on `st`
@@ -1566,7 +1495,7 @@ struct StripeDecode {
     int stage_host(const void* host_data, const void* host_parity, bool* rows_only)
     {
         const size_t data_bytes = ci.user_k * block, parity_bytes = ci.user_m * block;
-        if (!d->parity_dev) HIP_TRY(hipMalloc((void**)&d->parity_dev, parity_bytes + data_bytes));
+        RC_TRY(d->parity_dev.alloc((ci.user_m + ci.user_k) * S));
         if (d->host_lists_of != d->pattern_serial) {
             // the rows that travel back: known from the set-up (few losses), else read off the decoder's tables once per pattern
             d->host_lost_data.clear();
@@ -1657,9 +1586,8 @@ struct StripeDecode {
     // form does not take: *done stays false.
     int repair_split(bool* done)
     {
-        if (!d->split_q2 && hipMalloc((void**)&d->split_q2, N * block) != hipSuccess) {
+        if (d->split_q2.try_alloc(N * S) != hipSuccess) {
             (void)hipGetLastError();
-            d->split_q2 = nullptr;
             return FASTECC_OK;
         }
         const SplitRepair odd{d->split_q2, d->split_pos_data_odd, d->split_rows_out_parity, parity_out};
@@ -1679,7 +1607,7 @@ struct StripeDecode {
     // the 2k-block stripe, or a plan whose first pass cannot read the codeword: *done stays false.
     int repair_full(bool* done)
     {
-        if (!d->recovered_full && hipMalloc((void**)&d->recovered_full, d->positions * (size_t)S * 4) != hipSuccess) {
+        if (d->recovered_full.try_alloc(d->positions * S) != hipSuccess) {
             (void)hipGetLastError();
             return FASTECC_OK;
         }
@@ -1703,9 +1631,8 @@ struct StripeDecode {
             profile_scope_end(scope);
             return rc;
         }
-        if (ci.fold > 0 && !d->split_r0 && hipMalloc((void**)&d->split_r0, N * block) != hipSuccess) {
+        if (ci.fold > 0 && d->split_r0.try_alloc(N * S) != hipSuccess) {
             (void)hipGetLastError();
-            d->split_r0 = nullptr;
             return FASTECC_E_UNSUPPORTED;
         }
         void* scope = profile_scope_begin(c, st, "decode_split_transform", (3 * N + (uint64_t)d->split_groups * split_decode_group_rows(d->split)) * block);
@@ -1758,7 +1685,7 @@ struct StripeDecode {
     // only the lost blocks are copied — the surviving ones are left as they are
     int reencode_parity()
     {
-        if (!d->parity_again) HIP_TRY(hipMalloc((void**)&d->parity_again, ci.user_m * block));
+        RC_TRY(d->parity_again.alloc(ci.user_m * S));
         const int rc = encode_unlocked(c, data, d->parity_again, st);
         if (rc != FASTECC_OK) return rc;
         launch_rows(restore_parity_kernel<4>, restore_parity_kernel<1>, ci.user_m, S, {parity_out, d->parity_again}, st, d->parity_again, parity_out, d->parity_lost, S);
@@ -1772,8 +1699,8 @@ struct StripeDecode {
     int copy_back(void* host_data, void* host_parity, bool rows_only)
     {
         const uint64_t nd = d->erased_data != 0 ? d->host_lost_data.size() : 0, np = rebuild ? d->host_lost_parity.size() : 0;
-        if (rows_only && grow(&d->lost_rows_dev, &d->lost_rows_cap, nd + np, false) && grow(&d->pack_dev, &d->pack_words, (nd + np) * S, false) &&
-            grow(&d->pack_host, &d->pack_host_words, (nd + np) * S, true)) {
+        if (rows_only && d->lost_rows_dev.try_grow(nd + np) == hipSuccess && d->pack_dev.try_grow((nd + np) * S) == hipSuccess &&
+            d->pack_host.try_grow((nd + np) * S) == hipSuccess) {
             if (nd) HIP_TRY(hipMemcpyAsync(d->lost_rows_dev, d->host_lost_data.data(), nd * 4, hipMemcpyHostToDevice, st));
             if (np) HIP_TRY(hipMemcpyAsync(d->lost_rows_dev + nd, d->host_lost_parity.data(), np * 4, hipMemcpyHostToDevice, st));
             if (nd)
@@ -1969,43 +1896,17 @@ int prepare_set_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t*
             while ((1u << fresh->cls[q]) < desc[q].cstride) fresh->cls[q]++;
             fresh->rows[q] = desc[q].rows;
         }
-        HIP_TRY(hipMalloc((void**)&fresh->d_passes, P * sizeof(DirectSetPass)));
+        RC_TRY(fresh->d_passes.alloc(P));
         HIP_TRY(hipMemcpy(fresh->d_passes, desc.data(), P * sizeof(DirectSetPass), hipMemcpyHostToDevice));
         pt.mark("tables of the set");
     }
     const int rc = call.wait_idle();  // device work that still uses the previous set (its tables, its list buffer)
     if (rc != FASTECC_OK) return rc;
     if (fresh && slot) {  // the list buffers outlive a set
-        std::swap(fresh->h_list, slot->h_list);
-        std::swap(fresh->d_list, slot->d_list);
-        std::swap(fresh->list_cap, slot->list_cap);
-        std::swap(fresh->list_event, slot->list_event);
-        fresh->list_pending = slot->list_pending = false;  // (the wait above outlasted the last copy out of h_list)
+        fresh->list = std::move(slot->list);
+        fresh->list.pending = false;  // (the wait above outlasted the last copy out of the pinned side)
     }
     std::swap(slot, fresh);  // (DropFresh frees the previous set)
-    return FASTECC_OK;
-}
-
-// h_list / d_list for `entries` entries, h_list free to be written: a call whose predecessor's list is still on its way to the device waits for
-// that copy's event (not for the device); growing waits for the last use of the device buffer and allocates (update.hip: batch_list_buffers).
-int set_list_buffers(CallScope& call, PatternSet* s, size_t entries)
-{
-    if (!s->list_event) HIP_TRY(hipEventCreateWithFlags(&s->list_event, hipEventDisableTiming));
-    if (s->list_pending) {
-        HIP_TRY(hipEventSynchronize(s->list_event));
-        s->list_pending = false;
-    }
-    if (entries <= s->list_cap) return FASTECC_OK;
-    const size_t cap = std::max<size_t>(std::max<size_t>(entries, 2 * s->list_cap), 4096);
-    const int rc = call.wait_idle();  // the kernels that read d_list
-    if (rc != FASTECC_OK) return rc;
-    if (s->h_list) (void)hipHostFree(s->h_list);
-    if (s->d_list) (void)hipFree(s->d_list);
-    s->h_list = s->d_list = nullptr;
-    s->list_cap = 0;
-    HIP_TRY(hipHostMalloc((void**)&s->h_list, cap * sizeof(DirectSetEntry), hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void**)&s->d_list, cap * sizeof(DirectSetEntry)));
-    s->list_cap = cap;
     return FASTECC_OK;
 }
 
@@ -2044,7 +1945,7 @@ int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
     DeviceGuard dg(ci.device);
     if (!dg.ok) return FASTECC_E_DEVICE;
     hipStream_t st = (hipStream_t)stream;
-    int rc = set_list_buffers(call, s, total);
+    int rc = s->list.reserve(total, [&] { return call.wait_idle(); });  // (growing waits for the kernels that read the device list)
     if (rc != FASTECC_OK) return rc;
     uint64_t first[CLASSES], at[CLASSES], moved[CLASSES] = {};  // a class's entries: [first, first + per_class); blocks its passes read and write
     for (int k = 0; k < CLASSES; k++) first[k] = at[k] = k ? first[k - 1] + per_class[k - 1] : 0;
@@ -2054,7 +1955,7 @@ int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
         if (!work_of(q)) continue;
         const int k = s->cls[q];
         if (at[k] >= first[k] + per_class[k]) return FASTECC_E_INVAL;
-        s->h_list[at[k]++] = DirectSetEntry{b, q, 0};
+        s->list.host[at[k]++] = DirectSetEntry{b, q, 0};
         moved[k] += (uint64_t)s->rows[q] + (uint64_t)s->tables[q].ed + (repair ? (uint64_t)s->tables[q].ep : 0);
     }
     const uint64_t S = ci.words, data_words = ci.user_k * S, parity_words = ci.user_m * S;
@@ -2068,25 +1969,21 @@ int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
     }
     if ((rc = call.begin(st)) != FASTECC_OK) return rc;
     EndScope end{call, st};
-    if (any_kernel) {
-        HIP_TRY(hipMemcpyAsync(s->d_list, s->h_list, total * sizeof(DirectSetEntry), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(s->list_event, st));
-        s->list_pending = true;
-    }
+    if (any_kernel && (rc = s->list.publish(total, st)) != FASTECC_OK) return rc;
     for (int k = 0; k < CLASSES; k++) {
         const uint64_t n = at[k] - first[k];
         if (n == 0) continue;
         if (kernel[k]) {
             void* scope = profile_scope_begin(c, st, "direct_pass_set", moved[k] * block);
-            rc = direct_run_set(1 << k, s->d_passes, s->d_list + first[k], n, ddata, dparity, ddata, repair ? dparity : nullptr, S, data_words, parity_words, st);
+            rc = direct_run_set(1 << k, s->d_passes, s->list.dev + first[k], n, ddata, dparity, ddata, repair ? dparity : nullptr, S, data_words, parity_words, st);
             profile_scope_end(scope);
             if (rc != FASTECC_OK) return rc;
             continue;
         }
         void* scope = profile_scope_begin(c, st, "direct_pass", moved[k] * block);
         for (uint64_t i = first[k]; i < at[k] && rc == FASTECC_OK; i++) {
-            const uint64_t b = s->h_list[i].stripe;
-            const uint32_t q = s->h_list[i].pass;
+            const uint64_t b = s->list.host[i].stripe;
+            const uint32_t q = s->list.host[i].pass;
             uint32_t* db = ddata + b * data_words;
             uint32_t* pb = dparity + b * parity_words;
             const bool reads_parity = s->kind[q] != PatternSet::PARITY, writes_data = reads_parity, writes_parity = repair && s->kind[q] != PatternSet::DATA;

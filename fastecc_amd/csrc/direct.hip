@@ -27,6 +27,7 @@
 #include <new>
 #include <vector>
 
+#include "devmem.hpp"
 #include "gf.hpp"
 #include "internal.hpp"
 #include "lazy96.hpp"
@@ -544,18 +545,6 @@ __global__ __launch_bounds__(256) void interp_node_kernel(uint32_t* __restrict__
     coef[coef_index(K + (uint32_t)a, (uint32_t)t, K + (uint32_t)ed, (uint32_t)pad)] = v;
 }
 
-// grow-only device buffer
-template <class T> int ensure(T*& p, uint64_t& have, uint64_t need)
-{
-    if (have >= need && p) return FASTECC_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    have = 0;
-    HIP_TRY(hipMalloc((void**)&p, need * sizeof(T)));
-    have = need;
-    return FASTECC_OK;
-}
-
 int pad_of(int outputs)
 {
     int pad = 1;
@@ -566,14 +555,11 @@ int pad_of(int outputs)
 }  // namespace
 
 struct DirectPass {
-    uint32_t* coef = nullptr;     // [rows][pad], Montgomery form
-    uint64_t coef_words = 0;
-    uint32_t* params = nullptr;   // 3 * DIRECT_CAP field elements for the table kernels
-    uint32_t* lists = nullptr;    // [0, CAP) parity rows used as nodes; [CAP, 2 CAP) output positions (row << 1 | parity)
-    uint32_t* partial = nullptr;  // [chunks + DIRECT_SEGS][pad][S]
-    uint64_t partial_words = 0;
-    uint4* frag = nullptr;        // MFMA weight fragments
-    uint64_t frag_count = 0;
+    DeviceBuf<uint32_t> coef;     // [rows][pad], Montgomery form (grow-only, like partial and frag)
+    DeviceBuf<uint32_t> params;   // 3 * DIRECT_CAP field elements for the table kernels
+    DeviceBuf<uint32_t> lists;    // [0, CAP) parity rows used as nodes; [CAP, 2 CAP) output positions (row << 1 | parity)
+    DeviceBuf<uint32_t> partial;  // [chunks + DIRECT_SEGS][pad][S]
+    DeviceBuf<uint4> frag;        // MFMA weight fragments
     bool frag_valid = false;
     int mfma_pad = 0;             // outputs rounded up to the M-tiles of the MFMA kernel in use
     uint32_t rows = 0, data_rows = 0;
@@ -582,13 +568,7 @@ struct DirectPass {
 };
 
 DirectPass* direct_pass_new() { return new (std::nothrow) DirectPass(); }
-void direct_pass_free(DirectPass* p)
-{
-    if (!p) return;
-    for (void* b : {(void*)p->coef, (void*)p->params, (void*)p->lists, (void*)p->partial, (void*)p->frag})
-        if (b) (void)hipFree(b);
-    delete p;
-}
+void direct_pass_free(DirectPass* p) { delete p; }
 int direct_cap() { return DIRECT_CAP; }
 int direct_pass_outputs(const DirectPass* p) { return p && p->built ? p->outputs : 0; }
 
@@ -601,13 +581,9 @@ static int pass_common(DirectPass* p, uint32_t rows, uint32_t data_rows, int out
     p->data_rows = data_rows;
     p->outputs = outputs;
     p->pad = pad_of(outputs);
-    uint64_t fixed = p->params ? 3 * DIRECT_CAP : 0;
-    int rc = ensure(p->params, fixed, 3 * DIRECT_CAP);
-    if (rc != FASTECC_OK) return rc;
-    fixed = p->lists ? 2 * DIRECT_CAP : 0;
-    rc = ensure(p->lists, fixed, 2 * DIRECT_CAP);
-    if (rc != FASTECC_OK) return rc;
-    return ensure(p->coef, p->coef_words, (uint64_t)rows * p->pad);
+    RC_TRY(p->params.alloc(3 * DIRECT_CAP));
+    RC_TRY(p->lists.alloc(2 * DIRECT_CAP));
+    return p->coef.grow((uint64_t)rows * p->pad);
 }
 
 int direct_build_lagrange(DirectPass* p, uint32_t wd, uint32_t K, const std::vector<uint32_t>& y, const std::vector<uint32_t>& c, const std::vector<uint32_t>& out_pos,
@@ -672,7 +648,7 @@ static int launch_accumulate(DirectPass* p, const uint32_t* data, const uint32_t
     const uint32_t chunks = (p->rows - row_begin + rows_per_chunk - 1) / rows_per_chunk;
     const int vmax = eb <= 4 ? 4 : eb == 8 ? 2 : 1;
     int v = vmax;
-    const uintptr_t align = (uintptr_t)data | (uintptr_t)parity | (uintptr_t)p->partial;
+    const uintptr_t align = (uintptr_t)data | (uintptr_t)parity | (uintptr_t)p->partial.get();
     while (v > 1 && ((S % v) != 0 || (align & (4u * v - 1u)) != 0)) v >>= 1;
     AccArgs a{data, parity, p->lists, p->coef, p->partial, S, p->rows, p->data_rows, (uint32_t)pad, rows_per_chunk, (S + 64u * v - 1u) / (64u * v), 0, row_begin, chunk_base, ppad};
     a.items = (uint64_t)chunks * a.col_chunks;
@@ -736,7 +712,7 @@ int direct_run(DirectPass* p, const uint32_t* data, const uint32_t* parity, uint
         const uint32_t steps_alloc = bulk / 8u + MFMA_G;  // zero steps at the end: the prefetch of a stage never leaves the table
         if (!p->frag_valid || p->mfma_pad != pad) {
             const uint64_t count = (uint64_t)steps_alloc * mt_total * 64u;
-            const int rc = ensure(p->frag, p->frag_count, count);
+            const int rc = p->frag.grow(count);
             if (rc != FASTECC_OK) return rc;
             hipLaunchKernelGGL(mfma_weights_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, p->coef, p->frag, bulk, rows, (uint32_t)p->pad, mt_total, count);
             HIP_TRY(hipGetLastError());
@@ -753,7 +729,7 @@ int direct_run(DirectPass* p, const uint32_t* data, const uint32_t* parity, uint
         const uint32_t mchunks = (bulk + chunk_rows - 1) / chunk_rows;
         const uint32_t tail_chunks = rows > bulk ? (rows - bulk + TAIL_ROWS - 1) / TAIL_ROWS : 0;
         chunks = mchunks + tail_chunks;
-        int rc = ensure(p->partial, p->partial_words, ((uint64_t)chunks + DIRECT_SEGS) * pad * S);
+        int rc = p->partial.grow(((uint64_t)chunks + DIRECT_SEGS) * pad * S);
         if (rc != FASTECC_OK) return rc;
         MfmaArgs a{data, p->frag, p->partial, S, bulk, (uint32_t)pad, mt_total, mchunks, col_groups, sweeps, chunk_rows};
         const dim3 grid((mchunks + 7u) / 8u * 8u * a.col_groups * a.sweeps);
@@ -801,7 +777,7 @@ int direct_run(DirectPass* p, const uint32_t* data, const uint32_t* parity, uint
         const int sweeps = pad > 16 ? pad / 16 : 1;
         const uint32_t rows_per_chunk = DIRECT_ROWS * (uint32_t)std::min(sweeps, 8);
         chunks = (rows + rows_per_chunk - 1) / rows_per_chunk;
-        int rc = ensure(p->partial, p->partial_words, ((uint64_t)chunks + DIRECT_SEGS) * pad * S);
+        int rc = p->partial.grow(((uint64_t)chunks + DIRECT_SEGS) * pad * S);
         if (rc != FASTECC_OK) return rc;
         rc = launch_accumulate(p, data, parity, S, 0, 0, (uint32_t)pad, rows_per_chunk, st);
         if (rc != FASTECC_OK) return rc;
@@ -1126,16 +1102,11 @@ int direct_run_set(int eb, const DirectSetPass* passes, const DirectSetEntry* en
 // transform pipeline.  Exactly the polynomial evaluation the transform computes (RS.cpp:40-63), hence the same parity bits.
 // ------------------------------------------------------------------------------------------------
 struct DirectEncode {
-    DirectPass* pass = nullptr;
+    DirectPassPtr pass;
     uint32_t S = 0;
 };
 
-void direct_encode_destroy(DirectEncode* de)
-{
-    if (!de) return;
-    direct_pass_free(de->pass);
-    delete de;
-}
+void direct_encode_destroy(DirectEncode* de) { delete de; }
 
 int direct_encode_max() { return DIRECT_CAP; }
 
@@ -1148,7 +1119,7 @@ int direct_encode_build(DirectEncode** out, uint64_t N, uint64_t K, uint64_t m, 
     DirectEncode* de = new (std::nothrow) DirectEncode();
     if (!de) return FASTECC_E_NOMEM;
     de->S = (uint32_t)words;
-    de->pass = direct_pass_new();
+    de->pass.reset(direct_pass_new());
     if (!de->pass) {
         delete de;
         return FASTECC_E_NOMEM;

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/fastecc.h"
+#include "devmem.hpp"
 #include "gf61.hpp"
 #include "gf61_path.hpp"
 #include "internal.hpp"
@@ -675,40 +676,30 @@ struct RowGrid {
     dim3 grid(unsigned y = 1) const { return dim3((unsigned)((items + 3) / 4), y); }
 };
 
-// A buffer that only grows: *ptr holds *have units of `unit` bytes and is replaced when `need` is more (no memory: it holds nothing)
-template <class T> hipError_t grow(T** ptr, uint64_t* have, uint64_t need, uint64_t unit)
-{
-    if (*have >= need) return hipSuccess;
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr;
-    *have = 0;
-    const hipError_t err = hipMalloc((void**)ptr, need * unit);
-    if (err == hipSuccess) *have = need;
-    return err;
-}
+using PathPtr = Owned<Path, destroy>;
 
 }  // namespace
 
 struct Decoder {
     int log2k = 0;
     uint64_t N = 0, NC = 0, T = 0, elems = 0;
-    Path* transform = nullptr;         // size 2k, factor m / 2k, `elems` columns: x p'(x) on a whole stripe
-    Path* pattern = nullptr;           // size 2k, 2 columns: L and x L' on the points
-    std::vector<Path*> tree;           // level k >= LEAF_LOG: size 2^(k+1), T >> k columns
-    std::vector<Path*> tree_inv;       // the way back of level k: size 2^(k+1), T >> (k+1) columns (the products)
-    Path* narrow_tree_inv = nullptr;   // ... of the few-column levels: T / CHUNK rows of CHUNK columns
-    Path *narrow_tree = nullptr, *narrow_pattern = nullptr;  // the upper row bits of the few-column transforms (k_chunk_dif): 2T / CHUNK and 2 NC / CHUNK rows of CHUNK columns
-    uint64_t *tree_x = nullptr, *tree_y = nullptr, *tree_f = nullptr;  // 2T elements each
-    uint64_t *wpow = nullptr, *roots = nullptr, *lv = nullptr, *fin = nullptr, *gout = nullptr;
-    uint64_t* gout_all = nullptr;      // 2k factors by position (lazy: patterns that lose data AND parity), valid for the current pattern if gout_all_valid
+    PathPtr transform;                   // size 2k, factor m / 2k, `elems` columns: x p'(x) on a whole stripe
+    PathPtr pattern;                     // size 2k, 2 columns: L and x L' on the points
+    std::vector<PathPtr> tree;           // level k >= LEAF_LOG: size 2^(k+1), T >> k columns
+    std::vector<PathPtr> tree_inv;       // the way back of level k: size 2^(k+1), T >> (k+1) columns (the products)
+    PathPtr narrow_tree_inv;             // ... of the few-column levels: T / CHUNK rows of CHUNK columns
+    PathPtr narrow_tree, narrow_pattern; // the upper row bits of the few-column transforms (k_chunk_dif): 2T / CHUNK and 2 NC / CHUNK rows of CHUNK columns
+    DeviceBuf<uint64_t> tree_x, tree_y, tree_f;  // 2T elements each
+    DeviceBuf<uint64_t> wpow, roots, lv, fin, gout;
+    DeviceBuf<uint64_t> gout_all;        // 2k factors by position (lazy: patterns that lose data AND parity), valid for the current pattern if gout_all_valid
     bool gout_all_valid = false;
-    uint32_t* erased = nullptr;
-    uint8_t* state = nullptr;
-    uint64_t* work = nullptr;          // 2k blocks (lazy)
-    Path* half = nullptr;              // size k, 6-level MID: the DIT passes and tables of the folded transform (gf61_path.hpp: encode_fold)
-    uint64_t* rec = nullptr;           // k blocks: x p'(x) at the data positions, written by the folded transform (lazy)
-    uint64_t* again = nullptr;         // k parity blocks of the re-encode (lazy, repair only)
-    uint64_t* stage = nullptr;         // data + parity stripes of a host-memory call (lazy)
+    DeviceBuf<uint32_t> erased;
+    DeviceBuf<uint8_t> state;
+    DeviceBuf<uint64_t> work;            // 2k blocks (lazy)
+    PathPtr half;                        // size k, 6-level MID: the DIT passes and tables of the folded transform (gf61_path.hpp: encode_fold)
+    DeviceBuf<uint64_t> rec;             // k blocks: x p'(x) at the data positions, written by the folded transform (lazy)
+    DeviceBuf<uint64_t> again;           // k parity blocks of the re-encode (lazy, repair only)
+    DeviceBuf<uint64_t> stage;           // data + parity stripes of a host-memory call (lazy)
     // even / odd split ((2k,k) codes, k >= 2^11; the scheme of decode.hip's header): the data chain runs on `splitp`, a size-k path with the factor
     // (2m + k) / 2k; of the parity half only the blocks at multiples of 2^split_shift are used (the others count as erased in the locator), so its
     // DIF is the DIF of k >> shift rows (`small[shift]`, its stripe `small_buf`) and MID reads block p >> shift of it.
@@ -717,60 +708,43 @@ struct Decoder {
     // and up to n - k erasures (T = k << e roots in the locator's tree)
     int e = 1;
     uint64_t M = 0;                      // parity blocks: (2^e - 1) k
-    uint32_t* srcmap = nullptr;          // e > 1: position -> block (bit 31: parity stripe)
-    uint8_t* parity_lost = nullptr;      // e > 1: M flags, the caller's lost parity blocks
-    uint64_t* cos_work = nullptr;        // e > 1, repair: the k-block work stripe of the re-encode
-    Path* splitp = nullptr;
+    DeviceBuf<uint32_t> srcmap;          // e > 1: position -> block (bit 31: parity stripe)
+    DeviceBuf<uint8_t> parity_lost;      // e > 1: M flags, the caller's lost parity blocks
+    DeviceBuf<uint64_t> cos_work;        // e > 1, repair: the k-block work stripe of the re-encode
+    PathPtr splitp;
     bool split_unavailable = false;      // no such plan / no memory: the folded 2k-point transform serves
-    Path* small[6] = {};
-    uint64_t* small_buf = nullptr;       // small_rows blocks (grown on demand: k >> shift)
-    uint64_t small_rows = 0;
-    uint64_t* split_af = nullptr;        // k elements by position: -1/2 w^(-bitrev(p))
-    uint64_t* split_work = nullptr;      // k blocks: the data chain's intermediate stripe
-    uint8_t* state_real = nullptr;       // the caller's flags (the locator's `state` counts unused parity blocks as lost)
+    PathPtr small[6];
+    DeviceBuf<uint64_t> small_buf;       // k >> shift blocks (grown on demand)
+    DeviceBuf<uint64_t> split_af;        // k elements by position: -1/2 w^(-bitrev(p))
+    DeviceBuf<uint64_t> split_work;      // k blocks: the data chain's intermediate stripe
+    DeviceBuf<uint8_t> state_real;       // the caller's flags (the locator's `state` counts unused parity blocks as lost)
     uint32_t lost_coset_mask = 0;        // n = 4k / 8k: bit t set = coset t (parity blocks [t k, (t+1) k)) has lost a block: fastecc_repair re-encodes those cosets only
     // fastecc_repair through the split: a second MID + DIT chain over the same two halves gives x p'(x) at the odd positions — the lost parity blocks
-    uint64_t* split_q2 = nullptr;        // k blocks: q~ as the data chain's MID leaves it after its first half (lazy)
-    uint64_t* split_pos_odd = nullptr;   // k elements by position: -1/2 w^(+bitrev(p))
-    uint64_t* gout_par = nullptr;        // k elements by parity block: 1 / (w^(2j+1) l'(w^(2j+1))) where the caller lost block j, else 0
+    DeviceBuf<uint64_t> split_q2;        // k blocks: q~ as the data chain's MID leaves it after its first half (lazy)
+    DeviceBuf<uint64_t> split_pos_odd;   // k elements by position: -1/2 w^(+bitrev(p))
+    DeviceBuf<uint64_t> gout_par;        // k elements by parity block: 1 / (w^(2j+1) l'(w^(2j+1))) where the caller lost block j, else 0
     bool split_repair_ready = false;
     bool split_pos_odd_built = false;
     int split_shift = 0;
     bool split_ready = false;
     uint64_t erased_data = 0, erased_parity = 0;
-    bool built = false;  // contexts, buffers and the w^u table exist
+    bool built = false;                  // contexts, buffers and the w^u table exist
     // few losses: the direct path
     int direct = 0, direct_pad = 0;      // its outputs (0: the transform path) and their number rounded up to a power of two
     uint64_t direct_nc = 0;              // positions of the code the direct path works in (2k; NC unless e > 1)
     int direct_ed = 0;                   // ... of its outputs the first direct_ed are the lost data blocks
     uint64_t direct_rows = 0;            // ... and its rows: the k data blocks, then direct_ed parity blocks
-    uint32_t* direct_coef = nullptr;     // [NC][pad][COEF_WORDS]: the limbs of each weight
-    uint64_t direct_coef_elems = 0;
-    uint64_t* direct_inv = nullptr;      // the table kernels' parameters (3 DIRECT_MAX elements) and the parity nodes' weights
-    uint32_t* direct_pos = nullptr;      // [0, MAX) output positions, [MAX, 2 MAX) the parity nodes' rows
-    uint64_t* direct_partial = nullptr;  // [chunks + DIRECT_SEGS][pad][elems] elements
-    uint64_t direct_partial_elems = 0;
-    uint64_t* direct_wpow = nullptr;     // the w^u table when only this path has been used (else d->wpow)
+    DeviceBuf<uint32_t> direct_coef;     // [NC][pad][COEF_WORDS]: the limbs of each weight
+    DeviceBuf<uint64_t> direct_inv;      // the table kernels' parameters (3 DIRECT_MAX elements) and the parity nodes' weights
+    DeviceBuf<uint32_t> direct_pos;      // [0, MAX) output positions, [MAX, 2 MAX) the parity nodes' rows
+    DeviceBuf<uint64_t> direct_partial;  // [chunks + DIRECT_SEGS][pad][elems] elements
+    DeviceBuf<uint64_t> direct_wpow;     // the w^u table when only this path has been used (else d->wpow)
     bool ready = false;
 };
 
 bool decoder_ready(const Decoder* d) { return d && d->ready; }
 
-void destroy_decoder(Decoder* d)
-{
-    if (!d) return;
-    for (Path* p : {d->transform, d->half, d->pattern, d->narrow_tree, d->narrow_tree_inv, d->narrow_pattern, d->splitp}) destroy(p);
-    for (const std::vector<Path*>* level : {&d->tree, &d->tree_inv})
-        for (Path* p : *level) destroy(p);
-    for (Path* p : d->small) destroy(p);
-    for (void* b : {(void*)d->tree_x, (void*)d->tree_y, (void*)d->tree_f, (void*)d->wpow, (void*)d->roots, (void*)d->lv, (void*)d->fin, (void*)d->gout,
-                    (void*)d->gout_all, (void*)d->erased, (void*)d->state, (void*)d->work, (void*)d->rec, (void*)d->again, (void*)d->stage, (void*)d->srcmap,
-                    (void*)d->parity_lost, (void*)d->cos_work, (void*)d->small_buf, (void*)d->split_af, (void*)d->split_work, (void*)d->state_real,
-                    (void*)d->split_q2, (void*)d->split_pos_odd, (void*)d->gout_par, (void*)d->direct_coef, (void*)d->direct_inv, (void*)d->direct_pos,
-                    (void*)d->direct_partial, (void*)d->direct_wpow})
-        if (b) (void)hipFree(b);
-    delete d;
-}
+void destroy_decoder(Decoder* d) { delete d; }
 
 namespace {
 
@@ -925,8 +899,7 @@ struct Prepare {
             } else {
                 if (rc != FASTECC_E_NOMEM && rc != FASTECC_E_UNSUPPORTED) return rc;
                 forget_error();
-                destroy(d->splitp);
-                d->splitp = nullptr;
+                d->splitp.reset();
                 d->split_unavailable = true;  // (the pattern stays as it is: the folded transform decodes it)
             }
         }
@@ -1034,10 +1007,8 @@ struct Prepare {
         if (s.erased_parity == 0) {
             // fastecc_repair's re-encode stripes (n - k and, for n = 4k / 8k, k more blocks: up to 32 + 8 GiB at 2^17 x 64 KB) are only held while the
             // pattern has lost parity blocks; the caller has waited for the last call that used them
-            for (uint64_t** b : {&d->again, &d->cos_work}) {
-                if (*b) (void)hipFree(*b);
-                *b = nullptr;
-            }
+            d->again.reset();
+            d->cos_work.reset();
         }
         d->split_ready = false;
         d->split_repair_ready = false;
@@ -1051,7 +1022,7 @@ struct Prepare {
     // e > 1: the caller's lost parity blocks by number and the cosets that have one (what fastecc_repair re-encodes)
     int upload_parity_flags()
     {
-        if (!d->parity_lost) HIP_TRY(hipMalloc((void**)&d->parity_lost, M));
+        RC_TRY(d->parity_lost.alloc(M));
         HIP_TRY(hipMemcpyAsync(d->parity_lost, s.parity_lost.data(), M, hipMemcpyHostToDevice, nullptr));
         d->lost_coset_mask = 0;
         for (uint64_t q = 0; q < M; q++)
@@ -1069,28 +1040,25 @@ struct Prepare {
         DirectWeights w;
         if (!direct_weights(code, w)) return FASTECC_E_INVAL;
         const uint64_t Nd = code.NC / 2;
-        uint64_t* wp = code.inner ? d->direct_wpow : d->built ? d->wpow : d->direct_wpow;
+        uint64_t* wp = code.inner ? d->direct_wpow.get() : d->built ? d->wpow.get() : d->direct_wpow.get();
         if (!wp) {
             // the table becomes visible to later calls only once it has been filled
             const Elem root = gf61::h_root(code.NC);
-            uint64_t* fresh = nullptr;
-            HIP_TRY(hipMalloc((void**)&fresh, code.NC * 16));
-            hipLaunchKernelGGL(k_wpow, grid_of(code.NC), dim3(256), 0, s0, fresh, root.re, root.im, (uint32_t)code.NC);
-            hipError_t filled = hipGetLastError();
-            if (filled == hipSuccess) filled = hipStreamSynchronize(s0);
-            if (filled != hipSuccess) {
-                (void)hipFree(fresh);
-                return hip_fail(filled, "k_wpow");
-            }
-            d->direct_wpow = wp = fresh;
+            DeviceBuf<uint64_t> fresh;
+            RC_TRY(fresh.alloc(2 * code.NC));
+            hipLaunchKernelGGL(k_wpow, grid_of(code.NC), dim3(256), 0, s0, fresh.get(), root.re, root.im, (uint32_t)code.NC);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(s0));
+            wp = fresh;
+            d->direct_wpow = std::move(fresh);
         }
         // [k + ed][pad] weights: sized for this pattern's pad (0.5 GiB instead of 16 GiB at k = 2^24 for one lost block), grown on demand
         const uint64_t rows = Nd + (uint64_t)w.ed;
         const uint64_t chunks = (rows + DIRECT_ROWS - 1) / DIRECT_ROWS;
-        HIP_TRY(grow(&d->direct_coef, &d->direct_coef_elems, (rows + 4) * (uint64_t)w.pad, COEF_WORDS * 4));  // (k_direct_accumulate fetches the rows of a trip together)
-        if (!d->direct_inv) HIP_TRY(hipMalloc((void**)&d->direct_inv, (6 * DIRECT_MAX + 2 * DIRECT_MAX * DIRECT_MAX) * 8));  // the parameters, the nodes' weights
-        if (!d->direct_pos) HIP_TRY(hipMalloc((void**)&d->direct_pos, 2 * DIRECT_MAX * 4));
-        HIP_TRY(grow(&d->direct_partial, &d->direct_partial_elems, (chunks + DIRECT_SEGS) * w.pad * elems, 16));
+        RC_TRY(d->direct_coef.grow((rows + 4) * (uint64_t)w.pad * COEF_WORDS));  // (k_direct_accumulate fetches the rows of a trip together)
+        RC_TRY(d->direct_inv.alloc(6 * DIRECT_MAX + 2 * DIRECT_MAX * DIRECT_MAX));  // the parameters, the nodes' weights
+        RC_TRY(d->direct_pos.alloc(2 * DIRECT_MAX));
+        RC_TRY(d->direct_partial.grow((chunks + DIRECT_SEGS) * w.pad * elems * 2));
         HIP_TRY(hipMemcpyAsync(d->direct_pos, w.lists.data(), 2 * DIRECT_MAX * 4, hipMemcpyHostToDevice, s0));
         HIP_TRY(hipMemcpyAsync(d->direct_inv, w.params.data(), 6 * DIRECT_MAX * 8, hipMemcpyHostToDevice, s0));
         HIP_TRY(hipMemsetAsync(d->direct_coef + rows * w.pad * COEF_WORDS, 0, 4ull * w.pad * COEF_WORDS * 4, s0));  // (the four spare rows)
@@ -1118,48 +1086,48 @@ struct Prepare {
         // whose DIT passes finish the folded transform (encode_fold); where no such pair of plans exists all 2k outputs are computed
         // (n = 4k: every FOURTH position — the size-4k transform's 7-level MID pairs with the 5-level MID of a size-k path; n = 8k: every fourth
         //  position as well, with a size-2k path: 2k outputs instead of 8k, the data at the even ones)
-        int rc = create_transform_mid(&d->transform, log2k + e, elems, FACTOR_INDEX, 7, detail, cap);
+        int rc = create_transform_mid(d->transform.fill(), log2k + e, elems, FACTOR_INDEX, 7, detail, cap);
         ptb.mark("transform path");
-        if (rc == FASTECC_OK && log2k >= 6) rc = create_transform_mid(&d->half, e == 3 ? log2k + 1 : log2k, elems, FACTOR_ENCODE, e == 1 ? 6 : 5, detail, cap);
+        if (rc == FASTECC_OK && log2k >= 6) rc = create_transform_mid(d->half.fill(), e == 3 ? log2k + 1 : log2k, elems, FACTOR_ENCODE, e == 1 ? 6 : 5, detail, cap);
         if (rc == FASTECC_OK && e >= 2 && !(fold_caps(d->transform, d->half) & FOLD_PAIRS)) {
             // the two plans do not pair up at this size: the transform keeps its own choice of MID and computes all n outputs
-            destroy(d->transform);
-            d->transform = nullptr;
-            destroy(d->half);
-            d->half = nullptr;
-            rc = create_transform_mid(&d->transform, log2k + e, elems, FACTOR_INDEX, 0, detail, cap);
+            d->transform.reset();
+            d->half.reset();
+            rc = create_transform_mid(d->transform.fill(), log2k + e, elems, FACTOR_INDEX, 0, detail, cap);
         }
         ptb.mark("half path");
         // (of these paths only the stand-alone transform is used; few columns: the upper row bits by a path of CHUNK columns, the rest by k_chunk_dif)
-        if (rc == FASTECC_OK) rc = narrow_pattern ? create(&d->narrow_pattern, log2k + e + 1 - CHUNK_LOG, CHUNK, detail, cap) : create(&d->pattern, log2k + e, 2, detail, cap);
+        if (rc == FASTECC_OK) rc = narrow_pattern ? create(d->narrow_pattern.fill(), log2k + e + 1 - CHUNK_LOG, CHUNK, detail, cap) : create(d->pattern.fill(), log2k + e, 2, detail, cap);
         ptb.mark("pattern path");
         if (rc != FASTECC_OK) return rc;
-        d->tree.assign(lgT, nullptr);
-        d->tree_inv.assign(lgT, nullptr);
+        d->tree.clear();
+        d->tree_inv.clear();
+        d->tree.resize(lgT);
+        d->tree_inv.resize(lgT);
         for (int k = leaf_log; k < lgT; k++) {
             const bool few = (T >> k) <= NARROW_COLUMNS;
-            if (!(narrow_tree && few)) rc = create(&d->tree[k], k + 1, T >> k, detail, cap);
-            if (rc == FASTECC_OK && !(narrow_tree_inv && few)) rc = create(&d->tree_inv[k], k + 1, T >> (k + 1), detail, cap);
+            if (!(narrow_tree && few)) rc = create(d->tree[k].fill(), k + 1, T >> k, detail, cap);
+            if (rc == FASTECC_OK && !(narrow_tree_inv && few)) rc = create(d->tree_inv[k].fill(), k + 1, T >> (k + 1), detail, cap);
             if (rc != FASTECC_OK) return rc;
         }
         if (narrow_tree && lgT > leaf_log) {
-            rc = create(&d->narrow_tree, lgT + 1 - CHUNK_LOG, CHUNK, detail, cap);
-            if (rc == FASTECC_OK && narrow_tree_inv) rc = create(&d->narrow_tree_inv, lgT - CHUNK_LOG, CHUNK, detail, cap);
+            rc = create(d->narrow_tree.fill(), lgT + 1 - CHUNK_LOG, CHUNK, detail, cap);
+            if (rc == FASTECC_OK && narrow_tree_inv) rc = create(d->narrow_tree_inv.fill(), lgT - CHUNK_LOG, CHUNK, detail, cap);
             if (rc != FASTECC_OK) return rc;
         }
         ptb.mark("tree paths");
         d->T = T;
-        HIP_TRY(hipMalloc((void**)&d->tree_x, 2 * T * 16));
-        HIP_TRY(hipMalloc((void**)&d->tree_y, 2 * T * 16));
-        HIP_TRY(hipMalloc((void**)&d->tree_f, 2 * T * 16));
-        HIP_TRY(hipMalloc((void**)&d->wpow, NC * 16));
-        HIP_TRY(hipMalloc((void**)&d->roots, T * 16));
-        HIP_TRY(hipMalloc((void**)&d->lv, NC * 32));
-        HIP_TRY(hipMalloc((void**)&d->fin, NC * 16));
-        HIP_TRY(hipMalloc((void**)&d->gout, N * 16));
-        HIP_TRY(hipMalloc((void**)&d->erased, (T + 1) * 4));  // the list and its counter
-        HIP_TRY(hipMalloc((void**)&d->state, NC));
-        if (e > 1) HIP_TRY(hipMalloc((void**)&d->srcmap, NC * 4));
+        RC_TRY(d->tree_x.alloc(4 * T));
+        RC_TRY(d->tree_y.alloc(4 * T));
+        RC_TRY(d->tree_f.alloc(4 * T));
+        RC_TRY(d->wpow.alloc(2 * NC));
+        RC_TRY(d->roots.alloc(2 * T));
+        RC_TRY(d->lv.alloc(4 * NC));
+        RC_TRY(d->fin.alloc(2 * NC));
+        RC_TRY(d->gout.alloc(2 * N));
+        RC_TRY(d->erased.alloc(T + 1));  // the list and its counter
+        RC_TRY(d->state.alloc(NC));
+        if (e > 1) RC_TRY(d->srcmap.alloc(NC));
         const Elem w = gf61::h_root(NC);
         hipLaunchKernelGGL(k_wpow, grid_of(NC), dim3(256), 0, nullptr, d->wpow, w.re, w.im, (uint32_t)NC);
         HIP_TRY(hipGetLastError());
@@ -1172,7 +1140,7 @@ struct Prepare {
     int set_pattern()
     {
         HIP_TRY(hipMemcpyAsync(d->state, s.state.data(), NC, hipMemcpyHostToDevice, s0));
-        if (!d->state_real) HIP_TRY(hipMalloc((void**)&d->state_real, NC));
+        RC_TRY(d->state_real.alloc(NC));
         HIP_TRY(hipMemcpyAsync(d->state_real, d->state, NC, hipMemcpyDeviceToDevice, s0));
         if (s.split_shift != 0) {
             hipLaunchKernelGGL(k_mark_unused, grid_of(N), dim3(256), 0, s0, d->state, (uint32_t)N, (1u << s.split_shift) - 1u);
@@ -1191,22 +1159,20 @@ struct Prepare {
         const int h = s.split_shift;
         if (!d->splitp) {
             for (int mid : {5, 6, 0}) {  // MID with the addend is leanest at 5 or 6 levels (78 VGPRs; the 7-level one spills)
-                if (d->splitp) destroy(d->splitp);
-                d->splitp = nullptr;
-                const int rc = create_transform_mid(&d->splitp, log2k, elems, FACTOR_SPLIT, mid, detail, cap);
+                const int rc = create_transform_mid(d->splitp.fill(), log2k, elems, FACTOR_SPLIT, mid, detail, cap);
                 if (rc != FASTECC_OK) return rc;
                 if (split_decode_supported(d->splitp)) break;
             }
             if (!split_decode_supported(d->splitp)) return FASTECC_E_UNSUPPORTED;
         }
         if (!d->split_af) {
-            HIP_TRY(hipMalloc((void**)&d->split_af, N * 16));
+            RC_TRY(d->split_af.alloc(2 * N));
             const int rc = split_addend_factors(d->split_af, log2k, s0);
             if (rc != FASTECC_OK) return rc;
         }
-        if (!d->split_work) HIP_TRY(hipMalloc((void**)&d->split_work, N * elems * 16));
-        HIP_TRY(grow(&d->small_buf, &d->small_rows, N >> h, elems * 16));
-        if (!d->small[h]) return create(&d->small[h], log2k - h, elems, detail, cap);  // only its stand-alone transform's DIF passes are used
+        RC_TRY(d->split_work.alloc(N * elems * 2));
+        RC_TRY(d->small_buf.grow((N >> h) * elems * 2));
+        if (!d->small[h]) return create(d->small[h].fill(), log2k - h, elems, detail, cap);  // only its stand-alone transform's DIF passes are used
         return FASTECC_OK;
     }
 
@@ -1238,14 +1204,14 @@ struct Prepare {
         uint64_t *a = d->tree_x, *b = d->tree_f, *c = d->tree_y;
         for (int k = leaf_log; k < lgT; k++) {
             const uint64_t deg = 1ull << k, m = T >> k;
-            const bool few = d->tree[k] == nullptr;  // few columns: narrow()
+            const bool few = !d->tree[k];  // few columns: narrow()
             int rc = few ? narrow(d->narrow_tree, k + 1, lgT - k, a, b, false)
                          : dif_only_to(d->tree[k], a, b, false, s0, nullptr);  // all m polynomials at once, a -> b (a survives for the combine step); no reordering pass
             if (rc != FASTECC_OK) return rc;
             const Elem scale = gf61::h_inv(Elem{(2 * deg) % P, 0});
             hipLaunchKernelGGL(k_pairs, grid_of(deg * m), dim3(256), 0, s0, b, c, (uint32_t)m, deg * m, scale.re, scale.im, k + 1);
             HIP_TRY(hipGetLastError());
-            rc = d->tree_inv[k] == nullptr ? narrow(d->narrow_tree_inv, k + 1, lgT - k - 1, c, c, true) : dif_only(d->tree_inv[k], c, true, s0, nullptr);  // the m/2 products, left in bit-reversed row order
+            rc = !d->tree_inv[k] ? narrow(d->narrow_tree_inv, k + 1, lgT - k - 1, c, c, true) : dif_only(d->tree_inv[k], c, true, s0, nullptr);  // the m/2 products, left in bit-reversed row order
             if (rc != FASTECC_OK) return rc;
             const bool top = k + 1 == lgT;
             const uint64_t rows = top ? 2 * deg : 4 * deg;
@@ -1269,32 +1235,29 @@ struct Prepare {
         d->gout_all_valid = false;
         if (s.erased_data != 0 && s.erased_parity != 0 && e == 1) {  // fastecc_repair can then rebuild everything in one transform (no memory for the table: decode + encode)
             // (with the split the locator counts the unused parity blocks as lost: the table then only feeds gout_par below)
-            if (!d->gout_all && hipMalloc((void**)&d->gout_all, NC * 16) != hipSuccess) {
-                (void)hipGetLastError();
-                d->gout_all = nullptr;
-            }
+            if (d->gout_all.try_alloc(2 * NC) != hipSuccess) (void)hipGetLastError();
             d->gout_all_valid = d->gout_all != nullptr;
         }
         hipLaunchKernelGGL(k_finish, grid_of(NC), dim3(256), 0, s0, d->lv, d->state, d->wpow, d->fin, d->gout, (uint32_t)NC, (uint32_t)(T - n_erased),
-                           d->gout_all_valid ? d->gout_all : nullptr, e, log2k + e);
+                           d->gout_all_valid ? d->gout_all.get() : nullptr, e, log2k + e);
         // the inversions: one per position the CALLER lost.  The split's list also holds the parity blocks it leaves aside (their factors are never
         // read: k_gout_par takes those of state_real's lost blocks), so its pattern gets a list of its own, in a tree buffer (all three are free by now)
         const uint32_t* lost_list = d->erased;
         uint64_t lost_count = n_erased;
         if (s.split_shift != 0) {
-            uint32_t* scratch = reinterpret_cast<uint32_t*>(d->tree_y);  // NC positions and the counter: 4 (NC + 1) <= 32 T bytes
+            uint32_t* scratch = reinterpret_cast<uint32_t*>(d->tree_y.get());  // NC positions and the counter: 4 (NC + 1) <= 32 T bytes
             HIP_TRY(hipMemsetAsync(scratch + NC, 0, 4, s0));
             hipLaunchKernelGGL(k_erased_list, grid_of((NC + 15) / 16), dim3(256), 0, s0, d->state_real, (uint32_t)NC, scratch, scratch + NC);
             lost_list = scratch;
             lost_count = s.erased_data + s.erased_parity;
         }
         hipLaunchKernelGGL(k_finish_lost, grid_of(lost_count), dim3(256), 0, s0, d->lv, lost_list, (uint32_t)lost_count, d->wpow, d->gout, (uint32_t)NC,
-                           (uint32_t)(T - n_erased), d->gout_all_valid ? d->gout_all : nullptr, e, log2k + e);
+                           (uint32_t)(T - n_erased), d->gout_all_valid ? d->gout_all.get() : nullptr, e, log2k + e);
         HIP_TRY(hipGetLastError());
         if (d->split_ready && d->gout_all_valid) {
             // the second chain's tables: the factor of q~ by position (once) and the lost parity blocks' output factors (this pattern)
-            const hipError_t e1 = d->split_pos_odd ? hipSuccess : hipMalloc((void**)&d->split_pos_odd, N * 16);
-            const hipError_t e2 = e1 != hipSuccess ? e1 : d->gout_par ? hipSuccess : hipMalloc((void**)&d->gout_par, N * 16);
+            const hipError_t e1 = d->split_pos_odd.try_alloc(2 * N);
+            const hipError_t e2 = e1 != hipSuccess ? e1 : d->gout_par.try_alloc(2 * N);
             if (e2 == hipSuccess) {
                 if (!d->split_pos_odd_built) {
                     const int rc2 = split_addend_factors(d->split_pos_odd, log2k, s0, true);
@@ -1374,7 +1337,7 @@ struct StripeDecode {
     // blocks, each times its factor — in its last; no fold, no second encode.  *done = false: the plan has no such tiles.
     int repair_one_transform(bool* done)
     {
-        if (!d->work) HIP_TRY(hipMalloc((void**)&d->work, d->NC * d->elems * 16));
+        RC_TRY(d->work.alloc(d->NC * d->elems * 2));
         const int rc = encode_ends(d->transform, data, parity, d->fin, d->work, d->gout_all, data, parity, s0, hooks);
         *done = rc == FASTECC_OK;
         return rc == FASTECC_E_UNSUPPORTED ? FASTECC_OK : rc;
@@ -1392,13 +1355,12 @@ struct StripeDecode {
         int rc = dif_only(d->small[h], d->small_buf, true, s0, hooks);
         // (repair: the data chain also stores q~, and a second MID + DIT chain turns it and the same r~ into the lost parity blocks)
         bool second = rebuild && d->split_repair_ready;
-        if (second && !d->split_q2 && hipMalloc((void**)&d->split_q2, d->N * d->elems * 16) != hipSuccess) {
+        if (second && d->split_q2.try_alloc(d->N * d->elems * 2) != hipSuccess) {
             (void)hipGetLastError();
-            d->split_q2 = nullptr;
             second = false;  // no room for the extra stripe: the lost parity is re-encoded
         }
         if (rc == FASTECC_OK)
-            rc = split_decode(d->splitp, data, d->fin, 2, d->small_buf, h, d->split_af, d->split_work, d->gout, data, s0, hooks, second ? d->split_q2 : nullptr);
+            rc = split_decode(d->splitp, data, d->fin, 2, d->small_buf, h, d->split_af, d->split_work, d->gout, data, s0, hooks, second ? d->split_q2.get() : nullptr);
         if (rc != FASTECC_OK && rc != FASTECC_E_UNSUPPORTED) return rc;
         *data_done = rc == FASTECC_OK;
         if (*data_done && second) {
@@ -1416,7 +1378,7 @@ struct StripeDecode {
     // transform leaves 2k rows, the data at the even ones (k_scatter takes every second: no fused scatter)
     int transform_data()
     {
-        if (!d->work) HIP_TRY(hipMalloc((void**)&d->work, d->NC * d->elems * 16));
+        RC_TRY(d->work.alloc(d->NC * d->elems * 2));
         const int rec_shift = d->e == 3 ? 1 : 0;  // the folded transform leaves k << rec_shift rows
         const int caps = d->half ? fold_caps(d->transform, d->half) : 0;
         const bool folded = (caps & FOLD_PAIRS) != 0, fused_gather = folded && (caps & FOLD_GATHERS), fused_scatter = folded && (caps & FOLD_SCATTERS) && rec_shift == 0;
@@ -1427,12 +1389,12 @@ struct StripeDecode {
             HIP_TRY(hipGetLastError());
         }
         if (folded) {
-            if (!d->rec) HIP_TRY(hipMalloc((void**)&d->rec, (d->N << rec_shift) * d->elems * 16));
+            RC_TRY(d->rec.alloc((d->N << rec_shift) * d->elems * 2));
             FoldEnds ends;
             if (fused_gather) {
                 ends.parity = parity;
                 ends.fin = d->fin;
-                ends.map = d->e > 1 ? d->srcmap : nullptr;
+                ends.map = d->e > 1 ? d->srcmap.get() : nullptr;
             }
             if (fused_scatter) {
                 ends.gout = d->gout;
@@ -1456,7 +1418,7 @@ struct StripeDecode {
     // (2k,k): the lost parity blocks from the encoder again, on the repaired data
     int reencode_parity()
     {
-        if (!d->again) HIP_TRY(hipMalloc((void**)&d->again, d->N * d->elems * 16));
+        RC_TRY(d->again.alloc(d->N * d->elems * 2));
         const int rc = encode(rebuild_with, data, d->again, s0, hooks);
         if (rc != FASTECC_OK) return rc;
         const RowGrid g(d->N, elems);
@@ -1469,8 +1431,8 @@ struct StripeDecode {
     int rebuild_cosets(uint32_t coset_mask, bool first_coset_done)
     {
         if (cosets_of(rebuild_with) != (1 << d->e) - 1) return FASTECC_E_INVAL;
-        if (!d->again) HIP_TRY(hipMalloc((void**)&d->again, d->M * d->elems * 16));
-        if (encode_cosets_needs_work(rebuild_with) && !d->cos_work) HIP_TRY(hipMalloc((void**)&d->cos_work, d->N * d->elems * 16));
+        RC_TRY(d->again.alloc(d->M * d->elems * 2));
+        if (encode_cosets_needs_work(rebuild_with)) RC_TRY(d->cos_work.alloc(d->N * d->elems * 2));
         const int rc = encode_cosets(rebuild_with, data, d->again, d->cos_work, s0, hooks, coset_mask);
         if (rc != FASTECC_OK) return rc;
         // (after the inner code's direct path the first coset's blocks are in place and `again` holds nothing for them)
@@ -1505,7 +1467,7 @@ int decode_host(Decoder* d, void* data, void* parity, Path* rebuild_with, hipStr
     const bool rebuild = rebuild_with != nullptr && d->erased_parity != 0;
     if (d->erased_data == 0 && !rebuild) return FASTECC_OK;
     const size_t stripe = d->N * d->elems * 16, pstripe = (d->e > 1 ? d->M : d->N) * d->elems * 16;
-    if (!d->stage) HIP_TRY(hipMalloc((void**)&d->stage, stripe + pstripe));
+    RC_TRY(d->stage.alloc((stripe + pstripe) / 8));
     uint64_t* ddata = d->stage;
     uint64_t* dpar = d->stage + stripe / 8;
     HIP_TRY(hipMemcpyAsync(ddata, data, stripe, hipMemcpyHostToDevice, s0));

@@ -18,7 +18,7 @@
 // The stages, in the order of this file:
 //   state        per context (scrub_state): geometry, position map, w^u, the fixed erasures' locator; the blocks named absent — one pattern
 //                (set_erasures) or a set with a pattern per stripe (set_erasures_set, section 19) — seen through Erasures: the
-//                fingerprint kernels skip them, their locator joins the fixed erasures', w fewer syndromes are checked.  Buffers only grow (grow).
+//                fingerprint kernels skip them, their locator joins the fixed erasures', w fewer syndromes are checked.  Buffers only grow (DeviceBuf::grow).
 //   one stripe   locate: fingerprints (one wave per block, dwordx4 loads; a block with a word >= p is certainly corrupt: a known erasure), syndromes
 //                (F times the erasures' locator, the stand-alone inverse transform of NC points, every coefficient above the degree bound checked
 //                for zero and the first 2 locate_max of each column gathered), Berlekamp-Massey on the host per column and the longest LFSR as the
@@ -39,6 +39,7 @@
 #include <memory>
 #include <vector>
 
+#include "devmem.hpp"
 #include "drivers.hpp"
 #include "scrub_device.hpp"
 
@@ -63,14 +64,9 @@ struct ScrubSet {
     std::vector<std::vector<uint8_t>> is_absent;  // per pattern: n flags
     std::vector<uint32_t> mlo;                    // per pattern: N + fixed + w, the first coefficient that must vanish
     uint32_t mlo_min = 0;
-    uint32_t* d_pos = nullptr;                    // P x n words: d_pos with ABSENT set at the pattern's absent blocks
-    uint32_t* d_l = nullptr;                      // P x NC words: d_lfix (or 1) times the locator of the pattern's absent positions at w^u
-    uint32_t* d_mlo = nullptr;                    // P words: mlo
-    ~ScrubSet()
-    {
-        for (void* p : {(void*)d_pos, (void*)d_l, (void*)d_mlo})
-            if (p) (void)hipFree(p);
-    }
+    DeviceBuf<uint32_t> d_pos;                    // P x n words: d_pos with ABSENT set at the pattern's absent blocks
+    DeviceBuf<uint32_t> d_l;                      // P x NC words: d_lfix (or 1) times the locator of the pattern's absent positions at w^u
+    DeviceBuf<uint32_t> d_mlo;                    // P words: mlo
 };
 
 struct ScrubState {
@@ -79,53 +75,38 @@ struct ScrubState {
     uint64_t fixed = 0;                     // positions that hold no block (fixed erasures)
     std::vector<uint32_t> pos;              // block -> position
     std::vector<uint32_t> block_at;         // position -> block, ~0u if none (fixed erasure or known-zero data block)
-    fastecc_ctx* ntt = nullptr;             // stand-alone transform of NC points, 4 words per position
-    uint32_t* d_pos = nullptr;              // n words
-    uint32_t* d_wpow = nullptr;             // NC words: w^u
-    uint32_t* d_lfix = nullptr;             // NC words: the fixed erasures' locator at w^u (null: none)
-    uint32_t* d_F = nullptr;                // NC x 4 words: fingerprints by position (zero where no block is read)
-    uint32_t* d_G = nullptr;                // NC x 4 words: weighted fingerprints, transformed in place
-    uint32_t* d_small = nullptr;            // counters and lists: [bad: 1 + n], [flag: 1], [found: 1 + cap_found], syndromes, lambda, roots
-    uint64_t small_words = 0;
-    uint2* d_weights = nullptr;             // S packed weights of the current seed
+    CtxPtr ntt;                             // stand-alone transform of NC points, 4 words per position
+    DeviceBuf<uint32_t> d_pos;              // n words
+    DeviceBuf<uint32_t> d_wpow;             // NC words: w^u
+    DeviceBuf<uint32_t> d_lfix;             // NC words: the fixed erasures' locator at w^u (null: none)
+    DeviceBuf<uint32_t> d_F;                // NC x 4 words: fingerprints by position (zero where no block is read)
+    DeviceBuf<uint32_t> d_G;                // NC x 4 words: weighted fingerprints, transformed in place
+    DeviceBuf<uint32_t> d_small;            // counters and lists: [bad: 1 + n], [flag: 1], [found: 1 + cap_found], syndromes, lambda, roots
+    DeviceBuf<uint2> d_weights;             // S packed weights of the current seed
     uint64_t weights_seed = 0;
     bool weights_valid = false;
     // fastecc_verify_batch (built at its first call): a chunk of up to batch_cap stripes as word columns of one fingerprint stripe
-    fastecc_ctx* ntt_batch = nullptr;       // stand-alone transform of NC points over rows of 4 x batch_cap words
+    CtxPtr ntt_batch;                       // stand-alone transform of NC points over rows of 4 x batch_cap words
     uint64_t batch_cap = 0;
-    uint32_t* d_FB = nullptr;               // NC x 4 batch_cap words: weighted fingerprints by position (zero where no block is read)
-    uint32_t* d_GB = nullptr;               // their transform
-    uint8_t* d_flag = nullptr;              // one byte per stripe of the call: 1 = inconsistent
-    uint64_t flag_cap = 0;
+    DeviceBuf<uint32_t> d_FB;               // NC x 4 batch_cap words: weighted fingerprints by position (zero where no block is read)
+    DeviceBuf<uint32_t> d_GB;               // their transform
+    DeviceBuf<uint8_t> d_flag;              // one byte per stripe of the call: 1 = inconsistent
     // fastecc_scrub_erasures: the blocks the caller named absent (none: empty / null)
     std::vector<uint32_t> absent;           // their codeword indices, increasing
     std::vector<uint8_t> is_absent;         // n flags
-    uint32_t* d_pos_named = nullptr;        // n words: d_pos with ABSENT set at those blocks
-    uint32_t* d_lnamed = nullptr;           // NC words: d_lfix (or 1) times the locator of their positions at w^u
+    DeviceBuf<uint32_t> d_pos_named;        // n words: d_pos with ABSENT set at those blocks
+    DeviceBuf<uint32_t> d_lnamed;           // NC words: d_lfix (or 1) times the locator of their positions at w^u
     // batched location and the list forms, all grow-only
-    uint64_t* d_list = nullptr;             // the stripes a list pass runs over
-    uint64_t list_cap = 0;
-    uint8_t* d_lflag = nullptr;             // per list entry: [0, lflag_cap) inconsistent, [lflag_cap, 2 lflag_cap) a present block held a word >= p
-    uint64_t lflag_cap = 0;                 // (grows with list_cap)
-    uint32_t* d_loc = nullptr;              // one chunk's syndromes, then its locators, their lengths and the found lists
-    uint64_t loc_words = 0;
+    DeviceBuf<uint64_t> d_list;             // the stripes a list pass runs over
+    DeviceBuf<uint8_t> d_lflag;             // per list entry: [0, lflag_cap) inconsistent, [lflag_cap, 2 lflag_cap) a present block held a word >= p
+    uint64_t lflag_cap() const { return d_lflag.capacity() / 2; }  // (grows with d_list)
+    DeviceBuf<uint32_t> d_loc;              // one chunk's syndromes, then its locators, their lengths and the found lists
     // fastecc_scrub_erasures_set: the pattern set (null: none) and the device copy of a call's pattern_of (grow-only)
-    ScrubSet* set = nullptr;
-    uint32_t* d_pattern_of = nullptr;
-    uint64_t pattern_cap = 0;
+    std::unique_ptr<ScrubSet> set;
+    DeviceBuf<uint32_t> d_pattern_of;
 };
 
-void destroy_scrub_state(ScrubState* s)
-{
-    if (!s) return;
-    if (s->ntt) fastecc_destroy(s->ntt);
-    if (s->ntt_batch) fastecc_destroy(s->ntt_batch);
-    for (void* p : {(void*)s->d_pos, (void*)s->d_wpow, (void*)s->d_lfix, (void*)s->d_F, (void*)s->d_G, (void*)s->d_small, (void*)s->d_weights, (void*)s->d_FB,
-                    (void*)s->d_GB, (void*)s->d_flag, (void*)s->d_pos_named, (void*)s->d_lnamed, (void*)s->d_list, (void*)s->d_lflag, (void*)s->d_loc, (void*)s->d_pattern_of})
-        if (p) (void)hipFree(p);
-    delete s->set;
-    delete s;
-}
+void destroy_scrub_state(ScrubState* s) { delete s; }
 
 namespace {
 
@@ -150,21 +131,9 @@ Erasures erasures(const ScrubState* s, bool named)
 // pattern q of the set: its rows of the set's tables (the locator row is lfix, or 1, for a pattern that names nothing)
 Erasures set_view(const ScrubState* s, uint32_t q)
 {
-    const ScrubSet* t = s->set;
+    const ScrubSet* t = s->set.get();
     const uint64_t w = t->absent[q].size();
     return {t->d_pos + (uint64_t)q * s->n, t->d_l + (uint64_t)q * s->NC, w, w ? &t->absent[q] : nullptr, w ? &t->is_absent[q] : nullptr};
-}
-
-// A grow-only device buffer: *p holds *cap elements of `elem` bytes and is replaced when `need` is more; a failed allocation leaves null and 0
-int grow(void** p, uint64_t* cap, uint64_t need, uint64_t elem)
-{
-    if (*cap >= need) return FASTECC_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HIP_TRY(hipMalloc(p, need * elem));
-    *cap = need;
-    return FASTECC_OK;
 }
 
 // the fingerprint kernels' vector form: whole dwordx4 loads, 16-byte aligned stripes
@@ -174,7 +143,7 @@ bool vec_form(const fastecc_ctx* c, const void* data, const void* parity)
 }
 
 // a fingerprint kernel in its vector (kv) or scalar (ks) form over `groups` workgroups of four waves
-template <class... K, class... A> void launch_fp(void (*kv)(K...), void (*ks)(K...), bool vec, uint64_t groups, hipStream_t st, A... args)
+template <class... K, class... A> void launch_fp(void (*kv)(K...), void (*ks)(K...), bool vec, uint64_t groups, hipStream_t st, const A&... args)
 {
     hipLaunchKernelGGL(vec ? kv : ks, dim3((unsigned)groups), dim3(256), 0, st, args...);
 }
@@ -199,21 +168,9 @@ int scrub_args(fastecc_ctx* c, const void* data, const void* parity, int mem_kin
     return FASTECC_OK;
 }
 
-// The context's geometry, position map, w^u table and fixed-erasure locator (once per context; synchronous).
-int scrub_state(fastecc_ctx* c, ScrubState** out)
+// The context's geometry, position map, w^u table and fixed-erasure locator (synchronous).
+int build_scrub_state(fastecc_ctx* c, ScrubState* s)
 {
-    if (c->scrub) {
-        *out = c->scrub;
-        return FASTECC_OK;
-    }
-    ScrubState* s = new (std::nothrow) ScrubState();
-    if (!s) return FASTECC_E_NOMEM;
-    c->scrub = s;  // (partially built state is freed with the context; a failed build is retried from scratch)
-    auto fail = [&](int rc) {
-        destroy_scrub_state(s);
-        c->scrub = nullptr;
-        return rc;
-    };
     int e = 1;
     while ((1 << e) < c->cosets + 1) e++;
     s->N = c->N;
@@ -221,7 +178,7 @@ int scrub_state(fastecc_ctx* c, ScrubState** out)
     s->lgc = c->n + e;
     s->k = c->K;
     s->n = c->K + c->Mu;
-    if (s->NC > (1ull << 20) || s->NC < 4) return fail(FASTECC_E_UNSUPPORTED);
+    if (s->NC > (1ull << 20) || s->NC < 4) return FASTECC_E_UNSUPPORTED;
     auto parity_position = [&](uint64_t q) -> uint64_t { return code_parity_position(c->N, e, c->fold, c->cosets, q); };
     s->pos.resize(s->n);
     s->block_at.assign(s->NC, ~0u);
@@ -238,37 +195,45 @@ int scrub_state(fastecc_ctx* c, ScrubState** out)
     for (uint64_t u = 0; u < s->NC; u++)
         if (!held[u]) fixed_roots.push_back(gf::h_pow(w, u));
     s->fixed = fixed_roots.size();
-    if (s->N + s->fixed + (s->n - s->k) != s->NC) return fail(FASTECC_E_DEVICE);  // (the layout is inconsistent: cannot happen)
+    if (s->N + s->fixed + (s->n - s->k) != s->NC) return FASTECC_E_DEVICE;  // (the layout is inconsistent: cannot happen)
 
-    const int rc = create_ntt_ctx(&s->ntt, s->lgc, 4 * RW, c->device);
-    if (rc != FASTECC_OK) return fail(rc);
+    RC_TRY(create_ntt_ctx(s->ntt.fill(), s->lgc, 4 * RW, c->device));
     const uint64_t NC = s->NC;
-    hipError_t he = hipSuccess;
     auto grid = [](uint64_t items) { return dim3((unsigned)((items + 255) / 256)); };
-    if ((he = hipMalloc((void**)&s->d_pos, s->n * 4)) != hipSuccess || (he = hipMalloc((void**)&s->d_wpow, NC * 4)) != hipSuccess ||
-        (he = hipMalloc((void**)&s->d_F, NC * RW * 4)) != hipSuccess || (he = hipMalloc((void**)&s->d_G, NC * RW * 4)) != hipSuccess)
-        return fail(hip_fail(he, "hipMalloc"));
-    if ((he = hipMemcpy(s->d_pos, s->pos.data(), s->n * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(hip_fail(he, "hipMemcpy"));
+    RC_TRY(s->d_pos.alloc(s->n));
+    RC_TRY(s->d_wpow.alloc(NC));
+    RC_TRY(s->d_F.alloc(NC * RW));
+    RC_TRY(s->d_G.alloc(NC * RW));
+    HIP_TRY(hipMemcpy(s->d_pos, s->pos.data(), s->n * 4, hipMemcpyHostToDevice));
     // positions no block is read from (fixed erasures, known-zero data blocks) keep fingerprint 0 for good
-    if ((he = hipMemset(s->d_F, 0, NC * RW * 4)) != hipSuccess) return fail(hip_fail(he, "hipMemset"));
+    HIP_TRY(hipMemset(s->d_F, 0, NC * RW * 4));
     hipLaunchKernelGGL(powers_kernel, grid(NC), dim3(256), 0, nullptr, s->d_wpow, w, (uint32_t)NC);
-    if ((he = hipGetLastError()) != hipSuccess) return fail(hip_fail(he, "powers_kernel"));
+    HIP_TRY(hipGetLastError());
     if (!fixed_roots.empty()) {
-        uint32_t* d_roots = nullptr;
-        if ((he = hipMalloc((void**)&s->d_lfix, NC * 4)) != hipSuccess || (he = hipMalloc((void**)&d_roots, fixed_roots.size() * 4)) != hipSuccess)
-            return fail(hip_fail(he, "hipMalloc"));
-        he = hipMemcpy(d_roots, fixed_roots.data(), fixed_roots.size() * 4, hipMemcpyHostToDevice);
-        if (he == hipSuccess) {
-            hipLaunchKernelGGL(locator_kernel<false>, grid(NC), dim3(256), 0, nullptr, nullptr, d_roots, (uint32_t)fixed_roots.size(), s->d_wpow,
-                               (uint32_t)NC, nullptr, s->d_lfix);
-            he = hipGetLastError();
-        }
-        if (he == hipSuccess) he = hipDeviceSynchronize();
-        (void)hipFree(d_roots);
-        if (he != hipSuccess) return fail(hip_fail(he, "locator_kernel"));
+        DeviceBuf<uint32_t> d_roots;
+        RC_TRY(s->d_lfix.alloc(NC));
+        RC_TRY(d_roots.alloc(fixed_roots.size()));
+        HIP_TRY(hipMemcpy(d_roots, fixed_roots.data(), fixed_roots.size() * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(locator_kernel<false>, grid(NC), dim3(256), 0, nullptr, nullptr, d_roots, (uint32_t)fixed_roots.size(), s->d_wpow,
+                           (uint32_t)NC, nullptr, s->d_lfix);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());  // (d_roots goes here)
     }
-    if ((he = hipDeviceSynchronize()) != hipSuccess) return fail(hip_fail(he, "hipDeviceSynchronize"));
-    *out = s;
+    HIP_TRY(hipDeviceSynchronize());
+    return FASTECC_OK;
+}
+
+// ... once per context; a failed build leaves none and is retried from scratch
+int scrub_state(fastecc_ctx* c, ScrubState** out)
+{
+    if (!c->scrub) {
+        std::unique_ptr<ScrubState> s(new (std::nothrow) ScrubState());
+        if (!s) return FASTECC_E_NOMEM;
+        const int rc = build_scrub_state(c, s.get());
+        if (rc != FASTECC_OK) return rc;
+        c->scrub = s.release();
+    }
+    *out = c->scrub;
     return FASTECC_OK;
 }
 
@@ -286,7 +251,7 @@ int small_buffers(ScrubState* s, uint32_t locate_max, Small* sm)
     sm->gather = std::min<uint64_t>(2ull * locate_max, m);
     sm->roots_cap = m + 1;
     const uint64_t words = (1 + sm->bad_cap) + 1 + (1 + sm->found_cap) + R * std::max<uint64_t>(sm->gather, 1) + (locate_max + 1) + sm->roots_cap;
-    const int rc = grow((void**)&s->d_small, &s->small_words, words, 4);
+    const int rc = s->d_small.grow(words);
     if (rc != FASTECC_OK) return rc;
     uint32_t* p = s->d_small;
     sm->bad = p;
@@ -315,7 +280,7 @@ int upload_weights(fastecc_ctx* c, ScrubState* s, uint64_t seed, hipStream_t st)
         h[2 * w + 1] = r1 | ((r2 >> 12) << 20);
     }
     s->weights_valid = false;
-    if (!s->d_weights) HIP_TRY(hipMalloc((void**)&s->d_weights, 2 * c->S * 4 + 16));
+    RC_TRY(s->d_weights.alloc(c->S + 2));  // (16 bytes past the last weight)
     HIP_TRY(hipStreamSynchronize(st));  // (the previous call's kernels are done: calls end with a synchronise; this one has enqueued nothing yet)
     HIP_TRY(hipMemcpy(s->d_weights, h.data(), 2 * c->S * 4, hipMemcpyHostToDevice));
     s->weights_seed = seed;
@@ -541,25 +506,18 @@ int batch_state(fastecc_ctx* c, ScrubState* s)
     if (s->ntt_batch) return FASTECC_OK;
     uint64_t cap = 1;
     while (cap < (1ull << 16) && s->NC * 16 * (2 * cap) <= (32ull << 20)) cap *= 2;
-    const uint64_t bytes = s->NC * RW * cap * 4;
-    fastecc_ctx* t = nullptr;
-    uint32_t *F = nullptr, *G = nullptr;
-    int rc = create_ntt_ctx(&t, s->lgc, RW * 4 * cap, c->device);
-    if (rc != FASTECC_OK) return rc;
-    hipError_t he = hipMalloc((void**)&F, bytes);
-    if (he == hipSuccess) he = hipMalloc((void**)&G, bytes);
-    if (he == hipSuccess) he = hipMemset(F, 0, bytes);
-    if (he == hipSuccess) he = hipDeviceSynchronize();  // (the call's stream may not order after the null stream)
-    if (he != hipSuccess) {
-        fastecc_destroy(t);
-        if (F) (void)hipFree(F);
-        if (G) (void)hipFree(G);
-        return hip_fail(he, "scrub batch buffers");
-    }
-    s->ntt_batch = t;
+    const uint64_t words = s->NC * RW * cap;
+    CtxPtr t;
+    DeviceBuf<uint32_t> F, G;
+    RC_TRY(create_ntt_ctx(t.fill(), s->lgc, RW * 4 * cap, c->device));
+    RC_TRY(F.alloc(words));
+    RC_TRY(G.alloc(words));
+    HIP_TRY(hipMemset(F, 0, words * 4));
+    HIP_TRY(hipDeviceSynchronize());  // (the call's stream may not order after the null stream)
+    s->ntt_batch = std::move(t);
     s->batch_cap = cap;
-    s->d_FB = F;
-    s->d_GB = G;
+    s->d_FB = std::move(F);
+    s->d_GB = std::move(G);
     return FASTECC_OK;
 }
 
@@ -587,7 +545,7 @@ int batch_begin(fastecc_ctx* c, ScrubState* s, uint64_t count, uint64_t seed, hi
 {
     int rc = batch_state(c, s);
     if (rc != FASTECC_OK) return rc;
-    if ((rc = grow((void**)&s->d_flag, &s->flag_cap, count, 1)) != FASTECC_OK) return rc;
+    if ((rc = s->d_flag.grow(count)) != FASTECC_OK) return rc;
     if ((rc = upload_weights(c, s, seed, st)) != FASTECC_OK) return rc;
     HIP_TRY(hipMemsetAsync(s->d_flag, 0, count, st));
     return FASTECC_OK;
@@ -639,7 +597,7 @@ struct ChunkForm {
 int chunk_pass(fastecc_ctx* c, ScrubState* s, const ChunkForm& f, const uint32_t* data, const uint32_t* parity, uint64_t b0, uint64_t B, hipStream_t st,
                const Probe* probe = nullptr)
 {
-    const ScrubSet* t = s->set;
+    const ScrubSet* t = s->set.get();
     const uint64_t row = RW * s->batch_cap;
     const uint32_t k = (uint32_t)s->k, n = (uint32_t)s->n, S = (uint32_t)c->S, NC = (uint32_t)s->NC, m_lo = (uint32_t)f.m_lo;
     const bool vec = vec_form(c, data, parity), list = f.fp == Fp::LIST;
@@ -655,7 +613,7 @@ int chunk_pass(fastecc_ctx* c, ScrubState* s, const ChunkForm& f, const uint32_t
             break;
         case Fp::LIST:  // flags, list and big marks from the chunk's first entry on; b0 is not used
             launch_fp(fingerprint_batch_kernel<true, true>, fingerprint_batch_kernel<false, true>, vec, groups, st, data, parity, k, n, S, (uint64_t)0, B,
-                      s->d_weights, f.er.d_pos, f.er.d_loc, s->d_FB, row, flag + b0, s->d_list + b0, flag + s->lflag_cap + b0);
+                      s->d_weights, f.er.d_pos, f.er.d_loc, s->d_FB, row, flag + b0, s->d_list + b0, flag + s->lflag_cap() + b0);
             break;
         case Fp::SET:
             launch_fp(fingerprint_set_kernel<true>, fingerprint_set_kernel<false>, vec, groups, st, data, parity, k, n, S, b0, B, s->d_weights, s->d_pattern_of,
@@ -727,11 +685,11 @@ int list_begin(fastecc_ctx* c, ScrubState* s, const std::vector<uint64_t>& list,
     const uint64_t L = list.size();
     int rc = batch_state(c, s);
     if (rc == FASTECC_OK) rc = upload_weights(c, s, seed, st);
-    if (rc == FASTECC_OK) rc = grow((void**)&s->d_list, &s->list_cap, L, 8);
-    if (rc == FASTECC_OK) rc = grow((void**)&s->d_lflag, &s->lflag_cap, L, 2);
+    if (rc == FASTECC_OK) rc = s->d_list.grow(L);
+    if (rc == FASTECC_OK) rc = s->d_lflag.grow(2 * L);
     if (rc != FASTECC_OK) return rc;
     HIP_TRY(hipMemcpyAsync(s->d_list, list.data(), L * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(s->d_lflag, 0, 2 * s->lflag_cap, st));
+    HIP_TRY(hipMemsetAsync(s->d_lflag, 0, 2 * s->lflag_cap(), st));
     return FASTECC_OK;
 }
 
@@ -751,7 +709,7 @@ int verify_list_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t* par
         for (uint64_t l0 = 0; l0 < L; l0 += chunk)
             if ((rc = chunk_pass(c, s, f, data, parity, l0, std::min(chunk, L - l0), st, probe)) != FASTECC_OK) return rc;
         flag.assign(L, 0);
-        HIP_TRY(hipMemcpyAsync(flag.data(), s->d_lflag + (probe ? s->lflag_cap : 0), L, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(flag.data(), s->d_lflag + (probe ? s->lflag_cap() : 0), L, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return FASTECC_OK;
     });
@@ -800,7 +758,7 @@ struct LocateList {
         gather = std::min<uint64_t>(2 * tmax, avail);
         stride = cap = std::min<uint64_t>(tmax, gather / 2) + 1;
         const uint64_t syn_words = chunk * R * avail, lam_words = chunk * stride, found_words = chunk * (cap + 1);
-        const int rc = grow((void**)&s->d_loc, &s->loc_words, syn_words + lam_words + chunk + found_words, 4);
+        const int rc = s->d_loc.grow(syn_words + lam_words + chunk + found_words);
         if (rc != FASTECC_OK) return rc;
         form = pattern_form(s, Fp::LIST, true, s->d_loc);
         d_lam = s->d_loc + syn_words;
@@ -817,7 +775,7 @@ struct LocateList {
         const int rc = chunk_pass(c, s, form, data, parity, l0, B, st);
         if (rc != FASTECC_OK) return rc;
         HIP_TRY(hipMemcpyAsync(syn.data(), form.syn_out, B * R * avail * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(big.data(), s->d_lflag + s->lflag_cap + l0, B, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(big.data(), s->d_lflag + s->lflag_cap() + l0, B, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return FASTECC_OK;
     }
@@ -926,11 +884,10 @@ int locate_list(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, co
 int set_erasures(fastecc_ctx* c, const std::vector<uint32_t>& absent)
 {
     ScrubState* s = c->scrub;
-    uint32_t *d_pos = nullptr, *d_loc = nullptr, *d_roots = nullptr;
+    DeviceBuf<uint32_t> d_pos, d_loc;
     std::vector<uint8_t> is_absent;
     if (!absent.empty()) {
-        const int rc = scrub_state(c, &s);
-        if (rc != FASTECC_OK) return rc;
+        RC_TRY(scrub_state(c, &s));
         std::vector<uint32_t> pos(s->pos), roots(absent.size());
         is_absent.assign(s->n, 0);
         const uint32_t w = gf::h_root((uint32_t)s->NC);
@@ -939,29 +896,20 @@ int set_erasures(fastecc_ctx* c, const std::vector<uint32_t>& absent)
             pos[absent[i]] |= ABSENT;
             is_absent[absent[i]] = 1;
         }
-        hipError_t he = hipMalloc((void**)&d_pos, s->n * 4);
-        if (he == hipSuccess) he = hipMalloc((void**)&d_loc, s->NC * 4);
-        if (he == hipSuccess) he = hipMalloc((void**)&d_roots, roots.size() * 4);
-        if (he == hipSuccess) he = hipMemcpy(d_pos, pos.data(), s->n * 4, hipMemcpyHostToDevice);
-        if (he == hipSuccess) he = hipMemcpy(d_roots, roots.data(), roots.size() * 4, hipMemcpyHostToDevice);
-        if (he == hipSuccess) {
-            hipLaunchKernelGGL(locator_kernel<false>, dim3((unsigned)((s->NC + 255) / 256)), dim3(256), 0, nullptr, s->d_lfix, d_roots, (uint32_t)roots.size(),
-                               s->d_wpow, (uint32_t)s->NC, nullptr, d_loc);
-            he = hipGetLastError();
-        }
-        if (he == hipSuccess) he = hipDeviceSynchronize();
-        if (d_roots) (void)hipFree(d_roots);
-        if (he != hipSuccess) {
-            if (d_pos) (void)hipFree(d_pos);
-            if (d_loc) (void)hipFree(d_loc);
-            return hip_fail(he, "scrub erasure tables");
-        }
+        DeviceBuf<uint32_t> d_roots;
+        RC_TRY(d_pos.alloc(s->n));
+        RC_TRY(d_loc.alloc(s->NC));
+        RC_TRY(d_roots.alloc(roots.size()));
+        HIP_TRY(hipMemcpy(d_pos, pos.data(), s->n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_roots, roots.data(), roots.size() * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(locator_kernel<false>, dim3((unsigned)((s->NC + 255) / 256)), dim3(256), 0, nullptr, s->d_lfix, d_roots, (uint32_t)roots.size(),
+                           s->d_wpow, (uint32_t)s->NC, nullptr, d_loc);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
     }
     if (!s) return FASTECC_OK;  // no scrub state yet and nothing to name
-    if (s->d_pos_named) (void)hipFree(s->d_pos_named);
-    if (s->d_lnamed) (void)hipFree(s->d_lnamed);
-    s->d_pos_named = d_pos;
-    s->d_lnamed = d_loc;
+    s->d_pos_named = std::move(d_pos);
+    s->d_lnamed = std::move(d_loc);
     s->absent = absent;
     s->is_absent.swap(is_absent);
     return FASTECC_OK;
@@ -977,14 +925,10 @@ int set_erasures_set(fastecc_ctx* c, std::vector<std::vector<uint32_t>>& absent)
     ScrubState* s = c->scrub;
     const uint64_t P = absent.size();
     if (P == 0) {
-        if (s) {
-            delete s->set;
-            s->set = nullptr;
-        }
+        if (s) s->set.reset();
         return FASTECC_OK;
     }
-    const int rc = scrub_state(c, &s);
-    if (rc != FASTECC_OK) return rc;
+    RC_TRY(scrub_state(c, &s));
     const uint64_t n = s->n, NC = s->NC;
     if (P * NC > (1ull << 24)) return FASTECC_E_UNSUPPORTED;  // the locator tables stay at most 64 MiB
     std::unique_ptr<ScrubSet> t(new (std::nothrow) ScrubSet());
@@ -1007,27 +951,21 @@ int set_erasures_set(fastecc_ctx* c, std::vector<std::vector<uint32_t>>& absent)
     }
     t->mlo_min = *std::min_element(t->mlo.begin(), t->mlo.end());
     t->absent.swap(absent);
-    uint32_t *d_roots = nullptr, *d_off = nullptr;
-    hipError_t he = hipMalloc((void**)&t->d_pos, P * n * 4);
-    if (he == hipSuccess) he = hipMalloc((void**)&t->d_l, P * NC * 4);
-    if (he == hipSuccess) he = hipMalloc((void**)&t->d_mlo, P * 4);
-    if (he == hipSuccess) he = hipMalloc((void**)&d_roots, std::max<size_t>(roots.size(), 1) * 4);
-    if (he == hipSuccess) he = hipMalloc((void**)&d_off, (P + 1) * 4);
-    if (he == hipSuccess) he = hipMemcpy(t->d_pos, pos.data(), P * n * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(t->d_mlo, t->mlo.data(), P * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess && !roots.empty()) he = hipMemcpy(d_roots, roots.data(), roots.size() * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(d_off, off.data(), (P + 1) * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(locator_set_kernel, dim3((unsigned)((NC + 255) / 256), (unsigned)P), dim3(256), 0, nullptr, s->d_lfix, d_roots, d_off, s->d_wpow, (uint32_t)NC,
-                           t->d_l);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipDeviceSynchronize();
-    if (d_roots) (void)hipFree(d_roots);
-    if (d_off) (void)hipFree(d_off);
-    if (he != hipSuccess) return hip_fail(he, "scrub erasure set tables");
-    delete s->set;
-    s->set = t.release();
+    DeviceBuf<uint32_t> d_roots, d_off;
+    RC_TRY(t->d_pos.alloc(P * n));
+    RC_TRY(t->d_l.alloc(P * NC));
+    RC_TRY(t->d_mlo.alloc(P));
+    RC_TRY(d_roots.alloc(std::max<size_t>(roots.size(), 1)));
+    RC_TRY(d_off.alloc(P + 1));
+    HIP_TRY(hipMemcpy(t->d_pos, pos.data(), P * n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(t->d_mlo, t->mlo.data(), P * 4, hipMemcpyHostToDevice));
+    if (!roots.empty()) HIP_TRY(hipMemcpy(d_roots, roots.data(), roots.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_off, off.data(), (P + 1) * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(locator_set_kernel, dim3((unsigned)((NC + 255) / 256), (unsigned)P), dim3(256), 0, nullptr, s->d_lfix, d_roots, d_off,
+                       s->d_wpow, (uint32_t)NC, t->d_l);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    s->set = std::move(t);
     return FASTECC_OK;
 }
 
@@ -1051,8 +989,8 @@ int verify_batch_set_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t
 {
     return settled(st, [&]() -> int {
         ScrubState* s = c->scrub;
-        const ScrubSet* t = s->set;
-        int rc = grow((void**)&s->d_pattern_of, &s->pattern_cap, count, 4);
+        const ScrubSet* t = s->set.get();
+        int rc = s->d_pattern_of.grow(count);
         if (rc != FASTECC_OK) return rc;
         HIP_TRY(hipMemcpy(s->d_pattern_of, pattern_of, count * 4, hipMemcpyHostToDevice));
         if ((rc = batch_begin(c, s, count, seed, st)) != FASTECC_OK) return rc;
@@ -1161,15 +1099,6 @@ int report(const std::vector<uint32_t>& found, uint64_t* blocks, uint64_t cap, u
     return FASTECC_OK;
 }
 
-// a list the repair launches read, on the device for one call only (the repair runs outside the scrub state's lock)
-struct DeviceList {
-    uint64_t* p = nullptr;
-    ~DeviceList()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
-
 // fastecc_correct_batch (arguments checked): the locked verify and location, then — grouped — one prepare and one list-form repair per distinct lost
 // set and one closing verify for all of them, and fastecc_correct stripe by stripe for whatever that leaves
 struct CorrectBatch {
@@ -1186,7 +1115,7 @@ struct CorrectBatch {
     std::vector<std::vector<uint32_t>> lost_sets;  // per group: located and absent blocks, sorted
     std::vector<std::vector<uint64_t>> members;    // per group: its stripes
     std::vector<uint64_t> order;                   // the groups' stripes back to back: group g at its offset
-    DeviceList dev_order;
+    DeviceBuf<uint64_t> dev_order;                 // ... on the device for this call only (the repair runs outside the scrub state's lock)
     std::vector<uint8_t> status;
     bool uncorrectable = false;
 
@@ -1237,13 +1166,13 @@ struct CorrectBatch {
     // one fastecc_decode_prepare and one list-form repair per group (both take the lock themselves)
     int repair_groups()
     {
-        HIP_TRY(hipMalloc((void**)&dev_order.p, order.size() * 8));
-        HIP_TRY(hipMemcpy(dev_order.p, order.data(), order.size() * 8, hipMemcpyHostToDevice));
+        RC_TRY(dev_order.alloc(order.size()));
+        HIP_TRY(hipMemcpy(dev_order, order.data(), order.size() * 8, hipMemcpyHostToDevice));
         uint64_t at = 0;
         for (size_t g = 0; g < members.size(); g++) {
             int r = prepare_lost(c, lost_sets[g]);
             if (r != FASTECC_OK) return r;
-            if ((r = repair_list(c, data, parity, order.data() + at, dev_order.p + at, members[g].size(), stream)) != FASTECC_OK) return r;
+            if ((r = repair_list(c, data, parity, order.data() + at, dev_order + at, members[g].size(), stream)) != FASTECC_OK) return r;
             at += members[g].size();
         }
         return FASTECC_OK;

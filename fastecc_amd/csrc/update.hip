@@ -30,6 +30,7 @@
 #include <atomic>
 #include <vector>
 
+#include "devmem.hpp"
 #include "drivers.hpp"
 #include "lazy96.hpp"
 #include "ntt_device.hpp"
@@ -407,31 +408,16 @@ struct UpdateState {
     CodeGeom g;
     uint64_t NC = 0;
     uint32_t tshift = 0;
-    uint32_t* d_G = nullptr;  // weight table, (NC >> tshift) words
+    DeviceBuf<uint32_t> d_G;  // weight table, (NC >> tshift) words
     bool table_ready = false, table_pending = false;
-    hipEvent_t table_event = nullptr;  // end of the table kernel (on table_stream)
+    Event table_event;  // end of the table kernel (on table_stream)
     hipStream_t table_stream = nullptr;
-    uint32_t* d_delta = nullptr;  // ROWS x S words (an internal buffer: ordered between streams by buf_event)
-    // fastecc_update_batch: one call's sorted write list and segment tables, written into the pinned h_list and copied to d_list on the call's
-    // stream.  d_list is an internal buffer like d_delta; h_list is free again once list_event (the end of that copy) has passed.
-    uint32_t* h_list = nullptr;
-    uint32_t* d_list = nullptr;
-    size_t list_cap = 0;  // words of each
-    hipEvent_t list_event = nullptr;
-    bool list_pending = false;
+    DeviceBuf<uint32_t> d_delta;  // ROWS x S words (an internal buffer: ordered between streams by buf_event)
+    // fastecc_update_batch: one call's sorted write list and segment tables, in words (list.dev is an internal buffer like d_delta)
+    StagedList<uint32_t> list;
 };
 
-void destroy_update_state(UpdateState* s)
-{
-    if (!s) return;
-    if (s->d_G) (void)hipFree(s->d_G);
-    if (s->d_delta) (void)hipFree(s->d_delta);
-    if (s->table_event) (void)hipEventDestroy(s->table_event);
-    if (s->h_list) (void)hipHostFree(s->h_list);
-    if (s->d_list) (void)hipFree(s->d_list);
-    if (s->list_event) (void)hipEventDestroy(s->list_event);
-    delete s;
-}
+void destroy_update_state(UpdateState* s) { delete s; }
 
 namespace {
 
@@ -448,8 +434,8 @@ int update_table(fastecc_ctx* c, UpdateState* s, hipStream_t st)
         return FASTECC_OK;
     }
     const uint64_t words = s->NC >> s->tshift;
-    if (!s->d_G) HIP_TRY(hipMalloc((void**)&s->d_G, words * 4));
-    if (!s->table_event) HIP_TRY(hipEventCreateWithFlags(&s->table_event, hipEventDisableTiming));
+    RC_TRY(s->d_G.alloc(words));
+    RC_TRY(s->table_event.create());
     {
         ProfScope ps(c, st, "update_table", words * 4);
         hipLaunchKernelGGL(update_table_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, s->d_G, (uint32_t)words, gf::h_root((uint32_t)s->NC),
@@ -633,7 +619,7 @@ int update_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const uint64_t*
     UpdateState* s = nullptr;
     int rc = update_state(c, &s);
     if (rc != FASTECC_OK) return rc;
-    if (!s->d_delta) HIP_TRY(hipMalloc((void**)&s->d_delta, (size_t)ROWS * c->S * 4));
+    RC_TRY(s->d_delta.alloc((uint64_t)ROWS * c->S));
     rc = update_table(c, s, st);
     if (rc != FASTECC_OK) return rc;
     return with_internal_buffers(c, st, [&]() -> int {
@@ -690,28 +676,6 @@ struct BatchLaunch {
     uint32_t seg0, segs;  // its segment table: first word after the list, number of segments
 };
 
-// h_list / d_list for `words` words, h_list free to be written: a call whose predecessor's list is still on its way to the device waits for
-// that copy's event (not for the device); growing waits for the last use of the device buffer and allocates.
-int batch_list_buffers(fastecc_ctx* c, UpdateState* s, size_t words)
-{
-    if (!s->list_event) HIP_TRY(hipEventCreateWithFlags(&s->list_event, hipEventDisableTiming));
-    if (s->list_pending) {
-        HIP_TRY(hipEventSynchronize(s->list_event));
-        s->list_pending = false;
-    }
-    if (words <= s->list_cap) return FASTECC_OK;
-    const size_t cap = std::max<size_t>(std::max<size_t>(words, 2 * s->list_cap), 4096);
-    if (c->buf_used) HIP_TRY(hipEventSynchronize(c->buf_event));  // the kernels that read d_list
-    if (s->h_list) (void)hipHostFree(s->h_list);
-    if (s->d_list) (void)hipFree(s->d_list);
-    s->h_list = s->d_list = nullptr;
-    s->list_cap = 0;
-    HIP_TRY(hipHostMalloc((void**)&s->h_list, cap * 4, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void**)&s->d_list, cap * 4));
-    s->list_cap = cap;
-    return FASTECC_OK;
-}
-
 template <int V> void launch_batch_v(int T, const BatchArgs& a, dim3 grid, hipStream_t st)
 {
     switch (T) {
@@ -738,11 +702,15 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
     while (V > 1 && ((S % V) != 0 || (align & (4u * V - 1u)) != 0)) V >>= 1;
     const uint64_t slices = (S + 64u * V - 1) / (64u * V);
     if (slices * M > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (one segment's waves fit a launch)
-    rc = batch_list_buffers(c, s, (size_t)n * (LIST_WORDS + SEG_HEAD + 1));  // (a segment of len writes takes SEG_HEAD + T <= 3 len words)
+    // (a segment of len writes takes SEG_HEAD + T <= 3 len words; growing waits for the kernels that read the device list)
+    rc = s->list.reserve(n * (LIST_WORDS + SEG_HEAD + 1), [&]() -> int {
+        if (c->buf_used) HIP_TRY(hipEventSynchronize(c->buf_event));
+        return FASTECC_OK;
+    });
     if (rc != FASTECC_OK) return rc;
 
     // the list, and each stripe's writes cut into segments of at most ROWS: segment r of a stripe runs in round r, by padded length class
-    uint32_t* list = s->h_list;
+    uint32_t* list = s->list.host;
     std::vector<std::vector<uint32_t>> bucket;  // [round * 5 + class]: first write of each segment (its length: to the stripe's end, at most ROWS)
     std::vector<uint32_t> stripe_end(n);        // per write: one past the last write of its stripe
     for (uint64_t f = 0; f < n;) {
@@ -787,17 +755,16 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
         const size_t words = (size_t)n * LIST_WORDS + seg_words;
         {
             ProfScope ps(c, st, "update_batch_list", words * 4);
-            HIP_TRY(hipMemcpyAsync(s->d_list, s->h_list, words * 4, hipMemcpyHostToDevice, st));
+            const int r = s->list.publish(words, st);
+            if (r != FASTECC_OK) return r;
         }
-        HIP_TRY(hipEventRecord(s->list_event, st));
-        s->list_pending = true;
         BatchArgs a{};
         a.parity = parity;
         a.data = data;
         a.old_blocks = old_blocks;
         a.new_blocks = new_blocks;
         a.G = s->d_G;
-        a.list = s->d_list;
+        a.list = s->list.dev;
         a.S = S;
         a.K = K;
         a.M = (uint32_t)M;
@@ -815,7 +782,7 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
             ProfScope ps(c, st, "update_batch", (uint64_t)l.segs * M * S * 8);
             for (uint64_t s0 = 0; s0 < l.segs; s0 += launch_segs) {
                 const uint64_t waves = std::min<uint64_t>(launch_segs, l.segs - s0) * seg_waves;
-                a.segs = s->d_list + n * LIST_WORDS + l.seg0 + (size_t)s0 * (SEG_HEAD + l.T);
+                a.segs = s->list.dev + n * LIST_WORDS + l.seg0 + (size_t)s0 * (SEG_HEAD + l.T);
                 a.waves = (uint32_t)waves;
                 const dim3 grid((unsigned)((waves + 3) / 4));
                 if (V == 4) launch_batch_v<4>(l.T, a, grid, st);
@@ -830,7 +797,7 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
             ProfScope ps(c, st, "update_scatter", n * S * 8);
             for (uint64_t w0 = 0; w0 < n; w0 += launch_writes) {
                 const uint64_t waves = std::min<uint64_t>(launch_writes, n - w0) * slices;
-                sa.list = s->d_list + w0 * LIST_WORDS;
+                sa.list = s->list.dev + w0 * LIST_WORDS;
                 sa.waves = (uint32_t)waves;
                 const dim3 grid((unsigned)((waves + 3) / 4));
                 if (V == 4) hipLaunchKernelGGL(update_scatter_kernel<4>, grid, dim3(256), 0, st, sa);

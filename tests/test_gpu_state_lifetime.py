@@ -1,0 +1,222 @@
+"""GPU test (-m gpu): the device state behind a context gives back what it took.
+
+Eight identical cycles create contexts, drive every family of state through them (direct and transform decode, host staging and the packed
+copy-back, pattern sets and their swap, small writes and their batch form, the scrub family with named erasures and pattern sets, the 64-bit
+field's decoder) and close them.  Every result of a cycle equals the first cycle's bit for bit (and the first cycle's equal the stripes the
+damage was done to), and the device's free memory after cycle 8 is not below that after cycle 2 (cycle 1 pays for the runtime's one-time
+allocations).  A context held open across the cycles is the control: the free-memory reading must see it come and go, or the test is blind."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+P = 0xFFF00001
+P61 = (1 << 61) - 1
+CYCLES = 8
+# Largest drop of free memory from cycle 2 to cycle 8 that the reading itself shows on code that frees everything: measured three times on the
+# tree before the owning types, 0 bytes each time.
+SLACK = 0
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "-m gpu tests need a GPU"
+    return torch
+
+
+@pytest.fixture(scope="module")
+def fe(hip_lib):
+    import fastecc_amd
+    return fastecc_amd
+
+
+def dev32(torch, a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32).reshape(-1)).to("cuda:0")
+
+
+def dev64(torch, a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64).reshape(-1)).to("cuda:0")
+
+
+def host32(t):
+    return t.cpu().numpy().view(np.uint32).copy()
+
+
+def host64(t):
+    return t.cpu().numpy().view(np.uint64).copy()
+
+
+def flags(count, lost):
+    f = np.ones(count, np.uint8)
+    f[list(lost)] = 0
+    return f
+
+
+class Stripe:
+    """A codeword (data, parity) on the device, a damaged copy of it per erasure pattern, and work buffers the calls write to: all allocated
+    once, before the measurement starts."""
+
+    def __init__(self, torch, to_dev, data, parity, patterns):
+        self.data, self.parity = data, parity  # host, as encoded
+        self.clean = (to_dev(torch, data), to_dev(torch, parity))
+        self.work = (torch.empty_like(self.clean[0]), torch.empty_like(self.clean[1]))
+        self.present, self.damaged, self.damaged_host = [], [], []
+        for lost_d, lost_p in patterns:
+            bad_d, bad_p = data.copy(), parity.copy()
+            bad_d[list(lost_d)] = 11
+            bad_p[list(lost_p)] = 13
+            self.present.append((flags(len(data), lost_d), flags(len(parity), lost_p)))
+            self.damaged.append((to_dev(torch, bad_d), to_dev(torch, bad_p)))
+            self.damaged_host.append((bad_d, bad_p))
+
+    def damage(self, i):
+        self.work[0].copy_(self.damaged[i][0])
+        self.work[1].copy_(self.damaged[i][1])
+        return self.work
+
+
+def encoded(torch, fe, n, k, block_bytes, data, field=None, stripes=1):
+    """parity of `stripes` stripes back to back by fastecc_encode, on a context of its own (closed before the measurement)"""
+    p61 = field is not None
+    to_dev, to_host = (dev64, host64) if p61 else (dev32, host32)
+    per = (n - k) * block_bytes // (8 if p61 else 4)
+    out = []
+    with fe.Encoder(n, k, block_bytes, **({"field": field} if p61 else {})) as enc:
+        for b in range(stripes):
+            par = torch.zeros(per, dtype=torch.int64 if p61 else torch.int32, device="cuda:0")
+            enc.encode(to_dev(torch, data[b] if stripes > 1 else data), par)
+            torch.cuda.synchronize()
+            out.append(to_host(par))
+    return np.stack(out) if stripes > 1 else out[0]
+
+
+def test_contexts_give_back_their_device_memory(torch_cuda, fe):
+    torch = torch_cuda
+    rng = np.random.default_rng(2024)
+    free = lambda: torch.cuda.mem_get_info()[0]
+
+    # ---- everything the cycles touch, allocated up front ----
+    K, S = 1 << 10, 64  # (2k,k), 256-byte blocks
+    data = rng.integers(0, P, size=(K, S), dtype=np.uint64).astype(np.uint32)
+    parity = encoded(torch, fe, 2 * K, K, 4 * S, data).reshape(K, S)
+    few = ([5, 700], [9])
+    many = (sorted(rng.permutation(K)[: K // 8].tolist()), sorted(rng.permutation(K)[: K // 8].tolist()))  # k/4 blocks in all
+    big = Stripe(torch, dev32, data, parity, [few, many])
+    new3 = dev32(torch, rng.integers(0, P, size=(3, S), dtype=np.uint64))
+    junk = dev32(torch, rng.integers(0, P, size=S, dtype=np.uint64))
+    absent = (flags(K, [3]), flags(K, [4]))
+
+    PN, PK, PS, B = 20, 16, 4, 8  # the pool: (20,16), 16-byte blocks, 8 stripes
+    PM = PN - PK
+    pool_data = rng.integers(0, P, size=(B, PK, PS), dtype=np.uint64).astype(np.uint32)
+    pool_parity = encoded(torch, fe, PN, PK, 4 * PS, pool_data, stripes=B).reshape(B, PM, PS)
+    set4 = [([q, q + 5], [q % PM]) for q in range(4)]
+    pattern_of = [b % 4 for b in range(B)]
+    bad_d, bad_p = pool_data.copy(), pool_parity.copy()
+    for b in range(B):
+        bad_d[b, set4[pattern_of[b]][0]] = 11
+        bad_p[b, set4[pattern_of[b]][1]] = 13
+    pool_clean = (dev32(torch, pool_data), dev32(torch, pool_parity))
+    pool_bad = (dev32(torch, bad_d), dev32(torch, bad_p))
+    pool_work = (torch.empty_like(pool_clean[0]), torch.empty_like(pool_clean[1]))
+    set_flags = lambda pats: (np.stack([flags(PK, d) for d, _ in pats]), np.stack([flags(PM, p) for _, p in pats]))
+    writes_short = [0 * PK + 3, 2 * PK + 0, 2 * PK + 15, 5 * PK + 7, 7 * PK + 9]
+    writes_long = [int(x) for x in rng.permutation(B * PK)]  # every block of the pool: the longest list it allows
+    new_short = dev32(torch, rng.integers(0, P, size=(len(writes_short), PS), dtype=np.uint64))
+    new_long = dev32(torch, rng.integers(0, P, size=(len(writes_long), PS), dtype=np.uint64))
+    pool_junk = dev32(torch, rng.integers(0, P, size=PS, dtype=np.uint64))
+
+    K61, E61 = 1 << 8, 16  # GF((2^61-1)^2), (2k,k), 256-byte blocks
+    data61 = rng.integers(0, P61, size=(K61, 2 * E61), dtype=np.uint64)
+    parity61 = encoded(torch, fe, 2 * K61, K61, 16 * E61, data61, field=fe.FIELD_GF_P61_SQUARED).reshape(K61, 2 * E61)
+    many61 = (sorted(rng.permutation(K61)[: K61 // 8].tolist()), sorted(rng.permutation(K61)[: K61 // 8].tolist()))
+    wide = Stripe(torch, dev64, data61, parity61, [([1, 200], [7]), many61])
+    torch.cuda.synchronize()
+
+    def cycle():
+        out = []
+        with fe.Encoder(2 * K, K, 4 * S) as enc:
+            enc.decode_prepare(*big.present[0])  # 3 lost blocks: the direct path
+            d, q = big.damage(0)
+            enc.repair(d, q)
+            out += [host32(d), host32(q)]
+            enc.set_option("decode_direct_max", 0)  # k/4 lost blocks through the transform: locator tree, re-encode
+            enc.decode_prepare(*big.present[1])
+            d, q = big.damage(1)
+            enc.repair(d, q)
+            out += [host32(d), host32(q)]
+            hd, hq = big.damaged_host[1][0].copy(), big.damaged_host[1][1].copy()  # host memory: staging, packed copy-back
+            enc.repair(hd, hq, mem=fe.MEM_HOST)
+            out += [hd, hq]
+            enc.update(d, q, [1, 17, 1000], new3)
+            out += [host32(d), host32(q)]
+            enc.scrub_erasures(*absent)
+            out.append(np.array([enc.verify(d, q, seed=5)]))
+            d[77 * S:78 * S].copy_(junk)
+            out.append(np.array(enc.correct(d, q, seed=5), dtype=np.uint64))
+            out += [host32(d), host32(q)]
+        with fe.Encoder(PN, PK, 4 * PS) as enc:
+            enc.decode_prepare_set(*set_flags(set4))
+            pool_work[0].copy_(pool_bad[0])
+            pool_work[1].copy_(pool_bad[1])
+            enc.repair_batch_set(pool_work[0], pool_work[1], B, pattern_of)
+            out += [host32(pool_work[0]), host32(pool_work[1])]
+            enc.decode_prepare_set(*set_flags(set4[:2]))  # the swap
+            enc.update_batch(pool_work[0], pool_work[1], B, writes_short, new_short)
+            enc.update_batch(pool_work[0], pool_work[1], B, writes_long, new_long)
+            out += [host32(pool_work[0]), host32(pool_work[1])]
+            enc.scrub_erasures(flags(PK, [2]), None)
+            out.append(enc.verify_batch(pool_work[0], pool_work[1], B, seed=9))
+            pool_work[0][(3 * PK + 6) * PS:(3 * PK + 7) * PS].copy_(pool_junk)
+            out.append(enc.correct_batch(pool_work[0], pool_work[1], B, seed=9))
+            out += [host32(pool_work[0]), host32(pool_work[1])]
+            enc.scrub_erasures_set(*set_flags(set4))
+            out.append(enc.verify_batch_set(pool_work[0], pool_work[1], B, pattern_of, seed=9))
+            enc.scrub_erasures_set([], [])
+        with fe.Encoder(2 * K61, K61, 16 * E61, field=fe.FIELD_GF_P61_SQUARED) as enc:
+            for i in (0, 1):  # few losses (direct), k/4 losses (transform)
+                enc.decode_prepare(*wide.present[i])
+                d, q = wide.damage(i)
+                enc.repair(d, q)
+                out += [host64(d), host64(q)]
+        torch.cuda.synchronize()
+        return out
+
+    # ---- the control: a context that is held must show in the reading ----
+    CK, CBYTES = 1 << 10, 4096
+    before = free()
+    control = fe.Encoder(2 * CK, CK, CBYTES)
+    control.set_option("decode_direct_max", 0)
+    control.decode_prepare(flags(CK, range(0, CK, 4)), np.ones(CK, np.uint8))
+    torch.cuda.synchronize()
+    held = free()
+    largest = CK * CBYTES  # the k-block stripe the transform leaves x p'(x) in
+    assert before - held >= largest, (before, held, largest)
+
+    first, readings = None, []
+    for c in range(CYCLES):
+        out = cycle()
+        readings.append(free())
+        print("free memory after cycle %d: %d" % (c + 1, readings[-1]))
+        if first is None:
+            first = out
+            want = [big.data, big.parity, big.data, big.parity, big.data, big.parity]
+            for i, w in enumerate(want):
+                assert np.array_equal(out[i].reshape(w.shape), w), "cycle 1, result %d differs from the stripe as encoded" % i
+            assert out[8][0] and list(out[9]) == [77], (out[8], out[9])
+            assert np.array_equal(out[12].reshape(pool_data.shape), pool_data) and np.array_equal(out[13].reshape(pool_parity.shape), pool_parity)
+            assert out[16].all() and list(out[17]) == [0, 0, 0, 1, 0, 0, 0, 0] and out[20].all(), (out[16], out[17], out[20])
+            for i, w in zip(range(21, 25), [wide.data, wide.parity, wide.data, wide.parity]):
+                assert np.array_equal(out[i].reshape(w.shape), w), "cycle 1, result %d differs from the stripe as encoded" % i
+        else:
+            assert len(out) == len(first)
+            for i, (a, b) in enumerate(zip(out, first)):
+                assert np.array_equal(a, b), "cycle %d, result %d differs from cycle 1" % (c + 1, i)
+    print("drop from cycle 2 to cycle 8:", readings[1] - readings[-1])
+    assert readings[1] - readings[-1] <= SLACK, readings
+
+    with_control = free()
+    control.close()
+    torch.cuda.synchronize()
+    assert free() - with_control >= largest, (with_control, free(), largest)
