@@ -174,42 +174,10 @@ void fastecc_destroy(fastecc_ctx* c)
     c->direct_enc = nullptr;
     p61::destroy_decoder(c->decoder61);
     c->decoder61 = nullptr;
-    for (ProfileRec& r : c->prof) {
-        (void)hipEventDestroy(r.start);
-        (void)hipEventDestroy(r.stop);
-    }
-    if (c->slab_ready) {
-        for (int h = 0; h < fastecc_ctx::MAX_SLABS; h++) {
-            if (c->slab_stream[h]) (void)hipStreamSynchronize(c->slab_stream[h]);
-            if (c->slab_first_done[h]) (void)hipEventDestroy(c->slab_first_done[h]);
-            if (c->slab_done[h]) (void)hipEventDestroy(c->slab_done[h]);
-            if (c->slab_stream[h]) (void)hipStreamDestroy(c->slab_stream[h]);
-        }
-        if (c->slab_fork) (void)hipEventDestroy(c->slab_fork);
-    }
-    if (c->buf_event) (void)hipEventDestroy(c->buf_event);
-    p61::destroy(c->p61);
-    for (hipEvent_t e : c->tw_event)
-        if (e) (void)hipEventDestroy(e);
-    if (c->tw_enc_dif) (void)hipFree(c->tw_enc_dif);
-    if (c->tw_enc_dit) (void)hipFree(c->tw_enc_dit);
-    if (c->tw_ntt_fwd) (void)hipFree(c->tw_ntt_fwd);
-    if (c->tw_ntt_inv) (void)hipFree(c->tw_ntt_inv);
-    if (c->dscale) (void)hipFree(c->dscale);
-    if (c->factor) (void)hipFree(c->factor);
-    if (c->dbuf) (void)hipFree(c->dbuf);
-    if (c->rawbuf) (void)hipFree(c->rawbuf);
-    if (c->scratch) (void)hipFree(c->scratch);
-    if (c->parbuf) (void)hipFree(c->parbuf);
-    if (c->hostpar) (void)hipFree(c->hostpar);
-    if (c->tw_fold_dit) (void)hipFree(c->tw_fold_dit);
-    for (uint32_t* t : {c->q_tw_dif, c->q_tw_dit, c->q_dft_inv, c->q_dft_fwd, c->mixbuf})
-        if (t) (void)hipFree(t);
-    for (fastecc_ctx::StageRing* r : {&c->stage_up, &c->stage_down}) {
-        if (r->slots) (void)hipHostFree(r->slots);
-        for (hipEvent_t e : r->event)
-            if (e) (void)hipEventDestroy(e);
-    }
+    // the slabs' streams may still be running the last encode: a wait, not teardown, and before anything is released
+    for (hipStream_t sh : c->slab_stream)
+        if (sh) (void)hipStreamSynchronize(sh);
+    // everything else is the members' destructors (devmem.hpp), on the context's device
     delete c;
 }
 
@@ -247,7 +215,7 @@ int fastecc_encode(fastecc_ctx* c, const void* data, void* parity, int mem_kind,
         HIP_TRY(hipMemcpyAsync(c->dbuf, data, c->K * block_bytes, hipMemcpyHostToDevice, st));
         uint32_t* dpar = c->dbuf;
         if (c->cosets > 1 || c->Mu > c->K) {  // more parity than the data stripe has room for
-            if (!c->hostpar) HIP_TRY(hipMalloc((void**)&c->hostpar, c->Mu * block_bytes));
+            RC_TRY(c->hostpar.alloc(c->Mu * c->S));
             dpar = c->hostpar;
         }
         rc = encode_device(c, c->dbuf, dpar, st);
@@ -312,13 +280,13 @@ int fastecc_encode_blocks(fastecc_ctx* c, void* const* blocks)
     bool one_buffer = true;
     for (uint64_t i = 1; i < c->K && one_buffer; i++) one_buffer = (const char*)blocks[i] == (const char*)blocks[i - 1] + bb;
     if (one_buffer) HIP_TRY(hipMemcpyAsync(c->dbuf, blocks[0], c->K * bb, hipMemcpyHostToDevice, nullptr));
-    else rc = stage_transfer(c, StageJob{true, nullptr, 0, (char*)c->dbuf, bb, bb, (size_t)c->K, blocks}, nullptr);
+    else rc = stage_transfer(c, StageJob{true, nullptr, 0, (char*)c->dbuf.get(), bb, bb, (size_t)c->K, blocks}, nullptr);
     if (rc != FASTECC_OK) return rc;
     rc = encode_device(c, c->dbuf, c->dbuf, nullptr);
     if (rc != FASTECC_OK) return rc;
     // the first n - k blocks receive the parity
     if (one_buffer) rc = stage_download(c, blocks[0], c->dbuf, c->Mu * bb, nullptr);
-    else rc = stage_transfer(c, StageJob{false, nullptr, 0, (char*)c->dbuf, bb, bb, (size_t)c->Mu, blocks}, nullptr);
+    else rc = stage_transfer(c, StageJob{false, nullptr, 0, (char*)c->dbuf.get(), bb, bb, (size_t)c->Mu, blocks}, nullptr);
     if (rc != FASTECC_OK) return rc;
     return mark_internal_buffers(c, nullptr);
 }
@@ -428,7 +396,7 @@ int fastecc_check_range(fastecc_ctx* c, const void* data, int mem_kind, void* st
         dev = c->dbuf;
     }
     // c->factor (N >= 2 words of scratch) holds the 64-bit counter
-    unsigned long long* counter = reinterpret_cast<unsigned long long*>(c->factor);
+    unsigned long long* counter = reinterpret_cast<unsigned long long*>(c->factor.get());
     HIP_TRY(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
     if (c->p61) {
         ProfScope ps(c, st, "p61_count_out_of_range");
@@ -475,9 +443,7 @@ static int pack_args_ok(const fastecc_ctx* c, const void* a, const void* b)
 
 static int ensure_rawbuf(fastecc_ctx* c)
 {
-    if (c->rawbuf) return FASTECC_OK;
-    HIP_TRY(hipMalloc((void**)&c->rawbuf, c->N * (c->S - 1) * 4));
-    return FASTECC_OK;
+    return c->rawbuf.alloc(c->N * (c->S - 1));
 }
 
 int fastecc_pack_blocks(fastecc_ctx* c, const void* raw, void* packed, int mem_kind, void* stream)
@@ -536,7 +502,7 @@ int fastecc_unpack_blocks(fastecc_ctx* c, const void* packed, void* raw, int mem
         src = c->dbuf;
         dst = c->rawbuf;
     }
-    unsigned long long* counter = bad_blocks ? reinterpret_cast<unsigned long long*>(c->factor) : nullptr;  // N >= 2 words of scratch
+    unsigned long long* counter = bad_blocks ? reinterpret_cast<unsigned long long*>(c->factor.get()) : nullptr;  // N >= 2 words of scratch
     if (counter) HIP_TRY(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
     {
         ProfScope ps(c, st, "unpack_blocks", alg_bytes);

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/fastecc.h"
+#include "devmem.hpp"
 #include "gf.hpp"
 #include "gf61.hpp"
 #include "gf61_path.hpp"
@@ -34,9 +35,9 @@ struct Pass {
                     // launched by encode_mixed; run_passes skips it).  rlog = its register run, pair = false.
 };
 
-struct ProfileRec {
+struct ProfileRec {  // move-only: owns its pair of timed events
     std::string name;
-    hipEvent_t start, stop;
+    TimedEvent start, stop;
     uint64_t bytes;  // algorithmic bytes of the launch (stripe or slab read once + written once)
 };
 
@@ -65,6 +66,9 @@ struct CallBounds {
     const uint32_t* rows_out_factor = nullptr;  // the plan's last pass, a DIT tile, stores only the blocks with a non-zero factor, times it, to final_out (MODE_DIT_ROWS)
 };
 
+// the level-packed twiddle tables of a context (twiddle_table below)
+enum { TW_ENC_DIF = 0, TW_ENC_DIT = 1, TW_NTT_FWD = 2, TW_NTT_INV = 3, TW_FOLD_DIT = 4, TW_COUNT = 5 };
+
 }  // namespace fastecc
 
 using namespace fastecc;  // private header of three translation units that all do this
@@ -77,7 +81,7 @@ struct fastecc_ctx {
     // uses the context's internal device buffers (scratch, parbuf, dbuf, ...) on a stream other than the previous one
     // first waits for the previous use (buf_event), so one context may be driven from several streams.
     std::mutex mu;
-    hipEvent_t buf_event = nullptr;
+    Event buf_event;
     hipStream_t buf_stream = nullptr;
     bool buf_used = false;
     DecodeState* decoder = nullptr;  // fastecc_decode_prepare: erasure pattern tables (decode.hip)
@@ -90,7 +94,7 @@ struct fastecc_ctx {
     int locate_max = 256;               // option "locate_max": most unknown corrupted blocks fastecc_locate_errors looks for
     int scrub_batch_chunk = 0;          // option "scrub_batch_chunk": most stripes per chunk of fastecc_verify_batch (0 = the state's capacity)
     int p61_stride = 1;  // 64-bit field, codes other than (2N,N): parity block j of the code is block j * p61_stride of the (2N,N) parity (N = 2^n)
-    p61::Path* p61 = nullptr;  // FASTECC_FIELD_GF_P61_SQUARED: tables and plan of gf61_kernels.hip (everything uint32 below is unused)
+    Owned<p61::Path, p61::destroy> p61;  // FASTECC_FIELD_GF_P61_SQUARED: tables and plan of gf61_kernels.hip (everything uint32 below is unused)
     uint64_t N = 0;   // k
     int n = 0;        // log2 k
     uint64_t S = 0;   // words per block
@@ -112,38 +116,39 @@ struct fastecc_ctx {
     // N = 2^n is what everything else in this structure describes — q stripes of N blocks back to back.  K <= q*N data
     // blocks (zero-extended), the first Mu <= q*N parity blocks are handed out.  q = 1: an ordinary context.
     int q = 1;
-    uint32_t* q_tw_dif = nullptr;   // N x (q-1): w_(qN)^-(i2*j)
-    uint32_t* q_tw_dit = nullptr;   // N x (q-1): w_(qN)^+(i2*j)
-    uint32_t* q_dft_inv = nullptr;  // q x q: w_q^-(i*j)
-    uint32_t* q_dft_fwd = nullptr;  // q x q: w_q^+(i*j)
-    uint32_t* mixbuf = nullptr;     // q*N-block work stripe for callers whose parity buffer is shorter (lazy)
+    DeviceBuf<uint32_t> q_tw_dif;   // N x (q-1): w_(qN)^-(i2*j)
+    DeviceBuf<uint32_t> q_tw_dit;   // N x (q-1): w_(qN)^+(i2*j)
+    DeviceBuf<uint32_t> q_dft_inv;  // q x q: w_q^-(i*j)
+    DeviceBuf<uint32_t> q_dft_fwd;  // q x q: w_q^+(i*j)
+    DeviceBuf<uint32_t> mixbuf;     // q*N-block work stripe for callers whose parity buffer is shorter (lazy)
     uint64_t M = 0;             // parity blocks
     size_t parity_bytes = 0;    // M * block_bytes
-    uint32_t* scratch = nullptr;      // fold > 0: k-block work stripe for the DIF half (lazy)
-    uint32_t* tw_fold_dit = nullptr;  // fold > 0: forward roots of order M, level-packed for the DIT passes above MID
+    DeviceBuf<uint32_t> scratch;  // fold > 0: k-block work stripe for the DIF half (lazy)
 
     // device tables (Montgomery form, see gf.hpp)
-    // level-packed twiddle tables (ntt_device.hpp), N words each, rebuilt whenever the plan changes:
-    uint32_t* tw_enc_dif = nullptr;  // inverse roots, ordered for the encode plan's DIF/MID passes
-    uint32_t* tw_enc_dit = nullptr;  // forward roots, same ordering (the DIT passes mirror the DIF ones)
-    uint32_t* tw_ntt_fwd = nullptr;  // forward roots, ordered for the stand-alone transform's passes
-    uint32_t* tw_ntt_inv = nullptr;  // inverse roots, same ordering
+    // level-packed twiddle tables (ntt_device.hpp), rebuilt whenever the plan changes, by TW_*:
+    //   TW_ENC_DIF   inverse roots, ordered for the encode plan's DIF/MID passes (N words)
+    //   TW_ENC_DIT   forward roots, same ordering (the DIT passes mirror the DIF ones)
+    //   TW_NTT_FWD   forward roots, ordered for the stand-alone transform's passes
+    //   TW_NTT_INV   inverse roots, same ordering
+    //   TW_FOLD_DIT  fold > 0: forward roots of order M, level-packed for the DIT passes above MID
+    DeviceBuf<uint32_t> tw[TW_COUNT];
     unsigned tw_ready = 0;           // which of the five tables hold the current plan's values (bit TW_*): each is built on the device at first use
     unsigned tw_pending = 0;         // built by a kernel that may still be running: tw_event[i] marks its end, tw_stream[i] the stream it ran on
-    hipEvent_t tw_event[5] = {};
-    hipStream_t tw_stream[5] = {};
-    uint32_t* dscale = nullptr;  // position p -> w_2N^i / N with i = bitrev_n(p)     (RS.cpp:51-54)
-    uint32_t* factor = nullptr;  // scratch for fastecc_scale_blocks, N words
-    uint32_t* dbuf = nullptr;    // staging stripe for FASTECC_MEM_HOST calls (lazy)
-    uint32_t* parbuf = nullptr;  // Mu < M: the M computed parity blocks, of which the first Mu are handed out (lazy)
-    uint32_t* hostpar = nullptr; // device parity for FASTECC_MEM_HOST encodes with more parity than data blocks (lazy)
-    uint32_t* rawbuf = nullptr;  // staging for the raw side of fastecc_pack_blocks / _unpack_blocks on host memory (lazy)
+    Event tw_event[TW_COUNT];
+    hipStream_t tw_stream[TW_COUNT] = {};
+    DeviceBuf<uint32_t> dscale;   // position p -> w_2N^i / N with i = bitrev_n(p)     (RS.cpp:51-54)
+    DeviceBuf<uint32_t> factor;   // scratch for fastecc_scale_blocks, N words
+    DeviceBuf<uint32_t> dbuf;     // staging stripe for FASTECC_MEM_HOST calls (lazy)
+    DeviceBuf<uint32_t> parbuf;   // Mu < M: the M computed parity blocks, of which the first Mu are handed out (lazy)
+    DeviceBuf<uint32_t> hostpar;  // device parity for FASTECC_MEM_HOST encodes with more parity than data blocks (lazy)
+    DeviceBuf<uint32_t> rawbuf;   // staging for the raw side of fastecc_pack_blocks / _unpack_blocks on host memory (lazy)
     // pageable host memory (FASTECC_MEM_HOST results, fastecc_encode_blocks) moves through rings of pinned slots served by helper threads (lazy)
     static constexpr int STAGE_SLOTS = 4;
     static constexpr size_t STAGE_SLOT_BYTES = (size_t)16 << 20;
     struct StageRing {  // pinned slots between pageable host memory and the copy engine, one ring per direction (host_stage.hip stage_transfer)
-        char* slots = nullptr;
-        hipEvent_t event[STAGE_SLOTS] = {};
+        PinnedBuf<char> slots;
+        Event event[STAGE_SLOTS];
     };
     StageRing stage_up, stage_down;
 
@@ -171,8 +176,8 @@ struct fastecc_ctx {
     int slabs = 1;           // > 1: encode in this many column slabs on internal streams, staggered by one pass,
                              // so the VALU-bound MID of one slab runs beside the HBM-bound outer passes of others
     static constexpr int MAX_SLABS = 32;
-    hipStream_t slab_stream[MAX_SLABS] = {};
-    hipEvent_t slab_fork = nullptr, slab_first_done[MAX_SLABS] = {}, slab_done[MAX_SLABS] = {};
+    Stream slab_stream[MAX_SLABS];
+    Event slab_fork, slab_first_done[MAX_SLABS], slab_done[MAX_SLABS];
     bool slab_ready = false;
     int fuse_radix = 1;      // mixed-radix contexts: fuse the odd-radix level into the outermost tile where a shape exists (option "fuse_radix")
     bool slim_outer = true;  // outer 8/9-level tiles keep 16 words per lane instead of 32 (twice the waves per CU)
@@ -198,11 +203,10 @@ void build_plans(fastecc_ctx* c);
 const char* pass_name(const Pass& p, int vec, char* buf, size_t cap);
 std::vector<int> level_strides(const std::vector<Pass>& plan, int n, bool up = false);
 std::vector<uint32_t> build_level_table(int n, uint32_t root_of_order_N, const std::vector<int>& sl);
-int upload_table(uint32_t** dst, const std::vector<uint32_t>& src);
+int upload_table(DeviceBuf<uint32_t>& dst, const std::vector<uint32_t>& src);
 int upload_twiddles(fastecc_ctx* c);  // the plans changed: every twiddle table is rebuilt at its next use; the device must be idle w.r.t. this context
 // The table `which` for the current plans, built on the context's device (the current device) at first use: a context that only ever encodes
 // never builds the stand-alone transform's tables and vice versa (the decoder's ~19 internal contexts each use one kind).  nullptr on failure.
-enum { TW_ENC_DIF = 0, TW_ENC_DIT = 1, TW_NTT_FWD = 2, TW_NTT_INV = 3, TW_FOLD_DIT = 4 };
 // The table is written by a kernel enqueued on `st` — the stream that is about to use it — with NO host synchronisation: the first call on a
 // context stays asynchronous (and may run under stream capture).  A later use on another stream waits for the build's event on the device.
 const uint32_t* twiddle_table(fastecc_ctx* c, int which, hipStream_t st);

@@ -47,14 +47,12 @@ int setup_mixed(fastecc_ctx* c, int q, uint64_t k_user, uint64_t m_user, const u
     const uint32_t wq = gf::h_pow(wN1, M);
     dff = radix_dft_table(q, wq);
     dfi = radix_dft_table(q, gf::h_inv(wq));
-    (void)hipFree(c->dscale);  // sized for one stripe by create_impl
-    c->dscale = nullptr;
-    int rc = upload_table(&c->dscale, dsc);
-    if (rc == FASTECC_OK) rc = upload_table(&c->q_tw_dif, twd);
-    if (rc == FASTECC_OK) rc = upload_table(&c->q_tw_dit, twu);
-    if (rc == FASTECC_OK) rc = upload_table(&c->q_dft_inv, dfi);
-    if (rc == FASTECC_OK) rc = upload_table(&c->q_dft_fwd, dff);
-    if (rc != FASTECC_OK) return rc;
+    c->dscale.reset();  // sized for one stripe by create_impl
+    RC_TRY(upload_table(c->dscale, dsc));
+    RC_TRY(upload_table(c->q_tw_dif, twd));
+    RC_TRY(upload_table(c->q_tw_dit, twu));
+    RC_TRY(upload_table(c->q_dft_inv, dfi));
+    RC_TRY(upload_table(c->q_dft_fwd, dff));
     c->q = q;
     c->K = k_user;
     c->Mu = m_user;
@@ -239,12 +237,9 @@ int create_impl(fastecc_ctx** out, uint64_t n, uint64_t k, int lg, uint64_t bloc
         return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
     }
     if (f61) {
-        int rc = cosets > 1 ? p61::create_cosets(&c->p61, lg, block_bytes / 16, cosets, g_detail, sizeof g_detail)
-                            : p61::create(&c->p61, lg, block_bytes / 16, g_detail, sizeof g_detail);
-        if (rc == FASTECC_OK) {
-            const hipError_t e = hipMalloc((void**)&c->factor, 8);  // counter of fastecc_check_range
-            if (e != hipSuccess) rc = hip_fail(e, "hipMalloc(counter)");
-        }
+        int rc = cosets > 1 ? p61::create_cosets(c->p61.fill(), lg, block_bytes / 16, cosets, g_detail, sizeof g_detail)
+                            : p61::create(c->p61.fill(), lg, block_bytes / 16, g_detail, sizeof g_detail);
+        if (rc == FASTECC_OK) rc = c->factor.alloc(2);  // counter of fastecc_check_range
         if (rc != FASTECC_OK) {
             fastecc_destroy(c);
             return rc;
@@ -281,11 +276,8 @@ int create_impl(fastecc_ctx** out, uint64_t n, uint64_t k, int lg, uint64_t bloc
         }
     }
     int rc = upload_twiddles(c);
-    if (rc == FASTECC_OK && !ntt_only) rc = upload_table(&c->dscale, dsc);
-    if (rc == FASTECC_OK) {
-        const hipError_t e = hipMalloc((void**)&c->factor, (ntt_only ? 2 : N) * 4);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMalloc(factor)");
-    }
+    if (rc == FASTECC_OK && !ntt_only) rc = upload_table(c->dscale, dsc);
+    if (rc == FASTECC_OK) rc = c->factor.alloc(ntt_only ? 2 : N);
     if (rc != FASTECC_OK) {
         fastecc_destroy(c);
         return rc;
@@ -328,9 +320,9 @@ int create_ramp_transform_ctx(fastecc_ctx** out, int log2k, uint64_t block_bytes
     if (rc != FASTECC_OK) return rc;
     fastecc_ctx* c = *out;
     DeviceGuard dg(device);
-    hipError_t e = dg.ok ? hipMalloc((void**)&c->dscale, k * 4) : hipErrorInvalidDevice;
+    hipError_t e = dg.ok ? c->dscale.try_alloc(k) : hipErrorInvalidDevice;
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(ramp_factor_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, nullptr, c->dscale, (uint32_t)k, log2k,
+        hipLaunchKernelGGL(ramp_factor_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, nullptr, c->dscale.get(), (uint32_t)k, log2k,
                            gf::h_to_mont(gf::h_to_mont(scale % gf::P)), gf::h_to_mont(offset % gf::P));
         e = hipGetLastError();
     }

@@ -1,5 +1,7 @@
-// devmem.hpp — owners of what the state structs of decode.hip, direct.hip, update.hip, scrub.hip and gf61_decode.hip hold on the device: a struct's
-// destructor is its whole teardown.  Host code only.
+// devmem.hpp — owners of what the library holds on the device: the context (context.hpp), the 64-bit field's path (gf61_kernels.hip) and the state
+// structs of decode.hip, direct.hip, update.hip, scrub.hip and gf61_decode.hip.  A struct's destructor is its whole teardown, and this file is the
+// only one besides sharded.hip (whose teardown walks devices in an order of its own) that allocates or frees device or pinned memory, events or
+// streams.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -85,29 +87,58 @@ private:
 template <class T> using DeviceBuf = Buf<T, DeviceMem>;
 template <class T> using PinnedBuf = Buf<T, PinnedMem>;
 
-// An event without timing, created at its first use
-class Event {
+// An event created at its first use: without timing (Event), or one of a pair whose interval is read (TimedEvent: the profiler's records).
+// create returns what HIP_TRY returns; try_create leaves the error and its detail to the caller.
+template <unsigned Flags> class EventOf {
 public:
-    Event() = default;
-    Event(Event&& o) noexcept { std::swap(ev_, o.ev_); }
-    Event& operator=(Event&& o) noexcept
+    EventOf() = default;
+    EventOf(EventOf&& o) noexcept { std::swap(ev_, o.ev_); }
+    EventOf& operator=(EventOf&& o) noexcept
     {
         std::swap(ev_, o.ev_);  // (the other side destroys what this one held)
         return *this;
     }
-    ~Event()
+    ~EventOf()
     {
         if (ev_) (void)hipEventDestroy(ev_);
     }
+    hipError_t try_create() { return ev_ ? hipSuccess : hipEventCreateWithFlags(&ev_, Flags); }
     int create()
     {
-        if (!ev_) HIP_TRY(hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
-        return FASTECC_OK;
+        const hipError_t e = try_create();
+        return e == hipSuccess ? FASTECC_OK : hip_fail(e, "hipEventCreateWithFlags");
     }
     operator hipEvent_t() const { return ev_; }
 
 private:
     hipEvent_t ev_ = nullptr;
+};
+using Event = EventOf<hipEventDisableTiming>;
+using TimedEvent = EventOf<hipEventDefault>;
+
+// A non-blocking stream of the library's own, created at its first use.  The destructor does not wait: whoever must see the stream's work
+// finished synchronises it first (fastecc_destroy does).
+class Stream {
+public:
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() { reset(); }
+    void reset()
+    {
+        if (st_) (void)hipStreamDestroy(st_);
+        st_ = nullptr;
+    }
+    hipError_t try_create() { return st_ ? hipSuccess : hipStreamCreateWithFlags(&st_, hipStreamNonBlocking); }
+    int create()
+    {
+        const hipError_t e = try_create();
+        return e == hipSuccess ? FASTECC_OK : hip_fail(e, "hipStreamCreateWithFlags");
+    }
+    operator hipStream_t() const { return st_; }
+
+private:
+    hipStream_t st_ = nullptr;
 };
 
 // One call's list, written on the host and read by kernels: the pinned buffer the call fills, its device copy (an internal buffer: ordered between

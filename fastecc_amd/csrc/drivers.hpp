@@ -26,12 +26,8 @@ struct ProfScope {
         if (!c->profiling) return;
         if (c->prof_used == c->prof.size()) {
             ProfileRec r;
-            if (hipEventCreate(&r.start) != hipSuccess) return;
-            if (hipEventCreate(&r.stop) != hipSuccess) {
-                (void)hipEventDestroy(r.start);
-                return;
-            }
-            c->prof.push_back(r);
+            if (r.start.try_create() != hipSuccess || r.stop.try_create() != hipSuccess) return;
+            c->prof.push_back(std::move(r));
         }
         rec = &c->prof[c->prof_used++];
         rec->name = name;

@@ -30,7 +30,7 @@ int run_passes(fastecc_ctx* c, const std::vector<Pass>& plan, const uint32_t* in
     const bool folded = c->fold > 0 && is_encode;
     const int cosets = is_encode ? c->cosets : 1;
     const bool staged = folded || cosets > 1;
-    if (staged && !c->scratch) HIP_TRY(hipMalloc((void**)&c->scratch, c->N * c->ld * 4));
+    if (staged) RC_TRY(c->scratch.alloc(c->N * c->ld));
     int vec = staged ? std::min(pick_vec(c, in, out), pick_vec(c, c->scratch, c->scratch)) : pick_vec(c, in, out);
     // the last pass may store to another buffer and the decoder's first pass reads a second one: they bound the lane vector too
     while (vec > 1 && (width % vec) != 0) vec >>= 1;
@@ -162,11 +162,11 @@ int run_passes(fastecc_ctx* c, const std::vector<Pass>& plan, const uint32_t* in
 int ensure_slab_streams(fastecc_ctx* c)
 {
     if (c->slab_ready) return FASTECC_OK;
-    HIP_TRY(hipEventCreateWithFlags(&c->slab_fork, hipEventDisableTiming));
+    RC_TRY(c->slab_fork.create());
     for (int h = 0; h < fastecc_ctx::MAX_SLABS; h++) {
-        HIP_TRY(hipStreamCreateWithFlags(&c->slab_stream[h], hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&c->slab_first_done[h], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&c->slab_done[h], hipEventDisableTiming));
+        RC_TRY(c->slab_stream[h].create());
+        RC_TRY(c->slab_first_done[h].create());
+        RC_TRY(c->slab_done[h].create());
     }
     c->slab_ready = true;
     return FASTECC_OK;
@@ -187,7 +187,7 @@ int encode_mixed(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStre
     const uint64_t N1 = (uint64_t)c->q * c->N;
     uint32_t* work = parity;
     if (c->Mu != N1) {
-        if (!c->mixbuf) HIP_TRY(hipMalloc((void**)&c->mixbuf, N1 * c->ld * 4));
+        RC_TRY(c->mixbuf.alloc(N1 * c->ld));
         work = c->mixbuf;
     }
     // these passes are free to go as wide as the block size and the three pointers allow (the plan's `vec` is about its own passes)
@@ -302,12 +302,12 @@ int encode_device(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStr
         const size_t row = (size_t)c->S * 4;
         const uint32_t* src = data;
         if (c->K != c->N) {
-            if (!c->scratch) HIP_TRY(hipMalloc((void**)&c->scratch, c->N * row));
+            RC_TRY(c->scratch.alloc(c->N * c->S));
             HIP_TRY(hipMemcpyAsync(c->scratch, data, c->K * row, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemsetAsync((char*)c->scratch + c->K * row, 0, (c->N - c->K) * row, st));
+            HIP_TRY(hipMemsetAsync((char*)c->scratch.get() + c->K * row, 0, (c->N - c->K) * row, st));
             src = c->scratch;
         }
-        if (!c->parbuf) HIP_TRY(hipMalloc((void**)&c->parbuf, c->N * row));
+        RC_TRY(c->parbuf.alloc(c->N * c->S));
         const int rc = encode_pow2(c, src, c->parbuf, st);
         if (rc != FASTECC_OK) return rc;
         HIP_TRY(hipMemcpy2DAsync(parity, row, c->parbuf, (size_t)c->p61_stride * row, row, c->Mu, hipMemcpyDeviceToDevice, st));
@@ -316,11 +316,10 @@ int encode_device(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStr
     // any (n,k): the first pass reads the K existing data blocks and takes the rest of the stripe as zero, the last pass
     // writes only the first Mu of the M parity blocks it computes — both through the kernels' bounds handling, no copies.
     // The passes in between need all M blocks somewhere: the caller's parity buffer when it is that large, else parbuf.
-    const size_t row = (size_t)c->ld * 4;
     uint32_t* out = parity;
     CallBounds cb;
     if (c->Mu != c->M) {
-        if (!c->parbuf) HIP_TRY(hipMalloc((void**)&c->parbuf, c->M * row));
+        RC_TRY(c->parbuf.alloc(c->M * c->ld));
         out = c->parbuf;
         cb.final_out = parity;
         cb.out_rows = (uint32_t)c->Mu;
@@ -334,8 +333,8 @@ int encode_pow2(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStrea
     if (c->p61) {
         P61Hooks hk(c);
         if (c->cosets > 1) {  // n = 4k / 8k: the DIF half once into a k-block work stripe, MID and the DIT half once per coset
-            if (p61::encode_cosets_needs_work(c->p61) && !c->scratch) HIP_TRY(hipMalloc((void**)&c->scratch, c->N * (size_t)c->S * 4));
-            return p61::encode_cosets(c->p61, (const uint64_t*)data, (uint64_t*)parity, (uint64_t*)c->scratch, st, c->profiling ? &hk.h : nullptr);
+            if (p61::encode_cosets_needs_work(c->p61)) RC_TRY(c->scratch.alloc(c->N * c->S));
+            return p61::encode_cosets(c->p61, (const uint64_t*)data, (uint64_t*)parity, (uint64_t*)c->scratch.get(), st, c->profiling ? &hk.h : nullptr);
         }
         return p61::encode(c->p61, (const uint64_t*)data, (uint64_t*)parity, st, c->profiling ? &hk.h : nullptr);
     }
@@ -398,7 +397,7 @@ int order_internal_buffers(fastecc_ctx* c, hipStream_t st)
 }
 int mark_internal_buffers(fastecc_ctx* c, hipStream_t st)
 {
-    if (!c->buf_event) HIP_TRY(hipEventCreateWithFlags(&c->buf_event, hipEventDisableTiming));
+    RC_TRY(c->buf_event.create());
     HIP_TRY(hipEventRecord(c->buf_event, st));
     c->buf_stream = st;
     c->buf_used = true;
@@ -593,11 +592,10 @@ int CallScope::wait_idle()
 
 int p61_work_stripes(fastecc_ctx* c, uint64_t** data_full, uint64_t** parity_full)
 {
-    const size_t row = (size_t)c->S * 4;
-    if (!c->scratch) HIP_TRY(hipMalloc((void**)&c->scratch, c->N * row));
-    if (!c->parbuf) HIP_TRY(hipMalloc((void**)&c->parbuf, c->N * row));
-    *data_full = (uint64_t*)c->scratch;
-    *parity_full = (uint64_t*)c->parbuf;
+    RC_TRY(c->scratch.alloc(c->N * c->S));
+    RC_TRY(c->parbuf.alloc(c->N * c->S));
+    *data_full = (uint64_t*)c->scratch.get();
+    *parity_full = (uint64_t*)c->parbuf.get();
     return FASTECC_OK;
 }
 
@@ -612,7 +610,7 @@ int scratch_of(fastecc_ctx* c, uint32_t** out)
 {
     DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
-    if (!c->scratch) HIP_TRY(hipMalloc((void**)&c->scratch, c->N * c->ld * 4));
+    RC_TRY(c->scratch.alloc(c->N * c->ld));
     *out = c->scratch;
     return FASTECC_OK;
 }

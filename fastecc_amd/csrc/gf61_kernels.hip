@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/fastecc.h"
+#include "devmem.hpp"
 #include "gf61.hpp"
 #include "gf61_path.hpp"
 
@@ -820,11 +821,11 @@ struct Path {
     int split = 2;                // 7-level tiles: exchange rounds (2 = 64 KiB of LDS, two workgroups per CU)
     int force_mid = 0;            // > 0: MID covers exactly that many levels (the decoder's folded transform pairs a 7-level MID with a 6-level one)
     std::vector<Pass> enc, fwd;  // encode plan; stand-alone transform plan (all DIF, then the block permutation)
-    uint64_t* tw_fwd = nullptr;  // forward roots, level-packed for the encode plan
-    uint64_t* tw_inv = nullptr;  // inverse roots, the same packing
-    uint64_t* tw_ntt_fwd = nullptr;  // the two again, packed for the stand-alone transform's plan when its register runs
-    uint64_t* tw_ntt_inv = nullptr;  // differ from the encode plan's (a MID tile there, register passes here); else null
-    uint64_t* dscale = nullptr;  // per-block factors by position; `cosets` tables of N elements back to back
+    DeviceBuf<uint64_t> tw_fwd;  // forward roots, level-packed for the encode plan
+    DeviceBuf<uint64_t> tw_inv;  // inverse roots, the same packing
+    DeviceBuf<uint64_t> tw_ntt_fwd;  // the two again, packed for the stand-alone transform's plan when its register runs
+    DeviceBuf<uint64_t> tw_ntt_inv;  // differ from the encode plan's (a MID tile there, register passes here); else null
+    DeviceBuf<uint64_t> dscale;  // per-block factors by position; `cosets` tables of N elements back to back
     int cosets = 1;              // 1: the (2k,k) code; 3 / 7: n = 4k / 8k (one table per coset of evaluation points, create_cosets)
     SmallRoots sr{};  // forward w_16^(1,3,5,7)
     std::string text;
@@ -1023,31 +1024,29 @@ __global__ __launch_bounds__(256) void k_split_addend_factors(uint64_t* __restri
     d[2 * q + 1] = v.im;
 }
 
-int device_run_table(uint64_t** dst, int n, gf61::Elem root_of_order_N, const std::vector<Run>& runs, char* detail, size_t cap)
+int device_run_table(DeviceBuf<uint64_t>& dst, int n, gf61::Elem root_of_order_N, const std::vector<Run>& runs, char* detail, size_t cap)
 {
     const size_t words = 4 * std::max<size_t>((size_t)1 << n, 2);
-    hipError_t e = hipSuccess;
-    if (!*dst) e = hipMalloc((void**)dst, words * 8);
-    if (e != hipSuccess) return fail(detail, cap, e, "hipMalloc(gf61 table)");
-    e = hipMemsetAsync(*dst, 0, words * 8, nullptr);
+    hipError_t e = dst.try_alloc(words);
+    if (e != hipSuccess) return fail(detail, cap, e, "gf61 table allocation");
+    e = hipMemsetAsync(dst, 0, words * 8, nullptr);
     if (e != hipSuccess) return fail(detail, cap, e, "hipMemsetAsync(gf61 table)");
     for (const Run& run : runs) {
         const int lev = run.sl + run.r;
         const gf61::Elem root = gf61::h_pow(root_of_order_N, 1ull << (n - lev));  // order 2^(sl + r)
         const uint64_t count = 1ull << lev;
-        hipLaunchKernelGGL(k_run_table, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, nullptr, *dst, root.re, root.im, run.sl, run.r);
+        hipLaunchKernelGGL(k_run_table, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, nullptr, dst.get(), root.re, root.im, run.sl, run.r);
         e = hipGetLastError();
         if (e != hipSuccess) return fail(detail, cap, e, "gf61 twiddle table kernel");
     }
     return FASTECC_OK;
 }
 
-int upload(uint64_t** dst, const std::vector<uint64_t>& src, char* detail, size_t cap)
+int upload(DeviceBuf<uint64_t>& dst, const std::vector<uint64_t>& src, char* detail, size_t cap)
 {
-    hipError_t e = hipSuccess;
-    if (!*dst) e = hipMalloc((void**)dst, src.size() * 8);
-    if (e != hipSuccess) return fail(detail, cap, e, "hipMalloc(gf61 table)");
-    e = hipMemcpy(*dst, src.data(), src.size() * 8, hipMemcpyHostToDevice);
+    hipError_t e = dst.try_alloc(src.size());
+    if (e != hipSuccess) return fail(detail, cap, e, "gf61 table allocation");
+    e = hipMemcpy(dst, src.data(), src.size() * 8, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(detail, cap, e, "hipMemcpy(gf61 table)");
     return FASTECC_OK;
 }
@@ -1057,15 +1056,14 @@ int upload_tables(Path* p, char* detail, size_t cap)
 {
     const gf61::Elem wN = gf61::h_root(p->N), wNi = gf61::h_inv(wN);
     const std::vector<Run> sl = runs_of(p->enc), sl_ntt = runs_of(p->fwd);
-    int rc = device_run_table(&p->tw_fwd, p->n, wN, sl, detail, cap);
-    if (rc == FASTECC_OK) rc = device_run_table(&p->tw_inv, p->n, wNi, sl, detail, cap);
+    int rc = device_run_table(p->tw_fwd, p->n, wN, sl, detail, cap);
+    if (rc == FASTECC_OK) rc = device_run_table(p->tw_inv, p->n, wNi, sl, detail, cap);
     if (sl_ntt == sl) {
-        if (p->tw_ntt_fwd) (void)hipFree(p->tw_ntt_fwd);
-        if (p->tw_ntt_inv) (void)hipFree(p->tw_ntt_inv);
-        p->tw_ntt_fwd = p->tw_ntt_inv = nullptr;
+        p->tw_ntt_fwd.reset();
+        p->tw_ntt_inv.reset();
     } else {
-        if (rc == FASTECC_OK) rc = device_run_table(&p->tw_ntt_fwd, p->n, wN, sl_ntt, detail, cap);
-        if (rc == FASTECC_OK) rc = device_run_table(&p->tw_ntt_inv, p->n, wNi, sl_ntt, detail, cap);
+        if (rc == FASTECC_OK) rc = device_run_table(p->tw_ntt_fwd, p->n, wN, sl_ntt, detail, cap);
+        if (rc == FASTECC_OK) rc = device_run_table(p->tw_ntt_inv, p->n, wNi, sl_ntt, detail, cap);
     }
     return rc;
 }
@@ -1199,8 +1197,8 @@ int create_cosets(Path** out, int n, uint64_t elems, int cosets, char* detail, s
     int rc = create_transform(out, n, elems, FACTOR_ENCODE, detail, cap);
     if (rc != FASTECC_OK) return rc;
     Path* p = *out;
-    uint64_t* all = nullptr;
-    hipError_t e = hipMalloc((void**)&all, (size_t)cosets * 2 * p->N * 8);
+    DeviceBuf<uint64_t> all;
+    hipError_t e = all.try_alloc((size_t)cosets * 2 * p->N);
     if (e == hipSuccess) {
         const gf61::Elem c = gf61::h_inv(gf61::Elem{p->N % gf61::P, 0});
         for (int t = 0; t < cosets && e == hipSuccess; t++) {
@@ -1209,20 +1207,18 @@ int create_cosets(Path** out, int n, uint64_t elems, int cosets, char* detail, s
             while ((1 << j) - 1 <= t) j++;
             const uint64_t odd = 2ull * (uint64_t)(t + 1 - (1 << (j - 1))) + 1ull;
             const gf61::Elem g = gf61::h_pow(gf61::h_root(p->N << j), odd);
-            hipLaunchKernelGGL(k_block_factors, dim3((unsigned)((p->N + 255) / 256)), dim3(256), 0, nullptr, all + (size_t)t * 2 * p->N, c.re, c.im, g.re, g.im, n, false);
+            hipLaunchKernelGGL(k_block_factors, dim3((unsigned)((p->N + 255) / 256)), dim3(256), 0, nullptr, all.get() + (size_t)t * 2 * p->N, c.re, c.im, g.re, g.im, n, false);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     }
     if (e != hipSuccess) {
-        if (all) (void)hipFree(all);
         rc = fail(detail, cap, e, "gf61 coset factors");
         destroy(p);
         *out = nullptr;
         return rc;
     }
-    (void)hipFree(p->dscale);
-    p->dscale = all;
+    p->dscale = std::move(all);
     p->cosets = cosets;
     return FASTECC_OK;
 }
@@ -1352,10 +1348,10 @@ int create_transform_mid(Path** out, int n, uint64_t elems, int factor, int forc
     int rc = upload_tables(p, detail, cap);
     if (rc == FASTECC_OK) {
         const gf61::Elem w2N = gf61::h_root(2 * p->N), c = gf61::h_inv(gf61::Elem{p->N % gf61::P, 0});
-        hipError_t e = hipMalloc((void**)&p->dscale, 2 * p->N * 8);
+        hipError_t e = p->dscale.try_alloc(2 * p->N);
         if (e == hipSuccess) {
             const uint64_t half = gf61::h_inv(gf61::Elem{2, 0}).re;  // FACTOR_SPLIT: (2 m + N) / 2N = m / N + 1 / 2
-            hipLaunchKernelGGL(k_block_factors, dim3((unsigned)((p->N + 255) / 256)), dim3(256), 0, nullptr, p->dscale, c.re, c.im, w2N.re, w2N.im, n,
+            hipLaunchKernelGGL(k_block_factors, dim3((unsigned)((p->N + 255) / 256)), dim3(256), 0, nullptr, p->dscale.get(), c.re, c.im, w2N.re, w2N.im, n,
                                factor == FACTOR_INDEX || factor == FACTOR_SPLIT, factor == FACTOR_SPLIT ? half : 0ull);
             e = hipGetLastError();
         }
@@ -1373,16 +1369,7 @@ int create_transform_mid(Path** out, int n, uint64_t elems, int factor, int forc
     return FASTECC_OK;
 }
 
-void destroy(Path* p)
-{
-    if (!p) return;
-    if (p->tw_fwd) (void)hipFree(p->tw_fwd);
-    if (p->tw_inv) (void)hipFree(p->tw_inv);
-    if (p->tw_ntt_fwd) (void)hipFree(p->tw_ntt_fwd);
-    if (p->tw_ntt_inv) (void)hipFree(p->tw_ntt_inv);
-    if (p->dscale) (void)hipFree(p->dscale);
-    delete p;
-}
+void destroy(Path* p) { delete p; }
 
 int encode_columns(Path* p, const uint64_t* data, uint64_t* parity, uint64_t col0, uint64_t width, hipStream_t st, const LaunchHooks* hooks)
 {

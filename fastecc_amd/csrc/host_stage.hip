@@ -88,20 +88,12 @@ bool ensure_stage_ring(fastecc_ctx::StageRing& r)
 {
     constexpr int NSLOT = fastecc_ctx::STAGE_SLOTS;
     if (r.slots) return true;
-    if (hipHostMalloc((void**)&r.slots, NSLOT * fastecc_ctx::STAGE_SLOT_BYTES, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        r.slots = nullptr;
-        return false;
-    }
-    for (int i = 0; i < NSLOT; i++)
-        if (hipEventCreateWithFlags(&r.event[i], hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            for (int k = 0; k < i; k++) (void)hipEventDestroy(r.event[k]), r.event[k] = nullptr;
-            (void)hipHostFree(r.slots);
-            r.slots = nullptr;
-            return false;
-        }
-    return true;
+    hipError_t e = r.slots.try_alloc(NSLOT * fastecc_ctx::STAGE_SLOT_BYTES);
+    for (int i = 0; i < NSLOT && e == hipSuccess; i++) e = r.event[i].try_create();
+    if (e == hipSuccess) return true;
+    (void)hipGetLastError();
+    r = fastecc_ctx::StageRing();  // nothing half-built stays behind
+    return false;
 }
 
 int stage_transfer(fastecc_ctx* c, const StageJob& j, hipStream_t st, int threads)
@@ -297,11 +289,6 @@ int encode_host_pageable(fastecc_ctx* c, const uint32_t* data, uint32_t* parity,
     return rc;
 }
 
-int ensure_dbuf(fastecc_ctx* c)
-{
-    if (c->dbuf) return FASTECC_OK;
-    HIP_TRY(hipMalloc((void**)&c->dbuf, c->stripe_bytes));
-    return FASTECC_OK;
-}
+int ensure_dbuf(fastecc_ctx* c) { return c->dbuf.alloc(c->stripe_bytes / 4); }
 
 }  // namespace fastecc

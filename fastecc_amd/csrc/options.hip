@@ -49,10 +49,9 @@ int fastecc_set_option(fastecc_ctx* c, const char* name, int value)
             // (its transform context and tables assume the geometry they were built with)
             DeviceGuard dgs(c->device);
             (void)hipDeviceSynchronize();
-            if (c->scratch) (void)hipFree(c->scratch);
-            if (c->parbuf) (void)hipFree(c->parbuf);
-            if (c->mixbuf) (void)hipFree(c->mixbuf);
-            c->scratch = c->parbuf = c->mixbuf = nullptr;
+            c->scratch.reset();
+            c->parbuf.reset();
+            c->mixbuf.reset();
             destroy_decode_state(c->decoder);
             c->decoder = nullptr;
         }

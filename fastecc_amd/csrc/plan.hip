@@ -230,10 +230,10 @@ std::vector<uint32_t> build_level_table(int n, uint32_t root_of_order_N, const s
     return tab;
 }
 
-int upload_table(uint32_t** dst, const std::vector<uint32_t>& src)
+int upload_table(DeviceBuf<uint32_t>& dst, const std::vector<uint32_t>& src)
 {
-    if (!*dst) HIP_TRY(hipMalloc((void**)dst, src.size() * 4));
-    HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * 4, hipMemcpyHostToDevice));
+    RC_TRY(dst.alloc(src.size()));
+    HIP_TRY(hipMemcpy(dst, src.data(), src.size() * 4, hipMemcpyHostToDevice));
     return FASTECC_OK;
 }
 
@@ -264,17 +264,17 @@ __global__ __launch_bounds__(256) void level_table_kernel(uint32_t* __restrict__
     tab[h + (((i & ((1u << s) - 1u)) << t) | (i >> s))] = gf::mul(r, gf::MONT_ONE);
 }
 
-int device_level_table(uint32_t** dst, int n, uint32_t root_of_order_N, const std::vector<int>& sl, hipStream_t stream)
+int device_level_table(DeviceBuf<uint32_t>& dst, int n, uint32_t root_of_order_N, const std::vector<int>& sl, hipStream_t stream)
 {
     const size_t entries = std::max<size_t>((size_t)1 << n, 2);
-    if (!*dst) HIP_TRY(hipMalloc((void**)dst, entries * 4));
+    RC_TRY(dst.alloc(entries));
     if (n < 1) {
-        HIP_TRY(hipMemsetAsync(*dst, 0, entries * 4, stream));
+        HIP_TRY(hipMemsetAsync(dst, 0, entries * 4, stream));
         return FASTECC_OK;
     }
     LevelStrides st{};
     for (int l = 0; l < n && l < 32; l++) st.sl[l] = sl[l];
-    hipLaunchKernelGGL(level_table_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, stream, *dst, n, root_of_order_N, st);
+    hipLaunchKernelGGL(level_table_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, stream, dst.get(), n, root_of_order_N, st);
     HIP_TRY(hipGetLastError());
     return FASTECC_OK;
 }
@@ -287,7 +287,7 @@ int upload_twiddles(fastecc_ctx* c)
 {
     // (the build events cover the builds and the readers on the building stream; readers on other streams hold no event: every caller that
     //  changes a plan on a live context — fastecc_set_plan, fastecc_set_option — waits for the whole device under a DeviceGuard first)
-    for (int i = 0; i < 5; i++)
+    for (int i = 0; i < TW_COUNT; i++)
         if ((c->tw_pending & (1u << i)) && c->tw_event[i]) (void)hipEventSynchronize(c->tw_event[i]);
     c->tw_pending = 0;
     c->tw_ready = 0;
@@ -296,8 +296,7 @@ int upload_twiddles(fastecc_ctx* c)
 
 const uint32_t* twiddle_table(fastecc_ctx* c, int which, hipStream_t st)
 {
-    uint32_t** slot = which == TW_ENC_DIF ? &c->tw_enc_dif : which == TW_ENC_DIT ? &c->tw_enc_dit : which == TW_NTT_FWD ? &c->tw_ntt_fwd
-                    : which == TW_NTT_INV ? &c->tw_ntt_inv : &c->tw_fold_dit;
+    DeviceBuf<uint32_t>& slot = c->tw[which];
     const unsigned bit = 1u << which;
     if (c->tw_ready & bit) {
         // built earlier by a kernel on tw_stream: a use on another stream waits for that kernel on the device, until the event is seen complete
@@ -306,7 +305,7 @@ const uint32_t* twiddle_table(fastecc_ctx* c, int which, hipStream_t st)
             else if (hipStreamWaitEvent(st, c->tw_event[which], 0) != hipSuccess) return nullptr;
             (void)hipGetLastError();  // hipErrorNotReady of the query is not an error
         }
-        return *slot;
+        return slot;
     }
     // A call that is being captured into a graph must not leave "ready, built on st" behind: the build kernel and its event would be graph
     // nodes, i.e. the table would not exist before the first replay, an eager call on the same stream would read it unbuilt, and a call on
@@ -319,17 +318,19 @@ const uint32_t* twiddle_table(fastecc_ctx* c, int which, hipStream_t st)
     }
     const bool capturing = cap != hipStreamCaptureStatusNone;
     hipStream_t caller = st;
+    Stream aside;  // the build's own stream during a capture
     hipStreamCaptureMode prev_mode = hipStreamCaptureModeRelaxed;
     if (capturing) {
         if (hipThreadExchangeStreamCaptureMode(&prev_mode) != hipSuccess) {
             (void)hip_fail(hipGetLastError(), "hipThreadExchangeStreamCaptureMode");
             return nullptr;
         }
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-            (void)hip_fail(hipGetLastError(), "hipStreamCreateWithFlags(twiddle table during capture)");
+        if (aside.try_create() != hipSuccess) {
+            (void)hip_fail(hipGetLastError(), "stream for the twiddle table during capture");
             (void)hipThreadExchangeStreamCaptureMode(&prev_mode);
             return nullptr;
         }
+        st = aside;
     }
     auto leave_capture = [&](bool ok) -> bool {
         if (!capturing) return ok;
@@ -337,7 +338,7 @@ const uint32_t* twiddle_table(fastecc_ctx* c, int which, hipStream_t st)
             (void)hip_fail(hipGetLastError(), "hipStreamSynchronize(twiddle table during capture)");
             ok = false;
         }
-        (void)hipStreamDestroy(st);
+        aside.reset();  // while the capture mode is still relaxed
         (void)hipThreadExchangeStreamCaptureMode(&prev_mode);
         st = caller;
         return ok;
@@ -362,11 +363,10 @@ const uint32_t* twiddle_table(fastecc_ctx* c, int which, hipStream_t st)
     if (capturing) {  // complete and visible to every stream: nothing pending, nothing tied to the captured stream
         c->tw_pending &= ~bit;
         c->tw_ready |= bit;
-        return *slot;
+        return slot;
     }
     // no host synchronisation: the table's first reader follows on the same stream; other streams wait for this event (above)
-    hipError_t e = hipSuccess;
-    if (!c->tw_event[which]) e = hipEventCreateWithFlags(&c->tw_event[which], hipEventDisableTiming);
+    hipError_t e = c->tw_event[which].try_create();
     if (e == hipSuccess) e = hipEventRecord(c->tw_event[which], st);
     if (e != hipSuccess) {  // no event to be had: fall back to waiting here
         (void)hipGetLastError();
@@ -380,7 +380,7 @@ const uint32_t* twiddle_table(fastecc_ctx* c, int which, hipStream_t st)
         c->tw_stream[which] = st;
     }
     c->tw_ready |= bit;
-    return *slot;
+    return slot;
 }
 
 }  // namespace fastecc

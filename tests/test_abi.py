@@ -82,6 +82,23 @@ def test_product_does_not_reference_the_oracle():
                 assert "fastecc_oracle" not in text and "libfastecc_ref" not in text, f
 
 
+def test_device_resources_have_one_owner():
+    """Device and pinned memory, events and streams are taken and given back by the owning types of devmem.hpp alone (sharded.hip, whose
+    teardown walks devices in an order of its own, keeps its raw calls): no other file under csrc names those runtime calls."""
+    calls = re.compile(r"\b(?:(?:hipMalloc|hipFree|hipHostMalloc|hipHostFree|hipEventDestroy|hipStreamDestroy)\(|hipEventCreate|hipStreamCreate)")
+    csrc = os.path.join(ROOT, "fastecc_amd", "csrc")
+    checked = 0
+    for f in sorted(os.listdir(csrc)):
+        if f in ("devmem.hpp", "sharded.hip"):
+            continue
+        text = open(os.path.join(csrc, f), errors="ignore").read()
+        for i, line in enumerate(text.splitlines(), 1):
+            m = calls.search(line)
+            assert not m, "%s:%d names %s" % (f, i, m.group(0))
+        checked += 1
+    assert checked >= 30, checked  # the directory was found and read
+
+
 def test_p61_field_host_helpers_and_validation(hip_lib):
     """FASTECC_FIELD_GF_P61_SQUARED: scalar helpers against the oracle, argument checks before any device use."""
     import fastecc_amd as fe

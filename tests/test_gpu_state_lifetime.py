@@ -220,3 +220,211 @@ def test_contexts_give_back_their_device_memory(torch_cuda, fe):
     control.close()
     torch.cuda.synchronize()
     assert free() - with_control >= largest, (with_control, free(), largest)
+
+
+# The same reading for the second test, on the commit before the context's own members became owners: three runs of its cycles, drop from cycle 2
+# to cycle 8 of 0, 0 and 0 bytes; the largest is the slack.
+CTX_SLACK = 0
+
+
+def test_context_members_give_back_their_device_memory(torch_cuda, fe, oracle):
+    """The same construction for what the context itself and the 64-bit field's path own: work stripes (scratch, parbuf, mixbuf, hostpar, dbuf,
+    rawbuf), the twiddle and mixed-radix tables, the slab streams with their events, both staging rings, the profiler's event pairs, the 64-bit
+    field's tables.  Eight identical cycles; every result equals cycle 1's bit for bit, cycle 1's equal the oracle's; free memory after cycle 8
+    against cycle 2; a held (3k/2,k) context with 4 KiB blocks, whose 4 MiB scratch stripe only the context's members own, is the control.
+
+    Three choices the codes force: (130,100) and the mixed-radix code have few enough parity blocks for the direct encoder, which needs neither
+    parbuf nor mixbuf, so both contexts turn it off; no plan at k = 2^10 is all tiles with more than one pass, which is what the option `slabs`
+    needs to put its slabs on the internal streams, so a context at k = 2^12 with plan 1060 carries it as well; and a 32 MiB stripe in host
+    memory comes down through the download ring only (the pipelined form starts at 256 MiB), so the same context also encodes a table of
+    separate blocks, which goes up through the other ring."""
+    from oracle import OracleP61
+    from pool_model import MIXED_RADIX, Codec
+    torch = torch_cuda
+    rng = np.random.default_rng(2025)
+    free = lambda: torch.cuda.mem_get_info()[0]
+    below_p = lambda *shape: rng.integers(0, P, size=shape, dtype=np.uint64).astype(np.uint32)
+    empty32 = lambda words: torch.empty(words, dtype=torch.int32, device="cuda:0")
+
+    def padded(x, pitch):
+        out = np.zeros((x.shape[0], pitch), dtype=np.uint32)
+        out[:, :x.shape[1]] = x
+        return out
+
+    # ---- everything the cycles touch, allocated up front; what the oracle says, computed once ----
+    K = 1 << 10
+    SA, PA = 64, 96  # (3k/2,k), 256-byte blocks; the pitch of its second encode
+    xa = below_p(K, SA)
+    want_a = oracle.encode_fast(xa)[::2]
+    da, da_pitched = dev32(torch, xa), dev32(torch, padded(xa, PA))
+    out_a, out_a_pitched = empty32(K // 2 * SA), empty32(K // 2 * PA)
+
+    xb = below_p(100, 8)  # (130,100), 32-byte blocks
+    want_b = Codec(oracle, 130, 100).parity(xb)
+    db, out_b = dev32(torch, xb), empty32(30 * 8)
+
+    xc = below_p(16, 16)  # (64,16), 64-byte blocks: three cosets
+    want_c = Codec(oracle, 64, 16).parity(xc)
+    dc, out_c = dev32(torch, xc), empty32(48 * 16)
+
+    xd = below_p(96, 16)  # mixed radix, order 96 = 3 * 2^5; 64 parity blocks: fewer than the 96 the transform computes
+    want_d = Codec(oracle, 160, 96, MIXED_RADIX, 96).parity(xd)
+    dd, out_d = dev32(torch, xd), empty32(64 * 16)
+
+    SE, PE = 256, 288  # (2k,k), 1 KiB blocks
+    xe = below_p(K, SE)
+    want_e, want_e_ntt, want_e_scaled = oracle.encode_fast(xe), oracle.ntt_fast(xe, False), oracle.scale_blocks(xe, 3, 5)
+    de, de_pitched = dev32(torch, xe), dev32(torch, padded(xe, PE))
+    out_e, out_e_pitched, work_e = empty32(K * SE), empty32(K * PE), empty32(K * SE)
+    raw_e = rng.integers(0, 1 << 32, size=(K, SE - 1), dtype=np.uint64).astype(np.uint32)
+    want_e_packed = oracle.pack_blocks(raw_e)
+
+    KF, SF = 1 << 12, 128  # (2k,k), 512-byte blocks, an all-tile plan of three passes
+    xf = below_p(KF, SF)
+    want_f = oracle.encode_fast(xf)
+    df, out_f = dev32(torch, xf), empty32(KF * SF)
+
+    SG = 8192  # (2k,k), 32 KiB blocks: 32 MiB in host memory
+    xg = below_p(K, SG)
+    want_g = oracle.encode_fast(xg)
+    out_g = np.empty_like(xg)
+    rows_g = np.empty((K, SG + 16), dtype=np.uint32)  # a table of blocks that do not follow one another
+
+    K61, E61 = 1 << 8, 16  # GF((2^61-1)^2), 256-byte blocks
+    x61 = rng.integers(0, P61, size=(K61, 2 * E61), dtype=np.uint64)
+    o61 = OracleP61()
+    want_61, want_61_ntt = o61.encode(x61), o61.ntt(x61, False)
+    want_61_back = o61.ntt(want_61_ntt, True)  # (unscaled)
+    d61 = dev64(torch, x61)
+    out_61, out_61_wide, work_61 = torch.empty_like(d61), torch.empty(3 * d61.numel(), dtype=torch.int64, device="cuda:0"), torch.empty_like(d61)
+
+    CS = 1024  # the control: (3k/2,k), 4 KiB blocks
+    dctl, out_ctl = dev32(torch, below_p(K, CS)), empty32(K // 2 * CS)
+    torch.cuda.synchronize()
+
+    def cycle():
+        out = {}
+        with fe.Encoder(K + K // 2, K, 4 * SA) as enc:  # scratch, the folded twiddle table
+            enc.encode(da, out_a)
+            out["fold"] = host32(out_a)
+            enc.set_option("row_pitch_words", PA)  # the work stripe goes and comes back at the new pitch
+            enc.encode(da_pitched, out_a_pitched)
+            out["fold pitched"] = host32(out_a_pitched).reshape(-1, PA)[:, :SA]
+        with fe.Encoder(130, 100, 32) as enc:  # parbuf
+            enc.set_option("encode_direct_max", 0)
+            enc.encode(db, out_b)
+            out["zero-extended"] = host32(out_b)
+        with fe.Encoder(64, 16, 64) as enc:  # scratch; from host memory: dbuf, hostpar
+            enc.encode(dc, out_c)
+            out["cosets"] = host32(out_c)
+            got = np.empty_like(want_c)
+            enc.encode(xc, got, mem=fe.MEM_HOST)
+            out["cosets host"] = got
+        with fe.Encoder(160, 96, 64, flags=fe.CODE_MIXED_RADIX) as enc:  # the four tables of the odd radix, mixbuf
+            enc.set_option("encode_direct_max", 0)
+            enc.encode(dd, out_d)
+            out["mixed"] = host32(out_d)
+        with fe.Encoder(2 * K, K, 4 * SE) as enc:
+            enc.encode(de, out_e)
+            out["encode"] = host32(out_e)
+            enc.set_option("row_pitch_words", PE)
+            enc.encode(de_pitched, out_e_pitched)
+            out["encode pitched"] = host32(out_e_pitched).reshape(-1, PE)[:, :SE]
+            enc.set_option("row_pitch_words", 0)
+            for plan in (1060, 0):  # the tables are rebuilt
+                enc.set_plan(plan)
+                enc.encode(de, out_e)
+                out["encode plan %d" % plan] = host32(out_e)
+            work_e.copy_(de)
+            enc.ntt(work_e)
+            out["ntt"] = host32(work_e)
+            enc.ntt(work_e, inverse=True)
+            enc.scale_blocks(work_e, fe.gf_inv(K), 1)  # the transforms are unscaled: 1 / k closes the round trip
+            out["ntt back"] = host32(work_e)
+            enc.scale_blocks(work_e, 3, 5)
+            out["scaled"] = host32(work_e)
+            out["in range"] = np.array([enc.check_range(de), enc.check_range(xe, mem=fe.MEM_HOST)])
+            enc.profile(True)
+            enc.encode(de, out_e)
+            torch.cuda.synchronize()
+            out["profiled"] = np.array(sorted((name, launches) for name, (_, launches, _) in enc.profile_read().items()))
+            enc.profile(False)
+            enc.set_option("slabs", 4)
+            enc.encode(de, out_e)
+            out["encode slabs"] = host32(out_e)
+            packed, raw_back = np.empty((K, SE), dtype=np.uint32), np.empty_like(raw_e)  # rawbuf
+            enc.pack_blocks(raw_e, packed, mem=fe.MEM_HOST)
+            out["unpack bad"] = np.array([enc.unpack_blocks(packed, raw_back, mem=fe.MEM_HOST)])
+            out["packed"], out["unpacked"] = packed, raw_back
+        with fe.Encoder(2 * KF, KF, 4 * SF) as enc:  # the slab streams and their events
+            enc.set_plan(1060)
+            enc.set_option("slabs", 4)
+            out["slab plan"] = np.array([enc.plan()])
+            enc.encode(df, out_f)
+            out["slabs"] = host32(out_f)
+        with fe.Encoder(2 * K, K, 4 * SG) as enc:  # both staging rings
+            enc.set_option("host_pipeline", 1)
+            enc.encode_host(xg, out_g)
+            out["host"] = out_g.copy()
+            rows_g[:, :SG] = xg
+            enc.encode_blocks([rows_g[i].ctypes.data for i in range(K)])
+            out["host blocks"] = rows_g[:, :SG].copy()
+        with fe.Encoder(2 * K61, K61, 16 * E61, field=fe.FIELD_GF_P61_SQUARED) as enc:
+            enc.encode(d61, out_61)
+            out["p61"] = host64(out_61)
+            for plan in (3, 0):
+                enc.set_plan(plan)
+                enc.encode(d61, out_61)
+                out["p61 plan %d" % plan] = host64(out_61)
+            work_61.copy_(d61)
+            enc.ntt(work_61)
+            out["p61 ntt"] = host64(work_61)
+            enc.ntt(work_61, inverse=True)
+            out["p61 ntt back"] = host64(work_61)
+        with fe.Encoder(4 * K61, K61, 16 * E61, field=fe.FIELD_GF_P61_SQUARED) as enc:  # the cosets' factor table, scratch
+            enc.encode(d61, out_61_wide)
+            out["p61 cosets"] = host64(out_61_wide)
+            work_61.copy_(d61)
+            enc.ntt(work_61)
+            out["p61 cosets ntt"] = host64(work_61)
+        torch.cuda.synchronize()
+        return out
+
+    # ---- the control: a context that is held must show in the reading ----
+    before = free()
+    control = fe.Encoder(K + K // 2, K, 4 * CS)
+    control.encode(dctl, out_ctl)
+    torch.cuda.synchronize()
+    held = free()
+    largest = K * CS * 4  # its k-block work stripe
+    assert before - held >= largest, (before, held, largest)
+
+    first, readings = None, []
+    for c in range(CYCLES):
+        out = cycle()
+        readings.append(free())
+        print("free memory after cycle %d: %d" % (c + 1, readings[-1]))
+        if first is None:
+            first = out
+            want = {"fold": want_a, "fold pitched": want_a, "zero-extended": want_b, "cosets": want_c, "cosets host": want_c, "mixed": want_d,
+                    "encode": want_e, "encode pitched": want_e, "encode plan 1060": want_e, "encode plan 0": want_e, "ntt": want_e_ntt,
+                    "ntt back": xe, "scaled": want_e_scaled, "encode slabs": want_e, "packed": want_e_packed, "unpacked": raw_e,
+                    "slabs": want_f, "host": want_g, "host blocks": want_g, "p61": want_61, "p61 plan 3": want_61, "p61 plan 0": want_61,
+                    "p61 ntt": want_61_ntt, "p61 ntt back": want_61_back, "p61 cosets ntt": want_61_ntt}
+            for name, w in want.items():
+                assert np.array_equal(out[name].reshape(w.shape), w), "cycle 1: %s differs from the oracle" % name
+            assert np.array_equal(out["p61 cosets"].reshape(3 * K61, -1)[:K61], want_61), "cycle 1: the first coset is the (2k,k) parity"
+            assert list(out["in range"]) == [0, 0] and list(out["unpack bad"]) == [0], (out["in range"], out["unpack bad"])
+            assert len(out["profiled"]) and all(int(n) > 0 for _, n in out["profiled"]), out["profiled"]
+            assert all(part.startswith("T") for part in str(out["slab plan"][0]).split()[0].split(",")), out["slab plan"]
+        else:
+            assert out.keys() == first.keys()
+            for name in first:
+                assert np.array_equal(out[name], first[name]), "cycle %d: %s differs from cycle 1" % (c + 1, name)
+    print("drop from cycle 2 to cycle 8:", readings[1] - readings[-1])
+    assert readings[1] - readings[-1] <= CTX_SLACK, readings
+
+    with_control = free()
+    control.close()
+    torch.cuda.synchronize()
+    assert free() - with_control >= largest, (with_control, free(), largest)
