@@ -27,13 +27,15 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <deque>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <string>
 #include <thread>
 #include <vector>
 
-#include "internal.hpp"
+#include "devmem.hpp"
 
 namespace fastecc {
 
@@ -41,33 +43,23 @@ namespace {
 
 constexpr int MAX_SUB = 8;
 
+// What one slab holds on its device.  The members are owners (devmem.hpp); destroy_sharded lets them go with `device` current.
 struct Shard {
     int device = 0;
-    fastecc_ctx* ctx = nullptr;  // (n, k, block_bytes / G) on `device`
-    hipStream_t s_up = nullptr, s_comp = nullptr, s_down = nullptr;
-    hipEvent_t ev_up[MAX_SUB] = {}, ev_comp[MAX_SUB] = {};
-    hipEvent_t ev_all = nullptr;  // everything this shard did for the last call
+    CtxPtr ctx;  // (n, k, block_bytes / G) on `device`
+    Stream s_up, s_comp, s_down;
+    Event ev_up[MAX_SUB], ev_comp[MAX_SUB];
+    Event ev_all;  // everything this shard did for the last call
     bool used = false;
-    char* data_slab = nullptr;    // lazy: [k][slab_bytes], for callers that hand over full stripes
-    char* parity_slab = nullptr;  // lazy: [n-k][slab_bytes], when the caller keeps no parity slabs
-    std::vector<hipStream_t> s_peer;              // lazy, all-to-all on the copy engines: one stream per destination AND direction of the pipeline
-                                                  // ([lane * G + d]; lane 0 = the data push in front, 1 = the parity transpose behind), so the G links
-                                                  // work side by side and the push of sub-slab h + 1 is not queued behind the wait for compute h
-    std::vector<hipEvent_t> ev_peer;
+    DeviceBuf<char> data_slab;    // lazy: [k][slab_bytes], for callers that hand over full stripes
+    DeviceBuf<char> parity_slab;  // lazy: [n-k][slab_bytes], when the caller keeps no parity slabs
+    std::vector<Stream> s_peer;   // lazy, all-to-all on the copy engines: one stream per destination AND direction of the pipeline
+                                  // ([lane * G + d]; lane 0 = the data push in front, 1 = the parity transpose behind), so the G links
+                                  // work side by side and the push of sub-slab h + 1 is not queued behind the wait for compute h
+    std::vector<Event> ev_peer;
 };
 
-int fail(const char* what, hipError_t e)
-{
-    set_error_detail(what, e);
-    return e == hipErrorOutOfMemory ? FASTECC_E_NOMEM : FASTECC_E_DEVICE;
-}
-
-#define SH_TRY(expr)                                  \
-    do {                                              \
-        hipError_t e_ = (expr);                       \
-        if (e_ != hipSuccess) return fail(#expr, e_); \
-    } while (0)
-
+// the caller's device is current again at the end of the scope
 struct DeviceSwitch {
     int prev = -1;
     DeviceSwitch()
@@ -117,7 +109,7 @@ __global__ __launch_bounds__(256) void all_to_all_kernel(const T* __restrict__ s
 }  // namespace
 
 struct Sharded {
-    std::vector<Shard> shards;
+    std::deque<Shard> shards;  // built at its final size (a Stream does not move), given back from the front, shard by shard (destroy_sharded)
     int root = 0;
     int field = 0;
     uint64_t K = 0, M = 0;  // data / parity blocks of the caller's stripes
@@ -126,11 +118,10 @@ struct Sharded {
     int gather_mode = 1;  // 1 = hipMemcpy2DAsync (copy engines), 2 = copy kernel on the slab's GPU
     bool copy_engine_refused = false;  // mode 2 was forced by an error return of hipMemcpy2DAsync
     int all_pairs = 0;   // fastecc_encode_sharded_blocks: 0 = not tried, 1 = every slab device can access every other one, -1 = it cannot
-    hipEvent_t fork = nullptr;
+    Event fork;          // on the root device: the point of the caller's stream a call starts from
     int stage_threads = 0;  // option "stage_threads" as last set through this context (0 = automatic)
     int fault_at = 0;    // tests only (option "inject_fault"): the fault_at-th slab step of the next call fails after its work has been enqueued
     int fault_step = 0;
-    std::string text;
 };
 
 namespace {
@@ -154,7 +145,7 @@ int copy_window(Sharded* s, void* dst, size_t dpitch, const void* src, size_t sp
     if (s->gather_mode != 2 || !device_both) {
         const hipError_t e = hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, hipMemcpyDefault, st);
         if (e == hipSuccess) return FASTECC_OK;
-        if (!device_both) return fail("hipMemcpy2DAsync", e);
+        if (!device_both) return hip_fail(e, "hipMemcpy2DAsync");
         (void)hipGetLastError();
         s->gather_mode = 2;
         s->copy_engine_refused = true;
@@ -169,8 +160,17 @@ int copy_window(Sharded* s, void* dst, size_t dpitch, const void* src, size_t sp
     else
         hipLaunchKernelGGL(copy_window_kernel<uint32_t>, dim3(blocks), dim3(256), 0, st, (const uint32_t*)src, (uint32_t*)dst,
                            (uint32_t)(width / 4), (uint64_t)(spitch / 4), (uint64_t)(dpitch / 4), total);
-    SH_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return FASTECC_OK;
+}
+
+// The host waits for everything on the shard's streams, the peer streams included (its device is current).  Errors of the wait are ignored.
+void drain(Shard& sh)
+{
+    for (const Stream* q : {&sh.s_up, &sh.s_comp, &sh.s_down})
+        if (*q) (void)hipStreamSynchronize(*q);
+    for (const Stream& q : sh.s_peer)
+        if (q) (void)hipStreamSynchronize(q);
 }
 
 // An entry point that fails half way has already forked work onto some slabs' streams.  Before the error is returned that work is waited
@@ -180,14 +180,21 @@ void settle_after_failure(Sharded* s)
 {
     for (Shard& sh : s->shards) {
         if (hipSetDevice(sh.device) != hipSuccess) continue;
-        for (hipStream_t q : {sh.s_up, sh.s_comp, sh.s_down})
-            if (q) (void)hipStreamSynchronize(q);
-        for (hipStream_t q : sh.s_peer)
-            if (q) (void)hipStreamSynchronize(q);
+        drain(sh);
         sh.used = false;  // nothing of this shard is in flight any more
     }
     (void)hipGetLastError();
 }
+
+// An entry point's device work: the caller's device is current again after it, and a failure half way is settled before it is returned
+template <class Body> int settled(Sharded* s, Body body)
+{
+    DeviceSwitch restore;
+    const int rc = body();
+    if (rc != FASTECC_OK) settle_after_failure(s);
+    return rc;
+}
+
 // tests only: the "inject_fault"-th slab step of a call reports a device error AFTER its copies / kernels have been enqueued
 bool injected_fault(Sharded* s)
 {
@@ -199,6 +206,62 @@ bool injected_fault(Sharded* s)
     return true;
 }
 
+// Column sub-slabs of a call: the option, halved until the device context can encode the column range (whole 128-byte row segments)
+int sub_slab_count(const Sharded* s)
+{
+    int H = std::max(1, std::min(s->sub_slabs, MAX_SUB));
+    while (H > 1 && (!columns_supported(s->shards[0].ctx) || ((s->slab_bytes / 4) % (32u * H)) != 0)) H >>= 1;
+    return H;
+}
+
+// The shard's own slab buffers, at their first use (its device is current)
+int own_slabs(Sharded* s, Shard& sh, bool want_data, bool want_parity)
+{
+    if (want_data) RC_TRY(sh.data_slab.alloc(s->K * s->slab_bytes));
+    if (want_parity) RC_TRY(sh.parity_slab.alloc(s->M * s->slab_bytes));
+    return FASTECC_OK;
+}
+
+// How a call is ordered against the caller's stream and the call before it, three rules that every data path below goes through:
+// record_fork  the call's starting point on the caller's stream `st` (the root's)
+// start_after  each of `streams`, of one shard whose device is current, starts after that point and after the previous call of shards [o0, o1)
+// join         the caller's stream goes on after everything the call did on every shard
+int record_fork(Sharded* s, hipStream_t st)
+{
+    HIP_TRY(hipSetDevice(s->root));
+    HIP_TRY(hipEventRecord(s->fork, st));
+    return FASTECC_OK;
+}
+int start_after(Sharded* s, std::initializer_list<hipStream_t> streams, int o0, int o1)
+{
+    for (hipStream_t q : streams) {
+        HIP_TRY(hipStreamWaitEvent(q, s->fork, 0));
+        for (int o = o0; o < o1; o++)
+            if (s->shards[o].used) HIP_TRY(hipStreamWaitEvent(q, s->shards[o].ev_all, 0));
+    }
+    return FASTECC_OK;
+}
+int join(fastecc_ctx* shell, hipStream_t st)
+{
+    Sharded* s = sharded_of(shell);
+    HIP_TRY(hipSetDevice(s->root));
+    for (Shard& sh : s->shards) HIP_TRY(hipStreamWaitEvent(st, sh.ev_all, 0));
+    if (s->copy_engine_refused) describe(shell);
+    return FASTECC_OK;
+}
+
+// Sub-slab h of a shard's slab on s_comp, the whole slab where H = 1; what s_down does next comes after it
+int encode_sub_slab(Sharded* s, Shard& sh, const char* din, char* pout, int H, int h, size_t wbytes)
+{
+    RC_TRY(H > 1 ? fastecc_encode_columns(sh.ctx, din, pout, h * wbytes / 4, wbytes / 4, sh.s_comp)
+                 : fastecc_encode(sh.ctx, din, pout, FASTECC_MEM_DEVICE, sh.s_comp));
+    if (injected_fault(s)) return FASTECC_E_DEVICE;
+    HIP_TRY(hipSetDevice(sh.device));  // the entry points restore the caller's device; keep ours explicit
+    HIP_TRY(hipEventRecord(sh.ev_comp[h], sh.s_comp));
+    HIP_TRY(hipStreamWaitEvent(sh.s_down, sh.ev_comp[h], 0));
+    return FASTECC_OK;
+}
+
 // The whole data path.  Exactly one of (data_slabs, data_stripe) and at least one of (parity_slabs, parity_stripe).
 // stripe_on_host: the stripes are host memory (each GPU uses its own host link), else the root device's memory.
 int run_body(fastecc_ctx* shell, const void* const* data_slabs, const void* data_stripe, void* const* parity_slabs, void* parity_stripe,
@@ -207,64 +270,33 @@ int run_body(fastecc_ctx* shell, const void* const* data_slabs, const void* data
     Sharded* s = sharded_of(shell);
     const int G = (int)s->shards.size();
     const size_t slab = s->slab_bytes, full = s->block_bytes;
-    DeviceSwitch restore;
-
-    // sub-slabs only where the device context can encode a column range
-    int H = std::max(1, std::min(s->sub_slabs, MAX_SUB));
-    const uint64_t slab_words = slab / 4;
-    while (H > 1 && (!columns_supported(s->shards[0].ctx) || (slab_words % (32u * H)) != 0)) H >>= 1;
+    const int H = sub_slab_count(s);
     const size_t wbytes = slab / H;
 
-    SH_TRY(hipSetDevice(s->root));
-    SH_TRY(hipEventRecord(s->fork, st));
-
+    RC_TRY(record_fork(s, st));
     for (int g = 0; g < G; g++) {
         Shard& sh = s->shards[g];
-        SH_TRY(hipSetDevice(sh.device));
-        const char* din = data_slabs ? (const char*)data_slabs[g] : nullptr;
-        if (!din) {
-            if (!sh.data_slab) SH_TRY(hipMalloc((void**)&sh.data_slab, s->K * slab));
-            din = sh.data_slab;
-        }
-        char* pout = parity_slabs ? (char*)parity_slabs[g] : nullptr;
-        if (!pout) {
-            if (!sh.parity_slab) SH_TRY(hipMalloc((void**)&sh.parity_slab, s->M * slab));
-            pout = sh.parity_slab;
-        }
-        // this call starts after prior work on the caller's stream and after the shard's previous call
-        for (hipStream_t q : {sh.s_up, sh.s_comp}) {
-            SH_TRY(hipStreamWaitEvent(q, s->fork, 0));
-            if (sh.used) SH_TRY(hipStreamWaitEvent(q, sh.ev_all, 0));
-        }
+        HIP_TRY(hipSetDevice(sh.device));
+        RC_TRY(own_slabs(s, sh, !data_slabs, !parity_slabs));
+        const char* din = data_slabs ? (const char*)data_slabs[g] : sh.data_slab.get();
+        char* pout = parity_slabs ? (char*)parity_slabs[g] : sh.parity_slab.get();
+        RC_TRY(start_after(s, {sh.s_up, sh.s_comp}, g, g + 1));
         for (int h = 0; h < H; h++) {
             const size_t col = (size_t)h * wbytes;
             if (data_stripe) {
-                const int rc = copy_window(s, sh.data_slab + col, slab, (const char*)data_stripe + (size_t)g * slab + col, full, wbytes, s->K,
-                                           !stripe_on_host, sh.s_up);
-                if (rc != FASTECC_OK) return rc;
-                SH_TRY(hipEventRecord(sh.ev_up[h], sh.s_up));
-                SH_TRY(hipStreamWaitEvent(sh.s_comp, sh.ev_up[h], 0));
+                RC_TRY(copy_window(s, sh.data_slab + col, slab, (const char*)data_stripe + (size_t)g * slab + col, full, wbytes, s->K, !stripe_on_host,
+                                   sh.s_up));
+                HIP_TRY(hipEventRecord(sh.ev_up[h], sh.s_up));
+                HIP_TRY(hipStreamWaitEvent(sh.s_comp, sh.ev_up[h], 0));
             }
-            const int rc = H > 1 ? fastecc_encode_columns(sh.ctx, din, pout, col / 4, wbytes / 4, sh.s_comp)
-                                 : fastecc_encode(sh.ctx, din, pout, FASTECC_MEM_DEVICE, sh.s_comp);
-            if (rc != FASTECC_OK) return rc;
-            if (injected_fault(s)) return FASTECC_E_DEVICE;
-            SH_TRY(hipSetDevice(sh.device));  // the entry points restore the caller's device; keep ours explicit
-            SH_TRY(hipEventRecord(sh.ev_comp[h], sh.s_comp));
-            SH_TRY(hipStreamWaitEvent(sh.s_down, sh.ev_comp[h], 0));
-            if (parity_stripe) {
-                const int rc2 = copy_window(s, (char*)parity_stripe + (size_t)g * slab + col, full, pout + col, slab, wbytes, s->M,
-                                            !stripe_on_host, sh.s_down);
-                if (rc2 != FASTECC_OK) return rc2;
-            }
+            RC_TRY(encode_sub_slab(s, sh, din, pout, H, h, wbytes));
+            if (parity_stripe)
+                RC_TRY(copy_window(s, (char*)parity_stripe + (size_t)g * slab + col, full, pout + col, slab, wbytes, s->M, !stripe_on_host, sh.s_down));
         }
-        SH_TRY(hipEventRecord(sh.ev_all, sh.s_down));
+        HIP_TRY(hipEventRecord(sh.ev_all, sh.s_down));
         sh.used = true;
     }
-    SH_TRY(hipSetDevice(s->root));
-    for (int g = 0; g < G; g++) SH_TRY(hipStreamWaitEvent(st, s->shards[g].ev_all, 0));
-    if (s->copy_engine_refused) describe(shell);
-    return FASTECC_OK;
+    return join(shell, st);
 }
 
 // Stripes in PAGEABLE host memory (fastecc_encode with FASTECC_MEM_HOST on a sharded context): every slab has a host thread of its own that
@@ -277,15 +309,12 @@ int run_host_pageable(fastecc_ctx* shell, const void* data_stripe, void* parity_
     Sharded* s = sharded_of(shell);
     const int G = (int)s->shards.size();
     const size_t slab = s->slab_bytes, full = s->block_bytes;
-    DeviceSwitch restore;
-    SH_TRY(hipSetDevice(s->root));
-    SH_TRY(hipStreamSynchronize(st));
-    for (int g = 0; g < G; g++) {  // allocations and the previous call's tail, on this thread
-        Shard& sh = s->shards[g];
-        SH_TRY(hipSetDevice(sh.device));
-        if (!sh.data_slab) SH_TRY(hipMalloc((void**)&sh.data_slab, s->K * slab));
-        if (!sh.parity_slab) SH_TRY(hipMalloc((void**)&sh.parity_slab, s->M * slab));
-        if (sh.used) SH_TRY(hipEventSynchronize(sh.ev_all));
+    HIP_TRY(hipSetDevice(s->root));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (Shard& sh : s->shards) {  // allocations and the previous call's tail, on this thread
+        HIP_TRY(hipSetDevice(sh.device));
+        RC_TRY(own_slabs(s, sh, true, true));
+        if (sh.used) HIP_TRY(hipEventSynchronize(sh.ev_all));
     }
     const unsigned hw = std::thread::hardware_concurrency();
     // helper threads per slab: the "stage_threads" option of the slab contexts where it is set, else a share of the host's threads
@@ -335,15 +364,6 @@ int run_host_pageable(fastecc_ctx* shell, const void* data_stripe, void* parity_
     return FASTECC_OK;
 }
 
-int run(fastecc_ctx* shell, const void* const* data_slabs, const void* data_stripe, void* const* parity_slabs, void* parity_stripe, bool stripe_on_host,
-        hipStream_t st)
-{
-    DeviceSwitch restore;
-    const int rc = run_body(shell, data_slabs, data_stripe, parity_slabs, parity_stripe, stripe_on_host, st);
-    if (rc != FASTECC_OK) settle_after_failure(sharded_of(shell));
-    return rc;
-}
-
 // every slab device must reach every other one's memory (the gather only needs slab device -> root)
 int enable_all_pairs(Sharded* s)
 {
@@ -357,9 +377,9 @@ int enable_all_pairs(Sharded* s)
                 s->all_pairs = -1;
                 return FASTECC_E_UNSUPPORTED;
             }
-            SH_TRY(hipSetDevice(a.device));
+            HIP_TRY(hipSetDevice(a.device));
             const hipError_t e = hipDeviceEnablePeerAccess(b.device, 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return fail("hipDeviceEnablePeerAccess", e);
+            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return hip_fail(e, "hipDeviceEnablePeerAccess");
             (void)hipGetLastError();
         }
     s->all_pairs = 1;
@@ -376,29 +396,29 @@ int all_to_all_step(Sharded* s, Shard& sh, void* const* dst, size_t dpitch, cons
     if (rows == 0 || width == 0) return FASTECC_OK;
     if (s->gather_mode != 2) {
         if (sh.s_peer.empty()) {
-            sh.s_peer.assign(2 * (size_t)G, nullptr);
-            sh.ev_peer.assign(2 * (size_t)G, nullptr);
+            sh.s_peer = std::vector<Stream>(2 * (size_t)G);
+            sh.ev_peer = std::vector<Event>(2 * (size_t)G);
             for (int d = 0; d < 2 * G; d++) {
-                SH_TRY(hipStreamCreateWithFlags(&sh.s_peer[d], hipStreamNonBlocking));
-                SH_TRY(hipEventCreateWithFlags(&sh.ev_peer[d], hipEventDisableTiming));
+                RC_TRY(sh.s_peer[d].create());
+                RC_TRY(sh.ev_peer[d].create());
             }
         }
-        hipStream_t* const peer = sh.s_peer.data() + (size_t)(lane ? G : 0);
-        hipEvent_t* const pev = sh.ev_peer.data() + (size_t)(lane ? G : 0);
+        const Stream* const peer = sh.s_peer.data() + (size_t)(lane ? G : 0);
+        const Event* const pev = sh.ev_peer.data() + (size_t)(lane ? G : 0);
         bool refused = false;
         for (int d = 0; d < G && !refused; d++) {
-            SH_TRY(hipStreamWaitEvent(peer[d], after, 0));
+            HIP_TRY(hipStreamWaitEvent(peer[d], after, 0));
             const hipError_t e = hipMemcpy2DAsync(dst[d], dpitch, src + (size_t)d * sstride, spitch, width, rows, hipMemcpyDefault, peer[d]);
             if (e != hipSuccess) {  // a runtime that refuses pitched peer copies: the copy kernel takes over for good (as in copy_window)
                 (void)hipGetLastError();
                 s->gather_mode = 2;
                 s->copy_engine_refused = true;
                 refused = true;
-                for (int f = 0; f < d; f++) SH_TRY(hipStreamSynchronize(peer[f]));  // what was enqueued is simply repeated below
+                for (int f = 0; f < d; f++) HIP_TRY(hipStreamSynchronize(peer[f]));  // what was enqueued is simply repeated below
                 break;
             }
-            SH_TRY(hipEventRecord(pev[d], peer[d]));
-            SH_TRY(hipStreamWaitEvent(st, pev[d], 0));
+            HIP_TRY(hipEventRecord(pev[d], peer[d]));
+            HIP_TRY(hipStreamWaitEvent(st, pev[d], 0));
         }
         if (!refused) return FASTECC_OK;
     }
@@ -418,7 +438,7 @@ int all_to_all_step(Sharded* s, Shard& sh, void* const* dst, size_t dpitch, cons
     else
         hipLaunchKernelGGL(all_to_all_kernel<uint32_t>, dim3(blocks), dim3(256), 0, st, (const uint32_t*)src, pp, (uint32_t)(width / 4), (uint32_t)rows,
                            (uint64_t)(spitch / 4), (uint64_t)(sstride / 4), (uint64_t)(dpitch / 4), total);
-    SH_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return FASTECC_OK;
 }
 
@@ -434,30 +454,17 @@ int run_blocks_body(fastecc_ctx* shell, const void* const* data, bool data_block
     const int G = (int)s->shards.size();
     const size_t slab = s->slab_bytes, full = s->block_bytes;
     const uint64_t kg = s->K / G, mg = s->M / G;
-    DeviceSwitch restore;
-    {
-        const int rc = enable_all_pairs(s);
-        if (rc != FASTECC_OK) return rc;
-    }
-    int H = std::max(1, std::min(s->sub_slabs, MAX_SUB));
-    const uint64_t slab_words = slab / 4;
-    while (H > 1 && (!columns_supported(s->shards[0].ctx) || (slab_words % (32u * H)) != 0)) H >>= 1;
+    RC_TRY(enable_all_pairs(s));
+    const int H = sub_slab_count(s);
     const size_t wbytes = slab / H;
 
-    SH_TRY(hipSetDevice(s->root));
-    SH_TRY(hipEventRecord(s->fork, st));
+    RC_TRY(record_fork(s, st));
     // buffers, and the start of this call on every stream: after prior work on the caller's stream and after EVERY shard's previous call
     // (the pushes write into other shards' slab buffers, the transposes out into other shards' result blocks)
-    for (int g = 0; g < G; g++) {
-        Shard& sh = s->shards[g];
-        SH_TRY(hipSetDevice(sh.device));
-        if (data_blocks && !sh.data_slab) SH_TRY(hipMalloc((void**)&sh.data_slab, s->K * slab));
-        if (!sh.parity_slab) SH_TRY(hipMalloc((void**)&sh.parity_slab, s->M * slab));
-        for (hipStream_t q : {sh.s_up, sh.s_comp, sh.s_down}) {
-            SH_TRY(hipStreamWaitEvent(q, s->fork, 0));
-            for (int o = 0; o < G; o++)
-                if (s->shards[o].used) SH_TRY(hipStreamWaitEvent(q, s->shards[o].ev_all, 0));
-        }
+    for (Shard& sh : s->shards) {
+        HIP_TRY(hipSetDevice(sh.device));
+        RC_TRY(own_slabs(s, sh, data_blocks, true));
+        RC_TRY(start_after(s, {sh.s_up, sh.s_comp, sh.s_down}, 0, G));
     }
     std::vector<void*> dst(G);
     for (int h = 0; h < H; h++) {
@@ -465,105 +472,73 @@ int run_blocks_body(fastecc_ctx* shell, const void* const* data, bool data_block
         if (data_blocks) {
             for (int g = 0; g < G; g++) {  // GPU g pushes sub-slab h of its blocks to everyone
                 Shard& sh = s->shards[g];
-                SH_TRY(hipSetDevice(sh.device));
+                HIP_TRY(hipSetDevice(sh.device));
                 for (int d = 0; d < G; d++) dst[d] = s->shards[d].data_slab + (size_t)g * kg * slab + col;
-                SH_TRY(hipEventRecord(sh.ev_up[h], sh.s_up));  // the point the copy-engine form forks from; recorded again after the step
-                const int rc = all_to_all_step(s, sh, dst.data(), slab, (const char*)data[g] + col, full, slab, wbytes, kg, sh.s_up, sh.ev_up[h], 0);
-                if (rc != FASTECC_OK) return rc;
-                SH_TRY(hipEventRecord(sh.ev_up[h], sh.s_up));
+                HIP_TRY(hipEventRecord(sh.ev_up[h], sh.s_up));  // the point the copy-engine form forks from; recorded again after the step
+                RC_TRY(all_to_all_step(s, sh, dst.data(), slab, (const char*)data[g] + col, full, slab, wbytes, kg, sh.s_up, sh.ev_up[h], 0));
+                HIP_TRY(hipEventRecord(sh.ev_up[h], sh.s_up));
             }
         }
         for (int g = 0; g < G; g++) {
             Shard& sh = s->shards[g];
-            SH_TRY(hipSetDevice(sh.device));
+            HIP_TRY(hipSetDevice(sh.device));
             if (data_blocks)
-                for (int o = 0; o < G; o++) SH_TRY(hipStreamWaitEvent(sh.s_comp, s->shards[o].ev_up[h], 0));
-            const char* din = data_blocks ? sh.data_slab : (const char*)data[g];
-            const int rc = H > 1 ? fastecc_encode_columns(sh.ctx, din, sh.parity_slab, col / 4, wbytes / 4, sh.s_comp)
-                                 : fastecc_encode(sh.ctx, din, sh.parity_slab, FASTECC_MEM_DEVICE, sh.s_comp);
-            if (rc != FASTECC_OK) return rc;
-            if (injected_fault(s)) return FASTECC_E_DEVICE;
-            SH_TRY(hipSetDevice(sh.device));
-            SH_TRY(hipEventRecord(sh.ev_comp[h], sh.s_comp));
-            SH_TRY(hipStreamWaitEvent(sh.s_down, sh.ev_comp[h], 0));
+                for (Shard& o : s->shards) HIP_TRY(hipStreamWaitEvent(sh.s_comp, o.ev_up[h], 0));
+            RC_TRY(encode_sub_slab(s, sh, data_blocks ? sh.data_slab.get() : (const char*)data[g], sh.parity_slab, H, h, wbytes));
             for (int d = 0; d < G; d++) dst[d] = (char*)parity_blocks[d] + (size_t)g * slab + col;
-            const int rc2 = all_to_all_step(s, sh, dst.data(), full, sh.parity_slab + col, slab, (size_t)mg * slab, wbytes, mg, sh.s_down, sh.ev_comp[h], 1);
-            if (rc2 != FASTECC_OK) return rc2;
+            RC_TRY(all_to_all_step(s, sh, dst.data(), full, sh.parity_slab + col, slab, (size_t)mg * slab, wbytes, mg, sh.s_down, sh.ev_comp[h], 1));
         }
     }
-    for (int g = 0; g < G; g++) {
-        Shard& sh = s->shards[g];
-        SH_TRY(hipSetDevice(sh.device));
+    for (Shard& sh : s->shards) {
+        HIP_TRY(hipSetDevice(sh.device));
         if (data_blocks) {  // the slab buffers are free again once the last push AND the last read of them are done
-            SH_TRY(hipEventRecord(sh.ev_up[0], sh.s_up));
-            SH_TRY(hipStreamWaitEvent(sh.s_down, sh.ev_up[0], 0));
+            HIP_TRY(hipEventRecord(sh.ev_up[0], sh.s_up));
+            HIP_TRY(hipStreamWaitEvent(sh.s_down, sh.ev_up[0], 0));
         }
-        SH_TRY(hipEventRecord(sh.ev_all, sh.s_down));
+        HIP_TRY(hipEventRecord(sh.ev_all, sh.s_down));
         sh.used = true;
     }
-    SH_TRY(hipSetDevice(s->root));
-    for (int g = 0; g < G; g++) SH_TRY(hipStreamWaitEvent(st, s->shards[g].ev_all, 0));
-    if (s->copy_engine_refused) describe(shell);
-    return FASTECC_OK;
+    return join(shell, st);
 }
 
 // Decoding on a sharded context: erasures hit whole blocks, so every slab sees the same pattern and repairs its own columns
 // with its device context's decoder.  Full stripes (root memory or host): slab g of data and parity is pulled to GPU g,
 // repaired in place, and the data slab (with `repair`: the parity slab too) pushed back; only the columns move, no exchange
-// between slabs.  data_slabs / parity_slabs given: the slabs are repaired where they live.
-int run_decode_body(fastecc_ctx* shell, void* data_stripe, void* parity_stripe, void* const* data_slabs, void* const* parity_slabs, bool stripe_on_host,
-                    bool repair, hipStream_t st)
+// between slabs.
+int run_decode_body(fastecc_ctx* shell, void* data_stripe, void* parity_stripe, bool stripe_on_host, bool repair, hipStream_t st)
 {
     Sharded* s = sharded_of(shell);
     const int G = (int)s->shards.size();
     const size_t slab = s->slab_bytes, full = s->block_bytes;
-    DeviceSwitch restore;
-    SH_TRY(hipSetDevice(s->root));
-    SH_TRY(hipEventRecord(s->fork, st));
+    RC_TRY(record_fork(s, st));
     for (int g = 0; g < G; g++) {
         Shard& sh = s->shards[g];
-        SH_TRY(hipSetDevice(sh.device));
-        char* d = data_slabs ? (char*)data_slabs[g] : nullptr;
-        char* p = parity_slabs ? (char*)parity_slabs[g] : nullptr;
-        if (!d) {
-            if (!sh.data_slab) SH_TRY(hipMalloc((void**)&sh.data_slab, s->K * slab));
-            if (!sh.parity_slab) SH_TRY(hipMalloc((void**)&sh.parity_slab, s->M * slab));
-            d = sh.data_slab;
-            p = sh.parity_slab;
-        }
+        HIP_TRY(hipSetDevice(sh.device));
+        RC_TRY(own_slabs(s, sh, true, true));
+        char* const d = sh.data_slab;
+        char* const p = sh.parity_slab;
         hipStream_t q = sh.s_comp;  // one stream per slab: pull, repair, push
-        SH_TRY(hipStreamWaitEvent(q, s->fork, 0));
-        if (sh.used) SH_TRY(hipStreamWaitEvent(q, sh.ev_all, 0));
-        if (!data_slabs) {
-            int rc = copy_window(s, d, slab, (const char*)data_stripe + (size_t)g * slab, full, slab, s->K, !stripe_on_host, q);
-            if (rc == FASTECC_OK) rc = copy_window(s, p, slab, (const char*)parity_stripe + (size_t)g * slab, full, slab, s->M, !stripe_on_host, q);
-            if (rc != FASTECC_OK) return rc;
-        }
-        const int rc = repair ? fastecc_repair(sh.ctx, d, p, FASTECC_MEM_DEVICE, q) : fastecc_decode(sh.ctx, d, p, FASTECC_MEM_DEVICE, q);
-        if (rc != FASTECC_OK) return rc;
+        RC_TRY(start_after(s, {q}, g, g + 1));
+        RC_TRY(copy_window(s, d, slab, (const char*)data_stripe + (size_t)g * slab, full, slab, s->K, !stripe_on_host, q));
+        RC_TRY(copy_window(s, p, slab, (const char*)parity_stripe + (size_t)g * slab, full, slab, s->M, !stripe_on_host, q));
+        RC_TRY(repair ? fastecc_repair(sh.ctx, d, p, FASTECC_MEM_DEVICE, q) : fastecc_decode(sh.ctx, d, p, FASTECC_MEM_DEVICE, q));
         if (injected_fault(s)) return FASTECC_E_DEVICE;
-        SH_TRY(hipSetDevice(sh.device));
-        if (!data_slabs) {
-            int rc2 = copy_window(s, (char*)data_stripe + (size_t)g * slab, full, d, slab, slab, s->K, !stripe_on_host, q);
-            if (rc2 == FASTECC_OK && repair) rc2 = copy_window(s, (char*)parity_stripe + (size_t)g * slab, full, p, slab, slab, s->M, !stripe_on_host, q);
-            if (rc2 != FASTECC_OK) return rc2;
-        }
-        SH_TRY(hipEventRecord(sh.ev_all, q));
+        HIP_TRY(hipSetDevice(sh.device));
+        RC_TRY(copy_window(s, (char*)data_stripe + (size_t)g * slab, full, d, slab, slab, s->K, !stripe_on_host, q));
+        if (repair) RC_TRY(copy_window(s, (char*)parity_stripe + (size_t)g * slab, full, p, slab, slab, s->M, !stripe_on_host, q));
+        HIP_TRY(hipEventRecord(sh.ev_all, q));
         sh.used = true;
     }
-    SH_TRY(hipSetDevice(s->root));
-    for (int g = 0; g < G; g++) SH_TRY(hipStreamWaitEvent(st, s->shards[g].ev_all, 0));
-    if (s->copy_engine_refused) describe(shell);
-    return FASTECC_OK;
+    return join(shell, st);
 }
 
-int run_decode(fastecc_ctx* shell, void* data_stripe, void* parity_stripe, void* const* data_slabs, void* const* parity_slabs, bool stripe_on_host, bool repair,
-               hipStream_t st)
+// A host stripe's call is synchronous: the host waits for the caller's stream (the root's)
+int wait_for_caller(Sharded* s, hipStream_t st)
 {
     DeviceSwitch restore;
-    const int rc = run_decode_body(shell, data_stripe, parity_stripe, data_slabs, parity_slabs, stripe_on_host, repair, st);
-    if (rc != FASTECC_OK) settle_after_failure(sharded_of(shell));
-    return rc;
+    HIP_TRY(hipSetDevice(s->root));
+    HIP_TRY(hipStreamSynchronize(st));
+    return FASTECC_OK;
 }
 
 }  // namespace
@@ -613,71 +588,48 @@ int sharded_decode_prepare(fastecc_ctx* shell, const uint8_t* data_present, cons
 int sharded_decode_stripe(fastecc_ctx* shell, void* data, void* parity, int mem_kind, bool repair, hipStream_t st)
 {
     if (mem_kind != FASTECC_MEM_DEVICE && mem_kind != FASTECC_MEM_HOST && mem_kind != FASTECC_MEM_HOST_PINNED) return FASTECC_E_INVAL;
+    Sharded* s = sharded_of(shell);
     std::lock_guard<std::mutex> lk(mutex_of(shell));
-    const int rc = run_decode(shell, data, parity, nullptr, nullptr, mem_kind != FASTECC_MEM_DEVICE, repair, st);
+    const int rc = settled(s, [&] { return run_decode_body(shell, data, parity, mem_kind != FASTECC_MEM_DEVICE, repair, st); });
     // host stripes, pageable or pinned: synchronous, as include/fastecc.h says for fastecc_decode / fastecc_repair (the single-device path
     // stages both kinds the same way)
     if (rc != FASTECC_OK || mem_kind == FASTECC_MEM_DEVICE) return rc;
-    DeviceSwitch restore;
-    SH_TRY(hipSetDevice(sharded_of(shell)->root));
-    SH_TRY(hipStreamSynchronize(st));
-    return FASTECC_OK;
+    return wait_for_caller(s, st);
 }
 
+// Shard by shard, each with its device current, as far as that device can still be made current.  Three things are decisions and stay written
+// out: the host waits for the shard's streams before anything of the shard is given back; the shard's context goes before the streams and
+// events its work was ordered by; `fork` goes under the root device.  Everything else is the members' destructors (devmem.hpp).
 void destroy_sharded(Sharded* s)
 {
     if (!s) return;
     DeviceSwitch restore;
-    for (Shard& sh : s->shards) {
-        if (hipSetDevice(sh.device) != hipSuccess) continue;
-        for (hipStream_t q : {sh.s_up, sh.s_comp, sh.s_down})
-            if (q) (void)hipStreamSynchronize(q);
-        if (sh.ctx) fastecc_destroy(sh.ctx);
-        for (int h = 0; h < MAX_SUB; h++) {
-            if (sh.ev_up[h]) (void)hipEventDestroy(sh.ev_up[h]);
-            if (sh.ev_comp[h]) (void)hipEventDestroy(sh.ev_comp[h]);
-        }
-        if (sh.ev_all) (void)hipEventDestroy(sh.ev_all);
-        for (hipStream_t q : {sh.s_up, sh.s_comp, sh.s_down})
-            if (q) (void)hipStreamDestroy(q);
-        for (hipStream_t q : sh.s_peer)
-            if (q) {
-                (void)hipStreamSynchronize(q);
-                (void)hipStreamDestroy(q);
-            }
-        for (hipEvent_t e : sh.ev_peer)
-            if (e) (void)hipEventDestroy(e);
-        if (sh.data_slab) (void)hipFree(sh.data_slab);
-        if (sh.parity_slab) (void)hipFree(sh.parity_slab);
+    while (!s->shards.empty()) {
+        Shard& sh = s->shards.front();
+        if (hipSetDevice(sh.device) == hipSuccess) drain(sh);
+        sh.ctx.reset();
+        s->shards.pop_front();
     }
-    if (s->fork && hipSetDevice(s->root) == hipSuccess) (void)hipEventDestroy(s->fork);
+    (void)hipSetDevice(s->root);
     delete s;
 }
 
 int sharded_encode_stripe(fastecc_ctx* shell, const void* data, void* parity, int mem_kind, hipStream_t st)
 {
     if (mem_kind != FASTECC_MEM_DEVICE && mem_kind != FASTECC_MEM_HOST && mem_kind != FASTECC_MEM_HOST_PINNED) return FASTECC_E_INVAL;
-    if (parity == data && sharded_of(shell)->M > sharded_of(shell)->K) return FASTECC_E_INVAL;  // in place: the parity must fit the data stripe (as fastecc_encode on one device)
+    Sharded* s = sharded_of(shell);
+    if (parity == data && s->M > s->K) return FASTECC_E_INVAL;  // in place: the parity must fit the data stripe (as fastecc_encode on one device)
     std::lock_guard<std::mutex> lk(mutex_of(shell));
-    if (mem_kind == FASTECC_MEM_HOST && parity != data) {
-        DeviceSwitch restore;
-        const int rp = run_host_pageable(shell, data, parity, st);
-        if (rp != FASTECC_OK) settle_after_failure(sharded_of(shell));
-        return rp;
-    }
-    const int rc = run(shell, nullptr, data, nullptr, parity, mem_kind != FASTECC_MEM_DEVICE, st);
+    if (mem_kind == FASTECC_MEM_HOST && parity != data) return settled(s, [&] { return run_host_pageable(shell, data, parity, st); });
+    const int rc = settled(s, [&] { return run_body(shell, nullptr, data, nullptr, parity, mem_kind != FASTECC_MEM_DEVICE, st); });
     if (rc != FASTECC_OK || mem_kind != FASTECC_MEM_HOST) return rc;
-    // pageable host memory: the call is synchronous, like fastecc_encode on one device
-    DeviceSwitch restore;
-    SH_TRY(hipSetDevice(sharded_of(shell)->root));
-    SH_TRY(hipStreamSynchronize(st));
-    return FASTECC_OK;
+    return wait_for_caller(s, st);  // pageable host memory: the call is synchronous, like fastecc_encode on one device
 }
 
 fastecc_ctx* sharded_child(fastecc_ctx* shell, int g)
 {
     Sharded* s = sharded_of(shell);
-    return (s && g >= 0 && g < (int)s->shards.size()) ? s->shards[g].ctx : nullptr;
+    return (s && g >= 0 && g < (int)s->shards.size()) ? s->shards[g].ctx.get() : nullptr;
 }
 
 int sharded_forward(fastecc_ctx* shell, int what, const char* name, int value)
@@ -736,7 +688,7 @@ int fastecc_create_sharded(fastecc_ctx** out, uint64_t n, uint64_t k, uint64_t b
     int ndev = 0;
     {
         const hipError_t e = hipGetDeviceCount(&ndev);
-        if (e != hipSuccess || ndev <= 0) return fail("hipGetDeviceCount", e == hipSuccess ? hipErrorNoDevice : e);
+        if (e != hipSuccess || ndev <= 0) return hip_fail(e == hipSuccess ? hipErrorNoDevice : e, "hipGetDeviceCount");
     }
     for (int g = 0; g < n_gpus; g++)
         if (gpu_ids[g] < 0 || gpu_ids[g] >= ndev) return FASTECC_E_INVAL;
@@ -755,46 +707,43 @@ int fastecc_create_sharded(fastecc_ctx** out, uint64_t n, uint64_t k, uint64_t b
     s->M = n - k;
     s->block_bytes = block_bytes;
     s->slab_bytes = block_bytes / n_gpus;
-    s->shards.resize(n_gpus);
+    s->shards = std::deque<Shard>(n_gpus);
     DeviceSwitch restore;
-    auto bail = [&](int rc) {
-        fastecc_destroy(shell);
-        return rc;
-    };
-    for (int g = 0; g < n_gpus; g++) {
-        Shard& sh = s->shards[g];
-        sh.device = gpu_ids[g];
-        if (sh.device != s->root) {
-            int can = 0;
-            if (hipDeviceCanAccessPeer(&can, sh.device, s->root) != hipSuccess || !can) {
-                set_error_detail("hipDeviceCanAccessPeer(slab device -> root)", hipErrorPeerAccessUnsupported);
-                return bail(FASTECC_E_UNSUPPORTED);
+    auto build = [&]() -> int {
+        for (int g = 0; g < n_gpus; g++) {
+            Shard& sh = s->shards[g];
+            sh.device = gpu_ids[g];
+            if (sh.device != s->root) {
+                int can = 0;
+                if (hipDeviceCanAccessPeer(&can, sh.device, s->root) != hipSuccess || !can) {
+                    set_error_detail("hipDeviceCanAccessPeer(slab device -> root)", hipErrorPeerAccessUnsupported);
+                    return FASTECC_E_UNSUPPORTED;
+                }
             }
+            hipError_t e = hipSetDevice(sh.device);
+            if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+            if (sh.device != s->root) {
+                e = hipDeviceEnablePeerAccess(s->root, 0);
+                if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return hip_fail(e, "hipDeviceEnablePeerAccess");
+                (void)hipGetLastError();
+            }
+            RC_TRY(fastecc_create(sh.ctx.fill(), n, k, s->slab_bytes, field, sh.device));
+            for (Stream* q : {&sh.s_up, &sh.s_comp, &sh.s_down}) RC_TRY(q->create());
+            for (int h = 0; h < MAX_SUB; h++) {
+                RC_TRY(sh.ev_up[h].create());
+                RC_TRY(sh.ev_comp[h].create());
+            }
+            RC_TRY(sh.ev_all.create());
         }
-        hipError_t e = hipSetDevice(sh.device);
-        if (e != hipSuccess) return bail(fail("hipSetDevice", e));
-        if (sh.device != s->root) {
-            e = hipDeviceEnablePeerAccess(s->root, 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return bail(fail("hipDeviceEnablePeerAccess", e));
-            (void)hipGetLastError();
-        }
-        const int rc = fastecc_create(&sh.ctx, n, k, s->slab_bytes, field, sh.device);
-        if (rc != FASTECC_OK) return bail(rc);
-        for (hipStream_t* q : {&sh.s_up, &sh.s_comp, &sh.s_down}) {
-            e = hipStreamCreateWithFlags(q, hipStreamNonBlocking);
-            if (e != hipSuccess) return bail(fail("hipStreamCreateWithFlags", e));
-        }
-        for (int h = 0; h < MAX_SUB; h++) {
-            e = hipEventCreateWithFlags(&sh.ev_up[h], hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&sh.ev_comp[h], hipEventDisableTiming);
-            if (e != hipSuccess) return bail(fail("hipEventCreateWithFlags", e));
-        }
-        e = hipEventCreateWithFlags(&sh.ev_all, hipEventDisableTiming);
-        if (e != hipSuccess) return bail(fail("hipEventCreateWithFlags", e));
+        const hipError_t e = hipSetDevice(s->root);
+        if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+        return s->fork.create();
+    };
+    const int rc = build();
+    if (rc != FASTECC_OK) {
+        fastecc_destroy(shell);  // what a half-built context holds are owners: those never created give nothing back
+        return rc;
     }
-    hipError_t e = hipSetDevice(s->root);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->fork, hipEventDisableTiming);
-    if (e != hipSuccess) return bail(fail("hipEventCreateWithFlags(fork)", e));
     describe(shell);
     *out = shell;
     return FASTECC_OK;
@@ -811,7 +760,7 @@ int fastecc_encode_sharded(fastecc_ctx* c, const void* const* data_slabs, void* 
         if (parity_slabs && (!parity_slabs[g] || ((uintptr_t)parity_slabs[g] & mask))) return FASTECC_E_INVAL;
     }
     std::lock_guard<std::mutex> lk(mutex_of(c));
-    return run(c, data_slabs, nullptr, parity_slabs, parity, false, (hipStream_t)stream);
+    return settled(s, [&] { return run_body(c, data_slabs, nullptr, parity_slabs, parity, false, (hipStream_t)stream); });
 }
 
 int fastecc_encode_sharded_blocks(fastecc_ctx* c, const void* const* data, int data_layout, void* const* parity_blocks, void* stream)
@@ -825,10 +774,7 @@ int fastecc_encode_sharded_blocks(fastecc_ctx* c, const void* const* data, int d
     for (size_t g = 0; g < G; g++)
         if (!data[g] || ((uintptr_t)data[g] & mask) || !parity_blocks[g] || ((uintptr_t)parity_blocks[g] & mask)) return FASTECC_E_INVAL;
     std::lock_guard<std::mutex> lk(mutex_of(c));
-    DeviceSwitch restore;
-    const int rc = run_blocks_body(c, data, data_layout == FASTECC_SHARD_BLOCKS, parity_blocks, (hipStream_t)stream);
-    if (rc != FASTECC_OK) settle_after_failure(s);
-    return rc;
+    return settled(s, [&] { return run_blocks_body(c, data, data_layout == FASTECC_SHARD_BLOCKS, parity_blocks, (hipStream_t)stream); });
 }
 
 int fastecc_shard_info(const fastecc_ctx* c, int* n_slabs, uint64_t* slab_block_bytes, int* devices, int cap)

@@ -83,13 +83,13 @@ def test_product_does_not_reference_the_oracle():
 
 
 def test_device_resources_have_one_owner():
-    """Device and pinned memory, events and streams are taken and given back by the owning types of devmem.hpp alone (sharded.hip, whose
-    teardown walks devices in an order of its own, keeps its raw calls): no other file under csrc names those runtime calls."""
+    """Device and pinned memory, events and streams are taken and given back by the owning types of devmem.hpp alone: no other file under
+    csrc names those runtime calls."""
     calls = re.compile(r"\b(?:(?:hipMalloc|hipFree|hipHostMalloc|hipHostFree|hipEventDestroy|hipStreamDestroy)\(|hipEventCreate|hipStreamCreate)")
     csrc = os.path.join(ROOT, "fastecc_amd", "csrc")
     checked = 0
     for f in sorted(os.listdir(csrc)):
-        if f in ("devmem.hpp", "sharded.hip"):
+        if f == "devmem.hpp":
             continue
         text = open(os.path.join(csrc, f), errors="ignore").read()
         for i, line in enumerate(text.splitlines(), 1):

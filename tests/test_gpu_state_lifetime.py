@@ -428,3 +428,129 @@ def test_context_members_give_back_their_device_memory(torch_cuda, fe, oracle):
     control.close()
     torch.cuda.synchronize()
     assert free() - with_control >= largest, (with_control, free(), largest)
+
+
+# The same reading for the third test, on the commit before the sharded context's members became owners: three runs of its cycles, drop from
+# cycle 2 to cycle 8 of 0, 0 and 0 bytes; the largest is the slack.
+SHARD_SLACK = 0
+
+
+def test_sharded_contexts_give_back_their_device_memory(torch_cuda, fe, oracle):
+    """The same construction for what a sharded context owns on top of its slabs' contexts: three streams, 2 x 8 + 1 events and two slab
+    buffers per shard, the peer streams and events of the copy-engine all-to-all (2 G of each per shard), the fork event.  Eight identical
+    cycles on four slabs of one device, (2k,k) at k = 2^10 with 1 KiB blocks: a slab is 64 words, the smallest that still runs as two
+    sub-slabs.  Every data path in both gather modes, decode and repair, and a call failed by `inject_fault` with a good one after it.
+    Every result equals cycle 1's bit for bit, cycle 1's equal the oracle's; free memory after cycle 8 against cycle 2; a held context of two
+    slabs with 4 KiB blocks after one full-stripe encode, whose 2 x (2 + 2) MiB of slab buffers only the shards own, is the control."""
+    torch = torch_cuda
+    rng = np.random.default_rng(2026)
+    free = lambda: torch.cuda.mem_get_info()[0]
+    below_p = lambda *shape: rng.integers(0, P, size=shape, dtype=np.uint64).astype(np.uint32)
+    empty32 = lambda words: torch.empty(words, dtype=torch.int32, device="cuda:0")
+
+    # ---- everything the cycles touch, allocated up front; what the oracle says, computed once ----
+    K, S, G = 1 << 10, 256, 4
+    w, rows = S // G, K // G
+    x = below_p(K, S)
+    want = oracle.encode_fast(x)
+    slabs = [dev32(torch, x[:, g * w:(g + 1) * w]) for g in range(G)]
+    blocks = [dev32(torch, x[g * rows:(g + 1) * rows]) for g in range(G)]
+    out_slabs, out_blocks = [empty32(K * w) for _ in range(G)], [empty32(rows * S) for _ in range(G)]
+    dx, out_stripe = dev32(torch, x), empty32(K * S)
+    pinned_x = torch.from_numpy(x.view(np.int32).reshape(-1)).pin_memory()
+    pinned_out = torch.empty_like(pinned_x).pin_memory()
+    host_out = np.empty_like(x)
+    lost = ([5, 700], [9])
+    present = (flags(K, lost[0]), flags(K, lost[1]))
+    bad_d, bad_p = x.copy(), want.copy()
+    bad_d[lost[0]] = 11
+    bad_p[lost[1]] = 13
+    damaged = (dev32(torch, bad_d), dev32(torch, bad_p))
+    work = (torch.empty_like(damaged[0]), torch.empty_like(damaged[1]))
+
+    CS, CG = 1024, 2  # the control: two slabs, 4 KiB blocks
+    dctl, out_ctl = dev32(torch, below_p(K, CS)), empty32(K * CS)
+    torch.cuda.synchronize()
+
+    def cycle():
+        out = {}
+        with fe.ShardedEncoder(2 * K, K, 4 * S, [0] * G) as senc:
+            assert "sub_slabs=2" in senc.plan()
+            for mode in (1, 2):
+                senc.set_option("gather_mode", mode)
+                for t in out_slabs + out_blocks + [out_stripe, pinned_out]:
+                    t.zero_()
+                senc.encode_sharded(slabs, out_slabs, None)
+                torch.cuda.synchronize()
+                out["slabs to slabs, mode %d" % mode] = np.concatenate([host32(t).reshape(K, w) for t in out_slabs], axis=1)
+                senc.encode_sharded(slabs, None, out_stripe)
+                torch.cuda.synchronize()
+                out["slabs to a stripe, mode %d" % mode] = host32(out_stripe)
+                out_stripe.zero_()
+                senc.encode(dx, out_stripe)
+                torch.cuda.synchronize()
+                out["device stripe, mode %d" % mode] = host32(out_stripe)
+                senc.encode(pinned_x, pinned_out, mem=fe.MEM_HOST_PINNED)
+                torch.cuda.synchronize()
+                out["pinned stripe, mode %d" % mode] = pinned_out.numpy().view(np.uint32).copy()
+                host_out.fill(0)
+                senc.encode(x, host_out, mem=fe.MEM_HOST)
+                out["pageable stripe, mode %d" % mode] = host_out.copy()
+                for as_blocks in (False, True):  # mode 1 creates the peer streams and events
+                    senc.encode_sharded_blocks(blocks if as_blocks else slabs, out_blocks, data_is_blocks=as_blocks)
+                    torch.cuda.synchronize()
+                    out["%s to blocks, mode %d" % ("blocks" if as_blocks else "slabs", mode)] = np.concatenate([host32(t) for t in out_blocks])
+                    for t in out_blocks:
+                        t.zero_()
+            senc.set_option("gather_mode", 1)
+            senc.decode_prepare(*present)
+            for call in ("decode", "repair"):
+                work[0].copy_(damaged[0])
+                work[1].copy_(damaged[1])
+                getattr(senc, call)(*work)
+                torch.cuda.synchronize()
+                out[call + ", data"], out[call + ", parity"] = host32(work[0]), host32(work[1])
+            out_stripe.zero_()
+            senc.set_option("inject_fault", 3)
+            with pytest.raises(fe.FastEccError) as ei:
+                senc.encode(dx, out_stripe)
+            assert ei.value.code == fe.E_DEVICE
+            senc.encode(dx, out_stripe)
+            torch.cuda.synchronize()
+            out["after a failed call"] = host32(out_stripe)
+        torch.cuda.synchronize()
+        return out
+
+    # ---- the control: a context that is held must show in the reading ----
+    before = free()
+    control = fe.ShardedEncoder(2 * K, K, 4 * CS, [0] * CG)
+    control.encode(dctl, out_ctl)
+    torch.cuda.synchronize()
+    held = free()
+    largest = CG * (K + K) * (4 * CS // CG)  # every shard's data and parity slab buffers
+    assert largest == 2 * (2 + 2) << 20
+    assert before - held >= largest, (before, held, largest)
+
+    first, readings = None, []
+    for c in range(CYCLES):
+        out = cycle()
+        readings.append(free())
+        print("free memory after cycle %d: %d" % (c + 1, readings[-1]))
+        if first is None:
+            first = out
+            assert len(out) == 2 * 7 + 4 + 1, sorted(out)
+            other = {"decode, data": x, "decode, parity": bad_p, "repair, data": x}  # decode leaves the parity as it found it
+            for name, got in out.items():
+                expect = other.get(name, want)
+                assert np.array_equal(got.reshape(expect.shape), expect), "cycle 1: %s differs from the oracle" % name
+        else:
+            assert out.keys() == first.keys()
+            for name in first:
+                assert np.array_equal(out[name], first[name]), "cycle %d: %s differs from cycle 1" % (c + 1, name)
+    print("drop from cycle 2 to cycle 8:", readings[1] - readings[-1])
+    assert readings[1] - readings[-1] <= SHARD_SLACK, readings
+
+    with_control = free()
+    control.close()
+    torch.cuda.synchronize()
+    assert free() - with_control >= largest, (with_control, free(), largest)
