@@ -72,6 +72,7 @@ def lib():
     L.fastecc_destroy.argtypes, L.fastecc_destroy.restype = [vp], None
     L.fastecc_encode.argtypes, L.fastecc_encode.restype = [vp, vp, vp, i32, vp], i32
     L.fastecc_encode_batch.argtypes, L.fastecc_encode_batch.restype = [vp, vp, vp, u64, vp], i32
+    L.fastecc_encode_pool.argtypes, L.fastecc_encode_pool.restype = [vp, vp, vp, u64, vp], i32
     L.fastecc_encode_columns.argtypes, L.fastecc_encode_columns.restype = [vp, vp, vp, u64, u64, vp], i32
     L.fastecc_create_sharded.argtypes = [ctypes.POINTER(vp), u64, u64, u64, i32, ctypes.POINTER(i32), i32]
     L.fastecc_create_sharded.restype = i32
@@ -231,6 +232,14 @@ class Encoder:
         if parity is None:
             parity = data
         _check(lib().fastecc_encode_batch(self._h, _addr(data), _addr(parity), count, stream or None), "fastecc_encode_batch")
+        return parity
+
+    def encode_pool(self, data, parity, count, stream=0):
+        """Write a pool: `count` stripes back to back in device memory (the layout of decode_batch: stripe b's k data blocks at
+        data + b*k*block_bytes, its n - k parity blocks at parity + b*(n-k)*block_bytes); every stripe's parity is what encode gives for
+        it alone.  Any GF(0xFFF00001) code; data is read only and must not overlap parity.  Option "encode_pool_kernel" picks the kernel."""
+        count = self._batch_count(count)
+        _check(lib().fastecc_encode_pool(self._h, _addr(data), _addr(parity), count, stream or None), "fastecc_encode_pool")
         return parity
 
     def encode_host(self, data_np, parity_np=None):

@@ -257,6 +257,22 @@ int fastecc_encode_batch(fastecc_ctx* c, const void* data, void* parity, uint64_
                       nullptr, (uint32_t)count);
 }
 
+int fastecc_encode_pool(fastecc_ctx* c, const void* data, void* parity, uint64_t count, void* stream)
+{
+    if (!c || !data || !parity || count == 0 || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
+    if (c->sharded || c->p61 || c->field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
+    if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;  // stripes of a pool are contiguous
+    const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
+    const uint64_t d0 = (uint64_t)(uintptr_t)data, p0 = (uint64_t)(uintptr_t)parity;
+    if (count > UINT64_MAX / data_bytes || count > UINT64_MAX / parity_bytes) return FASTECC_E_INVAL;
+    if (d0 > UINT64_MAX - count * data_bytes || p0 > UINT64_MAX - count * parity_bytes) return FASTECC_E_INVAL;
+    if (d0 < p0 + count * parity_bytes && p0 < d0 + count * data_bytes) return FASTECC_E_INVAL;  // the parity is written while other stripes' data is still to be read
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallLock lk(c->mu);
+    return encode_pool_device(c, (const uint32_t*)data, (uint32_t*)parity, count, (hipStream_t)stream);
+}
+
 int fastecc_encode_blocks(fastecc_ctx* c, void* const* blocks)
 {
     if (!c || !blocks) return FASTECC_E_INVAL;

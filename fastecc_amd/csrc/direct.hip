@@ -31,6 +31,7 @@
 #include "gf.hpp"
 #include "internal.hpp"
 #include "lazy96.hpp"
+#include "mfma_digits.hpp"
 #include "ntt_device.hpp"
 
 namespace fastecc {
@@ -172,18 +173,6 @@ __global__ __launch_bounds__(256) void direct_reduce2_kernel(const uint32_t* __r
 // ------------------------------------------------------------------------------------------------
 // MFMA form
 // ------------------------------------------------------------------------------------------------
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-
-// Signed base-256 digits, packed: x = sum_a s_a 256^a (mod p) with s_a in [-128, 127], s_a = byte a of the result as int8.
-// y = x + 0x80808080 biases every digit by 128; where that would carry out of 32 bits (x >= 0x7F7F7F80) the value is taken as x - p
-// instead (2^32 = 2^20 - 1 mod p: y + 0xFFFFF, which cannot carry again).  Bytes of y are the biased digits; flipping bit 7 un-biases.
-__device__ __forceinline__ uint32_t balanced_digits(uint32_t x)
-{
-    const uint32_t bias = x >= 0x7F7F7F80u ? 0x8090807Fu : 0x80808080u;
-    return (x + bias) ^ 0x80808080u;
-}
-
 // Weight fragments for v_mfma_i32_32x32x32_i8, A operand: step ks covers rows [8 ks, 8 ks + 8), M-tile mt the outputs [8 mt, 8 mt + 8).
 // Lane l: m = l & 31 = 4 j' + b (output 8 mt + j', digit b of the weight), half = l >> 5; its 16 bytes, index 4 i + a: digit b of
 // 256^a * w[row 8 ks + 4 half + i][output] — k' = (row, a) pairs with digit a of the data word of that row (B operand, same index).
@@ -222,16 +211,6 @@ struct MfmaArgs {
     uint32_t S, rows, pad, mt_total, chunks, col_groups, sweeps;
     uint32_t chunk_rows;     // rows per chunk: a multiple of 8 * MFMA_G, at most MFMA_ROWS
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t direct_desc(const void* p, uint32_t bytes)
-{
-    // the pointer is wave-uniform; readfirstlane makes that provable (no waterfall loop around the buffer ops)
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
 // A workgroup = 4 waves owns (chunk of MFMA_ROWS rows, 256 columns), a wave 64 of them as two 32-column N-tiles (lane n = l & 31 holds
 // columns 2n, 2n+1: one dwordx2 per row; lanes 32-63 the rows 4 further down).  a sweep = 8*MT outputs.  At the top of a
@@ -352,20 +331,15 @@ __global__ __launch_bounds__(256 * MG, (MG == 2 ? 2 : MT <= 2 ? 3 : MT <= 4 ? 2 
         }
     }
     // D: column n = lane & 31, row m = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) = 4 j' + b: registers 4 q .. 4 q + 3 of a lane are the
-    // four digit sums of output j' = 2 q + half.  value = sum_b d_b 256^b, |d_b| < 2^28 here; + p * 2^24 makes it positive.
+    // four digit sums of output j' = 2 q + half, |d_b| < 2^28 here (digit_sums_to_word).
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             uint32_t r[2];
 #pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int64_t v = (int64_t)acc[mt][c][4 * q] + ((int64_t)acc[mt][c][4 * q + 1] << 8) + ((int64_t)acc[mt][c][4 * q + 2] << 16) +
-                                  ((int64_t)acc[mt][c][4 * q + 3] << 24);
-                const uint64_t t = (uint64_t)(v + ((int64_t)gf::P << 24));
-                const uint32_t tl = (uint32_t)t, th = (uint32_t)(t >> 32);  // th < 2^26
-                r[c] = gf::add(gf::mul(th, gf::MONT_ONE), tl >= gf::P ? tl - gf::P : tl);
-            }
+            for (int c = 0; c < 2; ++c)
+                r[c] = digit_sums_to_word(acc[mt][c][4 * q], acc[mt][c][4 * q + 1], acc[mt][c][4 * q + 2], acc[mt][c][4 * q + 3]);
             const uint32_t out = sweep * (8u * MTW) + 8u * (mg * MT + mt) + 2u * q + half;
             if (live) *reinterpret_cast<uint2*>(a.partial + ((size_t)chunk * a.pad + out) * a.S + col) = make_uint2(r[0], r[1]);
             __builtin_amdgcn_sched_barrier(0);  // one output at a time: 256 accumulators are not all read out before the first store
@@ -1104,9 +1078,44 @@ int direct_run_set(int eb, const DirectSetPass* passes, const DirectSetEntry* en
 struct DirectEncode {
     DirectPassPtr pass;
     uint32_t S = 0;
+    // the pool kernel's own weight fragments (pool_encode.hip): pass->frag is rewritten by direct_run with whatever padding the single-stripe
+    // kernel wants, possibly while a pool kernel on another stream still reads it.  Built once, by a kernel on the first pool call's stream;
+    // a use on another stream waits for that kernel on the device until the event is seen complete (as plan.hip's twiddle_table does).
+    DeviceBuf<uint4> pool_frag;
+    Event pool_frag_event;
+    hipStream_t pool_frag_stream = nullptr;
+    bool pool_frag_ready = false, pool_frag_pending = false;
 };
 
 void direct_encode_destroy(DirectEncode* de) { delete de; }
+
+DirectPass* direct_encode_pass(DirectEncode* de) { return de->pass.get(); }
+
+int direct_encode_pool_fragments(DirectEncode* de, int mt, hipStream_t st, const uint4** frag, uint32_t* mt_total)
+{
+    DirectPass* p = de->pass.get();
+    if (!p || !p->built || (mt != 1 && mt != 2 && mt != 4)) return FASTECC_E_INVAL;
+    *mt_total = ((uint32_t)p->outputs + 8u * mt - 1u) / (8u * mt) * (uint32_t)mt;  // whole sweeps of mt M-tiles
+    *frag = de->pool_frag;
+    if (de->pool_frag_ready) {
+        if (de->pool_frag_pending && st != de->pool_frag_stream) {
+            if (hipEventQuery(de->pool_frag_event) == hipSuccess) de->pool_frag_pending = false;
+            else HIP_TRY(hipStreamWaitEvent(st, de->pool_frag_event, 0));
+            (void)hipGetLastError();  // hipErrorNotReady of the query is not an error
+        }
+        return FASTECC_OK;
+    }
+    const uint64_t count = (uint64_t)((p->rows + 7u) / 8u) * *mt_total * 64u;  // rows past the last one and outputs past the pad: zero fragments
+    RC_TRY(de->pool_frag.alloc(count));
+    RC_TRY(de->pool_frag_event.create());
+    hipLaunchKernelGGL(mfma_weights_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, p->coef, de->pool_frag, p->rows, p->rows, (uint32_t)p->pad, *mt_total, count);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(de->pool_frag_event, st));
+    de->pool_frag_stream = st;
+    de->pool_frag_ready = de->pool_frag_pending = true;
+    *frag = de->pool_frag;
+    return FASTECC_OK;
+}
 
 int direct_encode_max() { return DIRECT_CAP; }
 

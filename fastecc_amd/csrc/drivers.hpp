@@ -73,6 +73,8 @@ int encode_pow2(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStrea
 int encode_mixed(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStream_t st);
 bool direct_encode_applies(const fastecc_ctx* c, const void* data = nullptr, const void* parity = nullptr);
 int encode_device(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStream_t st);
+// `count` stripes back to back (stripe b's k data blocks at data + b * k * S words, its n - k parity blocks at parity + b * (n - k) * S): fastecc_encode_pool
+int encode_pool_device(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, uint64_t count, hipStream_t st);
 int ntt_device(fastecc_ctx* c, uint32_t* data, bool inverse, hipStream_t st);
 int order_internal_buffers(fastecc_ctx* c, hipStream_t st);
 int mark_internal_buffers(fastecc_ctx* c, hipStream_t st);

@@ -328,6 +328,56 @@ int encode_device(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStr
     return encode_pow2(c, data, out, st, cb);
 }
 
+// n - k from which mode 0 of fastecc_encode_pool prefers the matrix-core kernel to the VALU one: the smallest measured n - k at which it won — 4, by
+// 1.10 x; 1.21 x at 8, 1.78 x at 16, 1.94 x at 32 (profiles/r07/encode_pool_bench.jsonl).  Fewer parity blocks were not measured.
+constexpr uint64_t POOL_MFMA_MIN_OUTPUTS = 4;
+
+// fastecc_encode_pool: `count` stripes stored back to back.  Where the direct path applies (the predicate a single stripe gets, for the pool's base
+// pointers) one launch computes every stripe's parity from the code's weight table — direct_batch_kernel (VALU) or pool_encode.hip's matrix-core
+// kernel, option "encode_pool_kernel" — when the pass has fewer than 4096 rows and the launch has at least 1024 waves (decode_batch_impl's rule,
+// measured there); the power-of-two (2k,k) codes of the transform path run their passes over the whole pool (fastecc_encode_batch's way); everything
+// else is encode_device stripe by stripe: correct, not faster than the caller's loop.
+int encode_pool_device(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, uint64_t count, hipStream_t st)
+{
+    const uint64_t S = c->S, data_words = c->K * S, parity_words = c->Mu * S;
+    const int mode = c->encode_pool_kernel;
+    auto stripe_by_stripe = [&] {
+        return with_internal_buffers(c, st, [&] {
+            int rc = FASTECC_OK;
+            for (uint64_t b = 0; b < count && rc == FASTECC_OK; b++) rc = encode_device(c, data + b * data_words, parity + b * parity_words, st);
+            return rc;
+        });
+    };
+    if (mode == 3) return stripe_by_stripe();
+    if (direct_encode_applies(c, data, parity)) {
+        int rc = FASTECC_OK;
+        if (!c->direct_enc) rc = direct_encode_build(&c->direct_enc, (uint64_t)c->q * c->N, c->K, c->Mu, c->fold, c->S);  // q > 1: the mixed-radix order
+        if (rc == FASTECC_E_NOMEM) {  // no room for the weight table: encode_device goes on to the transform pipeline
+            (void)hipGetLastError();
+            return stripe_by_stripe();
+        }
+        if (rc != FASTECC_OK) return rc;
+        DirectPass* p = direct_encode_pass(c->direct_enc);
+        if (mode == 0 && (c->K >= 4096 || direct_batch_waves(p, data, parity, S, count) < 1024)) return stripe_by_stripe();
+        const uint64_t bytes = count * (c->K + c->Mu) * S * 4ull;
+        if ((mode == 2 || (mode == 0 && c->Mu >= POOL_MFMA_MIN_OUTPUTS)) && pool_encode_mfma_applies(data, parity, c->K, S, count)) {
+            const uint4* frag = nullptr;
+            uint32_t mt_total = 0;
+            const int mt = pool_encode_mfma_tiles(c->Mu);
+            rc = direct_encode_pool_fragments(c->direct_enc, mt, st, &frag, &mt_total);
+            if (rc != FASTECC_OK) return rc;
+            ProfScope ps(c, st, "encode_pool_mfma", bytes);
+            return pool_encode_mfma_run(frag, mt_total, mt, data, parity, (uint32_t)c->K, (uint32_t)c->Mu, (uint32_t)S, count, st);
+        }
+        ProfScope ps(c, st, "encode_pool_valu", bytes);
+        return direct_run_batch(p, data, nullptr, nullptr, parity, S, count, data_words, parity_words, st);
+    }
+    // n = 2k = 2^m: every pass once over the whole pool (the parity stride is the data stride); 32-bit block indices
+    if (c->q == 1 && c->fold == 0 && c->cosets == 1 && c->K == c->N && c->Mu == c->M && count <= 0xFFFFFFFFull && count * c->N <= 0x7FFFFFFFull)
+        return run_passes(c, c->encode_plan, data, parity, twiddle_table(c, TW_ENC_DIF, st), twiddle_table(c, TW_ENC_DIT, st), st, 0, 0, nullptr, (uint32_t)count);
+    return stripe_by_stripe();
+}
+
 int encode_pow2(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStream_t st, const CallBounds& cb)
 {
     if (c->p61) {

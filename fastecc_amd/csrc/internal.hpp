@@ -164,6 +164,17 @@ int direct_encode_max();
 int direct_encode_build(DirectEncode** out, uint64_t N, uint64_t K, uint64_t m, int fold, uint64_t words);  // current device = the context's
 int direct_encode_run(DirectEncode* de, const uint32_t* data, uint32_t* parity, int kernel, hipStream_t st);
 void direct_encode_destroy(DirectEncode* de);
+DirectPass* direct_encode_pass(DirectEncode* de);  // its one pass: rows == data_rows == k, every output a parity row (for direct_run_batch)
+// The weight fragments of pool_encode.hip's kernel for sweeps of `mt` M-tiles (1, 2 or 4: 8 mt outputs): [ceil(k / 8)][*mt_total][64] uint4 in
+// mfma_weights_kernel's layout, zero for rows >= k and outputs >= n - k.  Built by a kernel on `st` at the first call and never rewritten; a later
+// call on another stream is ordered behind that kernel on the device.  No host synchronisation.
+int direct_encode_pool_fragments(DirectEncode* de, int mt, hipStream_t st, const uint4** frag, uint32_t* mt_total);
+
+// ---- pool_encode.hip: the parity of a pool of stripes on the matrix cores, one launch (fastecc_encode_pool, option "encode_pool_kernel" = 2) ----
+bool pool_encode_mfma_applies(const void* data, const void* parity, uint64_t k, uint64_t words, uint64_t count);
+int pool_encode_mfma_tiles(uint64_t outputs);  // M-tiles per wave and sweep: 1, 2 or 4
+int pool_encode_mfma_run(const uint4* frag, uint32_t mt_total, int mt, const uint32_t* data, uint32_t* parity, uint32_t k, uint32_t outputs, uint32_t words,
+                         uint64_t count, hipStream_t st);
 
 // ---- api.hip, encode.hip, host_stage.hip, create.hip ----
 struct CtxInfo {

@@ -122,6 +122,11 @@ int fastecc_set_option(fastecc_ctx* c, const char* name, int value)
         c->decode_batch_kernel = value;
         return FASTECC_OK;
     }
+    if (!strcmp(name, "encode_pool_kernel")) {  // fastecc_encode_pool, at call time: 0 = choose, 1 = VALU batch kernel, 2 = matrix-core pool kernel (1 where it cannot run), 3 = stripe by stripe
+        if (value < 0 || value > 3) return FASTECC_E_INVAL;
+        c->encode_pool_kernel = value;
+        return FASTECC_OK;
+    }
     if (!strcmp(name, "correct_batch_mode")) {  // fastecc_correct_batch, at call time: 0 = choose, 1 = batched location + grouped repair, 2 = fastecc_correct stripe by stripe
         if (value < 0 || value > 2) return FASTECC_E_INVAL;
         c->correct_batch_mode = value;

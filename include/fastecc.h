@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 380 /* 0.3.8: fastecc_scrub_erasures_set, fastecc_verify_batch_set / _correct_batch_set: absent blocks per stripe (scrub of a degraded rotated pool) */
+#define FASTECC_VERSION 390 /* 0.3.9: fastecc_encode_pool: the parity of a pool of stripes, any GF(0xFFF00001) code, option "encode_pool_kernel" */
 
 enum {
     FASTECC_OK = 0,
@@ -239,6 +239,30 @@ int fastecc_shard_info(const fastecc_ctx *ctx, int *n_slabs, uint64_t *slab_bloc
  * parity == data encodes in place; enqueued on `stream` without synchronising.
  */
 int fastecc_encode_batch(fastecc_ctx *ctx, const void *data, void *parity, uint64_t count, void *stream);
+
+/*
+ * Writing a pool: `count` stripes in the pool layout of fastecc_decode_batch, in DEVICE memory — stripe b's k data blocks at data +
+ * b*k*block_bytes, its n - k parity blocks at parity + b*(n-k)*block_bytes.  Every stripe's parity is, bit for bit, what
+ * fastecc_encode(FASTECC_MEM_DEVICE) gives for that stripe alone; `data` is read only and nothing outside the count*(n-k) parity blocks is
+ * written.  Every GF(0xFFF00001) code fastecc_encode takes on device memory: (2k,k), n = k + N/2^d, n = 4k / 8k, zero-extended (n,k),
+ * mixed radix and PFA.
+ *   - Codes of the direct path (n - k <= "encode_direct_max", the rule fastecc_encode applies to one stripe, here to the pool's base
+ *     pointers): ONE launch computes the parity of all stripes from the code's weight table when the code has k < 4096 and the launch
+ *     fills at least 1024 waves, else the stripes are encoded one by one.  Option "encode_pool_kernel" chooses the kernel (below).
+ *   - n = 2k = 2^m beyond the direct path: every transform pass once over the whole pool, as fastecc_encode_batch.
+ *   - Every other code (fold, cosets, zero extension, mixed radix beyond the direct path): fastecc_encode's work stripe by stripe —
+ *     correct, not faster than the caller's own loop.
+ * Enqueued on `stream` without synchronising, and nothing is staged on the host: steady-state calls are kernels only.  (The first call
+ * that takes the direct path builds the code's weight table and waits for it; the matrix-core kernel's fragment table is built on the
+ * first such call's stream, and calls on other streams are ordered behind that build on the device.)  The context's call lock is held
+ * as for fastecc_encode_batch.
+ * FASTECC_E_INVAL, before any device work: a null context, data or parity, count == 0, pointers not 4-byte aligned, byte sizes beyond
+ * 64 bits, a parity range that overlaps the data range (no in-place form: stripe b's parity would land on data still to be read).
+ * FASTECC_E_UNSUPPORTED: GF((2^61-1)^2), sharded contexts, a set "row_pitch_words".  A refused call writes nothing.
+ * fastecc_profile_* scopes: "encode_pool_valu" / "encode_pool_mfma" (one launch each; count*(k + n-k)*block_bytes algorithmic bytes);
+ * stripe by stripe: fastecc_encode's own ("direct_encode" or its passes).
+ */
+int fastecc_encode_pool(fastecc_ctx *ctx, const void *data, void *parity, uint64_t count, void *stream);
 
 /*
  * The reference's own calling form: an array of k HOST block pointers, transformed in place
@@ -740,6 +764,11 @@ const char *fastecc_plan_string(fastecc_ctx *ctx);
  *                  launch over all stripes whenever the pass allows it, 2 = stripe by stripe (direct_kernel then picks the kernel).  Same bits either way.
  *                  fastecc_decode_batch_set / _repair_batch_set read it too: 0 = one launch per class unless its passes read 4096 blocks or more,
  *                  1 = one launch per class always, 2 = stripe by stripe;
+ *   "encode_pool_kernel" = 0 / 1 / 2 / 3 (default 0 = choose; at call time): how fastecc_encode_pool runs a code of the direct path — 1 = the VALU
+ *                  batch kernel (96-bit lazy accumulation; any block size and alignment), 2 = the matrix-core pool kernel (i8 digits, a wave per stripe
+ *                  and 64 words; needs an even block of at least 64 words, 8-byte aligned pools, k < 4096 and a stripe below 4 GiB, and falls back
+ *                  to 1 where it cannot run), 3 = stripe by stripe (also for the (2k,k) codes of the transform path); 0 = one launch when k < 4096
+ *                  and it fills at least 1024 waves (the matrix-core kernel from n - k = 4 on where it can run: measured 1.1 x the VALU kernel at (20,16), 1.8 x at (48,32)), else stripe by stripe.  Same bits in every mode;
  *   "scrub_batch_chunk" = 0 .. INT_MAX (default 0 = the context's chunk capacity; at call time): the most stripes per chunk of
  *                  fastecc_verify_batch / _correct_batch / _locate_errors_batch.  Same answers either way;
  *   "correct_batch_mode" = 0 / 1 / 2 (default 0 = choose; at call time): how fastecc_correct_batch corrects the inconsistent stripes — 1 = batched
