@@ -23,6 +23,12 @@ int hip_fail(hipError_t e, const char* what)
     return e == hipErrorOutOfMemory ? FASTECC_E_NOMEM : FASTECC_E_DEVICE;
 }
 
+void set_error_text(const char* text) { snprintf(g_detail, sizeof g_detail, "%s", text ? text : ""); }
+
+int columns_supported(const fastecc_ctx* c)
+{
+    return !c->sharded && c->q == 1 && c->fold == 0 && c->cosets == 1 && c->K == c->N && c->Mu == c->M && c->slabs <= 1;
+}
 
 int ilog2_exact(uint64_t v)
 {
@@ -96,65 +102,6 @@ int fastecc_gf61_root(uint64_t order, uint64_t out[2])
     out[1] = r.im;
     return (r.re | r.im) ? FASTECC_OK : FASTECC_E_INVAL;
 }
-
-}  // extern "C"
-
-namespace fastecc {
-
-
-CtxInfo info_of(const fastecc_ctx* c)
-{
-    return CtxInfo{c->device, c->field, c->fold, c->cosets, c->n, c->N, c->S, c->ld, c->K != c->N || c->Mu != c->M, c->K, c->Mu, c->q, c->decode_direct_max, c->direct_kernel, c->p61_stride, c->decode_split, c->decode_batch_kernel};
-}
-DecodeState*& decoder_of(fastecc_ctx* c) { return c->decoder; }
-PatternSet*& pattern_set_of(fastecc_ctx* c) { return c->pattern_set; }
-Sharded*& sharded_of(fastecc_ctx* c) { return c->sharded; }
-p61::Decoder*& decoder61_of(fastecc_ctx* c) { return c->decoder61; }
-p61::Path* p61_path_of(fastecc_ctx* c) { return c->p61; }
-void* profile_scope_begin(fastecc_ctx* c, hipStream_t st, const char* name, uint64_t bytes)
-{
-    return c->profiling ? new (std::nothrow) ProfScope(c, st, name, bytes) : nullptr;
-}
-void profile_scope_end(void* scope) { delete (ProfScope*)scope; }
-const p61::LaunchHooks* p61_profile_hooks(fastecc_ctx* c, void** keep)
-{
-    *keep = nullptr;
-    if (!c->profiling) return nullptr;
-    P61Hooks* hk = new (std::nothrow) P61Hooks(c);
-    *keep = hk;
-    return hk ? &hk->h : nullptr;
-}
-void p61_profile_done(void* keep) { delete (P61Hooks*)keep; }
-std::mutex& mutex_of(fastecc_ctx* c) { return c->mu; }
-fastecc_ctx* new_shell_ctx(int root_device, int field, uint64_t k, uint64_t m, uint64_t block_bytes)
-{
-    fastecc_ctx* c = new (std::nothrow) fastecc_ctx();
-    if (!c) return nullptr;
-    c->device = root_device;
-    c->field = field;
-    c->N = c->K = k;
-    c->M = c->Mu = m;
-    c->S = c->ld = block_bytes / 4;
-    c->stripe_bytes = (size_t)k * block_bytes;
-    c->parity_bytes = (size_t)m * block_bytes;
-    return c;
-}
-void set_plan_text(fastecc_ctx* c, const std::string& t) { c->plan_text = t; }
-int columns_supported(const fastecc_ctx* c)
-{
-    return !c->sharded && c->q == 1 && c->fold == 0 && c->cosets == 1 && c->K == c->N && c->Mu == c->M && c->slabs <= 1;
-}
-int download_pageable(fastecc_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st) { return stage_download(c, dst, src, bytes, st); }
-int stage_rect(fastecc_ctx* c, bool to_device, void* host, size_t host_pitch, void* dev, size_t dev_pitch, size_t width, size_t rows, hipStream_t st, int threads)
-{
-    return stage_transfer(c, StageJob{to_device, (char*)host, host_pitch, (char*)dev, dev_pitch, width, rows}, st, threads);
-}
-void set_error_detail(const char* what, hipError_t e) { (void)hip_fail(e, what); }
-void set_error_text(const char* text) { snprintf(g_detail, sizeof g_detail, "%s", text ? text : ""); }
-
-}  // namespace fastecc
-
-extern "C" {
 
 void fastecc_destroy(fastecc_ctx* c)
 {
@@ -262,11 +209,10 @@ int fastecc_encode_pool(fastecc_ctx* c, const void* data, void* parity, uint64_t
     if (!c || !data || !parity || count == 0 || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
     if (c->sharded || c->p61 || c->field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
     if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;  // stripes of a pool are contiguous
-    const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
+    PoolExtent x;
+    RC_TRY(pool_extent(c, data, parity, count, &x));
     const uint64_t d0 = (uint64_t)(uintptr_t)data, p0 = (uint64_t)(uintptr_t)parity;
-    if (count > UINT64_MAX / data_bytes || count > UINT64_MAX / parity_bytes) return FASTECC_E_INVAL;
-    if (d0 > UINT64_MAX - count * data_bytes || p0 > UINT64_MAX - count * parity_bytes) return FASTECC_E_INVAL;
-    if (d0 < p0 + count * parity_bytes && p0 < d0 + count * data_bytes) return FASTECC_E_INVAL;  // the parity is written while other stripes' data is still to be read
+    if (d0 < p0 + count * x.parity_bytes && p0 < d0 + count * x.data_bytes) return FASTECC_E_INVAL;  // the parity is written while other stripes' data is still to be read
     DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
     CallLock lk(c->mu);

@@ -196,6 +196,12 @@ namespace fastecc {
 
 extern thread_local char g_detail[256];  // fastecc_last_error_detail
 
+// k or n - k is not the number of blocks the transform works on: the stripes hold fewer blocks than it computes
+inline bool zero_extended(const fastecc_ctx* c) { return c->K != c->N || c->Mu != c->M; }
+// the transform order: N, or q * N for the mixed-radix codes
+inline uint64_t transform_order(const fastecc_ctx* c) { return (uint64_t)c->q * c->N; }
+int columns_supported(const fastecc_ctx* c);  // fastecc_encode_columns works on this context (api.hip)
+
 int ilog2_exact(uint64_t v);
 uint32_t bitrev_host(uint32_t v, int bits);
 
@@ -213,5 +219,13 @@ int upload_twiddles(fastecc_ctx* c);  // the plans changed: every twiddle table 
 const uint32_t* twiddle_table(fastecc_ctx* c, int which, hipStream_t st);
 
 using CallLock = std::lock_guard<std::mutex>;
+
+// ---- sharded.hip: what the entry points do on a context that is a shell around per-device contexts (c->sharded != null) ----
+int sharded_encode_stripe(fastecc_ctx* shell, const void* data, void* parity, int mem_kind, hipStream_t st);
+enum { SH_PROFILE_ENABLE, SH_PROFILE_RESET, SH_SET_OPTION, SH_SET_PLAN };
+int sharded_forward(fastecc_ctx* shell, int what, const char* name, int value);  // to every slab's context (and the sharding's own options)
+int sharded_decode_prepare(fastecc_ctx* shell, const uint8_t* data_present, const uint8_t* parity_present);
+int sharded_decode_stripe(fastecc_ctx* shell, void* data, void* parity, int mem_kind, bool repair, hipStream_t st);
+fastecc_ctx* sharded_child(fastecc_ctx* shell, int g);  // slab g's context (nullptr: no such slab)
 
 }  // namespace fastecc

@@ -42,10 +42,7 @@
 #include <new>
 #include <vector>
 
-#include "devmem.hpp"
-#include "gf.hpp"
-#include "gf61_path.hpp"
-#include "internal.hpp"
+#include "drivers.hpp"
 #include "ntt_device.hpp"
 
 namespace fastecc {
@@ -680,43 +677,35 @@ void launch_rows(void (*k4)(K...), void (*k1)(K...), uint64_t rows, uint32_t S, 
 // the context's decoder state, made at its first use (nullptr: no memory)
 DecodeState* state_of(fastecc_ctx* c)
 {
-    DecodeState*& slot = decoder_of(c);
-    if (!slot) slot = new (std::nothrow) DecodeState();
-    return slot;
+    if (!c->decoder) c->decoder = new (std::nothrow) DecodeState();
+    return c->decoder;
 }
-
-// The decoder's work stripes and tables are internal buffers: a call orders its uses of them between streams (CallScope::begin, then this).
-struct EndScope {
-    CallScope& s;
-    hipStream_t st;
-    ~EndScope() { (void)s.end(st); }
-};
 
 // ---- fastecc_decode_prepare ----
 // The 64-bit field has its own decoder (gf61_decode.hip); its contexts are (2k,k), (4k,k) or (8k,k) with k a power of two (and their zero-extended
 // relatives), n = 4k / 8k the same decoder on the (k << e)-th roots of unity
-int prepare_p61(fastecc_ctx* c, const CtxInfo& ci, const uint8_t* data_present, const uint8_t* parity_present)
+int prepare_p61(fastecc_ctx* c, const uint8_t* data_present, const uint8_t* parity_present)
 {
-    DeviceGuard dg(ci.device);
+    DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
-    CallScope call(c);
-    const int rc0 = call.wait_idle();  // a decode still using the previous pattern
+    CallLock lk(c->mu);
+    const int rc0 = wait_idle(c);  // a decode still using the previous pattern
     if (rc0 != FASTECC_OK) return rc0;
     char detail[160] = "";
     // codes other than (2N,N): the decoder sees the (2N,N) codeword — data blocks beyond the caller's k are surviving zero blocks,
     // parity positions the code does not use are lost (which is what limits the losses to n - k)
     std::vector<uint8_t> dfull, pfull;
-    if (ci.zero_extended) {
-        dfull.assign(ci.k, 1);
-        pfull.assign(ci.k, 0);
-        for (uint64_t i = 0; i < ci.user_k; i++) dfull[i] = data_present[i] ? 1 : 0;
-        for (uint64_t q = 0; q < ci.user_m; q++) pfull[q * (uint64_t)ci.p61_stride] = parity_present[q] ? 1 : 0;
+    if (zero_extended(c)) {
+        dfull.assign(c->N, 1);
+        pfull.assign(c->N, 0);
+        for (uint64_t i = 0; i < c->K; i++) dfull[i] = data_present[i] ? 1 : 0;
+        for (uint64_t q = 0; q < c->Mu; q++) pfull[q * (uint64_t)c->p61_stride] = parity_present[q] ? 1 : 0;
         data_present = dfull.data();
         parity_present = pfull.data();
     }
-    const int rc = p61::decode_prepare(&decoder61_of(c), ci.log2k, ci.words / 4, data_present, parity_present, ci.direct_max, detail, sizeof detail,
-                                       ci.decode_split, code_coset_shift(ci.cosets));
-    if (rc != FASTECC_OK && detail[0]) set_error_detail(detail, hipErrorUnknown);
+    const int rc = p61::decode_prepare(&c->decoder61, c->n, c->S / 4, data_present, parity_present, c->decode_direct_max, detail, sizeof detail,
+                                       c->decode_split, code_coset_shift(c->cosets));
+    if (rc != FASTECC_OK && detail[0]) (void)hip_fail(hipErrorUnknown, detail);  // (the message of a failed p61::create*; the code stays p61's)
     return rc;
 }
 
@@ -783,7 +772,6 @@ struct PatternScan {
 // unity; the decoder's transform is a mixed-radix context one size up, the locator's values come from the way down of another one (mixed_dif).
 struct Prepare {
     fastecc_ctx* c;
-    CtxInfo ci;
     const uint8_t* data_present;
     const uint8_t* parity_present;
     bool mixed;     // mixed radix
@@ -807,12 +795,12 @@ struct Prepare {
     PhaseTimer pt;
 
     Prepare(fastecc_ctx* ctx, const uint8_t* dp, const uint8_t* pp)
-        : c(ctx), ci(info_of(ctx)), data_present(dp), parity_present(pp), mixed(ci.q > 1), N(mixed ? (uint64_t)ci.q * ci.k : ci.k),
-          e(code_coset_shift(ci.cosets)), NC(N << e), lgc(ci.log2k + e), standard(!mixed && ci.cosets == 1 && ci.fold == 0 && !ci.zero_extended),
+        : c(ctx), data_present(dp), parity_present(pp), mixed(c->q > 1), N(transform_order(c)), e(code_coset_shift(c->cosets)), NC(N << e), lgc(c->n + e),
+          standard(!mixed && c->cosets == 1 && c->fold == 0 && !zero_extended(c)),
           narrow(!mixed && (1ull << lgc) == NC)
     {
     }
-    uint64_t parity_position(uint64_t q) const { return code_parity_position(N, e, ci.fold, ci.cosets, q); }
+    uint64_t parity_position(uint64_t q) const { return code_parity_position(N, e, c->fold, c->cosets, q); }
     void new_pattern(uint64_t erased_data, uint64_t erased_total)  // (the previous pattern is dropped)
     {
         d->ready = false;
@@ -829,15 +817,15 @@ struct Prepare {
     // kernel was asked for — at 80 where the split transform (4.3 ms instead of 7.2 at k = 2^19 x 4 KB) is the alternative.
     int direct_limit() const
     {
-        int limit = std::min(ci.direct_max, direct_cap());
-        const bool split_applies = ci.decode_split && ci.q <= 1 && ci.cosets == 1 && ci.log2k >= 17;
-        if (ci.direct_kernel == 0 && !direct_mfma_applies(nullptr, nullptr, ci.words)) limit = std::min(limit, split_applies ? 80 : 96);
+        int limit = std::min(c->decode_direct_max, direct_cap());
+        const bool split_applies = c->decode_split && c->q <= 1 && c->cosets == 1 && c->n >= 17;
+        if (c->direct_kernel == 0 && !direct_mfma_applies(nullptr, nullptr, c->S)) limit = std::min(limit, split_applies ? 80 : 96);
         // orders above 2^20 (mixed radix): the locator tree is padded to 2^20 roots whatever the pattern
         uint64_t T20 = 1;
         while (T20 < NC - N) T20 <<= 1;
         // their tree costs a 2^20-point product: the direct path first, up to the caller's "decode_direct_max" (the 80 / 96 cap of rows the
         // matrix-core kernel cannot take is a speed trade-off against a transform path that is much dearer here, so it does not apply)
-        if (T20 > (1ull << 20) && ci.direct_max > 0) limit = std::max(limit, std::min(ci.direct_max, direct_cap()));
+        if (T20 > (1ull << 20) && c->decode_direct_max > 0) limit = std::max(limit, std::min(c->decode_direct_max, direct_cap()));
         return limit;
     }
 
@@ -858,7 +846,7 @@ struct Prepare {
         t.host_nomem = false;
         t.ed = ed;
         t.ep = ep;
-        const uint32_t K = (uint32_t)ci.user_k;
+        const uint32_t K = (uint32_t)c->K;
         const uint32_t w = gf::h_root((uint32_t)NC), wd = gf::h_pow(w, 1ull << e);  // data row i sits at wd^i
         std::vector<uint32_t> xr(ed), ya(ed);  // the points of the lost data blocks and of their parity nodes
         for (int r = 0; r < ed; r++) xr[r] = gf::h_pow(w, (uint64_t)R[r] << e);
@@ -903,26 +891,26 @@ struct Prepare {
     {
         *done = false;
         const int limit = direct_limit();
-        if (limit <= 0 || ci.user_k >= 0xFFFFFFF0ull) return FASTECC_OK;
+        if (limit <= 0 || c->K >= 0xFFFFFFF0ull) return FASTECC_OK;
         PhaseTimer ptd;
         std::vector<uint32_t> R, Pl, A;  // lost data blocks, lost parity blocks, the surviving parity blocks that serve as nodes
         bool over = false;
-        each_lost(data_present, ci.user_k, [&](uint64_t i) { R.push_back((uint32_t)i); return !(over = (int)R.size() > limit); });
-        if (!over) each_lost(parity_present, ci.user_m, [&](uint64_t q) { Pl.push_back((uint32_t)q); return !(over = (int)(R.size() + Pl.size()) > limit); });
-        for (uint64_t q = 0; q < ci.user_m && !over && A.size() < R.size(); q++)
+        each_lost(data_present, c->K, [&](uint64_t i) { R.push_back((uint32_t)i); return !(over = (int)R.size() > limit); });
+        if (!over) each_lost(parity_present, c->Mu, [&](uint64_t q) { Pl.push_back((uint32_t)q); return !(over = (int)(R.size() + Pl.size()) > limit); });
+        for (uint64_t q = 0; q < c->Mu && !over && A.size() < R.size(); q++)
             if (parity_present[q]) A.push_back((uint32_t)q);
         if (over || R.size() + Pl.size() < 1 || A.size() != R.size()) return FASTECC_OK;
         const int ed = (int)R.size(), ep = (int)Pl.size();
         ptd.mark("few losses: pattern scan");
-        DeviceGuard dg(ci.device);
+        DeviceGuard dg(c->device);
         if (!dg.ok) return FASTECC_E_DEVICE;
-        CallScope call(c);
+        CallLock lk(c->mu);
         if (!(d = state_of(c))) return FASTECC_E_NOMEM;
         new_pattern(ed, ed + ep);
         d->sub = false;
         d->erased_parity = ep;
-        d->direct_kernel = ci.direct_kernel;
-        int rc = call.wait_idle();  // a decode still using the previous pattern
+        d->direct_kernel = c->direct_kernel;
+        int rc = wait_idle(c);  // a decode still using the previous pattern
         if (rc != FASTECC_OK) return rc;
         ptd.mark("few losses: lock, idle");
         const PatternTables& t = d->direct;
@@ -947,16 +935,16 @@ struct Prepare {
     int transform_path()
     {
         pt = PhaseTimer();
-        DeviceGuard dg(ci.device);
+        DeviceGuard dg(c->device);
         if (!dg.ok) return FASTECC_E_DEVICE;
-        CallScope call(c);  // (held from here on: the device scan already writes the context's pattern state)
+        CallLock lk(c->mu);  // (held from here on: the device scan already writes the context's pattern state)
         if (!(d = state_of(c))) return FASTECC_E_NOMEM;
         int rc;
-        if (standard && N <= 0x7FFFFFFFull && (rc = scan_device(call)) != FASTECC_OK) return rc;
+        if (standard && N <= 0x7FFFFFFFull && (rc = scan_device()) != FASTECC_OK) return rc;
         if (!s.device_scan) scan_host();
         if (s.erased_count > NC - N) return FASTECC_E_INVAL;  // fewer than k blocks survive: not decodable
         pt.mark(s.device_scan ? "pattern scan (device)" : "pattern scan (host)");
-        if ((rc = set_pattern(call)) != FASTECC_OK) return rc;
+        if ((rc = set_pattern()) != FASTECC_OK) return rc;
         if (s.erased_data == 0) {  // no data block to recover
             // standard_state_kernel's writes of the lost-parity flags are still pending on the null stream: a repair on a non-blocking
             // stream is not ordered after them (the full path below ends with the same synchronise)
@@ -968,9 +956,9 @@ struct Prepare {
         while ((1ull << lgT) < T) lgT++;
         if (s.erased_count > T) return FASTECC_E_UNSUPPORTED;
         leaf_log = lgT >= TREE_LOW + 2 ? TREE_LOW : std::min(LEAF_LOG, lgT);
-        parity_factors = d->erased_parity != 0 && (d->standard || (s.split_groups != 0 && ci.fold == 0));
+        parity_factors = d->erased_parity != 0 && (d->standard || (s.split_groups != 0 && c->fold == 0));
         if ((rc = build_shape()) != FASTECC_OK) return rc;
-        if ((rc = call.wait_idle()) != FASTECC_OK) return rc;  // a decode still using the previous pattern
+        if ((rc = wait_idle(c)) != FASTECC_OK) return rc;  // a decode still using the previous pattern
         pt.mark("tables, tile order");
         uint32_t* coeffs = nullptr;
         if ((rc = locator_tree(&coeffs)) != FASTECC_OK || (rc = locator_tables(coeffs)) != FASTECC_OK) return rc;
@@ -984,13 +972,13 @@ struct Prepare {
     // four passes over a million byte-sized coin flips).  Two 512 KB uploads, one counting kernel, 32 bytes back; the per-position state and the
     // lost-parity flags are then written by a kernel.  Patterns the "small form" of the split transform does not take (too few surviving parity
     // blocks at multiples of 2^h) leave s as it is: the host scan.
-    int scan_device(CallScope& call)
+    int scan_device()
     {
         RC_TRY(d->dev_present.alloc(2 * N));
         RC_TRY(d->dev_counts.alloc(8));
         RC_TRY(d->dev_state.alloc(NC));
-        RC_TRY(d->parity_lost.alloc(ci.user_m));
-        RC_TRY(call.wait_idle());  // a decode or repair still reading the previous pattern's state
+        RC_TRY(d->parity_lost.alloc(c->Mu));
+        RC_TRY(wait_idle(c));  // a decode or repair still reading the previous pattern's state
         d->ready = false;
         HIP_TRY(hipMemcpyAsync(d->dev_present, data_present, N, hipMemcpyHostToDevice, nullptr));
         HIP_TRY(hipMemcpyAsync(d->dev_present + N, parity_present, N, hipMemcpyHostToDevice, nullptr));
@@ -1001,8 +989,8 @@ struct Prepare {
         HIP_TRY(hipMemcpy(counts, d->dev_counts, sizeof counts, hipMemcpyDeviceToHost));
         const uint64_t erased_data = counts[0], erased_parity = counts[1];
         uint32_t shift = 0;
-        const bool want_split = ci.decode_split && ci.log2k >= 17 && erased_data != 0;
-        if (want_split && ci.decode_split != 2)
+        const bool want_split = c->decode_split && c->n >= 17 && erased_data != 0;
+        if (want_split && c->decode_split != 2)
             for (int h = 5; h >= 1 && shift == 0; h--)
                 if (counts[1 + h] >= erased_data) shift = (uint32_t)h;
         if (want_split && shift == 0) return FASTECC_OK;  // the host path counts again
@@ -1035,15 +1023,15 @@ struct Prepare {
         } else {
             std::vector<uint32_t>& srcmap = s.srcmap;
             srcmap.assign(NC, 0);
-            for (uint64_t i = 0; i < ci.user_k; i++) {
+            for (uint64_t i = 0; i < c->K; i++) {
                 const uint64_t u = i << e;
                 const uint32_t held = data_present[i] != 0;
                 state[u] = held ? ST_HELD : ST_LOST;
                 srcmap[u] = (uint32_t)i & (0u - held);
                 s.erased_data += 1u - held;
             }
-            for (uint64_t i = ci.user_k; i < N; i++) state[i << e] = ST_ZERO;
-            for (uint64_t q = 0; q < ci.user_m; q++) {
+            for (uint64_t i = c->K; i < N; i++) state[i << e] = ST_ZERO;
+            for (uint64_t q = 0; q < c->Mu; q++) {
                 const uint64_t u = parity_position(q);
                 const uint32_t held = parity_present[q] != 0;
                 state[u] = held ? ST_HELD : ST_LOST;
@@ -1051,7 +1039,7 @@ struct Prepare {
                 s.erased_parity += 1u - held;
             }
         }
-        if (ci.decode_split && !mixed && ci.cosets == 1 && ci.log2k >= 17 && s.erased_data != 0) choose_split();
+        if (c->decode_split && !mixed && c->cosets == 1 && c->n >= 17 && s.erased_data != 0) choose_split();
         if (s.split_groups != 0 && !s.srcmap.empty())
             for (uint64_t u = 1; u < NC; u += 2) s.srcmap[u] &= 0u - (uint32_t)(state[u] != ST_UNUSED);
         // the erased positions themselves are listed on the device (erased_list_kernel): the host needs their number only
@@ -1069,13 +1057,13 @@ struct Prepare {
         // first choice: the surviving parity blocks at multiples of 2^h of the parity half, the largest h <= 5 that still leaves as many as there
         // are lost data blocks (2 % of the codeword lost: h = 5) — r~ is then the transform of k >> h rows (see DecodeState::split_shift)
         uint64_t at_multiple[6] = {};
-        for (uint64_t q = 0; q < ci.user_m; q++) {
+        for (uint64_t q = 0; q < c->Mu; q++) {
             if (!parity_present[q]) continue;
-            const uint64_t hpos = q << ci.fold;
+            const uint64_t hpos = q << c->fold;
             for (int h = 1; h <= 5 && (hpos & ((1ull << h) - 1ull)) == 0; h++) at_multiple[h]++;
         }
         for (int h = 5; h >= 1 && s.split_shift == 0; h--)
-            if (at_multiple[h] >= s.erased_data && ci.decode_split != 2) s.split_shift = (uint32_t)h;
+            if (at_multiple[h] >= s.erased_data && c->decode_split != 2) s.split_shift = (uint32_t)h;
         if (s.split_shift != 0) {
             const uint64_t mask = (1ull << s.split_shift) - 1ull;
             for (uint64_t q = 0; q < N; q++)
@@ -1085,7 +1073,7 @@ struct Prepare {
         }
         constexpr uint32_t GROUPS = 1024;
         uint32_t held_in[GROUPS] = {};
-        for (uint64_t q = 0; q < ci.user_m; q++) held_in[(q << ci.fold) & (GROUPS - 1u)] += parity_present[q] != 0;
+        for (uint64_t q = 0; q < c->Mu; q++) held_in[(q << c->fold) & (GROUPS - 1u)] += parity_present[q] != 0;
         uint64_t have = 0;
         while (s.split_groups < GROUPS && have < s.erased_data) have += held_in[s.split_groups++];
         if (have < s.erased_data) {
@@ -1097,17 +1085,17 @@ struct Prepare {
     }
 
     // the pattern's counts into the decoder's state (the previous pattern is dropped) and the lost-parity flags of a host scan to the device
-    int set_pattern(CallScope& call)
+    int set_pattern()
     {
         new_pattern(s.erased_data, s.erased_count);
         pt.mark("lock, state");
         d->erased_parity = s.erased_parity;
         if (!s.device_scan) {
-            std::vector<uint32_t> plost(ci.user_m);
-            for (uint64_t q = 0; q < ci.user_m; q++) plost[q] = parity_present[q] ? 0u : 1u;
-            RC_TRY(d->parity_lost.alloc(ci.user_m));
-            RC_TRY(call.wait_idle());  // a repair still reading the previous pattern
-            HIP_TRY(hipMemcpy(d->parity_lost, plost.data(), ci.user_m * 4, hipMemcpyHostToDevice));
+            std::vector<uint32_t> plost(c->Mu);
+            for (uint64_t q = 0; q < c->Mu; q++) plost[q] = parity_present[q] ? 0u : 1u;
+            RC_TRY(d->parity_lost.alloc(c->Mu));
+            RC_TRY(wait_idle(c));  // a repair still reading the previous pattern
+            HIP_TRY(hipMemcpy(d->parity_lost, plost.data(), c->Mu * 4, hipMemcpyHostToDevice));
         }
         pt.mark("lost-parity flags");
         d->sub = false;
@@ -1130,7 +1118,7 @@ struct Prepare {
         if (s.split_groups != 0 && d->split && (rc = split_buffers()) != FASTECC_OK) return rc;
         if (d->standard && d->erased_parity != 0 && !(s.split_groups != 0 && d->split) && !d->transform_full) {
             // repair in one transform (see DecodeState::transform_full): the form for patterns or plans the split transform does not take
-            rc = create_ramp_transform_ctx(d->transform_full.fill(), lgc, ci.words * 4, 0, gf::h_inv((uint32_t)NC), ci.device);
+            rc = create_ramp_transform_ctx(d->transform_full.fill(), lgc, c->S * 4, 0, gf::h_inv((uint32_t)NC), c->device);
             if (rc != FASTECC_OK && rc != FASTECC_E_NOMEM) return rc;
             d->full_ok = d->transform_full && same_tile_order(d->transform, d->transform_full);
             if (getenv("FASTECC_TRACE_PREPARE"))
@@ -1159,11 +1147,11 @@ struct Prepare {
             int rc;
             if (mixed) {
                 const std::vector<uint32_t> ones(NC, 1u);
-                rc = create_mixed_transform_ctx(d->pattern_ntt.fill(), ci.q, lgc, 8, ones.data(), ci.device);
+                rc = create_mixed_transform_ctx(d->pattern_ntt.fill(), c->q, lgc, 8, ones.data(), c->device);
             } else {
                 // only its stand-alone transform is used; long ones as the upper row bits of a four-step transform (chunk_transform_kernel)
                 d->pattern_narrow = narrow && lgc + 1 - CHUNK_LOG >= 1;
-                rc = d->pattern_narrow ? create_ntt_ctx(d->pattern_ntt.fill(), lgc + 1 - CHUNK_LOG, 4 * CHUNK, ci.device) : create_ntt_ctx(d->pattern_ntt.fill(), lgc, 8, ci.device);
+                rc = d->pattern_narrow ? create_ntt_ctx(d->pattern_ntt.fill(), lgc + 1 - CHUNK_LOG, 4 * CHUNK, c->device) : create_ntt_ctx(d->pattern_ntt.fill(), lgc, 8, c->device);
             }
             if (rc != FASTECC_OK) return rc;
         }
@@ -1178,9 +1166,9 @@ struct Prepare {
                 std::vector<uint32_t> factor(NC);
                 const uint32_t inv_nc_m = gf::h_to_mont(inv_nc);
                 for (uint64_t m = 0; m < NC; m++) factor[m] = gf::h_mont_mul((uint32_t)m, inv_nc_m);
-                rc = create_mixed_transform_ctx(d->transform.fill(), ci.q, lgc, ci.words * 4, factor.data(), ci.device);
+                rc = create_mixed_transform_ctx(d->transform.fill(), c->q, lgc, c->S * 4, factor.data(), c->device);
             } else {
-                rc = create_ramp_transform_ctx(d->transform.fill(), lgc, ci.words * 4, e, inv_nc, ci.device);
+                rc = create_ramp_transform_ctx(d->transform.fill(), lgc, c->S * 4, e, inv_nc, c->device);
             }
             if (rc != FASTECC_OK) return rc;
         }
@@ -1197,11 +1185,11 @@ struct Prepare {
         const bool narrow_tree = narrow && lgT + 1 - CHUNK_LOG >= 1 && lgT > leaf_log;
         for (int lv = leaf_log; lv < lgT; lv++) {
             if (narrow_tree && (T >> lv) <= NARROW_COLUMNS) continue;  // tree_top + chunk_transform_kernel
-            const int rc = create_ntt_ctx(d->tree_ctx[lv].fill(), lv + 1, 4 * (T >> lv), ci.device);
+            const int rc = create_ntt_ctx(d->tree_ctx[lv].fill(), lv + 1, 4 * (T >> lv), c->device);
             if (rc != FASTECC_OK) return rc;
         }
         if (narrow_tree) {
-            const int rc = create_ntt_ctx(d->tree_top.fill(), lgT + 1 - CHUNK_LOG, 4 * CHUNK, ci.device);
+            const int rc = create_ntt_ctx(d->tree_top.fill(), lgT + 1 - CHUNK_LOG, 4 * CHUNK, c->device);
             if (rc != FASTECC_OK) return rc;
         }
         for (DeviceBuf<uint32_t>* b : {&d->tree_x, &d->tree_f, &d->tree_y, &d->tree_p, &d->roots, &d->dev_erased}) b->reset();
@@ -1231,7 +1219,7 @@ struct Prepare {
         RC_TRY(d->gout.alloc(N));
         if (parity_factors) RC_TRY(d->gout_par.alloc(N));
         // mixed radix: the work stripe of all NC positions, transformed in place; else the N recovered data positions
-        return d->recovered.alloc((mixed ? NC : N) * ci.words);
+        return d->recovered.alloc((mixed ? NC : N) * c->S);
     }
 
     // The split transform's context and tables (once).  Anything missing — a plan without the tile shapes, no memory for the two extra stripes —
@@ -1240,7 +1228,7 @@ struct Prepare {
     {
         const int rc = [&]() -> int {
             // per-block factor (2m + k) / 2k = m / k + 1 / 2
-            const int rc = create_ramp_transform_ctx(d->split.fill(), ci.log2k, ci.words * 4, 0, gf::h_inv((uint32_t)N), ci.device, gf::h_inv(2u));
+            const int rc = create_ramp_transform_ctx(d->split.fill(), c->n, c->S * 4, 0, gf::h_inv((uint32_t)N), c->device, gf::h_inv(2u));
             if (rc != FASTECC_OK) return rc;
             if (!split_decode_supported(d->split) || split_decode_groups(d->split) != 1024u) return FASTECC_E_UNSUPPORTED;
             for (DeviceBuf<uint32_t>* b : {&d->split_order, &d->split_rows_data, &d->split_rows_parity, &d->split_rows_out, &d->split_pos_parity,
@@ -1251,8 +1239,8 @@ struct Prepare {
             RC_TRY(d->split_impulse.alloc(table.size()));
             HIP_TRY(hipMemcpy(d->split_impulse, table.data(), table.size() * 4, hipMemcpyHostToDevice));
             const uint32_t neg_half = (uint32_t)(gf::P - gf::h_inv(2u));
-            hipLaunchKernelGGL(split_pos_kernel, grid_of(N), dim3(256), 0, nullptr, d->wpow, d->split_pos_parity, (uint32_t)N, ci.log2k, neg_half, false);
-            hipLaunchKernelGGL(split_pos_kernel, grid_of(N), dim3(256), 0, nullptr, d->wpow, d->split_pos_data_odd, (uint32_t)N, ci.log2k, neg_half, true);
+            hipLaunchKernelGGL(split_pos_kernel, grid_of(N), dim3(256), 0, nullptr, d->wpow, d->split_pos_parity, (uint32_t)N, c->n, neg_half, false);
+            hipLaunchKernelGGL(split_pos_kernel, grid_of(N), dim3(256), 0, nullptr, d->wpow, d->split_pos_data_odd, (uint32_t)N, c->n, neg_half, true);
             HIP_TRY(hipGetLastError());
             return FASTECC_OK;
         }();
@@ -1280,15 +1268,15 @@ struct Prepare {
         if (s.split_shift != 0) {
             const uint64_t rows = N >> s.split_shift;
             if (!d->split_small[s.split_shift]) {
-                const int rc = create_ntt_ctx(d->split_small[s.split_shift].fill(), ci.log2k - (int)s.split_shift, ci.words * 4, ci.device);
+                const int rc = create_ntt_ctx(d->split_small[s.split_shift].fill(), c->n - (int)s.split_shift, c->S * 4, c->device);
                 if (rc != FASTECC_OK && rc != FASTECC_E_NOMEM && rc != FASTECC_E_UNSUPPORTED) return rc;
                 if (rc != FASTECC_OK) err = hipErrorOutOfMemory;
             }
-            if (err == hipSuccess) err = d->split_small_buf.try_grow(rows * ci.words);
+            if (err == hipSuccess) err = d->split_small_buf.try_grow(rows * c->S);
         } else if (!d->split_r1 || !d->split_r2) {
-            err = d->split_r1.try_alloc(N * ci.words);
-            if (err == hipSuccess) err = d->split_r2.try_alloc(N * ci.words);
-            if (err == hipSuccess) err = hipMemsetAsync(d->split_r1, 0, N * ci.words * 4, nullptr);
+            err = d->split_r1.try_alloc(N * c->S);
+            if (err == hipSuccess) err = d->split_r2.try_alloc(N * c->S);
+            if (err == hipSuccess) err = hipMemsetAsync(d->split_r1, 0, N * c->S * 4, nullptr);
             d->split_dirty = 0;
             if (err != hipSuccess) {
                 d->split_r1.reset();
@@ -1377,7 +1365,7 @@ struct Prepare {
                                            : transform_bitrev(d->pattern_ntt, d->pattern_buf, d->pattern_buf, false, false, 2, st);
         if (rc != FASTECC_OK) return rc;
         hipLaunchKernelGGL(finish_tables_kernel, grid_of(NC), dim3(256), 0, st, d->pattern_buf, (const uint32_t*)d->dev_state.get(), d->wpow, d->fin, d->gout, (uint32_t)NC,
-                           (uint32_t)(T - s.erased_count), e, (uint32_t)ci.user_k, (uint32_t)(mixed ? ci.q : 1), lgc, parity_factors ? d->gout_par.get() : nullptr,
+                           (uint32_t)(T - s.erased_count), e, (uint32_t)c->K, (uint32_t)(mixed ? c->q : 1), lgc, parity_factors ? d->gout_par.get() : nullptr,
                            !mixed);
         HIP_TRY(hipGetLastError());
         if (d->fin_first_pass != d->fin) {
@@ -1394,8 +1382,8 @@ struct Prepare {
         d->split_shift = s.split_shift;
         if (s.split_shift == 0 && d->split_dirty > s.split_groups) {
             // rows of groups this pattern does not write any more: group g = blocks g + (t << 10)
-            const size_t row = ci.words * 4;
-            HIP_TRY(hipMemset2DAsync(d->split_r1 + (size_t)s.split_groups * ci.words, 1024 * row, 0, (d->split_dirty - s.split_groups) * row,
+            const size_t row = c->S * 4;
+            HIP_TRY(hipMemset2DAsync(d->split_r1 + (size_t)s.split_groups * c->S, 1024 * row, 0, (d->split_dirty - s.split_groups) * row,
                                      split_decode_group_rows(d->split), st));
             d->split_dirty = s.split_groups;
         }
@@ -1408,11 +1396,10 @@ struct Prepare {
 int decode_prepare_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t* parity_present)
 {
     if (!c || !data_present || !parity_present) return FASTECC_E_INVAL;
-    if (sharded_of(c)) return sharded_decode_prepare(c, data_present, parity_present);
-    const CtxInfo ci = info_of(c);
-    if (ci.field == FASTECC_FIELD_GF_P61_SQUARED) return prepare_p61(c, ci, data_present, parity_present);
-    if (ci.field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
-    if (ci.pitch != ci.words) return FASTECC_E_UNSUPPORTED;
+    if (c->sharded) return sharded_decode_prepare(c, data_present, parity_present);
+    if (c->field == FASTECC_FIELD_GF_P61_SQUARED) return prepare_p61(c, data_present, parity_present);
+    if (c->field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
+    if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;
     Prepare p(c, data_present, parity_present);
     bool done = false;
     const int rc = p.direct(&done);
@@ -1420,53 +1407,46 @@ int decode_prepare_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8
 }
 
 // ---- fastecc_decode / fastecc_repair ----
-// The 64-bit field's decode (gf61_decode.hip), the context's call lock held.  Codes other than (2N,N): the padded (2N,N) codeword is decoded in
-// the context's two work stripes and the caller's blocks are copied back.
-int decode_p61(fastecc_ctx* c, CallScope& call, void* data, const void* parity, int mem_kind, hipStream_t st, void* parity_out)
+// The 64-bit field's decode (gf61_decode.hip).  Codes other than (2N,N): the padded (2N,N) codeword is decoded in the context's two work stripes
+// and the caller's blocks are copied back.  The caller holds c->mu.
+int decode_p61(fastecc_ctx* c, void* data, const void* parity, int mem_kind, hipStream_t st, void* parity_out)
 {
     if ((((uintptr_t)data | (uintptr_t)parity) & 15u)) return FASTECC_E_INVAL;
-    p61::Decoder* d61 = decoder61_of(c);
+    p61::Decoder* d61 = c->decoder61;
     if (!p61::decoder_ready(d61)) return FASTECC_E_INVAL;
-    const CtxInfo ci = info_of(c);
-    DeviceGuard dg(ci.device);
+    DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
-    int rc = call.begin(st);  // the decoder's work stripe and tables are internal buffers
-    if (rc != FASTECC_OK) return rc;
-    void* prof = nullptr;
-    const p61::LaunchHooks* hooks = p61_profile_hooks(c, &prof);
-    p61::Path* encoder = parity_out ? p61_path_of(c) : nullptr;
-    if (!ci.zero_extended) {
-        rc = mem_kind == FASTECC_MEM_DEVICE ? p61::decode(d61, (uint64_t*)data, (uint64_t*)const_cast<void*>(parity), encoder, st, hooks)
-                                            : p61::decode_host(d61, data, const_cast<void*>(parity), encoder, st, hooks);
-    } else if (mem_kind != FASTECC_MEM_DEVICE) {
-        (void)call.end(st);
-        return FASTECC_E_UNSUPPORTED;
-    } else {
-        const size_t row = ci.words * 4, prow = row * (size_t)ci.p61_stride;
+    return with_internal_buffers(c, st, [&]() -> int {  // the decoder's work stripe and tables are internal buffers
+        P61Hooks hk(c);
+        const p61::LaunchHooks* hooks = c->profiling ? &hk.h : nullptr;
+        p61::Path* encoder = parity_out ? c->p61.get() : nullptr;
+        if (!zero_extended(c))
+            return mem_kind == FASTECC_MEM_DEVICE ? p61::decode(d61, (uint64_t*)data, (uint64_t*)const_cast<void*>(parity), encoder, st, hooks)
+                                                  : p61::decode_host(d61, data, const_cast<void*>(parity), encoder, st, hooks);
+        if (mem_kind != FASTECC_MEM_DEVICE) return FASTECC_E_UNSUPPORTED;
+        const size_t row = c->S * 4, prow = row * (size_t)c->p61_stride;
         uint64_t *wd = nullptr, *wp = nullptr;
-        rc = p61_work_stripes(c, &wd, &wp);
+        int rc = p61_work_stripes(c, &wd, &wp);
         auto step = [&](hipError_t e, const char* what) {
             if (rc == FASTECC_OK && e != hipSuccess) rc = hip_fail(e, what);
         };
         if (rc == FASTECC_OK) {
-            step(hipMemcpyAsync(wd, data, ci.user_k * row, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync(data)");
-            step(hipMemsetAsync((char*)wd + ci.user_k * row, 0, (ci.k - ci.user_k) * row, st), "hipMemsetAsync");
-            step(hipMemcpy2DAsync(wp, prow, parity, row, row, ci.user_m, hipMemcpyDeviceToDevice, st), "hipMemcpy2DAsync(parity)");
+            step(hipMemcpyAsync(wd, data, c->K * row, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync(data)");
+            step(hipMemsetAsync((char*)wd + c->K * row, 0, (c->N - c->K) * row, st), "hipMemsetAsync");
+            step(hipMemcpy2DAsync(wp, prow, parity, row, row, c->Mu, hipMemcpyDeviceToDevice, st), "hipMemcpy2DAsync(parity)");
         }
         if (rc == FASTECC_OK) rc = p61::decode(d61, wd, wp, encoder, st, hooks);
         if (rc == FASTECC_OK) {
-            step(hipMemcpyAsync(data, wd, ci.user_k * row, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync(data back)");
-            if (parity_out) step(hipMemcpy2DAsync(parity_out, row, wp, prow, row, ci.user_m, hipMemcpyDeviceToDevice, st), "hipMemcpy2DAsync(parity back)");
+            step(hipMemcpyAsync(data, wd, c->K * row, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync(data back)");
+            if (parity_out) step(hipMemcpy2DAsync(parity_out, row, wp, prow, row, c->Mu, hipMemcpyDeviceToDevice, st), "hipMemcpy2DAsync(parity back)");
         }
-    }
-    p61_profile_done(prof);
-    const int rc_end = call.end(st);
-    return rc != FASTECC_OK ? rc : rc_end;
+        return rc;
+    });
 }
 
-// The direct path's passes over a stripe or a batch: pass(p, parity_in, data_out, parity_out) runs one of them.  Data and parity lost with a table
+// The direct path's passes over a stripe or a batch: run(p, parity_in, data_out, parity_out) runs one of them.  Data and parity lost with a table
 // for both: one pass over the survivors writes both (fastecc_decode: the data only); else the lost data, then (rebuild) the lost parity from it.
-template <class Pass> int direct_passes(const DecodeState* d, bool rebuild, uint32_t* data, const uint32_t* parity, uint32_t* parity_out, Pass&& pass)
+template <class Run> int direct_passes(const DecodeState* d, bool rebuild, uint32_t* data, const uint32_t* parity, uint32_t* parity_out, Run&& pass)
 {
     if (d->sub_both && (rebuild || d->sub_only_both)) return pass(d->direct.both, parity, data, rebuild ? parity_out : nullptr);
     if (d->sub_lost_data > 0) {
@@ -1480,7 +1460,6 @@ template <class Pass> int direct_passes(const DecodeState* d, bool rebuild, uint
 struct StripeDecode {
     fastecc_ctx* c;
     DecodeState* d;
-    CtxInfo ci;
     hipStream_t st;
     bool rebuild;            // fastecc_repair of a pattern that lost parity blocks
     uint32_t* data;          // the data stripe on the device (FASTECC_MEM_HOST: the staging copy)
@@ -1494,21 +1473,21 @@ struct StripeDecode {
     // that is known to be a few blocks or block groups.  *rows_only: only the rebuilt blocks will travel back (few enough of them, their rows known).
     int stage_host(const void* host_data, const void* host_parity, bool* rows_only)
     {
-        const size_t data_bytes = ci.user_k * block, parity_bytes = ci.user_m * block;
-        RC_TRY(d->parity_dev.alloc((ci.user_m + ci.user_k) * S));
+        const size_t data_bytes = c->K * block, parity_bytes = c->Mu * block;
+        RC_TRY(d->parity_dev.alloc((c->Mu + c->K) * S));
         if (d->host_lists_of != d->pattern_serial) {
             // the rows that travel back: known from the set-up (few losses), else read off the decoder's tables once per pattern
             d->host_lost_data.clear();
             d->host_lost_parity.clear();
-            if (d->erased_data + d->erased_parity <= (ci.user_k + ci.user_m) / 8 && d->parity_lost && (d->erased_data == 0 || d->gout)) {
-                std::vector<uint32_t> flags(std::max(ci.user_k, ci.user_m));
+            if (d->erased_data + d->erased_parity <= (c->K + c->Mu) / 8 && d->parity_lost && (d->erased_data == 0 || d->gout)) {
+                std::vector<uint32_t> flags(std::max(c->K, c->Mu));
                 if (d->erased_data != 0) {
-                    HIP_TRY(hipMemcpy(flags.data(), d->gout, ci.user_k * 4, hipMemcpyDeviceToHost));
-                    for (uint64_t i = 0; i < ci.user_k; i++)
+                    HIP_TRY(hipMemcpy(flags.data(), d->gout, c->K * 4, hipMemcpyDeviceToHost));
+                    for (uint64_t i = 0; i < c->K; i++)
                         if (flags[i] != 0) d->host_lost_data.push_back((uint32_t)i);
                 }
-                HIP_TRY(hipMemcpy(flags.data(), d->parity_lost, ci.user_m * 4, hipMemcpyDeviceToHost));
-                for (uint64_t q = 0; q < ci.user_m; q++)
+                HIP_TRY(hipMemcpy(flags.data(), d->parity_lost, c->Mu * 4, hipMemcpyDeviceToHost));
+                for (uint64_t q = 0; q < c->Mu; q++)
                     if (flags[q] != 0) d->host_lost_parity.push_back((uint32_t)q);
                 if (d->host_lost_data.size() != d->erased_data) d->host_lost_data.clear(), d->host_lost_parity.clear();  // (tables of another shape: whole stripes back)
             }
@@ -1516,16 +1495,16 @@ struct StripeDecode {
         }
         const uint64_t back = (d->erased_data != 0 ? d->host_lost_data.size() : 0) + (rebuild ? d->host_lost_parity.size() : 0);
         *rows_only = back != 0 && (d->erased_data == 0 || d->host_lost_data.size() == d->erased_data) &&
-                     (!rebuild || d->host_lost_parity.size() == d->erased_parity) && back <= (ci.user_k + ci.user_m) / 8;
+                     (!rebuild || d->host_lost_parity.size() == d->erased_parity) && back <= (c->K + c->Mu) / 8;
         const bool partial = !rebuild || *rows_only;  // (a repair that copies the whole parity stripe back must have staged all of it)
         const bool split = !d->sub && d->split_ready && d->standard && d->erased_data != 0 && partial;
         if (split && d->split_shift != 0) {
             // split transform, small form: the parity blocks at multiples of 2^shift are all it reads — one strided copy of every 2^shift-th block
             const size_t pitch = block << d->split_shift;
-            HIP_TRY(hipMemcpy2DAsync(d->parity_dev, pitch, host_parity, pitch, block, (ci.user_m + (1ull << d->split_shift) - 1) >> d->split_shift, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpy2DAsync(d->parity_dev, pitch, host_parity, pitch, block, (c->Mu + (1ull << d->split_shift) - 1) >> d->split_shift, hipMemcpyHostToDevice, st));
         } else if (split && d->split_groups < 512) {
             // group form: groups g < split_groups = blocks g + 1024 t, one strided copy
-            HIP_TRY(hipMemcpy2DAsync(d->parity_dev, 1024 * block, host_parity, 1024 * block, (size_t)d->split_groups * block, ci.user_m / 1024, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpy2DAsync(d->parity_dev, 1024 * block, host_parity, 1024 * block, (size_t)d->split_groups * block, c->Mu / 1024, hipMemcpyHostToDevice, st));
         } else if (d->sub && partial) {
             // few losses: the direct path reads as many parity blocks as data blocks are lost (at most 256 copies of a block)
             for (uint32_t q : d->host_parity_used)
@@ -1533,9 +1512,9 @@ struct StripeDecode {
         } else {
             HIP_TRY(hipMemcpyAsync(d->parity_dev, host_parity, parity_bytes, hipMemcpyHostToDevice, st));
         }
-        HIP_TRY(hipMemcpyAsync(d->parity_dev + ci.user_m * S, host_data, data_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d->parity_dev + c->Mu * S, host_data, data_bytes, hipMemcpyHostToDevice, st));
         parity = parity_out = d->parity_dev;
-        data = d->parity_dev + ci.user_m * S;
+        data = d->parity_dev + c->Mu * S;
         return FASTECC_OK;
     }
 
@@ -1543,10 +1522,8 @@ struct StripeDecode {
     int direct()
     {
         return direct_passes(d, rebuild, data, parity, parity_out, [&](DirectPass* p, const uint32_t* par_in, uint32_t* data_to, uint32_t* par_to) {
-            void* scope = profile_scope_begin(c, st, "direct_pass", (ci.user_k + (uint64_t)d->sub_lost_data) * block);
-            const int rc = direct_run(p, data, par_in, data_to, par_to, S, d->direct_kernel, st);
-            profile_scope_end(scope);
-            return rc;
+            ProfScope ps(c, st, "direct_pass", (c->K + (uint64_t)d->sub_lost_data) * block);
+            return direct_run(p, data, par_in, data_to, par_to, S, d->direct_kernel, st);
         });
     }
 
@@ -1573,12 +1550,12 @@ struct StripeDecode {
     int split_small(const SplitRepair* odd)
     {
         launch_rows(split_small_gather_kernel<4>, split_small_gather_kernel<1>, N >> d->split_shift, S, {parity, d->split_small_buf}, st, parity, d->split_small_buf,
-                    d->fin, S, (int)d->split_shift, ci.fold, (uint32_t)ci.user_m);
+                    d->fin, S, (int)d->split_shift, c->fold, (uint32_t)c->Mu);
         HIP_TRY(hipGetLastError());
         const int rc = transform_bitrev(d->split_small[d->split_shift], d->split_small_buf, d->split_small_buf, false, true, S, st);
         if (rc != FASTECC_OK) return rc;
         return run_split_decode(d->split, data, nullptr, d->split_rows_data, nullptr, 0, d->split_pos_parity, d->recovered, nullptr, nullptr, d->split_rows_out,
-                                data, nullptr, (uint32_t)ci.user_k, (uint32_t)ci.user_m, st, odd, d->split_small_buf, d->split_shift);
+                                data, nullptr, (uint32_t)c->K, (uint32_t)c->Mu, st, odd, d->split_small_buf, d->split_shift);
     }
 
     // fastecc_repair through the split transform: the data chain as in fastecc_decode, and a second MID + DIT over the same two halves for x p'(x)
@@ -1592,12 +1569,11 @@ struct StripeDecode {
         }
         const SplitRepair odd{d->split_q2, d->split_pos_data_odd, d->split_rows_out_parity, parity_out};
         d->split_dirty = std::max(d->split_dirty, d->split_groups);  // (before the launches: a failure half way must not hide written groups)
-        void* scope = profile_scope_begin(c, st, "repair_split_transform", (5 * N + (uint64_t)d->split_groups * split_decode_group_rows(d->split)) * block);
+        ProfScope ps(c, st, "repair_split_transform", (5 * N + (uint64_t)d->split_groups * split_decode_group_rows(d->split)) * block);
         const int rc = d->split_shift != 0 ? split_small(&odd)
                                            : run_split_decode(d->split, data, parity, d->split_rows_data, d->split_rows_parity, d->split_groups, d->split_pos_parity,
                                                               d->recovered, d->split_r1, d->split_r2, d->split_rows_out, data, d->split_impulse,
-                                                              (uint32_t)ci.user_k, (uint32_t)ci.user_m, st, &odd);
-        profile_scope_end(scope);
+                                                              (uint32_t)c->K, (uint32_t)c->Mu, st, &odd);
         if (rc == FASTECC_E_UNSUPPORTED) return FASTECC_OK;
         *done = rc == FASTECC_OK;
         return rc;
@@ -1626,29 +1602,25 @@ struct StripeDecode {
     int decode_split()
     {
         if (d->split_shift != 0) {
-            void* scope = profile_scope_begin(c, st, "decode_split_transform", (3 * N + 3 * (N >> d->split_shift)) * block);
-            const int rc = split_small(nullptr);
-            profile_scope_end(scope);
-            return rc;
+            ProfScope ps(c, st, "decode_split_transform", (3 * N + 3 * (N >> d->split_shift)) * block);
+            return split_small(nullptr);
         }
-        if (ci.fold > 0 && d->split_r0.try_alloc(N * S) != hipSuccess) {
+        if (c->fold > 0 && d->split_r0.try_alloc(N * S) != hipSuccess) {
             (void)hipGetLastError();
             return FASTECC_E_UNSUPPORTED;
         }
-        void* scope = profile_scope_begin(c, st, "decode_split_transform", (3 * N + (uint64_t)d->split_groups * split_decode_group_rows(d->split)) * block);
+        ProfScope ps(c, st, "decode_split_transform", (3 * N + (uint64_t)d->split_groups * split_decode_group_rows(d->split)) * block);
         const uint32_t* parity_half = parity;
-        uint32_t parity_half_blocks = (uint32_t)ci.user_m;
-        if (ci.fold > 0) {
+        uint32_t parity_half_blocks = (uint32_t)c->Mu;
+        if (c->fold > 0) {
             // fewer parity blocks than data blocks: block j belongs at j << fold of the parity half — the blocks in use are copied there
-            launch_rows(split_stage_kernel<4>, split_stage_kernel<1>, ci.user_m, S, {parity, d->split_r0}, st, parity, d->split_r0, d->fin, S, ci.fold);
+            launch_rows(split_stage_kernel<4>, split_stage_kernel<1>, c->Mu, S, {parity, d->split_r0}, st, parity, d->split_r0, d->fin, S, c->fold);
             parity_half = d->split_r0;
             parity_half_blocks = (uint32_t)N;
         }
         d->split_dirty = std::max(d->split_dirty, d->split_groups);  // (before the launches, as in repair_split)
-        const int rc = run_split_decode(d->split, data, parity_half, d->split_rows_data, d->split_rows_parity, d->split_groups, d->split_pos_parity, d->recovered,
-                                        d->split_r1, d->split_r2, d->split_rows_out, data, d->split_impulse, (uint32_t)ci.user_k, parity_half_blocks, st);
-        profile_scope_end(scope);
-        return rc;
+        return run_split_decode(d->split, data, parity_half, d->split_rows_data, d->split_rows_parity, d->split_groups, d->split_pos_parity, d->recovered,
+                                d->split_r1, d->split_r2, d->split_rows_out, data, d->split_impulse, (uint32_t)c->K, parity_half_blocks, st);
     }
 
     // The lost data blocks: the split transform, else the 2k-point one.  The (2k,k) layout lets the transform's first pass read the two halves of
@@ -1659,9 +1631,8 @@ struct StripeDecode {
         int rc = d->split_ready ? decode_split() : FASTECC_E_UNSUPPORTED;
         if (rc == FASTECC_OK) return FASTECC_OK;
         if (rc == FASTECC_E_UNSUPPORTED && d->standard) {
-            void* scope = profile_scope_begin(c, st, "decode_transform_2k", 3 * N * block);
+            ProfScope ps(c, st, "decode_transform_2k", 3 * N * block);
             rc = run_gathered(d->transform, data, parity, d->fin_first_pass, d->recovered, st);
-            profile_scope_end(scope);
         }
         const bool fused = rc == FASTECC_OK;
         if (!fused && rc != FASTECC_E_UNSUPPORTED) return rc;
@@ -1685,10 +1656,10 @@ struct StripeDecode {
     // only the lost blocks are copied — the surviving ones are left as they are
     int reencode_parity()
     {
-        RC_TRY(d->parity_again.alloc(ci.user_m * S));
-        const int rc = encode_unlocked(c, data, d->parity_again, st);
+        RC_TRY(d->parity_again.alloc(c->Mu * S));
+        const int rc = encode_device(c, data, d->parity_again, st);
         if (rc != FASTECC_OK) return rc;
-        launch_rows(restore_parity_kernel<4>, restore_parity_kernel<1>, ci.user_m, S, {parity_out, d->parity_again}, st, d->parity_again, parity_out, d->parity_lost, S);
+        launch_rows(restore_parity_kernel<4>, restore_parity_kernel<1>, c->Mu, S, {parity_out, d->parity_again}, st, d->parity_again, parity_out, d->parity_lost, S);
         HIP_TRY(hipGetLastError());
         return FASTECC_OK;
     }
@@ -1718,11 +1689,11 @@ struct StripeDecode {
         }
         if (rows_only) (void)hipGetLastError();  // out of memory for the shortcut only
         if (d->erased_data != 0) {
-            const int rc = download_pageable(c, host_data, data, ci.user_k * block, st);
+            const int rc = stage_download(c, host_data, data, c->K * block, st);
             if (rc != FASTECC_OK) return rc;
         }
         if (rebuild) {
-            const int rc = download_pageable(c, host_parity, d->parity_dev, ci.user_m * block, st);
+            const int rc = stage_download(c, host_parity, d->parity_dev, c->Mu * block, st);
             if (rc != FASTECC_OK) return rc;
         }
         HIP_TRY(hipStreamSynchronize(st));
@@ -1730,40 +1701,37 @@ struct StripeDecode {
     }
 };
 
-// one stripe, the context's call lock held (fastecc_decode_batch runs the transform path through this, stripe by stripe).  parity_out != null
-// (== parity): also rebuild the lost parity blocks
-int decode_locked(fastecc_ctx* c, CallScope& call, void* data, const void* parity, int mem_kind, void* stream, void* parity_out)
+// one stripe (fastecc_decode_batch runs the transform path through this, stripe by stripe).  parity_out != null (== parity): also rebuild the lost
+// parity blocks.  The caller holds c->mu.
+int decode_locked(fastecc_ctx* c, void* data, const void* parity, int mem_kind, void* stream, void* parity_out)
 {
-    if (info_of(c).field == FASTECC_FIELD_GF_P61_SQUARED) return decode_p61(c, call, data, parity, mem_kind, (hipStream_t)stream, parity_out);
-    DecodeState* d = decoder_of(c);
+    if (c->field == FASTECC_FIELD_GF_P61_SQUARED) return decode_p61(c, data, parity, mem_kind, (hipStream_t)stream, parity_out);
+    DecodeState* d = c->decoder;
     if (!d || !d->ready) return FASTECC_E_INVAL;  // fastecc_decode_prepare first
     const bool rebuild = parity_out != nullptr && d->erased_parity != 0;
     if (d->erased_data == 0 && !rebuild) return FASTECC_OK;
-    const CtxInfo ci = info_of(c);
-    if (ci.pitch != ci.words) return FASTECC_E_UNSUPPORTED;  // the gather / scatter passes address contiguous stripes
-    DeviceGuard dg(ci.device);
+    if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;  // the gather / scatter passes address contiguous stripes
+    DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
     hipStream_t st = (hipStream_t)stream;
-    int rc = call.begin(st);
-    if (rc != FASTECC_OK) return rc;
-    EndScope end{call, st};
-    StripeDecode j{c, d, ci, st, rebuild, (uint32_t*)data, (const uint32_t*)parity, (uint32_t*)parity_out, d->mixed ? (uint64_t)ci.q * ci.k : ci.k, ci.words * 4,
-                   (uint32_t)ci.words};
-    const bool host = mem_kind == FASTECC_MEM_HOST;
-    bool rows_only = false;
-    if (host && (rc = j.stage_host(data, parity, &rows_only)) != FASTECC_OK) return rc;
-    if ((rc = d->sub ? j.direct() : j.transform()) != FASTECC_OK) return rc;
-    return host ? j.copy_back(data, parity_out, rows_only) : FASTECC_OK;
+    return with_internal_buffers(c, st, [&]() -> int {  // the decoder's work stripes and tables are internal buffers
+        StripeDecode j{c, d, st, rebuild, (uint32_t*)data, (const uint32_t*)parity, (uint32_t*)parity_out, transform_order(c), c->S * 4, (uint32_t)c->S};
+        const bool host = mem_kind == FASTECC_MEM_HOST;
+        bool rows_only = false;
+        if (host) RC_TRY(j.stage_host(data, parity, &rows_only));
+        RC_TRY(d->sub ? j.direct() : j.transform());
+        return host ? j.copy_back(data, parity_out, rows_only) : FASTECC_OK;
+    });
 }
 
 int decode_impl(fastecc_ctx* c, void* data, const void* parity, int mem_kind, void* stream, void* parity_out)
 {
     if (!c || !data || !parity || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
-    if (sharded_of(c)) return sharded_decode_stripe(c, data, const_cast<void*>(parity), mem_kind, parity_out != nullptr, (hipStream_t)stream);
+    if (c->sharded) return sharded_decode_stripe(c, data, const_cast<void*>(parity), mem_kind, parity_out != nullptr, (hipStream_t)stream);
     if (mem_kind == FASTECC_MEM_HOST_PINNED) mem_kind = FASTECC_MEM_HOST;  // the same staging; the copies are simply faster from pinned memory
     if (mem_kind != FASTECC_MEM_HOST && mem_kind != FASTECC_MEM_DEVICE) return FASTECC_E_INVAL;
-    CallScope call(c);
-    return decode_locked(c, call, data, parity, mem_kind, stream, parity_out);
+    CallLock lk(c->mu);
+    return decode_locked(c, data, parity, mem_kind, stream, parity_out);
 }
 
 // `count` stripes back to back in device memory, all with the prepared pattern.  The direct path runs each of its passes over the whole batch in
@@ -1776,59 +1744,51 @@ int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, 
                       const uint64_t* dev_list = nullptr)
 {
     if (!c || !data || !parity || count == 0 || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
-    if (sharded_of(c)) return FASTECC_E_UNSUPPORTED;
-    CallScope call(c);
-    const CtxInfo ci = info_of(c);
-    if (ci.field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
-    if (ci.pitch != ci.words) return FASTECC_E_UNSUPPORTED;  // stripes of a batch are contiguous
-    const uint64_t block = ci.words * 4, data_bytes = ci.user_k * block, parity_bytes = ci.user_m * block;
-    if (count > UINT64_MAX / data_bytes || count > UINT64_MAX / parity_bytes) return FASTECC_E_INVAL;
-    if (!host_list && ((uint64_t)(uintptr_t)data > UINT64_MAX - count * data_bytes || (uint64_t)(uintptr_t)parity > UINT64_MAX - count * parity_bytes)) return FASTECC_E_INVAL;
+    if (c->sharded) return FASTECC_E_UNSUPPORTED;
+    CallLock lk(c->mu);
+    if (c->field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
+    if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;  // stripes of a batch are contiguous
+    PoolExtent x;
+    RC_TRY(pool_extent(c, data, parity, count, &x, !host_list));
+    const uint64_t block = x.block;
     if ((host_list != nullptr) != (dev_list != nullptr)) return FASTECC_E_INVAL;
     auto stripe_of = [&](uint64_t b) { return host_list ? host_list[b] : b; };
-    DecodeState* d = decoder_of(c);
+    DecodeState* d = c->decoder;
     if (!d || !d->ready) return FASTECC_E_INVAL;  // fastecc_decode_prepare first
     const bool rebuild = repair && d->erased_parity != 0;
     if (d->erased_data == 0 && !rebuild) return FASTECC_OK;
-    DeviceGuard dg(ci.device);
+    DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
     hipStream_t st = (hipStream_t)stream;
     if (!d->sub) {
         // more losses than the direct path takes: correct, not faster than the caller's own loop
         for (uint64_t b = 0; b < count; b++) {
-            char* pb = (char*)parity + stripe_of(b) * parity_bytes;
-            const int rc = decode_locked(c, call, (char*)data + stripe_of(b) * data_bytes, pb, FASTECC_MEM_DEVICE, stream, repair ? pb : nullptr);
-            if (rc != FASTECC_OK) return rc;
+            char* pb = (char*)parity + stripe_of(b) * x.parity_bytes;
+            RC_TRY(decode_locked(c, (char*)data + stripe_of(b) * x.data_bytes, pb, FASTECC_MEM_DEVICE, stream, repair ? pb : nullptr));
         }
         return FASTECC_OK;
     }
-    const int rc = call.begin(st);
-    if (rc != FASTECC_OK) return rc;
-    EndScope end{call, st};
-    const uint64_t S = ci.words, data_words = ci.user_k * S, parity_words = ci.user_m * S;
+    const uint64_t S = c->S, data_words = c->K * S, parity_words = c->Mu * S;
     uint32_t* ddata = (uint32_t*)data;
     uint32_t* dparity = (uint32_t*)parity;
-    return direct_passes(d, rebuild, ddata, dparity, dparity, [&](DirectPass* p, const uint32_t* par_in, uint32_t* data_to, uint32_t* par_to) -> int {
+    auto run = [&](DirectPass* p, const uint32_t* par_in, uint32_t* data_to, uint32_t* par_to) -> int {
         const uint64_t rows = (uint64_t)direct_pass_rows(p);
-        const int mode = ci.decode_batch_kernel;
+        const int mode = c->decode_batch_kernel;
         const bool batched = mode == 1 || (mode == 0 && d->direct_kernel != 2 && rows < 4096 && direct_batch_waves(p, ddata, dparity, S, count) >= 1024);
         if (batched) {
             const uint64_t outputs = (data_to ? (uint64_t)d->sub_lost_data : 0) + (par_to ? (uint64_t)d->sub_lost_parity : 0);
-            void* scope = profile_scope_begin(c, st, dev_list ? "direct_pass_list" : "direct_pass_batch", count * (rows + outputs) * block);
-            const int r = direct_run_batch(p, ddata, par_in, data_to, par_to, S, count, data_words, parity_words, st, dev_list);
-            profile_scope_end(scope);
-            return r;
+            ProfScope ps(c, st, dev_list ? "direct_pass_list" : "direct_pass_batch", count * (rows + outputs) * block);
+            return direct_run_batch(p, ddata, par_in, data_to, par_to, S, count, data_words, parity_words, st, dev_list);
         }
-        void* scope = profile_scope_begin(c, st, "direct_pass", count * (ci.user_k + (uint64_t)d->sub_lost_data) * block);
-        int r = FASTECC_OK;
-        for (uint64_t b = 0; b < count && r == FASTECC_OK; b++) {
+        ProfScope ps(c, st, "direct_pass", count * (c->K + (uint64_t)d->sub_lost_data) * block);
+        for (uint64_t b = 0; b < count; b++) {
             const uint64_t sb = stripe_of(b);
-            r = direct_run(p, ddata + sb * data_words, par_in ? par_in + sb * parity_words : nullptr, data_to ? data_to + sb * data_words : nullptr,
-                           par_to ? par_to + sb * parity_words : nullptr, (uint32_t)S, d->direct_kernel, st);
+            RC_TRY(direct_run(p, ddata + sb * data_words, par_in ? par_in + sb * parity_words : nullptr, data_to ? data_to + sb * data_words : nullptr,
+                              par_to ? par_to + sb * parity_words : nullptr, (uint32_t)S, d->direct_kernel, st));
         }
-        profile_scope_end(scope);
-        return r;
-    });
+        return FASTECC_OK;
+    };
+    return with_internal_buffers(c, st, [&] { return direct_passes(d, rebuild, ddata, dparity, dparity, run); });
 }
 
 // ---- fastecc_decode_prepare_set / _decode_batch_set / _repair_batch_set: a pattern per stripe ----
@@ -1839,9 +1799,8 @@ constexpr size_t SET_MAX_LOST = 16;  // one direct pass of a single sweep: pad <
 int prepare_set_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t* parity_present, uint64_t P)
 {
     if (!c || P > SET_MAX_PATTERNS || (P > 0 && (!data_present || !parity_present))) return FASTECC_E_INVAL;
-    if (sharded_of(c)) return FASTECC_E_UNSUPPORTED;
-    const CtxInfo ci = info_of(c);
-    if (ci.field != FASTECC_FIELD_GF_FFF00001 || ci.pitch != ci.words || ci.user_k >= 0xFFFFFFF0ull) return FASTECC_E_UNSUPPORTED;
+    if (c->sharded) return FASTECC_E_UNSUPPORTED;
+    if (c->field != FASTECC_FIELD_GF_FFF00001 || c->ld != c->S || c->K >= 0xFFFFFFF0ull) return FASTECC_E_UNSUPPORTED;
     // every pattern's lists first, on the host: lost data blocks, lost parity blocks, the surviving parity blocks that serve as nodes
     struct Lists {
         std::vector<uint32_t> R, Pl, A;
@@ -1849,28 +1808,27 @@ int prepare_set_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t*
     std::vector<Lists> lists(P);
     bool too_many = false;
     for (uint64_t q = 0; q < P; q++) {
-        const uint8_t* dp = data_present + q * ci.user_k;
-        const uint8_t* pp = parity_present + q * ci.user_m;
+        const uint8_t* dp = data_present + q * c->K;
+        const uint8_t* pp = parity_present + q * c->Mu;
         Lists& l = lists[q];
         uint64_t lost = 0;
-        each_lost(dp, ci.user_k, [&](uint64_t i) {
+        each_lost(dp, c->K, [&](uint64_t i) {
             if (++lost <= SET_MAX_LOST) l.R.push_back((uint32_t)i);
             return true;
         });
-        each_lost(pp, ci.user_m, [&](uint64_t j) {
+        each_lost(pp, c->Mu, [&](uint64_t j) {
             if (++lost <= SET_MAX_LOST) l.Pl.push_back((uint32_t)j);
             return true;
         });
-        if (lost > ci.user_m) return FASTECC_E_INVAL;  // fewer than k blocks survive: not decodable
+        if (lost > c->Mu) return FASTECC_E_INVAL;  // fewer than k blocks survive: not decodable
         too_many |= lost > SET_MAX_LOST;
-        for (uint64_t j = 0; j < ci.user_m && !too_many && l.A.size() < l.R.size(); j++)
+        for (uint64_t j = 0; j < c->Mu && !too_many && l.A.size() < l.R.size(); j++)
             if (pp[j]) l.A.push_back((uint32_t)j);
     }
     if (too_many) return FASTECC_E_UNSUPPORTED;
-    DeviceGuard dg(ci.device);
+    DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
-    CallScope call(c);
-    PatternSet*& slot = pattern_set_of(c);
+    CallLock lk(c->mu);
     PatternSet* fresh = nullptr;
     struct DropFresh {  // (whatever was built goes unless it became the context's set)
         PatternSet*& f;
@@ -1900,13 +1858,12 @@ int prepare_set_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t*
         HIP_TRY(hipMemcpy(fresh->d_passes, desc.data(), P * sizeof(DirectSetPass), hipMemcpyHostToDevice));
         pt.mark("tables of the set");
     }
-    const int rc = call.wait_idle();  // device work that still uses the previous set (its tables, its list buffer)
-    if (rc != FASTECC_OK) return rc;
-    if (fresh && slot) {  // the list buffers outlive a set
-        fresh->list = std::move(slot->list);
+    RC_TRY(wait_idle(c));  // device work that still uses the previous set (its tables, its list buffer)
+    if (fresh && c->pattern_set) {  // the list buffers outlive a set
+        fresh->list = std::move(c->pattern_set->list);
         fresh->list.pending = false;  // (the wait above outlasted the last copy out of the pinned side)
     }
-    std::swap(slot, fresh);  // (DropFresh frees the previous set)
+    std::swap(c->pattern_set, fresh);  // (DropFresh frees the previous set)
     return FASTECC_OK;
 }
 
@@ -1917,15 +1874,14 @@ int prepare_set_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t*
 int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, void* stream, bool repair)
 {
     if (!c || !data || !parity || !pattern_of || count == 0 || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
-    if (sharded_of(c)) return FASTECC_E_UNSUPPORTED;
-    CallScope call(c);
-    const CtxInfo ci = info_of(c);
-    if (ci.field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
-    if (ci.pitch != ci.words) return FASTECC_E_UNSUPPORTED;  // stripes of a pool are contiguous
-    const uint64_t block = ci.words * 4, data_bytes = ci.user_k * block, parity_bytes = ci.user_m * block;
-    if (count > UINT64_MAX / data_bytes || count > UINT64_MAX / parity_bytes) return FASTECC_E_INVAL;
-    if ((uint64_t)(uintptr_t)data > UINT64_MAX - count * data_bytes || (uint64_t)(uintptr_t)parity > UINT64_MAX - count * parity_bytes) return FASTECC_E_INVAL;
-    PatternSet* s = pattern_set_of(c);
+    if (c->sharded) return FASTECC_E_UNSUPPORTED;
+    CallLock lk(c->mu);
+    if (c->field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
+    if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;  // stripes of a pool are contiguous
+    PoolExtent x;
+    RC_TRY(pool_extent(c, data, parity, count, &x));
+    const uint64_t block = x.block;
+    PatternSet* s = c->pattern_set;
     if (!s) return FASTECC_E_INVAL;  // fastecc_decode_prepare_set first
     const uint64_t P = s->tables.size();
     constexpr int CLASSES = 5;
@@ -1942,11 +1898,10 @@ int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
         total++;
     }
     if (total == 0) return FASTECC_OK;
-    DeviceGuard dg(ci.device);
+    DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
     hipStream_t st = (hipStream_t)stream;
-    int rc = s->list.reserve(total, [&] { return call.wait_idle(); });  // (growing waits for the kernels that read the device list)
-    if (rc != FASTECC_OK) return rc;
+    RC_TRY(s->list.reserve(total, [&] { return wait_idle(c); }));  // (growing waits for the kernels that read the device list)
     uint64_t first[CLASSES], at[CLASSES], moved[CLASSES] = {};  // a class's entries: [first, first + per_class); blocks its passes read and write
     for (int k = 0; k < CLASSES; k++) first[k] = at[k] = k ? first[k - 1] + per_class[k - 1] : 0;
     for (uint64_t b = 0; b < count; b++) {
@@ -1958,41 +1913,37 @@ int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
         s->list.host[at[k]++] = DirectSetEntry{b, q, 0};
         moved[k] += (uint64_t)s->rows[q] + (uint64_t)s->tables[q].ed + (repair ? (uint64_t)s->tables[q].ep : 0);
     }
-    const uint64_t S = ci.words, data_words = ci.user_k * S, parity_words = ci.user_m * S;
+    const uint64_t S = c->S, data_words = c->K * S, parity_words = c->Mu * S;
     uint32_t* ddata = (uint32_t*)data;
     uint32_t* dparity = (uint32_t*)parity;
-    const int mode = ci.decode_batch_kernel;
+    const int mode = c->decode_batch_kernel;
     bool kernel[CLASSES], any_kernel = false;
     for (int k = 0; k < CLASSES; k++) {
         kernel[k] = at[k] > first[k] && (mode == 1 || (mode == 0 && rows_max[k] < 4096)) && direct_set_waves_per_entry(1 << k, data, parity, S) <= (1ull << 24);
         any_kernel |= kernel[k];
     }
-    if ((rc = call.begin(st)) != FASTECC_OK) return rc;
-    EndScope end{call, st};
-    if (any_kernel && (rc = s->list.publish(total, st)) != FASTECC_OK) return rc;
-    for (int k = 0; k < CLASSES; k++) {
-        const uint64_t n = at[k] - first[k];
-        if (n == 0) continue;
-        if (kernel[k]) {
-            void* scope = profile_scope_begin(c, st, "direct_pass_set", moved[k] * block);
-            rc = direct_run_set(1 << k, s->d_passes, s->list.dev + first[k], n, ddata, dparity, ddata, repair ? dparity : nullptr, S, data_words, parity_words, st);
-            profile_scope_end(scope);
-            if (rc != FASTECC_OK) return rc;
-            continue;
+    return with_internal_buffers(c, st, [&]() -> int {  // the set's tables and the list are internal buffers
+        if (any_kernel) RC_TRY(s->list.publish(total, st));
+        for (int k = 0; k < CLASSES; k++) {
+            const uint64_t n = at[k] - first[k];
+            if (n == 0) continue;
+            if (kernel[k]) {
+                ProfScope ps(c, st, "direct_pass_set", moved[k] * block);
+                RC_TRY(direct_run_set(1 << k, s->d_passes, s->list.dev + first[k], n, ddata, dparity, ddata, repair ? dparity : nullptr, S, data_words, parity_words, st));
+                continue;
+            }
+            ProfScope ps(c, st, "direct_pass", moved[k] * block);
+            for (uint64_t i = first[k]; i < at[k]; i++) {
+                const uint64_t b = s->list.host[i].stripe;
+                const uint32_t q = s->list.host[i].pass;
+                uint32_t* db = ddata + b * data_words;
+                uint32_t* pb = dparity + b * parity_words;
+                const bool reads_parity = s->kind[q] != PatternSet::PARITY, writes_data = reads_parity, writes_parity = repair && s->kind[q] != PatternSet::DATA;
+                RC_TRY(direct_run(s->pass(q), db, reads_parity ? pb : nullptr, writes_data ? db : nullptr, writes_parity ? pb : nullptr, (uint32_t)S, c->direct_kernel, st));
+            }
         }
-        void* scope = profile_scope_begin(c, st, "direct_pass", moved[k] * block);
-        for (uint64_t i = first[k]; i < at[k] && rc == FASTECC_OK; i++) {
-            const uint64_t b = s->list.host[i].stripe;
-            const uint32_t q = s->list.host[i].pass;
-            uint32_t* db = ddata + b * data_words;
-            uint32_t* pb = dparity + b * parity_words;
-            const bool reads_parity = s->kind[q] != PatternSet::PARITY, writes_data = reads_parity, writes_parity = repair && s->kind[q] != PatternSet::DATA;
-            rc = direct_run(s->pass(q), db, reads_parity ? pb : nullptr, writes_data ? db : nullptr, writes_parity ? pb : nullptr, (uint32_t)S, ci.direct_kernel, st);
-        }
-        profile_scope_end(scope);
-        if (rc != FASTECC_OK) return rc;
-    }
-    return FASTECC_OK;
+        return FASTECC_OK;
+    });
 }
 
 }  // namespace

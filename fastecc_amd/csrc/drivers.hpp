@@ -1,5 +1,7 @@
 // drivers.hpp — what the translation units behind the C ABI share beyond context.hpp: the encode drivers (encode.hip), the host staging
-// paths (host_stage.hip) and context creation (create.hip), called from the entry points in api.hip.  Nothing here is part of the ABI.
+// paths (host_stage.hip) and context creation (create.hip), called from the entry points in api.hip, decode.hip, scrub.hip, update.hip and
+// sharded.hip; and the one mechanism each for profiling (ProfScope, P61Hooks), for ordering the internal buffers between streams
+// (with_internal_buffers, wait_idle) and for the extent of a pool (pool_extent).  Nothing here is part of the ABI.
 #pragma once
 #include <condition_variable>
 #include <thread>
@@ -76,8 +78,12 @@ int encode_device(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStr
 // `count` stripes back to back (stripe b's k data blocks at data + b * k * S words, its n - k parity blocks at parity + b * (n - k) * S): fastecc_encode_pool
 int encode_pool_device(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, uint64_t count, hipStream_t st);
 int ntt_device(fastecc_ctx* c, uint32_t* data, bool inverse, hipStream_t st);
+// Work that uses the context's internal device buffers is ordered between streams (fastecc_ctx::buf_event); the caller holds c->mu for all three:
+// order makes `st` wait for the previous such work, mark records this one, wait_idle is the host-side wait for the last recorded one (instead of a
+// device-wide synchronise: before tables that device work may still read are rebuilt).
 int order_internal_buffers(fastecc_ctx* c, hipStream_t st);
 int mark_internal_buffers(fastecc_ctx* c, hipStream_t st);
+int wait_idle(fastecc_ctx* c);
 // Runs `body` (which enqueues work on `st` that uses internal buffers) between the two.
 template <class F> int with_internal_buffers(fastecc_ctx* c, hipStream_t st, F body)
 {
@@ -87,6 +93,33 @@ template <class F> int with_internal_buffers(fastecc_ctx* c, hipStream_t st, F b
     const int rc2 = mark_internal_buffers(c, st);  // also after a failure: part of the work may have been enqueued
     return rc != FASTECC_OK ? rc : rc2;
 }
+// The k-block work stripe of a fold > 0 / multi-coset context (allocated on first use); a caller may build its input
+// there and pass it as `data` to fastecc_encode, which then runs the DIF half in place.
+int scratch_of(fastecc_ctx* c, uint32_t** out);
+// GF((2^61-1)^2) codes other than (2N,N) work on padded copies of the caller's stripes: the context's two N-block work stripes
+int p61_work_stripes(fastecc_ctx* c, uint64_t** data_full, uint64_t** parity_full);
+
+// `count` stripes back to back (a pool): bytes per block, per data stripe and per parity stripe.  FASTECC_E_INVAL when count is 0, when the pool's
+// byte extent overflows 64 bits, or (wraps) when either pointer plus its extent wraps; a null `data` has nothing to wrap (fastecc_update_parity_batch
+// has no data pool).  wraps = false: the caller of a list form has already checked the pool.  *out is filled either way.
+struct PoolExtent {
+    uint64_t block, data_bytes, parity_bytes;
+};
+inline int pool_extent(const fastecc_ctx* c, const void* data, const void* parity, uint64_t count, PoolExtent* out, bool wraps = true)
+{
+    const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
+    *out = PoolExtent{block, data_bytes, parity_bytes};
+    if (count == 0 || count > UINT64_MAX / data_bytes || count > UINT64_MAX / parity_bytes) return FASTECC_E_INVAL;
+    if (!wraps) return FASTECC_OK;
+    if ((uint64_t)(uintptr_t)data > UINT64_MAX - count * data_bytes || (uint64_t)(uintptr_t)parity > UINT64_MAX - count * parity_bytes) return FASTECC_E_INVAL;
+    return FASTECC_OK;
+}
+
+// ---- decode.hip, for the scrubber (fastecc_correct_batch) ----
+// fastecc_repair_batch's work on the `count` stripes list[0 .. count) of a pool of back-to-back stripes, with the prepared pattern.  The list is
+// given twice: on the host (the stripe-by-stripe forms) and on the device (the batched launch).  The caller has checked the pool's pointers and
+// extent; takes the context's call lock itself.
+int repair_list(fastecc_ctx* c, void* data, void* parity, const uint64_t* host_list, const uint64_t* dev_list, uint64_t count, void* stream);
 // ---- host_stage.hip: stripes in host memory ----
 // PAGEABLE host memory (what RS.cpp's malloc'ed buffers are) <-> device.  The runtime's own pageable download stages through pinned memory
 // with one copying host thread: 2 GiB took 89 ms (24 GB/s) on a link that moves them in 37 ms.  Here a ring of pinned slots sits between the

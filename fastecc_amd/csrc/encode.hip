@@ -453,6 +453,11 @@ int mark_internal_buffers(fastecc_ctx* c, hipStream_t st)
     c->buf_used = true;
     return FASTECC_OK;
 }
+int wait_idle(fastecc_ctx* c)
+{
+    if (c->buf_used) HIP_TRY(hipEventSynchronize(c->buf_event));
+    return FASTECC_OK;
+}
 int mixed_dif(fastecc_ctx* c, const uint32_t* in, uint32_t* out, hipStream_t st)
 {
     if (c->q <= 1 || c->ntt_plan.empty()) return FASTECC_E_UNSUPPORTED;
@@ -630,16 +635,6 @@ int run_split_decode(fastecc_ctx* c, const uint32_t* data, const uint32_t* parit
     return rc;
 }
 
-CallScope::CallScope(fastecc_ctx* c) : c_(c) { c_->mu.lock(); }
-CallScope::~CallScope() { c_->mu.unlock(); }
-int CallScope::begin(hipStream_t st) { return order_internal_buffers(c_, st); }
-int CallScope::end(hipStream_t st) { return mark_internal_buffers(c_, st); }
-int CallScope::wait_idle()
-{
-    if (c_->buf_used) HIP_TRY(hipEventSynchronize(c_->buf_event));
-    return FASTECC_OK;
-}
-
 int p61_work_stripes(fastecc_ctx* c, uint64_t** data_full, uint64_t** parity_full)
 {
     RC_TRY(c->scratch.alloc(c->N * c->S));
@@ -647,13 +642,6 @@ int p61_work_stripes(fastecc_ctx* c, uint64_t** data_full, uint64_t** parity_ful
     *data_full = (uint64_t*)c->scratch.get();
     *parity_full = (uint64_t*)c->parbuf.get();
     return FASTECC_OK;
-}
-
-int encode_unlocked(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStream_t st)
-{
-    DeviceGuard dg(c->device);
-    if (!dg.ok) return FASTECC_E_DEVICE;
-    return encode_device(c, data, parity, st);
 }
 
 int scratch_of(fastecc_ctx* c, uint32_t** out)

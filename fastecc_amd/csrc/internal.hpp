@@ -1,4 +1,7 @@
-// internal.hpp — what decode.hip needs from api.hip / encode.hip / host_stage.hip / create.hip (nothing here is part of the ABI).
+// internal.hpp — what the translation units share that needs no fastecc_ctx member: the error helpers (HIP_TRY / hip_fail), DeviceGuard, guarded,
+// PhaseTimer, the code positions, the sub-states' forward declarations and destroy functions, and the interfaces of direct.hip, pool_encode.hip,
+// the transform contexts and the split transform (which take a context as an opaque pointer).  Whoever reads or writes the context itself includes
+// context.hpp (the struct) or drivers.hpp (the drivers, the call lock, buffer ordering, profiling).  Nothing here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -6,9 +9,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
-#include <mutex>
 #include <new>
-#include <string>
 #include <vector>
 
 #include "../../include/fastecc.h"
@@ -100,15 +101,8 @@ inline uint64_t code_parity_position(uint64_t N, int e, int fold, int cosets, ui
     return ((q << fold) << 1) + 1;
 }
 
-// ---- sharded.hip: one stripe in column slabs on several devices (fastecc_create_sharded) ----
-struct Sharded;
-void destroy_sharded(Sharded*);
-int sharded_encode_stripe(fastecc_ctx* shell, const void* data, void* parity, int mem_kind, hipStream_t st);
-enum { SH_PROFILE_ENABLE, SH_PROFILE_RESET, SH_SET_OPTION, SH_SET_PLAN };
-int sharded_forward(fastecc_ctx* shell, int what, const char* name, int value);
-int sharded_decode_prepare(fastecc_ctx* shell, const uint8_t* data_present, const uint8_t* parity_present);
-int sharded_decode_stripe(fastecc_ctx* shell, void* data, void* parity, int mem_kind, bool repair, hipStream_t st);
-fastecc_ctx* sharded_child(fastecc_ctx* shell, int g);
+struct Sharded;                            // sharded.hip: one stripe in column slabs on several devices (fastecc_create_sharded; its calls: context.hpp)
+void destroy_sharded(Sharded*);            // sharded.hip, called by fastecc_destroy
 
 // ---- direct.hip: blocks as fixed linear combinations of other blocks (few lost blocks / few parity blocks) ----
 struct DirectPass;                 // the weights of one pattern (or code) and the work buffers of its pass
@@ -154,10 +148,6 @@ uint64_t direct_set_waves_per_entry(int eb, const void* data, const void* parity
 int direct_run_set(int eb, const DirectSetPass* passes, const DirectSetEntry* entries, uint64_t n_entries, const uint32_t* data, const uint32_t* parity,
                    uint32_t* data_out, uint32_t* parity_out, uint64_t S, uint64_t data_stride, uint64_t parity_stride, hipStream_t st);
 bool direct_mfma_applies(const void* data, const void* parity, uint64_t words);
-// decode.hip, for the scrubber (fastecc_correct_batch): fastecc_repair_batch's work on the `count` stripes list[0 .. count) of a pool of back-to-back
-// stripes, with the prepared pattern.  The list is given twice: on the host (the stripe-by-stripe forms) and on the device (the batched launch).
-// The caller has checked the pool's pointers and extent; takes the context's call lock itself.
-int repair_list(fastecc_ctx* c, void* data, void* parity, const uint64_t* host_list, const uint64_t* dev_list, uint64_t count, void* stream);
 // encoding straight from the Lagrange basis for codes with few parity blocks (n - k <= direct_encode_max())
 struct DirectEncode;
 int direct_encode_max();
@@ -176,51 +166,12 @@ int pool_encode_mfma_tiles(uint64_t outputs);  // M-tiles per wave and sweep: 1,
 int pool_encode_mfma_run(const uint4* frag, uint32_t mt_total, int mt, const uint32_t* data, uint32_t* parity, uint32_t k, uint32_t outputs, uint32_t words,
                          uint64_t count, hipStream_t st);
 
-// ---- api.hip, encode.hip, host_stage.hip, create.hip ----
-struct CtxInfo {
-    int device, field, fold, cosets, log2k;
-    uint64_t k, words, pitch;  // blocks, words per block, words between device blocks
-    bool zero_extended;        // k or n - k is not the power of two the transform works on
-    uint64_t user_k, user_m;   // data / parity blocks of the caller's stripes (== k, k >> fold unless zero_extended)
-    int q;                     // > 1: the transform order is q * k (mixed radix); k is its power-of-two part
-    int direct_max;            // decoder: patterns with at most this many lost blocks take the direct path (option "decode_direct_max")
-    int direct_kernel;         // 0 choose, 1 VALU, 2 MFMA (option "direct_kernel")
-    int p61_stride;            // GF((2^61-1)^2) codes other than (2N,N): parity block j = block j * p61_stride of the (2N,N) parity
-    int decode_split;          // option "decode_split"
-    int decode_batch_kernel;   // option "decode_batch_kernel": 0 choose, 1 the batched kernel, 2 stripe by stripe
-};
-CtxInfo info_of(const fastecc_ctx* c);
-DecodeState*& decoder_of(fastecc_ctx* c);
-PatternSet*& pattern_set_of(fastecc_ctx* c);
-Sharded*& sharded_of(fastecc_ctx* c);
-namespace p61 {
-struct Decoder;
-struct Path;
-struct LaunchHooks;
-}
-p61::Decoder*& decoder61_of(fastecc_ctx* c);  // the erasure decoder of a GF((2^61-1)^2) context (gf61_decode.hip)
-p61::Path* p61_path_of(fastecc_ctx* c);       // its encoder
-// fastecc_profile_* over the launches of a p61 call: nullptr unless the context is profiling; *keep goes to p61_profile_done after the call
-// one record of fastecc_profile_* around a step of the decoder (its inner contexts are not the caller's): nullptr unless the context is profiling
-void* profile_scope_begin(fastecc_ctx* c, hipStream_t st, const char* name, uint64_t bytes);
-void profile_scope_end(void* scope);
-const p61::LaunchHooks* p61_profile_hooks(fastecc_ctx* c, void** keep);
-void p61_profile_done(void* keep);
-std::mutex& mutex_of(fastecc_ctx* c);
-// a context that owns nothing but its geometry: fastecc_create_sharded hangs the per-device contexts on it
-fastecc_ctx* new_shell_ctx(int root_device, int field, uint64_t k, uint64_t m, uint64_t block_bytes);
-void set_plan_text(fastecc_ctx* c, const std::string& t);
-int columns_supported(const fastecc_ctx* c);  // fastecc_encode_columns works on this context
-void set_error_detail(const char* what, hipError_t e);
+// ---- api.hip, host_copy.hip ----
 void set_error_text(const char* text);  // this thread's fastecc_last_error_detail, verbatim (a worker thread's text republished on the caller's)
 // host_copy.hip: `rows` pieces of `width` bytes between two pitched host buffers (software prefetch + streaming stores)
 void host_copy_rows(char* dst, size_t dst_pitch, const char* src, size_t src_pitch, size_t width, size_t rows);
-// a rows x width rectangle between PAGEABLE host memory and the device through c's ring of pinned slots (host_stage.hip stage_transfer); c's call lock is
-// the caller's business; threads = 0: the default number of helper threads
-int stage_rect(fastecc_ctx* c, bool to_device, void* host, size_t host_pitch, void* dev, size_t dev_pitch, size_t width, size_t rows, hipStream_t st, int threads);
-// device -> pageable host memory through a ring of pinned slots emptied by helper threads (host_stage.hip); synchronous; c's call lock held by the caller
-int download_pageable(fastecc_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st);
 
+// ---- create.hip, encode.hip: the transform contexts ----
 // A transform context (GF(0xFFF00001)): DIF over all log2k levels with inverse roots, the block holding coefficient m
 // multiplied by factor[m] (plain representatives, k entries), DIT back with forward roots keeping every 2^fold-th
 // output block.  fastecc_encode(ctx, in, out, FASTECC_MEM_DEVICE, stream) runs it; k may be 2^20 (no root of order 2k
@@ -281,28 +232,5 @@ int run_split_decode(fastecc_ctx* c, const uint32_t* data, const uint32_t* parit
 // impulse_table (optional): [IMPULSE_MAX][16][64] words (Montgomery form), entry [t][g][c] = block g + 16 c of a 1024-block tile after the DIF
 // levels with strides 512 ... 16 when block g + 16 t alone was 1 — with at most 16 IMPULSE_MAX parity groups in use those six of the parity
 // half's low levels are a multiply-add per word and block in use (MODE_DIF_IMPULSE)
-// The k-block work stripe of a fold > 0 / multi-coset context (allocated on first use); a caller may build its input
-// there and pass it as `data` to fastecc_encode, which then runs the DIF half in place.
-int scratch_of(fastecc_ctx* c, uint32_t** out);
-// GF((2^61-1)^2) codes other than (2N,N) work on padded copies of the caller's stripes: the context's two N-block work stripes
-int p61_work_stripes(fastecc_ctx* c, uint64_t** data_full, uint64_t** parity_full);
-// fastecc_encode on DEVICE memory for a caller that already holds the context's call lock (decode.hip: fastecc_repair)
-int encode_unlocked(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStream_t st);
-
-// Calls on one context are serialised on the host, and work that uses the context's internal device buffers is ordered
-// between streams (encode.hip: fastecc_ctx::mu / buf_event).  decode.hip's entry points take part through this scope:
-// the constructor locks, begin() makes `st` wait for the previous user of the internal buffers, end() records this one.
-class CallScope {
-public:
-    explicit CallScope(fastecc_ctx* c);
-    ~CallScope();
-    int begin(hipStream_t st);
-    int end(hipStream_t st);
-    int wait_idle();  // host-side wait for the last recorded use (instead of a device-wide synchronise)
-    CallScope(const CallScope&) = delete;
-    CallScope& operator=(const CallScope&) = delete;
-private:
-    fastecc_ctx* c_;
-};
 
 }  // namespace fastecc

@@ -492,10 +492,8 @@ int batch_args(fastecc_ctx* c, const void* data, const void* parity, uint64_t co
     if (count == 0) return FASTECC_E_INVAL;
     const int rc = scrub_args(c, data, parity, FASTECC_MEM_DEVICE);
     if (rc != FASTECC_OK) return rc;
-    const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
-    if (count > UINT64_MAX / data_bytes || count > UINT64_MAX / parity_bytes) return FASTECC_E_INVAL;
-    if ((uint64_t)(uintptr_t)data > UINT64_MAX - count * data_bytes || (uint64_t)(uintptr_t)parity > UINT64_MAX - count * parity_bytes) return FASTECC_E_INVAL;
-    return FASTECC_OK;
+    PoolExtent x;
+    return pool_extent(c, data, parity, count, &x);
 }
 
 // The chunk buffers (once per context): the largest power-of-two chunk whose fingerprint stripe holds at most 32 MiB with rows of at most 1 MiB.

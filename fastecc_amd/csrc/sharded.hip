@@ -35,7 +35,7 @@
 #include <thread>
 #include <vector>
 
-#include "devmem.hpp"
+#include "drivers.hpp"
 
 namespace fastecc {
 
@@ -128,11 +128,11 @@ namespace {
 
 void describe(fastecc_ctx* shell)
 {
-    Sharded* s = sharded_of(shell);
+    Sharded* s = shell->sharded;
     char buf[128];
     snprintf(buf, sizeof buf, "%d slabs x %llu B/block, sub_slabs=%d, gather=%s | ", (int)s->shards.size(), (unsigned long long)s->slab_bytes,
              s->sub_slabs, s->gather_mode == 2 ? (s->copy_engine_refused ? "kernel (copy engine refused)" : "kernel") : "copy-engine");
-    set_plan_text(shell, std::string(buf) + fastecc_plan_string(s->shards[0].ctx));
+    shell->plan_text = std::string(buf) + fastecc_plan_string(s->shards[0].ctx);
 }
 
 // A [rows][width bytes] window between two pitched buffers, on `st` of the current device.  Between device buffers the
@@ -202,7 +202,7 @@ bool injected_fault(Sharded* s)
     if (++s->fault_step != s->fault_at) return false;
     s->fault_at = 0;
     s->fault_step = 0;
-    set_error_detail("injected fault (option inject_fault)", hipErrorUnknown);
+    (void)hip_fail(hipErrorUnknown, "injected fault (option inject_fault)");
     return true;
 }
 
@@ -243,7 +243,7 @@ int start_after(Sharded* s, std::initializer_list<hipStream_t> streams, int o0, 
 }
 int join(fastecc_ctx* shell, hipStream_t st)
 {
-    Sharded* s = sharded_of(shell);
+    Sharded* s = shell->sharded;
     HIP_TRY(hipSetDevice(s->root));
     for (Shard& sh : s->shards) HIP_TRY(hipStreamWaitEvent(st, sh.ev_all, 0));
     if (s->copy_engine_refused) describe(shell);
@@ -267,7 +267,7 @@ int encode_sub_slab(Sharded* s, Shard& sh, const char* din, char* pout, int H, i
 int run_body(fastecc_ctx* shell, const void* const* data_slabs, const void* data_stripe, void* const* parity_slabs, void* parity_stripe,
              bool stripe_on_host, hipStream_t st)
 {
-    Sharded* s = sharded_of(shell);
+    Sharded* s = shell->sharded;
     const int G = (int)s->shards.size();
     const size_t slab = s->slab_bytes, full = s->block_bytes;
     const int H = sub_slab_count(s);
@@ -306,7 +306,7 @@ int run_body(fastecc_ctx* shell, const void* const* data_slabs, const void* data
 // Synchronous; the caller's stream has been waited for.
 int run_host_pageable(fastecc_ctx* shell, const void* data_stripe, void* parity_stripe, hipStream_t st)
 {
-    Sharded* s = sharded_of(shell);
+    Sharded* s = shell->sharded;
     const int G = (int)s->shards.size();
     const size_t slab = s->slab_bytes, full = s->block_bytes;
     HIP_TRY(hipSetDevice(s->root));
@@ -328,14 +328,14 @@ int run_host_pageable(fastecc_ctx* shell, const void* data_stripe, void* parity_
         int rc = FASTECC_OK;
         try {
             if (hipSetDevice(sh.device) != hipSuccess) rc = FASTECC_E_DEVICE;
-            if (rc == FASTECC_OK) rc = stage_rect(sh.ctx, true, const_cast<char*>((const char*)data_stripe) + (size_t)g * slab, full, sh.data_slab, slab, slab, s->K, sh.s_up, T);
+            if (rc == FASTECC_OK) rc = stage_transfer(sh.ctx, StageJob{true, const_cast<char*>((const char*)data_stripe) + (size_t)g * slab, full, sh.data_slab, slab, slab, s->K}, sh.s_up, T);
             if (rc == FASTECC_OK) rc = fastecc_encode(sh.ctx, sh.data_slab, sh.parity_slab, FASTECC_MEM_DEVICE, sh.s_up);
             if (rc == FASTECC_OK) {
                 std::lock_guard<std::mutex> lk(fault_mu);
                 if (injected_fault(s)) rc = FASTECC_E_DEVICE;
             }
             if (rc == FASTECC_OK && hipSetDevice(sh.device) != hipSuccess) rc = FASTECC_E_DEVICE;
-            if (rc == FASTECC_OK) rc = stage_rect(sh.ctx, false, (char*)parity_stripe + (size_t)g * slab, full, sh.parity_slab, slab, slab, s->M, sh.s_up, T);
+            if (rc == FASTECC_OK) rc = stage_transfer(sh.ctx, StageJob{false, (char*)parity_stripe + (size_t)g * slab, full, sh.parity_slab, slab, slab, s->M}, sh.s_up, T);
         } catch (...) {
             rc = FASTECC_E_NOMEM;
         }
@@ -373,7 +373,7 @@ int enable_all_pairs(Sharded* s)
             if (a.device == b.device) continue;
             int can = 0;
             if (hipDeviceCanAccessPeer(&can, a.device, b.device) != hipSuccess || !can) {
-                set_error_detail("hipDeviceCanAccessPeer(slab device -> slab device)", hipErrorPeerAccessUnsupported);
+                (void)hip_fail(hipErrorPeerAccessUnsupported, "hipDeviceCanAccessPeer(slab device -> slab device)");
                 s->all_pairs = -1;
                 return FASTECC_E_UNSUPPORTED;
             }
@@ -450,7 +450,7 @@ int all_to_all_step(Sharded* s, Shard& sh, void* const* dst, size_t dpitch, cons
 // so sub-slab h+1 is transposed in and sub-slab h-1 transposed out while sub-slab h is in the kernels.
 int run_blocks_body(fastecc_ctx* shell, const void* const* data, bool data_blocks, void* const* parity_blocks, hipStream_t st)
 {
-    Sharded* s = sharded_of(shell);
+    Sharded* s = shell->sharded;
     const int G = (int)s->shards.size();
     const size_t slab = s->slab_bytes, full = s->block_bytes;
     const uint64_t kg = s->K / G, mg = s->M / G;
@@ -507,7 +507,7 @@ int run_blocks_body(fastecc_ctx* shell, const void* const* data, bool data_block
 // between slabs.
 int run_decode_body(fastecc_ctx* shell, void* data_stripe, void* parity_stripe, bool stripe_on_host, bool repair, hipStream_t st)
 {
-    Sharded* s = sharded_of(shell);
+    Sharded* s = shell->sharded;
     const int G = (int)s->shards.size();
     const size_t slab = s->slab_bytes, full = s->block_bytes;
     RC_TRY(record_fork(s, st));
@@ -541,12 +541,27 @@ int wait_for_caller(Sharded* s, hipStream_t st)
     return FASTECC_OK;
 }
 
+// a context that owns nothing but its geometry: fastecc_create_sharded hangs the per-device contexts on it
+fastecc_ctx* new_shell_ctx(int root_device, int field, uint64_t k, uint64_t m, uint64_t block_bytes)
+{
+    fastecc_ctx* c = new (std::nothrow) fastecc_ctx();
+    if (!c) return nullptr;
+    c->device = root_device;
+    c->field = field;
+    c->N = c->K = k;
+    c->M = c->Mu = m;
+    c->S = c->ld = block_bytes / 4;
+    c->stripe_bytes = (size_t)k * block_bytes;
+    c->parity_bytes = (size_t)m * block_bytes;
+    return c;
+}
+
 }  // namespace
 
 int sharded_decode_prepare(fastecc_ctx* shell, const uint8_t* data_present, const uint8_t* parity_present)
 {
-    Sharded* s = sharded_of(shell);
-    std::lock_guard<std::mutex> lk(mutex_of(shell));
+    Sharded* s = shell->sharded;
+    CallLock lk(shell->mu);
     // the same pattern for every slab (each context keeps its own tables on its own device): one host thread per slab, so the set-ups — a host
     // scan and a few dozen small kernels each, synchronous — run side by side instead of n_slabs times 2.3 ms one after the other.
     // The error detail is thread-local and a worker must not throw: each worker maps exceptions to a code and hands its detail text back,
@@ -588,8 +603,8 @@ int sharded_decode_prepare(fastecc_ctx* shell, const uint8_t* data_present, cons
 int sharded_decode_stripe(fastecc_ctx* shell, void* data, void* parity, int mem_kind, bool repair, hipStream_t st)
 {
     if (mem_kind != FASTECC_MEM_DEVICE && mem_kind != FASTECC_MEM_HOST && mem_kind != FASTECC_MEM_HOST_PINNED) return FASTECC_E_INVAL;
-    Sharded* s = sharded_of(shell);
-    std::lock_guard<std::mutex> lk(mutex_of(shell));
+    Sharded* s = shell->sharded;
+    CallLock lk(shell->mu);
     const int rc = settled(s, [&] { return run_decode_body(shell, data, parity, mem_kind != FASTECC_MEM_DEVICE, repair, st); });
     // host stripes, pageable or pinned: synchronous, as include/fastecc.h says for fastecc_decode / fastecc_repair (the single-device path
     // stages both kinds the same way)
@@ -617,9 +632,9 @@ void destroy_sharded(Sharded* s)
 int sharded_encode_stripe(fastecc_ctx* shell, const void* data, void* parity, int mem_kind, hipStream_t st)
 {
     if (mem_kind != FASTECC_MEM_DEVICE && mem_kind != FASTECC_MEM_HOST && mem_kind != FASTECC_MEM_HOST_PINNED) return FASTECC_E_INVAL;
-    Sharded* s = sharded_of(shell);
+    Sharded* s = shell->sharded;
     if (parity == data && s->M > s->K) return FASTECC_E_INVAL;  // in place: the parity must fit the data stripe (as fastecc_encode on one device)
-    std::lock_guard<std::mutex> lk(mutex_of(shell));
+    CallLock lk(shell->mu);
     if (mem_kind == FASTECC_MEM_HOST && parity != data) return settled(s, [&] { return run_host_pageable(shell, data, parity, st); });
     const int rc = settled(s, [&] { return run_body(shell, nullptr, data, nullptr, parity, mem_kind != FASTECC_MEM_DEVICE, st); });
     if (rc != FASTECC_OK || mem_kind != FASTECC_MEM_HOST) return rc;
@@ -628,14 +643,14 @@ int sharded_encode_stripe(fastecc_ctx* shell, const void* data, void* parity, in
 
 fastecc_ctx* sharded_child(fastecc_ctx* shell, int g)
 {
-    Sharded* s = sharded_of(shell);
+    Sharded* s = shell->sharded;
     return (s && g >= 0 && g < (int)s->shards.size()) ? s->shards[g].ctx.get() : nullptr;
 }
 
 int sharded_forward(fastecc_ctx* shell, int what, const char* name, int value)
 {
-    Sharded* s = sharded_of(shell);
-    std::lock_guard<std::mutex> lk(mutex_of(shell));
+    Sharded* s = shell->sharded;
+    CallLock lk(shell->mu);
     if (what == SH_SET_OPTION && !strcmp(name, "sub_slabs")) {
         if (value < 1 || value > MAX_SUB || (value & (value - 1))) return FASTECC_E_INVAL;
         s->sub_slabs = value;
@@ -700,7 +715,7 @@ int fastecc_create_sharded(fastecc_ctx** out, uint64_t n, uint64_t k, uint64_t b
         if (shell) fastecc_destroy(shell);
         return FASTECC_E_NOMEM;
     }
-    sharded_of(shell) = s;  // from here on fastecc_destroy(shell) releases everything built so far
+    shell->sharded = s;  // from here on fastecc_destroy(shell) releases everything built so far
     s->root = gpu_ids[0];
     s->field = field;
     s->K = k;
@@ -716,7 +731,7 @@ int fastecc_create_sharded(fastecc_ctx** out, uint64_t n, uint64_t k, uint64_t b
             if (sh.device != s->root) {
                 int can = 0;
                 if (hipDeviceCanAccessPeer(&can, sh.device, s->root) != hipSuccess || !can) {
-                    set_error_detail("hipDeviceCanAccessPeer(slab device -> root)", hipErrorPeerAccessUnsupported);
+                    (void)hip_fail(hipErrorPeerAccessUnsupported, "hipDeviceCanAccessPeer(slab device -> root)");
                     return FASTECC_E_UNSUPPORTED;
                 }
             }
@@ -751,35 +766,35 @@ int fastecc_create_sharded(fastecc_ctx** out, uint64_t n, uint64_t k, uint64_t b
 
 int fastecc_encode_sharded(fastecc_ctx* c, const void* const* data_slabs, void* const* parity_slabs, void* parity, void* stream)
 {
-    if (!c || !sharded_of(c) || !data_slabs || (!parity_slabs && !parity)) return FASTECC_E_INVAL;
-    Sharded* s = sharded_of(c);
+    if (!c || !c->sharded || !data_slabs || (!parity_slabs && !parity)) return FASTECC_E_INVAL;
+    Sharded* s = c->sharded;
     const uintptr_t mask = s->field == FASTECC_FIELD_GF_P61_SQUARED ? 15u : 3u;
     if ((uintptr_t)parity & mask) return FASTECC_E_INVAL;
     for (size_t g = 0; g < s->shards.size(); g++) {
         if (!data_slabs[g] || ((uintptr_t)data_slabs[g] & mask)) return FASTECC_E_INVAL;
         if (parity_slabs && (!parity_slabs[g] || ((uintptr_t)parity_slabs[g] & mask))) return FASTECC_E_INVAL;
     }
-    std::lock_guard<std::mutex> lk(mutex_of(c));
+    CallLock lk(c->mu);
     return settled(s, [&] { return run_body(c, data_slabs, nullptr, parity_slabs, parity, false, (hipStream_t)stream); });
 }
 
 int fastecc_encode_sharded_blocks(fastecc_ctx* c, const void* const* data, int data_layout, void* const* parity_blocks, void* stream)
 {
-    if (!c || !sharded_of(c) || !data || !parity_blocks) return FASTECC_E_INVAL;
+    if (!c || !c->sharded || !data || !parity_blocks) return FASTECC_E_INVAL;
     if (data_layout != FASTECC_SHARD_SLABS && data_layout != FASTECC_SHARD_BLOCKS) return FASTECC_E_INVAL;
-    Sharded* s = sharded_of(c);
+    Sharded* s = c->sharded;
     const size_t G = s->shards.size();
     if (s->M % G || (data_layout == FASTECC_SHARD_BLOCKS && s->K % G)) return FASTECC_E_INVAL;  // whole blocks per GPU
     const uintptr_t mask = s->field == FASTECC_FIELD_GF_P61_SQUARED ? 15u : 3u;
     for (size_t g = 0; g < G; g++)
         if (!data[g] || ((uintptr_t)data[g] & mask) || !parity_blocks[g] || ((uintptr_t)parity_blocks[g] & mask)) return FASTECC_E_INVAL;
-    std::lock_guard<std::mutex> lk(mutex_of(c));
+    CallLock lk(c->mu);
     return settled(s, [&] { return run_blocks_body(c, data, data_layout == FASTECC_SHARD_BLOCKS, parity_blocks, (hipStream_t)stream); });
 }
 
 int fastecc_shard_info(const fastecc_ctx* c, int* n_slabs, uint64_t* slab_block_bytes, int* devices, int cap)
 {
-    Sharded* s = c ? sharded_of(const_cast<fastecc_ctx*>(c)) : nullptr;
+    Sharded* s = c ? c->sharded : nullptr;
     if (!s) return FASTECC_E_INVAL;
     if (n_slabs) *n_slabs = (int)s->shards.size();
     if (slab_block_bytes) *slab_block_bytes = s->slab_bytes;

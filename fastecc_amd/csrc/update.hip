@@ -644,10 +644,9 @@ int update_batch_args(fastecc_ctx* c, const void* data, const void* parity, uint
     if ((((uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks) & 3u) != 0) return FASTECC_E_INVAL;
     if (c->sharded || c->p61 || c->field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
     if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;  // stripes of a pool are contiguous
-    const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
-    if (count > UINT64_MAX / data_bytes || count > UINT64_MAX / parity_bytes) return FASTECC_E_INVAL;
-    if ((with_data && (uint64_t)(uintptr_t)data > UINT64_MAX - count * data_bytes) || (uint64_t)(uintptr_t)parity > UINT64_MAX - count * parity_bytes)
-        return FASTECC_E_INVAL;
+    PoolExtent x;
+    RC_TRY(pool_extent(c, with_data ? data : nullptr, parity, count, &x));
+    const uint64_t block = x.block;
     if (n_writes > UINT64_MAX / block) return FASTECC_E_INVAL;
     if (n_writes > 0xFFFFFFFFull / (LIST_WORDS + SEG_HEAD + 1)) return FASTECC_E_UNSUPPORTED;  // (rows and list offsets are 32-bit: over 700 million writes in one call)
     if (block + 64 * 16 > 0xFFFFFFFFull) return FASTECC_E_UNSUPPORTED;  // (blocks of 4 GiB: the kernel addresses a block through one buffer descriptor)
