@@ -119,6 +119,8 @@ def lib():
         f.argtypes, f.restype = [vp, vp, vp, u64, ctypes.POINTER(u32), vp, u64, u8p, u64p], i32
     L.fastecc_locate_errors_batch.argtypes = [vp, vp, vp, u64, vp, u64, u8p, u64p, u64, ctypes.POINTER(u32), u64p]
     L.fastecc_locate_errors_batch.restype = i32
+    L.fastecc_locate_errors_batch_set.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u32), vp, u64, u8p, u64p, u64, ctypes.POINTER(u32), u64p]
+    L.fastecc_locate_errors_batch_set.restype = i32
     L.fastecc_scrub_fingerprints.argtypes, L.fastecc_scrub_fingerprints.restype = [vp, vp, vp, u64, u64p, i32, vp, u64, ctypes.POINTER(u32), u8p], i32
     L.fastecc_update.argtypes, L.fastecc_update.restype = [vp, vp, vp, u64p, u64, vp, i32, vp], i32
     L.fastecc_update_parity.argtypes, L.fastecc_update_parity.restype = [vp, vp, u64p, u64, vp, vp, i32, vp], i32
@@ -472,7 +474,9 @@ class Encoder:
 
     def correct_batch_set(self, data, parity, count, pattern_of, seed=0, stream=0):
         """verify_batch_set, then what scrub_erasures(its pattern) + correct does to each inconsistent stripe (replaces the prepared
-        erasure pattern, not the decode_prepare_set set).  Returns the numpy uint8 status array: 0 = consistent or skipped and untouched,
+        erasure pattern — which one is left behind is unspecified — not the decode_prepare_set set).  Option "correct_batch_mode": 2 = stripe
+        by stripe, 1 = one batched location pass and one grouped repair through a pattern set private to the call, 0 (default) = 1 from two
+        qualifying stripes on; the same status and bytes in every mode.  Returns the numpy uint8 status array: 0 = consistent or skipped and untouched,
         1 = corrected (the whole codeword is back), 2 = uncorrectable.  If any stripe is uncorrectable, raises FastEccError with code
         E_UNCORRECTABLE after the others were corrected; the full status array is its `status` attribute."""
         code, out = self._scrub_batch_set(lib().fastecc_correct_batch_set, data, parity, count, pattern_of, seed, stream)
@@ -498,13 +502,37 @@ class Encoder:
         code = lib().fastecc_locate_errors_batch(self._h, _addr(data), _addr(parity), count, stream or None, seed,
                                                  status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), blocks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
                                                  cap, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(bad))
+        return self._located_batch(code, "fastecc_locate_errors_batch", status, blocks, counts, cap)
+
+    @staticmethod
+    def _located_batch(code, what, status, blocks, counts, cap):
+        """(status, lists) of a batched location call, or its error (E_UNCORRECTABLE carries both)"""
+        count = len(status)
         lists = [[int(x) for x in blocks[b * cap:b * cap + min(int(counts[b]), cap)]] for b in range(count)] if code in (OK, E_UNCORRECTABLE) else None
         if code == E_UNCORRECTABLE:
-            err = FastEccError(code, "fastecc_locate_errors_batch")
+            err = FastEccError(code, what)
             err.status, err.lists = status, lists
             raise err
-        _check(code, "fastecc_locate_errors_batch")
+        _check(code, what)
         return status, lists
+
+    def locate_errors_batch_set(self, data, parity, count, pattern_of, seed=0, stream=0):
+        """locate_errors_batch with stripe b under pattern pattern_of[b] of the scrub_erasures_set set: (status, lists) as there, each stripe's
+        answer the one scrub_erasures(that pattern) + locate_errors with the same seed gives; absent blocks are neither read nor listed, and a
+        PATTERN_NONE stripe is not read and has status 0.  Reads only.  Raises like locate_errors_batch, with `status` and `lists`."""
+        import numpy as np
+        count = self._batch_count(count)
+        keep, po = self._pattern_list(pattern_of, count)
+        cap = self.n - self.k
+        status = np.zeros(count, np.uint8)
+        blocks = np.zeros(count * cap, np.uint64)
+        counts = np.zeros(count, np.uint32)
+        bad = ctypes.c_uint64()
+        code = lib().fastecc_locate_errors_batch_set(self._h, _addr(data), _addr(parity), count, po, stream or None, seed,
+                                                     status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), blocks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                                     cap, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(bad))
+        del keep
+        return self._located_batch(code, "fastecc_locate_errors_batch_set", status, blocks, counts, cap)
 
     def scrub_fingerprints(self, data, parity, count=1, form=0, stripes=None, seed=0, stream=0):
         """What the fingerprint pass of the scrub calls computes (tests only): (F, big) with F a numpy uint32 array [entries, n, 3], F[i, j, c]

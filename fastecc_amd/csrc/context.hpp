@@ -172,7 +172,7 @@ struct fastecc_ctx {
     int direct_kernel = 0;        // 0 choose, 1 VALU, 2 MFMA
     int decode_batch_kernel = 0;  // fastecc_decode_batch / _repair_batch: 0 choose, 1 one launch per pass whenever it can, 2 stripe by stripe
     int encode_pool_kernel = 0;   // fastecc_encode_pool, direct path: 0 choose, 1 the VALU batch kernel, 2 the matrix-core pool kernel where it can run, 3 stripe by stripe
-    int correct_batch_mode = 0;   // fastecc_correct_batch: 0 choose, 1 batched location and grouped repair for every qualifying stripe, 2 fastecc_correct stripe by stripe
+    int correct_batch_mode = 0;   // fastecc_correct_batch / _correct_batch_set: 0 choose, 1 batched location and grouped repair for every qualifying stripe, 2 fastecc_correct stripe by stripe
     int slab_mode = 0;       // how `slabs` > 1 are scheduled (fastecc_set_option "slab_mode")
     int slabs = 1;           // > 1: encode in this many column slabs on internal streams, staggered by one pass,
                              // so the VALU-bound MID of one slab runs beside the HBM-bound outer passes of others

@@ -1792,8 +1792,40 @@ int decode_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, 
 }
 
 // ---- fastecc_decode_prepare_set / _decode_batch_set / _repair_batch_set: a pattern per stripe ----
-constexpr uint64_t SET_MAX_PATTERNS = 4096;
-constexpr size_t SET_MAX_LOST = 16;  // one direct pass of a single sweep: pad <= 16
+
+// one pattern on the host: lost data blocks, lost parity blocks, the surviving parity blocks that serve as nodes (one per lost data block)
+struct LostLists {
+    std::vector<uint32_t> R, Pl, A;
+};
+
+// The table-building part of fastecc_decode_prepare_set: the tables, kinds, classes and the device descriptor table of the patterns `lists` (each at
+// most SET_MAX_LOST blocks) into the empty set `fresh`.  The context's device is current; touches no context state (the context's own set comes through
+// here, and the scrubber's private one: repair_lost_sets).
+int fill_pattern_set(fastecc_ctx* c, const std::vector<LostLists>& lists, PatternSet* fresh)
+{
+    const uint64_t P = lists.size();
+    fresh->tables.resize(P);
+    fresh->kind.assign(P, PatternSet::NOTHING);
+    fresh->cls.assign(P, 0);
+    fresh->rows.assign(P, 0);
+    std::vector<DirectSetPass> desc(P, DirectSetPass{});
+    Prepare geometry(c, nullptr, nullptr);
+    PhaseTimer quiet;  // one line per set, not two per pattern
+    quiet.on = false;
+    for (uint64_t q = 0; q < P; q++) {
+        const LostLists& l = lists[q];
+        if (l.R.empty() && l.Pl.empty()) continue;  // nothing lost: its stripes are not touched
+        int rc = geometry.direct_tables(l.R, l.Pl, l.A, fresh->tables[q], quiet);
+        if (rc != FASTECC_OK) return rc;
+        fresh->kind[q] = !l.R.empty() && !l.Pl.empty() ? PatternSet::BOTH : !l.R.empty() ? PatternSet::DATA : PatternSet::PARITY;
+        if ((rc = direct_set_describe(fresh->pass(q), &desc[q])) != FASTECC_OK) return rc;
+        while ((1u << fresh->cls[q]) < desc[q].cstride) fresh->cls[q]++;
+        fresh->rows[q] = desc[q].rows;
+    }
+    RC_TRY(fresh->d_passes.alloc(P));
+    HIP_TRY(hipMemcpy(fresh->d_passes, desc.data(), P * sizeof(DirectSetPass), hipMemcpyHostToDevice));
+    return FASTECC_OK;
+}
 
 // The new set is built aside and swapped in at the end: a refused or failed call leaves the previous one in force.
 int prepare_set_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t* parity_present, uint64_t P)
@@ -1801,16 +1833,13 @@ int prepare_set_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t*
     if (!c || P > SET_MAX_PATTERNS || (P > 0 && (!data_present || !parity_present))) return FASTECC_E_INVAL;
     if (c->sharded) return FASTECC_E_UNSUPPORTED;
     if (c->field != FASTECC_FIELD_GF_FFF00001 || c->ld != c->S || c->K >= 0xFFFFFFF0ull) return FASTECC_E_UNSUPPORTED;
-    // every pattern's lists first, on the host: lost data blocks, lost parity blocks, the surviving parity blocks that serve as nodes
-    struct Lists {
-        std::vector<uint32_t> R, Pl, A;
-    };
-    std::vector<Lists> lists(P);
+    // every pattern's lists first, on the host
+    std::vector<LostLists> lists(P);
     bool too_many = false;
     for (uint64_t q = 0; q < P; q++) {
         const uint8_t* dp = data_present + q * c->K;
         const uint8_t* pp = parity_present + q * c->Mu;
-        Lists& l = lists[q];
+        LostLists& l = lists[q];
         uint64_t lost = 0;
         each_lost(dp, c->K, [&](uint64_t i) {
             if (++lost <= SET_MAX_LOST) l.R.push_back((uint32_t)i);
@@ -1836,26 +1865,8 @@ int prepare_set_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t*
     } drop{fresh};
     if (P > 0) {
         if (!(fresh = new (std::nothrow) PatternSet())) return FASTECC_E_NOMEM;
-        fresh->tables.resize(P);
-        fresh->kind.assign(P, PatternSet::NOTHING);
-        fresh->cls.assign(P, 0);
-        fresh->rows.assign(P, 0);
-        std::vector<DirectSetPass> desc(P, DirectSetPass{});
-        Prepare geometry(c, nullptr, nullptr);
-        PhaseTimer pt("[fastecc prepare_set]"), quiet;  // one line per set, not two per pattern
-        quiet.on = false;
-        for (uint64_t q = 0; q < P; q++) {
-            const Lists& l = lists[q];
-            if (l.R.empty() && l.Pl.empty()) continue;  // nothing lost: its stripes are not touched
-            int rc = geometry.direct_tables(l.R, l.Pl, l.A, fresh->tables[q], quiet);
-            if (rc != FASTECC_OK) return rc;
-            fresh->kind[q] = !l.R.empty() && !l.Pl.empty() ? PatternSet::BOTH : !l.R.empty() ? PatternSet::DATA : PatternSet::PARITY;
-            if ((rc = direct_set_describe(fresh->pass(q), &desc[q])) != FASTECC_OK) return rc;
-            while ((1u << fresh->cls[q]) < desc[q].cstride) fresh->cls[q]++;
-            fresh->rows[q] = desc[q].rows;
-        }
-        RC_TRY(fresh->d_passes.alloc(P));
-        HIP_TRY(hipMemcpy(fresh->d_passes, desc.data(), P * sizeof(DirectSetPass), hipMemcpyHostToDevice));
+        PhaseTimer pt("[fastecc prepare_set]");
+        RC_TRY(fill_pattern_set(c, lists, fresh));
         pt.mark("tables of the set");
     }
     RC_TRY(wait_idle(c));  // device work that still uses the previous set (its tables, its list buffer)
@@ -1867,22 +1878,16 @@ int prepare_set_impl(fastecc_ctx* c, const uint8_t* data_present, const uint8_t*
     return FASTECC_OK;
 }
 
-// `count` stripes back to back in device memory, stripe b with pattern pattern_of[b] of the prepared set (FASTECC_PATTERN_NONE: not touched).
+// The launch part of fastecc_decode_batch_set / _repair_batch_set, on a locked context: `count` stripes of the pool, item i = stripe stripe_of(i) with
+// pattern pattern_at(i) of the set s (FASTECC_PATTERN_NONE: not touched) — the pool's stripes under the caller's pattern_of (decode_batch_set_impl), or a
+// list of stripes each with its pass (repair_lost_sets).
 // The stripes that have work are sorted by the pad class of their pattern's pass; a class is ONE launch of direct_set_kernel when all its passes
 // read fewer than 4096 rows (from 4096 data rows on, the single-stripe path takes the matrix cores), else direct_run stripe by stripe with each
 // stripe's own table; option "decode_batch_kernel" decides when set.
-int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, void* stream, bool repair)
+template <class StripeOf, class PatternAt>
+int run_pattern_set(fastecc_ctx* c, PatternSet* s, void* data, void* parity, uint64_t block, uint64_t count, StripeOf stripe_of, PatternAt pattern_at, void* stream,
+                    bool repair)
 {
-    if (!c || !data || !parity || !pattern_of || count == 0 || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
-    if (c->sharded) return FASTECC_E_UNSUPPORTED;
-    CallLock lk(c->mu);
-    if (c->field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
-    if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;  // stripes of a pool are contiguous
-    PoolExtent x;
-    RC_TRY(pool_extent(c, data, parity, count, &x));
-    const uint64_t block = x.block;
-    PatternSet* s = c->pattern_set;
-    if (!s) return FASTECC_E_INVAL;  // fastecc_decode_prepare_set first
     const uint64_t P = s->tables.size();
     constexpr int CLASSES = 5;
     // the pass stripe b takes in this call: none for FASTECC_PATTERN_NONE, a pattern that lost nothing, and (decode) one that lost only parity
@@ -1890,7 +1895,7 @@ int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
     uint64_t per_class[CLASSES] = {}, total = 0;
     uint32_t rows_max[CLASSES] = {};
     for (uint64_t b = 0; b < count; b++) {
-        const uint32_t q = pattern_of[b];
+        const uint32_t q = pattern_at(b);
         if (q != FASTECC_PATTERN_NONE && q >= P) return FASTECC_E_INVAL;
         if (!work_of(q)) continue;
         per_class[s->cls[q]]++;
@@ -1905,12 +1910,12 @@ int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
     uint64_t first[CLASSES], at[CLASSES], moved[CLASSES] = {};  // a class's entries: [first, first + per_class); blocks its passes read and write
     for (int k = 0; k < CLASSES; k++) first[k] = at[k] = k ? first[k - 1] + per_class[k - 1] : 0;
     for (uint64_t b = 0; b < count; b++) {
-        const uint32_t q = pattern_of[b];
+        const uint32_t q = pattern_at(b);
         if (q != FASTECC_PATTERN_NONE && q >= P) return FASTECC_E_INVAL;  // (the caller's array changed under the call)
         if (!work_of(q)) continue;
         const int k = s->cls[q];
         if (at[k] >= first[k] + per_class[k]) return FASTECC_E_INVAL;
-        s->list.host[at[k]++] = DirectSetEntry{b, q, 0};
+        s->list.host[at[k]++] = DirectSetEntry{stripe_of(b), q, 0};
         moved[k] += (uint64_t)s->rows[q] + (uint64_t)s->tables[q].ed + (repair ? (uint64_t)s->tables[q].ep : 0);
     }
     const uint64_t S = c->S, data_words = c->K * S, parity_words = c->Mu * S;
@@ -1946,7 +1951,62 @@ int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
     });
 }
 
+// `count` stripes back to back in device memory, stripe b with pattern pattern_of[b] of the prepared set: the argument checks, then run_pattern_set
+int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, void* stream, bool repair)
+{
+    if (!c || !data || !parity || !pattern_of || count == 0 || (((uintptr_t)data | (uintptr_t)parity) & 3u)) return FASTECC_E_INVAL;
+    if (c->sharded) return FASTECC_E_UNSUPPORTED;
+    CallLock lk(c->mu);
+    if (c->field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
+    if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;  // stripes of a pool are contiguous
+    PoolExtent x;
+    RC_TRY(pool_extent(c, data, parity, count, &x));
+    PatternSet* s = c->pattern_set;
+    if (!s) return FASTECC_E_INVAL;  // fastecc_decode_prepare_set first
+    return run_pattern_set(c, s, data, parity, x.block, count, [](uint64_t b) { return b; }, [&](uint64_t b) { return pattern_of[b]; }, stream, repair);
+}
+
 }  // namespace
+
+// The scrubber's grouped repair (drivers.hpp): a pattern set of the lost sets, private to the call — fill_pattern_set, run_pattern_set
+// over the (stripe, set) list, and the set freed once the stream's work is done
+int repair_lost_sets(fastecc_ctx* c, void* data, void* parity, const std::vector<std::vector<uint32_t>>& lost_sets, const std::vector<uint64_t>& stripes,
+                     const std::vector<uint32_t>& set_of, void* stream)
+{
+    if (lost_sets.empty() || lost_sets.size() > SET_MAX_PATTERNS || stripes.empty() || stripes.size() != set_of.size()) return FASTECC_E_INVAL;
+    std::vector<LostLists> lists(lost_sets.size());
+    for (size_t q = 0; q < lost_sets.size(); q++) {
+        LostLists& l = lists[q];
+        if (lost_sets[q].size() > SET_MAX_LOST) return FASTECC_E_INVAL;
+        std::vector<uint8_t> parity_lost(c->Mu, 0);
+        for (uint32_t j : lost_sets[q]) {
+            if (j >= c->K + c->Mu) return FASTECC_E_INVAL;
+            if (j < c->K) {
+                l.R.push_back(j);
+            } else {
+                l.Pl.push_back((uint32_t)(j - c->K));
+                parity_lost[j - c->K] = 1;
+            }
+        }
+        for (uint64_t j = 0; j < c->Mu && l.A.size() < l.R.size(); j++)
+            if (!parity_lost[j]) l.A.push_back((uint32_t)j);
+        if (l.A.size() != l.R.size()) return FASTECC_E_INVAL;  // fewer than k blocks survive
+    }
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallLock lk(c->mu);
+    PatternSetPtr set;
+    struct Settle {  // (declared after the set: the stream's work, which reads the set's tables and list, is over before the set goes, on every path)
+        hipStream_t st;
+        ~Settle() { (void)hipStreamSynchronize(st); }
+    } settle{(hipStream_t)stream};
+    set.reset(new (std::nothrow) PatternSet());
+    if (!set) return FASTECC_E_NOMEM;
+    PhaseTimer pt("[fastecc correct_batch_set]");
+    RC_TRY(fill_pattern_set(c, lists, set));
+    pt.mark("  private set: tables");
+    return run_pattern_set(c, set, data, parity, c->S * 4, stripes.size(), [&](uint64_t i) { return stripes[i]; }, [&](uint64_t i) { return set_of[i]; }, stream, true);
+}
 
 int repair_list(fastecc_ctx* c, void* data, void* parity, const uint64_t* host_list, const uint64_t* dev_list, uint64_t count, void* stream)
 {

@@ -206,5 +206,6 @@ private:
 inline void destroy_ctx(fastecc_ctx* c) { (void)fastecc_destroy(c); }
 using CtxPtr = Owned<fastecc_ctx, destroy_ctx>;
 using DirectPassPtr = Owned<DirectPass, direct_pass_free>;
+using PatternSetPtr = Owned<PatternSet, destroy_pattern_set>;
 
 }  // namespace fastecc

@@ -120,6 +120,15 @@ inline int pool_extent(const fastecc_ctx* c, const void* data, const void* parit
 // given twice: on the host (the stripe-by-stripe forms) and on the device (the batched launch).  The caller has checked the pool's pointers and
 // extent; takes the context's call lock itself.
 int repair_list(fastecc_ctx* c, void* data, void* parity, const uint64_t* host_list, const uint64_t* dev_list, uint64_t count, void* stream);
+// What a pattern set takes (fastecc_decode_prepare_set, and the private set below)
+constexpr uint64_t SET_MAX_PATTERNS = 4096;
+constexpr size_t SET_MAX_LOST = 16;  // one direct pass of a single sweep: pad <= 16
+// fastecc_repair_batch_set's work through a pattern set PRIVATE to the call (fastecc_correct_batch_set): stripe stripes[i] of the
+// pool loses exactly the blocks lost_sets[set_of[i]] (codeword indices; at most 16 per set, at most 4096 sets).  One direct_set_kernel launch per size
+// class, as for the context's own set, which is neither read nor changed.  The caller has checked the pool's pointers and extent; takes the context's
+// call lock itself and returns only when the stream's work is done and the private set is freed.
+int repair_lost_sets(fastecc_ctx* c, void* data, void* parity, const std::vector<std::vector<uint32_t>>& lost_sets, const std::vector<uint64_t>& stripes,
+                     const std::vector<uint32_t>& set_of, void* stream);
 // ---- host_stage.hip: stripes in host memory ----
 // PAGEABLE host memory (what RS.cpp's malloc'ed buffers are) <-> device.  The runtime's own pageable download stages through pinned memory
 // with one copying host thread: 2 GiB took 89 ms (24 GB/s) on a link that moves them in 37 ms.  Here a ring of pinned slots sits between the

@@ -127,7 +127,7 @@ int fastecc_set_option(fastecc_ctx* c, const char* name, int value)
         c->encode_pool_kernel = value;
         return FASTECC_OK;
     }
-    if (!strcmp(name, "correct_batch_mode")) {  // fastecc_correct_batch, at call time: 0 = choose, 1 = batched location + grouped repair, 2 = fastecc_correct stripe by stripe
+    if (!strcmp(name, "correct_batch_mode")) {  // fastecc_correct_batch / _correct_batch_set, at call time: 0 = choose, 1 = batched location + grouped repair, 2 = fastecc_correct stripe by stripe
         if (value < 0 || value > 2) return FASTECC_E_INVAL;
         c->correct_batch_mode = value;
         return FASTECC_OK;

@@ -26,13 +26,17 @@
 //                (accept_root), and the confirmation: the syndromes once more with the located positions erased must all vanish, in every column.
 //   chunk pass   many stripes (section 14): the stripe index becomes extra word columns of the fingerprint stripe, so one transform serves a whole
 //                chunk of stripes.  chunk_pass runs one chunk — fingerprints, transform, syndrome launch — in the form a ChunkForm names, for
-//                verify_batch_locked (the stripes of a batch), verify_list_locked and LocateList (a LIST of stripes of the pool, section 17) and
-//                verify_batch_set_locked (a pattern per stripe).  A pass that fails part-way waits for what it enqueued (settled).
+//                verify_batch_locked (the stripes of a batch), verify_list_locked and LocateList (a LIST of stripes of the pool, section 17),
+//                verify_batch_set_locked (a pattern per stripe) and LocateList under the set (a list, a pattern per entry: section 27).  A pass that
+//                fails part-way waits for what it enqueued (settled).
 //   location     LocateList, per chunk of the flagged stripes: gather_chunk (all syndromes at once), solve_chunk (Berlekamp-Massey and the recurrence
-//                check per stripe on the host), search_chunk (one root search for all locators), accept_chunk.
+//                check per stripe on the host), search_chunk (one root search for all locators), accept_chunk.  locate_list: every entry under the
+//                single named pattern; locate_list_set: each under the pattern of the set its stripe has.
 //   correction   correct_stripe: locate, fastecc_decode_prepare + fastecc_repair of the located and the absent blocks, the closing verify.
 //                CorrectBatch: flag_and_locate, group_by_lost_set, repair_groups (one prepare and one list-form repair, decode.hip repair_list, per
 //                distinct set of lost blocks), closing_verify, fallbacks (correct_stripe's work on what the grouped path does not take).
+//                CorrectBatchSet (section 27): the same with a pattern per stripe — flag_and_group, repair_groups (ONE pattern set private to the call,
+//                decode.hip repair_lost_sets; the wide lost sets as CorrectBatch does), closing_verify, fallbacks.
 //   entry points argument checks, then the stage inside on_device.
 #include <algorithm>
 #include <map>
@@ -574,10 +578,12 @@ template <class F> int settled(hipStream_t st, F pass)
 // Fp, the fingerprint launch: BATCH stripes [b0, b0 + B) of the call under `er`, flags in d_flag; LIST entries [b0, b0 + B) of d_list under `er`, flags
 // and big marks in d_lflag; SET stripes [b0, b0 + B) under d_pattern_of and the set's tables, flags in d_flag.  Syn, the syndrome launch: FLAGS a non-zero
 // coefficient from m_lo on sets the entry's flag; GATHER all of them are copied to syn_out; SET they are checked from the stripe's own bound on.
-enum class Fp { BATCH, LIST, SET };
-enum class Syn { FLAGS, GATHER, SET };
-constexpr const char* FP_SCOPE[] = {"fingerprint_batch", "fingerprint_batch_list", "fingerprint_set"};
-constexpr const char* SYN_SCOPE[] = {"scrub_syndromes_batch", "scrub_syndromes_gather", "scrub_syndromes_set"};
+// SET_LIST (section 27): LIST entries, each under the pattern d_pattern_of gives its stripe; GATHER_SET: each entry's coefficients from its own pattern's
+// bound on are copied to syn_out, `stride` words per column.
+enum class Fp { BATCH, LIST, SET, SET_LIST };
+enum class Syn { FLAGS, GATHER, SET, GATHER_SET };
+constexpr const char* FP_SCOPE[] = {"fingerprint_batch", "fingerprint_batch_list", "fingerprint_set", "fingerprint_set_list"};
+constexpr const char* SYN_SCOPE[] = {"scrub_syndromes_batch", "scrub_syndromes_gather", "scrub_syndromes_set", "scrub_syndromes_gather_set"};
 
 struct ChunkForm {
     Fp fp;
@@ -585,8 +591,9 @@ struct ChunkForm {
     uint64_t m_lo;         // the first coefficient the syndrome launch looks at
     bool check;            // some coefficient is left to check (else the chunk ends after its fingerprints: only the words >= p count)
     Erasures er;           // BATCH, LIST: the pattern
-    uint32_t* syn_out;     // GATHER: device, B x R x (NC - m_lo) words
-    uint64_t blocks_read;  // SET: the blocks the chunk reads (the others read B (n - er.w))
+    uint32_t* syn_out;     // GATHER: device, B x R x (NC - m_lo) words; GATHER_SET: B x R x stride words
+    uint64_t blocks_read;  // SET, SET_LIST: the blocks the chunk reads (the others read B (n - er.w))
+    uint64_t stride = 0;   // GATHER_SET: words per column of syn_out
 };
 
 // One chunk of B entries from b0 on: the fingerprints (weighed by the erasures' locator as they are stored; absent blocks are not read and store
@@ -598,12 +605,12 @@ int chunk_pass(fastecc_ctx* c, ScrubState* s, const ChunkForm& f, const uint32_t
     const ScrubSet* t = s->set.get();
     const uint64_t row = RW * s->batch_cap;
     const uint32_t k = (uint32_t)s->k, n = (uint32_t)s->n, S = (uint32_t)c->S, NC = (uint32_t)s->NC, m_lo = (uint32_t)f.m_lo;
-    const bool vec = vec_form(c, data, parity), list = f.fp == Fp::LIST;
-    // every workgroup resident at once, as for one stripe: six waves per SIMD, five for the list kernel
+    const bool vec = vec_form(c, data, parity), list = f.fp == Fp::LIST || f.fp == Fp::SET_LIST, per_stripe = f.fp == Fp::SET || f.fp == Fp::SET_LIST;
+    // every workgroup resident at once, as for one stripe: six waves per SIMD, five for the list kernels
     const uint64_t groups = std::min<uint64_t>((B * n + 3) / 4, (uint64_t)c->cus * (list ? 5 : 6));
     uint8_t* flag = list ? s->d_lflag : s->d_flag;
     {
-        ProfScope ps(c, st, FP_SCOPE[(int)f.fp], (f.fp == Fp::SET ? f.blocks_read : B * (n - f.er.w)) * S * 4);
+        ProfScope ps(c, st, FP_SCOPE[(int)f.fp], (per_stripe ? f.blocks_read : B * (n - f.er.w)) * S * 4);
         switch (f.fp) {
         case Fp::BATCH:
             launch_fp(fingerprint_batch_kernel<true>, fingerprint_batch_kernel<false>, vec, groups, st, data, parity, k, n, S, b0, B, s->d_weights, f.er.d_pos,
@@ -616,6 +623,10 @@ int chunk_pass(fastecc_ctx* c, ScrubState* s, const ChunkForm& f, const uint32_t
         case Fp::SET:
             launch_fp(fingerprint_set_kernel<true>, fingerprint_set_kernel<false>, vec, groups, st, data, parity, k, n, S, b0, B, s->d_weights, s->d_pattern_of,
                       t->d_pos, t->d_l, NC, s->d_FB, row, flag);
+            break;
+        case Fp::SET_LIST:  // as LIST; d_pattern_of is indexed by stripe
+            launch_fp(fingerprint_set_list_kernel<true>, fingerprint_set_list_kernel<false>, vec, groups, st, data, parity, k, n, S, B, s->d_weights,
+                      s->d_pattern_of, t->d_pos, t->d_l, NC, s->d_FB, row, flag + b0, s->d_list + b0, flag + s->lflag_cap() + b0);
             break;
         }
         HIP_TRY(hipGetLastError());
@@ -640,6 +651,10 @@ int chunk_pass(fastecc_ctx* c, ScrubState* s, const ChunkForm& f, const uint32_t
             break;
         case Syn::SET:
             hipLaunchKernelGGL(syndrome_set_kernel, grid, dim3(256), 0, st, s->d_GB, s->lgc, NC, m_lo, row, (uint32_t)B, b0, s->d_pattern_of, t->d_mlo, flag);
+            break;
+        case Syn::GATHER_SET:
+            hipLaunchKernelGGL(syndrome_gather_set_kernel, grid, dim3(256), 0, st, s->d_GB, s->lgc, NC, m_lo, row, (uint32_t)B, s->d_list + b0, s->d_pattern_of, t->d_mlo,
+                               (uint32_t)f.stride, f.syn_out);
             break;
         }
         HIP_TRY(hipGetLastError());
@@ -732,6 +747,8 @@ enum : uint8_t { LOC_FALLBACK = 0, LOC_FOUND = 1, LOC_UNCORRECTABLE = 2 };
 // LOC_UNCORRECTABLE where it would refuse, or LOC_FALLBACK for a stripe this path does not take: a present block holds a word >= p, or the code
 // has more than 512 syndromes.  Per chunk: one list pass that gathers every syndrome (gather_chunk), Berlekamp-Massey and the recurrence check on
 // the host (solve_chunk), one root search over all locators (search_chunk), the roots' blocks (accept_chunk); two synchronisations.
+// pattern_of (host, by stripe): every entry under its own pattern of the set instead — the SET_LIST pass, avail per entry
+// (each in [1, GATHER_MAX]: locate_list_set lists no others), the device copy d_pattern_of that the call's verify pass made.
 struct LocateList {
     static constexpr uint64_t GATHER_MAX = 512;
     fastecc_ctx* c;
@@ -742,8 +759,9 @@ struct LocateList {
     hipStream_t st;
     std::vector<uint8_t>& state;
     std::vector<std::vector<uint32_t>>& blocks;
+    const uint32_t* pattern_of = nullptr;
     ChunkForm form{};                                                  // the list pass that gathers; form.syn_out: the chunk's syndromes
-    uint64_t avail = 0, tmax = 0, gather = 0, stride = 0, cap = 0;     // syndromes per column, locate_max, those Berlekamp-Massey reads, words per locator, roots kept
+    uint64_t avail = 0, tmax = 0, gather = 0, stride = 0, cap = 0;     // syndromes per column (the most of any entry), locate_max, those Berlekamp-Massey reads, words per locator, roots kept
     uint32_t *d_lam = nullptr, *d_len = nullptr, *d_found = nullptr;   // the chunk's locators, their lengths, the found lists
     std::vector<uint32_t> syn, len, found, cand;                       // host copies; Berlekamp-Massey's scratch
     std::vector<uint8_t> big;
@@ -758,7 +776,10 @@ struct LocateList {
         const uint64_t syn_words = chunk * R * avail, lam_words = chunk * stride, found_words = chunk * (cap + 1);
         const int rc = s->d_loc.grow(syn_words + lam_words + chunk + found_words);
         if (rc != FASTECC_OK) return rc;
-        form = pattern_form(s, Fp::LIST, true, s->d_loc);
+        if (pattern_of)
+            form = ChunkForm{Fp::SET_LIST, Syn::GATHER_SET, s->set->mlo_min, true, {}, s->d_loc, 0, avail};
+        else
+            form = pattern_form(s, Fp::LIST, true, s->d_loc);
         d_lam = s->d_loc + syn_words;
         d_len = d_lam + lam_words;
         d_found = d_len + chunk;
@@ -770,6 +791,8 @@ struct LocateList {
     // the list pass over entries [l0, l0 + B), every syndrome and the big marks copied back; the chunk's first synchronisation
     int gather_chunk(uint64_t l0, uint64_t B)
     {
+        form.blocks_read = 0;
+        for (uint64_t i = l0; pattern_of && i < l0 + B; i++) form.blocks_read += s->n - view_of(i).w;
         const int rc = chunk_pass(c, s, form, data, parity, l0, B, st);
         if (rc != FASTECC_OK) return rc;
         HIP_TRY(hipMemcpyAsync(syn.data(), form.syn_out, B * R * avail * 4, hipMemcpyDeviceToHost, st));
@@ -777,6 +800,10 @@ struct LocateList {
         HIP_TRY(hipStreamSynchronize(st));
         return FASTECC_OK;
     }
+
+    // the erasures entry i is located under, and the syndromes it has per column
+    Erasures view_of(uint64_t i) const { return pattern_of ? set_view(s, pattern_of[list[i]]) : form.er; }
+    uint64_t avail_of(uint64_t i) const { return pattern_of ? s->n - s->k - view_of(i).w : avail; }
 
     // host only: who and lambdas, the entries with a locator that every syndrome confirms; the others keep LOC_FALLBACK or become LOC_UNCORRECTABLE
     void solve_chunk(uint64_t l0, uint64_t B)
@@ -786,13 +813,16 @@ struct LocateList {
         for (uint64_t b = 0; b < B; b++) {
             if (big[b]) continue;  // known erasures besides the named ones: the single-stripe code
             const uint32_t* sy = syn.data() + b * R * avail;
-            if (std::all_of(sy, sy + R * avail, [](uint32_t v) { return v == 0; })) continue;  // (consistent after all: cannot happen for a stripe the same seed flagged)
+            const uint64_t have = avail_of(l0 + b);  // (the entry's columns are `avail` words apart and hold `have`)
+            bool zero = true;
+            for (int col = 0; col < R && zero; col++) zero = std::all_of(sy + col * avail, sy + col * avail + have, [](uint32_t v) { return v == 0; });
+            if (zero) continue;  // (consistent after all: cannot happen for a stripe the same seed flagged)
             state[l0 + b] = LOC_UNCORRECTABLE;
             std::vector<uint32_t> lambda;
-            if (longest_lfsr(sy, avail, gather, tmax, lambda, cand) == 0) continue;
+            if (longest_lfsr(sy, avail, std::min<uint64_t>(2 * tmax, have), tmax, lambda, cand) == 0) continue;
             // confirmation: every syndrome of every column obeys the locator's recurrence
             bool ok = true;
-            for (int col = 0; col < R && ok; col++) ok = obeys_recurrence(sy + col * avail, avail, lambda);
+            for (int col = 0; col < R && ok; col++) ok = obeys_recurrence(sy + col * avail, have, lambda);
             if (!ok) continue;
             who.push_back(l0 + b);
             lambdas.push_back(std::move(lambda));
@@ -832,7 +862,8 @@ struct LocateList {
             if (f[0] != len[e]) continue;  // a locator splits into distinct roots at the code's positions, or it is no locator
             std::vector<uint32_t> js;
             bool ok = true;
-            for (uint32_t i = 0; i < f[0] && ok; i++) ok = accept_root(f[1 + i], s->block_at, form.er, nullptr, js);
+            const Erasures er = view_of(who[e]);
+            for (uint32_t i = 0; i < f[0] && ok; i++) ok = accept_root(f[1 + i], s->block_at, er, nullptr, js);
             if (!ok) continue;
             std::sort(js.begin(), js.end());
             blocks[who[e]] = std::move(js);
@@ -846,6 +877,8 @@ struct LocateList {
         state.assign(L, LOC_FALLBACK);
         blocks.assign(L, {});
         avail = m > w ? m - w : 0;
+        if (pattern_of) avail = 0;
+        for (uint64_t i = 0; pattern_of && i < L; i++) avail = std::max(avail, avail_of(i));
         tmax = (uint64_t)c->locate_max;
         if (L == 0 || avail == 0 || avail > GATHER_MAX) return FASTECC_OK;
         int rc = list_begin(c, s, list, seed, st);
@@ -873,6 +906,37 @@ int locate_list(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, co
         if (rc != FASTECC_OK) return rc;
         LocateList ll{c, s, data, parity, list, seed, st, state, blocks};
         return ll.run();
+    });
+}
+
+// locate_list with stripe list[i] under pattern pattern_of[list[i]] of the set (every listed stripe has a pattern).  Called under the
+// same lock as the verify_batch_set_locked whose flags made the list: its device copy of pattern_of serves the list pass.  Entries whose pattern leaves
+// no syndrome or more than the batched pass gathers are not passed on and keep LOC_FALLBACK, so stripes of both kinds may share a call.
+int locate_list_set(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, const std::vector<uint64_t>& list, const uint32_t* pattern_of, uint64_t seed,
+                    hipStream_t st, std::vector<uint8_t>& state, std::vector<std::vector<uint32_t>>& blocks)
+{
+    return settled(st, [&]() -> int {
+        ScrubState* s = c->scrub;
+        const uint64_t m = s->n - s->k;
+        std::vector<uint64_t> taken, at;  // the entries the batched pass takes: their stripes, their places in `list`
+        for (size_t i = 0; i < list.size(); i++) {
+            const uint64_t w = s->set->absent[pattern_of[list[i]]].size();
+            if (w >= m || m - w > LocateList::GATHER_MAX) continue;
+            taken.push_back(list[i]);
+            at.push_back(i);
+        }
+        state.assign(list.size(), LOC_FALLBACK);
+        blocks.assign(list.size(), {});
+        std::vector<uint8_t> st_taken;
+        std::vector<std::vector<uint32_t>> bl_taken;
+        LocateList ll{c, s, data, parity, taken, seed, st, st_taken, bl_taken, pattern_of};
+        const int rc = ll.run();
+        if (rc != FASTECC_OK) return rc;
+        for (size_t e = 0; e < at.size(); e++) {
+            state[at[e]] = st_taken[e];
+            blocks[at[e]] = std::move(bl_taken[e]);
+        }
+        return FASTECC_OK;
     });
 }
 
@@ -1090,6 +1154,33 @@ int correct_stripe(fastecc_ctx* c, void* data, void* parity, void* stream, uint6
     return ok ? FASTECC_OK : FASTECC_E_UNCORRECTABLE;
 }
 
+// A batched location's outputs as its entry points report them — state[i] (LOC_FOUND / LOC_UNCORRECTABLE, no LOC_FALLBACK left) and found[i] of stripe
+// list[i], every other stripe consistent — and its return code.  Every output is written only here, at the end: a failed call leaves them alone.
+int report_located(const std::vector<uint64_t>& list, const std::vector<uint8_t>& state, const std::vector<std::vector<uint32_t>>& found, uint64_t count,
+                   uint8_t* status, uint64_t* blocks, uint64_t cap, uint32_t* counts, uint64_t* inconsistent)
+{
+    uint64_t bad = 0;
+    bool uncorrectable = false;
+    std::fill(status, status + count, (uint8_t)0);
+    if (counts) std::fill(counts, counts + count, 0u);
+    for (size_t i = 0; i < list.size(); i++) {
+        const uint64_t b = list[i];
+        if (state[i] == LOC_UNCORRECTABLE) {
+            status[b] = 2;
+            uncorrectable = true;
+            bad++;
+            continue;
+        }
+        if (found[i].empty()) continue;  // (consistent after all)
+        status[b] = 1;
+        bad++;
+        if (counts) counts[b] = (uint32_t)found[i].size();
+        for (uint64_t q = 0; q < found[i].size() && q < cap; q++) blocks[b * cap + q] = found[i][q];
+    }
+    *inconsistent = bad;
+    return uncorrectable ? FASTECC_E_UNCORRECTABLE : FASTECC_OK;
+}
+
 int report(const std::vector<uint32_t>& found, uint64_t* blocks, uint64_t cap, uint64_t* count)
 {
     for (uint64_t i = 0; i < found.size() && i < cap; i++) blocks[i] = found[i];
@@ -1217,6 +1308,165 @@ struct CorrectBatch {
             if (!order.empty() && ((r = repair_groups()) != FASTECC_OK || (r = closing_verify()) != FASTECC_OK)) return r;
         }
         if ((r = fallbacks()) != FASTECC_OK) return r;
+        std::copy(status.begin(), status.end(), status_out);
+        *inconsistent = list.size();
+        return uncorrectable ? FASTECC_E_UNCORRECTABLE : FASTECC_OK;
+    }
+};
+
+// fastecc_verify_batch_set on a locked context (set_args passed): the inconsistent stripes, increasing
+int flagged_set(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, const uint32_t* pattern_of, uint64_t seed, hipStream_t st,
+                std::vector<uint64_t>& list)
+{
+    std::vector<uint8_t> flag;
+    const int r = verify_batch_set_locked(c, data, parity, count, pattern_of, seed, st, flag);
+    if (r != FASTECC_OK) return r;
+    for (uint64_t b = 0; b < count; b++)
+        if (flag[b]) list.push_back(b);
+    return FASTECC_OK;
+}
+
+// fastecc_correct_batch_set (arguments checked): CorrectBatch with a pattern per stripe.  Grouped: the located stripes by lost set —
+// located blocks and the blocks absent under the stripe's own pattern — repaired through ONE pattern set private to the call (repair_lost_sets: one launch
+// per size class; lost sets of more than 16 blocks and distinct sets beyond the 4096th take section 17's route, one prepare and one list-form repair per
+// set), one closing verify for all of them, and correct_stripe under the stripe's pattern for whatever that leaves.
+struct CorrectBatchSet {
+    fastecc_ctx* c;
+    void *data, *parity;
+    uint64_t count;
+    const uint32_t* pattern_of;
+    void* stream;
+    uint64_t seed;
+    std::vector<uint64_t> list;                    // the inconsistent stripes
+    std::vector<uint8_t> state;                    // grouped: LOC_* per list entry
+    std::vector<std::vector<uint32_t>> found;      // grouped: the located blocks per list entry
+    bool grouped = false;
+    std::vector<std::vector<uint32_t>> lost_sets;  // per distinct lost set of the private set: located and absent blocks, sorted
+    std::vector<uint64_t> stripes;                 // the private set's stripes ...
+    std::vector<uint32_t> set_of;                  // ... and the lost set of each
+    std::vector<std::vector<uint32_t>> wide_sets;  // the lost sets that go set by set
+    std::vector<std::vector<uint64_t>> wide_members;
+    std::vector<uint64_t> order;                   // every repaired stripe: the private set's, then the wide sets' members back to back
+    DeviceBuf<uint64_t> dev_order;                 // the wide sets' part of it on the device, for this call only
+    std::vector<uint8_t> status;
+    bool uncorrectable = false;
+    PhaseTimer pt{"[fastecc correct_batch_set]"};  // (FASTECC_TRACE_PREPARE: where a call's wall time goes, host work included)
+
+    // under the lock: the inconsistent stripes and, where the mode and their number allow grouping, their located blocks and lost sets (the set's own
+    // lists of absent blocks are read here: another call may replace the set once the lock is released)
+    int flag_and_group()
+    {
+        const int mode = c->correct_batch_mode;
+        CallLock lk(c->mu);
+        int r = set_args(c, pattern_of, count);
+        if (r != FASTECC_OK) return r;
+        r = flagged_set(c, (const uint32_t*)data, (const uint32_t*)parity, count, pattern_of, seed, (hipStream_t)stream, list);
+        if (r != FASTECC_OK) return r;
+        status.assign(count, 0);
+        const size_t least = mode == 1 ? 1 : 2;  // as for fastecc_correct_batch
+        pt.mark("verify pass");
+        if (mode == 2 || list.size() < least) return FASTECC_OK;
+        if ((r = locate_list_set(c, (const uint32_t*)data, (const uint32_t*)parity, list, pattern_of, seed, (hipStream_t)stream, state, found)) != FASTECC_OK) return r;
+        pt.mark("batched location");
+        grouped = list.size() - (size_t)std::count(state.begin(), state.end(), (uint8_t)LOC_FALLBACK) >= least;
+        if (!grouped) return FASTECC_OK;
+        const ScrubSet* t = c->scrub->set.get();
+        std::map<std::vector<uint32_t>, size_t> narrow_of, wide_of;
+        for (size_t i = 0; i < list.size(); i++) {
+            if (state[i] == LOC_UNCORRECTABLE) {
+                status[list[i]] = 2;
+                uncorrectable = true;
+            }
+            if (state[i] != LOC_FOUND || found[i].empty()) continue;
+            std::vector<uint32_t> lost(found[i]);
+            const std::vector<uint32_t>& absent = t->absent[pattern_of[list[i]]];
+            lost.insert(lost.end(), absent.begin(), absent.end());
+            std::sort(lost.begin(), lost.end());
+            auto it = narrow_of.find(lost);
+            if (it == narrow_of.end() && lost.size() <= SET_MAX_LOST && lost_sets.size() < SET_MAX_PATTERNS) {
+                it = narrow_of.emplace(lost, lost_sets.size()).first;
+                lost_sets.push_back(lost);
+            }
+            if (it != narrow_of.end()) {
+                stripes.push_back(list[i]);
+                set_of.push_back((uint32_t)it->second);
+                continue;
+            }
+            auto wt = wide_of.find(lost);
+            if (wt == wide_of.end()) {
+                wt = wide_of.emplace(lost, wide_sets.size()).first;
+                wide_sets.push_back(lost);
+                wide_members.emplace_back();
+            }
+            wide_members[wt->second].push_back(list[i]);
+        }
+        order = stripes;
+        for (const auto& mb : wide_members) order.insert(order.end(), mb.begin(), mb.end());
+        pt.mark("lost sets");
+        return FASTECC_OK;
+    }
+
+    // the private set's stripes in one call, then one prepare and one list-form repair per wide set (all take the lock themselves)
+    int repair_groups()
+    {
+        if (!stripes.empty()) RC_TRY(repair_lost_sets(c, data, parity, lost_sets, stripes, set_of, stream));
+        if (wide_sets.empty()) return FASTECC_OK;
+        const uint64_t first = stripes.size();
+        RC_TRY(dev_order.alloc(order.size() - first));
+        HIP_TRY(hipMemcpy(dev_order, order.data() + first, (order.size() - first) * 8, hipMemcpyHostToDevice));
+        return settled((hipStream_t)stream, [&]() -> int {  // (dev_order goes with this object: a failure waits for the repairs that read it)
+            uint64_t at = 0;
+            for (size_t g = 0; g < wide_sets.size(); g++) {
+                RC_TRY(prepare_lost(c, wide_sets[g]));
+                RC_TRY(repair_list(c, data, parity, order.data() + first + at, dev_order + at, wide_members[g].size(), stream));
+                at += wide_members[g].size();
+            }
+            return FASTECC_OK;
+        });
+    }
+
+    // as CorrectBatch::closing_verify: every block of every repaired stripe, whatever pattern is named
+    int closing_verify()
+    {
+        std::vector<uint8_t> still;
+        {
+            CallLock lk(c->mu);
+            RC_TRY(verify_list_locked(c, (const uint32_t*)data, (const uint32_t*)parity, order, closing_seed(seed), (hipStream_t)stream, false, still));
+        }
+        for (size_t i = 0; i < order.size(); i++) {
+            status[order[i]] = still[i] ? 2 : 1;
+            uncorrectable = uncorrectable || still[i];
+        }
+        return FASTECC_OK;
+    }
+
+    // fastecc_correct under the stripe's own pattern (correct_stripe takes the lock itself) on what the grouped path left: every inconsistent stripe, or
+    // the LOC_FALLBACK ones
+    int fallbacks()
+    {
+        const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
+        std::vector<uint32_t> located;
+        for (size_t i = 0; i < list.size(); i++) {
+            if (grouped && state[i] != LOC_FALLBACK) continue;
+            const uint64_t b = list[i];
+            int r = correct_stripe(c, (char*)data + b * data_bytes, (char*)parity + b * parity_bytes, stream, seed, true, pattern_of[b], located);
+            if ((r = record_status(r, !located.empty(), &status[b], &uncorrectable)) != FASTECC_OK) return r;
+        }
+        return FASTECC_OK;
+    }
+
+    int run(uint8_t* status_out, uint64_t* inconsistent)
+    {
+        int r = flag_and_group();
+        if (r != FASTECC_OK) return r;
+        if (!order.empty()) {
+            if ((r = repair_groups()) != FASTECC_OK) return r;
+            pt.mark("private set and repair");
+            if ((r = closing_verify()) != FASTECC_OK) return r;
+            pt.mark("closing verify");
+        }
+        if ((r = fallbacks()) != FASTECC_OK) return r;
+        pt.mark("stripe by stripe");
         std::copy(status.begin(), status.end(), status_out);
         *inconsistent = list.size();
         return uncorrectable ? FASTECC_E_UNCORRECTABLE : FASTECC_OK;
@@ -1376,26 +1626,7 @@ int fastecc_locate_errors_batch(fastecc_ctx* c, const void* data, const void* pa
                        found[i], false);
             if ((r = record_status(r, !found[i].empty(), &state[i], &uncorrectable)) != FASTECC_OK) return r;  // (the status codes 1 and 2 are LOC_FOUND and LOC_UNCORRECTABLE)
         }
-        // every output is written only now: a failed call leaves them alone
-        uint64_t bad = 0;
-        std::fill(status, status + count, (uint8_t)0);
-        if (counts) std::fill(counts, counts + count, 0u);
-        for (size_t i = 0; i < list.size(); i++) {
-            const uint64_t b = list[i];
-            if (state[i] == LOC_UNCORRECTABLE) {
-                status[b] = 2;
-                uncorrectable = true;
-                bad++;
-                continue;
-            }
-            if (found[i].empty()) continue;  // (consistent after all)
-            status[b] = 1;
-            bad++;
-            if (counts) counts[b] = (uint32_t)found[i].size();
-            for (uint64_t q = 0; q < found[i].size() && q < cap; q++) blocks[b * cap + q] = found[i][q];
-        }
-        *inconsistent = bad;
-        return uncorrectable ? FASTECC_E_UNCORRECTABLE : FASTECC_OK;
+        return report_located(list, state, found, count, status, blocks, cap, counts, inconsistent);
     });
 }
 
@@ -1450,31 +1681,41 @@ int fastecc_correct_batch_set(fastecc_ctx* c, void* data, void* parity, uint64_t
                               uint64_t* inconsistent)
 {
     if (!status || !inconsistent || !pattern_of) return FASTECC_E_INVAL;
-    int rc = batch_args(c, data, parity, count);
+    const int rc = batch_args(c, data, parity, count);
     if (rc != FASTECC_OK) return rc;
     return on_device(c, [&]() -> int {
-        std::vector<uint8_t> flag;
-        {
-            CallLock lk(c->mu);
-            int r = set_args(c, pattern_of, count);
-            if (r != FASTECC_OK) return r;
-            if ((r = verify_batch_set_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, pattern_of, seed, (hipStream_t)stream, flag)) != FASTECC_OK) return r;
-        }
-        // fastecc_correct under the stripe's own pattern on each inconsistent stripe, one after the other (it takes the lock itself)
-        const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
-        std::vector<uint8_t> st(count, 0);
-        std::vector<uint32_t> found;
+        CorrectBatchSet cb{c, data, parity, count, pattern_of, stream, seed};
+        return cb.run(status, inconsistent);
+    });
+}
+
+int fastecc_locate_errors_batch_set(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const uint32_t* pattern_of, void* stream, uint64_t seed,
+                                    uint8_t* status, uint64_t* blocks, uint64_t cap, uint32_t* counts, uint64_t* inconsistent)
+{
+    if (!status || !inconsistent || !pattern_of || (cap && (!blocks || !counts))) return FASTECC_E_INVAL;
+    const int rc = batch_args(c, data, parity, count);
+    if (rc != FASTECC_OK) return rc;
+    if (cap && count > UINT64_MAX / 8 / cap) return FASTECC_E_INVAL;
+    return on_device(c, [&]() -> int {
+        CallLock lk(c->mu);
+        hipStream_t st = (hipStream_t)stream;
+        const uint32_t *d = (const uint32_t*)data, *p = (const uint32_t*)parity;
+        int r = set_args(c, pattern_of, count);
+        if (r != FASTECC_OK) return r;
+        std::vector<uint64_t> list;
+        std::vector<uint8_t> state;
+        std::vector<std::vector<uint32_t>> found;
         bool uncorrectable = false;
-        uint64_t bad = 0;
-        for (uint64_t b = 0; b < count; b++) {
-            if (!flag[b]) continue;
-            bad++;
-            int r = correct_stripe(c, (char*)data + b * data_bytes, (char*)parity + b * parity_bytes, stream, seed, true, pattern_of[b], found);
-            if ((r = record_status(r, !found.empty(), &st[b], &uncorrectable)) != FASTECC_OK) return r;
+        if ((r = flagged_set(c, d, p, count, pattern_of, seed, st, list)) != FASTECC_OK) return r;
+        if ((r = locate_list_set(c, d, p, list, pattern_of, seed, st, state, found)) != FASTECC_OK) return r;
+        const uint64_t data_words = c->K * c->S, parity_words = c->Mu * c->S;
+        for (size_t i = 0; i < list.size(); i++) {
+            if (state[i] != LOC_FALLBACK) continue;
+            // a word >= p in a present block, no syndrome left or more than the batched pass gathers: the single-stripe code under the stripe's pattern
+            r = locate(c, c->scrub, set_view(c->scrub, pattern_of[list[i]]), d + list[i] * data_words, p + list[i] * parity_words, seed, st, found[i], false);
+            if ((r = record_status(r, !found[i].empty(), &state[i], &uncorrectable)) != FASTECC_OK) return r;  // (the status codes 1 and 2 are LOC_FOUND and LOC_UNCORRECTABLE)
         }
-        std::copy(st.begin(), st.end(), status);
-        *inconsistent = bad;
-        return uncorrectable ? FASTECC_E_UNCORRECTABLE : FASTECC_OK;
+        return report_located(list, state, found, count, status, blocks, cap, counts, inconsistent);
     });
 }
 

@@ -1,6 +1,6 @@
 // scrub_device.hpp — device code of the scrub path, included by scrub.hip only (its head comment says what every pass computes): the block
-// fingerprint and its three kernels, the locator tables, the syndrome checks and gathers, the root searches.  The kernels are tuned one by one
-// (79/80/82 VGPRs, five or six waves per SIMD: DESIGN.md sections 14, 17 and 19) and are not merged or re-templated.
+// fingerprint and its four kernels, the locator tables, the syndrome checks and gathers, the root searches.  The kernels are tuned one by one
+// (79/80/82 VGPRs, five or six waves per SIMD: DESIGN.md sections 14, 17, 19 and 27) and are not merged or re-templated.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -242,6 +242,54 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void f
     }
 }
 
+// Batched location under a pattern per stripe: fingerprint_set_kernel's body with the LIST form's addressing.  The chunk is B
+// entries of a list of stripes of the pool: list[entry] names the stripe whose blocks are read and whose pattern q = pattern_of[stripe] holds (both
+// wave-uniform: scalar loads, q through readfirstlane; pattern_of is the whole call's array, indexed by stripe), while the fingerprint columns, flag[]
+// and big[] are addressed by the position in the chunk (the host passes the three from the chunk's first entry on).  The host lists only stripes with
+// a pattern (q < P).  A present block stores F * lset[q * NC + u] and an absent one its zero entry, so every (entry, block) of the chunk is stored by
+// every launch and nothing an earlier call left in F is read; big[entry] = 1 when a present block held a word >= p (flag[entry] as well).
+// Five waves per SIMD with the grid to match, as for the list kernel: the vector form needs more than 80 VGPRs.
+template <bool VEC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void fingerprint_set_list_kernel(const uint32_t* __restrict__ data, const uint32_t* __restrict__ parity, uint32_t k_blocks,
+                                                                   uint32_t n_blocks, uint32_t S, uint64_t B, const uint2* __restrict__ wt,
+                                                                   const uint32_t* __restrict__ pattern_of, const uint32_t* __restrict__ pos_set,
+                                                                   const uint32_t* __restrict__ lset, uint32_t NC, uint32_t* __restrict__ F, uint64_t row,
+                                                                   uint8_t* __restrict__ flag, const uint64_t* __restrict__ list, uint8_t* __restrict__ big)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint64_t waves = (gridDim.x * blockDim.x) >> 6;
+    const uint64_t total = B * n_blocks;
+    const uint64_t m_blocks = n_blocks - k_blocks;
+    for (uint64_t g = wave; g < total; g += waves) {
+        const uint64_t bl = g / n_blocks;
+        const uint32_t j = (uint32_t)(g - bl * n_blocks);
+        const uint32_t entry = __builtin_amdgcn_readfirstlane((uint32_t)bl);  // (a chunk has at most 2^16 entries)
+        const uint64_t b = list[entry];
+        const uint32_t q = __builtin_amdgcn_readfirstlane(pattern_of[b]);
+        const uint32_t u = pos_set[q * n_blocks + j];
+        if (u & ABSENT) {
+            if (lane == 0) *reinterpret_cast<uint4*>(F + (uint64_t)(u & ~ABSENT) * row + bl * RW) = make_uint4(0, 0, 0, 0);
+            continue;
+        }
+        const uint32_t* blk = j < k_blocks ? data + (b * k_blocks + j) * S : parity + (b * m_blocks + (j - k_blocks)) * S;
+        uint32_t fp[R];
+        bool any_big;
+        block_fingerprint<VEC>(blk, S, wt, lane, fp, any_big);
+        if (lane == 0) {
+            const uint32_t l = lset[q * NC + u];
+            uint32_t* f = F + (uint64_t)u * row + bl * RW;
+            f[0] = gf::mul(fp[0], l);
+            f[1] = gf::mul(fp[1], l);
+            f[2] = gf::mul(fp[2], l);
+            if (any_big) {
+                flag[entry] = 1;
+                big[entry] = 1;
+            }
+        }
+    }
+}
+
 // out[u] = base[u] (or 1) * prod_i (w^u - roots[i]); WITH_F: G[u][c] = F[u][c] * that instead (all plain representatives)
 template <bool WITH_F>
 __global__ __launch_bounds__(256) void locator_kernel(const uint32_t* __restrict__ base, const uint32_t* __restrict__ roots, uint32_t nroots,
@@ -334,6 +382,27 @@ __global__ __launch_bounds__(256) void syndrome_gather_kernel(const uint32_t* __
     o[0] = g.x;
     o[avail] = g.y;
     o[2 * (uint64_t)avail] = g.z;
+}
+
+// Batched location under a pattern per stripe: syndrome_set_kernel's item mapping from m_lo = the set's smallest bound on, over the
+// chunk's B list entries.  Entry b (stripe list[b], pattern q = pattern_of[list[b]]) keeps the coefficients from its own bound mlo_set[q] on:
+// syn[(b * 3 + c) * stride + (m - mlo_set[q])]; the ones below it are legitimately non-zero and are not stored, and an entry with more than `stride`
+// coefficients (the host lists none) stores only the first `stride`.
+__global__ __launch_bounds__(256) void syndrome_gather_set_kernel(const uint32_t* __restrict__ G, int lgc, uint32_t NC, uint32_t m_lo, uint64_t row, uint32_t B,
+                                                                  const uint64_t* __restrict__ list, const uint32_t* __restrict__ pattern_of,
+                                                                  const uint32_t* __restrict__ mlo_set, uint32_t stride, uint32_t* __restrict__ syn)
+{
+    const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= (NC - m_lo) * B) return;
+    const uint32_t b = item % B, m = m_lo + item / B;
+    const uint32_t lo = mlo_set[pattern_of[list[b]]];
+    if (m < lo || m - lo >= stride) return;
+    const uint32_t slot = __brev(m) >> (32 - lgc);
+    const uint4 g = *reinterpret_cast<const uint4*>(G + (uint64_t)slot * row + (uint64_t)b * RW);
+    uint32_t* o = syn + (uint64_t)b * R * stride + (m - lo);
+    o[0] = g.x;
+    o[stride] = g.y;
+    o[2 * (uint64_t)stride] = g.z;
 }
 
 // Batched location: thread (e, u) evaluates the locator of entry e — lambda[e * stride + 0 .. L[e]] — at w^u; a root is appended to entry e's own list

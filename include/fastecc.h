@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 390 /* 0.3.9: fastecc_encode_pool: the parity of a pool of stripes, any GF(0xFFF00001) code, option "encode_pool_kernel" */
+#define FASTECC_VERSION 400 /* 0.4.0: fastecc_locate_errors_batch_set; fastecc_correct_batch_set honours "correct_batch_mode" (grouped repair through a private pattern set) */
 
 enum {
     FASTECC_OK = 0,
@@ -584,16 +584,43 @@ int fastecc_locate_errors_batch(fastecc_ctx *ctx, const void *data, const void *
  *       rebuild located and absent blocks in one fastecc_decode_prepare + fastecc_repair, closing verify over all blocks with the derived seed.
  *       status[b]: 0 = consistent or skipped, untouched, absent blocks included; 1 = corrected, the whole codeword is back; 2 = uncorrectable,
  *       untouched.  *inconsistent = the number of stripes the verify pass flagged.  Returns FASTECC_E_UNCORRECTABLE if any status is 2, with
- *       status filled either way.  REPLACES the context's single prepared decode pattern, as fastecc_correct does; the decode pattern SET is left
- *       alone.  Inconsistent stripes are corrected one after the other ("correct_batch_mode" does not apply).  Workflow: this call makes the bad
- *       stripes whole, then fastecc_repair_batch_set with the same flag arrays and pattern_of brings back the absent blocks of all the others.
- * Profile scopes: "fingerprint_set" (its bytes: the blocks actually read), "scrub_transform_batch", "scrub_syndromes_set".
+ *       status filled either way.  REPLACES the context's single prepared decode pattern; which pattern is left behind is unspecified.  The decode
+ *       pattern SET, the single scrub pattern and the scrub set are left alone.  Option "correct_batch_mode" (at call time) chooses how, with the
+ *       meaning it has for fastecc_correct_batch: 2 = the inconsistent stripes one after the other, each as above; 1 = the grouped path (DESIGN.md
+ *       section 27): one batched location pass over the inconsistent stripes (as fastecc_locate_errors_batch_set), the located stripes grouped by
+ *       their lost set (located blocks and the blocks absent under the stripe's own pattern), ONE pattern set private to the call built from the
+ *       distinct lost sets and one repair launch per size class over all their stripes (fastecc_repair_batch_set's kernel and its choice, option
+ *       "decode_batch_kernel" included; lost sets of more than 16 blocks and distinct sets beyond the 4096th of a call go one
+ *       fastecc_decode_prepare and one list-form repair per set), and one closing verify over all repaired stripes with fastecc_correct's second
+ *       seed; 0 (default) = the grouped path when at least two inconsistent stripes qualify for it, else the loop.  Status bytes, *inconsistent,
+ *       the return code and every byte of the pool are the same in every mode.  Uncorrectable and consistent stripes are never written.
+ *       Workflow: this call makes the bad stripes whole, then fastecc_repair_batch_set with the same flag arrays and pattern_of brings back the
+ *       absent blocks of all the others.
+ *   fastecc_locate_errors_batch_set : fastecc_locate_errors_batch with a pattern per stripe; the outputs are those of that call (status 0 / 1 / 2,
+ *       counts, blocks[b*cap + i], *inconsistent), written only at the end; FASTECC_E_UNCORRECTABLE if any status is 2, with every output filled.
+ *       pattern_of[b] < n_patterns: the answer of stripe b is, bit for bit, what fastecc_scrub_erasures(that pattern) followed by
+ *       fastecc_locate_errors with the same seed gives for that stripe alone; absent blocks are never read and never listed.
+ *       FASTECC_PATTERN_NONE: the stripe is not read, has status 0 and is not counted.  Reads only.  Refusals, before any device work and with
+ *       nothing written: those of fastecc_verify_batch_set (no set prepared, an entry >= n_patterns that is not FASTECC_PATTERN_NONE, a null
+ *       pattern_of), and fastecc_locate_errors_batch's on null outputs and on cap.  FASTECC_E_UNSUPPORTED for the contexts
+ *       fastecc_scrub_erasures_set refuses.
+ * Batched location under the set: the list pass of fastecc_locate_errors_batch with the erasure view per list entry.  Each
+ * entry follows fastecc_locate_errors' decisions under its own pattern (n - k - w syndromes, w that pattern's absent blocks); a root at a block
+ * absent under the stripe's pattern refuses the stripe.  Through the single-stripe code under the stripe's pattern instead, with the same answers: a
+ * stripe in which a present block holds a word >= p, one whose pattern leaves more than 512 syndromes, one whose pattern leaves none.  Stripes of
+ * all kinds may share a call and a chunk.
+ * Profile scopes: "fingerprint_set" (its bytes: the blocks actually read), "scrub_transform_batch", "scrub_syndromes_set"; of the batched location
+ * and the grouped repair: "fingerprint_set_list" (bytes as above), "scrub_syndromes_gather_set", and the reused "scrub_root_search_batch" and
+ * "direct_pass_set" (the wide lost sets: "direct_pass_list" / "direct_pass").
  */
 int fastecc_scrub_erasures_set(fastecc_ctx *ctx, const uint8_t *data_present, const uint8_t *parity_present, uint64_t n_patterns);
 int fastecc_verify_batch_set(fastecc_ctx *ctx, const void *data, const void *parity, uint64_t count, const uint32_t *pattern_of,
                              void *stream, uint64_t seed, uint8_t *consistent, uint64_t *inconsistent);
 int fastecc_correct_batch_set(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, const uint32_t *pattern_of,
                               void *stream, uint64_t seed, uint8_t *status, uint64_t *inconsistent);
+int fastecc_locate_errors_batch_set(fastecc_ctx *ctx, const void *data, const void *parity, uint64_t count, const uint32_t *pattern_of,
+                                    void *stream, uint64_t seed, uint8_t *status, uint64_t *blocks, uint64_t cap, uint32_t *counts,
+                                    uint64_t *inconsistent);
 /*
  * The fingerprints themselves (tests only, like fastecc_gf_binary: this call is no part of the scrub contract and may change).  It runs the
  * fingerprint pass of the scrub calls above — the same kernels through the same host paths and launch configurations — stops before the
@@ -771,7 +798,7 @@ const char *fastecc_plan_string(fastecc_ctx *ctx);
  *                  and it fills at least 1024 waves (the matrix-core kernel from n - k = 4 on where it can run: measured 1.1 x the VALU kernel at (20,16), 1.8 x at (48,32)), else stripe by stripe.  Same bits in every mode;
  *   "scrub_batch_chunk" = 0 .. INT_MAX (default 0 = the context's chunk capacity; at call time): the most stripes per chunk of
  *                  fastecc_verify_batch / _correct_batch / _locate_errors_batch.  Same answers either way;
- *   "correct_batch_mode" = 0 / 1 / 2 (default 0 = choose; at call time): how fastecc_correct_batch corrects the inconsistent stripes — 1 = batched
+ *   "correct_batch_mode" = 0 / 1 / 2 (default 0 = choose; at call time): how fastecc_correct_batch and fastecc_correct_batch_set correct the inconsistent stripes — 1 = batched
  *                  location and one repair per lost-block pattern for every stripe that qualifies, 2 = fastecc_correct stripe by stripe, 0 = 1 when
  *                  at least two inconsistent stripes qualify, else 2.  Same status and same bytes either way;
  *   "fuse_radix" = 0 / 1 (default 1; mixed-radix contexts): the odd-radix level fused into the outer tile passes, or as its own passes;
