@@ -104,6 +104,9 @@ def lib():
     L.fastecc_decode_prepare_set.argtypes, L.fastecc_decode_prepare_set.restype = [vp, u8p, u8p, u64], i32
     L.fastecc_decode_batch_set.argtypes, L.fastecc_decode_batch_set.restype = [vp, vp, vp, u64, ctypes.POINTER(u32), vp], i32
     L.fastecc_repair_batch_set.argtypes, L.fastecc_repair_batch_set.restype = [vp, vp, vp, u64, ctypes.POINTER(u32), vp], i32
+    L.fastecc_read_batch_set.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u32), ctypes.POINTER(u64), u64, u64, u64, vp, vp]
+    L.fastecc_read_batch_set.restype = i32
+    L.fastecc_read_batch.argtypes, L.fastecc_read_batch.restype = [vp, vp, vp, u64, ctypes.POINTER(u64), u64, u64, u64, vp, vp], i32
     L.fastecc_scrub_erasures.argtypes, L.fastecc_scrub_erasures.restype = [vp, u8p, u8p], i32
     L.fastecc_verify.argtypes, L.fastecc_verify.restype = [vp, vp, vp, i32, vp, u64, ctypes.POINTER(i32)], i32
     for name in ("locate_errors", "correct"):
@@ -396,6 +399,52 @@ class Encoder:
         _check(lib().fastecc_repair_batch_set(self._h, _addr(data), _addr(parity), count, po, stream or None), "fastecc_repair_batch_set")
         del keep
         return data, parity
+
+    @classmethod
+    def _read_list(cls, reads):
+        """(entries, object to keep alive, uint64 pointer) of the pool block indices of a read call"""
+        import numpy as np
+        if isinstance(reads, np.ndarray) and reads.dtype == np.uint64 and reads.ndim == 1 and reads.flags["C_CONTIGUOUS"]:
+            return len(reads), reads, reads.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))  # goes through as it is
+        idx = [int(b) for b in reads]
+        if any(b < 0 or b >= 1 << 64 for b in idx):
+            raise ValueError("a pool block index is a uint64")
+        n, arr = cls._block_list(idx)
+        return n, arr, arr
+
+    def _read_window(self, col0, width):
+        if isinstance(col0, bool) or not isinstance(col0, int) or (width is not None and (isinstance(width, bool) or not isinstance(width, int))):
+            raise TypeError("col0 and width are ints (words)")
+        if col0 < 0 or col0 >= 1 << 64:
+            raise ValueError("col0 must be in [0, 2^64)")
+        if width is None:
+            width = self.words_per_block - col0  # the whole block from col0 on
+        if width < 1 or width >= 1 << 64:
+            raise ValueError("the window must hold at least one word of the block")
+        return col0, width
+
+    def read_batch_set(self, data, parity, count, pattern_of, reads, out, col0=0, width=None, stream=0):
+        """Degraded reads of a pool of `count` stripes (the layout of decode_batch) with stripe b under pattern pattern_of[b] of the
+        decode_prepare_set set (PATTERN_NONE: every block present): row u of `out` (width words each, device memory) receives the words
+        [col0, col0 + width) of pool block reads[u] = b * k + i — a copy where the block is present, else what decode would rebuild.  The pool
+        is not written.  width=None: the whole block from col0 on.  Any order, duplicates allowed."""
+        count = self._batch_count(count)
+        keep, po = self._pattern_list(pattern_of, count)
+        col0, width = self._read_window(col0, width)
+        n, keep_r, arr = self._read_list(reads)
+        _check(lib().fastecc_read_batch_set(self._h, _addr(data), _addr(parity), count, po, arr, n, col0, width, _addr(out), stream or None),
+               "fastecc_read_batch_set")
+        del keep, keep_r
+        return out
+
+    def read_batch(self, data, parity, count, reads, out, col0=0, width=None, stream=0):
+        """read_batch_set with every stripe under the single decode_prepare pattern (direct-path patterns only)."""
+        count = self._batch_count(count)
+        col0, width = self._read_window(col0, width)
+        n, keep_r, arr = self._read_list(reads)
+        _check(lib().fastecc_read_batch(self._h, _addr(data), _addr(parity), count, arr, n, col0, width, _addr(out), stream or None), "fastecc_read_batch")
+        del keep_r
+        return out
 
     def scrub_erasures(self, data_present=None, parity_present=None):
         """Name the blocks that are known to be absent (a device is down) for verify, locate_errors, correct and their batched forms:

@@ -138,6 +138,8 @@ struct DecodeState {
     int sub_lost_data = 0, sub_lost_parity = 0;
     bool sub = false;
     int direct_kernel = 0;                  // 0 choose, 1 VALU, 2 MFMA (option "direct_kernel")
+    DeviceBuf<DirectSetPass> read_desc;     // fastecc_read_batch: the descriptor of the pass that rebuilds the lost data, valid for pattern `read_desc_of` (lazy)
+    uint64_t read_desc_of = ~0ull;
     uint64_t positions = 0;                 // code length on the roots of unity: k << log2(n / k) rounded up to powers of two
     bool mixed = false;                     // mixed-radix code: `recovered` is the whole work stripe (all positions), transformed in place
     bool standard = false;                  // the reference's (2k,k) layout: position u = data u/2 or parity u/2, every block in memory
@@ -154,6 +156,7 @@ struct PatternSet {
     std::vector<uint8_t> kind;          // ... its pass
     std::vector<uint8_t> cls;           // ... log2 of that pass's pad (1, 2, 4, 8, 16): the class a launch is templated on
     std::vector<uint32_t> rows;         // ... the rows it reads
+    std::vector<std::vector<uint32_t>> lost_data;  // ... its lost data blocks, in the order of the pass's outputs (fastecc_read_batch_set)
     DeviceBuf<DirectSetPass> d_passes;  // device: the descriptor table, entry q = pattern q's pass
     // one call's entries, sorted by class (list.dev is an internal buffer: ordered between streams by the context's buf_event).  Outlives the set.
     StagedList<DirectSetEntry> list;
@@ -1808,6 +1811,7 @@ int fill_pattern_set(fastecc_ctx* c, const std::vector<LostLists>& lists, Patter
     fresh->kind.assign(P, PatternSet::NOTHING);
     fresh->cls.assign(P, 0);
     fresh->rows.assign(P, 0);
+    fresh->lost_data.assign(P, {});
     std::vector<DirectSetPass> desc(P, DirectSetPass{});
     Prepare geometry(c, nullptr, nullptr);
     PhaseTimer quiet;  // one line per set, not two per pattern
@@ -1821,6 +1825,7 @@ int fill_pattern_set(fastecc_ctx* c, const std::vector<LostLists>& lists, Patter
         if ((rc = direct_set_describe(fresh->pass(q), &desc[q])) != FASTECC_OK) return rc;
         while ((1u << fresh->cls[q]) < desc[q].cstride) fresh->cls[q]++;
         fresh->rows[q] = desc[q].rows;
+        fresh->lost_data[q] = l.R;
     }
     RC_TRY(fresh->d_passes.alloc(P));
     HIP_TRY(hipMemcpy(fresh->d_passes, desc.data(), P * sizeof(DirectSetPass), hipMemcpyHostToDevice));
@@ -1966,6 +1971,119 @@ int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
     return run_pattern_set(c, s, data, parity, x.block, count, [](uint64_t b) { return b; }, [&](uint64_t b) { return pattern_of[b]; }, stream, repair);
 }
 
+// ---- fastecc_read_batch / _read_batch_set: degraded reads ----
+// The requested data blocks reads[0 .. n_reads) of a pool, words [col0, col0 + width) of each, into row u of `out`; the pool is only read.
+// set_form: stripe b under pattern pattern_of[b] of the prepared set; else every stripe under the single prepared pattern (direct path only).
+// The argument checks, the pool's extent, then every request on the host — (stripe, pattern, present or the block's output index in the pass that
+// fastecc_decode_batch[_set] takes for the lost data) — and only when all of them are valid ONE launch of direct_read_kernel over the staged list.
+int read_batch_impl(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const uint32_t* pattern_of, bool set_form, const uint64_t* reads,
+                    uint64_t n_reads, uint64_t col0, uint64_t width, void* out, void* stream)
+{
+    if (!c || count == 0 || width == 0 || (set_form && !pattern_of)) return FASTECC_E_INVAL;
+    if (n_reads > 0 && (!data || !parity || !reads || !out)) return FASTECC_E_INVAL;
+    if (((uintptr_t)data | (uintptr_t)parity | (uintptr_t)out) & 3u) return FASTECC_E_INVAL;
+    if (c->sharded) return FASTECC_E_UNSUPPORTED;
+    CallLock lk(c->mu);
+    if (c->field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
+    if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;  // stripes of a pool are contiguous
+    const uint64_t S = c->S, K = c->K;
+    if (col0 > S || width > S - col0) return FASTECC_E_INVAL;
+    PoolExtent x;
+    RC_TRY(pool_extent(c, data, parity, count, &x));
+    if (n_reads > UINT64_MAX / (width * 4u)) return FASTECC_E_INVAL;
+    const uint64_t out_bytes = n_reads * width * 4u;
+    const uint64_t o0 = (uint64_t)(uintptr_t)out, d0 = (uint64_t)(uintptr_t)data, p0 = (uint64_t)(uintptr_t)parity;
+    if (o0 > UINT64_MAX - out_bytes) return FASTECC_E_INVAL;
+    auto overlaps = [&](uint64_t base, uint64_t bytes) { return o0 < base + bytes && base < o0 + out_bytes; };
+    if (n_reads > 0 && (overlaps(d0, count * x.data_bytes) || overlaps(p0, count * x.parity_bytes))) return FASTECC_E_INVAL;
+    // the tables: the set's descriptor table, or the single pattern's pass for the lost data
+    PatternSet* s = nullptr;
+    DecodeState* d = nullptr;
+    DirectPass* single = nullptr;  // (null: the single pattern lost no data block — every request is a copy)
+    if (set_form) {
+        if (!(s = c->pattern_set)) return FASTECC_E_INVAL;  // fastecc_decode_prepare_set first
+    } else {
+        d = c->decoder;
+        if (!d || !d->ready) return FASTECC_E_INVAL;  // fastecc_decode_prepare first
+        if (!d->sub) return FASTECC_E_UNSUPPORTED;    // a pattern of the transform path
+        if (d->sub_lost_data > 0) {
+            single = d->sub_both && d->sub_only_both ? d->direct.both.get() : d->direct.data.get();
+            if (!single || d->host_lost_data.size() != (size_t)d->sub_lost_data) return FASTECC_E_DEVICE;
+        }
+    }
+    if (n_reads == 0) return FASTECC_OK;
+    const uint64_t P = s ? s->tables.size() : 0, blocks = count * K;  // (count * K * block fits 64 bits: pool_extent)
+    const uint32_t single_rows = single ? (uint32_t)direct_pass_rows(single) : 0;
+    const bool small = blocks <= 0xFFFFFFFFull;
+    // request u -> its entry and the rows its wave reads
+    auto translate = [&](uint64_t u, DirectReadEntry* ent, uint64_t* rows_read) -> int {
+        const uint64_t idx = reads[u];
+        if (idx >= blocks) return FASTECC_E_INVAL;
+        const uint64_t b = small ? (uint64_t)((uint32_t)idx / (uint32_t)K) : idx / K;  // (the common case: a 32-bit division)
+        const uint32_t i = (uint32_t)(idx - b * K);
+        *ent = DirectReadEntry{b, 0, i, DIRECT_READ_PRESENT, 0};
+        *rows_read = 1;
+        if (set_form) {
+            const uint32_t q = pattern_of[b];
+            if (q == FASTECC_PATTERN_NONE) return FASTECC_OK;
+            if (q >= P) return FASTECC_E_INVAL;
+            if (s->kind[q] != PatternSet::DATA && s->kind[q] != PatternSet::BOTH) return FASTECC_OK;
+            const std::vector<uint32_t>& R = s->lost_data[q];
+            for (size_t j = 0; j < R.size(); j++)
+                if (R[j] == i) {
+                    ent->pass = q;
+                    ent->out = (uint32_t)j;
+                    *rows_read = s->rows[q];
+                    break;
+                }
+            return FASTECC_OK;
+        }
+        if (single) {
+            const std::vector<uint32_t>& R = d->host_lost_data;  // increasing (Prepare::direct)
+            const auto it = std::lower_bound(R.begin(), R.end(), i);
+            if (it != R.end() && *it == i) {
+                ent->out = (uint32_t)(it - R.begin());
+                *rows_read = single_rows;
+            }
+        }
+        return FASTECC_OK;
+    };
+    const uint32_t* ddata = (const uint32_t*)data;
+    const uint32_t* dparity = (const uint32_t*)parity;
+    if (direct_read_waves_per_entry(data, parity, out, S, col0, width) > (1ull << 24)) return FASTECC_E_UNSUPPORTED;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    // ONE pass over the requests, straight into the pinned side of the list (reserve allocates, and waits for the previous call's copy; it enqueues
+    // nothing): a request that is refused leaves a half-written list that no device work ever sees
+    StagedList<DirectReadEntry>& list = c->read_list;
+    RC_TRY(list.reserve(n_reads, [&] { return wait_idle(c); }));  // (growing waits for the kernels that read the device list)
+    uint64_t rows_total = 0;
+    for (uint64_t u = 0; u < n_reads; u++) {
+        uint64_t rows_read;
+        RC_TRY(translate(u, &list.host[u], &rows_read));
+        rows_total += rows_read + 1;
+    }
+    const DirectSetPass* passes = s ? s->d_passes.get() : nullptr;
+    if (!set_form) {
+        if (single && d->read_desc_of != d->pattern_serial) {
+            // (no read that used the previous descriptor is in flight: fastecc_decode_prepare waited for them before it rebuilt the tables)
+            DirectSetPass desc;
+            RC_TRY(direct_read_describe(single, &desc));
+            RC_TRY(d->read_desc.alloc(1));
+            HIP_TRY(hipMemcpy(d->read_desc, &desc, sizeof(desc), hipMemcpyHostToDevice));
+            d->read_desc_of = d->pattern_serial;
+        }
+        RC_TRY(d->read_desc.alloc(1));  // (a pattern that lost no data: the table is never read, but the launch takes a pointer)
+        passes = d->read_desc.get();
+    }
+    return with_internal_buffers(c, st, [&]() -> int {  // the tables and the list are internal buffers
+        RC_TRY(list.publish(n_reads, st));
+        ProfScope ps(c, st, set_form ? "direct_read_set" : "direct_read", rows_total * width * 4u);
+        return direct_run_read(passes, list.dev, n_reads, ddata, dparity, (uint32_t*)out, S, col0, width, K * S, c->Mu * S, st);
+    });
+}
+
 }  // namespace
 
 // The scrubber's grouped repair (drivers.hpp): a pattern set of the lost sets, private to the call — fill_pattern_set, run_pattern_set
@@ -2058,6 +2176,18 @@ int fastecc_decode_batch_set(fastecc_ctx* c, void* data, const void* parity, uin
 int fastecc_repair_batch_set(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, void* stream)
 {
     return guarded([&]() -> int { return decode_batch_set_impl(c, data, parity, count, pattern_of, stream, true); });
+}
+
+int fastecc_read_batch_set(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const uint32_t* pattern_of, const uint64_t* reads, uint64_t n_reads,
+                           uint64_t col0_words, uint64_t width_words, void* out, void* stream)
+{
+    return guarded([&]() -> int { return read_batch_impl(c, data, parity, count, pattern_of, true, reads, n_reads, col0_words, width_words, out, stream); });
+}
+
+int fastecc_read_batch(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const uint64_t* reads, uint64_t n_reads, uint64_t col0_words,
+                       uint64_t width_words, void* out, void* stream)
+{
+    return guarded([&]() -> int { return read_batch_impl(c, data, parity, count, nullptr, false, reads, n_reads, col0_words, width_words, out, stream); });
 }
 
 }  // extern "C"

@@ -1071,6 +1071,141 @@ int direct_run_set(int eb, const DirectSetPass* passes, const DirectSetEntry* en
 }
 
 // ------------------------------------------------------------------------------------------------
+// DEGRADED READS (fastecc_read_batch / _read_batch_set): a list of requests, each one data block of a pool over the word columns
+// [col0, col0 + width), into row `entry index` of a compact buffer.  The pool is only read.  As in direct_set_kernel an entry owns
+// ceil(width / (64 V)) WHOLE waves, a wave finds its entry from its index in the launch (readfirstlane) and loads the entry and its pass
+// descriptor with scalar loads; lanes whose column is >= width read nothing and store nothing.
+//   present block: the window of that one row, copied as stored (words >= p included);
+//   lost block:    output j of the pass — the ONE weight coef[u][j] per row u (a scalar load), U rows in flight, 96-bit accumulation, one
+//                  reduction, a canonical store.  The weight's address follows coef_index with the row stride read from the descriptor
+//                  (cstride = min(pad, 16)), so one launch serves every pad class of a set and the sweep-major tables of wider passes.
+// One output per row read: the pass is bound by the row stream (rows x width words in for width words out); the matrix cores have nothing to
+// add.  A pass of thousands of rows (k >= 4096, the single-pattern form) is walked by one wave per 64 V columns: correct, not tuned —
+// fastecc_decode remains the tool for single large stripes.
+// ------------------------------------------------------------------------------------------------
+struct ReadArgs {
+    const uint32_t* data;     // stripe b's data rows at data + b * data_stride
+    const uint32_t* parity;   // ... its parity rows at parity + b * parity_stride
+    uint32_t* out;            // row (row_base + e) of `width` words for entry e of the launch
+    uint64_t data_stride, parity_stride;
+    const DirectReadEntry* entries;  // the launch's first entry
+    const DirectSetPass* passes;     // the descriptor table
+    uint64_t row_base;               // output row of the launch's first entry
+    uint32_t waves;                  // entries of the launch * waves_per_entry (at most SET_LAUNCH_WAVES)
+    uint32_t waves_per_entry;
+    uint32_t S, col0, width;
+};
+using const_read_entry_ptr = const DirectReadEntry __attribute__((address_space(4)))*;
+
+template <int V>
+__global__ __launch_bounds__(256) void direct_read_kernel(const ReadArgs a)
+{
+    constexpr int U = 8;  // rows in flight: U weights in SGPRs, U * V words in VGPRs
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (w >= a.waves) return;
+    const uint32_t e = w / a.waves_per_entry, cc = w - e * a.waves_per_entry;  // (wave-uniform)
+    const const_read_entry_ptr ent = (const_read_entry_ptr)(reinterpret_cast<uintptr_t>(a.entries)) + e;
+    const uint64_t b = ent->stripe;
+    const uint32_t j = ent->out;
+    const uint32_t c = (cc * 64u + lane) * V;  // (32 bits: cc < waves_per_entry <= 2^24 and V <= 4)
+    const bool live = c < a.width;             // (V divides width: a live lane's V words lie inside the window)
+    uint32_t* dst = a.out + (a.row_base + e) * a.width + c;
+    const uint32_t* dbase = a.data + b * a.data_stride + a.col0 + c;
+    if (j == DIRECT_READ_PRESENT) {  // wave-uniform
+        if (live) {
+            uint32_t x[V];
+            load_vec<V>(x, dbase + (size_t)ent->block * a.S);
+            store_vec<V>(dst, x);
+        }
+        return;
+    }
+    const const_set_pass_ptr d = (const_set_pass_ptr)(reinterpret_cast<uintptr_t>(a.passes)) + ent->pass;
+    const uint32_t rows = d->rows, data_rows = d->data_rows, cstride = d->cstride;
+    const_u32_ptr coef = as_constant(d->coef) + ((size_t)(j >> 4) * rows * cstride + (j & 15u));  // coef_index(u, j) = this + u * cstride
+    const_u32_ptr extra = as_constant(d->extra);
+    const uint64_t poff = b * a.parity_stride + a.col0 + c;  // (a lane's parity rows: a.parity + poff + row * S)
+    uint64_t lo[V];
+    uint32_t hi[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) lo[v] = 0, hi[v] = 0;
+    for (uint32_t ub = 0; ub < rows; ub += U) {
+        uint32_t wt[U], x[U][V];
+#pragma unroll
+        for (int i = 0; i < U; ++i) {
+            const uint32_t u = ub + i;
+            const bool in = u < rows;  // wave-uniform
+            wt[i] = 0;
+            if (in) wt[i] = coef[(size_t)u * cstride];
+#pragma unroll
+            for (int v = 0; v < V; ++v) x[i][v] = 0;
+            if (in && live) {  // a lost row holds anything: its weight is zero
+                const uint32_t* row = u < data_rows ? dbase + (size_t)u * a.S : a.parity + poff + (size_t)extra[u - data_rows] * a.S;
+                load_vec<V>(x[i], row);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < U; ++i)
+#pragma unroll
+            for (int v = 0; v < V; ++v) mac96(lo[v], hi[v], x[i][v], wt[i]);
+    }
+    if (live) {
+        uint32_t r[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) r[v] = reduce96(lo[v], hi[v]);
+        store_vec<V>(dst, r);
+    }
+}
+
+int direct_read_describe(const DirectPass* p, DirectSetPass* out)
+{
+    if (!p || !p->built) return FASTECC_E_INVAL;
+    *out = DirectSetPass{p->coef, p->lists, p->lists + DIRECT_CAP, p->rows, p->data_rows, (uint32_t)p->outputs, (uint32_t)std::min(p->pad, 16)};
+    return FASTECC_OK;
+}
+
+// Words per lane: set_vec's rule applied to everything a lane touches — the pool (rows S words apart), the output rows (width words apart)
+// and the window's first column — then halved while the window is shorter than a wave of such lanes
+static int read_vec(const void* data, const void* parity, const void* out, uint64_t S, uint64_t col0, uint64_t width)
+{
+    const uintptr_t align = (uintptr_t)data | (uintptr_t)parity | (uintptr_t)out;
+    int v = 4;
+    while (v > 1 && ((S % v) != 0 || (col0 % v) != 0 || (width % v) != 0 || (align & (4u * v - 1u)) != 0)) v >>= 1;
+    while (v > 1 && width < 64u * (uint64_t)v) v >>= 1;
+    return v;
+}
+
+uint64_t direct_read_waves_per_entry(const void* data, const void* parity, const void* out, uint64_t S, uint64_t col0, uint64_t width)
+{
+    const uint64_t v = (uint64_t)read_vec(data, parity, out, S, col0, width);
+    return (width + 64u * v - 1u) / (64u * v);
+}
+
+int direct_run_read(const DirectSetPass* passes, const DirectReadEntry* entries, uint64_t n_entries, const uint32_t* data, const uint32_t* parity, uint32_t* out,
+                    uint64_t S, uint64_t col0, uint64_t width, uint64_t data_stride, uint64_t parity_stride, hipStream_t st)
+{
+    if (!passes || !entries || !out || n_entries == 0 || S == 0 || S > 0xFFFFFFFFull || width == 0 || col0 > S || width > S - col0) return FASTECC_E_INVAL;
+    const int v = read_vec(data, parity, out, S, col0, width);
+    const uint64_t wpe = direct_read_waves_per_entry(data, parity, out, S, col0, width);
+    if (wpe > SET_LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (a window of more than 2^30 lane groups)
+    ReadArgs a{data, parity, out, data_stride, parity_stride, entries, passes, 0, 0, (uint32_t)wpe, (uint32_t)S, (uint32_t)col0, (uint32_t)width};
+    const uint64_t launch_entries = SET_LAUNCH_WAVES / wpe;
+    for (uint64_t e0 = 0; e0 < n_entries; e0 += launch_entries) {
+        a.entries = entries + e0;
+        a.row_base = e0;
+        a.waves = (uint32_t)(std::min(launch_entries, n_entries - e0) * wpe);
+        const dim3 grid((a.waves + 3u) / 4u);
+        switch (v) {
+            case 4: hipLaunchKernelGGL(direct_read_kernel<4>, grid, dim3(256), 0, st, a); break;
+            case 2: hipLaunchKernelGGL(direct_read_kernel<2>, grid, dim3(256), 0, st, a); break;
+            default: hipLaunchKernelGGL(direct_read_kernel<1>, grid, dim3(256), 0, st, a); break;
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return FASTECC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // ENCODING when a code has few parity blocks: with the data points x_i = w_N^i the parity block j = f(y_j) = sum_i data_i * L_i(y_j),
 // y_j = w_2N^(odd): y_j^N = -1, so coef[i][j] = -2 x_i / (N (y_j - x_i)) — one read of the data instead of the three trips of the
 // transform pipeline.  Exactly the polynomial evaluation the transform computes (RS.cpp:40-63), hence the same parity bits.

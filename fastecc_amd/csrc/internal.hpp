@@ -147,6 +147,26 @@ int direct_set_describe(const DirectPass* p, DirectSetPass* out);  // FASTECC_E_
 uint64_t direct_set_waves_per_entry(int eb, const void* data, const void* parity, uint64_t S);
 int direct_run_set(int eb, const DirectSetPass* passes, const DirectSetEntry* entries, uint64_t n_entries, const uint32_t* data, const uint32_t* parity,
                    uint32_t* data_out, uint32_t* parity_out, uint64_t S, uint64_t data_stride, uint64_t parity_stride, hipStream_t st);
+// Degraded reads (fastecc_read_batch / _read_batch_set; direct_read_kernel): a list of requests, each ONE data block of a pool over the word
+// columns [col0, col0 + width), stored to row `entry index` of a compact buffer `out` of `width` words per row.  The pool is only read.
+// A present block is a copy of its window; a lost one is output `out` of the pass passes[entry.pass] over its stripe's survivors — one column
+// of that pass's weight table.  The table's row stride comes from the descriptor, so one launch serves every pad class of a set and, with
+// direct_read_describe, the sweep-major tables of passes with more than 16 outputs.  Both arrays in DEVICE memory.
+constexpr uint32_t DIRECT_READ_PRESENT = 0xFFFFFFFFu;
+struct DirectReadEntry {
+    uint64_t stripe;  // of the pool
+    uint32_t pass;    // index into the descriptor table (not looked at for a present block)
+    uint32_t block;   // the data block of the stripe
+    uint32_t out;     // its output index in the pass, or DIRECT_READ_PRESENT
+    uint32_t reserved;
+};
+// direct_set_describe for a pass of any pad: cstride = min(pad, 16), the row stride inside a sweep of the table (coef_index).  For direct_run_read only.
+int direct_read_describe(const DirectPass* p, DirectSetPass* out);
+// waves one request takes (V chosen for the pointers' alignment, S, col0 and width); more than 2^24: direct_run_read refuses (FASTECC_E_UNSUPPORTED)
+uint64_t direct_read_waves_per_entry(const void* data, const void* parity, const void* out, uint64_t S, uint64_t col0, uint64_t width);
+// The caller guarantees col0 + width <= S, entry.block < data rows, entry.out < the pass's outputs and room for n_entries * width words at `out`.
+int direct_run_read(const DirectSetPass* passes, const DirectReadEntry* entries, uint64_t n_entries, const uint32_t* data, const uint32_t* parity, uint32_t* out,
+                    uint64_t S, uint64_t col0, uint64_t width, uint64_t data_stride, uint64_t parity_stride, hipStream_t st);
 bool direct_mfma_applies(const void* data, const void* parity, uint64_t words);
 // encoding straight from the Lagrange basis for codes with few parity blocks (n - k <= direct_encode_max())
 struct DirectEncode;

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 400 /* 0.4.0: fastecc_locate_errors_batch_set; fastecc_correct_batch_set honours "correct_batch_mode" (grouped repair through a private pattern set) */
+#define FASTECC_VERSION 410 /* 0.4.1: fastecc_read_batch, fastecc_read_batch_set (degraded reads: requested blocks of a pool into a compact buffer, the pool untouched) */
 
 enum {
     FASTECC_OK = 0,
@@ -443,6 +443,49 @@ int fastecc_repair_batch(fastecc_ctx *ctx, void *data, void *parity, uint64_t co
 int fastecc_decode_prepare_set(fastecc_ctx *ctx, const uint8_t *data_present, const uint8_t *parity_present, uint64_t n_patterns);
 int fastecc_decode_batch_set(fastecc_ctx *ctx, void *data, const void *parity, uint64_t count, const uint32_t *pattern_of, void *stream);
 int fastecc_repair_batch_set(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, const uint32_t *pattern_of, void *stream);
+
+/*
+ * Degraded reads: serving reads of a pool while a device is down.  The requested data blocks — often a sector-sized window of them — go to a
+ * compact output buffer; the pool itself is left exactly as it is, and healthy and degraded requests may be mixed in one list, in any order.
+ *   Layout: the pool layout of fastecc_decode_batch, DEVICE memory: stripe b's k data blocks at data + b*k*block_bytes, its n - k parity blocks
+ *       at parity + b*(n-k)*block_bytes, `count` stripes.  data and parity are read only: no byte of the pool is written by either call.
+ *   reads: a HOST array of n_reads pool block indices in the numbering of fastecc_update_batch's `writes`: reads[u] = b*k + i is data block i of
+ *       stripe b.  Any order, duplicates allowed; the array may be reused as soon as the call returns.
+ *   out: DEVICE memory of n_reads rows of width_words 32-bit words, row u for reads[u]: it receives the words [col0_words, col0_words +
+ *       width_words) of the requested block.  Nothing outside these n_reads * width_words words is written.
+ *   fastecc_read_batch_set : stripe b is taken under pattern pattern_of[b] of the set stored by fastecc_decode_prepare_set.  pattern_of is a HOST
+ *       array of `count` entries; only the entries of stripes that some read names are looked at.  FASTECC_PATTERN_NONE, or a pattern that loses
+ *       nothing, means every block of that stripe is present.
+ *   fastecc_read_batch : every stripe is taken under the single pattern of the last fastecc_decode_prepare, as by fastecc_decode_batch.  Only
+ *       patterns of the direct path are served (up to "decode_direct_max" lost blocks); a pattern prepared for the transform path returns
+ *       FASTECC_E_UNSUPPORTED.  A pattern with no lost data block is valid: every request is then a copy.
+ *   What a request returns:
+ *     - a block that is present under its stripe's pattern: a plain copy of the window out of the pool.  No other block of the stripe is read; the
+ *       words are copied as stored, words >= p included.
+ *     - a lost data block: the window of that block as reconstructed from the survivors — bit for bit the same words of what
+ *       fastecc_decode_prepare(that pattern) + fastecc_decode writes into that block for the stripe alone (exact arithmetic, canonical results).
+ *       The content of the stripe's lost blocks, data or parity, has no influence on the result: they may hold anything, words >= p included.
+ *   Every GF(0xFFF00001) code fastecc_repair_batch_set takes.  ONE launch per call whatever the number of patterns and size classes among the
+ *   requests: a request owns whole waves of 64 lanes over its window, and its wave walks the survivors with the one weight per row that the
+ *   requested block needs.  Requests of one stripe that ask for several lost blocks each re-read the survivors.  Patterns with many rows — up to
+ *   256 lost blocks, codes with k >= 4096 — are served by the same loop, one wave per 64 to 256 columns walking all rows: correct, not tuned;
+ *   fastecc_decode remains the tool for single large stripes.
+ *   Enqueued on `stream`; steady-state calls do not synchronise the device.  The request list travels through a pinned host buffer and a device
+ *   buffer owned by the context, with the rules of fastecc_update_batch / fastecc_repair_batch_set: they grow on demand (a growing call waits for
+ *   the previous one), an event guards reuse of the pinned buffer, and the calls cannot be captured into a hipGraph.  fastecc_decode_prepare and
+ *   fastecc_decode_prepare_set wait for reads still in flight before they replace tables.  Neither call changes the prepared pattern, the set,
+ *   any scrub state or any option.
+ *   n_reads == 0 with otherwise valid arguments returns FASTECC_OK and does nothing.
+ *   FASTECC_E_INVAL, before any device work and with nothing written: a null context; a null data, parity, reads or out with n_reads > 0, a null
+ *   pattern_of (set form); count == 0; data, parity or out not 4-byte aligned; width_words == 0, or col0_words + width_words beyond the words of a
+ *   block; a read index >= count*k; byte sizes beyond 64 bits; an `out` range that overlaps the data or the parity range; no set prepared (no
+ *   pattern prepared for fastecc_read_batch); an entry of a named stripe that is >= n_patterns and not FASTECC_PATTERN_NONE.
+ *   FASTECC_E_UNSUPPORTED: GF((2^61-1)^2), sharded contexts, a set "row_pitch_words", and for fastecc_read_batch a transform-path pattern.
+ */
+int fastecc_read_batch_set(fastecc_ctx *ctx, const void *data, const void *parity, uint64_t count, const uint32_t *pattern_of,
+                           const uint64_t *reads, uint64_t n_reads, uint64_t col0_words, uint64_t width_words, void *out, void *stream);
+int fastecc_read_batch(fastecc_ctx *ctx, const void *data, const void *parity, uint64_t count,
+                       const uint64_t *reads, uint64_t n_reads, uint64_t col0_words, uint64_t width_words, void *out, void *stream);
 
 /*
  * Error detection and location ("scrub"): find blocks that are present but wrong — bit rot, torn or misdirected writes — which
