@@ -2005,8 +2005,11 @@ int read_batch_impl(fastecc_ctx* c, const void* data, const void* parity, uint64
     } else {
         d = c->decoder;
         if (!d || !d->ready) return FASTECC_E_INVAL;  // fastecc_decode_prepare first
-        if (!d->sub) return FASTECC_E_UNSUPPORTED;    // a pattern of the transform path
-        if (d->sub_lost_data > 0) {
+        // a pattern of the transform path is not served — but a pattern that lost NOTHING has no tables on either path (Prepare::direct leaves it to
+        // transform_path, which finds nothing to build): it has no lost data block, so every request is a copy.  (erased_total is no measure of
+        // that: on the transform path it counts the positions of a folded or zero-extended code that hold no block.)
+        if (!d->sub && (d->erased_data != 0 || d->erased_parity != 0)) return FASTECC_E_UNSUPPORTED;
+        if (d->sub && d->sub_lost_data > 0) {
             single = d->sub_both && d->sub_only_both ? d->direct.both.get() : d->direct.data.get();
             if (!single || d->host_lost_data.size() != (size_t)d->sub_lost_data) return FASTECC_E_DEVICE;
         }

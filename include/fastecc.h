@@ -458,7 +458,8 @@ int fastecc_repair_batch_set(fastecc_ctx *ctx, void *data, void *parity, uint64_
  *       nothing, means every block of that stripe is present.
  *   fastecc_read_batch : every stripe is taken under the single pattern of the last fastecc_decode_prepare, as by fastecc_decode_batch.  Only
  *       patterns of the direct path are served (up to "decode_direct_max" lost blocks); a pattern prepared for the transform path returns
- *       FASTECC_E_UNSUPPORTED.  A pattern with no lost data block is valid: every request is then a copy.
+ *       FASTECC_E_UNSUPPORTED.  A pattern with no lost data block is valid: every request is then a copy.  (A pattern that lost nothing at all
+ *       is served whatever "decode_direct_max" was when it was prepared: there is no table to build on either path.)
  *   What a request returns:
  *     - a block that is present under its stripe's pattern: a plain copy of the window out of the pool.  No other block of the stripe is read; the
  *       words are copied as stored, words >= p included.

@@ -37,8 +37,26 @@ State probes (each a short scripted run of operations that ends in a check on a 
   refused_bad_write                 an index >= count*k in writes: FASTECC_E_INVAL, nothing written         (627-630)
   refused_bad_pattern               pattern_of[b] == n_patterns: FASTECC_E_INVAL, nothing written           (413-416)
   refused_count0                    count == 0: FASTECC_E_INVAL                                             (375-377)
+Extended sequences (EXT_SEEDS) run these instead, and prepared_after_locate on rotated pools too (fastecc_locate_errors_batch_set, 643-647):
+  prepared_after_read               decode_prepare's pattern survives fastecc_read_batch / _read_batch_set  (477-478)
+  set_after_read                    the pattern set survives ...                                            (477-478)
+  scrub_after_read                  the scrub pattern survives ...                                          (477-478)
+  read_after_prepare                decode_prepare(A), read, decode_prepare(B), read on a scratch stripe: the second read rebuilds B's lost
+                                    blocks and copies A's (459-468).  B loses as many data blocks as A and differs in one; variant "transform":
+                                    A is prepared under decode_direct_max = 0 and its read is refused FASTECC_E_UNSUPPORTED with nothing
+                                    written (459-461, 484), B is direct; variant "parity": B loses parity only, every request a copy (461)
+  read_after_prepare_set            decode_prepare_set, a read on the side stream, a second decode_prepare_set with other patterns and nothing
+                                    synchronised in between (it waits for the read itself: 476-477), a read: it follows the new set (456-458)
+  refused_bad_read                  a read index >= count*k; pattern_of[b] == n_patterns for a requested stripe: FASTECC_E_INVAL, the output
+                                    all canary, the context unchanged                                        (480-483)
 
-Bursts: a "burst" operation enqueues 2 to 4 calls (writes of every form, at most one rebuild) back to back on the null and the side stream
+Reads ("read", extended sequences): fastecc_read_batch on fixed placement, fastecc_read_batch_set on rotated, over the whole pool: a present
+block gives the mirror's words (a corrupted block reads back corrupted, a quarantined stripe's garbage is copied), a block lost under its
+stripe's pattern gives the truth; lost blocks are requested only in stripes without a corrupted survivor (which survivors a pass reads is
+left open by the header).  The backend presets n_reads + 1 output rows to CANARY and returns the rows and the extra row ("guard").
+
+Bursts: a "burst" operation enqueues 2 to 4 calls (writes of every form, at most one rebuild; in extended sequences reads too, their output
+read back only after the burst) back to back on the null and the side stream
 with nothing read in between, so a call meets the previous call's staged list and buffers still in flight; its prediction is the calls
 applied in order.
 
@@ -56,6 +74,7 @@ PATTERN_NONE = 0xFFFFFFFF
 OK, E_INVAL, E_UNSUPPORTED = 0, -1, -4
 UNSPECIFIED = "UNSPECIFIED"
 MIXED_RADIX = 1  # FASTECC_CODE_MIXED_RADIX
+CANARY = 0xFFFA5A5A  # what the output rows of a read hold before the call (>= p: no word of the truth)
 
 
 # ---- the code forms (shared with test_gpu_fuzz.py and test_gpu_cosets.py) ----
@@ -117,10 +136,24 @@ def _configs():
 
 CONFIGS = _configs()
 SEEDS = (1, 2, 3, 4)
+EXT_SEEDS = (5, 6)  # the extended sequences: reads, set location, whole-stripe writes (Generator(extended=True))
 
 
 def config_named(name):
     return next(c for c in CONFIGS if c.name == name)
+
+
+def writes_of(op, k):
+    """the pool block indices a write names: its list, or every data block of the stripes [b0, b1) of a whole-stripe write"""
+    return list(range(op["b0"] * k, op["b1"] * k)) if op["form"] == "pool" else op["writes"]
+
+
+def window(row, op):
+    return row[op["col0"]:op["col0"] + op["width"]]
+
+
+def canary_rows(n, width):
+    return np.full((n, width), CANARY, dtype=np.uint32)
 
 
 class ModelError(Exception):
@@ -150,11 +183,12 @@ class Ctx:
         self.prepared_set = None  # None or a tuple of such tuples
         self.scrub = ()           # the absent blocks fastecc_scrub_erasures named
         self.scrub_set = None
-        self.options = {"scrub_batch_chunk": 0, "direct_kernel": 0, "decode_direct_max": 256, "locate_max": 256}
+        self.prepared_limit = 256  # "decode_direct_max" when the pattern was prepared: it chose the pattern's path
+        self.options = {"scrub_batch_chunk": 0, "direct_kernel": 0, "decode_direct_max": 256, "locate_max": 256, "encode_pool_kernel": 0}
         self.stream = 0
 
     def snapshot(self):
-        return (self.prepared, self.prepared_set, self.scrub, self.scrub_set, tuple(sorted(self.options.items())), self.stream)
+        return (self.prepared, self.prepared_limit, self.prepared_set, self.scrub, self.scrub_set, tuple(sorted(self.options.items())), self.stream)
 
 
 class PoolModel:
@@ -232,6 +266,23 @@ class PoolModel:
             raise ModelError("the single prepared pattern is %s: decode_prepare first" % (self.ctx.prepared,))
         return self.ctx.prepared
 
+    def _set_pattern(self, q):
+        if self.ctx.prepared_set is None:
+            raise ModelError("no pattern set")
+        return self.ctx.prepared_set[q]
+
+    def _served(self):
+        """fastecc_read_batch serves the single prepared pattern: one of the direct path (at most "decode_direct_max" lost blocks when it was
+        prepared), or one that lost nothing"""
+        return len(self._prepared()) <= self.ctx.prepared_limit
+
+    def _scratch_stripe(self, rng, b, lost):
+        """stripe b's truth with the blocks of `lost` overwritten with garbage"""
+        d, p = self.truth_d[b].copy(), self.truth_p[b].copy()
+        for j in lost:
+            (d[j] if j < self.k else p[j - self.k])[:] = _garbage(rng, self.S, j % 2 == 0)
+        return d, p
+
     # -- the arrays an operation carries (a function of the model and the operation's dseed)
     def payload(self, op):
         kind, rng = op["op"], _rng("data", self.cfg.name, self.seed, op.get("dseed", 0))
@@ -253,10 +304,18 @@ class PoolModel:
         elif kind == "device_down":
             pay["pokes"] = [(b, j, _garbage(rng, self.S, b % 2 == 0)) for b in self.live() for j in self.blocks_on(b, [op["dev"]])]
         elif kind == "write":
-            new = _below_p(rng, (len(op["writes"]), self.S))
+            writes = writes_of(op, self.k)
+            new = _below_p(rng, (len(writes), self.S))
             new.reshape(-1)[:3] = [P - 1, 0, 1][: min(3, new.size)]
             pay["new"] = new
-            pay["old"] = np.stack([self.mirror_d[w // self.k, w % self.k] for w in op["writes"]])
+            if op["form"] != "pool":
+                pay["old"] = np.stack([self.mirror_d[w // self.k, w % self.k] for w in writes])
+        elif kind == "probe_read":
+            lost = self._prepared() if not op["set"] else self._set_pattern(op["q"])
+            pay["scratch_d"], pay["scratch_p"] = self._scratch_stripe(rng, op["b"], lost)
+            pay["src"] = op["b"]
+        elif kind == "probe_read_swap":
+            pay["src"], pay["scratch"] = op["b"], [self._scratch_stripe(rng, op["b"], half["patterns"][half["q"]]) for half in op["halves"]]
         elif kind in ("probe_repair", "probe_repair_set"):
             lost = self._prepared() if kind == "probe_repair" else self.ctx.prepared_set[op["q"]]
             d, p = self.truth_d[op["b"]].copy(), self.truth_p[op["b"]].copy()
@@ -317,10 +376,15 @@ class PoolModel:
         return {}
 
     def _write(self, op, pay):
-        writes = op["writes"]
+        writes = writes_of(op, self.k)
         if len(set(writes)) != len(writes):
             raise ModelError("duplicate write")
         touched = sorted({w // self.k for w in writes})
+        if op["form"] == "pool":  # every data block is new and every parity block is encoded: what was corrupted is gone
+            if not touched or any(b in self.quarantined or self.absent[b] for b in touched):
+                raise ModelError("a whole-stripe write into a stripe that is quarantined or has an absent block")
+            for b in touched:
+                self.corrupt[b].clear()
         if not all(self.whole(b) for b in touched):
             raise ModelError("a write into a stripe that is not whole")
         for u, w in enumerate(writes):
@@ -331,6 +395,7 @@ class PoolModel:
 
     def _prepare(self, op, pay):
         self.ctx.prepared = tuple(op["lost"])
+        self.ctx.prepared_limit = self.ctx.options["decode_direct_max"]
 
     def _prepare_set(self, op, pay):
         self.ctx.prepared_set = tuple(tuple(q) for q in op["patterns"])
@@ -369,11 +434,16 @@ class PoolModel:
     def _locate(self, op, pay):
         if self.mixed:
             return {"code": E_UNSUPPORTED}
-        if self.rotated:
-            raise ModelError("locate is a fixed-placement operation")
-        self._scrub_ready(False)
+        use_set = bool(op.get("set"))
+        if use_set != self.rotated:
+            raise ModelError("locate is a fixed-placement operation, locate under the set a rotated one")
+        if use_set and op["pattern_of"] != self.pattern_of(op["b0"], op["b1"], lambda b: b not in self.quarantined):
+            raise ModelError("pattern_of does not skip what it must")
+        self._scrub_ready(use_set)
         self._check_budget(op["b0"], op["b1"])
-        lists = [sorted(self.corrupt[b]) for b in range(op["b0"], op["b1"])]
+        # stripe b's absent blocks (under the set those of its own pattern) are never read and never listed
+        lists = [[] if b in self.quarantined else [j for j in sorted(self.corrupt[b]) if j not in self.blocks_on(b, self.devs)]
+                 for b in range(op["b0"], op["b1"])]
         status = [1 if x else 0 for x in lists]
         return {"code": OK, "status": status, "lists": lists, "inconsistent": sum(status)}
 
@@ -443,13 +513,74 @@ class PoolModel:
 
     def _burst(self, op, pay):
         """several enqueued calls back to back, nothing read in between: the prediction is the calls applied in order"""
-        pay["subs"], codes = [], []
+        pay["subs"], codes, reads = [], [], []
+        for sub in op["ops"]:  # a read is drawn against the patterns as the burst meets them (a rebuild of the burst may bring a device back:
+            if sub["op"] == "read":  # its blocks are then present and whole, and lost under the pattern in force — the truth either way)
+                self._read_check(sub)
         for sub in op["ops"]:
-            if sub["op"] not in ("write", "repair", "decode"):
+            if sub["op"] not in ("write", "repair", "decode", "read"):
                 raise ModelError("a burst holds enqueued calls only")
-            pay["subs"].append(self.payload(sub))
-            codes.append(self.apply(sub, pay["subs"][-1])["code"])
-        return {"code": OK, "codes": codes}
+            pay["subs"].append(dict(self.payload(sub), in_burst=True))
+            out = self.apply(sub, pay["subs"][-1])
+            codes.append(out["code"])
+            if sub["op"] == "read":
+                reads.append(out)
+        out = {"code": OK, "codes": codes}
+        if reads:  # every read's rows, then every read's guard row, as the backend reads them back after the burst
+            out["rows"] = np.concatenate([r["rows"].reshape(-1) for r in reads])
+            out["guard"] = np.concatenate([r["guard"] for r in reads])
+        return out
+
+    def _read_check(self, op):
+        if op["set"] != self.rotated:
+            raise ModelError("the pool's placement needs the other form")
+        if not op["reads"] or op["width"] < 1 or op["col0"] + op["width"] > self.S:
+            raise ModelError("no such read")
+        if op["set"]:
+            if self.ctx.prepared_set != self.needed_set():
+                raise ModelError("the prepared pattern set is stale")
+            if op["pattern_of"] != self.pattern_of(0, self.count, lambda b: b not in self.quarantined):
+                raise ModelError("pattern_of does not skip what it must")
+        elif self._prepared() != self.needed_single():
+            raise ModelError("the prepared pattern is not the pool's")
+
+    def _read(self, op, pay):
+        """fastecc_read_batch / _read_batch_set over the whole pool: a present block is a copy of the mirror, a lost one the truth"""
+        if not pay.get("in_burst"):
+            self._read_check(op)
+        n, guard = len(op["reads"]), np.full(op["width"], CANARY, dtype=np.uint32)
+        if not op["set"] and not self._served():
+            return {"code": E_UNSUPPORTED, "rows": canary_rows(n, op["width"]), "guard": guard}
+        rows = []
+        for idx in op["reads"]:
+            b, i = divmod(idx, self.k)
+            if not 0 <= b < self.count:
+                raise ModelError("no such block")
+            if b not in self.quarantined and self.dev_of(b, i) in self.devs:  # lost under its stripe's pattern
+                if self.corrupt[b]:
+                    raise ModelError("a lost block of stripe %d, which has a corrupted survivor" % b)
+                rows.append(window(self.truth_d[b, i], op))
+            else:
+                rows.append(window(self.mirror_d[b, i], op))
+        return {"code": OK, "rows": np.stack(rows), "guard": guard}
+
+    def _probe_read(self, op, pay):
+        """a read of a scratch stripe (stripe b's truth, garbage where the pattern in force lost a block): the truth, whatever is asked for"""
+        n, guard = len(op["reads"]), np.full(op["width"], CANARY, dtype=np.uint32)
+        if op["set"]:
+            self._set_pattern(op["q"])
+        elif not self._served():
+            return {"code": E_UNSUPPORTED, "rows": canary_rows(n, op["width"]), "guard": guard}
+        return {"code": OK, "rows": np.stack([window(self.truth_d[op["b"], i], op) for i in op["reads"]]), "guard": guard}
+
+    def _probe_read_swap(self, op, pay):
+        """decode_prepare_set(first patterns), a read on the side stream, decode_prepare_set(second patterns) with nothing synchronised, a read"""
+        rows = []
+        for half in op["halves"]:
+            self.ctx.prepared_set = tuple(tuple(q) for q in half["patterns"])
+            rows.append(np.stack([window(self.truth_d[op["b"], i], half) for i in half["reads"]]).reshape(-1))
+        return {"code": OK, "codes": [OK] * 4, "rows": np.concatenate(rows),
+                "guard": np.concatenate([np.full(half["width"], CANARY, dtype=np.uint32) for half in op["halves"]])}
 
     def _probe_repair(self, op, pay):
         lost = self._prepared()
@@ -478,6 +609,8 @@ class PoolModel:
         return {"code": OK, "ok": [1, 0]}
 
     def _refused(self, op, pay):
+        if op["which"] == "bad_read":  # two refused reads, (n_reads + 1) rows each: all canary
+            return {"code": E_INVAL, "codes": [E_INVAL, E_INVAL], "rows": canary_rows(2 * (len(op["reads"]) + 1), op["width"]).reshape(-1)}
         return {"code": E_INVAL}
 
 
@@ -494,17 +627,30 @@ WEIGHTS = {"write": 12, "corrupt": 12, "device_down": 6, "device_replaced": 9, "
            "decode": 5, "reencode": 5, "option": 6, "stream": 4, "burst": 8}
 
 
+# Extended sequences (the seeds EXT_SEEDS): the kinds above and "read"; "locate" on rotated pools too (fastecc_locate_errors_batch_set); writes
+# and re-encodes have the form "pool" (fastecc_encode_pool); option "encode_pool_kernel" is flipped; bursts hold reads.  Their probes are
+# EXT_PROBES, met in turn like PROBES: the two seeds and two placements of a configuration start 5 apart, so every probe is met at least twice.
+EXT_KINDS = KINDS + ("read",)
+EXT_WEIGHTS = dict(WEIGHTS, read=16, write=20, reencode=18, locate=9)
+EXT_PROBES = [("read", "prepare"), ("prepared", "read"), ("set", "read"), ("scrub", "read"), ("read", "prepare_transform"),
+              ("read", "prepare_set"), ("refused", "bad_read"), ("read", "prepare_parity"), ("prepared", "locate")]
+WINDOWS = ("whole", "word", "narrow", "tail")
+
+
 class Generator:
-    def __init__(self, model, seed):
+    def __init__(self, model, seed, extended=False):
         self.m, self.rng = model, _rng("gen", model.cfg.name, seed)
         self.queue = collections.deque()
         self.drawn = self.skipped = 0
         self.dseed = 0
         self.verifies = 0
         m = model
-        kinds = [k for k in KINDS if not (m.mixed and k == "corrupt") and not (m.rotated and k == "locate")]
+        self.extended, self.seed, self.pool_encodes, self.used_form = extended, seed, 0, collections.Counter()
+        self.weights, self.probe_list = (EXT_WEIGHTS, EXT_PROBES) if extended else (WEIGHTS, PROBES)
+        kinds = [k for k in (EXT_KINDS if extended else KINDS)
+                 if not (m.mixed and k == "corrupt") and not (m.rotated and k == "locate" and not extended)]
         self.emitted = self.probes_started = 0
-        self.probe_at = 2 * (seed + (4 if model.rotated else 0))
+        self.probe_at = 5 * (seed - EXT_SEEDS[0] + (2 if m.rotated else 0)) if extended else 2 * (seed + (4 if model.rotated else 0))
         self.kinds = kinds
         self.used = collections.Counter()
 
@@ -518,9 +664,10 @@ class Generator:
 
     def _next_probe(self):
         m = self.m
-        for _ in range(len(PROBES)):
-            family, variant = PROBES[self.probe_at % len(PROBES)]
-            skip = ((m.mixed and (family == "scrub" or variant in ("correct", "locate"))) or (m.rotated and variant == "locate"))
+        for _ in range(len(self.probe_list)):
+            family, variant = self.probe_list[self.probe_at % len(self.probe_list)]
+            skip = ((m.mixed and (family == "scrub" or variant in ("correct", "locate")))
+                    or (m.rotated and variant == "locate" and not self.extended))
             if not skip:
                 ops = getattr(self, "make_probe_" + family)(variant)
                 if ops is None:
@@ -537,7 +684,11 @@ class Generator:
                 "device_down": len(m.devs) >= min(m.m, 2) or not all(m.budget(b, extra_w=1) for b in m.live()),
                 "write": not any(m.whole(b) for b in m.live())}
         idle["burst"] = idle["write"]
-        w = np.array([WEIGHTS[k] * (0.25 if idle.get(k) else 3.0 if not self.used[k] else 1.0) for k in self.kinds])
+        if self.extended:
+            if any(not m.absent[b] for b in m.live()):  # a whole-stripe write takes corrupted stripes too
+                idle["write"] = False
+            idle["reencode"] = not any(not any(j < m.k for j in list(m.corrupt[b]) + list(m.absent[b])) for b in m.live())
+        w = np.array([self.weights[k] * (0.25 if idle.get(k) else 3.0 if not self.used[k] else 1.0) for k in self.kinds])
         return self.kinds[int(self.rng.choice(len(self.kinds), p=w / w.sum()))]
 
     def _range(self, ok=None):
@@ -607,8 +758,18 @@ class Generator:
         return self._state_prepare() if m.ctx.prepared != m.needed_single() else None
 
     # operations: each returns a list of operations (prerequisites first) or None when the state does not allow it
-    def make_write(self):
+    def make_write(self, in_burst=False):
         m, rng = self.m, self.rng
+        # extended: whole stripes — new data and fastecc_encode_pool over the run — two times in five, and outside bursts a sequence's first two
+        # writes and every write while no stripe is whole.  Corrupted stripes qualify (the write makes them whole), but not inside a burst, whose
+        # other calls were drawn against the marks as they are
+        pool = self.extended and rng.random() < 0.4
+        if self.extended and not in_burst and (self.used_form["write_pool"] < 2 or not any(m.whole(b) for b in m.live())):
+            pool = True
+        if pool:
+            self.used_form["write_pool"] += 1
+            r = self._range((lambda b: m.whole(b)) if in_burst else (lambda b: b not in m.quarantined and not m.absent[b]))
+            return None if r is None else [{"op": "write", "form": "pool", "b0": r[0], "b1": r[1], "dseed": self._ds()}]
         whole = [b for b in range(m.count) if m.whole(b)]
         if not whole:
             return None
@@ -680,7 +841,12 @@ class Generator:
     def make_locate(self):
         pre = self._scrub_prereq()
         b0, b1 = self._range()
-        return ([pre] if pre else []) + [{"op": "locate", "b0": b0, "b1": b1, "seed": int(self.rng.integers(1 << 40))}]
+        op = {"op": "locate", "b0": b0, "b1": b1, "seed": int(self.rng.integers(1 << 40))}
+        if self.extended:  # fastecc_locate_errors_batch_set on rotated pools, pattern_of as for verify
+            op["set"] = self.m.rotated
+            if self.m.rotated:
+                op["pattern_of"] = self.m.pattern_of(b0, b1, lambda b: b not in self.m.quarantined)
+        return ([pre] if pre else []) + [op]
 
     def make_correct(self):
         m = self.m
@@ -721,6 +887,13 @@ class Generator:
         good = [b for b in range(m.count) if clean(b)]
         if not good:
             return None
+        if self.extended and (self.rng.random() < 0.6 or self.pool_encodes < 2):  # fastecc_encode_pool into the scratch parity, the kernel choice flipped first
+            b0, b1 = self._range(clean)
+            # under each kernel choice in turn (0 = choose, 1 = VALU, 2 = matrix cores), starting where the seed and the placement say
+            want = (self.pool_encodes + self.seed + (1 if m.rotated else 0)) % 3
+            self.pool_encodes += 1
+            pre = [{"op": "option", "name": "encode_pool_kernel", "value": want}] if m.ctx.options["encode_pool_kernel"] != want else []
+            return pre + [{"op": "reencode", "form": "pool", "b0": b0, "b1": b1}]
         if m.n == 2 * m.k and not m.mixed and self.rng.random() < 0.5:
             b0, b1 = self._range(clean)
             return [{"op": "reencode", "form": "batch", "b0": b0, "b1": b1}]
@@ -729,9 +902,12 @@ class Generator:
 
     def make_option(self):
         m = self.m
-        name = self._pick(["scrub_batch_chunk", "scrub_batch_chunk", "direct_kernel", "decode_direct_max", "locate_max"])
+        name = self._pick(["scrub_batch_chunk", "scrub_batch_chunk", "direct_kernel", "decode_direct_max", "locate_max"]
+                          + (["encode_pool_kernel"] * 3 if self.extended else []))
         if not m.mixed and self.used["option"] == 0:  # a sequence's first flip makes its scrub calls take several chunks
             return [{"op": "option", "name": "scrub_batch_chunk", "value": int(self._pick([3, 4]))}]
+        if name == "encode_pool_kernel":  # 0 = choose, 1 = VALU, 2 = matrix cores (VALU where they cannot run): always another value
+            return [{"op": "option", "name": name, "value": (m.ctx.options[name] + 1 + int(self.rng.integers(2))) % 3}]
         if name == "locate_max":
             t = max([sum(1 for v in m.corrupt[b].values() if v == "small") for b in m.live()] + [1])
             value = self._pick([v for v in (1, 2, 8, 256) if v >= t])
@@ -742,23 +918,152 @@ class Generator:
     def make_stream(self):
         return [{"op": "stream", "stream": 1 - self.m.ctx.stream}]
 
+    def _window(self, shape=None):
+        """(shape, col0, width): the whole block, one word, a narrow window with odd col0 and odd width, a window that ends at S"""
+        S, rng = self.m.S, self.rng
+        shape = shape or self._pick(WINDOWS)
+        if shape == "whole":
+            return shape, 0, S
+        if shape == "word":
+            return shape, int(rng.integers(S)), 1
+        if shape == "narrow":
+            col0 = 1 + 2 * int(rng.integers((S - 3) // 2))
+            return shape, col0, 1 + 2 * int(rng.integers(1, min(6, (S - col0 - 1) // 2 + 1)))
+        width = int(rng.integers(2, S // 2 + 1))
+        return shape, S - width, width
+
+    def _read_prereq(self):
+        """what makes the pool's own patterns the ones in force for a read ([] when they are): on fixed placement a pattern of the direct path"""
+        m = self.m
+        if m.rotated:
+            return [self._state_prepare_set()] if m.ctx.prepared_set != m.needed_set() else []
+        need, pre = m.needed_single(), []
+        if len(need) > m.ctx.options["decode_direct_max"]:
+            pre.append({"op": "option", "name": "decode_direct_max", "value": 256})
+        if pre or m.ctx.prepared != need or len(need) > m.ctx.prepared_limit:
+            pre.append(self._state_prepare())
+        return pre
+
+    def make_read(self, prefer=()):
+        """1 to about 3k requests over the whole pool: present and lost blocks, duplicates, quarantined stripes, corrupted blocks, shuffled"""
+        m, rng = self.m, self.rng
+        lost = [b * m.k + i for b in m.live() if not m.corrupt[b] for i in m.blocks_on(b, m.devs) if i < m.k]
+        barred = {b * m.k + i for b in m.live() if m.corrupt[b] for i in m.blocks_on(b, m.devs) if i < m.k}
+        special = [b * m.k + i for b in sorted(m.quarantined) for i in range(m.k)]
+        special += [b * m.k + j for b in m.live() for j in m.corrupt[b] if j < m.k]
+        n = int(rng.integers(1, 3 * m.k + 1)) if rng.random() < 0.5 else int(rng.integers(1, 9))
+        reads = [int(x) for x in prefer][: max(1, n // 2)]
+        if lost and n >= 3:  # the mix of one list: a lost block, a present one, a duplicate
+            x = self._pick(lost)
+            reads += [x, x]
+        while len(reads) < n:
+            u = rng.random()
+            if u < 0.3 and lost:
+                reads.append(self._pick(lost))
+            elif u < 0.45 and special:
+                reads.append(self._pick(special))
+            elif u < 0.55 and reads:
+                reads.append(self._pick(reads))
+            else:
+                x = int(rng.integers(m.count * m.k))
+                if x not in barred:
+                    reads.append(x)
+        reads = [reads[i] for i in rng.permutation(len(reads))]
+        shape, col0, width = self._window()
+        op = {"op": "read", "set": m.rotated, "reads": reads, "col0": col0, "width": width, "shape": shape}
+        if m.rotated:
+            op["pattern_of"] = m.pattern_of(0, m.count, lambda b: b not in m.quarantined)
+        return self._read_prereq() + [op]
+
+    def _probe_read(self, use_set, lost, probe=None, q=0, variant=None):
+        """a read of a scratch stripe under the single pattern or pattern q of the set: the blocks of `lost` (those the pattern in force then
+        has lost, and whatever else the probe wants to see), some others, a duplicate"""
+        m, rng = self.m, self.rng
+        reads = [j for j in lost if j < m.k] + [int(x) for x in rng.integers(m.k, size=int(rng.integers(1, 4)))]
+        reads.append(reads[0])
+        reads = [int(reads[i]) for i in rng.permutation(len(reads))]
+        shape, col0, width = self._window()
+        op = {"op": "probe_read", "set": use_set, "q": q, "b": self._pick(m.live()), "reads": reads, "col0": col0, "width": width, "shape": shape,
+              "dseed": self._ds(), "probe": probe}
+        if variant:
+            op["variant"] = variant
+        return op
+
+    def _mid_read(self):
+        """[a state operation, a scratch read]: the read whose effect on other state a probe looks for, in either form"""
+        m = self.m
+        if self.rng.random() < 0.5:
+            lost = self._probe_lost()
+            pre = [] if m.ctx.options["decode_direct_max"] >= len(lost) else [{"op": "option", "name": "decode_direct_max", "value": 256}]
+            return pre + [self._state_prepare(lost), self._probe_read(False, lost)]
+        sp = self._state_prepare_set()
+        q = int(self.rng.integers(len(sp["patterns"])))
+        return [sp, self._probe_read(True, sp["patterns"][q], q=q)]
+
+    def make_probe_read(self, x):
+        """read_after_prepare (plain: B loses as many data blocks as A and differs in one; "transform": A on the transform path, its read
+        refused; "parity": B loses parity only) and read_after_prepare_set"""
+        m, rng = self.m, self.rng
+        if x == "prepare_set":
+            halves = []
+            for _ in range(2):
+                patterns = [self._random_pattern(4) for _ in range(3)]
+                q = int(rng.integers(3))
+                r = self._probe_read(True, patterns[q] + (halves[0]["patterns"][halves[0]["q"]] if halves else []), q=q)
+                halves.append({"patterns": patterns, "q": q, "reads": r["reads"], "col0": r["col0"], "width": r["width"], "shape": r["shape"]})
+            return [{"op": "probe_read_swap", "halves": halves, "b": self._pick(m.live()), "dseed": self._ds(), "probe": "read_after_prepare_set"}]
+        # A: r lost data blocks (more than 16 where the code allows: the single form serves up to 256, a set 16 per pattern) and some parity
+        r = int(rng.integers(17, 21)) if m.m >= 40 and x == "prepare" else int(rng.integers(1, min(m.m, m.k - 1, 6) + 1))
+        a_data = sorted(int(i) for i in rng.choice(m.k, size=r, replace=False))
+        a_par = sorted(m.k + int(i) for i in rng.choice(m.m, size=int(rng.integers(0, min(m.m - r, 2) + 1)), replace=False))
+        if x == "prepare_parity":
+            b_lost = sorted(m.k + int(i) for i in rng.choice(m.m, size=int(rng.integers(1, min(m.m, 3) + 1)), replace=False))
+        else:
+            b_data = list(a_data)
+            b_data[int(rng.integers(r))] = self._pick([i for i in range(m.k) if i not in a_data])
+            b_lost = sorted(b_data) + a_par
+        a_lost = a_data + a_par
+        ops = []
+        limit = m.ctx.options["decode_direct_max"]
+        if x == "prepare_transform":
+            ops.append({"op": "option", "name": "decode_direct_max", "value": 0})
+        elif limit < max(len(a_lost), len(b_lost)):
+            ops.append({"op": "option", "name": "decode_direct_max", "value": 256})
+        ops += [self._state_prepare(a_lost), self._probe_read(False, a_lost)]
+        if x == "prepare_transform":
+            ops.append({"op": "option", "name": "decode_direct_max", "value": 256})
+        ops += [self._state_prepare(b_lost), self._probe_read(False, b_lost + a_lost, "read_after_prepare", variant=x[8:] or "plain")]
+        return ops
+
     def make_burst(self):
         """2 to 4 enqueued calls back to back (writes of every form, at most one rebuild), each on the null or the side stream"""
         m, rng = self.m, self.rng
         ops = []
         for _ in range(int(rng.integers(2, 5))):
-            w = self.make_write()
+            w = self.make_write(in_burst=True) if self.extended else self.make_write()
             if w:
                 ops += w
         if self._rebuild_prereq() is None and rng.random() < 0.6:
             r = self._make_rebuild(self._pick(["repair", "decode"]))
             if r:
                 ops.insert(int(rng.integers(len(ops) + 1)), r[-1])
+        pre = []
+        if self.extended and ops and (rng.random() < 0.7 or not self.used_form["burst_read"]):
+            self.used_form["burst_read"] += 1
+            pre = self._read_prereq()  # (the pool's own patterns, made the ones in force before the burst)
+            # a read behind one of the calls, asking for blocks that the write before it has just replaced
+            at = int(rng.integers(1, len(ops) + 1))
+            before = [x for x in ops[:at] if x["op"] == "write"]
+            ops.insert(at, self.make_read(prefer=writes_of(before[-1], m.k) if before else ())[-1])
         if len(ops) < 2:
             return None
         for sub in ops:
             sub["stream"] = int(rng.integers(2))
-        return [{"op": "burst", "ops": ops}]
+        if self.extended and len({sub["stream"] for sub in ops}) == 1:  # a read of a burst runs beside a call on the other stream
+            for sub in ops:
+                if sub["op"] == "read":
+                    sub["stream"] = 1 - sub["stream"]
+        return pre + [{"op": "burst", "ops": ops}]
 
     def _probe_lost(self):
         return self._random_pattern(20)
@@ -780,6 +1085,17 @@ class Generator:
             if mid is None:
                 return None
             mid[0]["form"] = "batch"
+        elif x == "read":  # a scratch read under the probe's own pattern, or one under the set
+            lost = self._probe_lost()
+            if self.rng.random() < 0.5:
+                mid = [self._probe_read(False, lost)]
+                if m.ctx.options["decode_direct_max"] < len(lost):
+                    mid.insert(0, {"op": "option", "name": "decode_direct_max", "value": 256})
+            else:
+                sp = self._state_prepare_set()
+                q = int(self.rng.integers(len(sp["patterns"])))
+                mid = [sp, self._probe_read(True, sp["patterns"][q], q=q)]
+            return mid[:-1] + [self._state_prepare(lost)] + mid[-1:] + [self._probe_repair("prepared_after_read")]
         else:
             mid = self.make_verify() if x == "verify" else self.make_locate()
         pre, mid = mid[:-1], mid[-1:]
@@ -800,6 +1116,15 @@ class Generator:
             pr = self._probe_repair(None)
             pr["form"] = self._pick(["decode", "repair"]) + ("_batch" if y == "batch" else "")
             ops.append(pr)
+        elif y == "read":  # a scratch read under a single pattern of its own, or one under the set itself
+            if self.rng.random() < 0.5:
+                lost = self._probe_lost()
+                if m.ctx.options["decode_direct_max"] < len(lost):
+                    ops.append({"op": "option", "name": "decode_direct_max", "value": 256})
+                ops += [self._state_prepare(lost), self._probe_read(False, lost)]
+            else:
+                q = int(self.rng.integers(len(patterns)))
+                ops.append(self._probe_read(True, list(patterns[q]), q=q))
         else:
             ops = self.make_correct()[:-1] + ops + self.make_correct()[-1:]
         q = int(self.rng.integers(len(patterns)))
@@ -821,6 +1146,8 @@ class Generator:
             pr = self._probe_repair(None)
             pr["form"] = self._pick(["decode", "repair"])
             ops.append(pr)
+        elif z == "read":
+            ops += self._mid_read()
         else:
             ops.append(self.make_correct()[-1])
         j = self._pick([j for j in range(m.n) if j not in scrub])
@@ -829,6 +1156,12 @@ class Generator:
         return ops
 
     def make_probe_refused(self, which):
+        if which == "bad_read":  # among valid requests an index count*k; for a requested stripe a pattern_of entry equal to the number of patterns
+            m = self.m
+            reads = [int(x) for x in self.rng.integers(m.count * m.k, size=int(self.rng.integers(2, 6)))]
+            shape, col0, width = self._window()
+            return [{"op": "refused", "which": which, "entry": len(m.ctx.prepared_set or ()), "reads": reads, "at": int(self.rng.integers(len(reads))),
+                     "col0": col0, "width": width, "shape": shape, "probe": "refused_" + which}]
         return [{"op": "refused", "which": which, "entry": len(self.m.ctx.prepared_set or ()), "probe": "refused_" + which}]
 
     def next_op(self):
@@ -855,10 +1188,10 @@ class Generator:
 
 # ---- the driver ----
 class SequenceFailure(AssertionError):
-    def __init__(self, cfg, seed, step, what, log):
+    def __init__(self, cfg, seed, step, what, log, extended=False):
         self.cfg, self.seed, self.step, self.what, self.log = cfg, seed, step, what, log
-        super().__init__("config %s seed %d step %d: %s\nreplay: run_sequence(backend, config_named(%r), %d, steps=%d)\noperations:\n%s"
-                         % (cfg.name, seed, step, what, cfg.name, seed, step + 1, "\n".join(log)))
+        super().__init__("config %s seed %d step %d: %s\nreplay: run_sequence(backend, config_named(%r), %d, steps=%d%s)\noperations:\n%s"
+                         % (cfg.name, seed, step, what, cfg.name, seed, step + 1, ", extended=True" if extended else "", "\n".join(log)))
 
 
 def _same(a, b):
@@ -867,17 +1200,19 @@ def _same(a, b):
     return a == b
 
 
-def run_sequence(backend, cfg, seed, steps=None, oracle=None, on_step=None):
+def run_sequence(backend, cfg, seed, steps=None, oracle=None, on_step=None, extended=False, log=None):
     """Apply the sequence of (cfg, seed) to a fresh model and to `backend`; after every step compare every host output and the whole pool.
-    Returns the model's Coverage.  Raises SequenceFailure (config, seed, step, the operation log) at the first difference."""
+    Returns the model's Coverage.  Raises SequenceFailure (config, seed, step, the operation log) at the first difference.  `extended`: the
+    generator draws the extended kinds as well (the seeds EXT_SEEDS; off, a sequence is what it always was).  `log`: a list that receives the
+    operation log, one JSON line per step."""
     if oracle is None:
         from oracle import Oracle
         oracle = Oracle()
     model = PoolModel(cfg, seed, oracle)
-    gen = Generator(model, seed)
+    gen = Generator(model, seed, extended)
     cov = Coverage(model)
     backend.start(model.mirror_d, model.mirror_p, sorted(model.quarantined))
-    log = []
+    log = [] if log is None else log
     for step in range(cfg.steps if steps is None else steps):
         op = gen.next_op()
         log.append("%3d %s" % (step, json.dumps(op, separators=(",", ":"))))
@@ -891,13 +1226,13 @@ def run_sequence(backend, cfg, seed, steps=None, oracle=None, on_step=None):
         got = backend.run(op, pay)
         for key in want:
             if key not in got or not _same(want[key], got[key]):
-                raise SequenceFailure(cfg, seed, step, "output %r is %r, the model says %r" % (key, got.get(key), want[key]), log)
+                raise SequenceFailure(cfg, seed, step, "output %r is %r, the model says %r" % (key, got.get(key), want[key]), log, extended)
         d, p = backend.read_pool()
         if not np.array_equal(d, model.mirror_d) or not np.array_equal(p, model.mirror_p):
             bad = sorted({int(b) for b in np.nonzero((d != model.mirror_d).any(axis=(1, 2)) | (p != model.mirror_p).any(axis=(1, 2)))[0]})
             blocks = [j for j in range(model.n) if not np.array_equal(model.block(d, p, bad[0], j), model.block(model.mirror_d, model.mirror_p, bad[0], j))]
             raise SequenceFailure(cfg, seed, step, "the pool differs from the model in stripes %s (quarantined: %s); stripe %d blocks %s"
-                                  % (bad, sorted(model.quarantined), bad[0], blocks), log)
+                                  % (bad, sorted(model.quarantined), bad[0], blocks), log, extended)
         cov.after(op)
         if on_step:
             on_step(step, op)
@@ -923,8 +1258,28 @@ class Coverage:
                 self.before(sub)
             if len({sub["stream"] for sub in op["ops"]}) > 1:
                 self.variants["burst_two_streams"] += 1
+                if any(sub["op"] == "read" for sub in op["ops"]):
+                    self.variants["read_in_two_stream_burst"] += 1
+            if any(sub["op"] == "read" and sub["stream"] == 1 for sub in op["ops"]):
+                self.variants["read_side_stream"] += 1
             return
         v = self.variants
+        if kind in ("read", "probe_read"):
+            self._read(op, v)
+        if kind == "probe_read_swap":
+            v["read_side_stream"] += 1
+            for half in op["halves"]:
+                v["window_" + half["shape"]] += 1
+        if kind == "refused" and op["which"] == "bad_read":
+            v["window_" + op["shape"]] += 1
+        if kind == "locate" and op.get("set"):
+            self.kinds["locate_set"] += 1
+            v["locate_set"] += 1
+        if kind in ("write", "reencode") and op["form"] == "pool":
+            self.kinds[kind + "_pool"] += 1
+            v["%s_pool_kernel_%d" % (kind, m.ctx.options["encode_pool_kernel"])] += 1
+            if kind == "write" and (op["b0"], op["b1"]) != (0, m.count):
+                v["write_pool_subrange"] += 1
         if "b0" in op and (op["b0"], op["b1"]) != (0, m.count) and kind != "reencode":
             self.kinds["subrange"] += 1
             v["subrange"] += 1
@@ -943,13 +1298,41 @@ class Coverage:
             v["kernel_%d" % op["kernel"]] += 1
         if kind == "write":
             v["write_" + op["form"]] += 1
-            per = collections.Counter(w // m.k for w in op["writes"])
-            if op["form"] != "single" and max(per.values()) > 16:
+            per = collections.Counter(w // m.k for w in writes_of(op, m.k))
+            if op["form"] not in ("single", "pool") and max(per.values()) > 16:
                 v["segment_over_16"] += 1
         if kind == "corrupt" and len(op["blocks"]) + len(m.devs) > 16:
             v["over_16_lost"] += 1
         if m.ctx.stream == 1 and kind not in ("stream", "option", "device_replaced", "corrupt", "device_down"):
             v["side_stream"] += 1
+
+    def _read(self, op, v):
+        """the variants of one read (a pool read or a probe's scratch read), against the patterns in force as the call meets them"""
+        m = self.m
+        if not op["set"]:
+            m._prepared()
+        if m.ctx.stream == 1:
+            v["read_side_stream"] += 1
+        v["read_set" if op["set"] else "read_single"] += 1
+        v["window_" + op["shape"]] += 1
+        if op["op"] == "probe_read":
+            lost = m.ctx.prepared_set[op["q"]] if op["set"] else m.ctx.prepared
+            kinds = {"lost" if i in lost else "present" for i in op["reads"]}
+            patterns = [lost]
+        else:
+            stripes = sorted({idx // m.k for idx in op["reads"]})
+            if any(b in m.quarantined for b in stripes):
+                v["read_pattern_none"] += 1
+            kinds = {"lost" if b not in m.quarantined and m.dev_of(b, i) in m.devs else "present" for b, i in (divmod(idx, m.k) for idx in op["reads"])}
+            patterns = [m.blocks_on(b, m.devs) for b in stripes if b not in m.quarantined] if op["set"] else [m.ctx.prepared]
+        if kinds == {"lost", "present"} and len(set(op["reads"])) < len(op["reads"]):
+            v["read_mixed_list"] += 1
+        if any(q and min(q) >= m.k for q in patterns):
+            v["read_parity_only"] += 1
+        if not op["set"] and len(m.ctx.prepared) > 16 and len(m.ctx.prepared) <= m.ctx.prepared_limit:
+            v["read_single_over_16_lost"] += 1
+        if op.get("probe") == "read_after_prepare":
+            v["read_after_prepare_" + op["variant"]] += 1
 
     def after(self, op):
         if op.get("probe"):
@@ -977,6 +1360,7 @@ class ModelBackend:
         self.d, self.p = d.copy(), p.copy()
         self.td, self.tp = d.copy(), p.copy()
         self.prepared, self.prepared_set, self.scrub, self.scrub_set = None, None, (), None
+        self.prepared_limit = 256
         self.options = {}
 
     def read_pool(self):
@@ -1003,14 +1387,22 @@ class ModelBackend:
 
     def op_write(self, op, pay):
         """fastecc_update_batch, fastecc_update on one stripe, or fastecc_update_parity_batch + the caller's own store of the data blocks"""
-        for u, w in enumerate(op["writes"]):
+        writes = writes_of(op, self.k)  # (form "pool": the harness stores every data block of the run, fastecc_encode_pool encodes it)
+        for u, w in enumerate(writes):
             self.d[w // self.k, w % self.k] = pay["new"][u]
-        for b in sorted({w // self.k for w in op["writes"]}):
-            self.p[b] = self.codec.parity(self.d[b])
-            self.td[b], self.tp[b] = self.d[b], self.p[b]
+        touched = sorted({w // self.k for w in writes})
+        encoded = self.encoded_stripes(op, touched)
+        for b in touched:
+            self.td[b], self.tp[b] = self.d[b], self.codec.parity(self.d[b])
+            if b in encoded:
+                self.p[b] = self.tp[b]
+
+    def encoded_stripes(self, op, stripes):
+        return stripes
 
     def op_prepare(self, op, pay):
         self.prepared = tuple(op["lost"])
+        self.prepared_limit = self.options.get("decode_direct_max", 256)
 
     def op_prepare_set(self, op, pay):
         self.prepared_set = tuple(tuple(q) for q in op["patterns"])
@@ -1030,7 +1422,7 @@ class ModelBackend:
 
     def _absent_of(self, op, b):
         """the absent blocks a scrub call applies to stripe b, or None for FASTECC_PATTERN_NONE"""
-        if not op["set"]:
+        if not op.get("set"):
             return self.scrub
         q = op["pattern_of"][b - op["b0"]]
         return None if q == PATTERN_NONE else self.scrub_set[q]
@@ -1053,7 +1445,8 @@ class ModelBackend:
     def op_locate(self, op, pay):
         if self.mixed:
             return {"code": E_UNSUPPORTED}
-        lists = [self._wrong(b, self.scrub) for b in range(op["b0"], op["b1"])]
+        absent = [self._absent_of(op, b) for b in range(op["b0"], op["b1"])]
+        lists = [[] if a is None else self._wrong(b, a) for b, a in zip(range(op["b0"], op["b1"]), absent)]
         status = [1 if x else 0 for x in lists]
         return {"code": OK, "status": status, "lists": lists, "inconsistent": sum(status)}
 
@@ -1098,7 +1491,58 @@ class ModelBackend:
         pass
 
     def op_burst(self, op, pay):
-        return {"code": OK, "codes": [self.run(sub, pz)["code"] for sub, pz in zip(op["ops"], pay["subs"])]}
+        outs = [self.run(sub, pz) for sub, pz in zip(op["ops"], pay["subs"])]
+        out = {"code": OK, "codes": [o["code"] for o in outs]}
+        reads = [o for sub, o in zip(op["ops"], outs) if sub["op"] == "read"]
+        if reads:
+            out["rows"] = np.concatenate([r["rows"].reshape(-1) for r in reads])
+            out["guard"] = np.concatenate([r["guard"] for r in reads])
+        return out
+
+    # -- degraded reads: (n_reads + 1) rows of canary, row u the window of the requested block — as stored where the block is present under the
+    # pattern in force, the truth where it is lost
+    def single_pattern(self):
+        return self.prepared
+
+    def read_rows(self, d, td, reads, lost_of, col0, width):
+        out = canary_rows(len(reads) + 1, width)
+        for u, (b, i) in enumerate(reads):
+            out[u] = (td if i in lost_of(b) else d)[b, i, col0:col0 + width]
+        return out
+
+    def read_out(self, code, out):
+        return {"code": code, "rows": out[:-1], "guard": out[-1]}
+
+    def op_read(self, op, pay):
+        reads = [divmod(idx, self.k) for idx in op["reads"]]
+        if op["set"]:
+            def lost_of(b):
+                return () if op["pattern_of"][b] == PATTERN_NONE else self.prepared_set[op["pattern_of"][b]]
+        else:
+            if len(self.prepared) > self.prepared_limit:
+                return self.read_out(E_UNSUPPORTED, canary_rows(len(reads) + 1, op["width"]))
+            lost = self.single_pattern()
+
+            def lost_of(b):
+                return lost
+        return self.read_out(OK, self.read_rows(self.d, self.td, reads, lost_of, op["col0"], op["width"]))
+
+    def _scratch_read(self, d, src, lost, half):
+        """one read of a scratch stripe `d` whose truth is stripe src's"""
+        return self.read_rows(d[None], self.td[src][None], [(0, i) for i in half["reads"]], lambda b: lost, half["col0"], half["width"])
+
+    def op_probe_read(self, op, pay):
+        if not op["set"] and len(self.prepared) > self.prepared_limit:
+            return self.read_out(E_UNSUPPORTED, canary_rows(len(op["reads"]) + 1, op["width"]))
+        lost = self.prepared_set[op["q"]] if op["set"] else self.single_pattern()
+        return self.read_out(OK, self._scratch_read(pay["scratch_d"], pay["src"], lost, op))
+
+    def op_probe_read_swap(self, op, pay):
+        outs = []
+        for half, (d, p) in zip(op["halves"], pay["scratch"]):
+            self.prepared_set = tuple(tuple(q) for q in half["patterns"])
+            outs.append(self._scratch_read(d, pay["src"], self.prepared_set[half["q"]], half))
+        return {"code": OK, "codes": [OK] * 4, "rows": np.concatenate([o[:-1].reshape(-1) for o in outs]), "guard": np.concatenate([o[-1] for o in outs])}
 
     def _scratch_rebuild(self, pay, lost, repair):
         d, p = pay["scratch_d"].copy(), pay["scratch_p"].copy()
@@ -1123,6 +1567,8 @@ class ModelBackend:
         return {"code": OK, "ok": ok}
 
     def op_refused(self, op, pay):
+        if op["which"] == "bad_read":
+            return {"code": E_INVAL, "codes": [E_INVAL, E_INVAL], "rows": canary_rows(2 * (len(op["reads"]) + 1), op["width"]).reshape(-1)}
         return {"code": E_INVAL}
 
 
@@ -1184,6 +1630,7 @@ class GpuBackend:
 
     def start(self, d, p, quarantined):
         torch = self.torch
+        self.quarantined = set(quarantined)
         self.D = torch.empty(self.count * self.dw, dtype=torch.int32, device="cuda:0")
         self.Q = torch.empty(self.count * self.pw, dtype=torch.int32, device="cuda:0")
         self.D.copy_(self._dev(d))
@@ -1226,8 +1673,15 @@ class GpuBackend:
         return staged
 
     def op_write(self, op, pay, staged=None):
-        writes, k = op["writes"], self.k
+        k = self.k
         new, old = staged or self._stage(op, pay)
+        if op["form"] == "pool":  # the caller stores the run's data blocks itself, on the call's stream; fastecc_encode_pool writes their parity
+            D, Q = self._pool(op["b0"])
+            cnt, lib = op["b1"] - op["b0"], self._lib()
+            with self.torch.cuda.stream(self.streams[self.cur]):
+                D[:cnt * self.dw].copy_(new)
+            return {"code": self._code(self.enc.encode_pool, D, Q, cnt, stream=lib)}
+        writes = op["writes"]
         if op["form"] == "batch":
             return {"code": self._code(self.enc.update_batch, self.D, self.Q, self.count, writes, new, stream=self._lib())}
         if op["form"] == "single":
@@ -1243,14 +1697,74 @@ class GpuBackend:
     def op_burst(self, op, pay):
         """every block uploaded first, then the calls enqueued back to back, each on its stream, with event waits between streams and no
         synchronisation: the next call meets the previous one's list and buffers still in flight"""
-        staged = [self._stage(sub, pz) if sub["op"] == "write" else None for sub, pz in zip(op["ops"], pay["subs"])]
-        cur, codes = self.cur, []
+        staged = [self._stage(sub, pz) if sub["op"] == "write" else self._read_buffer(len(sub["reads"]), sub["width"]) if sub["op"] == "read" else None
+                  for sub, pz in zip(op["ops"], pay["subs"])]
+        cur, codes, reads = self.cur, [], []
         for sub, pz, st in zip(op["ops"], pay["subs"], staged):
             self.cur = sub["stream"]
-            out = self.op_write(sub, pz, st) if sub["op"] == "write" else self.run_sub(sub, pz)
+            if sub["op"] == "read":  # enqueued like the rest; its output is read back after the burst
+                out = {"code": self._read_call(sub, self.D, self.Q, self.count, sub["reads"], sub.get("pattern_of"), st)}
+                reads.append((st, len(sub["reads"]), sub["width"]))
+            else:
+                out = self.op_write(sub, pz, st) if sub["op"] == "write" else self.run_sub(sub, pz)
             codes.append(out["code"])
         self.cur = cur
-        return {"code": OK, "codes": codes}
+        out = {"code": OK, "codes": codes}
+        if reads:
+            got = [self._read_back(OK, *r) for r in reads]
+            out["rows"] = np.concatenate([g["rows"].reshape(-1) for g in got])
+            out["guard"] = np.concatenate([g["guard"] for g in got])
+        return out
+
+    # -- degraded reads: the output is (n_reads + 1) rows preset to CANARY on the null stream; the call runs on the sequence's stream
+    def _read_buffer(self, n, width):
+        self._order(0)
+        out = self._dev(canary_rows(n + 1, width))
+        self.keep.append(out)
+        return out
+
+    def _read_call(self, op, D, Q, count, reads, pattern_of, out):
+        """fastecc_read_batch_set (pattern_of given) or fastecc_read_batch: the code; nothing is read back here"""
+        if pattern_of is not None:
+            po = np.array(pattern_of, dtype=np.uint32)
+            code = self._code(self.enc.read_batch_set, D, Q, count, po, reads, out, col0=op["col0"], width=op["width"], stream=self._lib())
+            po[:] = 0xFFFFFFFE  # pattern_of may be reused as soon as the call returns
+            return code
+        return self._code(self.enc.read_batch, D, Q, count, reads, out, col0=op["col0"], width=op["width"], stream=self._lib())
+
+    def _read_back(self, code, out, n, width):
+        self._order(0)
+        host = self._host(out).reshape(n + 1, width)
+        return {"code": code, "rows": host[:n], "guard": host[n]}
+
+    def op_read(self, op, pay):
+        out = self._read_buffer(len(op["reads"]), op["width"])
+        code = self._read_call(op, self.D, self.Q, self.count, op["reads"], op.get("pattern_of") if op["set"] else None, out)
+        return self._read_back(code, out, len(op["reads"]), op["width"])
+
+    def op_probe_read(self, op, pay):
+        sd, sq = self._scratch(pay["scratch_d"], pay["scratch_p"])
+        out = self._read_buffer(len(op["reads"]), op["width"])
+        code = self._read_call(op, sd, sq, 1, op["reads"], [op["q"]] if op["set"] else None, out)
+        return self._read_back(code, out, len(op["reads"]), op["width"])
+
+    def op_probe_read_swap(self, op, pay):
+        """the two scratch stripes and both outputs first; then decode_prepare_set, a read on the side stream, decode_prepare_set again with
+        nothing synchronised here (the library waits for the read itself), a read on the sequence's stream; read back at the end"""
+        self._order(0)
+        for s, (d, p) in enumerate(pay["scratch"]):
+            self.sd[s * self.dw:][:self.dw].copy_(self._dev(d))
+            self.sq[s * self.pw:][:self.pw].copy_(self._dev(p))
+        outs = [self._read_buffer(len(half["reads"]), half["width"]) for half in op["halves"]]
+        cur, codes = self.cur, []
+        for s, (half, out) in enumerate(zip(op["halves"], outs)):
+            codes.append(self._code(self.enc.decode_prepare_set, *self._flag_rows(half["patterns"])))
+            self.cur = 1 if s == 0 else cur
+            codes.append(self._read_call(half, self.sd[s * self.dw:], self.sq[s * self.pw:], 1, half["reads"], [half["q"]], out))
+        self.cur = cur
+        got = [self._read_back(OK, out, len(half["reads"]), half["width"]) for half, out in zip(op["halves"], outs)]
+        return {"code": OK, "codes": codes, "rows": np.concatenate([g["rows"].reshape(-1) for g in got]),
+                "guard": np.concatenate([g["guard"] for g in got])}
 
     def run_sub(self, sub, pz):
         return getattr(self, "op_" + sub["op"])(sub, pz)
@@ -1305,7 +1819,11 @@ class GpuBackend:
     def op_locate(self, op, pay):
         D, Q = self._pool(op["b0"])
         try:
-            status, lists = self.enc.locate_errors_batch(D, Q, op["b1"] - op["b0"], seed=op["seed"], stream=self._lib())
+            if op.get("set"):
+                po = np.array(op["pattern_of"], dtype=np.uint32)
+                status, lists = self.enc.locate_errors_batch_set(D, Q, op["b1"] - op["b0"], po, seed=op["seed"], stream=self._lib())
+            else:
+                status, lists = self.enc.locate_errors_batch(D, Q, op["b1"] - op["b0"], seed=op["seed"], stream=self._lib())
         except self.fe.FastEccError as e:
             return {"code": e.code, "status": getattr(e, "status", None), "lists": getattr(e, "lists", None)}
         status = status.tolist()
@@ -1336,7 +1854,9 @@ class GpuBackend:
     def op_reencode(self, op, pay):
         D, _ = self._pool(op["b0"])
         cnt = op["b1"] - op["b0"]
-        if op["form"] == "batch":
+        if op["form"] == "pool":
+            code = self._code(self.enc.encode_pool, D, self.sq, cnt, stream=self._lib())
+        elif op["form"] == "batch":
             code = self._code(self.enc.encode_batch, D, self.sq, cnt, stream=self._lib())
         else:
             code = self._code(self.enc.encode, D, self.sq, stream=self._lib())
@@ -1380,6 +1900,18 @@ class GpuBackend:
 
     def op_refused(self, op, pay):
         D, Q, lib, h = self.D, self.Q, self.fe.lib(), self.enc._h
+        if op["which"] == "bad_read":
+            n, rotated = len(op["reads"]), self.cfg.placement == "rotated"
+            outs = [self._read_buffer(n, op["width"]) for _ in range(2)]
+            bad = list(op["reads"])
+            bad[op["at"]] = self.count * self.k  # one past the pool's last block, among valid requests
+            po = [b % self.n if b not in self.quarantined else PATTERN_NONE for b in range(self.count)]
+            codes = [self._read_call(op, D, Q, self.count, bad, po if rotated else None, outs[0])]
+            po = [PATTERN_NONE] * self.count
+            po[op["reads"][op["at"]] // self.k] = op["entry"]  # the number of patterns in force: one past the last
+            codes.append(self._read_call(op, D, Q, self.count, op["reads"], po, outs[1]))
+            self._order(0)
+            return {"code": codes[0], "codes": codes, "rows": np.concatenate([self._host(o) for o in outs])}
         if op["which"] == "bad_write":
             new = self._dev(np.zeros(2 * self.S, np.uint32))
             self.keep.append(new)

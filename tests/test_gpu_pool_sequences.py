@@ -2,10 +2,12 @@
 
 Writes (fastecc_update_batch, _update_parity_batch, fastecc_update), silent corruption, devices going down and coming back, verify, locate,
 correct, repair, decode, re-encode, option and stream flips, sub-range calls and the state probes of pool_model's docstring follow one another
-as the generator draws them; after every step every host output equals the model's prediction and the whole pool, data and parity, quarantined
-stripes included, equals the model's mirror bit for bit.  The model's parity is the oracle's; no comparison here uses the library as its own
+as the generator draws them — in the extended sequences (the seeds pool_model.EXT_SEEDS) degraded reads (fastecc_read_batch, _read_batch_set)
+alone and inside bursts, location under the pattern set (fastecc_locate_errors_batch_set) and whole-stripe writes and re-encodes
+(fastecc_encode_pool under every "encode_pool_kernel") as well; after every step every host output equals the model's prediction and the
+whole pool, data and parity, quarantined stripes included, equals the model's mirror bit for bit.  The model's parity is the oracle's; no comparison here uses the library as its own
 reference, and none has a tolerance.  A failure names the configuration, the seed, the step and the operations so far;
-pool_model.run_sequence(backend, config, seed, steps=N) replays the prefix."""
+pool_model.run_sequence(backend, config, seed, steps=N) replays the prefix (with extended=True for an extended sequence: the message says so)."""
 import pytest
 
 import pool_model as pm
@@ -27,14 +29,15 @@ def fe(hip_lib):
 
 
 CASES = [(cfg.name, seed) for cfg in pm.CONFIGS for seed in pm.SEEDS]
+EXT_CASES = [(cfg.name, seed) for cfg in pm.CONFIGS for seed in pm.EXT_SEEDS]
 
 
-@pytest.mark.parametrize("name,seed", CASES)
+@pytest.mark.parametrize("name,seed", CASES + EXT_CASES)
 def test_sequence(torch_cuda, fe, oracle, name, seed):
     cfg = pm.config_named(name)
     backend = pm.GpuBackend(fe, torch_cuda, cfg)
     try:
-        pm.run_sequence(backend, cfg, seed, oracle=oracle)
+        pm.run_sequence(backend, cfg, seed, oracle=oracle, extended=seed in pm.EXT_SEEDS)
     finally:
         backend.close()
 
@@ -65,3 +68,23 @@ def test_batched_kernels_ran(torch_cuda, fe, oracle):
     assert not missing, (missing, sorted(seen))
     assert "direct_pass_batch" in seen or "direct_pass_list" in seen, sorted(seen)
     assert free_direct, "only the steps that asked for mode 2 ran a direct pass"
+
+
+EXTENDED_SCOPES = ("direct_read", "direct_read_set", "fingerprint_set_list", "encode_pool_valu", "encode_pool_mfma")
+
+
+def test_extended_kernels_ran(torch_cuda, fe, oracle):
+    """One long extended sequence per placement with profiling on: the read kernel ran in both forms, the set location ran its list pass, and the
+    pool encode ran as one launch under both kernels (an even block of 64 words: the matrix-core kernel can run)."""
+    seen = set()
+    for name in ("20_16_s64_fixed", "20_16_s64_rotated"):
+        cfg = pm.config_named(name)
+        backend = pm.GpuBackend(fe, torch_cuda, cfg, profile=True)
+        try:
+            pm.run_sequence(backend, cfg, 11, steps=LONG_STEPS, oracle=oracle, extended=True)
+        finally:
+            backend.close()
+        for names in backend.scopes.values():
+            seen |= names
+    missing = [x for x in EXTENDED_SCOPES if x not in seen]
+    assert not missing, (missing, sorted(seen))

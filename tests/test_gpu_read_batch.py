@@ -270,6 +270,32 @@ def test_read_batch_unprepared_and_transform_path(torch_cuda, fe):
         assert bool((out == 0).all())  # (the all-zero codeword)
 
 
+@pytest.mark.parametrize("n,k,flags", [(20, 16, 0), (64, 32, 0), (72, 48, 1)], ids=["20_16", "64_32", "72_48_mixed"])
+def test_read_batch_under_a_pattern_that_lost_nothing(torch_cuda, fe, n, k, flags):
+    """A healthy pool with fixed placement: decode_prepare with every block present, then fastecc_read_batch.  "A pattern with no lost data block
+    is valid: every request is then a copy" (include/fastecc.h) — also the pattern that lost nothing at all, which has tables on neither path,
+    so whatever "decode_direct_max" was when it was prepared.  (Found by the pool sequences of tests/pool_model.py: the call was refused
+    FASTECC_E_UNSUPPORTED.)  The words are copied as stored, words >= p included."""
+    torch = torch_cuda
+    S, count = 20, 5
+    with fe.Encoder(n, k, 4 * S, flags=flags) as enc:
+        D = garbage(torch, (count, k, S), 7)
+        Q = garbage(torch, (count, n - k, S), 8)
+        D0, Q0 = D.clone(), Q.clone()
+        reads = np.array([0, count * k - 1, k + 3, k + 3, 2], dtype=np.uint64)
+        idx = torch.tensor(reads.astype(np.int64), device="cuda:0")
+        for direct_max in (256, 0):
+            enc.set_option("decode_direct_max", direct_max)
+            enc.decode_prepare(np.ones(k, np.uint8), np.ones(n - k, np.uint8))
+            for col0, width in ((0, S), (3, 5), (S - 1, 1)):
+                out = torch.full((len(reads) + 1, width), CANARY, dtype=torch.int32, device="cuda:0")
+                assert raw(fe, enc, False, D, Q, count, None, reads, len(reads), col0, width, out) == fe.OK, (direct_max, col0, width)
+                torch.cuda.synchronize()
+                assert torch.equal(out[:-1], D0.view(-1, S)[idx, col0:col0 + width]), (direct_max, col0, width)
+                assert bool((out[-1] == CANARY).all())
+        assert torch.equal(D, D0) and torch.equal(Q, Q0), "the pool is not written"
+
+
 # ---- 6. one launch, whatever the classes ----
 def test_one_launch_and_bytes(torch_cuda, fe):
     torch = torch_cuda

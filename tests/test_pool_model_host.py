@@ -2,10 +2,14 @@
 
   - the model is sound: its parity equals the generator matrix of fastecc_code_coefficient (host-only arithmetic of the library, the one
     thing here that is not the oracle), and decoding its truth under every device-down pattern gives the truth back;
-  - every (config, seed) of tests/test_gpu_pool_sequences.py runs green on the exact numpy backend;
-  - seven injected defects are each reported at the step where they first change a byte or an answer;
+  - every (config, seed) of tests/test_gpu_pool_sequences.py runs green on the exact numpy backend, the extended sequences (EXT_SEEDS) included;
+  - the 64 sequences of SEEDS are, operation for operation, what they were before the extended kinds existed (recorded digests);
+  - seven injected defects, and seven more in the extended operations, are each reported at the step where they first change a byte or an answer;
   - the committed seeds of every configuration cover what they must (operation kinds, variants, state probes, few illegal draws, the budget)."""
+import hashlib
 import itertools
+import json
+import os
 
 import numpy as np
 import pytest
@@ -16,6 +20,7 @@ from pool_model import P
 
 FIXED = [c for c in pm.CONFIGS if c.placement == "fixed"]
 CASES = [(cfg.name, seed) for cfg in pm.CONFIGS for seed in pm.SEEDS]
+EXT_CASES = [(cfg.name, seed) for cfg in pm.CONFIGS for seed in pm.EXT_SEEDS]
 
 
 def group_of(cfg):
@@ -114,18 +119,34 @@ def test_truth_decodes_under_every_device_down_pattern(oracle, generator_matrix,
         assert np.array_equal(got, d), lost
 
 
-_DRY = {}
+_DRY, _LOGS = {}, {}
 
 
 def dry_run(oracle, name, seed):
-    """the sequence of (name, seed) on the exact backend, once per session: its Coverage"""
+    """the sequence of (name, seed) on the exact backend, once per session: its Coverage (the seeds of EXT_SEEDS are the extended sequences)"""
     if (name, seed) not in _DRY:
         cfg = pm.config_named(name)
-        _DRY[name, seed] = pm.run_sequence(pm.ModelBackend(cfg, oracle), cfg, seed, oracle=oracle)
+        _LOGS[name, seed] = []
+        _DRY[name, seed] = pm.run_sequence(pm.ModelBackend(cfg, oracle), cfg, seed, oracle=oracle, extended=seed in pm.EXT_SEEDS, log=_LOGS[name, seed])
     return _DRY[name, seed]
 
 
-@pytest.mark.parametrize("name,seed", CASES)
+def test_the_committed_sequences_are_unchanged(oracle):
+    """tests/golden/pool_sequence_digests.json: sha256 of the operation log (run_sequence's JSON lines, joined by newlines) of every (config, seed)
+    of SEEDS, recorded on the commit before the generator learned the extended kinds.  With `extended` off it draws what it drew then."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pool_sequence_digests.json")) as f:
+        recorded = json.load(f)
+    assert sorted(recorded) == sorted("%s:%d" % c for c in CASES)
+    changed = []
+    for name, seed in CASES:
+        dry_run(oracle, name, seed)
+        assert len(_LOGS[name, seed]) == pm.config_named(name).steps
+        if hashlib.sha256("\n".join(_LOGS[name, seed]).encode()).hexdigest() != recorded["%s:%d" % (name, seed)]:
+            changed.append((name, seed))
+    assert not changed
+
+
+@pytest.mark.parametrize("name,seed", CASES + EXT_CASES)
 def test_harness_passes_on_the_exact_backend(oracle, name, seed):
     cfg = pm.config_named(name)
     cov = dry_run(oracle, name, seed)
@@ -160,6 +181,33 @@ def test_coverage_of_the_committed_seeds(oracle, group):
     assert not {x: total.probes[x] for x in probes if total.probes[x] < 2}
 
 
+NEW_PROBES = ["prepared_after_read", "set_after_read", "scrub_after_read", "read_after_prepare", "read_after_prepare_set", "refused_bad_read"]
+
+
+@pytest.mark.parametrize("group", GROUPS)
+def test_coverage_of_the_extended_seeds(oracle, group):
+    """What the two extended seeds of a configuration's two placements must meet between them (counted on the model, as above)."""
+    cfgs = [c for c in pm.CONFIGS if group_of(c) == group]
+    total, fixed = pm.Coverage(None), pm.Coverage(None)
+    for cfg in cfgs:
+        for seed in pm.EXT_SEEDS:
+            total.merge(dry_run(oracle, cfg.name, seed))
+            if cfg.placement == "fixed":
+                fixed.merge(dry_run(oracle, cfg.name, seed))
+    mixed = bool(cfgs[0].flags)
+    kinds = ["read", "write_pool", "reencode_pool", "locate"]  # the new kind, the new forms, and locate now on both placements
+    assert not {x: total.kinds[x] for x in kinds if total.kinds[x] < 5}
+    probes = [x for x in NEW_PROBES if not (mixed and x.startswith("scrub_"))] + ([] if mixed else ["prepared_after_locate"])
+    assert not {x: total.probes[x] for x in probes if total.probes[x] < 2}
+    variants = ["read_set", "read_single", "read_mixed_list", "read_pattern_none", "read_parity_only", "read_side_stream", "read_in_two_stream_burst",
+                "locate_set", "write_pool_subrange", "reencode_pool_kernel_0", "reencode_pool_kernel_1", "reencode_pool_kernel_2",
+                "read_after_prepare_plain", "read_after_prepare_transform", "read_after_prepare_parity"]
+    variants += ["window_" + x for x in pm.WINDOWS]
+    assert not [x for x in variants if not total.variants[x]]
+    if group == "256_128":  # the single form serves up to 256 lost blocks, a set at most 16 per pattern
+        assert fixed.variants["read_single_over_16_lost"]
+
+
 def test_sequences_are_deterministic_and_replayable(oracle):
     cfg = pm.config_named("20_16_s64_rotated")
     logs = []
@@ -184,8 +232,14 @@ def test_the_prepared_pattern_is_unspecified_after_correct(oracle):
         model.payload(probe)
     with pytest.raises(pm.ModelError):
         model.apply({"op": "repair", "set": False, "b0": 0, "b1": 2, "kernel": 0}, {})
+    read = {"op": "read", "set": False, "reads": [0, 17], "col0": 0, "width": cfg.S, "shape": "whole"}
+    with pytest.raises(pm.ModelError):
+        model.apply(read, {})  # fastecc_read_batch reads the single prepared pattern too
+    with pytest.raises(pm.ModelError):
+        model.payload({"op": "probe_read", "set": False, "q": 0, "b": 0, "reads": [1], "col0": 0, "width": 1, "shape": "word", "dseed": 2})
     model.apply({"op": "prepare", "lost": []}, {})
     model.apply({"op": "repair", "set": False, "b0": 0, "b1": 2, "kernel": 0}, {})
+    assert model.apply(read, {})["code"] == pm.OK
 
 
 # ---- injected defects: each a ModelBackend that is wrong in one way; `fired` is the step at which the defect first changed a byte of the
@@ -231,7 +285,7 @@ class TouchesAnotherStripe(Defective):
 
     def op_write(self, op, pay):
         super().op_write(op, pay)
-        touched = {w // self.k for w in op["writes"]}
+        touched = {w // self.k for w in pm.writes_of(op, self.k)}
         others = [b for b in range(self.count) if b not in touched]
         if op["form"] == "batch" and others:
             self.p[others[len(others) // 2], 0, 0] ^= np.uint32(1)
@@ -299,18 +353,109 @@ class StaleChunking(Defective):
         return out
 
 
+# ---- defects in the extended operations ----
+class CopiesLostBlocks(Defective):
+    """a read returns what the pool holds for a lost block: a copy instead of a rebuild"""
+
+    def read_rows(self, d, td, reads, lost_of, col0, width):
+        return super().read_rows(d, td, reads, lambda b: (), col0, width)
+
+
+class ReadsUnderTheOldPattern(Defective):
+    """fastecc_read_batch keeps using the pattern that was prepared before the last decode_prepare (a stale descriptor)"""
+    before = None
+
+    def op_prepare(self, op, pay):
+        self.before = self.prepared
+        return super().op_prepare(op, pay)
+
+    def single_pattern(self):
+        return self.prepared if self.before is None else self.before
+
+
+class ReadWritesPastItsRows(Defective):
+    """a read writes one row past n_reads"""
+
+    def read_rows(self, d, td, reads, lost_of, col0, width):
+        out = super().read_rows(d, td, reads, lost_of, col0, width)
+        out[len(reads)] = out[0]
+        return out
+
+
+class ReadWritesThePool(Defective):
+    """a read writes a word into the pool"""
+
+    def op_read(self, op, pay):
+        out = super().op_read(op, pay)
+        b, i = divmod(op["reads"][0], self.k)
+        self.d[b, i, op["col0"]] ^= np.uint32(1)
+        return out
+
+
+class ShiftedSetLocation(Defective):
+    """fastecc_locate_errors_batch_set answers stripe b under pattern pattern_of[b + 1]"""
+
+    def op_locate(self, op, pay):
+        if op.get("set"):
+            po = op["pattern_of"]
+            nxt = [po[i + 1] if i + 1 < len(po) and pm.PATTERN_NONE not in (po[i], po[i + 1]) else po[i] for i in range(len(po))]
+            op = dict(op, pattern_of=nxt)
+        return super().op_locate(op, pay)
+
+
+class PoolEncodeSkipsTheLastStripe(Defective):
+    """fastecc_encode_pool leaves the last stripe of a sub-range unencoded"""
+
+    def encoded_stripes(self, op, stripes):
+        return stripes[:-1] if op["form"] == "pool" else stripes
+
+    def op_reencode(self, op, pay):
+        out = super().op_reencode(op, pay)
+        if op["form"] == "pool":
+            out["parity"][-1] = 0  # (what the scratch parity held)
+        return out
+
+
+class BurstReadSeesTheOldPool(Defective):
+    """a read inside a burst sees the pool as it was before the preceding write of the burst"""
+
+    def op_burst(self, op, pay):
+        ops = op["ops"]
+        real_run = self.run
+
+        def run(sub, pz):
+            at = next(i for i, x in enumerate(ops) if x is sub)
+            if sub["op"] == "write":
+                self.old = self.d.copy()
+            if sub["op"] == "read" and at > 0 and ops[at - 1]["op"] == "write":
+                now, self.d = self.d, self.old
+                try:
+                    return real_run(sub, pz)
+                finally:
+                    self.d = now
+            return real_run(sub, pz)
+        self.run = run
+        try:
+            return super().op_burst(op, pay)
+        finally:
+            del self.run
+
+
+EXT_DEFECTS = [CopiesLostBlocks, ReadsUnderTheOldPattern, ReadWritesPastItsRows, ReadWritesThePool, ShiftedSetLocation, PoolEncodeSkipsTheLastStripe,
+               BurstReadSeesTheOldPool]
 DEFECTS = [SkipsAParityBlock, TouchesAnotherStripe, ShiftedPatterns, RewritesAbsentBlocks, ReadsQuarantined, SetClobbersPrepared, StaleChunking]
 DEFECT_CONFIGS = ("20_16_s64_fixed", "20_16_s64_rotated", "64_32_rotated", "32_8_fixed")
 
 
-@pytest.mark.parametrize("defect", DEFECTS, ids=[d.__name__ for d in DEFECTS])
+@pytest.mark.parametrize("defect", DEFECTS + EXT_DEFECTS, ids=[d.__name__ for d in DEFECTS + EXT_DEFECTS])
 def test_injected_defect_is_reported_at_its_step(oracle, defect):
     caught = 0
-    for name, seed in itertools.product(DEFECT_CONFIGS, pm.SEEDS):
+    extended = defect in EXT_DEFECTS  # a defect of the extended operations is looked for in the extended sequences
+    for name, seed in itertools.product(DEFECT_CONFIGS, pm.EXT_SEEDS if extended else pm.SEEDS):
         cfg = pm.config_named(name)
         backend = defect(cfg, oracle)
         try:
-            pm.run_sequence(backend, cfg, seed, oracle=oracle)
+            pm.run_sequence(backend, cfg, seed, oracle=oracle, extended=extended)
         except pm.SequenceFailure as e:
             assert backend.fired == e.step, (name, seed, backend.fired, e.step)
             text = str(e)
