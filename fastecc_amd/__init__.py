@@ -616,6 +616,10 @@ class Encoder:
 
     @staticmethod
     def _block_list(blocks):
+        """(entries, uint64 pointer or array) of a list of block or stripe indices"""
+        import numpy as np
+        if isinstance(blocks, np.ndarray) and blocks.dtype == np.uint64 and blocks.ndim == 1 and blocks.flags["C_CONTIGUOUS"] and len(blocks):
+            return len(blocks), blocks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))  # goes through as it is (the pointer keeps the array alive)
         idx = [int(b) for b in blocks]
         return len(idx), (ctypes.c_uint64 * max(len(idx), 1))(*idx)
 

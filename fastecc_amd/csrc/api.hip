@@ -200,8 +200,7 @@ int fastecc_encode_batch(fastecc_ctx* c, const void* data, void* parity, uint64_
     DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
     CallLock lk(c->mu);
-    return run_passes(c, c->encode_plan, (const uint32_t*)data, (uint32_t*)parity, twiddle_table(c, TW_ENC_DIF, (hipStream_t)stream), twiddle_table(c, TW_ENC_DIT, (hipStream_t)stream), (hipStream_t)stream, 0, 0,
-                      nullptr, (uint32_t)count);
+    return encode_batch_passes(c, (const uint32_t*)data, (uint32_t*)parity, count, (hipStream_t)stream);
 }
 
 int fastecc_encode_pool(fastecc_ctx* c, const void* data, void* parity, uint64_t count, void* stream)
@@ -285,6 +284,9 @@ int fastecc_scale_blocks(fastecc_ctx* c, void* data, uint32_t scale, uint32_t ba
     if (!dg.ok) return FASTECC_E_DEVICE;
     if (mem_kind != FASTECC_MEM_HOST && mem_kind != FASTECC_MEM_DEVICE) return FASTECC_E_INVAL;
     hipStream_t st = (hipStream_t)stream;
+    // one launch over the stripe: within a dispatch, or refused before any device work (a host stripe is scaled in the context's aligned copy)
+    const void* where = mem_kind == FASTECC_MEM_DEVICE ? data : nullptr;
+    if (!wave_launch_fits(rows_waves((uint32_t)c->S, pick_vec(c, where, where), c->N))) return FASTECC_E_UNSUPPORTED;
     std::vector<uint32_t> f(c->N);
     uint32_t cur = scale;
     for (uint64_t i = 0; i < c->N; i++) {

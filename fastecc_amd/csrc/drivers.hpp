@@ -7,6 +7,7 @@
 #include <thread>
 
 #include "context.hpp"
+#include "launch_limits.hpp"
 
 namespace fastecc {
 
@@ -69,6 +70,10 @@ struct P61Hooks {
 int run_passes(fastecc_ctx* c, const std::vector<Pass>& plan, const uint32_t* in, uint32_t* out, const uint32_t* tw_dif,
                const uint32_t* tw_dit, hipStream_t st, uint32_t col0 = 0, uint32_t width = 0, hipEvent_t first_done = nullptr,
                uint32_t batch = 1, const CallBounds& cb = CallBounds());
+// The encode plan of a (2k,k) power-of-two code over `count` stripes back to back (k blocks apart in both buffers), cut into runs of stripes so that
+// no pass of a run takes more than MAX_LAUNCH_WAVES waves (a stripe of more waves than that is a run of its own).  FASTECC_E_UNSUPPORTED, before any
+// device work, when a pass of one stripe does not fit a dispatch (run_passes).
+int encode_batch_passes(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, uint64_t count, hipStream_t st);
 int ensure_slab_streams(fastecc_ctx* c);
 bool plan_is_all_tiles(const std::vector<Pass>& plan);
 int encode_pow2(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStream_t st, const CallBounds& cb = CallBounds());

@@ -37,6 +37,21 @@ int run_passes(fastecc_ctx* c, const std::vector<Pass>& plan, const uint32_t* in
     if (cb.final_out) vec = std::min(vec, pick_vec(c, cb.final_out + col0, cb.final_out + col0));
     if (cb.gather_odd) vec = std::min(vec, pick_vec(c, cb.gather_odd + col0, cb.gather_odd + col0));
 
+    // Every launch of the plan within one dispatch (launch_limits.hpp), or nothing is launched: a stripe cannot be cut, and a refusal between two
+    // passes would leave it half transformed.  (tile_kernels.hip's launcher checks its 32-bit tile index only; this is launch_tile's only caller.)
+    for (const Pass& p : plan) {
+        if (p.fused) continue;
+        const int n_eff = folded && p.mode == MODE_DIT ? c->n - c->fold : c->n;
+        const uint64_t stripes = batch > 1 ? batch : 1u;
+        if (!p.tile) {
+            if (!wave_launch_fits(pass_stripe_waves(p.logr, vec, width, n_eff) * stripes)) return FASTECC_E_UNSUPPORTED;
+            continue;
+        }
+        uint64_t tiles = tile_stripe_tiles(p.logr, p.pair, width, n_eff) * stripes;
+        if (cb.rows_factor && cb.groups && &p == &plan.front() && p.mode == MODE_DIF) tiles = (uint64_t)cb.groups * tile_stripe_tiles(p.logr, p.pair, width, p.logr);
+        if (!tile_launch_fits(tiles, p.logr, p.pair, p.rlog, p.mode == MODE_DIF || p.mode == MODE_DIT, c->split2, p.wide, c->persistent ? c->cus : 0)) return FASTECC_E_UNSUPPORTED;
+    }
+
     auto run_one = [&](const Pass& p, const uint32_t* src, uint32_t* dst, const uint32_t* dscale, bool last = false) -> int {
         const uint32_t in_rows = src == in ? cb.in_rows : 0;
         uint32_t out_rows = 0;
@@ -328,6 +343,25 @@ int encode_device(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, hipStr
     return encode_pow2(c, data, out, st, cb);
 }
 
+int encode_batch_passes(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, uint64_t count, hipStream_t st)
+{
+    // the waves one stripe takes in its largest pass (the lane vector of every run is the whole batch's: a stripe is a multiple of vec words long)
+    const int vec = pick_vec(c, data, parity);
+    uint64_t stripe_waves = 0;
+    for (const Pass& p : c->encode_plan) {
+        if (p.fused) continue;
+        stripe_waves = std::max(stripe_waves, p.tile ? tile_stripe_waves(p.logr, p.pair, p.rlog, (uint32_t)c->S, c->n) : pass_stripe_waves(p.logr, vec, (uint32_t)c->S, c->n));
+    }
+    if (stripe_waves == 0) return FASTECC_E_UNSUPPORTED;
+    // (a stripe of more waves than a run holds goes alone: run_passes refuses it, before any device work, only if it does not fit a dispatch)
+    const uint64_t run = std::max<uint64_t>(1, MAX_LAUNCH_WAVES / stripe_waves), stride = c->N * c->ld;
+    const uint32_t* tw_dif = twiddle_table(c, TW_ENC_DIF, st);
+    const uint32_t* tw_dit = twiddle_table(c, TW_ENC_DIT, st);
+    for (uint64_t b0 = 0; b0 < count; b0 += run)
+        RC_TRY(run_passes(c, c->encode_plan, data + b0 * stride, parity + b0 * stride, tw_dif, tw_dit, st, 0, 0, nullptr, (uint32_t)std::min(run, count - b0)));
+    return FASTECC_OK;
+}
+
 // n - k from which mode 0 of fastecc_encode_pool prefers the matrix-core kernel to the VALU one: the smallest measured n - k at which it won — 4, by
 // 1.10 x; 1.21 x at 8, 1.78 x at 16, 1.94 x at 32 (profiles/r07/encode_pool_bench.jsonl).  Fewer parity blocks were not measured.
 constexpr uint64_t POOL_MFMA_MIN_OUTPUTS = 4;
@@ -374,7 +408,7 @@ int encode_pool_device(fastecc_ctx* c, const uint32_t* data, uint32_t* parity, u
     }
     // n = 2k = 2^m: every pass once over the whole pool (the parity stride is the data stride); 32-bit block indices
     if (c->q == 1 && c->fold == 0 && c->cosets == 1 && c->K == c->N && c->Mu == c->M && count <= 0xFFFFFFFFull && count * c->N <= 0x7FFFFFFFull)
-        return run_passes(c, c->encode_plan, data, parity, twiddle_table(c, TW_ENC_DIF, st), twiddle_table(c, TW_ENC_DIT, st), st, 0, 0, nullptr, (uint32_t)count);
+        return encode_batch_passes(c, data, parity, count, st);
     return stripe_by_stripe();
 }
 
@@ -428,6 +462,7 @@ int ntt_device(fastecc_ctx* c, uint32_t* data, bool inverse, hipStream_t st)
         P61Hooks hk(c);
         return p61::ntt(c->p61, (uint64_t*)data, inverse, st, c->profiling ? &hk.h : nullptr);
     }
+    if (c->n >= 2 && !wave_launch_fits(rows_waves((uint32_t)c->S, pick_vec(c, data, data), c->N))) return FASTECC_E_UNSUPPORTED;  // (the bit reversal: before the passes)
     const uint32_t* tw = inverse ? twiddle_table(c, TW_NTT_INV, st) : twiddle_table(c, TW_NTT_FWD, st);
     int rc = run_passes(c, c->ntt_plan, data, data, tw, tw, st);
     if (rc != FASTECC_OK) return rc;

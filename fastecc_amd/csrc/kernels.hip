@@ -22,6 +22,7 @@
 
 #include "gf.hpp"
 #include "kernels.hpp"
+#include "launch_limits.hpp"
 #include "ntt_device.hpp"
 
 namespace fastecc {
@@ -242,9 +243,8 @@ hipError_t launch_pass(int logr, int vec, int mode, PassArgs a, hipStream_t st)
 {
     a.col_chunks = (a.S + 64u * vec - 1u) / (64u * vec);
     a.items = ((uint64_t)a.col_chunks * (a.batch > 1 ? a.batch : 1u)) << (a.n - logr);
-    const uint64_t blocks = (a.items + 3u) / 4u;
-    if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)blocks);
+    if (!wave_launch_fits(a.items)) return hipErrorInvalidValue;  // (one wave per item; run_passes has refused it before any device work)
+    const dim3 grid((unsigned)((a.items + 3u) / 4u));
     switch (vec) {
         case 1: return launch_pass_v<1>(logr, mode, a, grid, st);
         case 2: return launch_pass_v<2>(logr, mode, a, grid, st);
@@ -257,6 +257,7 @@ hipError_t launch_bitrev_rows(uint32_t* data, uint32_t S, int n, int vec, hipStr
 {
     const uint32_t col_chunks = (S + 64u * vec - 1u) / (64u * vec);
     const uint64_t items = (uint64_t)col_chunks << n;
+    if (!wave_launch_fits(items)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((items + 3u) / 4u));
     switch (vec) {
         case 1: hipLaunchKernelGGL((bitrev_rows_kernel<1>), grid, dim3(256), 0, st, data, S, n, col_chunks, items); break;
@@ -270,6 +271,7 @@ hipError_t launch_scale_rows(uint32_t* data, const uint32_t* factor, uint32_t S,
 {
     const uint32_t col_chunks = (S + 64u * vec - 1u) / (64u * vec);
     const uint64_t items = (uint64_t)col_chunks * rows;
+    if (!wave_launch_fits(items)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((items + 3u) / 4u));
     switch (vec) {
         case 1: hipLaunchKernelGGL((scale_rows_kernel<1>), grid, dim3(256), 0, st, data, factor, S, col_chunks, items); break;

@@ -158,6 +158,9 @@ void fastecc_destroy(fastecc_ctx *ctx);
  *          synchronise — not even the first call on a context: its twiddle tables are written by a kernel on `stream` in front of the
  *          first pass (a use on another stream later waits for that kernel on the device), so calls may be captured into a hipGraph.  FASTECC_MEM_HOST: pointers are host memory; the call stages through HBM and
  *          returns when `parity` is complete.
+ * A stripe is not cut into several launches, and a dispatch holds fewer than 2^32 work-items.  A transform pass takes one wave (64 work-items) per
+ * 64-word piece of a block (256-word where rows are 16-byte aligned) and group of 2 to 32 blocks, so only stripes of tens of GiB come near that;
+ * one that would need more in a pass is refused with FASTECC_E_UNSUPPORTED — by the power-of-two GF(0xFFF00001) codes before any device work.
  */
 int fastecc_encode(fastecc_ctx *ctx, const void *data, void *parity, int mem_kind, void *stream);
 
@@ -237,6 +240,9 @@ int fastecc_shard_info(const fastecc_ctx *ctx, int *n_slabs, uint64_t *slab_bloc
  * fastecc_encode calls; meant for small codes — a (256,128) x 4 KB stripe is 1 MiB and a single launch of it is
  * launch-bound, a batch of them runs at the rate of the large stripes.  n = 2k = 2^m over GF(0xFFF00001) only;
  * parity == data encodes in place; enqueued on `stream` without synchronising.
+ * A dispatch holds fewer than 2^32 work-items, so a batch whose passes would take more than 2^24 waves is cut into runs of stripes, each
+ * run one launch per pass (a (4,2) x 4 B batch: runs of 2^24 stripes); same bits.  FASTECC_E_UNSUPPORTED, before any device work: count * k
+ * beyond 2^31 - 1 blocks, or a code whose single stripe does not fit a dispatch in one of its passes (see fastecc_encode).
  */
 int fastecc_encode_batch(fastecc_ctx *ctx, const void *data, void *parity, uint64_t count, void *stream);
 
@@ -249,7 +255,8 @@ int fastecc_encode_batch(fastecc_ctx *ctx, const void *data, void *parity, uint6
  *   - Codes of the direct path (n - k <= "encode_direct_max", the rule fastecc_encode applies to one stripe, here to the pool's base
  *     pointers): ONE launch computes the parity of all stripes from the code's weight table when the code has k < 4096 and the launch
  *     fills at least 1024 waves, else the stripes are encoded one by one.  Option "encode_pool_kernel" chooses the kernel (below).
- *   - n = 2k = 2^m beyond the direct path: every transform pass once over the whole pool, as fastecc_encode_batch.
+ *   - n = 2k = 2^m beyond the direct path: every transform pass once over the whole pool, as fastecc_encode_batch (and cut into runs of
+ *     stripes like it; FASTECC_E_UNSUPPORTED where one stripe alone does not fit a dispatch in a pass).
  *   - Every other code (fold, cosets, zero extension, mixed radix beyond the direct path): fastecc_encode's work stripe by stripe —
  *     correct, not faster than the caller's own loop.
  * Enqueued on `stream` without synchronising, and nothing is staged on the host: steady-state calls are kernels only.  (The first call
@@ -279,14 +286,16 @@ int fastecc_encode_blocks(fastecc_ctx *ctx, void *const *blocks);
  * Length-k number-theoretic transform of the stripe, natural order in and out, unscaled, forward
  * root w_k (inverse != 0: w_k^-1).  Replaces MFA_NTT<T,P>(data,N,SIZE,InvNTT) (ntt.cpp:382-447) and
  * Rec_NTT (ntt.cpp:349-378) followed by reading the blocks through the permuted pointer array.
- * In place on `data` (k*block_bytes bytes).
+ * In place on `data` (k*block_bytes bytes).  FASTECC_E_UNSUPPORTED, with `data` untouched, when a pass or the final reordering (one wave per
+ * 64-word, or 256-word, piece of every block) would need 2^32 work-items or more in one launch.
  */
 int fastecc_ntt(fastecc_ctx *ctx, void *data, int inverse, int mem_kind, void *stream);
 
 /*
  * block i *= scale * base^i for i in [0,k): the per-block twiddle multiply of RS.cpp:51-59
  * (scale = 1/N, base = root(2N)) and, with other arguments, the MFA twiddle of ntt.cpp:421-431.
- * In place on device or host memory as for fastecc_encode.
+ * In place on device or host memory as for fastecc_encode.  One launch over the stripe (one wave per 64-word, or 256-word, piece of every
+ * block): FASTECC_E_UNSUPPORTED, with `data` untouched, when that would be 2^32 work-items or more.
  */
 int fastecc_scale_blocks(fastecc_ctx *ctx, void *data, uint32_t scale, uint32_t base, int mem_kind, void *stream);
 

@@ -60,6 +60,23 @@ def test_argument_validation_needs_no_device(hip_lib):
     assert hip_lib.fastecc_version() >= 100
 
 
+def test_block_lists_pass_uint64_arrays_through():
+    """Encoder._block_list (the write lists of update / update_batch, the stripe list of scrub_fingerprints): a contiguous uint64 numpy array is
+    handed to the library as it is — no Python list of its entries — and everything else is converted to the same words."""
+    import numpy as np
+    import fastecc_amd as fe
+    arr = np.array([5, 0, (1 << 64) - 1, 7], dtype=np.uint64)
+    n, p = fe.Encoder._block_list(arr)
+    assert n == 4 and ctypes.cast(p, ctypes.c_void_p).value == arr.ctypes.data  # the array's own memory
+    assert [int(p[i]) for i in range(n)] == [5, 0, (1 << 64) - 1, 7]
+    for other in ([5, 0, (1 << 64) - 1, 7], arr[::-1][::-1].tolist(), np.array([5, 0, 7], dtype=np.int64), arr[::2]):
+        n2, q = fe.Encoder._block_list(other)
+        assert n2 == len(other) and [int(q[i]) for i in range(n2)] == [int(v) for v in other]
+        assert ctypes.cast(q, ctypes.c_void_p).value != arr.ctypes.data  # a copy
+    n0, z = fe.Encoder._block_list(np.zeros(0, dtype=np.uint64))
+    assert n0 == 0 and len(z) == 1  # an empty list still gives the call an address
+
+
 def test_no_cpu_fallback_without_gpu(hip_lib):
     """On a box without a GPU the product must refuse to run rather than compute on the CPU."""
     import torch
