@@ -467,13 +467,54 @@ class Encoder:
         _check(lib().fastecc_verify(self._h, _addr(data), _addr(parity), mem, stream or None, seed, ctypes.byref(ok)), "fastecc_verify")
         return bool(ok.value)
 
-    def _scrub_batch(self, fn, data, parity, count, seed, stream):
+    def _pool_patterns(self, pattern_of, count):
+        """(object to keep alive, the arguments a pool call's set form takes after `count`): none for the single-pattern form (pattern_of None)"""
+        if pattern_of is None:
+            return None, ()
+        keep, po = self._pattern_list(pattern_of, count)
+        return keep, (po,)
+
+    def _scrub_batch(self, fn, data, parity, count, seed, stream, pattern_of=None):
+        """(return code, uint8 array with one entry per stripe) of a batched verify or correct, in its set form where pattern_of is given"""
         import numpy as np
         count = self._batch_count(count)
+        keep, po = self._pool_patterns(pattern_of, count)
         out = np.zeros(count, np.uint8)
         bad = ctypes.c_uint64()
-        code = fn(self._h, _addr(data), _addr(parity), count, stream or None, seed, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(bad))
+        code = fn(self._h, _addr(data), _addr(parity), count, *po, stream or None, seed, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(bad))
+        del keep
         return code, out
+
+    @staticmethod
+    def _corrected(code, what, status):
+        """the status array of a batched correction, or its error (E_UNCORRECTABLE carries the array)"""
+        if code == E_UNCORRECTABLE:
+            err = FastEccError(code, what)
+            err.status = status
+            raise err
+        _check(code, what)
+        return status
+
+    def _locate_batch(self, fn, what, data, parity, count, seed, stream, pattern_of=None):
+        """(status, lists) of a batched location call, in its set form where pattern_of is given, or its error (E_UNCORRECTABLE carries both)"""
+        import numpy as np
+        count = self._batch_count(count)
+        keep, po = self._pool_patterns(pattern_of, count)
+        cap = self.n - self.k
+        status = np.zeros(count, np.uint8)
+        blocks = np.zeros(count * cap, np.uint64)
+        counts = np.zeros(count, np.uint32)
+        bad = ctypes.c_uint64()
+        code = fn(self._h, _addr(data), _addr(parity), count, *po, stream or None, seed, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                  blocks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), cap, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(bad))
+        del keep
+        lists = [[int(x) for x in blocks[b * cap:b * cap + min(int(counts[b]), cap)]] for b in range(count)] if code in (OK, E_UNCORRECTABLE) else None
+        if code == E_UNCORRECTABLE:
+            err = FastEccError(code, what)
+            err.status, err.lists = status, lists
+            raise err
+        _check(code, what)
+        return status, lists
 
     def verify_batch(self, data, parity, count, seed=0, stream=0):
         """`count` stripes back to back in device memory (the layout of decode_batch): a numpy bool array, True where verify with the
@@ -490,12 +531,7 @@ class Encoder:
         uncorrectable, raises FastEccError with code E_UNCORRECTABLE after the others were corrected; the full status array is its
         `status` attribute."""
         code, out = self._scrub_batch(lib().fastecc_correct_batch, data, parity, count, seed, stream)
-        if code == E_UNCORRECTABLE:
-            err = FastEccError(code, "fastecc_correct_batch")
-            err.status = out
-            raise err
-        _check(code, "fastecc_correct_batch")
-        return out
+        return self._corrected(code, "fastecc_correct_batch", out)
 
     def scrub_erasures_set(self, data_present, parity_present):
         """A set of P absent-block patterns for verify_batch_set / correct_batch_set (a degraded pool with rotated placement): P rows of k
@@ -503,21 +539,11 @@ class Encoder:
         blocks absent.  P = 0 (two empty arguments) clears the set.  Independent of the scrub_erasures pattern and of both decode patterns."""
         self._pattern_set(lib().fastecc_scrub_erasures_set, "fastecc_scrub_erasures_set", data_present, parity_present)
 
-    def _scrub_batch_set(self, fn, data, parity, count, pattern_of, seed, stream):
-        import numpy as np
-        count = self._batch_count(count)
-        keep, po = self._pattern_list(pattern_of, count)
-        out = np.zeros(count, np.uint8)
-        bad = ctypes.c_uint64()
-        code = fn(self._h, _addr(data), _addr(parity), count, po, stream or None, seed, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(bad))
-        del keep
-        return code, out
-
     def verify_batch_set(self, data, parity, count, pattern_of, seed=0, stream=0):
         """verify_batch with stripe b under pattern pattern_of[b] of the scrub_erasures_set set: a numpy bool array, True where
         scrub_erasures(that pattern) + verify with the same seed finds the stripe consistent, and for PATTERN_NONE stripes, which are
         not read.  Reads only."""
-        code, out = self._scrub_batch_set(lib().fastecc_verify_batch_set, data, parity, count, pattern_of, seed, stream)
+        code, out = self._scrub_batch(lib().fastecc_verify_batch_set, data, parity, count, seed, stream, pattern_of)
         _check(code, "fastecc_verify_batch_set")
         return out.astype(bool)
 
@@ -528,60 +554,21 @@ class Encoder:
         qualifying stripes on; the same status and bytes in every mode.  Returns the numpy uint8 status array: 0 = consistent or skipped and untouched,
         1 = corrected (the whole codeword is back), 2 = uncorrectable.  If any stripe is uncorrectable, raises FastEccError with code
         E_UNCORRECTABLE after the others were corrected; the full status array is its `status` attribute."""
-        code, out = self._scrub_batch_set(lib().fastecc_correct_batch_set, data, parity, count, pattern_of, seed, stream)
-        if code == E_UNCORRECTABLE:
-            err = FastEccError(code, "fastecc_correct_batch_set")
-            err.status = out
-            raise err
-        _check(code, "fastecc_correct_batch_set")
-        return out
+        code, out = self._scrub_batch(lib().fastecc_correct_batch_set, data, parity, count, seed, stream, pattern_of)
+        return self._corrected(code, "fastecc_correct_batch_set", out)
 
     def locate_errors_batch(self, data, parity, count, seed=0, stream=0):
         """locate_errors for each of `count` stripes back to back in device memory: (status, lists) with the numpy uint8 status array
         (0 = consistent, 1 = located, 2 = cannot be located) and one list of codeword indices per stripe (increasing; [] for status 0
         and 2).  Reads only.  If any stripe cannot be located, raises FastEccError with code E_UNCORRECTABLE carrying both as its
         `status` and `lists` attributes."""
-        import numpy as np
-        count = self._batch_count(count)
-        cap = self.n - self.k
-        status = np.zeros(count, np.uint8)
-        blocks = np.zeros(count * cap, np.uint64)
-        counts = np.zeros(count, np.uint32)
-        bad = ctypes.c_uint64()
-        code = lib().fastecc_locate_errors_batch(self._h, _addr(data), _addr(parity), count, stream or None, seed,
-                                                 status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), blocks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
-                                                 cap, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(bad))
-        return self._located_batch(code, "fastecc_locate_errors_batch", status, blocks, counts, cap)
-
-    @staticmethod
-    def _located_batch(code, what, status, blocks, counts, cap):
-        """(status, lists) of a batched location call, or its error (E_UNCORRECTABLE carries both)"""
-        count = len(status)
-        lists = [[int(x) for x in blocks[b * cap:b * cap + min(int(counts[b]), cap)]] for b in range(count)] if code in (OK, E_UNCORRECTABLE) else None
-        if code == E_UNCORRECTABLE:
-            err = FastEccError(code, what)
-            err.status, err.lists = status, lists
-            raise err
-        _check(code, what)
-        return status, lists
+        return self._locate_batch(lib().fastecc_locate_errors_batch, "fastecc_locate_errors_batch", data, parity, count, seed, stream)
 
     def locate_errors_batch_set(self, data, parity, count, pattern_of, seed=0, stream=0):
         """locate_errors_batch with stripe b under pattern pattern_of[b] of the scrub_erasures_set set: (status, lists) as there, each stripe's
         answer the one scrub_erasures(that pattern) + locate_errors with the same seed gives; absent blocks are neither read nor listed, and a
         PATTERN_NONE stripe is not read and has status 0.  Reads only.  Raises like locate_errors_batch, with `status` and `lists`."""
-        import numpy as np
-        count = self._batch_count(count)
-        keep, po = self._pattern_list(pattern_of, count)
-        cap = self.n - self.k
-        status = np.zeros(count, np.uint8)
-        blocks = np.zeros(count * cap, np.uint64)
-        counts = np.zeros(count, np.uint32)
-        bad = ctypes.c_uint64()
-        code = lib().fastecc_locate_errors_batch_set(self._h, _addr(data), _addr(parity), count, po, stream or None, seed,
-                                                     status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), blocks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
-                                                     cap, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(bad))
-        del keep
-        return self._located_batch(code, "fastecc_locate_errors_batch_set", status, blocks, counts, cap)
+        return self._locate_batch(lib().fastecc_locate_errors_batch_set, "fastecc_locate_errors_batch_set", data, parity, count, seed, stream, pattern_of)
 
     def scrub_fingerprints(self, data, parity, count=1, form=0, stripes=None, seed=0, stream=0):
         """What the fingerprint pass of the scrub calls computes (tests only): (F, big) with F a numpy uint32 array [entries, n, 3], F[i, j, c]

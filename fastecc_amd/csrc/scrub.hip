@@ -30,13 +30,15 @@
 //                verify_batch_set_locked (a pattern per stripe) and LocateList under the set (a list, a pattern per entry: section 27).  A pass that
 //                fails part-way waits for what it enqueued (settled).
 //   location     LocateList, per chunk of the flagged stripes: gather_chunk (all syndromes at once), solve_chunk (Berlekamp-Massey and the recurrence
-//                check per stripe on the host), search_chunk (one root search for all locators), accept_chunk.  locate_list: every entry under the
-//                single named pattern; locate_list_set: each under the pattern of the set its stripe has.
+//                check per stripe on the host), search_chunk (one root search for all locators), accept_chunk.
+//   pool calls   StripePatterns holds what the single-pattern and the per-stripe-pattern form of a pool call differ in (section 30): the form's own
+//                argument check, its verify pass, the erasure view and the absent blocks of a stripe, the room in the call-private pattern set.  Written
+//                once on top of it: flagged (the verify pass's inconsistent stripes), locate_list (LocateList over those of them the batched pass takes),
+//                verify_pool_impl, locate_pool_impl and CorrectPool.
 //   correction   correct_stripe: locate, fastecc_decode_prepare + fastecc_repair of the located and the absent blocks, the closing verify.
-//                CorrectBatch: flag_and_locate, group_by_lost_set, repair_groups (one prepare and one list-form repair, decode.hip repair_list, per
-//                distinct set of lost blocks), closing_verify, fallbacks (correct_stripe's work on what the grouped path does not take).
-//                CorrectBatchSet (section 27): the same with a pattern per stripe — flag_and_group, repair_groups (ONE pattern set private to the call,
-//                decode.hip repair_lost_sets; the wide lost sets as CorrectBatch does), closing_verify, fallbacks.
+//                CorrectPool: flag_and_locate, group_by_lost_set, repair_groups (the lost sets of at most 16 blocks through ONE pattern set private to
+//                the call, decode.hip repair_lost_sets, where the form has one: section 27; every other distinct lost set one prepare and one list-form
+//                repair, decode.hip repair_list), closing_verify, fallbacks (correct_stripe on what the grouped path does not take).
 //   entry points argument checks, then the stage inside on_device.
 #include <algorithm>
 #include <map>
@@ -748,7 +750,7 @@ enum : uint8_t { LOC_FALLBACK = 0, LOC_FOUND = 1, LOC_UNCORRECTABLE = 2 };
 // has more than 512 syndromes.  Per chunk: one list pass that gathers every syndrome (gather_chunk), Berlekamp-Massey and the recurrence check on
 // the host (solve_chunk), one root search over all locators (search_chunk), the roots' blocks (accept_chunk); two synchronisations.
 // pattern_of (host, by stripe): every entry under its own pattern of the set instead — the SET_LIST pass, avail per entry
-// (each in [1, GATHER_MAX]: locate_list_set lists no others), the device copy d_pattern_of that the call's verify pass made.
+// (each in [1, GATHER_MAX]: locate_list lists no others), the device copy d_pattern_of that the call's verify pass made.
 struct LocateList {
     static constexpr uint64_t GATHER_MAX = 512;
     fastecc_ctx* c;
@@ -897,49 +899,6 @@ struct LocateList {
     }
 };
 
-int locate_list(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, const std::vector<uint64_t>& list, uint64_t seed, hipStream_t st,
-                std::vector<uint8_t>& state, std::vector<std::vector<uint32_t>>& blocks)
-{
-    return settled(st, [&]() -> int {
-        ScrubState* s = nullptr;
-        const int rc = scrub_state(c, &s);
-        if (rc != FASTECC_OK) return rc;
-        LocateList ll{c, s, data, parity, list, seed, st, state, blocks};
-        return ll.run();
-    });
-}
-
-// locate_list with stripe list[i] under pattern pattern_of[list[i]] of the set (every listed stripe has a pattern).  Called under the
-// same lock as the verify_batch_set_locked whose flags made the list: its device copy of pattern_of serves the list pass.  Entries whose pattern leaves
-// no syndrome or more than the batched pass gathers are not passed on and keep LOC_FALLBACK, so stripes of both kinds may share a call.
-int locate_list_set(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, const std::vector<uint64_t>& list, const uint32_t* pattern_of, uint64_t seed,
-                    hipStream_t st, std::vector<uint8_t>& state, std::vector<std::vector<uint32_t>>& blocks)
-{
-    return settled(st, [&]() -> int {
-        ScrubState* s = c->scrub;
-        const uint64_t m = s->n - s->k;
-        std::vector<uint64_t> taken, at;  // the entries the batched pass takes: their stripes, their places in `list`
-        for (size_t i = 0; i < list.size(); i++) {
-            const uint64_t w = s->set->absent[pattern_of[list[i]]].size();
-            if (w >= m || m - w > LocateList::GATHER_MAX) continue;
-            taken.push_back(list[i]);
-            at.push_back(i);
-        }
-        state.assign(list.size(), LOC_FALLBACK);
-        blocks.assign(list.size(), {});
-        std::vector<uint8_t> st_taken;
-        std::vector<std::vector<uint32_t>> bl_taken;
-        LocateList ll{c, s, data, parity, taken, seed, st, st_taken, bl_taken, pattern_of};
-        const int rc = ll.run();
-        if (rc != FASTECC_OK) return rc;
-        for (size_t e = 0; e < at.size(); e++) {
-            state[at[e]] = st_taken[e];
-            blocks[at[e]] = std::move(bl_taken[e]);
-        }
-        return FASTECC_OK;
-    });
-}
-
 // fastecc_scrub_erasures on a locked context: `absent` (codeword indices, increasing, at most n - k) replaces the named pattern.  The marked
 // position table and the locator table lfix * prod (x - w^pos) are built aside and swapped in, so a failure leaves the previous pattern in
 // force.  Synchronous; every scrub call ends with a synchronise, so nothing in flight reads the tables that are freed here.
@@ -1074,6 +1033,89 @@ int verify_batch_set_locked(fastecc_ctx* c, const uint32_t* data, const uint32_t
     });
 }
 
+// ---- the pool calls, written once for both forms ----
+
+// What the two forms of a pool call differ in: every stripe under the single fastecc_scrub_erasures pattern (pattern_of null), or stripe b under pattern
+// pattern_of[b] of the set (host, by stripe).  Every member is evaluated under the context's lock.
+struct StripePatterns {
+    const uint32_t* pattern_of;
+
+    // the form's own argument check
+    int args(const fastecc_ctx* c, uint64_t count) const { return pattern_of ? set_args(c, pattern_of, count) : FASTECC_OK; }
+
+    // its verify pass over the pool
+    int verify(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, uint64_t seed, hipStream_t st, std::vector<uint8_t>& flag) const
+    {
+        if (pattern_of) return verify_batch_set_locked(c, data, parity, count, pattern_of, seed, st, flag);
+        return verify_batch_locked(c, data, parity, count, seed, st, flag);
+    }
+
+    // the erasures `stripe` is scrubbed under; no view (d_pos null) where the set has no such pattern: args passed under this lock, or the set was
+    // replaced since (correct_stripe)
+    Erasures view(const ScrubState* s, uint64_t stripe) const
+    {
+        if (!pattern_of) return erasures(s, true);
+        const uint32_t q = pattern_of[stripe];
+        return s->set && q < s->set->P ? set_view(s, q) : Erasures{};
+    }
+
+    // the blocks absent under that view (the scrub state's own list: another call may replace the pattern or the set once the lock is released)
+    const std::vector<uint32_t>& absent(const ScrubState* s, uint64_t stripe) const
+    {
+        static const std::vector<uint32_t> none;
+        const Erasures er = view(s, stripe);
+        return er.w ? *er.absent : none;
+    }
+
+    // whether the pattern set private to a correcting call (section 27) takes one more distinct lost set, of `blocks` blocks, after `sets`: the
+    // single form has no such set, every lost set goes set by set there
+    bool private_set_takes(size_t sets, size_t blocks) const { return pattern_of && blocks <= SET_MAX_LOST && sets < SET_MAX_PATTERNS; }
+};
+
+// the form's verify pass on a locked context (args passed): the inconsistent stripes, increasing
+int flagged(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, const StripePatterns& pats, uint64_t seed, hipStream_t st,
+            std::vector<uint64_t>& list)
+{
+    std::vector<uint8_t> flag;
+    const int r = pats.verify(c, data, parity, count, seed, st, flag);
+    if (r != FASTECC_OK) return r;
+    for (uint64_t b = 0; b < count; b++)
+        if (flag[b]) list.push_back(b);
+    return FASTECC_OK;
+}
+
+// LocateList over the flagged stripes `list`, stripe list[i] under pats.view (DESIGN.md sections 17 and 27).  Called under the same lock as the verify pass
+// whose flags made the list: the scrub state is there, and under the set the pass's device copy of pattern_of serves the list pass.  Entries whose view
+// leaves no syndrome or more than the batched pass gathers are not passed on and keep LOC_FALLBACK, so stripes of both kinds may share a call (under the
+// single pattern every entry is of one kind).
+int locate_list(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, const std::vector<uint64_t>& list, const StripePatterns& pats, uint64_t seed,
+                hipStream_t st, std::vector<uint8_t>& state, std::vector<std::vector<uint32_t>>& blocks)
+{
+    std::vector<uint64_t> taken, at;  // the entries the batched pass takes: their stripes (the list pass copies them from here), their places in `list`
+    return settled(st, [&]() -> int {
+        ScrubState* s = c->scrub;
+        const uint64_t m = s->n - s->k;
+        for (size_t i = 0; i < list.size(); i++) {
+            const uint64_t w = pats.view(s, list[i]).w;
+            if (w >= m || m - w > LocateList::GATHER_MAX) continue;
+            taken.push_back(list[i]);
+            at.push_back(i);
+        }
+        state.assign(list.size(), LOC_FALLBACK);
+        blocks.assign(list.size(), {});
+        std::vector<uint8_t> st_taken;
+        std::vector<std::vector<uint32_t>> bl_taken;
+        LocateList ll{c, s, data, parity, taken, seed, st, st_taken, bl_taken, pats.pattern_of};
+        const int rc = ll.run();
+        if (rc != FASTECC_OK) return rc;
+        for (size_t e = 0; e < at.size(); e++) {
+            state[at[e]] = st_taken[e];
+            blocks[at[e]] = std::move(bl_taken[e]);
+        }
+        return FASTECC_OK;
+    });
+}
+
 // the seed of the closing verify of fastecc_correct and fastecc_correct_batch
 uint64_t closing_seed(uint64_t seed)
 {
@@ -1124,9 +1166,10 @@ int verify_impl(fastecc_ctx* c, const void* data, const void* parity, int mem_ki
     });
 }
 
-// fastecc_correct on one stripe (DEVICE memory, arguments checked): locate under the single fastecc_scrub_erasures pattern, or under pattern q of
-// the set (from_set), then rebuild located and absent blocks and verify the whole codeword with the derived seed.  found: the located blocks.
-int correct_stripe(fastecc_ctx* c, void* data, void* parity, void* stream, uint64_t seed, bool from_set, uint32_t q, std::vector<uint32_t>& found)
+// fastecc_correct on one stripe (DEVICE memory, arguments checked; data and parity are the stripe's own): locate under the view pats gives stripe
+// `stripe` — the single fastecc_scrub_erasures pattern, or the stripe's pattern of the set — then rebuild located and absent blocks and verify the whole
+// codeword with the derived seed.  found: the located blocks.
+int correct_stripe(fastecc_ctx* c, void* data, void* parity, void* stream, uint64_t seed, const StripePatterns& pats, uint64_t stripe, std::vector<uint32_t>& found)
 {
     std::vector<uint32_t> absent;
     {
@@ -1134,8 +1177,8 @@ int correct_stripe(fastecc_ctx* c, void* data, void* parity, void* stream, uint6
         ScrubState* s = nullptr;
         int r = scrub_state(c, &s);
         if (r != FASTECC_OK) return r;
-        if (from_set && (!s->set || q >= s->set->P)) return FASTECC_E_INVAL;  // (the set was replaced while the call ran)
-        const Erasures er = from_set ? set_view(s, q) : erasures(s, true);
+        const Erasures er = pats.view(s, stripe);
+        if (!er.d_pos) return FASTECC_E_INVAL;  // (the set was replaced while the call ran)
         if (er.w) absent = *er.absent;
         r = locate(c, s, er, (const uint32_t*)data, (const uint32_t*)parity, seed, (hipStream_t)stream, found, false);
         if (r != FASTECC_OK) return r;
@@ -1188,155 +1231,67 @@ int report(const std::vector<uint32_t>& found, uint64_t* blocks, uint64_t cap, u
     return FASTECC_OK;
 }
 
-// fastecc_correct_batch (arguments checked): the locked verify and location, then — grouped — one prepare and one list-form repair per distinct lost
-// set and one closing verify for all of them, and fastecc_correct stripe by stripe for whatever that leaves
-struct CorrectBatch {
-    fastecc_ctx* c;
-    void *data, *parity;
-    uint64_t count;
-    void* stream;
-    uint64_t seed;
-    std::vector<uint64_t> list;                    // the inconsistent stripes
-    std::vector<uint8_t> state;                    // grouped: LOC_* per list entry
-    std::vector<std::vector<uint32_t>> found;      // grouped: the located blocks per list entry
-    std::vector<uint32_t> absent;                  // grouped: the blocks named absent when the stripes were located
-    bool grouped = false;
-    std::vector<std::vector<uint32_t>> lost_sets;  // per group: located and absent blocks, sorted
-    std::vector<std::vector<uint64_t>> members;    // per group: its stripes
-    std::vector<uint64_t> order;                   // the groups' stripes back to back: group g at its offset
-    DeviceBuf<uint64_t> dev_order;                 // ... on the device for this call only (the repair runs outside the scrub state's lock)
-    std::vector<uint8_t> status;
-    bool uncorrectable = false;
-
-    // under the lock: the inconsistent stripes and, where the mode and their number allow grouping, their located blocks
-    int flag_and_locate()
-    {
-        const int mode = c->correct_batch_mode;
-        const uint32_t *d = (const uint32_t*)data, *p = (const uint32_t*)parity;
-        std::vector<uint8_t> flag;
-        CallLock lk(c->mu);
-        int r = verify_batch_locked(c, d, p, count, seed, (hipStream_t)stream, flag);
-        if (r != FASTECC_OK) return r;
-        for (uint64_t b = 0; b < count; b++)
-            if (flag[b]) list.push_back(b);
-        // one stripe has nothing to share; mode 0 groups from two qualifying stripes on (DESIGN.md section 17)
-        const size_t least = mode == 1 ? 1 : 2;
-        if (mode == 2 || list.size() < least) return FASTECC_OK;
-        if ((r = locate_list(c, d, p, list, seed, (hipStream_t)stream, state, found)) != FASTECC_OK) return r;
-        grouped = list.size() - (size_t)std::count(state.begin(), state.end(), (uint8_t)LOC_FALLBACK) >= least;
-        if (grouped) absent = c->scrub->absent;
-        return FASTECC_OK;
-    }
-
-    // the located stripes by their lost set — located blocks and blocks named absent — in the order the first stripe of each set appears
-    void group_by_lost_set()
-    {
-        std::map<std::vector<uint32_t>, size_t> group_of;
-        for (size_t i = 0; i < list.size(); i++) {
-            if (state[i] == LOC_UNCORRECTABLE) {
-                status[list[i]] = 2;
-                uncorrectable = true;
-            }
-            if (state[i] != LOC_FOUND || found[i].empty()) continue;
-            std::vector<uint32_t> lost(found[i]);
-            lost.insert(lost.end(), absent.begin(), absent.end());
-            std::sort(lost.begin(), lost.end());
-            auto it = group_of.find(lost);
-            if (it == group_of.end()) {
-                it = group_of.emplace(lost, lost_sets.size()).first;
-                lost_sets.push_back(lost);
-                members.emplace_back();
-            }
-            members[it->second].push_back(list[i]);
-        }
-        for (const auto& mb : members) order.insert(order.end(), mb.begin(), mb.end());
-    }
-
-    // one fastecc_decode_prepare and one list-form repair per group (both take the lock themselves)
-    int repair_groups()
-    {
-        RC_TRY(dev_order.alloc(order.size()));
-        HIP_TRY(hipMemcpy(dev_order, order.data(), order.size() * 8, hipMemcpyHostToDevice));
-        uint64_t at = 0;
-        for (size_t g = 0; g < members.size(); g++) {
-            int r = prepare_lost(c, lost_sets[g]);
-            if (r != FASTECC_OK) return r;
-            if ((r = repair_list(c, data, parity, order.data() + at, dev_order + at, members[g].size(), stream)) != FASTECC_OK) return r;
-            at += members[g].size();
-        }
-        return FASTECC_OK;
-    }
-
-    // the closing verify of fastecc_correct for all repaired stripes at once: its second seed, every block read (the stripes are whole now)
-    int closing_verify()
-    {
-        std::vector<uint8_t> still;
-        {
-            CallLock lk(c->mu);
-            const int r = verify_list_locked(c, (const uint32_t*)data, (const uint32_t*)parity, order, closing_seed(seed), (hipStream_t)stream, false, still);
-            if (r != FASTECC_OK) return r;
-        }
-        for (size_t i = 0; i < order.size(); i++) {
-            status[order[i]] = still[i] ? 2 : 1;
-            uncorrectable = uncorrectable || still[i];
-        }
-        return FASTECC_OK;
-    }
-
-    // fastecc_correct through the stripe's own pointers (it takes the lock itself) on what the grouped path left: every inconsistent stripe, or
-    // the LOC_FALLBACK ones
-    int fallbacks()
-    {
-        const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
-        for (size_t i = 0; i < list.size(); i++) {
-            if (grouped && state[i] != LOC_FALLBACK) continue;
-            const uint64_t b = list[i];
-            uint64_t n_found = 0;
-            int r = fastecc_correct(c, (char*)data + b * data_bytes, (char*)parity + b * parity_bytes, FASTECC_MEM_DEVICE, stream, seed, nullptr, 0, &n_found);
-            if ((r = record_status(r, n_found != 0, &status[b], &uncorrectable)) != FASTECC_OK) return r;
-        }
-        return FASTECC_OK;
-    }
-
-    int run(uint8_t* status_out, uint64_t* inconsistent)
-    {
-        int r = flag_and_locate();
-        if (r != FASTECC_OK) return r;
-        status.assign(count, 0);
-        if (grouped) {
-            group_by_lost_set();
-            if (!order.empty() && ((r = repair_groups()) != FASTECC_OK || (r = closing_verify()) != FASTECC_OK)) return r;
-        }
-        if ((r = fallbacks()) != FASTECC_OK) return r;
-        std::copy(status.begin(), status.end(), status_out);
-        *inconsistent = list.size();
-        return uncorrectable ? FASTECC_E_UNCORRECTABLE : FASTECC_OK;
-    }
-};
-
-// fastecc_verify_batch_set on a locked context (set_args passed): the inconsistent stripes, increasing
-int flagged_set(fastecc_ctx* c, const uint32_t* data, const uint32_t* parity, uint64_t count, const uint32_t* pattern_of, uint64_t seed, hipStream_t st,
-                std::vector<uint64_t>& list)
+// fastecc_verify_batch / _verify_batch_set (null pointers refused): flags of the form's verify pass
+int verify_pool_impl(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const StripePatterns& pats, void* stream, uint64_t seed,
+                     uint8_t* consistent, uint64_t* inconsistent)
 {
-    std::vector<uint8_t> flag;
-    const int r = verify_batch_set_locked(c, data, parity, count, pattern_of, seed, st, flag);
-    if (r != FASTECC_OK) return r;
-    for (uint64_t b = 0; b < count; b++)
-        if (flag[b]) list.push_back(b);
-    return FASTECC_OK;
+    const int rc = batch_args(c, data, parity, count);
+    if (rc != FASTECC_OK) return rc;
+    return on_device(c, [&]() -> int {
+        CallLock lk(c->mu);
+        int r = pats.args(c, count);
+        if (r != FASTECC_OK) return r;
+        std::vector<uint8_t> flag;
+        r = pats.verify(c, (const uint32_t*)data, (const uint32_t*)parity, count, seed, (hipStream_t)stream, flag);
+        if (r == FASTECC_OK) report_flags(flag, consistent, inconsistent);
+        return r;
+    });
 }
 
-// fastecc_correct_batch_set (arguments checked): CorrectBatch with a pattern per stripe.  Grouped: the located stripes by lost set —
-// located blocks and the blocks absent under the stripe's own pattern — repaired through ONE pattern set private to the call (repair_lost_sets: one launch
-// per size class; lost sets of more than 16 blocks and distinct sets beyond the 4096th take section 17's route, one prepare and one list-form repair per
-// set), one closing verify for all of them, and correct_stripe under the stripe's pattern for whatever that leaves.
-struct CorrectBatchSet {
+// fastecc_locate_errors_batch / _locate_errors_batch_set (null pointers refused): the verify pass, the batched location of the flagged stripes, the
+// single-stripe code for what that leaves, all under one lock
+int locate_pool_impl(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const StripePatterns& pats, void* stream, uint64_t seed,
+                     uint8_t* status, uint64_t* blocks, uint64_t cap, uint32_t* counts, uint64_t* inconsistent)
+{
+    const int rc = batch_args(c, data, parity, count);
+    if (rc != FASTECC_OK) return rc;
+    if (cap && count > UINT64_MAX / 8 / cap) return FASTECC_E_INVAL;
+    return on_device(c, [&]() -> int {
+        CallLock lk(c->mu);
+        hipStream_t st = (hipStream_t)stream;
+        const uint32_t *d = (const uint32_t*)data, *p = (const uint32_t*)parity;
+        int r = pats.args(c, count);
+        if (r != FASTECC_OK) return r;
+        std::vector<uint64_t> list;
+        std::vector<uint8_t> state;
+        std::vector<std::vector<uint32_t>> found;
+        bool uncorrectable = false;
+        if ((r = flagged(c, d, p, count, pats, seed, st, list)) != FASTECC_OK) return r;
+        if ((r = locate_list(c, d, p, list, pats, seed, st, state, found)) != FASTECC_OK) return r;
+        const uint64_t data_words = c->K * c->S, parity_words = c->Mu * c->S;
+        for (size_t i = 0; i < list.size(); i++) {
+            if (state[i] != LOC_FALLBACK) continue;
+            // a word >= p in a present block, no syndrome left or more than the batched pass gathers: the single-stripe code through the stripe's own
+            // pointers, under the stripe's view
+            r = locate(c, c->scrub, pats.view(c->scrub, list[i]), d + list[i] * data_words, p + list[i] * parity_words, seed, st, found[i], false);
+            if ((r = record_status(r, !found[i].empty(), &state[i], &uncorrectable)) != FASTECC_OK) return r;  // (the status codes 1 and 2 are LOC_FOUND and LOC_UNCORRECTABLE)
+        }
+        return report_located(list, state, found, count, status, blocks, cap, counts, inconsistent);
+    });
+}
+
+// fastecc_correct_batch / _correct_batch_set (arguments checked; DESIGN.md sections 17 and 27): the locked verify and location, then — grouped — the located
+// stripes by lost set: located blocks and the blocks absent under the stripe's view.  The lost sets of at most 16 blocks, up to the 4096th distinct one, are
+// repaired through ONE pattern set private to the call where the form has one (repair_lost_sets: one launch per size class); every other lost set takes one
+// prepare and one list-form repair.  One closing verify for all of them, and correct_stripe under the stripe's view for whatever that leaves.
+struct CorrectPool {
     fastecc_ctx* c;
     void *data, *parity;
     uint64_t count;
-    const uint32_t* pattern_of;
+    StripePatterns pats;
     void* stream;
     uint64_t seed;
+    const char* trace_label;                       // of the phase lines under FASTECC_TRACE_PREPARE
     std::vector<uint64_t> list;                    // the inconsistent stripes
     std::vector<uint8_t> state;                    // grouped: LOC_* per list entry
     std::vector<std::vector<uint32_t>> found;      // grouped: the located blocks per list entry
@@ -1344,33 +1299,40 @@ struct CorrectBatchSet {
     std::vector<std::vector<uint32_t>> lost_sets;  // per distinct lost set of the private set: located and absent blocks, sorted
     std::vector<uint64_t> stripes;                 // the private set's stripes ...
     std::vector<uint32_t> set_of;                  // ... and the lost set of each
-    std::vector<std::vector<uint32_t>> wide_sets;  // the lost sets that go set by set
+    std::vector<std::vector<uint32_t>> wide_sets;  // the lost sets that go set by set, in the order the first stripe of each appears
     std::vector<std::vector<uint64_t>> wide_members;
     std::vector<uint64_t> order;                   // every repaired stripe: the private set's, then the wide sets' members back to back
-    DeviceBuf<uint64_t> dev_order;                 // the wide sets' part of it on the device, for this call only
+    DeviceBuf<uint64_t> dev_order;                 // the wide sets' part of it on the device, for this call only (the repair runs outside the scrub state's lock)
     std::vector<uint8_t> status;
     bool uncorrectable = false;
-    PhaseTimer pt{"[fastecc correct_batch_set]"};  // (FASTECC_TRACE_PREPARE: where a call's wall time goes, host work included)
+    PhaseTimer pt{trace_label};                    // (where a call's wall time goes, host work included)
 
-    // under the lock: the inconsistent stripes and, where the mode and their number allow grouping, their located blocks and lost sets (the set's own
-    // lists of absent blocks are read here: another call may replace the set once the lock is released)
-    int flag_and_group()
+    // under the lock: the inconsistent stripes and, where the mode and their number allow grouping, their located blocks and lost sets
+    int flag_and_locate()
     {
         const int mode = c->correct_batch_mode;
+        const uint32_t *d = (const uint32_t*)data, *p = (const uint32_t*)parity;
         CallLock lk(c->mu);
-        int r = set_args(c, pattern_of, count);
+        int r = pats.args(c, count);
         if (r != FASTECC_OK) return r;
-        r = flagged_set(c, (const uint32_t*)data, (const uint32_t*)parity, count, pattern_of, seed, (hipStream_t)stream, list);
-        if (r != FASTECC_OK) return r;
+        if ((r = flagged(c, d, p, count, pats, seed, (hipStream_t)stream, list)) != FASTECC_OK) return r;
         status.assign(count, 0);
-        const size_t least = mode == 1 ? 1 : 2;  // as for fastecc_correct_batch
         pt.mark("verify pass");
+        // one stripe has nothing to share; mode 0 groups from two qualifying stripes on (DESIGN.md section 17)
+        const size_t least = mode == 1 ? 1 : 2;
         if (mode == 2 || list.size() < least) return FASTECC_OK;
-        if ((r = locate_list_set(c, (const uint32_t*)data, (const uint32_t*)parity, list, pattern_of, seed, (hipStream_t)stream, state, found)) != FASTECC_OK) return r;
+        if ((r = locate_list(c, d, p, list, pats, seed, (hipStream_t)stream, state, found)) != FASTECC_OK) return r;
         pt.mark("batched location");
         grouped = list.size() - (size_t)std::count(state.begin(), state.end(), (uint8_t)LOC_FALLBACK) >= least;
-        if (!grouped) return FASTECC_OK;
-        const ScrubSet* t = c->scrub->set.get();
+        if (grouped) group_by_lost_set();
+        return FASTECC_OK;
+    }
+
+    // the located stripes by their lost set — located blocks and the blocks absent under the stripe's view — into the private set while it takes them,
+    // else set by set.  Under flag_and_locate's lock: the scrub state's lists of absent blocks are read here, and another call may replace the pattern
+    // or the set once the lock is released.
+    void group_by_lost_set()
+    {
         std::map<std::vector<uint32_t>, size_t> narrow_of, wide_of;
         for (size_t i = 0; i < list.size(); i++) {
             if (state[i] == LOC_UNCORRECTABLE) {
@@ -1379,11 +1341,11 @@ struct CorrectBatchSet {
             }
             if (state[i] != LOC_FOUND || found[i].empty()) continue;
             std::vector<uint32_t> lost(found[i]);
-            const std::vector<uint32_t>& absent = t->absent[pattern_of[list[i]]];
+            const std::vector<uint32_t>& absent = pats.absent(c->scrub, list[i]);
             lost.insert(lost.end(), absent.begin(), absent.end());
             std::sort(lost.begin(), lost.end());
             auto it = narrow_of.find(lost);
-            if (it == narrow_of.end() && lost.size() <= SET_MAX_LOST && lost_sets.size() < SET_MAX_PATTERNS) {
+            if (it == narrow_of.end() && pats.private_set_takes(lost_sets.size(), lost.size())) {
                 it = narrow_of.emplace(lost, lost_sets.size()).first;
                 lost_sets.push_back(lost);
             }
@@ -1403,7 +1365,6 @@ struct CorrectBatchSet {
         order = stripes;
         for (const auto& mb : wide_members) order.insert(order.end(), mb.begin(), mb.end());
         pt.mark("lost sets");
-        return FASTECC_OK;
     }
 
     // the private set's stripes in one call, then one prepare and one list-form repair per wide set (all take the lock themselves)
@@ -1425,7 +1386,8 @@ struct CorrectBatchSet {
         });
     }
 
-    // as CorrectBatch::closing_verify: every block of every repaired stripe, whatever pattern is named
+    // the closing verify of fastecc_correct for all repaired stripes at once: its second seed, every block read whatever pattern is named (the
+    // stripes are whole now)
     int closing_verify()
     {
         std::vector<uint8_t> still;
@@ -1440,8 +1402,8 @@ struct CorrectBatchSet {
         return FASTECC_OK;
     }
 
-    // fastecc_correct under the stripe's own pattern (correct_stripe takes the lock itself) on what the grouped path left: every inconsistent stripe, or
-    // the LOC_FALLBACK ones
+    // fastecc_correct under the stripe's view, through the stripe's own pointers (correct_stripe takes the lock itself), on what the grouped path left:
+    // every inconsistent stripe, or the LOC_FALLBACK ones
     int fallbacks()
     {
         const uint64_t block = c->S * 4, data_bytes = c->K * block, parity_bytes = c->Mu * block;
@@ -1449,7 +1411,7 @@ struct CorrectBatchSet {
         for (size_t i = 0; i < list.size(); i++) {
             if (grouped && state[i] != LOC_FALLBACK) continue;
             const uint64_t b = list[i];
-            int r = correct_stripe(c, (char*)data + b * data_bytes, (char*)parity + b * parity_bytes, stream, seed, true, pattern_of[b], located);
+            int r = correct_stripe(c, (char*)data + b * data_bytes, (char*)parity + b * parity_bytes, stream, seed, pats, b, located);
             if ((r = record_status(r, !located.empty(), &status[b], &uncorrectable)) != FASTECC_OK) return r;
         }
         return FASTECC_OK;
@@ -1457,7 +1419,7 @@ struct CorrectBatchSet {
 
     int run(uint8_t* status_out, uint64_t* inconsistent)
     {
-        int r = flag_and_group();
+        int r = flag_and_locate();
         if (r != FASTECC_OK) return r;
         if (!order.empty()) {
             if ((r = repair_groups()) != FASTECC_OK) return r;
@@ -1579,7 +1541,7 @@ int fastecc_correct(fastecc_ctx* c, void* data, void* parity, int mem_kind, void
     if (rc != FASTECC_OK) return rc;
     return on_device(c, [&]() -> int {
         std::vector<uint32_t> found;
-        const int r = correct_stripe(c, data, parity, stream, seed, false, 0, found);
+        const int r = correct_stripe(c, data, parity, stream, seed, StripePatterns{nullptr}, 0, found);
         return r == FASTECC_OK ? report(found, blocks, cap, count) : r;
     });
 }
@@ -1588,46 +1550,14 @@ int fastecc_verify_batch(fastecc_ctx* c, const void* data, const void* parity, u
                          uint64_t* inconsistent)
 {
     if (!consistent || !inconsistent) return FASTECC_E_INVAL;
-    const int rc = batch_args(c, data, parity, count);
-    if (rc != FASTECC_OK) return rc;
-    return on_device(c, [&]() -> int {
-        CallLock lk(c->mu);
-        std::vector<uint8_t> flag;
-        const int r = verify_batch_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, seed, (hipStream_t)stream, flag);
-        if (r == FASTECC_OK) report_flags(flag, consistent, inconsistent);
-        return r;
-    });
+    return verify_pool_impl(c, data, parity, count, {nullptr}, stream, seed, consistent, inconsistent);
 }
 
 int fastecc_locate_errors_batch(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, void* stream, uint64_t seed, uint8_t* status,
                                 uint64_t* blocks, uint64_t cap, uint32_t* counts, uint64_t* inconsistent)
 {
     if (!status || !inconsistent || (cap && (!blocks || !counts))) return FASTECC_E_INVAL;
-    const int rc = batch_args(c, data, parity, count);
-    if (rc != FASTECC_OK) return rc;
-    if (cap && count > UINT64_MAX / 8 / cap) return FASTECC_E_INVAL;
-    return on_device(c, [&]() -> int {
-        CallLock lk(c->mu);
-        hipStream_t st = (hipStream_t)stream;
-        std::vector<uint8_t> flag, state;
-        bool uncorrectable = false;
-        int r = verify_batch_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, seed, st, flag);
-        if (r != FASTECC_OK) return r;
-        std::vector<uint64_t> list;
-        for (uint64_t b = 0; b < count; b++)
-            if (flag[b]) list.push_back(b);
-        std::vector<std::vector<uint32_t>> found;
-        if ((r = locate_list(c, (const uint32_t*)data, (const uint32_t*)parity, list, seed, st, state, found)) != FASTECC_OK) return r;
-        const uint64_t data_words = c->K * c->S, parity_words = c->Mu * c->S;
-        for (size_t i = 0; i < list.size(); i++) {
-            if (state[i] != LOC_FALLBACK) continue;
-            // a word >= p in a present block, or more syndromes than the batched pass gathers: the single-stripe code through the stripe's own pointers
-            r = locate(c, c->scrub, erasures(c->scrub, true), (const uint32_t*)data + list[i] * data_words, (const uint32_t*)parity + list[i] * parity_words, seed, st,
-                       found[i], false);
-            if ((r = record_status(r, !found[i].empty(), &state[i], &uncorrectable)) != FASTECC_OK) return r;  // (the status codes 1 and 2 are LOC_FOUND and LOC_UNCORRECTABLE)
-        }
-        return report_located(list, state, found, count, status, blocks, cap, counts, inconsistent);
-    });
+    return locate_pool_impl(c, data, parity, count, {nullptr}, stream, seed, status, blocks, cap, counts, inconsistent);
 }
 
 int fastecc_correct_batch(fastecc_ctx* c, void* data, void* parity, uint64_t count, void* stream, uint64_t seed, uint8_t* status, uint64_t* inconsistent)
@@ -1636,8 +1566,8 @@ int fastecc_correct_batch(fastecc_ctx* c, void* data, void* parity, uint64_t cou
     const int rc = batch_args(c, data, parity, count);
     if (rc != FASTECC_OK) return rc;
     return on_device(c, [&]() -> int {
-        CorrectBatch cb{c, data, parity, count, stream, seed};
-        return cb.run(status, inconsistent);
+        CorrectPool cp{c, data, parity, count, {nullptr}, stream, seed, "[fastecc correct_batch]"};
+        return cp.run(status, inconsistent);
     });
 }
 
@@ -1665,16 +1595,7 @@ int fastecc_verify_batch_set(fastecc_ctx* c, const void* data, const void* parit
                              uint8_t* consistent, uint64_t* inconsistent)
 {
     if (!consistent || !inconsistent || !pattern_of) return FASTECC_E_INVAL;
-    int rc = batch_args(c, data, parity, count);
-    if (rc != FASTECC_OK) return rc;
-    return on_device(c, [&]() -> int {
-        CallLock lk(c->mu);
-        if ((rc = set_args(c, pattern_of, count)) != FASTECC_OK) return rc;
-        std::vector<uint8_t> flag;
-        const int r = verify_batch_set_locked(c, (const uint32_t*)data, (const uint32_t*)parity, count, pattern_of, seed, (hipStream_t)stream, flag);
-        if (r == FASTECC_OK) report_flags(flag, consistent, inconsistent);
-        return r;
-    });
+    return verify_pool_impl(c, data, parity, count, {pattern_of}, stream, seed, consistent, inconsistent);
 }
 
 int fastecc_correct_batch_set(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, void* stream, uint64_t seed, uint8_t* status,
@@ -1684,8 +1605,8 @@ int fastecc_correct_batch_set(fastecc_ctx* c, void* data, void* parity, uint64_t
     const int rc = batch_args(c, data, parity, count);
     if (rc != FASTECC_OK) return rc;
     return on_device(c, [&]() -> int {
-        CorrectBatchSet cb{c, data, parity, count, pattern_of, stream, seed};
-        return cb.run(status, inconsistent);
+        CorrectPool cp{c, data, parity, count, {pattern_of}, stream, seed, "[fastecc correct_batch_set]"};
+        return cp.run(status, inconsistent);
     });
 }
 
@@ -1693,30 +1614,7 @@ int fastecc_locate_errors_batch_set(fastecc_ctx* c, const void* data, const void
                                     uint8_t* status, uint64_t* blocks, uint64_t cap, uint32_t* counts, uint64_t* inconsistent)
 {
     if (!status || !inconsistent || !pattern_of || (cap && (!blocks || !counts))) return FASTECC_E_INVAL;
-    const int rc = batch_args(c, data, parity, count);
-    if (rc != FASTECC_OK) return rc;
-    if (cap && count > UINT64_MAX / 8 / cap) return FASTECC_E_INVAL;
-    return on_device(c, [&]() -> int {
-        CallLock lk(c->mu);
-        hipStream_t st = (hipStream_t)stream;
-        const uint32_t *d = (const uint32_t*)data, *p = (const uint32_t*)parity;
-        int r = set_args(c, pattern_of, count);
-        if (r != FASTECC_OK) return r;
-        std::vector<uint64_t> list;
-        std::vector<uint8_t> state;
-        std::vector<std::vector<uint32_t>> found;
-        bool uncorrectable = false;
-        if ((r = flagged_set(c, d, p, count, pattern_of, seed, st, list)) != FASTECC_OK) return r;
-        if ((r = locate_list_set(c, d, p, list, pattern_of, seed, st, state, found)) != FASTECC_OK) return r;
-        const uint64_t data_words = c->K * c->S, parity_words = c->Mu * c->S;
-        for (size_t i = 0; i < list.size(); i++) {
-            if (state[i] != LOC_FALLBACK) continue;
-            // a word >= p in a present block, no syndrome left or more than the batched pass gathers: the single-stripe code under the stripe's pattern
-            r = locate(c, c->scrub, set_view(c->scrub, pattern_of[list[i]]), d + list[i] * data_words, p + list[i] * parity_words, seed, st, found[i], false);
-            if ((r = record_status(r, !found[i].empty(), &state[i], &uncorrectable)) != FASTECC_OK) return r;  // (the status codes 1 and 2 are LOC_FOUND and LOC_UNCORRECTABLE)
-        }
-        return report_located(list, state, found, count, status, blocks, cap, counts, inconsistent);
-    });
+    return locate_pool_impl(c, data, parity, count, {pattern_of}, stream, seed, status, blocks, cap, counts, inconsistent);
 }
 
 }  // extern "C"

@@ -301,6 +301,14 @@ def test_correct_batch_set_modes(torch_cuda, fe):
         list_chunks = [flagged[i:i + 8] for i in range(0, len(flagged), 8)]
         searched = sum(1 for c in list_chunks if any(b != big_stripe for b in c))
         classes = {1 << (len(wrong[b]) + len(absent(b)) - 1).bit_length() for b in fixable if len(wrong[b]) + len(absent(b)) <= 16}
+        # the lost sets of more than 16 blocks go set by set: one prepare and one list-form repair each, whose passes are the single pattern's (DESIGN.md
+        # section 13: data AND parity lost, more than 32 blocks in all, is the data pass and then the parity pass; anything else is one pass).  A pass
+        # over so few stripes has far fewer than 1024 waves, so the default rule runs it stripe by stripe under "direct_pass", the scope that
+        # fastecc_repair of the modes' single-stripe corrections records too: the batched form is asked for, which records "direct_pass_list".
+        lost_sets = {tuple(sorted(wrong[b] + absent(b))) for b in fixable}
+        wide_passes = sum(2 if len(ls) > 32 and min(ls) < k <= max(ls) else 1 for ls in lost_sets if len(ls) > 16)
+        assert wide_passes == 1  # stripe 12 alone: 18 blocks
+        enc.set_option("decode_batch_kernel", 1)
         results = {}
         enc.profile(True)
         for mode in (0, 1, 2):
@@ -314,11 +322,14 @@ def test_correct_batch_set_modes(torch_cuda, fe):
             assert torch.equal(D, DL) and torch.equal(Q, QL), mode  # the loop's bytes
             if mode == 2:
                 assert not [x for x in GROUPED_SCOPES if x in prof], prof
+                assert "direct_pass_list" not in prof, prof
             else:
+                assert prof["direct_pass_list"][1] == wide_passes, prof
                 assert prof["fingerprint_set_list"][1] == len(list_chunks) and prof["scrub_syndromes_gather_set"][1] == len(list_chunks), prof
                 assert prof["scrub_root_search_batch"][1] == searched, prof
                 assert prof["direct_pass_set"][1] == len(classes), (prof, classes)
         enc.profile(False)
+        enc.set_option("decode_batch_kernel", 0)
         # (c) corrected stripes hold the original codeword, absent blocks included; the others are untouched
         hd, hq = pool.contents(D, Q)
         for b in range(count):

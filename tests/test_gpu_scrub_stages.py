@@ -1,13 +1,16 @@
 """GPU tests (-m gpu) that pin the dispatch structure of the batched scrub calls: how many launches every profile scope records, chunk
-by chunk, for fastecc_verify_batch, fastecc_verify_batch_set, fastecc_locate_errors_batch and fastecc_correct_batch.
+by chunk, for fastecc_verify_batch, fastecc_verify_batch_set, fastecc_locate_errors_batch, fastecc_correct_batch and the last two with a
+pattern per stripe, fastecc_locate_errors_batch_set and fastecc_correct_batch_set.
 
 The expected counts are formulas of the documented algorithm (the head comment of fastecc_amd/csrc/scrub.hip, DESIGN.md sections 14, 16,
-17 and 19), never numbers read back from a run.  With "scrub_batch_chunk" = CHUNK a pass over X stripes takes ceil(X / CHUNK) chunks, and
+17, 19 and 27), never numbers read back from a run.  With "scrub_batch_chunk" = CHUNK a pass over X stripes takes ceil(X / CHUNK) chunks, and
 per chunk
   a verify chunk is one fingerprint launch, one transform and one syndrome check; with n - k blocks named absent no coefficient is left
       to check and the chunk ends after its fingerprints; a chunk of a set call whose stripes are all PATTERN_NONE is skipped;
   batched location runs one list pass per chunk of the FLAGGED stripes (list fingerprints, transform, syndrome gather) and one root search
       per chunk that holds a locator; a stripe with a word >= p in a present block is left to the single-stripe code;
+  with a pattern per stripe the same passes run in their set forms, over the flagged stripes whose pattern leaves 1 .. 512 syndromes, and the
+      grouped repair is one launch per size class of the lost sets;
   the grouped correction closes with one list verify (list fingerprints, transform, syndrome check) over the repaired stripes;
   fastecc_correct on one stripe reads the stripe twice: the fingerprints of its location and of its closing verify.
 Every case also checks the call's result: the pool's parity is the oracle's (tests/pool_model.py Codec), the corruption is the test's own."""
@@ -241,3 +244,97 @@ def test_correct_batch_grouped_with_a_word_above_p(torch_cuda, fe, codewords, S,
         assert got.get("fingerprint", 0) == 2, got  # fastecc_correct on the one stripe: its location and its closing verify
         hd, hp = pool.read()
         assert np.array_equal(hd, codewords[S][0]) and np.array_equal(hp, codewords[S][1])
+
+
+# ---- the same two calls with a pattern per stripe ----
+SET_PATTERNS = [[2], [18, 5]]  # n - k - w = 3 and 2 syndromes: one wrong block is within reach under either
+LOCATE_PATTERN_OF = [0, 1, 1, 0, NONE]  # every stripe of BAD has a pattern that leaves its corrupted block present; the chunk {4} is all PATTERN_NONE
+LOCATE_SET_CHUNKS = len({b // CHUNK for b, q in enumerate(LOCATE_PATTERN_OF) if q != NONE})
+assert all(BAD[b] not in SET_PATTERNS[LOCATE_PATTERN_OF[b]] for b in BAD) and LOCATE_SET_CHUNKS == 2
+
+
+def degraded(codewords, S, big=None):
+    """corrupted() with the absent blocks of every stripe, and every block of the PATTERN_NONE stripe, overwritten: (d, p, d and p as a correction
+    must leave them: the clean codewords, whole, for the corrected stripes; a consistent stripe and the PATTERN_NONE stripe as they were)"""
+    d, p = corrupted(codewords, S, big=big)
+    want_d, want_p = codewords[S][0].copy(), codewords[S][1].copy()
+    for b, q in enumerate(LOCATE_PATTERN_OF):
+        garbage(d, p, b, range(N) if q == NONE else SET_PATTERNS[q])
+        if b not in BAD:
+            garbage(want_d, want_p, b, range(N) if q == NONE else SET_PATTERNS[q])
+    return d, p, want_d, want_p
+
+
+def open_set_encoder(fe, S):
+    enc = open_encoder(fe, S)
+    enc.scrub_erasures_set([presence(q)[0] for q in SET_PATTERNS], [presence(q)[1] for q in SET_PATTERNS])
+    return enc
+
+
+def lost_set_classes(stripes):
+    """the launches of the grouped repair through the call's private pattern set: one per size class of the lost sets (located and absent blocks;
+    the class of a pass: its outputs rounded up to a power of two) — the rule of test_gpu_locate_batch_set.py::test_correct_batch_set_modes"""
+    return len({1 << (1 + len(SET_PATTERNS[LOCATE_PATTERN_OF[b]]) - 1).bit_length() for b in stripes})
+
+
+@pytest.mark.parametrize("S,skew", SHAPES)
+def test_locate_errors_batch_set(torch_cuda, fe, codewords, S, skew):
+    d, p, _, _ = degraded(codewords, S)
+    with open_set_encoder(fe, S) as enc:
+        pool = Pool(torch_cuda, d, p, skew)
+        (status, lists), got = launches(enc, lambda: enc.locate_errors_batch_set(pool.D, pool.Q, COUNT, LOCATE_PATTERN_OF, seed=SEED))
+        assert status.tolist() == [1 if b in BAD else 0 for b in range(COUNT)]
+        assert lists == [[BAD[b]] if b in BAD else [] for b in range(COUNT)]
+        # the verify pass: the chunks that hold a stripe with a pattern; the list pass: every flagged stripe has 1 .. 512 syndromes left
+        assert got.get("fingerprint_set", 0) == LOCATE_SET_CHUNKS and got.get("scrub_syndromes_set", 0) == LOCATE_SET_CHUNKS, got
+        for scope in ("fingerprint_set_list", "scrub_syndromes_gather_set", "scrub_root_search_batch"):
+            assert got.get(scope, 0) == chunks(L), (scope, got)
+        assert got.get("scrub_transform_batch", 0) == LOCATE_SET_CHUNKS + chunks(L), got
+        assert got.get("fingerprint", 0) == 0, got
+        assert not [x for x in ("fingerprint_batch", "fingerprint_batch_list", "scrub_syndromes_batch", "scrub_syndromes_gather") if x in got], got
+        hd, hp = pool.read()
+        assert np.array_equal(hd, d) and np.array_equal(hp, p)  # reads only
+
+
+@pytest.mark.parametrize("S,skew", SHAPES)
+def test_correct_batch_set_grouped(torch_cuda, fe, codewords, S, skew):
+    d, p, want_d, want_p = degraded(codewords, S)
+    with open_set_encoder(fe, S) as enc:
+        enc.set_option("correct_batch_mode", 1)
+        pool = Pool(torch_cuda, d, p, skew)
+        status, got = launches(enc, lambda: enc.correct_batch_set(pool.D, pool.Q, COUNT, LOCATE_PATTERN_OF, seed=SEED))
+        assert status.tolist() == [1 if b in BAD else 0 for b in range(COUNT)]
+        assert got.get("fingerprint_set", 0) == LOCATE_SET_CHUNKS and got.get("scrub_syndromes_set", 0) == LOCATE_SET_CHUNKS, got
+        for scope in ("fingerprint_set_list", "scrub_syndromes_gather_set", "scrub_root_search_batch"):
+            assert got.get(scope, 0) == chunks(L), (scope, got)
+        assert lost_set_classes(BAD) == 2 and got.get("direct_pass_set", 0) == lost_set_classes(BAD), got
+        # the closing list verify over the L repaired stripes: every block is read, whatever pattern is named
+        assert got.get("fingerprint_batch_list", 0) == chunks(L) and got.get("scrub_syndromes_batch", 0) == chunks(L), got
+        assert got.get("scrub_transform_batch", 0) == LOCATE_SET_CHUNKS + 2 * chunks(L), got
+        assert got.get("fingerprint", 0) == 0, got
+        hd, hp = pool.read()
+        assert np.array_equal(hd, want_d) and np.array_equal(hp, want_p)  # the clean codewords, absent blocks included; the other stripes untouched
+
+
+@pytest.mark.parametrize("S,skew", SHAPES)
+def test_correct_batch_set_grouped_with_a_word_above_p(torch_cuda, fe, codewords, S, skew):
+    big = 3  # the flagged list's second chunk is this stripe alone: no locator there, no root search; the stripe is left to the single-stripe code
+    d, p, want_d, want_p = degraded(codewords, S, big=big)
+    batched = L - 1  # the stripes the grouped path repairs
+    with open_set_encoder(fe, S) as enc:
+        enc.set_option("correct_batch_mode", 1)
+        pool = Pool(torch_cuda, d, p, skew)
+        status, got = launches(enc, lambda: enc.correct_batch_set(pool.D, pool.Q, COUNT, LOCATE_PATTERN_OF, seed=SEED))
+        assert status.tolist() == [1 if b in BAD else 0 for b in range(COUNT)]
+        assert got.get("fingerprint_set", 0) == LOCATE_SET_CHUNKS and got.get("scrub_syndromes_set", 0) == LOCATE_SET_CHUNKS, got
+        assert got.get("fingerprint_set_list", 0) == chunks(L) and got.get("scrub_syndromes_gather_set", 0) == chunks(L), got
+        flagged = sorted(BAD)
+        with_locator = len({i // CHUNK for i, b in enumerate(flagged) if b != big})
+        assert with_locator == 1 and got.get("scrub_root_search_batch", 0) == with_locator, got
+        assert got.get("direct_pass_set", 0) == lost_set_classes(b for b in BAD if b != big), got
+        # the stripe is missing from the closing list
+        assert got.get("fingerprint_batch_list", 0) == chunks(batched) and got.get("scrub_syndromes_batch", 0) == chunks(batched), got
+        assert got.get("scrub_transform_batch", 0) == LOCATE_SET_CHUNKS + chunks(L) + chunks(batched), got
+        assert got.get("fingerprint", 0) == 2, got  # correct_stripe on the one stripe: its location and its closing verify
+        hd, hp = pool.read()
+        assert np.array_equal(hd, want_d) and np.array_equal(hp, want_p)
