@@ -158,6 +158,7 @@ def test_encode_of_edge_stripes(torch_cuda, fe, plan):
         x, names = edge_stripe(logn)
         with fe.Encoder(2 << logn, 1 << logn, 4 * S) as enc:
             enc.set_plan(plan)
+            enc.set_option("encode_direct_max", 0)   # up to 160 parity blocks (k = 2^4, 2^7) the default is the direct encode, whatever the plan
             encode_both_ways(torch_cuda, enc, x, edge_parity(logn), names, "k=2^%d plan %d" % (logn, plan))
 
 
@@ -273,6 +274,7 @@ def mixed_case(torch, fe, oracle, q, m, fused, words=S):
         # the kernel kind, so that a planner change cannot silently drop coverage: R<q>+ is the odd-radix level fused into the outer tile,
         # R<q>: the stand-alone radix kernel around the power-of-two pipeline
         assert (("R%d+dif" % q) in enc.plan()) == fused and (("R%d:dif1" % q) in enc.plan()) == (not fused), enc.plan()
+        enc.set_option("encode_direct_max", 0)   # (the orders up to 160 would be encoded directly, without the radix kernels)
         encode_both_ways(torch, enc, x, want, names, "order %d * 2^%d" % (q, m))
 
 
