@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "devmem.hpp"
@@ -61,6 +62,42 @@ __device__ __forceinline__ uint32_t dev_pow(uint32_t x, uint32_t e)
 __host__ __device__ __forceinline__ size_t coef_index(uint32_t row, uint32_t out, uint32_t rows, uint32_t pad)
 {
     return pad <= 16u ? (size_t)row * pad + out : ((size_t)(out >> 4) * rows + row) * 16u + (out & 15u);
+}
+
+// The row loop of every VALU kernel: lo/hi[j][v] += sum over the rows u in [u0, u1) of row_of(u)[v] * coef[u * cstride + j], j < EB, v < V.
+// U rows are in flight: their U * EB weights are scalar loads into SGPRs (coef, cstride and the bounds are wave-uniform), their U * V words
+// one load_vec per lane, then U * EB * V mac96.  Which U the SGPR budget allows is the calling kernel's business.  Past u1 a weight and a
+// word are zero, so the last group may be partial; a lane that is not `live` loads nothing and sums zeros.  A lost row holds anything: its
+// weights are zero.  row_of(u) is the lane's pointer to its V words of row u; it is called for u in [u0, u1) only, and only in live lanes.
+// Exact for any number of rows <= 2^32: every term is < 2^64 and hi counts the carries out of lo; the caller reduces once (reduce96).
+template <int EB, int V, int U, class RowOf>
+__device__ __forceinline__ void weigh_rows(uint64_t (&lo)[EB][V], uint32_t (&hi)[EB][V], const_u32_ptr coef, uint32_t cstride, uint32_t u0, uint32_t u1, bool live,
+                                           RowOf row_of)
+{
+    for (uint32_t ub = u0; ub < u1; ub += U) {
+        uint32_t w[U][EB], x[U][V];
+#pragma unroll
+        for (int i = 0; i < U; ++i) {
+            const uint32_t u = ub + i;
+            const bool in = u < u1;  // wave-uniform
+#pragma unroll
+            for (int j = 0; j < EB; ++j) w[i][j] = 0;
+            if (in) {
+                const_u32_ptr cf = coef + (size_t)u * cstride;
+#pragma unroll
+                for (int j = 0; j < EB; ++j) w[i][j] = cf[j];
+            }
+#pragma unroll
+            for (int v = 0; v < V; ++v) x[i][v] = 0;
+            if (in && live) load_vec<V>(x[i], row_of(u));
+        }
+#pragma unroll
+        for (int i = 0; i < U; ++i)
+#pragma unroll
+            for (int j = 0; j < EB; ++j)
+#pragma unroll
+                for (int v = 0; v < V; ++v) mac96(lo[j][v], hi[j][v], x[i][v], w[i][j]);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -103,6 +140,9 @@ __global__ __launch_bounds__(256) void direct_accumulate_kernel(const AccArgs a)
     // pad <= 16: one sweep, rows of `pad` weights; else sweep-major runs of 16 (coef_index)
     const uint32_t cstride = a.pad <= 16u ? a.pad : 16u;
     const_u32_ptr coef = as_constant(a.coef) + (size_t)sweep * a.rows * 16u;
+    // weigh_rows' loop, written out: through the helper hipcc zeroes the weights of rows 1.. of every group before it branches on `in` (48
+    // scalar moves per group at EB = 16) where this form zeroes them only past the end, and a stripe-by-stripe loop of (256,128) decodes
+    // with 16 lost blocks — one wave per SIMD at most, nothing to hide them behind — measured 4.5 % slower (HISTORY.md)
     for (uint32_t ub = u0; ub < u1; ub += U) {
         uint32_t w[U][EB], x[U][V];
 #pragma unroll
@@ -118,7 +158,7 @@ __global__ __launch_bounds__(256) void direct_accumulate_kernel(const AccArgs a)
             }
 #pragma unroll
             for (int v = 0; v < V; ++v) x[i][v] = 0;
-            if (in && live) {  // a lost row holds anything: its weights are zero
+            if (in && live) {
                 const uint32_t* row = u < a.data_rows ? a.data + (size_t)u * a.S : a.parity + (size_t)as_constant(a.extra)[u - a.data_rows] * a.S;
                 load_vec<V>(x[i], row + col);
             }
@@ -526,6 +566,40 @@ int pad_of(int outputs)
     return outputs <= 16 ? pad : (outputs + 15) / 16 * 16;
 }
 
+// The instantiated VALU kernels: EB outputs per lane (the pad of the pass, 16 per sweep beyond that) x V words per lane, EB * V <= 16
+// accumulators — (1, 2, 4) x (4, 2, 1), 8 x (2, 1), 16 x 1, and no other pair.  launch(EB, V) gets the pair as constants.
+template <int N> using Int = std::integral_constant<int, N>;
+template <class Launch>
+void with_class(int eb, int v, Launch&& launch)
+{
+    switch (eb * 8 + v) {
+        case 1 * 8 + 4: launch(Int<1>(), Int<4>()); break;
+        case 1 * 8 + 2: launch(Int<1>(), Int<2>()); break;
+        case 1 * 8 + 1: launch(Int<1>(), Int<1>()); break;
+        case 2 * 8 + 4: launch(Int<2>(), Int<4>()); break;
+        case 2 * 8 + 2: launch(Int<2>(), Int<2>()); break;
+        case 2 * 8 + 1: launch(Int<2>(), Int<1>()); break;
+        case 4 * 8 + 4: launch(Int<4>(), Int<4>()); break;
+        case 4 * 8 + 2: launch(Int<4>(), Int<2>()); break;
+        case 4 * 8 + 1: launch(Int<4>(), Int<1>()); break;
+        case 8 * 8 + 2: launch(Int<8>(), Int<2>()); break;
+        case 8 * 8 + 1: launch(Int<8>(), Int<1>()); break;
+        default: launch(Int<16>(), Int<1>()); break;
+    }
+}
+
+// Words per lane: the widest V of the class `eb` (with_class) that divides every length in `lengths` (ORed together: V is a power of two)
+// and leaves every pointer in `pointers` (ORed) on a V-word boundary — everything a lane touches, read or written; then, where an entry
+// owns whole waves, halved while `fill` (its words; 0: lanes are flattened over entries) is shorter than a wave of such lanes
+// (64 words: V = 1 fills the wave where V = 4 would leave 48 lanes idle).
+int lane_words(int eb, uint64_t lengths, uintptr_t pointers, uint64_t fill = 0)
+{
+    int v = eb <= 4 ? 4 : eb == 8 ? 2 : 1;
+    while (v > 1 && ((lengths % v) != 0 || (pointers & (4u * v - 1u)) != 0)) v >>= 1;
+    while (v > 1 && fill != 0 && fill < 64u * (uint64_t)v) v >>= 1;
+    return v;
+}
+
 }  // namespace
 
 struct DirectPass {
@@ -620,29 +694,14 @@ static int launch_accumulate(DirectPass* p, const uint32_t* data, const uint32_t
 {
     const int pad = p->pad, sweeps = pad > 16 ? pad / 16 : 1, eb = std::min(pad, 16);
     const uint32_t chunks = (p->rows - row_begin + rows_per_chunk - 1) / rows_per_chunk;
-    const int vmax = eb <= 4 ? 4 : eb == 8 ? 2 : 1;
-    int v = vmax;
-    const uintptr_t align = (uintptr_t)data | (uintptr_t)parity | (uintptr_t)p->partial.get();
-    while (v > 1 && ((S % v) != 0 || (align & (4u * v - 1u)) != 0)) v >>= 1;
+    const int v = lane_words(eb, S, (uintptr_t)data | (uintptr_t)parity | (uintptr_t)p->partial.get());
     AccArgs a{data, parity, p->lists, p->coef, p->partial, S, p->rows, p->data_rows, (uint32_t)pad, rows_per_chunk, (S + 64u * v - 1u) / (64u * v), 0, row_begin, chunk_base, ppad};
     a.items = (uint64_t)chunks * a.col_chunks;
     const dim3 grid((unsigned)((a.items + 3) / 4), (unsigned)sweeps);
-#define FASTECC_ACC(EB, V) hipLaunchKernelGGL((direct_accumulate_kernel<EB, V>), grid, dim3(256), 0, st, a)
-    switch (eb * 8 + v) {
-        case 1 * 8 + 4: FASTECC_ACC(1, 4); break;
-        case 1 * 8 + 2: FASTECC_ACC(1, 2); break;
-        case 1 * 8 + 1: FASTECC_ACC(1, 1); break;
-        case 2 * 8 + 4: FASTECC_ACC(2, 4); break;
-        case 2 * 8 + 2: FASTECC_ACC(2, 2); break;
-        case 2 * 8 + 1: FASTECC_ACC(2, 1); break;
-        case 4 * 8 + 4: FASTECC_ACC(4, 4); break;
-        case 4 * 8 + 2: FASTECC_ACC(4, 2); break;
-        case 4 * 8 + 1: FASTECC_ACC(4, 1); break;
-        case 8 * 8 + 2: FASTECC_ACC(8, 2); break;
-        case 8 * 8 + 1: FASTECC_ACC(8, 1); break;
-        default: FASTECC_ACC(16, 1); break;
-    }
-#undef FASTECC_ACC
+    with_class(eb, v, [&](auto eb_c, auto v_c) {
+        constexpr int EB = eb_c, V = v_c;
+        hipLaunchKernelGGL((direct_accumulate_kernel<EB, V>), grid, dim3(256), 0, st, a);
+    });
     HIP_TRY(hipGetLastError());
     return FASTECC_OK;
 }
@@ -799,77 +858,43 @@ __global__ __launch_bounds__(256) void direct_batch_kernel(const BatchArgs a)
     const uint32_t sweep = blockIdx.y;
     const uint32_t cstride = a.pad <= 16u ? a.pad : 16u;
     const_u32_ptr coef = as_constant(a.coef) + (size_t)sweep * a.rows * 16u;
-    {
-        const uint64_t g = a.group_base + ((uint64_t)blockIdx.x * 4u + wave) * 64u + lane;
-        const bool live = g < a.groups;
-        const uint64_t word = live ? g * V : 0, entry = word / a.S, c = word - entry * a.S;
-        const uint64_t b = LIST ? (live ? a.list[entry] : 0) : entry;
-        const uint32_t* dbase = a.data + b * a.data_stride + c;
-        const uint64_t poff = b * a.parity_stride + c;  // (a lane's parity rows: a.parity + poff + row * S)
-        uint64_t lo[EB][V];
-        uint32_t hi[EB][V];
+    const uint64_t g = a.group_base + ((uint64_t)blockIdx.x * 4u + wave) * 64u + lane;
+    const bool live = g < a.groups;
+    const uint64_t word = live ? g * V : 0, entry = word / a.S, c = word - entry * a.S;
+    const uint64_t b = LIST ? (live ? a.list[entry] : 0) : entry;
+    const uint32_t* dbase = a.data + b * a.data_stride + c;
+    const uint64_t poff = b * a.parity_stride + c;  // (a lane's parity rows: a.parity + poff + row * S)
+    uint64_t lo[EB][V];
+    uint32_t hi[EB][V];
 #pragma unroll
-        for (int j = 0; j < EB; ++j)
+    for (int j = 0; j < EB; ++j)
 #pragma unroll
-            for (int v = 0; v < V; ++v) lo[j][v] = 0, hi[j][v] = 0;
-        for (uint32_t ub = 0; ub < a.rows; ub += U) {
-            uint32_t w[U][EB], x[U][V];
+        for (int v = 0; v < V; ++v) lo[j][v] = 0, hi[j][v] = 0;
+    weigh_rows<EB, V, U>(lo, hi, coef, cstride, 0, a.rows, live, [&](uint32_t u) {
+        return u < a.data_rows ? dbase + (size_t)u * a.S : a.parity + poff + (size_t)as_constant(a.extra)[u - a.data_rows] * a.S;
+    });
 #pragma unroll
-            for (int i = 0; i < U; ++i) {
-                const uint32_t u = ub + i;
-                const bool in = u < a.rows;  // wave-uniform
+    for (int j = 0; j < EB; ++j) {
+        const uint32_t t = sweep * EB + j;
+        if (t >= a.outputs) break;  // wave-uniform
+        const uint32_t p = as_constant(a.pos)[t];
+        uint32_t* out = (p & 1u) ? a.parity_out : a.data_out;
+        if (!out || !live) continue;  // (no stripe given for that kind of output: fastecc_decode_batch on a pass that also holds the lost parity blocks)
+        const uint64_t stride = (p & 1u) ? a.parity_stride : a.data_stride;
+        uint32_t r[V];
 #pragma unroll
-                for (int j = 0; j < EB; ++j) w[i][j] = 0;
-                if (in) {
-                    const_u32_ptr cf = coef + (size_t)u * cstride;
-#pragma unroll
-                    for (int j = 0; j < EB; ++j) w[i][j] = cf[j];
-                }
-#pragma unroll
-                for (int v = 0; v < V; ++v) x[i][v] = 0;
-                if (in && live) {
-                    const uint32_t* row = u < a.data_rows ? dbase + (size_t)u * a.S : a.parity + poff + (size_t)as_constant(a.extra)[u - a.data_rows] * a.S;
-                    load_vec<V>(x[i], row);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < U; ++i)
-#pragma unroll
-                for (int j = 0; j < EB; ++j)
-#pragma unroll
-                    for (int v = 0; v < V; ++v) mac96(lo[j][v], hi[j][v], x[i][v], w[i][j]);
-        }
-#pragma unroll
-        for (int j = 0; j < EB; ++j) {
-            const uint32_t t = sweep * EB + j;
-            if (t >= a.outputs) break;  // wave-uniform
-            const uint32_t p = as_constant(a.pos)[t];
-            uint32_t* out = (p & 1u) ? a.parity_out : a.data_out;
-            if (!out || !live) continue;  // (no stripe given for that kind of output: fastecc_decode_batch on a pass that also holds the lost parity blocks)
-            const uint64_t stride = (p & 1u) ? a.parity_stride : a.data_stride;
-            uint32_t r[V];
-#pragma unroll
-            for (int v = 0; v < V; ++v) r[v] = reduce96(lo[j][v], hi[j][v]);
-            store_vec<V>(out + b * stride + (size_t)(p >> 1) * a.S + c, r);
-        }
+        for (int v = 0; v < V; ++v) r[v] = reduce96(lo[j][v], hi[j][v]);
+        store_vec<V>(out + b * stride + (size_t)(p >> 1) * a.S + c, r);
     }
 }
 
 int direct_pass_rows(const DirectPass* p) { return p && p->built ? (int)p->rows : 0; }
 
-static int batch_vec(const DirectPass* p, const void* data, const void* parity, uint64_t S)
-{
-    const int eb = std::min(p->pad, 16), vmax = eb <= 4 ? 4 : eb == 8 ? 2 : 1;
-    const uintptr_t align = (uintptr_t)data | (uintptr_t)parity;
-    int v = vmax;
-    while (v > 1 && ((S % v) != 0 || (align & (4u * v - 1u)) != 0)) v >>= 1;
-    return v;
-}
-
 uint64_t direct_batch_waves(const DirectPass* p, const void* data, const void* parity, uint64_t S, uint64_t count)
 {
     if (!p || !p->built) return 0;
-    const uint64_t v = (uint64_t)batch_vec(p, data, parity, S), sweeps = p->pad > 16 ? (uint64_t)p->pad / 16u : 1u;
+    const uint64_t v = (uint64_t)lane_words(std::min(p->pad, 16), S, (uintptr_t)data | (uintptr_t)parity);
+    const uint64_t sweeps = p->pad > 16 ? (uint64_t)p->pad / 16u : 1u;
     return (count * S / v + 63u) / 64u * sweeps;
 }
 
@@ -879,34 +904,19 @@ int direct_run_batch(DirectPass* p, const uint32_t* data, const uint32_t* parity
     if (!p || !p->built || S == 0 || S > 0xFFFFFFFFull || count == 0) return FASTECC_E_INVAL;
     const int pad = p->pad, sweeps = pad > 16 ? pad / 16 : 1, eb = std::min(pad, 16);
     // every pointer a lane touches: the stripes it reads and the ones it writes (data_out / parity_out are data / parity or null)
-    const int v = batch_vec(p, (const void*)((uintptr_t)data | (uintptr_t)data_out), (const void*)((uintptr_t)parity | (uintptr_t)parity_out), S);
+    const int v = lane_words(eb, S, (uintptr_t)data | (uintptr_t)data_out | (uintptr_t)parity | (uintptr_t)parity_out);
     BatchArgs a{data, parity, p->lists, p->coef, p->lists + DIRECT_CAP, data_out, parity_out, data_stride, parity_stride, count * S / (uint64_t)v, 0,
                 (uint32_t)S, p->rows, p->data_rows, (uint32_t)pad, (uint32_t)p->outputs, list};
     // a dispatch holds fewer than 2^32 work-items per dimension: at most 2^22 workgroups (2^30 groups) per launch
     constexpr uint64_t LAUNCH_GROUPS = 1ull << 30;
     for (a.group_base = 0; a.group_base < a.groups; a.group_base += LAUNCH_GROUPS) {
-    const dim3 grid((unsigned)((std::min(a.groups - a.group_base, LAUNCH_GROUPS) + 255u) / 256u), (unsigned)sweeps);
-#define FASTECC_BATCH(EB, V)                                                                          \
-    do {                                                                                              \
-        if (list) hipLaunchKernelGGL((direct_batch_kernel<EB, V, true>), grid, dim3(256), 0, st, a);  \
-        else hipLaunchKernelGGL((direct_batch_kernel<EB, V>), grid, dim3(256), 0, st, a);             \
-    } while (0)
-    switch (eb * 8 + v) {
-        case 1 * 8 + 4: FASTECC_BATCH(1, 4); break;
-        case 1 * 8 + 2: FASTECC_BATCH(1, 2); break;
-        case 1 * 8 + 1: FASTECC_BATCH(1, 1); break;
-        case 2 * 8 + 4: FASTECC_BATCH(2, 4); break;
-        case 2 * 8 + 2: FASTECC_BATCH(2, 2); break;
-        case 2 * 8 + 1: FASTECC_BATCH(2, 1); break;
-        case 4 * 8 + 4: FASTECC_BATCH(4, 4); break;
-        case 4 * 8 + 2: FASTECC_BATCH(4, 2); break;
-        case 4 * 8 + 1: FASTECC_BATCH(4, 1); break;
-        case 8 * 8 + 2: FASTECC_BATCH(8, 2); break;
-        case 8 * 8 + 1: FASTECC_BATCH(8, 1); break;
-        default: FASTECC_BATCH(16, 1); break;
+        const dim3 grid((unsigned)((std::min(a.groups - a.group_base, LAUNCH_GROUPS) + 255u) / 256u), (unsigned)sweeps);
+        with_class(eb, v, [&](auto eb_c, auto v_c) {
+            constexpr int EB = eb_c, V = v_c;
+            if (list) hipLaunchKernelGGL((direct_batch_kernel<EB, V, true>), grid, dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((direct_batch_kernel<EB, V>), grid, dim3(256), 0, st, a);
+        });
     }
-    }
-#undef FASTECC_BATCH
     HIP_TRY(hipGetLastError());
     return FASTECC_OK;
 }
@@ -916,11 +926,11 @@ int direct_run_batch(DirectPass* p, const uint32_t* data, const uint32_t* parity
 // The launch gets a list of entries (stripe of the pool, pass of the pattern set) and the set's table of pass descriptors — what BatchArgs
 // takes from one DirectPass, per pattern.  Weights live in SGPRs, so a wave must not span two entries: an entry owns
 // ceil(S / (64 V)) WHOLE waves, and a wave finds its entry and column base from its index in the launch (made provably uniform by
-// readfirstlane), loads the entry and its descriptor with scalar loads and masks the lanes whose column is >= S.  The row loop, the 96-bit
-// accumulators, the single reduction and the canonical store are direct_batch_kernel's; the loop bound `rows` differs per pattern and is
+// readfirstlane), loads the entry and its descriptor with scalar loads and masks the lanes whose column is >= S.  The row loop is
+// weigh_rows; the single reduction and the canonical store are direct_batch_kernel's; the loop bound `rows` differs per pattern and is
 // wave-uniform.  EB is the pad class of every pass of the launch (the host sorts the entries by it), which is also the row stride of
 // their weight tables ([rows][pad], pad = EB <= 16: one sweep), so no lane multiplies by padding weights of a smaller pattern.
-// Blocks shorter than 64 V words leave lanes of their wave idle (S = 1: 63 of 64) — the price of uniform weights; set_vec picks the widest
+// Blocks shorter than 64 V words leave lanes of their wave idle (S = 1: 63 of 64) — the price of uniform weights; lane_words picks the widest
 // V that still fills a wave, and fastecc_repair_batch (lanes flattened over stripes) remains the tool for one pattern and very short blocks.
 // In place like direct_batch_kernel; here a lane reads all rows of its own columns before it writes them and nobody else touches them.
 // ------------------------------------------------------------------------------------------------
@@ -964,33 +974,9 @@ __global__ __launch_bounds__(256) void direct_set_kernel(const SetArgs a)
     for (int j = 0; j < EB; ++j)
 #pragma unroll
         for (int v = 0; v < V; ++v) lo[j][v] = 0, hi[j][v] = 0;
-    for (uint32_t ub = 0; ub < rows; ub += U) {
-        uint32_t wt[U][EB], x[U][V];
-#pragma unroll
-        for (int i = 0; i < U; ++i) {
-            const uint32_t u = ub + i;
-            const bool in = u < rows;  // wave-uniform
-#pragma unroll
-            for (int j = 0; j < EB; ++j) wt[i][j] = 0;
-            if (in) {
-                const_u32_ptr cf = coef + (size_t)u * EB;
-#pragma unroll
-                for (int j = 0; j < EB; ++j) wt[i][j] = cf[j];
-            }
-#pragma unroll
-            for (int v = 0; v < V; ++v) x[i][v] = 0;
-            if (in && live) {  // a lost row holds anything: its weights are zero
-                const uint32_t* row = u < data_rows ? dbase + (size_t)u * a.S : a.parity + poff + (size_t)extra[u - data_rows] * a.S;
-                load_vec<V>(x[i], row);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < U; ++i)
-#pragma unroll
-            for (int j = 0; j < EB; ++j)
-#pragma unroll
-                for (int v = 0; v < V; ++v) mac96(lo[j][v], hi[j][v], x[i][v], wt[i][j]);
-    }
+    weigh_rows<EB, V, U>(lo, hi, coef, EB, 0, rows, live, [&](uint32_t u) {  // (the stride: the class itself, a constant)
+        return u < data_rows ? dbase + (size_t)u * a.S : a.parity + poff + (size_t)extra[u - data_rows] * a.S;
+    });
 #pragma unroll
     for (int j = 0; j < EB; ++j) {
         if ((uint32_t)j < outputs) {  // wave-uniform
@@ -1009,28 +995,34 @@ __global__ __launch_bounds__(256) void direct_set_kernel(const SetArgs a)
 
 constexpr uint64_t SET_LAUNCH_WAVES = 1ull << 24;  // 2^30 lane groups, as LAUNCH_GROUPS of direct_run_batch
 
-int direct_set_describe(const DirectPass* p, DirectSetPass* out)
+// What the set and read kernels take from one built pass.  cstride = min(pad, 16): the row stride inside a sweep of the table (coef_index)
+static int describe_pass(const DirectPass* p, int pad_max, DirectSetPass* out)
 {
-    if (!p || !p->built || p->pad > 16) return FASTECC_E_INVAL;  // (one sweep: at most 16 outputs)
-    *out = DirectSetPass{p->coef, p->lists, p->lists + DIRECT_CAP, p->rows, p->data_rows, (uint32_t)p->outputs, (uint32_t)p->pad};
+    if (!p || !p->built || p->pad > pad_max) return FASTECC_E_INVAL;
+    *out = DirectSetPass{p->coef, p->lists, p->lists + DIRECT_CAP, p->rows, p->data_rows, (uint32_t)p->outputs, (uint32_t)std::min(p->pad, 16)};
     return FASTECC_OK;
 }
 
-// Words per lane: batch_vec's rule for the class, then halved while a block is shorter than a wave of such lanes (S = 64: V = 1 fills the
-// wave where V = 4 would leave 48 lanes idle)
-static int set_vec(int eb, const void* data, const void* parity, uint64_t S)
+int direct_set_describe(const DirectPass* p, DirectSetPass* out) { return describe_pass(p, 16, out); }  // (one sweep: at most 16 outputs)
+
+// The launches of a list of entries that own `wpe` whole waves each: launch(e0, waves) for the entries from e0 on
+template <class Launch>
+static int launch_entries(uint64_t n_entries, uint64_t wpe, Launch&& launch)
 {
-    const uintptr_t align = (uintptr_t)data | (uintptr_t)parity;
-    int v = eb <= 4 ? 4 : eb == 8 ? 2 : 1;
-    while (v > 1 && ((S % v) != 0 || (align & (4u * v - 1u)) != 0)) v >>= 1;
-    while (v > 1 && S < 64u * (uint64_t)v) v >>= 1;
-    return v;
+    if (wpe > SET_LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (a block or window of more than 2^30 lane groups)
+    const uint64_t per_launch = SET_LAUNCH_WAVES / wpe;
+    for (uint64_t e0 = 0; e0 < n_entries; e0 += per_launch) {
+        launch(e0, (uint32_t)(std::min(per_launch, n_entries - e0) * wpe));
+        HIP_TRY(hipGetLastError());
+    }
+    return FASTECC_OK;
 }
+
+static uint64_t waves_of(uint64_t words, int v) { return (words + 64u * (uint64_t)v - 1u) / (64u * (uint64_t)v); }
 
 uint64_t direct_set_waves_per_entry(int eb, const void* data, const void* parity, uint64_t S)
 {
-    const uint64_t v = (uint64_t)set_vec(eb, data, parity, S);
-    return (S + 64u * v - 1u) / (64u * v);
+    return waves_of(S, lane_words(eb, S, (uintptr_t)data | (uintptr_t)parity, S));
 }
 
 int direct_run_set(int eb, const DirectSetPass* passes, const DirectSetEntry* entries, uint64_t n_entries, const uint32_t* data, const uint32_t* parity,
@@ -1038,36 +1030,17 @@ int direct_run_set(int eb, const DirectSetPass* passes, const DirectSetEntry* en
 {
     if (!passes || !entries || n_entries == 0 || S == 0 || S > 0xFFFFFFFFull || eb < 1 || eb > 16 || (eb & (eb - 1))) return FASTECC_E_INVAL;
     // every pointer a lane touches: the stripes it reads and the ones it writes (data_out / parity_out are data / parity or null)
-    const void* dptr = (const void*)((uintptr_t)data | (uintptr_t)data_out);
-    const void* pptr = (const void*)((uintptr_t)parity | (uintptr_t)parity_out);
-    const int v = set_vec(eb, dptr, pptr, S);
-    const uint64_t wpe = direct_set_waves_per_entry(eb, dptr, pptr, S);
-    if (wpe > SET_LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (a block of more than 2^30 lane groups: the caller goes stripe by stripe)
+    const int v = lane_words(eb, S, (uintptr_t)data | (uintptr_t)data_out | (uintptr_t)parity | (uintptr_t)parity_out, S);
+    const uint64_t wpe = waves_of(S, v);  // (more than SET_LAUNCH_WAVES: refused, the caller goes stripe by stripe)
     SetArgs a{data, parity, data_out, parity_out, data_stride, parity_stride, entries, passes, 0, (uint32_t)wpe, (uint32_t)S};
-    const uint64_t launch_entries = SET_LAUNCH_WAVES / wpe;
-    for (uint64_t e0 = 0; e0 < n_entries; e0 += launch_entries) {
+    return launch_entries(n_entries, wpe, [&](uint64_t e0, uint32_t waves) {
         a.entries = entries + e0;
-        a.waves = (uint32_t)(std::min(launch_entries, n_entries - e0) * wpe);
-        const dim3 grid((a.waves + 3u) / 4u);
-#define FASTECC_SET(EB, V) hipLaunchKernelGGL((direct_set_kernel<EB, V>), grid, dim3(256), 0, st, a)
-        switch (eb * 8 + v) {
-            case 1 * 8 + 4: FASTECC_SET(1, 4); break;
-            case 1 * 8 + 2: FASTECC_SET(1, 2); break;
-            case 1 * 8 + 1: FASTECC_SET(1, 1); break;
-            case 2 * 8 + 4: FASTECC_SET(2, 4); break;
-            case 2 * 8 + 2: FASTECC_SET(2, 2); break;
-            case 2 * 8 + 1: FASTECC_SET(2, 1); break;
-            case 4 * 8 + 4: FASTECC_SET(4, 4); break;
-            case 4 * 8 + 2: FASTECC_SET(4, 2); break;
-            case 4 * 8 + 1: FASTECC_SET(4, 1); break;
-            case 8 * 8 + 2: FASTECC_SET(8, 2); break;
-            case 8 * 8 + 1: FASTECC_SET(8, 1); break;
-            default: FASTECC_SET(16, 1); break;
-        }
-#undef FASTECC_SET
-        HIP_TRY(hipGetLastError());
-    }
-    return FASTECC_OK;
+        a.waves = waves;
+        with_class(eb, v, [&](auto eb_c, auto v_c) {
+            constexpr int EB = eb_c, V = v_c;
+            hipLaunchKernelGGL((direct_set_kernel<EB, V>), dim3((waves + 3u) / 4u), dim3(256), 0, st, a);
+        });
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1125,84 +1098,48 @@ __global__ __launch_bounds__(256) void direct_read_kernel(const ReadArgs a)
     const_u32_ptr coef = as_constant(d->coef) + ((size_t)(j >> 4) * rows * cstride + (j & 15u));  // coef_index(u, j) = this + u * cstride
     const_u32_ptr extra = as_constant(d->extra);
     const uint64_t poff = b * a.parity_stride + a.col0 + c;  // (a lane's parity rows: a.parity + poff + row * S)
-    uint64_t lo[V];
-    uint32_t hi[V];
+    uint64_t lo[1][V];
+    uint32_t hi[1][V];
 #pragma unroll
-    for (int v = 0; v < V; ++v) lo[v] = 0, hi[v] = 0;
-    for (uint32_t ub = 0; ub < rows; ub += U) {
-        uint32_t wt[U], x[U][V];
-#pragma unroll
-        for (int i = 0; i < U; ++i) {
-            const uint32_t u = ub + i;
-            const bool in = u < rows;  // wave-uniform
-            wt[i] = 0;
-            if (in) wt[i] = coef[(size_t)u * cstride];
-#pragma unroll
-            for (int v = 0; v < V; ++v) x[i][v] = 0;
-            if (in && live) {  // a lost row holds anything: its weight is zero
-                const uint32_t* row = u < data_rows ? dbase + (size_t)u * a.S : a.parity + poff + (size_t)extra[u - data_rows] * a.S;
-                load_vec<V>(x[i], row);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < U; ++i)
-#pragma unroll
-            for (int v = 0; v < V; ++v) mac96(lo[v], hi[v], x[i][v], wt[i]);
-    }
+    for (int v = 0; v < V; ++v) lo[0][v] = 0, hi[0][v] = 0;
+    weigh_rows<1, V, U>(lo, hi, coef, cstride, 0, rows, live, [&](uint32_t u) {
+        return u < data_rows ? dbase + (size_t)u * a.S : a.parity + poff + (size_t)extra[u - data_rows] * a.S;
+    });
     if (live) {
         uint32_t r[V];
 #pragma unroll
-        for (int v = 0; v < V; ++v) r[v] = reduce96(lo[v], hi[v]);
+        for (int v = 0; v < V; ++v) r[v] = reduce96(lo[0][v], hi[0][v]);
         store_vec<V>(dst, r);
     }
 }
 
-int direct_read_describe(const DirectPass* p, DirectSetPass* out)
-{
-    if (!p || !p->built) return FASTECC_E_INVAL;
-    *out = DirectSetPass{p->coef, p->lists, p->lists + DIRECT_CAP, p->rows, p->data_rows, (uint32_t)p->outputs, (uint32_t)std::min(p->pad, 16)};
-    return FASTECC_OK;
-}
+int direct_read_describe(const DirectPass* p, DirectSetPass* out) { return describe_pass(p, pad_of(DIRECT_CAP), out); }  // (any pad)
 
-// Words per lane: set_vec's rule applied to everything a lane touches — the pool (rows S words apart), the output rows (width words apart)
-// and the window's first column — then halved while the window is shorter than a wave of such lanes
-static int read_vec(const void* data, const void* parity, const void* out, uint64_t S, uint64_t col0, uint64_t width)
-{
-    const uintptr_t align = (uintptr_t)data | (uintptr_t)parity | (uintptr_t)out;
-    int v = 4;
-    while (v > 1 && ((S % v) != 0 || (col0 % v) != 0 || (width % v) != 0 || (align & (4u * v - 1u)) != 0)) v >>= 1;
-    while (v > 1 && width < 64u * (uint64_t)v) v >>= 1;
-    return v;
-}
-
+// Words per lane, one output each (class 1): a lane touches the pool (rows S words apart), the output rows (width words apart) and the
+// window's first column; an entry's waves are filled by its window
 uint64_t direct_read_waves_per_entry(const void* data, const void* parity, const void* out, uint64_t S, uint64_t col0, uint64_t width)
 {
-    const uint64_t v = (uint64_t)read_vec(data, parity, out, S, col0, width);
-    return (width + 64u * v - 1u) / (64u * v);
+    return waves_of(width, lane_words(1, S | col0 | width, (uintptr_t)data | (uintptr_t)parity | (uintptr_t)out, width));
 }
 
 int direct_run_read(const DirectSetPass* passes, const DirectReadEntry* entries, uint64_t n_entries, const uint32_t* data, const uint32_t* parity, uint32_t* out,
                     uint64_t S, uint64_t col0, uint64_t width, uint64_t data_stride, uint64_t parity_stride, hipStream_t st)
 {
     if (!passes || !entries || !out || n_entries == 0 || S == 0 || S > 0xFFFFFFFFull || width == 0 || col0 > S || width > S - col0) return FASTECC_E_INVAL;
-    const int v = read_vec(data, parity, out, S, col0, width);
-    const uint64_t wpe = direct_read_waves_per_entry(data, parity, out, S, col0, width);
-    if (wpe > SET_LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (a window of more than 2^30 lane groups)
+    const int v = lane_words(1, S | col0 | width, (uintptr_t)data | (uintptr_t)parity | (uintptr_t)out, width);  // (direct_read_waves_per_entry's)
+    const uint64_t wpe = waves_of(width, v);
     ReadArgs a{data, parity, out, data_stride, parity_stride, entries, passes, 0, 0, (uint32_t)wpe, (uint32_t)S, (uint32_t)col0, (uint32_t)width};
-    const uint64_t launch_entries = SET_LAUNCH_WAVES / wpe;
-    for (uint64_t e0 = 0; e0 < n_entries; e0 += launch_entries) {
+    return launch_entries(n_entries, wpe, [&](uint64_t e0, uint32_t waves) {
         a.entries = entries + e0;
         a.row_base = e0;
-        a.waves = (uint32_t)(std::min(launch_entries, n_entries - e0) * wpe);
-        const dim3 grid((a.waves + 3u) / 4u);
+        a.waves = waves;
+        const dim3 grid((waves + 3u) / 4u);
         switch (v) {
             case 4: hipLaunchKernelGGL(direct_read_kernel<4>, grid, dim3(256), 0, st, a); break;
             case 2: hipLaunchKernelGGL(direct_read_kernel<2>, grid, dim3(256), 0, st, a); break;
             default: hipLaunchKernelGGL(direct_read_kernel<1>, grid, dim3(256), 0, st, a); break;
         }
-        HIP_TRY(hipGetLastError());
-    }
-    return FASTECC_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

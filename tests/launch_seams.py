@@ -50,7 +50,7 @@ LAUNCH_GROUPS, SET_LAUNCH_WAVES, LAUNCH_WAVES, POOL_LAUNCH_WAVES, MAX_LAUNCH_WAV
 
 # ---- the launchers' own arithmetic (device pools are at least 16-byte aligned) ----
 def set_waves_per_entry(eb, S):
-    """direct.hip: set_vec and direct_set_waves_per_entry for pad class eb"""
+    """direct.hip: lane_words and direct_set_waves_per_entry for pad class eb"""
     v = 4 if eb <= 4 else 2 if eb == 8 else 1
     while v > 1 and S % v:
         v >>= 1
@@ -60,7 +60,7 @@ def set_waves_per_entry(eb, S):
 
 
 def read_waves_per_entry(S, col0, width):
-    """direct.hip: read_vec and direct_read_waves_per_entry"""
+    """direct.hip: lane_words and direct_read_waves_per_entry"""
     v = 4
     while v > 1 and (S % v or col0 % v or width % v):
         v >>= 1
@@ -70,7 +70,7 @@ def read_waves_per_entry(S, col0, width):
 
 
 def batch_groups(eb, S, count):
-    """direct.hip: batch_vec and BatchArgs::groups"""
+    """direct.hip: lane_words and BatchArgs::groups"""
     v = 4 if eb <= 4 else 2 if eb == 8 else 1
     while v > 1 and S % v:
         v >>= 1
