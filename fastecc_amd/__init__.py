@@ -129,6 +129,9 @@ def lib():
     L.fastecc_update_parity.argtypes, L.fastecc_update_parity.restype = [vp, vp, u64p, u64, vp, vp, i32, vp], i32
     L.fastecc_update_batch.argtypes, L.fastecc_update_batch.restype = [vp, vp, vp, u64, u64p, u64, vp, vp], i32
     L.fastecc_update_parity_batch.argtypes, L.fastecc_update_parity_batch.restype = [vp, vp, u64, u64p, u64, vp, vp, vp], i32
+    L.fastecc_update_batch_set.argtypes, L.fastecc_update_batch_set.restype = [vp, vp, vp, u64, ctypes.POINTER(u32), u64p, u64, vp, vp], i32
+    L.fastecc_update_parity_batch_set.argtypes = [vp, vp, u64, ctypes.POINTER(u32), u64p, u64, vp, vp, vp]
+    L.fastecc_update_parity_batch_set.restype = i32
     L.fastecc_code_coefficient.argtypes = [u64, u64, ctypes.c_uint, u64, u64, ctypes.POINTER(u32)]
     L.fastecc_code_coefficient.restype = i32
     L.fastecc_gf_berlekamp_massey.argtypes = [ctypes.POINTER(u32), u32, ctypes.POINTER(u32), u32]
@@ -639,6 +642,28 @@ class Encoder:
         n, arr = self._block_list(writes)
         _check(lib().fastecc_update_parity_batch(self._h, _addr(parity), count, arr, n, _addr(old), _addr(new), stream or None),
                "fastecc_update_parity_batch")
+        return parity
+
+    def update_batch_set(self, data, parity, count, pattern_of, writes, new, stream=0):
+        """update_batch for a pool whose stripes miss blocks: stripe b under pattern pattern_of[b] of the decode_prepare_set set (PATTERN_NONE,
+        or a pattern that loses nothing: whole).  Every PRESENT block of a touched stripe becomes what encode gives for the stripe's true data
+        — absent data blocks as decode would rebuild them — with the written blocks replaced; absent blocks are neither read nor written, so a
+        later repair_batch_set under the same patterns completes the stripes, and read_batch_set of an absent written block returns its new row."""
+        count = self._batch_count(count)
+        keep, po = self._pattern_list(pattern_of, count)
+        n, arr = self._block_list(writes)
+        _check(lib().fastecc_update_batch_set(self._h, _addr(data), _addr(parity), count, po, arr, n, _addr(new), stream or None), "fastecc_update_batch_set")
+        del keep
+        return data, parity
+
+    def update_parity_batch_set(self, parity, count, pattern_of, writes, new, old=None, stream=0):
+        """update_parity_batch that leaves the absent parity blocks of every touched stripe alone (only the parity flags of a pattern matter)."""
+        count = self._batch_count(count)
+        keep, po = self._pattern_list(pattern_of, count)
+        n, arr = self._block_list(writes)
+        _check(lib().fastecc_update_parity_batch_set(self._h, _addr(parity), count, po, arr, n, _addr(old), _addr(new), stream or None),
+               "fastecc_update_parity_batch_set")
+        del keep
         return parity
 
     def pack_blocks(self, raw, packed, stream=0, mem=MEM_DEVICE):

@@ -157,7 +157,9 @@ struct PatternSet {
     std::vector<uint8_t> cls;           // ... log2 of that pass's pad (1, 2, 4, 8, 16): the class a launch is templated on
     std::vector<uint32_t> rows;         // ... the rows it reads
     std::vector<std::vector<uint32_t>> lost_data;  // ... its lost data blocks, in the order of the pass's outputs (fastecc_read_batch_set)
+    std::vector<std::vector<uint32_t>> lost_parity;  // ... its lost parity blocks, increasing (fastecc_update_batch_set)
     DeviceBuf<DirectSetPass> d_passes;  // device: the descriptor table, entry q = pattern q's pass
+    DeviceBuf<uint32_t> d_lost_parity;  // device: P + 1 rows of SET_LOST_ROW words, row q = lost_parity[q] padded with SET_LOST_END; row P loses nothing
     // one call's entries, sorted by class (list.dev is an internal buffer: ordered between streams by the context's buf_event).  Outlives the set.
     StagedList<DirectSetEntry> list;
     DirectPass* pass(uint64_t q) const { return kind[q] == DATA ? tables[q].data.get() : kind[q] == PARITY ? tables[q].parity.get() : tables[q].both.get(); }
@@ -1812,7 +1814,9 @@ int fill_pattern_set(fastecc_ctx* c, const std::vector<LostLists>& lists, Patter
     fresh->cls.assign(P, 0);
     fresh->rows.assign(P, 0);
     fresh->lost_data.assign(P, {});
+    fresh->lost_parity.assign(P, {});
     std::vector<DirectSetPass> desc(P, DirectSetPass{});
+    std::vector<uint32_t> lost_rows((P + 1) * SET_LOST_ROW, SET_LOST_END);
     Prepare geometry(c, nullptr, nullptr);
     PhaseTimer quiet;  // one line per set, not two per pattern
     quiet.on = false;
@@ -1826,9 +1830,14 @@ int fill_pattern_set(fastecc_ctx* c, const std::vector<LostLists>& lists, Patter
         while ((1u << fresh->cls[q]) < desc[q].cstride) fresh->cls[q]++;
         fresh->rows[q] = desc[q].rows;
         fresh->lost_data[q] = l.R;
+        fresh->lost_parity[q] = l.Pl;
+        std::sort(fresh->lost_parity[q].begin(), fresh->lost_parity[q].end());
+        std::copy(fresh->lost_parity[q].begin(), fresh->lost_parity[q].end(), lost_rows.begin() + q * SET_LOST_ROW);  // (at most SET_MAX_LOST < SET_LOST_ROW)
     }
     RC_TRY(fresh->d_passes.alloc(P));
     HIP_TRY(hipMemcpy(fresh->d_passes, desc.data(), P * sizeof(DirectSetPass), hipMemcpyHostToDevice));
+    RC_TRY(fresh->d_lost_parity.alloc(lost_rows.size()));
+    HIP_TRY(hipMemcpy(fresh->d_lost_parity, lost_rows.data(), lost_rows.size() * 4, hipMemcpyHostToDevice));
     return FASTECC_OK;
 }
 
@@ -2088,6 +2097,18 @@ int read_batch_impl(fastecc_ctx* c, const void* data, const void* parity, uint64
 }
 
 }  // namespace
+
+// The context's pattern set as the degraded writes see it (drivers.hpp; update.hip)
+bool pattern_set_view(const fastecc_ctx* c, PatternSetView* out)
+{
+    const PatternSet* s = c->pattern_set;
+    if (!s) return false;
+    *out = PatternSetView{s->tables.size(), s->d_passes.get(), s->d_lost_parity.get()};
+    return true;
+}
+const std::vector<uint32_t>& pattern_lost_data(const fastecc_ctx* c, uint64_t q) { return c->pattern_set->lost_data[q]; }
+const std::vector<uint32_t>& pattern_lost_parity(const fastecc_ctx* c, uint64_t q) { return c->pattern_set->lost_parity[q]; }
+uint32_t pattern_rows(const fastecc_ctx* c, uint64_t q) { return c->pattern_set->rows[q]; }
 
 // The scrubber's grouped repair (drivers.hpp): a pattern set of the lost sets, private to the call — fill_pattern_set, run_pattern_set
 // over the (stripe, set) list, and the set freed once the stream's work is done

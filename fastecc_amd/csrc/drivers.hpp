@@ -134,6 +134,22 @@ constexpr size_t SET_MAX_LOST = 16;  // one direct pass of a single sweep: pad <
 // call lock itself and returns only when the stream's work is done and the private set is freed.
 int repair_lost_sets(fastecc_ctx* c, void* data, void* parity, const std::vector<std::vector<uint32_t>>& lost_sets, const std::vector<uint64_t>& stripes,
                      const std::vector<uint32_t>& set_of, void* stream);
+// ---- decode.hip, for the degraded writes (update.hip: fastecc_update_batch_set) ----
+// What a write under the context's pattern set (fastecc_decode_prepare_set) needs of it; PatternSet itself stays private to decode.hip.  The caller
+// holds c->mu, and everything is valid until the lock is released (a later fastecc_decode_prepare_set waits for the enqueued work: wait_idle).
+constexpr int SET_LOST_ROW = (int)SET_MAX_LOST + 1;  // words per pattern of lost_parity: its lost parity blocks, increasing, then SET_LOST_END to the end
+constexpr uint32_t SET_LOST_END = 0xFFFFFFFFu;       // (a pattern loses at most SET_MAX_LOST blocks: every row ends with at least one)
+struct PatternSetView {
+    uint64_t patterns;            // P
+    const DirectSetPass* passes;  // device: the descriptor table of direct_run_read, entry q = pattern q's pass
+    const uint32_t* lost_parity;  // device: P + 1 rows of SET_LOST_ROW words; row P loses nothing (a whole stripe)
+};
+bool pattern_set_view(const fastecc_ctx* c, PatternSetView* out);  // false: no set prepared
+// pattern q < P of that set: its lost data blocks in the order of its pass's outputs (DirectReadEntry::out), its lost parity blocks (increasing),
+// the rows its pass reads
+const std::vector<uint32_t>& pattern_lost_data(const fastecc_ctx* c, uint64_t q);
+const std::vector<uint32_t>& pattern_lost_parity(const fastecc_ctx* c, uint64_t q);
+uint32_t pattern_rows(const fastecc_ctx* c, uint64_t q);
 // ---- host_stage.hip: stripes in host memory ----
 // PAGEABLE host memory (what RS.cpp's malloc'ed buffers are) <-> device.  The runtime's own pageable download stages through pinned memory
 // with one copying host thread: 2 GiB took 89 ms (24 GB/s) on a link that moves them in 37 ms.  Here a ring of pinned slots sits between the

@@ -1,4 +1,5 @@
-// update.hip — small writes: fastecc_update, fastecc_update_parity, their pool forms fastecc_update_batch, fastecc_update_parity_batch, and
+// update.hip — small writes: fastecc_update, fastecc_update_parity, their pool forms fastecc_update_batch, fastecc_update_parity_batch, the pool forms for
+// stripes that miss blocks fastecc_update_batch_set, fastecc_update_parity_batch_set, and
 // fastecc_code_coefficient (include/fastecc.h).
 //
 // The code is linear, so after data blocks i_u change by D_u = new_u - old_u the parity changes by
@@ -26,6 +27,13 @@
 //                          <= T rows in VGPRs (no delta buffer) and streams its parity blocks exactly as update_parity_kernel does;
 //   update_scatter_kernel: after the last round, fastecc_update_batch only: new_blocks row u into its data block (several waves of the parity
 //                          kernel need the same old row, so the store waits for a later kernel on the same stream: no race, no flag).
+//
+// A pool whose stripes miss blocks (fastecc_update_batch_set / _update_parity_batch_set): stripe b under pattern pattern_of[b] of the
+// set of fastecc_decode_prepare_set.  The same host code (update_batch_run with a SetForm), and on the stream
+//   direct_run_read      : the old rows of the written data blocks that are absent, rebuilt into UpdateState::d_recon before any parity launch;
+//   update_set_kernel    : update_batch_kernel with each old row at an offset the host chose (the pool, or d_recon) and the stripe's absent parity
+//                          blocks skipped — neither loaded nor stored;
+//   update_scatter_kernel: only the writes whose data block is present.
 #include <algorithm>
 #include <atomic>
 #include <vector>
@@ -378,12 +386,137 @@ __global__ __launch_bounds__(256) void update_batch_kernel(const BatchArgs a)
     }
 }
 
+// ---- a pool of stripes with absent blocks (fastecc_update_batch_set / _update_parity_batch_set) ----
+constexpr int SET_LIST_WORDS = LIST_WORDS + 2;  // ... and where the write's old row is: its offset in words from SetArgs::old_base (low, high word; negative where the
+                                                // row lies below the base) — the pool's data block, or for an ABSENT data block its row of the reconstruction
+                                                // buffer; the parity form: its row of old_blocks.  An absent block's write has ROW_ABSENT set in its row word.
+constexpr int SET_SEG_HEAD = SEG_HEAD + 1;      // ... and the offset (words) of its stripe's row of the pattern set's lost parity blocks
+constexpr uint32_t ROW_ABSENT = 0x80000000u;    // (a call has fewer than 2^31 rows: update_batch_args)
+constexpr uint32_t OLD_IN_POOL = 0xFFFFFFFFu;   // host: SetForm::old_row of a write whose data block is present
+
+struct SetArgs {
+    BatchArgs b;               // list and segs in the two formats above
+    const uint32_t* old_base;  // what the old rows' offsets count from: the pool's data, else old_blocks, else new_blocks (no old rows: masked away)
+    const uint32_t* lost;      // the pattern set's lost parity blocks (drivers.hpp: PatternSetView::lost_parity)
+};
+
+// update_batch_kernel for stripes that miss blocks.  The old row of a write comes from the pool or from the reconstruction buffer — the host has put its
+// offset into the list, so the kernel chooses nothing and the 2T row loads still go out together — and the wave walks only the PRESENT parity blocks of
+// its run: its stripe's lost parity blocks are a sorted list ending in SET_LOST_END, read by scalar loads behind a cursor (q and the cursor are
+// wave-uniform: scalar control flow, no lane-divergent branch).  An absent parity block is neither loaded nor stored.  The pipeline is the same: the
+// next PRESENT block's load is in flight during the current block's arithmetic.
+template <int T, int V>
+__global__ __launch_bounds__(256) void update_set_kernel(const SetArgs s)
+{
+    const BatchArgs& a = s.b;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (wave >= a.waves) return;
+    const uint32_t slice = wave % a.slices, rest = wave / a.slices;
+    const uint32_t q0 = (rest % a.runs) * a.run, q1 = min(q0 + a.run, a.M);
+    const_u32_ptr seg = as_constant(a.segs) + (size_t)(rest / a.runs) * (SET_SEG_HEAD + T);
+    const uint32_t len = seg[1];
+    const_u32_ptr lost = as_constant(s.lost) + seg[2];
+    const_u32_ptr list = as_constant(a.list) + (size_t)seg[0] * SET_LIST_WORDS;
+    const uint64_t stripe = ((uint64_t)list[3] << 32) | list[2];
+    const uint64_t col = ((uint64_t)slice * 64u + lane) * V;
+    const bool live = col < a.S;  // (V > 1 only when S % V == 0: a live lane's V words all exist)
+    const uint64_t lcol = live ? col : 0;
+    const uint32_t bytes = (uint32_t)(a.S * 4u);
+    const uint32_t voff = live ? (uint32_t)col * 4u : bytes;  // (S * 4 < 2^32: update_batch_run)
+    const uint32_t omask = (a.data || a.old_blocks) ? 0xFFFFFFFFu : 0u;
+    const uint32_t* obase = s.old_base + lcol;  // (pointer arithmetic, not integers: the loads stay global loads)
+    uint32_t x[T][V];
+    constexpr int H = T * V > 32 ? T / 2 : T;
+#pragma unroll
+    for (int h = 0; h < T; h += H) {
+        uint32_t nv[H][V], ov[H][V];
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            const_u32_ptr wr = list + ((uint32_t)(h + i) < len ? h + i : 0) * SET_LIST_WORDS;
+            const uint64_t nrow = (uint64_t)(wr[1] & ~ROW_ABSENT) * a.S;
+            const int64_t orow = (int64_t)(((uint64_t)wr[LIST_WORDS + 1] << 32) | wr[LIST_WORDS]);
+            load_vec<V>(nv[i], a.new_blocks + nrow + lcol);
+            load_vec<V>(ov[i], obase + orow);
+        }
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            const uint32_t imask = (uint32_t)(h + i) < len ? 0xFFFFFFFFu : 0u;
+#pragma unroll
+            for (int v = 0; v < V; ++v) x[h + i][v] = gf::sub(nv[i][v], ov[i][v] & omask) & imask;
+        }
+        // (nothing but registers ties the halves together here: unless the first half's differences are pinned where they are formed, the scheduler lifts
+        // the second half's loads above the first half's subtractions and the kernel holds 2 T V words beside x after all — 156 VGPRs instead of 104 at
+        // T = 16, V = 4)
+        if constexpr (H < T) {
+#pragma unroll
+            for (int i = 0; i < H; ++i)
+#pragma unroll
+                for (int v = 0; v < V; ++v) asm volatile("" : "+v"(x[h + i][v]));  // (the differences exist here, not where the loop first uses them)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    // the first present parity block at or after q (it may lie past the run: the caller compares with q1); the cursor only moves forward
+    uint32_t cur = 0;
+    auto present_from = [&](uint32_t q) {
+        for (;;) {
+            const uint32_t l = lost[cur];
+            if (l > q) return q;  // (SET_LOST_END ends every row)
+            cur++;
+            if (l == q) q++;
+        }
+    };
+    uint32_t q = present_from(q0);
+    if (q >= q1) return;  // an empty run, or every parity block of the run is absent
+    const_u32_ptr G = as_constant(a.G);
+    const uint32_t* pbase = a.parity + stripe * a.M * a.S;
+    auto desc = [&](uint32_t qq) { return block_desc(pbase + (uint64_t)qq * a.S, bytes); };
+    auto step = [&](uint32_t qq, const uint32_t (&old)[V]) {
+        const uint32_t pos = a.off[qq >> a.qs] + ((qq & a.qmask) << a.ps);
+        uint32_t w[T];
+#pragma unroll
+        for (int i = 0; i < T; ++i) {
+            int32_t u = (int32_t)(pos - seg[SET_SEG_HEAD + i]);
+            if (u < 0) u += (int32_t)a.NC;
+            w[i] = G[(uint32_t)u >> a.tshift];
+        }
+        uint64_t lo[V];
+        uint32_t hi[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) lo[v] = 0, hi[v] = 0;
+#pragma unroll
+        for (int i = 0; i < T; ++i)
+#pragma unroll
+            for (int v = 0; v < V; ++v) mac96(lo[v], hi[v], x[i][v], w[i]);
+        uint32_t r[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) r[v] = gf::add(reduce96(lo[v], hi[v]), old[v]);
+        store_nt<V>(r, desc(qq), voff);
+    };
+    // (past the last present block the next load asks for the current block once more, as update_batch_kernel asks for `last`: never used)
+    uint32_t pa[V], pb[V];
+    load_nt<V>(pa, desc(q), voff);
+    for (;;) {
+        uint32_t next = present_from(q + 1);
+        load_nt<V>(pb, desc(next < q1 ? next : q), voff);
+        step(q, pa);
+        if (next >= q1) break;
+        q = next;
+        next = present_from(q + 1);
+        load_nt<V>(pa, desc(next < q1 ? next : q), voff);
+        step(q, pb);
+        if (next >= q1) break;
+        q = next;
+    }
+}
+
 struct ScatterArgs {
     uint32_t* data;
     const uint32_t* new_blocks;
     const uint32_t* list;  // the launch's first write
     uint64_t S, K;
     uint32_t slices, waves, e;
+    uint32_t list_words;   // LIST_WORDS, or SET_LIST_WORDS: a write whose data block is absent (ROW_ABSENT) is not stored
 };
 
 // wave (write, column slice): row u of new_blocks into data block (stripe, position >> e)
@@ -393,7 +526,8 @@ __global__ __launch_bounds__(256) void update_scatter_kernel(const ScatterArgs a
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     if (wave >= a.waves) return;
-    const_u32_ptr wr = as_constant(a.list) + (size_t)(wave / a.slices) * LIST_WORDS;
+    const_u32_ptr wr = as_constant(a.list) + (size_t)(wave / a.slices) * a.list_words;
+    if (wr[1] & ROW_ABSENT) return;  // (wave-uniform; never set in a list of fastecc_update_batch)
     const uint64_t stripe = ((uint64_t)wr[3] << 32) | wr[2];
     const uint64_t col = ((uint64_t)(wave % a.slices) * 64u + lane) * V;
     if (col >= a.S) return;
@@ -415,6 +549,8 @@ struct UpdateState {
     DeviceBuf<uint32_t> d_delta;  // ROWS x S words (an internal buffer: ordered between streams by buf_event)
     // fastecc_update_batch: one call's sorted write list and segment tables, in words (list.dev is an internal buffer like d_delta)
     StagedList<uint32_t> list;
+    // fastecc_update_batch_set: the old rows of one call's absent written blocks, S words each, rebuilt by direct_run_read (an internal buffer)
+    DeviceBuf<uint32_t> d_recon;
 };
 
 void destroy_update_state(UpdateState* s) { delete s; }
@@ -488,18 +624,32 @@ template <int V> const void* batch_kernel_v(int T)
     }
 }
 
-// waves of update_parity_kernel<T, V> (batch: update_batch_kernel<T, V>) one SIMD holds: 512 VGPRs in granules of 8, at most 8 (queried once per shape)
-int resident_waves_per_simd(int T, int V, bool batch = false)
+template <int V> const void* set_kernel_v(int T)
 {
-    static std::atomic<int> cache[2][3][5];  // zero-initialised (static storage)
+    switch (T) {
+        case 1: return (const void*)update_set_kernel<1, V>;
+        case 2: return (const void*)update_set_kernel<2, V>;
+        case 4: return (const void*)update_set_kernel<4, V>;
+        case 8: return (const void*)update_set_kernel<8, V>;
+        default: return (const void*)update_set_kernel<ROWS, V>;
+    }
+}
+
+enum KernelKind { KERNEL_PARITY = 0, KERNEL_BATCH = 1, KERNEL_SET = 2 };  // update_parity_kernel, update_batch_kernel, update_set_kernel
+
+// waves of that kernel<T, V> one SIMD holds: 512 VGPRs in granules of 8, at most 8 (queried once per shape)
+int resident_waves_per_simd(int T, int V, KernelKind kind = KERNEL_PARITY)
+{
+    static std::atomic<int> cache[3][3][5];  // zero-initialised (static storage)
     const int vi = V == 4 ? 0 : V == 2 ? 1 : 2;
     int ti = 0;
     while ((1 << ti) < T) ti++;
-    std::atomic<int>& slot = cache[batch ? 1 : 0][vi][ti];
+    std::atomic<int>& slot = cache[kind][vi][ti];
     if (!slot.load()) {
         hipFuncAttributes attr{};
-        const void* fn = batch ? (V == 4 ? batch_kernel_v<4>(T) : V == 2 ? batch_kernel_v<2>(T) : batch_kernel_v<1>(T))
-                               : (V == 4 ? parity_kernel_v<4>(T) : V == 2 ? parity_kernel_v<2>(T) : parity_kernel_v<1>(T));
+        const void* fn = kind == KERNEL_SET     ? (V == 4 ? set_kernel_v<4>(T) : V == 2 ? set_kernel_v<2>(T) : set_kernel_v<1>(T))
+                         : kind == KERNEL_BATCH ? (V == 4 ? batch_kernel_v<4>(T) : V == 2 ? batch_kernel_v<2>(T) : batch_kernel_v<1>(T))
+                                                : (V == 4 ? parity_kernel_v<4>(T) : V == 2 ? parity_kernel_v<2>(T) : parity_kernel_v<1>(T));
         int waves = 4;  // (if the query fails: a safe middle)
         if (hipFuncGetAttributes(&attr, fn) == hipSuccess && attr.numRegs > 0) waves = std::max(1, std::min(8, 512 / ((attr.numRegs + 7) / 8 * 8)));
         (void)hipGetLastError();
@@ -672,7 +822,8 @@ int sort_writes(const fastecc_ctx* c, uint64_t count, const uint64_t* writes, ui
 
 struct BatchLaunch {
     int T;
-    uint32_t seg0, segs;  // its segment table: first word after the list, number of segments
+    uint32_t seg0, segs;     // its segment table: first word after the list, number of segments
+    uint64_t parity_blocks;  // parity blocks its segments read and write (the profile's byte count)
 };
 
 template <int V> void launch_batch_v(int T, const BatchArgs& a, dim3 grid, hipStream_t st)
@@ -686,41 +837,82 @@ template <int V> void launch_batch_v(int T, const BatchArgs& a, dim3 grid, hipSt
     }
 }
 
+template <int V> void launch_set_v(int T, const SetArgs& a, dim3 grid, hipStream_t st)
+{
+    switch (T) {
+        case 1: hipLaunchKernelGGL((update_set_kernel<1, V>), grid, dim3(256), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((update_set_kernel<2, V>), grid, dim3(256), 0, st, a); break;
+        case 4: hipLaunchKernelGGL((update_set_kernel<4, V>), grid, dim3(256), 0, st, a); break;
+        case 8: hipLaunchKernelGGL((update_set_kernel<8, V>), grid, dim3(256), 0, st, a); break;
+        default: hipLaunchKernelGGL((update_set_kernel<ROWS, V>), grid, dim3(256), 0, st, a); break;
+    }
+}
+
 constexpr uint64_t LAUNCH_WAVES = 1ull << 24;  // a dispatch holds fewer than 2^32 work-items per dimension: at most 2^22 workgroups of 4 waves
 
-// sw: the call's writes, sorted and checked.  data == null: the parity form.
+// What fastecc_update_batch_set / _update_parity_batch_set add to a call (update_batch_set_impl fills it): every array is by write of the SORTED list.
+struct SetForm {
+    PatternSetView view;
+    std::vector<uint32_t> lost_row;        // its stripe's row of view.lost_parity (view.patterns: a whole stripe)
+    std::vector<uint32_t> present_parity;  // its stripe's present parity blocks
+    std::vector<uint32_t> old_row;         // OLD_IN_POOL, or its row of the reconstruction buffer (its data block is absent)
+    uint64_t rebuilt = 0;                  // rows of the reconstruction buffer: the first `rebuilt` entries of c->read_list.host say how to rebuild them
+    uint64_t rebuilt_rows_read = 0;        // rows those passes read, and the ones they write
+};
+
+// sw: the call's writes, sorted and checked.  data == null: the parity form.  set != null: stripes with absent blocks (update_set_kernel; with data, first
+// the old rows of the absent written blocks into the reconstruction buffer, and at the end only present blocks are stored).
 int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std::vector<SortedWrite>& sw, const uint32_t* old_blocks, const uint32_t* new_blocks,
-                     hipStream_t st)
+                     hipStream_t st, const SetForm* set = nullptr)
 {
     UpdateState* s = nullptr;
     int rc = update_state(c, &s);
     if (rc != FASTECC_OK) return rc;
     const uint64_t S = c->S, K = c->K, M = c->Mu, n = sw.size();
+    const int list_words = set ? SET_LIST_WORDS : LIST_WORDS, seg_head = set ? SET_SEG_HEAD : SEG_HEAD;
     int V = 4;
     const uintptr_t align = (uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks;  // every pointer a lane touches
     while (V > 1 && ((S % V) != 0 || (align & (4u * V - 1u)) != 0)) V >>= 1;
     const uint64_t slices = (S + 64u * V - 1) / (64u * V);
     if (slices * M > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (one segment's waves fit a launch)
-    // (a segment of len writes takes SEG_HEAD + T <= 3 len words; growing waits for the kernels that read the device list)
-    rc = s->list.reserve(n * (LIST_WORDS + SEG_HEAD + 1), [&]() -> int {
+    const auto wait_buffers = [&]() -> int {  // the host-side wait for the kernels that read an internal buffer about to be replaced
         if (c->buf_used) HIP_TRY(hipEventSynchronize(c->buf_event));
         return FASTECC_OK;
-    });
+    };
+    // (a segment of len writes takes seg_head + T <= (seg_head + 1) len words; growing waits for the kernels that read the device list)
+    rc = s->list.reserve(n * (list_words + seg_head + 1), wait_buffers);
     if (rc != FASTECC_OK) return rc;
+    if (set && set->rebuilt) {
+        if (direct_read_waves_per_entry(data, parity, nullptr, S, 0, S) > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;
+        if (set->rebuilt > s->d_recon.capacity() / S) {  // (rebuilt * S words fit 64 bits: the call's new blocks are more)
+            RC_TRY(wait_buffers());
+            RC_TRY(s->d_recon.grow(std::max<uint64_t>(set->rebuilt * S, 2 * s->d_recon.capacity())));  // FASTECC_E_NOMEM: it does not fit
+        }
+    }
 
     // the list, and each stripe's writes cut into segments of at most ROWS: segment r of a stripe runs in round r, by padded length class
+    const uint32_t* old_base = data ? data : old_blocks ? old_blocks : new_blocks;  // (update_set_kernel: the old rows' offsets count from here)
     uint32_t* list = s->list.host;
     std::vector<std::vector<uint32_t>> bucket;  // [round * 5 + class]: first write of each segment (its length: to the stripe's end, at most ROWS)
     std::vector<uint32_t> stripe_end(n);        // per write: one past the last write of its stripe
+    uint64_t stored = n;                        // writes whose data block is there to be stored
     for (uint64_t f = 0; f < n;) {
         const uint64_t b = sw[f].index / K;
         uint64_t g = f;
         for (; g < n && sw[g].index < (b + 1) * K; g++) {
-            uint32_t* wr = list + g * LIST_WORDS;
+            uint32_t* wr = list + g * list_words;
             wr[0] = (uint32_t)((sw[g].index - b * K) << s->g.e);
             wr[1] = sw[g].row;
             wr[2] = (uint32_t)b;
             wr[3] = (uint32_t)(b >> 32);
+            if (set) {  // its old row, from old_base
+                const uint32_t r = set->old_row[g];
+                const uint64_t off = r != OLD_IN_POOL ? (uint64_t)(((intptr_t)s->d_recon.get() - (intptr_t)old_base) / 4) + (uint64_t)r * S  // (both on word boundaries)
+                                                      : (data ? sw[g].index : (uint64_t)sw[g].row) * S;
+                wr[LIST_WORDS] = (uint32_t)off;
+                wr[LIST_WORDS + 1] = (uint32_t)(off >> 32);
+                if (r != OLD_IN_POOL) wr[1] |= ROW_ABSENT, stored--;
+            }
         }
         for (uint64_t a0 = f, r = 0; a0 < g; a0 += ROWS, r++) {
             int cls = 0;
@@ -732,32 +924,42 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
         f = g;
     }
     std::vector<BatchLaunch> launches;
-    uint32_t* segs = list + n * LIST_WORDS;
+    uint32_t* segs = list + n * list_words;
     uint32_t seg_words = 0;
     for (size_t i = 0; i < bucket.size(); i++) {
         if (bucket[i].empty()) continue;
         const int T = 1 << (int)(i % 5);
-        launches.push_back(BatchLaunch{T, seg_words, (uint32_t)bucket[i].size()});
+        launches.push_back(BatchLaunch{T, seg_words, (uint32_t)bucket[i].size(), 0});
         for (uint32_t first : bucket[i]) {
             const uint32_t len = std::min<uint32_t>(ROWS, stripe_end[first] - first);
             uint32_t* seg = segs + seg_words;
             seg[0] = first;
             seg[1] = len;
-            for (int r = 0; r < T; r++) seg[SEG_HEAD + r] = list[(size_t)(first + ((uint32_t)r < len ? r : 0)) * LIST_WORDS];
-            seg_words += SEG_HEAD + T;
+            if (set) seg[SEG_HEAD] = set->lost_row[first] * (uint32_t)SET_LOST_ROW;
+            for (int r = 0; r < T; r++) seg[seg_head + r] = list[(size_t)(first + ((uint32_t)r < len ? r : 0)) * list_words];
+            seg_words += seg_head + T;
+            launches.back().parity_blocks += set ? set->present_parity[first] : M;
         }
     }
 
     rc = update_table(c, s, st);
     if (rc != FASTECC_OK) return rc;
     return with_internal_buffers(c, st, [&]() -> int {
-        const size_t words = (size_t)n * LIST_WORDS + seg_words;
+        const size_t words = (size_t)n * list_words + seg_words;
         {
             ProfScope ps(c, st, "update_batch_list", words * 4);
             const int r = s->list.publish(words, st);
             if (r != FASTECC_OK) return r;
         }
-        BatchArgs a{};
+        if (set && set->rebuilt) {
+            // The old rows of the absent written blocks, before ANY parity launch of the call: the passes read parity blocks that those launches
+            // rewrite (and present data blocks, which only the scatter at the very end overwrites).
+            RC_TRY(c->read_list.publish(set->rebuilt, st));
+            ProfScope ps(c, st, "update_set_recon", set->rebuilt_rows_read * S * 4);
+            RC_TRY(direct_run_read(set->view.passes, c->read_list.dev, set->rebuilt, data, parity, s->d_recon, S, 0, S, K * S, M * S, st));
+        }
+        SetArgs sa{};
+        BatchArgs& a = sa.b;
         a.parity = parity;
         a.data = data;
         a.old_blocks = old_blocks;
@@ -770,38 +972,46 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
         a.slices = (uint32_t)slices;
         a.e = (uint32_t)s->g.e;
         set_positions(s, a);
+        sa.old_base = old_base;
+        if (set) sa.lost = set->view.lost_parity;
         for (const BatchLaunch& l : launches) {
             // at least every resident wave of the device, where the parity count allows it: runs of parity blocks per segment
-            const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(l.T, V, true);
+            const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(l.T, V, set ? KERNEL_SET : KERNEL_BATCH);
             const uint64_t per_run = (uint64_t)l.segs * slices;
             const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>(M, (target + per_run - 1) / per_run));
             a.run = (uint32_t)((M + want - 1) / want);
             a.runs = (uint32_t)((M + a.run - 1) / a.run);
             const uint64_t seg_waves = slices * a.runs, launch_segs = LAUNCH_WAVES / seg_waves;
-            ProfScope ps(c, st, "update_batch", (uint64_t)l.segs * M * S * 8);
+            ProfScope ps(c, st, set ? "update_set" : "update_batch", l.parity_blocks * S * 8);
             for (uint64_t s0 = 0; s0 < l.segs; s0 += launch_segs) {
                 const uint64_t waves = std::min<uint64_t>(launch_segs, l.segs - s0) * seg_waves;
-                a.segs = s->list.dev + n * LIST_WORDS + l.seg0 + (size_t)s0 * (SEG_HEAD + l.T);
+                a.segs = s->list.dev + n * list_words + l.seg0 + (size_t)s0 * (seg_head + l.T);
                 a.waves = (uint32_t)waves;
                 const dim3 grid((unsigned)((waves + 3) / 4));
-                if (V == 4) launch_batch_v<4>(l.T, a, grid, st);
-                else if (V == 2) launch_batch_v<2>(l.T, a, grid, st);
-                else launch_batch_v<1>(l.T, a, grid, st);
+                if (set) {
+                    if (V == 4) launch_set_v<4>(l.T, sa, grid, st);
+                    else if (V == 2) launch_set_v<2>(l.T, sa, grid, st);
+                    else launch_set_v<1>(l.T, sa, grid, st);
+                } else {
+                    if (V == 4) launch_batch_v<4>(l.T, a, grid, st);
+                    else if (V == 2) launch_batch_v<2>(l.T, a, grid, st);
+                    else launch_batch_v<1>(l.T, a, grid, st);
+                }
                 HIP_TRY(hipGetLastError());
             }
         }
-        if (data) {
-            ScatterArgs sa{data, new_blocks, nullptr, S, K, (uint32_t)slices, 0, (uint32_t)s->g.e};
+        if (data && stored) {
+            ScatterArgs ca{data, new_blocks, nullptr, S, K, (uint32_t)slices, 0, (uint32_t)s->g.e, (uint32_t)list_words};
             const uint64_t launch_writes = LAUNCH_WAVES / slices;
-            ProfScope ps(c, st, "update_scatter", n * S * 8);
+            ProfScope ps(c, st, "update_scatter", stored * S * 8);
             for (uint64_t w0 = 0; w0 < n; w0 += launch_writes) {
                 const uint64_t waves = std::min<uint64_t>(launch_writes, n - w0) * slices;
-                sa.list = s->list.dev + w0 * LIST_WORDS;
-                sa.waves = (uint32_t)waves;
+                ca.list = s->list.dev + w0 * list_words;
+                ca.waves = (uint32_t)waves;
                 const dim3 grid((unsigned)((waves + 3) / 4));
-                if (V == 4) hipLaunchKernelGGL(update_scatter_kernel<4>, grid, dim3(256), 0, st, sa);
-                else if (V == 2) hipLaunchKernelGGL(update_scatter_kernel<2>, grid, dim3(256), 0, st, sa);
-                else hipLaunchKernelGGL(update_scatter_kernel<1>, grid, dim3(256), 0, st, sa);
+                if (V == 4) hipLaunchKernelGGL(update_scatter_kernel<4>, grid, dim3(256), 0, st, ca);
+                else if (V == 2) hipLaunchKernelGGL(update_scatter_kernel<2>, grid, dim3(256), 0, st, ca);
+                else hipLaunchKernelGGL(update_scatter_kernel<1>, grid, dim3(256), 0, st, ca);
                 HIP_TRY(hipGetLastError());
             }
         }
@@ -822,6 +1032,68 @@ int update_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, 
     CallLock lk(c->mu);
     return update_batch_run(c, with_data ? (uint32_t*)data : nullptr, (uint32_t*)parity, sw, (const uint32_t*)old_blocks, (const uint32_t*)new_blocks,
                             (hipStream_t)stream);
+}
+
+// fastecc_update_batch_set / _update_parity_batch_set: stripe b under pattern pattern_of[b] of the prepared set.  Everything is decided on the host before any
+// device work: the checks of update_batch_impl, the rows against the pool, the set, and per touched stripe its pattern — which of its written data blocks are
+// absent (their old rows are rebuilt: one DirectReadEntry each, as read_batch_impl's translate makes them) and which parity blocks update_set_kernel skips.
+int update_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, const uint64_t* writes, uint64_t n_writes,
+                          const void* old_blocks, const void* new_blocks, void* stream, bool with_data)
+{
+    RC_TRY(update_batch_args(c, data, parity, count, writes, n_writes, old_blocks, new_blocks, with_data));
+    if (!pattern_of) return FASTECC_E_INVAL;
+    if (n_writes > 0xFFFFFFFFull / (SET_LIST_WORDS + SET_SEG_HEAD + 1)) return FASTECC_E_UNSUPPORTED;  // (the limit of update_batch_args for the longer records)
+    PoolExtent x;
+    RC_TRY(pool_extent(c, with_data ? data : nullptr, parity, count, &x, false));
+    const uint64_t rows_bytes = n_writes * x.block;  // (fits 64 bits: update_batch_args)
+    const auto overlaps_pool = [&](const void* rows) {
+        const uint64_t r0 = (uint64_t)(uintptr_t)rows;
+        const auto hits = [&](const void* base, uint64_t bytes) { return r0 < (uint64_t)(uintptr_t)base + bytes && (uint64_t)(uintptr_t)base < r0 + rows_bytes; };
+        return rows && n_writes > 0 && (r0 > UINT64_MAX - rows_bytes || (with_data && hits(data, count * x.data_bytes)) || hits(parity, count * x.parity_bytes));
+    };
+    if (overlaps_pool(new_blocks) || overlaps_pool(old_blocks)) return FASTECC_E_INVAL;
+    CallLock lk(c->mu);
+    SetForm set;
+    if (!pattern_set_view(c, &set.view)) return FASTECC_E_INVAL;  // fastecc_decode_prepare_set first
+    if (n_writes == 0) return FASTECC_OK;
+    std::vector<SortedWrite> sw;
+    RC_TRY(sort_writes(c, count, writes, n_writes, sw));
+    const uint64_t K = c->K, P = set.view.patterns, n = sw.size();
+    set.lost_row.resize(n);
+    set.present_parity.resize(n);
+    set.old_row.assign(n, OLD_IN_POOL);
+    std::vector<DirectReadEntry> rebuild;
+    const bool small = count * K <= 0xFFFFFFFFull;  // (count * K fits 64 bits: update_batch_args)
+    for (uint64_t f = 0; f < n;) {
+        const uint64_t b = small ? (uint64_t)((uint32_t)sw[f].index / (uint32_t)K) : sw[f].index / K;  // (the common case: a 32-bit division, as read_batch_impl)
+        const uint32_t q = pattern_of[b];  // (only touched stripes' entries are looked at)
+        if (q != FASTECC_PATTERN_NONE && q >= P) return FASTECC_E_INVAL;
+        const bool whole = q == FASTECC_PATTERN_NONE;
+        const std::vector<uint32_t>* R = whole || !with_data ? nullptr : &pattern_lost_data(c, q);  // (the parity form: only the parity flags matter)
+        const uint32_t present = (uint32_t)(c->Mu - (whole ? 0 : pattern_lost_parity(c, q).size()));
+        for (; f < n && sw[f].index < (b + 1) * K; f++) {
+            set.lost_row[f] = whole ? (uint32_t)P : q;
+            set.present_parity[f] = present;
+            if (!R) continue;
+            const uint32_t i = (uint32_t)(sw[f].index - b * K);
+            for (size_t j = 0; j < R->size(); j++)
+                if ((*R)[j] == i) {
+                    set.old_row[f] = (uint32_t)rebuild.size();
+                    rebuild.push_back(DirectReadEntry{b, q, i, (uint32_t)j, 0});
+                    set.rebuilt_rows_read += (uint64_t)pattern_rows(c, q) + 1;
+                    break;
+                }
+        }
+    }
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    if (!rebuild.empty()) {  // (reserve allocates, and waits for the previous call's copy out of the pinned side; it enqueues nothing)
+        RC_TRY(c->read_list.reserve(rebuild.size(), [&] { return wait_idle(c); }));
+        std::copy(rebuild.begin(), rebuild.end(), c->read_list.host.get());
+        set.rebuilt = rebuild.size();
+    }
+    return update_batch_run(c, with_data ? (uint32_t*)data : nullptr, (uint32_t*)parity, sw, (const uint32_t*)old_blocks, (const uint32_t*)new_blocks,
+                            (hipStream_t)stream, &set);
 }
 
 }  // namespace
@@ -866,6 +1138,18 @@ int fastecc_update_parity_batch(fastecc_ctx* c, void* parity, uint64_t count, co
                                 const void* new_blocks, void* stream)
 {
     return guarded([&]() -> int { return update_batch_impl(c, nullptr, parity, count, writes, n_writes, old_blocks, new_blocks, stream, false); });
+}
+
+int fastecc_update_batch_set(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, const uint64_t* writes, uint64_t n_writes,
+                             const void* new_blocks, void* stream)
+{
+    return guarded([&]() -> int { return update_batch_set_impl(c, data, parity, count, pattern_of, writes, n_writes, nullptr, new_blocks, stream, true); });
+}
+
+int fastecc_update_parity_batch_set(fastecc_ctx* c, void* parity, uint64_t count, const uint32_t* pattern_of, const uint64_t* writes, uint64_t n_writes,
+                                    const void* old_blocks, const void* new_blocks, void* stream)
+{
+    return guarded([&]() -> int { return update_batch_set_impl(c, nullptr, parity, count, pattern_of, writes, n_writes, old_blocks, new_blocks, stream, false); });
 }
 
 int fastecc_code_coefficient(uint64_t n, uint64_t k, unsigned flags, uint64_t data_block, uint64_t parity_block, uint32_t* out)

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 410 /* 0.4.1: fastecc_read_batch, fastecc_read_batch_set (degraded reads: requested blocks of a pool into a compact buffer, the pool untouched) */
+#define FASTECC_VERSION 420 /* 0.4.2: fastecc_update_batch_set, fastecc_update_parity_batch_set (degraded writes: small writes into a pool whose stripes miss blocks) */
 
 enum {
     FASTECC_OK = 0,
@@ -746,6 +746,41 @@ int fastecc_update_batch(fastecc_ctx *ctx, void *data, void *parity, uint64_t co
                          const void *new_blocks, void *stream);
 int fastecc_update_parity_batch(fastecc_ctx *ctx, void *parity, uint64_t count, const uint64_t *writes, uint64_t n_writes,
                                 const void *old_blocks, const void *new_blocks, void *stream);
+/*
+ * Degraded writes: fastecc_update_batch / fastecc_update_parity_batch for a pool in which stripes miss blocks.  Layout, `writes`, new_blocks and
+ * old_blocks are exactly those of the two calls above; pattern_of is exactly that of fastecc_read_batch_set: a HOST array of `count` entries, stripe
+ * b is taken under pattern pattern_of[b] of the set stored by fastecc_decode_prepare_set, only the entries of stripes that some write names are
+ * looked at, and FASTECC_PATTERN_NONE, or a pattern that loses nothing, means the stripe is whole.  A block is ABSENT when its stripe's pattern says
+ * it is lost.
+ *   fastecc_update_batch_set : for a touched stripe let X be its true old data — present data blocks as stored, absent ones as
+ *       fastecc_decode_prepare(that pattern) + fastecc_decode would rebuild them — and X' be X with the written blocks replaced.  After the call
+ *       every PRESENT data block of the stripe holds its block of X', and every PRESENT parity block holds, bit for bit, the parity block
+ *       fastecc_encode gives for X'.  No absent block, data or parity, is written, and its content has no influence on anything: it may hold
+ *       words >= p.  So a later fastecc_repair_batch_set of the pool under the same patterns leaves every touched stripe bit-identical to a fresh
+ *       fastecc_encode of X', and fastecc_read_batch_set of an absent written block returns its new content.  For a whole stripe the result is
+ *       bit-identical to fastecc_update_batch.
+ *   fastecc_update_parity_batch_set : the data lives elsewhere and the old rows come from old_blocks (NULL: zero), so only the parity flags of a
+ *       pattern matter: present parity blocks are updated as by fastecc_update_parity_batch, absent ones are not touched.
+ * A stripe that no write names is neither read nor written.  Inputs of touched stripes' PRESENT blocks must be < p.  n_writes == 0 with otherwise
+ * valid arguments (a set prepared included) is a no-op.  Neither call changes the pattern set, the single prepared pattern, any scrub state or any
+ * option; fastecc_decode_prepare_set waits for a degraded write still in flight before it swaps tables, as it does for reads.
+ * Refusals, before any device work and with nothing written.  FASTECC_E_INVAL: everything fastecc_update_batch refuses (a null context, count == 0,
+ * null pointers with n_writes > 0, misalignment, an index >= count*k, a duplicate, byte sizes beyond 64 bits), a null pattern_of, no set prepared,
+ * an entry of a TOUCHED stripe that is >= n_patterns and not FASTECC_PATTERN_NONE, new_blocks / old_blocks overlapping the pool.
+ * FASTECC_E_UNSUPPORTED: GF((2^61-1)^2), sharded contexts, a set "row_pitch_words" (and more than (2^32 - 1) / 10 writes in one call).
+ * FASTECC_E_NOMEM: the reconstruction buffer — one block per absent written block, owned by the context and grown on demand — does not fit.
+ * Method, two phases on `stream`: the old rows of the absent written blocks are rebuilt into the reconstruction buffer by the
+ * kernel of fastecc_read_batch_set (one request each); then update_set_kernel does what the kernel of fastecc_update_batch does, with each old row
+ * taken from the pool or from that buffer and the stripe's absent parity blocks skipped (neither loaded nor stored); at the end only present data
+ * blocks are stored.
+ * Streams: the stream and staging rules of fastecc_update_batch hold word for word — enqueued on `stream`, steady-state calls do not synchronise the
+ * device, the staged lists travel through pinned and device buffers owned by the context that grow on demand, an event guards the reuse of the
+ * pinned side, and the calls cannot be captured into a hipGraph.
+ */
+int fastecc_update_batch_set(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, const uint32_t *pattern_of, const uint64_t *writes,
+                             uint64_t n_writes, const void *new_blocks, void *stream);
+int fastecc_update_parity_batch_set(fastecc_ctx *ctx, void *parity, uint64_t count, const uint32_t *pattern_of, const uint64_t *writes,
+                                    uint64_t n_writes, const void *old_blocks, const void *new_blocks, void *stream);
 /* Host only, no device: the code's generator-matrix entry L_i(y_q) for data block i and parity block q of the (n,k) code that
  * fastecc_create_ex(n, k, ..., flags) builds over GF(0xFFF00001), plain form in [0,p): parity block q = sum_i L_i(y_q) data block i.
  * FASTECC_E_INVAL for a null out, an index out of range or unknown flags; FASTECC_E_UNSUPPORTED for a code fastecc_create_ex refuses. */
