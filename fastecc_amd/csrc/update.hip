@@ -18,13 +18,16 @@
 //                         rows of its slice into VGPRs once, then streams its parity blocks: T wave-uniform weights from G (scalar
 //                         loads behind one wait), T x V mac96 into 96-bit sums (lazy96.hpp), + the old parity word, one reduction, a
 //                         non-temporal store.  The next block's parity load is in flight during the current block's arithmetic.
+// The three parity kernels (this one and the two below) differ in how a wave finds its rows and forms the deltas.  From there on the two pool
+// kernels call stream_parity with the position of row i and the next block to visit as callables; this one keeps the same loop written out, for
+// a measured reason.  The host picks the instantiation <T, V> through with_class and V through lane_words.
 //
 // A pool of stripes stored back to back (fastecc_update_batch): G does not depend on the stripe, so nothing per stripe is
 // built.  The host sorts the writes by (stripe, block), cuts each stripe's writes into segments of at most ROWS, and uploads the sorted list and
 // the segment tables; the r-th segment of every stripe runs in round r (segments of one stripe read-modify-write the same parity blocks), one
 // launch per padded segment length T in {1, 2, 4, 8, 16}:
 //   update_batch_kernel  : a wave owns one segment, one column slice and one run of that stripe's parity blocks.  It forms D = new - old of its
-//                          <= T rows in VGPRs (no delta buffer) and streams its parity blocks exactly as update_parity_kernel does;
+//                          <= T rows in VGPRs (no delta buffer) and streams its parity blocks through stream_parity;
 //   update_scatter_kernel: after the last round, fastecc_update_batch only: new_blocks row u into its data block (several waves of the parity
 //                          kernel need the same old row, so the store waits for a later kernel on the same stream: no race, no flag).
 //
@@ -32,7 +35,7 @@
 // set of fastecc_decode_prepare_set.  The same host code (update_batch_run with a SetForm), and on the stream
 //   direct_run_read      : the old rows of the written data blocks that are absent, rebuilt into UpdateState::d_recon before any parity launch;
 //   update_set_kernel    : update_batch_kernel with each old row at an offset the host chose (the pool, or d_recon) and the stripe's absent parity
-//                          blocks skipped — neither loaded nor stored;
+//                          blocks skipped — neither loaded nor stored: stream_parity's next block is the next PRESENT one;
 //   update_scatter_kernel: only the writes whose data block is present.
 #include <algorithm>
 #include <atomic>
@@ -169,20 +172,25 @@ __global__ __launch_bounds__(256) void update_delta_kernel(const DeltaArgs a)
     a.delta[(uint64_t)r * a.S + w] = gf::sub(nv, ov);
 }
 
-struct ParityArgs {
-    uint32_t* parity;        // Mu blocks of S words
-    const uint32_t* delta;   // [rows][S]
-    const uint32_t* G;       // weight table (Montgomery form)
-    uint64_t S;
-    uint32_t M;              // parity blocks
-    uint32_t slices;         // column slices of 64 V words
-    uint32_t run;            // parity blocks per wave
-    uint32_t waves;
-    uint32_t rows;           // live delta rows of the pass (<= T)
-    uint32_t NC, tshift;     // positions; weight index = ((pos - d) mod NC) >> tshift
+// pos(q) of the code, and where the weight of a data block at position d (i << e) for parity block q stands in G
+struct Positions {
+    uint32_t NC, tshift;     // weight index = ((pos(q) - d) mod NC) >> tshift
     uint32_t qs, qmask, ps;  // pos(q) = off[q >> qs] + ((q & qmask) << ps)
     uint32_t off[8];
-    uint32_t d[ROWS];        // position of each row's data block (i << e)
+    __device__ __forceinline__ uint32_t pos(uint32_t q) const { return off[q >> qs] + ((q & qmask) << ps); }
+};
+
+struct ParityArgs {
+    uint32_t* parity;       // Mu blocks of S words
+    const uint32_t* delta;  // [T][S]
+    const uint32_t* G;      // weight table (Montgomery form)
+    uint64_t S;
+    uint32_t M;             // parity blocks
+    uint32_t slices;        // column slices of 64 V words
+    uint32_t run;           // parity blocks per wave
+    uint32_t waves;
+    Positions p;
+    uint32_t d[ROWS];       // position of each row's data block (i << e)
 };
 
 // Parity blocks through buffer descriptors: the descriptor (base = the block, range = its S words) is scalar and the lane offset is one
@@ -221,36 +229,43 @@ template <int V> __device__ __forceinline__ void store_nt(const uint32_t (&src)[
     }
 }
 
-// The loop has no branch on the row count or the lane: every one of the T delta rows is loaded (rows past the pass's count are zero in
-// d_delta and point at a valid weight), dead lanes read column 0 and only skip the store, and the parity block of the next step is
-// requested at a clamped index.  So the T weights of a block go out as T scalar loads behind one wait, and the next block's parity load
-// stays in flight under the current block's arithmetic (two register sets, the loop unrolled by two: no copy between them).
-template <int T, int V>
-__global__ __launch_bounds__(256) void update_parity_kernel(const ParityArgs a)
+// The V words of a block of S words that a lane of column slice `slice` owns (V > 1 only when S % V == 0: a live lane's V words all exist;
+// S * 4 < 2^32: update_pass, update_batch_args).  A dead lane — one past the end of the row — reads column 0 and stores nothing.
+struct LaneColumns {
+    uint64_t lcol;   // the lane's first word for plain loads (a dead lane: 0)
+    uint32_t bytes;  // of a block: the range of its descriptor
+    uint32_t voff;   // the lane's byte offset in a block for load_nt / store_nt (a dead lane: outside the range)
+};
+template <int V> __device__ __forceinline__ LaneColumns lane_columns(uint32_t slice, uint32_t lane, uint64_t S)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    if (wave >= a.waves) return;
-    const uint32_t slice = wave % a.slices;
-    const uint32_t q0 = (wave / a.slices) * a.run, q1 = min(q0 + a.run, a.M);
     const uint64_t col = ((uint64_t)slice * 64u + lane) * V;
-    const bool live = col < a.S;  // (V > 1 only when S % V == 0: a live lane's V words all exist)
-    const uint64_t lcol = live ? col : 0;
-    const uint32_t bytes = (uint32_t)(a.S * 4u);
-    const uint32_t voff = live ? (uint32_t)col * 4u : bytes;  // (S * 4 < 2^32: update_pass)
-    uint32_t x[T][V];
-#pragma unroll
-    for (int i = 0; i < T; ++i) load_vec<V>(x[i], a.delta + (uint64_t)i * a.S + lcol);
-    const_u32_ptr G = as_constant(a.G);
-    auto desc = [&](uint32_t q) { return block_desc(a.parity + (uint64_t)q * a.S, bytes); };
-    auto step = [&](uint32_t q, const uint32_t (&old)[V]) {
-        const uint32_t pos = a.off[q >> a.qs] + ((q & a.qmask) << a.ps);
+    const bool live = col < S;
+    const uint32_t bytes = (uint32_t)(S * 4u);
+    return LaneColumns{live ? col : 0, bytes, live ? (uint32_t)col * 4u : bytes};
+}
+
+// The tail of update_batch_kernel and update_set_kernel (update_parity_kernel has the same loop written out): the wave adds
+// sum_i weight(row i, q) * x[i] to its column slice of the parity blocks q, next(q + 1), next(next(q + 1) + 1), ... < q1 of the stripe at
+// pbase; q < q1 is the first of them.  next(q') is the first block >= q' the wave is to visit
+// (the identity where every block is there; it may lie past q1) and row_pos(i) the position of row i's data block, both wave-uniform.
+// A block costs T weights from G (T scalar loads behind one wait), T x V mac96 into 96-bit sums, + the old word, one reduction, a non-temporal
+// store.  The loop has no branch on the row count or the lane: rows past the count are zero and point at a valid weight, dead lanes only have
+// their stores dropped, and past the last block the next load asks for the current block once more (never used).  So the next block's parity
+// load stays in flight under the current block's arithmetic (two register sets, the loop unrolled by two: no copy between them).
+template <int T, int V, class RowPos, class Next>
+__device__ __forceinline__ void stream_parity(const uint32_t (&x)[T][V], const uint32_t* pbase, uint64_t S, const LaneColumns& c, const uint32_t* weights,
+                                              const Positions& p, uint32_t q, uint32_t q1, RowPos row_pos, Next next)
+{
+    const_u32_ptr G = as_constant(weights);
+    auto desc = [&](uint32_t qq) { return block_desc(pbase + (uint64_t)qq * S, c.bytes); };
+    auto step = [&](uint32_t qq, const uint32_t (&old)[V]) {
+        const uint32_t pos = p.pos(qq);
         uint32_t w[T];
 #pragma unroll
         for (int i = 0; i < T; ++i) {
-            int32_t u = (int32_t)(pos - a.d[i]);
-            if (u < 0) u += (int32_t)a.NC;
-            w[i] = G[(uint32_t)u >> a.tshift];
+            int32_t u = (int32_t)(pos - row_pos(i));
+            if (u < 0) u += (int32_t)p.NC;
+            w[i] = G[(uint32_t)u >> p.tshift];
         }
         uint64_t lo[V];
         uint32_t hi[V];
@@ -263,17 +278,72 @@ __global__ __launch_bounds__(256) void update_parity_kernel(const ParityArgs a)
         uint32_t r[V];
 #pragma unroll
         for (int v = 0; v < V; ++v) r[v] = gf::add(reduce96(lo[v], hi[v]), old[v]);
-        store_nt<V>(r, desc(q), voff);
+        store_nt<V>(r, desc(qq), c.voff);
+    };
+    uint32_t pa[V], pb[V];
+    load_nt<V>(pa, desc(q), c.voff);
+    for (;;) {
+        uint32_t n = next(q + 1);
+        load_nt<V>(pb, desc(n < q1 ? n : q), c.voff);
+        step(q, pa);
+        if (n >= q1) break;
+        q = n;
+        n = next(q + 1);
+        load_nt<V>(pa, desc(n < q1 ? n : q), c.voff);
+        step(q, pb);
+        if (n >= q1) break;
+        q = n;
+    }
+}
+
+// Every one of the T delta rows is loaded: rows past the pass's count are zero in d_delta.  This kernel keeps stream_parity's loop written out, in
+// the form it had before there was a helper (the next block at a clamped index): through the helper its T = 16, V = 4 instance, which is bound by
+// its instruction stream, measured 0.3-0.7 % slower (HISTORY.md).  A change to the weight index, the descriptor or the pipeline goes into both.
+template <int T, int V>
+__global__ __launch_bounds__(256) void update_parity_kernel(const ParityArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (wave >= a.waves) return;
+    const uint32_t slice = wave % a.slices;
+    const uint32_t q0 = (wave / a.slices) * a.run, q1 = min(q0 + a.run, a.M);
+    const LaneColumns c = lane_columns<V>(slice, lane, a.S);
+    uint32_t x[T][V];
+#pragma unroll
+    for (int i = 0; i < T; ++i) load_vec<V>(x[i], a.delta + (uint64_t)i * a.S + c.lcol);
+    const_u32_ptr G = as_constant(a.G);
+    auto desc = [&](uint32_t q) { return block_desc(a.parity + (uint64_t)q * a.S, c.bytes); };
+    auto step = [&](uint32_t q, const uint32_t (&old)[V]) {
+        const uint32_t pos = a.p.pos(q);
+        uint32_t w[T];
+#pragma unroll
+        for (int i = 0; i < T; ++i) {
+            int32_t u = (int32_t)(pos - a.d[i]);
+            if (u < 0) u += (int32_t)a.p.NC;
+            w[i] = G[(uint32_t)u >> a.p.tshift];
+        }
+        uint64_t lo[V];
+        uint32_t hi[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) lo[v] = 0, hi[v] = 0;
+#pragma unroll
+        for (int i = 0; i < T; ++i)
+#pragma unroll
+            for (int v = 0; v < V; ++v) mac96(lo[v], hi[v], x[i][v], w[i]);
+        uint32_t r[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) r[v] = gf::add(reduce96(lo[v], hi[v]), old[v]);
+        store_nt<V>(r, desc(q), c.voff);
     };
     if (q0 >= q1) return;
     const uint32_t last = q1 - 1;
     uint32_t pa[V], pb[V];
-    load_nt<V>(pa, desc(q0), voff);
+    load_nt<V>(pa, desc(q0), c.voff);
     for (uint32_t q = q0; q < q1; q += 2) {
-        load_nt<V>(pb, desc(min(q + 1, last)), voff);
+        load_nt<V>(pb, desc(min(q + 1, last)), c.voff);
         step(q, pa);
         if (q + 1 > last) break;
-        load_nt<V>(pa, desc(min(q + 2, last)), voff);
+        load_nt<V>(pa, desc(min(q + 2, last)), c.voff);
         step(q + 1, pb);
     }
 }
@@ -297,9 +367,7 @@ struct BatchArgs {
     uint32_t run, runs;          // parity blocks per wave, runs per segment
     uint32_t waves;              // segments of the launch x runs x slices
     uint32_t e;                  // data block = position >> e
-    uint32_t NC, tshift;         // weight index = ((pos - d) mod NC) >> tshift
-    uint32_t qs, qmask, ps;      // pos(q) = off[q >> qs] + ((q & qmask) << ps)
-    uint32_t off[8];
+    Positions p;
 };
 
 // update_parity_kernel with the delta rows formed in registers and everything about the stripe read from the segment table and the write list
@@ -317,11 +385,7 @@ __global__ __launch_bounds__(256) void update_batch_kernel(const BatchArgs a)
     const uint32_t len = seg[1];
     const_u32_ptr list = as_constant(a.list) + (size_t)seg[0] * LIST_WORDS;
     const uint64_t stripe = ((uint64_t)list[3] << 32) | list[2];
-    const uint64_t col = ((uint64_t)slice * 64u + lane) * V;
-    const bool live = col < a.S;  // (V > 1 only when S % V == 0: a live lane's V words all exist)
-    const uint64_t lcol = live ? col : 0;
-    const uint32_t bytes = (uint32_t)(a.S * 4u);
-    const uint32_t voff = live ? (uint32_t)col * 4u : bytes;  // (S * 4 < 2^32: update_batch_run)
+    const LaneColumns c = lane_columns<V>(slice, lane, a.S);
     // One form of the loop for the three sources of the old rows (no old rows: the new row once more, masked away), and masks instead of
     // conditions: the row loads go out together, with no branch or wait between them.
     const uint32_t omask = (a.data || a.old_blocks) ? 0xFFFFFFFFu : 0u;
@@ -338,8 +402,8 @@ __global__ __launch_bounds__(256) void update_batch_kernel(const BatchArgs a)
             const_u32_ptr wr = list + ((uint32_t)(h + i) < len ? h + i : 0) * LIST_WORDS;
             const uint64_t nrow = (uint64_t)wr[1] * a.S;
             const uint64_t orow = (first_block + (((wr[0] >> a.e) & dmask) | (wr[1] & ~dmask))) * a.S;
-            load_vec<V>(nv[i], a.new_blocks + nrow + lcol);
-            load_vec<V>(ov[i], obase + orow + lcol);
+            load_vec<V>(nv[i], a.new_blocks + nrow + c.lcol);
+            load_vec<V>(ov[i], obase + orow + c.lcol);
         }
 #pragma unroll
         for (int i = 0; i < H; ++i) {
@@ -349,41 +413,7 @@ __global__ __launch_bounds__(256) void update_batch_kernel(const BatchArgs a)
         }
     }
     if (q0 >= q1) return;
-    const_u32_ptr G = as_constant(a.G);
-    const uint32_t* pbase = a.parity + stripe * a.M * a.S;
-    auto desc = [&](uint32_t q) { return block_desc(pbase + (uint64_t)q * a.S, bytes); };
-    auto step = [&](uint32_t q, const uint32_t (&old)[V]) {
-        const uint32_t pos = a.off[q >> a.qs] + ((q & a.qmask) << a.ps);
-        uint32_t w[T];
-#pragma unroll
-        for (int i = 0; i < T; ++i) {
-            int32_t u = (int32_t)(pos - seg[SEG_HEAD + i]);
-            if (u < 0) u += (int32_t)a.NC;
-            w[i] = G[(uint32_t)u >> a.tshift];
-        }
-        uint64_t lo[V];
-        uint32_t hi[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) lo[v] = 0, hi[v] = 0;
-#pragma unroll
-        for (int i = 0; i < T; ++i)
-#pragma unroll
-            for (int v = 0; v < V; ++v) mac96(lo[v], hi[v], x[i][v], w[i]);
-        uint32_t r[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) r[v] = gf::add(reduce96(lo[v], hi[v]), old[v]);
-        store_nt<V>(r, desc(q), voff);
-    };
-    const uint32_t last = q1 - 1;
-    uint32_t pa[V], pb[V];
-    load_nt<V>(pa, desc(q0), voff);
-    for (uint32_t q = q0; q < q1; q += 2) {
-        load_nt<V>(pb, desc(min(q + 1, last)), voff);
-        step(q, pa);
-        if (q + 1 > last) break;
-        load_nt<V>(pa, desc(min(q + 2, last)), voff);
-        step(q + 1, pb);
-    }
+    stream_parity<T, V>(x, a.parity + stripe * a.M * a.S, a.S, c, a.G, a.p, q0, q1, [&](int i) { return seg[SEG_HEAD + i]; }, [](uint32_t q) { return q; });
 }
 
 // ---- a pool of stripes with absent blocks (fastecc_update_batch_set / _update_parity_batch_set) ----
@@ -419,13 +449,9 @@ __global__ __launch_bounds__(256) void update_set_kernel(const SetArgs s)
     const_u32_ptr lost = as_constant(s.lost) + seg[2];
     const_u32_ptr list = as_constant(a.list) + (size_t)seg[0] * SET_LIST_WORDS;
     const uint64_t stripe = ((uint64_t)list[3] << 32) | list[2];
-    const uint64_t col = ((uint64_t)slice * 64u + lane) * V;
-    const bool live = col < a.S;  // (V > 1 only when S % V == 0: a live lane's V words all exist)
-    const uint64_t lcol = live ? col : 0;
-    const uint32_t bytes = (uint32_t)(a.S * 4u);
-    const uint32_t voff = live ? (uint32_t)col * 4u : bytes;  // (S * 4 < 2^32: update_batch_run)
+    const LaneColumns c = lane_columns<V>(slice, lane, a.S);
     const uint32_t omask = (a.data || a.old_blocks) ? 0xFFFFFFFFu : 0u;
-    const uint32_t* obase = s.old_base + lcol;  // (pointer arithmetic, not integers: the loads stay global loads)
+    const uint32_t* obase = s.old_base + c.lcol;  // (pointer arithmetic, not integers: the loads stay global loads)
     uint32_t x[T][V];
     constexpr int H = T * V > 32 ? T / 2 : T;
 #pragma unroll
@@ -436,7 +462,7 @@ __global__ __launch_bounds__(256) void update_set_kernel(const SetArgs s)
             const_u32_ptr wr = list + ((uint32_t)(h + i) < len ? h + i : 0) * SET_LIST_WORDS;
             const uint64_t nrow = (uint64_t)(wr[1] & ~ROW_ABSENT) * a.S;
             const int64_t orow = (int64_t)(((uint64_t)wr[LIST_WORDS + 1] << 32) | wr[LIST_WORDS]);
-            load_vec<V>(nv[i], a.new_blocks + nrow + lcol);
+            load_vec<V>(nv[i], a.new_blocks + nrow + c.lcol);
             load_vec<V>(ov[i], obase + orow);
         }
 #pragma unroll
@@ -466,48 +492,9 @@ __global__ __launch_bounds__(256) void update_set_kernel(const SetArgs s)
             if (l == q) q++;
         }
     };
-    uint32_t q = present_from(q0);
+    const uint32_t q = present_from(q0);
     if (q >= q1) return;  // an empty run, or every parity block of the run is absent
-    const_u32_ptr G = as_constant(a.G);
-    const uint32_t* pbase = a.parity + stripe * a.M * a.S;
-    auto desc = [&](uint32_t qq) { return block_desc(pbase + (uint64_t)qq * a.S, bytes); };
-    auto step = [&](uint32_t qq, const uint32_t (&old)[V]) {
-        const uint32_t pos = a.off[qq >> a.qs] + ((qq & a.qmask) << a.ps);
-        uint32_t w[T];
-#pragma unroll
-        for (int i = 0; i < T; ++i) {
-            int32_t u = (int32_t)(pos - seg[SET_SEG_HEAD + i]);
-            if (u < 0) u += (int32_t)a.NC;
-            w[i] = G[(uint32_t)u >> a.tshift];
-        }
-        uint64_t lo[V];
-        uint32_t hi[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) lo[v] = 0, hi[v] = 0;
-#pragma unroll
-        for (int i = 0; i < T; ++i)
-#pragma unroll
-            for (int v = 0; v < V; ++v) mac96(lo[v], hi[v], x[i][v], w[i]);
-        uint32_t r[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) r[v] = gf::add(reduce96(lo[v], hi[v]), old[v]);
-        store_nt<V>(r, desc(qq), voff);
-    };
-    // (past the last present block the next load asks for the current block once more, as update_batch_kernel asks for `last`: never used)
-    uint32_t pa[V], pb[V];
-    load_nt<V>(pa, desc(q), voff);
-    for (;;) {
-        uint32_t next = present_from(q + 1);
-        load_nt<V>(pb, desc(next < q1 ? next : q), voff);
-        step(q, pa);
-        if (next >= q1) break;
-        q = next;
-        next = present_from(q + 1);
-        load_nt<V>(pa, desc(next < q1 ? next : q), voff);
-        step(q, pb);
-        if (next >= q1) break;
-        q = next;
-    }
+    stream_parity<T, V>(x, a.parity + stripe * a.M * a.S, a.S, c, a.G, a.p, q, q1, [&](int i) { return seg[SET_SEG_HEAD + i]; }, present_from);
 }
 
 struct ScatterArgs {
@@ -602,54 +589,57 @@ int update_state(fastecc_ctx* c, UpdateState** out)
     return FASTECC_OK;
 }
 
-template <int V> const void* parity_kernel_v(int T)
+// The instantiated kernels: T rows (the padded length of a pass or segment: 1, 2, 4, 8, ROWS) x V words per lane (4, 2, 1).  launch(T, V) gets
+// the pair as constants.
+template <int N> using Int = std::integral_constant<int, N>;
+template <int T, class Launch>
+void with_words(int V, Launch&& launch)
+{
+    switch (V) {
+        case 4: launch(Int<T>(), Int<4>()); break;
+        case 2: launch(Int<T>(), Int<2>()); break;
+        default: launch(Int<T>(), Int<1>()); break;
+    }
+}
+template <class Launch>
+void with_class(int T, int V, Launch&& launch)
 {
     switch (T) {
-        case 1: return (const void*)update_parity_kernel<1, V>;
-        case 2: return (const void*)update_parity_kernel<2, V>;
-        case 4: return (const void*)update_parity_kernel<4, V>;
-        case 8: return (const void*)update_parity_kernel<8, V>;
-        default: return (const void*)update_parity_kernel<ROWS, V>;
+        case 1: with_words<1>(V, launch); break;
+        case 2: with_words<2>(V, launch); break;
+        case 4: with_words<4>(V, launch); break;
+        case 8: with_words<8>(V, launch); break;
+        default: with_words<ROWS>(V, launch); break;
     }
 }
 
-template <int V> const void* batch_kernel_v(int T)
+// Words per lane: the widest V that divides the block's S words and leaves every pointer in `pointers` (ORed) on a V-word boundary —
+// everything a lane touches through it, read or written
+int lane_words(uint64_t S, uintptr_t pointers)
 {
-    switch (T) {
-        case 1: return (const void*)update_batch_kernel<1, V>;
-        case 2: return (const void*)update_batch_kernel<2, V>;
-        case 4: return (const void*)update_batch_kernel<4, V>;
-        case 8: return (const void*)update_batch_kernel<8, V>;
-        default: return (const void*)update_batch_kernel<ROWS, V>;
-    }
-}
-
-template <int V> const void* set_kernel_v(int T)
-{
-    switch (T) {
-        case 1: return (const void*)update_set_kernel<1, V>;
-        case 2: return (const void*)update_set_kernel<2, V>;
-        case 4: return (const void*)update_set_kernel<4, V>;
-        case 8: return (const void*)update_set_kernel<8, V>;
-        default: return (const void*)update_set_kernel<ROWS, V>;
-    }
+    int V = 4;
+    while (V > 1 && ((S % V) != 0 || (pointers & (4u * V - 1u)) != 0)) V >>= 1;
+    return V;
 }
 
 enum KernelKind { KERNEL_PARITY = 0, KERNEL_BATCH = 1, KERNEL_SET = 2 };  // update_parity_kernel, update_batch_kernel, update_set_kernel
 
 // waves of that kernel<T, V> one SIMD holds: 512 VGPRs in granules of 8, at most 8 (queried once per shape)
-int resident_waves_per_simd(int T, int V, KernelKind kind = KERNEL_PARITY)
+int resident_waves_per_simd(KernelKind kind, int T, int V)
 {
     static std::atomic<int> cache[3][3][5];  // zero-initialised (static storage)
-    const int vi = V == 4 ? 0 : V == 2 ? 1 : 2;
     int ti = 0;
     while ((1 << ti) < T) ti++;
-    std::atomic<int>& slot = cache[kind][vi][ti];
+    std::atomic<int>& slot = cache[kind][V >> 1][ti];  // (V in {1, 2, 4}: entries 0, 1, 2; nothing else indexes the cache)
     if (!slot.load()) {
         hipFuncAttributes attr{};
-        const void* fn = kind == KERNEL_SET     ? (V == 4 ? set_kernel_v<4>(T) : V == 2 ? set_kernel_v<2>(T) : set_kernel_v<1>(T))
-                         : kind == KERNEL_BATCH ? (V == 4 ? batch_kernel_v<4>(T) : V == 2 ? batch_kernel_v<2>(T) : batch_kernel_v<1>(T))
-                                                : (V == 4 ? parity_kernel_v<4>(T) : V == 2 ? parity_kernel_v<2>(T) : parity_kernel_v<1>(T));
+        const void* fn = nullptr;
+        with_class(T, V, [&](auto t_c, auto v_c) {
+            constexpr int Tc = t_c, Vc = v_c;
+            fn = kind == KERNEL_SET     ? (const void*)update_set_kernel<Tc, Vc>
+                 : kind == KERNEL_BATCH ? (const void*)update_batch_kernel<Tc, Vc>
+                                        : (const void*)update_parity_kernel<Tc, Vc>;
+        });
         int waves = 4;  // (if the query fails: a safe middle)
         if (hipFuncGetAttributes(&attr, fn) == hipSuccess && attr.numRegs > 0) waves = std::max(1, std::min(8, 512 / ((attr.numRegs + 7) / 8 * 8)));
         (void)hipGetLastError();
@@ -658,35 +648,24 @@ int resident_waves_per_simd(int T, int V, KernelKind kind = KERNEL_PARITY)
     return slot.load();
 }
 
-template <int V> void launch_parity_v(int T, const ParityArgs& a, dim3 grid, hipStream_t st)
-{
-    switch (T) {
-        case 1: hipLaunchKernelGGL((update_parity_kernel<1, V>), grid, dim3(256), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((update_parity_kernel<2, V>), grid, dim3(256), 0, st, a); break;
-        case 4: hipLaunchKernelGGL((update_parity_kernel<4, V>), grid, dim3(256), 0, st, a); break;
-        case 8: hipLaunchKernelGGL((update_parity_kernel<8, V>), grid, dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL((update_parity_kernel<ROWS, V>), grid, dim3(256), 0, st, a); break;
-    }
-}
-
-// pos(q) of the code, in the form the two parity kernels evaluate it
-template <class Args> void set_positions(const UpdateState* s, Args& pa)
+// pos(q) of the code, in the form the parity kernels evaluate it
+void set_positions(const UpdateState* s, Positions& p)
 {
     const CodeGeom& g = s->g;
-    pa.NC = (uint32_t)s->NC;
-    pa.tshift = s->tshift;
+    p.NC = (uint32_t)s->NC;
+    p.tshift = s->tshift;
     if (g.cosets > 1) {  // N a power of two: coset t = q >> log2 N
         int lgN = 0;
         while ((1ull << lgN) < g.N) lgN++;
-        pa.qs = (uint32_t)lgN;
-        pa.qmask = (uint32_t)(g.N - 1);
-        pa.ps = (uint32_t)g.e;
-        for (int t = 0; t < g.cosets && t < 8; t++) pa.off[t] = (uint32_t)code_parity_position(g.N, g.e, g.fold, g.cosets, (uint64_t)t * g.N);
+        p.qs = (uint32_t)lgN;
+        p.qmask = (uint32_t)(g.N - 1);
+        p.ps = (uint32_t)g.e;
+        for (int t = 0; t < g.cosets && t < 8; t++) p.off[t] = (uint32_t)code_parity_position(g.N, g.e, g.fold, g.cosets, (uint64_t)t * g.N);
     } else {
-        pa.qs = 31;  // q < 2^31: always entry 0
-        pa.qmask = 0xFFFFFFFFu;
-        pa.ps = (uint32_t)g.fold + 1u;
-        pa.off[0] = 1;
+        p.qs = 31;  // q < 2^31: always entry 0
+        p.qmask = 0xFFFFFFFFu;
+        p.ps = (uint32_t)g.fold + 1u;
+        p.off[0] = 1;
     }
 }
 
@@ -721,14 +700,12 @@ int update_pass(fastecc_ctx* c, UpdateState* s, uint32_t* data, uint32_t* parity
     pa.G = s->d_G;
     pa.S = S;
     pa.M = (uint32_t)g.Mu;
-    pa.rows = rows;
-    set_positions(s, pa);
+    set_positions(s, pa.p);
     if (S * 4 + 64 * 16 > 0xFFFFFFFFull) return FASTECC_E_UNSUPPORTED;  // (blocks of 4 GiB: the kernel addresses a block through one buffer descriptor)
-    int V = 4;
-    while (V > 1 && ((S % V) != 0 || ((uintptr_t)parity & (4u * V - 1u)) != 0)) V >>= 1;
+    const int V = lane_words(S, (uintptr_t)parity);  // (the delta rows are the context's own: aligned)
     pa.slices = (uint32_t)((S + 64u * V - 1) / (64u * V));
     // every wave resident at once (the kernel's waves per SIMD from its register count), each with an equal run of parity blocks
-    const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(T, V);
+    const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(KERNEL_PARITY, T, V);
     const uint64_t runs = std::max<uint64_t>(1, std::min<uint64_t>(g.Mu, target / pa.slices));
     pa.run = (uint32_t)((g.Mu + runs - 1) / runs);
     const uint64_t waves = (uint64_t)pa.slices * ((g.Mu + pa.run - 1) / pa.run);
@@ -737,9 +714,10 @@ int update_pass(fastecc_ctx* c, UpdateState* s, uint32_t* data, uint32_t* parity
     const dim3 grid((unsigned)((waves + 3) / 4));
     {
         ProfScope ps(c, st, "update_parity", g.Mu * S * 8);
-        if (V == 4) launch_parity_v<4>(T, pa, grid, st);
-        else if (V == 2) launch_parity_v<2>(T, pa, grid, st);
-        else launch_parity_v<1>(T, pa, grid, st);
+        with_class(T, V, [&](auto t_c, auto v_c) {
+            constexpr int Tc = t_c, Vc = v_c;
+            hipLaunchKernelGGL((update_parity_kernel<Tc, Vc>), grid, dim3(256), 0, st, pa);
+        });
         HIP_TRY(hipGetLastError());
     }
     return FASTECC_OK;
@@ -826,28 +804,6 @@ struct BatchLaunch {
     uint64_t parity_blocks;  // parity blocks its segments read and write (the profile's byte count)
 };
 
-template <int V> void launch_batch_v(int T, const BatchArgs& a, dim3 grid, hipStream_t st)
-{
-    switch (T) {
-        case 1: hipLaunchKernelGGL((update_batch_kernel<1, V>), grid, dim3(256), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((update_batch_kernel<2, V>), grid, dim3(256), 0, st, a); break;
-        case 4: hipLaunchKernelGGL((update_batch_kernel<4, V>), grid, dim3(256), 0, st, a); break;
-        case 8: hipLaunchKernelGGL((update_batch_kernel<8, V>), grid, dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL((update_batch_kernel<ROWS, V>), grid, dim3(256), 0, st, a); break;
-    }
-}
-
-template <int V> void launch_set_v(int T, const SetArgs& a, dim3 grid, hipStream_t st)
-{
-    switch (T) {
-        case 1: hipLaunchKernelGGL((update_set_kernel<1, V>), grid, dim3(256), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((update_set_kernel<2, V>), grid, dim3(256), 0, st, a); break;
-        case 4: hipLaunchKernelGGL((update_set_kernel<4, V>), grid, dim3(256), 0, st, a); break;
-        case 8: hipLaunchKernelGGL((update_set_kernel<8, V>), grid, dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL((update_set_kernel<ROWS, V>), grid, dim3(256), 0, st, a); break;
-    }
-}
-
 constexpr uint64_t LAUNCH_WAVES = 1ull << 24;  // a dispatch holds fewer than 2^32 work-items per dimension: at most 2^22 workgroups of 4 waves
 
 // What fastecc_update_batch_set / _update_parity_batch_set add to a call (update_batch_set_impl fills it): every array is by write of the SORTED list.
@@ -870,9 +826,7 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
     if (rc != FASTECC_OK) return rc;
     const uint64_t S = c->S, K = c->K, M = c->Mu, n = sw.size();
     const int list_words = set ? SET_LIST_WORDS : LIST_WORDS, seg_head = set ? SET_SEG_HEAD : SEG_HEAD;
-    int V = 4;
-    const uintptr_t align = (uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks;  // every pointer a lane touches
-    while (V > 1 && ((S % V) != 0 || (align & (4u * V - 1u)) != 0)) V >>= 1;
+    const int V = lane_words(S, (uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks);
     const uint64_t slices = (S + 64u * V - 1) / (64u * V);
     if (slices * M > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (one segment's waves fit a launch)
     const auto wait_buffers = [&]() -> int {  // the host-side wait for the kernels that read an internal buffer about to be replaced
@@ -971,12 +925,12 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
         a.M = (uint32_t)M;
         a.slices = (uint32_t)slices;
         a.e = (uint32_t)s->g.e;
-        set_positions(s, a);
+        set_positions(s, a.p);
         sa.old_base = old_base;
         if (set) sa.lost = set->view.lost_parity;
         for (const BatchLaunch& l : launches) {
             // at least every resident wave of the device, where the parity count allows it: runs of parity blocks per segment
-            const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(l.T, V, set ? KERNEL_SET : KERNEL_BATCH);
+            const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(set ? KERNEL_SET : KERNEL_BATCH, l.T, V);
             const uint64_t per_run = (uint64_t)l.segs * slices;
             const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>(M, (target + per_run - 1) / per_run));
             a.run = (uint32_t)((M + want - 1) / want);
@@ -988,15 +942,11 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
                 a.segs = s->list.dev + n * list_words + l.seg0 + (size_t)s0 * (seg_head + l.T);
                 a.waves = (uint32_t)waves;
                 const dim3 grid((unsigned)((waves + 3) / 4));
-                if (set) {
-                    if (V == 4) launch_set_v<4>(l.T, sa, grid, st);
-                    else if (V == 2) launch_set_v<2>(l.T, sa, grid, st);
-                    else launch_set_v<1>(l.T, sa, grid, st);
-                } else {
-                    if (V == 4) launch_batch_v<4>(l.T, a, grid, st);
-                    else if (V == 2) launch_batch_v<2>(l.T, a, grid, st);
-                    else launch_batch_v<1>(l.T, a, grid, st);
-                }
+                with_class(l.T, V, [&](auto t_c, auto v_c) {
+                    constexpr int Tc = t_c, Vc = v_c;
+                    if (set) hipLaunchKernelGGL((update_set_kernel<Tc, Vc>), grid, dim3(256), 0, st, sa);
+                    else hipLaunchKernelGGL((update_batch_kernel<Tc, Vc>), grid, dim3(256), 0, st, a);
+                });
                 HIP_TRY(hipGetLastError());
             }
         }
@@ -1009,9 +959,7 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
                 ca.list = s->list.dev + w0 * list_words;
                 ca.waves = (uint32_t)waves;
                 const dim3 grid((unsigned)((waves + 3) / 4));
-                if (V == 4) hipLaunchKernelGGL(update_scatter_kernel<4>, grid, dim3(256), 0, st, ca);
-                else if (V == 2) hipLaunchKernelGGL(update_scatter_kernel<2>, grid, dim3(256), 0, st, ca);
-                else hipLaunchKernelGGL(update_scatter_kernel<1>, grid, dim3(256), 0, st, ca);
+                with_words<1>(V, [&](auto, auto v_c) { hipLaunchKernelGGL(update_scatter_kernel<decltype(v_c)::value>, grid, dim3(256), 0, st, ca); });
                 HIP_TRY(hipGetLastError());
             }
         }
