@@ -1,6 +1,6 @@
 // drivers.hpp — what the translation units behind the C ABI share beyond context.hpp: the encode drivers (encode.hip), the host staging
-// paths (host_stage.hip) and context creation (create.hip), called from the entry points in api.hip, decode.hip, scrub.hip, update.hip and
-// sharded.hip; and the one mechanism each for profiling (ProfScope, P61Hooks), for ordering the internal buffers between streams
+// paths (host_stage.hip) and context creation (create.hip), called from the entry points in api.hip, the decoder's three files (decode_prepare.hip,
+// decode.hip, pattern_set.hip), scrub.hip, update.hip and sharded.hip; and the one mechanism each for profiling (ProfScope, P61Hooks), for ordering the internal buffers between streams
 // (with_internal_buffers, wait_idle) and for the extent of a pool (pool_extent).  Nothing here is part of the ABI.
 #pragma once
 #include <condition_variable>
@@ -125,6 +125,7 @@ inline int pool_extent(const fastecc_ctx* c, const void* data, const void* parit
 // given twice: on the host (the stripe-by-stripe forms) and on the device (the batched launch).  The caller has checked the pool's pointers and
 // extent; takes the context's call lock itself.
 int repair_list(fastecc_ctx* c, void* data, void* parity, const uint64_t* host_list, const uint64_t* dev_list, uint64_t count, void* stream);
+// ---- pattern_set.hip, for the scrubber ----
 // What a pattern set takes (fastecc_decode_prepare_set, and the private set below)
 constexpr uint64_t SET_MAX_PATTERNS = 4096;
 constexpr size_t SET_MAX_LOST = 16;  // one direct pass of a single sweep: pad <= 16
@@ -134,8 +135,9 @@ constexpr size_t SET_MAX_LOST = 16;  // one direct pass of a single sweep: pad <
 // call lock itself and returns only when the stream's work is done and the private set is freed.
 int repair_lost_sets(fastecc_ctx* c, void* data, void* parity, const std::vector<std::vector<uint32_t>>& lost_sets, const std::vector<uint64_t>& stripes,
                      const std::vector<uint32_t>& set_of, void* stream);
-// ---- decode.hip, for the degraded writes (update.hip: fastecc_update_batch_set) ----
-// What a write under the context's pattern set (fastecc_decode_prepare_set) needs of it; PatternSet itself stays private to decode.hip.  The caller
+// ---- pattern_set.hip, for the degraded writes (update.hip: fastecc_update_batch_set) ----
+// What a write under the context's pattern set (fastecc_decode_prepare_set) needs of it; PatternSet itself stays private to the decoder's files
+// (decode_state.hpp).  The caller
 // holds c->mu, and everything is valid until the lock is released (a later fastecc_decode_prepare_set waits for the enqueued work: wait_idle).
 constexpr int SET_LOST_ROW = (int)SET_MAX_LOST + 1;  // words per pattern of lost_parity: its lost parity blocks, increasing, then SET_LOST_END to the end
 constexpr uint32_t SET_LOST_END = 0xFFFFFFFFu;       // (a pattern loses at most SET_MAX_LOST blocks: every row ends with at least one)

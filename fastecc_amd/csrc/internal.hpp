@@ -71,10 +71,10 @@ template <class F> int guarded(F body)
     }
 }
 
-struct DecodeState;                        // decode.hip: tables of one erasure pattern + the size-2k transform context
+struct DecodeState;                        // decode_state.hpp: tables of one erasure pattern + the size-2k transform context
 void destroy_decode_state(DecodeState*);   // decode.hip, called by fastecc_destroy
-struct PatternSet;                         // decode.hip: the tables of a pattern set (fastecc_decode_prepare_set) and the set calls' list buffers
-void destroy_pattern_set(PatternSet*);     // decode.hip, called by fastecc_destroy
+struct PatternSet;                         // decode_state.hpp: the tables of a pattern set (fastecc_decode_prepare_set) and the set calls' list buffers
+void destroy_pattern_set(PatternSet*);     // pattern_set.hip, called by fastecc_destroy
 struct ScrubState;                         // scrub.hip: error detection and location (fastecc_verify, _locate_errors, _correct)
 void destroy_scrub_state(ScrubState*);     // scrub.hip, called by fastecc_destroy
 struct UpdateState;                        // update.hip: the parity update's weight table and delta rows (fastecc_update, _update_parity)
@@ -82,7 +82,7 @@ void destroy_update_state(UpdateState*);   // update.hip, called by fastecc_dest
 
 // Every GF(0xFFF00001) code is f (degree < N, the transform order: a power of two, or q * 2^m for the mixed-radix codes) on a subset of
 // the NC-th roots of unity, NC = N << e, position u <-> w_NC^u: data block i at i << e, parity block q at code_parity_position — odd
-// multiples of 2^fold for the codes inside (2N,N), the cosets' offsets for n = 4k / 8k (fastecc_create).  decode.hip, scrub.hip, update.hip.
+// multiples of 2^fold for the codes inside (2N,N), the cosets' offsets for n = 4k / 8k (fastecc_create).  decode_prepare.hip, scrub.hip, update.hip.
 inline int code_coset_shift(int cosets)
 {
     int e = 1;
@@ -215,7 +215,7 @@ int run_gathered(fastecc_ctx* c, const uint32_t* even_blocks, const uint32_t* od
 // Half a stand-alone transform of a transform context, on the word columns [0, width) of every block: dit = false runs the
 // DIF passes (natural order in, bit-reversed order out), dit = true the mirrored DIT passes (bit-reversed in, natural out);
 // unscaled, forward roots or (inverse_roots) their inverses.  A product of transforms does not care about the order, so
-// polynomial products on the device need no permutation pass (decode.hip: the erasure locator's product tree).
+// polynomial products on the device need no permutation pass (decode_prepare.hip: the erasure locator's product tree).
 int transform_bitrev(fastecc_ctx* c, const uint32_t* in, uint32_t* out, bool dit, bool inverse_roots, uint32_t width, hipStream_t st);
 // The order in which that first pass wants row_factor: returns false when it is the natural order (register pass),
 // else fills `order` with order[i] = codeword position whose factor is entry i of the table (two-window DIF tile:

@@ -37,7 +37,7 @@
 //                verify_pool_impl, locate_pool_impl and CorrectPool.
 //   correction   correct_stripe: locate, fastecc_decode_prepare + fastecc_repair of the located and the absent blocks, the closing verify.
 //                CorrectPool: flag_and_locate, group_by_lost_set, repair_groups (the lost sets of at most 16 blocks through ONE pattern set private to
-//                the call, decode.hip repair_lost_sets, where the form has one: section 27; every other distinct lost set one prepare and one list-form
+//                the call, pattern_set.hip repair_lost_sets, where the form has one: section 27; every other distinct lost set one prepare and one list-form
 //                repair, decode.hip repair_list), closing_verify, fallbacks (correct_stripe on what the grouped path does not take).
 //   entry points argument checks, then the stage inside on_device.
 #include <algorithm>
