@@ -132,6 +132,13 @@ def lib():
     L.fastecc_update_batch_set.argtypes, L.fastecc_update_batch_set.restype = [vp, vp, vp, u64, ctypes.POINTER(u32), u64p, u64, vp, vp], i32
     L.fastecc_update_parity_batch_set.argtypes = [vp, vp, u64, ctypes.POINTER(u32), u64p, u64, vp, vp, vp]
     L.fastecc_update_parity_batch_set.restype = i32
+    L.fastecc_update_batch_window.argtypes, L.fastecc_update_batch_window.restype = [vp, vp, vp, u64, u64p, u64, u64, u64, vp, vp], i32
+    L.fastecc_update_parity_batch_window.argtypes = [vp, vp, u64, u64p, u64, u64, u64, vp, vp, vp]
+    L.fastecc_update_parity_batch_window.restype = i32
+    L.fastecc_update_batch_set_window.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u32), u64p, u64, u64, u64, vp, vp]
+    L.fastecc_update_batch_set_window.restype = i32
+    L.fastecc_update_parity_batch_set_window.argtypes = [vp, vp, u64, ctypes.POINTER(u32), u64p, u64, u64, u64, vp, vp, vp]
+    L.fastecc_update_parity_batch_set_window.restype = i32
     L.fastecc_code_coefficient.argtypes = [u64, u64, ctypes.c_uint, u64, u64, ctypes.POINTER(u32)]
     L.fastecc_code_coefficient.restype = i32
     L.fastecc_gf_berlekamp_massey.argtypes = [ctypes.POINTER(u32), u32, ctypes.POINTER(u32), u32]
@@ -627,42 +634,74 @@ class Encoder:
                "fastecc_update_parity")
         return parity
 
-    def update_batch(self, data, parity, count, writes, new, stream=0):
+    def _write_window(self, col0, width):
+        """None for the whole block (col0=0, width=None: the whole-block entry point), else the checked (col0, width) of a window call"""
+        if width is None and isinstance(col0, int) and not isinstance(col0, bool) and col0 == 0:
+            return None
+        return self._read_window(col0, width)
+
+    def update_batch(self, data, parity, count, writes, new, stream=0, col0=0, width=None):
         """Small writes into a pool of `count` stripes back to back in device memory (the layout of decode_batch): pool block
         writes[u] = b * k + i (data block i of stripe b; distinct, any order) becomes row u of `new`, and every touched stripe's parity is
-        brought up to date — data and parity of those stripes then equal encode of the new stripe.  Other stripes are not touched."""
+        brought up to date — data and parity of those stripes then equal encode of the new stripe.  Other stripes are not touched.
+        A window (col0, width in words; width=None: from col0 to the end of the block): row u of `new` holds `width` words and replaces the
+        words [col0, col0 + width) of its block; no word outside those columns is read or written, in any block."""
         count = self._batch_count(count)
+        window = self._write_window(col0, width)
         n, arr = self._block_list(writes)
-        _check(lib().fastecc_update_batch(self._h, _addr(data), _addr(parity), count, arr, n, _addr(new), stream or None), "fastecc_update_batch")
+        if window is None:
+            _check(lib().fastecc_update_batch(self._h, _addr(data), _addr(parity), count, arr, n, _addr(new), stream or None), "fastecc_update_batch")
+        else:
+            _check(lib().fastecc_update_batch_window(self._h, _addr(data), _addr(parity), count, arr, n, window[0], window[1], _addr(new), stream or None),
+                   "fastecc_update_batch_window")
         return data, parity
 
-    def update_parity_batch(self, parity, count, writes, new, old=None, stream=0):
-        """update_batch for the parity alone: pool blocks `writes` changed from row u of `old` (None: from zero) to row u of `new`."""
+    def update_parity_batch(self, parity, count, writes, new, old=None, stream=0, col0=0, width=None):
+        """update_batch for the parity alone: pool blocks `writes` changed from row u of `old` (None: from zero) to row u of `new` (a window: rows
+        of `width` words, as for update_batch)."""
         count = self._batch_count(count)
+        window = self._write_window(col0, width)
         n, arr = self._block_list(writes)
-        _check(lib().fastecc_update_parity_batch(self._h, _addr(parity), count, arr, n, _addr(old), _addr(new), stream or None),
-               "fastecc_update_parity_batch")
+        if window is None:
+            _check(lib().fastecc_update_parity_batch(self._h, _addr(parity), count, arr, n, _addr(old), _addr(new), stream or None),
+                   "fastecc_update_parity_batch")
+        else:
+            _check(lib().fastecc_update_parity_batch_window(self._h, _addr(parity), count, arr, n, window[0], window[1], _addr(old), _addr(new),
+                                                            stream or None), "fastecc_update_parity_batch_window")
         return parity
 
-    def update_batch_set(self, data, parity, count, pattern_of, writes, new, stream=0):
+    def update_batch_set(self, data, parity, count, pattern_of, writes, new, stream=0, col0=0, width=None):
         """update_batch for a pool whose stripes miss blocks: stripe b under pattern pattern_of[b] of the decode_prepare_set set (PATTERN_NONE,
         or a pattern that loses nothing: whole).  Every PRESENT block of a touched stripe becomes what encode gives for the stripe's true data
         — absent data blocks as decode would rebuild them — with the written blocks replaced; absent blocks are neither read nor written, so a
-        later repair_batch_set under the same patterns completes the stripes, and read_batch_set of an absent written block returns its new row."""
+        later repair_batch_set under the same patterns completes the stripes, and read_batch_set of an absent written block returns its new row.
+        A window (col0, width, as for update_batch): the same for the words [col0, col0 + width) alone, the old window of an absent written block
+        rebuilt from those columns of the survivors."""
         count = self._batch_count(count)
+        window = self._write_window(col0, width)
         keep, po = self._pattern_list(pattern_of, count)
         n, arr = self._block_list(writes)
-        _check(lib().fastecc_update_batch_set(self._h, _addr(data), _addr(parity), count, po, arr, n, _addr(new), stream or None), "fastecc_update_batch_set")
+        if window is None:
+            _check(lib().fastecc_update_batch_set(self._h, _addr(data), _addr(parity), count, po, arr, n, _addr(new), stream or None),
+                   "fastecc_update_batch_set")
+        else:
+            _check(lib().fastecc_update_batch_set_window(self._h, _addr(data), _addr(parity), count, po, arr, n, window[0], window[1], _addr(new),
+                                                         stream or None), "fastecc_update_batch_set_window")
         del keep
         return data, parity
 
-    def update_parity_batch_set(self, parity, count, pattern_of, writes, new, old=None, stream=0):
+    def update_parity_batch_set(self, parity, count, pattern_of, writes, new, old=None, stream=0, col0=0, width=None):
         """update_parity_batch that leaves the absent parity blocks of every touched stripe alone (only the parity flags of a pattern matter)."""
         count = self._batch_count(count)
+        window = self._write_window(col0, width)
         keep, po = self._pattern_list(pattern_of, count)
         n, arr = self._block_list(writes)
-        _check(lib().fastecc_update_parity_batch_set(self._h, _addr(parity), count, po, arr, n, _addr(old), _addr(new), stream or None),
-               "fastecc_update_parity_batch_set")
+        if window is None:
+            _check(lib().fastecc_update_parity_batch_set(self._h, _addr(parity), count, po, arr, n, _addr(old), _addr(new), stream or None),
+                   "fastecc_update_parity_batch_set")
+        else:
+            _check(lib().fastecc_update_parity_batch_set_window(self._h, _addr(parity), count, po, arr, n, window[0], window[1], _addr(old), _addr(new),
+                                                                stream or None), "fastecc_update_parity_batch_set_window")
         del keep
         return parity
 

@@ -37,6 +37,13 @@
 //   update_set_kernel    : update_batch_kernel with each old row at an offset the host chose (the pool, or d_recon) and the stripe's absent parity
 //                          blocks skipped — neither loaded nor stored: stream_parity's next block is the next PRESENT one;
 //   update_scatter_kernel: only the writes whose data block is present.
+//
+// One window of word columns [col0, col0 + width) of every written block (the four fastecc_update_*_window calls): the same host code
+// once more (update_batch_run<true> with a Window), rows of `width` words, and on the stream
+//   direct_run_read             : the old WINDOWS of the absent written blocks, into d_recon at pitch width;
+//   update_window_kernel        : update_set_kernel with the lane's columns counted from the window, for the set forms and the plain ones alike (a call
+//                                 without a pattern set gives every stripe a row that loses nothing); no word outside the window is loaded or stored;
+//   update_window_scatter_kernel: row u into the window of its present data block.
 #include <algorithm>
 #include <atomic>
 #include <vector>
@@ -497,6 +504,104 @@ __global__ __launch_bounds__(256) void update_set_kernel(const SetArgs s)
     stream_parity<T, V>(x, a.parity + stripe * a.M * a.S, a.S, c, a.G, a.p, q, q1, [&](int i) { return seg[SET_SEG_HEAD + i]; }, present_from);
 }
 
+// ---- a column window of the pool's blocks (the four fastecc_update_*_window calls) ----
+// One kernel for the four calls: the list and the segments in update_set_kernel's formats (a call without a pattern set points every segment at
+// UpdateState::d_lost_none, a row that loses nothing).  b.parity is the pool's parity shifted by col0 words, b.S the pool's block (the stride of the
+// parity blocks), b.slices the slices of `width` words; an old row's offset from old_base already holds col0 (a pool block) or counts rows of `width`
+// words (the reconstruction buffer, old_blocks).
+struct WindowArgs {
+    SetArgs s;
+    uint64_t width;  // words of a row of new_blocks, old_blocks and the reconstruction buffer, and of the window in a pool block
+};
+
+// update_set_kernel over the word columns [col0, col0 + width) of every block.  The lane's columns count from the window (a lane past `width` is dead),
+// the new rows and the old rows outside the pool sit at pitch `width`, and the parity blocks are addressed through descriptors of width * 4 bytes
+// whose bases are S words apart: no word outside the window is loaded or stored.  Rows past the segment's length and dead lanes load from valid
+// addresses inside the window (row 0, column 0 of the window) without a branch.  All stripe offsets are 64-bit.
+template <int T, int V>
+__global__ __launch_bounds__(256) void update_window_kernel(const WindowArgs w)
+{
+    const BatchArgs& a = w.s.b;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (wave >= a.waves) return;
+    const uint32_t slice = wave % a.slices, rest = wave / a.slices;
+    const uint32_t q0 = (rest % a.runs) * a.run, q1 = min(q0 + a.run, a.M);
+    const_u32_ptr seg = as_constant(a.segs) + (size_t)(rest / a.runs) * (SET_SEG_HEAD + T);
+    const uint32_t len = seg[1];
+    const_u32_ptr lost = as_constant(w.s.lost) + seg[2];
+    const_u32_ptr list = as_constant(a.list) + (size_t)seg[0] * SET_LIST_WORDS;
+    const uint64_t stripe = ((uint64_t)list[3] << 32) | list[2];
+    const LaneColumns c = lane_columns<V>(slice, lane, w.width);
+    const uint32_t omask = (a.data || a.old_blocks) ? 0xFFFFFFFFu : 0u;
+    const uint32_t* obase = w.s.old_base + c.lcol;
+    const uint32_t* nbase = a.new_blocks + c.lcol;
+    uint32_t x[T][V];
+    constexpr int H = T * V > 32 ? T / 2 : T;
+#pragma unroll
+    for (int h = 0; h < T; h += H) {
+        uint32_t nv[H][V], ov[H][V];
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            const_u32_ptr wr = list + ((uint32_t)(h + i) < len ? h + i : 0) * SET_LIST_WORDS;
+            const uint64_t nrow = (uint64_t)(wr[1] & ~ROW_ABSENT) * w.width;
+            const int64_t orow = (int64_t)(((uint64_t)wr[LIST_WORDS + 1] << 32) | wr[LIST_WORDS]);
+            load_vec<V>(nv[i], nbase + nrow);
+            load_vec<V>(ov[i], obase + orow);
+        }
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            const uint32_t imask = (uint32_t)(h + i) < len ? 0xFFFFFFFFu : 0u;
+#pragma unroll
+            for (int v = 0; v < V; ++v) x[h + i][v] = gf::sub(nv[i][v], ov[i][v] & omask) & imask;
+        }
+        if constexpr (H < T) {  // (as in update_set_kernel: the first half's differences are formed before the second half's loads go out)
+#pragma unroll
+            for (int i = 0; i < H; ++i)
+#pragma unroll
+                for (int v = 0; v < V; ++v) asm volatile("" : "+v"(x[h + i][v]));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    uint32_t cur = 0;
+    auto present_from = [&](uint32_t q) {
+        for (;;) {
+            const uint32_t l = lost[cur];
+            if (l > q) return q;  // (SET_LOST_END ends every row)
+            cur++;
+            if (l == q) q++;
+        }
+    };
+    const uint32_t q = present_from(q0);
+    if (q >= q1) return;
+    stream_parity<T, V>(x, a.parity + stripe * a.M * a.S, a.S, c, a.G, a.p, q, q1, [&](int i) { return seg[SET_SEG_HEAD + i]; }, present_from);
+}
+
+struct WindowScatterArgs {
+    uint32_t* data;  // the pool's data shifted by col0 words
+    const uint32_t* new_blocks;
+    const uint32_t* list;  // the launch's first write (SET_LIST_WORDS each)
+    uint64_t S, K, width;
+    uint32_t slices, waves, e;
+};
+
+// update_scatter_kernel for a window: row u of new_blocks (pitch width) into columns [col0, col0 + width) of its present data block
+template <int V>
+__global__ __launch_bounds__(256) void update_window_scatter_kernel(const WindowScatterArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (wave >= a.waves) return;
+    const_u32_ptr wr = as_constant(a.list) + (size_t)(wave / a.slices) * SET_LIST_WORDS;
+    if (wr[1] & ROW_ABSENT) return;  // (wave-uniform)
+    const uint64_t stripe = ((uint64_t)wr[3] << 32) | wr[2];
+    const uint64_t col = ((uint64_t)(wave % a.slices) * 64u + lane) * V;
+    if (col >= a.width) return;
+    uint32_t t[V];
+    load_vec<V>(t, a.new_blocks + (uint64_t)wr[1] * a.width + col);
+    store_vec<V>(a.data + (stripe * a.K + (wr[0] >> a.e)) * a.S + col, t);
+}
+
 struct ScatterArgs {
     uint32_t* data;
     const uint32_t* new_blocks;
@@ -538,6 +643,9 @@ struct UpdateState {
     StagedList<uint32_t> list;
     // fastecc_update_batch_set: the old rows of one call's absent written blocks, S words each, rebuilt by direct_run_read (an internal buffer)
     DeviceBuf<uint32_t> d_recon;
+    // the window calls: such rows at `width` words each; and one row of SET_LOST_ROW words that loses nothing, for the calls without a pattern set
+    // (written once, by a synchronous copy at the first window call of the context)
+    DeviceBuf<uint32_t> d_lost_none;
 };
 
 void destroy_update_state(UpdateState* s) { delete s; }
@@ -621,13 +729,17 @@ int lane_words(uint64_t S, uintptr_t pointers)
     while (V > 1 && ((S % V) != 0 || (pointers & (4u * V - 1u)) != 0)) V >>= 1;
     return V;
 }
+// ... for the word columns [col0, col0 + width) of such blocks, with rows of `width` words beside them: V also divides col0 and width, so a
+// window's first word in a block and every row of `width` words lie on a V-word boundary where the pointers do (V a power of two: one test)
+int lane_words(uint64_t S, uint64_t col0, uint64_t width, uintptr_t pointers) { return lane_words(S | col0 | width, pointers); }
 
-enum KernelKind { KERNEL_PARITY = 0, KERNEL_BATCH = 1, KERNEL_SET = 2 };  // update_parity_kernel, update_batch_kernel, update_set_kernel
+// update_parity_kernel, update_batch_kernel, update_set_kernel, update_window_kernel
+enum KernelKind { KERNEL_PARITY = 0, KERNEL_BATCH = 1, KERNEL_SET = 2, KERNEL_WINDOW = 3 };
 
 // waves of that kernel<T, V> one SIMD holds: 512 VGPRs in granules of 8, at most 8 (queried once per shape)
 int resident_waves_per_simd(KernelKind kind, int T, int V)
 {
-    static std::atomic<int> cache[3][3][5];  // zero-initialised (static storage)
+    static std::atomic<int> cache[4][3][5];  // zero-initialised (static storage)
     int ti = 0;
     while ((1 << ti) < T) ti++;
     std::atomic<int>& slot = cache[kind][V >> 1][ti];  // (V in {1, 2, 4}: entries 0, 1, 2; nothing else indexes the cache)
@@ -636,7 +748,8 @@ int resident_waves_per_simd(KernelKind kind, int T, int V)
         const void* fn = nullptr;
         with_class(T, V, [&](auto t_c, auto v_c) {
             constexpr int Tc = t_c, Vc = v_c;
-            fn = kind == KERNEL_SET     ? (const void*)update_set_kernel<Tc, Vc>
+            fn = kind == KERNEL_WINDOW  ? (const void*)update_window_kernel<Tc, Vc>
+                 : kind == KERNEL_SET   ? (const void*)update_set_kernel<Tc, Vc>
                  : kind == KERNEL_BATCH ? (const void*)update_batch_kernel<Tc, Vc>
                                         : (const void*)update_parity_kernel<Tc, Vc>;
         });
@@ -816,19 +929,41 @@ struct SetForm {
     uint64_t rebuilt_rows_read = 0;        // rows those passes read, and the ones they write
 };
 
+// The word columns [col0, col0 + width) of every block that a window call works on (checked against S by the caller); width == 0: the whole block.
+struct Window {
+    uint64_t col0 = 0, width = 0;
+};
+
 // sw: the call's writes, sorted and checked.  data == null: the parity form.  set != null: stripes with absent blocks (update_set_kernel; with data, first
-// the old rows of the absent written blocks into the reconstruction buffer, and at the end only present blocks are stored).
+// the old rows of the absent written blocks into the reconstruction buffer, and at the end only present blocks are stored).  A window (win.width != 0):
+// update_window_kernel and update_window_scatter_kernel for either form, with the list and the segments in the set form's formats, the caller's rows and
+// the reconstruction buffer at pitch W = width, and col0 folded into the parity pointer, the scatter's data pointer and the old rows' pool offsets.
+// WINDOW is a template parameter so that the whole-block calls keep the host code they had: W = S and col0 = 0 fold away.
+template <bool WINDOW>
 int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std::vector<SortedWrite>& sw, const uint32_t* old_blocks, const uint32_t* new_blocks,
-                     hipStream_t st, const SetForm* set = nullptr)
+                     hipStream_t st, const SetForm* set, const Window win)
 {
     UpdateState* s = nullptr;
     int rc = update_state(c, &s);
     if (rc != FASTECC_OK) return rc;
     const uint64_t S = c->S, K = c->K, M = c->Mu, n = sw.size();
-    const int list_words = set ? SET_LIST_WORDS : LIST_WORDS, seg_head = set ? SET_SEG_HEAD : SEG_HEAD;
-    const int V = lane_words(S, (uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks);
-    const uint64_t slices = (S + 64u * V - 1) / (64u * V);
+    constexpr bool window = WINDOW;
+    const bool long_form = set || window;
+    const uint64_t W = window ? win.width : S, col0 = window ? win.col0 : 0;
+    const int list_words = long_form ? SET_LIST_WORDS : LIST_WORDS, seg_head = long_form ? SET_SEG_HEAD : SEG_HEAD;
+    const uintptr_t pointers = (uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks;
+    const int V = window ? lane_words(S, col0, W, pointers) : lane_words(S, pointers);
+    const uint64_t slices = (W + 64u * V - 1) / (64u * V);
     if (slices * M > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (one segment's waves fit a launch)
+    if (window && !set && !s->d_lost_none) {  // (the whole-block calls never read it)
+        const std::vector<uint32_t> none(SET_LOST_ROW, SET_LOST_END);
+        RC_TRY(s->d_lost_none.alloc(none.size()));
+        const hipError_t e = hipMemcpy(s->d_lost_none, none.data(), none.size() * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            s->d_lost_none.reset();  // (the next call tries again)
+            return hip_fail(e, "hipMemcpy");
+        }
+    }
     const auto wait_buffers = [&]() -> int {  // the host-side wait for the kernels that read an internal buffer about to be replaced
         if (c->buf_used) HIP_TRY(hipEventSynchronize(c->buf_event));
         return FASTECC_OK;
@@ -837,10 +972,10 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
     rc = s->list.reserve(n * (list_words + seg_head + 1), wait_buffers);
     if (rc != FASTECC_OK) return rc;
     if (set && set->rebuilt) {
-        if (direct_read_waves_per_entry(data, parity, nullptr, S, 0, S) > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;
-        if (set->rebuilt > s->d_recon.capacity() / S) {  // (rebuilt * S words fit 64 bits: the call's new blocks are more)
+        if (direct_read_waves_per_entry(data, parity, nullptr, S, col0, W) > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;
+        if (set->rebuilt > s->d_recon.capacity() / W) {  // (rebuilt * W words fit 64 bits: the call's new blocks are more)
             RC_TRY(wait_buffers());
-            RC_TRY(s->d_recon.grow(std::max<uint64_t>(set->rebuilt * S, 2 * s->d_recon.capacity())));  // FASTECC_E_NOMEM: it does not fit
+            RC_TRY(s->d_recon.grow(std::max<uint64_t>(set->rebuilt * W, 2 * s->d_recon.capacity())));  // FASTECC_E_NOMEM: it does not fit
         }
     }
 
@@ -859,10 +994,11 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
             wr[1] = sw[g].row;
             wr[2] = (uint32_t)b;
             wr[3] = (uint32_t)(b >> 32);
-            if (set) {  // its old row, from old_base
-                const uint32_t r = set->old_row[g];
-                const uint64_t off = r != OLD_IN_POOL ? (uint64_t)(((intptr_t)s->d_recon.get() - (intptr_t)old_base) / 4) + (uint64_t)r * S  // (both on word boundaries)
-                                                      : (data ? sw[g].index : (uint64_t)sw[g].row) * S;
+            if (long_form) {  // its old row, from old_base (a window: its columns of the pool's block, or a row of W words)
+                const uint32_t r = set ? set->old_row[g] : OLD_IN_POOL;
+                const uint64_t off = r != OLD_IN_POOL ? (uint64_t)(((intptr_t)s->d_recon.get() - (intptr_t)old_base) / 4) + (uint64_t)r * W  // (both on word boundaries)
+                                     : data       ? sw[g].index * S + col0
+                                                  : (uint64_t)sw[g].row * W;
                 wr[LIST_WORDS] = (uint32_t)off;
                 wr[LIST_WORDS + 1] = (uint32_t)(off >> 32);
                 if (r != OLD_IN_POOL) wr[1] |= ROW_ABSENT, stored--;
@@ -889,7 +1025,7 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
             uint32_t* seg = segs + seg_words;
             seg[0] = first;
             seg[1] = len;
-            if (set) seg[SEG_HEAD] = set->lost_row[first] * (uint32_t)SET_LOST_ROW;
+            if (long_form) seg[SEG_HEAD] = set ? set->lost_row[first] * (uint32_t)SET_LOST_ROW : 0;  // (no set: the one row of d_lost_none)
             for (int r = 0; r < T; r++) seg[seg_head + r] = list[(size_t)(first + ((uint32_t)r < len ? r : 0)) * list_words];
             seg_words += seg_head + T;
             launches.back().parity_blocks += set ? set->present_parity[first] : M;
@@ -909,12 +1045,13 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
             // The old rows of the absent written blocks, before ANY parity launch of the call: the passes read parity blocks that those launches
             // rewrite (and present data blocks, which only the scatter at the very end overwrites).
             RC_TRY(c->read_list.publish(set->rebuilt, st));
-            ProfScope ps(c, st, "update_set_recon", set->rebuilt_rows_read * S * 4);
-            RC_TRY(direct_run_read(set->view.passes, c->read_list.dev, set->rebuilt, data, parity, s->d_recon, S, 0, S, K * S, M * S, st));
+            ProfScope ps(c, st, window ? "update_window_recon" : "update_set_recon", set->rebuilt_rows_read * W * 4);
+            RC_TRY(direct_run_read(set->view.passes, c->read_list.dev, set->rebuilt, data, parity, s->d_recon, S, col0, W, K * S, M * S, st));
         }
-        SetArgs sa{};
+        WindowArgs wa{};
+        SetArgs& sa = wa.s;
         BatchArgs& a = sa.b;
-        a.parity = parity;
+        a.parity = parity + col0;
         a.data = data;
         a.old_blocks = old_blocks;
         a.new_blocks = new_blocks;
@@ -927,16 +1064,17 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
         a.e = (uint32_t)s->g.e;
         set_positions(s, a.p);
         sa.old_base = old_base;
-        if (set) sa.lost = set->view.lost_parity;
+        sa.lost = set ? set->view.lost_parity : s->d_lost_none.get();  // (read by update_set_kernel and update_window_kernel only)
+        wa.width = W;
         for (const BatchLaunch& l : launches) {
             // at least every resident wave of the device, where the parity count allows it: runs of parity blocks per segment
-            const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(set ? KERNEL_SET : KERNEL_BATCH, l.T, V);
+            const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(window ? KERNEL_WINDOW : set ? KERNEL_SET : KERNEL_BATCH, l.T, V);
             const uint64_t per_run = (uint64_t)l.segs * slices;
             const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>(M, (target + per_run - 1) / per_run));
             a.run = (uint32_t)((M + want - 1) / want);
             a.runs = (uint32_t)((M + a.run - 1) / a.run);
             const uint64_t seg_waves = slices * a.runs, launch_segs = LAUNCH_WAVES / seg_waves;
-            ProfScope ps(c, st, set ? "update_set" : "update_batch", l.parity_blocks * S * 8);
+            ProfScope ps(c, st, window ? "update_window" : set ? "update_set" : "update_batch", l.parity_blocks * W * 8);
             for (uint64_t s0 = 0; s0 < l.segs; s0 += launch_segs) {
                 const uint64_t waves = std::min<uint64_t>(launch_segs, l.segs - s0) * seg_waves;
                 a.segs = s->list.dev + n * list_words + l.seg0 + (size_t)s0 * (seg_head + l.T);
@@ -944,13 +1082,26 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
                 const dim3 grid((unsigned)((waves + 3) / 4));
                 with_class(l.T, V, [&](auto t_c, auto v_c) {
                     constexpr int Tc = t_c, Vc = v_c;
-                    if (set) hipLaunchKernelGGL((update_set_kernel<Tc, Vc>), grid, dim3(256), 0, st, sa);
+                    if constexpr (window) hipLaunchKernelGGL((update_window_kernel<Tc, Vc>), grid, dim3(256), 0, st, wa);
+                    else if (set) hipLaunchKernelGGL((update_set_kernel<Tc, Vc>), grid, dim3(256), 0, st, sa);
                     else hipLaunchKernelGGL((update_batch_kernel<Tc, Vc>), grid, dim3(256), 0, st, a);
                 });
                 HIP_TRY(hipGetLastError());
             }
         }
-        if (data && stored) {
+        if (window && data && stored) {
+            WindowScatterArgs ca{data + col0, new_blocks, nullptr, S, K, W, (uint32_t)slices, 0, (uint32_t)s->g.e};
+            const uint64_t launch_writes = LAUNCH_WAVES / slices;
+            ProfScope ps(c, st, "update_window_scatter", stored * W * 8);
+            for (uint64_t w0 = 0; w0 < n; w0 += launch_writes) {
+                const uint64_t waves = std::min<uint64_t>(launch_writes, n - w0) * slices;
+                ca.list = s->list.dev + w0 * list_words;
+                ca.waves = (uint32_t)waves;
+                const dim3 grid((unsigned)((waves + 3) / 4));
+                with_words<1>(V, [&](auto, auto v_c) { hipLaunchKernelGGL(update_window_scatter_kernel<decltype(v_c)::value>, grid, dim3(256), 0, st, ca); });
+                HIP_TRY(hipGetLastError());
+            }
+        } else if (data && stored) {
             ScatterArgs ca{data, new_blocks, nullptr, S, K, (uint32_t)slices, 0, (uint32_t)s->g.e, (uint32_t)list_words};
             const uint64_t launch_writes = LAUNCH_WAVES / slices;
             ProfScope ps(c, st, "update_scatter", stored * S * 8);
@@ -967,10 +1118,39 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
     });
 }
 
+// True where n_writes rows of row_bytes bytes at `rows` touch the pool (or wrap the address space).  The pool's extent has been checked (pool_extent).
+bool rows_overlap_pool(const fastecc_ctx* c, const void* data, const void* parity, uint64_t count, bool with_data, const void* rows, uint64_t n_writes,
+                       uint64_t row_bytes)
+{
+    PoolExtent x;
+    (void)pool_extent(c, with_data ? data : nullptr, parity, count, &x, false);
+    const uint64_t rows_bytes = n_writes * row_bytes;  // (fits 64 bits: update_batch_args, row_bytes <= x.block)
+    const uint64_t r0 = (uint64_t)(uintptr_t)rows;
+    const auto hits = [&](const void* base, uint64_t bytes) { return r0 < (uint64_t)(uintptr_t)base + bytes && (uint64_t)(uintptr_t)base < r0 + rows_bytes; };
+    return rows && n_writes > 0 && (r0 > UINT64_MAX - rows_bytes || (with_data && hits(data, count * x.data_bytes)) || hits(parity, count * x.parity_bytes));
+}
+
+// A window call's own refusals, after update_batch_args: the window {col0_words, width_words} against the block, and the caller's rows of width words
+// against the pool.  *win is the window to run.
+int window_args(const fastecc_ctx* c, const void* data, const void* parity, uint64_t count, uint64_t n_writes, const void* old_blocks, const void* new_blocks,
+                bool with_data, const uint64_t* col0_width, Window* win)
+{
+    const uint64_t col0 = col0_width[0], width = col0_width[1];
+    if (width == 0 || col0 > c->S || width > c->S - col0) return FASTECC_E_INVAL;  // (no sum: nothing to overflow)
+    if (rows_overlap_pool(c, data, parity, count, with_data, new_blocks, n_writes, width * 4) ||
+        rows_overlap_pool(c, data, parity, count, with_data, old_blocks, n_writes, width * 4))
+        return FASTECC_E_INVAL;
+    *win = Window{col0, width};
+    return FASTECC_OK;
+}
+
+// col0_width: null (the whole-block forms), or the window {col0_words, width_words} of a window call
 int update_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint64_t* writes, uint64_t n_writes, const void* old_blocks,
-                      const void* new_blocks, void* stream, bool with_data)
+                      const void* new_blocks, void* stream, bool with_data, const uint64_t* col0_width = nullptr)
 {
     int rc = update_batch_args(c, data, parity, count, writes, n_writes, old_blocks, new_blocks, with_data);
+    Window win;
+    if (rc == FASTECC_OK && col0_width) rc = window_args(c, data, parity, count, n_writes, old_blocks, new_blocks, with_data, col0_width, &win);
     if (rc != FASTECC_OK || n_writes == 0) return rc;
     std::vector<SortedWrite> sw;
     rc = sort_writes(c, count, writes, n_writes, sw);
@@ -978,28 +1158,27 @@ int update_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, 
     DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
     CallLock lk(c->mu);
-    return update_batch_run(c, with_data ? (uint32_t*)data : nullptr, (uint32_t*)parity, sw, (const uint32_t*)old_blocks, (const uint32_t*)new_blocks,
-                            (hipStream_t)stream);
+    const auto run = col0_width ? update_batch_run<true> : update_batch_run<false>;
+    return run(c, with_data ? (uint32_t*)data : nullptr, (uint32_t*)parity, sw, (const uint32_t*)old_blocks, (const uint32_t*)new_blocks, (hipStream_t)stream,
+               nullptr, win);
 }
 
 // fastecc_update_batch_set / _update_parity_batch_set: stripe b under pattern pattern_of[b] of the prepared set.  Everything is decided on the host before any
 // device work: the checks of update_batch_impl, the rows against the pool, the set, and per touched stripe its pattern — which of its written data blocks are
 // absent (their old rows are rebuilt: one DirectReadEntry each, as read_batch_impl's translate makes them) and which parity blocks update_set_kernel skips.
 int update_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, const uint64_t* writes, uint64_t n_writes,
-                          const void* old_blocks, const void* new_blocks, void* stream, bool with_data)
+                          const void* old_blocks, const void* new_blocks, void* stream, bool with_data, const uint64_t* col0_width = nullptr)
 {
     RC_TRY(update_batch_args(c, data, parity, count, writes, n_writes, old_blocks, new_blocks, with_data));
     if (!pattern_of) return FASTECC_E_INVAL;
     if (n_writes > 0xFFFFFFFFull / (SET_LIST_WORDS + SET_SEG_HEAD + 1)) return FASTECC_E_UNSUPPORTED;  // (the limit of update_batch_args for the longer records)
-    PoolExtent x;
-    RC_TRY(pool_extent(c, with_data ? data : nullptr, parity, count, &x, false));
-    const uint64_t rows_bytes = n_writes * x.block;  // (fits 64 bits: update_batch_args)
-    const auto overlaps_pool = [&](const void* rows) {
-        const uint64_t r0 = (uint64_t)(uintptr_t)rows;
-        const auto hits = [&](const void* base, uint64_t bytes) { return r0 < (uint64_t)(uintptr_t)base + bytes && (uint64_t)(uintptr_t)base < r0 + rows_bytes; };
-        return rows && n_writes > 0 && (r0 > UINT64_MAX - rows_bytes || (with_data && hits(data, count * x.data_bytes)) || hits(parity, count * x.parity_bytes));
-    };
-    if (overlaps_pool(new_blocks) || overlaps_pool(old_blocks)) return FASTECC_E_INVAL;
+    Window win;
+    if (col0_width) {
+        RC_TRY(window_args(c, data, parity, count, n_writes, old_blocks, new_blocks, with_data, col0_width, &win));
+    } else if (rows_overlap_pool(c, data, parity, count, with_data, new_blocks, n_writes, c->S * 4) ||
+               rows_overlap_pool(c, data, parity, count, with_data, old_blocks, n_writes, c->S * 4)) {
+        return FASTECC_E_INVAL;
+    }
     CallLock lk(c->mu);
     SetForm set;
     if (!pattern_set_view(c, &set.view)) return FASTECC_E_INVAL;  // fastecc_decode_prepare_set first
@@ -1040,8 +1219,9 @@ int update_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
         std::copy(rebuild.begin(), rebuild.end(), c->read_list.host.get());
         set.rebuilt = rebuild.size();
     }
-    return update_batch_run(c, with_data ? (uint32_t*)data : nullptr, (uint32_t*)parity, sw, (const uint32_t*)old_blocks, (const uint32_t*)new_blocks,
-                            (hipStream_t)stream, &set);
+    const auto run = col0_width ? update_batch_run<true> : update_batch_run<false>;
+    return run(c, with_data ? (uint32_t*)data : nullptr, (uint32_t*)parity, sw, (const uint32_t*)old_blocks, (const uint32_t*)new_blocks, (hipStream_t)stream,
+               &set, win);
 }
 
 }  // namespace
@@ -1098,6 +1278,35 @@ int fastecc_update_parity_batch_set(fastecc_ctx* c, void* parity, uint64_t count
                                     const void* old_blocks, const void* new_blocks, void* stream)
 {
     return guarded([&]() -> int { return update_batch_set_impl(c, nullptr, parity, count, pattern_of, writes, n_writes, old_blocks, new_blocks, stream, false); });
+}
+
+int fastecc_update_batch_window(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint64_t* writes, uint64_t n_writes, uint64_t col0_words,
+                                uint64_t width_words, const void* new_blocks, void* stream)
+{
+    const uint64_t win[2] = {col0_words, width_words};
+    return guarded([&]() -> int { return update_batch_impl(c, data, parity, count, writes, n_writes, nullptr, new_blocks, stream, true, win); });
+}
+
+int fastecc_update_parity_batch_window(fastecc_ctx* c, void* parity, uint64_t count, const uint64_t* writes, uint64_t n_writes, uint64_t col0_words,
+                                       uint64_t width_words, const void* old_blocks, const void* new_blocks, void* stream)
+{
+    const uint64_t win[2] = {col0_words, width_words};
+    return guarded([&]() -> int { return update_batch_impl(c, nullptr, parity, count, writes, n_writes, old_blocks, new_blocks, stream, false, win); });
+}
+
+int fastecc_update_batch_set_window(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, const uint64_t* writes,
+                                    uint64_t n_writes, uint64_t col0_words, uint64_t width_words, const void* new_blocks, void* stream)
+{
+    const uint64_t win[2] = {col0_words, width_words};
+    return guarded([&]() -> int { return update_batch_set_impl(c, data, parity, count, pattern_of, writes, n_writes, nullptr, new_blocks, stream, true, win); });
+}
+
+int fastecc_update_parity_batch_set_window(fastecc_ctx* c, void* parity, uint64_t count, const uint32_t* pattern_of, const uint64_t* writes, uint64_t n_writes,
+                                           uint64_t col0_words, uint64_t width_words, const void* old_blocks, const void* new_blocks, void* stream)
+{
+    const uint64_t win[2] = {col0_words, width_words};
+    return guarded(
+        [&]() -> int { return update_batch_set_impl(c, nullptr, parity, count, pattern_of, writes, n_writes, old_blocks, new_blocks, stream, false, win); });
 }
 
 int fastecc_code_coefficient(uint64_t n, uint64_t k, unsigned flags, uint64_t data_block, uint64_t parity_block, uint32_t* out)

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 420 /* 0.4.2: fastecc_update_batch_set, fastecc_update_parity_batch_set (degraded writes: small writes into a pool whose stripes miss blocks) */
+#define FASTECC_VERSION 430 /* 0.4.3: the four fastecc_update_*_window calls (sub-block writes: one window of word columns of every written pool block) */
 
 enum {
     FASTECC_OK = 0,
@@ -781,6 +781,39 @@ int fastecc_update_batch_set(fastecc_ctx *ctx, void *data, void *parity, uint64_
                              uint64_t n_writes, const void *new_blocks, void *stream);
 int fastecc_update_parity_batch_set(fastecc_ctx *ctx, void *parity, uint64_t count, const uint32_t *pattern_of, const uint64_t *writes,
                                     uint64_t n_writes, const void *old_blocks, const void *new_blocks, void *stream);
+/*
+ * Sub-block writes: the four pool calls above for one window of word columns [col0_words, col0_words + width_words) of every written block — a
+ * 512-byte sector of a 4 KB block is (col0_words, 128).  One window holds per call; callers group their writes by window.  Each call takes the
+ * arguments of its whole-block form with the window in front of the rows.
+ *   new_blocks, old_blocks : n_writes ROWS of width_words words, compact at pitch width_words (not blocks): row u belongs to writes[u] and holds
+ *       words [col0_words, col0_words + width_words) of that block.  old_blocks == NULL still means zero.
+ *   writes, pattern_of, the pool layout, streams and staging keep the meaning they have in the whole-block forms, word for word (the calls still
+ *       cannot be captured into a hipGraph).
+ * Result for a touched stripe: let X' be the stripe's true data (absent blocks as fastecc_decode would rebuild them) with words
+ * [col0_words, col0_words + width_words) of each written block replaced by its row.  Afterwards those columns of every written data block that is
+ * PRESENT hold the row (the parity forms store no data), and the same columns of every PRESENT parity block hold, bit for bit, what fastecc_encode gives
+ * for X' in those columns.
+ * Footprint: no word outside the window's columns is read or written, in any block of the pool; such words may be >= p.  Inside the window the
+ * inputs of touched stripes' present blocks must be < p.  Absent blocks and untouched stripes are neither read nor written.  The old window of an
+ * absent written block is rebuilt from the window columns of the survivors only (into a buffer of width_words words per such block).
+ * With col0_words = 0 and width_words = block_bytes / 4 every call is bit-identical to its whole-block form; on a pool whose words are all < p a
+ * window call is bit-identical to the whole-block call given "the old block with the window replaced".  The vector width of the kernels follows
+ * the window: 4 words per lane need col0_words, width_words and block_bytes / 4 divisible by 4 and 16-byte aligned pointers (2: by 2, 8 bytes).
+ * Refusals, before any device work and with nothing written: everything the corresponding whole-block call refuses, with the same code;
+ * FASTECC_E_INVAL for width_words == 0 or col0_words + width_words beyond the block's words (checked without overflow), and for new_blocks or
+ * old_blocks (as n_writes * width_words words) overlapping the pool — in all four forms.  n_writes == 0 with otherwise valid arguments is a no-op.
+ * Method: one kernel family, update_window_kernel, for the four calls; the parity read-modify-write touches width_words
+ * words of every present parity block of a touched stripe instead of the whole block.
+ */
+int fastecc_update_batch_window(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, const uint64_t *writes, uint64_t n_writes,
+                                uint64_t col0_words, uint64_t width_words, const void *new_blocks, void *stream);
+int fastecc_update_parity_batch_window(fastecc_ctx *ctx, void *parity, uint64_t count, const uint64_t *writes, uint64_t n_writes,
+                                       uint64_t col0_words, uint64_t width_words, const void *old_blocks, const void *new_blocks, void *stream);
+int fastecc_update_batch_set_window(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, const uint32_t *pattern_of, const uint64_t *writes,
+                                    uint64_t n_writes, uint64_t col0_words, uint64_t width_words, const void *new_blocks, void *stream);
+int fastecc_update_parity_batch_set_window(fastecc_ctx *ctx, void *parity, uint64_t count, const uint32_t *pattern_of, const uint64_t *writes,
+                                           uint64_t n_writes, uint64_t col0_words, uint64_t width_words, const void *old_blocks,
+                                           const void *new_blocks, void *stream);
 /* Host only, no device: the code's generator-matrix entry L_i(y_q) for data block i and parity block q of the (n,k) code that
  * fastecc_create_ex(n, k, ..., flags) builds over GF(0xFFF00001), plain form in [0,p): parity block q = sum_i L_i(y_q) data block i.
  * FASTECC_E_INVAL for a null out, an index out of range or unknown flags; FASTECC_E_UNSUPPORTED for a code fastecc_create_ex refuses. */
