@@ -151,6 +151,9 @@ def lib():
     L.fastecc_gf61_inv.argtypes, L.fastecc_gf61_inv.restype = [pair, pair], i32
     L.fastecc_gf61_root.argtypes, L.fastecc_gf61_root.restype = [u64, pair], i32
     L.fastecc_gf61_binary.argtypes, L.fastecc_gf61_binary.restype = [vp, i32, vp, vp, vp, u64, vp], i32
+    L.fastecc_gf61_update.argtypes, L.fastecc_gf61_update.restype = [vp, vp, vp, u64p, u64, vp, vp], i32
+    L.fastecc_gf61_update_parity.argtypes, L.fastecc_gf61_update_parity.restype = [vp, vp, u64p, u64, vp, vp, vp], i32
+    L.fastecc_gf61_code_coefficient.argtypes, L.fastecc_gf61_code_coefficient.restype = [u64, u64, u64, u64, pair], i32
     L.fastecc_profile_enable.argtypes, L.fastecc_profile_enable.restype = [vp, i32], i32
     L.fastecc_profile_reset.argtypes, L.fastecc_profile_reset.restype = [vp], i32
     L.fastecc_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double),
@@ -634,6 +637,21 @@ class Encoder:
                "fastecc_update_parity")
         return parity
 
+    def gf61_update(self, data, parity, blocks, new, stream=0):
+        """update() for a FIELD_GF_P61_SQUARED context (16-byte elements, device memory): data blocks `blocks` become the len(blocks)
+        contiguous blocks of `new` and the parity follows; data and parity then equal encode of the new stripe."""
+        count, arr = self._block_list(blocks)
+        _check(lib().fastecc_gf61_update(self._h, _addr(data), _addr(parity), arr, count, _addr(new), stream or None), "fastecc_gf61_update")
+        return data, parity
+
+    def gf61_update_parity(self, parity, blocks, new, old=None, stream=0):
+        """update_parity() for a FIELD_GF_P61_SQUARED context: parity += the effect of data blocks `blocks` changing from `old` to `new`
+        (contiguous blocks each; old=None: from zero)."""
+        count, arr = self._block_list(blocks)
+        _check(lib().fastecc_gf61_update_parity(self._h, _addr(parity), arr, count, _addr(old), _addr(new), stream or None),
+               "fastecc_gf61_update_parity")
+        return parity
+
     def _write_window(self, col0, width):
         """None for the whole block (col0=0, width=None: the whole-block entry point), else the checked (col0, width) of a window call"""
         if width is None and isinstance(col0, int) and not isinstance(col0, bool) and col0 == 0:
@@ -859,4 +877,11 @@ def gf61_inv(x):
 def gf61_root(order):
     out = _pair((0, 0))
     _check(lib().fastecc_gf61_root(order, out), "fastecc_gf61_root")
+    return (int(out[0]), int(out[1]))
+
+
+def gf61_code_coefficient(n, k, data_block, parity_block):
+    """Host-only: the weight (re, im) of data block `data_block` in parity block `parity_block` of the (n,k) code over GF((2^61-1)^2)."""
+    out = _pair((0, 0))
+    _check(lib().fastecc_gf61_code_coefficient(n, k, data_block, parity_block, out), "fastecc_gf61_code_coefficient")
     return (int(out[0]), int(out[1]))

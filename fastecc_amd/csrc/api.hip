@@ -116,6 +116,8 @@ void fastecc_destroy(fastecc_ctx* c)
     c->scrub = nullptr;
     destroy_update_state(c->update);
     c->update = nullptr;
+    destroy_gf61_update_state(c->update61);
+    c->update61 = nullptr;
     DeviceGuard dg(c->device);
     direct_encode_destroy(c->direct_enc);
     c->direct_enc = nullptr;

@@ -92,7 +92,8 @@ struct fastecc_ctx {
     p61::Decoder* decoder61 = nullptr;  // the same for FASTECC_FIELD_GF_P61_SQUARED (gf61_decode.hip)
     ScrubState* scrub = nullptr;        // fastecc_verify / _locate_errors / _correct: position map, fixed-erasure locator, fingerprint buffers (scrub.hip)
     UpdateState* update = nullptr;      // fastecc_update / _update_parity: weight table and delta rows (update.hip)
-    int locate_max = 256;               // option "locate_max": most unknown corrupted blocks fastecc_locate_errors looks for
+    Gf61UpdateState* update61 = nullptr;  // fastecc_gf61_update / _gf61_update_parity: limb weight table and delta rows (gf61_update.hip)
+    int locate_max = 256;              // option "locate_max": most unknown corrupted blocks fastecc_locate_errors looks for
     int scrub_batch_chunk = 0;          // option "scrub_batch_chunk": most stripes per chunk of fastecc_verify_batch (0 = the state's capacity)
     int p61_stride = 1;  // 64-bit field, codes other than (2N,N): parity block j of the code is block j * p61_stride of the (2N,N) parity (N = 2^n)
     Owned<p61::Path, p61::destroy> p61;  // FASTECC_FIELD_GF_P61_SQUARED: tables and plan of gf61_kernels.hip (everything uint32 below is unused)

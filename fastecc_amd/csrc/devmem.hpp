@@ -1,5 +1,5 @@
 // devmem.hpp — owners of what the library holds on the device: the context (context.hpp), the 64-bit field's path (gf61_kernels.hip), the shards of
-// a sharded context (sharded.hip) and the state structs of decode_state.hpp, direct.hip, update.hip, scrub.hip and gf61_decode.hip.  A struct's destructor
+// a sharded context (sharded.hip) and the state structs of decode_state.hpp, direct.hip, update.hip, gf61_update.hip, scrub.hip and gf61_decode.hip.  A struct's destructor
 // is its whole teardown, and this file is the only one that allocates or frees device or pinned memory, events or streams.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -79,6 +79,8 @@ struct ScrubState;                         // scrub.hip: error detection and loc
 void destroy_scrub_state(ScrubState*);     // scrub.hip, called by fastecc_destroy
 struct UpdateState;                        // update.hip: the parity update's weight table and delta rows (fastecc_update, _update_parity)
 void destroy_update_state(UpdateState*);   // update.hip, called by fastecc_destroy
+struct Gf61UpdateState;                    // gf61_update.hip: the same for the 64-bit field (fastecc_gf61_update, _gf61_update_parity)
+void destroy_gf61_update_state(Gf61UpdateState*);  // gf61_update.hip, called by fastecc_destroy
 
 // Every GF(0xFFF00001) code is f (degree < N, the transform order: a power of two, or q * 2^m for the mixed-radix codes) on a subset of
 // the NC-th roots of unity, NC = N << e, position u <-> w_NC^u: data block i at i << e, parity block q at code_parity_position — odd

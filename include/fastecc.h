@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 430 /* 0.4.3: the four fastecc_update_*_window calls (sub-block writes: one window of word columns of every written pool block) */
+#define FASTECC_VERSION 440 /* 0.4.4: fastecc_gf61_update, fastecc_gf61_update_parity, fastecc_gf61_code_coefficient (small writes over the 64-bit field) */
 
 enum {
     FASTECC_OK = 0,
@@ -818,6 +818,39 @@ int fastecc_update_parity_batch_set_window(fastecc_ctx *ctx, void *parity, uint6
  * fastecc_create_ex(n, k, ..., flags) builds over GF(0xFFF00001), plain form in [0,p): parity block q = sum_i L_i(y_q) data block i.
  * FASTECC_E_INVAL for a null out, an index out of range or unknown flags; FASTECC_E_UNSUPPORTED for a code fastecc_create_ex refuses. */
 int fastecc_code_coefficient(uint64_t n, uint64_t k, unsigned flags, uint64_t data_block, uint64_t parity_block, uint32_t *out);
+
+/*
+ * Small writes over FASTECC_FIELD_GF_P61_SQUARED: fastecc_update / fastecc_update_parity for the 64-bit field, on 16-byte elements in DEVICE
+ * memory (there is no mem_kind).  fastecc_update, fastecc_update_parity and every pool form (fastecc_update_batch*, the _set and _window forms)
+ * keep refusing this field with FASTECC_E_UNSUPPORTED; these two calls are the field's own, named like fastecc_gf61_binary.
+ *   fastecc_gf61_update        : data is the whole k-block stripe.  Reads the old content of data[blocks[u]], adds its change to parity and
+ *                                writes new_blocks[u] (count blocks, contiguous) into the stripe.
+ *   fastecc_gf61_update_parity : the data blocks live elsewhere: old_blocks and new_blocks are count contiguous blocks each; old_blocks == NULL
+ *                                means zero blocks (incremental encoding: zero the parity, then add blocks as they arrive).
+ * Afterwards data (fastecc_gf61_update) and parity are bit for bit what fastecc_encode gives for the new stripe: canonical words, re and im < p.
+ * blocks: a host array of `count` distinct indices < k in any order (it may be reused as soon as the call returns); count == 0 is a no-op and
+ * there is no upper limit: a call runs in passes of at most 16 changed blocks, each one read-modify-write pass over the parity.  Enqueued on
+ * `stream` without synchronising, the first call included: its weight table (72 bytes per entry, k (n/k - 1) entries for (2k,k), 4k and 8k,
+ * N = 2^ceil(log2 k) entries for the other codes; 38 MB at k = 2^19) is built by a kernel on `stream` and guarded by an event of its own.
+ * Inputs must be canonical (re, im < p); new_blocks / old_blocks must not overlap data or parity.
+ * Codes: every code fastecc_create accepts for this field — (2k,k) with k = 2^m, 1 <= m <= 24; n = 4k and 8k; and the other (n,k) codes (zero
+ * extension, fewer parity blocks), for which the update works directly on the caller's k data and n - k parity blocks: no padded copies.
+ * Refusals, decided before any device work (a refused call writes nothing).  FASTECC_E_INVAL: a null context, null pointers with count > 0,
+ * an index >= k, a duplicate index, pointers that are not 8-byte aligned.  FASTECC_E_UNSUPPORTED: a GF(0xFFF00001) context, a sharded
+ * context, blocks of 4 GiB - 1 KiB and more (the parity kernel addresses a block through one buffer descriptor, whose range and lane offsets
+ * are 32-bit byte counts).  FASTECC_E_NOMEM: the table or the 16 delta rows do not fit.
+ * Cost, measured at (2^20, 2^19) x 64 KB: 13.7 ms for one changed block and 52.3 ms for 16 against 62.0 ms for a fresh
+ * fastecc_encode; an update is cheaper up to 16 changed blocks (one pass) and dearer from 17 on (32: 104.8 ms).
+ */
+int fastecc_gf61_update(fastecc_ctx *ctx, void *data, void *parity, const uint64_t *blocks, uint64_t count, const void *new_blocks,
+                        void *stream);
+int fastecc_gf61_update_parity(fastecc_ctx *ctx, void *parity, const uint64_t *blocks, uint64_t count, const void *old_blocks,
+                               const void *new_blocks, void *stream);
+/* Host only, no device, no context: the generator-matrix entry L_i(y_q) for data block i and parity block q of the (n,k) code fastecc_create
+ * builds over FASTECC_FIELD_GF_P61_SQUARED, out = (re, im), canonical: parity block q = sum_i L_i(y_q) data block i.  FASTECC_E_INVAL for
+ * n <= k, data_block >= k, parity_block >= n - k or a null out; FASTECC_E_UNSUPPORTED for a shape fastecc_create refuses for this field
+ * (k > 2^24; n - k above the transform order 2^ceil(log2 k) and not 3k or 7k with k a power of two). */
+int fastecc_gf61_code_coefficient(uint64_t n, uint64_t k, uint64_t data_block, uint64_t parity_block, uint64_t out[2]);
 
 /*
  * Data packing (GF.md:72-104 "Efficient data packing", README.md:160-163): RS.cpp only encodes words < p, so
