@@ -50,6 +50,35 @@ Extended sequences (EXT_SEEDS) run these instead, and prepared_after_locate on r
   refused_bad_read                  a read index >= count*k; pattern_of[b] == n_patterns for a requested stripe: FASTECC_E_INVAL, the output
                                     all canary, the context unchanged                                        (480-483)
 
+Degraded sequences (DEG_SEEDS) run these instead (the lines are those of "Degraded writes" and "Sub-block writes" in include/fastecc.h):
+  prepared_after_degraded_write     decode_prepare's pattern survives fastecc_update_batch_set / _update_parity_batch_set, whole-block or window,
+                                    into a scratch stripe under a set of its own                                (765-766)
+  set_after_degraded_write          the pattern set survives ...                                                (765-766)
+  scrub_after_degraded_write        the scrub pattern survives ...                                              (765-766)
+  write_after_prepare_set           decode_prepare_set(A), a degraded write on the side stream, decode_prepare_set(B) with nothing synchronised
+                                    in between (it waits for the write itself: 766), a degraded write: the first result is A's, the second B's
+  read_after_degraded_write         a degraded write of absent blocks on one stream, fastecc_read_batch_set of them on the other, ordered by an
+                                    event only: the read returns the new rows                                   (759-760)
+  repair_after_degraded_write       a degraded window write, then fastecc_repair_batch_set under the same pattern: every block of the scratch
+                                    stripe is the oracle's encode of X'                                         (758-760, 792-795)
+  untouched_pattern_ignored         pattern_of[b] == n_patterns for a stripe that no write names: the call succeeds (752-753, 764)
+  refused_bad_degraded_write        one variant per draw: such an entry for a TOUCHED stripe, a null pattern_of (767-769); width 0, col0 + width =
+                                    S + 1, col0 = 2^64 - 1 with width 2 (the sum overflows), rows that overlap the pool (802-804):
+                                    FASTECC_E_INVAL, the pool, the caller's rows and the context unchanged.  The operation is a write the model
+                                    allows (the pool's own set in force, legal stripes, a window inside the block) with that one argument
+                                    spoiled, so nothing else can be the reason; the first two and the last through both kinds of entry point
+  refused_no_set                    a _set write before any fastecc_decode_prepare_set: FASTECC_E_INVAL (768); step 0 of the seed DEG_SEEDS[0]
+(An option cannot be read back from a context: that no option changes shows only in the calls that follow.)
+
+Writes: the forms "batch", "parity", "single" (fastecc_update_batch, _update_parity_batch, fastecc_update), "pool" (extended: whole stripes and
+fastecc_encode_pool) and, in degraded sequences, "batch_set" and "parity_set" (fastecc_update_batch_set, _update_parity_batch_set) and an optional
+window {"col0", "width", "shape"} on the four pool forms (the fastecc_update_*_window calls; rows compact at pitch width).  One rule, the header's:
+no touched stripe is quarantined; inside the window's columns every PRESENT block of a touched stripe equals the truth (so a window may lie beside
+a single wrong word, and the corruption mark stays: 796-797); absent blocks only under a _set form.  The truth takes the rows in the window and the
+oracle's whole re-encode; the mirror's present blocks take the truth in the window's columns; its other columns and every absent block stay as
+they are.  The parity forms store no data: the backend, as the caller, stores the window into the present data blocks itself, and hands
+"parity_set" the truth as the old row of an absent block.  Both placements use the set needed_set() with pattern_of[b] = b mod n.
+
 Reads ("read", extended sequences): fastecc_read_batch on fixed placement, fastecc_read_batch_set on rotated, over the whole pool: a present
 block gives the mirror's words (a corrupted block reads back corrupted, a quarantined stripe's garbage is copied), a block lost under its
 stripe's pattern gives the truth; lost blocks are requested only in stripes without a corrupted survivor (which survivors a pass reads is
@@ -58,7 +87,8 @@ left open by the header).  The backend presets n_reads + 1 output rows to CANARY
 Bursts: a "burst" operation enqueues 2 to 4 calls (writes of every form, at most one rebuild; in extended sequences reads too, their output
 read back only after the burst) back to back on the null and the side stream
 with nothing read in between, so a call meets the previous call's staged list and buffers still in flight; its prediction is the calls
-applied in order.
+applied in order.  In degraded sequences a burst's middle is read, write, write, read on alternating streams where absent data blocks can be
+written: both writes rebuild old rows (through the staged list the reads use), one a window call and one a whole-block call.
 
 Determinism: the generator reads the model only, never a backend's answer, so (config, seed) fixes the sequence.  Every operation is one JSON
 line (its arrays come from the "dseed" it names); run_sequence(backend, config, seed, steps=N) replays a prefix.
@@ -137,6 +167,9 @@ def _configs():
 CONFIGS = _configs()
 SEEDS = (1, 2, 3, 4)
 EXT_SEEDS = (5, 6)  # the extended sequences: reads, set location, whole-stripe writes (Generator(extended=True))
+DEG_SEEDS = (7, 8)  # the degraded sequences: degraded writes and column-window writes as well (Generator(degraded=True))
+SET_FORMS = ("batch_set", "parity_set")  # fastecc_update_batch_set, fastecc_update_parity_batch_set: stripes may miss blocks
+WINDOW_FORMS = ("batch", "parity") + SET_FORMS  # the four pool forms that take a column window ("single" and "pool" keep none)
 
 
 def config_named(name):
@@ -305,11 +338,27 @@ class PoolModel:
             pay["pokes"] = [(b, j, _garbage(rng, self.S, b % 2 == 0)) for b in self.live() for j in self.blocks_on(b, [op["dev"]])]
         elif kind == "write":
             writes = writes_of(op, self.k)
-            new = _below_p(rng, (len(writes), self.S))
+            col0, width = op.get("col0", 0), op.get("width", self.S)  # a window: rows of `width` words
+            new = _below_p(rng, (len(writes), width))
             new.reshape(-1)[:3] = [P - 1, 0, 1][: min(3, new.size)]
             pay["new"] = new
-            if op["form"] != "pool":
-                pay["old"] = np.stack([self.mirror_d[w // self.k, w % self.k] for w in writes])
+            if op["form"] != "pool":  # the old rows: the caller's own copy (the truth) where the block is absent, what the pool holds elsewhere
+                pay["old"] = np.stack([(self.truth_d if w % self.k in self.lost_for_write(w // self.k, op["form"]) else self.mirror_d)
+                                       [w // self.k, w % self.k, col0:col0 + width] for w in writes])
+        elif kind == "probe_write":
+            lost = self._set_pattern(op["q"])
+            pay["scratch_d"], pay["scratch_p"] = self._scratch_stripe(rng, op["b"], lost)
+            pay["src"] = op["b"]
+            pay["new"] = _below_p(rng, (len(op["writes"]), op["width"]))
+            pay["old"] = np.stack([window(self.truth_d[op["b"], i], op) for i in op["writes"]])
+        elif kind == "probe_write_swap":
+            pay["src"], pay["scratch"], pay["new"], pay["old"] = op["b"], [], [], []
+            for half in op["halves"]:
+                pay["scratch"].append(self._scratch_stripe(rng, op["b"], half["patterns"][half["q"]]))
+                pay["new"].append(_below_p(rng, (len(half["writes"]), half["width"])))
+                pay["old"].append(np.stack([window(self.truth_d[op["b"], i], half) for i in half["writes"]]))
+        elif kind == "refused" and op["which"] in ("bad_degraded_write", "no_set"):
+            pay["new"] = _below_p(rng, (len(op["writes"]), self.S))  # (rows of S words: what the whole-block entry point takes)
         elif kind == "probe_read":
             lost = self._prepared() if not op["set"] else self._set_pattern(op["q"])
             pay["scratch_d"], pay["scratch_p"] = self._scratch_stripe(rng, op["b"], lost)
@@ -380,6 +429,8 @@ class PoolModel:
         if len(set(writes)) != len(writes):
             raise ModelError("duplicate write")
         touched = sorted({w // self.k for w in writes})
+        if op["form"] in SET_FORMS or "width" in op:
+            return self._write_degraded(op, pay, writes, touched)
         if op["form"] == "pool":  # every data block is new and every parity block is encoded: what was corrupted is gone
             if not touched or any(b in self.quarantined or self.absent[b] for b in touched):
                 raise ModelError("a whole-stripe write into a stripe that is quarantined or has an absent block")
@@ -392,6 +443,102 @@ class PoolModel:
         for b in touched:
             self.truth_p[b] = self.codec.parity(self.truth_d[b])
             self.mirror_d[b], self.mirror_p[b] = self.truth_d[b], self.truth_p[b]
+
+    def lost_for_write(self, b, form):
+        """the blocks of stripe b that a write of this form takes as absent: those its pattern loses (_set forms), none (plain forms)"""
+        return self.blocks_on(b, self.devs) if form in SET_FORMS and b not in self.quarantined else ()
+
+    def wrong_columns(self, b):
+        """the word columns in which a PRESENT block of stripe b differs from the truth (blocks on a device that is down or replaced aside)"""
+        lost = self.blocks_on(b, self.devs)
+        bad = np.zeros(self.S, dtype=bool)
+        for j in range(self.n):
+            if j not in lost:
+                bad |= self.block(self.mirror_d, self.mirror_p, b, j) != self.block(self.truth_d, self.truth_p, b, j)
+        return np.nonzero(bad)[0]
+
+    def write_legal(self, b, form, col0, width):
+        """include/fastecc.h, "Inside the window the inputs of touched stripes' present blocks must be < p" and what makes the answer unique: the
+        stripe is not quarantined and inside the window's columns every PRESENT block equals the truth; absent blocks only under a _set form"""
+        if b in self.quarantined or (form not in SET_FORMS and self.absent[b]):
+            return False
+        if not self.corrupt[b]:
+            return True
+        lost = self.lost_for_write(b, form)
+        return all(np.array_equal(self.block(self.mirror_d, self.mirror_p, b, j)[col0:col0 + width], self.block(self.truth_d, self.truth_p, b, j)[col0:col0 + width])
+                   for j in range(self.n) if j not in lost)
+
+    def _write_degraded(self, op, pay, writes, touched):
+        """the _set forms and the window forms (include/fastecc.h: "Degraded writes", "Sub-block writes"): the truth takes the rows in the window and
+        the oracle's whole re-encode; every PRESENT block of a touched stripe takes the truth in the window's columns; nothing else changes"""
+        form, S = op["form"], self.S
+        col0, width = op.get("col0", 0), op.get("width", S)
+        if form not in WINDOW_FORMS:
+            raise ModelError("the forms single and pool keep no window")
+        if not writes or width < 1 or col0 < 0 or col0 + width > S:
+            raise ModelError("no such write")
+        if form in SET_FORMS:
+            if self.ctx.prepared_set != self.needed_set():
+                raise ModelError("the prepared pattern set is stale")
+            if op["pattern_of"] != self.pattern_of(0, self.count, lambda b: b not in self.quarantined):
+                raise ModelError("pattern_of does not skip what it must")
+            if op.get("ignored") is not None and op["ignored"] in touched:
+                raise ModelError("the entry to ignore belongs to a touched stripe")
+        for b in touched:
+            if not self.write_legal(b, form, col0, width):
+                raise ModelError("a %s write into stripe %d: quarantined, an absent block under a plain form, or a wrong word in the window" % (form, b))
+        for u, w in enumerate(writes):
+            self.truth_d[w // self.k, w % self.k, col0:col0 + width] = pay["new"][u]
+        for b in touched:
+            self.truth_p[b] = self.codec.parity(self.truth_d[b])
+            lost = self.lost_for_write(b, form)
+            for j in range(self.n):
+                src, dst = self.block(self.truth_d, self.truth_p, b, j), self.block(self.mirror_d, self.mirror_p, b, j)
+                if j not in lost:
+                    dst[col0:col0 + width] = src[col0:col0 + width]
+                elif not np.array_equal(src, dst):  # (a block rebuilt on a replaced device goes stale again: its pattern still calls it lost)
+                    self.absent[b].add(j)
+
+    def _probe_write(self, op, pay):
+        """a degraded write into a scratch stripe (stripe b's truth, garbage where pattern q of the set lost a block); "after": a repair under the
+        same pattern (every block is then the oracle's encode of X'), or a read of the written blocks on the other stream (the new rows)"""
+        lost = self._set_pattern(op["q"])
+        if op["form"] not in SET_FORMS or len(set(op["writes"])) != len(op["writes"]):
+            raise ModelError("no such scratch write")
+        return self._scratch_write(op, pay["scratch_d"], pay["scratch_p"], pay["new"], lost, op.get("after"))
+
+    def _scratch_write(self, half, d, p, new, lost, after=None):
+        """X' = stripe half["b"]'s true data with the rows in the window, its parity the oracle's: the present blocks take it in the window"""
+        d, p, x = d.copy(), p.copy(), self.truth_d[half["b"]].copy()
+        win = slice(half["col0"], half["col0"] + half["width"])
+        for u, i in enumerate(half["writes"]):
+            x[i, win] = new[u]
+        xp = self.codec.parity(x)
+        for j in range(self.n):
+            src, dst = (x[j], d[j]) if j < self.k else (xp[j - self.k], p[j - self.k])
+            if j not in lost:
+                dst[win] = src[win]
+            elif after == "repair":
+                dst[:] = src
+        out = {"code": OK, "scratch_d": d, "scratch_p": p}
+        if after == "repair":
+            out["codes"] = [OK, OK]
+        if after == "read":
+            out["codes"] = [OK, OK]
+            out["rows"] = np.stack([x[i, win] for i in half["reads"]])
+            out["guard"] = np.full(half["width"], CANARY, dtype=np.uint32)
+        return out
+
+    def _probe_write_swap(self, op, pay):
+        """decode_prepare_set(first patterns), a degraded write on the side stream, decode_prepare_set(second patterns) with nothing synchronised, a
+        degraded write: the first write's result is the first set's, the second follows the second set"""
+        ds, ps = [], []
+        for half, (d, p), new in zip(op["halves"], pay["scratch"], pay["new"]):
+            self.ctx.prepared_set = tuple(tuple(q) for q in half["patterns"])
+            out = self._scratch_write(dict(half, b=op["b"]), d, p, new, self.ctx.prepared_set[half["q"]])
+            ds.append(out["scratch_d"])
+            ps.append(out["scratch_p"])
+        return {"code": OK, "codes": [OK] * 4, "scratch_d": np.stack(ds), "scratch_p": np.stack(ps)}
 
     def _prepare(self, op, pay):
         self.ctx.prepared = tuple(op["lost"])
@@ -611,6 +758,23 @@ class PoolModel:
     def _refused(self, op, pay):
         if op["which"] == "bad_read":  # two refused reads, (n_reads + 1) rows each: all canary
             return {"code": E_INVAL, "codes": [E_INVAL, E_INVAL], "rows": canary_rows(2 * (len(op["reads"]) + 1), op["width"]).reshape(-1)}
+        if op["which"] in ("bad_degraded_write", "no_set"):  # refused with nothing written: the pool (compared after every step) and the caller's rows
+            if (op["which"] == "no_set") != (self.ctx.prepared_set is None):
+                raise ModelError("refused_no_set needs a context without a set, every other refusal one with a set")
+            # but for the argument that the variant spoils the call is a write the model allows: nothing else can be the reason to refuse it
+            if op["which"] == "bad_degraded_write" and (self.ctx.prepared_set != self.needed_set() or op["entry"] != len(self.ctx.prepared_set)):
+                raise ModelError("the pool's own set is not the one in force, or the entry is not its number of patterns")
+            if op["pattern_of"] != self.pattern_of(0, self.count, lambda b: b not in self.quarantined) or len(set(op["writes"])) != len(op["writes"]):
+                raise ModelError("pattern_of or the write list would be refused by itself")
+            if op["width"] < 1 or op["col0"] + op["width"] > self.S or not op["writes"] or not all(
+                    0 <= w < self.count * self.k and self.write_legal(w // self.k, op["form"], op["col0"], op["width"]) for w in op["writes"]):
+                raise ModelError("the write would not be legal without the variant's own argument")
+            call = (op["call_col0"], op["call_width"])
+            want = {"width0": (op["col0"], 0), "past_end": (self.S + 1 - op["width"], op["width"]), "overflow": ((1 << 64) - 1, 2)}
+            if call != want.get(op.get("variant"), (op["col0"], op["width"])):
+                raise ModelError("the window of the call is not what the variant says")
+            codes = [E_INVAL] * len(op["entries"])
+            return {"code": E_INVAL, "codes": codes, "rows": pay["new"].reshape(-1)}
         return {"code": E_INVAL}
 
 
@@ -636,21 +800,37 @@ EXT_PROBES = [("read", "prepare"), ("prepared", "read"), ("set", "read"), ("scru
               ("read", "prepare_set"), ("refused", "bad_read"), ("read", "prepare_parity"), ("prepared", "locate")]
 WINDOWS = ("whole", "word", "narrow", "tail")
 
+# Degraded sequences (the seeds DEG_SEEDS): the extended kinds, with writes of the forms "batch_set" and "parity_set" (fastecc_update_batch_set,
+# _update_parity_batch_set) that go on while devices are down, and a column window on the four pool forms (the fastecc_update_*_window calls).  A
+# window has one of the shapes of WINDOWS or, for the vector-width rule, "quad" (col0 and width multiples of 4: every configuration's S is one,
+# so 4 words per lane) or "pair" (both even, not both multiples of 4).  Their probes are DEG_PROBES, met in turn like EXT_PROBES; step 0 of the
+# seed DEG_SEEDS[0] is refused_no_set (no later step can meet a context without a set).
+WRITE_WINDOWS = WINDOWS + ("quad", "pair")
+DEG_WEIGHTS = {"write": 40, "burst": 24, "corrupt": 12, "device_down": 10, "device_replaced": 8, "verify": 2, "locate": 2, "correct": 4, "repair": 8,
+               "decode": 3, "reencode": 3, "option": 3, "stream": 4, "read": 10}
+DEG_PROBES = [("prepared", "degraded_write"), ("write", "prepare_set"), ("set", "degraded_write"), ("write", "read"), ("scrub", "degraded_write"),
+              ("write", "repair"), ("refused", "bad_degraded_write"), ("write", "ignored")]
+BAD_DEGRADED_WRITES = ("entry", "null_pattern_of", "width0", "past_end", "overflow", "overlap")
+
 
 class Generator:
-    def __init__(self, model, seed, extended=False):
+    def __init__(self, model, seed, extended=False, degraded=False):
         self.m, self.rng = model, _rng("gen", model.cfg.name, seed)
+        self.degraded, extended = degraded, extended or degraded
+        self.bad_writes, self.absent_written = 0, []
         self.queue = collections.deque()
         self.drawn = self.skipped = 0
         self.dseed = 0
         self.verifies = 0
         m = model
         self.extended, self.seed, self.pool_encodes, self.used_form = extended, seed, 0, collections.Counter()
-        self.weights, self.probe_list = (EXT_WEIGHTS, EXT_PROBES) if extended else (WEIGHTS, PROBES)
+        self.weights, self.probe_list = (DEG_WEIGHTS, DEG_PROBES) if degraded else (EXT_WEIGHTS, EXT_PROBES) if extended else (WEIGHTS, PROBES)
         kinds = [k for k in (EXT_KINDS if extended else KINDS)
                  if not (m.mixed and k == "corrupt") and not (m.rotated and k == "locate" and not extended)]
         self.emitted = self.probes_started = 0
         self.probe_at = 5 * (seed - EXT_SEEDS[0] + (2 if m.rotated else 0)) if extended else 2 * (seed + (4 if model.rotated else 0))
+        if degraded:
+            self.probe_at = 5 * (seed - DEG_SEEDS[0] + (2 if m.rotated else 0))
         self.kinds = kinds
         self.used = collections.Counter()
 
@@ -688,7 +868,20 @@ class Generator:
             if any(not m.absent[b] for b in m.live()):  # a whole-stripe write takes corrupted stripes too
                 idle["write"] = False
             idle["reencode"] = not any(not any(j < m.k for j in list(m.corrupt[b]) + list(m.absent[b])) for b in m.live())
+        if self.degraded:  # the _set forms go on writing while devices are down
+            idle["write"] = idle["burst"] = False
+            # (first the plain forms, which need stripes without absent blocks)
+            idle["device_down"] = idle["device_down"] or (self.emitted <= 26 and self._plain_forms_due())
         w = np.array([self.weights[k] * (0.25 if idle.get(k) else 3.0 if not self.used[k] else 1.0) for k in self.kinds])
+        if self.degraded and m.devs and not self.used_form["burst_pair"]:  # a device is down: the burst with a pair of rebuilding calls, soon
+            w[self.kinds.index("burst")] *= 3
+        if self.degraded and self._forms_due():
+            w[self.kinds.index("write")] *= 2.5
+        if self.degraded and not m.devs:  # bursts are for the time a device is down; the plain forms, and one directly after a prepare_set, for now
+            w[self.kinds.index("burst")] *= 0.4
+            w[self.kinds.index("write")] *= 1.6
+            if not self._plain_forms_due():
+                w[self.kinds.index("device_down")] *= 3
         return self.kinds[int(self.rng.choice(len(self.kinds), p=w / w.sum()))]
 
     def _range(self, ok=None):
@@ -760,6 +953,8 @@ class Generator:
     # operations: each returns a list of operations (prerequisites first) or None when the state does not allow it
     def make_write(self, in_burst=False):
         m, rng = self.m, self.rng
+        if self.degraded:
+            return self._make_degraded_write(in_burst)
         # extended: whole stripes — new data and fastecc_encode_pool over the run — two times in five, and outside bursts a sequence's first two
         # writes and every write while no stripe is whole.  Corrupted stripes qualify (the write makes them whole), but not inside a burst, whose
         # other calls were drawn against the marks as they are
@@ -791,9 +986,269 @@ class Generator:
             writes = [writes[i] for i in rng.permutation(len(writes))]
         return [{"op": "write", "form": form, "writes": writes, "dseed": self._ds()}]
 
+    # -- degraded sequences: writes of the _set forms and column windows
+    def _write_window(self, shape=None):
+        """(shape, col0, width) of a write: _window()'s four shapes, "quad" (col0 and width multiples of 4) and "pair" (both even, col0 = 2 mod 4)"""
+        S, rng = self.m.S, self.rng
+        shape = shape or self._pick(WRITE_WINDOWS)
+        if shape == "quad":
+            col0 = 4 * int(rng.integers(S // 4))
+            return shape, col0, 4 * int(rng.integers(1, (S - col0) // 4 + 1))
+        if shape == "pair":
+            col0 = 2 + 4 * int(rng.integers((S - 4) // 4 + 1))
+            return shape, col0, 2 * int(rng.integers(1, (S - col0) // 2 + 1))
+        return self._window(shape)
+
+    def _forms_due(self):
+        """a (form, window or not) of the four pool forms has not run twice in this sequence yet"""
+        return any(self.used_form[f, w] < 2 for f in WINDOW_FORMS for w in (True, False))
+
+    def _plain_forms_due(self):
+        return any(self.used_form[f, w] < 2 for f in ("batch", "parity") for w in (True, False))
+
+    def _needed_set_op(self):
+        return {"op": "prepare_set", "patterns": [list(q) for q in self.m.needed_set()]}
+
+    def _set_prereq(self):
+        """what makes the pool's own patterns the set in force ([] when they are); a fixed pool uses the same set, every pattern needed_single()"""
+        return [self._needed_set_op()] if self.m.ctx.prepared_set != self.m.needed_set() else []
+
+    def _beside_corruption(self):
+        """(stripe, shape, col0, width): a stripe whose present blocks are wrong in a few word columns only, and a window that misses them all"""
+        m = self.m
+        for b in [b for b in m.live() if m.corrupt[b]]:
+            cols = m.wrong_columns(b)
+            if 1 <= len(cols) <= 24:
+                for _ in range(8):
+                    shape, col0, width = self._write_window(self._pick(WRITE_WINDOWS[1:]))
+                    if not ((cols >= col0) & (cols < col0 + width)).any():
+                        return b, shape, col0, width
+        return None
+
+    def _degraded_write(self, want_rebuilt=False, whole_block=None, form=None, in_burst=False):
+        """(prerequisites, a write of one of the four pool forms) or None.  One list holds absent data blocks, present data blocks of degraded stripes
+        and stripes that lose parity only or nothing, whichever the pool has; where k > 16 a stripe with more than 16 writes two times in five.
+        want_rebuilt: form "batch_set" with at least two absent data blocks written (their old rows are rebuilt).  whole_block: True the whole-block
+        entry point, False a window narrower than the block, None either.  in_burst: a plain form keeps to stripes with no block on a device that is
+        down or replaced (a _set write earlier in the burst leaves such a block, rebuilt since, stale again: the stripe then has an absent block)."""
+        m, rng = self.m, self.rng
+        if want_rebuilt:
+            form = "batch_set"
+        if form is None or whole_block is None:  # the (form, window or not) that this sequence has used least, among those the pool allows now: the
+            # plain forms need stripes without absent blocks, so while no device is down or replaced they come first, until each has run twice
+            forms = [form] if form else list(SET_FORMS) if m.devs or (not self._plain_forms_due() and rng.random() < 0.75) else ["batch", "parity"]
+            combos = [(f, w) for f in forms for w in ([True, False] if whole_block is None else [whole_block])]
+            least = min(self.used_form[c] for c in combos)
+            form, whole_block = self._pick([c for c in combos if self.used_form[c] == least])
+        target = None
+        shape, col0, width = None, 0, m.S  # (shape None: the whole-block entry point)
+        if not whole_block:
+            shape, col0, width = self._write_window(self._pick(WRITE_WINDOWS[1:]) if want_rebuilt else None)
+            if not m.mixed and (rng.random() < 0.6 or not self.used_form["beside"]):
+                beside = self._beside_corruption()
+                if beside:
+                    target, shape, col0, width = beside
+                    self.used_form["beside"] += 1
+        legal = [b for b in m.live() if m.write_legal(b, form, col0, width) and not (in_burst and form not in SET_FORMS and m.blocks_on(b, m.devs))]
+        if not legal:
+            return None
+        absent_d = [b * m.k + i for b in legal for i in m.lost_for_write(b, form) if i < m.k]
+        if want_rebuilt and len(absent_d) < 2:
+            return None
+        writes = []
+        if m.k > 16 and rng.random() < 0.4:  # more than 16 writes in one stripe, its absent data blocks among them: a second round
+            with_absent = [b for b in legal if any(i < m.k for i in m.lost_for_write(b, form))]
+            b = self._pick(with_absent if with_absent and rng.random() < 0.7 else legal)
+            first = [i for i in m.lost_for_write(b, form) if i < m.k]
+            rest = [int(i) for i in rng.permutation(m.k) if int(i) not in first]
+            writes = [b * m.k + i for i in (first + rest)[: int(rng.integers(17, min(m.k, 36) + 1))]]
+        if target is not None and target in legal and not any(w // m.k == target for w in writes):
+            writes.append(target * m.k + int(rng.integers(m.k)))
+        if absent_d and (want_rebuilt or rng.random() < 0.7):
+            more = [int(x) for x in rng.choice(absent_d, size=min(len(absent_d), int(rng.integers(2, 5))), replace=False)]
+            writes += [w for w in more if w not in writes]
+        parity_only = [b for b in legal if m.lost_for_write(b, form) and min(m.lost_for_write(b, form)) >= m.k]
+        if parity_only and rng.random() < 0.8:  # a stripe that loses parity only
+            w = self._pick(parity_only) * m.k + int(rng.integers(m.k))
+            writes += [w] if w not in writes else []
+        taken = set(writes)
+        free = [b * m.k + i for b in legal for i in range(m.k) if b * m.k + i not in taken]
+        more = min(max(0 if writes else 1, int(rng.integers(1, 41)) - len(writes)), len(free))
+        writes += [int(x) for x in rng.choice(free, size=more, replace=False)]
+        writes = [writes[i] for i in rng.permutation(len(writes))]
+        self.used_form[form, whole_block] += 1
+        op = {"op": "write", "form": form, "writes": writes, "dseed": self._ds()}
+        if shape is not None:
+            op.update(col0=col0, width=width, shape=shape)
+        if form in SET_FORMS:
+            op["pattern_of"] = m.pattern_of(0, m.count, lambda b: b not in m.quarantined)
+            self.absent_written += [w for w in writes if w in absent_d]
+        return (self._set_prereq() if form in SET_FORMS else []), op
+
+    def _make_degraded_write(self, in_burst=False):
+        m, rng = self.m, self.rng
+        if not in_burst and rng.random() < 0.12:  # whole stripes, as in the extended sequences
+            r = self._range(lambda b: b not in m.quarantined and not m.absent[b])
+            if r is not None:
+                self.used_form["write_pool"] += 1
+                return [{"op": "write", "form": "pool", "b0": r[0], "b1": r[1], "dseed": self._ds()}]
+        if not in_burst and rng.random() < 0.08 and any(m.whole(b) for b in m.live()):  # fastecc_update on one whole stripe
+            b = self._pick([b for b in m.live() if m.whole(b)])
+            blocks = rng.choice(m.k, size=int(rng.integers(1, min(m.k, 20) + 1)), replace=False)
+            return [{"op": "write", "form": "single", "writes": [b * m.k + int(i) for i in blocks], "dseed": self._ds()}]
+        r = self._degraded_write(in_burst=in_burst)
+        if r is None:
+            return None
+        pre, op = r
+        # a plain window write directly after a decode_prepare_set of other patterns: the "loses nothing" row survives the swap of tables
+        if not in_burst and op["form"] in ("batch", "parity") and "width" in op and (rng.random() < 0.5 or not self.used_form["window_after_set"]):
+            self.used_form["window_after_set"] += 1
+            return [{"op": "prepare_set", "patterns": self._write_patterns()}, op]
+        if not in_burst and rng.random() < 0.6:  # a second write as the next step (drawn like a burst's: the first may leave a rebuilt block stale)
+            second = self._degraded_write(in_burst=True)
+            if second:
+                return pre + [op] + [x for x in second[0] if x not in pre] + [second[1]]
+        return pre + [op]
+
+    def _write_patterns(self):
+        """three patterns for a scratch write, each losing at least one data block"""
+        m, out = self.m, []
+        for _ in range(3):
+            q = self._random_pattern(4)
+            if q[0] >= m.k:
+                q = sorted([int(self.rng.integers(m.k))] + q[1:])
+            out.append(q)
+        return out
+
+    def _probe_write(self, patterns, q, probe=None, after=None):
+        """a degraded write into a scratch stripe under pattern q: absent data blocks and present ones in one list, usually a window"""
+        m, rng = self.m, self.rng
+        lost_d = [j for j in patterns[q] if j < m.k]
+        n = int(rng.integers(17, min(m.k, 30) + 1)) if m.k > 16 and rng.random() < 0.3 else int(rng.integers(1, min(m.k - len(lost_d), 5) + 1))
+        writes = lost_d + [int(i) for i in rng.permutation(m.k) if int(i) not in lost_d][:n]
+        writes = [writes[i] for i in rng.permutation(len(writes))]
+        if after is None and (self.used_form["probe_write"] + self.seed) % 2 == 0:  # every other one through the whole-block entry point
+            shape, col0, width = "whole_block", 0, m.S
+        else:
+            shape, col0, width = self._write_window(self._pick(WRITE_WINDOWS[1:]) if after == "repair" else None)
+        self.used_form["probe_write"] += after is None
+        op = {"op": "probe_write", "b": self._pick(m.live()), "q": q, "form": self._pick(["batch_set", "batch_set", "parity_set"]), "writes": writes,
+              "col0": col0, "width": width, "shape": shape, "dseed": self._ds(), "probe": probe}
+        if after:
+            op["after"] = after
+        if after == "read":  # the written blocks, the absent ones first, a duplicate
+            op["reads"] = lost_d + writes[:2] + lost_d[:1]
+        return op
+
+    def _scratch_set_write(self, probe=None, after=None):
+        sp = {"op": "prepare_set", "patterns": self._write_patterns()}
+        return [sp, self._probe_write(sp["patterns"], int(self.rng.integers(3)), probe, after)]
+
+    def make_probe_write(self, x):
+        """write_after_prepare_set, read_after_degraded_write, repair_after_degraded_write, untouched_pattern_ignored"""
+        m, rng = self.m, self.rng
+        if x == "prepare_set":
+            halves = []
+            for _ in range(2):
+                patterns = self._write_patterns()
+                w = self._probe_write(patterns, int(rng.integers(3)))
+                halves.append({"patterns": patterns, "q": w["q"], "form": w["form"], "writes": w["writes"], "col0": w["col0"], "width": w["width"],
+                               "shape": w["shape"]})
+            return [{"op": "probe_write_swap", "halves": halves, "b": self._pick(m.live()), "dseed": self._ds(), "probe": "write_after_prepare_set"}]
+        if x == "read":
+            return self._scratch_set_write("read_after_degraded_write", "read")
+        if x == "repair":
+            return self._scratch_set_write("repair_after_degraded_write", "repair")
+        r = self._degraded_write(form=self._pick(SET_FORMS))  # "ignored": the entry of a stripe that no write names is the number of patterns
+        if r is None:
+            return None
+        pre, op = r
+        others = [b for b in range(m.count) if b not in {w // m.k for w in op["writes"]}]
+        if not others:
+            return None
+        op.update(ignored=self._pick(others), entry=m.npat, probe="untouched_pattern_ignored")
+        return pre + [op]
+
+    def _refused_degraded_write(self, which):
+        """A degraded write that must be refused: `which` "no_set" (no set was ever prepared) or "bad_degraded_write", one variant per draw.  The
+        operation is a write that the model would allow — the pool's own set in force, legal stripes, a window inside the block — so that the one
+        argument the backend then spoils is the only reason to refuse it; "call_col0" / "call_width" are the window as the call gets it.  The
+        variants that are no matter of the window go through the whole-block entry point and the window entry point, one call each."""
+        m, rng = self.m, self.rng
+        used, absent_written = self.used_form.copy(), list(self.absent_written)
+        r = self._degraded_write(form=self._pick(SET_FORMS), whole_block=False)
+        self.used_form, self.absent_written = used, absent_written  # (nothing is written)
+        if r is None:
+            return None
+        pre, w = r
+        op = {"op": "refused", "which": which, "form": w["form"], "writes": w["writes"][:5], "pattern_of": w["pattern_of"], "col0": w["col0"],
+              "width": w["width"], "shape": w["shape"], "call_col0": w["col0"], "call_width": w["width"], "entries": ["window"],
+              "dseed": w["dseed"], "probe": "refused_" + which}
+        if which == "no_set":
+            return [op]
+        variant = BAD_DEGRADED_WRITES[(self.bad_writes + self.seed + CONFIGS.index(m.cfg) // 2 + (3 if m.rotated else 0)) % len(BAD_DEGRADED_WRITES)]
+        self.bad_writes += 1
+        op.update(variant=variant, entry=m.npat)
+        if variant in ("entry", "null_pattern_of", "overlap"):
+            op["entries"] = ["whole_block", "window"]
+        elif variant == "width0":
+            op["call_width"] = 0
+        elif variant == "past_end":
+            op["call_col0"] = m.S + 1 - op["width"]
+        elif variant == "overflow":
+            op.update(call_col0=(1 << 64) - 1, call_width=2)
+        return pre + [op]
+
+    def _make_degraded_burst(self):
+        """Enqueued calls back to back.  Where absent data blocks can be written, its middle is read, write, write, read on alternating streams:
+        both writes rebuild old rows, one a window call and one a whole-block call (in either order: different widths of the one reconstruction
+        buffer), and each read asks for absent blocks that the write beside it replaces."""
+        m, rng = self.m, self.rng
+        pre, mid = [], []
+
+        def add(to, made):
+            if made:
+                for x in made[:-1]:
+                    if x not in pre:
+                        pre.append(x)
+                to.append(made[-1])
+
+        def absent_of(w):
+            return [x for x in w["writes"] if (x % m.k) in m.lost_for_write(x // m.k, "batch_set") and not m.corrupt[x // m.k]]
+        if m.devs and (rng.random() < 0.8 or not self.used_form["burst_pair"]):
+            window_first = (self.used_form["burst_pair"] + self.seed) % 2 == 0
+            first = self._degraded_write(want_rebuilt=True, whole_block=not window_first, in_burst=True)
+            second = self._degraded_write(want_rebuilt=True, whole_block=window_first, in_burst=True) if first else None
+            if first:
+                self.used_form["burst_pair"] += 1
+                add(mid, self.make_read(prefer=absent_of(first[1])))
+                add(mid, list(first[0]) + [first[1]])
+                if second and second[1].get("width", m.S) != first[1].get("width", m.S):
+                    add(mid, list(second[0]) + [second[1]])
+                add(mid, self.make_read(prefer=absent_of(mid[-1])))
+        before, after = [], []
+        for _ in range(int(rng.integers(1, 3) if mid else rng.integers(2, 4))):
+            add(before if rng.random() < 0.5 else after, self.make_write(in_burst=True))
+        if not mid and rng.random() < 0.5:
+            add(after if rng.random() < 0.5 else before, self.make_read())
+        ops = before + mid + after
+        if self._rebuild_prereq() is None and rng.random() < 0.3:  # a rebuild, last: the calls before it were drawn against the patterns as they are
+            r = self._make_rebuild(self._pick(["repair", "decode"]))
+            if r:
+                ops.append(r[-1])
+        if len(ops) < 2:
+            return None
+        for sub in ops:
+            sub["stream"] = int(rng.integers(2))
+        for i, sub in enumerate(mid):
+            sub["stream"] = (mid[0]["stream"] + i) % 2
+        return pre + [{"op": "burst", "ops": ops}]
+
     def make_corrupt(self):
         m, rng = self.m, self.rng
         how = self._pick(["word", "word", "block", "big"])
+        if self.degraded and how == "block" and rng.random() < 0.6:  # a single wrong word leaves room for a window beside it
+            how = "word"
         for _ in range(16):
             b = self._pick(m.live())
             free = [j for j in range(m.n) if m.dev_of(b, j) not in m.devs and j not in m.corrupt[b]]
@@ -814,7 +1269,12 @@ class Generator:
         m = self.m
         if len(m.devs) >= min(m.m, 2) or not all(m.budget(b, extra_w=1) for b in m.live()):
             return None
-        return [{"op": "device_down", "dev": self._pick([d for d in range(m.n) if d not in m.devs]), "dseed": self._ds()}]
+        up = [d for d in range(m.n) if d not in m.devs]
+        if self.degraded:  # a device whose loss costs some stripes a data block and others parity only; on a fixed pool first a data block's device
+            live = m.live()
+            both = [d for d in up if len({j < m.k for b in live for j in m.blocks_on(b, [d])}) == 2]
+            up = both if both and self.rng.random() < 0.8 else [d for d in up if (d < m.k) != bool(m.devs)] if not m.rotated else up
+        return [{"op": "device_down", "dev": self._pick(up), "dseed": self._ds()}]
 
     def make_device_replaced(self):
         down = [d for d, s in self.m.devs.items() if s == "down"]
@@ -947,6 +1407,8 @@ class Generator:
     def make_read(self, prefer=()):
         """1 to about 3k requests over the whole pool: present and lost blocks, duplicates, quarantined stripes, corrupted blocks, shuffled"""
         m, rng = self.m, self.rng
+        if self.degraded:  # an absent block that a degraded write replaced, read before any rebuild: the new row must come back
+            prefer = [w for w in (list(prefer) or self.absent_written[-4:]) if m.dev_of(w // m.k, w % m.k) in m.devs and not m.corrupt[w // m.k]]
         lost = [b * m.k + i for b in m.live() if not m.corrupt[b] for i in m.blocks_on(b, m.devs) if i < m.k]
         barred = {b * m.k + i for b in m.live() if m.corrupt[b] for i in m.blocks_on(b, m.devs) if i < m.k}
         special = [b * m.k + i for b in sorted(m.quarantined) for i in range(m.k)]
@@ -1038,6 +1500,8 @@ class Generator:
     def make_burst(self):
         """2 to 4 enqueued calls back to back (writes of every form, at most one rebuild), each on the null or the side stream"""
         m, rng = self.m, self.rng
+        if self.degraded:
+            return self._make_degraded_burst()
         ops = []
         for _ in range(int(rng.integers(2, 5))):
             w = self.make_write(in_burst=True) if self.extended else self.make_write()
@@ -1085,6 +1549,8 @@ class Generator:
             if mid is None:
                 return None
             mid[0]["form"] = "batch"
+        elif x == "degraded_write":  # a degraded write into a scratch stripe, under a set of its own
+            mid = self._scratch_set_write()
         elif x == "read":  # a scratch read under the probe's own pattern, or one under the set
             lost = self._probe_lost()
             if self.rng.random() < 0.5:
@@ -1104,12 +1570,17 @@ class Generator:
     def make_probe_set(self, y):
         m = self.m
         ops = []
-        if m.ctx.prepared_set is None or (m.rotated and m.ctx.prepared_set != m.needed_set()):
+        if y == "degraded_write":  # a set of its own, a scratch write under one of its patterns, a scratch repair under another
+            ops = self._scratch_set_write()
+            patterns = ops[0]["patterns"]
+        elif m.ctx.prepared_set is None or (m.rotated and m.ctx.prepared_set != m.needed_set()):
             ops.append(self._state_prepare_set())
             patterns = ops[0]["patterns"]
         else:
             patterns = m.ctx.prepared_set
-        if y == "prepare":
+        if y == "degraded_write":
+            pass
+        elif y == "prepare":
             ops.append(self._state_prepare(self._probe_lost()))
         elif y in ("single", "batch"):
             ops.append(self._state_prepare(self._probe_lost()))
@@ -1148,6 +1619,8 @@ class Generator:
             ops.append(pr)
         elif z == "read":
             ops += self._mid_read()
+        elif z == "degraded_write":
+            ops += self._scratch_set_write()
         else:
             ops.append(self.make_correct()[-1])
         j = self._pick([j for j in range(m.n) if j not in scrub])
@@ -1156,6 +1629,8 @@ class Generator:
         return ops
 
     def make_probe_refused(self, which):
+        if which == "bad_degraded_write":
+            return self._refused_degraded_write(which)
         if which == "bad_read":  # among valid requests an index count*k; for a requested stripe a pattern_of entry equal to the number of patterns
             m = self.m
             reads = [int(x) for x in self.rng.integers(m.count * m.k, size=int(self.rng.integers(2, 6)))]
@@ -1166,6 +1641,8 @@ class Generator:
 
     def next_op(self):
         self.emitted += 1
+        if self.degraded and self.emitted == 1 and self.seed == DEG_SEEDS[0]:  # refused_no_set: no later step meets a context without a set
+            return self._refused_degraded_write("no_set")[0]
         if self.queue:
             return self.queue.popleft()
         if self.probes_started < PROBES_PER_SEQUENCE and self.emitted > 2 + 7 * self.probes_started:
@@ -1188,10 +1665,11 @@ class Generator:
 
 # ---- the driver ----
 class SequenceFailure(AssertionError):
-    def __init__(self, cfg, seed, step, what, log, extended=False):
+    def __init__(self, cfg, seed, step, what, log, extended=False, degraded=False):
         self.cfg, self.seed, self.step, self.what, self.log = cfg, seed, step, what, log
+        flag = ", degraded=True" if degraded else ", extended=True" if extended else ""
         super().__init__("config %s seed %d step %d: %s\nreplay: run_sequence(backend, config_named(%r), %d, steps=%d%s)\noperations:\n%s"
-                         % (cfg.name, seed, step, what, cfg.name, seed, step + 1, ", extended=True" if extended else "", "\n".join(log)))
+                         % (cfg.name, seed, step, what, cfg.name, seed, step + 1, flag, "\n".join(log)))
 
 
 def _same(a, b):
@@ -1200,16 +1678,17 @@ def _same(a, b):
     return a == b
 
 
-def run_sequence(backend, cfg, seed, steps=None, oracle=None, on_step=None, extended=False, log=None):
+def run_sequence(backend, cfg, seed, steps=None, oracle=None, on_step=None, extended=False, log=None, degraded=False):
     """Apply the sequence of (cfg, seed) to a fresh model and to `backend`; after every step compare every host output and the whole pool.
     Returns the model's Coverage.  Raises SequenceFailure (config, seed, step, the operation log) at the first difference.  `extended`: the
-    generator draws the extended kinds as well (the seeds EXT_SEEDS; off, a sequence is what it always was).  `log`: a list that receives the
+    generator draws the extended kinds as well (the seeds EXT_SEEDS; off, a sequence is what it always was).  `degraded`: degraded and column-window
+    writes as well (the seeds DEG_SEEDS; it implies the extended kinds).  `log`: a list that receives the
     operation log, one JSON line per step."""
     if oracle is None:
         from oracle import Oracle
         oracle = Oracle()
     model = PoolModel(cfg, seed, oracle)
-    gen = Generator(model, seed, extended)
+    gen = Generator(model, seed, extended, degraded)
     cov = Coverage(model)
     backend.start(model.mirror_d, model.mirror_p, sorted(model.quarantined))
     log = [] if log is None else log
@@ -1226,13 +1705,13 @@ def run_sequence(backend, cfg, seed, steps=None, oracle=None, on_step=None, exte
         got = backend.run(op, pay)
         for key in want:
             if key not in got or not _same(want[key], got[key]):
-                raise SequenceFailure(cfg, seed, step, "output %r is %r, the model says %r" % (key, got.get(key), want[key]), log, extended)
+                raise SequenceFailure(cfg, seed, step, "output %r is %r, the model says %r" % (key, got.get(key), want[key]), log, extended, degraded)
         d, p = backend.read_pool()
         if not np.array_equal(d, model.mirror_d) or not np.array_equal(p, model.mirror_p):
             bad = sorted({int(b) for b in np.nonzero((d != model.mirror_d).any(axis=(1, 2)) | (p != model.mirror_p).any(axis=(1, 2)))[0]})
             blocks = [j for j in range(model.n) if not np.array_equal(model.block(d, p, bad[0], j), model.block(model.mirror_d, model.mirror_p, bad[0], j))]
             raise SequenceFailure(cfg, seed, step, "the pool differs from the model in stripes %s (quarantined: %s); stripe %d blocks %s"
-                                  % (bad, sorted(model.quarantined), bad[0], blocks), log, extended)
+                                  % (bad, sorted(model.quarantined), bad[0], blocks), log, extended, degraded)
         cov.after(op)
         if on_step:
             on_step(step, op)
@@ -1249,13 +1728,61 @@ class Coverage:
         self.variants = collections.Counter()
         self.probes = collections.Counter()
         self.drawn = self.skipped = 0
+        self.prev = None            # the kind of the step before
+        self.written_absent = set()  # absent data blocks that a degraded write replaced and no rebuild has visited since
+
+    def _rebuilt(self, op):
+        """the absent data blocks whose old rows a write rebuilds (fastecc_update_batch_set alone: the parity form is handed its old rows)"""
+        m = self.m
+        if op["op"] != "write" or op["form"] != "batch_set":
+            return []
+        return [w for w in op["writes"] if w % m.k in m.lost_for_write(w // m.k, "batch_set")]
+
+    def _degraded_write(self, op, v):
+        """the variants of a write of the four pool forms (against the model as the call, or its burst, meets it)"""
+        m, form = self.m, op["form"]
+        v["write_%s_%s" % (form, "window" if "width" in op else "whole_block")] += 1
+        if "width" in op:
+            v["write_window_" + op["shape"]] += 1
+            if self.prev == "prepare_set" and form not in SET_FORMS:
+                v["window_after_prepare_set"] += 1
+        touched = sorted({w // m.k for w in op["writes"]})
+        if any(m.corrupt[b] for b in touched) and "width" in op:
+            v["window_beside_corruption"] += 1
+        if form not in SET_FORMS:
+            return
+        if PATTERN_NONE in op["pattern_of"]:
+            v["write_pattern_none"] += 1
+        absent = [w for w in op["writes"] if w % m.k in m.lost_for_write(w // m.k, form)]
+        if absent:
+            v["write_absent_data"] += 1
+            self.written_absent |= set(absent)
+        if any(w not in absent and m.lost_for_write(w // m.k, form) for w in op["writes"]):
+            v["write_present_of_degraded"] += 1
+        if absent and len(absent) < len(op["writes"]):
+            v["write_mixed_list"] += 1
+        if any(m.lost_for_write(b, form) and min(m.lost_for_write(b, form)) >= m.k for b in touched):
+            v["write_parity_only_stripe"] += 1
+        if self._rebuilt(op):
+            v["write_rebuilt_rows"] += 1
+            if max(collections.Counter(w // m.k for w in op["writes"]).values()) > 16:
+                v["segment_over_16_rebuilt"] += 1
 
     def before(self, op):
         m, kind = self.m, op["op"]
         self.kinds[kind] += 1
         if kind == "burst":
+            self.prev = "burst"  # (no call of a burst counts as the step after the operation before the burst)
             for sub in op["ops"]:
                 self.before(sub)
+            for x, y in zip(op["ops"], op["ops"][1:]):  # neighbours on different streams: a read beside a rebuilding write, two rebuilding writes
+                if x["stream"] != y["stream"]:
+                    if x["op"] == "read" and self._rebuilt(y):
+                        self.variants["burst_read_then_rebuilding_write"] += 1
+                    if self._rebuilt(x) and y["op"] == "read":
+                        self.variants["burst_rebuilding_write_then_read"] += 1
+                    if self._rebuilt(x) and self._rebuilt(y) and x.get("width", m.S) != y.get("width", m.S):
+                        self.variants["burst_rebuilding_writes_two_widths"] += 1
             if len({sub["stream"] for sub in op["ops"]}) > 1:
                 self.variants["burst_two_streams"] += 1
                 if any(sub["op"] == "read" for sub in op["ops"]):
@@ -1296,6 +1823,19 @@ class Coverage:
             v["correct_mode_%d" % op["mode"]] += 1
         if kind in ("repair", "decode"):
             v["kernel_%d" % op["kernel"]] += 1
+        if kind == "write" and op["form"] in WINDOW_FORMS:
+            self._degraded_write(op, v)
+        if kind in ("repair", "decode", "correct") or (kind == "write" and op["form"] == "pool"):
+            self.written_absent.clear()
+        if kind == "read" and any(w in self.written_absent and m.dev_of(w // m.k, w % m.k) in m.devs for w in op["reads"]):
+            v["read_of_written_absent_block"] += 1
+        if kind in ("probe_write", "probe_write_swap"):  # scratch writes: counted apart from the pool's
+            for half in (op["halves"] if kind == "probe_write_swap" else [op]):
+                v["probe_write_" + ("whole_block" if half["shape"] == "whole_block" else "window")] += 1
+                if kind == "probe_write" and not op.get("after"):
+                    v["state_probe_write_" + ("whole_block" if half["shape"] == "whole_block" else "window")] += 1
+            if kind == "probe_write_swap":
+                v["side_stream_scratch_write"] += 1
         if kind == "write":
             v["write_" + op["form"]] += 1
             per = collections.Counter(w // m.k for w in writes_of(op, m.k))
@@ -1337,6 +1877,11 @@ class Coverage:
     def after(self, op):
         if op.get("probe"):
             self.probes[op["probe"]] += 1
+            if op["op"] == "refused" and op.get("variant"):  # (the model has checked that the variant's argument is the only thing wrong)
+                self.variants["refused_" + op["variant"]] += 1
+                for entry in op["entries"]:
+                    self.variants["refused_%s_%s" % (op["variant"], entry)] += 1
+        self.prev = op["op"]
 
     def merge(self, other):
         self.kinds.update(other.kinds)
@@ -1388,6 +1933,12 @@ class ModelBackend:
     def op_write(self, op, pay):
         """fastecc_update_batch, fastecc_update on one stripe, or fastecc_update_parity_batch + the caller's own store of the data blocks"""
         writes = writes_of(op, self.k)  # (form "pool": the harness stores every data block of the run, fastecc_encode_pool encodes it)
+        if op["form"] in SET_FORMS or "width" in op:
+            def lost_of(b):
+                q = op["pattern_of"][b] if op["form"] in SET_FORMS else PATTERN_NONE
+                return () if q == PATTERN_NONE else self.prepared_set[q]
+            return self.write_rows(self.d, self.p, self.td, self.tp, [divmod(w, self.k) for w in writes], pay["new"], lost_of, op["form"],
+                                   op.get("col0", 0), op.get("width", self.S))
         for u, w in enumerate(writes):
             self.d[w // self.k, w % self.k] = pay["new"][u]
         touched = sorted({w // self.k for w in writes})
@@ -1399,6 +1950,80 @@ class ModelBackend:
 
     def encoded_stripes(self, op, stripes):
         return stripes
+
+    # -- degraded and window writes, from the definition: the truth takes the rows, the parity is the oracle's re-encode of the truth, the present
+    # blocks take both in the window's columns.  The library updates the parity from the CHANGE of each written block, so an old row it gets wrong
+    # shows in the parity as the re-encode of a stripe that is off by that much: write_rows keeps this form, so that defects in the old rows can be
+    # injected (the exact backend's old rows are the truth, and the term is zero).
+    def write_rows(self, d, p, td, tp, writes, new, lost_of, form, col0, width):
+        """d, p: a pool (stripes, k or n - k, S) and td, tp its truth; writes: (stripe, block) pairs, row u of `new` for writes[u]"""
+        win = slice(col0, col0 + width)
+        rebuilt = [u for u, (b, i) in enumerate(writes) if form == "batch_set" and i in lost_of(b)]
+        recon = dict(zip(rebuilt, self.rebuilt_rows(d, td, [writes[u] for u in rebuilt], col0, width)))
+        off = {}
+        for u, (b, i) in enumerate(writes):
+            absent = i in lost_of(b)
+            if u in recon and not np.array_equal(recon[u], td[b, i, win]):  # (what the parity will be wrong by)
+                off[b, i] = (td[b, i, win].astype(np.int64) - recon[u].astype(np.int64) % P) % P
+            td[b, i, win] = new[u]
+            if self.stores_data(form, absent):  # (the parity forms: the harness, as the caller, stores the window into present data blocks)
+                self.store_data(d, b, i, col0, width, new[u], form)
+        for b in sorted({b for b, _ in writes}):
+            tp[b] = self.codec.parity(td[b])
+            rows = tp[b]
+            if any(x == b for x, _ in off):
+                x = td[b].copy()
+                for (bb, i), e in off.items():
+                    if bb == b:
+                        x[i, win] = ((x[i, win].astype(np.int64) + e) % P).astype(np.uint32)
+                rows = self.codec.parity(x)
+            self.store_parity(p, b, rows, [q - self.k for q in lost_of(b) if q >= self.k], col0, width)
+
+    def rebuilt_rows(self, d, td, blocks, col0, width):
+        """the old rows of the absent written blocks, as a rebuild from the survivors gives them"""
+        return [td[b, i, col0:col0 + width].copy() for b, i in blocks]
+
+    def stores_data(self, form, absent):
+        return not absent
+
+    def store_data(self, d, b, i, col0, width, row, form):
+        d[b, i, col0:col0 + width] = row
+
+    def store_parity(self, p, b, rows, lost, col0, width):
+        for q in range(self.m):
+            if q not in lost:
+                p[b, q, col0:col0 + width] = rows[q, col0:col0 + width]
+
+    def _scratch_write(self, half, pay_d, pay_p, new, src, lost):
+        """one degraded write into a scratch stripe whose truth is stripe src's: (d, p, its new truth)"""
+        d, p, td, tp = pay_d.copy()[None], pay_p.copy()[None], self.td[src].copy()[None], self.tp[src].copy()[None]
+        self.write_rows(d, p, td, tp, [(0, i) for i in half["writes"]], new, lambda b: lost, half["form"], half["col0"], half["width"])
+        return d[0], p[0], td[0], tp[0]
+
+    def op_probe_write(self, op, pay):
+        lost = self.prepared_set[op["q"]]
+        d, p, td, tp = self._scratch_write(op, pay["scratch_d"], pay["scratch_p"], pay["new"], pay["src"], lost)
+        out = {"code": OK}
+        if op.get("after") == "repair":
+            for j in lost:
+                (d if j < self.k else p)[j if j < self.k else j - self.k] = (td if j < self.k else tp)[j if j < self.k else j - self.k]
+            out["codes"] = [OK, OK]
+        if op.get("after") == "read":
+            rows = self.read_rows(d[None], td[None], [(0, i) for i in op["reads"]], lambda b: lost, op["col0"], op["width"])
+            out.update(codes=[OK, OK], rows=rows[:-1], guard=rows[-1])
+        return dict(out, scratch_d=d, scratch_p=p)
+
+    def op_probe_write_swap(self, op, pay):
+        ds, ps = [], []
+        for half, (d, p), new in zip(op["halves"], pay["scratch"], pay["new"]):
+            self.prepared_set = tuple(tuple(q) for q in half["patterns"])
+            d, p, _, _ = self._scratch_write(half, d, p, new, pay["src"], self.swap_pattern(op, half))
+            ds.append(d)
+            ps.append(p)
+        return {"code": OK, "codes": [OK] * 4, "scratch_d": np.stack(ds), "scratch_p": np.stack(ps)}
+
+    def swap_pattern(self, op, half):
+        return self.prepared_set[half["q"]]
 
     def op_prepare(self, op, pay):
         self.prepared = tuple(op["lost"])
@@ -1569,6 +2194,8 @@ class ModelBackend:
     def op_refused(self, op, pay):
         if op["which"] == "bad_read":
             return {"code": E_INVAL, "codes": [E_INVAL, E_INVAL], "rows": canary_rows(2 * (len(op["reads"]) + 1), op["width"]).reshape(-1)}
+        if op["which"] in ("bad_degraded_write", "no_set"):
+            return {"code": E_INVAL, "codes": [E_INVAL] * len(op["entries"]), "rows": pay["new"].reshape(-1).copy()}
         return {"code": E_INVAL}
 
 
@@ -1668,7 +2295,7 @@ class GpuBackend:
     def _stage(self, op, pay):
         """the new (and old) blocks of a write in device memory, uploaded on the null stream before the call is enqueued"""
         self._order(0)
-        staged = (self._dev(pay["new"]), self._dev(pay["old"]) if op["form"] == "parity" else None)
+        staged = (self._dev(pay["new"]), self._dev(pay["old"]) if op["form"] in ("parity", "parity_set") else None)
         self.keep.append(staged)
         return staged
 
@@ -1682,6 +2309,13 @@ class GpuBackend:
                 D[:cnt * self.dw].copy_(new)
             return {"code": self._code(self.enc.encode_pool, D, Q, cnt, stream=lib)}
         writes = op["writes"]
+        if op["form"] in SET_FORMS or "width" in op:
+            po = None
+            if op["form"] in SET_FORMS:
+                po = np.array(op["pattern_of"], dtype=np.uint32)
+                if op.get("ignored") is not None:
+                    po[op["ignored"]] = op["entry"]  # the number of patterns in force, for a stripe that no write names
+            return {"code": self._pool_write(op, self.D, self.Q, self.count, po, writes, new, old)}
         if op["form"] == "batch":
             return {"code": self._code(self.enc.update_batch, self.D, self.Q, self.count, writes, new, stream=self._lib())}
         if op["form"] == "single":
@@ -1693,6 +2327,109 @@ class GpuBackend:
             for u, w in enumerate(writes):
                 self.D[w * self.S:][:self.S].copy_(new[u * self.S:][:self.S])
         return {"code": code}
+
+    def _pool_write(self, op, D, Q, count, po, writes, new, old):
+        """one of the four pool forms on the pool (D, Q) of `count` stripes, on the sequence's stream: the _set forms with pattern_of `po`, a
+        window where the operation has one (col0 = 0, width = None is the whole-block entry point); rows compact at pitch width.  The parity
+        forms store no data: the harness, as the caller, stores the window into the PRESENT data blocks itself, on the same stream."""
+        kw = {"col0": op["col0"], "width": op["width"]} if "width" in op and op.get("shape") != "whole_block" else {}
+        form, lib = op["form"], self._lib()
+        if form == "batch":
+            return self._code(self.enc.update_batch, D, Q, count, writes, new, stream=lib, **kw)
+        if form == "batch_set":
+            code = self._code(self.enc.update_batch_set, D, Q, count, po, writes, new, stream=lib, **kw)
+            po[:] = 0xFFFFFFFE  # pattern_of may be reused as soon as the call returns
+            return code
+        lost = [()] * len(writes)
+        if form == "parity":
+            code = self._code(self.enc.update_parity_batch, Q, count, writes, new, old=old, stream=lib, **kw)
+        else:
+            lost = [() if po[w // self.k] == PATTERN_NONE else self.patterns[int(po[w // self.k])] for w in writes]
+            code = self._code(self.enc.update_parity_batch_set, Q, count, po, writes, new, old=old, stream=lib, **kw)
+            po[:] = 0xFFFFFFFE
+        col0, W = op.get("col0", 0), op.get("width", self.S)
+        with self.torch.cuda.stream(self.streams[self.cur]):
+            for u, w in enumerate(writes):
+                if w % self.k not in lost[u]:
+                    D[w * self.S + col0:][:W].copy_(new[u * W:][:W])
+        return code
+
+    def _set_patterns(self, patterns):
+        """fastecc_decode_prepare_set, and the patterns kept for the caller's own stores of the parity form"""
+        code = self._code(self.enc.decode_prepare_set, *self._flag_rows(patterns))
+        self.patterns = [tuple(q) for q in patterns]
+        return code
+
+    def op_probe_write(self, op, pay):
+        """a degraded write into the scratch stripe under pattern q; then nothing, a repair under the same pattern on the same stream, or a read of
+        the written blocks on the OTHER stream, ordered behind the write by an event only"""
+        sd, sq = self._scratch(pay["scratch_d"], pay["scratch_p"])
+        new, old = self._dev(pay["new"]), self._dev(pay["old"])
+        out = self._read_buffer(len(op["reads"]), op["width"]) if op.get("after") == "read" else None
+        self.keep.append((new, old))
+        codes = [self._pool_write(op, sd, sq, 1, np.array([op["q"]], dtype=np.uint32), op["writes"], new, old)]
+        got = {}
+        if op.get("after") == "repair":
+            codes.append(self._code(self.enc.repair_batch_set, sd, sq, 1, [op["q"]], stream=self._lib()))
+        if op.get("after") == "read":
+            cur, self.cur = self.cur, 1 - self.cur
+            codes.append(self._read_call(op, sd, sq, 1, op["reads"], [op["q"]], out))
+            self.cur = cur
+            got = self._read_back(OK, out, len(op["reads"]), op["width"])
+        res = dict(self._scratch_out(codes[0]), **{x: got[x] for x in ("rows", "guard") if x in got})
+        if len(codes) > 1:
+            res["codes"] = codes
+        return res
+
+    def op_probe_write_swap(self, op, pay):
+        """the two scratch stripes and the rows first; then decode_prepare_set, a degraded write on the side stream, decode_prepare_set again with
+        nothing synchronised here (the library waits for the write itself), a degraded write on the sequence's stream; read back at the end"""
+        self._order(0)
+        rows = []
+        for s, (d, p) in enumerate(pay["scratch"]):
+            self.sd[s * self.dw:][:self.dw].copy_(self._dev(d))
+            self.sq[s * self.pw:][:self.pw].copy_(self._dev(p))
+            rows.append((self._dev(pay["new"][s]), self._dev(pay["old"][s])))
+        self.keep.append(rows)
+        cur, codes = self.cur, []
+        for s, (half, (new, old)) in enumerate(zip(op["halves"], rows)):
+            codes.append(self._set_patterns(half["patterns"]))
+            self.cur = 1 if s == 0 else cur
+            codes.append(self._pool_write(half, self.sd[s * self.dw:], self.sq[s * self.pw:], 1, np.array([half["q"]], dtype=np.uint32), half["writes"], new, old))
+        self.cur = cur
+        self._order(0)
+        return {"code": OK, "codes": codes, "scratch_d": self._host(self.sd[:2 * self.dw]).reshape(2, self.k, self.S),
+                "scratch_p": self._host(self.sq[:2 * self.pw]).reshape(2, self.m, self.S)}
+
+    def _refused_write(self, op, pay):
+        """A degraded write that the library must refuse, through the C entry points (past what the Python methods let through): the codes and the
+        caller's rows read back.  The operation is a valid write — its own pattern_of, legal stripes, a window inside the block, rows of S words
+        outside the pool — and only the argument that the variant names is spoiled here; one call per entry point it lists."""
+        ct, lib, h = self.ct, self.fe.lib(), self.enc._h
+        n, variant = len(op["writes"]), op.get("variant")
+        rows = self._dev(pay["new"])
+        self.keep.append(rows)
+        writes = (ct.c_uint64 * n)(*op["writes"])
+        po = np.array(op["pattern_of"], dtype=np.uint32)
+        if variant == "entry":
+            po[op["writes"][0] // self.k] = op["entry"]  # the number of patterns in force, for a touched stripe
+        pp = None if variant == "null_pattern_of" else po.ctypes.data_as(ct.POINTER(ct.c_uint32))
+        st = self._lib() or None
+        D, Q, codes = self.D.data_ptr(), self.Q.data_ptr(), []
+        for entry in op["entries"]:
+            whole = entry == "whole_block"
+            new = rows.data_ptr()
+            if variant == "overlap":  # the rows, as n_writes * width words (n_writes blocks for the whole-block call), are the end of the parity pool
+                new = self.Q[self.count * self.pw - n * (self.S if whole else op["call_width"]):].data_ptr()
+            window = () if whole else (op["call_col0"], op["call_width"])
+            if op["form"] == "batch_set":
+                call = lib.fastecc_update_batch_set if whole else lib.fastecc_update_batch_set_window
+                codes.append(call(h, D, Q, self.count, pp, writes, n, *window, new, st))
+            else:
+                call = lib.fastecc_update_parity_batch_set if whole else lib.fastecc_update_parity_batch_set_window
+                codes.append(call(h, Q, self.count, pp, writes, n, *window, None, new, st))
+        self._order(0)
+        return {"code": codes[0], "codes": codes, "rows": self._host(rows)}
 
     def op_burst(self, op, pay):
         """every block uploaded first, then the calls enqueued back to back, each on its stream, with event waits between streams and no
@@ -1758,7 +2495,7 @@ class GpuBackend:
         outs = [self._read_buffer(len(half["reads"]), half["width"]) for half in op["halves"]]
         cur, codes = self.cur, []
         for s, (half, out) in enumerate(zip(op["halves"], outs)):
-            codes.append(self._code(self.enc.decode_prepare_set, *self._flag_rows(half["patterns"])))
+            codes.append(self._set_patterns(half["patterns"]))
             self.cur = 1 if s == 0 else cur
             codes.append(self._read_call(half, self.sd[s * self.dw:], self.sq[s * self.pw:], 1, half["reads"], [half["q"]], out))
         self.cur = cur
@@ -1786,7 +2523,7 @@ class GpuBackend:
         return {"code": self._code(self.enc.decode_prepare, *self._flags(op["lost"]))}
 
     def op_prepare_set(self, op, pay):
-        return {"code": self._code(self.enc.decode_prepare_set, *self._flag_rows(op["patterns"]))}
+        return {"code": self._set_patterns(op["patterns"])}
 
     def op_scrub_pattern(self, op, pay):
         return {"code": self._code(self.enc.scrub_erasures, *self._flags(op["absent"]))}
@@ -1900,6 +2637,8 @@ class GpuBackend:
 
     def op_refused(self, op, pay):
         D, Q, lib, h = self.D, self.Q, self.fe.lib(), self.enc._h
+        if op["which"] in ("bad_degraded_write", "no_set"):
+            return self._refused_write(op, pay)
         if op["which"] == "bad_read":
             n, rotated = len(op["reads"]), self.cfg.placement == "rotated"
             outs = [self._read_buffer(n, op["width"]) for _ in range(2)]

@@ -4,10 +4,13 @@ Writes (fastecc_update_batch, _update_parity_batch, fastecc_update), silent corr
 correct, repair, decode, re-encode, option and stream flips, sub-range calls and the state probes of pool_model's docstring follow one another
 as the generator draws them — in the extended sequences (the seeds pool_model.EXT_SEEDS) degraded reads (fastecc_read_batch, _read_batch_set)
 alone and inside bursts, location under the pattern set (fastecc_locate_errors_batch_set) and whole-stripe writes and re-encodes
-(fastecc_encode_pool under every "encode_pool_kernel") as well; after every step every host output equals the model's prediction and the
+(fastecc_encode_pool under every "encode_pool_kernel") as well; in the degraded sequences (the seeds pool_model.DEG_SEEDS) the writes go on while
+devices are down (fastecc_update_batch_set, _update_parity_batch_set: absent blocks written, rebuilt rows, bursts that put a read beside such a
+write and two such writes of different widths on different streams) and the four pool forms take column windows (the fastecc_update_*_window
+calls); after every step every host output equals the model's prediction and the
 whole pool, data and parity, quarantined stripes included, equals the model's mirror bit for bit.  The model's parity is the oracle's; no comparison here uses the library as its own
 reference, and none has a tolerance.  A failure names the configuration, the seed, the step and the operations so far;
-pool_model.run_sequence(backend, config, seed, steps=N) replays the prefix (with extended=True for an extended sequence: the message says so)."""
+pool_model.run_sequence(backend, config, seed, steps=N) replays the prefix (with extended=True for an extended sequence, degraded=True for a degraded one: the message says so)."""
 import pytest
 
 import pool_model as pm
@@ -30,14 +33,15 @@ def fe(hip_lib):
 
 CASES = [(cfg.name, seed) for cfg in pm.CONFIGS for seed in pm.SEEDS]
 EXT_CASES = [(cfg.name, seed) for cfg in pm.CONFIGS for seed in pm.EXT_SEEDS]
+DEG_CASES = [(cfg.name, seed) for cfg in pm.CONFIGS for seed in pm.DEG_SEEDS]
 
 
-@pytest.mark.parametrize("name,seed", CASES + EXT_CASES)
+@pytest.mark.parametrize("name,seed", CASES + EXT_CASES + DEG_CASES)
 def test_sequence(torch_cuda, fe, oracle, name, seed):
     cfg = pm.config_named(name)
     backend = pm.GpuBackend(fe, torch_cuda, cfg)
     try:
-        pm.run_sequence(backend, cfg, seed, oracle=oracle, extended=seed in pm.EXT_SEEDS)
+        pm.run_sequence(backend, cfg, seed, oracle=oracle, extended=seed in pm.EXT_SEEDS, degraded=seed in pm.DEG_SEEDS)
     finally:
         backend.close()
 
@@ -87,4 +91,24 @@ def test_extended_kernels_ran(torch_cuda, fe, oracle):
         for names in backend.scopes.values():
             seen |= names
     missing = [x for x in EXTENDED_SCOPES if x not in seen]
+    assert not missing, (missing, sorted(seen))
+
+
+DEGRADED_SCOPES = ("update_set", "update_set_recon", "update_window", "update_window_recon", "update_window_scatter")
+
+
+def test_degraded_kernels_ran(torch_cuda, fe, oracle):
+    """One long degraded sequence per placement with profiling on: the set kernel and the window kernel ran, each with a reconstruction pass for
+    absent written blocks, and the window scatter stored rows."""
+    seen = set()
+    for name in ("20_16_s64_fixed", "20_16_s64_rotated"):
+        cfg = pm.config_named(name)
+        backend = pm.GpuBackend(fe, torch_cuda, cfg, profile=True)
+        try:
+            pm.run_sequence(backend, cfg, 11, steps=LONG_STEPS, oracle=oracle, degraded=True)
+        finally:
+            backend.close()
+        for names in backend.scopes.values():
+            seen |= names
+    missing = [x for x in DEGRADED_SCOPES if x not in seen]
     assert not missing, (missing, sorted(seen))

@@ -2,9 +2,12 @@
 
   - the model is sound: its parity equals the generator matrix of fastecc_code_coefficient (host-only arithmetic of the library, the one
     thing here that is not the oracle), and decoding its truth under every device-down pattern gives the truth back;
-  - every (config, seed) of tests/test_gpu_pool_sequences.py runs green on the exact numpy backend, the extended sequences (EXT_SEEDS) included;
-  - the 64 sequences of SEEDS are, operation for operation, what they were before the extended kinds existed (recorded digests);
-  - seven injected defects, and seven more in the extended operations, are each reported at the step where they first change a byte or an answer;
+  - every (config, seed) of tests/test_gpu_pool_sequences.py runs green on the exact numpy backend, the extended sequences (EXT_SEEDS) and the
+    degraded ones (DEG_SEEDS) included;
+  - the 64 sequences of SEEDS are, operation for operation, what they were before the extended kinds existed, and the 32 of EXT_SEEDS what they
+    were before the degraded kinds existed (recorded digests);
+  - seven injected defects, seven more in the extended operations and ten in the degraded and window writes are each reported at the step where
+    they first change a byte or an answer;
   - the committed seeds of every configuration cover what they must (operation kinds, variants, state probes, few illegal draws, the budget)."""
 import hashlib
 import itertools
@@ -21,6 +24,7 @@ from pool_model import P
 FIXED = [c for c in pm.CONFIGS if c.placement == "fixed"]
 CASES = [(cfg.name, seed) for cfg in pm.CONFIGS for seed in pm.SEEDS]
 EXT_CASES = [(cfg.name, seed) for cfg in pm.CONFIGS for seed in pm.EXT_SEEDS]
+DEG_CASES = [(cfg.name, seed) for cfg in pm.CONFIGS for seed in pm.DEG_SEEDS]
 
 
 def group_of(cfg):
@@ -123,22 +127,25 @@ _DRY, _LOGS = {}, {}
 
 
 def dry_run(oracle, name, seed):
-    """the sequence of (name, seed) on the exact backend, once per session: its Coverage (the seeds of EXT_SEEDS are the extended sequences)"""
+    """the sequence of (name, seed) on the exact backend, once per session: its Coverage (the seeds of EXT_SEEDS are the extended sequences, those
+    of DEG_SEEDS the degraded ones)"""
     if (name, seed) not in _DRY:
         cfg = pm.config_named(name)
         _LOGS[name, seed] = []
-        _DRY[name, seed] = pm.run_sequence(pm.ModelBackend(cfg, oracle), cfg, seed, oracle=oracle, extended=seed in pm.EXT_SEEDS, log=_LOGS[name, seed])
+        _DRY[name, seed] = pm.run_sequence(pm.ModelBackend(cfg, oracle), cfg, seed, oracle=oracle, extended=seed in pm.EXT_SEEDS, degraded=seed in pm.DEG_SEEDS,
+                                                log=_LOGS[name, seed])
     return _DRY[name, seed]
 
 
 def test_the_committed_sequences_are_unchanged(oracle):
     """tests/golden/pool_sequence_digests.json: sha256 of the operation log (run_sequence's JSON lines, joined by newlines) of every (config, seed)
-    of SEEDS, recorded on the commit before the generator learned the extended kinds.  With `extended` off it draws what it drew then."""
+    of SEEDS, recorded on the commit before the generator learned the extended kinds, and of EXT_SEEDS, recorded on the commit before it learned
+    the degraded kinds.  With `extended` off it draws what it drew then, and with `degraded` off an extended sequence is what it was."""
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pool_sequence_digests.json")) as f:
         recorded = json.load(f)
-    assert sorted(recorded) == sorted("%s:%d" % c for c in CASES)
+    assert sorted(recorded) == sorted("%s:%d" % c for c in CASES + EXT_CASES)
     changed = []
-    for name, seed in CASES:
+    for name, seed in CASES + EXT_CASES:
         dry_run(oracle, name, seed)
         assert len(_LOGS[name, seed]) == pm.config_named(name).steps
         if hashlib.sha256("\n".join(_LOGS[name, seed]).encode()).hexdigest() != recorded["%s:%d" % (name, seed)]:
@@ -146,7 +153,7 @@ def test_the_committed_sequences_are_unchanged(oracle):
     assert not changed
 
 
-@pytest.mark.parametrize("name,seed", CASES + EXT_CASES)
+@pytest.mark.parametrize("name,seed", CASES + EXT_CASES + DEG_CASES)
 def test_harness_passes_on_the_exact_backend(oracle, name, seed):
     cfg = pm.config_named(name)
     cov = dry_run(oracle, name, seed)
@@ -206,6 +213,106 @@ def test_coverage_of_the_extended_seeds(oracle, group):
     assert not [x for x in variants if not total.variants[x]]
     if group == "256_128":  # the single form serves up to 256 lost blocks, a set at most 16 per pattern
         assert fixed.variants["read_single_over_16_lost"]
+
+
+DEG_PROBES = ["prepared_after_degraded_write", "set_after_degraded_write", "scrub_after_degraded_write", "write_after_prepare_set",
+              "read_after_degraded_write", "repair_after_degraded_write", "untouched_pattern_ignored", "refused_bad_degraded_write", "refused_no_set"]
+
+
+@pytest.mark.parametrize("group", GROUPS)
+def test_coverage_of_the_degraded_seeds(oracle, group):
+    """What the two degraded seeds of a configuration's two placements must meet between them (counted on the model, as above)."""
+    cfgs = [c for c in pm.CONFIGS if group_of(c) == group]
+    total = pm.Coverage(None)
+    for cfg in cfgs:
+        for seed in pm.DEG_SEEDS:
+            total.merge(dry_run(oracle, cfg.name, seed))
+    mixed, k = bool(cfgs[0].flags), cfgs[0].k
+    probes = [x for x in DEG_PROBES if not (mixed and x.startswith("scrub_"))]
+    assert not {x: total.probes[x] for x in probes if total.probes[x] < 2}
+    forms = ["write_%s_%s" % (f, w) for f in pm.WINDOW_FORMS for w in ("window", "whole_block")]  # every form, with and without a window
+    assert not {x: total.variants[x] for x in forms if total.variants[x] < 5}
+    variants = ["write_window_" + x for x in pm.WRITE_WINDOWS]  # (pool writes alone: a probe's scratch write counts as probe_write_*)
+    # the scratch writes of the probes, and those in the middle of a state probe, through the whole-block and the window entry points
+    variants += ["probe_write_whole_block", "probe_write_window", "state_probe_write_whole_block", "state_probe_write_window"]
+    variants += ["write_absent_data", "write_present_of_degraded", "write_mixed_list", "write_parity_only_stripe", "write_pattern_none",
+                 "read_of_written_absent_block"]
+    variants += [] if mixed else ["window_beside_corruption"]  # the mixed-radix group draws no corruption
+    # the bursts: (a) a read beside a rebuilding write on the other stream, in both orders, (b) two rebuilding writes of different widths on
+    # different streams, and (c) a plain window write directly after a decode_prepare_set
+    variants += ["burst_read_then_rebuilding_write", "burst_rebuilding_write_then_read", "burst_rebuilding_writes_two_widths", "window_after_prepare_set"]
+    variants += ["segment_over_16_rebuilt"] if k > 16 else []
+    assert not [x for x in variants if not total.variants[x]]
+
+
+def test_every_refused_degraded_write_is_drawn(oracle):
+    """refused_bad_degraded_write draws one variant per probe: the committed sequences meet all six between them, each as a write that the model
+    allows but for the variant's own argument (PoolModel._refused raises ModelError otherwise), the variants that are no matter of the window
+    through the whole-block and the window entry point"""
+    total = pm.Coverage(None)
+    for name, seed in DEG_CASES:
+        total.merge(dry_run(oracle, name, seed))
+    assert not [x for x in pm.BAD_DEGRADED_WRITES if not total.variants["refused_" + x]]
+    assert not [(x, e) for x in ("entry", "null_pattern_of", "overlap") for e in ("whole_block", "window") if not total.variants["refused_%s_%s" % (x, e)]]
+    assert not [x for x in ("width0", "past_end", "overflow") if not total.variants["refused_%s_window" % x]]
+
+
+def test_a_refused_degraded_write_has_one_reason(oracle):
+    """the model refuses to predict a refusal that has a second reason: a set in force whose number of patterns a touched stripe's entry reaches,
+    a quarantined stripe, a window of the call that is not the variant's"""
+    cfg = pm.config_named("20_16_s64_rotated")
+    model = pm.PoolModel(cfg, 7, oracle)
+    b = model.live()[5]
+    op = {"op": "refused", "which": "bad_degraded_write", "variant": "past_end", "form": "batch_set", "writes": [b * cfg.k + 1], "entry": model.npat,
+          "pattern_of": model.pattern_of(0, cfg.count, lambda x: x not in model.quarantined), "col0": 3, "width": 5, "shape": "narrow",
+          "call_col0": cfg.S + 1 - 5, "call_width": 5, "entries": ["window"], "dseed": 1}
+    model.apply({"op": "prepare_set", "patterns": [[1], [2], [3]]}, {})  # stripe b's entry b mod n is beyond these three patterns
+    with pytest.raises(pm.ModelError):
+        model.apply(op, model.payload(op))
+    model.apply({"op": "prepare_set", "patterns": [list(q) for q in model.needed_set()]}, {})
+    assert model.apply(op, model.payload(op))["codes"] == [pm.E_INVAL]
+    for wrong in ({"writes": [sorted(model.quarantined)[0] * cfg.k]}, {"call_col0": 3}, {"entry": 3}, {"writes": [cfg.count * cfg.k]}):
+        with pytest.raises(pm.ModelError):
+            model.apply(dict(op, **wrong), model.payload(dict(op, **wrong)))
+
+
+def test_the_model_refuses_illegal_degraded_writes(oracle):
+    """include/fastecc.h: a plain form into a stripe with an absent block, a window over a wrong word and a quarantined stripe have no defined
+    result: ModelError.  A window beside a single wrong word is legal and the corruption mark stays."""
+    cfg = pm.config_named("20_16_s64_rotated")
+    model = pm.PoolModel(cfg, 7, oracle)
+    b = model.live()[0]
+
+    def write(form, blocks, **kw):
+        op = dict({"op": "write", "form": form, "writes": blocks, "dseed": 1}, **kw)
+        if form in pm.SET_FORMS:
+            op["pattern_of"] = model.pattern_of(0, cfg.count, lambda x: x not in model.quarantined)
+        return model.apply(op, model.payload(op))
+    corrupt = {"op": "corrupt", "b": b, "blocks": [1], "how": "word", "dseed": 2}
+    model.apply(corrupt, model.payload(corrupt))
+    col = int(model.wrong_columns(b)[0])
+    beside = (col + 1) % cfg.S
+    with pytest.raises(pm.ModelError):
+        write("batch", [b * cfg.k], col0=col, width=1, shape="word")
+    with pytest.raises(pm.ModelError):
+        write("batch", [b * cfg.k])
+    with pytest.raises(pm.ModelError):
+        write("single", [b * cfg.k + 2], col0=beside, width=1, shape="word")  # single and pool keep no window
+    write("batch", [b * cfg.k + 1], col0=beside, width=1, shape="word")  # the corrupted block itself, beside its wrong word
+    assert model.corrupt[b] == {1: "small"} and model.mirror_d[b, 1, col] != model.truth_d[b, 1, col]
+    assert np.array_equal(model.truth_p[b][:, beside], model.mirror_p[b][:, beside])
+    with pytest.raises(pm.ModelError):
+        write("batch_set", [b * cfg.k + 3])  # no set prepared
+    down = {"op": "device_down", "dev": (0 + b) % cfg.n, "dseed": 3}  # stripe b loses data block 0
+    model.apply(down, model.payload(down))
+    model.apply({"op": "prepare_set", "patterns": [list(q) for q in model.needed_set()]}, {})
+    with pytest.raises(pm.ModelError):
+        write("parity", [b * cfg.k + 3], col0=beside, width=1, shape="word")  # a plain form, an absent block
+    garbage = model.mirror_d[b, 0].copy()
+    write("batch_set", [b * cfg.k, b * cfg.k + 3], col0=beside, width=1, shape="word")
+    assert np.array_equal(model.mirror_d[b, 0], garbage) and model.truth_d[b, 0, beside] != garbage[beside]  # the absent block stays as it is
+    with pytest.raises(pm.ModelError):
+        write("batch_set", [sorted(model.quarantined)[0] * cfg.k], col0=beside, width=1, shape="word")
 
 
 def test_sequences_are_deterministic_and_replayable(oracle):
@@ -441,27 +548,134 @@ class BurstReadSeesTheOldPool(Defective):
             del self.run
 
 
+# ---- defects in the degraded and window writes ----
+class StoresIntoAnAbsentBlock(Defective):
+    """fastecc_update_batch_set stores the new row into an ABSENT data block"""
+
+    def stores_data(self, form, absent):
+        return True if form == "batch_set" else super().stores_data(form, absent)
+
+
+class UpdatesAnAbsentParityBlock(Defective):
+    """a _set form updates an absent parity block"""
+
+    def store_parity(self, p, b, rows, lost, col0, width):
+        super().store_parity(p, b, rows, (), col0, width)
+
+
+class OldRowFromThePool(Defective):
+    """an absent written block's old row is taken from the pool (garbage), not from a rebuild"""
+
+    def rebuilt_rows(self, d, td, blocks, col0, width):
+        return [d[b, i, col0:col0 + width].copy() for b, i in blocks]
+
+
+class ParityOneColumnTooWide(Defective):
+    """a window call writes width + 1 columns of the parity"""
+
+    def store_parity(self, p, b, rows, lost, col0, width):
+        super().store_parity(p, b, rows, lost, col0, width)
+        if col0 + width < self.S:
+            for q in range(self.m):
+                if q not in lost:
+                    p[b, q, col0 + width] ^= np.uint32(1)
+
+
+class DataWindowShiftedRight(Defective):
+    """the data store of a window call applies the window one column to the right"""
+
+    def store_data(self, d, b, i, col0, width, row, form):
+        if form in ("batch", "batch_set") and width < self.S:
+            n = min(width, self.S - col0 - 1)
+            d[b, i, col0 + 1:col0 + 1 + n] = row[:n]
+        else:
+            super().store_data(d, b, i, col0, width, row, form)
+
+
+class OldRowsAtTheEarlierWidth(Defective):
+    """the second of two rebuilding writes reads its old rows from the reconstruction buffer at the first one's pitch"""
+    pitch = None
+
+    def rebuilt_rows(self, d, td, blocks, col0, width):
+        rows = super().rebuilt_rows(d, td, blocks, col0, width)
+        if rows and self.pitch not in (None, width):
+            flat = np.concatenate(rows + [np.zeros(len(rows) * self.pitch + width, np.uint32)])
+            rows = [flat[r * self.pitch:r * self.pitch + width].copy() for r in range(len(rows))]
+        if rows:
+            self.pitch = width
+        return rows
+
+
+class WritesUnderTheOldSet(Defective):
+    """a degraded write after a second decode_prepare_set still uses the first set (the write_after_prepare_set probe)"""
+
+    def swap_pattern(self, op, half):
+        first = op["halves"][0]
+        return tuple(first["patterns"][first["q"]])
+
+
+class BurstReadAnswersTheNextRebuildList(Defective):
+    """a read of a burst answers the requests of the following write's rebuild list: the staged list is shared"""
+
+    def op_burst(self, op, pay):
+        ops, real_run = op["ops"], self.run
+
+        def run(sub, pz):
+            at = next(i for i, x in enumerate(ops) if x is sub)
+            nxt = ops[at + 1] if at + 1 < len(ops) else None
+            if sub["op"] == "read" and nxt and nxt["op"] == "write" and nxt["form"] == "batch_set":
+                rebuilt = [w for w in nxt["writes"] if w % self.k in self.prepared_set[nxt["pattern_of"][w // self.k]]]
+                sub = dict(sub, reads=(rebuilt + sub["reads"][len(rebuilt):])[:len(sub["reads"])])
+            return real_run(sub, pz)
+        self.run = run
+        try:
+            return super().op_burst(op, pay)
+        finally:
+            del self.run
+
+
+class ParityFormStoresData(Defective):
+    """a parity form stores data: the window of an absent data block that only its caller may hold"""
+
+    def stores_data(self, form, absent):
+        return True if form in ("parity", "parity_set") else super().stores_data(form, absent)
+
+
+class TouchesAnIgnoredStripe(Defective):
+    """a _set form touches a stripe whose pattern_of entry it should have ignored (no write names it)"""
+
+    def op_write(self, op, pay):
+        out = super().op_write(op, pay)
+        if op.get("ignored") is not None:
+            self.p[op["ignored"], 0, 0] ^= np.uint32(1)
+        return out
+
+
+DEG_DEFECTS = [StoresIntoAnAbsentBlock, UpdatesAnAbsentParityBlock, OldRowFromThePool, ParityOneColumnTooWide, DataWindowShiftedRight,
+               OldRowsAtTheEarlierWidth, WritesUnderTheOldSet, BurstReadAnswersTheNextRebuildList, ParityFormStoresData, TouchesAnIgnoredStripe]
 EXT_DEFECTS = [CopiesLostBlocks, ReadsUnderTheOldPattern, ReadWritesPastItsRows, ReadWritesThePool, ShiftedSetLocation, PoolEncodeSkipsTheLastStripe,
                BurstReadSeesTheOldPool]
 DEFECTS = [SkipsAParityBlock, TouchesAnotherStripe, ShiftedPatterns, RewritesAbsentBlocks, ReadsQuarantined, SetClobbersPrepared, StaleChunking]
 DEFECT_CONFIGS = ("20_16_s64_fixed", "20_16_s64_rotated", "64_32_rotated", "32_8_fixed")
 
 
-@pytest.mark.parametrize("defect", DEFECTS + EXT_DEFECTS, ids=[d.__name__ for d in DEFECTS + EXT_DEFECTS])
+@pytest.mark.parametrize("defect", DEFECTS + EXT_DEFECTS + DEG_DEFECTS, ids=[d.__name__ for d in DEFECTS + EXT_DEFECTS + DEG_DEFECTS])
 def test_injected_defect_is_reported_at_its_step(oracle, defect):
     caught = 0
     extended = defect in EXT_DEFECTS  # a defect of the extended operations is looked for in the extended sequences
-    for name, seed in itertools.product(DEFECT_CONFIGS, pm.EXT_SEEDS if extended else pm.SEEDS):
+    degraded = defect in DEG_DEFECTS  # ... one of the degraded and window writes in the degraded sequences
+    for name, seed in itertools.product(DEFECT_CONFIGS, pm.DEG_SEEDS if degraded else pm.EXT_SEEDS if extended else pm.SEEDS):
         cfg = pm.config_named(name)
         backend = defect(cfg, oracle)
         try:
-            pm.run_sequence(backend, cfg, seed, oracle=oracle, extended=extended)
+            pm.run_sequence(backend, cfg, seed, oracle=oracle, extended=extended, degraded=degraded)
         except pm.SequenceFailure as e:
             assert backend.fired == e.step, (name, seed, backend.fired, e.step)
             text = str(e)
             assert cfg.name in text and "seed %d" % seed in text and "step %d" % e.step in text
             assert len(e.log) == e.step + 1 and all(line in text for line in e.log)  # the operation log up to that step
             assert "steps=%d" % (e.step + 1) in text                                   # ... and how to replay it
+            assert ("degraded=True" in text) == degraded and ("extended=True" in text) == extended  # ... under the flag of its family
             caught += 1
         else:
             assert backend.fired is None, (name, seed, backend.fired)  # the defect changed something and no step noticed
