@@ -23,6 +23,7 @@ CODE_MIXED_RADIX = 1  # fastecc_create_ex flag: transform order q * 2^m, q in {1
 CODE_MIXED_RADIX_PFA = 4  # ... and the composite q = 21, 35, 39, 45, 63, 65, 91, 105, 117 (prime-factor map)
 CODE_TOP_RADIX2 = 2  # fastecc_create_ex flag (A/B experiment): the top level of a power-of-two transform through the fused odd-radix kernel
 
+WRITE_NONE = 0xFFFFFFFFFFFFFFFF  # entry of a device write list (update_batch_device, update_parity_batch_device): the row is skipped
 PATTERN_NONE = 0xFFFFFFFF  # pattern_of entry of the set calls (decode_batch_set, repair_batch_set, verify_batch_set, correct_batch_set): the stripe is neither read nor written
 
 OK, E_INVAL, E_NOMEM, E_DEVICE, E_UNSUPPORTED, E_UNCORRECTABLE = 0, -1, -2, -3, -4, -5
@@ -139,6 +140,10 @@ def lib():
     L.fastecc_update_batch_set_window.restype = i32
     L.fastecc_update_parity_batch_set_window.argtypes = [vp, vp, u64, ctypes.POINTER(u32), u64p, u64, u64, u64, vp, vp, vp]
     L.fastecc_update_parity_batch_set_window.restype = i32
+    L.fastecc_update_batch_device.argtypes = [vp, vp, vp, u64, vp, u64, u32, u64, u64, vp, vp, vp]
+    L.fastecc_update_batch_device.restype = i32
+    L.fastecc_update_parity_batch_device.argtypes = [vp, vp, u64, vp, u64, u32, u64, u64, vp, vp, vp, vp]
+    L.fastecc_update_parity_batch_device.restype = i32
     L.fastecc_code_coefficient.argtypes = [u64, u64, ctypes.c_uint, u64, u64, ctypes.POINTER(u32)]
     L.fastecc_code_coefficient.restype = i32
     L.fastecc_gf_berlekamp_massey.argtypes = [ctypes.POINTER(u32), u32, ctypes.POINTER(u32), u32]
@@ -686,6 +691,37 @@ class Encoder:
         else:
             _check(lib().fastecc_update_parity_batch_window(self._h, _addr(parity), count, arr, n, window[0], window[1], _addr(old), _addr(new),
                                                             stream or None), "fastecc_update_parity_batch_window")
+        return parity
+
+    def _device_list(self, count, n_writes, max_per_stripe, col0, width):
+        """the checked (count, n_writes, max_per_stripe, col0, width) of a device-list call; the window as the window methods check it"""
+        count = self._batch_count(count)
+        for name, v in (("n_writes", n_writes), ("max_per_stripe", max_per_stripe)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise TypeError(name + " must be an int")
+        if n_writes < 0 or n_writes >= 1 << 64:
+            raise ValueError("n_writes must be in [0, 2^64)")
+        if max_per_stripe < 1 or max_per_stripe > 16:
+            raise ValueError("max_per_stripe must be in [1, 16]")
+        col0, width = self._read_window(col0, width)
+        return count, n_writes, max_per_stripe, col0, width
+
+    def update_batch_device(self, data, parity, count, writes, n_writes, new, status, max_per_stripe=1, stream=0, col0=0, width=None):
+        """update_batch with the write list in DEVICE memory: `writes` (a device tensor or address, uint64 entries, 8-byte aligned) holds n_writes
+        entries b * k + i or WRITE_NONE (the row is skipped), read when the call's kernels run on `stream`, never by the host.  `status` (one
+        uint64 of device memory) is set by the call on the stream: 0 when the list was applied, else (error code as uint32) << 32 | one row at
+        fault, and then no word of the pool has been written.  max_per_stripe (1 .. 16) is the caller's promise about the writes one stripe gets.
+        col0, width (words; width=None: from col0 to the end of the block) as for update_batch; rows of `new` hold `width` words."""
+        count, n_writes, max_per_stripe, col0, width = self._device_list(count, n_writes, max_per_stripe, col0, width)
+        _check(lib().fastecc_update_batch_device(self._h, _addr(data), _addr(parity), count, _addr(writes), n_writes, max_per_stripe, col0, width,
+                                                 _addr(new), _addr(status), stream or None), "fastecc_update_batch_device")
+        return data, parity
+
+    def update_parity_batch_device(self, parity, count, writes, n_writes, new, status, old=None, max_per_stripe=1, stream=0, col0=0, width=None):
+        """update_batch_device for the parity alone: the blocks changed from row u of `old` (None: from zero) to row u of `new`."""
+        count, n_writes, max_per_stripe, col0, width = self._device_list(count, n_writes, max_per_stripe, col0, width)
+        _check(lib().fastecc_update_parity_batch_device(self._h, _addr(parity), count, _addr(writes), n_writes, max_per_stripe, col0, width,
+                                                        _addr(old), _addr(new), _addr(status), stream or None), "fastecc_update_parity_batch_device")
         return parity
 
     def update_batch_set(self, data, parity, count, pattern_of, writes, new, stream=0, col0=0, width=None):

@@ -44,6 +44,12 @@
 //   update_window_kernel        : update_set_kernel with the lane's columns counted from the window, for the set forms and the plain ones alike (a call
 //                                 without a pattern set gives every stripe a row that loses nothing); no word outside the window is loaded or stored;
 //   update_window_scatter_kernel: row u into the window of its present data block.
+//
+// The write list in device memory (fastecc_update_batch_device / _update_parity_batch_device): no host code looks at the list.
+// update_device_run enqueues the reset of the per-stripe counters and the caller's status word, three kernels that build the records and the
+// segment tables in the window form's formats (device_count_kernel, device_fill_kernel, device_segments_kernel), update_window_device_kernel per
+// admitted length class — update_window_kernel's wave behind a look at the status and at the class's real segment count — and
+// update_device_scatter_kernel straight from the caller's list.
 #include <algorithm>
 #include <atomic>
 #include <vector>
@@ -518,13 +524,16 @@ struct WindowArgs {
 // the new rows and the old rows outside the pool sit at pitch `width`, and the parity blocks are addressed through descriptors of width * 4 bytes
 // whose bases are S words apart: no word outside the window is loaded or stored.  Rows past the segment's length and dead lanes load from valid
 // addresses inside the window (row 0, column 0 of the window) without a branch.  All stripe offsets are 64-bit.
-template <int T, int V>
-__global__ __launch_bounds__(256) void update_window_kernel(const WindowArgs w)
+// The kernel's body is update_window_wave, shared with update_window_device_kernel (below), which learns on the device how many of its launch's
+// segments exist: admit(wave) says whether the wave has work (update_window_kernel: always).
+template <int T, int V, class Admit>
+__device__ __forceinline__ void update_window_wave(const WindowArgs& w, Admit admit)
 {
     const BatchArgs& a = w.s.b;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     if (wave >= a.waves) return;
+    if (!admit(wave)) return;  // (wave-uniform)
     const uint32_t slice = wave % a.slices, rest = wave / a.slices;
     const uint32_t q0 = (rest % a.runs) * a.run, q1 = min(q0 + a.run, a.M);
     const_u32_ptr seg = as_constant(a.segs) + (size_t)(rest / a.runs) * (SET_SEG_HEAD + T);
@@ -575,6 +584,12 @@ __global__ __launch_bounds__(256) void update_window_kernel(const WindowArgs w)
     const uint32_t q = present_from(q0);
     if (q >= q1) return;
     stream_parity<T, V>(x, a.parity + stripe * a.M * a.S, a.S, c, a.G, a.p, q, q1, [&](int i) { return seg[SET_SEG_HEAD + i]; }, present_from);
+}
+
+template <int T, int V>
+__global__ __launch_bounds__(256) void update_window_kernel(const WindowArgs w)
+{
+    update_window_wave<T, V>(w, [](uint32_t) { return true; });
 }
 
 struct WindowScatterArgs {
@@ -628,6 +643,191 @@ __global__ __launch_bounds__(256) void update_scatter_kernel(const ScatterArgs a
     store_vec<V>(a.data + (stripe * a.K + (wr[0] >> a.e)) * a.S + col, t);
 }
 
+// ---- the write list in device memory (fastecc_update_batch_device / _update_parity_batch_device) ----
+// The host never reads the list, so what update_batch_run builds on the host — the list's records and the segment tables of update_window_kernel — is
+// built by three kernels on the stream, without a sort:
+//   device_count_kernel   : lane u takes slot = cnt[stripe]++ of its write (cnt is zeroed by the call); the lane that draws slot 0 gives the stripe its
+//                           segment number, from one counter;
+//   device_fill_kernel    : lane u writes its record (SET_LIST_WORDS) at seg_of[stripe] * max_per_stripe + slot;
+//   device_segments_kernel: lane per segment: its length cnt[stripe], the pairwise duplicate check, and its record (SET_SEG_HEAD + T) in the table of
+//                           its length class, at a slot from that class's counter.
+// Kernel boundaries order the three and the parity launches behind them; nothing waits inside a kernel.  The counters that many lanes draw from (one
+// for the segments, five for the classes) take ONE atomic per workgroup: ballot and mbcnt inside a wave, LDS between the four waves.  A fault of the
+// list goes into the caller's status word — the first compare-and-swap from 0 wins — and every later kernel of the call returns when it is non-zero,
+// so a refused list writes no word of the pool.  The order of a stripe's records depends on atomic arrival; the parity does not (exact 96-bit sums).
+constexpr uint32_t DEVICE_COUNTERS = 8;             // behind cnt[count]: [0] segments, [1 + c] segments of class c (T = 1 << c); zeroed with cnt
+constexpr uint64_t DEVICE_MAX = 1ull << 24;         // stripes of a pool and entries of a list the device form takes
+constexpr uint64_t WRITE_NONE = FASTECC_WRITE_NONE;
+
+struct DeviceListArgs {
+    const uint64_t* writes;
+    unsigned long long* status;
+    uint32_t* cnt;        // [count] writes per stripe, then the DEVICE_COUNTERS
+    uint32_t* counters;   // cnt + count
+    uint32_t* seg_of;     // [count] the stripe's segment (stripes with a write)
+    uint32_t* stripe_of;  // [segments] and back
+    uint32_t* slot_of;    // [n] the slot lane u drew (>= mps: no record)
+    uint32_t* records;    // [segments][mps] x SET_LIST_WORDS
+    uint32_t* tables;     // the five class tables, class c at table_off[c], SET_SEG_HEAD + (1 << c) words a segment
+    uint64_t n, limit, K;  // entries of the list; count * K
+    uint64_t S, col0, W;
+    uint32_t mps, e, with_data, small;  // small: count * K fits 32 bits
+    uint32_t table_off[5];
+};
+
+__device__ __forceinline__ void device_list_fail(unsigned long long* status, int code, uint64_t u)
+{
+    atomicCAS(status, 0ull, ((unsigned long long)(uint32_t)code << 32) | (uint32_t)u);
+}
+__device__ __forceinline__ uint32_t lanes_before(uint64_t mask)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+__device__ __forceinline__ uint64_t stripe_of_index(const DeviceListArgs& a, uint64_t idx)
+{
+    return a.small ? (uint64_t)((uint32_t)idx / (uint32_t)a.K) : idx / a.K;
+}
+
+__global__ __launch_bounds__(256) void device_count_kernel(const DeviceListArgs a)
+{
+    __shared__ uint32_t wave_sum[4], block_base;
+    const uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    bool first = false;
+    uint32_t b = 0;
+    if (u < a.n) {
+        uint32_t slot = 0xFFFFFFFFu;
+        const uint64_t idx = a.writes[u];
+        if (idx != WRITE_NONE) {
+            if (idx >= a.limit) {
+                device_list_fail(a.status, FASTECC_E_INVAL, u);
+            } else {
+                b = (uint32_t)stripe_of_index(a, idx);
+                slot = atomicAdd(&a.cnt[b], 1u);
+                if (slot >= a.mps) device_list_fail(a.status, FASTECC_E_UNSUPPORTED, u);
+                first = slot == 0;
+            }
+        }
+        a.slot_of[u] = slot;
+    }
+    const uint64_t firsts = __ballot(first);
+    if (lane == 0) wave_sum[wave] = (uint32_t)__popcll(firsts);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t total = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+        block_base = total ? atomicAdd(&a.counters[0], total) : 0u;
+    }
+    __syncthreads();
+    if (!first) return;
+    uint32_t seg = block_base + lanes_before(firsts);
+    for (uint32_t w = 0; w < wave; ++w) seg += wave_sum[w];
+    a.seg_of[b] = seg;  // (seg < min(count, n): one per stripe with a write)
+    a.stripe_of[seg] = b;
+}
+
+__global__ __launch_bounds__(256) void device_fill_kernel(const DeviceListArgs a)
+{
+    const uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= a.n) return;
+    const uint32_t slot = a.slot_of[u];
+    if (slot >= a.mps) return;  // FASTECC_WRITE_NONE, an index out of range, or one write too many for its stripe: no record (the status is set)
+    const uint64_t idx = a.writes[u];
+    const uint64_t b = stripe_of_index(a, idx);
+    const uint64_t off = a.with_data ? idx * a.S + a.col0 : u * a.W;  // the old row from old_base, as update_batch_run's long form
+    uint32_t* wr = a.records + ((uint64_t)a.seg_of[b] * a.mps + slot) * SET_LIST_WORDS;
+    wr[0] = (uint32_t)((idx - b * a.K) << a.e);
+    wr[1] = (uint32_t)u;
+    wr[2] = (uint32_t)b;
+    wr[3] = 0;  // (b < DEVICE_MAX)
+    wr[LIST_WORDS] = (uint32_t)off;
+    wr[LIST_WORDS + 1] = (uint32_t)(off >> 32);
+}
+
+__global__ __launch_bounds__(256) void device_segments_kernel(const DeviceListArgs a)
+{
+    __shared__ uint32_t wave_sum[5][4], block_base[5];
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    bool live = *a.status == 0ull && g < a.counters[0];  // (a list refused by device_count_kernel: nothing to build)
+    uint32_t len = 0, cls = 0;
+    const uint32_t* rec = a.records + (uint64_t)g * a.mps * SET_LIST_WORDS;
+    if (live) {
+        len = a.cnt[a.stripe_of[g]];  // (1 .. mps: the status is 0)
+        for (uint32_t j = 1; j < len && live; ++j)
+            for (uint32_t i = 0; i < j; ++i)
+                if (rec[i * SET_LIST_WORDS] == rec[j * SET_LIST_WORDS]) {  // two writes to one block
+                    device_list_fail(a.status, FASTECC_E_INVAL, rec[j * SET_LIST_WORDS + 1]);
+                    live = false;
+                    break;
+                }
+        while ((1u << cls) < len) cls++;
+    }
+    uint32_t before = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < 5; ++c) {
+        const uint64_t m = __ballot(live && cls == c);
+        if (lane == 0) wave_sum[c][wave] = (uint32_t)__popcll(m);
+        if (cls == c) before = lanes_before(m);
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        const uint32_t c = threadIdx.x, total = wave_sum[c][0] + wave_sum[c][1] + wave_sum[c][2] + wave_sum[c][3];
+        block_base[c] = total ? atomicAdd(&a.counters[1 + c], total) : 0u;
+    }
+    __syncthreads();
+    if (!live) return;
+    uint32_t slot = block_base[cls] + before;
+    for (uint32_t w = 0; w < wave; ++w) slot += wave_sum[cls][w];
+    const uint32_t T = 1u << cls;
+    const uint32_t off = cls == 0 ? a.table_off[0] : cls == 1 ? a.table_off[1] : cls == 2 ? a.table_off[2] : cls == 3 ? a.table_off[3] : a.table_off[4];
+    uint32_t* seg = a.tables + off + (uint64_t)slot * (SET_SEG_HEAD + T);  // (slot < the class's bound: segments of class T > 1 hold more than T / 2 writes)
+    seg[0] = g * a.mps;
+    seg[1] = len;
+    seg[SEG_HEAD] = 0;  // the one row of UpdateState::d_lost_none
+    for (uint32_t r = 0; r < T; ++r) seg[SET_SEG_HEAD + r] = rec[(r < len ? r : 0) * SET_LIST_WORDS];
+}
+
+// update_window_kernel for segment tables built on the device: the launch is sized from the host's upper bound on its class's segments, and the wave
+// reads the status and the class's real count (scalar loads) before anything else.  seg0: the launch's first segment in the class's table.
+template <int T, int V>
+__global__ __launch_bounds__(256) void update_window_device_kernel(const WindowArgs w, const uint32_t* status, const uint32_t* built, const uint32_t seg0)
+{
+    update_window_wave<T, V>(w, [&](uint32_t wave) {
+        const_u32_ptr st = as_constant(status);
+        if ((st[0] | st[1]) != 0) return false;  // a refused list: all or nothing
+        return seg0 + wave / w.s.b.slices / w.s.b.runs < as_constant(built)[0];
+    });
+}
+
+struct DeviceScatterArgs {
+    uint32_t* data;  // the pool's data shifted by col0 words
+    const uint32_t* new_blocks;
+    const uint32_t* writes;  // the launch's first entry (two words each)
+    const uint32_t* status;
+    uint64_t S, width;
+    uint32_t slices, waves, row0;  // row0: the row of the launch's first entry
+};
+
+// update_window_scatter_kernel straight from the caller's list: wave (entry u, column slice)
+template <int V>
+__global__ __launch_bounds__(256) void update_device_scatter_kernel(const DeviceScatterArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (wave >= a.waves) return;
+    const_u32_ptr st = as_constant(a.status);
+    if ((st[0] | st[1]) != 0) return;
+    const uint32_t u = wave / a.slices;
+    const_u32_ptr wr = as_constant(a.writes) + (size_t)u * 2;
+    const uint64_t idx = ((uint64_t)wr[1] << 32) | wr[0];
+    if (idx == WRITE_NONE) return;  // (every other entry is < count * K: the status is 0)
+    const uint64_t col = ((uint64_t)(wave % a.slices) * 64u + lane) * V;
+    if (col >= a.width) return;
+    uint32_t t[V];
+    load_vec<V>(t, a.new_blocks + (uint64_t)(a.row0 + u) * a.width + col);
+    store_vec<V>(a.data + idx * a.S + col, t);
+}
+
 }  // namespace
 
 struct UpdateState {
@@ -644,8 +844,10 @@ struct UpdateState {
     // fastecc_update_batch_set: the old rows of one call's absent written blocks, S words each, rebuilt by direct_run_read (an internal buffer)
     DeviceBuf<uint32_t> d_recon;
     // the window calls: such rows at `width` words each; and one row of SET_LOST_ROW words that loses nothing, for the calls without a pattern set
-    // (written once, by a synchronous copy at the first window call of the context)
+    // (written once, by a synchronous copy at the first window or device-list call of the context: lost_none_row)
     DeviceBuf<uint32_t> d_lost_none;
+    // the device-list calls (DeviceListArgs): what the three build kernels write and the parity launches read, grown on demand (internal buffers)
+    DeviceBuf<uint32_t> dl_cnt, dl_seg_of, dl_stripe_of, dl_slot_of, dl_records, dl_tables;
 };
 
 void destroy_update_state(UpdateState* s) { delete s; }
@@ -934,6 +1136,20 @@ struct Window {
     uint64_t col0 = 0, width = 0;
 };
 
+// UpdateState::d_lost_none, written once by a synchronous copy at the first call of the context that needs it
+int lost_none_row(UpdateState* s)
+{
+    if (s->d_lost_none) return FASTECC_OK;
+    const std::vector<uint32_t> none(SET_LOST_ROW, SET_LOST_END);
+    RC_TRY(s->d_lost_none.alloc(none.size()));
+    const hipError_t e = hipMemcpy(s->d_lost_none, none.data(), none.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        s->d_lost_none.reset();  // (the next call tries again)
+        return hip_fail(e, "hipMemcpy");
+    }
+    return FASTECC_OK;
+}
+
 // sw: the call's writes, sorted and checked.  data == null: the parity form.  set != null: stripes with absent blocks (update_set_kernel; with data, first
 // the old rows of the absent written blocks into the reconstruction buffer, and at the end only present blocks are stored).  A window (win.width != 0):
 // update_window_kernel and update_window_scatter_kernel for either form, with the list and the segments in the set form's formats, the caller's rows and
@@ -955,15 +1171,7 @@ int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std
     const int V = window ? lane_words(S, col0, W, pointers) : lane_words(S, pointers);
     const uint64_t slices = (W + 64u * V - 1) / (64u * V);
     if (slices * M > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (one segment's waves fit a launch)
-    if (window && !set && !s->d_lost_none) {  // (the whole-block calls never read it)
-        const std::vector<uint32_t> none(SET_LOST_ROW, SET_LOST_END);
-        RC_TRY(s->d_lost_none.alloc(none.size()));
-        const hipError_t e = hipMemcpy(s->d_lost_none, none.data(), none.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            s->d_lost_none.reset();  // (the next call tries again)
-            return hip_fail(e, "hipMemcpy");
-        }
-    }
+    if (window && !set) RC_TRY(lost_none_row(s));  // (the whole-block calls never read it)
     const auto wait_buffers = [&]() -> int {  // the host-side wait for the kernels that read an internal buffer about to be replaced
         if (c->buf_used) HIP_TRY(hipEventSynchronize(c->buf_event));
         return FASTECC_OK;
@@ -1224,6 +1432,171 @@ int update_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
                &set, win);
 }
 
+// ---- the write list in device memory (fastecc_update_batch_device / _update_parity_batch_device) ----
+// Everything on `st`, nothing read back: the reset of the per-stripe counters and of *status, the three build kernels, one launch of
+// update_window_device_kernel per admitted length class — sized from the host's upper bound on that class's segments: a segment of class T > 1 holds
+// more than T / 2 of the list's n entries — and, with a data pool, the scatter after the last of them (section 15: waves of the parity launches
+// read the old rows).  The scratch grows on demand behind the host-side wait for the kernels that read it; a steady-state call allocates nothing,
+// copies nothing and waits for nothing.
+int update_device_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, uint64_t count, const uint64_t* writes, uint64_t n, uint32_t mps, const Window win,
+                      const uint32_t* old_blocks, const uint32_t* new_blocks, uint64_t* status, hipStream_t st)
+{
+    UpdateState* s = nullptr;
+    RC_TRY(update_state(c, &s));
+    const uint64_t S = c->S, K = c->K, M = c->Mu, W = win.width, col0 = win.col0;
+    const uintptr_t pointers = (uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks;
+    const int V = lane_words(S, col0, W, pointers);
+    const uint64_t slices = (W + 64u * V - 1) / (64u * V);
+    if (slices * M > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (one segment's waves fit a launch)
+    RC_TRY(lost_none_row(s));
+    // upper bounds: segments in all (one per touched stripe), and per admitted class
+    const uint64_t segs_max = std::min(count, n);
+    uint64_t bound[5] = {}, table_words = 0;
+    DeviceListArgs la{};
+    for (int cl = 0; cl < 5 && (cl == 0 || (1u << (cl - 1)) < mps); cl++) {
+        const uint64_t T = 1ull << cl;
+        bound[cl] = cl == 0 ? segs_max : std::min(count, n / (T / 2 + 1));
+        la.table_off[cl] = (uint32_t)table_words;
+        table_words += bound[cl] * (SET_SEG_HEAD + T);  // (n <= DEVICE_MAX: under 14 n words)
+    }
+    const auto wait_buffers = [&]() -> int {  // the host-side wait for the kernels that read an internal buffer about to be replaced
+        if (c->buf_used) HIP_TRY(hipEventSynchronize(c->buf_event));
+        return FASTECC_OK;
+    };
+    const auto room = [&](DeviceBuf<uint32_t>& buf, uint64_t words) -> int {
+        if (words <= buf.capacity()) return FASTECC_OK;
+        RC_TRY(wait_buffers());
+        return buf.grow(std::max<uint64_t>(words, 2 * buf.capacity()));  // FASTECC_E_NOMEM: it does not fit
+    };
+    RC_TRY(room(s->dl_cnt, count + DEVICE_COUNTERS));
+    RC_TRY(room(s->dl_seg_of, count));
+    RC_TRY(room(s->dl_stripe_of, segs_max));
+    RC_TRY(room(s->dl_slot_of, n));
+    RC_TRY(room(s->dl_records, segs_max * mps * SET_LIST_WORDS));  // (under 2^32 words: DEVICE_MAX x ROWS x SET_LIST_WORDS)
+    RC_TRY(room(s->dl_tables, table_words));
+    RC_TRY(update_table(c, s, st));
+    return with_internal_buffers(c, st, [&]() -> int {
+        la.writes = writes;
+        la.status = (unsigned long long*)status;
+        la.cnt = s->dl_cnt;
+        la.counters = s->dl_cnt + count;
+        la.seg_of = s->dl_seg_of;
+        la.stripe_of = s->dl_stripe_of;
+        la.slot_of = s->dl_slot_of;
+        la.records = s->dl_records;
+        la.tables = s->dl_tables;
+        la.n = n;
+        la.limit = count * K;  // (fits: update_batch_args)
+        la.K = K;
+        la.S = S;
+        la.col0 = col0;
+        la.W = W;
+        la.mps = mps;
+        la.e = (uint32_t)s->g.e;
+        la.with_data = data ? 1u : 0u;
+        la.small = la.limit <= 0xFFFFFFFFull ? 1u : 0u;
+        {
+            ProfScope ps(c, st, "update_device_build", (count + DEVICE_COUNTERS) * 4 + n * (8 + 8 + SET_LIST_WORDS * 4));
+            HIP_TRY(hipMemsetAsync(s->dl_cnt, 0, (count + DEVICE_COUNTERS) * 4, st));
+            HIP_TRY(hipMemsetAsync(status, 0, 8, st));
+            const dim3 per_entry((unsigned)((n + 255) / 256)), per_segment((unsigned)((segs_max + 255) / 256));
+            hipLaunchKernelGGL(device_count_kernel, per_entry, dim3(256), 0, st, la);
+            hipLaunchKernelGGL(device_fill_kernel, per_entry, dim3(256), 0, st, la);
+            hipLaunchKernelGGL(device_segments_kernel, per_segment, dim3(256), 0, st, la);
+            HIP_TRY(hipGetLastError());
+        }
+        WindowArgs wa{};
+        SetArgs& sa = wa.s;
+        BatchArgs& a = sa.b;
+        a.parity = parity + col0;
+        a.data = data;
+        a.old_blocks = old_blocks;
+        a.new_blocks = new_blocks;
+        a.G = s->d_G;
+        a.list = s->dl_records;
+        a.S = S;
+        a.K = K;
+        a.M = (uint32_t)M;
+        a.slices = (uint32_t)slices;
+        a.e = (uint32_t)s->g.e;
+        set_positions(s, a.p);
+        sa.old_base = data ? data : old_blocks ? old_blocks : new_blocks;
+        sa.lost = s->d_lost_none.get();
+        wa.width = W;
+        {
+            ProfScope ps(c, st, "update_device", n * M * W * 8);  // (every entry a write)
+            for (int cl = 0; cl < 5; cl++) {
+                if (!bound[cl]) continue;
+                const int T = 1 << cl;
+                const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(KERNEL_WINDOW, T, V);
+                const uint64_t per_run = bound[cl] * slices;
+                const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>(M, (target + per_run - 1) / per_run));
+                a.run = (uint32_t)((M + want - 1) / want);
+                a.runs = (uint32_t)((M + a.run - 1) / a.run);
+                const uint64_t seg_waves = slices * a.runs, launch_segs = LAUNCH_WAVES / seg_waves;
+                for (uint64_t s0 = 0; s0 < bound[cl]; s0 += launch_segs) {
+                    const uint64_t waves = std::min<uint64_t>(launch_segs, bound[cl] - s0) * seg_waves;
+                    a.segs = s->dl_tables + la.table_off[cl] + (size_t)s0 * (SET_SEG_HEAD + T);
+                    a.waves = (uint32_t)waves;
+                    const dim3 grid((unsigned)((waves + 3) / 4));
+                    with_class(T, V, [&](auto t_c, auto v_c) {
+                        constexpr int Tc = t_c, Vc = v_c;
+                        hipLaunchKernelGGL((update_window_device_kernel<Tc, Vc>), grid, dim3(256), 0, st, wa, (const uint32_t*)status,
+                                           (const uint32_t*)(la.counters + 1 + cl), (uint32_t)s0);
+                    });
+                    HIP_TRY(hipGetLastError());
+                }
+            }
+        }
+        if (data) {
+            DeviceScatterArgs ca{data + col0, new_blocks, nullptr, (const uint32_t*)status, S, W, (uint32_t)slices, 0, 0};
+            const uint64_t launch_writes = LAUNCH_WAVES / slices;
+            ProfScope ps(c, st, "update_device_scatter", n * W * 8);
+            for (uint64_t w0 = 0; w0 < n; w0 += launch_writes) {
+                const uint64_t waves = std::min<uint64_t>(launch_writes, n - w0) * slices;
+                ca.writes = (const uint32_t*)(writes + w0);
+                ca.row0 = (uint32_t)w0;
+                ca.waves = (uint32_t)waves;
+                const dim3 grid((unsigned)((waves + 3) / 4));
+                with_words<1>(V, [&](auto, auto v_c) { hipLaunchKernelGGL(update_device_scatter_kernel<decltype(v_c)::value>, grid, dim3(256), 0, st, ca); });
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        return FASTECC_OK;
+    });
+}
+
+// What the host can decide without the list; then update_device_run.  col0_width: the window {col0_words, width_words}.
+int update_batch_device_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint64_t* writes, uint64_t n_writes, uint32_t max_per_stripe,
+                             const uint64_t* col0_width, const void* old_blocks, const void* new_blocks, uint64_t* status, void* stream, bool with_data)
+{
+    RC_TRY(update_batch_args(c, data, parity, count, writes, n_writes, old_blocks, new_blocks, with_data));
+    if (!status || max_per_stripe < 1 || max_per_stripe > (uint32_t)ROWS) return FASTECC_E_INVAL;
+    if ((((uintptr_t)writes | (uintptr_t)status) & 7u) != 0) return FASTECC_E_INVAL;
+    if (count > DEVICE_MAX || n_writes > DEVICE_MAX) return FASTECC_E_UNSUPPORTED;  // (the counters reset by every call: 4 bytes per stripe)
+    Window win;
+    RC_TRY(window_args(c, data, parity, count, n_writes, old_blocks, new_blocks, with_data, col0_width, &win));
+    // the list and the status word against the pool, the rows and each other (n_writes <= DEVICE_MAX: no product wraps)
+    const auto hits = [](const void* p, uint64_t pbytes, const void* q, uint64_t qbytes) {
+        const uint64_t p0 = (uint64_t)(uintptr_t)p, q0 = (uint64_t)(uintptr_t)q;
+        return p && q && pbytes && qbytes && p0 < q0 + qbytes && q0 < p0 + pbytes;
+    };
+    const uint64_t rows_bytes = n_writes * win.width * 4;  // (fits: window_args has walked them)
+    if (rows_overlap_pool(c, data, parity, count, with_data, writes, n_writes, 8) || rows_overlap_pool(c, data, parity, count, with_data, status, 1, 8) ||
+        hits(writes, n_writes * 8, new_blocks, rows_bytes) || hits(writes, n_writes * 8, old_blocks, rows_bytes) || hits(status, 8, new_blocks, rows_bytes) ||
+        hits(status, 8, old_blocks, rows_bytes) || hits(status, 8, writes, n_writes * 8))
+        return FASTECC_E_INVAL;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    CallLock lk(c->mu);
+    if (n_writes == 0) {
+        HIP_TRY(hipMemsetAsync(status, 0, 8, (hipStream_t)stream));
+        return FASTECC_OK;
+    }
+    return update_device_run(c, with_data ? (uint32_t*)data : nullptr, (uint32_t*)parity, count, writes, n_writes, max_per_stripe, win,
+                             (const uint32_t*)old_blocks, (const uint32_t*)new_blocks, status, (hipStream_t)stream);
+}
+
 }  // namespace
 
 }  // namespace fastecc
@@ -1307,6 +1680,25 @@ int fastecc_update_parity_batch_set_window(fastecc_ctx* c, void* parity, uint64_
     const uint64_t win[2] = {col0_words, width_words};
     return guarded(
         [&]() -> int { return update_batch_set_impl(c, nullptr, parity, count, pattern_of, writes, n_writes, old_blocks, new_blocks, stream, false, win); });
+}
+
+int fastecc_update_batch_device(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint64_t* writes, uint64_t n_writes, uint32_t max_per_stripe,
+                                uint64_t col0_words, uint64_t width_words, const void* new_blocks, uint64_t* status, void* stream)
+{
+    const uint64_t win[2] = {col0_words, width_words};
+    return guarded([&]() -> int {
+        return update_batch_device_impl(c, data, parity, count, writes, n_writes, max_per_stripe, win, nullptr, new_blocks, status, stream, true);
+    });
+}
+
+int fastecc_update_parity_batch_device(fastecc_ctx* c, void* parity, uint64_t count, const uint64_t* writes, uint64_t n_writes, uint32_t max_per_stripe,
+                                       uint64_t col0_words, uint64_t width_words, const void* old_blocks, const void* new_blocks, uint64_t* status,
+                                       void* stream)
+{
+    const uint64_t win[2] = {col0_words, width_words};
+    return guarded([&]() -> int {
+        return update_batch_device_impl(c, nullptr, parity, count, writes, n_writes, max_per_stripe, win, old_blocks, new_blocks, status, stream, false);
+    });
 }
 
 int fastecc_code_coefficient(uint64_t n, uint64_t k, unsigned flags, uint64_t data_block, uint64_t parity_block, uint32_t* out)

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 440 /* 0.4.4: fastecc_gf61_update, fastecc_gf61_update_parity, fastecc_gf61_code_coefficient (small writes over the 64-bit field) */
+#define FASTECC_VERSION 450 /* 0.4.5: fastecc_update_batch_device, fastecc_update_parity_batch_device (pool writes from a write list in device memory) */
 
 enum {
     FASTECC_OK = 0,
@@ -814,6 +814,44 @@ int fastecc_update_batch_set_window(fastecc_ctx *ctx, void *data, void *parity, 
 int fastecc_update_parity_batch_set_window(fastecc_ctx *ctx, void *parity, uint64_t count, const uint32_t *pattern_of, const uint64_t *writes,
                                            uint64_t n_writes, uint64_t col0_words, uint64_t width_words, const void *old_blocks,
                                            const void *new_blocks, void *stream);
+/*
+ * Pool writes from a write list in DEVICE memory: fastecc_update_batch_window / fastecc_update_parity_batch_window with `writes` produced on the
+ * GPU (a storage stack that batches there, a previous kernel) and no host work in the loop.  The host never dereferences `writes` or `status`.
+ *   writes  : n_writes entries of device memory, 8-byte aligned.  writes[u] = b*k + i and row u of new_blocks / old_blocks (pitch width_words) mean
+ *             what they mean for the window calls above; col0_words = 0 and width_words = block_bytes / 4 is the whole block and leaves the bytes of
+ *             fastecc_update_batch / fastecc_update_parity_batch.  Every entry that is not FASTECC_WRITE_NONE is a write; n_writes is the list's
+ *             capacity, and a device-side producer pads a shorter list with FASTECC_WRITE_NONE (row u of such an entry is not read).  The list is
+ *             read when the call's kernels run, in stream order, not when the call is made.
+ *   max_per_stripe : the caller's promise about how many writes one stripe gets in this call, 1 to 16 (16 is the pass size of fastecc_update).
+ *             It selects the launches: one per padded segment length 1, 2, 4, 8, 16 up to the promise rounded up to a power of two — with the usual
+ *             promise of 1 the parity work is ONE launch.  The device form has no rounds: a burst with more than 16 writes to one stripe goes
+ *             through the host-list calls (fastecc_update_batch and friends) or a re-encode (fastecc_encode_pool).
+ *   status  : one uint64 of device memory, 8-byte aligned, set by the call on `stream`: 0 when the list was applied.  Otherwise the high 32 bits
+ *             hold the error code as (uint32_t)code and the low 32 bits one row u that is at fault (any one of them: the first compare-and-swap
+ *             from 0 wins).  FASTECC_E_INVAL: an index >= count*k, or two writes to the same block.  FASTECC_E_UNSUPPORTED: a stripe with more than
+ *             max_per_stripe writes.  All or nothing: when status is non-zero, no word of the pool has been written by the call.
+ * The return value covers only what the host can decide without the list, before any device work and with nothing written: everything
+ * fastecc_update_batch_window / fastecc_update_parity_batch_window refuse without looking at the list, with the same codes (a null context, count ==
+ * 0, null or misaligned pointers, byte sizes beyond 64 bits, a window outside the block, rows overlapping the pool; GF((2^61-1)^2), sharded contexts
+ * and a set "row_pitch_words" are FASTECC_E_UNSUPPORTED); FASTECC_E_INVAL for a null status, max_per_stripe outside 1 .. 16, and writes or status
+ * that are not 8-byte aligned or overlap the pool or the rows; FASTECC_E_UNSUPPORTED for count or n_writes above 2^24 (the per-stripe counters are
+ * reset by every call: 4 bytes per stripe).  n_writes == 0 is FASTECC_OK after those checks, with *status set to 0 on the stream.  FASTECC_OK
+ * otherwise means "enqueued": the list's own faults are reported through *status alone.
+ * Streams: in steady state — the same or a smaller n_writes, count and max_per_stripe than an earlier call on the context — a call makes no
+ * host-device copy and no allocation, waits on no event or stream and touches no pinned memory: it resets its counters and *status
+ * (hipMemsetAsync), launches and returns.  The first call and a growing call allocate the context's scratch and may wait, as
+ * fastecc_update_batch does.  hipGraph capture is not claimed.  There are no _set (degraded) forms of these two calls.
+ * Method: the segment tables of update_window_kernel are built by three kernels without a sort — a slot per write from a
+ * per-stripe counter, the records, the segments by length class — and the order of a stripe's writes inside its segment, which depends on atomic
+ * arrival, has no influence on the result: the sums are exact 96-bit integers reduced once, so any permutation of the list leaves the same bytes.
+ */
+#define FASTECC_WRITE_NONE UINT64_MAX /* writes[u] of the two calls below: row u is skipped */
+int fastecc_update_batch_device(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, const uint64_t *writes /* device */, uint64_t n_writes,
+                                uint32_t max_per_stripe, uint64_t col0_words, uint64_t width_words, const void *new_blocks,
+                                uint64_t *status /* device */, void *stream);
+int fastecc_update_parity_batch_device(fastecc_ctx *ctx, void *parity, uint64_t count, const uint64_t *writes /* device */, uint64_t n_writes,
+                                       uint32_t max_per_stripe, uint64_t col0_words, uint64_t width_words, const void *old_blocks /* may be NULL: zero */,
+                                       const void *new_blocks, uint64_t *status /* device */, void *stream);
 /* Host only, no device: the code's generator-matrix entry L_i(y_q) for data block i and parity block q of the (n,k) code that
  * fastecc_create_ex(n, k, ..., flags) builds over GF(0xFFF00001), plain form in [0,p): parity block q = sum_i L_i(y_q) data block i.
  * FASTECC_E_INVAL for a null out, an index out of range or unknown flags; FASTECC_E_UNSUPPORTED for a code fastecc_create_ex refuses. */
