@@ -24,6 +24,7 @@ CODE_MIXED_RADIX_PFA = 4  # ... and the composite q = 21, 35, 39, 45, 63, 65, 91
 CODE_TOP_RADIX2 = 2  # fastecc_create_ex flag (A/B experiment): the top level of a power-of-two transform through the fused odd-radix kernel
 
 WRITE_NONE = 0xFFFFFFFFFFFFFFFF  # entry of a device write list (update_batch_device, update_parity_batch_device): the row is skipped
+READ_NONE = 0xFFFFFFFFFFFFFFFF  # entry of a device request list (read_batch_set_device, read_batch_device): row u of out is left alone
 PATTERN_NONE = 0xFFFFFFFF  # pattern_of entry of the set calls (decode_batch_set, repair_batch_set, verify_batch_set, correct_batch_set): the stripe is neither read nor written
 
 OK, E_INVAL, E_NOMEM, E_DEVICE, E_UNSUPPORTED, E_UNCORRECTABLE = 0, -1, -2, -3, -4, -5
@@ -108,6 +109,8 @@ def lib():
     L.fastecc_read_batch_set.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u32), ctypes.POINTER(u64), u64, u64, u64, vp, vp]
     L.fastecc_read_batch_set.restype = i32
     L.fastecc_read_batch.argtypes, L.fastecc_read_batch.restype = [vp, vp, vp, u64, ctypes.POINTER(u64), u64, u64, u64, vp, vp], i32
+    L.fastecc_read_batch_set_device.argtypes, L.fastecc_read_batch_set_device.restype = [vp, vp, vp, u64, vp, vp, u64, u64, u64, vp, vp, vp], i32
+    L.fastecc_read_batch_device.argtypes, L.fastecc_read_batch_device.restype = [vp, vp, vp, u64, vp, u64, u64, u64, vp, vp, vp], i32
     L.fastecc_scrub_erasures.argtypes, L.fastecc_scrub_erasures.restype = [vp, u8p, u8p], i32
     L.fastecc_verify.argtypes, L.fastecc_verify.restype = [vp, vp, vp, i32, vp, u64, ctypes.POINTER(i32)], i32
     for name in ("locate_errors", "correct"):
@@ -462,6 +465,34 @@ class Encoder:
         n, keep_r, arr = self._read_list(reads)
         _check(lib().fastecc_read_batch(self._h, _addr(data), _addr(parity), count, arr, n, col0, width, _addr(out), stream or None), "fastecc_read_batch")
         del keep_r
+        return out
+
+    def _device_reads(self, count, n_reads, col0, width):
+        """the checked (count, n_reads, col0, width) of a device-list read; count and the window as _device_list checks them"""
+        count = self._batch_count(count)
+        if isinstance(n_reads, bool) or not isinstance(n_reads, int):
+            raise TypeError("n_reads must be an int")
+        if n_reads < 0 or n_reads >= 1 << 64:
+            raise ValueError("n_reads must be in [0, 2^64)")
+        col0, width = self._read_window(col0, width)
+        return count, n_reads, col0, width
+
+    def read_batch_set_device(self, data, parity, count, pattern_of, reads, n_reads, out, status, col0=0, width=None, stream=0):
+        """read_batch_set with the request list and pattern_of in DEVICE memory: `reads` (a device tensor or address, uint64 entries, 8-byte
+        aligned) holds n_reads entries b * k + i or READ_NONE (row u of `out` is left alone), `pattern_of` (uint32, `count` entries) the
+        pattern of every stripe; both are read when the call's kernels run on `stream`, never by the host.  `status` (one uint64 of device
+        memory) is set by the call on the stream: 0 when every request was served, else (error code as uint32) << 32 | one row at fault, and
+        then no word of `out` has been written.  col0, width (words; width=None: from col0 to the end of the block) as for read_batch_set."""
+        count, n_reads, col0, width = self._device_reads(count, n_reads, col0, width)
+        _check(lib().fastecc_read_batch_set_device(self._h, _addr(data), _addr(parity), count, _addr(pattern_of), _addr(reads), n_reads, col0, width,
+                                                   _addr(out), _addr(status), stream or None), "fastecc_read_batch_set_device")
+        return out
+
+    def read_batch_device(self, data, parity, count, reads, n_reads, out, status, col0=0, width=None, stream=0):
+        """read_batch_set_device with every stripe under the single decode_prepare pattern (direct-path patterns only)."""
+        count, n_reads, col0, width = self._device_reads(count, n_reads, col0, width)
+        _check(lib().fastecc_read_batch_device(self._h, _addr(data), _addr(parity), count, _addr(reads), n_reads, col0, width, _addr(out),
+                                               _addr(status), stream or None), "fastecc_read_batch_device")
         return out
 
     def scrub_erasures(self, data_present=None, parity_present=None):

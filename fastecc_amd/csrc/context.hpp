@@ -87,6 +87,7 @@ struct fastecc_ctx {
     DecodeState* decoder = nullptr;  // fastecc_decode_prepare: erasure pattern tables (decode_state.hpp; built by decode_prepare.hip, used by decode.hip)
     PatternSet* pattern_set = nullptr;  // fastecc_decode_prepare_set: a pattern per stripe (pattern_set.hip); independent of `decoder`
     StagedList<DirectReadEntry> read_list;  // fastecc_read_batch / _read_batch_set: one call's requests (pattern_set.hip); dev is an internal buffer
+    DeviceBuf<DirectReadEntry> read_entries;  // fastecc_read_batch_device / _read_batch_set_device: one call's entries, made on the device (an internal buffer)
     Sharded* sharded = nullptr;      // fastecc_create_sharded: the per-device contexts of the column slabs (sharded.hip); a
                                      // context that has it is only a shell around them
     p61::Decoder* decoder61 = nullptr;  // the same for FASTECC_FIELD_GF_P61_SQUARED (gf61_decode.hip)

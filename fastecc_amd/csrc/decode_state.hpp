@@ -48,6 +48,8 @@ struct FewLosses {
     PatternTables direct;
     DeviceBuf<DirectSetPass> read_desc;  // fastecc_read_batch: the descriptor of the pass that rebuilds the lost data, valid for pattern `read_desc_of` (lazy)
     uint64_t read_desc_of = ~0ull;
+    DeviceBuf<uint32_t> read_lost;       // fastecc_read_batch_device: HostStaging::lost_data (increasing, at most 256) of pattern `read_lost_of` (lazy)
+    uint64_t read_lost_of = ~0ull;
 };
 
 // The transform path's contexts and per-position tables.  The contexts, `recovered`, the tile order and the table buffers are built once per context by
@@ -171,6 +173,10 @@ struct PatternSet {
     std::vector<std::vector<uint32_t>> lost_parity;  // ... its lost parity blocks, increasing (fastecc_update_batch_set)
     DeviceBuf<DirectSetPass> d_passes;  // device: the descriptor table, entry q = pattern q's pass
     DeviceBuf<uint32_t> d_lost_parity;  // device: P + 1 rows of SET_LOST_ROW words, row q = lost_parity[q] padded with SET_LOST_END; row P loses nothing
+    // device, behind those rows in the same buffer (one upload): P rows of DIRECT_READ_LOST_ROW words, row q = lost_data[q] padded with SET_LOST_END —
+    // an empty row for a pattern that lost no data (fastecc_read_batch_set_device: read_translate_kernel)
+    const uint32_t* d_lost_data = nullptr;
+    uint32_t rows_max = 0;              // the most rows any of its passes reads
     // one call's entries, sorted by class (list.dev is an internal buffer: ordered between streams by the context's buf_event).  Outlives the set.
     StagedList<DirectSetEntry> list;
     DirectPass* pass(uint64_t q) const { return kind[q] == DATA ? tables[q].data.get() : kind[q] == PARITY ? tables[q].parity.get() : tables[q].both.get(); }

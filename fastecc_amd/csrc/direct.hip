@@ -1070,8 +1070,11 @@ struct ReadArgs {
 };
 using const_read_entry_ptr = const DirectReadEntry __attribute__((address_space(4)))*;
 
-template <int V>
-__global__ __launch_bounds__(256) void direct_read_kernel(const ReadArgs a)
+// One wave of a read launch.  admit(j), j the entry's output index (wave-uniform): false = the wave does nothing — the device-list form's look at the
+// status word and at DIRECT_READ_SKIP; direct_read_kernel admits every wave.  (`a` by value: through a reference the three instantiations of
+// direct_read_kernel took 3 to 4 more VGPRs than the kernel had with its body in place — DESIGN.md section 39.)
+template <int V, class Admit>
+__device__ __forceinline__ void direct_read_wave(const ReadArgs a, Admit admit)
 {
     constexpr int U = 8;  // rows in flight: U weights in SGPRs, U * V words in VGPRs
     const uint32_t lane = threadIdx.x & 63u;
@@ -1081,6 +1084,7 @@ __global__ __launch_bounds__(256) void direct_read_kernel(const ReadArgs a)
     const const_read_entry_ptr ent = (const_read_entry_ptr)(reinterpret_cast<uintptr_t>(a.entries)) + e;
     const uint64_t b = ent->stripe;
     const uint32_t j = ent->out;
+    if (!admit(j)) return;
     const uint32_t c = (cc * 64u + lane) * V;  // (32 bits: cc < waves_per_entry <= 2^24 and V <= 4)
     const bool live = c < a.width;             // (V divides width: a live lane's V words lie inside the window)
     uint32_t* dst = a.out + (a.row_base + e) * a.width + c;
@@ -1113,6 +1117,69 @@ __global__ __launch_bounds__(256) void direct_read_kernel(const ReadArgs a)
     }
 }
 
+template <int V>
+__global__ __launch_bounds__(256) void direct_read_kernel(const ReadArgs a)
+{
+    direct_read_wave<V>(a, [](uint32_t) { return true; });
+}
+
+// ---- the request list in device memory (fastecc_read_batch_device / _read_batch_set_device) ----
+// Two launches on the stream and nothing on the host: read_translate_kernel turns request u into entry u of the context's scratch list, and
+// direct_read_device_kernel is direct_read_kernel whose wave first reads the status word (a scalar load) and the entry's sentinel.  A fault found
+// by ANY lane of the first launch is in the status word before the first wave of the second starts — the kernel boundary — so a refused list
+// writes no word of `out`.  The first launch writes the scratch list and the status word and nothing else.
+constexpr uint64_t READ_NONE = FASTECC_READ_NONE;
+
+__global__ __launch_bounds__(256) void read_translate_kernel(const ReadTranslate t)
+{
+    const uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= t.n) return;
+    const uint64_t idx = t.reads[u];
+    DirectReadEntry ent{0, 0, 0, DIRECT_READ_SKIP, 0};  // FASTECC_READ_NONE, and a request at fault (no wave gets as far as its entry)
+    bool fault = false;
+    if (idx != READ_NONE) {
+        fault = idx >= t.blocks;
+        if (!fault) {
+            const uint64_t b = t.blocks <= 0xFFFFFFFFull ? (uint64_t)((uint32_t)idx / (uint32_t)t.K) : idx / t.K;  // (the common case: a 32-bit division)
+            const uint32_t i = (uint32_t)(idx - b * t.K);
+            ent = DirectReadEntry{b, 0, i, DIRECT_READ_PRESENT, 0};
+            if (t.pattern_of) {
+                const uint32_t q = t.pattern_of[b];
+                if (q != FASTECC_PATTERN_NONE) {
+                    fault = q >= t.patterns;
+                    if (!fault) {
+                        const uint32_t* row = t.lost + (size_t)q * DIRECT_READ_LOST_ROW;  // (the padding matches no block: i < K < 0xFFFFFFF0)
+                        for (uint32_t j = 0; j < DIRECT_READ_LOST_ROW; ++j)
+                            if (row[j] == i) ent.pass = q, ent.out = j;
+                    }
+                }
+            } else {
+                uint32_t lo = 0, hi = t.n_lost;  // the first entry >= i of the increasing list
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (t.lost[mid] < i) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (lo < t.n_lost && t.lost[lo] == i) ent.out = lo;
+            }
+        }
+    }
+    if (fault) {
+        ent.out = DIRECT_READ_SKIP;
+        atomicCAS((unsigned long long*)t.status, 0ull, ((unsigned long long)(uint32_t)FASTECC_E_INVAL << 32) | (uint32_t)u);  // (u < 2^24)
+    }
+    t.entries[u] = ent;
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void direct_read_device_kernel(const ReadArgs a, const uint32_t* status)
+{
+    direct_read_wave<V>(a, [&](uint32_t j) {
+        const_u32_ptr st = as_constant(status);
+        return (st[0] | st[1]) == 0 && j != DIRECT_READ_SKIP;  // a refused list: all or nothing
+    });
+}
+
 int direct_read_describe(const DirectPass* p, DirectSetPass* out) { return describe_pass(p, pad_of(DIRECT_CAP), out); }  // (any pad)
 
 // Words per lane, one output each (class 1): a lane touches the pool (rows S words apart), the output rows (width words apart) and the
@@ -1138,6 +1205,40 @@ int direct_run_read(const DirectSetPass* passes, const DirectReadEntry* entries,
             case 4: hipLaunchKernelGGL(direct_read_kernel<4>, grid, dim3(256), 0, st, a); break;
             case 2: hipLaunchKernelGGL(direct_read_kernel<2>, grid, dim3(256), 0, st, a); break;
             default: hipLaunchKernelGGL(direct_read_kernel<1>, grid, dim3(256), 0, st, a); break;
+        }
+    });
+}
+
+int direct_run_read_translate(const ReadTranslate& t, hipStream_t st)
+{
+    if (!t.reads || !t.status || !t.entries || t.n == 0 || t.n > SET_LAUNCH_WAVES || t.K == 0 || (!t.pattern_of && t.n_lost > 0 && !t.lost) ||
+        (t.pattern_of && !t.lost))
+        return FASTECC_E_INVAL;
+    hipLaunchKernelGGL(read_translate_kernel, dim3((unsigned)((t.n + 255) / 256)), dim3(256), 0, st, t);
+    HIP_TRY(hipGetLastError());
+    return FASTECC_OK;
+}
+
+// direct_run_read for entries made by read_translate_kernel: the same words per lane, waves per entry and split into launches
+int direct_run_read_device(const DirectSetPass* passes, const DirectReadEntry* entries, uint64_t n_entries, const uint32_t* data, const uint32_t* parity,
+                           uint32_t* out, uint64_t S, uint64_t col0, uint64_t width, uint64_t data_stride, uint64_t parity_stride, const uint64_t* status,
+                           hipStream_t st)
+{
+    if (!passes || !entries || !out || !status || n_entries == 0 || S == 0 || S > 0xFFFFFFFFull || width == 0 || col0 > S || width > S - col0)
+        return FASTECC_E_INVAL;
+    const int v = lane_words(1, S | col0 | width, (uintptr_t)data | (uintptr_t)parity | (uintptr_t)out, width);  // (direct_read_waves_per_entry's)
+    const uint64_t wpe = waves_of(width, v);
+    ReadArgs a{data, parity, out, data_stride, parity_stride, entries, passes, 0, 0, (uint32_t)wpe, (uint32_t)S, (uint32_t)col0, (uint32_t)width};
+    const uint32_t* st_words = (const uint32_t*)status;
+    return launch_entries(n_entries, wpe, [&](uint64_t e0, uint32_t waves) {
+        a.entries = entries + e0;
+        a.row_base = e0;
+        a.waves = waves;
+        const dim3 grid((waves + 3u) / 4u);
+        switch (v) {
+            case 4: hipLaunchKernelGGL(direct_read_device_kernel<4>, grid, dim3(256), 0, st, a, st_words); break;
+            case 2: hipLaunchKernelGGL(direct_read_device_kernel<2>, grid, dim3(256), 0, st, a, st_words); break;
+            default: hipLaunchKernelGGL(direct_read_device_kernel<1>, grid, dim3(256), 0, st, a, st_words); break;
         }
     });
 }

@@ -169,6 +169,28 @@ uint64_t direct_read_waves_per_entry(const void* data, const void* parity, const
 // The caller guarantees col0 + width <= S, entry.block < data rows, entry.out < the pass's outputs and room for n_entries * width words at `out`.
 int direct_run_read(const DirectSetPass* passes, const DirectReadEntry* entries, uint64_t n_entries, const uint32_t* data, const uint32_t* parity, uint32_t* out,
                     uint64_t S, uint64_t col0, uint64_t width, uint64_t data_stride, uint64_t parity_stride, hipStream_t st);
+// The request list in device memory (fastecc_read_batch_device / _read_batch_set_device): read_translate_kernel, one lane per
+// request, makes entry u of `entries` from reads[u] on the stream — what read_batch_impl's translate makes on the host — and direct_run_read_device
+// is direct_run_read behind a look at the status word.  A FASTECC_READ_NONE request becomes an entry with out = DIRECT_READ_SKIP: no wave touches
+// its row.  A request at fault (an index >= blocks, in the set form a pattern_of entry that is neither FASTECC_PATTERN_NONE nor < patterns) sets
+// *status to (uint32_t)FASTECC_E_INVAL << 32 | u unless it is non-zero already; every wave of the read launches returns on a non-zero status.
+constexpr uint32_t DIRECT_READ_SKIP = 0xFFFFFFFEu;
+constexpr uint32_t DIRECT_READ_LOST_ROW = 16;  // words per pattern of ReadTranslate::lost in the set form
+struct ReadTranslate {
+    const uint64_t* reads;       // device: n requests b * K + i, or FASTECC_READ_NONE
+    const uint32_t* pattern_of;  // device: the pool's `count` entries (set form); null: the single pattern
+    // device.  Set form: `patterns` rows of DIRECT_READ_LOST_ROW words, row q = pattern q's lost data blocks in the order of its pass's outputs, then
+    // 0xFFFFFFFF to the end.  Single pattern: its n_lost lost data blocks, increasing (not read when n_lost == 0).
+    const uint32_t* lost;
+    uint64_t* status;            // device
+    DirectReadEntry* entries;    // device: room for n entries
+    uint64_t n, blocks, K;       // requests; count * K
+    uint32_t patterns, n_lost;
+};
+int direct_run_read_translate(const ReadTranslate& t, hipStream_t st);
+int direct_run_read_device(const DirectSetPass* passes, const DirectReadEntry* entries, uint64_t n_entries, const uint32_t* data, const uint32_t* parity,
+                           uint32_t* out, uint64_t S, uint64_t col0, uint64_t width, uint64_t data_stride, uint64_t parity_stride, const uint64_t* status,
+                           hipStream_t st);
 bool direct_mfma_applies(const void* data, const void* parity, uint64_t words);
 // encoding straight from the Lagrange basis for codes with few parity blocks (n - k <= direct_encode_max())
 struct DirectEncode;

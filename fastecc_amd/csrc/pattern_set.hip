@@ -32,7 +32,10 @@ int fill_pattern_set(fastecc_ctx* c, const std::vector<LostLists>& lists, Patter
     fresh->lost_data.assign(P, {});
     fresh->lost_parity.assign(P, {});
     std::vector<DirectSetPass> desc(P, DirectSetPass{});
-    std::vector<uint32_t> lost_rows((P + 1) * SET_LOST_ROW, SET_LOST_END);
+    // the lost parity blocks (P + 1 rows of SET_LOST_ROW words), then the lost data blocks (P rows of DIRECT_READ_LOST_ROW words): one buffer, one upload
+    static_assert(DIRECT_READ_LOST_ROW == SET_MAX_LOST, "a row of the read table holds a pattern's lost data blocks");
+    const size_t lost_data_at = (P + 1) * SET_LOST_ROW;
+    std::vector<uint32_t> lost_rows(lost_data_at + P * DIRECT_READ_LOST_ROW, SET_LOST_END);
     const CodeGeometry geometry(c);
     PhaseTimer quiet;  // one line per set, not two per pattern
     quiet.on = false;
@@ -45,7 +48,9 @@ int fill_pattern_set(fastecc_ctx* c, const std::vector<LostLists>& lists, Patter
         if ((rc = direct_set_describe(fresh->pass(q), &desc[q])) != FASTECC_OK) return rc;
         while ((1u << fresh->cls[q]) < desc[q].cstride) fresh->cls[q]++;
         fresh->rows[q] = desc[q].rows;
+        fresh->rows_max = std::max(fresh->rows_max, desc[q].rows);
         fresh->lost_data[q] = l.R;
+        std::copy(l.R.begin(), l.R.end(), lost_rows.begin() + lost_data_at + q * DIRECT_READ_LOST_ROW);  // (at most SET_MAX_LOST)
         fresh->lost_parity[q] = l.Pl;
         std::sort(fresh->lost_parity[q].begin(), fresh->lost_parity[q].end());
         std::copy(fresh->lost_parity[q].begin(), fresh->lost_parity[q].end(), lost_rows.begin() + q * SET_LOST_ROW);  // (at most SET_MAX_LOST < SET_LOST_ROW)
@@ -54,6 +59,7 @@ int fill_pattern_set(fastecc_ctx* c, const std::vector<LostLists>& lists, Patter
     HIP_TRY(hipMemcpy(fresh->d_passes, desc.data(), P * sizeof(DirectSetPass), hipMemcpyHostToDevice));
     RC_TRY(fresh->d_lost_parity.alloc(lost_rows.size()));
     HIP_TRY(hipMemcpy(fresh->d_lost_parity, lost_rows.data(), lost_rows.size() * 4, hipMemcpyHostToDevice));
+    fresh->d_lost_data = fresh->d_lost_parity.get() + lost_data_at;
     return FASTECC_OK;
 }
 
@@ -196,22 +202,28 @@ int decode_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
     return run_pattern_set(c, s, data, parity, x.block, count, [](uint64_t b) { return b; }, [&](uint64_t b) { return pattern_of[b]; }, stream, repair);
 }
 
-// ---- fastecc_read_batch / _read_batch_set: degraded reads ----
-// The requested data blocks reads[0 .. n_reads) of a pool, words [col0, col0 + width) of each, into row u of `out`; the pool is only read.
-// set_form: stripe b under pattern pattern_of[b] of the prepared set; else every stripe under the single prepared pattern (direct path only).
-// The argument checks, the pool's extent, then every request on the host — (stripe, pattern, present or the block's output index in the pass that
-// fastecc_decode_batch[_set] takes for the lost data) — and only when all of them are valid ONE launch of direct_read_kernel over the staged list.
-int read_batch_impl(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const uint32_t* pattern_of, bool set_form, const uint64_t* reads,
-                    uint64_t n_reads, uint64_t col0, uint64_t width, void* out, void* stream)
+// ---- fastecc_read_batch / _read_batch_set and their device-list forms: degraded reads ----
+// The tables a read call works under: the set, or the single pattern's pass for the lost data
+struct ReadTables {
+    PatternSet* s = nullptr;
+    DecodeState* d = nullptr;
+    DirectPass* single = nullptr;  // (null: the single pattern lost no data block — every request is a copy)
+};
+
+// What the host decides without looking at the request list, for the host-list and the device-list forms alike (`reads` is tested for null only):
+// the arguments, the context's kind — from there on under the call lock, which `lk` holds when this returns FASTECC_OK —, the window, the pool's
+// extent, `out` against the pool, and the prepared set or pattern.
+int read_batch_checks(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const uint32_t* pattern_of, bool set_form, const uint64_t* reads,
+                      uint64_t n_reads, uint64_t col0, uint64_t width, const void* out, std::unique_lock<std::mutex>& lk, ReadTables* tables)
 {
     if (!c || count == 0 || width == 0 || (set_form && !pattern_of)) return FASTECC_E_INVAL;
     if (n_reads > 0 && (!data || !parity || !reads || !out)) return FASTECC_E_INVAL;
     if (((uintptr_t)data | (uintptr_t)parity | (uintptr_t)out) & 3u) return FASTECC_E_INVAL;
     if (c->sharded) return FASTECC_E_UNSUPPORTED;
-    CallLock lk(c->mu);
+    lk = std::unique_lock<std::mutex>(c->mu);
     if (c->field != FASTECC_FIELD_GF_FFF00001) return FASTECC_E_UNSUPPORTED;
     if (c->ld != c->S) return FASTECC_E_UNSUPPORTED;  // stripes of a pool are contiguous
-    const uint64_t S = c->S, K = c->K;
+    const uint64_t S = c->S;
     if (col0 > S || width > S - col0) return FASTECC_E_INVAL;
     PoolExtent x;
     RC_TRY(pool_extent(c, data, parity, count, &x));
@@ -222,9 +234,9 @@ int read_batch_impl(fastecc_ctx* c, const void* data, const void* parity, uint64
     auto overlaps = [&](uint64_t base, uint64_t bytes) { return o0 < base + bytes && base < o0 + out_bytes; };
     if (n_reads > 0 && (overlaps(d0, count * x.data_bytes) || overlaps(p0, count * x.parity_bytes))) return FASTECC_E_INVAL;
     // the tables: the set's descriptor table, or the single pattern's pass for the lost data
-    PatternSet* s = nullptr;
-    DecodeState* d = nullptr;
-    DirectPass* single = nullptr;  // (null: the single pattern lost no data block — every request is a copy)
+    PatternSet*& s = tables->s;
+    DecodeState*& d = tables->d;
+    DirectPass*& single = tables->single;
     if (set_form) {
         if (!(s = c->pattern_set)) return FASTECC_E_INVAL;  // fastecc_decode_prepare_set first
     } else {
@@ -239,7 +251,40 @@ int read_batch_impl(fastecc_ctx* c, const void* data, const void* parity, uint64
             if (!single || d->host.lost_data.size() != (size_t)d->few.direct.ed) return FASTECC_E_DEVICE;
         }
     }
+    return FASTECC_OK;
+}
+
+// The single pattern's descriptor table on the device, uploaded once per prepared pattern.  (No read that used the previous one is in flight:
+// fastecc_decode_prepare waited for them before it rebuilt the tables.)
+int single_read_desc(DecodeState* d, DirectPass* single, const DirectSetPass** passes)
+{
+    if (single && d->few.read_desc_of != d->pattern.serial) {
+        DirectSetPass desc;
+        RC_TRY(direct_read_describe(single, &desc));
+        RC_TRY(d->few.read_desc.alloc(1));
+        HIP_TRY(hipMemcpy(d->few.read_desc, &desc, sizeof(desc), hipMemcpyHostToDevice));
+        d->few.read_desc_of = d->pattern.serial;
+    }
+    RC_TRY(d->few.read_desc.alloc(1));  // (a pattern that lost no data: the table is never read, but the launch takes a pointer)
+    *passes = d->few.read_desc.get();
+    return FASTECC_OK;
+}
+
+// The requested data blocks reads[0 .. n_reads) of a pool, words [col0, col0 + width) of each, into row u of `out`; the pool is only read.
+// set_form: stripe b under pattern pattern_of[b] of the prepared set; else every stripe under the single prepared pattern (direct path only).
+// read_batch_checks, then every request on the host — (stripe, pattern, present or the block's output index in the pass that
+// fastecc_decode_batch[_set] takes for the lost data) — and only when all of them are valid ONE launch of direct_read_kernel over the staged list.
+int read_batch_impl(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const uint32_t* pattern_of, bool set_form, const uint64_t* reads,
+                    uint64_t n_reads, uint64_t col0, uint64_t width, void* out, void* stream)
+{
+    std::unique_lock<std::mutex> lk;
+    ReadTables tables;
+    RC_TRY(read_batch_checks(c, data, parity, count, pattern_of, set_form, reads, n_reads, col0, width, out, lk, &tables));
+    PatternSet* const s = tables.s;
+    DecodeState* const d = tables.d;
+    DirectPass* const single = tables.single;
     if (n_reads == 0) return FASTECC_OK;
+    const uint64_t S = c->S, K = c->K;
     const uint64_t P = s ? s->tables.size() : 0, blocks = count * K;  // (count * K * block fits 64 bits: pool_extent)
     const uint32_t single_rows = single ? (uint32_t)direct_pass_rows(single) : 0;
     const bool small = blocks <= 0xFFFFFFFFull;
@@ -293,22 +338,94 @@ int read_batch_impl(fastecc_ctx* c, const void* data, const void* parity, uint64
         rows_total += rows_read + 1;
     }
     const DirectSetPass* passes = s ? s->d_passes.get() : nullptr;
-    if (!set_form) {
-        if (single && d->few.read_desc_of != d->pattern.serial) {
-            // (no read that used the previous descriptor is in flight: fastecc_decode_prepare waited for them before it rebuilt the tables)
-            DirectSetPass desc;
-            RC_TRY(direct_read_describe(single, &desc));
-            RC_TRY(d->few.read_desc.alloc(1));
-            HIP_TRY(hipMemcpy(d->few.read_desc, &desc, sizeof(desc), hipMemcpyHostToDevice));
-            d->few.read_desc_of = d->pattern.serial;
-        }
-        RC_TRY(d->few.read_desc.alloc(1));  // (a pattern that lost no data: the table is never read, but the launch takes a pointer)
-        passes = d->few.read_desc.get();
-    }
+    if (!set_form) RC_TRY(single_read_desc(d, single, &passes));
     return with_internal_buffers(c, st, [&]() -> int {  // the tables and the list are internal buffers
         RC_TRY(list.publish(n_reads, st));
         ProfScope ps(c, st, set_form ? "direct_read_set" : "direct_read", rows_total * width * 4u);
         return direct_run_read(passes, list.dev, n_reads, ddata, dparity, (uint32_t*)out, S, col0, width, K * S, c->Mu * S, st);
+    });
+}
+
+// fastecc_read_batch_device / _read_batch_set_device: read_batch_impl with `reads`, `pattern_of` (set form) and `status` in
+// DEVICE memory, never dereferenced here.  What the host decides without the lists, then on the stream: *status = 0, read_translate_kernel into the
+// context's own entry list (not read_list.dev, which the degraded writes use too) and direct_read_device_kernel over it.  A steady-state call
+// allocates nothing, copies nothing and waits for nothing; the entry list grows behind the host-side wait for the kernels that read it, and the
+// single pattern's two small tables are uploaded once per prepared pattern.
+constexpr uint64_t READ_DEVICE_MAX = 1ull << 24;  // requests of one list: the row field of the status word is 32 bits, a launch holds 2^24 waves
+
+int read_batch_device_impl(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const uint32_t* pattern_of, bool set_form,
+                           const uint64_t* reads, uint64_t n_reads, uint64_t col0, uint64_t width, void* out, uint64_t* status, void* stream)
+{
+    if (!c || !status) return FASTECC_E_INVAL;
+    if ((((uintptr_t)reads | (uintptr_t)status) & 7u) != 0 || (set_form && ((uintptr_t)pattern_of & 3u) != 0)) return FASTECC_E_INVAL;
+    if (n_reads > READ_DEVICE_MAX) return FASTECC_E_UNSUPPORTED;
+    std::unique_lock<std::mutex> lk;
+    ReadTables tables;
+    RC_TRY(read_batch_checks(c, data, parity, count, pattern_of, set_form, reads, n_reads, col0, width, out, lk, &tables));
+    // the lists and the status word against `out`, the status word against the lists (count * 4 and n_reads * width * 4 fit: read_batch_checks)
+    const auto hits = [](const void* p, uint64_t pbytes, const void* q, uint64_t qbytes) {
+        const uint64_t p0 = (uint64_t)(uintptr_t)p, q0 = (uint64_t)(uintptr_t)q;
+        return p && q && pbytes && qbytes && p0 < q0 + qbytes && q0 < p0 + pbytes;
+    };
+    const uint64_t out_bytes = n_reads * width * 4u, reads_bytes = n_reads * 8u, pattern_bytes = set_form ? count * 4u : 0;
+    if (hits(reads, reads_bytes, out, out_bytes) || hits(pattern_of, pattern_bytes, out, out_bytes) || hits(status, 8, out, out_bytes) ||
+        hits(status, 8, reads, reads_bytes) || hits(status, 8, pattern_of, pattern_bytes))
+        return FASTECC_E_INVAL;
+    const uint64_t S = c->S, K = c->K;
+    if (n_reads > 0 && direct_read_waves_per_entry(data, parity, out, S, col0, width) > (1ull << 24)) return FASTECC_E_UNSUPPORTED;
+    DeviceGuard dg(c->device);
+    if (!dg.ok) return FASTECC_E_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_reads == 0) {
+        HIP_TRY(hipMemsetAsync(status, 0, 8, st));
+        return FASTECC_OK;
+    }
+    ReadTranslate t{};
+    t.reads = reads;
+    t.pattern_of = set_form ? pattern_of : nullptr;
+    t.status = status;
+    t.n = n_reads;
+    t.blocks = count * K;  // (fits: pool_extent)
+    t.K = K;
+    const DirectSetPass* passes = nullptr;
+    uint64_t rows_max = 0;
+    if (set_form) {
+        PatternSet* s = tables.s;
+        passes = s->d_passes.get();
+        t.lost = s->d_lost_data;
+        t.patterns = (uint32_t)s->tables.size();
+        rows_max = s->rows_max;
+    } else {
+        DecodeState* d = tables.d;
+        RC_TRY(single_read_desc(d, tables.single, &passes));
+        if (tables.single) {
+            const std::vector<uint32_t>& R = d->host.lost_data;  // increasing (Prepare::direct)
+            if (d->few.read_lost_of != d->pattern.serial) {  // (as for the descriptor: no read under the previous pattern is in flight)
+                RC_TRY(d->few.read_lost.alloc((uint64_t)direct_cap()));
+                if (R.size() > d->few.read_lost.capacity()) return FASTECC_E_DEVICE;
+                HIP_TRY(hipMemcpy(d->few.read_lost, R.data(), R.size() * 4, hipMemcpyHostToDevice));
+                d->few.read_lost_of = d->pattern.serial;
+            }
+            t.lost = d->few.read_lost.get();
+            t.n_lost = (uint32_t)R.size();
+            rows_max = (uint64_t)direct_pass_rows(tables.single);
+        }
+    }
+    if (n_reads > c->read_entries.capacity()) {
+        RC_TRY(wait_idle(c));  // the kernels that read the list about to be replaced
+        RC_TRY(c->read_entries.grow(std::max<uint64_t>(std::max<uint64_t>(n_reads, 2 * c->read_entries.capacity()), 4096)));
+    }
+    t.entries = c->read_entries.get();
+    return with_internal_buffers(c, st, [&]() -> int {  // the tables and the entry list are internal buffers
+        HIP_TRY(hipMemsetAsync(status, 0, 8, st));
+        {
+            ProfScope ps(c, st, "direct_read_device_translate", n_reads * (8 + sizeof(DirectReadEntry) + (set_form ? 4 : 0)));
+            RC_TRY(direct_run_read_translate(t, st));
+        }
+        // (the bytes: a BOUND, every request taken for a lost block of the pattern with the most rows — what the requests are is known on the device only)
+        ProfScope ps(c, st, set_form ? "direct_read_device_set" : "direct_read_device", n_reads * (rows_max + 1) * width * 4u);
+        return direct_run_read_device(passes, t.entries, n_reads, (const uint32_t*)data, (const uint32_t*)parity, (uint32_t*)out, S, col0, width, K * S,
+                                      c->Mu * S, status, st);
     });
 }
 
@@ -397,6 +514,20 @@ int fastecc_read_batch(fastecc_ctx* c, const void* data, const void* parity, uin
                        uint64_t width_words, void* out, void* stream)
 {
     return guarded([&]() -> int { return read_batch_impl(c, data, parity, count, nullptr, false, reads, n_reads, col0_words, width_words, out, stream); });
+}
+
+int fastecc_read_batch_set_device(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const uint32_t* pattern_of, const uint64_t* reads,
+                                  uint64_t n_reads, uint64_t col0_words, uint64_t width_words, void* out, uint64_t* status, void* stream)
+{
+    return guarded(
+        [&]() -> int { return read_batch_device_impl(c, data, parity, count, pattern_of, true, reads, n_reads, col0_words, width_words, out, status, stream); });
+}
+
+int fastecc_read_batch_device(fastecc_ctx* c, const void* data, const void* parity, uint64_t count, const uint64_t* reads, uint64_t n_reads,
+                              uint64_t col0_words, uint64_t width_words, void* out, uint64_t* status, void* stream)
+{
+    return guarded(
+        [&]() -> int { return read_batch_device_impl(c, data, parity, count, nullptr, false, reads, n_reads, col0_words, width_words, out, status, stream); });
 }
 
 }  // extern "C"

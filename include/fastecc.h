@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 450 /* 0.4.5: fastecc_update_batch_device, fastecc_update_parity_batch_device (pool writes from a write list in device memory) */
+#define FASTECC_VERSION 460 /* 0.4.6: fastecc_read_batch_set_device, fastecc_read_batch_device (degraded reads from a request list in device memory) */
 
 enum {
     FASTECC_OK = 0,
@@ -496,6 +496,46 @@ int fastecc_read_batch_set(fastecc_ctx *ctx, const void *data, const void *parit
                            const uint64_t *reads, uint64_t n_reads, uint64_t col0_words, uint64_t width_words, void *out, void *stream);
 int fastecc_read_batch(fastecc_ctx *ctx, const void *data, const void *parity, uint64_t count,
                        const uint64_t *reads, uint64_t n_reads, uint64_t col0_words, uint64_t width_words, void *out, void *stream);
+/*
+ * Degraded reads from a request list in DEVICE memory: fastecc_read_batch_set / fastecc_read_batch with `reads` — and, in the set form,
+ * `pattern_of` — produced on the GPU (a storage stack that batches there, a previous kernel) and no host work in the loop.  The host never
+ * dereferences `reads`, `pattern_of` or `status`.
+ *   reads   : n_reads entries of device memory, 8-byte aligned.  reads[u] = b*k + i, the window [col0_words, col0_words + width_words) and row u
+ *             of `out` mean what they mean for the two calls above, and every row that is written holds, bit for bit, the words the host-list call
+ *             writes for the same request.  The pool is never written.  n_reads is the list's capacity: a device-side producer pads a shorter list
+ *             with FASTECC_READ_NONE, and row u of `out` of such an entry is neither read nor written.  The list is read when the call's kernels
+ *             run, in stream order, not when the call is made.
+ *   pattern_of : (set form) `count` entries of device memory, 4-byte aligned, read in stream order like the list; only the entries of stripes that
+ *             some request names are looked at.  It is a device array because the host cannot know which stripes a device-made list touches, and
+ *             copying `count` entries per call would put the host back into the loop.
+ *   status  : one uint64 of device memory, 8-byte aligned, set by the call on `stream`: 0 when every request was served.  Otherwise the high 32
+ *             bits hold the error code as (uint32_t)code and the low 32 bits one row u that is at fault (any one of them: the first
+ *             compare-and-swap from 0 wins).  FASTECC_E_INVAL: an index >= count*k, or (set form) a pattern_of[b] of a requested stripe that is
+ *             neither FASTECC_PATTERN_NONE nor below the set's size.
+ *             All or nothing: when status is non-zero, no word of out has been written by the call.
+ * The return value covers only what the host can decide without the lists, before any device work and with nothing written: everything
+ * fastecc_read_batch_set / fastecc_read_batch refuse without looking at `reads`, with the same codes (a null context, count == 0, null or
+ * misaligned data, parity or out, an empty window or one outside the block, byte sizes beyond 64 bits, `out` overlapping the pool, no set or no
+ * pattern prepared; GF((2^61-1)^2), sharded contexts, a set "row_pitch_words" and for fastecc_read_batch_device a transform-path pattern are
+ * FASTECC_E_UNSUPPORTED); FASTECC_E_INVAL for a null status, for reads or status that are not 8-byte aligned or a pattern_of that is not 4-byte
+ * aligned, and for reads, pattern_of or status overlapping `out` or status overlapping either list; FASTECC_E_UNSUPPORTED for n_reads above 2^24
+ * (the row field of the status word is 32 bits, and a launch holds 2^24 waves).  n_reads == 0 is FASTECC_OK after those checks, with *status set
+ * to 0 on the stream.  FASTECC_OK otherwise means "enqueued": the lists' own faults are reported through *status alone.
+ * Streams: in steady state — the same or a smaller n_reads than an earlier call on the context, and the same prepared set or pattern — a call
+ * makes no host-device copy and no allocation, waits on no event or stream and touches no pinned memory: it resets *status (hipMemsetAsync),
+ * launches and returns.  The first call, a growing call and the first call after a fastecc_decode_prepare[_set] may allocate, copy a small table
+ * synchronously and wait, as fastecc_read_batch does.  fastecc_decode_prepare and fastecc_decode_prepare_set wait for reads still in flight
+ * before they replace tables.  hipGraph capture is not claimed.
+ * Method: one kernel with a lane per request translates the list into the entries of the host-list form's read kernel, in
+ * a scratch list of the context; the read kernel's waves then look at the status word and at their entry before they do the host-list form's
+ * work.  The boundary between the two launches is what makes "all or nothing" hold.
+ */
+#define FASTECC_READ_NONE UINT64_MAX /* reads[u] of the two calls below: row u of out is left alone */
+int fastecc_read_batch_set_device(fastecc_ctx *ctx, const void *data, const void *parity, uint64_t count,
+                                  const uint32_t *pattern_of /* device, count entries */, const uint64_t *reads /* device */, uint64_t n_reads,
+                                  uint64_t col0_words, uint64_t width_words, void *out, uint64_t *status /* device */, void *stream);
+int fastecc_read_batch_device(fastecc_ctx *ctx, const void *data, const void *parity, uint64_t count, const uint64_t *reads /* device */,
+                              uint64_t n_reads, uint64_t col0_words, uint64_t width_words, void *out, uint64_t *status /* device */, void *stream);
 
 /*
  * Error detection and location ("scrub"): find blocks that are present but wrong — bit rot, torn or misdirected writes — which
