@@ -32,14 +32,14 @@
 //                          kernel need the same old row, so the store waits for a later kernel on the same stream: no race, no flag).
 //
 // A pool whose stripes miss blocks (fastecc_update_batch_set / _update_parity_batch_set): stripe b under pattern pattern_of[b] of the
-// set of fastecc_decode_prepare_set.  The same host code (update_batch_run with a SetForm), and on the stream
+// set of fastecc_decode_prepare_set.  The same host code (update_batch_run with a SetForm; build_update_list, update_list.hpp, with its arrays), and on the stream
 //   direct_run_read      : the old rows of the written data blocks that are absent, rebuilt into UpdateState::d_recon before any parity launch;
 //   update_set_kernel    : update_batch_kernel with each old row at an offset the host chose (the pool, or d_recon) and the stripe's absent parity
 //                          blocks skipped — neither loaded nor stored: stream_parity's next block is the next PRESENT one;
 //   update_scatter_kernel: only the writes whose data block is present.
 //
 // One window of word columns [col0, col0 + width) of every written block (the four fastecc_update_*_window calls): the same host code
-// once more (update_batch_run<true> with a Window), rows of `width` words, and on the stream
+// once more (update_batch_run with a Window), rows of `width` words, and on the stream
 //   direct_run_read             : the old WINDOWS of the absent written blocks, into d_recon at pitch width;
 //   update_window_kernel        : update_set_kernel with the lane's columns counted from the window, for the set forms and the plain ones alike (a call
 //                                 without a pattern set gives every stripe a row that loses nothing); no word outside the window is loaded or stored;
@@ -50,6 +50,10 @@
 // segment tables in the window form's formats (device_count_kernel, device_fill_kernel, device_segments_kernel), update_window_device_kernel per
 // admitted length class — update_window_kernel's wave behind a look at the status and at the class's real segment count — and
 // update_device_scatter_kernel straight from the caller's list.
+//
+// The host side of the pool calls: the formats of the list and of the segment tables, sort_writes and build_update_list are in
+// update_list.hpp, which needs no HIP; update_batch_run and update_device_run are written out of the same stages (pool_lanes, grow_behind_wait,
+// pool_kernel_args, split_runs, launch_split).
 #include <algorithm>
 #include <atomic>
 #include <vector>
@@ -58,12 +62,11 @@
 #include "drivers.hpp"
 #include "lazy96.hpp"
 #include "ntt_device.hpp"
+#include "update_list.hpp"
 
 namespace fastecc {
 
 namespace {
-
-constexpr int ROWS = 16;  // changed blocks per pass: delta rows held in VGPRs (32 spills SGPRs: the 32 row positions and their weights)
 
 struct CodeGeom {
     uint64_t N = 0;  // transform order (q * 2^m for the mixed-radix codes)
@@ -362,10 +365,7 @@ __global__ __launch_bounds__(256) void update_parity_kernel(const ParityArgs a)
 }
 
 // ---- a pool of stripes (fastecc_update_batch / _update_parity_batch) ----
-constexpr int LIST_WORDS = 4;  // one write of the sorted list: position of its data block (i << e), its row of new_blocks, its stripe (low, high word)
-constexpr int SEG_HEAD = 2;    // one segment of a launch of class T: its first write in the sorted list, its number of writes (1 .. T), then the T
-                               // positions of its rows (rows past its length: that of row 0) — SEG_HEAD + T words
-
+// (the formats of the sorted list and of the segment tables: update_list.hpp)
 struct BatchArgs {
     uint32_t* parity;            // the pool's parity: stripe b's M blocks at parity + b * M * S
     const uint32_t* data;        // fastecc_update_batch: the pool's data (old rows), stripe b's K blocks at data + b * K * S; else null
@@ -430,13 +430,7 @@ __global__ __launch_bounds__(256) void update_batch_kernel(const BatchArgs a)
 }
 
 // ---- a pool of stripes with absent blocks (fastecc_update_batch_set / _update_parity_batch_set) ----
-constexpr int SET_LIST_WORDS = LIST_WORDS + 2;  // ... and where the write's old row is: its offset in words from SetArgs::old_base (low, high word; negative where the
-                                                // row lies below the base) — the pool's data block, or for an ABSENT data block its row of the reconstruction
-                                                // buffer; the parity form: its row of old_blocks.  An absent block's write has ROW_ABSENT set in its row word.
-constexpr int SET_SEG_HEAD = SEG_HEAD + 1;      // ... and the offset (words) of its stripe's row of the pattern set's lost parity blocks
-constexpr uint32_t ROW_ABSENT = 0x80000000u;    // (a call has fewer than 2^31 rows: update_batch_args)
-constexpr uint32_t OLD_IN_POOL = 0xFFFFFFFFu;   // host: SetForm::old_row of a write whose data block is present
-
+// (the longer records, SET_LIST_WORDS and SET_SEG_HEAD + T words: update_list.hpp)
 struct SetArgs {
     BatchArgs b;               // list and segs in the two formats above
     const uint32_t* old_base;  // what the old rows' offsets count from: the pool's data, else old_blocks, else new_blocks (no old rows: masked away)
@@ -644,7 +638,7 @@ __global__ __launch_bounds__(256) void update_scatter_kernel(const ScatterArgs a
 }
 
 // ---- the write list in device memory (fastecc_update_batch_device / _update_parity_batch_device) ----
-// The host never reads the list, so what update_batch_run builds on the host — the list's records and the segment tables of update_window_kernel — is
+// The host never reads the list, so what build_update_list builds on the host — the list's records and the segment tables of update_window_kernel — is
 // built by three kernels on the stream, without a sort:
 //   device_count_kernel   : lane u takes slot = cnt[stripe]++ of its write (cnt is zeroed by the call); the lane that draws slot 0 gives the stripe its
 //                           segment number, from one counter;
@@ -733,7 +727,7 @@ __global__ __launch_bounds__(256) void device_fill_kernel(const DeviceListArgs a
     if (slot >= a.mps) return;  // FASTECC_WRITE_NONE, an index out of range, or one write too many for its stripe: no record (the status is set)
     const uint64_t idx = a.writes[u];
     const uint64_t b = stripe_of_index(a, idx);
-    const uint64_t off = a.with_data ? idx * a.S + a.col0 : u * a.W;  // the old row from old_base, as update_batch_run's long form
+    const uint64_t off = a.with_data ? idx * a.S + a.col0 : u * a.W;  // the old row from old_base, as build_update_list's long form
     uint32_t* wr = a.records + ((uint64_t)a.seg_of[b] * a.mps + slot) * SET_LIST_WORDS;
     wr[0] = (uint32_t)((idx - b * a.K) << a.e);
     wr[1] = (uint32_t)u;
@@ -1096,29 +1090,6 @@ int update_batch_args(fastecc_ctx* c, const void* data, const void* parity, uint
     return FASTECC_OK;
 }
 
-struct SortedWrite {
-    uint64_t index;  // b * k + i
-    uint32_t row;    // its row of new_blocks / old_blocks
-};
-
-// The writes by (stripe, block), each with its row of the caller's blocks; FASTECC_E_INVAL for an index >= count * k or a duplicate
-int sort_writes(const fastecc_ctx* c, uint64_t count, const uint64_t* writes, uint64_t n_writes, std::vector<SortedWrite>& out)
-{
-    out.resize(n_writes);
-    for (uint64_t u = 0; u < n_writes; u++) out[u] = SortedWrite{writes[u], (uint32_t)u};
-    std::sort(out.begin(), out.end(), [](const SortedWrite& x, const SortedWrite& y) { return x.index < y.index; });
-    if (out.back().index >= count * c->K) return FASTECC_E_INVAL;  // (count * k fits: update_batch_args)
-    for (uint64_t u = 1; u < n_writes; u++)
-        if (out[u].index == out[u - 1].index) return FASTECC_E_INVAL;
-    return FASTECC_OK;
-}
-
-struct BatchLaunch {
-    int T;
-    uint32_t seg0, segs;     // its segment table: first word after the list, number of segments
-    uint64_t parity_blocks;  // parity blocks its segments read and write (the profile's byte count)
-};
-
 constexpr uint64_t LAUNCH_WAVES = 1ull << 24;  // a dispatch holds fewer than 2^32 work-items per dimension: at most 2^22 workgroups of 4 waves
 
 // What fastecc_update_batch_set / _update_parity_batch_set add to a call (update_batch_set_impl fills it): every array is by write of the SORTED list.
@@ -1150,180 +1121,169 @@ int lost_none_row(UpdateState* s)
     return FASTECC_OK;
 }
 
+// ---- the stages the two pool drivers are written out of ----
+// How a call's waves cut its rows: V words per lane, `slices` column slices of 64 V words over the W words of a row (the window's width, else the block),
+// the window's first column.  FASTECC_E_UNSUPPORTED where one segment's waves do not fit a launch.
+struct PoolLanes {
+    int V;
+    uint64_t slices, W, col0;
+};
+int pool_lanes(const fastecc_ctx* c, const Window win, uintptr_t pointers, PoolLanes* l)
+{
+    l->W = win.width ? win.width : c->S;
+    l->col0 = win.width ? win.col0 : 0;
+    l->V = lane_words(c->S, l->col0, l->W, pointers);  // (the whole block: lane_words(S, pointers))
+    l->slices = (l->W + 64u * l->V - 1) / (64u * l->V);
+    return l->slices * c->Mu > LAUNCH_WAVES ? FASTECC_E_UNSUPPORTED : FASTECC_OK;
+}
+
+// Room for `words` in an internal buffer: replacing it waits, on the host, for the kernels that read it (FASTECC_E_NOMEM: it does not fit)
+int grow_behind_wait(fastecc_ctx* c, DeviceBuf<uint32_t>& buf, uint64_t words)
+{
+    if (words <= buf.capacity()) return FASTECC_OK;
+    RC_TRY(wait_idle(c));
+    return buf.grow(std::max<uint64_t>(words, 2 * buf.capacity()));
+}
+
+// What the old rows' offsets of the long records count from
+const uint32_t* old_rows_base(const uint32_t* data, const uint32_t* old_blocks, const uint32_t* new_blocks) { return data ? data : old_blocks ? old_blocks : new_blocks; }
+
+// What every parity launch of a call is told, in the nested form the three kernel families read (update_batch_kernel: wa.s.b, update_set_kernel: wa.s);
+// segs, waves, run and runs belong to a launch (split_runs, launch_split).  col0 is folded into the parity pointer.
+void pool_kernel_args(const fastecc_ctx* c, const UpdateState* s, const uint32_t* data, uint32_t* parity, const uint32_t* old_blocks, const uint32_t* new_blocks,
+                      const PoolLanes& l, const uint32_t* list, const uint32_t* lost, WindowArgs& wa)
+{
+    BatchArgs& a = wa.s.b;
+    a.parity = parity + l.col0;
+    a.data = data;
+    a.old_blocks = old_blocks;
+    a.new_blocks = new_blocks;
+    a.G = s->d_G;
+    a.list = list;
+    a.S = c->S;
+    a.K = c->K;
+    a.M = (uint32_t)c->Mu;
+    a.slices = (uint32_t)l.slices;
+    a.e = (uint32_t)s->g.e;
+    set_positions(s, a.p);
+    wa.s.old_base = old_rows_base(data, old_blocks, new_blocks);
+    wa.s.lost = lost;  // (read by update_set_kernel and the window kernels only)
+    wa.width = l.W;
+}
+
+// a.run and a.runs of a launch of `segs` segments of class T: at least every resident wave of the device, where the parity count allows it, in runs of
+// parity blocks per segment.  Returns the waves of one segment.
+uint64_t split_runs(const fastecc_ctx* c, KernelKind kind, int T, int V, uint64_t segs, uint64_t slices, uint64_t M, BatchArgs& a)
+{
+    const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(kind, T, V);
+    const uint64_t per_run = segs * slices;
+    const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>(M, (target + per_run - 1) / per_run));
+    a.run = (uint32_t)((M + want - 1) / want);
+    a.runs = (uint32_t)((M + a.run - 1) / a.run);
+    return slices * a.runs;
+}
+
+// `items` (segments of a parity launch, writes of a scatter) of item_waves waves each, LAUNCH_WAVES waves at a time: launch_one(first item, waves, grid)
+// enqueues one launch.  The one place where a pool write call is cut into launches.
+template <class LaunchOne>
+int launch_split(uint64_t items, uint64_t item_waves, LaunchOne&& launch_one)
+{
+    const uint64_t launch_items = LAUNCH_WAVES / item_waves;
+    for (uint64_t i0 = 0; i0 < items; i0 += launch_items) {
+        const uint64_t waves = std::min<uint64_t>(launch_items, items - i0) * item_waves;
+        launch_one(i0, (uint32_t)waves, dim3((unsigned)((waves + 3) / 4)));
+        HIP_TRY(hipGetLastError());
+    }
+    return FASTECC_OK;
+}
+
+// The host-list driver: checks, the list and the segment tables (build_update_list, into the pinned side of the staged list), the reconstruction reads,
+// the parity launches round by round, the scatter.
 // sw: the call's writes, sorted and checked.  data == null: the parity form.  set != null: stripes with absent blocks (update_set_kernel; with data, first
 // the old rows of the absent written blocks into the reconstruction buffer, and at the end only present blocks are stored).  A window (win.width != 0):
 // update_window_kernel and update_window_scatter_kernel for either form, with the list and the segments in the set form's formats, the caller's rows and
 // the reconstruction buffer at pitch W = width, and col0 folded into the parity pointer, the scatter's data pointer and the old rows' pool offsets.
-// WINDOW is a template parameter so that the whole-block calls keep the host code they had: W = S and col0 = 0 fold away.
-template <bool WINDOW>
 int update_batch_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, const std::vector<SortedWrite>& sw, const uint32_t* old_blocks, const uint32_t* new_blocks,
                      hipStream_t st, const SetForm* set, const Window win)
 {
     UpdateState* s = nullptr;
-    int rc = update_state(c, &s);
-    if (rc != FASTECC_OK) return rc;
+    RC_TRY(update_state(c, &s));
     const uint64_t S = c->S, K = c->K, M = c->Mu, n = sw.size();
-    constexpr bool window = WINDOW;
-    const bool long_form = set || window;
-    const uint64_t W = window ? win.width : S, col0 = window ? win.col0 : 0;
+    const bool window = win.width != 0, long_form = set || window;
     const int list_words = long_form ? SET_LIST_WORDS : LIST_WORDS, seg_head = long_form ? SET_SEG_HEAD : SEG_HEAD;
-    const uintptr_t pointers = (uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks;
-    const int V = window ? lane_words(S, col0, W, pointers) : lane_words(S, pointers);
-    const uint64_t slices = (W + 64u * V - 1) / (64u * V);
-    if (slices * M > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (one segment's waves fit a launch)
+    PoolLanes l;
+    RC_TRY(pool_lanes(c, win, (uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks, &l));
     if (window && !set) RC_TRY(lost_none_row(s));  // (the whole-block calls never read it)
-    const auto wait_buffers = [&]() -> int {  // the host-side wait for the kernels that read an internal buffer about to be replaced
-        if (c->buf_used) HIP_TRY(hipEventSynchronize(c->buf_event));
-        return FASTECC_OK;
-    };
-    // (a segment of len writes takes seg_head + T <= (seg_head + 1) len words; growing waits for the kernels that read the device list)
-    rc = s->list.reserve(n * (list_words + seg_head + 1), wait_buffers);
-    if (rc != FASTECC_OK) return rc;
+    RC_TRY(s->list.reserve(n * (list_words + seg_head + 1), [&] { return wait_idle(c); }));  // (build_update_list's bound; growing waits for the kernels that read the list)
     if (set && set->rebuilt) {
-        if (direct_read_waves_per_entry(data, parity, nullptr, S, col0, W) > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;
-        if (set->rebuilt > s->d_recon.capacity() / W) {  // (rebuilt * W words fit 64 bits: the call's new blocks are more)
-            RC_TRY(wait_buffers());
-            RC_TRY(s->d_recon.grow(std::max<uint64_t>(set->rebuilt * W, 2 * s->d_recon.capacity())));  // FASTECC_E_NOMEM: it does not fit
-        }
+        if (direct_read_waves_per_entry(data, parity, nullptr, S, l.col0, l.W) > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;
+        RC_TRY(grow_behind_wait(c, s->d_recon, set->rebuilt * l.W));  // (rebuilt * W words fit 64 bits: the call's new blocks are more)
     }
 
-    // the list, and each stripe's writes cut into segments of at most ROWS: segment r of a stripe runs in round r, by padded length class
-    const uint32_t* old_base = data ? data : old_blocks ? old_blocks : new_blocks;  // (update_set_kernel: the old rows' offsets count from here)
-    uint32_t* list = s->list.host;
-    std::vector<std::vector<uint32_t>> bucket;  // [round * 5 + class]: first write of each segment (its length: to the stripe's end, at most ROWS)
-    std::vector<uint32_t> stripe_end(n);        // per write: one past the last write of its stripe
-    uint64_t stored = n;                        // writes whose data block is there to be stored
-    for (uint64_t f = 0; f < n;) {
-        const uint64_t b = sw[f].index / K;
-        uint64_t g = f;
-        for (; g < n && sw[g].index < (b + 1) * K; g++) {
-            uint32_t* wr = list + g * list_words;
-            wr[0] = (uint32_t)((sw[g].index - b * K) << s->g.e);
-            wr[1] = sw[g].row;
-            wr[2] = (uint32_t)b;
-            wr[3] = (uint32_t)(b >> 32);
-            if (long_form) {  // its old row, from old_base (a window: its columns of the pool's block, or a row of W words)
-                const uint32_t r = set ? set->old_row[g] : OLD_IN_POOL;
-                const uint64_t off = r != OLD_IN_POOL ? (uint64_t)(((intptr_t)s->d_recon.get() - (intptr_t)old_base) / 4) + (uint64_t)r * W  // (both on word boundaries)
-                                     : data       ? sw[g].index * S + col0
-                                                  : (uint64_t)sw[g].row * W;
-                wr[LIST_WORDS] = (uint32_t)off;
-                wr[LIST_WORDS + 1] = (uint32_t)(off >> 32);
-                if (r != OLD_IN_POOL) wr[1] |= ROW_ABSENT, stored--;
-            }
-        }
-        for (uint64_t a0 = f, r = 0; a0 < g; a0 += ROWS, r++) {
-            int cls = 0;
-            while ((1u << cls) < std::min<uint64_t>(ROWS, g - a0)) cls++;
-            if (bucket.size() < (r + 1) * 5) bucket.resize((r + 1) * 5);
-            bucket[r * 5 + cls].push_back((uint32_t)a0);
-            stripe_end[a0] = (uint32_t)g;
-        }
-        f = g;
-    }
+    const ListShape shape{K, s->g.e, S, l.W, l.col0, M, data != nullptr, long_form};
+    ListSet ls{};
+    if (set)  // (the reconstruction buffer and old_base both lie on word boundaries)
+        ls = ListSet{set->old_row.data(), set->lost_row.data(), set->present_parity.data(), (uint32_t)SET_LOST_ROW,
+                     (uint64_t)(((intptr_t)s->d_recon.get() - (intptr_t)old_rows_base(data, old_blocks, new_blocks)) / 4)};
     std::vector<BatchLaunch> launches;
-    uint32_t* segs = list + n * list_words;
-    uint32_t seg_words = 0;
-    for (size_t i = 0; i < bucket.size(); i++) {
-        if (bucket[i].empty()) continue;
-        const int T = 1 << (int)(i % 5);
-        launches.push_back(BatchLaunch{T, seg_words, (uint32_t)bucket[i].size(), 0});
-        for (uint32_t first : bucket[i]) {
-            const uint32_t len = std::min<uint32_t>(ROWS, stripe_end[first] - first);
-            uint32_t* seg = segs + seg_words;
-            seg[0] = first;
-            seg[1] = len;
-            if (long_form) seg[SEG_HEAD] = set ? set->lost_row[first] * (uint32_t)SET_LOST_ROW : 0;  // (no set: the one row of d_lost_none)
-            for (int r = 0; r < T; r++) seg[seg_head + r] = list[(size_t)(first + ((uint32_t)r < len ? r : 0)) * list_words];
-            seg_words += seg_head + T;
-            launches.back().parity_blocks += set ? set->present_parity[first] : M;
-        }
-    }
+    const BuiltList built = build_update_list(sw, shape, set ? &ls : nullptr, s->list.host.get(), launches);
 
-    rc = update_table(c, s, st);
-    if (rc != FASTECC_OK) return rc;
+    RC_TRY(update_table(c, s, st));
     return with_internal_buffers(c, st, [&]() -> int {
-        const size_t words = (size_t)n * list_words + seg_words;
+        const size_t words = (size_t)n * list_words + built.seg_words;
         {
             ProfScope ps(c, st, "update_batch_list", words * 4);
-            const int r = s->list.publish(words, st);
-            if (r != FASTECC_OK) return r;
+            RC_TRY(s->list.publish(words, st));
         }
         if (set && set->rebuilt) {
             // The old rows of the absent written blocks, before ANY parity launch of the call: the passes read parity blocks that those launches
             // rewrite (and present data blocks, which only the scatter at the very end overwrites).
             RC_TRY(c->read_list.publish(set->rebuilt, st));
-            ProfScope ps(c, st, window ? "update_window_recon" : "update_set_recon", set->rebuilt_rows_read * W * 4);
-            RC_TRY(direct_run_read(set->view.passes, c->read_list.dev, set->rebuilt, data, parity, s->d_recon, S, col0, W, K * S, M * S, st));
+            ProfScope ps(c, st, window ? "update_window_recon" : "update_set_recon", set->rebuilt_rows_read * l.W * 4);
+            RC_TRY(direct_run_read(set->view.passes, c->read_list.dev, set->rebuilt, data, parity, s->d_recon, S, l.col0, l.W, K * S, M * S, st));
         }
         WindowArgs wa{};
-        SetArgs& sa = wa.s;
-        BatchArgs& a = sa.b;
-        a.parity = parity + col0;
-        a.data = data;
-        a.old_blocks = old_blocks;
-        a.new_blocks = new_blocks;
-        a.G = s->d_G;
-        a.list = s->list.dev;
-        a.S = S;
-        a.K = K;
-        a.M = (uint32_t)M;
-        a.slices = (uint32_t)slices;
-        a.e = (uint32_t)s->g.e;
-        set_positions(s, a.p);
-        sa.old_base = old_base;
-        sa.lost = set ? set->view.lost_parity : s->d_lost_none.get();  // (read by update_set_kernel and update_window_kernel only)
-        wa.width = W;
-        for (const BatchLaunch& l : launches) {
-            // at least every resident wave of the device, where the parity count allows it: runs of parity blocks per segment
-            const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(window ? KERNEL_WINDOW : set ? KERNEL_SET : KERNEL_BATCH, l.T, V);
-            const uint64_t per_run = (uint64_t)l.segs * slices;
-            const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>(M, (target + per_run - 1) / per_run));
-            a.run = (uint32_t)((M + want - 1) / want);
-            a.runs = (uint32_t)((M + a.run - 1) / a.run);
-            const uint64_t seg_waves = slices * a.runs, launch_segs = LAUNCH_WAVES / seg_waves;
-            ProfScope ps(c, st, window ? "update_window" : set ? "update_set" : "update_batch", l.parity_blocks * W * 8);
-            for (uint64_t s0 = 0; s0 < l.segs; s0 += launch_segs) {
-                const uint64_t waves = std::min<uint64_t>(launch_segs, l.segs - s0) * seg_waves;
-                a.segs = s->list.dev + n * list_words + l.seg0 + (size_t)s0 * (seg_head + l.T);
-                a.waves = (uint32_t)waves;
-                const dim3 grid((unsigned)((waves + 3) / 4));
-                with_class(l.T, V, [&](auto t_c, auto v_c) {
+        pool_kernel_args(c, s, data, parity, old_blocks, new_blocks, l, s->list.dev, set ? set->view.lost_parity : s->d_lost_none.get(), wa);
+        BatchArgs& a = wa.s.b;
+        for (const BatchLaunch& bl : launches) {
+            const uint64_t seg_waves = split_runs(c, window ? KERNEL_WINDOW : set ? KERNEL_SET : KERNEL_BATCH, bl.T, l.V, bl.segs, l.slices, M, a);
+            const uint32_t* table = s->list.dev + n * list_words + bl.seg0;
+            ProfScope ps(c, st, window ? "update_window" : set ? "update_set" : "update_batch", bl.parity_blocks * l.W * 8);
+            RC_TRY(launch_split(bl.segs, seg_waves, [&](uint64_t s0, uint32_t waves, dim3 grid) {
+                a.segs = table + (size_t)s0 * (seg_head + bl.T);
+                a.waves = waves;
+                with_class(bl.T, l.V, [&](auto t_c, auto v_c) {
                     constexpr int Tc = t_c, Vc = v_c;
-                    if constexpr (window) hipLaunchKernelGGL((update_window_kernel<Tc, Vc>), grid, dim3(256), 0, st, wa);
-                    else if (set) hipLaunchKernelGGL((update_set_kernel<Tc, Vc>), grid, dim3(256), 0, st, sa);
+                    if (window) hipLaunchKernelGGL((update_window_kernel<Tc, Vc>), grid, dim3(256), 0, st, wa);
+                    else if (set) hipLaunchKernelGGL((update_set_kernel<Tc, Vc>), grid, dim3(256), 0, st, wa.s);
                     else hipLaunchKernelGGL((update_batch_kernel<Tc, Vc>), grid, dim3(256), 0, st, a);
                 });
-                HIP_TRY(hipGetLastError());
-            }
+            }));
         }
-        if (window && data && stored) {
-            WindowScatterArgs ca{data + col0, new_blocks, nullptr, S, K, W, (uint32_t)slices, 0, (uint32_t)s->g.e};
-            const uint64_t launch_writes = LAUNCH_WAVES / slices;
-            ProfScope ps(c, st, "update_window_scatter", stored * W * 8);
-            for (uint64_t w0 = 0; w0 < n; w0 += launch_writes) {
-                const uint64_t waves = std::min<uint64_t>(launch_writes, n - w0) * slices;
+        if (!data || !built.stored) return FASTECC_OK;
+        ProfScope ps(c, st, window ? "update_window_scatter" : "update_scatter", built.stored * l.W * 8);
+        if (window) {
+            WindowScatterArgs ca{data + l.col0, new_blocks, nullptr, S, K, l.W, (uint32_t)l.slices, 0, (uint32_t)s->g.e};
+            return launch_split(n, l.slices, [&](uint64_t w0, uint32_t waves, dim3 grid) {
                 ca.list = s->list.dev + w0 * list_words;
-                ca.waves = (uint32_t)waves;
-                const dim3 grid((unsigned)((waves + 3) / 4));
-                with_words<1>(V, [&](auto, auto v_c) { hipLaunchKernelGGL(update_window_scatter_kernel<decltype(v_c)::value>, grid, dim3(256), 0, st, ca); });
-                HIP_TRY(hipGetLastError());
-            }
-        } else if (data && stored) {
-            ScatterArgs ca{data, new_blocks, nullptr, S, K, (uint32_t)slices, 0, (uint32_t)s->g.e, (uint32_t)list_words};
-            const uint64_t launch_writes = LAUNCH_WAVES / slices;
-            ProfScope ps(c, st, "update_scatter", stored * S * 8);
-            for (uint64_t w0 = 0; w0 < n; w0 += launch_writes) {
-                const uint64_t waves = std::min<uint64_t>(launch_writes, n - w0) * slices;
-                ca.list = s->list.dev + w0 * list_words;
-                ca.waves = (uint32_t)waves;
-                const dim3 grid((unsigned)((waves + 3) / 4));
-                with_words<1>(V, [&](auto, auto v_c) { hipLaunchKernelGGL(update_scatter_kernel<decltype(v_c)::value>, grid, dim3(256), 0, st, ca); });
-                HIP_TRY(hipGetLastError());
-            }
+                ca.waves = waves;
+                with_words<1>(l.V, [&](auto, auto v_c) { hipLaunchKernelGGL(update_window_scatter_kernel<decltype(v_c)::value>, grid, dim3(256), 0, st, ca); });
+            });
         }
-        return FASTECC_OK;
+        ScatterArgs ca{data, new_blocks, nullptr, S, K, (uint32_t)l.slices, 0, (uint32_t)s->g.e, (uint32_t)list_words};
+        return launch_split(n, l.slices, [&](uint64_t w0, uint32_t waves, dim3 grid) {
+            ca.list = s->list.dev + w0 * list_words;
+            ca.waves = waves;
+            with_words<1>(l.V, [&](auto, auto v_c) { hipLaunchKernelGGL(update_scatter_kernel<decltype(v_c)::value>, grid, dim3(256), 0, st, ca); });
+        });
     });
+}
+
+// True where the pbytes bytes at p and the qbytes bytes at q share a byte (neither range wraps; a null pointer or an empty range shares nothing)
+bool ranges_overlap(const void* p, uint64_t pbytes, const void* q, uint64_t qbytes)
+{
+    const uint64_t p0 = (uint64_t)(uintptr_t)p, q0 = (uint64_t)(uintptr_t)q;
+    return p && q && pbytes && qbytes && p0 < q0 + qbytes && q0 < p0 + pbytes;
 }
 
 // True where n_writes rows of row_bytes bytes at `rows` touch the pool (or wrap the address space).  The pool's extent has been checked (pool_extent).
@@ -1333,9 +1293,8 @@ bool rows_overlap_pool(const fastecc_ctx* c, const void* data, const void* parit
     PoolExtent x;
     (void)pool_extent(c, with_data ? data : nullptr, parity, count, &x, false);
     const uint64_t rows_bytes = n_writes * row_bytes;  // (fits 64 bits: update_batch_args, row_bytes <= x.block)
-    const uint64_t r0 = (uint64_t)(uintptr_t)rows;
-    const auto hits = [&](const void* base, uint64_t bytes) { return r0 < (uint64_t)(uintptr_t)base + bytes && (uint64_t)(uintptr_t)base < r0 + rows_bytes; };
-    return rows && n_writes > 0 && (r0 > UINT64_MAX - rows_bytes || (with_data && hits(data, count * x.data_bytes)) || hits(parity, count * x.parity_bytes));
+    if ((uint64_t)(uintptr_t)rows > UINT64_MAX - rows_bytes) return rows && n_writes > 0;
+    return (with_data && ranges_overlap(rows, rows_bytes, data, count * x.data_bytes)) || ranges_overlap(rows, rows_bytes, parity, count * x.parity_bytes);
 }
 
 // A window call's own refusals, after update_batch_args: the window {col0_words, width_words} against the block, and the caller's rows of width words
@@ -1361,14 +1320,12 @@ int update_batch_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, 
     if (rc == FASTECC_OK && col0_width) rc = window_args(c, data, parity, count, n_writes, old_blocks, new_blocks, with_data, col0_width, &win);
     if (rc != FASTECC_OK || n_writes == 0) return rc;
     std::vector<SortedWrite> sw;
-    rc = sort_writes(c, count, writes, n_writes, sw);
-    if (rc != FASTECC_OK) return rc;
+    if (!sort_writes(c->K, count, writes, n_writes, sw)) return FASTECC_E_INVAL;
     DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
     CallLock lk(c->mu);
-    const auto run = col0_width ? update_batch_run<true> : update_batch_run<false>;
-    return run(c, with_data ? (uint32_t*)data : nullptr, (uint32_t*)parity, sw, (const uint32_t*)old_blocks, (const uint32_t*)new_blocks, (hipStream_t)stream,
-               nullptr, win);
+    return update_batch_run(c, with_data ? (uint32_t*)data : nullptr, (uint32_t*)parity, sw, (const uint32_t*)old_blocks, (const uint32_t*)new_blocks,
+                            (hipStream_t)stream, nullptr, win);
 }
 
 // fastecc_update_batch_set / _update_parity_batch_set: stripe b under pattern pattern_of[b] of the prepared set.  Everything is decided on the host before any
@@ -1392,7 +1349,7 @@ int update_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
     if (!pattern_set_view(c, &set.view)) return FASTECC_E_INVAL;  // fastecc_decode_prepare_set first
     if (n_writes == 0) return FASTECC_OK;
     std::vector<SortedWrite> sw;
-    RC_TRY(sort_writes(c, count, writes, n_writes, sw));
+    if (!sort_writes(c->K, count, writes, n_writes, sw)) return FASTECC_E_INVAL;
     const uint64_t K = c->K, P = set.view.patterns, n = sw.size();
     set.lost_row.resize(n);
     set.present_parity.resize(n);
@@ -1427,9 +1384,8 @@ int update_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
         std::copy(rebuild.begin(), rebuild.end(), c->read_list.host.get());
         set.rebuilt = rebuild.size();
     }
-    const auto run = col0_width ? update_batch_run<true> : update_batch_run<false>;
-    return run(c, with_data ? (uint32_t*)data : nullptr, (uint32_t*)parity, sw, (const uint32_t*)old_blocks, (const uint32_t*)new_blocks, (hipStream_t)stream,
-               &set, win);
+    return update_batch_run(c, with_data ? (uint32_t*)data : nullptr, (uint32_t*)parity, sw, (const uint32_t*)old_blocks, (const uint32_t*)new_blocks,
+                            (hipStream_t)stream, &set, win);
 }
 
 // ---- the write list in device memory (fastecc_update_batch_device / _update_parity_batch_device) ----
@@ -1438,16 +1394,15 @@ int update_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
 // more than T / 2 of the list's n entries — and, with a data pool, the scatter after the last of them (section 15: waves of the parity launches
 // read the old rows).  The scratch grows on demand behind the host-side wait for the kernels that read it; a steady-state call allocates nothing,
 // copies nothing and waits for nothing.
+// The stages are update_batch_run's, with the three build kernels where that one calls build_update_list.
 int update_device_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, uint64_t count, const uint64_t* writes, uint64_t n, uint32_t mps, const Window win,
                       const uint32_t* old_blocks, const uint32_t* new_blocks, uint64_t* status, hipStream_t st)
 {
     UpdateState* s = nullptr;
     RC_TRY(update_state(c, &s));
-    const uint64_t S = c->S, K = c->K, M = c->Mu, W = win.width, col0 = win.col0;
-    const uintptr_t pointers = (uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks;
-    const int V = lane_words(S, col0, W, pointers);
-    const uint64_t slices = (W + 64u * V - 1) / (64u * V);
-    if (slices * M > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;  // (one segment's waves fit a launch)
+    const uint64_t S = c->S, K = c->K, M = c->Mu;
+    PoolLanes l;
+    RC_TRY(pool_lanes(c, win, (uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks, &l));
     RC_TRY(lost_none_row(s));
     // upper bounds: segments in all (one per touched stripe), and per admitted class
     const uint64_t segs_max = std::min(count, n);
@@ -1459,21 +1414,12 @@ int update_device_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, uint64_t
         la.table_off[cl] = (uint32_t)table_words;
         table_words += bound[cl] * (SET_SEG_HEAD + T);  // (n <= DEVICE_MAX: under 14 n words)
     }
-    const auto wait_buffers = [&]() -> int {  // the host-side wait for the kernels that read an internal buffer about to be replaced
-        if (c->buf_used) HIP_TRY(hipEventSynchronize(c->buf_event));
-        return FASTECC_OK;
-    };
-    const auto room = [&](DeviceBuf<uint32_t>& buf, uint64_t words) -> int {
-        if (words <= buf.capacity()) return FASTECC_OK;
-        RC_TRY(wait_buffers());
-        return buf.grow(std::max<uint64_t>(words, 2 * buf.capacity()));  // FASTECC_E_NOMEM: it does not fit
-    };
-    RC_TRY(room(s->dl_cnt, count + DEVICE_COUNTERS));
-    RC_TRY(room(s->dl_seg_of, count));
-    RC_TRY(room(s->dl_stripe_of, segs_max));
-    RC_TRY(room(s->dl_slot_of, n));
-    RC_TRY(room(s->dl_records, segs_max * mps * SET_LIST_WORDS));  // (under 2^32 words: DEVICE_MAX x ROWS x SET_LIST_WORDS)
-    RC_TRY(room(s->dl_tables, table_words));
+    RC_TRY(grow_behind_wait(c, s->dl_cnt, count + DEVICE_COUNTERS));
+    RC_TRY(grow_behind_wait(c, s->dl_seg_of, count));
+    RC_TRY(grow_behind_wait(c, s->dl_stripe_of, segs_max));
+    RC_TRY(grow_behind_wait(c, s->dl_slot_of, n));
+    RC_TRY(grow_behind_wait(c, s->dl_records, segs_max * mps * SET_LIST_WORDS));  // (under 2^32 words: DEVICE_MAX x ROWS x SET_LIST_WORDS)
+    RC_TRY(grow_behind_wait(c, s->dl_tables, table_words));
     RC_TRY(update_table(c, s, st));
     return with_internal_buffers(c, st, [&]() -> int {
         la.writes = writes;
@@ -1489,8 +1435,8 @@ int update_device_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, uint64_t
         la.limit = count * K;  // (fits: update_batch_args)
         la.K = K;
         la.S = S;
-        la.col0 = col0;
-        la.W = W;
+        la.col0 = l.col0;
+        la.W = l.W;
         la.mps = mps;
         la.e = (uint32_t)s->g.e;
         la.with_data = data ? 1u : 0u;
@@ -1506,63 +1452,34 @@ int update_device_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, uint64_t
             HIP_TRY(hipGetLastError());
         }
         WindowArgs wa{};
-        SetArgs& sa = wa.s;
-        BatchArgs& a = sa.b;
-        a.parity = parity + col0;
-        a.data = data;
-        a.old_blocks = old_blocks;
-        a.new_blocks = new_blocks;
-        a.G = s->d_G;
-        a.list = s->dl_records;
-        a.S = S;
-        a.K = K;
-        a.M = (uint32_t)M;
-        a.slices = (uint32_t)slices;
-        a.e = (uint32_t)s->g.e;
-        set_positions(s, a.p);
-        sa.old_base = data ? data : old_blocks ? old_blocks : new_blocks;
-        sa.lost = s->d_lost_none.get();
-        wa.width = W;
+        pool_kernel_args(c, s, data, parity, old_blocks, new_blocks, l, s->dl_records, s->d_lost_none.get(), wa);
+        BatchArgs& a = wa.s.b;
         {
-            ProfScope ps(c, st, "update_device", n * M * W * 8);  // (every entry a write)
+            ProfScope ps(c, st, "update_device", n * M * l.W * 8);  // (every entry a write)
             for (int cl = 0; cl < 5; cl++) {
                 if (!bound[cl]) continue;
                 const int T = 1 << cl;
-                const uint64_t target = (uint64_t)c->cus * 4u * (uint64_t)resident_waves_per_simd(KERNEL_WINDOW, T, V);
-                const uint64_t per_run = bound[cl] * slices;
-                const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>(M, (target + per_run - 1) / per_run));
-                a.run = (uint32_t)((M + want - 1) / want);
-                a.runs = (uint32_t)((M + a.run - 1) / a.run);
-                const uint64_t seg_waves = slices * a.runs, launch_segs = LAUNCH_WAVES / seg_waves;
-                for (uint64_t s0 = 0; s0 < bound[cl]; s0 += launch_segs) {
-                    const uint64_t waves = std::min<uint64_t>(launch_segs, bound[cl] - s0) * seg_waves;
+                const uint64_t seg_waves = split_runs(c, KERNEL_WINDOW, T, l.V, bound[cl], l.slices, M, a);
+                RC_TRY(launch_split(bound[cl], seg_waves, [&](uint64_t s0, uint32_t waves, dim3 grid) {
                     a.segs = s->dl_tables + la.table_off[cl] + (size_t)s0 * (SET_SEG_HEAD + T);
-                    a.waves = (uint32_t)waves;
-                    const dim3 grid((unsigned)((waves + 3) / 4));
-                    with_class(T, V, [&](auto t_c, auto v_c) {
+                    a.waves = waves;
+                    with_class(T, l.V, [&](auto t_c, auto v_c) {
                         constexpr int Tc = t_c, Vc = v_c;
                         hipLaunchKernelGGL((update_window_device_kernel<Tc, Vc>), grid, dim3(256), 0, st, wa, (const uint32_t*)status,
                                            (const uint32_t*)(la.counters + 1 + cl), (uint32_t)s0);
                     });
-                    HIP_TRY(hipGetLastError());
-                }
+                }));
             }
         }
-        if (data) {
-            DeviceScatterArgs ca{data + col0, new_blocks, nullptr, (const uint32_t*)status, S, W, (uint32_t)slices, 0, 0};
-            const uint64_t launch_writes = LAUNCH_WAVES / slices;
-            ProfScope ps(c, st, "update_device_scatter", n * W * 8);
-            for (uint64_t w0 = 0; w0 < n; w0 += launch_writes) {
-                const uint64_t waves = std::min<uint64_t>(launch_writes, n - w0) * slices;
-                ca.writes = (const uint32_t*)(writes + w0);
-                ca.row0 = (uint32_t)w0;
-                ca.waves = (uint32_t)waves;
-                const dim3 grid((unsigned)((waves + 3) / 4));
-                with_words<1>(V, [&](auto, auto v_c) { hipLaunchKernelGGL(update_device_scatter_kernel<decltype(v_c)::value>, grid, dim3(256), 0, st, ca); });
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        return FASTECC_OK;
+        if (!data) return FASTECC_OK;
+        DeviceScatterArgs ca{data + l.col0, new_blocks, nullptr, (const uint32_t*)status, S, l.W, (uint32_t)l.slices, 0, 0};
+        ProfScope ps(c, st, "update_device_scatter", n * l.W * 8);
+        return launch_split(n, l.slices, [&](uint64_t w0, uint32_t waves, dim3 grid) {
+            ca.writes = (const uint32_t*)(writes + w0);
+            ca.row0 = (uint32_t)w0;
+            ca.waves = waves;
+            with_words<1>(l.V, [&](auto, auto v_c) { hipLaunchKernelGGL(update_device_scatter_kernel<decltype(v_c)::value>, grid, dim3(256), 0, st, ca); });
+        });
     });
 }
 
@@ -1577,14 +1494,10 @@ int update_batch_device_impl(fastecc_ctx* c, void* data, void* parity, uint64_t 
     Window win;
     RC_TRY(window_args(c, data, parity, count, n_writes, old_blocks, new_blocks, with_data, col0_width, &win));
     // the list and the status word against the pool, the rows and each other (n_writes <= DEVICE_MAX: no product wraps)
-    const auto hits = [](const void* p, uint64_t pbytes, const void* q, uint64_t qbytes) {
-        const uint64_t p0 = (uint64_t)(uintptr_t)p, q0 = (uint64_t)(uintptr_t)q;
-        return p && q && pbytes && qbytes && p0 < q0 + qbytes && q0 < p0 + pbytes;
-    };
     const uint64_t rows_bytes = n_writes * win.width * 4;  // (fits: window_args has walked them)
     if (rows_overlap_pool(c, data, parity, count, with_data, writes, n_writes, 8) || rows_overlap_pool(c, data, parity, count, with_data, status, 1, 8) ||
-        hits(writes, n_writes * 8, new_blocks, rows_bytes) || hits(writes, n_writes * 8, old_blocks, rows_bytes) || hits(status, 8, new_blocks, rows_bytes) ||
-        hits(status, 8, old_blocks, rows_bytes) || hits(status, 8, writes, n_writes * 8))
+        ranges_overlap(writes, n_writes * 8, new_blocks, rows_bytes) || ranges_overlap(writes, n_writes * 8, old_blocks, rows_bytes) ||
+        ranges_overlap(status, 8, new_blocks, rows_bytes) || ranges_overlap(status, 8, old_blocks, rows_bytes) || ranges_overlap(status, 8, writes, n_writes * 8))
         return FASTECC_E_INVAL;
     DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;

@@ -11,8 +11,8 @@ tests/test_launch_seams_host.py finds each constexpr by its name in that file, s
   SET_LAUNCH_WAVES         direct_run_set (decode_batch_set,               a.entries = entries + e0
                            repair_batch_set, grouped repair)
   SET_LAUNCH_WAVES         direct_run_read (read_batch, read_batch_set)    a.entries, a.row_base = e0
-  LAUNCH_WAVES             update_batch_run (update_batch,                 a.segs + s0 * (SEG_HEAD + T), sa.list + w0 * LIST_WORDS
-                           update_parity_batch)
+  LAUNCH_WAVES             launch_split, for update_batch_run              a.segs + s0 * (SEG_HEAD + T), ca.list + w0 * LIST_WORDS
+                           (update_batch, update_parity_batch)
   POOL_LAUNCH_WAVES        pool_encode_mfma_applies (encode_pool's         no second launch: past the limit the call takes the VALU kernel
                            matrix-core kernel)
   MAX_LAUNCH_WAVES         encode_batch_passes (encode_batch, the (2k,k)   data + b0 * stride, parity + b0 * stride, batch = b1 - b0
