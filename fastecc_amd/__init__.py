@@ -147,6 +147,10 @@ def lib():
     L.fastecc_update_batch_device.restype = i32
     L.fastecc_update_parity_batch_device.argtypes = [vp, vp, u64, vp, u64, u32, u64, u64, vp, vp, vp, vp]
     L.fastecc_update_parity_batch_device.restype = i32
+    L.fastecc_update_batch_set_device.argtypes = [vp, vp, vp, u64, vp, vp, u64, u32, u64, u64, u64, vp, vp, vp]
+    L.fastecc_update_batch_set_device.restype = i32
+    L.fastecc_update_parity_batch_set_device.argtypes = [vp, vp, u64, vp, vp, u64, u32, u64, u64, vp, vp, vp, vp]
+    L.fastecc_update_parity_batch_set_device.restype = i32
     L.fastecc_code_coefficient.argtypes = [u64, u64, ctypes.c_uint, u64, u64, ctypes.POINTER(u32)]
     L.fastecc_code_coefficient.restype = i32
     L.fastecc_gf_berlekamp_massey.argtypes = [ctypes.POINTER(u32), u32, ctypes.POINTER(u32), u32]
@@ -753,6 +757,36 @@ class Encoder:
         count, n_writes, max_per_stripe, col0, width = self._device_list(count, n_writes, max_per_stripe, col0, width)
         _check(lib().fastecc_update_parity_batch_device(self._h, _addr(parity), count, _addr(writes), n_writes, max_per_stripe, col0, width,
                                                         _addr(old), _addr(new), _addr(status), stream or None), "fastecc_update_parity_batch_device")
+        return parity
+
+    def update_batch_set_device(self, data, parity, count, pattern_of, writes, n_writes, new, status, max_per_stripe=1, max_absent=None, stream=0,
+                                col0=0, width=None):
+        """update_batch_set with the write list AND pattern_of in DEVICE memory: `writes`, `status`, max_per_stripe, col0, width and the rows as for
+        update_batch_device; `pattern_of` (a device tensor or address, uint32, `count` entries) is read when the call's kernels run on `stream`,
+        never by the host, and only for the stripes that a write names.  max_absent is the caller's bound on the written data blocks that are
+        absent under their stripe's pattern (None: n_writes, always safe; 0: a promise that none is): it sizes the reconstruction buffer.  A
+        non-zero status — as update_batch_device's, and E_INVAL for a bad pattern_of entry of a touched stripe, E_NOMEM for more absent written
+        blocks than max_absent — means that no word of the pool has been written."""
+        count, n_writes, max_per_stripe, col0, width = self._device_list(count, n_writes, max_per_stripe, col0, width)
+        if max_absent is None:
+            max_absent = n_writes
+        if isinstance(max_absent, bool) or not isinstance(max_absent, int):
+            raise TypeError("max_absent must be an int or None")
+        if max_absent < 0 or max_absent >= 1 << 64:
+            raise ValueError("max_absent must be in [0, 2^64)")
+        _check(lib().fastecc_update_batch_set_device(self._h, _addr(data), _addr(parity), count, _addr(pattern_of), _addr(writes), n_writes,
+                                                     max_per_stripe, max_absent, col0, width, _addr(new), _addr(status), stream or None),
+               "fastecc_update_batch_set_device")
+        return data, parity
+
+    def update_parity_batch_set_device(self, parity, count, pattern_of, writes, n_writes, new, status, old=None, max_per_stripe=1, stream=0, col0=0,
+                                       width=None):
+        """update_batch_set_device for the parity alone: the blocks changed from row u of `old` (None: from zero) to row u of `new`; of a pattern only
+        its lost parity blocks matter."""
+        count, n_writes, max_per_stripe, col0, width = self._device_list(count, n_writes, max_per_stripe, col0, width)
+        _check(lib().fastecc_update_parity_batch_set_device(self._h, _addr(parity), count, _addr(pattern_of), _addr(writes), n_writes, max_per_stripe,
+                                                            col0, width, _addr(old), _addr(new), _addr(status), stream or None),
+               "fastecc_update_parity_batch_set_device")
         return parity
 
     def update_batch_set(self, data, parity, count, pattern_of, writes, new, stream=0, col0=0, width=None):

@@ -145,6 +145,8 @@ struct PatternSetView {
     uint64_t patterns;            // P
     const DirectSetPass* passes;  // device: the descriptor table of direct_run_read, entry q = pattern q's pass
     const uint32_t* lost_parity;  // device: P + 1 rows of SET_LOST_ROW words; row P loses nothing (a whole stripe)
+    const uint32_t* lost_data;    // device: P rows of DIRECT_READ_LOST_ROW words, row q = pattern q's lost data blocks in the order of its pass's
+                                  // outputs (DirectReadEntry::out), then SET_LOST_END to the end — what the device-list forms scan (section 41)
 };
 bool pattern_set_view(const fastecc_ctx* c, PatternSetView* out);  // false: no set prepared
 // pattern q < P of that set: its lost data blocks in the order of its pass's outputs (DirectReadEntry::out), its lost parity blocks (increasing),

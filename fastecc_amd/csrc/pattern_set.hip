@@ -436,7 +436,7 @@ bool pattern_set_view(const fastecc_ctx* c, PatternSetView* out)
 {
     const PatternSet* s = c->pattern_set;
     if (!s) return false;
-    *out = PatternSetView{s->tables.size(), s->d_passes.get(), s->d_lost_parity.get()};
+    *out = PatternSetView{s->tables.size(), s->d_passes.get(), s->d_lost_parity.get(), s->d_lost_data};
     return true;
 }
 const std::vector<uint32_t>& pattern_lost_data(const fastecc_ctx* c, uint64_t q) { return c->pattern_set->lost_data[q]; }

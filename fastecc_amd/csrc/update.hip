@@ -51,6 +51,12 @@
 // admitted length class — update_window_kernel's wave behind a look at the status and at the class's real segment count — and
 // update_device_scatter_kernel straight from the caller's list.
 //
+// ... for a pool whose stripes miss blocks (fastecc_update_batch_set_device / _update_parity_batch_set_device): pattern_of is a
+// device array as well.  The same driver with the set forms of the three build kernels — the lane that opens a stripe's segment reads and checks
+// pattern_of[b]; a write to an absent data block draws a row of d_recon and its DirectReadEntry, the segment points at its pattern's lost parity blocks —
+// then direct_run_read_device over those entries, the same update_window_device_kernel launches with the set's lost-parity table, and
+// update_device_set_scatter_kernel, which leaves the absent blocks alone.
+//
 // The host side of the pool calls: the formats of the list and of the segment tables, sort_writes and build_update_list are in
 // update_list.hpp, which needs no HIP; update_batch_run and update_device_run are written out of the same stages (pool_lanes, grow_behind_wait,
 // pool_kernel_args, split_runs, launch_split).
@@ -650,6 +656,7 @@ __global__ __launch_bounds__(256) void update_scatter_kernel(const ScatterArgs a
 // list goes into the caller's status word — the first compare-and-swap from 0 wins — and every later kernel of the call returns when it is non-zero,
 // so a refused list writes no word of the pool.  The order of a stripe's records depends on atomic arrival; the parity does not (exact 96-bit sums).
 constexpr uint32_t DEVICE_COUNTERS = 8;             // behind cnt[count]: [0] segments, [1 + c] segments of class c (T = 1 << c); zeroed with cnt
+constexpr uint32_t DEVICE_ABSENT = 6;               // ... [6] rows of the reconstruction buffer handed out (the set forms)
 constexpr uint64_t DEVICE_MAX = 1ull << 24;         // stripes of a pool and entries of a list the device form takes
 constexpr uint64_t WRITE_NONE = FASTECC_WRITE_NONE;
 
@@ -682,8 +689,24 @@ __device__ __forceinline__ uint64_t stripe_of_index(const DeviceListArgs& a, uin
     return a.small ? (uint64_t)((uint32_t)idx / (uint32_t)a.K) : idx / a.K;
 }
 
-__global__ __launch_bounds__(256) void device_count_kernel(const DeviceListArgs a)
+// What the set forms (fastecc_update_batch_set_device / _update_parity_batch_set_device) add to DeviceListArgs; NoSet: the plain forms,
+// whose kernels are the bodies below with every `if constexpr (SET)` gone.
+struct DeviceSetArgs {
+    const uint32_t* pattern_of;  // the caller's `count` entries (device); only touched stripes' entries are read, once each, by device_count_set_kernel
+    const uint32_t* lost_data;   // PatternSetView::lost_data
+    uint32_t* pattern_seg;       // [segments] the stripe's pattern, FASTECC_PATTERN_NONE and a bad entry as `patterns` (the row that loses nothing)
+    DirectReadEntry* entries;    // [cap] how to rebuild row r of the reconstruction buffer; device_count_set_kernel fills them with skip entries
+    uint32_t* absent;            // the counter the reconstruction rows are drawn from (zeroed with cnt)
+    uint64_t recon_offset;       // the reconstruction buffer's offset from old_base, in words (two's complement where it lies below)
+    uint32_t patterns, cap;      // P; rows of the reconstruction buffer: min(max_absent, n), 0 for the parity form
+};
+struct NoSet {};
+template <class Set> constexpr bool is_set_form = std::is_same<Set, DeviceSetArgs>::value;
+
+template <class Set>
+__device__ __forceinline__ void device_count_body(const DeviceListArgs& a, const Set& s)
 {
+    constexpr bool SET = is_set_form<Set>;
     __shared__ uint32_t wave_sum[4], block_base;
     const uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -703,6 +726,9 @@ __global__ __launch_bounds__(256) void device_count_kernel(const DeviceListArgs 
             }
         }
         a.slot_of[u] = slot;
+        if constexpr (SET) {  // (cap <= n) the rebuild launch is sized by cap: a row that device_fill_set_kernel does not hand out is skipped
+            if (u < s.cap) s.entries[u] = DirectReadEntry{0, 0, 0, DIRECT_READ_SKIP, 0};
+        }
     }
     const uint64_t firsts = __ballot(first);
     if (lane == 0) wave_sum[wave] = (uint32_t)__popcll(firsts);
@@ -717,28 +743,96 @@ __global__ __launch_bounds__(256) void device_count_kernel(const DeviceListArgs 
     for (uint32_t w = 0; w < wave; ++w) seg += wave_sum[w];
     a.seg_of[b] = seg;  // (seg < min(count, n): one per stripe with a write)
     a.stripe_of[seg] = b;
+    if constexpr (SET) {  // the one look at pattern_of[b] (a stripe that no write names: none)
+        uint32_t q = s.pattern_of[b];
+        if (q == FASTECC_PATTERN_NONE) {
+            q = s.patterns;
+        } else if (q >= s.patterns) {
+            device_list_fail(a.status, FASTECC_E_INVAL, u);
+            q = s.patterns;  // (the later build kernels run whatever the status: they find a valid row)
+        }
+        s.pattern_seg[seg] = q;
+    }
 }
+__global__ __launch_bounds__(256) void device_count_kernel(const DeviceListArgs a) { device_count_body(a, NoSet{}); }
+__global__ __launch_bounds__(256) void device_count_set_kernel(const DeviceListArgs a, const DeviceSetArgs s) { device_count_body(a, s); }
 
-__global__ __launch_bounds__(256) void device_fill_kernel(const DeviceListArgs a)
+// The set form: a write whose data block is absent under its stripe's pattern (the data form only) draws row r of the reconstruction buffer — one atomic
+// per workgroup, as the segment counter is drawn — and gets the record of build_update_list's long form: ROW_ABSENT, the old row at r, and
+// DirectReadEntry r for the rebuild.  ROW_ABSENT also goes into slot_of[u], where the scatter finds it.  (Every lane of the set form reaches the barriers.)
+template <class Set>
+__device__ __forceinline__ void device_fill_body(const DeviceListArgs& a, const Set& s)
 {
+    constexpr bool SET = is_set_form<Set>;
     const uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= a.n) return;
-    const uint32_t slot = a.slot_of[u];
-    if (slot >= a.mps) return;  // FASTECC_WRITE_NONE, an index out of range, or one write too many for its stripe: no record (the status is set)
-    const uint64_t idx = a.writes[u];
+    uint32_t slot = 0xFFFFFFFFu;
+    if constexpr (SET) {
+        if (u < a.n) slot = a.slot_of[u];
+    } else {
+        if (u >= a.n) return;
+        slot = a.slot_of[u];
+        if (slot >= a.mps) return;  // FASTECC_WRITE_NONE, an index out of range, or one write too many for its stripe: no record (the status is set)
+    }
+    const bool record = slot < a.mps;
+    const uint64_t idx = !SET || record ? a.writes[u] : 0;
     const uint64_t b = stripe_of_index(a, idx);
-    const uint64_t off = a.with_data ? idx * a.S + a.col0 : u * a.W;  // the old row from old_base, as build_update_list's long form
-    uint32_t* wr = a.records + ((uint64_t)a.seg_of[b] * a.mps + slot) * SET_LIST_WORDS;
+    uint64_t off = a.with_data ? idx * a.S + a.col0 : u * a.W;  // the old row from old_base, as build_update_list's long form
+    uint32_t row = (uint32_t)u;
+    uint32_t seg = 0;
+    if constexpr (!SET) seg = a.seg_of[b];
+    if constexpr (SET) {
+        if (record) seg = a.seg_of[b];
+        __shared__ uint32_t wave_sum[4], block_base;
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        const uint32_t i = (uint32_t)(idx - b * a.K);
+        uint32_t q = 0, j = 0;
+        bool absent = false;
+        if (record && a.with_data) {  // (the parity form: only the parity flags matter)
+            q = s.pattern_seg[seg];
+            if (q < s.patterns) {
+                const uint32_t* lost = s.lost_data + (size_t)q * DIRECT_READ_LOST_ROW;  // (the padding matches no block: i < K < 0xFFFFFFF0)
+                for (uint32_t t = 0; t < DIRECT_READ_LOST_ROW; ++t)
+                    if (lost[t] == i) absent = true, j = t;
+            }
+        }
+        const uint64_t absents = __ballot(absent);
+        if (lane == 0) wave_sum[wave] = (uint32_t)__popcll(absents);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint32_t total = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+            block_base = total ? atomicAdd(s.absent, total) : 0u;
+        }
+        __syncthreads();
+        if (!record) return;
+        if (absent) {
+            uint32_t r = block_base + lanes_before(absents);
+            for (uint32_t w = 0; w < wave; ++w) r += wave_sum[w];
+            if (r >= s.cap) {
+                device_list_fail(a.status, FASTECC_E_NOMEM, u);  // (no row for it: the record below stays the present block's, and nothing reads it)
+            } else {
+                s.entries[r] = DirectReadEntry{b, q, i, j, 0};
+                off = s.recon_offset + (uint64_t)r * a.W;
+                row |= ROW_ABSENT;
+                a.slot_of[u] = slot | ROW_ABSENT;
+            }
+        }
+    }
+    uint32_t* wr = a.records + ((uint64_t)seg * a.mps + slot) * SET_LIST_WORDS;
     wr[0] = (uint32_t)((idx - b * a.K) << a.e);
-    wr[1] = (uint32_t)u;
+    wr[1] = row;
     wr[2] = (uint32_t)b;
     wr[3] = 0;  // (b < DEVICE_MAX)
     wr[LIST_WORDS] = (uint32_t)off;
     wr[LIST_WORDS + 1] = (uint32_t)(off >> 32);
 }
+__global__ __launch_bounds__(256) void device_fill_kernel(const DeviceListArgs a) { device_fill_body(a, NoSet{}); }
+__global__ __launch_bounds__(256) void device_fill_set_kernel(const DeviceListArgs a, const DeviceSetArgs s) { device_fill_body(a, s); }
 
-__global__ __launch_bounds__(256) void device_segments_kernel(const DeviceListArgs a)
+// The set form: the segment points at its stripe's row of the set's lost parity blocks (PatternSetView::lost_parity; row P loses nothing)
+template <class Set>
+__device__ __forceinline__ void device_segments_body(const DeviceListArgs& a, const Set& s)
 {
+    constexpr bool SET = is_set_form<Set>;
     __shared__ uint32_t wave_sum[5][4], block_base[5];
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -750,7 +844,7 @@ __global__ __launch_bounds__(256) void device_segments_kernel(const DeviceListAr
         for (uint32_t j = 1; j < len && live; ++j)
             for (uint32_t i = 0; i < j; ++i)
                 if (rec[i * SET_LIST_WORDS] == rec[j * SET_LIST_WORDS]) {  // two writes to one block
-                    device_list_fail(a.status, FASTECC_E_INVAL, rec[j * SET_LIST_WORDS + 1]);
+                    device_list_fail(a.status, FASTECC_E_INVAL, rec[j * SET_LIST_WORDS + 1] & (SET ? ~ROW_ABSENT : 0xFFFFFFFFu));
                     live = false;
                     break;
                 }
@@ -777,9 +871,12 @@ __global__ __launch_bounds__(256) void device_segments_kernel(const DeviceListAr
     uint32_t* seg = a.tables + off + (uint64_t)slot * (SET_SEG_HEAD + T);  // (slot < the class's bound: segments of class T > 1 hold more than T / 2 writes)
     seg[0] = g * a.mps;
     seg[1] = len;
-    seg[SEG_HEAD] = 0;  // the one row of UpdateState::d_lost_none
+    if constexpr (SET) seg[SEG_HEAD] = s.pattern_seg[g] * (uint32_t)SET_LOST_ROW;
+    else seg[SEG_HEAD] = 0;  // the one row of UpdateState::d_lost_none
     for (uint32_t r = 0; r < T; ++r) seg[SET_SEG_HEAD + r] = rec[(r < len ? r : 0) * SET_LIST_WORDS];
 }
+__global__ __launch_bounds__(256) void device_segments_kernel(const DeviceListArgs a) { device_segments_body(a, NoSet{}); }
+__global__ __launch_bounds__(256) void device_segments_set_kernel(const DeviceListArgs a, const DeviceSetArgs s) { device_segments_body(a, s); }
 
 // update_window_kernel for segment tables built on the device: the launch is sized from the host's upper bound on its class's segments, and the wave
 // reads the status and the class's real count (scalar loads) before anything else.  seg0: the launch's first segment in the class's table.
@@ -803,8 +900,9 @@ struct DeviceScatterArgs {
 };
 
 // update_window_scatter_kernel straight from the caller's list: wave (entry u, column slice)
-template <int V>
-__global__ __launch_bounds__(256) void update_device_scatter_kernel(const DeviceScatterArgs a)
+// present(row): false = the write's data block is absent and nothing is stored (the set form; wave-uniform)
+template <int V, class Present>
+__device__ __forceinline__ void update_device_scatter_wave(const DeviceScatterArgs& a, Present present)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
@@ -812,6 +910,7 @@ __global__ __launch_bounds__(256) void update_device_scatter_kernel(const Device
     const_u32_ptr st = as_constant(a.status);
     if ((st[0] | st[1]) != 0) return;
     const uint32_t u = wave / a.slices;
+    if (!present(a.row0 + u)) return;
     const_u32_ptr wr = as_constant(a.writes) + (size_t)u * 2;
     const uint64_t idx = ((uint64_t)wr[1] << 32) | wr[0];
     if (idx == WRITE_NONE) return;  // (every other entry is < count * K: the status is 0)
@@ -820,6 +919,17 @@ __global__ __launch_bounds__(256) void update_device_scatter_kernel(const Device
     uint32_t t[V];
     load_vec<V>(t, a.new_blocks + (uint64_t)(a.row0 + u) * a.width + col);
     store_vec<V>(a.data + idx * a.S + col, t);
+}
+template <int V>
+__global__ __launch_bounds__(256) void update_device_scatter_kernel(const DeviceScatterArgs a)
+{
+    update_device_scatter_wave<V>(a, [](uint32_t) { return true; });
+}
+// ... of the set form: device_fill_set_kernel has put ROW_ABSENT into slot_of[row] of a write whose data block is absent
+template <int V>
+__global__ __launch_bounds__(256) void update_device_set_scatter_kernel(const DeviceScatterArgs a, const uint32_t* slot_of)
+{
+    update_device_scatter_wave<V>(a, [&](uint32_t row) { return (as_constant(slot_of)[row] & ROW_ABSENT) == 0; });
 }
 
 }  // namespace
@@ -842,7 +952,11 @@ struct UpdateState {
     DeviceBuf<uint32_t> d_lost_none;
     // the device-list calls (DeviceListArgs): what the three build kernels write and the parity launches read, grown on demand (internal buffers)
     DeviceBuf<uint32_t> dl_cnt, dl_seg_of, dl_stripe_of, dl_slot_of, dl_records, dl_tables;
+    // their set forms (DeviceSetArgs): the pattern of each segment, and the DirectReadEntry of each row of d_recon, ENTRY_WORDS words each
+    DeviceBuf<uint32_t> dl_pattern_seg, dl_entries;
 };
+constexpr uint64_t ENTRY_WORDS = sizeof(DirectReadEntry) / 4;
+static_assert(sizeof(DirectReadEntry) % 8 == 0, "entries in a buffer of words: an allocation is aligned for them");
 
 void destroy_update_state(UpdateState* s) { delete s; }
 
@@ -1395,15 +1509,25 @@ int update_batch_set_impl(fastecc_ctx* c, void* data, void* parity, uint64_t cou
 // read the old rows).  The scratch grows on demand behind the host-side wait for the kernels that read it; a steady-state call allocates nothing,
 // copies nothing and waits for nothing.
 // The stages are update_batch_run's, with the three build kernels where that one calls build_update_list.
+// set != null (fastecc_update_batch_set_device / _update_parity_batch_set_device): stripe b under pattern set->pattern_of[b].  The
+// build kernels are their set forms; with a data pool the old rows of the absent written blocks are rebuilt into d_recon from entries made on the device,
+// after the build (the status is final) and before ANY parity launch (update_batch_run's hazard: the rebuild reads parity that those launches rewrite and
+// data that the scatter overwrites); the parity launches skip the stripes' absent parity blocks and the scatter the absent data blocks.  Steps 2 to 5 write
+// scratch alone; the parity launches and the scatter write the pool, each wave behind a look at the status.
+struct DeviceSetForm {
+    PatternSetView view;
+    const uint32_t* pattern_of;  // device
+    uint64_t max_absent;         // the caller's bound on the absent written data blocks
+};
 int update_device_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, uint64_t count, const uint64_t* writes, uint64_t n, uint32_t mps, const Window win,
-                      const uint32_t* old_blocks, const uint32_t* new_blocks, uint64_t* status, hipStream_t st)
+                      const uint32_t* old_blocks, const uint32_t* new_blocks, uint64_t* status, hipStream_t st, const DeviceSetForm* set = nullptr)
 {
     UpdateState* s = nullptr;
     RC_TRY(update_state(c, &s));
     const uint64_t S = c->S, K = c->K, M = c->Mu;
     PoolLanes l;
     RC_TRY(pool_lanes(c, win, (uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks, &l));
-    RC_TRY(lost_none_row(s));
+    if (!set) RC_TRY(lost_none_row(s));  // (the set forms never read it)
     // upper bounds: segments in all (one per touched stripe), and per admitted class
     const uint64_t segs_max = std::min(count, n);
     uint64_t bound[5] = {}, table_words = 0;
@@ -1420,8 +1544,26 @@ int update_device_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, uint64_t
     RC_TRY(grow_behind_wait(c, s->dl_slot_of, n));
     RC_TRY(grow_behind_wait(c, s->dl_records, segs_max * mps * SET_LIST_WORDS));  // (under 2^32 words: DEVICE_MAX x ROWS x SET_LIST_WORDS)
     RC_TRY(grow_behind_wait(c, s->dl_tables, table_words));
+    const uint64_t cap = set && data ? std::min(set->max_absent, n) : 0;  // rows of the reconstruction buffer
+    if (set) RC_TRY(grow_behind_wait(c, s->dl_pattern_seg, segs_max));
+    if (cap) {
+        if (direct_read_waves_per_entry(data, parity, nullptr, S, l.col0, l.W) > LAUNCH_WAVES) return FASTECC_E_UNSUPPORTED;
+        RC_TRY(grow_behind_wait(c, s->d_recon, cap * l.W));  // (cap <= DEVICE_MAX and W < 2^30: no wrap)
+        RC_TRY(grow_behind_wait(c, s->dl_entries, cap * ENTRY_WORDS));
+    }
     RC_TRY(update_table(c, s, st));
     return with_internal_buffers(c, st, [&]() -> int {
+        DeviceSetArgs sa{};
+        if (set) {
+            sa.pattern_of = set->pattern_of;
+            sa.lost_data = set->view.lost_data;
+            sa.pattern_seg = s->dl_pattern_seg;
+            sa.entries = (DirectReadEntry*)s->dl_entries.get();
+            sa.absent = s->dl_cnt + count + DEVICE_ABSENT;
+            sa.recon_offset = cap ? (uint64_t)(((intptr_t)s->d_recon.get() - (intptr_t)data) / 4) : 0;  // (both on word boundaries)
+            sa.patterns = (uint32_t)set->view.patterns;
+            sa.cap = (uint32_t)cap;
+        }
         la.writes = writes;
         la.status = (unsigned long long*)status;
         la.cnt = s->dl_cnt;
@@ -1442,20 +1584,30 @@ int update_device_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, uint64_t
         la.with_data = data ? 1u : 0u;
         la.small = la.limit <= 0xFFFFFFFFull ? 1u : 0u;
         {
-            ProfScope ps(c, st, "update_device_build", (count + DEVICE_COUNTERS) * 4 + n * (8 + 8 + SET_LIST_WORDS * 4));
+            ProfScope ps(c, st, set ? "update_set_device_build" : "update_device_build", (count + DEVICE_COUNTERS) * 4 + n * (8 + 8 + SET_LIST_WORDS * 4));
             HIP_TRY(hipMemsetAsync(s->dl_cnt, 0, (count + DEVICE_COUNTERS) * 4, st));
             HIP_TRY(hipMemsetAsync(status, 0, 8, st));
             const dim3 per_entry((unsigned)((n + 255) / 256)), per_segment((unsigned)((segs_max + 255) / 256));
-            hipLaunchKernelGGL(device_count_kernel, per_entry, dim3(256), 0, st, la);
-            hipLaunchKernelGGL(device_fill_kernel, per_entry, dim3(256), 0, st, la);
-            hipLaunchKernelGGL(device_segments_kernel, per_segment, dim3(256), 0, st, la);
+            if (set) {
+                hipLaunchKernelGGL(device_count_set_kernel, per_entry, dim3(256), 0, st, la, sa);
+                hipLaunchKernelGGL(device_fill_set_kernel, per_entry, dim3(256), 0, st, la, sa);
+                hipLaunchKernelGGL(device_segments_set_kernel, per_segment, dim3(256), 0, st, la, sa);
+            } else {
+                hipLaunchKernelGGL(device_count_kernel, per_entry, dim3(256), 0, st, la);
+                hipLaunchKernelGGL(device_fill_kernel, per_entry, dim3(256), 0, st, la);
+                hipLaunchKernelGGL(device_segments_kernel, per_segment, dim3(256), 0, st, la);
+            }
             HIP_TRY(hipGetLastError());
         }
+        if (cap) {  // (the bytes: a bound, every row taken and rebuilt from K rows — how many are absent is known on the device only)
+            ProfScope ps(c, st, "update_set_device_recon", cap * (K + 1) * l.W * 4);
+            RC_TRY(direct_run_read_device(set->view.passes, sa.entries, cap, data, parity, s->d_recon, S, l.col0, l.W, K * S, M * S, status, st));
+        }
         WindowArgs wa{};
-        pool_kernel_args(c, s, data, parity, old_blocks, new_blocks, l, s->dl_records, s->d_lost_none.get(), wa);
+        pool_kernel_args(c, s, data, parity, old_blocks, new_blocks, l, s->dl_records, set ? set->view.lost_parity : s->d_lost_none.get(), wa);
         BatchArgs& a = wa.s.b;
         {
-            ProfScope ps(c, st, "update_device", n * M * l.W * 8);  // (every entry a write)
+            ProfScope ps(c, st, set ? "update_set_device" : "update_device", n * M * l.W * 8);  // (every entry a write, every parity block present)
             for (int cl = 0; cl < 5; cl++) {
                 if (!bound[cl]) continue;
                 const int T = 1 << cl;
@@ -1473,19 +1625,30 @@ int update_device_run(fastecc_ctx* c, uint32_t* data, uint32_t* parity, uint64_t
         }
         if (!data) return FASTECC_OK;
         DeviceScatterArgs ca{data + l.col0, new_blocks, nullptr, (const uint32_t*)status, S, l.W, (uint32_t)l.slices, 0, 0};
-        ProfScope ps(c, st, "update_device_scatter", n * l.W * 8);
+        ProfScope ps(c, st, set ? "update_set_device_scatter" : "update_device_scatter", n * l.W * 8);
         return launch_split(n, l.slices, [&](uint64_t w0, uint32_t waves, dim3 grid) {
             ca.writes = (const uint32_t*)(writes + w0);
             ca.row0 = (uint32_t)w0;
             ca.waves = waves;
-            with_words<1>(l.V, [&](auto, auto v_c) { hipLaunchKernelGGL(update_device_scatter_kernel<decltype(v_c)::value>, grid, dim3(256), 0, st, ca); });
+            with_words<1>(l.V, [&](auto, auto v_c) {
+                constexpr int Vc = decltype(v_c)::value;
+                if (set) hipLaunchKernelGGL(update_device_set_scatter_kernel<Vc>, grid, dim3(256), 0, st, ca, (const uint32_t*)s->dl_slot_of.get());
+                else hipLaunchKernelGGL(update_device_scatter_kernel<Vc>, grid, dim3(256), 0, st, ca);
+            });
         });
     });
 }
 
 // What the host can decide without the list; then update_device_run.  col0_width: the window {col0_words, width_words}.
+// set_args != null: the set forms, {pattern_of, max_absent} — pattern_of against the pool as well, and the prepared set (none: FASTECC_E_INVAL, as
+// fastecc_update_batch_set says it, and before an empty list is accepted).
+struct DeviceSetCall {
+    const uint32_t* pattern_of;
+    uint64_t max_absent;
+};
 int update_batch_device_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint64_t* writes, uint64_t n_writes, uint32_t max_per_stripe,
-                             const uint64_t* col0_width, const void* old_blocks, const void* new_blocks, uint64_t* status, void* stream, bool with_data)
+                             const uint64_t* col0_width, const void* old_blocks, const void* new_blocks, uint64_t* status, void* stream, bool with_data,
+                             const DeviceSetCall* set_args = nullptr)
 {
     RC_TRY(update_batch_args(c, data, parity, count, writes, n_writes, old_blocks, new_blocks, with_data));
     if (!status || max_per_stripe < 1 || max_per_stripe > (uint32_t)ROWS) return FASTECC_E_INVAL;
@@ -1499,15 +1662,47 @@ int update_batch_device_impl(fastecc_ctx* c, void* data, void* parity, uint64_t 
         ranges_overlap(writes, n_writes * 8, new_blocks, rows_bytes) || ranges_overlap(writes, n_writes * 8, old_blocks, rows_bytes) ||
         ranges_overlap(status, 8, new_blocks, rows_bytes) || ranges_overlap(status, 8, old_blocks, rows_bytes) || ranges_overlap(status, 8, writes, n_writes * 8))
         return FASTECC_E_INVAL;
+    if (set_args && rows_overlap_pool(c, data, parity, count, with_data, set_args->pattern_of, count, 4)) return FASTECC_E_INVAL;
     DeviceGuard dg(c->device);
     if (!dg.ok) return FASTECC_E_DEVICE;
     CallLock lk(c->mu);
+    DeviceSetForm set{};
+    if (set_args) {
+        if (!pattern_set_view(c, &set.view)) return FASTECC_E_INVAL;  // fastecc_decode_prepare_set first
+        set.pattern_of = set_args->pattern_of;
+        set.max_absent = set_args->max_absent;
+    }
     if (n_writes == 0) {
         HIP_TRY(hipMemsetAsync(status, 0, 8, (hipStream_t)stream));
         return FASTECC_OK;
     }
     return update_device_run(c, with_data ? (uint32_t*)data : nullptr, (uint32_t*)parity, count, writes, n_writes, max_per_stripe, win,
-                             (const uint32_t*)old_blocks, (const uint32_t*)new_blocks, status, (hipStream_t)stream);
+                             (const uint32_t*)old_blocks, (const uint32_t*)new_blocks, status, (hipStream_t)stream, set_args ? &set : nullptr);
+}
+
+// The set forms: first what can be refused without reading the context — the pointers, the promise, the bounds of 2^24 and pattern_of against the
+// list, the status word and the rows — then everything update_batch_device_impl refuses.
+int update_batch_set_device_impl(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, const uint64_t* writes, uint64_t n_writes,
+                                 uint32_t max_per_stripe, uint64_t max_absent, const uint64_t* col0_width, const void* old_blocks, const void* new_blocks,
+                                 uint64_t* status, void* stream, bool with_data)
+{
+    if (!c || count == 0 || !pattern_of || !status) return FASTECC_E_INVAL;
+    if (n_writes > 0 && (!parity || !writes || !new_blocks || (with_data && !data))) return FASTECC_E_INVAL;
+    if (((uintptr_t)pattern_of & 3u) != 0 || (((uintptr_t)writes | (uintptr_t)status) & 7u) != 0) return FASTECC_E_INVAL;
+    if ((((uintptr_t)data | (uintptr_t)parity | (uintptr_t)old_blocks | (uintptr_t)new_blocks) & 3u) != 0) return FASTECC_E_INVAL;
+    if (max_per_stripe < 1 || max_per_stripe > (uint32_t)ROWS || col0_width[1] == 0) return FASTECC_E_INVAL;
+    if (count > DEVICE_MAX || n_writes > DEVICE_MAX) return FASTECC_E_UNSUPPORTED;
+    // (no product wraps: count and n_writes <= 2^24; a width that no block of under 4 GiB holds is refused with the window)
+    const uint64_t rows_bytes = col0_width[1] < (1ull << 30) ? n_writes * col0_width[1] * 4 : 0, pattern_bytes = count * 4, writes_bytes = n_writes * 8;
+    if (ranges_overlap(pattern_of, pattern_bytes, writes, writes_bytes) || ranges_overlap(pattern_of, pattern_bytes, status, 8) ||
+        ranges_overlap(pattern_of, pattern_bytes, new_blocks, rows_bytes) || ranges_overlap(pattern_of, pattern_bytes, old_blocks, rows_bytes) ||
+        ranges_overlap(status, 8, writes, writes_bytes) || ranges_overlap(writes, writes_bytes, new_blocks, rows_bytes) ||
+        ranges_overlap(writes, writes_bytes, old_blocks, rows_bytes) || ranges_overlap(status, 8, new_blocks, rows_bytes) ||
+        ranges_overlap(status, 8, old_blocks, rows_bytes))
+        return FASTECC_E_INVAL;
+    const DeviceSetCall set_args{pattern_of, max_absent};
+    return update_batch_device_impl(c, data, parity, count, writes, n_writes, max_per_stripe, col0_width, old_blocks, new_blocks, status, stream, with_data,
+                                    &set_args);
 }
 
 }  // namespace
@@ -1611,6 +1806,28 @@ int fastecc_update_parity_batch_device(fastecc_ctx* c, void* parity, uint64_t co
     const uint64_t win[2] = {col0_words, width_words};
     return guarded([&]() -> int {
         return update_batch_device_impl(c, nullptr, parity, count, writes, n_writes, max_per_stripe, win, old_blocks, new_blocks, status, stream, false);
+    });
+}
+
+int fastecc_update_batch_set_device(fastecc_ctx* c, void* data, void* parity, uint64_t count, const uint32_t* pattern_of, const uint64_t* writes, uint64_t n_writes,
+                                    uint32_t max_per_stripe, uint64_t max_absent, uint64_t col0_words, uint64_t width_words, const void* new_blocks,
+                                    uint64_t* status, void* stream)
+{
+    const uint64_t win[2] = {col0_words, width_words};
+    return guarded([&]() -> int {
+        return update_batch_set_device_impl(c, data, parity, count, pattern_of, writes, n_writes, max_per_stripe, max_absent, win, nullptr, new_blocks, status,
+                                            stream, true);
+    });
+}
+
+int fastecc_update_parity_batch_set_device(fastecc_ctx* c, void* parity, uint64_t count, const uint32_t* pattern_of, const uint64_t* writes, uint64_t n_writes,
+                                           uint32_t max_per_stripe, uint64_t col0_words, uint64_t width_words, const void* old_blocks, const void* new_blocks,
+                                           uint64_t* status, void* stream)
+{
+    const uint64_t win[2] = {col0_words, width_words};
+    return guarded([&]() -> int {
+        return update_batch_set_device_impl(c, nullptr, parity, count, pattern_of, writes, n_writes, max_per_stripe, 0, win, old_blocks, new_blocks, status,
+                                            stream, false);
     });
 }
 

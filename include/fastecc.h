@@ -34,7 +34,9 @@
 extern "C" {
 #endif
 
-#define FASTECC_VERSION 460 /* 0.4.6: fastecc_read_batch_set_device, fastecc_read_batch_device (degraded reads from a request list in device memory) */
+#define FASTECC_VERSION 470 /* 0.4.7: fastecc_update_batch_set_device, fastecc_update_parity_batch_set_device (degraded writes from a write list in device memory) */
+/* The version before, for code that tests for it: "#define FASTECC_VERSION 460" was 0.4.6, fastecc_read_batch_set_device and fastecc_read_batch_device
+ * (degraded reads from a request list in device memory). */
 
 enum {
     FASTECC_OK = 0,
@@ -880,7 +882,8 @@ int fastecc_update_parity_batch_set_window(fastecc_ctx *ctx, void *parity, uint6
  * Streams: in steady state — the same or a smaller n_writes, count and max_per_stripe than an earlier call on the context — a call makes no
  * host-device copy and no allocation, waits on no event or stream and touches no pinned memory: it resets its counters and *status
  * (hipMemsetAsync), launches and returns.  The first call and a growing call allocate the context's scratch and may wait, as
- * fastecc_update_batch does.  hipGraph capture is not claimed.  There are no _set (degraded) forms of these two calls.
+ * fastecc_update_batch does.  hipGraph capture is not claimed.  The _set (degraded) forms of these two calls are
+ * fastecc_update_batch_set_device / fastecc_update_parity_batch_set_device, below.
  * Method: the segment tables of update_window_kernel are built by three kernels without a sort — a slot per write from a
  * per-stripe counter, the records, the segments by length class — and the order of a stripe's writes inside its segment, which depends on atomic
  * arrival, has no influence on the result: the sums are exact 96-bit integers reduced once, so any permutation of the list leaves the same bytes.
@@ -892,6 +895,48 @@ int fastecc_update_batch_device(fastecc_ctx *ctx, void *data, void *parity, uint
 int fastecc_update_parity_batch_device(fastecc_ctx *ctx, void *parity, uint64_t count, const uint64_t *writes /* device */, uint64_t n_writes,
                                        uint32_t max_per_stripe, uint64_t col0_words, uint64_t width_words, const void *old_blocks /* may be NULL: zero */,
                                        const void *new_blocks, uint64_t *status /* device */, void *stream);
+/*
+ * Degraded pool writes from a write list in DEVICE memory: fastecc_update_batch_set_window / fastecc_update_parity_batch_set_window with `writes`
+ * AND `pattern_of` produced on the GPU, so that a caller of the two calls above stays on the device when a device of the pool fails.  Stripe b is
+ * under pattern pattern_of[b] of the set of fastecc_decode_prepare_set (or FASTECC_PATTERN_NONE: a whole stripe).
+ * Result: when *status == 0, every word of the pool is bit-identical to what fastecc_update_batch_set_window /
+ * fastecc_update_parity_batch_set_window leave for the same list with its FASTECC_WRITE_NONE entries removed and the rows renumbered accordingly:
+ * present data blocks of a touched stripe hold X' in the window, present parity blocks what fastecc_encode gives for X' in the window; absent blocks,
+ * untouched stripes and words outside the window are neither read for their content nor written.  (0, block_bytes / 4) is the whole block.
+ *   writes, max_per_stripe, col0_words, width_words, the rows and FASTECC_WRITE_NONE : exactly those of fastecc_update_batch_device, with its bounds of
+ *             2^24 stripes and 2^24 entries.
+ *   pattern_of : `count` entries of device memory, 4-byte aligned, as in fastecc_read_batch_set_device.  The host never dereferences writes,
+ *             pattern_of or status: they are read when the call's kernels run, in stream order.  Entries of pattern_of for stripes that no write
+ *             names are never looked at and may hold anything.
+ *   max_absent : (the data form) the caller's bound on how many written data blocks are absent under their stripe's pattern.  It sizes the
+ *             reconstruction buffer — min(max_absent, n_writes) rows of width_words words, owned by the context and grown on demand — and the launch
+ *             that rebuilds the old rows.  0 is allowed and means the caller promises that none is absent; n_writes is always safe.  The host cannot
+ *             know the number, and a buffer of n_writes blocks is 64 GiB at the call's own limits: the number is a promise, like max_per_stripe.
+ *   status  : 0, or (uint32_t)code << 32 | row; the first compare-and-swap from 0 wins.  FASTECC_E_INVAL: an index >= count*k, two writes to one
+ *             block, or a pattern_of[b] of a touched stripe that is neither FASTECC_PATTERN_NONE nor below the set's size.  FASTECC_E_UNSUPPORTED:
+ *             a stripe with more than max_per_stripe writes.  FASTECC_E_NOMEM: more absent written blocks than max_absent; the row is one write
+ *             that got no slot.  All or nothing: a non-zero status means that no word of the pool has been written by the call.
+ * The return value covers what the host can decide without the lists, before any device work and with nothing written: everything
+ * fastecc_update_batch_device refuses, with its codes; everything fastecc_update_batch_set_window refuses without its list (no set prepared is
+ * FASTECC_E_INVAL; GF((2^61-1)^2), sharded contexts and a set "row_pitch_words" are FASTECC_E_UNSUPPORTED); FASTECC_E_INVAL for a pattern_of that
+ * is null, not 4-byte aligned, or overlaps the pool, the rows, writes or status; FASTECC_E_NOMEM if the reconstruction buffer does not fit.
+ * n_writes == 0 is FASTECC_OK after those checks, with *status set to 0 on the stream.
+ * Streams: in steady state — the same or a smaller n_writes, count, max_per_stripe and max_absent than an earlier call on the context, and the same
+ * prepared set — a call makes no host-device copy and no allocation, waits on no event or stream and uses no pinned memory.
+ * fastecc_decode_prepare_set waits for a call in flight before it swaps the set's tables.  hipGraph capture is not claimed, and there are no rounds
+ * beyond 16 writes per stripe.
+ * Method: the three build kernels of the calls above in their set forms — the lane that opens a stripe's segment reads and
+ * checks pattern_of[b], a write to an absent data block draws a row of the reconstruction buffer from one counter — then the degraded read's kernel
+ * over those rows, the same parity launches with the set's table of lost parity blocks, and a scatter that leaves absent blocks alone.  Only the last
+ * two write the pool, each wave behind a look at the status word.
+ */
+int fastecc_update_batch_set_device(fastecc_ctx *ctx, void *data, void *parity, uint64_t count, const uint32_t *pattern_of /* device, count entries */,
+                                    const uint64_t *writes /* device */, uint64_t n_writes, uint32_t max_per_stripe, uint64_t max_absent,
+                                    uint64_t col0_words, uint64_t width_words, const void *new_blocks, uint64_t *status /* device */, void *stream);
+int fastecc_update_parity_batch_set_device(fastecc_ctx *ctx, void *parity, uint64_t count, const uint32_t *pattern_of /* device */,
+                                           const uint64_t *writes /* device */, uint64_t n_writes, uint32_t max_per_stripe, uint64_t col0_words,
+                                           uint64_t width_words, const void *old_blocks /* may be NULL: zero */, const void *new_blocks,
+                                           uint64_t *status /* device */, void *stream);
 /* Host only, no device: the code's generator-matrix entry L_i(y_q) for data block i and parity block q of the (n,k) code that
  * fastecc_create_ex(n, k, ..., flags) builds over GF(0xFFF00001), plain form in [0,p): parity block q = sum_i L_i(y_q) data block i.
  * FASTECC_E_INVAL for a null out, an index out of range or unknown flags; FASTECC_E_UNSUPPORTED for a code fastecc_create_ex refuses. */
